@@ -14,7 +14,9 @@ maxPathLength 5, fixed RNG seed, scene resident in HBM.  Two ways to run N GPUs,
                 (RaylibAMD_RenderDevice), one RCCL gather per frame brings them to rank 0.  --gpus must equal WORLD_SIZE.
 
 Strong scaling: the total work is fixed.  Outside the timed region the frame is checked against windows rendered by the reference
-build (tests/golden/bench_windows.npz).  Rank 0 prints ONE JSON line; DESIGN.md section 5 describes every field.
+build (tests/golden/bench_windows.npz).  Rank 0 prints ONE JSON line; DESIGN.md section 5 describes every field.  The line leaves out
+prose definitions and replayed counter detail (result_line); `--details FILE` writes the whole object.  `--dump-outputs DIR` writes the
+frame of the last timed step as DIR/image.npy, so that two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -125,6 +127,68 @@ def golden_windows(workload_name, frame_hw):
     n = len(pos) * 256
     return ("%d / %d pixels of %d reference-rendered windows bit-identical" % (n - bad, n, len(pos))) if bad == 0 else \
            ("MISMATCH: %d of %d pixels of the reference-rendered windows differ" % (bad, n))
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: the arrays the timed path handed its caller in the last timed step, one DIR/<name>.npy each (float32), so that two
+    builds run with the same arguments -- the same scene, camera and seed -- can be compared output for output."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise SystemExit("--dump-outputs: %d bytes exceed the 64 MB bound" % total)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
+ROOFLINE_SUMMARY = ("bound", "achieved", "peak", "unit", "frac", "resource", "kernel", "avg_launch_ms", "launches", "algorithmic")
+
+
+def result_line(out):
+    """The printed line: `out` without its prose definitions, the replayed VALU class counts and dynamic mix (profiles/pmc_traffic.json holds
+    them) and, for the further workloads, without the roofline beyond its summary.  With three further workloads the whole object passed
+    20 kB, more than a reader of the run's output keeps; the whole object goes to --details FILE."""
+    def roof(r, summary):
+        if not r:
+            return r
+        r = {k: v for k, v in r.items() if k in ROOFLINE_SUMMARY} if summary else dict(r)
+        if r.get("algorithmic"):
+            r["algorithmic"] = {k: v for k, v in r["algorithmic"].items() if k != "definition"}
+        if r.get("valu"):
+            r["valu"] = {k: v for k, v in r["valu"].items() if k not in ("class_counts", "dynamic_mix")}
+        if r.get("vmem_requests"):
+            r["vmem_requests"] = {k: v for k, v in r["vmem_requests"].items() if k != "definition"}
+        return r
+
+    def without(d, *keys):
+        return {k: v for k, v in d.items() if k not in keys} if isinstance(d, dict) else d
+
+    line = dict(out)
+    cfg = line["config"] = dict(line["config"])
+    if "work" in cfg:
+        cfg["work"] = without(cfg["work"], "definition")
+    if "n1_reference" in cfg:
+        cfg["n1_reference"] = without(cfg["n1_reference"], "note")
+    line["roofline"] = roof(line["roofline"], False)
+    for key in ("extra", "extra_interior", "extra_textured"):
+        if key in line:
+            e = line[key] = dict(line[key])
+            e["work"] = without(e["work"], "definition")
+            e["roofline"] = roof(e["roofline"], True)
+    if "cpu_baseline" in line:
+        line["cpu_baseline"] = without(line["cpu_baseline"], "sample")
+    return line
+
+
+def emit(out, details):
+    """Rank 0's output: the whole object to --details FILE (if given), the result line to stdout."""
+    if details:
+        with open(details, "w") as f:
+            json.dump(out, f)
+            f.write("\n")
+    print(json.dumps(result_line(out)))
+    sys.stdout.flush()
 
 
 def step_times(ts):
@@ -350,7 +414,8 @@ def library_run(lib, binding, scenes, workload_name, steps, warmup, n_gpus, rank
     # ---- untimed from here on -------------------------------------------------------------------------------------------------
     host = np.zeros(w * h * 3, np.float32)
     lib.Raylib_DumpImageData(image, host.ctypes.data_as(C.POINTER(C.c_float)))
-    frame_check = golden_windows(workload_name, host.reshape(h, w, 3))
+    last_frame = host.reshape(h, w, 3).copy()        # the last timed step's frame, as the caller of Raylib_Render reads it back
+    frame_check = golden_windows(workload_name, last_frame)
     # what a front-end observes: the render plus the read-back of the frame (the reference's Raylib_Render returns with the pixels
     # in host memory, render/renderer.cc:292-356; here the first reader pays the 33 MB copy)
     k2 = max(1, min(steps, 10))
@@ -387,7 +452,7 @@ def library_run(lib, binding, scenes, workload_name, steps, warmup, n_gpus, rank
     lib.Raylib_DestroyImage(image)
     ses.close()
     return dict(acc=acc, elapsed=elapsed, per_step=per_step, frame_check=frame_check, boundary=boundary, tree_walk=tree_walk,
-                ntris=ntris, last_stats=last, wl=wl, cam=cam)
+                ntris=ntris, last_stats=last, wl=wl, cam=cam, frame=last_frame)
 
 
 def main():
@@ -398,6 +463,10 @@ def main():
     ap.add_argument("--workload", default=HEADLINE, choices=list(WORKLOADS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the second workload (a memory-bound megakernel) reported under \"extra\"")
+    ap.add_argument("--details", metavar="FILE", default=None,
+                    help="write the whole result object to FILE: the printed line leaves out prose definitions and replayed counter detail")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame the last timed step produced (the headline workload's) as DIR/image.npy, float32")
     args = ap.parse_args()
     if args.gpus < 1 or args.steps < 1:
         raise SystemExit("--gpus and --steps must be positive")
@@ -439,6 +508,8 @@ def main():
     if ranks != n:
         raise SystemExit("asked for %d GPU(s) but the library rendered on %d rank(s)" % (n, ranks))
     acc, elapsed, wl = r["acc"], r["elapsed"], r["wl"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"image": r["frame"]})
     out = {
         "metric": "Mrays/sec (primary+secondary) + frame time, Cornell Box 1080p 64spp",
         "value": acc["rays"] / elapsed / 1e6,
@@ -487,8 +558,7 @@ def main():
                         "roofline": roofline_block(name, ea, 1, build_id, e["tree_walk"])}
     if ranks == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(wl, r["cam"], (acc["rays"] + acc["culled_rays"]) / max(1.0, acc["samples"] + acc["culled_samples"]), elapsed / args.steps)
-    print(json.dumps(out))
-    sys.stdout.flush()
+    emit(out, args.details)
 
 
 def process_mode(args, rank, local_rank, world, torch, binding, scenes):
@@ -616,6 +686,10 @@ def process_mode(args, rank, local_rank, world, torch, binding, scenes):
         else:
             os.environ["RAYLIB_LEAF_LIST"] = keep
     frame_check = None
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's assembled frame as the caller's device buffer holds it (RGBA, row-major; the re-render above wrote a send buffer, not this)
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, {"image": frame.reshape(h, w, 4).cpu().numpy()})
     if rank == 0:
         # outside the timed region: the frame assembled from the ranks' cells against this rank's own render of the whole frame
         torch.cuda.synchronize()
@@ -661,8 +735,7 @@ def process_mode(args, rank, local_rank, world, torch, binding, scenes):
         }
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(wl, cam, total_frame_rays / max(1.0, total_frame_samples), elapsed / args.steps)
-        print(json.dumps(out))
-        sys.stdout.flush()
+        emit(out, args.details)
     ses.close()
     dist.barrier()
     dist.destroy_process_group()

@@ -370,6 +370,7 @@ def test_bench_default_run_times_the_boundary_and_checks_the_frame():
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stderr[-2000:]
+    assert len(lines[0]) < 10000, "the result line must stay short enough to be read from the end of the output (%d bytes)" % len(lines[0])
     d = json.loads(lines[0])
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["config"]["boundary"]["timed_entry"] == "Raylib_Render"
     assert d["config"]["frame_check"].endswith("reference-rendered windows bit-identical") and "MISMATCH" not in d["config"]["frame_check"]
@@ -418,6 +419,39 @@ def test_bench_default_run_times_the_boundary_and_checks_the_frame():
     assert et["workload"] == "breakfast_textured_interior_300k_1080p_128spp" and et["value"] > 0 and et["scene_triangles"] == e["scene_triangles"]
     assert et["frame_check"].endswith("reference-rendered windows bit-identical") and et["roofline"]["kernel"] == "k_trace_pool"
     assert et["work"]["cells_culled"] == 0 and et["work"]["texel_fetches_per_ray"] > 0.5
+
+
+def test_bench_dump_outputs_writes_the_last_timed_frame(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the frame of the last timed step as DIR/image.npy (float32, what Raylib_Render's caller reads
+    back): the same bits whatever --steps is, the reference-rendered windows inside it, and `--steps` is the number of timed steps.
+    `--details FILE` holds the whole result object the printed line is cut from."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RAYLIB_POOL", "RAYLIB_LIB", "BENCH_SHARE_GPU", "WORLD_SIZE", "RANK", "LOCAL_RANK", "RAYLIB_NUM_GPUS", "RAYLIB_GPU_MAP", "RAYLIB_JOB_HEADS"):
+        env.pop(k, None)
+    frames = []
+    for steps in (2, 3):
+        d_out = tmp_path / ("s%d" % steps)
+        details = tmp_path / ("details%d.json" % steps)
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline", "--no-extra",
+                              "--dump-outputs", str(d_out), "--details", str(details)], env=env, capture_output=True, text=True, timeout=300)
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == steps and d["ms_per_step_spread"]["n"] == steps and d["ms_per_step"] > 0
+        # --details: the whole object, of which the printed line is a part
+        full = json.load(open(str(details)))
+        assert full["value"] == d["value"] and full["ms_per_step"] == d["ms_per_step"] and full["config"]["build_id"] == d["config"]["build_id"]
+        assert "definition" in full["config"]["work"] and "definition" not in d["config"]["work"]
+        assert sorted(os.listdir(str(d_out))) == ["image.npy"]
+        img = np.load(str(d_out / "image.npy"))
+        assert img.dtype == np.float32 and img.shape == (1080, 1920, 3) and np.isfinite(img).all()
+        frames.append(img)
+    assert np.array_equal(frames[0].view(np.uint32), frames[1].view(np.uint32))
+    g = np.load(os.path.join(root, "tests", "golden", "bench_windows.npz"))
+    for (x0, y0), want in zip(g["cornell_1080p_64spp_pos"], g["cornell_1080p_64spp_px"]):
+        assert np.array_equal(frames[0][y0:y0 + 16, x0:x0 + 16].view(np.uint32), np.ascontiguousarray(want[..., :3]).view(np.uint32)), (x0, y0)
 
 
 def test_bench_library_mode_runs_n_ranks_behind_raylib_render_or_refuses():
