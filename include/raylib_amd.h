@@ -19,6 +19,9 @@
  *                  entry per rank; a device may be named more than once, which puts several ranks on it: tests) -- and gathers
  *                  the cells on the first device.  The frame is bit-identical to the one-device frame.  Default 1.
  *   RAYLIB_GATHER  rccl (default: grouped ncclSend / ncclRecv, librccl loaded at run time) | peer (hipMemcpyPeerAsync pushes)
+ *   RAYLIB_DENOISER  1: the denoiser switch starts on (RaylibAMD_EnableDenoiser), so that unmodified front-ends get
+ *                  Raylib_IsDenoiserSupported() == 1 and a working Raylib_Denoise.  Default 0: both return 0, as in the reference
+ *                  builds without OIDN.
  */
 #ifndef RAYLIB_AMD_H
 #define RAYLIB_AMD_H
@@ -210,6 +213,29 @@ RAYLIB_API int32_t RaylibAMD_ImageSize(ImageHandle image, uint32_t* outWidth, ui
 /* Replace a material's texture by an image handle (slot: 0 albedo, 1 normal, 2 roughness,
  * 3 metallic, 4 emissive) -- the OBJ loader does the same from map_* statements. */
 RAYLIB_API int32_t RaylibAMD_OBJModelSetTexture(OBJModelHandle obj, const char* materialName, int32_t slot, ImageHandle image);
+
+/* ---- denoiser: an edge-avoiding a-trous wavelet filter guided by the Albedo and MicrosurfaceNormal AOVs (csrc/rl_denoise.hip
+ *      defines it exactly).  Inputs are RGBA float images of one size; their alpha is ignored; the output's alpha is 1. ---- */
+typedef struct RaylibAMDDenoiseParams {
+	int32_t iterations;       /* K, 1 .. 8: filter steps 1, 2, 4, ... 2^(K-1) pixels apart */
+	float   sigmaColor;       /* tolerance of the colour distance (halved per step); each sigma in [1e-3, 1e3] */
+	float   sigmaNormal;      /* ... of the normal distance */
+	float   sigmaAlbedo;      /* ... of the albedo distance */
+} RaylibAMDDenoiseParams;
+/* NULL params = defaults. albedo / normal may be 0. Returns 1 on success; 0 on a null main / out, a guide whose size differs from
+ * main's, params out of range, or no device. On 0, out is untouched.  out is reallocated to main's size and may be main; the result
+ * stays on the device as after Raylib_Render (Raylib_PostProcess / Raylib_DumpImageData work on it there). */
+RAYLIB_API int32_t RaylibAMD_Denoise(ImageHandle main, int32_t bHDR, ImageHandle albedo, ImageHandle normal,
+                                     ImageHandle out, const RaylibAMDDenoiseParams* params);
+/* The same filter on the host, on caller arrays of W*H*4 floats: the oracle of the device path, no device needed.
+ * Same return convention (outRGBA may be colorRGBA). */
+RAYLIB_API int32_t RaylibAMD_DenoiseHost(uint32_t width, uint32_t height, const float* colorRGBA, int32_t bHDR,
+                                         const float* albedoRGBA, const float* normalRGBA,
+                                         const RaylibAMDDenoiseParams* params, float* outRGBA);
+/* Process-wide switch, default off (the env var RAYLIB_DENOISER=1 turns it on for unmodified front-ends).
+ * On: Raylib_IsDenoiserSupported() returns RaylibAMD_DeviceAvailable(), and Raylib_Denoise(m, hdr, a, n, o)
+ * = RaylibAMD_Denoise(m, hdr, a, n, o, NULL). Off: both keep today's behaviour exactly (return 0). */
+RAYLIB_API void    RaylibAMD_EnableDenoiser(int32_t enable);
 
 #ifdef __cplusplus
 }

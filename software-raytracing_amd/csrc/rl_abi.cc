@@ -40,6 +40,22 @@ std::mutex g_stateMu;
 uint64_t g_seed = 1;
 bool g_seedSet = false;
 RaylibAMDStats g_lastStats;
+int g_denoiser = -1;   // RaylibAMD_EnableDenoiser; -1: not set yet, RAYLIB_DENOISER decides at first use
+
+bool DenoiserEnabled()
+{
+	std::lock_guard<std::mutex> lk(g_stateMu);
+	if (g_denoiser < 0) { const char* e = getenv("RAYLIB_DENOISER"); g_denoiser = (e && e[0] == '1' && e[1] == 0) ? 1 : 0; }
+	return g_denoiser == 1;
+}
+
+// Chosen with the Cornell quality test (tests/test_gpu_denoise.py; DESIGN.md, "Denoiser").
+const RaylibAMDDenoiseParams kDenoiseDefaults = { 5, 2.0f, 0.3f, 0.05f };
+bool DenoiseParamsValid(const RaylibAMDDenoiseParams& P)
+{
+	auto ok = [](float s) { return s >= 1e-3f && s <= 1e3f; };   // (also false for NaN): 1 / s^2 and 4^7 / s^2 stay finite and nonzero
+	return P.iterations >= 1 && P.iterations <= 8 && ok(P.sigmaColor) && ok(P.sigmaNormal) && ok(P.sigmaAlbedo);
+}
 
 uint64_t CurrentSeed()
 {
@@ -280,9 +296,12 @@ void Raylib_Render(const RendererSettings* settings, SceneHandle scene, CameraHa
 	else { img->devValid = (dev != nullptr); img->hostStale = (dev != nullptr); img->Touch(); }
 }
 
-int32_t Raylib_Denoise(ImageHandle, int32_t, ImageHandle, ImageHandle, ImageHandle)
+int32_t Raylib_Denoise(ImageHandle mainImage, int32_t bHDR, ImageHandle albedo, ImageHandle normal, ImageHandle out)
 {
-	return 0;   // reference render/renderer.cc:358-370 returns false when OIDN is not integrated (every non-Windows build)
+	// reference render/renderer.cc:358-370 returns false when OIDN is not integrated (every non-Windows build); here the same unless the
+	// denoiser switch is on (RaylibAMD_EnableDenoiser, RAYLIB_DENOISER=1), and then the a-trous filter of csrc/rl_denoise.hip with its defaults
+	if (!DenoiserEnabled()) return 0;
+	return RaylibAMD_Denoise(mainImage, bHDR, albedo, normal, out, nullptr);
 }
 
 void Raylib_PostProcess(ImageHandle h)
@@ -296,7 +315,7 @@ void Raylib_PostProcess(ImageHandle h)
 	}
 }
 
-int32_t Raylib_IsDenoiserSupported(void) { return 0; }
+int32_t Raylib_IsDenoiserSupported(void) { return DenoiserEnabled() ? RaylibAMD_DeviceAvailable() : 0; }
 
 // ---------------------------------------------------------------------------
 // reference raylib.cc:298-331
@@ -334,6 +353,32 @@ int32_t RaylibAMD_DeviceAvailable(void) { return DeviceAvailable() ? 1 : 0; }
 #define RL_BUILD_ID "unknown"
 #endif
 const char* RaylibAMD_BuildId(void) { return RL_BUILD_ID; }
+
+void RaylibAMD_EnableDenoiser(int32_t enable) { std::lock_guard<std::mutex> lk(g_stateMu); g_denoiser = enable ? 1 : 0; }
+
+int32_t RaylibAMD_Denoise(ImageHandle mainImage, int32_t bHDR, ImageHandle albedo, ImageHandle normal, ImageHandle out, const RaylibAMDDenoiseParams* params)
+{
+	Image* m = (Image*)mainImage; Image* a = (Image*)albedo; Image* n = (Image*)normal; Image* o = (Image*)out;
+	const RaylibAMDDenoiseParams& P = params ? *params : kDenoiseDefaults;
+	if (!m || !o) { Log("RaylibAMD_Denoise: null main or output image"); return 0; }
+	for (Image* g : { a, n })
+		if (g && (g->width != m->width || g->height != m->height)) { Log("RaylibAMD_Denoise: a guide's size differs from the main image's"); return 0; }
+	if (!DenoiseParamsValid(P)) { Log("RaylibAMD_Denoise: parameters out of range"); return 0; }
+	if (!DeviceAvailable()) return 0;
+	// a whole-frame render over several ranks returns with the frame in flight: wait for it, and keep its numbers for RaylibAMD_GetLastStats
+	RaylibAMDStats late;
+	if (DeviceDrain(&late)) { std::lock_guard<std::mutex> lk(g_stateMu); g_lastStats = late; }
+	return DeviceDenoise(*m, bHDR != 0, a, n, *o, P) ? 1 : 0;
+}
+
+int32_t RaylibAMD_DenoiseHost(uint32_t width, uint32_t height, const float* colorRGBA, int32_t bHDR, const float* albedoRGBA, const float* normalRGBA,
+                              const RaylibAMDDenoiseParams* params, float* outRGBA)
+{
+	const RaylibAMDDenoiseParams& P = params ? *params : kDenoiseDefaults;
+	if (!colorRGBA || !outRGBA || !DenoiseParamsValid(P)) return 0;
+	DenoiseHost(width, height, colorRGBA, bHDR != 0, albedoRGBA, normalRGBA, P, outRGBA);
+	return 1;
+}
 
 uint32_t RaylibAMD_NumCells(uint32_t w, uint32_t h) { return ((w + 7) / 8) * ((h + 7) / 8); }
 uint64_t RaylibAMD_CellBufferFloats(uint32_t w, uint32_t h, uint32_t cellFirst, uint32_t cellStride)

@@ -244,4 +244,11 @@ bool DeviceVerifyExactMath(int which, uint64_t* outMismatches, uint64_t* outFirs
 bool DeviceEvalHook(int kind, Scene* sc, const DCamera* cam, int a, int b, const float* in, int n, uint64_t seed, float* out);
 void DeviceReleaseScene(DeviceScene* dev);
 
+// denoiser (rl_denoise.hip): the a-trous filter on the device and its host restatement; params checked by the caller (rl_abi.cc)
+void DenoiseHost(uint32_t width, uint32_t height, const float* color, bool hdr, const float* albedo, const float* normal,
+                 const RaylibAMDDenoiseParams& params, float* out);
+// main, albedo and normal are uploaded first when their pixels live only on the host; out (which may be any of them) is reallocated
+// to main's size and left on the device (devValid, hostStale).  The caller has waited for frames in flight (DeviceDrain).
+bool DeviceDenoise(Image& main, bool hdr, Image* albedo, Image* normal, Image& out, const RaylibAMDDenoiseParams& params);
+
 } // namespace rl

@@ -23,6 +23,11 @@ class RendererSettings(C.Structure):
                 ("rayTMin", C.c_float), ("renderMode", C.c_uint32)]
 
 
+class DenoiseParams(C.Structure):
+    """include/raylib_amd.h RaylibAMDDenoiseParams."""
+    _fields_ = [("iterations", C.c_int32), ("sigmaColor", C.c_float), ("sigmaNormal", C.c_float), ("sigmaAlbedo", C.c_float)]
+
+
 class Stats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("nodesVisited", C.c_uint64), ("trisTested", C.c_uint64),
                 ("shadedHits", C.c_uint64), ("texFetches", C.c_uint64), ("cameraSamples", C.c_uint64),
@@ -136,6 +141,10 @@ _EXPORTS = {
     "RaylibAMD_CreateImageFromData": (C.c_void_p, [C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
     "RaylibAMD_DumpImageRGBA": (None, [C.c_void_p, C.POINTER(C.c_float)]),
     "RaylibAMD_OBJModelSetTexture": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p]),
+    "RaylibAMD_Denoise": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DenoiseParams)]),
+    "RaylibAMD_DenoiseHost": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                          C.POINTER(DenoiseParams), C.POINTER(C.c_float)]),
+    "RaylibAMD_EnableDenoiser": (None, [C.c_int32]),
 }
 RAYLIB_H_EXPORTS = [k for k in _EXPORTS if k.startswith("Raylib_")]
 RAYLIB_AMD_H_EXPORTS = [k for k in _EXPORTS if k.startswith("RaylibAMD_")]

@@ -18,4 +18,7 @@ void DeviceShutdown() {}
 int DeviceNumRanks() { return 0; }
 bool DeviceDrain(RaylibAMDStats*) { return false; }
 bool DeviceVerifyExactMath(int, uint64_t*, uint64_t*) { return false; }
+// rl_denoise.hip is a HIP unit too: the device filter fails, and its host restatement (RaylibAMD_DenoiseHost) is not part of this build
+bool DeviceDenoise(Image&, bool, Image*, Image*, Image&, const RaylibAMDDenoiseParams&) { return false; }
+void DenoiseHost(uint32_t, uint32_t, const float*, bool, const float*, const float*, const RaylibAMDDenoiseParams&, float*) {}
 }
