@@ -195,6 +195,11 @@ RAYLIB_API int32_t RaylibAMD_SceneWalk8Host(SceneHandle scene, const float* rays
 /* The leaf list of a small scene (at most 24 leaves, 108 triangles): what k_trace walks instead of the tree when the scene is LDS-resident.
  * Returns the number of leaves (0 = the scene has none); the list's validity is part of RaylibAMD_SceneBVH4Info's check. */
 RAYLIB_API int32_t RaylibAMD_SceneLeafListInfo(SceneHandle scene, uint32_t* outMaxTrianglesPerLeaf);
+/* 1 when no material of the finalized scene has a texture slot and no leaf of its leaf list carries the cut-out bit: with no sky image, k_trace's leaf
+ * list is then walked by the kernel's plain instance (no texture, cut-out or sky code; RAYLIB_PLAIN_KERNEL=0 keeps the general one).  0 otherwise.  No device needed. */
+RAYLIB_API int32_t RaylibAMD_ScenePlain(SceneHandle scene);
+/* 1 when the megakernel of the last path-traced render on this process was the leaf-list kernel's plain instance, else 0. */
+RAYLIB_API int32_t RaylibAMD_LastTracePlain(void);
 /* FNV-1a of the flat BVH (node records + leaf order): the multi-threaded build (RAYLIB_BUILD_THREADS, default = host
  * threads, <= 32) must give the tree of the single-threaded one. */
 RAYLIB_API uint64_t RaylibAMD_SceneBVHHash(SceneHandle scene);

@@ -605,6 +605,12 @@ int32_t RaylibAMD_SceneLeafListInfo(SceneHandle sh, uint32_t* maxPerLeaf)
 	if (maxPerLeaf) *maxPerLeaf = most;
 	return leaves;
 }
+int32_t RaylibAMD_ScenePlain(SceneHandle sh)
+{
+	Scene* s = (Scene*)sh;
+	return (s && s->finalized && ScenePlain(*s)) ? 1 : 0;
+}
+int32_t RaylibAMD_LastTracePlain(void) { return DeviceLastTracePlain(); }
 uint64_t RaylibAMD_SceneBVHHash(SceneHandle sh)
 {
 	Scene* s = (Scene*)sh;

@@ -186,6 +186,9 @@ struct Scene {
 	void Finalize();
 	bool BuildAccel(float t0, float t1);   // false: the scene exceeds the BVH's addressing (logged); nothing was built
 };
+// true when no material has a texture slot (>= 0) and no leaf of the leaf list carries the cut-out bit: the leaf-list kernel's
+// plain instance may render the scene (rl_runtime.inl PlainLeafList adds the per-render conditions)
+bool ScenePlain(const Scene& sc);
 
 // loaders (rl_obj_loader.cc, rl_image_io.cc)
 bool LoadOBJ(const char* path, OBJModel& out);
@@ -227,6 +230,7 @@ bool DecodeJPEG(const std::vector<uint8_t>& data, uint32_t& w, uint32_t& h, std:
 bool DecodeTGA(const std::vector<uint8_t>& data, uint32_t& w, uint32_t& h, std::vector<uint8_t>& rgba);
 bool EncodeJPEG(uint32_t w, uint32_t h, const uint8_t* rgbTopDown, std::vector<uint8_t>& out);   // baseline, quality 75, 4:2:0
 bool DeviceRender(Scene& scene, const RenderRequest& req, RaylibAMDStats& stats);
+int32_t DeviceLastTracePlain();   // 1: the last path-traced render's megakernel was the leaf-list kernel's plain instance (rl_runtime.inl PlainLeafList)
 bool DeviceDrain(RaylibAMDStats* outLastStats);   // waits for multi-rank frames in flight; true + stats when that completed the last render call's numbers
 bool DeviceClosestHit(Scene& scene, const float* rays, int32_t n, float tMin, void* outHits);
 bool DevicePostProcess(Image& img);          // Image2D::PostProcess on the device; false when no device

@@ -85,6 +85,9 @@ __device__ __forceinline__ void sincos_(float x, float* s, float* c) { const flo
 __device__ __forceinline__ void sincos_signs_(float x, bool* sn, bool* cn) { rlm::sincosf_signs(x, sn, cn); }
 #endif
 __device__ __forceinline__ float fmod1_(float x) { return fmodf(x, 1.0f); }
+// tanf and powf always inline, for the one kernel instance that may take them so (rl_render.hip RL_PLAIN_INLINE_TAN / _POW)
+__device__ __forceinline__ float tan_inline_(float x)  { return rlm::tanf_(x); }
+__device__ __forceinline__ float pow_inline_(float x, float y) { return rlm::powf_(x, y); }
 
 // ---- 1.0f / x and sqrtf(x), correctly rounded, in fewer issue cycles ---------------------------------------------------------------------
 // The compiler's IEEE expansions are long: 1.0f / x = v_div_scale x 2, v_rcp, five fma / mul, v_div_fmas, v_div_fixup = 36 VALU issue cycles per

@@ -261,15 +261,21 @@ template <int LDS> struct LdsAt {
 	static constexpr int TOTAL = MATS + RL_LDS_MAXMATS * 5;
 };
 
+// PLAIN (k_trace's instance for scenes without a texture slot, rl_runtime.inl PlainLeafList): the record in LDS is the first four float4 of the
+// material (RL_LDS_MSTRIDE), and every texture slot is the constant -1 -- what each slot of such a scene holds, or another negative number, which every
+// reader takes the same way (tex >= 0 is "textured") -- so that the texture branches of the shading code fold away with their calls.
+#define RL_LDS_MSTRIDE(plain) ((plain) ? 4 : 5)
+template <bool PLAIN = false>
 __device__ __forceinline__ Mat MatFrom(const float4* p)
 {
-	float4 a = p[0], b = p[1], c = p[2], d = p[3], e = p[4];
+	float4 a = p[0], b = p[1], c = p[2], d = p[3], e = PLAIN ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : p[4];
 	Mat m;
 	m.type = __float_as_int(a.x); m.albedo = v3(a.y, a.z, a.w);
 	m.roughness = b.x; m.metallic = b.y; m.emissive = v3(b.z, b.w, c.x);
 	m.ior = c.y; m.transmission = v3(c.z, c.w, d.x); m.fuzz = d.y;
 	m.tex0 = __float_as_int(d.z); m.tex1 = __float_as_int(d.w);
 	m.tex2 = __float_as_int(e.x); m.tex3 = __float_as_int(e.y); m.tex4 = __float_as_int(e.z);
+	if (PLAIN) m.tex0 = m.tex1 = m.tex2 = m.tex3 = m.tex4 = -1;
 	return m;
 }
 
@@ -658,7 +664,8 @@ __device__ __forceinline__ uint4 GLoadU4(const void* p, int i) { const rl_v4u v 
 // test, with an out-of-line walk that applies it per candidate for the lane whose winner fails it.  Sound -- the search finds the nearest of a larger set, and
 // a winner that passes the rule is the nearest of the smaller one too -- and 0.5 % faster, but the call made the register allocator keep the 24 keys in
 // scratch memory: 28 GB of spill traffic per frame, three times everything else the kernel moves.)
-template <bool ANYHIT>
+// PLAIN: no leaf carries the cut-out bit (rl_runtime.inl PlainLeafList), so the walk does not test it.
+template <bool ANYHIT, bool PLAIN = false>
 __device__ __forceinline__ bool TraverseLeafList(const DSceneView& S, V3 o, V3 d, float tMin, HitRec& best, Counters& c, const float4* sm)
 {
 	c.rays++;
@@ -746,7 +753,7 @@ __device__ __forceinline__ bool TraverseLeafList(const DSceneView& S, V3 o, V3 d
 		const uint32_t code = (uint32_t)~ref;
 		const int first = (int)(code >> 6);
 		const int count = (int)(code & 7u) + 1;
-		const bool alpha = (code & 8u) != 0;
+		const bool alpha = !PLAIN && (code & 8u) != 0;
 #if defined(RL_DIAG_STAMPS) && RL_DIAG_STAMPS >= 2
 		// diagnostic build: what regrouping the (ray, triangle) pairs of this round across the wave could save at best.  The lanes that visit a leaf in this
 		// round test `count` triangles each; dealt evenly to 64 lanes the round's pairs would take ceil(pairs / 64) wave steps instead of max(count) -- and no
@@ -787,10 +794,10 @@ __device__ __forceinline__ bool TraverseLeafList(const DSceneView& S, V3 o, V3 d
 
 // The same closest-hit search on the BVH4 (DNode4): four slab tests per step, hit children ordered by entry distance.
 // FULL: float boxes (S.nodes4f), else the grid nodes (S.nodes4)
-template <int STACK, bool ANYHIT, bool PRIMS, bool FULL, int LDS = 0>
+template <int STACK, bool ANYHIT, bool PRIMS, bool FULL, int LDS = 0, bool PLAIN = false>
 __device__ __forceinline__ bool Traverse4(const DSceneView& S, V3 o, V3 d, float rayTime, float tMin, HitRec& best, int* stk, Counters& c, const float4* sm = nullptr)
 {
-	if constexpr (LDS == 2) return TraverseLeafList<ANYHIT>(S, o, d, tMin, best, c, sm);
+	if constexpr (LDS == 2) return TraverseLeafList<ANYHIT, PLAIN>(S, o, d, tMin, best, c, sm);
 	c.rays++;
 	V3 invb = v3(rtm::rcp1_(d.x), rtm::rcp1_(d.y), rtm::rcp1_(d.z));   // for the box tests (the candidate rule divides again: exact, and rare)
 	if (!FULL) invb = ClampInv(invb);
@@ -965,8 +972,22 @@ __device__ __forceinline__ float SinThetaL(V3 w) { return rtm::sqrt_(fmaxf(0.0f,
 __device__ __forceinline__ float CosPhi(V3 w) { float s = SinThetaL(w); return (s == 0) ? 1 : Clampf(w.x / s, -1, 1); }
 __device__ __forceinline__ float SinPhi(V3 w) { float s = SinThetaL(w); return (s == 0) ? 0 : Clampf(w.y / s, -1, 1); }
 
+// k_trace's PLAIN instance has fewer registers to place around a call (no texture, cut-out or sky code): there the tan_ of GeometryBeckmann and the pow_ of
+// the Fresnel term may be inlined, measured in DESIGN.md section 2.  Every other kernel keeps the calls.  (The sampler's pow_ stays a call everywhere: a template
+// parameter on BeckmannSample would change how the compiler inlines it into every other kernel.)
+#ifndef RL_PLAIN_INLINE_TAN
+#define RL_PLAIN_INLINE_TAN 0
+#endif
+#ifndef RL_PLAIN_INLINE_POW
+#define RL_PLAIN_INLINE_POW 0
+#endif
+template <bool INL> __device__ __forceinline__ float TanSel(float x) { return INL ? rtm::tan_inline_(x) : rtm::tan_(x); }
+template <bool INL> __device__ __forceinline__ float PowSel(float x, float y) { return INL ? rtm::pow_inline_(x, y) : rtm::pow_(x, y); }
+
 // reference render/material.cc:83-165
-__device__ void BeckmannSample11(float cosThetaI, float U1, float U2, float* slope_x, float* slope_y, Counters& cn)
+// (__forceinline__ on the sampler and its caller below: the compiler inlined both into every kernel of its own accord until k_trace's PLAIN instance added
+//  one more call site, after which it kept BeckmannSample out of line in all of them)
+__device__ __forceinline__ void BeckmannSample11(float cosThetaI, float U1, float U2, float* slope_x, float* slope_y, Counters& cn)
 {
 	(void)cn;   // diagnostic builds count Newton iterations
 	const float Pi = RL_PI;
@@ -1018,7 +1039,7 @@ __device__ void BeckmannSample11(float cosThetaI, float U1, float U2, float* slo
 	*slope_y = ErfInv(2.0f * fmaxf(U2, (float)1e-6f) - 1.0f);
 }
 // reference render/material.cc:166-190
-__device__ V3 BeckmannSample(V3 wi, float alpha_x, float alpha_y, float U1, float U2, Counters& cn)
+__device__ __forceinline__ V3 BeckmannSample(V3 wi, float alpha_x, float alpha_y, float U1, float U2, Counters& cn)
 {
 	V3 wiStretched = normalize(v3(alpha_x * wi.x, alpha_y * wi.y, wi.z));
 	float slope_x, slope_y;
@@ -1044,10 +1065,11 @@ __device__ __forceinline__ float DistributionBeckmann(V3 N, V3 H, float roughnes
 	return num / denom;
 }
 // reference render/brdf.h:74-93
+template <bool ITAN = false>
 __device__ __forceinline__ float GeometryBeckmann(V3 N, V3 H, V3 V, float roughness)
 {
 	float thetaV = rtm::acos_(dot(N, V));
-	float tanThetaV = rtm::tan_(thetaV);
+	float tanThetaV = TanSel<ITAN>(thetaV);
 	float a = rtm::rcp1_(roughness * tanThetaV);
 	float aa = a * a;
 	if (dot(V, H) / dot(V, N) <= 0.0f) return 0.0f;
@@ -1107,6 +1129,8 @@ __device__ __forceinline__ V3 Emitted(const DSceneView& S, const Mat& m, const S
 // One scattering event.  Returns false when the material does not scatter.
 // Outputs reflectance, new direction, pdf and ScatteringPdf (the value the
 // reference recomputes at renderer.cc:144).
+// PLAIN: k_trace's instance for plain scenes (MatFrom<true>), which takes the inlining choices above.
+template <bool PLAIN = false>
 __device__ __forceinline__ bool Scatter(const DSceneView& S, const Mat& m, V3 inD, const Surf& s, Rng& g, Counters& c,
                                         V3& refl, V3& outD, float& pdf, float& sp)
 {
@@ -1197,9 +1221,9 @@ __device__ __forceinline__ bool Scatter(const DSceneView& S, const Mat& m, V3 in
 
 			V3 F0 = v3s(0.04f);
 			F0 = mix(F0, baseColor, metallic);
-			V3 F = F0 + (1.0f - F0) * rtm::pow_(1.0f - absDot(Wh, Wo), 5.0f);
-			float ggx2 = GeometryBeckmann(N, Wh, Wo, roughness);
-			float ggx1 = GeometryBeckmann(N, Wh, Wi, roughness);
+			V3 F = F0 + (1.0f - F0) * PowSel<PLAIN && RL_PLAIN_INLINE_POW>(1.0f - absDot(Wh, Wo), 5.0f);
+			float ggx2 = GeometryBeckmann<PLAIN && RL_PLAIN_INLINE_TAN>(N, Wh, Wo, roughness);
+			float ggx1 = GeometryBeckmann<PLAIN && RL_PLAIN_INLINE_TAN>(N, Wh, Wi, roughness);
 			float G = rtm::rcp1_(1.0f + ggx1 * ggx2);
 			float NDF = DistributionBeckmann(N, Wh, roughness);
 
@@ -1270,11 +1294,12 @@ __device__ __forceinline__ void PixelUV(const DRenderParams& P, uint32_t x, uint
 struct SkyRot { float m0[3], m1[3], m2[3]; };   // Rotator(yaw 90).rotate rows, computed on the host (renderer.cc:166-168)
 
 // Miss shader: sky panorama + sun (reference render/renderer.cc:155-199)
-template <int STACK, bool PRIMS, bool FULL, int LDS = 0>
+// PLAIN: the launch has no sky image (rl_runtime.inl PlainLeafList), and the panorama lookup is compiled out
+template <int STACK, bool PRIMS, bool FULL, int LDS = 0, bool PLAIN = false>
 __device__ __forceinline__ V3 MissShader(const DSceneView& S, const SkyRot& R, V3 o, V3 d, float rayTime, float rayTMin, int* stk, Counters& c, const float4* sm = nullptr)
 {
 	V3 missResult = v3s(0.0f);
-	if (S.sky) {
+	if (!PLAIN && S.sky) {
 		V3 dir = normalize(d);
 		V3 D = v3(dot(ld3(R.m0), dir), dot(ld3(R.m1), dir), dot(ld3(R.m2), dir));
 		float u = rtm::atan2_(D.z, D.x), v = rtm::asin_(D.y);
@@ -1289,7 +1314,7 @@ __device__ __forceinline__ V3 MissShader(const DSceneView& S, const SkyRot& R, V
 	if (S.hasSun) {
 		HitRec tmp;
 		bool occluded;
-		if constexpr (LDS != 0) occluded = Traverse4<STACK, true, PRIMS, FULL, LDS>(S, o, -ld3(S.sunDirection), rayTime, rayTMin, tmp, stk, c, sm);
+		if constexpr (LDS != 0) occluded = Traverse4<STACK, true, PRIMS, FULL, LDS, PLAIN>(S, o, -ld3(S.sunDirection), rayTime, rayTMin, tmp, stk, c, sm);
 		else occluded = (!PRIMS && (FULL ? (const void*)S.nodes4f : (const void*)S.nodes4)) ? Traverse4<STACK, true, PRIMS, FULL, LDS>(S, o, -ld3(S.sunDirection), rayTime, rayTMin, tmp, stk, c, sm)
 		                                           : Traverse<STACK, true, PRIMS>(S, o, -ld3(S.sunDirection), rayTime, rayTMin, tmp, stk, c);
 		if (!occluded) missResult = missResult + ld3(S.sunIlluminance);
@@ -1479,7 +1504,7 @@ template <class T> __device__ __forceinline__ T KArg(uint32_t offset)
 	(void)P; (void)S; (void)R; (void)samples; (void)pathStack; (void)counters; (void)jobCounter
 #endif
 
-template <int STACK, bool PRIMS, bool FULL, int LDS = 0>
+template <int STACK, bool PRIMS, bool FULL, int LDS = 0, bool PLAIN = false>
 __global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 2))
 k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB* __restrict__ samplesK,
         float* __restrict__ pathStackK, unsigned long long* __restrict__ countersK, unsigned int* __restrict__ jobCounterK)
@@ -1498,7 +1523,7 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 #endif
 	if (LDS) {
 		RL_ARGS();
-		const uint32_t nN = (uint32_t)(LDS == 2 ? S.numLeafRecords : S.numNodes4) * 8u, nT = (uint32_t)S.numTriangles * 4u, nM = (uint32_t)S.numMaterials * 5u;
+		const uint32_t nN = (uint32_t)(LDS == 2 ? S.numLeafRecords : S.numNodes4) * 8u, nT = (uint32_t)S.numTriangles * 4u, nM = (uint32_t)S.numMaterials * RL_LDS_MSTRIDE(PLAIN);
 		for (uint32_t i = threadIdx.x; i < 4u; i += RL_BLOCK) s_scene[RL_LDS_ROOT + i] = ((const float4*)S.nodes)[i];
 		for (uint32_t i = threadIdx.x; i < nN; i += RL_BLOCK) s_scene[RL_LDS_NODES + (i >> 3) * RL_LDS_NSTRIDE + (i & 7u)] = ((const float4*)(LDS == 2 ? S.leafList : S.nodes4f))[i];
 		if (LDS == 2) {
@@ -1514,7 +1539,7 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 		} else {
 			for (uint32_t i = threadIdx.x; i < nT; i += RL_BLOCK) { const uint32_t at = (i >> 2) * RL_LDS_TSTRIDE + (i & 3u); s_scene[LdsAt<LDS>::ISECT + at] = ((const float4*)S.isect)[i]; s_scene[LdsAt<LDS>::SHADE + at] = ((const float4*)S.shade)[i]; }
 		}
-		for (uint32_t i = threadIdx.x; i < nM; i += RL_BLOCK) s_scene[LdsAt<LDS>::MATS + i] = ((const float4*)S.materials)[i];
+		for (uint32_t i = threadIdx.x; i < nM; i += RL_BLOCK) s_scene[LdsAt<LDS>::MATS + i] = ((const float4*)S.materials)[PLAIN ? (i >> 2) * 5u + (i & 3u) : i];
 		__syncthreads();
 	}
 	int* stk = s_stack + threadIdx.x;
@@ -1662,7 +1687,7 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 							if (sunQuick) {
 								c.rays++; c.nodes++;   // the closest-hit query this replaces fetches the root node and stops
 								DSceneView Sq = S; Sq.hasSun = 0;
-								V3 L = MissShader<STACK, PRIMS, FULL, LDS>(Sq, R, qo, qd, qTime, P.rayTMin, stk, c, sm);
+								V3 L = MissShader<STACK, PRIMS, FULL, LDS, PLAIN>(Sq, R, qo, qd, qTime, P.rayTMin, stk, c, sm);
 								if (S.hasSun) { c.rays++; c.nodes++; L = L + ld3(S.sunIlluminance); }
 								samples[qOut] = make_sample(L.x, L.y, L.z);
 								survive = false;
@@ -1734,7 +1759,7 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 							if (sunQuick) {
 								c.rays++; c.nodes++;   // the closest-hit query this replaces fetches the root node and stops
 								DSceneView Sq = S; Sq.hasSun = 0;
-								V3 L = MissShader<STACK, PRIMS, FULL, LDS>(Sq, R, o, d, rayTime, P.rayTMin, stk, c, sm);
+								V3 L = MissShader<STACK, PRIMS, FULL, LDS, PLAIN>(Sq, R, o, d, rayTime, P.rayTMin, stk, c, sm);
 								if (S.hasSun) { c.rays++; c.nodes++; L = L + ld3(S.sunIlluminance); }
 								samples[outIndex] = make_sample(L.x, L.y, L.z);
 								active = false;
@@ -1761,7 +1786,7 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 		doTrace = active && depth < P.maxPathLength;   // renderer.cc:120-123 otherwise
 		// the 4-wide tree when the launch carries it (triangle scenes; half the steps: 24.6 -> 22.4 ms on the Cornell frame)
 		if (doTrace) {
-			if constexpr (LDS != 0) hit = Traverse4<STACK, false, PRIMS, FULL, LDS>(S, o, d, rayTime, P.rayTMin, h, stk, c, sm);   // an LDS-resident scene has its wide tree
+			if constexpr (LDS != 0) hit = Traverse4<STACK, false, PRIMS, FULL, LDS, PLAIN>(S, o, d, rayTime, P.rayTMin, h, stk, c, sm);   // an LDS-resident scene has its wide tree
 			else hit = (!PRIMS && (FULL ? (const void*)S.nodes4f : (const void*)S.nodes4)) ? Traverse4<STACK, false, PRIMS, FULL, LDS>(S, o, d, rayTime, P.rayTMin, h, stk, c, sm) : Traverse<STACK, false, PRIMS>(S, o, d, rayTime, P.rayTMin, h, stk, c);
 		}
 		}
@@ -1781,11 +1806,11 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 				subLast = __builtin_amdgcn_s_memtime();
 #endif
 				const int mi = BuildSurface<PRIMS, LDS>(S, o, d, h, s, true, c, sm);
-				const Mat m = LDS ? MatFrom(sm + LdsAt<LDS>::MATS + mi * 5) : LoadMat(S, mi);
+				const Mat m = LDS ? MatFrom<PLAIN>(sm + LdsAt<LDS>::MATS + mi * RL_LDS_MSTRIDE(PLAIN)) : LoadMat(S, mi);
 				RL_SUBSTAMP(0);
 				V3 refl = v3s(0.0f), outD = v3s(0.0f);
 				float pdf = 0.0f, sp = 0.0f;
-				const bool scattered = Scatter(S, m, d, s, g, c, refl, outD, pdf, sp);
+				const bool scattered = Scatter<PLAIN>(S, m, d, s, g, c, refl, outD, pdf, sp);
 				RL_SUBSTAMP(1);
 				const V3 E = Emitted(S, m, s, c);
 				if (scattered && pdf > 0.0f) {
@@ -1815,7 +1840,7 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 			} else {
 				RL_ARGS();
 				RL_LANEBEGIN();
-				L = MissShader<STACK, PRIMS, FULL, LDS>(S, R, o, d, rayTime, P.rayTMin, stk, c, sm);
+				L = MissShader<STACK, PRIMS, FULL, LDS, PLAIN>(S, R, o, d, rayTime, P.rayTMin, stk, c, sm);
 				done = true;
 				RL_LANESTAMP(2, true);
 			}

@@ -40,6 +40,7 @@ struct DeviceScene {
 	bool hasNodes4 = false, hasNodes8 = false; uint32_t depth8 = 0; float sahNodes4 = 0.0f;
 	double boundsMin[3] = { 0, 0, 0 }, boundsMax[3] = { 0, 0, 0 };   // of all triangle vertices (CullCells)
 	bool boundsValid = false;                                        // triangles only, every coordinate finite
+	bool plain = false;                                              // ScenePlain: no texture slot, no cut-out leaf (PlainLeafList)
 };
 
 namespace {
@@ -438,6 +439,7 @@ bool UploadScene(Scene& sc)
 	}
 
 	DeviceScene* D = new DeviceScene;
+	D->plain = ScenePlain(sc);
 	D->bvhDepth = sc.bvh.depth; D->stackNeed4 = sc.bvh.stackNeed4; D->hasNodes4 = !sc.bvh.nodes4.empty(); D->hasNodes8 = !sc.bvh.nodes8.empty(); D->depth8 = sc.bvh.depth8; D->sahNodes4 = sc.bvh.sahNodes4;
 	{   // Rotator(yaw = 90).rotate rows, reference geom/transform.cc:47-65 (host libm, as the reference)
 		const float pi_f = (float)3.1415926535897932385;
@@ -531,6 +533,19 @@ bool SyncSky(Scene& sc)
 }
 
 typedef void (*TraceKernel)(const DRenderParams, const DSceneView, const SkyRot, SampleRGB*, float*, unsigned long long*, unsigned int*);
+
+// The leaf-list kernel (k_trace<16, false, true, 2>: a scene of few leaves, in LDS) has a PLAIN instance without the texture, cut-out and sky code, which
+// computes the same values in the same order for the scenes it takes: those without a texture slot or a cut-out leaf (ScenePlain, once per scene) rendered
+// without a sky image (per render).  RAYLIB_PLAIN_KERNEL=0 keeps the general instance.  Every place that picks or recognises the leaf-list kernel goes
+// through these three.
+static std::atomic<int32_t> g_lastTracePlain{0};   // RaylibAMD_LastTracePlain
+static bool PlainLeafList(const DeviceScene* DS, const DSceneView& v)
+{
+	const char* e = getenv("RAYLIB_PLAIN_KERNEL");
+	return DS->plain && v.sky == nullptr && (e ? atoi(e) != 0 : true);
+}
+static TraceKernel LeafListKernel(bool plain) { return plain ? (TraceKernel)k_trace<16, false, true, 2, true> : (TraceKernel)k_trace<16, false, true, 2>; }
+static bool IsLeafListKernel(TraceKernel k) { return k == LeafListKernel(false) || k == LeafListKernel(true); }
 
 // poolK = 0: k_trace (one path per lane); poolK = K: k_trace_pool with 64*K paths per wave
 template <int STACK, bool PRIMS>
@@ -672,11 +687,12 @@ bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRende
 				const char* f = getenv("RAYLIB_LEAF_LIST");
 				const bool flat = lds && traceView.leafList != nullptr && traceView.numLeafRecords <= RL_LEAFLIST_RECORDS && sc.triangles.size() <= RL_LEAFLIST_MAXTRIS && (f ? atoi(f) != 0 : true)
 				                  && st.rayTMin >= 0.0f;   // its sortable keys are entry distances, never negative (rl_render.hip TraverseLeafList)
-				if (flat) { traceKernel = (TraceKernel)k_trace<STACK, PRIMS, true, 2>; width = 0; }
+				if (flat) { traceKernel = LeafListKernel(PlainLeafList(DS, traceView)); width = 0; }
 				else if (lds) traceKernel = (TraceKernel)k_trace<STACK, PRIMS, true, 1>;
 			}
 			if (!lds) traceKernel = full ? (TraceKernel)k_trace<STACK, PRIMS, true> : (TraceKernel)k_trace<STACK, PRIMS, false>;
 		}
+		g_lastTracePlain.store(traceKernel == LeafListKernel(true) ? 1 : 0, std::memory_order_relaxed);
 		const uint32_t pathsPerThread = poolK > 0 ? (uint32_t)poolK : 1u;
 		pend.schedulePaths = pathsPerThread; pend.treeWidth = (uint32_t)width;
 		// ---- cells that cannot see the scene leave the job list (CullCells) ----
@@ -768,7 +784,7 @@ bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRende
 				}
 				// the leaf-list kernel's chunk belongs to a workgroup, whose four waves draw batches of 64 from it (RL_QUEUE_SHARED_CHUNK): four waves' worth,
 				// RAYLIB_JOB_CHUNK_MAX (default 1024) at most
-				if (RL_QUEUE_SHARED_CHUNK && traceKernel == (TraceKernel)k_trace<16, false, true, 2> && !getenv("RAYLIB_JOB_CHUNK")) {
+				if (RL_QUEUE_SHARED_CHUNK && IsLeafListKernel(traceKernel) && !getenv("RAYLIB_JOB_CHUNK")) {
 					uint64_t cap = 1024; if (const char* e = getenv("RAYLIB_JOB_CHUNK_MAX")) cap = (uint64_t)std::max(64, atoi(e));
 					P.jobChunk = (uint32_t)std::min<uint64_t>(cap, std::max<uint64_t>(256, 4 * chunk));
 				}
@@ -783,7 +799,7 @@ bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRende
 				heads = (std::max(1u, numActive) + cellsPerHead - 1) / cellsPerHead;   // no empty band: every head's first job exists (and h * jobsPerHead < numJobs < 2^32)
 				P.numHeads = heads; P.jobsPerHead = cellsPerHead * cnt * 64u;
 				{   // guided draws at the end of a band: 2^shift ~ twice the drawers per head (waves; workgroups in the leaf-list kernel, whose chunk is shared)
-					const bool perBlockChunk = RL_QUEUE_SHARED_CHUNK && traceKernel == (TraceKernel)k_trace<16, false, true, 2>;
+					const bool perBlockChunk = RL_QUEUE_SHARED_CHUNK && IsLeafListKernel(traceKernel);
 					const uint32_t drawers = std::max(1u, blocks * (perBlockChunk ? 1u : (uint32_t)(RL_BLOCK / 64)) / heads);
 					uint32_t shift = 1; while ((1u << shift) < 2u * drawers && shift < 24u) ++shift;
 					int guided = 0;   // measured: no gain on either bench workload -- a heavy chunk drawn three rounds before the end outlasts the guided ones
@@ -1147,6 +1163,8 @@ bool DeviceRender(Scene& sc, const RenderRequest& req, RaylibAMDStats& stats)
 	if (!(whole && (g_rt.ranks.size() > 1 || g_rt.gatherSelf))) stats.wallMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 	return ok;
 }
+
+int32_t DeviceLastTracePlain() { return g_lastTracePlain.load(std::memory_order_relaxed); }
 
 // Waits for whatever Raylib_Render left in flight.  True with `out` filled when that completed the LAST render call's numbers (counters, times)
 // that the call itself could not report yet.

@@ -179,6 +179,16 @@ bool Scene::BuildAccel(float t0, float t1)
 	return true;
 }
 
+bool ScenePlain(const Scene& sc)
+{
+	for (const HostMaterial& m : sc.materials) for (int k = 0; k < 5; ++k) if (m.tex[k] >= 0) return false;
+	for (const DNode4& n : sc.bvh.leafList) for (int k = 0; k < 4; ++k) {
+		const int32_t ref = n.child[k];
+		if (ref < 0 && ref != DNODE_EMPTY && (((uint32_t)~ref) & 8u) != 0u) return false;
+	}
+	return true;
+}
+
 // Image2D::PostProcess on the host (reference render/image.cc:44-103): max-luminance
 // scan, extended Reinhard on luminance, clamp to white, gamma 1/2.2.
 void PostProcessHost(Image& img)
