@@ -200,6 +200,24 @@ RAYLIB_API int32_t RaylibAMD_SceneLeafListInfo(SceneHandle scene, uint32_t* outM
 RAYLIB_API int32_t RaylibAMD_ScenePlain(SceneHandle scene);
 /* 1 when the megakernel of the last path-traced render on this process was the leaf-list kernel's plain instance, else 0. */
 RAYLIB_API int32_t RaylibAMD_LastTracePlain(void);
+/* What a one-rank Raylib_Render of `settings` would launch under the current environment (csrc/rl_plan.cc): the kernel instance, its tree and the job
+ * layout of its first launch over every cell of the frame, for a device of numCUs CUs on which the kernel fits workgroupsPerCU workgroups.  No device needed.
+ * Returns 1, -1 when the scene's BVH is too deep to render (the plan is then not filled in further), 0 for a bad argument or a scene not finalized. */
+typedef struct RaylibAMDRenderPlan {
+	int32_t pathTrace;        /* 0: a debug render mode (k_aov on the BVH2) */
+	int32_t stack, prims;     /* the instance's STACK; spheres or cubes */
+	int32_t poolK;            /* 0: k_trace; K: k_trace_pool, 64 K paths per wave */
+	int32_t tree;             /* 0 none (the leaf list), 1 BVH2, 2 4-wide float boxes, 3 4-wide grid nodes, 4 8-wide */
+	int32_t lstack;           /* k_trace_pool: traversal-stack entries in LDS */
+	int32_t lds;              /* k_trace: 0, 1 the scene in LDS, 2 the leaf list */
+	int32_t plain;            /* the leaf-list kernel's plain instance */
+	uint32_t pathsPerWave, treeWidth, nodeBytes;   /* as RaylibAMDStats reports them */
+	int32_t keepNodes4, keepNodes4f;               /* the launch carries the grid / float-box wide nodes */
+	int32_t eagerTree;        /* the wide tree the scene's upload puts on the device (tree code, 0: none) */
+	uint32_t batch, sampleCount, blocks, stackStride, jobChunk, heads, jobsPerHead, guideShift;
+	uint64_t jobs;
+} RaylibAMDRenderPlan;
+RAYLIB_API int32_t RaylibAMD_PlanRender(SceneHandle scene, const RendererSettings* settings, int32_t hasSky, int32_t numCUs, int32_t workgroupsPerCU, RaylibAMDRenderPlan* out);
 /* FNV-1a of the flat BVH (node records + leaf order): the multi-threaded build (RAYLIB_BUILD_THREADS, default = host
  * threads, <= 32) must give the tree of the single-threaded one. */
 RAYLIB_API uint64_t RaylibAMD_SceneBVHHash(SceneHandle scene);

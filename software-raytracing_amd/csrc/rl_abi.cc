@@ -5,6 +5,7 @@
 #include "raylib.h"
 #include "raylib_amd.h"
 #include "rl_host.h"
+#include "rl_plan.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -611,6 +612,24 @@ int32_t RaylibAMD_ScenePlain(SceneHandle sh)
 	return (s && s->finalized && ScenePlain(*s)) ? 1 : 0;
 }
 int32_t RaylibAMD_LastTracePlain(void) { return DeviceLastTracePlain(); }
+int32_t RaylibAMD_PlanRender(SceneHandle sh, const RendererSettings* settings, int32_t hasSky, int32_t numCUs, int32_t workgroupsPerCU, RaylibAMDRenderPlan* out)
+{
+	Scene* s = (Scene*)sh;
+	if (!s || !s->finalized || !settings || !out || numCUs < 1) return 0;
+	memset(out, 0, sizeof(*out));
+	const RenderKnobs knobs = ReadRenderKnobs();
+	const TracePlan t = PlanTrace(*s, *settings, hasSky != 0, knobs);
+	if (!t.ok) return -1;
+	out->pathTrace = t.pathTrace; out->stack = t.stack; out->prims = t.prims; out->poolK = t.poolK; out->tree = t.tree; out->lstack = t.lstack; out->lds = t.lds; out->plain = t.plain;
+	out->pathsPerWave = t.pathsPerWave; out->treeWidth = t.treeWidth; out->nodeBytes = t.nodeBytes;
+	out->keepNodes4 = t.keepNodes4; out->keepNodes4f = t.keepNodes4f; out->eagerTree = t.eagerTree;
+	const uint32_t cells = ((settings->viewportWidth + 7) / 8) * ((settings->viewportHeight + 7) / 8);
+	const uint32_t spp = (uint32_t)(settings->samplesPerPixel > 1 ? settings->samplesPerPixel : 1);
+	const LaunchPlan L = PlanLaunch(cells, cells, spp, 0, numCUs, workgroupsPerCU, t, knobs);
+	out->batch = L.batch; out->sampleCount = L.sampleCount; out->blocks = L.blocks; out->stackStride = L.stackStride; out->jobChunk = L.jobChunk;
+	out->heads = L.heads; out->jobsPerHead = L.jobsPerHead; out->guideShift = L.guideShift; out->jobs = L.jobs;
+	return 1;
+}
 uint64_t RaylibAMD_SceneBVHHash(SceneHandle sh)
 {
 	Scene* s = (Scene*)sh;

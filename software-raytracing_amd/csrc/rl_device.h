@@ -78,7 +78,7 @@ struct alignas(16) DNode8 {
 	uint32_t qlo[3][2], qhi[3][2];
 };
 static_assert(sizeof(DNode8) == 80, "DNode8");
-#define RL_POOL8_MAXLEVELS 16    /* levels of an 8-wide tree the pool kernel's stack of groups holds (k_trace_pool<2 * this, ..., 3>; rl_runtime.inl selects the walk only then) */
+#define RL_POOL8_MAXLEVELS 16    /* levels of an 8-wide tree the pool kernel's stack of groups holds (k_trace_pool<2 * this, ..., 3>; rl_plan.cc selects the walk only then) */
 // An LDS copy of the top of the 8-wide tree (round 5, measured and not kept: RL_TOP8_NODES > 0 builds it).  Nodes are numbered breadth first, so the first N of them
 // are the levels every ray starts with -- 23 % of all node steps on the 298 k-triangle room for N = 73, 10 % on the 10 M-triangle one (diagnostic build
 // -DRL_DIAG_TOPN) -- and a step on one of them costs the vector memory path nothing (ds_read_b128 instead of global_load_dwordx4) and waits for no cache.  Four
@@ -91,11 +91,6 @@ static_assert(sizeof(DNode8) == 80, "DNode8");
 #endif
 #ifndef RL_POOL8_LSTACK
 #define RL_POOL8_LSTACK 16       /* words of the 8-wide walk's stack that live in LDS: two per group */
-#endif
-// which of the two the POOL schedule walks (a build-time switch so that both can be timed: make variant EXTRA=-DRL_Q4=0);
-// k_trace has both as instantiations and takes the float boxes whenever the scene carries them
-#ifndef RL_Q4
-#define RL_Q4 1
 #endif
 
 // Triangle intersection record, 64 B.  The reference tests ray vs plane, then
@@ -169,6 +164,33 @@ struct DCamera {
 #endif
 // ... and at most this many triangles: 4.5 per leaf on average -- beyond, the leaves grow towards 8 triangles and the tree wins again (tools/gpu_leaflist.py)
 #define RL_LEAFLIST_MAXTRIS (RL_LEAFLIST_RECORDS * 18)
+
+// ---- launch limits the host plans against (rl_plan.cc) and the kernels are built for (rl_render.hip) ----
+#define RL_BLOCK 256   /* threads per workgroup of every kernel */
+// A scene small enough lives in LDS for the duration of a k_trace workgroup (rl_render.hip RL_LDS_*): at most this many wide nodes, triangles, materials
+#ifndef RL_LDS_MAXNODES
+#define RL_LDS_MAXNODES 32
+#endif
+#ifndef RL_LDS_MAXTRIS
+#define RL_LDS_MAXTRIS 128
+#endif
+#ifndef RL_LDS_MAXMATS
+#define RL_LDS_MAXMATS 32
+#endif
+#ifndef RL_POOL_SHORT_LSTACK
+#define RL_POOL_SHORT_LSTACK 18   /* LDS entries of the "short" 32-deep stack: 18 KiB + 20.5 KiB pool + 640 B of libm tables = 4 workgroups per CU */
+#endif
+#define RL_POOL_SHORT_MAXDEPTH 24 /* BVH depth up to which the short variant is used (deeper trees overflow too often: measured) */
+#ifndef RL_QUEUE_SHARED_CHUNK
+#define RL_QUEUE_SHARED_CHUNK 1   /* leaf-list kernel: the workgroup's waves share one job chunk (see the refill) */
+#endif
+#define RL_MAX_HEADS 8u           /* heads of the job list: one per XCD (rl_render.hip TakeJobs) */
+// The pool schedule walks the 8-wide tree (when its levels fit RL_POOL8_MAXLEVELS) for scenes whose rays are expected to take at least this many node steps on
+// the 4-wide tree (BVH::sahNodes4); the builder splits leaves for the 8-wide plan only in those scenes (rl_host.h BVHBuildOptions::minSteps8)
+#define RL_BVH8_MIN_STEPS 40.0f
+
+// one path's radiance in the sample buffer: 12 bytes (the buffer is written once and read once per sample: a fourth float would be a quarter more of both)
+struct SampleRGB { float x, y, z; };
 
 struct DSceneView {
 	const DNode* nodes;

@@ -134,7 +134,7 @@ struct PrimRef { f3 mn, mx; uint8_t kind; uint32_t index; };
 // weighs against an expected node step in that plan.
 // (Round 5, measured: triangle tests per ray 2.26 -> 1.96 ... 2.03 on the 298 k room whatever triCost8 between 0.25 and 2, no frame gets shorter -- the triangle steps
 //  are a twelfth of the walk --, and the binary and 4-wide trees, emitted from the same nodes, gain a level or two: off unless RAYLIB_W8_SPLIT=1 asks for it.)
-struct BVHBuildOptions { bool wideGreedy = false; bool splitLeaves8 = false; float triCost8 = 0.5f; float minSteps8 = 40.0f; };
+struct BVHBuildOptions { bool wideGreedy = false; bool splitLeaves8 = false; float triCost8 = 0.5f; float minSteps8 = RL_BVH8_MIN_STEPS; };
 void BuildBVH(const std::vector<PrimRef>& prims, BVH& out, const BVHBuildOptions& opt = BVHBuildOptions());
 bool BVHCapacityOk(size_t numPrimitives);   // a leaf reference addresses 2^25 primitive slots
 bool ValidateBVH(const BVH& bvh, const std::vector<HostTriangle>& tris);
@@ -187,7 +187,7 @@ struct Scene {
 	bool BuildAccel(float t0, float t1);   // false: the scene exceeds the BVH's addressing (logged); nothing was built
 };
 // true when no material has a texture slot (>= 0) and no leaf of the leaf list carries the cut-out bit: the leaf-list kernel's
-// plain instance may render the scene (rl_runtime.inl PlainLeafList adds the per-render conditions)
+// plain instance may render the scene (rl_plan.cc adds the per-render conditions)
 bool ScenePlain(const Scene& sc);
 
 // loaders (rl_obj_loader.cc, rl_image_io.cc)
@@ -230,7 +230,7 @@ bool DecodeJPEG(const std::vector<uint8_t>& data, uint32_t& w, uint32_t& h, std:
 bool DecodeTGA(const std::vector<uint8_t>& data, uint32_t& w, uint32_t& h, std::vector<uint8_t>& rgba);
 bool EncodeJPEG(uint32_t w, uint32_t h, const uint8_t* rgbTopDown, std::vector<uint8_t>& out);   // baseline, quality 75, 4:2:0
 bool DeviceRender(Scene& scene, const RenderRequest& req, RaylibAMDStats& stats);
-int32_t DeviceLastTracePlain();   // 1: the last path-traced render's megakernel was the leaf-list kernel's plain instance (rl_runtime.inl PlainLeafList)
+int32_t DeviceLastTracePlain();   // 1: the last path-traced render's megakernel was the leaf-list kernel's plain instance (rl_plan.cc)
 bool DeviceDrain(RaylibAMDStats* outLastStats);   // waits for multi-rank frames in flight; true + stats when that completed the last render call's numbers
 bool DeviceClosestHit(Scene& scene, const float* rays, int32_t n, float tMin, void* outHits);
 bool DevicePostProcess(Image& img);          // Image2D::PostProcess on the device; false when no device

@@ -1,0 +1,183 @@
+// The one place that decides which megakernel instance a render launches, on which tree, and the launch's job layout (rl_plan.h).
+// Every measurement behind a default is cited where the default is made; DESIGN.md section 5 has the tables.
+#include "rl_plan.h"
+
+#include <algorithm>
+#include <atomic>
+#include <stdlib.h>
+
+namespace rl {
+
+RenderKnobs ReadRenderKnobs()
+{
+	RenderKnobs k;
+	auto flag = [](const char* name) { const char* e = getenv(name); return e ? (atoi(e) != 0 ? 1 : 0) : -1; };
+	if (const char* e = getenv("RAYLIB_POOL")) { const int v = atoi(e); k.pool = (v == 2 || v == 3 || v == 4) ? v : 0; }
+	if (const char* e = getenv("RAYLIB_POOL_MIN_TRIS")) k.poolMinTris = (uint32_t)atoi(e);
+	if (const char* e = getenv("RAYLIB_POOL_SHORT_STACK")) { const int v = atoi(e); k.poolShortStack = (v == 0 || v == 4) ? v : 1; }
+	k.bvh4 = flag("RAYLIB_BVH4"); k.bvh8 = flag("RAYLIB_BVH8");
+	k.ldsScene = flag("RAYLIB_LDS_SCENE"); k.leafList = flag("RAYLIB_LEAF_LIST"); k.plainKernel = flag("RAYLIB_PLAIN_KERNEL");
+	if (const char* e = getenv("RAYLIB_SAMPLE_BATCH")) k.sampleBatch = std::max(0, atoi(e));
+	if (const char* e = getenv("RAYLIB_SAMPLE_BUFFER_GIB")) k.sampleBufferGiB = std::max(0, atoi(e));
+	if (const char* e = getenv("RAYLIB_JOB_CHUNK")) k.jobChunk = std::max(0, atoi(e));
+	if (const char* e = getenv("RAYLIB_JOB_HEADS")) k.jobHeads = std::max(1, atoi(e));
+	if (const char* e = getenv("RAYLIB_GUIDED")) k.guided = atoi(e);
+	if (const char* e = getenv("RAYLIB_BLOCKS_PER_CU")) k.blocksPerCU = std::max(0, atoi(e));
+	if (const char* e = getenv("RAYLIB_CULL_CELLS")) k.cullCells = atoi(e);
+	return k;
+}
+
+namespace {
+
+// the launch's choice; `say`: log what the render should know (only for the plan that is launched)
+TracePlan Pick(const Scene& sc, const RendererSettings& st, bool hasSky, const RenderKnobs& k, bool say)
+{
+	TracePlan p;
+	const BVH& b = sc.bvh;
+	const size_t ntri = sc.triangles.size();
+	p.prims = !sc.spheres.empty() || !sc.cubes.empty();
+	if (b.depth > 64) {
+		if (say) Log("Raylib_Render: BVH depth %u exceeds the traversal stack (64)", b.depth);
+		p.ok = false;
+		return p;
+	}
+	p.stack = (b.depth <= 16 && !p.prims) ? 16 : b.depth <= 32 ? 32 : 64;
+	p.pathTrace = st.renderMode == RAYLIB_RENDERMODE_Default;
+	if (!p.pathTrace) return p;   // k_aov walks the BVH2
+	const bool hasNodes4 = !b.nodes4.empty(), hasNodes8 = !b.nodes8.empty();
+
+	// The pool schedule for triangle scenes from RAYLIB_POOL_MIN_TRIS triangles on, else k_trace (the Cornell class: tens of triangles, shading-bound).
+	// Measured crossover (tools/gpu_crossover.py, tessellated rooms at 1080p x 16 spp, pool time / k_trace time): 36 triangles 1.07, 144: 0.97, 324: 0.95,
+	// 1296: 0.89, 5184: 0.80, 20736: 0.67.  RAYLIB_POOL=0|2|3|4 overrides.
+	const bool poolable = p.stack <= 32 && !p.prims;
+	const int poolK = k.pool >= 0 ? k.pool : (poolable && ntri >= k.poolMinTris ? 2 : 0);
+	if (poolable && poolK > 0) {
+		p.poolK = poolK; p.pathsPerWave = 64u * (uint32_t)poolK;
+		// the wide tree: whenever the scene carries one whose worst-case stack fits; RAYLIB_BVH4=0|1 overrides
+		if (poolK == 2 && hasNodes4 && b.stackNeed4 <= 64 && k.bvh4 != 0) {
+			p.tree = TREE_GRID4; p.treeWidth = 4;
+			p.stack = b.stackNeed4 <= 32 ? 32 : 64;
+			if (k.poolShortStack == 0) { p.lstack = 32; return p; }
+			// the 8-wide tree (0.67 x the steps of the 4-wide one, each 1.4 x as long) when the scene carries one of at most RL_POOL8_MAXLEVELS levels -- a group
+			// of hit children per level is all its stack ever holds -- and its rays are expected to take many steps: measured over rooms and colonnades of 1 k ...
+			// 10 M triangles (tools/gpu_bvh8_sweep.py, profiles/r04_bvh8_sweep.log) the 8-wide walk loses 2 - 8 % below ~30 expected steps of the 4-wide tree
+			// (the builder's sum of node areas over the root's), breaks even between 30 and 42 and wins 3 - 9 % from 59 up.  RAYLIB_BVH8=0|1 overrides.
+			const bool want8 = hasNodes8 && (k.bvh8 >= 0 ? k.bvh8 != 0 : b.sahNodes4 >= RL_BVH8_MIN_STEPS);
+			if (want8 && b.depth8 <= RL_POOL8_MAXLEVELS) {
+				p.tree = TREE_WIDE8; p.treeWidth = 8; p.nodeBytes = (uint32_t)sizeof(DNode8);
+				p.stack = 2 * RL_POOL8_MAXLEVELS; p.lstack = RL_POOL8_LSTACK;
+				return p;
+			}
+			if (want8 && say) {   // (a deeper 8-wide tree is not walked, and that is said once per scene)
+				static std::atomic<const Scene*> told{ nullptr };
+				if (told.exchange(&sc) != &sc) Log("Raylib_Render: the scene's 8-wide tree has %u levels, the pool kernel's stack holds %d: walking the 4-wide tree", b.depth8, (int)RL_POOL8_MAXLEVELS);
+			}
+			p.lstack = RL_POOL_SHORT_LSTACK;
+			return p;
+		}
+		p.lstack = p.stack;
+		if (p.stack == 32 && poolK == 2) {
+			if (k.poolShortStack == 4) p.lstack = 4;
+			else if (k.poolShortStack >= 0 ? k.poolShortStack != 0 : b.depth <= RL_POOL_SHORT_MAXDEPTH) p.lstack = RL_POOL_SHORT_LSTACK;
+		}
+		return p;
+	}
+
+	// k_trace walks the 4-wide tree too when the scene has one whose worst-case stack fits the instance's LDS stack: on float boxes if the scene carries them
+	// (small scenes, where the grid's extra arithmetic buys nothing: Cornell frame 22.8 ms on float boxes, 23.8 ms on the grid), else on the grid nodes
+	const bool floatBoxes = hasNodes4 && ntri < RL_FLOAT_BOX_MAX_TRIS;
+	const bool wide = !p.prims && hasNodes4 && b.stackNeed4 <= (uint32_t)p.stack && k.bvh4 != 0;
+	p.tree = !wide ? TREE_BVH2 : floatBoxes ? TREE_BOX4 : TREE_GRID4;
+	p.treeWidth = wide ? 4 : 2;
+	p.keepNodes4 = p.tree == TREE_GRID4;
+	p.keepNodes4f = p.tree == TREE_BOX4;
+	// the whole scene in LDS when it fits the fixed layout (rl_device.h RL_LDS_*); RAYLIB_LDS_SCENE=0 keeps it in global memory
+	if (p.stack == 16 && p.tree == TREE_BOX4 && k.ldsScene != 0 && b.nodes4.size() <= RL_LDS_MAXNODES && ntri <= RL_LDS_MAXTRIS && sc.materials.size() <= RL_LDS_MAXMATS) {
+		p.lds = 1;
+		// ... and a scene of few leaves without a tree (rl_bvh.cc "the leaf list"); RAYLIB_LEAF_LIST=0 walks its BVH4 instead.  Its sortable keys are entry
+		// distances, never negative (rl_render.hip TraverseLeafList): not with rayTMin < 0.
+		if (!b.leafList.empty() && b.leafList.size() <= RL_LEAFLIST_RECORDS && ntri <= RL_LEAFLIST_MAXTRIS && k.leafList != 0 && st.rayTMin >= 0.0f) {
+			p.lds = 2; p.tree = TREE_NONE; p.treeWidth = 0;
+			// the instance without the texture, cut-out and sky code computes the same values in the same order for the scenes it takes: those without a texture
+			// slot or a cut-out leaf (ScenePlain) rendered without a sky image.  RAYLIB_PLAIN_KERNEL=0 keeps the general instance.
+			p.plain = !hasSky && k.plainKernel != 0 && ScenePlain(sc);
+		}
+	}
+	return p;
+}
+
+} // namespace
+
+int32_t EagerTree(const Scene& sc)
+{
+	RendererSettings st = {};
+	st.renderMode = RAYLIB_RENDERMODE_Default;
+	const TracePlan d = Pick(sc, st, false, RenderKnobs(), false);
+	return (d.tree == TREE_GRID4 || d.tree == TREE_WIDE8) ? d.tree : TREE_NONE;
+}
+
+TracePlan PlanTrace(const Scene& sc, const RendererSettings& st, bool hasSky, const RenderKnobs& knobs)
+{
+	TracePlan p = Pick(sc, st, hasSky, knobs, true);
+	p.eagerTree = EagerTree(sc);
+	return p;
+}
+
+LaunchPlan PlanLaunch(uint32_t numLocalCells, uint32_t numActive, uint32_t spp, uint32_t sampleBegin, int numCUs, int workgroupsPerCU,
+                      const TracePlan& trace, const RenderKnobs& k)
+{
+	LaunchPlan L;
+	// sample batches: one launch per <= 16 GiB of sample buffer (288 GB of HBM: few, large launches -- every launch pays its ramp-up and its tail once;
+	// measured on the 298 k-triangle scene at 128 spp: 1 launch 61.3 ms, 2 launches 68.9, 4 launches 90.1)
+	const size_t perSample = (size_t)numLocalCells * 64u * sizeof(SampleRGB);
+	const size_t capBytes = (size_t)(k.sampleBufferGiB > 0 ? k.sampleBufferGiB : 16) << 30;
+	L.batch = (uint32_t)std::max<size_t>(1, std::min<size_t>(spp, perSample ? capBytes / perSample : spp));
+	if (k.sampleBatch > 0) L.batch = std::min<uint32_t>((uint32_t)k.sampleBatch, spp);
+	L.sampleCount = sampleBegin < spp ? std::min(L.batch, spp - sampleBegin) : 0;
+	const uint32_t pathsPerThread = trace.poolK > 0 ? (uint32_t)trace.poolK : 1u;
+	const int perCU = k.blocksPerCU > 0 ? k.blocksPerCU : std::max(1, workgroupsPerCU);
+	const uint64_t jobs64 = (uint64_t)numActive * L.sampleCount * 64u;
+	L.jobs = jobs64;
+	L.blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)numCUs * perCU, (jobs64 + RL_BLOCK * pathsPerThread - 1) / (RL_BLOCK * pathsPerThread)));
+	L.stackStride = L.blocks * RL_BLOCK * pathsPerThread;
+	const bool leafList = trace.poolK == 0 && trace.lds == 2;
+	{   // jobs per global atomic: ~1/16 of a wave's share, rounded to a multiple of 64 (one cell at one sample), 64..1024.
+		// Measured on the slice one of 8 ranks renders of the 1080p x 64 spp Cornell frame (16.6 M jobs): 64 -> 4.10 ms,
+		// 128 -> 3.62, 256 -> 3.45, 512 -> 3.53, 1024 -> 4.07; on the whole frame 1024 is best (64 -> 33.6 ms: the atomic saturates).
+		const uint64_t waves = (uint64_t)L.blocks * (RL_BLOCK / 64);
+		uint64_t chunk = ((jobs64 / (waves * 16)) + 32) & ~63ull;
+		if (k.jobChunk >= 0) chunk = (uint64_t)k.jobChunk;
+		L.jobChunk = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(64, chunk));
+		// The pool schedule's jobs differ by two orders of magnitude (a cell that misses the scene's root box against one full of geometry): the launch's
+		// tail is what a wave needs for its LAST chunk, and on the 298 k-triangle frame a chunk of 1024 heavy jobs is 6 ms of a 45 ms launch (wave timeline,
+		// tools/gpu_timeline_pool.py: first wave out of jobs at 39.7 ms, last at 46.0).  One head took chunks no smaller than 1024 (256: 48.1 ms, the atomic's
+		// queue); with a head per XCD 256 is the best: 1024 -> 46.5 ms, 512 -> 45.0, 256 -> 44.0, 128 -> 44.0, 64 -> 48.4 (one head, 1024: 44.9).
+		if (trace.poolK > 0 && k.jobChunk < 0) {
+			const uint32_t h = k.jobHeads > 0 ? (uint32_t)k.jobHeads : RL_MAX_HEADS;
+			if (h >= 4) L.jobChunk = std::min<uint32_t>(L.jobChunk, 256u);
+			// ... and with the cells that cannot see the scene out of the list (CullCells) every job is a heavy one and there are far fewer of them: 128
+			// as long as that stays under ~400 k draws per launch (298 k frame, 29 M jobs: 256 -> 37.75 ms, 128 -> 37.25, 64 -> 37.2, 512 -> 38.7)
+			if (h >= 4 && numActive < numLocalCells && jobs64 / 128u <= 400000u) L.jobChunk = std::min<uint32_t>(L.jobChunk, 128u);
+		}
+		// the leaf-list kernel's chunk belongs to a workgroup, whose four waves draw batches of 64 from it (RL_QUEUE_SHARED_CHUNK): four waves' worth, 1024 at most
+		if (RL_QUEUE_SHARED_CHUNK && leafList && k.jobChunk < 0) L.jobChunk = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(256, 4 * chunk));
+		// a chunk is whole batches of 64 jobs (one cell at one sample: DecodeJobBatch decodes base >> 6, TakeJobs packs the head's number into the low
+		// bits of a band's job count) whatever the environment asked for
+		L.jobChunk = std::max(64u, L.jobChunk & ~63u);
+	}
+	{   // the job list in bands of whole cells, one head per XCD (rl_render.hip TakeJobs)
+		uint32_t heads = k.jobHeads > 0 ? std::min<uint32_t>(RL_MAX_HEADS, (uint32_t)k.jobHeads) : RL_MAX_HEADS;
+		const uint32_t cellsPerHead = (std::max(1u, numActive) + heads - 1) / heads;
+		heads = (std::max(1u, numActive) + cellsPerHead - 1) / cellsPerHead;   // no empty band: every head's first job exists (and h * jobsPerHead < numJobs < 2^32)
+		L.heads = heads; L.jobsPerHead = cellsPerHead * L.sampleCount * 64u;
+		// guided draws at the end of a band: 2^shift ~ twice the drawers per head (waves; workgroups in the leaf-list kernel, whose chunk is shared)
+		const bool perBlockChunk = RL_QUEUE_SHARED_CHUNK && leafList;
+		const uint32_t drawers = std::max(1u, L.blocks * (perBlockChunk ? 1u : (uint32_t)(RL_BLOCK / 64)) / heads);
+		uint32_t shift = 1; while ((1u << shift) < 2u * drawers && shift < 24u) ++shift;
+		// measured: no gain on either bench workload -- a heavy chunk drawn three rounds before the end outlasts the guided ones
+		L.guideShift = k.guided > 0 ? shift + (uint32_t)(k.guided - 1) : 0u;
+	}
+	return L;
+}
+
+} // namespace rl

@@ -1,0 +1,59 @@
+// Which megakernel instance a render launches, on which tree, and how its job list is laid out: host facts in, plain structs out,
+// no HIP calls (rl_plan.cc).  rl_runtime.inl launches what these say; RaylibAMD_PlanRender exposes them to the tests.
+#pragma once
+
+#include "rl_host.h"
+
+namespace rl {
+
+#define RL_POOL_DEFAULT_MIN_TRIS 256u   /* triangles from which the pool schedule is the default (RAYLIB_POOL_MIN_TRIS) */
+#define RL_FLOAT_BOX_MAX_TRIS 4096u     /* scenes below this many triangles carry the float-box wide nodes (and the leaf list) on the device */
+
+// The per-render switches of INTEGRATION.md, read from the environment by ReadRenderKnobs() on every render (tests change them between renders).
+// A default-constructed RenderKnobs is "nothing set".  -1: not set; the 0 / 1 switches hold atoi(value) != 0.
+struct RenderKnobs {
+	int pool = -1;                                // RAYLIB_POOL: 0 (k_trace), 2, 3 or 4 (any other value: 0)
+	uint32_t poolMinTris = RL_POOL_DEFAULT_MIN_TRIS;   // RAYLIB_POOL_MIN_TRIS
+	int poolShortStack = -1;                      // RAYLIB_POOL_SHORT_STACK: 0, 4 (tests: nearly every push overflows) or 1 (any other value)
+	int bvh4 = -1, bvh8 = -1;                     // RAYLIB_BVH4, RAYLIB_BVH8
+	int ldsScene = -1, leafList = -1, plainKernel = -1;   // RAYLIB_LDS_SCENE, RAYLIB_LEAF_LIST, RAYLIB_PLAIN_KERNEL
+	int sampleBatch = 0, sampleBufferGiB = 0;     // RAYLIB_SAMPLE_BATCH, RAYLIB_SAMPLE_BUFFER_GIB (0: not set or not positive)
+	int jobChunk = -1;                            // RAYLIB_JOB_CHUNK: max(0, value)
+	int jobHeads = 0;                             // RAYLIB_JOB_HEADS: max(1, value); 0: not set
+	int guided = 0;                               // RAYLIB_GUIDED
+	int blocksPerCU = 0;                          // RAYLIB_BLOCKS_PER_CU (0: not set or not positive)
+	int cullCells = 1;                            // RAYLIB_CULL_CELLS (rl_cull.cc reads it for itself; the runtime keys its cached cell lists on it)
+};
+RenderKnobs ReadRenderKnobs();
+
+enum PlanTree : int32_t { TREE_NONE = 0, TREE_BVH2 = 1, TREE_BOX4 = 2, TREE_GRID4 = 3, TREE_WIDE8 = 4 };
+
+struct TracePlan {
+	bool ok = true;             // false: the BVH is deeper than any traversal stack (logged)
+	bool pathTrace = true;      // false: a debug render mode, k_aov<stack, prims> on the BVH2
+	int stack = 16;             // the instance's STACK
+	bool prims = false;         // spheres or cubes
+	int poolK = 0;              // 0: k_trace (one path per lane); K: k_trace_pool with 64 K paths per wave
+	int32_t tree = TREE_BVH2;   // what the walk reads (TREE_NONE: the leaf list)
+	int lstack = 0;             // pool: entries of the traversal stack in LDS
+	int lds = 0;                // k_trace: 0, 1 = the scene in LDS, 2 = the leaf list
+	bool plain = false;         // the leaf-list kernel's instance without texture, cut-out and sky code
+	uint32_t pathsPerWave = 64, treeWidth = 2, nodeBytes = 64;   // RaylibAMDStats
+	bool keepNodes4 = true, keepNodes4f = true;   // the launch's view keeps the grid / float-box wide nodes (k_trace tells the tree by which is set)
+	int32_t eagerTree = TREE_NONE;   // the wide tree UploadScene puts on the device (TREE_GRID4, TREE_WIDE8 or none): the default plan's
+};
+// sc is finalized; hasSky: the render has a sky image (sc.sky of non-zero size)
+TracePlan PlanTrace(const Scene& sc, const RendererSettings& st, bool hasSky, const RenderKnobs& knobs);
+int32_t EagerTree(const Scene& sc);   // = PlanTrace(sc, <a path-traced render>, false, RenderKnobs()).eagerTree
+
+struct LaunchPlan {
+	uint32_t batch = 1;         // samples per launch
+	uint32_t sampleCount = 0;   // of this launch (from sampleBegin)
+	uint64_t jobs = 0;          // numActive * sampleCount * 64
+	uint32_t blocks = 1, stackStride = 0, jobChunk = 64, heads = 1, jobsPerHead = 0, guideShift = 0;
+};
+// One launch of a path-traced render: numActive of the rank's numLocalCells cells are in the job list, samples from sampleBegin; workgroupsPerCU as the occupancy query gave it.
+LaunchPlan PlanLaunch(uint32_t numLocalCells, uint32_t numActive, uint32_t spp, uint32_t sampleBegin, int numCUs, int workgroupsPerCU,
+                      const TracePlan& trace, const RenderKnobs& knobs);
+
+} // namespace rl

@@ -56,7 +56,6 @@ __shared__ double rlm_lds_tab[80];
 
 namespace rl {
 
-#define RL_BLOCK 256
 #ifndef RL_POOL_NODEPTR_VGPR
 #define RL_POOL_NODEPTR_VGPR 1   /* 298 k-triangle frame 43.0 -> 42.6 ms */
 #endif
@@ -230,22 +229,13 @@ __device__ __forceinline__ Mat LoadMat(const DSceneView& S, int i)
 // through the vector memory pipeline (TA / L1 / L2), which sixteen waves per CU keep busy with 64-address gathers.
 #define RL_LDS_ROOT   0
 #define RL_LDS_NODES  4
-#ifndef RL_LDS_MAXNODES
-#define RL_LDS_MAXNODES 32
-#endif
 #ifndef RL_LDS_NSTRIDE
 #define RL_LDS_NSTRIDE 8   /* float4 per node record (8 = packed) */
 #define RL_LDS_TSTRIDE 4   /* float4 per triangle record, both arrays */
 #endif
 #define RL_LDS_ISECT  (RL_LDS_NODES + RL_LDS_MAXNODES * RL_LDS_NSTRIDE)
-#ifndef RL_LDS_MAXTRIS
-#define RL_LDS_MAXTRIS 128
-#endif
 #define RL_LDS_SHADE  (RL_LDS_ISECT + RL_LDS_MAXTRIS * RL_LDS_TSTRIDE)
 #define RL_LDS_MATS   (RL_LDS_SHADE + RL_LDS_MAXTRIS * RL_LDS_TSTRIDE)
-#ifndef RL_LDS_MAXMATS
-#define RL_LDS_MAXMATS 32
-#endif
 #define RL_LDS_TOTAL  (RL_LDS_MATS + RL_LDS_MAXMATS * 5)
 // The leaf-list kernel (LDS == 2) has its own layout: six records of leaf boxes instead of a tree, at most 108 triangles, and an intersection
 // record of SIX float4 that holds what the triangle test would otherwise recompute per test -- the edges u = v1 - v0, v = v2 - v0 (triangle.cc:30-31)
@@ -261,7 +251,7 @@ template <int LDS> struct LdsAt {
 	static constexpr int TOTAL = MATS + RL_LDS_MAXMATS * 5;
 };
 
-// PLAIN (k_trace's instance for scenes without a texture slot, rl_runtime.inl PlainLeafList): the record in LDS is the first four float4 of the
+// PLAIN (k_trace's instance for scenes without a texture slot, rl_plan.cc): the record in LDS is the first four float4 of the
 // material (RL_LDS_MSTRIDE), and every texture slot is the constant -1 -- what each slot of such a scene holds, or another negative number, which every
 // reader takes the same way (tex >= 0 is "textured") -- so that the texture branches of the shading code fold away with their calls.
 #define RL_LDS_MSTRIDE(plain) ((plain) ? 4 : 5)
@@ -595,7 +585,7 @@ __device__ __forceinline__ bool Traverse(const DSceneView& S, V3 o, V3 d, float 
 }
 
 // ---- one step on the wide tree: entry distances t0..t3 (INFINITY: not entered) of the four children of S.nodes4[cur] ----
-// RL_Q4 (default): the 64-byte grid node (DNode4Q).  The planes are never decoded: with A = step * inv and B = (origin - o) * inv
+// The 64-byte grid node (DNode4Q).  The planes are never decoded: with A = step * inv and B = (origin - o) * inv
 // per axis, plane q's parameter is fma(q, A, B) -- one v_cvt_f32_ubyte and one v_fma per plane, four 16-byte loads per lane instead
 // of seven.  The fused form rounds differently from the reference's (bound - o) * inv, by at most (|B| + 255 |A|) * 2^-23 in
 // absolute terms (cancellation when the ray starts inside the node); four times that bound widens every slab -- near planes earlier,
@@ -664,7 +654,7 @@ __device__ __forceinline__ uint4 GLoadU4(const void* p, int i) { const rl_v4u v 
 // test, with an out-of-line walk that applies it per candidate for the lane whose winner fails it.  Sound -- the search finds the nearest of a larger set, and
 // a winner that passes the rule is the nearest of the smaller one too -- and 0.5 % faster, but the call made the register allocator keep the 24 keys in
 // scratch memory: 28 GB of spill traffic per frame, three times everything else the kernel moves.)
-// PLAIN: no leaf carries the cut-out bit (rl_runtime.inl PlainLeafList), so the walk does not test it.
+// PLAIN: no leaf carries the cut-out bit (rl_plan.cc), so the walk does not test it.
 template <bool ANYHIT, bool PLAIN = false>
 __device__ __forceinline__ bool TraverseLeafList(const DSceneView& S, V3 o, V3 d, float tMin, HitRec& best, Counters& c, const float4* sm)
 {
@@ -1294,7 +1284,7 @@ __device__ __forceinline__ void PixelUV(const DRenderParams& P, uint32_t x, uint
 struct SkyRot { float m0[3], m1[3], m2[3]; };   // Rotator(yaw 90).rotate rows, computed on the host (renderer.cc:166-168)
 
 // Miss shader: sky panorama + sun (reference render/renderer.cc:155-199)
-// PLAIN: the launch has no sky image (rl_runtime.inl PlainLeafList), and the panorama lookup is compiled out
+// PLAIN: the launch has no sky image (rl_plan.cc), and the panorama lookup is compiled out
 template <int STACK, bool PRIMS, bool FULL, int LDS = 0, bool PLAIN = false>
 __device__ __forceinline__ V3 MissShader(const DSceneView& S, const SkyRot& R, V3 o, V3 d, float rayTime, float rayTMin, int* stk, Counters& c, const float4* sm = nullptr)
 {
@@ -1322,8 +1312,6 @@ __device__ __forceinline__ V3 MissShader(const DSceneView& S, const SkyRot& R, V
 	return missResult;
 }
 
-// one path's radiance in the sample buffer: 12 bytes (the buffer is written once and read once per sample: a fourth float would be a quarter more of both)
-struct SampleRGB { float x, y, z; };
 __device__ __forceinline__ SampleRGB make_sample(float x, float y, float z) { SampleRGB s; s.x = x; s.y = y; s.z = z; return s; }
 
 // job -> (local cell, sample, pixel in cell) -> image coordinates
@@ -1390,7 +1378,6 @@ __device__ __forceinline__ JobPixel DecodeJobBatch(const DRenderParams& P, uint3
 // Results cannot depend on any of this: streams are keyed by (seed, pixel, sample).
 // The reference's analogue is the single LIFO work queue of core/thread_pool.cc:93-112.
 #define RL_HEAD_STRIDE 32u   /* uint32 words between two heads (128 B: one L2 line each) */
-#define RL_MAX_HEADS 8u
 __device__ __forceinline__ uint32_t XccId()
 {
 	return (uint32_t)__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u;   // GETREG_IMMED(size - 1 = 3, offset 0, XCC_ID = 20): bits 3:0 of XCC_ID
@@ -1455,9 +1442,6 @@ __device__ __forceinline__ void WaveLdsSync()
 // ---------------------------------------------------------------------------
 // The megakernel.  samples: [sampleCount][numLocalCells*64] SampleRGB.
 // pathStack: [maxPathLength][stackStride] records of 2 float4 (refl.xyz, sp | pdf, E.xyz).
-#ifndef RL_QUEUE_SHARED_CHUNK
-#define RL_QUEUE_SHARED_CHUNK 1   /* leaf-list kernel: the workgroup's waves share one job chunk (see the refill) */
-#endif
 #ifndef RL_QUEUE_SPIN_LIMIT
 // 0: a wave waits for the workgroup's chunk until the wave that is refilling it is done (microseconds: one global atomic).  N > 0: after N waits of 128
 // cycles it takes one batch straight from the global counter instead (1: test build that always does; parity-tested).  The bounded form is not the
@@ -1937,10 +1921,6 @@ enum { F_OX = 0, F_OY, F_OZ, F_DX, F_DY, F_DZ, F_T, F_TRI, F_A, F_B, F_TIME, F_C
 #define Q_MISS     (-7)   /* result of a closest-hit query that hit nothing (distinct from Q_CLOSEST: a straggler may deliver it while the next phase is handing out slots) */
 #define Q_CLEAR    (-8)   /* result of a sun query: nothing in the way */
 #define RL_POOL_WIDEN RL_BOX_WIDEN
-#ifndef RL_POOL_SHORT_LSTACK
-#define RL_POOL_SHORT_LSTACK 18   /* LDS entries of the "short" 32-deep stack: 18 KiB + 20.5 KiB pool + 640 B of libm tables = 4 workgroups per CU */
-#endif
-#define RL_POOL_SHORT_MAXDEPTH 24 /* BVH depth up to which the short variant is used (deeper trees overflow too often: measured) */
 #ifndef RL_POOL_MAXBLOCKS
 #define RL_POOL_MAXBLOCKS 4   /* workgroups per CU the pool kernel is compiled for (register budget 512 / (4 * blocks) per lane) */
 #endif
@@ -2059,19 +2039,15 @@ __device__ __forceinline__ bool NodeStep(const DSceneView& S, Trav& T, float tMi
 	if (hr) { T.cur = k.y; return false; }
 	return PopOrFinish<LSTACK, STACK>(T, stk, ovf);
 }
-// One step on the BVH4 (DNode4, 128 B): four slab tests, the hit children ordered by entry distance (5-comparator network),
-// the nearest followed, the others pushed far-to-near.  Counts as two 64-byte node records.
+// One step on the BVH4 (grid nodes, DNode4Q, 64 B): four slab tests, the hit children ordered by entry distance (5-comparator network),
+// the nearest followed, the others pushed far-to-near.
 template <int LSTACK, int STACK>
 __device__ __forceinline__ bool NodeStep4(const DSceneView& S, Trav& T, float tMin, int* stk, int* ovf, Counters& c)
 {
 	RL_WSTEP(4);
-	c.nodes += RL_Q4 ? 1 : 2;   // 64-byte records fetched
+	c.nodes += 1;   // 64-byte records fetched
 	const float tmx = ClampToFltMax(T.best.t);
-#if RL_Q4
 	RL_WIDE_STEP_Q(S, T.cur, T.o, T.inv, T.nx, T.ny, T.nz, tMin, tmx, RL_POOL_WIDEN, t0, t1, t2, t3, ch)   // T.inv was clamped when the ray was fetched
-#else
-	RL_WIDE_STEP_F((const float4*)(S.nodes4f + T.cur), T.o, T.inv, T.nx, T.ny, T.nz, tMin, tmx, RL_POOL_WIDEN, t0, t1, t2, t3, ch)
-#endif
 	int r0 = ch.x, r1 = ch.y, r2 = ch.z, r3 = ch.w;
 	if (r0 == DNODE_EMPTY) t0 = INFINITY;
 	if (r1 == DNODE_EMPTY) t1 = INFINITY;
@@ -2142,7 +2118,7 @@ __device__ __forceinline__ bool LeafStep(const DSceneView& S, Trav& T, float tMi
 __device__ __forceinline__ void Push8(Trav& T, int* stk, int* ovf, const int G, const int GMAX)
 {
 	if (T.sp < G) { stk[(2 * T.sp) * RL_BLOCK] = (int)T.gx; stk[(2 * T.sp + 1) * RL_BLOCK] = (int)T.gy; ++T.sp; }
-	else if (T.sp < GMAX) { ovf[2 * (T.sp - G)] = (int)T.gx; ovf[2 * (T.sp - G) + 1] = (int)T.gy; ++T.sp; }   // (GMAX = RL_POOL8_MAXLEVELS: the host selects this walk only for trees of at most that many levels, rl_runtime.inl SelectTraceKernel)
+	else if (T.sp < GMAX) { ovf[2 * (T.sp - G)] = (int)T.gx; ovf[2 * (T.sp - G) + 1] = (int)T.gy; ++T.sp; }   // (GMAX = RL_POOL8_MAXLEVELS: the host selects this walk only for trees of at most that many levels, rl_plan.cc)
 }
 // what comes next for a lane whose triangles are done: the rest of its group, else the stack's top group, else nothing (true: the ray is finished)
 __device__ __forceinline__ bool Next8(Trav& T, int* stk, int* ovf, const int G)
@@ -2331,7 +2307,7 @@ template <int LSTACK, bool PRIMS, int K> struct PoolOcc {
 };
 
 // STACK: capacity of the traversal stack; LSTACK <= STACK: how much of it lives in LDS (the rest is private overflow)
-// WIDE: 0 the BVH2; 1 the BVH4 (S.nodes4: 64-byte grid nodes; RL_Q4 = 0: float boxes); 3 the 8-wide tree (S.nodes8; STACK / LSTACK then count words: two per group)
+// WIDE: 0 the BVH2; 1 the BVH4 (S.nodes4: 64-byte grid nodes); 3 the 8-wide tree (S.nodes8; STACK / LSTACK then count words: two per group)
 template <int STACK, bool PRIMS, int K, int LSTACK = STACK, int WIDE = 0>
 __global__ void __launch_bounds__(RL_BLOCK, (PoolOcc<LSTACK, PRIMS, K>::kBlocks))
 k_trace_pool(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB* __restrict__ samplesK,
@@ -2596,7 +2572,7 @@ k_trace_pool(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, Sampl
 							T.d = T.anyhit ? -ld3(S.sunDirection) : v3(pool[F_DX][slot], pool[F_DY][slot], pool[F_DZ][slot]);
 							T.rayTime = PRIMS ? pool[F_TIME][slot] : 0.0f;
 							T.inv = v3(FastRcp(T.d.x), FastRcp(T.d.y), FastRcp(T.d.z));
-							if ((WIDE && RL_Q4) || WIDE == 3) T.inv = ClampInv(T.inv);   // only the grid nodes' fused plane arithmetic wants finite reciprocals; Slab() relies on +-inf / NaN
+							if (WIDE) T.inv = ClampInv(T.inv);   // only the grid nodes' fused plane arithmetic wants finite reciprocals; Slab() relies on +-inf / NaN
 							T.nx = T.inv.x < 0.0f; T.ny = T.inv.y < 0.0f; T.nz = T.inv.z < 0.0f;
 							T.best.t = INFINITY; T.best.tri = -1; T.best.a = 0.0f; T.best.b = 0.0f;
 							T.cur = 0; T.sp = 0; T.leafI = 0;
@@ -2797,7 +2773,7 @@ k_trace_pool(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, Sampl
 	}
 }
 #endif
-// The instances the runtime selects from (rl_runtime.inl SelectTraceKernel): defined in rl_render_pool.hip's translation unit, referenced from this one.
+// The instances the runtime selects from (rl_runtime.inl KernelFor): defined in rl_render_pool.hip's translation unit, referenced from this one.
 #define RL_POOL_INSTANCES(X) \
 	X(16, false, 2, 16, 0) X(16, false, 3, 16, 0) X(16, false, 4, 16, 0) X(32, false, 2, 32, 0) X(32, false, 3, 32, 0) X(32, false, 4, 32, 0) \
 	X(32, false, 2, 4, 0) X(32, false, 2, RL_POOL_SHORT_LSTACK, 0) \

@@ -12,6 +12,10 @@
 // new arguments.  RAYLIB_GPU_MAP = "d0,d1,..." names the physical device of every logical rank; naming one device
 // several times (e.g. "0,0,0,0") runs the whole N-rank path on one GPU, which is how the GPU test suite covers it.
 // RAYLIB_GATHER_SELF=1 (tests) sends rank 0's own cells through the gather mechanism too.
+//
+// Which kernel instance a render launches, on which tree, and its job layout are decided in rl_plan.cc; this file launches what it says.
+
+#include "rl_plan.h"
 
 namespace rl {
 
@@ -36,11 +40,8 @@ struct DeviceSceneCopy {
 struct DeviceScene {
 	std::vector<DeviceSceneCopy*> copy;   // by device slot (Runtime::devices)
 	SkyRot skyRot;
-	uint32_t bvhDepth = 0, stackNeed4 = 0;
-	bool hasNodes4 = false, hasNodes8 = false; uint32_t depth8 = 0; float sahNodes4 = 0.0f;
 	double boundsMin[3] = { 0, 0, 0 }, boundsMax[3] = { 0, 0, 0 };   // of all triangle vertices (CullCells)
 	bool boundsValid = false;                                        // triangles only, every coordinate finite
-	bool plain = false;                                              // ScenePlain: no texture slot, no cut-out leaf (PlainLeafList)
 };
 
 namespace {
@@ -279,24 +280,21 @@ bool Upload(T*& dst, const T* src, size_t count)
 	return true;
 }
 
-#define RL_BVH8_MIN_STEPS 40.0f
-#define RL_POOL_DEFAULT_MIN_TRIS 256u
-// what SelectTraceKernel's default choice comes to for a scene (no environment overrides): the pool schedule on the 8-wide tree
-static bool Walks8ByDefault(const DeviceScene* D, size_t numTriangles)
+// the wide tree a render is about to walk (TracePlan::tree), on this rank's device: UploadScene puts the default plan's there (TracePlan::eagerTree), the other
+// follows the first time a render asks for it.  The copy's pointers are set only once the tree is there.
+template <typename T>
+static bool UploadOnce(T*& have, const T*& inView, const std::vector<T>& src)
 {
-	return D->hasNodes8 && D->depth8 <= RL_POOL8_MAXLEVELS && D->sahNodes4 >= RL_BVH8_MIN_STEPS && numTriangles >= RL_POOL_DEFAULT_MIN_TRIS;
+	if (have || src.empty()) return true;
+	T* p = nullptr;
+	if (!Upload(p, src.data(), src.size())) { if (p) (void)hipFree(p); return false; }
+	have = p; inView = p;
+	return true;
 }
-// the wide tree a render is about to walk, on this rank's device (uploaded with the scene only when it is the default choice)
-static bool EnsureWideTree(DeviceSceneCopy* C, const Scene& sc, int width, bool gridNodes)
+static bool EnsureWideTree(DeviceSceneCopy* C, const Scene& sc, int32_t tree)
 {
-	if (width == 8 && !C->nodes8 && !sc.bvh.nodes8.empty()) {
-		if (!Upload(C->nodes8, sc.bvh.nodes8.data(), sc.bvh.nodes8.size())) return false;
-		C->view.nodes8 = C->nodes8;
-	}
-	if (width == 4 && gridNodes && RL_Q4 && !C->nodes4 && !sc.bvh.nodes4q.empty()) {
-		if (!Upload(C->nodes4, sc.bvh.nodes4q.data(), sc.bvh.nodes4q.size())) return false;
-		C->view.nodes4 = C->nodes4;
-	}
+	if (tree == TREE_WIDE8) return UploadOnce(C->nodes8, C->view.nodes8, sc.bvh.nodes8);
+	if (tree == TREE_GRID4) return UploadOnce(C->nodes4, C->view.nodes4, sc.bvh.nodes4q);
 	return true;
 }
 void FreeCopy(DeviceSceneCopy* C)
@@ -439,8 +437,6 @@ bool UploadScene(Scene& sc)
 	}
 
 	DeviceScene* D = new DeviceScene;
-	D->plain = ScenePlain(sc);
-	D->bvhDepth = sc.bvh.depth; D->stackNeed4 = sc.bvh.stackNeed4; D->hasNodes4 = !sc.bvh.nodes4.empty(); D->hasNodes8 = !sc.bvh.nodes8.empty(); D->depth8 = sc.bvh.depth8; D->sahNodes4 = sc.bvh.sahNodes4;
 	{   // Rotator(yaw = 90).rotate rows, reference geom/transform.cc:47-65 (host libm, as the reference)
 		const float pi_f = (float)3.1415926535897932385;
 		const float ry = 90.0f * pi_f / 180.0f, rp = 0.0f * pi_f / 180.0f, rr = 0.0f * pi_f / 180.0f;
@@ -464,6 +460,11 @@ bool UploadScene(Scene& sc)
 			D->boundsValid = ok;
 		}
 	}
+	// the float-box wide nodes (and the leaf list) for scenes small enough to stay in the caches (k_trace's class); of the two wide trees the pool schedule can walk, the
+	// one the default plan walks goes to the device now, the other follows when a render asks for it (EnsureWideTree: the switches are read per render).  A 10 M-triangle
+	// scene keeps 190 MB of nodes per device instead of 290.
+	const bool wantFull = !sc.bvh.nodes4.empty() && n < RL_FLOAT_BOX_MAX_TRIS;
+	const int32_t eager = EagerTree(sc);
 	for (size_t slot = 0; slot < g_rt.devices.size(); ++slot) {
 		DeviceSceneCopy* C = new DeviceSceneCopy;
 		C->device = g_rt.devices[slot];
@@ -471,15 +472,8 @@ bool UploadScene(Scene& sc)
 		D->copy.push_back(C);
 		bool ok = hipSetDevice(C->device) == hipSuccess;
 		ok = ok && Upload(C->nodes, sc.bvh.nodes.data(), sc.bvh.nodes.size());
-		// the grid nodes for the pool schedule; the float-box nodes for scenes small enough to stay in the caches (k_trace's class),
-		// where the grid's extra arithmetic buys nothing (Cornell frame: 22.8 ms on float boxes, 23.8 ms on the grid)
-		const bool wantFull = D->hasNodes4 && (!RL_Q4 || sc.triangles.size() < 4096);
-		// Of the two wide trees the pool schedule can walk, the one its default choice walks (SelectTraceKernel: the 8-wide tree for scenes whose rays are expected to take
-		// many steps) goes to the device now; the other follows the first time a render asks for it (EnsureWideTree: RAYLIB_BVH8 / RAYLIB_BVH4 / RAYLIB_POOL are read
-		// per render).  A 10 M-triangle scene keeps 190 MB of nodes per device instead of 290.
-		const bool walks8 = Walks8ByDefault(D, sc.triangles.size());
-		if (ok && D->hasNodes4 && RL_Q4 && !walks8) ok = Upload(C->nodes4, sc.bvh.nodes4q.data(), sc.bvh.nodes4q.size());
-		if (ok && D->hasNodes8 && walks8) ok = Upload(C->nodes8, sc.bvh.nodes8.data(), sc.bvh.nodes8.size());
+		if (ok && eager == TREE_GRID4) ok = Upload(C->nodes4, sc.bvh.nodes4q.data(), sc.bvh.nodes4q.size());
+		if (ok && eager == TREE_WIDE8) ok = Upload(C->nodes8, sc.bvh.nodes8.data(), sc.bvh.nodes8.size());
 		if (ok && wantFull) ok = Upload(C->nodes4f, sc.bvh.nodes4.data(), sc.bvh.nodes4.size());
 		if (ok && wantFull && !sc.bvh.leafList.empty()) ok = Upload(C->leafList, sc.bvh.leafList.data(), sc.bvh.leafList.size());
 		ok = ok && Upload(C->isect, isect.data(), n) && Upload(C->shade, shade.data(), n);
@@ -533,66 +527,41 @@ bool SyncSky(Scene& sc)
 }
 
 typedef void (*TraceKernel)(const DRenderParams, const DSceneView, const SkyRot, SampleRGB*, float*, unsigned long long*, unsigned int*);
+typedef void (*AovKernel)(const DRenderParams, const DSceneView, float4*, unsigned long long*);
 
-// The leaf-list kernel (k_trace<16, false, true, 2>: a scene of few leaves, in LDS) has a PLAIN instance without the texture, cut-out and sky code, which
-// computes the same values in the same order for the scenes it takes: those without a texture slot or a cut-out leaf (ScenePlain, once per scene) rendered
-// without a sky image (per render).  RAYLIB_PLAIN_KERNEL=0 keeps the general instance.  Every place that picks or recognises the leaf-list kernel goes
-// through these three.
-static std::atomic<int32_t> g_lastTracePlain{0};   // RaylibAMD_LastTracePlain
-static bool PlainLeafList(const DeviceScene* DS, const DSceneView& v)
-{
-	const char* e = getenv("RAYLIB_PLAIN_KERNEL");
-	return DS->plain && v.sky == nullptr && (e ? atoi(e) != 0 : true);
-}
-static TraceKernel LeafListKernel(bool plain) { return plain ? (TraceKernel)k_trace<16, false, true, 2, true> : (TraceKernel)k_trace<16, false, true, 2>; }
-static bool IsLeafListKernel(TraceKernel k) { return k == LeafListKernel(false) || k == LeafListKernel(true); }
-
-// poolK = 0: k_trace (one path per lane); poolK = K: k_trace_pool with 64*K paths per wave
+// The kernel instance of a plan (rl_plan.cc): the only code that names the instances of k_trace, k_trace_pool and k_aov a render launches.
 template <int STACK, bool PRIMS>
-TraceKernel SelectTraceKernel(int& poolK, const DeviceScene* D, bool& shortStack, int& width)
+static TraceKernel TraceFor(bool floatBoxes) { return floatBoxes ? (TraceKernel)k_trace<STACK, PRIMS, true> : (TraceKernel)k_trace<STACK, PRIMS, false>; }
+static TraceKernel KernelFor(const TracePlan& p)
 {
-	shortStack = false; width = 2;
-	if constexpr (STACK <= 32 && !PRIMS) {
-		const char* e = getenv("RAYLIB_POOL_SHORT_STACK");
-		// the wide tree: default whenever the scene carries one whose worst-case stack fits; RAYLIB_BVH4=0|1 overrides
-		const char* w = getenv("RAYLIB_BVH4");
-		const bool haveWide = D && D->hasNodes4 && D->stackNeed4 <= 64;   // (the pool's node format is a build-time choice: RL_Q4)
-		const bool wantWide = haveWide && (w ? atoi(w) != 0 : true);
-		if (poolK == 2 && wantWide) {
-			width = 4; shortStack = true;
-			if (e && atoi(e) == 0) { shortStack = false; return D->stackNeed4 <= 32 ? (TraceKernel)k_trace_pool<32, PRIMS, 2, 32, 1> : (TraceKernel)k_trace_pool<64, PRIMS, 2, 32, 1>; }
-			// the 8-wide tree (0.67 x the steps of the 4-wide one, each 1.4 x as long) when the scene carries one of at most 16 levels -- a group of hit children per
-			// level is all its stack ever holds -- and its rays are expected to take many steps: measured over rooms and colonnades of 1 k ... 10 M triangles
-			// (tools/gpu_bvh8_sweep.py, profiles/r04_bvh8_sweep.log) the 8-wide walk loses 2 - 8 % below ~30 expected steps of the 4-wide tree (the builder's sum of
-			// node areas over the root's), breaks even between 30 and 42 and wins 3 - 9 % from 59 up.  RAYLIB_BVH8=0|1 overrides the choice.
-			const char* w8 = getenv("RAYLIB_BVH8");
-			const bool want8 = D->hasNodes8 && (w8 ? atoi(w8) != 0 : D->sahNodes4 >= RL_BVH8_MIN_STEPS);
-			if (want8 && D->depth8 <= RL_POOL8_MAXLEVELS) { width = 8; return (TraceKernel)k_trace_pool<2 * RL_POOL8_MAXLEVELS, PRIMS, 2, RL_POOL8_LSTACK, 3>; }
-			if (want8) {   // (the kernel's stack holds one group of hit children per level: a deeper 8-wide tree is not walked, and that is said once per scene)
-				static const DeviceScene* told = nullptr;
-				if (told != D) { told = D; Log("Raylib_Render: the scene's 8-wide tree has %u levels, the pool kernel's stack holds %d: walking the 4-wide tree", D->depth8, (int)RL_POOL8_MAXLEVELS); }
-			}
-			return D->stackNeed4 <= 32 ? (TraceKernel)k_trace_pool<32, PRIMS, 2, RL_POOL_SHORT_LSTACK, 1> : (TraceKernel)k_trace_pool<64, PRIMS, 2, RL_POOL_SHORT_LSTACK, 1>;
-		}
-		if constexpr (STACK == 32) {
-			const bool wantShort = e ? atoi(e) != 0 : D->bvhDepth <= RL_POOL_SHORT_MAXDEPTH;
-			if (poolK == 2 && e && atoi(e) == 4) { shortStack = true; return k_trace_pool<STACK, PRIMS, 2, 4>; }   // tests: nearly every push overflows
-			if (poolK == 2 && wantShort) { shortStack = true; return k_trace_pool<STACK, PRIMS, 2, RL_POOL_SHORT_LSTACK>; }
-		}
-		if (poolK == 2) return k_trace_pool<STACK, PRIMS, 2>;
-		if (poolK == 3) return k_trace_pool<STACK, PRIMS, 3>;
-		if (poolK == 4) return k_trace_pool<STACK, PRIMS, 4>;
+	if (p.poolK > 0) {   // the instances rl_render_pool.hip defines: (STACK, PRIMS, K, LSTACK, WIDE), WIDE 0 the BVH2, 1 the grid nodes, 3 the 8-wide tree
+		const int wide = p.tree == TREE_WIDE8 ? 3 : p.tree == TREE_GRID4 ? 1 : 0;
+#define RL_POOL_PICK(a, b, c, d, e) if (p.stack == a && p.prims == b && p.poolK == c && p.lstack == d && wide == e) return (TraceKernel)k_trace_pool<a, b, c, d, e>;
+		RL_POOL_INSTANCES(RL_POOL_PICK)
+#undef RL_POOL_PICK
+		return nullptr;
 	}
-	poolK = 0;
-	return nullptr;   // k_trace: the caller picks the instantiation for the node format the scene carries
+	if (p.lds == 2) return p.plain ? (TraceKernel)k_trace<16, false, true, 2, true> : (TraceKernel)k_trace<16, false, true, 2>;
+	if (p.lds == 1) return (TraceKernel)k_trace<16, false, true, 1>;
+	const bool full = p.tree == TREE_BOX4;
+	if (p.stack == 16) return TraceFor<16, false>(full);
+	if (p.stack == 32) return p.prims ? TraceFor<32, true>(full) : TraceFor<32, false>(full);
+	return p.prims ? TraceFor<64, true>(full) : TraceFor<64, false>(full);
 }
+static AovKernel AovKernelFor(const TracePlan& p)
+{
+	if (p.stack == 16) return k_aov<16, false>;
+	if (p.stack == 32) return p.prims ? k_aov<32, true> : k_aov<32, false>;
+	return p.prims ? k_aov<64, true> : k_aov<64, false>;
+}
+static std::atomic<int32_t> g_lastTracePlain{0};   // RaylibAMD_LastTracePlain
 
 // What EnqueueRender leaves for FinishRender: everything is queued on the rank's stream, nothing has been waited for.
 struct PendingRender {
 	RankCtx* ctx = nullptr;
 	bool pathTrace = false, lastBatchPending = false;
 	float traceMs = 0.0f;
-	uint32_t launches = 0, schedulePaths = 1, jobHeads = 0, treeWidth = 2;
+	uint32_t launches = 0, jobHeads = 0, pathsPerWave = 64, treeWidth = 2, nodeBytes = 64;   // (the last three: TracePlan's)
 	uint64_t pixels = 0;
 	uint64_t culledSamples = 0; uint32_t culledRaysPerSample = 0, culledSkyTexels = 0;   // camera samples of cells outside the scene's silhouette: reported apart, not traced (CullCells)
 	uint32_t culledCells = 0, listedCells = 0;
@@ -604,12 +573,14 @@ struct PendingRender {
 
 // One rank's share of a render, queued on its stream: counters reset, the megakernel (or k_aov) per sample batch, k_resolve,
 // end event, counter read-back.  `req.outDevice` receives the row-major frame (cellStride 1) or the rank's cells back to back.
-template <int STACK, bool PRIMS>
 bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRender& pend)
 {
 	DeviceScene* DS = sc.device;
 	DeviceSceneCopy* D = DS->copy[(size_t)R.devSlot];
 	const RendererSettings& st = req.settings;
+	const RenderKnobs knobs = ReadRenderKnobs();
+	const TracePlan plan = PlanTrace(sc, st, D->view.sky != nullptr, knobs);
+	if (!plan.ok) return false;
 	const uint32_t W = st.viewportWidth, H = st.viewportHeight;
 	const uint32_t cellsX = (W + 7) / 8, cellsY = (H + 7) / 8, numCells = cellsX * cellsY;
 	const uint32_t stride = req.cellStride ? req.cellStride : 1;
@@ -642,59 +613,17 @@ bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRende
 		// nothing to do for this rank
 	} else if (!pathTrace) {
 		const uint32_t blocks = (numSlots + RL_BLOCK - 1) / RL_BLOCK;
-		hipLaunchKernelGGL((k_aov<STACK, PRIMS>), dim3(blocks), dim3(RL_BLOCK), 0, R.stream, P, D->view, out, R.counters);
+		hipLaunchKernelGGL(AovKernelFor(plan), dim3(blocks), dim3(RL_BLOCK), 0, R.stream, P, D->view, out, R.counters);
 		HIP_OK(hipGetLastError());
 	} else {
-		// sample batches: one launch per <= 16 GiB of sample buffer (288 GB of HBM: few, large launches -- every launch pays its
-		// ramp-up and its tail once; measured on the 298 k-triangle scene at 128 spp: 1 launch 61.3 ms, 2 launches 68.9, 4 launches 90.1)
-		const size_t perSample = (size_t)numSlots * sizeof(SampleRGB);
-		size_t capBytes = (size_t)16 << 30;
-		if (const char* e = getenv("RAYLIB_SAMPLE_BUFFER_GIB")) { const int v = atoi(e); if (v > 0) capBytes = (size_t)v << 30; }
-		uint32_t batch = (uint32_t)std::max<size_t>(1, std::min<size_t>(SPP, capBytes / perSample));
-		if (const char* e = getenv("RAYLIB_SAMPLE_BATCH")) { int v = atoi(e); if (v > 0) batch = std::min<uint32_t>((uint32_t)v, SPP); }
-		if (!Grow(R.samples, R.samplesBytes, perSample * batch)) return false;
-		if (batch < SPP && !Grow(R.accum, R.accumBytes, (size_t)numSlots * sizeof(float4))) return false;
-		// Scheduling of the megakernel: the pool schedule for triangle scenes from RAYLIB_POOL_MIN_TRIS triangles on, else k_trace
-		// (the Cornell class: tens of triangles, shading-bound).  Measured crossover (tools/gpu_crossover.py, tessellated rooms at
-		// 1080p x 16 spp, pool time / k_trace time): 36 triangles 1.07, 144: 0.97, 324: 0.95, 1296: 0.89, 5184: 0.80, 20736: 0.67.
-		// RAYLIB_POOL=0|2|3|4 overrides.
-		uint32_t minTris = RL_POOL_DEFAULT_MIN_TRIS; if (const char* e = getenv("RAYLIB_POOL_MIN_TRIS")) minTris = (uint32_t)atoi(e);
-		int poolK = (STACK <= 32 && !PRIMS && sc.triangles.size() >= minTris) ? 2 : 0;
-		if (const char* e = getenv("RAYLIB_POOL")) poolK = atoi(e);
-		bool shortStack = false; int width = 2;
-		TraceKernel traceKernel = SelectTraceKernel<STACK, PRIMS>(poolK, DS, shortStack, width);
-		// k_trace walks the 4-wide tree too when the scene has one whose worst-case stack fits this instantiation's LDS stack:
-		// on float boxes if the scene carries them (small scenes), else on the grid nodes
-		// (k_trace walks the grid nodes too when the scene carries no float-box ones)
-		if (!EnsureWideTree(D, sc, poolK > 0 ? width : (DS->hasNodes4 ? 4 : 2), poolK > 0 || !D->nodes4f)) return false;
+		const TraceKernel traceKernel = KernelFor(plan);
+		if (!traceKernel) { Log("Raylib_Render: no megakernel instance for STACK %d, K %d, stack in LDS %d", plan.stack, plan.poolK, plan.lstack); return false; }
+		if (!EnsureWideTree(D, sc, plan.tree)) return false;
 		DSceneView traceView = D->view;
-#if !RL_Q4
-		traceView.nodes4 = nullptr;
-#endif
-		if (poolK == 0) {
-			const char* w = getenv("RAYLIB_BVH4");
-			const bool baseWide = !PRIMS && DS->hasNodes4 && DS->stackNeed4 <= (uint32_t)STACK && (w ? atoi(w) != 0 : true);
-			if (!baseWide) { traceView.nodes4 = nullptr; traceView.nodes4f = nullptr; }
-			width = baseWide ? 4 : 2;
-			const bool full = traceView.nodes4f != nullptr;
-			if (full) traceView.nodes4 = nullptr;
-			// the whole scene in LDS when it fits the fixed layout (rl_render.hip RL_LDS_*); RAYLIB_LDS_SCENE=0 keeps it in global memory
-			bool lds = false;
-			if constexpr (STACK == 16 && !PRIMS) {
-				const char* e = getenv("RAYLIB_LDS_SCENE");
-				lds = full && (e ? atoi(e) != 0 : true) && sc.bvh.nodes4.size() <= RL_LDS_MAXNODES && sc.triangles.size() <= RL_LDS_MAXTRIS && sc.materials.size() <= RL_LDS_MAXMATS;
-				// ... and a scene of few leaves without a tree (rl_bvh.cc "the leaf list"); RAYLIB_LEAF_LIST=0 walks its BVH4 instead
-				const char* f = getenv("RAYLIB_LEAF_LIST");
-				const bool flat = lds && traceView.leafList != nullptr && traceView.numLeafRecords <= RL_LEAFLIST_RECORDS && sc.triangles.size() <= RL_LEAFLIST_MAXTRIS && (f ? atoi(f) != 0 : true)
-				                  && st.rayTMin >= 0.0f;   // its sortable keys are entry distances, never negative (rl_render.hip TraverseLeafList)
-				if (flat) { traceKernel = LeafListKernel(PlainLeafList(DS, traceView)); width = 0; }
-				else if (lds) traceKernel = (TraceKernel)k_trace<STACK, PRIMS, true, 1>;
-			}
-			if (!lds) traceKernel = full ? (TraceKernel)k_trace<STACK, PRIMS, true> : (TraceKernel)k_trace<STACK, PRIMS, false>;
-		}
-		g_lastTracePlain.store(traceKernel == LeafListKernel(true) ? 1 : 0, std::memory_order_relaxed);
-		const uint32_t pathsPerThread = poolK > 0 ? (uint32_t)poolK : 1u;
-		pend.schedulePaths = pathsPerThread; pend.treeWidth = (uint32_t)width;
+		if (!plan.keepNodes4) traceView.nodes4 = nullptr;
+		if (!plan.keepNodes4f) traceView.nodes4f = nullptr;
+		g_lastTracePlain.store(plan.plain ? 1 : 0, std::memory_order_relaxed);
+		pend.pathsPerWave = plan.pathsPerWave; pend.treeWidth = plan.treeWidth; pend.nodeBytes = plan.nodeBytes;
 		// ---- cells that cannot see the scene leave the job list (CullCells) ----
 		uint32_t numActive = numLocalCells;
 		{
@@ -702,7 +631,7 @@ bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRende
 			std::vector<unsigned char> key;
 			auto put = [&](const void* ptr, size_t n) { const unsigned char* b = (const unsigned char*)ptr; key.insert(key.end(), b, b + n); };
 			const uint32_t geo[7] = { W, H, req.cellFirst, stride, numLocalCells, (uint32_t)st.maxPathLength, __builtin_bit_cast(uint32_t, st.rayTMin) };
-			const int flags[3] = { traceView.sky ? 1 : 0, traceView.hasSun, getenv("RAYLIB_CULL_CELLS") ? atoi(getenv("RAYLIB_CULL_CELLS")) : 1 };
+			const int flags[3] = { traceView.sky ? 1 : 0, traceView.hasSun, knobs.cullCells };
 			put(&req.camera, sizeof(req.camera)); put(geo, sizeof(geo)); put(flags, sizeof(flags)); put(traceView.sunDirection, sizeof(traceView.sunDirection));
 			put(traceView.sunIlluminance, sizeof(traceView.sunIlluminance)); put(DS->boundsMin, sizeof(DS->boundsMin)); put(DS->boundsMax, sizeof(DS->boundsMax));
 			const void* sceneId = DS; put(&sceneId, sizeof(sceneId));
@@ -710,7 +639,7 @@ bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRende
 				CullResult cr;
 				CullScene cs;
 				for (int k = 0; k < 3; ++k) { cs.boundsMin[k] = DS->boundsMin[k]; cs.boundsMax[k] = DS->boundsMax[k]; cs.sunDirection[k] = traceView.sunDirection[k]; cs.sunIlluminance[k] = traceView.sunIlluminance[k]; }
-				cs.boundsValid = DS->boundsValid; cs.prims = PRIMS; cs.hasSky = traceView.sky != nullptr; cs.hasSun = traceView.hasSun != 0;
+				cs.boundsValid = DS->boundsValid; cs.prims = plan.prims; cs.hasSky = traceView.sky != nullptr; cs.hasSun = traceView.hasSun != 0;
 				const bool culled = CullCells(cs, req.camera, st.maxPathLength, st.rayTMin, W, H, cellsX, req.cellFirst, stride, numLocalCells, cr);
 				R.cullKey[q].clear();   // (valid again once the slot's buffers hold this view)
 				R.cullActive[q] = numLocalCells; R.cullEmptyPixels[q] = 0;
@@ -748,69 +677,28 @@ bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRende
 			if (it == R.occupancy.end()) {
 				HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, traceKernel, RL_BLOCK, 0));
 				R.occupancy[(const void*)traceKernel] = blocksPerCU;
-				if (getenv("RAYLIB_PRINT_OCCUPANCY")) Log("megakernel (%u paths per lane, tree width %d): %d workgroups per CU", pathsPerThread, width, blocksPerCU);
+				if (getenv("RAYLIB_PRINT_OCCUPANCY")) Log("megakernel (%u paths per lane, tree width %u): %d workgroups per CU", plan.pathsPerWave / 64u, plan.treeWidth, blocksPerCU);
 			} else blocksPerCU = it->second;
 		}
-		if (blocksPerCU < 1) blocksPerCU = 1;
-		if (const char* e = getenv("RAYLIB_BLOCKS_PER_CU")) { int v = atoi(e); if (v > 0) blocksPerCU = v; }
+		const uint32_t batch = PlanLaunch(numLocalCells, numActive, SPP, 0, R.numCUs, blocksPerCU, plan, knobs).batch;
+		if (!Grow(R.samples, R.samplesBytes, (size_t)numSlots * sizeof(SampleRGB) * batch)) return false;
+		if (batch < SPP && !Grow(R.accum, R.accumBytes, (size_t)numSlots * sizeof(float4))) return false;
 		const int depthSlots = st.maxPathLength > 1 ? st.maxPathLength : 1;
 		for (uint32_t s0 = 0; s0 < SPP; s0 += batch) {
-			const uint32_t cnt = std::min(batch, SPP - s0);
+			const LaunchPlan L = PlanLaunch(numLocalCells, numActive, SPP, s0, R.numCUs, blocksPerCU, plan, knobs);
+			const uint32_t cnt = L.sampleCount;
 			P.sampleBegin = s0; P.sampleCount = cnt;
 			P.magicSamples = cnt > 1 ? (uint32_t)(0x100000000ull / cnt) : 0xFFFFFFFFu;
-			const uint64_t jobs64 = (uint64_t)numActive * cnt * 64u;
-			if (jobs64 > 0xF0000000ull) { Log("Raylib_Render: job count overflow"); return false; }   // (a head overshoots its band by one chunk per wave and attempt)
-			P.numJobs = (uint32_t)jobs64;
-			uint32_t blocks = (uint32_t)std::min<uint64_t>((uint64_t)R.numCUs * blocksPerCU, (jobs64 + RL_BLOCK * pathsPerThread - 1) / (RL_BLOCK * pathsPerThread));
-			if (blocks < 1) blocks = 1;
-			P.stackStride = blocks * RL_BLOCK * pathsPerThread;
-			{   // jobs per global atomic: ~1/16 of a wave's share, rounded to a multiple of 64 (one cell at one sample), 64..1024.
-				// Measured on the slice one of 8 ranks renders of the 1080p x 64 spp Cornell frame (16.6 M jobs): 64 -> 4.10 ms,
-				// 128 -> 3.62, 256 -> 3.45, 512 -> 3.53, 1024 -> 4.07; on the whole frame 1024 is best (64 -> 33.6 ms: the atomic saturates).
-				const uint64_t waves = (uint64_t)blocks * (RL_BLOCK / 64);
-				uint64_t chunk = ((jobs64 / (waves * 16)) + 32) & ~63ull;
-				if (const char* e = getenv("RAYLIB_JOB_CHUNK")) chunk = (uint64_t)std::max(0, atoi(e));
-				P.jobChunk = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(64, chunk));
-				// The pool schedule's jobs differ by two orders of magnitude (a cell that misses the scene's root box against one full of geometry): the launch's
-				// tail is what a wave needs for its LAST chunk, and on the 298 k-triangle frame a chunk of 1024 heavy jobs is 6 ms of a 45 ms launch (wave timeline,
-				// tools/gpu_timeline_pool.py: first wave out of jobs at 39.7 ms, last at 46.0).  One head took chunks no smaller than 1024 (256: 48.1 ms, the atomic's
-				// queue); with a head per XCD 256 is the best: 1024 -> 46.5 ms, 512 -> 45.0, 256 -> 44.0, 128 -> 44.0, 64 -> 48.4 (one head, 1024: 44.9).
-				if (poolK > 0 && !getenv("RAYLIB_JOB_CHUNK")) {
-					uint32_t h = RL_MAX_HEADS; if (const char* e = getenv("RAYLIB_JOB_HEADS")) h = (uint32_t)std::max(1, atoi(e));
-					if (h >= 4) P.jobChunk = std::min<uint32_t>(P.jobChunk, 256u);
-					// ... and with the cells that cannot see the scene out of the list (CullCells) every job is a heavy one and there are far fewer of them: 128
-					// as long as that stays under ~400 k draws per launch (298 k frame, 29 M jobs: 256 -> 37.75 ms, 128 -> 37.25, 64 -> 37.2, 512 -> 38.7)
-					if (h >= 4 && numActive < numLocalCells && jobs64 / 128u <= 400000u) P.jobChunk = std::min<uint32_t>(P.jobChunk, 128u);
-				}
-				// the leaf-list kernel's chunk belongs to a workgroup, whose four waves draw batches of 64 from it (RL_QUEUE_SHARED_CHUNK): four waves' worth,
-				// RAYLIB_JOB_CHUNK_MAX (default 1024) at most
-				if (RL_QUEUE_SHARED_CHUNK && IsLeafListKernel(traceKernel) && !getenv("RAYLIB_JOB_CHUNK")) {
-					uint64_t cap = 1024; if (const char* e = getenv("RAYLIB_JOB_CHUNK_MAX")) cap = (uint64_t)std::max(64, atoi(e));
-					P.jobChunk = (uint32_t)std::min<uint64_t>(cap, std::max<uint64_t>(256, 4 * chunk));
-				}
-				// a chunk is whole batches of 64 jobs (one cell at one sample: DecodeJobBatch decodes base >> 6, TakeJobs packs the head's number into the low
-				// bits of a band's job count) whatever the environment asked for
-				P.jobChunk = std::max(64u, P.jobChunk & ~63u);
-			}
+			if (L.jobs > 0xF0000000ull) { Log("Raylib_Render: job count overflow"); return false; }   // (a head overshoots its band by one chunk per wave and attempt)
+			P.numJobs = (uint32_t)L.jobs;
+			const uint32_t blocks = L.blocks;
+			P.stackStride = L.stackStride; P.jobChunk = L.jobChunk;
+			P.numHeads = L.heads; P.jobsPerHead = L.jobsPerHead; P.guideShift = L.guideShift;
 			if (!Grow(R.pathStack, R.pathStackBytes, (size_t)depthSlots * 8 * P.stackStride * sizeof(float))) return false;
-			{   // the job list in bands of whole cells, one head per XCD (rl_render.hip TakeJobs); heads count from their band's first job: one memset
-				uint32_t heads = RL_MAX_HEADS; if (const char* e = getenv("RAYLIB_JOB_HEADS")) heads = (uint32_t)std::min<int>((int)RL_MAX_HEADS, std::max(1, atoi(e)));
-				const uint32_t cellsPerHead = (std::max(1u, numActive) + heads - 1) / heads;
-				heads = (std::max(1u, numActive) + cellsPerHead - 1) / cellsPerHead;   // no empty band: every head's first job exists (and h * jobsPerHead < numJobs < 2^32)
-				P.numHeads = heads; P.jobsPerHead = cellsPerHead * cnt * 64u;
-				{   // guided draws at the end of a band: 2^shift ~ twice the drawers per head (waves; workgroups in the leaf-list kernel, whose chunk is shared)
-					const bool perBlockChunk = RL_QUEUE_SHARED_CHUNK && IsLeafListKernel(traceKernel);
-					const uint32_t drawers = std::max(1u, blocks * (perBlockChunk ? 1u : (uint32_t)(RL_BLOCK / 64)) / heads);
-					uint32_t shift = 1; while ((1u << shift) < 2u * drawers && shift < 24u) ++shift;
-					int guided = 0;   // measured: no gain on either bench workload -- a heavy chunk drawn three rounds before the end outlasts the guided ones
-					if (const char* e = getenv("RAYLIB_GUIDED")) guided = atoi(e);
-					P.guideShift = guided > 0 ? shift + (uint32_t)(guided - 1) : 0u;
-				}
-				pend.jobHeads = heads;
-				HIP_OK(hipMemsetAsync(R.jobCounter, 0, RL_MAX_HEADS * RL_HEAD_STRIDE * sizeof(unsigned int), R.stream));
-			}
+			pend.jobHeads = L.heads;
+			HIP_OK(hipMemsetAsync(R.jobCounter, 0, RL_MAX_HEADS * RL_HEAD_STRIDE * sizeof(unsigned int), R.stream));   // heads count from their band's first job: one memset
 			HIP_OK(hipEventRecord(R.ev[q][2], R.stream));
-			if (jobs64 > 0) {   // (no cell of this rank sees the scene: k_resolve has all it needs)
+			if (L.jobs > 0) {   // (no cell of this rank sees the scene: k_resolve has all it needs)
 				hipLaunchKernelGGL(traceKernel, dim3(blocks), dim3(RL_BLOCK), 0, R.stream,
 				                   P, traceView, DS->skyRot, R.samples, R.pathStack, R.counters, R.jobCounter);
 				HIP_OK(hipGetLastError());
@@ -843,16 +731,6 @@ bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRende
 	return true;
 }
 
-bool EnqueueDispatch(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRender& pend)
-{
-	const bool prims = !sc.spheres.empty() || !sc.cubes.empty();
-	if (sc.bvh.depth <= 16 && !prims) return EnqueueRender<16, false>(R, sc, req, pend);
-	if (sc.bvh.depth <= 32) return prims ? EnqueueRender<32, true>(R, sc, req, pend) : EnqueueRender<32, false>(R, sc, req, pend);
-	if (sc.bvh.depth <= 64) return prims ? EnqueueRender<64, true>(R, sc, req, pend) : EnqueueRender<64, false>(R, sc, req, pend);
-	Log("Raylib_Render: BVH depth %u exceeds the traversal stack (64)", sc.bvh.depth);
-	return false;
-}
-
 // The one host synchronisation of a rank's render, then its numbers.  Adds to `stats` (counters are summed over ranks, times
 // are the slowest rank's).
 bool FinishRender(PendingRender& pend, RaylibAMDStats& stats)
@@ -882,8 +760,7 @@ bool FinishRender(PendingRender& pend, RaylibAMDStats& stats)
 	stats.culledSamples += pend.culledSamples; stats.culledRays += pend.culledSamples * pend.culledRaysPerSample;
 	stats.texFetches += pend.culledSamples * pend.culledSkyTexels;   // (k_resolve DOES look up the sky texel of every sample of a dropped cell: executed, counted)
 	stats.waveTrips += cnt[CNT_TRIPS];
-	stats.pathsPerWave = 64u * pend.schedulePaths;
-	stats.treeWidth = pend.treeWidth; stats.nodeBytes = pend.treeWidth == 8 ? (uint32_t)sizeof(DNode8) : 64u;
+	stats.pathsPerWave = pend.pathsPerWave; stats.treeWidth = pend.treeWidth; stats.nodeBytes = pend.nodeBytes;
 	stats.pixels += pend.pixels;
 	stats.kernelMs = std::max(stats.kernelMs, (double)totalMs);
 	stats.traceKernelMs = std::max(stats.traceKernelMs, (double)(pend.pathTrace ? pend.traceMs : totalMs));
@@ -1044,7 +921,7 @@ bool RenderMulti(Scene& sc, const RenderRequest& req, RaylibAMDStats& stats, boo
 		float4* dst = gather + plan.offset[r];
 		if (remote[(size_t)r]) { if (!Grow(C.cells, C.cellsBytes, std::max<size_t>(16, bytes))) return false; q.outDevice = C.cells; }
 		else q.outDevice = dst;   // same device as rank 0: rendered in place, nothing to move
-		if (!EnqueueDispatch(C, sc, q, pend[(size_t)r])) return false;
+		if (!EnqueueRender(C, sc, q, pend[(size_t)r])) return false;
 		if (remote[(size_t)r] && !useRccl && bytes) HIP_OK(hipMemcpyPeerAsync(dst, R0.device, C.cells, C.device, bytes, C.stream));
 		HIP_OK(hipEventRecord(C.ev[b][4], C.stream));
 		return true;
@@ -1153,7 +1030,7 @@ bool DeviceRender(Scene& sc, const RenderRequest& req, RaylibAMDStats& stats)
 		(void)DrainLocked();        // this path uses rank 0's slot-0 events and counter block
 		g_deferredUnreported = false;   // ... and its numbers are the ones the caller reads next
 		PendingRender pend;
-		ok = EnqueueDispatch(Rank0(), sc, req, pend);
+		ok = EnqueueRender(Rank0(), sc, req, pend);
 		if (ok && req.outHostRGBA) HIP_OK(hipMemcpyAsync(req.outHostRGBA, pend.out, pend.outBytes, hipMemcpyDeviceToHost, Rank0().stream));
 		if (pend.ctx) ok = FinishRender(pend, stats) && ok;
 		else (void)hipStreamSynchronize(Rank0().stream);

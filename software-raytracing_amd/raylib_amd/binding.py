@@ -53,6 +53,19 @@ class Stats(C.Structure):
         return d
 
 
+class RenderPlan(C.Structure):
+    """include/raylib_amd.h RaylibAMDRenderPlan."""
+    _fields_ = [(k, C.c_int32) for k in ("pathTrace", "stack", "prims", "poolK", "tree", "lstack", "lds", "plain")] + \
+               [(k, C.c_uint32) for k in ("pathsPerWave", "treeWidth", "nodeBytes")] + \
+               [(k, C.c_int32) for k in ("keepNodes4", "keepNodes4f", "eagerTree")] + \
+               [(k, C.c_uint32) for k in ("batch", "sampleCount", "blocks", "stackStride", "jobChunk", "heads", "jobsPerHead", "guideShift")] + \
+               [("jobs", C.c_uint64)]
+    TREES = {0: "none", 1: "bvh2", 2: "box4", 3: "grid4", 4: "wide8"}
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # Per-ray / per-unit algorithmic byte constants of the flat layout (csrc/rl_device.h)
 NODE_B, TRI_B, SHADE_B, TEXEL_B, PIXEL_B = 64, 64, 64, 16, 16
 
@@ -137,6 +150,7 @@ _EXPORTS = {
     "RaylibAMD_SceneLeafListInfo": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "RaylibAMD_ScenePlain": (C.c_int32, [C.c_void_p]),
     "RaylibAMD_LastTracePlain": (C.c_int32, []),
+    "RaylibAMD_PlanRender": (C.c_int32, [C.c_void_p, C.POINTER(RendererSettings), C.c_int32, C.c_int32, C.c_int32, C.POINTER(RenderPlan)]),
     "RaylibAMD_SceneWalk8Host": (C.c_int32, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "RaylibAMD_SceneBVHHash": (C.c_uint64, [C.c_void_p]),
     "RaylibAMD_CameraExport": (None, [C.c_void_p, C.POINTER(C.c_float)]),
@@ -250,6 +264,7 @@ class SceneSession:
         lib.Raylib_AddOBJModelToScene(self.scene, self.obj)
         lib.Raylib_SetSunIlluminance(self.scene, *[float(x) for x in sun])
         lib.Raylib_SetSunDirection(self.scene, *[float(x) for x in sun_dir])
+        self.has_sky = sky_image is not None
         if sky_image is not None:
             sky = np.ascontiguousarray(sky_image, np.float32)
             ih = lib.RaylibAMD_CreateImageFromData(sky.shape[1], sky.shape[0], _fp(sky))

@@ -71,6 +71,19 @@ def camera_for_case(c):
     return ffi.make_camera(c["origin"], c["look_at"], c["fov"], c["aspect"], c["aperture"], c["focal"], *c["shutter"])
 
 
+def assert_planned(lib, ses, stats, w, h, spp, max_path=5, tmin=1e-4):
+    """The render just made of `ses` (numbers in `stats`) launched what RaylibAMD_PlanRender predicts for it under the same environment (csrc/rl_plan.cc)."""
+    import ctypes as C
+    from raylib_amd import binding
+    st = binding.RendererSettings(int(w), int(h), int(spp), int(max_path), float(tmin), 0)
+    p = binding.RenderPlan()
+    assert lib.RaylibAMD_PlanRender(ses.scene, C.byref(st), int(getattr(ses, "has_sky", False)), 256, 4, C.byref(p)) == 1
+    s = stats if isinstance(stats, dict) else stats.as_dict()
+    got = (s["treeWidth"], s["pathsPerWave"], s["nodeBytes"], lib.RaylibAMD_LastTracePlain())
+    assert got == (p.treeWidth, p.pathsPerWave, p.nodeBytes, p.plain), (got, p.as_dict())
+    return p.as_dict()
+
+
 def session_for_case(lib, name, tmpdir):
     from raylib_amd import binding
     obj, c = build_case(name, tmpdir)

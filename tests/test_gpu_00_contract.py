@@ -143,6 +143,7 @@ def test_config2_whole_frames_against_the_oracle(config2_scene, gpu_lib, oracle)
     img = ses.render(1920, 1080, 4)
     st = ses.stats().as_dict()
     assert st["treeWidth"] == 8 and st["pathsPerWave"] == 128 and st["frameSamples"] == 1920 * 1080 * 4
+    helpers.assert_planned(gpu_lib, ses, st, 1920, 1080, 4)
     whole_frame_vs_oracle(oracle, scene, cam, 1920, 1080, 4, img, "configs[2] exterior, 4 spp", max_tied=40)
     cin = helpers.scenes.CONFIG_CAMERAS["breakfast_interior"]
     gpu_lib.Raylib_CameraSetPosition(ses.camera, *[float(x) for x in cin["origin"]]); gpu_lib.Raylib_CameraSetLookAt(ses.camera, *[float(x) for x in cin["look_at"]])
@@ -178,6 +179,7 @@ def test_eight_wide_builder_options_walk_to_the_same_frame(gpu_lib, oracle, work
         img = ses.render(W, H, SPP)
         st = ses.stats().as_dict()
         assert st["treeWidth"] == 8 and st["nodeBytes"] == 80 and st["frameSamples"] == W * H * SPP, (env, st)
+        helpers.assert_planned(gpu_lib, ses, st, W, H, SPP)
         n8, lv, s4, s8 = C.c_uint32(0), C.c_uint32(0), C.c_float(0), C.c_float(0)
         assert gpu_lib.RaylibAMD_SceneBVH8Info(ses.scene, C.byref(n8), C.byref(lv), C.byref(s4), C.byref(s8)) == 1
         shapes.add((n8.value, lv.value, round(s8.value, 3), st["nodesVisited"], st["trisTested"]))   # (another tree: other node counts, other records per frame)

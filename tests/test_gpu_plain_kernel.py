@@ -21,10 +21,12 @@ def _render_both(ses, lib, monkeypatch, w, h, spp, **kw):
     a = ses.render(w, h, spp, **kw)
     plain = lib.RaylibAMD_LastTracePlain()
     sa = ses.stats()
+    helpers.assert_planned(lib, ses, sa, w, h, spp, **kw)
     monkeypatch.setenv("RAYLIB_PLAIN_KERNEL", "0")
     b = ses.render(w, h, spp, **kw)
     general = lib.RaylibAMD_LastTracePlain()
     sb = ses.stats()
+    helpers.assert_planned(lib, ses, sb, w, h, spp, **kw)
     monkeypatch.delenv("RAYLIB_PLAIN_KERNEL")
     assert sa.treeWidth == 0 and sb.treeWidth == 0, "not the leaf-list kernel"
     assert general == 0
@@ -79,6 +81,7 @@ def test_cornell_goldens_through_the_plain_instance(gpu_lib, oracle, workdir, mo
         ties = tie_mask(oracle, flat, helpers.ffi.make_camera(c["origin"], c["look_at"], c["fov"], c["aspect"]), 64, 64)
         img = ses.render(64, 64, 4)
         assert gpu_lib.RaylibAMD_LastTracePlain() == 1, name
+        helpers.assert_planned(gpu_lib, ses, ses.stats(), 64, 64, 4)
         assert_same_outside_ties(img, g["mode0_spp4"], ties, name)
         ses.close()
 
@@ -94,6 +97,7 @@ def test_textures_cutouts_and_sky_keep_the_general_instance(gpu_lib, oracle, wor
         ties = tie_mask(oracle, flat, helpers.ffi.make_camera(c["origin"], c["look_at"], c["fov"], c["aspect"]), 64, 64)
         img = ses.render(64, 64, 4)
         assert ses.stats().treeWidth == 0 and gpu_lib.RaylibAMD_LastTracePlain() == 0, name
+        helpers.assert_planned(gpu_lib, ses, ses.stats(), 64, 64, 4)
         assert_same_outside_ties(img, g["mode0_spp4"], ties, name)
         ses.close()
     # the cut-out scene without a sky: the cut-out bit alone keeps the general instance
@@ -104,6 +108,7 @@ def test_textures_cutouts_and_sky_keep_the_general_instance(gpu_lib, oracle, wor
     assert gpu_lib.RaylibAMD_ScenePlain(ses.scene) == 0
     img = ses.render(96, 96, 4)
     assert ses.stats().treeWidth == 0 and gpu_lib.RaylibAMD_LastTracePlain() == 0
+    helpers.assert_planned(gpu_lib, ses, ses.stats(), 96, 96, 4)
     monkeypatch.setenv("RAYLIB_LEAF_LIST", "0")   # the BVH4 walk of the same scene: an independent kernel
     ref = ses.render(96, 96, 4)
     monkeypatch.delenv("RAYLIB_LEAF_LIST")
@@ -114,6 +119,7 @@ def test_textures_cutouts_and_sky_keep_the_general_instance(gpu_lib, oracle, wor
     assert gpu_lib.RaylibAMD_ScenePlain(ses.scene) == 1
     img = ses.render(160, 90, 4)
     assert ses.stats().treeWidth == 0 and gpu_lib.RaylibAMD_LastTracePlain() == 0
+    helpers.assert_planned(gpu_lib, ses, ses.stats(), 160, 90, 4)
     assert ses.stats().texFetches > 0
     monkeypatch.setenv("RAYLIB_LEAF_LIST", "0")
     ref = ses.render(160, 90, 4)
