@@ -260,6 +260,44 @@ RAYLIB_API int32_t RaylibAMD_DenoiseHost(uint32_t width, uint32_t height, const 
  * = RaylibAMD_Denoise(m, hdr, a, n, o, NULL). Off: both keep today's behaviour exactly (return 0). */
 RAYLIB_API void    RaylibAMD_EnableDenoiser(int32_t enable);
 
+/* ---- progressive rendering: a frame in passes of samples, each pass ending with a preview, and (optionally) cells that stop early.
+ *      After any sequence of passes that brings an 8x8 cell to n samples, that cell's pixels are bit for bit those of Raylib_Render with
+ *      samplesPerPixel = n and the same settings, scene, camera and seed: a uniform session previews one-shot frames, an adaptive one ends
+ *      with a mosaic of them.  A session renders on the first device (RAYLIB_NUM_GPUS > 1: rank 0's). ---- */
+typedef uintptr_t RaylibAMDProgressiveHandle;
+typedef struct RaylibAMDProgressiveParams {
+	float    threshold;   /* adaptive stopping: a cell stops when its error (below) is < threshold; 0 = never (uniform passes); finite, >= 0 */
+	uint32_t minSamples;  /* samples every cell takes before it may stop; >= 2 */
+} RaylibAMDProgressiveParams;
+/* The stopping rule.  Every sample's y = L / (1 + L), L its luminance (0.2126 R + 0.7152 G + 0.0722 B, as Raylib_PostProcess); per pixel
+ * S1 = sum of y and S2 = sum of y * y in float, in sample order.  A pixel's error after n samples is
+ * se = sqrt(max(0, (S2 - S1 * S1 / n) / (n - 1)) / n), +inf when S1, S2 or se is not finite; a cell's error is the largest of its valid pixels'.  After a
+ * pass, a live cell stops when n >= minSamples and its error < threshold; culled cells (outside the scene's silhouette) follow the same rule. */
+
+/* Opens a session on (settings, scene, camera) that renders into `out` in passes; settings->samplesPerPixel (max(1, .)) is the cap.
+ * The seed (RaylibAMD_SetSeed / RAYLIB_SEED), the camera and the settings are captured here; `out` is resized to the viewport as by
+ * Raylib_Render.  params == NULL: uniform passes.  Returns 0 when an argument is null, the scene is not finalized, the render mode is not
+ * RAYLIB_RENDERMODE_Default, params are out of range, the viewport is empty, or there is no device. */
+RAYLIB_API RaylibAMDProgressiveHandle RaylibAMD_BeginProgressive(const RendererSettings* settings, SceneHandle scene, CameraHandle camera,
+                                                                 ImageHandle out, const RaylibAMDProgressiveParams* params);
+/* Renders up to `samples` (>= 1) more samples per live cell (clamped to the cap), then rewrites every pixel of `out` with its cell's mean
+ * so far; the result stays on the device, as after Raylib_Render, and RaylibAMD_GetLastStats reports this pass.  Returns the number of
+ * cells still live (0 = finished: every cell stopped or reached the cap; a later Step does nothing and returns 0), or -1: a null, unknown
+ * or ended handle, samples == 0, a scene that changed since Begin (finalized anew, sun, shutter), a sky panorama that changed, an image
+ * that was resized or destroyed, or a device failure.  On -1 the image and the session are unchanged (a device failure excepted). */
+RAYLIB_API int32_t RaylibAMD_ProgressiveStep(RaylibAMDProgressiveHandle h, uint32_t samples);
+/* Per cell (cellsX * cellsY, row-major): its samples so far and 1 if it has stopped; per pixel (W * H, row-major): S1 and S2 of the rule.
+ * Any pointer may be NULL.  Returns 1, or 0 for an unknown handle or without a device. */
+RAYLIB_API int32_t RaylibAMD_ProgressiveExport(RaylibAMDProgressiveHandle h, uint32_t* cellSamples, uint8_t* cellStopped, float* sumY, float* sumY2);
+/* Frees the session's device buffers (the image stays as the last pass left it).  1, or 0 for an unknown handle.  A session that is never
+ * ended holds its buffers until the process exits, as an image that is never destroyed does. */
+RAYLIB_API int32_t RaylibAMD_EndProgressive(RaylibAMDProgressiveHandle h);
+/* The stopping rule on the host, the oracle of the device's decision (no device needed): for a W x H frame's cells with the given sample
+ * counts and moments (as exported), one byte per cell in outStop, 1 = the cell stops.  params == NULL: uniform (nothing stops).
+ * Returns 1, or 0 for a null array or params out of range. */
+RAYLIB_API int32_t RaylibAMD_ProgressiveDecideHost(uint32_t width, uint32_t height, const uint32_t* cellSamples, const float* sumY,
+                                                   const float* sumY2, const RaylibAMDProgressiveParams* params, uint8_t* outStop);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@
 #include "raylib_amd.h"
 #include "rl_host.h"
 #include "rl_plan.h"
+#include "rl_progressive.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -68,22 +69,29 @@ uint64_t CurrentSeed()
 	return g_seed;
 }
 
-bool RenderInternal(const RendererSettings* settings, Scene* scene, Camera* camera,
-                    uint32_t cellFirst, uint32_t cellStride, void* outDevice, float* outHost, bool callerOwnsOut = false)
+// What every render checks and prepares before it reaches the device (Raylib_Render and RaylibAMD_BeginProgressive; `who` names the caller in the log).
+bool PrepareRender(const char* who, const RendererSettings* settings, Scene* scene, Camera* camera)
 {
-	if (!settings || !scene || !camera) { Log("Raylib_Render: null argument"); return false; }
-	if (!scene->finalized) { Log("Raylib_Render: scene was not finalized (Raylib_FinalizeScene)"); return false; }
-	if (settings->renderMode >= RAYLIB_RENDERMODE_MAX) { Log("Raylib_Render: invalid render mode %u", settings->renderMode); return false; }
+	if (!settings || !scene || !camera) { Log("%s: null argument", who); return false; }
+	if (!scene->finalized) { Log("%s: scene was not finalized (Raylib_FinalizeScene)", who); return false; }
+	if (settings->renderMode >= RAYLIB_RENDERMODE_MAX) { Log("%s: invalid render mode %u", who, settings->renderMode); return false; }
 	if (scene->hasMovingCubes && (scene->accelT0 != camera->beginTime || scene->accelT1 != camera->endTime)) {
 		// moving cubes: their boxes must cover the motion over THIS camera's shutter interval
 		if (scene->device) { DeviceReleaseScene(scene->device); scene->device = nullptr; }
-		if (!scene->BuildAccel(camera->beginTime, camera->endTime)) { Log("Raylib_Render: the acceleration structure could not be rebuilt for this camera's shutter interval"); return false; }
+		if (!scene->BuildAccel(camera->beginTime, camera->endTime)) { Log("%s: the acceleration structure could not be rebuilt for this camera's shutter interval", who); return false; }
 	}
 	if (scene->sky && !g_images.contains(scene->sky)) {
 		// the reference would read freed memory here; a destroyed panorama is treated as none
-		Log("Raylib_Render: the scene's sky panorama was destroyed; rendering without it");
+		Log("%s: the scene's sky panorama was destroyed; rendering without it", who);
 		scene->sky = nullptr;
 	}
+	return true;
+}
+
+bool RenderInternal(const RendererSettings* settings, Scene* scene, Camera* camera,
+                    uint32_t cellFirst, uint32_t cellStride, void* outDevice, float* outHost, bool callerOwnsOut = false)
+{
+	if (!PrepareRender("Raylib_Render", settings, scene, camera)) return false;
 	RenderRequest req;
 	req.settings = *settings;
 	req.camera = camera->ToDevice();
@@ -95,6 +103,20 @@ bool RenderInternal(const RendererSettings* settings, Scene* scene, Camera* came
 	bool ok = DeviceRender(*scene, req, stats);
 	{ std::lock_guard<std::mutex> lk(g_stateMu); g_lastStats = stats; }
 	return ok;
+}
+
+// A progressive session as the ABI hands it out: the device session and the handles it was begun with.
+struct Progressive {
+	Scene* scene;
+	Image* out;
+	uint32_t width, height;
+	ProgressiveSession* dev;
+};
+Registry<Progressive> g_progressive;
+
+bool ProgressiveParamsValid(const RaylibAMDProgressiveParams& P)
+{
+	return P.threshold >= 0.0f && P.threshold <= 3.40282347e+38f && P.minSamples >= 2;   // (false for NaN)
 }
 
 } // namespace
@@ -378,6 +400,93 @@ int32_t RaylibAMD_DenoiseHost(uint32_t width, uint32_t height, const float* colo
 	const RaylibAMDDenoiseParams& P = params ? *params : kDenoiseDefaults;
 	if (!colorRGBA || !outRGBA || !DenoiseParamsValid(P)) return 0;
 	DenoiseHost(width, height, colorRGBA, bHDR != 0, albedoRGBA, normalRGBA, P, outRGBA);
+	return 1;
+}
+
+RaylibAMDProgressiveHandle RaylibAMD_BeginProgressive(const RendererSettings* settings, SceneHandle scene, CameraHandle camera,
+                                                      ImageHandle out, const RaylibAMDProgressiveParams* params)
+{
+	Scene* s = (Scene*)scene; Camera* c = (Camera*)camera; Image* img = (Image*)out;
+	if (!settings || !s || !c || !img) { Log("RaylibAMD_BeginProgressive: null argument"); return 0; }
+	if (settings->renderMode != RAYLIB_RENDERMODE_Default) { Log("RaylibAMD_BeginProgressive: render mode %u is not the path-traced one", settings->renderMode); return 0; }
+	if (params && !ProgressiveParamsValid(*params)) { Log("RaylibAMD_BeginProgressive: parameters out of range"); return 0; }
+	if ((uint64_t)settings->viewportWidth * settings->viewportHeight == 0) { Log("RaylibAMD_BeginProgressive: empty viewport"); return 0; }
+	if (!s->finalized) { Log("RaylibAMD_BeginProgressive: scene was not finalized (Raylib_FinalizeScene)"); return 0; }
+	if (!DeviceAvailable()) return 0;
+	if (!PrepareRender("RaylibAMD_BeginProgressive", settings, s, c)) return 0;
+	if (settings->viewportWidth != img->width || settings->viewportHeight != img->height)
+		img->Reallocate(settings->viewportWidth, settings->viewportHeight, 0.0f, 0.0f, 0.0f, 1.0f);   // as Raylib_Render
+	if (!DeviceImagePixels(*img)) return 0;
+	RenderRequest req;
+	req.settings = *settings;
+	req.camera = c->ToDevice();
+	req.seed = CurrentSeed();
+	req.cellFirst = 0; req.cellStride = 1;
+	req.outDevice = nullptr; req.outHostRGBA = nullptr;
+	ProgressiveSession* d = DeviceProgressiveBegin(*s, req, params ? params->threshold : 0.0f, params ? params->minSamples : 2u);
+	if (!d) return 0;
+	Progressive* p = new Progressive{ s, img, settings->viewportWidth, settings->viewportHeight, d };
+	g_progressive.add(p);
+	return (RaylibAMDProgressiveHandle)p;
+}
+
+int32_t RaylibAMD_ProgressiveStep(RaylibAMDProgressiveHandle h, uint32_t samples)
+{
+	Progressive* p = (Progressive*)h;
+	if (!p || !g_progressive.contains(p)) { Log("RaylibAMD_ProgressiveStep: unknown session"); return -1; }
+	if (samples == 0) { Log("RaylibAMD_ProgressiveStep: no samples asked for"); return -1; }
+	if (!g_scenes.contains(p->scene)) { Log("RaylibAMD_ProgressiveStep: the session's scene was destroyed"); return -1; }
+	if (!g_images.contains(p->out)) { Log("RaylibAMD_ProgressiveStep: the session's image was destroyed"); return -1; }
+	if (p->out->width != p->width || p->out->height != p->height) { Log("RaylibAMD_ProgressiveStep: the session's image was resized; it is unchanged"); return -1; }
+	if (p->scene->sky && !g_images.contains(p->scene->sky)) { Log("RaylibAMD_ProgressiveStep: the scene's sky panorama was destroyed; the image is unchanged"); return -1; }
+	void* dev = DeviceImagePixels(*p->out);
+	if (!dev) return -1;
+	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
+	bool rendered = false;
+	const int32_t r = DeviceProgressiveStep(*p->dev, samples, dev, stats, rendered);
+	if (rendered) {
+		p->out->devValid = true; p->out->hostStale = true; p->out->Touch();
+		std::lock_guard<std::mutex> lk(g_stateMu);
+		g_lastStats = stats;
+	}
+	return r;
+}
+
+int32_t RaylibAMD_ProgressiveExport(RaylibAMDProgressiveHandle h, uint32_t* cellSamples, uint8_t* cellStopped, float* sumY, float* sumY2)
+{
+	Progressive* p = (Progressive*)h;
+	if (!p || !g_progressive.contains(p)) return 0;
+	return DeviceProgressiveExport(*p->dev, cellSamples, cellStopped, sumY, sumY2) ? 1 : 0;
+}
+
+int32_t RaylibAMD_EndProgressive(RaylibAMDProgressiveHandle h)
+{
+	Progressive* p = (Progressive*)h;
+	if (!p || !g_progressive.eraseFirst(p)) return 0;
+	DeviceProgressiveEnd(p->dev);
+	delete p;
+	return 1;
+}
+
+int32_t RaylibAMD_ProgressiveDecideHost(uint32_t width, uint32_t height, const uint32_t* cellSamples, const float* sumY,
+                                        const float* sumY2, const RaylibAMDProgressiveParams* params, uint8_t* outStop)
+{
+	if (!cellSamples || !sumY || !sumY2 || !outStop) return 0;
+	if (params && !ProgressiveParamsValid(*params)) return 0;
+	const float threshold = params ? params->threshold : 0.0f;
+	const uint32_t minSamples = params ? params->minSamples : 2u;
+	const uint32_t cellsX = (width + 7) / 8, cellsY = (height + 7) / 8;
+	for (uint32_t cy = 0; cy < cellsY; ++cy)
+		for (uint32_t cx = 0; cx < cellsX; ++cx) {
+			const uint32_t n = cellSamples[(size_t)cy * cellsX + cx];
+			float e = 0.0f;
+			for (uint32_t y = cy * 8; y < std::min(height, cy * 8 + 8); ++y)
+				for (uint32_t x = cx * 8; x < std::min(width, cx * 8 + 8); ++x) {
+					const float v = ProgressivePixelError(sumY[(size_t)y * width + x], sumY2[(size_t)y * width + x], n);
+					e = e < v ? v : e;
+				}
+			outStop[(size_t)cy * cellsX + cx] = ProgressiveCellStops(e, n, threshold, minSamples) ? 1 : 0;
+		}
 	return 1;
 }
 

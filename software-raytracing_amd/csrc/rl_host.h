@@ -248,6 +248,14 @@ bool DeviceVerifyExactMath(int which, uint64_t* outMismatches, uint64_t* outFirs
 bool DeviceEvalHook(int kind, Scene* sc, const DCamera* cam, int a, int b, const float* in, int n, uint64_t seed, float* out);
 void DeviceReleaseScene(DeviceScene* dev);
 
+// Progressive rendering (include/raylib_amd.h RaylibAMD_BeginProgressive; rl_runtime.inl).  Begin: nullptr without a device or memory.  Step: the number of
+// live cells after the pass (0: finished), -1 when refused or failed -- `rendered` tells whether a pass ran (and `stats` is its numbers).
+struct ProgressiveSession;
+ProgressiveSession* DeviceProgressiveBegin(Scene& sc, const RenderRequest& req, float threshold, uint32_t minSamples);
+int32_t DeviceProgressiveStep(ProgressiveSession& S, uint32_t samples, void* outDevice, RaylibAMDStats& stats, bool& rendered);
+bool DeviceProgressiveExport(ProgressiveSession& S, uint32_t* cellSamples, uint8_t* cellStopped, float* sumY, float* sumY2);
+void DeviceProgressiveEnd(ProgressiveSession* S);
+
 // denoiser (rl_denoise.hip): the a-trous filter on the device and its host restatement; params checked by the caller (rl_abi.cc)
 void DenoiseHost(uint32_t width, uint32_t height, const float* color, bool hdr, const float* albedo, const float* normal,
                  const RaylibAMDDenoiseParams& params, float* out);

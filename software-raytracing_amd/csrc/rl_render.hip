@@ -37,6 +37,7 @@ __shared__ double rlm_lds_tab[80];
 #define RL_MATH_PROLOGUE()
 #endif
 #include "rl_math.h"
+#include "rl_progressive.h"
 #include "raylib_amd_rng.h"
 
 #include <algorithm>
@@ -2788,6 +2789,42 @@ RL_POOL_INSTANCES(RL_POOL_X)
 #undef RL_POOL_X
 
 #ifndef RL_TU_POOL   // everything below belongs to the main translation unit alone
+// One slot's samples of this batch added to `a` in sample order -- the megakernel's from the sample buffer, or, for a cell outside the scene's silhouette,
+// the miss shader's value every one of them comes to -- and each sample's RGB handed to `each` (k_resolve: nothing; k_progressive_resolve: the
+// luminance moments of its stopping rule).
+template <class EACH>
+__device__ __forceinline__ float4 SumSlotBatch(const DRenderParams& P, const DSceneView& S, const SkyRot& R, const SampleRGB* samples,
+                                               uint32_t numSlots, uint32_t slot, uint32_t cellLocal, uint32_t x, uint32_t y, float4 a, EACH&& each)
+{
+	if (P.cellEmpty && P.cellEmpty[cellLocal]) {
+		// a cell outside the scene's silhouette (rl_cull.cc): none of its samples can meet the scene, every one of them is the miss shader's value -- the sun's
+		// illuminance or nothing, the same for all; with a sky panorama the texel its camera ray points at on top (renderer.cc:155-199), so the ray is
+		// generated here exactly as the megakernel generates it (same stream, same draws: jitter, lens, shutter) -- added up sample by sample as if stored
+		if (P.emptySky) {
+			Counters c; c.rays = c.nodes = c.tris = c.shaded = c.texels = c.samples = c.trips = 0; RL_DIAG_BIND(c);
+			for (uint32_t s = 0; s < P.sampleCount; ++s) {
+				const uint32_t sidx = P.sampleBegin + s;
+				Rng g; g.s = raylib_rng_begin_mixed(P.seedMixed, y * P.width + x, sidx);
+				float u, v;
+				PixelUV(P, x, y, sidx, g, u, v);
+				V3 o, d; float rayTime;
+				CameraRay(P.camera, u, v, g, o, d, rayTime);
+				V3 L = MissSky(S, R, d, c);
+				if (S.hasSun) L = L + ld3(S.sunIlluminance);
+				a.x += L.x; a.y += L.y; a.z += L.z;
+				each(L.x, L.y, L.z);
+			}
+		} else
+		for (uint32_t s = 0; s < P.sampleCount; ++s) { a.x += P.emptyL[0]; a.y += P.emptyL[1]; a.z += P.emptyL[2]; each(P.emptyL[0], P.emptyL[1], P.emptyL[2]); }
+	} else
+	for (uint32_t s = 0; s < P.sampleCount; ++s) {
+		const SampleRGB v = samples[(size_t)s * numSlots + slot];
+		a.x += v.x; a.y += v.y; a.z += v.z;
+		each(v.x, v.y, v.z);
+	}
+	return a;
+}
+
 // Sequential per-pixel sum of this batch's samples, then (last batch) the mean.
 // reference render/renderer.cc:244-248 + core/vec3.h:214-220 (operator/= multiplies by 1/SPP)
 __global__ void __launch_bounds__(RL_BLOCK)
@@ -2804,30 +2841,7 @@ k_resolve(const DRenderParams P, const DSceneView S, const SkyRot R, const Sampl
 	float4 a = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
 	if (valid) {
 		if (!firstBatch) a = accum[slot];
-		if (P.cellEmpty && P.cellEmpty[cellLocal]) {
-			// a cell outside the scene's silhouette (rl_cull.cc): none of its samples can meet the scene, every one of them is the miss shader's value -- the sun's
-			// illuminance or nothing, the same for all; with a sky panorama the texel its camera ray points at on top (renderer.cc:155-199), so the ray is
-			// generated here exactly as the megakernel generates it (same stream, same draws: jitter, lens, shutter) -- added up sample by sample as if stored
-			if (P.emptySky) {
-				Counters c; c.rays = c.nodes = c.tris = c.shaded = c.texels = c.samples = c.trips = 0; RL_DIAG_BIND(c);
-				for (uint32_t s = 0; s < P.sampleCount; ++s) {
-					const uint32_t sidx = P.sampleBegin + s;
-					Rng g; g.s = raylib_rng_begin_mixed(P.seedMixed, y * P.width + x, sidx);
-					float u, v;
-					PixelUV(P, x, y, sidx, g, u, v);
-					V3 o, d; float rayTime;
-					CameraRay(P.camera, u, v, g, o, d, rayTime);
-					V3 L = MissSky(S, R, d, c);
-					if (S.hasSun) L = L + ld3(S.sunIlluminance);
-					a.x += L.x; a.y += L.y; a.z += L.z;
-				}
-			} else
-			for (uint32_t s = 0; s < P.sampleCount; ++s) { a.x += P.emptyL[0]; a.y += P.emptyL[1]; a.z += P.emptyL[2]; }
-		} else
-		for (uint32_t s = 0; s < P.sampleCount; ++s) {
-			const SampleRGB v = samples[(size_t)s * numSlots + slot];
-			a.x += v.x; a.y += v.y; a.z += v.z;
-		}
+		a = SumSlotBatch(P, S, R, samples, numSlots, slot, cellLocal, x, y, a, [](float, float, float) __attribute__((always_inline)) {});
 		if (lastBatch) {
 			const float k = rtm::rcp1_((float)P.spp);
 			a.x *= k; a.y *= k; a.z *= k; a.w = 1.0f;
@@ -2838,6 +2852,121 @@ k_resolve(const DRenderParams P, const DSceneView S, const SkyRot R, const Sampl
 	if (lastBatch) {
 		if (P.rowMajorOutput) { if (valid) out[(size_t)y * P.width + x] = a; }
 		else out[slot] = valid ? a : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+	}
+}
+
+// ---- progressive rendering (rl_runtime.inl ProgressiveSession; include/raylib_amd.h RaylibAMD_BeginProgressive) ----
+// What a session keeps on the device, cell-major (slot = cell * 64 + pixel of the cell): the running colour sum in sample order, the moments of y, and
+// per cell its samples so far and whether it has stopped.
+struct ProgressiveState {
+	float4* sum;
+	float* s1;
+	float* s2;
+	uint32_t* cellSamples;
+	uint8_t* stopped;
+	float threshold;
+	uint32_t minSamples;
+};
+
+// One pass's batch over EVERY cell of the frame (one wave = one 8x8 cell): a cell still sampled adds the batch's samples to its sums (the megakernel
+// traced it: P.activeCells holds the session's list; or it lies outside the silhouette: P.cellEmpty), exactly as k_resolve does.  The pass's last batch
+// then decides whether the cell stops (ProgressivePixelError, maximum over the wave) and writes every valid pixel of the row-major frame as its
+// cell's sum * (1 / samples): the frame a one-shot render at that sample count would give, whatever touched the image since the last pass.
+__global__ void __launch_bounds__(RL_BLOCK)
+k_progressive_resolve(const DRenderParams P, const DSceneView S, const SkyRot R, const SampleRGB* __restrict__ samples, const ProgressiveState st,
+                      float4* __restrict__ out, int lastBatch)
+{
+	RL_MATH_PROLOGUE();
+	const uint32_t numSlots = P.numLocalCells * 64u;
+	const uint32_t slot = blockIdx.x * RL_BLOCK + threadIdx.x;
+	if (slot >= numSlots) return;   // (whole waves: numSlots is a multiple of 64)
+	const uint32_t p = slot & 63u, cellLocal = slot >> 6;
+	const uint32_t x = (cellLocal % P.cellsX) * 8u + (p & 7u), y = (cellLocal / P.cellsX) * 8u + (p >> 3);
+	const bool valid = x < P.width && y < P.height;
+	float4 a = st.sum[slot];
+	uint32_t n;
+	if (!st.stopped[cellLocal]) {
+		n = P.sampleBegin + P.sampleCount;
+		float s1 = 0.0f, s2 = 0.0f;
+		if (valid) {
+			s1 = st.s1[slot]; s2 = st.s2[slot];
+			a = SumSlotBatch(P, S, R, samples, numSlots, slot, cellLocal, x, y, a, [&](float r, float g, float b) __attribute__((always_inline)) {
+				const float L = dot(v3(r, g, b), v3(0.2126f, 0.7152f, 0.0722f));   // (k_pp_max's luminance)
+				const float yv = L / (1.0f + L);
+				s1 += yv; s2 += yv * yv;
+			});
+			st.sum[slot] = a; st.s1[slot] = s1; st.s2[slot] = s2;
+		}
+		if (lastBatch) {
+			float e = valid ? ProgressivePixelError(s1, s2, n) : 0.0f;
+			for (int off = 32; off > 0; off >>= 1) { const float o = __shfl_xor(e, off); e = e < o ? o : e; }   // (no NaN: the error is +inf instead)
+			if (p == 0) {
+				st.cellSamples[cellLocal] = n;
+				if (ProgressiveCellStops(e, n, st.threshold, st.minSamples)) st.stopped[cellLocal] = 1;
+			}
+		}
+	} else n = st.cellSamples[cellLocal];
+	if (lastBatch && valid) {
+		const float k = rtm::rcp1_((float)n);
+		out[(size_t)y * P.width + x] = make_float4(a.x * k, a.y * k, a.z * k, 1.0f);
+	}
+}
+
+// The session's lists after a pass, in one workgroup: `live` (every cell still sampled, ascending) loses the cells that stopped, in place and in order,
+// and `trace` becomes the live cells inside the silhouette, in order -- the megakernel's job list of the next pass, bands of whole cells as before.
+// counts: [0] live cells, [1] listed cells, [2..3] valid pixels of the live cells outside the silhouette (64 bits; the next pass's culled samples per sample).
+#define RL_COMPACT_BLOCK 1024
+#define RL_COMPACT_PER 8
+__global__ void __launch_bounds__(RL_COMPACT_BLOCK)
+k_progressive_compact(uint32_t* __restrict__ live, uint32_t* __restrict__ trace, const uint8_t* __restrict__ stopped, const uint8_t* __restrict__ empty,
+                      uint32_t numLive, uint32_t width, uint32_t height, uint32_t cellsX, uint32_t* __restrict__ counts)
+{
+	constexpr uint32_t WAVES = RL_COMPACT_BLOCK / 64;
+	__shared__ uint32_t sLive[WAVES], sTrace[WAVES];
+	__shared__ unsigned long long sPx[WAVES];
+	const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+	uint32_t doneLive = 0, doneTrace = 0;   // entries written by the chunks before (the same in every thread)
+	unsigned long long px = 0;
+	for (uint32_t base = 0; base < numLive; base += RL_COMPACT_BLOCK * RL_COMPACT_PER) {
+		// a thread's RL_COMPACT_PER consecutive entries: all of the chunk is read before the barrier, and every entry moves to an index <= its own
+		uint32_t c[RL_COMPACT_PER], keep = 0, listed = 0;
+		#pragma unroll
+		for (int k = 0; k < RL_COMPACT_PER; ++k) {
+			const uint32_t i = base + t * RL_COMPACT_PER + (uint32_t)k;
+			c[k] = i < numLive ? live[i] : 0u;
+			if (i < numLive && !stopped[c[k]]) {
+				keep |= 1u << k;
+				if (!empty || !empty[c[k]]) listed |= 1u << k;
+				else { const uint32_t cx = c[k] % cellsX, cy = c[k] / cellsX; px += (unsigned long long)min(8u, width - cx * 8u) * min(8u, height - cy * 8u); }
+			}
+		}
+		const uint32_t nl = __popc(keep), nt = __popc(listed);
+		uint32_t il = nl, it = nt;   // inclusive scan over the wave
+		for (uint32_t off = 1; off < 64; off <<= 1) {
+			const uint32_t ul = __shfl_up(il, off), ut = __shfl_up(it, off);
+			if (lane >= off) { il += ul; it += ut; }
+		}
+		if (lane == 63) { sLive[wave] = il; sTrace[wave] = it; }
+		__syncthreads();
+		uint32_t ol = doneLive + il - nl, ot = doneTrace + it - nt;
+		for (uint32_t w = 0; w < WAVES; ++w) {
+			if (w < wave) { ol += sLive[w]; ot += sTrace[w]; }
+			doneLive += sLive[w]; doneTrace += sTrace[w];
+		}
+		#pragma unroll
+		for (int k = 0; k < RL_COMPACT_PER; ++k) {
+			if (keep >> k & 1u) live[ol++] = c[k];
+			if (listed >> k & 1u) trace[ot++] = c[k];
+		}
+		__syncthreads();   // (sLive / sTrace are re-used by the next chunk)
+	}
+	for (int off = 32; off > 0; off >>= 1) px += __shfl_down(px, off);
+	if (lane == 0) sPx[wave] = px;
+	__syncthreads();
+	if (t == 0) {
+		unsigned long long sum = 0;
+		for (uint32_t w = 0; w < WAVES; ++w) sum += sPx[w];
+		counts[0] = doneLive; counts[1] = doneTrace; counts[2] = (uint32_t)sum; counts[3] = (uint32_t)(sum >> 32);
 	}
 }
 

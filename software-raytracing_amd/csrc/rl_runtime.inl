@@ -42,6 +42,29 @@ struct DeviceScene {
 	SkyRot skyRot;
 	double boundsMin[3] = { 0, 0, 0 }, boundsMax[3] = { 0, 0, 0 };   // of all triangle vertices (CullCells)
 	bool boundsValid = false;                                        // triangles only, every coordinate finite
+	uint64_t serial = 0;                                             // 1, 2, 3, ... per upload in this process: a progressive session notices a scene uploaded anew
+};
+
+// A progressive render (include/raylib_amd.h RaylibAMD_BeginProgressive): what it was begun on, and its state on rank 0's device.  Every cell that is
+// still sampled ("live") has the same number of samples, `samples`: a pass renders the samples [samples, passEnd) of the live cells through
+// EnqueueRender, with the session's lists as the job list and k_progressive_resolve as the resolve.
+struct ProgressiveSession {
+	Scene* scene = nullptr;
+	uint64_t sceneSerial = 0;                      // DeviceScene::serial of the upload the session began on
+	const Image* sky = nullptr; uint64_t skyVersion = 0;
+	float accelT0 = 0.0f, accelT1 = 0.0f;          // the shutter interval the scene's boxes were built for
+	RenderRequest req;                             // settings, camera and seed as of Begin
+	uint32_t width = 0, height = 0, numCells = 0, cap = 1;
+	ProgressiveState st;                           // sums, moments, per-cell samples and stop flags (rl_render.hip) + the rule's parameters
+	uint32_t* live = nullptr;                      // the live cells, ascending
+	uint32_t* trace = nullptr;                     // ... those of them inside the scene's silhouette: the megakernel's job list
+	uint8_t* empty = nullptr;                      // per cell: outside the silhouette (the cull's flags)
+	uint32_t* counts = nullptr; uint32_t* countsHost = nullptr;   // k_progressive_compact's counts; pinned copy
+	uint32_t samples = 0, passes = 0, passEnd = 0;
+	uint32_t numLive = 0, numTrace = 0;
+	uint64_t emptyLivePixels = 0;                  // valid pixels of the live cells outside the silhouette
+	float emptyL[3] = { 0, 0, 0 }; uint32_t culledRays = 1;
+	bool seeded = false;                           // the lists hold the cull's result (its first pass)
 };
 
 namespace {
@@ -437,6 +460,8 @@ bool UploadScene(Scene& sc)
 	}
 
 	DeviceScene* D = new DeviceScene;
+	static uint64_t s_serial = 0;
+	D->serial = ++s_serial;   // (under the runtime lock)
 	{   // Rotator(yaw = 90).rotate rows, reference geom/transform.cc:47-65 (host libm, as the reference)
 		const float pi_f = (float)3.1415926535897932385;
 		const float ry = 90.0f * pi_f / 180.0f, rp = 0.0f * pi_f / 180.0f, rr = 0.0f * pi_f / 180.0f;
@@ -573,7 +598,9 @@ struct PendingRender {
 
 // One rank's share of a render, queued on its stream: counters reset, the megakernel (or k_aov) per sample batch, k_resolve,
 // end event, counter read-back.  `req.outDevice` receives the row-major frame (cellStride 1) or the rank's cells back to back.
-bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRender& pend)
+// With `prog` (rank 0, the whole frame): one pass of a progressive session -- the samples [prog->samples, prog->passEnd) of its live cells, its lists in place
+// of the cull's (seeded from the cull at its first pass), k_progressive_resolve in place of k_resolve, and k_progressive_compact behind the last batch.
+bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRender& pend, ProgressiveSession* prog = nullptr)
 {
 	DeviceScene* DS = sc.device;
 	DeviceSceneCopy* D = DS->copy[(size_t)R.devSlot];
@@ -588,6 +615,7 @@ bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRende
 	const uint32_t numSlots = numLocalCells * 64u;
 	const bool rowMajor = (stride == 1 && req.cellFirst == 0 && !req.cellMajor);
 	const uint32_t SPP = (uint32_t)(st.samplesPerPixel > 1 ? st.samplesPerPixel : 1);
+	const uint32_t sBegin = prog ? prog->samples : 0u, sEnd = prog ? prog->passEnd : SPP;   // the samples this call renders
 	const bool pathTrace = (st.renderMode == RAYLIB_RENDERMODE_Default);
 	pend.ctx = &R; pend.pathTrace = pathTrace;
 	const int q = req.slot & 1;
@@ -626,7 +654,7 @@ bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRende
 		pend.pathsPerWave = plan.pathsPerWave; pend.treeWidth = plan.treeWidth; pend.nodeBytes = plan.nodeBytes;
 		// ---- cells that cannot see the scene leave the job list (CullCells) ----
 		uint32_t numActive = numLocalCells;
-		{
+		if (!prog || !prog->seeded) {
 			// what the decision depends on: an unchanged view keeps the lists the slot already holds on the device
 			std::vector<unsigned char> key;
 			auto put = [&](const void* ptr, size_t n) { const unsigned char* b = (const unsigned char*)ptr; key.insert(key.end(), b, b + n); };
@@ -671,6 +699,24 @@ bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRende
 			}
 			pend.culledCells = numLocalCells - numActive; pend.listedCells = numActive;
 		}
+		if (prog) {
+			if (!prog->seeded) {   // the session's first pass: its lists start from the cull's (every cell is live)
+				if (numActive < numLocalCells) {
+					HIP_OK(hipMemcpyAsync(prog->trace, R.cellList[q], (size_t)numActive * sizeof(uint32_t), hipMemcpyDeviceToDevice, R.stream));
+					HIP_OK(hipMemcpyAsync(prog->empty, R.cellList[q] + R.cellListCells[q], numLocalCells, hipMemcpyDeviceToDevice, R.stream));
+					prog->emptyLivePixels = R.cullEmptyPixels[q]; prog->culledRays = R.cullRays[q];
+					for (int k = 0; k < 3; ++k) prog->emptyL[k] = R.cullL[q][k];
+				}
+				prog->numLive = numLocalCells; prog->numTrace = numActive;
+				prog->seeded = true;
+			}
+			numActive = prog->numTrace;
+			P.activeCells = prog->trace; P.cellEmpty = prog->empty; P.numActiveCells = numActive;
+			P.emptyL[0] = prog->emptyL[0]; P.emptyL[1] = prog->emptyL[1]; P.emptyL[2] = prog->emptyL[2];
+			P.emptySky = traceView.sky ? 1u : 0u;
+			pend.culledSamples = prog->emptyLivePixels * (uint64_t)(sEnd - sBegin); pend.culledRaysPerSample = prog->culledRays; pend.culledSkyTexels = traceView.sky ? 1u : 0u;
+			pend.culledCells = prog->numLive - prog->numTrace; pend.listedCells = prog->numTrace;
+		}
 		int blocksPerCU = 0;
 		{
 			auto it = R.occupancy.find((const void*)traceKernel);
@@ -680,12 +726,12 @@ bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRende
 				if (getenv("RAYLIB_PRINT_OCCUPANCY")) Log("megakernel (%u paths per lane, tree width %u): %d workgroups per CU", plan.pathsPerWave / 64u, plan.treeWidth, blocksPerCU);
 			} else blocksPerCU = it->second;
 		}
-		const uint32_t batch = PlanLaunch(numLocalCells, numActive, SPP, 0, R.numCUs, blocksPerCU, plan, knobs).batch;
-		if (!Grow(R.samples, R.samplesBytes, (size_t)numSlots * sizeof(SampleRGB) * batch)) return false;
-		if (batch < SPP && !Grow(R.accum, R.accumBytes, (size_t)numSlots * sizeof(float4))) return false;
+		const uint32_t batch = PlanLaunch(numLocalCells, numActive, sEnd, sBegin, R.numCUs, blocksPerCU, plan, knobs).batch;
+		if (!Grow(R.samples, R.samplesBytes, (size_t)numSlots * sizeof(SampleRGB) * std::min(batch, sEnd - sBegin))) return false;
+		if (!prog && batch < SPP && !Grow(R.accum, R.accumBytes, (size_t)numSlots * sizeof(float4))) return false;
 		const int depthSlots = st.maxPathLength > 1 ? st.maxPathLength : 1;
-		for (uint32_t s0 = 0; s0 < SPP; s0 += batch) {
-			const LaunchPlan L = PlanLaunch(numLocalCells, numActive, SPP, s0, R.numCUs, blocksPerCU, plan, knobs);
+		for (uint32_t s0 = sBegin; s0 < sEnd; s0 += batch) {
+			const LaunchPlan L = PlanLaunch(numLocalCells, numActive, sEnd, s0, R.numCUs, blocksPerCU, plan, knobs);
 			const uint32_t cnt = L.sampleCount;
 			P.sampleBegin = s0; P.sampleCount = cnt;
 			P.magicSamples = cnt > 1 ? (uint32_t)(0x100000000ull / cnt) : 0xFFFFFFFFu;
@@ -705,16 +751,24 @@ bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRende
 			}
 			HIP_OK(hipEventRecord(R.ev[q][3], R.stream));
 			const uint32_t rblocks = (numSlots + RL_BLOCK - 1) / RL_BLOCK;
-			hipLaunchKernelGGL(k_resolve, dim3(rblocks), dim3(RL_BLOCK), 0, R.stream,
-			                   P, traceView, DS->skyRot, R.samples, R.accum, out, (int)(s0 == 0), (int)(s0 + cnt >= SPP));
+			if (prog) hipLaunchKernelGGL(k_progressive_resolve, dim3(rblocks), dim3(RL_BLOCK), 0, R.stream,
+			                             P, traceView, DS->skyRot, R.samples, prog->st, out, (int)(s0 + cnt >= sEnd));
+			else hipLaunchKernelGGL(k_resolve, dim3(rblocks), dim3(RL_BLOCK), 0, R.stream,
+			                        P, traceView, DS->skyRot, R.samples, R.accum, out, (int)(s0 == 0), (int)(s0 + cnt >= SPP));
 			HIP_OK(hipGetLastError());
 			++pend.launches;
-			if (s0 + cnt < SPP) {   // the event pair is reused by the next batch; the last batch's pair is read after the one final sync
+			if (s0 + cnt < sEnd) {   // the event pair is reused by the next batch; the last batch's pair is read after the one final sync
 				HIP_OK(hipEventSynchronize(R.ev[q][3]));
 				float ms = 0.0f;
 				HIP_OK(hipEventElapsedTime(&ms, R.ev[q][2], R.ev[q][3]));
 				pend.traceMs += ms;
 			} else pend.lastBatchPending = true;
+		}
+		if (prog) {   // the cells that stopped leave the lists; the counts go to pinned memory, where the session reads them once the pass is waited for
+			hipLaunchKernelGGL(k_progressive_compact, dim3(1), dim3(RL_COMPACT_BLOCK), 0, R.stream,
+			                   prog->live, prog->trace, (const uint8_t*)prog->st.stopped, (const uint8_t*)prog->empty, prog->numLive, W, H, cellsX, prog->counts);
+			HIP_OK(hipGetLastError());
+			HIP_OK(hipMemcpyAsync(prog->countsHost, prog->counts, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, R.stream));
 		}
 	}
 	HIP_OK(hipEventRecord(R.ev[q][1], R.stream));
@@ -1287,6 +1341,131 @@ bool DevicePostProcess(Image& img)
 	img.Touch();
 	Log("Max white luminance: %f", white);
 	return true;
+}
+
+// ---- progressive sessions: rank 0's device and stream, whatever RAYLIB_NUM_GPUS says (a pass is one EnqueueRender of the whole frame) ----
+namespace {
+void FreeProgressive(ProgressiveSession* S)
+{
+	(void)hipFree(S->st.sum); (void)hipFree(S->st.s1); (void)hipFree(S->st.s2); (void)hipFree(S->st.cellSamples); (void)hipFree(S->st.stopped);
+	(void)hipFree(S->live); (void)hipFree(S->trace); (void)hipFree(S->empty); (void)hipFree(S->counts);
+	if (S->countsHost) (void)hipHostFree(S->countsHost);
+	delete S;
+}
+bool AllocProgressive(ProgressiveSession& S)
+{
+	const size_t slots = (size_t)S.numCells * 64u, cells = S.numCells;
+	HIP_OK(hipMalloc((void**)&S.st.sum, slots * sizeof(float4)));
+	HIP_OK(hipMalloc((void**)&S.st.s1, slots * sizeof(float)));
+	HIP_OK(hipMalloc((void**)&S.st.s2, slots * sizeof(float)));
+	HIP_OK(hipMalloc((void**)&S.st.cellSamples, cells * sizeof(uint32_t)));
+	HIP_OK(hipMalloc((void**)&S.st.stopped, cells));
+	HIP_OK(hipMalloc((void**)&S.live, cells * sizeof(uint32_t)));
+	HIP_OK(hipMalloc((void**)&S.trace, cells * sizeof(uint32_t)));
+	HIP_OK(hipMalloc((void**)&S.empty, cells));
+	HIP_OK(hipMalloc((void**)&S.counts, 4 * sizeof(uint32_t)));
+	HIP_OK(hipHostMalloc((void**)&S.countsHost, 4 * sizeof(uint32_t), hipHostMallocDefault));
+	HIP_OK(hipMemset(S.st.sum, 0, slots * sizeof(float4)));
+	HIP_OK(hipMemset(S.st.s1, 0, slots * sizeof(float)));
+	HIP_OK(hipMemset(S.st.s2, 0, slots * sizeof(float)));
+	HIP_OK(hipMemset(S.st.cellSamples, 0, cells * sizeof(uint32_t)));
+	HIP_OK(hipMemset(S.st.stopped, 0, cells));
+	HIP_OK(hipMemset(S.empty, 0, cells));
+	std::vector<uint32_t> all(cells);
+	for (size_t c = 0; c < cells; ++c) all[c] = (uint32_t)c;
+	HIP_OK(hipMemcpy(S.live, all.data(), cells * sizeof(uint32_t), hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(S.trace, all.data(), cells * sizeof(uint32_t), hipMemcpyHostToDevice));
+	return true;
+}
+} // namespace
+
+ProgressiveSession* DeviceProgressiveBegin(Scene& sc, const RenderRequest& req, float threshold, uint32_t minSamples)
+{
+	std::lock_guard<std::mutex> lk(g_rt.lock);
+	if (!EnsureRuntime()) return nullptr;
+	if (hipSetDevice(Rank0().device) != hipSuccess) return nullptr;
+	if (!UploadScene(sc) || !SyncSky(sc)) return nullptr;
+	(void)DrainLocked();
+	ProgressiveSession* S = new ProgressiveSession;
+	S->scene = &sc; S->sceneSerial = sc.device->serial;
+	S->sky = sc.sky; S->skyVersion = sc.sky ? sc.sky->version : 0;
+	S->accelT0 = sc.accelT0; S->accelT1 = sc.accelT1;
+	S->req = req; S->req.cellFirst = 0; S->req.cellStride = 1; S->req.cellMajor = false; S->req.slot = 0;
+	S->req.outDevice = nullptr; S->req.outHostRGBA = nullptr; S->req.callerOwnsOut = false;
+	S->width = req.settings.viewportWidth; S->height = req.settings.viewportHeight;
+	S->numCells = ((S->width + 7) / 8) * ((S->height + 7) / 8);
+	S->cap = (uint32_t)(req.settings.samplesPerPixel > 1 ? req.settings.samplesPerPixel : 1);
+	S->st.threshold = threshold; S->st.minSamples = minSamples;
+	S->numLive = S->numTrace = S->numCells;
+	if (!AllocProgressive(*S)) { Log("RaylibAMD_BeginProgressive: the session's buffers could not be allocated"); FreeProgressive(S); return nullptr; }
+	return S;
+}
+
+int32_t DeviceProgressiveStep(ProgressiveSession& S, uint32_t samples, void* outDevice, RaylibAMDStats& stats, bool& rendered)
+{
+	std::lock_guard<std::mutex> lk(g_rt.lock);
+	const auto t0 = std::chrono::steady_clock::now();
+	rendered = false;
+	if (!g_rt.ok) return -1;
+	Scene& sc = *S.scene;
+	// what the frame depends on must be what the session began on: anything else would make a mosaic of two scenes
+	if (!sc.device || sc.device->serial != S.sceneSerial || sc.accelT0 != S.accelT0 || sc.accelT1 != S.accelT1) {
+		Log("RaylibAMD_ProgressiveStep: the scene changed since the session began (finalized, sun or shutter); the image is unchanged");
+		return -1;
+	}
+	if (sc.sky != S.sky || (sc.sky && sc.sky->version != S.skyVersion)) {
+		Log("RaylibAMD_ProgressiveStep: the scene's sky panorama changed since the session began; the image is unchanged");
+		return -1;
+	}
+	if (S.samples >= S.cap || S.numLive == 0) return 0;
+	const uint32_t cnt = std::min(samples, S.cap - S.samples);
+	(void)DrainLocked();
+	g_deferredUnreported = false;   // (the numbers the caller reads next are this pass's)
+	if (hipSetDevice(Rank0().device) != hipSuccess || !SyncSky(sc)) return -1;
+	S.passEnd = S.samples + cnt;
+	RenderRequest req = S.req;
+	req.outDevice = outDevice;
+	PendingRender pend;
+	bool ok = EnqueueRender(Rank0(), sc, req, pend, &S);
+	if (pend.ctx) ok = FinishRender(pend, stats) && ok;
+	else (void)hipStreamSynchronize(Rank0().stream);
+	if (!ok) return -1;
+	rendered = true;
+	S.samples += cnt; ++S.passes;
+	S.numLive = S.countsHost[0]; S.numTrace = S.countsHost[1];
+	S.emptyLivePixels = (uint64_t)S.countsHost[2] | ((uint64_t)S.countsHost[3] << 32);
+	stats.ranks = 1; stats.devices = 1;
+	stats.numNodes = (uint32_t)sc.bvh.nodes.size(); stats.numTriangles = (uint32_t)sc.triangles.size(); stats.bvhDepth = sc.bvh.depth;
+	stats.wallMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	return S.samples >= S.cap ? 0 : (int32_t)S.numLive;
+}
+
+// The session's per-cell samples and stop flags, and the moments of y per pixel in row-major order (the device keeps them cell-major).
+bool DeviceProgressiveExport(ProgressiveSession& S, uint32_t* cellSamples, uint8_t* cellStopped, float* sumY, float* sumY2)
+{
+	std::lock_guard<std::mutex> lk(g_rt.lock);
+	if (!g_rt.ok) return false;
+	HIP_OK(hipSetDevice(Rank0().device));
+	if (cellSamples) HIP_OK(hipMemcpy(cellSamples, S.st.cellSamples, (size_t)S.numCells * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (cellStopped) HIP_OK(hipMemcpy(cellStopped, S.st.stopped, S.numCells, hipMemcpyDeviceToHost));
+	const uint32_t cellsX = (S.width + 7) / 8;
+	std::vector<float> slots((size_t)S.numCells * 64u);
+	for (int m = 0; m < 2; ++m) {
+		float* dst = m ? sumY2 : sumY;
+		if (!dst) continue;
+		HIP_OK(hipMemcpy(slots.data(), m ? S.st.s2 : S.st.s1, slots.size() * sizeof(float), hipMemcpyDeviceToHost));
+		for (uint32_t y = 0; y < S.height; ++y)
+			for (uint32_t x = 0; x < S.width; ++x) dst[(size_t)y * S.width + x] = slots[((size_t)(y / 8) * cellsX + x / 8) * 64u + (y % 8) * 8u + x % 8];
+	}
+	return true;
+}
+
+void DeviceProgressiveEnd(ProgressiveSession* S)
+{
+	if (!S) return;
+	std::lock_guard<std::mutex> lk(g_rt.lock);
+	if (g_rt.ok) (void)hipSetDevice(Rank0().device);
+	FreeProgressive(S);
 }
 
 void DeviceReleaseScene(DeviceScene* D)

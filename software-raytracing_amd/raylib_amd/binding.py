@@ -28,6 +28,11 @@ class DenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("sigmaColor", C.c_float), ("sigmaNormal", C.c_float), ("sigmaAlbedo", C.c_float)]
 
 
+class ProgressiveParams(C.Structure):
+    """include/raylib_amd.h RaylibAMDProgressiveParams."""
+    _fields_ = [("threshold", C.c_float), ("minSamples", C.c_uint32)]
+
+
 class Stats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("nodesVisited", C.c_uint64), ("trisTested", C.c_uint64),
                 ("shadedHits", C.c_uint64), ("texFetches", C.c_uint64), ("cameraSamples", C.c_uint64),
@@ -161,6 +166,12 @@ _EXPORTS = {
     "RaylibAMD_DenoiseHost": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                           C.POINTER(DenoiseParams), C.POINTER(C.c_float)]),
     "RaylibAMD_EnableDenoiser": (None, [C.c_int32]),
+    "RaylibAMD_BeginProgressive": (C.c_size_t, [C.POINTER(RendererSettings), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ProgressiveParams)]),
+    "RaylibAMD_ProgressiveStep": (C.c_int32, [C.c_size_t, C.c_uint32]),
+    "RaylibAMD_ProgressiveExport": (C.c_int32, [C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "RaylibAMD_EndProgressive": (C.c_int32, [C.c_size_t]),
+    "RaylibAMD_ProgressiveDecideHost": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                    C.POINTER(ProgressiveParams), C.POINTER(C.c_uint8)]),
 }
 RAYLIB_H_EXPORTS = [k for k in _EXPORTS if k.startswith("Raylib_")]
 RAYLIB_AMD_H_EXPORTS = [k for k in _EXPORTS if k.startswith("RaylibAMD_")]
@@ -190,6 +201,55 @@ def create_material(lib, mat):
     """mat: one record of the oracle's MAT_DTYPE layout (type, albedo, roughness, metallic, emissive, ior, transmission, fuzziness)."""
     return lib.RaylibAMD_CreateMaterial(int(mat["type"]), _f3(mat["albedo"]), float(mat["roughness"]), float(mat["metallic"]),
                                         _f3(mat["emissive"]), float(mat["ior"]), _f3(mat["transmission"]), float(mat["fuzziness"]))
+
+
+def progressive_decide_host(lib, width, height, cell_samples, sum_y, sum_y2, threshold=None, min_samples=2):
+    """RaylibAMD_ProgressiveDecideHost: one bool per cell (cellsY, cellsX); threshold None = no params (uniform).  None when the call refuses."""
+    cells = np.ascontiguousarray(cell_samples, np.uint32)
+    s1, s2 = np.ascontiguousarray(sum_y, np.float32), np.ascontiguousarray(sum_y2, np.float32)
+    out = np.zeros(((height + 7) // 8, (width + 7) // 8), np.uint8)
+    prm = None if threshold is None else C.byref(ProgressiveParams(float(threshold), int(min_samples)))
+    ok = lib.RaylibAMD_ProgressiveDecideHost(width, height, cells.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(s1), _fp(s2), prm,
+                                             out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    return out.astype(bool) if ok == 1 else None
+
+
+class Progressive:
+    """A progressive session (include/raylib_amd.h RaylibAMD_BeginProgressive) on a session's scene and camera, rendering into its own image:
+    step(n) -> live cells (0 = finished), frame() -> (H, W, 4) float32, export() -> (cell samples, stopped, S1, S2)."""
+
+    def __init__(self, ses, w, h, spp, max_path=5, tmin=1e-4, mode=RENDERMODE_DEFAULT, threshold=None, min_samples=2, image=None):
+        self.lib, self.w, self.h = ses.lib, int(w), int(h)
+        st = RendererSettings(int(w), int(h), int(spp), int(max_path), float(tmin), int(mode))
+        self.own_image = image is None
+        self.image = self.lib.Raylib_CreateImage(w, h) if image is None else image
+        prm = None if threshold is None else C.byref(ProgressiveParams(float(threshold), int(min_samples)))
+        self.handle = self.lib.RaylibAMD_BeginProgressive(C.byref(st), ses.scene, ses.camera, self.image, prm)
+
+    def step(self, samples):
+        return self.lib.RaylibAMD_ProgressiveStep(self.handle, int(samples))
+
+    def frame(self):
+        out = np.zeros((self.h, self.w, 4), np.float32)
+        self.lib.RaylibAMD_DumpImageRGBA(self.image, _fp(out))
+        return out
+
+    def export(self):
+        cy, cx = (self.h + 7) // 8, (self.w + 7) // 8
+        n = np.zeros((cy, cx), np.uint32)
+        stopped = np.zeros((cy, cx), np.uint8)
+        s1 = np.zeros((self.h, self.w), np.float32)
+        s2 = np.zeros((self.h, self.w), np.float32)
+        ok = self.lib.RaylibAMD_ProgressiveExport(self.handle, n.ctypes.data_as(C.POINTER(C.c_uint32)), stopped.ctypes.data_as(C.POINTER(C.c_uint8)), _fp(s1), _fp(s2))
+        assert ok == 1
+        return n, stopped.astype(bool), s1, s2
+
+    def close(self):
+        r = self.lib.RaylibAMD_EndProgressive(self.handle) if self.handle else 0
+        if self.own_image:
+            self.lib.Raylib_DestroyImage(self.image)
+        self.handle = 0
+        return r
 
 
 class ProceduralSession:

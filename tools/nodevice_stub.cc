@@ -22,4 +22,8 @@ bool DeviceVerifyExactMath(int, uint64_t*, uint64_t*) { return false; }
 // rl_denoise.hip is a HIP unit too: the device filter fails, and its host restatement (RaylibAMD_DenoiseHost) is not part of this build
 bool DeviceDenoise(Image&, bool, Image*, Image*, Image&, const RaylibAMDDenoiseParams&) { return false; }
 void DenoiseHost(uint32_t, uint32_t, const float*, bool, const float*, const float*, const RaylibAMDDenoiseParams&, float*) {}
+ProgressiveSession* DeviceProgressiveBegin(Scene&, const RenderRequest&, float, uint32_t) { return nullptr; }
+int32_t DeviceProgressiveStep(ProgressiveSession&, uint32_t, void*, RaylibAMDStats&, bool& rendered) { rendered = false; return -1; }
+bool DeviceProgressiveExport(ProgressiveSession&, uint32_t*, uint8_t*, float*, float*) { return false; }
+void DeviceProgressiveEnd(ProgressiveSession*) {}
 }
