@@ -160,7 +160,8 @@ RAYLIB_API int32_t RaylibAMD_CullCells(CameraHandle camera, const float* bounds,
  * which = 2: a / b with the divisor's correctly rounded reciprocal in hand (csrc/rl_math.h div_by_: the pixel -> [0, 1) divisions of a camera ray and the two
  * barycentric divisions of a triangle test) -- every bit pattern as numerator of a set of divisors and as divisor of a set of numerators, wherever the
  * sequence's stated conditions hold; which = 3: the triangle test's short barycentric form (csrc/rl_render.hip Barycentric) against the two divisions and
- * the reference's test, every bit pattern in each of its three operands: same verdict, same quotients.
+ * the reference's test, every bit pattern in each of its three operands: same verdict, same quotients; which = 4: acosf and tanf with their divisions in the
+ * short form (csrc/rl_glibc_math.h acosf_t / tanf_t, RL_EXACT_DIV bit 4) against the same functions with IEEE divisions, every bit pattern.
  * outMismatches: inputs whose results differ (a NaN may differ in payload); outFirstBits: the smallest such bit pattern.  Returns 1 when the sweep ran. */
 RAYLIB_API int32_t RaylibAMD_VerifyExactMath(int32_t which, uint64_t* outMismatches, uint64_t* outFirstBits);
 

@@ -47,6 +47,16 @@ RLM_FN double fma_(double a, double b, double c) { return __builtin_fma(a, b, c)
 #ifndef RL_EXACT_FAST_RCP_SQRT
 #define RL_EXACT_FAST_RCP_SQRT 1
 #endif
+// the short reciprocal without its guard (device): RN(1 / x) for 2^-126 <= |x| < 2^126, the caller's to guarantee
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ static float rcp1_in_range_(float x)
+{
+	const float r0 = __builtin_amdgcn_rcpf(x);
+	return __builtin_fmaf(__builtin_fmaf(-x, r0, 1.0f), r0, r0);
+}
+#else
+RLM_FN float rcp1_in_range_(float x) { return 1.0f / x; }
+#endif
 #if defined(__HIP_DEVICE_COMPILE__) && RL_EXACT_FAST_RCP_SQRT
 // (the out-of-range path inline: as a call -- __noinline__ -- every one of the ~45 sites constrains the register allocation around it, and the Cornell
 // frame took 14.75 ms instead of 14.00; measured, round 3)
@@ -57,10 +67,8 @@ __device__ RL_EXACT_SLOW_ATTR static float rcp1_slow_(float x) { return 1.0f / x
 __device__ RL_EXACT_SLOW_ATTR static float sqrt_slow_(float x) { return __builtin_sqrtf(x); }
 __device__ __forceinline__ static float rcp1_(float x)
 {
-	if (((asuint(x) & 0x7fffffffu) - 0x00800000u) < (0x7e800000u - 0x00800000u)) {   // 2^-126 <= |x| < 2^126
-		const float r0 = __builtin_amdgcn_rcpf(x);
-		return __builtin_fmaf(__builtin_fmaf(-x, r0, 1.0f), r0, r0);
-	}
+	if (((asuint(x) & 0x7fffffffu) - 0x00800000u) < (0x7e800000u - 0x00800000u))   // 2^-126 <= |x| < 2^126
+		return rcp1_in_range_(x);
 	return rcp1_slow_(x);
 }
 __device__ __forceinline__ static float sqrtf_(float x)
@@ -77,6 +85,33 @@ RLM_FN float rcp1_(float x) { return 1.0f / x; }
 RLM_FN float sqrtf_(float x) { return __builtin_sqrtf(x); }
 #endif
 RLM_FN float fabsf_(float x) { return __builtin_fabsf(x); }
+// Divisions in the short form of rl_math.h (rtm::div_by_ with y = rcp1_in_range_(b)), selected by the bits of RL_EXACT_DIV:
+//   1: the scattering event's quotients with one divisor for several numerators or divisors in a provable range (rl_render.hip)
+//   2: GeometryBeckmann's `dot(V, H) / dot(V, N) <= 0` as a predicate on signs, zeros and NaN (rl_render.hip)
+//   4: the divisions inside acosf_ and tanf_ below, UNGUARDED: every one of their 2^32 inputs gives the bits of the IEEE form
+//      (RaylibAMD_VerifyExactMath mode 4 compares acosf_t<true> / tanf_t<true> with acosf_t<false> / tanf_t<false>, tests/test_exact_div.py)
+// RL_EXACT_DIV=0 keeps the compiler's IEEE expansions everywhere (the A/B baseline).  The pool kernel's unit keeps them too (rl_render.hip).
+// Measured on the Cornell frame (k_trace, 3 interleaved runs of 100 steps each): 11.89 - 11.91 ms with none, bit 1 11.70 - 11.72,
+// bit 4 11.70 - 11.73, bit 2 11.86 - 11.94 (no gain beyond the noise: off by default), bits 1 + 2 + 4 11.49 - 11.56.
+#ifndef RL_EXACT_DIV
+#define RL_EXACT_DIV 5
+#endif
+// a / b; with FAST on the device the short form, which the sweep above has to show exact for every input of the function it sits in
+template <bool FAST> RLM_FN float qdiv_(float a, float b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+	if (FAST) { const float y = rcp1_in_range_(b), q0 = a * y; return __builtin_fmaf(__builtin_fmaf(-b, q0, a), y, q0); }
+#endif
+	return a / b;
+}
+// -1.0f / b (negation is exact, so -RN(1 / b) is the quotient)
+template <bool FAST> RLM_FN float qneg_rcp_(float b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+	if (FAST) return -rcp1_in_range_(b);
+#endif
+	return -1.0f / b;
+}
 
 // ---------------------------------------------------------------------------------------
 // tables (function-local statics would not work on device; kept as macros expanding to
@@ -410,7 +445,7 @@ RLM_FN void sincosf_signs(float y, bool* sinNeg, bool* cosNeg)
 // ---------------------------------------------------------------------------------------
 // fdlibm-derived float routines (glibc sysdeps/ieee754/flt-32/e_acosf.c, e_asinf.c,
 // s_atanf.c, e_atan2f.c, s_tanf.c + k_tanf.c + e_rem_pio2f.c); float arithmetic, no FMA.
-RLM_FN float acosf_(float x)
+template <bool FD> RLM_FN float acosf_t(float x)
 {
 	// Same operations per input as glibc's three-way branch (|x|<0.5, x<-0.5, x>0.5), arranged so that a
 	// wave whose lanes fall into different ranges evaluates the shared rational p(z)/q(z) once: only the
@@ -430,7 +465,7 @@ RLM_FN float acosf_(float x)
 	const float z = small ? x * x : (neg ? (one + x) * 0.5f : (one - x) * 0.5f);
 	const float p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
 	const float q = one + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
-	const float r = p / q;
+	const float r = qdiv_<FD>(p, q);   // q in [0.22, 1]
 	const float s = sqrtf_(z);
 	// |x| < 0.5
 	const float rSmall = pio2_hi - (x - (pio2_lo - r * x));
@@ -439,11 +474,12 @@ RLM_FN float acosf_(float x)
 	const float rNeg = pi - 2.0f * (s + wNeg);
 	// x > 0.5
 	const float df = asfloat(asuint(s) & 0xfffff000u);
-	const float c = (z - df * df) / (s + df);
+	const float c = qdiv_<FD>(z - df * df, s + df);   // for x > 0.5: s + df >= 2^-12, z - df * df is +0 or >= 2^-49
 	const float wPos = r * s + c;
 	const float rPos = 2.0f * (df + wPos);
 	return small ? rSmall : (neg ? rNeg : rPos);
 }
+RLM_FN float acosf_(float x) { return acosf_t<(RL_EXACT_DIV & 4) != 0>(x); }
 
 // asinf (glibc e_asinf.c: glibc's own minimax p0..p4, not fdlibm's rational)
 RLM_FN float asinf_(float x)
@@ -571,7 +607,7 @@ RLM_FN float atan2f_(float y, float x)
 }
 
 // __kernel_tanf (glibc k_tanf.c)
-RLM_FN float kernel_tanf(float x, float y, int iy)
+template <bool FD> RLM_FN float kernel_tanf(float x, float y, int iy)
 {
 	const float one = 1.0f, pio4 = 7.8539812565e-01f, pio4lo = 3.7748947079e-08f;
 	const float T[13] = { 3.3333334327e-01f, 1.3333334029e-01f, 5.3968254477e-02f, 2.1869488060e-02f, 8.8632395491e-03f,
@@ -603,14 +639,14 @@ RLM_FN float kernel_tanf(float x, float y, int iy)
 	w = x + r;
 	if (ix >= 0x3f2ca140) {
 		v = (float)iy;
-		return (float)(1 - ((hx >> 30) & 2)) * (v - 2.0f * (x - (w * w / (w + v) - r)));
+		return (float)(1 - ((hx >> 30) & 2)) * (v - 2.0f * (x - (qdiv_<FD>(w * w, w + v) - r)));   // |w + v| in [0.89, 1.11], w >= 2^-13
 	}
 	if (iy == 1) return w;
 	{
 		float a, t;
 		z = asfloat(asuint(w) & 0xfffff000u);
 		v = r - (z - x);
-		t = a = -1.0f / w;
+		t = a = qneg_rcp_<FD>(w);   // |w| in [2^-13, 0.81]
 		t = asfloat(asuint(t) & 0xfffff000u);
 		s = 1.0f + t * z;
 		return t + a * (s + t * v);
@@ -620,7 +656,7 @@ RLM_FN float kernel_tanf(float x, float y, int iy)
 // tanf (glibc 2.35 s_tanf.c): range reduction shares sinf/cosf's reduce_fast / reduce_large
 // (double arithmetic, NOT fused: tanf has no FMA ifunc variant), then fdlibm's __kernel_tanf
 // on the float head/tail of the reduced argument.
-RLM_FN float tanf_(float x)
+template <bool FD> RLM_FN float tanf_t(float x)
 {
 	const double hpi_inv = 0x1.45f306dc9c883p+23, hpi = 0x1.921fb54442d18p+0;
 	const uint32_t ux = asuint(x);
@@ -641,8 +677,9 @@ RLM_FN float tanf_(float x)
 	}
 	float y0 = (float)dx;
 	float y1 = (float)(dx - (double)y0);
-	return kernel_tanf(y0, y1, 1 - ((n & 1) << 1));
+	return kernel_tanf<FD>(y0, y1, 1 - ((n & 1) << 1));
 }
+RLM_FN float tanf_(float x) { return tanf_t<(RL_EXACT_DIV & 4) != 0>(x); }
 
 #if defined(RLM_LDS_TABLES) && defined(__HIPCC__)
 // First statement of every kernel that reaches expf_ / logf_ / powf_ (all threads of the block must call it: it ends in a barrier).

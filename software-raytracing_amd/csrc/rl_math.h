@@ -112,5 +112,7 @@ __device__ __forceinline__ float sqrt_(float x) { return rlm::sqrtf_(x); }
 //   2^-126 <= |b| <= 2^126 (y normal),  |a| >= 2^-102 (the residual a - q0 b, a multiple of 2^(exponent(a) - 47), is exact: RaylibAMD_VerifyExactMath's sweep fails at 2^-103),  2^-126 <= |a / b| < 2^127.
 // a = +0 gives +0 like the division (for positive b); other zeros, infinities and NaN are the caller's to keep away or to not care about.
 __device__ __forceinline__ float div_by_(float a, float b, float y) { const float q0 = a * y; return __builtin_fmaf(__builtin_fmaf(-b, q0, a), y, q0); }
+// whether p holds on any active lane of the wave: a branch on it is a scalar one (s_cbranch), taken or skipped by the whole wave
+__device__ __forceinline__ bool wave_any_(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0; }
 
 }} // namespace rl::rtm

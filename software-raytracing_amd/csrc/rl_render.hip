@@ -26,6 +26,12 @@
 #include <hip/hip_runtime.h>
 
 #include "rl_host.h"
+// The pool schedule's unit keeps the compiler's IEEE divisions (RL_EXACT_DIV, rl_glibc_math.h): the short forms were measured on k_trace only, and the pool
+// kernel's register allocation has answered arithmetic savings with losses before (Makefile, POOLFLAGS).
+#ifdef RL_TU_POOL
+#undef RL_EXACT_DIV
+#define RL_EXACT_DIV 0
+#endif
 // the exact-libm tables (rl_glibc_math.h) in LDS: 640 B per workgroup, filled by rlm_fill_lds_tables() at the top of every kernel that
 // evaluates expf / logf / powf.  A microfacet scattering event makes ~16 such look-ups; from constant memory each one is a gather through
 // the vector memory pipeline with a full s_waitcnt behind it.
@@ -960,8 +966,58 @@ __device__ RL_ERF_ATTR float Erf(float x)
 	return sign * y;
 }
 __device__ __forceinline__ float SinThetaL(V3 w) { return rtm::sqrt_(fmaxf(0.0f, 1.0f - w.z * w.z)); }
+
+// ---- the scattering event's divisions in the short form (RL_EXACT_DIV bits 1 and 2, rl_glibc_math.h) ----
+// An IEEE division is 36 VALU issue cycles; y = RN(1 / b) without rcp1_'s guard is 13 and each quotient rtm::div_by_(a, b, y) 7 more, a compare 4.4 (tools/valu_calib.hip).
+// div_by_ is exact only under its conditions (rl_math.h): 2^-126 <= |b| < 2^126 here, |a| >= 2^-102 and a normal quotient.  The sites below take the short form where
+// the divisor's range is known and test what is not with compares that fail on NaN; if any lane fails, the whole wave takes the IEEE divisions in a branch on the
+// ballot (rarely taken: zero or tiny numerators, degenerate directions).  A site with nothing known about its divisor would pay two compares for it plus the
+// numerator's and the quotient's (>= 20 cycles of guard, 41 in all): DistributionBeckmann, the pdf and the Newton step keep their divisions.
+// |q| in [2^-91, 2^126): for a divisor in [2^-10, 8] this proves |a| >= 2^-102 and a normal quotient; a q computed from a zero, tiny, huge, infinite or NaN
+// numerator or a NaN divisor falls outside (those stay within a few ulps of, or as far out as, the true quotient)
+__device__ __forceinline__ bool QuotientInRange(float q) { return fabsf(q) >= 0x1p-91f && fabsf(q) < 0x1p126f; }
+// the specular term's vec3 / float: b = 4 |N.Wi| |N.Wo| + 0.001 lies in [0.001, 4.001] (unit vectors) -- or is NaN
+__device__ __forceinline__ V3 DivSpecular(V3 a, float b)
+{
+#if RL_EXACT_DIV & 1
+	const float y = rlm::rcp1_in_range_(b);
+	const V3 q = v3(rtm::div_by_(a.x, b, y), rtm::div_by_(a.y, b, y), rtm::div_by_(a.z, b, y));
+	if (rtm::wave_any_(!(QuotientInRange(q.x) && QuotientInRange(q.y) && QuotientInRange(q.z)))) return a / b;
+	return q;
+#else
+	return a / b;
+#endif
+}
 __device__ __forceinline__ float CosPhi(V3 w) { float s = SinThetaL(w); return (s == 0) ? 1 : Clampf(w.x / s, -1, 1); }
 __device__ __forceinline__ float SinPhi(V3 w) { float s = SinThetaL(w); return (s == 0) ? 0 : Clampf(w.y / s, -1, 1); }
+#if RL_EXACT_DIV & 1
+// CosPhi(w) and SinPhi(w) of one vector, sharing the divisor
+__device__ __forceinline__ void CosSinPhi(V3 w, float& cosPhi, float& sinPhi)
+{
+	const float s = SinThetaL(w);
+	// s is 0 or in [2^-12, 1] (1 - z z >= 2^-24 when it is positive), and |w.x|, |w.y| <= 1 + 2^-22: with numerators of at least 2^-102 every condition holds.  A zero
+	// numerator (its sign would come out wrong), a tiny one or NaN sends the wave to the divisions; lanes with s = 0 take the constants and do not count.
+	const float y = rlm::rcp1_in_range_(s);
+	float qx = rtm::div_by_(w.x, s, y), qy = rtm::div_by_(w.y, s, y);
+	if (rtm::wave_any_(!(s == 0 || (fabsf(w.x) >= 0x1p-102f && fabsf(w.y) >= 0x1p-102f)))) { qx = w.x / s; qy = w.y / s; }
+	cosPhi = (s == 0) ? 1 : Clampf(qx, -1, 1);
+	sinPhi = (s == 0) ? 0 : Clampf(qy, -1, 1);
+}
+#endif
+// dot(V, H) / dot(V, N) <= 0 (RL_EXACT_DIV bit 2).  n / d <= 0 holds exactly when the quotient is a zero, a negative number or -inf:
+//   n = +-0 with d neither zero nor NaN (+-0; 0 / 0 is NaN),
+//   n nonzero, neither NaN, with opposite sign bits (-inf when d = +-0, a negative number otherwise) --
+// except for a quotient that underflows to zero and d = +-inf, neither of which can happen here: d is the dot product of two unit vectors, |d| <= 1 + 2^-21, so it is
+// finite, and |n / d| > 2^-150 for every n != 0 (denormals included), which rounds to a nonzero quotient.
+__device__ __forceinline__ bool QuotientNotPositive(float n, float d)
+{
+#if RL_EXACT_DIV & 2
+	const bool opposite = (int32_t)(__float_as_uint(n) ^ __float_as_uint(d)) < 0;
+	return (n == 0.0f) ? __builtin_islessgreater(d, 0.0f) : (!__builtin_isunordered(n, d) && opposite);
+#else
+	return n / d <= 0.0f;
+#endif
+}
 
 // k_trace's PLAIN instance has fewer registers to place around a call (no texture, cut-out or sky code): there the tan_ of GeometryBeckmann and the pow_ of
 // the Fresnel term may be inlined, measured in DESIGN.md section 2.  Every other kernel keeps the calls.  (The sampler's pow_ stays a call everywhere: a template
@@ -990,7 +1046,14 @@ __device__ __forceinline__ void BeckmannSample11(float cosThetaI, float U1, floa
 		return;
 	}
 	float sinThetaI = rtm::sqrt_(fmaxf((float)0, (float)1 - cosThetaI * cosThetaI));
+#if RL_EXACT_DIV & 1
+	// cosThetaI <= .9999 here, so sinThetaI is in [0.014, 1]; with 2^-126 <= cosThetaI < 1 the quotient is in [0.014, 2^126] and div_by_'s conditions hold.
+	// cosThetaI = +-0, tiny or NaN sends the wave to the division.
+	float tanThetaI = rtm::div_by_(sinThetaI, cosThetaI, rlm::rcp1_in_range_(cosThetaI));
+	if (rtm::wave_any_(!(cosThetaI >= 0x1p-126f))) tanThetaI = sinThetaI / cosThetaI;
+#else
 	float tanThetaI = sinThetaI / cosThetaI;
+#endif
 	float cotThetaI = rtm::rcp1_(tanThetaI);
 
 	float a = -1, c = Erf(cotThetaI);
@@ -1035,8 +1098,14 @@ __device__ __forceinline__ V3 BeckmannSample(V3 wi, float alpha_x, float alpha_y
 	V3 wiStretched = normalize(v3(alpha_x * wi.x, alpha_y * wi.y, wi.z));
 	float slope_x, slope_y;
 	BeckmannSample11(wiStretched.z, U1, U2, &slope_x, &slope_y, cn);
+#if RL_EXACT_DIV & 1
+	float cosPhi, sinPhi; CosSinPhi(wiStretched, cosPhi, sinPhi);
+	float tmp = cosPhi * slope_x - sinPhi * slope_y;
+	slope_y = sinPhi * slope_x + cosPhi * slope_y;
+#else
 	float tmp = CosPhi(wiStretched) * slope_x - SinPhi(wiStretched) * slope_y;
 	slope_y = SinPhi(wiStretched) * slope_x + CosPhi(wiStretched) * slope_y;
+#endif
 	slope_x = tmp;
 	slope_x = alpha_x * slope_x;
 	slope_y = alpha_y * slope_y;
@@ -1063,7 +1132,7 @@ __device__ __forceinline__ float GeometryBeckmann(V3 N, V3 H, V3 V, float roughn
 	float tanThetaV = TanSel<ITAN>(thetaV);
 	float a = rtm::rcp1_(roughness * tanThetaV);
 	float aa = a * a;
-	if (dot(V, H) / dot(V, N) <= 0.0f) return 0.0f;
+	if (QuotientNotPositive(dot(V, H), dot(V, N))) return 0.0f;
 	if (a < 1.6f) {
 		float num = 3.535f * a + 2.181f * aa;
 		float denom = 1.0f + 2.276f * a + 2.577f * aa;
@@ -1221,7 +1290,7 @@ __device__ __forceinline__ bool Scatter(const DSceneView& S, const Mat& m, V3 in
 			V3 kS = F;
 			V3 kD = 1.0f - kS;
 			V3 diffuse = baseColor * (1.0f - metallic);
-			V3 specular = (F * G * NDF) / (4.0f * NdotWi * absDot(N, Wo) + 0.001f);
+			V3 specular = DivSpecular(F * G * NDF, 4.0f * NdotWi * absDot(N, Wo) + 0.001f);
 
 			V3 WiW = LocalToWorld(s, Wi);
 			outD = WiW;
@@ -3250,6 +3319,8 @@ k_verify_exact_math(int which, unsigned long long* __restrict__ out)
 		} else if (which == 2) {
 			for (int k = 0; k < 12; ++k) { const float d = fixedB[k]; if (DivByHolds(x, d) && !SameBits(rtm::div_by_(x, d, 1.0f / d), x / d)) differs = true; }
 			for (int k = 0; k < 10; ++k) { const float a = fixedA[k]; if (DivByHolds(a, x) && !SameBits(rtm::div_by_(a, x, 1.0f / x), a / x)) differs = true; }
+		} else if (which == 4) {
+			differs = !SameBits(rlm::acosf_t<true>(x), rlm::acosf_t<false>(x)) || !SameBits(rlm::tanf_t<true>(x), rlm::tanf_t<false>(x));
 		} else {
 			// (X, Y, denom) of ordinary hits, of hits on an edge and at a vertex, of misses by a hair, with tiny, huge and special members
 			const float T[14][3] = { { 1.0e9f, 2.0e9f, 9.5e10f }, { -1.0e9f, -2.0e9f, -9.5e10f }, { 0.0f, 4.0e10f, 9.5e10f }, { -0.0f, 0.0f, 9.5e10f }, { 1e-3f, 9.4999e10f, 9.5e10f },
