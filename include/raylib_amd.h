@@ -144,7 +144,8 @@ RAYLIB_API int32_t RaylibAMD_EvalCameraRays(CameraHandle camera, const float* uv
 RAYLIB_API int32_t RaylibAMD_EvalTexture(SceneHandle scene, int32_t texture, int32_t bSRGB, const float* uv, int32_t n, float* out);
 /* Test hook: out[i] = f(x[i] [, y[i]]) evaluated by the DEVICE math the megakernel uses (csrc/rl_math.h).
  * fn: 0 sinf, 1 cosf, 2 tanf, 3 acosf, 4 asinf, 5 atan2f(x,y), 6 expf, 7 logf, 8 powf(x,y), 9/10 sincos (sin / cos
- * part), 11 sqrtf, 12 x / y, 13 fmodf(x, 1).  y may be NULL for one-argument functions. */
+ * part), 11 sqrtf, 12 x / y, 13 fmodf(x, 1) (the texture wrap), 14 1.0f / x and 15 sqrtf(x) in their short exact forms
+ * (csrc/rl_math.h rcp1_ / sqrt_, range guards included).  y may be NULL for one-argument functions. */
 RAYLIB_API int32_t RaylibAMD_EvalDeviceMath(int32_t fn, const float* x, const float* y, int32_t n, float* out);
 
 /* Test hook (host only, no device needed): which 8 x 8 cells of a width x height frame can no ray of the camera -- pinhole or thin lens, no sky panorama -- meet the box

@@ -252,8 +252,9 @@ RLM_FN float powf_(float x, float y)
 	uint32_t ix = asuint(x), iy = asuint(y);
 	if (ix - 0x00800000u >= 0x7f800000u - 0x00800000u || powf_zeroinfnan(iy)) {
 		if (powf_zeroinfnan(iy)) {
-			if (2 * iy == 0) return 1.0f;
-			if (ix == 0x3f800000u) return 1.0f;
+			// pow(x, +-0) and pow(1, y) are 1 even for a quiet NaN, but a signalling one gives NaN (glibc's issignalingf_inline)
+			if (2 * iy == 0) return (2 * (ix ^ 0x00400000u) > 2u * 0x7fc00000u) ? x + y : 1.0f;
+			if (ix == 0x3f800000u) return (2 * (iy ^ 0x00400000u) > 2u * 0x7fc00000u) ? x + y : 1.0f;
 			if (2 * ix > 2u * 0x7f800000u || 2 * iy > 2u * 0x7f800000u) return x + y;
 			if (2 * ix == 2 * 0x3f800000u) return 1.0f;
 			if ((2 * ix < 2 * 0x3f800000u) == !(iy & 0x80000000u)) return 0.0f;
