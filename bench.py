@@ -13,10 +13,13 @@ maxPathLength 5, fixed RNG seed, scene resident in HBM.  Two ways to run N GPUs,
                 --gpus N ...` (what the driver launches for N > 1): one process per GPU, each renders its cells into device memory
                 (RaylibAMD_RenderDevice), one RCCL gather per frame brings them to rank 0.  --gpus must equal WORLD_SIZE.
 
-Strong scaling: the total work is fixed.  Outside the timed region the frame is checked against windows rendered by the reference
-build (tests/golden/bench_windows.npz).  Rank 0 prints ONE JSON line; DESIGN.md section 5 describes every field.  The line leaves out
-prose definitions and replayed counter detail (result_line); `--details FILE` writes the whole object.  `--dump-outputs DIR` writes the
-frame of the last timed step as DIR/image.npy, so that two builds run with the same arguments can be compared output for output.
+Strong scaling: the total work is fixed.  A plain run does what the headline needs and nothing more: it sets up, warms up, times the
+K steps, writes --dump-outputs and prints the line.  `--full` adds, outside the timed region: the frame checked against windows rendered
+by the reference build (tests/golden/bench_windows.npz; process mode: also against a one-GPU render), the render + read-back and
+device-entry times, the tree walk's algorithmic bytes (one more frame), the three further workloads (`--no-extra` drops them) and the
+CPU reference's time (`--no-cpu-baseline` drops it).  Rank 0 prints ONE JSON line; DESIGN.md section 5 describes every field.  The line
+leaves out prose definitions and replayed counter detail (result_line); `--details FILE` writes the whole object.  `--dump-outputs DIR`
+writes the frame of the last timed step as DIR/image.npy, so that two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -364,9 +367,10 @@ def work_block(acc, steps):
                           "Samples of cells outside the scene's silhouette are neither generated nor traced: k_resolve writes the miss shader's constant for them"}
 
 
-def library_run(lib, binding, scenes, workload_name, steps, warmup, n_gpus, rank_tag="0", want_device_entry=True):
-    """K timed Raylib_Render calls on one workload (library mode).  Returns the measurements and, untimed, the frame check, the
-    render + dump time, the device-pointer entry's time and the tree-walk record counts."""
+def library_run(lib, binding, scenes, workload_name, steps, warmup, n_gpus, rank_tag="0", want_device_entry=True, full=True, want_frame=True):
+    """K timed Raylib_Render calls on one workload (library mode).  Returns the measurements, the last timed frame if `want_frame` or
+    `full` and, untimed and only if `full`, the frame check, the render + dump time, the device-pointer entry's time and the tree-walk
+    record counts."""
     import numpy as np
     wl = WORKLOADS[workload_name]
     cam = scenes.CONFIG_CAMERAS[wl["camera"]]
@@ -412,43 +416,44 @@ def library_run(lib, binding, scenes, workload_name, steps, warmup, n_gpus, rank
             accumulate(acc, stats, binding)
     last = stats.as_dict()
     # ---- untimed from here on -------------------------------------------------------------------------------------------------
-    host = np.zeros(w * h * 3, np.float32)
-    lib.Raylib_DumpImageData(image, host.ctypes.data_as(C.POINTER(C.c_float)))
-    last_frame = host.reshape(h, w, 3).copy()        # the last timed step's frame, as the caller of Raylib_Render reads it back
-    frame_check = golden_windows(workload_name, last_frame)
-    # what a front-end observes: the render plus the read-back of the frame (the reference's Raylib_Render returns with the pixels
-    # in host memory, render/renderer.cc:292-356; here the first reader pays the 33 MB copy)
-    k2 = max(1, min(steps, 10))
-    t1 = time.perf_counter()
-    for _ in range(k2):
-        lib.Raylib_Render(C.byref(st), ses.scene, ses.camera, image)
+    boundary = {"timed_entry": "Raylib_Render", "raylib_render_ms_per_step": elapsed / steps * 1e3}
+    last_frame, frame_check, tree_walk = None, None, None
+    if want_frame or full:
+        host = np.zeros(w * h * 3, np.float32)
         lib.Raylib_DumpImageData(image, host.ctypes.data_as(C.POINTER(C.c_float)))
-    render_plus_dump = (time.perf_counter() - t1) / k2
-    boundary = {"timed_entry": "Raylib_Render", "raylib_render_ms_per_step": elapsed / steps * 1e3,
-                "render_plus_dump_ms_per_step": render_plus_dump * 1e3}
-    if want_device_entry and n_gpus == 1:
-        dev = torch.zeros(w * h * 4, dtype=torch.float32, device="cuda")
-        torch.cuda.synchronize()
-        t2 = time.perf_counter()
+        last_frame = host.reshape(h, w, 3).copy()        # the last timed step's frame, as the caller of Raylib_Render reads it back
+    if full:
+        frame_check = golden_windows(workload_name, last_frame)
+        # what a front-end observes: the render plus the read-back of the frame (the reference's Raylib_Render returns with the pixels
+        # in host memory, render/renderer.cc:292-356; here the first reader pays the 33 MB copy)
+        k2 = max(1, min(steps, 10))
+        t1 = time.perf_counter()
         for _ in range(k2):
-            if lib.RaylibAMD_RenderDevice(C.byref(st), ses.scene, ses.camera, 0, 1, C.c_void_p(dev.data_ptr())) != 1:
-                raise SystemExit("RaylibAMD_RenderDevice failed")
-        torch.cuda.synchronize()
-        boundary["render_device_ms_per_step"] = (time.perf_counter() - t2) / k2 * 1e3
-    tree_walk = None
-    if acc.get("tree_width") == 0:
-        # the workload's algorithmic bytes: the same frame on the BVH4 walk (the leaf-list kernel reads every leaf box per ray, from LDS); with several ranks
-        # behind the call the counters are the ranks' sum and the launch count one rank's, as in the timed frames
-        keep = os.environ.get("RAYLIB_LEAF_LIST")
-        lib.RaylibAMD_GetLastStats(C.byref(stats))     # (nothing of the frames above is still in flight when the switch changes)
-        os.environ["RAYLIB_LEAF_LIST"] = "0"
-        lib.Raylib_Render(C.byref(st), ses.scene, ses.camera, image)
-        lib.RaylibAMD_GetLastStats(C.byref(stats))
-        if keep is None:
-            del os.environ["RAYLIB_LEAF_LIST"]
-        else:
-            os.environ["RAYLIB_LEAF_LIST"] = keep
-        tree_walk = {"bytes_per_launch": binding.algorithmic_bytes(stats) / max(1, stats.traceLaunches), "launch_ms": stats.traceKernelMs / max(1, stats.traceLaunches)}
+            lib.Raylib_Render(C.byref(st), ses.scene, ses.camera, image)
+            lib.Raylib_DumpImageData(image, host.ctypes.data_as(C.POINTER(C.c_float)))
+        boundary["render_plus_dump_ms_per_step"] = (time.perf_counter() - t1) / k2 * 1e3
+        if want_device_entry and n_gpus == 1:
+            dev = torch.zeros(w * h * 4, dtype=torch.float32, device="cuda")
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            for _ in range(k2):
+                if lib.RaylibAMD_RenderDevice(C.byref(st), ses.scene, ses.camera, 0, 1, C.c_void_p(dev.data_ptr())) != 1:
+                    raise SystemExit("RaylibAMD_RenderDevice failed")
+            torch.cuda.synchronize()
+            boundary["render_device_ms_per_step"] = (time.perf_counter() - t2) / k2 * 1e3
+        if acc.get("tree_width") == 0:
+            # the workload's algorithmic bytes: the same frame on the BVH4 walk (the leaf-list kernel reads every leaf box per ray, from LDS); with several ranks
+            # behind the call the counters are the ranks' sum and the launch count one rank's, as in the timed frames
+            keep = os.environ.get("RAYLIB_LEAF_LIST")
+            lib.RaylibAMD_GetLastStats(C.byref(stats))     # (nothing of the frames above is still in flight when the switch changes)
+            os.environ["RAYLIB_LEAF_LIST"] = "0"
+            lib.Raylib_Render(C.byref(st), ses.scene, ses.camera, image)
+            lib.RaylibAMD_GetLastStats(C.byref(stats))
+            if keep is None:
+                del os.environ["RAYLIB_LEAF_LIST"]
+            else:
+                os.environ["RAYLIB_LEAF_LIST"] = keep
+            tree_walk = {"bytes_per_launch": binding.algorithmic_bytes(stats) / max(1, stats.traceLaunches), "launch_ms": stats.traceKernelMs / max(1, stats.traceLaunches)}
     lib.Raylib_DestroyImage(image)
     ses.close()
     return dict(acc=acc, elapsed=elapsed, per_step=per_step, frame_check=frame_check, boundary=boundary, tree_walk=tree_walk,
@@ -461,8 +466,11 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=HEADLINE, choices=list(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the second workload (a memory-bound megakernel) reported under \"extra\"")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also check the frame against the reference-rendered windows, time the render + read-back and the "
+                         "device entry, render one tree-walk frame for the algorithmic bytes, run the further workloads and time the CPU reference")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU reference's time (\"cpu_baseline\")")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the further workloads reported under \"extra\", \"extra_interior\" and \"extra_textured\"")
     ap.add_argument("--details", metavar="FILE", default=None,
                     help="write the whole result object to FILE: the printed line leaves out prose definitions and replayed counter detail")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -503,7 +511,7 @@ def main():
     lib.RaylibAMD_SetSeed(1)
     build_id = lib.RaylibAMD_BuildId().decode()
 
-    r = library_run(lib, binding, scenes, args.workload, args.steps, args.warmup, n)
+    r = library_run(lib, binding, scenes, args.workload, args.steps, args.warmup, n, full=args.full, want_frame=bool(args.dump_outputs))
     ranks = int(r["last_stats"]["ranks"])
     if ranks != n:
         raise SystemExit("asked for %d GPU(s) but the library rendered on %d rank(s)" % (n, ranks))
@@ -529,7 +537,7 @@ def main():
                    "tiling": "8x8 cells round-robin over %d rank(s)" % ranks, "rays_per_step": acc["rays"] / args.steps,
                    "camera_samples_per_step": acc["samples"] / args.steps, "work": work_block(acc, args.steps),
                    "frame_check": r["frame_check"], "boundary": r["boundary"],
-                   "build_id": build_id, "timed_region_s": elapsed},
+                   "build_id": build_id, "timed_region_s": elapsed, "full": args.full},
         "roofline": roofline_block(args.workload, acc, ranks, build_id, r["tree_walk"], gpus_in_acc=ranks,
                                    frame_samples_per_launch=acc["samples"] / max(1, acc["launches"])),
     }
@@ -545,7 +553,7 @@ def main():
         out["multi_gpu"] = {"ranks": ranks, "devices": s["devices"], "gpu_map": gpu_map, "gather": s["gatherMode"], "rccl_comm_size": s["rcclCommSize"],
                             "gather_ms": s["gatherMs"], "scatter_ms": s["scatterMs"], "rank_kernel_ms": s["rankKernelMs"], "rank_trace_ms": s["rankTraceMs"],
                             "note": "last timed frame; gather_ms = rank 0's stream from the end of its own kernels until every rank's cells are on its device"}
-    if ranks == 1 and not args.no_extra and args.workload == HEADLINE:
+    if args.full and ranks == 1 and not args.no_extra and args.workload == HEADLINE:
         # further objects in the same invocation: the configs[2]-sized scene, whose megakernel (the pool schedule) waits on memory -- seen from outside
         # (SURVEY 8d's stand-in camera: 89 % of that frame is empty sky and is not traced) and from INSIDE (every pixel is geometry, nothing is dropped)
         k = max(3, min(20, args.steps // 5))
@@ -556,7 +564,7 @@ def main():
                         "ms_per_step": e["elapsed"] / k * 1e3, "ms_per_step_spread": step_times(e["per_step"]), "scene_triangles": e["ntris"],
                         "spp": e["wl"]["spp"], "work": work_block(ea, k), "frame_check": e["frame_check"], "boundary": e["boundary"],
                         "roofline": roofline_block(name, ea, 1, build_id, e["tree_walk"])}
-    if ranks == 1 and not args.no_cpu_baseline:
+    if args.full and ranks == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(wl, r["cam"], (acc["rays"] + acc["culled_rays"]) / max(1.0, acc["samples"] + acc["culled_samples"]), elapsed / args.steps)
     emit(out, args.details)
 
@@ -671,10 +679,10 @@ def process_mode(args, rank, local_rank, world, torch, binding, scenes):
     km[rank] = stats.traceKernelMs
     dist.all_reduce(km, op=dist.ReduceOp.SUM)
 
-    # outside the timed region: this rank's share once more on the tree walk, where the kernel that ran read its scene from LDS (the leaf list) -- the workload's
-    # algorithmic bytes are the tree walk's, whatever schedule ran
+    # outside the timed region (--full): this rank's share once more on the tree walk, where the kernel that ran read its scene from LDS (the leaf list) -- the
+    # workload's algorithmic bytes are the tree walk's, whatever schedule ran
     tree_walk = None
-    if acc.get("tree_width") == 0:
+    if args.full and acc.get("tree_width") == 0:
         keep = os.environ.get("RAYLIB_LEAF_LIST")
         os.environ["RAYLIB_LEAF_LIST"] = "0"
         torch.cuda.synchronize()
@@ -691,15 +699,16 @@ def process_mode(args, rank, local_rank, world, torch, binding, scenes):
         torch.cuda.synchronize()
         dump_outputs(args.dump_outputs, {"image": frame.reshape(h, w, 4).cpu().numpy()})
     if rank == 0:
-        # outside the timed region: the frame assembled from the ranks' cells against this rank's own render of the whole frame
-        torch.cuda.synchronize()
-        whole = torch.zeros(h * w * 4, dtype=torch.float32, device=dev)
-        if lib.RaylibAMD_RenderDevice(C.byref(st), ses.scene, ses.camera, 0, 1, C.c_void_p(whole.data_ptr())) == 1:
-            same = bool(torch.equal(whole.view(torch.int32), frame.reshape(-1).view(torch.int32)))
-            frame_check = "assembled frame bit-identical to a one-GPU render" if same else "MISMATCH between the assembled frame and a one-GPU render"
-            gw = golden_windows(args.workload, frame.reshape(h, w, 4).cpu().numpy())
-            if gw is not None:
-                frame_check += "; " + gw
+        if args.full:
+            # outside the timed region: the frame assembled from the ranks' cells against this rank's own render of the whole frame
+            torch.cuda.synchronize()
+            whole = torch.zeros(h * w * 4, dtype=torch.float32, device=dev)
+            if lib.RaylibAMD_RenderDevice(C.byref(st), ses.scene, ses.camera, 0, 1, C.c_void_p(whole.data_ptr())) == 1:
+                same = bool(torch.equal(whole.view(torch.int32), frame.reshape(-1).view(torch.int32)))
+                frame_check = "assembled frame bit-identical to a one-GPU render" if same else "MISMATCH between the assembled frame and a one-GPU render"
+                gw = golden_windows(args.workload, frame.reshape(h, w, 4).cpu().numpy())
+                if gw is not None:
+                    frame_check += "; " + gw
         out = {
             "metric": "Mrays/sec (primary+secondary) + frame time, Cornell Box 1080p 64spp",
             "value": total_rays / elapsed / 1e6,
@@ -726,14 +735,14 @@ def process_mode(args, rank, local_rank, world, torch, binding, scenes):
                        "n1_reference": {"note": "the driver's N = 1 line is library mode (`python bench.py --gpus 1`: Raylib_Render); this line is process mode "
                                                 "(RaylibAMD_RenderDevice per rank + one gather per frame), whose own one-rank time is `boundary.render_device_ms_per_step` of the N = 1 line "
                                                 "(or this line at WORLD_SIZE = 1)"},
-                       "build_id": build_id, "timed_region_s": elapsed},
+                       "build_id": build_id, "timed_region_s": elapsed, "full": args.full},
             # rank 0's own launches (the other ranks run the same kernel on their share of the cells: rank_trace_ms below)
             "roofline": roofline_block(args.workload, acc, world, build_id, tree_walk, gpus_in_acc=1,
                                        frame_samples_per_launch=total_samples / max(1, acc["launches"])),
             "multi_gpu": {"ranks": world, "devices": min(world, visible), "gather": "gloo via host (BENCH_SHARE_GPU)" if share else "rccl (torch.distributed gather)",
                           "rank_trace_ms": [float(x) for x in km.tolist()], "note": "rank_trace_ms: every rank's megakernel time in the last timed frame"},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(wl, cam, total_frame_rays / max(1.0, total_frame_samples), elapsed / args.steps)
         emit(out, args.details)
     ses.close()

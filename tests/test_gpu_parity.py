@@ -315,14 +315,14 @@ def test_pool_schedule_is_default_on_deep_bvh_and_bit_identical(mid_scene, gpu_l
 def test_bench_multi_rank_frame_assembly_on_one_gpu():
     """bench.py's N > 1 path on a 1-GPU box: BENCH_SHARE_GPU=1 puts 2 ranks on the one device and stages the gather through the
     host over gloo (RCCL refuses two ranks per device).  What is checked is the logic the real run uses -- cells dealt round-robin,
-    double-buffered send, scatter plan -- by bench.py's own frame check: the assembled frame equals a one-GPU render bit for bit."""
+    double-buffered send, scatter plan -- by bench.py's own frame check (--full): the assembled frame equals a one-GPU render bit for bit."""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BENCH_SHARE_GPU="1")
     for k in ("RAYLIB_POOL", "RAYLIB_LIB"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29533",
-           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra"]
+           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stderr[-2000:]
@@ -361,15 +361,15 @@ def check_multi_rank_roofline(r, leaf_list):
 
 
 def test_bench_default_run_times_the_boundary_and_checks_the_frame():
-    """`python bench.py` as the driver runs it at N = 1: the timed call is Raylib_Render, and the frame it produced is compared, outside
-    the timed region, with windows the reference build rendered (tests/golden/bench_windows.npz).  The same invocation reports the
-    configs[2]-sized scene (a memory-bound megakernel) under "extra"."""
+    """`python bench.py --full` at N = 1: the timed call is Raylib_Render, and the frame it produced is compared, outside the timed
+    region, with windows the reference build rendered (tests/golden/bench_windows.npz).  The same invocation reports the configs[2]-sized
+    scene (a memory-bound megakernel) under "extra"."""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ)
     for k in ("RAYLIB_POOL", "RAYLIB_LIB", "BENCH_SHARE_GPU", "WORLD_SIZE", "RANK", "LOCAL_RANK", "RAYLIB_NUM_GPUS", "RAYLIB_GPU_MAP", "RAYLIB_JOB_HEADS"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "1", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stderr[-2000:]
     assert len(lines[0]) < 10000, "the result line must stay short enough to be read from the end of the output (%d bytes)" % len(lines[0])
@@ -423,6 +423,31 @@ def test_bench_default_run_times_the_boundary_and_checks_the_frame():
     assert et["work"]["cells_culled"] == 0 and et["work"]["texel_fetches_per_ray"] > 0.5
 
 
+def test_bench_plain_run_does_only_what_the_headline_needs():
+    """`python bench.py` without --full: set-up, warm-up, the timed steps and the line, whose headline fields mean what they mean under
+    --full.  Nothing else runs: no frame check, no further render for the boundary times or the tree walk's bytes, no further workload,
+    no CPU reference."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RAYLIB_POOL", "RAYLIB_LIB", "BENCH_SHARE_GPU", "WORLD_SIZE", "RANK", "LOCAL_RANK", "RAYLIB_NUM_GPUS", "RAYLIB_GPU_MAP", "RAYLIB_JOB_HEADS"):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1"], env=env, capture_output=True, text=True, timeout=300)
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "Mrays/sec (primary+secondary) + frame time, Cornell Box 1080p 64spp" and d["unit"] == "Mrays/s" and d["dtype"] == "f32"
+    assert d["higher_is_better"] is True and d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step_spread"]["n"] == 3
+    wk = d["config"]["work"]
+    assert wk["cells_culled"] == 20190 and wk["camera_samples_executed_per_step"] == (32400 - 20190) * 64 * 64
+    assert d["ms_per_step"] > 0 and abs(d["value"] - wk["rays_executed_per_step"] / d["ms_per_step"] / 1e3) < 1e-6 * d["value"]
+    assert not {"extra", "extra_interior", "extra_textured", "cpu_baseline"} & set(d)
+    assert d["config"]["full"] is False and d["config"]["frame_check"] is None
+    assert set(d["config"]["boundary"]) == {"timed_entry", "raylib_render_ms_per_step"} and d["config"]["n1_reference"]["process_mode_entry_ms_per_step"] is None
+    a = d["roofline"]["algorithmic"]
+    assert a["tree_width"] == 0 and a["bytes_per_launch"] is None and a["served_elsewhere"]["lds_served_bytes_per_launch"] > 0
+
+
 def test_bench_dump_outputs_writes_the_last_timed_frame(tmp_path):
     """`bench.py --dump-outputs DIR` writes the frame of the last timed step as DIR/image.npy (float32, what Raylib_Render's caller reads
     back): the same bits whatever --steps is, the reference-rendered windows inside it, and `--steps` is the number of timed steps.
@@ -466,7 +491,7 @@ def test_bench_library_mode_runs_n_ranks_behind_raylib_render_or_refuses():
     for k in ("RAYLIB_POOL", "RAYLIB_LIB", "BENCH_SHARE_GPU", "WORLD_SIZE", "RANK", "LOCAL_RANK", "RAYLIB_NUM_GPUS", "RAYLIB_GPU_MAP", "RAYLIB_GATHER_SELF"):
         env.pop(k, None)
     import torch
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extra"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra"]
     if torch.cuda.device_count() < 2:
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
         assert out.returncode != 0 and not [l for l in out.stdout.splitlines() if l.startswith("{")], out.stdout[-500:]
@@ -509,7 +534,7 @@ def test_bench_rccl_gather_path_with_one_rank():
     for k in ("RAYLIB_POOL", "RAYLIB_LIB", "BENCH_SHARE_GPU"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29534",
-           os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extra"]
+           os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stderr[-2000:]

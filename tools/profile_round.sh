@@ -4,6 +4,7 @@
 #   PMC passes (separate --pmc runs, no trace domains), the derived figures (tools/pmc_traffic.py) and the bench lines that replay them.
 # usage: tools/profile_round.sh <round tag, e.g. r03>      (then copy gpurun_out/round_<tag>/... into profiles/, see profiles/README.md)
 TAG=${1:-r05}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=/root/repo/gpurun_out/round_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
@@ -31,11 +32,11 @@ if [ -f /root/repo/software-raytracing_amd/libraylib_stamps2.so ]; then
 fi
 python3 /root/repo/tools/dynamic_mix.py cornell_1080p_64spp,breakfast_300k_1080p_128spp,breakfast_interior_300k_1080p_128spp,breakfast_textured_interior_300k_1080p_128spp > $OUT/dynamic_mix.txt 2>&1
 cp /root/repo/profiles/pmc_traffic.json $OUT/pmc_traffic.json
-# the bench lines, now carrying this round's counters: the default invocation (headline + extra + cpu baseline) and the second workload on its own
-python3 /root/repo/bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-python3 /root/repo/bench.py --steps 20 --warmup 2 --workload breakfast_300k_1080p_128spp > $OUT/bench_breakfast_300k_1080p_128spp.json 2> $OUT/bench_breakfast_300k_1080p_128spp.err
-python3 /root/repo/bench.py --steps 10 --warmup 2 --workload breakfast_interior_300k_1080p_128spp > $OUT/bench_breakfast_interior_300k_1080p_128spp.json 2> $OUT/bench_breakfast_interior_300k_1080p_128spp.err
-python3 /root/repo/bench.py --steps 10 --warmup 2 --workload breakfast_textured_interior_300k_1080p_128spp > $OUT/bench_breakfast_textured_interior_300k_1080p_128spp.json 2> $OUT/bench_breakfast_textured_interior_300k_1080p_128spp.err
+# the bench lines, now carrying this round's counters: the --full invocation (headline + extra workloads + frame checks + cpu baseline) and each further workload on its own
+python3 $ROOT/bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+python3 $ROOT/bench.py --full --steps 20 --warmup 2 --workload breakfast_300k_1080p_128spp > $OUT/bench_breakfast_300k_1080p_128spp.json 2> $OUT/bench_breakfast_300k_1080p_128spp.err
+python3 $ROOT/bench.py --full --steps 10 --warmup 2 --workload breakfast_interior_300k_1080p_128spp > $OUT/bench_breakfast_interior_300k_1080p_128spp.json 2> $OUT/bench_breakfast_interior_300k_1080p_128spp.err
+python3 $ROOT/bench.py --full --steps 10 --warmup 2 --workload breakfast_textured_interior_300k_1080p_128spp > $OUT/bench_breakfast_textured_interior_300k_1080p_128spp.json 2> $OUT/bench_breakfast_textured_interior_300k_1080p_128spp.err
 timeout 120 /root/repo/tools/vmem_width_bench > $OUT/vmem_width_bench.txt 2>&1
 # the memory pipeline's counters of the interior frame (TA / TCP / TD) and the gather microbenchmark they are read against
 WL=breakfast_interior_300k_1080p_128spp bash /root/repo/tools/pmc_mem.sh round_${TAG}_interior > $OUT/pmc_mem_interior.txt 2>&1
