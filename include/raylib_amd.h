@@ -220,6 +220,33 @@ typedef struct RaylibAMDRenderPlan {
 	uint64_t jobs;
 } RaylibAMDRenderPlan;
 RAYLIB_API int32_t RaylibAMD_PlanRender(SceneHandle scene, const RendererSettings* settings, int32_t hasSky, int32_t numCUs, int32_t workgroupsPerCU, RaylibAMDRenderPlan* out);
+/* ---- several views of one scene in one megakernel launch (INTEGRATION.md "Several views") ---- */
+#define RAYLIB_AMD_MAX_VIEWS 64
+/* Renders `count` views of one scene at one RendererSettings.  outImages[i] receives, bit for bit, what
+ * Raylib_Render(settings, scene, cameras[i], outImages[i]) would give with the same seed, in every render mode.
+ * Each image is resized to the viewport, and its result stays on the device as after Raylib_Render.
+ * RaylibAMD_GetLastStats reports the batch: counters summed over the views, one megakernel launch per sample
+ * batch for the whole set.  Returns 1, or 0 with no image touched when:
+ *   - an argument is null, or count is outside 1..RAYLIB_AMD_MAX_VIEWS;
+ *   - a camera or image handle is 0 or unknown, or an image appears twice;
+ *   - the scene is not finalized, or the viewport is empty;
+ *   - the job count of a one-sample batch would overflow (count * cells of the viewport * 64 > 0xF0000000);
+ *   - the scene has moving cubes and the cameras' shutter intervals differ (its boxes are built for one interval);
+ *   - there is no device.
+ * With RAYLIB_NUM_GPUS > 1 the batch renders on rank 0's device, as a progressive session does. */
+RAYLIB_API int32_t RaylibAMD_RenderViews(const RendererSettings* settings, SceneHandle scene,
+        const CameraHandle* cameras, int32_t count, const ImageHandle* outImages);
+/* The same into caller device memory: count * W * H * 4 floats, view-major, row-major inside a view.
+ * outDevice == 0: the library's own buffer (for timing), as RaylibAMD_RenderDevice. */
+RAYLIB_API int32_t RaylibAMD_RenderViewsDevice(const RendererSettings* settings, SceneHandle scene,
+        const CameraHandle* cameras, int32_t count, void* outDevice);
+/* What RaylibAMD_RenderViews would launch under the current environment, as RaylibAMD_PlanRender for one view: the instance and tree (those of the one-view
+ * plan) and the job layout of the first launch over every view's listed cells.  outCellEmpty (count * ceil(W/8) * ceil(H/8) bytes, may be null): per cell of
+ * each view, view by view, 1 when it is dropped from the job list (RaylibAMD_CullCells of that view's camera).  hasSky as for RaylibAMD_PlanRender.  No device
+ * needed.  Returns 1, -1 when the scene's BVH is too deep to render, 0 for a bad argument (as RaylibAMD_RenderViews refuses them), a scene not finalized or a
+ * job count that would overflow. */
+RAYLIB_API int32_t RaylibAMD_PlanViews(SceneHandle scene, const RendererSettings* settings, const CameraHandle* cameras, int32_t count, int32_t hasSky,
+        int32_t numCUs, int32_t workgroupsPerCU, RaylibAMDRenderPlan* outPlan, uint8_t* outCellEmpty);
 /* FNV-1a of the flat BVH (node records + leaf order): the multi-threaded build (RAYLIB_BUILD_THREADS, default = host
  * threads, <= 32) must give the tree of the single-threaded one. */
 RAYLIB_API uint64_t RaylibAMD_SceneBVHHash(SceneHandle scene);

@@ -119,6 +119,53 @@ bool ProgressiveParamsValid(const RaylibAMDProgressiveParams& P)
 	return P.threshold >= 0.0f && P.threshold <= 3.40282347e+38f && P.minSamples >= 2;   // (false for NaN)
 }
 
+// The checks RaylibAMD_RenderViews / RenderViewsDevice / PlanViews make before anything is touched (include/raylib_amd.h); images may be null (the device form)
+bool ViewsArgsValid(const char* who, const RendererSettings* settings, Scene* scene, const CameraHandle* cameras, int32_t count, const ImageHandle* images)
+{
+	if (!settings || !scene || !cameras) { Log("%s: null argument", who); return false; }
+	if (count < 1 || count > RAYLIB_AMD_MAX_VIEWS) { Log("%s: %d views (1..%d)", who, count, RAYLIB_AMD_MAX_VIEWS); return false; }
+	if (!g_scenes.contains(scene)) { Log("%s: unknown scene", who); return false; }
+	for (int32_t v = 0; v < count; ++v) {
+		Camera* c = (Camera*)cameras[v];
+		if (!c || !g_cameras.contains(c)) { Log("%s: camera %d is 0 or unknown", who, v); return false; }
+		if (images) {
+			Image* img = (Image*)images[v];
+			if (!img || !g_images.contains(img)) { Log("%s: image %d is 0 or unknown", who, v); return false; }
+			for (int32_t w = 0; w < v; ++w) if (images[w] == images[v]) { Log("%s: image %d appears twice", who, v); return false; }
+		}
+	}
+	if (!scene->finalized) { Log("%s: scene was not finalized (Raylib_FinalizeScene)", who); return false; }
+	if (settings->renderMode >= RAYLIB_RENDERMODE_MAX) { Log("%s: invalid render mode %u", who, settings->renderMode); return false; }
+	if ((uint64_t)settings->viewportWidth * settings->viewportHeight == 0) { Log("%s: empty viewport", who); return false; }
+	const uint64_t cells = (uint64_t)((settings->viewportWidth + 7) / 8) * ((settings->viewportHeight + 7) / 8);
+	if (cells * (uint64_t)count * 64u > 0xF0000000ull) { Log("%s: job count overflow", who); return false; }
+	if (scene->hasMovingCubes) {
+		const Camera* c0 = (const Camera*)cameras[0];
+		for (int32_t v = 1; v < count; ++v) {
+			const Camera* c = (const Camera*)cameras[v];
+			if (c->beginTime != c0->beginTime || c->endTime != c0->endTime) { Log("%s: the scene has moving cubes and the cameras' shutter intervals differ", who); return false; }
+		}
+	}
+	return true;
+}
+
+bool RenderViewsInternal(const char* who, const RendererSettings* settings, Scene* s, const CameraHandle* cameras, int32_t count, void* outDevice, void* const* imagePixels)
+{
+	if (!PrepareRender(who, settings, s, (Camera*)cameras[0])) return false;
+	RenderRequest req;
+	req.settings = *settings;
+	req.camera = ((Camera*)cameras[0])->ToDevice();
+	req.seed = CurrentSeed();
+	req.cellFirst = 0; req.cellStride = 1;
+	req.outDevice = nullptr; req.outHostRGBA = nullptr;
+	std::vector<DCamera> cams((size_t)count);
+	for (int32_t v = 0; v < count; ++v) cams[(size_t)v] = ((Camera*)cameras[v])->ToDevice();
+	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
+	const bool ok = DeviceRenderViews(*s, req, cams.data(), (uint32_t)count, outDevice, imagePixels, stats);
+	{ std::lock_guard<std::mutex> lk(g_stateMu); g_lastStats = stats; }
+	return ok;
+}
+
 } // namespace
 
 extern "C" {
@@ -490,6 +537,36 @@ int32_t RaylibAMD_ProgressiveDecideHost(uint32_t width, uint32_t height, const u
 	return 1;
 }
 
+int32_t RaylibAMD_RenderViews(const RendererSettings* settings, SceneHandle scene, const CameraHandle* cameras, int32_t count, const ImageHandle* outImages)
+{
+	static const char* who = "RaylibAMD_RenderViews";
+	Scene* s = (Scene*)scene;
+	if (!outImages) { Log("%s: null argument", who); return 0; }
+	if (!ViewsArgsValid(who, settings, s, cameras, count, outImages)) return 0;
+	if (!DeviceAvailable()) return 0;
+	// Every refusal is behind us: the images take the viewport's size and device storage (as Raylib_Render), and the batch's frames are copied there
+	std::vector<void*> dev((size_t)count);
+	for (int32_t v = 0; v < count; ++v) {
+		Image* img = (Image*)outImages[v];
+		if (settings->viewportWidth != img->width || settings->viewportHeight != img->height)
+			img->Reallocate(settings->viewportWidth, settings->viewportHeight, 0.0f, 0.0f, 0.0f, 1.0f);
+		dev[(size_t)v] = DeviceImagePixels(*img);
+		if (!dev[(size_t)v]) { Log("%s: no device storage for image %d", who, v); return 0; }
+	}
+	if (!RenderViewsInternal(who, settings, s, cameras, count, nullptr, dev.data())) return 0;
+	for (int32_t v = 0; v < count; ++v) { Image* img = (Image*)outImages[v]; img->devValid = true; img->hostStale = true; img->Touch(); }
+	return 1;
+}
+
+int32_t RaylibAMD_RenderViewsDevice(const RendererSettings* settings, SceneHandle scene, const CameraHandle* cameras, int32_t count, void* outDevice)
+{
+	static const char* who = "RaylibAMD_RenderViewsDevice";
+	Scene* s = (Scene*)scene;
+	if (!ViewsArgsValid(who, settings, s, cameras, count, nullptr)) return 0;
+	if (!DeviceAvailable()) return 0;
+	return RenderViewsInternal(who, settings, s, cameras, count, outDevice, nullptr) ? 1 : 0;
+}
+
 uint32_t RaylibAMD_NumCells(uint32_t w, uint32_t h) { return ((w + 7) / 8) * ((h + 7) / 8); }
 uint64_t RaylibAMD_CellBufferFloats(uint32_t w, uint32_t h, uint32_t cellFirst, uint32_t cellStride)
 {
@@ -735,6 +812,28 @@ int32_t RaylibAMD_PlanRender(SceneHandle sh, const RendererSettings* settings, i
 	const uint32_t cells = ((settings->viewportWidth + 7) / 8) * ((settings->viewportHeight + 7) / 8);
 	const uint32_t spp = (uint32_t)(settings->samplesPerPixel > 1 ? settings->samplesPerPixel : 1);
 	const LaunchPlan L = PlanLaunch(cells, cells, spp, 0, numCUs, workgroupsPerCU, t, knobs);
+	out->batch = L.batch; out->sampleCount = L.sampleCount; out->blocks = L.blocks; out->stackStride = L.stackStride; out->jobChunk = L.jobChunk;
+	out->heads = L.heads; out->jobsPerHead = L.jobsPerHead; out->guideShift = L.guideShift; out->jobs = L.jobs;
+	return 1;
+}
+int32_t RaylibAMD_PlanViews(SceneHandle sh, const RendererSettings* settings, const CameraHandle* cameras, int32_t count, int32_t hasSky,
+                           int32_t numCUs, int32_t workgroupsPerCU, RaylibAMDRenderPlan* out, uint8_t* outCellEmpty)
+{
+	Scene* s = (Scene*)sh;
+	if (!out || numCUs < 1 || !ViewsArgsValid("RaylibAMD_PlanViews", settings, s, cameras, count, nullptr)) return 0;
+	memset(out, 0, sizeof(*out));
+	const RenderKnobs knobs = ReadRenderKnobs();
+	const TracePlan t = PlanTrace(*s, *settings, hasSky != 0, knobs);
+	if (!t.ok) return -1;
+	out->pathTrace = t.pathTrace; out->stack = t.stack; out->prims = t.prims; out->poolK = t.poolK; out->tree = t.tree; out->lstack = t.lstack; out->lds = t.lds; out->plain = t.plain;
+	out->pathsPerWave = t.pathsPerWave; out->treeWidth = t.treeWidth; out->nodeBytes = t.nodeBytes;
+	out->keepNodes4 = t.keepNodes4; out->keepNodes4f = t.keepNodes4f; out->eagerTree = t.eagerTree;
+	std::vector<DCamera> cams((size_t)count);
+	for (int32_t v = 0; v < count; ++v) cams[(size_t)v] = ((Camera*)cameras[v])->ToDevice();
+	const ViewsPlan V = PlanViews(SceneCullScene(*s, hasSky != 0), *settings, cams.data(), (uint32_t)count, t, numCUs, workgroupsPerCU, knobs);
+	if (!V.ok) return 0;
+	if (outCellEmpty) memcpy(outCellEmpty, V.empty.data(), V.empty.size());
+	const LaunchPlan& L = V.launch;
 	out->batch = L.batch; out->sampleCount = L.sampleCount; out->blocks = L.blocks; out->stackStride = L.stackStride; out->jobChunk = L.jobChunk;
 	out->heads = L.heads; out->jobsPerHead = L.jobsPerHead; out->guideShift = L.guideShift; out->jobs = L.jobs;
 	return 1;

@@ -257,4 +257,15 @@ struct DRenderParams {
 	DCamera camera;
 };
 
+// Several views of one scene in one launch (RaylibAMD_RenderViews): the views twins of the kernels (k_trace_views, k_trace_pool_views, k_resolve_views,
+// k_aov_views) take this as one extra trailing argument; DRenderParams then describes the batch -- numLocalCells = views * cellsPerView, batch cell
+// v * cellsPerView + c is cell c of view v -- and its `camera` is not read.  Everything else that could differ between views is the same for all of them
+// (the cull's constant: rl_runtime.inl RenderViewsLocked).
+#define RL_MAX_VIEWS 64
+struct DViews {
+	const DCamera* cameras;      // [views], on the device
+	uint32_t cellsPerView;       // ceil(W / 8) * ceil(H / 8)
+	uint32_t magicCellsPerView;  // floor(2^32 / cellsPerView): batch cell -> view by multiply-high (DecodeView)
+};
+
 } // namespace rl

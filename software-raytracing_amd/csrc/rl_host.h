@@ -230,6 +230,9 @@ bool DecodeJPEG(const std::vector<uint8_t>& data, uint32_t& w, uint32_t& h, std:
 bool DecodeTGA(const std::vector<uint8_t>& data, uint32_t& w, uint32_t& h, std::vector<uint8_t>& rgba);
 bool EncodeJPEG(uint32_t w, uint32_t h, const uint8_t* rgbTopDown, std::vector<uint8_t>& out);   // baseline, quality 75, 4:2:0
 bool DeviceRender(Scene& scene, const RenderRequest& req, RaylibAMDStats& stats);
+// RaylibAMD_RenderViews: `count` views (cameras[v]) of req.settings / req.seed into outDevice (view-major, count * W * H float4; nullptr: the library's
+// own buffer) and, when imagePixels is given, each view's frame copied into imagePixels[v] (W * H float4 on rank 0's device).  Synchronous.
+bool DeviceRenderViews(Scene& scene, const RenderRequest& req, const DCamera* cameras, uint32_t count, void* outDevice, void* const* imagePixels, RaylibAMDStats& stats);
 int32_t DeviceLastTracePlain();   // 1: the last path-traced render's megakernel was the leaf-list kernel's plain instance (rl_plan.cc)
 bool DeviceDrain(RaylibAMDStats* outLastStats);   // waits for multi-rank frames in flight; true + stats when that completed the last render call's numbers
 bool DeviceClosestHit(Scene& scene, const float* rays, int32_t n, float tMin, void* outHits);

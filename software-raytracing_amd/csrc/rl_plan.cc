@@ -4,6 +4,8 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
+#include <cstring>
 #include <stdlib.h>
 
 namespace rl {
@@ -178,6 +180,68 @@ LaunchPlan PlanLaunch(uint32_t numLocalCells, uint32_t numActive, uint32_t spp, 
 		L.guideShift = k.guided > 0 ? shift + (uint32_t)(k.guided - 1) : 0u;
 	}
 	return L;
+}
+
+ViewsPlan PlanViews(const CullScene& cs, const RendererSettings& st, const DCamera* cameras, uint32_t count, const TracePlan& trace,
+                    int numCUs, int workgroupsPerCU, const RenderKnobs& knobs)
+{
+	ViewsPlan V;
+	const uint32_t W = st.viewportWidth, H = st.viewportHeight, cellsX = (W + 7) / 8;
+	V.cellsPerView = cellsX * ((H + 7) / 8);
+	V.numCells = V.cellsPerView * count;
+	V.empty.assign(V.numCells, 0);
+	V.culledPerView.assign(count, 0);
+	V.active.reserve(V.numCells);
+	bool haveL = false;
+	for (uint32_t v = 0; v < count; ++v) {
+		CullResult cr;
+		const uint32_t base = v * V.cellsPerView;
+		bool culled = trace.pathTrace && CullCells(cs, cameras[v], st.maxPathLength, st.rayTMin, W, H, cellsX, 0, 1, V.cellsPerView, cr);
+		if (culled && haveL && (memcmp(cr.L, V.emptyL, sizeof(V.emptyL)) != 0 || cr.raysPerSample != V.raysPerSample)) culled = false;   // (does not happen: see rl_plan.h)
+		if (!culled) { for (uint32_t c = 0; c < V.cellsPerView; ++c) V.active.push_back(base + c); continue; }
+		if (!haveL) { memcpy(V.emptyL, cr.L, sizeof(V.emptyL)); V.raysPerSample = cr.raysPerSample; haveL = true; }
+		for (uint32_t k : cr.active) V.active.push_back(base + k);
+		for (uint32_t c = 0; c < V.cellsPerView; ++c) V.empty[base + c] = cr.empty[c];
+		V.culledPerView[v] = V.cellsPerView - (uint32_t)cr.active.size();
+		V.emptyPixels += cr.emptyPixels;
+	}
+	V.numActive = (uint32_t)V.active.size();
+	const uint32_t spp = (uint32_t)(st.samplesPerPixel > 1 ? st.samplesPerPixel : 1);
+	// the job-count guard of a launch (rl_runtime.inl EnqueueRender) splits samples into batches, never views
+	const uint64_t perSample = (uint64_t)V.numActive * 64u;
+	const uint64_t maxBatch = perSample ? 0xF0000000ull / perSample : spp;
+	V.knobs = knobs;
+	if (maxBatch == 0) return V;
+	V.launch = PlanLaunch(V.numCells, V.numActive, spp, 0, numCUs, workgroupsPerCU, trace, V.knobs);
+	if (V.launch.batch > maxBatch) {
+		V.knobs.sampleBatch = (int)maxBatch;
+		V.launch = PlanLaunch(V.numCells, V.numActive, spp, 0, numCUs, workgroupsPerCU, trace, V.knobs);
+	}
+	V.ok = true;
+	return V;
+}
+
+CullScene SceneCullScene(const Scene& sc, bool hasSky)
+{
+	CullScene cs;
+	cs.prims = !sc.spheres.empty() || !sc.cubes.empty();
+	cs.hasSky = hasSky;
+	cs.hasSun = !(sc.sunIlluminance.x == 0.0f && sc.sunIlluminance.y == 0.0f && sc.sunIlluminance.z == 0.0f);
+	cs.sunIlluminance[0] = sc.sunIlluminance.x; cs.sunIlluminance[1] = sc.sunIlluminance.y; cs.sunIlluminance[2] = sc.sunIlluminance.z;
+	cs.sunDirection[0] = sc.sunDirection.x; cs.sunDirection[1] = sc.sunDirection.y; cs.sunDirection[2] = sc.sunDirection.z;
+	if (!cs.prims && !sc.bvh.nodes.empty() && !sc.triangles.empty()) {
+		const DNode& root = sc.bvh.nodes[0];
+		bool ok = true;
+		for (int k = 0; k < 3; ++k) {
+			double lo = 1e300, hi = -1e300;
+			if (root.left != DNODE_EMPTY) { lo = std::min(lo, (double)root.lmin[k]); hi = std::max(hi, (double)root.lmax[k]); }
+			if (root.right != DNODE_EMPTY) { lo = std::min(lo, (double)root.rmin[k]); hi = std::max(hi, (double)root.rmax[k]); }
+			if (!(lo <= hi) || !std::isfinite(lo) || !std::isfinite(hi)) ok = false;
+			cs.boundsMin[k] = lo; cs.boundsMax[k] = hi;
+		}
+		cs.boundsValid = ok;
+	}
+	return cs;
 }
 
 } // namespace rl

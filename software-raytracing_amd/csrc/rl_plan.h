@@ -56,4 +56,25 @@ struct LaunchPlan {
 LaunchPlan PlanLaunch(uint32_t numLocalCells, uint32_t numActive, uint32_t spp, uint32_t sampleBegin, int numCUs, int workgroupsPerCU,
                       const TracePlan& trace, const RenderKnobs& knobs);
 
+// Several views of one scene in one launch per sample batch (RaylibAMD_RenderViews): the job list of the batch.  Cell c of view v is batch cell
+// v * cellsPerView + c; the list is every view's listed cells, view by view, each view culled on its own (CullCells), a view that is not eligible listing all
+// of its cells.  What the kernels add up for a dropped cell is one constant for the whole batch (emptyL: the sun's illuminance or nothing -- CullCells
+// drops cells only where the sun ray misses the scene, so the constant depends on the scene alone); a view whose constant would differ lists all its cells.
+struct ViewsPlan {
+	bool ok = false;                      // false: the job count of a one-sample batch would overflow
+	uint32_t cellsPerView = 0, numCells = 0, numActive = 0;
+	std::vector<uint32_t> active;         // listed batch cells, ascending
+	std::vector<unsigned char> empty;     // per batch cell: dropped
+	std::vector<uint32_t> culledPerView;  // cells dropped per view
+	uint64_t emptyPixels = 0;             // valid pixels of the dropped cells (per sample)
+	float emptyL[3] = { 0, 0, 0 };
+	uint32_t raysPerSample = 1;           // of a dropped cell's sample (counters)
+	RenderKnobs knobs;                    // the knobs every launch of the batch is planned with: RAYLIB_SAMPLE_BATCH lowered where the job count needs it
+	LaunchPlan launch;                    // the first launch
+};
+ViewsPlan PlanViews(const CullScene& cs, const RendererSettings& st, const DCamera* cameras, uint32_t count, const TracePlan& trace,
+                    int numCUs, int workgroupsPerCU, const RenderKnobs& knobs);
+// The scene's box as the device upload takes it (the root node's two child boxes, rl_runtime.inl UploadScene): a CullScene without a device
+CullScene SceneCullScene(const Scene& sc, bool hasSky);
+
 } // namespace rl

@@ -1436,6 +1436,67 @@ __device__ __forceinline__ JobPixel DecodeJobBatch(const DRenderParams& P, uint3
 	return j;
 }
 
+// ---- the views twins (DViews): a batch cell is (view, cell of that view's frame) ----
+// batch cell -> view (one more multiply-high, corrected as for cellsX) and the cell inside the view
+__device__ __forceinline__ uint32_t DecodeView(const DViews& V, uint32_t batchCell, uint32_t& cellInView)
+{
+	uint32_t view = __umulhi(batchCell, V.magicCellsPerView);
+	uint32_t c = batchCell - view * V.cellsPerView;
+	while (c >= V.cellsPerView) { c -= V.cellsPerView; ++view; }
+	cellInView = c;
+	return view;
+}
+// DecodeJob of a views launch: the pixel of the view's own frame (its stream index and PixelUV are that frame's), the slot of the batch
+__device__ __forceinline__ JobPixel DecodeJobViews(const DRenderParams& P, const DViews& V, uint32_t job, uint32_t& view)
+{
+	JobPixel j;
+	const uint32_t p = job & 63u;
+	const uint32_t rest = job >> 6;
+	uint32_t cellLocal = __umulhi(rest, P.magicSamples);
+	uint32_t sLocal = rest - cellLocal * P.sampleCount;
+	while (sLocal >= P.sampleCount) { sLocal -= P.sampleCount; ++cellLocal; }
+	if (P.activeCells) cellLocal = P.activeCells[cellLocal];
+	uint32_t cell;
+	view = DecodeView(V, cellLocal, cell);
+	uint32_t cy = __umulhi(cell, P.magicCellsX);
+	uint32_t cx = cell - cy * P.cellsX;
+	while (cx >= P.cellsX) { cx -= P.cellsX; ++cy; }
+	j.x = cx * 8u + (p & 7u); j.y = cy * 8u + (p >> 3);
+	j.slot = cellLocal * 64u + p;
+	j.sample = sLocal;
+	j.valid = (j.x < P.width) && (j.y < P.height);
+	return j;
+}
+// DecodeJobBatch of a views launch: the batch is one (cell, sample), so the view is wave-uniform (scalar registers)
+__device__ __forceinline__ JobPixel DecodeJobBatchViews(const DRenderParams& P, const DViews& V, uint32_t base, uint32_t lane, uint32_t& view)
+{
+	JobPixel j;
+	const uint32_t rest = (uint32_t)__builtin_amdgcn_readfirstlane((int)base) >> 6;
+	uint32_t cellLocal = __umulhi(rest, P.magicSamples);
+	uint32_t sLocal = rest - cellLocal * P.sampleCount;
+	while (sLocal >= P.sampleCount) { sLocal -= P.sampleCount; ++cellLocal; }
+	if (P.activeCells) cellLocal = *(const __attribute__((address_space(4))) uint32_t*)(P.activeCells + cellLocal);
+	uint32_t cell;
+	view = DecodeView(V, cellLocal, cell);
+	uint32_t cy = __umulhi(cell, P.magicCellsX);
+	uint32_t cx = cell - cy * P.cellsX;
+	while (cx >= P.cellsX) { cx -= P.cellsX; ++cy; }
+	j.x = cx * 8u + (lane & 7u); j.y = cy * 8u + (lane >> 3);
+	j.slot = cellLocal * 64u + lane;
+	j.sample = sLocal;
+	j.valid = (j.x < P.width) && (j.y < P.height);
+	return j;
+}
+// A view's camera: per lane (a vector load; the table is at most 64 x 96 bytes and stays in the caches) or, for a wave-uniform view, through the
+// scalar cache (the table is written before the launch: constant address space)
+__device__ __forceinline__ DCamera LoadViewCamera(const DViews& V, uint32_t view) { return V.cameras[view]; }
+__device__ __forceinline__ DCamera LoadViewCameraUniform(const DViews& V, uint32_t view)
+{
+	DCamera k;
+	__builtin_memcpy(&k, (const __attribute__((address_space(4))) DCamera*)(V.cameras + (uint32_t)__builtin_amdgcn_readfirstlane((int)view)), sizeof(DCamera));
+	return k;
+}
+
 // ---------------------------------------------------------------------------
 // The job list, sharded over the chip's XCDs.  An MI355X is 8 XCDs with a private, non-coherent 4 MiB L2 each; workgroups are dealt
 // round-robin over them (MI355X_MICROARCH.md "Workgroup dispatch, XCD placement").  The job list (cell-major: all samples of local cell 0,
@@ -1557,415 +1618,33 @@ template <class T> __device__ __forceinline__ T KArg(uint32_t offset)
 	unsigned long long* const counters = countersK; unsigned int* const jobCounter = jobCounterK; \
 	(void)P; (void)S; (void)R; (void)samples; (void)pathStack; (void)counters; (void)jobCounter
 #endif
-
-template <int STACK, bool PRIMS, bool FULL, int LDS = 0, bool PLAIN = false>
-__global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 2))
-k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB* __restrict__ samplesK,
-        float* __restrict__ pathStackK, unsigned long long* __restrict__ countersK, unsigned int* __restrict__ jobCounterK)
-{
-	(void)Pk; (void)Sk; (void)Rk; (void)samplesK; (void)pathStackK; (void)countersK; (void)jobCounterK;
-	RL_TEX_PROLOGUE(Sk);
-	RL_MATH_PROLOGUE();
-	__shared__ int s_stack[STACK * RL_BLOCK];
-	__shared__ float4 s_scene[LDS ? LdsAt<LDS>::TOTAL : 1];
-	const float4* sm = s_scene;
-#if RL_QUEUE_SHARED_CHUNK
-	// LDS == 2: the workgroup's four waves draw their batches of 64 jobs from ONE chunk (low word: next job, high word: end of the chunk)
-	__shared__ unsigned long long s_jobs;
-	__shared__ unsigned int s_lock, s_done;
-	if (LDS == 2 && threadIdx.x == 0) { s_jobs = 0ull; s_lock = 0u; s_done = 0u; }   // empty: the first wave to ask draws the workgroup's first chunk from its XCD's head
-#endif
-	if (LDS) {
-		RL_ARGS();
-		const uint32_t nN = (uint32_t)(LDS == 2 ? S.numLeafRecords : S.numNodes4) * 8u, nT = (uint32_t)S.numTriangles * 4u, nM = (uint32_t)S.numMaterials * RL_LDS_MSTRIDE(PLAIN);
-		for (uint32_t i = threadIdx.x; i < 4u; i += RL_BLOCK) s_scene[RL_LDS_ROOT + i] = ((const float4*)S.nodes)[i];
-		for (uint32_t i = threadIdx.x; i < nN; i += RL_BLOCK) s_scene[RL_LDS_NODES + (i >> 3) * RL_LDS_NSTRIDE + (i & 7u)] = ((const float4*)(LDS == 2 ? S.leafList : S.nodes4f))[i];
-		if (LDS == 2) {
-			for (uint32_t i = threadIdx.x; i < nT; i += RL_BLOCK) s_scene[LdsAt<LDS>::SHADE + i] = ((const float4*)S.shade)[i];
-			for (uint32_t t = threadIdx.x; t < (uint32_t)S.numTriangles; t += RL_BLOCK) {   // the six-float4 record (LdsAt): edges and own box worked out here, once
-				const Tri T = LoadTri(S, (int)t);
-				const V3 mn = v3(fminf(fminf(T.v0.x, T.v1.x), T.v2.x), fminf(fminf(T.v0.y, T.v1.y), T.v2.y), fminf(fminf(T.v0.z, T.v1.z), T.v2.z));
-				const V3 mx = v3(fmaxf(fmaxf(T.v0.x, T.v1.x), T.v2.x), fmaxf(fmaxf(T.v0.y, T.v1.y), T.v2.y), fmaxf(fmaxf(T.v0.z, T.v1.z), T.v2.z));
-				float4* r = s_scene + LdsAt<LDS>::ISECT + t * 6u;
-				r[0] = make_float4(T.v0.x, T.v0.y, T.v0.z, T.n.x); r[1] = make_float4(T.n.y, T.n.z, T.u.x, T.u.y); r[2] = make_float4(T.u.z, T.v.x, T.v.y, T.v.z);
-				r[3] = make_float4(T.uv, T.uu, T.vv, T.denom); r[4] = make_float4(mn.x, mn.y, mn.z, mx.x); r[5] = make_float4(mx.y, mx.z, T.rden, 0.0f);
-			}
-		} else {
-			for (uint32_t i = threadIdx.x; i < nT; i += RL_BLOCK) { const uint32_t at = (i >> 2) * RL_LDS_TSTRIDE + (i & 3u); s_scene[LdsAt<LDS>::ISECT + at] = ((const float4*)S.isect)[i]; s_scene[LdsAt<LDS>::SHADE + at] = ((const float4*)S.shade)[i]; }
-		}
-		for (uint32_t i = threadIdx.x; i < nM; i += RL_BLOCK) s_scene[LdsAt<LDS>::MATS + i] = ((const float4*)S.materials)[PLAIN ? (i >> 2) * 5u + (i & 3u) : i];
-		__syncthreads();
-	}
-	int* stk = s_stack + threadIdx.x;
-	const uint32_t gtid = blockIdx.x * RL_BLOCK + threadIdx.x;
-	const uint32_t lane = threadIdx.x & 63u;
-	uint32_t numSlots;
-	JobSource js;
-	{ RL_ARGS(); numSlots = P.numLocalCells * 64u; js = JobSourceInit(P); }
-
-	Counters c; c.rays = c.nodes = c.tris = c.shaded = c.texels = c.samples = c.trips = 0; RL_DIAG_BIND(c);
-	Rng g; g.s.state = 0;
-	V3 o = v3s(0.0f), d = v3s(0.0f);
-	float rayTime = 0.0f;
-	int depth = 0;
-	uint32_t outIndex = 0;
-	bool active = false;
-	bool exhausted = false;
-
-	// Wave-local job range: the wave takes P.jobChunk (64..1024) consecutive jobs from the global counter
-	// with ONE atomic and deals them to its lanes itself.  (A returning atomic on one address
-	// saturates near 88 dequeues/us chip-wide -- MI355X_MICROARCH.md "dequeue" -- and one atomic
-	// per wave and bounce was exactly that rate: the kernel ran at the atomic's speed.)
-	// (Round 2 gave every wave its first chunk without an atomic, because 4096 waves asking ONE counter at the same instant stood in line for ~45 us; with a
-	// head per XCD the line is an eighth as long and the first chunk comes from the wave's own band like every other.)
-	uint32_t chunkNext = 0, chunkEnd = 0;
-	bool globalDone = false;
-	uint32_t qCount = 0;   // LDS == 2: camera rays waiting in the wave's queue
-	RL_TIMELINE(0);
-#ifdef RL_DIAG_STAMPS
-	// diagnostic build only: shader-clock time per phase (refill | traverse | shade | fold), summed per wave
-	unsigned long long stampAcc[4] = { 0, 0, 0, 0 }, subAcc[4] = { 0, 0, 0, 0 }, laneAcc[4] = { 0, 0, 0, 0 }, laneT[4] = { 0, 0, 0, 0 };
-	{ RL_ARGS(); c.diag = counters; }
-	unsigned long long stampLast = __builtin_amdgcn_s_memtime();
-	#define RL_SUBSTAMP(k) { __builtin_amdgcn_sched_barrier(0); const unsigned long long now_ = __builtin_amdgcn_s_memtime(); subAcc[k] += now_ - subLast; subLast = now_; __builtin_amdgcn_sched_barrier(0); }
-	unsigned long long subLast = 0;
-	#define RL_STAMP(k) { __builtin_amdgcn_sched_barrier(0); const unsigned long long now_ = __builtin_amdgcn_s_memtime(); stampAcc[k] += now_ - stampLast; stampLast = now_; __builtin_amdgcn_sched_barrier(0); }
-	// lane-weighted: clock x lanes that took part in the phase (k: 0 traverse, 1 shade a hit, 2 miss shader, 3 fold)
-	#define RL_LANESTAMP(k, cond) { __builtin_amdgcn_sched_barrier(0); const unsigned long long now_ = __builtin_amdgcn_s_memtime(); laneAcc[k] += (now_ - laneLast) * (unsigned long long)__popcll(Ballot(cond)); laneT[k] += now_ - laneLast; __builtin_amdgcn_sched_barrier(0); }
-	#define RL_LANEBEGIN() { __builtin_amdgcn_sched_barrier(0); laneLast = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
-	unsigned long long laneLast = 0;
+// The views twins' arguments: KTraceArgs and the view table behind it, so that RL_ARGS() reads the same offsets in both
+struct KTraceViewsArgs { KTraceArgs A; DViews V; };
+#if RL_KARG_RELOAD
+#define RL_VIEWS() const DViews VW = KArg<DViews>((uint32_t)offsetof(KTraceViewsArgs, V)); (void)VW
 #else
-	#define RL_STAMP(k)
-	#define RL_SUBSTAMP(k)
-	#define RL_LANESTAMP(k, cond)
-	#define RL_LANEBEGIN()
+#define RL_VIEWS() const DViews& VW = Vk; (void)VW
 #endif
 
-#ifdef RL_WATCHDOG
-	unsigned guardMain = 0;
-#endif
-	for (;;) {
-#ifdef RL_WATCHDOG
-		if (++guardMain > 200000u) { if (lane == 0) printf("k_trace main loop stuck: block %u wave %u active %llx exhausted %llx qCount %u globalDone %d chunk %u %u depth %d\n", blockIdx.x, threadIdx.x >> 6, (unsigned long long)Ballot(active), (unsigned long long)Ballot(exhausted), qCount, (int)globalDone, chunkNext, chunkEnd, depth); break; }
-#endif
-		// ---- refill idle lanes: wave64 ballot + prefix rank ----
-		// Up to RL_REFILL_ROUNDS rounds: a fresh camera ray that misses both boxes of the root node can
-		// only run the (sun-less) miss shader, so it is finished here and its lane takes another job at
-		// once instead of occupying a lane slot through a whole bounce trip (in a 16:9 Cornell frame
-		// more than half of the camera samples never touch the scene).
-		if constexpr (LDS == 2) {
-			RL_ARGS();
-			// Leaf-list scenes need no traversal stack, and its LDS (1024 dwords per wave) is a QUEUE of camera rays instead: rays are
-			// generated 64 at a time -- every lane takes a job, the same code for all of them -- the ones that cannot hit anything are finished
-			// on the spot as in the rounds below, the others are written to the queue back to back (ballot + prefix rank), and the idle
-			// lanes take theirs from its end.  The rounds below generate for the idle lanes only: a third of the wave in the first round, then a half
-			// of that (in a 16:9 Cornell frame more than half of the camera samples miss the room), a quarter ... at the cost of a whole wave each time.
-			enum { QCAP = 112, QFIELDS = 9 };   // 9 x 112 dwords <= 1024
-			int* q = s_stack + (threadIdx.x >> 6) * (STACK * 64);
-			const bool need = !active && !exhausted;
-			const unsigned long long needMask = Ballot(need);
-			const uint32_t n = (uint32_t)__popcll(needMask);
-			while (n > 0 && qCount < n && qCount <= QCAP - 64 && !(globalDone && chunkNext >= chunkEnd)) {
-#if RL_QUEUE_SHARED_CHUNK
-				// The next batch of the workgroup's chunk: one LDS atomic.  The chunk is the granule of the GLOBAL job list (one global atomic per
-				// P.jobChunk jobs, as before), the batch the granule of a wave's work: when the list runs dry a wave has at most its batch in
-				// front of it, not a chunk -- the launch's tail shrinks from "one chunk per wave" to "a quarter of one".
-				// Whoever finds the chunk used up takes the lock, asks the global counter and publishes the new chunk; the others wait for it.
-				for (;;) {
-					unsigned long long st = 0ull;
-					if (lane == 0) st = atomicAdd(&s_jobs, 64ull);
-					st = __shfl(st, 0);
-					const uint32_t nx = (uint32_t)st, en = (uint32_t)(st >> 32);
-					if (nx < en) { chunkNext = nx; chunkEnd = min(nx + 64u, en); break; }
-					if (__atomic_load_n(&s_done, __ATOMIC_RELAXED) != 0u) { globalDone = true; chunkNext = chunkEnd = 0; break; }
-					uint32_t won = 0;
-					if (lane == 0) won = atomicCAS(&s_lock, 0u, 1u) == 0u ? 1u : 0u;
-					won = __shfl(won, 0);
-					if (won) {
-						__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-						const unsigned long long cur = __atomic_load_n(&s_jobs, __ATOMIC_RELAXED);
-						if ((uint32_t)cur >= (uint32_t)(cur >> 32) && __atomic_load_n(&s_done, __ATOMIC_RELAXED) == 0u) {   // still used up: nobody refilled it in between
-							uint32_t base = 0, bend = 0;
-							const bool got = TakeJobs(P, jobCounter, js, P.jobChunk, lane, base, bend);
-							if (lane == 0) {
-								if (!got) __atomic_store_n(&s_done, 1u, __ATOMIC_RELAXED);
-								else __atomic_store_n(&s_jobs, (unsigned long long)base | ((unsigned long long)bend << 32), __ATOMIC_RELAXED);
-							}
-						}
-						__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-						if (lane == 0) __atomic_store_n(&s_lock, 0u, __ATOMIC_RELAXED);
-					} else {
-						// wait for the wave that is asking the global counter (microseconds).  Not for ever: a wave that has waited ~1 ms stops relying
-						// on its neighbours and takes one batch straight from the global counter -- always correct, the counter is the truth
-#if RL_QUEUE_SPIN_LIMIT == 0
-						while (__atomic_load_n(&s_lock, __ATOMIC_RELAXED) != 0u) __builtin_amdgcn_s_sleep(2);
-						if (false) {
+#define RL_VIEWS_TWIN 0
+#include "rl_k_trace.inl"
+#undef RL_VIEWS_TWIN
+#define RL_VIEWS_TWIN 1
+#include "rl_k_trace.inl"
+#undef RL_VIEWS_TWIN
+// The twins' instances are compiled in a translation unit of their own (rl_render_views.hip): instantiated here beside the one-view kernels they would change
+// how the helpers both call are inlined into those (tools/isa_equivalence.py).  (STACK, PRIMS, FULL, LDS, PLAIN): every instance rl_runtime.inl KernelFor names.
+#define RL_TRACE_INSTANCES(X) \
+	X(16, false, false, 0, false) X(16, false, true, 0, false) X(16, false, true, 1, false) X(16, false, true, 2, false) X(16, false, true, 2, true) \
+	X(32, false, false, 0, false) X(32, false, true, 0, false) X(32, true, false, 0, false) X(32, true, true, 0, false) \
+	X(64, false, false, 0, false) X(64, false, true, 0, false) X(64, true, false, 0, false) X(64, true, true, 0, false)
+#ifdef RL_TU_VIEWS
+#define RL_TRACE_X(a, b, c, d, e) template __global__ void k_trace_views<a, b, c, d, e>(const DRenderParams, const DSceneView, const SkyRot, SampleRGB* __restrict__, float* __restrict__, unsigned long long* __restrict__, unsigned int* __restrict__, const DViews);
 #else
-						uint32_t spins = 0;
-						while (__atomic_load_n(&s_lock, __ATOMIC_RELAXED) != 0u && ++spins < RL_QUEUE_SPIN_LIMIT) __builtin_amdgcn_s_sleep(2);
-						if (spins >= RL_QUEUE_SPIN_LIMIT) {
+#define RL_TRACE_X(a, b, c, d, e) extern template __global__ void k_trace_views<a, b, c, d, e>(const DRenderParams, const DSceneView, const SkyRot, SampleRGB* __restrict__, float* __restrict__, unsigned long long* __restrict__, unsigned int* __restrict__, const DViews);
 #endif
-							uint32_t base = 0, bend = 0;
-							if (!TakeJobs(P, jobCounter, js, 64u, lane, base, bend)) { globalDone = true; chunkNext = chunkEnd = 0; }
-							else { chunkNext = base; chunkEnd = bend; }
-							break;
-						}
-					}
-				}
-				if (globalDone) { RL_TIMELINE(1); break; }
-#else
-				if (chunkNext >= chunkEnd) {
-					uint32_t base = 0, bend = 0;
-					if (!TakeJobs(P, jobCounter, js, P.jobChunk, lane, base, bend)) { globalDone = true; RL_TIMELINE(1); break; }
-					chunkNext = base; chunkEnd = bend;
-				}
-#endif
-				const uint32_t avail = chunkEnd - chunkNext;
-				bool survive = false;
-				V3 qo = v3s(0.0f), qd = v3s(0.0f); Rng qg; qg.s.state = 0; uint32_t qOut = 0;
-				if (lane < avail) {
-					const JobPixel j = DecodeJobBatch(P, chunkNext, lane);
-					if (j.valid) {
-						// GenerateCell body, reference render/renderer.cc:232-239
-						const uint32_t sm_ = P.sampleBegin + j.sample;
-						qg.s = raylib_rng_begin_mixed(P.seedMixed, j.y * P.width + j.x, sm_);
-						float u, v;
-						PixelUV(P, j.x, j.y, sm_, qg, u, v);
-						float qTime;
-						CameraRay(P.camera, u, v, qg, qo, qd, qTime);
-						qOut = j.sample * numSlots + j.slot;
-						c.samples++;
-						survive = true;
-						if (P.maxPathLength > 0 && RootMiss<LDS>(S, qo, qd, P.rayTMin, sm)) {
-							const bool sunQuick = !S.hasSun || RootMiss<LDS>(S, qo, -ld3(S.sunDirection), P.rayTMin, sm);
-							if (sunQuick) {
-								c.rays++; c.nodes++;   // the closest-hit query this replaces fetches the root node and stops
-								DSceneView Sq = S; Sq.hasSun = 0;
-								V3 L = MissShader<STACK, PRIMS, FULL, LDS, PLAIN>(Sq, R, qo, qd, qTime, P.rayTMin, stk, c, sm);
-								if (S.hasSun) { c.rays++; c.nodes++; L = L + ld3(S.sunIlluminance); }
-								samples[qOut] = make_sample(L.x, L.y, L.z);
-								survive = false;
-							}
-						}
-					}
-				}
-				chunkNext += min(64u, avail);
-				const unsigned long long sv = Ballot(survive);
-				if (survive) {
-					const uint32_t at = qCount + (uint32_t)__popcll(sv & ((1ull << lane) - 1ull));
-					q[0 * QCAP + at] = __float_as_int(qo.x); q[1 * QCAP + at] = __float_as_int(qo.y); q[2 * QCAP + at] = __float_as_int(qo.z);
-					q[3 * QCAP + at] = __float_as_int(qd.x); q[4 * QCAP + at] = __float_as_int(qd.y); q[5 * QCAP + at] = __float_as_int(qd.z);
-					q[6 * QCAP + at] = (int)(uint32_t)qg.s.state; q[7 * QCAP + at] = (int)(uint32_t)(qg.s.state >> 32); q[8 * QCAP + at] = (int)qOut;
-				}
-				qCount += (uint32_t)__popcll(sv);
-				WaveLdsSync();
-			}
-			if (need) {
-				const uint32_t rank = (uint32_t)__popcll(needMask & ((1ull << lane) - 1ull));
-				if (rank < qCount) {
-					const uint32_t at = qCount - 1u - rank;
-					o = v3(__int_as_float(q[0 * QCAP + at]), __int_as_float(q[1 * QCAP + at]), __int_as_float(q[2 * QCAP + at]));
-					d = v3(__int_as_float(q[3 * QCAP + at]), __int_as_float(q[4 * QCAP + at]), __int_as_float(q[5 * QCAP + at]));
-					g.s.state = (uint64_t)(uint32_t)q[6 * QCAP + at] | ((uint64_t)(uint32_t)q[7 * QCAP + at] << 32);
-					outIndex = (uint32_t)q[8 * QCAP + at];
-					rayTime = 0.0f;   // leaf-list scenes are triangle scenes: nothing moves, the ray's time is not read
-					depth = 0;
-					active = true;
-				} else if (globalDone && chunkNext >= chunkEnd) exhausted = true;
-			}
-			qCount -= min(n, qCount);
-			WaveLdsSync();
-		} else
-		for (int round = 0; round < RL_REFILL_ROUNDS; ++round) {
-			RL_ARGS();
-			const bool need = !active && !exhausted;
-			const unsigned long long mask = Ballot(need);
-			if (mask == 0ull) break;
-			if (chunkNext >= chunkEnd && !globalDone) {
-				uint32_t base = 0, bend = 0;
-				if (!TakeJobs(P, jobCounter, js, P.jobChunk, lane, base, bend)) { globalDone = true; RL_TIMELINE(1); }
-				else { chunkNext = base; chunkEnd = bend; }
-			}
-			const uint32_t avail = chunkEnd - chunkNext;
-			if (need) {
-				const uint32_t rank = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-				if (rank >= avail) {
-					if (globalDone) exhausted = true;   // else: served in a later round / trip from the next chunk
-				} else {
-					const uint32_t job = chunkNext + rank;
-					const JobPixel j = DecodeJob(P, job);
-					if (j.valid) {
-						// GenerateCell body, reference render/renderer.cc:232-239
-						const uint32_t s = P.sampleBegin + j.sample;
-						g.s = raylib_rng_begin_mixed(P.seedMixed, j.y * P.width + j.x, s);
-						float u, v;
-						PixelUV(P, j.x, j.y, s, g, u, v);
-						CameraRay(P.camera, u, v, g, o, d, rayTime);
-						depth = 0;
-						outIndex = j.sample * numSlots + j.slot;
-						active = true;
-						c.samples++;
-						if (P.maxPathLength > 0 && RootMiss<LDS>(S, o, d, P.rayTMin, sm)) {
-							// The camera ray cannot hit anything.  Its miss shader (renderer.cc:155-199) is the sky lookup plus,
-							// with a sun, one occlusion query from the ray origin; if that shadow ray misses the root too, the
-							// whole sample is decided here.
-							const bool sunQuick = !S.hasSun || RootMiss<LDS>(S, o, -ld3(S.sunDirection), P.rayTMin, sm);
-							if (sunQuick) {
-								c.rays++; c.nodes++;   // the closest-hit query this replaces fetches the root node and stops
-								DSceneView Sq = S; Sq.hasSun = 0;
-								V3 L = MissShader<STACK, PRIMS, FULL, LDS, PLAIN>(Sq, R, o, d, rayTime, P.rayTMin, stk, c, sm);
-								if (S.hasSun) { c.rays++; c.nodes++; L = L + ld3(S.sunIlluminance); }
-								samples[outIndex] = make_sample(L.x, L.y, L.z);
-								active = false;
-							}
-						}
-					}
-				}
-			}
-			chunkNext += min((uint32_t)__popcll(mask), avail);
-		}
-		if (Ballot(active) == 0ull) {
-			if (Ballot(!exhausted) == 0ull) break;
-			continue;
-		}
-
-		// ---- one bounce for every active lane (TraceScene, reference render/renderer.cc:114-208) ----
-		if (lane == 0) c.trips++;
-		RL_STAMP(0);
-		RL_LANEBEGIN();
-		HitRec h; h.tri = -1;
-		bool doTrace, hit = false;
-		{
-		RL_ARGS();
-		doTrace = active && depth < P.maxPathLength;   // renderer.cc:120-123 otherwise
-		// the 4-wide tree when the launch carries it (triangle scenes; half the steps: 24.6 -> 22.4 ms on the Cornell frame)
-		if (doTrace) {
-			if constexpr (LDS != 0) hit = Traverse4<STACK, false, PRIMS, FULL, LDS, PLAIN>(S, o, d, rayTime, P.rayTMin, h, stk, c, sm);   // an LDS-resident scene has its wide tree
-			else hit = (!PRIMS && (FULL ? (const void*)S.nodes4f : (const void*)S.nodes4)) ? Traverse4<STACK, false, PRIMS, FULL, LDS>(S, o, d, rayTime, P.rayTMin, h, stk, c, sm) : Traverse<STACK, false, PRIMS>(S, o, d, rayTime, P.rayTMin, h, stk, c);
-		}
-		}
-		RL_LANESTAMP(0, doTrace);
-		RL_STAMP(1);
-		if (active) {
-			bool done = false, store = false;
-			float4 rec0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rec1 = rec0;
-			V3 L = v3s(0.0f);
-			if (!doTrace) {
-				done = true;
-			} else if (hit) {
-				RL_ARGS();
-				Surf s;
-				RL_LANEBEGIN();
-#ifdef RL_DIAG_STAMPS
-				subLast = __builtin_amdgcn_s_memtime();
-#endif
-				const int mi = BuildSurface<PRIMS, LDS>(S, o, d, h, s, true, c, sm);
-				const Mat m = LDS ? MatFrom<PLAIN>(sm + LdsAt<LDS>::MATS + mi * RL_LDS_MSTRIDE(PLAIN)) : LoadMat(S, mi);
-				RL_SUBSTAMP(0);
-				V3 refl = v3s(0.0f), outD = v3s(0.0f);
-				float pdf = 0.0f, sp = 0.0f;
-				const bool scattered = Scatter<PLAIN>(S, m, d, s, g, c, refl, outD, pdf, sp);
-				RL_SUBSTAMP(1);
-				const V3 E = Emitted(S, m, s, c);
-				if (scattered && pdf > 0.0f) {
-					if (depth + 1 >= P.maxPathLength) {
-						// the next TraceScene returns 0 at once (renderer.cc:120-123): this vertex is the path's last, and its step of the
-						// fold -- radiance = (0 + refl * 0 * sp / pdf) + E, the reference's expression -- is taken from the registers
-						V3 radiance = v3s(0.0f);
-						radiance = radiance + refl * L * sp / pdf;
-						radiance = radiance + E;
-						L = radiance;
-						done = true;
-					} else {
-						// the vertex record (refl, sp | pdf, E) goes to the path stack BEHIND this trip's fold (below): a wave counts loads and
-						// stores in one in-order counter, and a fold that waits for its loads behind this trip's stores waits for their write
-						// acknowledgements too
-						store = true;
-						rec0 = make_float4(refl.x, refl.y, refl.z, sp);
-						rec1 = make_float4(pdf, E.x, E.y, E.z);
-						o = s.p; d = outD;
-					}
-				} else {
-					L = v3s(0.0f) + E;                        // radiance(0) += Emitted, renderer.cc:137,151
-					done = true;
-				}
-				RL_SUBSTAMP(2);
-				RL_LANESTAMP(1, true);
-			} else {
-				RL_ARGS();
-				RL_LANEBEGIN();
-				L = MissShader<STACK, PRIMS, FULL, LDS, PLAIN>(S, R, o, d, rayTime, P.rayTMin, stk, c, sm);
-				done = true;
-				RL_LANESTAMP(2, true);
-			}
-			RL_STAMP(2);
-			if (done) {
-				RL_ARGS();
-				RL_LANEBEGIN();
-				// fold back to the camera: radiance = (0 + refl*Li*sp/pdf) + E at every vertex
-#if RL_FOLD_PREFETCH > 0
-				if (depth <= RL_FOLD_PREFETCH) {
-					// all vertex records of the path are fetched before the dependent chain starts (one memory latency instead of one per vertex)
-					float4 q0[RL_FOLD_PREFETCH], q1[RL_FOLD_PREFETCH];
-					#pragma unroll
-					for (int k = 0; k < RL_FOLD_PREFETCH; ++k) {
-						const int kk = k < depth ? k : 0;
-						const float4* st = (const float4*)pathStack + ((size_t)kk * P.stackStride + gtid) * 2u;
-						q0[k] = st[0]; q1[k] = st[1];
-					}
-					#pragma unroll
-					for (int k = RL_FOLD_PREFETCH - 1; k >= 0; --k) {
-						if (k < depth) {
-							const V3 refl = v3(q0[k].x, q0[k].y, q0[k].z);
-							const float sp = q0[k].w, pdf = q1[k].x;
-							const V3 E = v3(q1[k].y, q1[k].z, q1[k].w);
-							V3 radiance = v3s(0.0f);
-							radiance = radiance + refl * L * sp / pdf;
-							radiance = radiance + E;
-							L = radiance;
-						}
-					}
-				} else
-#endif
-				for (int k = depth - 1; k >= 0; --k) {
-					const float4* st = (const float4*)pathStack + ((size_t)k * P.stackStride + gtid) * 2u;
-					const float4 r0 = st[0], r1 = st[1];
-					const V3 refl = v3(r0.x, r0.y, r0.z);
-					const float sp = r0.w, pdf = r1.x;
-					const V3 E = v3(r1.y, r1.z, r1.w);
-					V3 radiance = v3s(0.0f);
-					radiance = radiance + refl * L * sp / pdf;
-					radiance = radiance + E;
-					L = radiance;
-				}
-				samples[outIndex] = make_sample(L.x, L.y, L.z);
-				active = false;
-				RL_LANESTAMP(3, true);
-			}
-			if (store) {
-				RL_ARGS();
-				// path vertex record: 32 contiguous bytes per lane, two 16-byte stores
-				float4* st = (float4*)pathStack + ((size_t)depth * P.stackStride + gtid) * 2u;
-				st[0] = rec0; st[1] = rec1;
-				depth++;
-			}
-		}
-		RL_STAMP(3);
-	}
-
-	RL_ARGS();
-#ifdef RL_DIAG_STAMPS
-	if (lane == 0) for (int k = 0; k < 4; ++k) { atomicAdd(&counters[CNT_COUNT + k], stampAcc[k]); atomicAdd(&counters[CNT_COUNT + 8 + k], subAcc[k]); atomicAdd(&counters[CNT_COUNT + 12 + k], c.tAcc[k]); atomicAdd(&counters[CNT_COUNT + 20 + k], laneAcc[k]); if (RL_DIAG_STAMPS < 2) atomicAdd(&counters[CNT_COUNT + 4 + k], laneT[k]); }
-#endif
-	RL_TIMELINE(2);
-	// ---- counters: wave reduction, one atomic per wave and counter ----
-	uint32_t vals[CNT_COUNT] = { c.rays, c.nodes, c.tris, c.shaded, c.texels, c.samples, c.trips };
-	for (int k = 0; k < CNT_COUNT; ++k) {
-		unsigned long long v = vals[k];
-		for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-		if (lane == 0 && v) atomicAdd(&counters[k], v);
-	}
-}
+RL_TRACE_INSTANCES(RL_TRACE_X)
+#undef RL_TRACE_X
 
 // ---------------------------------------------------------------------------
 // The pool megakernel.  Same job queue, same per-path arithmetic and the same outputs as k_trace, but a wave
@@ -2378,477 +2057,26 @@ template <int LSTACK, bool PRIMS, int K> struct PoolOcc {
 
 // STACK: capacity of the traversal stack; LSTACK <= STACK: how much of it lives in LDS (the rest is private overflow)
 // WIDE: 0 the BVH2; 1 the BVH4 (S.nodes4: 64-byte grid nodes); 3 the 8-wide tree (S.nodes8; STACK / LSTACK then count words: two per group)
-template <int STACK, bool PRIMS, int K, int LSTACK = STACK, int WIDE = 0>
-__global__ void __launch_bounds__(RL_BLOCK, (PoolOcc<LSTACK, PRIMS, K>::kBlocks))
-k_trace_pool(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB* __restrict__ samplesK,
-             float* __restrict__ pathStackK, unsigned long long* __restrict__ countersK, unsigned int* __restrict__ jobCounterK)
-#ifndef RL_TU_POOL
-;   // defined in the translation unit of rl_render_pool.hip: this same source, compiled with a scheduler strategy of its own (Makefile); instances below
-#else
-{
-	(void)Pk; (void)Sk; (void)Rk; (void)samplesK; (void)pathStackK; (void)countersK; (void)jobCounterK;   // read through RL_ARGS() where a part of the loop needs them (k_trace)
-	RL_TEX_PROLOGUE(Sk);
-	RL_MATH_PROLOGUE();
-	constexpr int PP = 64 * K;
-	static_assert(LSTACK <= STACK, "the LDS part cannot exceed the stack");
-	__shared__ int s_stack[LSTACK * RL_BLOCK];
-	int ovfStore[LSTACK < STACK ? STACK - LSTACK : 1];
-	int* ovf = ovfStore;
-	__shared__ float s_pool[RL_BLOCK / 64][PoolOcc<LSTACK, PRIMS, K>::kFields][PP];
-	__shared__ unsigned char s_free[RL_BLOCK / 64][PP];
-	// the 8-wide walk: s_perm[oct * 256 + y] = the byte y with every bit b moved to bit b XOR oct (slot order -> visiting order of a ray of octant oct)
-	// ... and the top of that tree: its first RL_TOP8_NODES nodes (rl_device.h), five 16-byte rows each
-	__shared__ uint4 s_top[(WIDE == 3 && RL_TOP8_NODES > 0) ? RL_TOP8_NODES * 5 : 1];
-	__shared__ unsigned char s_perm[WIDE == 3 ? 8 * 256 : 1];
-	if constexpr (WIDE == 3) {
-#if RL_TOP8_NODES > 0
-		{
-			RL_ARGS();
-			const uint32_t rows = (uint32_t)(S.numNodes8 < RL_TOP8_NODES ? S.numNodes8 : RL_TOP8_NODES) * 5u;
-			for (uint32_t i = threadIdx.x; i < (uint32_t)RL_TOP8_NODES * 5u; i += RL_BLOCK) s_top[i] = i < rows ? GLoadU4(S.nodes8, (int)i) : make_uint4(0u, 0u, 0u, 0u);
-		}
-#endif
-		for (uint32_t i = threadIdx.x; i < 8u * 256u; i += RL_BLOCK) {
-			const uint32_t m = i >> 8, y = i & 255u;
-			uint32_t r = 0;
-			for (uint32_t bb = 0; bb < 8u; ++bb) if ((y >> bb) & 1u) r |= 1u << (bb ^ m);
-			s_perm[i] = (unsigned char)r;
-		}
-		__syncthreads();
-	}
-	constexpr int G8 = LSTACK / 2, GMAX8 = STACK / 2;   // groups in the LDS part of the stack, groups in all
-
-	int* stk = s_stack + threadIdx.x;
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	float (*pool)[PP] = s_pool[wave];
-	unsigned char* freeList = s_free[wave];
-	uint32_t numSlots;
-	JobSource js;
-	{ RL_ARGS(); numSlots = P.numLocalCells * 64u; js = JobSourceInit(P); }
-	const unsigned long long laneLt = (1ull << lane) - 1ull;
-	// path-stack column of home slot p: consecutive lanes -> consecutive columns
-	const uint32_t homeBase = blockIdx.x * (RL_BLOCK * K) + threadIdx.x;
-
-	Counters c; c.rays = c.nodes = c.tris = c.shaded = c.texels = c.samples = c.trips = 0; RL_DIAG_BIND(c);
-	// home-lane registers of slot p*64 + lane
-	unsigned long long stRng[K];
-	uint32_t stOut[K];
-	int stDepth[K];
-	bool stActive[K];
-	#pragma unroll
-	for (int p = 0; p < K; ++p) { stRng[p] = 0; stOut[p] = 0; stDepth[p] = 0; stActive[p] = false; pool[F_TRI][p * 64 + lane] = __int_as_float(Q_EMPTY); }
-	// (Round 2 gave every wave its first chunk without an atomic, because 4096 waves asking ONE counter at the same instant stood in line for ~45 us; with a
-	// head per XCD the line is an eighth as long and the first chunk comes from the wave's own band like every other.)
-	uint32_t chunkNext = 0, chunkEnd = 0;
-	bool globalDone = false, exhausted = false;   // wave-uniform
-#ifdef RL_DIAG_TIMELINE
-	const uint32_t gtid = blockIdx.x * RL_BLOCK + threadIdx.x;
-#endif
-	RL_TIMELINE(0);
-	uint32_t surviveQ8 = 256u;                    // share of freshly generated camera samples that reached a pool slot, x 256 (wave-uniform)
-	// traversal state of the ray this lane is tracing; survives trips (a straggler keeps going while the rest of the pool is shaded)
-	// A lane without a ray has T.cur == IDLE (no node index, not negative like a leaf reference): "busy", "at an inner node", "at a leaf" are then ONE integer
-	// compare each, and a wave vote on a compare is that compare's lane mask.  (A vote on a bool that is not a compare -- `busy && T.cur >= 0` -- makes the
-	// compiler write the bool out as 0 / 1 and compare it with zero again: v_cndmask + v_cmp_ne per vote, four votes per traversal step.)
-	constexpr int IDLE = 0x7fffffff;
-	int mySlot = 0;
-	Trav T;
-	T.o = T.d = T.inv = v3s(0.0f); T.rayTime = 0.0f; T.nx = T.ny = T.nz = T.anyhit = false;
-	T.best.t = INFINITY; T.best.a = T.best.b = 0.0f; T.best.tri = -1; T.cur = IDLE; T.sp = 0; T.leafI = 0;
-	T.gx = T.gy = T.tx = T.ty = T.tz = T.oct = 0u; T.m8x = T.m8y = T.m8z = 0u;
-#ifdef RL_DIAG_STAMPS
-	unsigned long long stampAcc[4] = { 0, 0, 0, 0 };
-	{ RL_ARGS(); c.diag = counters; }
-	unsigned long long stampLast = __builtin_amdgcn_s_memtime();
-	#define RL_PSTAMP(k) { __builtin_amdgcn_sched_barrier(0); const unsigned long long now_ = __builtin_amdgcn_s_memtime(); stampAcc[k] += now_ - stampLast; stampLast = now_; __builtin_amdgcn_sched_barrier(0); }
-#else
-	#define RL_PSTAMP(k)
-#endif
-
-#ifdef RL_POOL_WATCHDOG
-	uint32_t wdSteps = 0, wdTrips = 0; bool wdAbort = false;
-#endif
-	for (;;) {
-#ifdef RL_POOL_WATCHDOG
-		if (++wdTrips > 20000u || Ballot(wdAbort) != 0ull) {
-			uint32_t nAct = 0, nEmpty = 0, nQ = 0, nH = 0, nPend = 0, nRes = 0;
-			for (int p = 0; p < K; ++p) {
-				const int q = __float_as_int(pool[F_TRI][p * 64 + (int)lane]);
-				nAct += (uint32_t)__popcll(Ballot(stActive[p]));
-				nEmpty += (uint32_t)__popcll(Ballot(stActive[p] && q == Q_EMPTY));
-				nQ += (uint32_t)__popcll(Ballot(stActive[p] && (q == Q_CLOSEST || q == Q_SHADOW)));
-				nH += (uint32_t)__popcll(Ballot(stActive[p] && q >= 0));
-				nPend += (uint32_t)__popcll(Ballot(stActive[p] && (q == Q_PENDING || q == Q_PENDING_SHADOW)));
-				nRes += (uint32_t)__popcll(Ballot(stActive[p] && (q == Q_MISS || q == Q_CLEAR || q == Q_OCCLUDED)));
-			}
-			if (lane == 0) {
-				RL_ARGS();
-				atomicAdd(&counters[CNT_COUNT + 21], 1ull);
-				atomicAdd(&counters[CNT_COUNT + 4], (unsigned long long)nAct); atomicAdd(&counters[CNT_COUNT + 5], (unsigned long long)nEmpty);
-				atomicAdd(&counters[CNT_COUNT + 6], (unsigned long long)nQ); atomicAdd(&counters[CNT_COUNT + 7], (unsigned long long)nH);
-				atomicAdd(&counters[CNT_COUNT + 8], (unsigned long long)nPend); atomicAdd(&counters[CNT_COUNT + 9], (unsigned long long)nRes);
-				atomicAdd(&counters[CNT_COUNT + 10], (unsigned long long)(exhausted ? 1 : 0)); atomicAdd(&counters[CNT_COUNT + 11], (unsigned long long)__popcll(Ballot(T.cur != IDLE)));
-			}
-			break;
-		}
-#endif
-		// ---- refill: deal new camera samples to the free slots (wave64 ballot + prefix ranks) ----
-		if (!exhausted) {
-			RL_ARGS();
-			uint32_t pos[K];
-			uint32_t nFree = 0;
-			#pragma unroll
-			for (int p = 0; p < K; ++p) {
-				const bool fr = !stActive[p];
-				const unsigned long long m = Ballot(fr);
-				pos[p] = fr ? nFree + (uint32_t)__popcll(m & laneLt) : 0xffffffffu;
-				if (fr) freeList[pos[p]] = (unsigned char)(p * 64 + (int)lane);
-				nFree += (uint32_t)__popcll(m);
-			}
-			WaveLdsSync();
-			uint32_t filled = 0;
-			for (int round = 0; round < RL_REFILL_ROUNDS && filled < nFree; ++round) {
-				RL_WSTEP(6);   // (level-2 diagnostic build: refill rounds, wave level -- tools/dynamic_mix.py)
-				if (chunkNext >= chunkEnd && !globalDone) {
-					uint32_t base = 0, bend = 0;
-					// (a chunk shared by the workgroup's waves in 64-job batches, as in the leaf-list kernel, was measured here too: 44.5 ms against 43.9)
-					if (!TakeJobs(P, jobCounter, js, P.jobChunk, lane, base, bend)) { globalDone = true; RL_TIMELINE(1); }
-					else { chunkNext = base; chunkEnd = bend; }
-				}
-				const uint32_t avail = chunkEnd - chunkNext;
-				if (avail == 0) { exhausted = true; break; }
-				// How many camera samples to generate this round.  A sample that misses the scene's root box is finished right here and
-				// fills no slot; where most do (a camera outside the model: 90 % in the configs[2] stand-in) asking for exactly as many
-				// samples as there are free slots fills a tenth of them per round.  So the round asks for more -- free slots / the share
-				// that survived lately -- and, if more survive than fit, keeps the first `room` survivors and hands the jobs behind the
-				// last one kept back to the queue (chunkNext only advances past the lanes that were committed: the same jobs come
-				// round again, same pixel, same stream).  Nothing is written or counted for a lane before it is committed.
-				const uint32_t room = nFree - filled;
-				uint32_t want = room;
-				if (surviveQ8 < 230u) want = min(64u, (room * 256u) / max(24u, surviveQ8 + (surviveQ8 >> 3)));   // a little under 1 / survival rate
-				const uint32_t take = min(min(64u, max(room, want)), avail);
-				bool alive = false, quick = false;   // quick: decided by the root test (sample written at commit)
-				V3 o = v3s(0.0f), d = v3s(0.0f);
-				float rayTime = 0.0f;
-				Rng g; g.s.state = 0;
-				uint32_t outIndex = 0;
-				if (lane < take) {
-					const JobPixel j = DecodeJob(P, chunkNext + lane);
-					if (j.valid) {
-						// GenerateCell body, reference render/renderer.cc:232-239
-						const uint32_t sidx = P.sampleBegin + j.sample;
-						g.s = raylib_rng_begin_mixed(P.seedMixed, j.y * P.width + j.x, sidx);
-						float u, v;
-						PixelUV(P, j.x, j.y, sidx, g, u, v);
-						CameraRay(P.camera, u, v, g, o, d, rayTime);
-						outIndex = j.sample * numSlots + j.slot;
-						alive = true;
-						if (P.maxPathLength <= 0) { alive = false; quick = true; }   // renderer.cc:120-123
-						else if (RootMiss(S, o, d, P.rayTMin)) {
-							// cannot hit anything: sky lookup plus (with a sun) one occlusion query that may be decided at the root too
-							const bool sunQuick = !S.hasSun || RootMiss(S, o, -ld3(S.sunDirection), P.rayTMin);
-							if (sunQuick) { alive = false; quick = true; }
-						}
-					}
-				}
-				unsigned long long am = Ballot(alive);
-				uint32_t n = (uint32_t)__popcll(am);
-				uint32_t commit = take;                    // lanes [0, commit) are this round's samples
-				if (n > room) {
-					// the lane of the (room + 1)-th survivor: everything from there on goes back to the queue
-					const unsigned long long over = Ballot(alive && (uint32_t)__popcll(am & laneLt) == room);
-					commit = (uint32_t)__ffsll((long long)over) - 1u;
-					if (lane >= commit) { alive = false; quick = false; }
-					am = Ballot(alive);
-					n = room;
-				}
-				{   // survival rate of the committed samples, 8-bit fixed point, smoothed over the last few rounds
-					const uint32_t rate = commit ? (n * 256u) / commit : 256u;
-					surviveQ8 = (surviveQ8 * 3u + rate + 2u) >> 2;
-				}
-				if (lane < commit && (alive || quick)) c.samples++;
-				if (quick) {
-					if (P.maxPathLength <= 0) samples[outIndex] = make_sample(0.0f, 0.0f, 0.0f);
-					else {
-						c.rays++; c.nodes++;
-						V3 L = MissSky(S, R, d, c);
-						if (S.hasSun) { c.rays++; c.nodes++; L = L + ld3(S.sunIlluminance); }
-						samples[outIndex] = make_sample(L.x, L.y, L.z);
-					}
-				}
-				chunkNext += commit;
-				if (n == 0) continue;
-				if (alive) {
-					// the r-th surviving ray goes to the (filled + r)-th free slot; the fields a traversal fills in later carry
-					// the RNG state and the output index to the slot's home lane
-					const int f = (int)freeList[filled + (uint32_t)__popcll(am & laneLt)];
-					pool[F_OX][f] = o.x; pool[F_OY][f] = o.y; pool[F_OZ][f] = o.z;
-					pool[F_DX][f] = d.x; pool[F_DY][f] = d.y; pool[F_DZ][f] = d.z;
-					if (PRIMS) pool[F_TIME][f] = rayTime;
-					pool[F_TRI][f] = __int_as_float(Q_CLOSEST);
-					pool[F_T][f] = __int_as_float((int)(uint32_t)(g.s.state & 0xffffffffull));
-					pool[F_A][f] = __int_as_float((int)(uint32_t)(g.s.state >> 32));
-					pool[F_B][f] = __int_as_float((int)outIndex);
-				}
-				WaveLdsSync();
-				#pragma unroll
-				for (int p = 0; p < K; ++p) {
-					if (pos[p] >= filled && pos[p] < filled + n) {
-						const int slot = p * 64 + (int)lane;
-						stRng[p] = (unsigned long long)(uint32_t)__float_as_int(pool[F_T][slot]) | ((unsigned long long)(uint32_t)__float_as_int(pool[F_A][slot]) << 32);
-						stOut[p] = (uint32_t)__float_as_int(pool[F_B][slot]);
-						stDepth[p] = 0;
-						stActive[p] = true;
-					}
-				}
-				filled += n;
-			}
-		}
-		bool anyActive = false;
-		#pragma unroll
-		for (int p = 0; p < K; ++p) anyActive = anyActive || stActive[p];
-		if (Ballot(anyActive) == 0ull) {
-			if (exhausted) break;
-			continue;
-		}
-		if (lane == 0) c.trips++;
-		RL_PSTAMP(0);
-
-		// ---- traversal phase: every waiting query of the pool; a lane takes the next slot whenever its ray is finished ----
-		{
-			RL_ARGS();
-			const float tMinC = __builtin_canonicalizef(P.rayTMin);   // known to be canonical: the box tests' max chains start from it without a v_max x, x per step
-#if RL_POOL_NODEPTR_VGPR
-			// the wide nodes' base address in a VGPR pair for the phase: as one of the loop's many uniform values it would be spilled to a VGPR's lanes and
-			// read back (two v_readlane, 4 issue cycles each) at every traversal step
-			DSceneView St = S;
-			if constexpr (WIDE == 3) { }   // (the 8-wide node's rows are loaded from an SGPR base plus a 32-bit offset: NodeStep8)
-			else { const DNode4Q* pn = S.nodes4; asm volatile("" : "+v"(pn)); St.nodes4 = pn; }
-#else
-			const DSceneView& St = S;
-#endif
-			WaveLdsSync();
-			uint32_t nextSlot = 0;
-			uint32_t finished = 0;      // rays completed in this phase (wave-uniform)
-			for (;;) {
-				if (nextSlot < (uint32_t)PP) {
-					const unsigned long long idle = Ballot(T.cur == IDLE);
-					const uint32_t slot = nextSlot + (uint32_t)__popcll(idle & laneLt);
-					if (T.cur == IDLE && slot < (uint32_t)PP) {
-						const int q = __float_as_int(pool[F_TRI][slot]);
-						if (q == Q_CLOSEST || q == Q_SHADOW) {
-							T.o = v3(pool[F_OX][slot], pool[F_OY][slot], pool[F_OZ][slot]);
-							T.anyhit = (q == Q_SHADOW);
-							T.d = T.anyhit ? -ld3(S.sunDirection) : v3(pool[F_DX][slot], pool[F_DY][slot], pool[F_DZ][slot]);
-							T.rayTime = PRIMS ? pool[F_TIME][slot] : 0.0f;
-							T.inv = v3(FastRcp(T.d.x), FastRcp(T.d.y), FastRcp(T.d.z));
-							if (WIDE) T.inv = ClampInv(T.inv);   // only the grid nodes' fused plane arithmetic wants finite reciprocals; Slab() relies on +-inf / NaN
-							T.nx = T.inv.x < 0.0f; T.ny = T.inv.y < 0.0f; T.nz = T.inv.z < 0.0f;
-							T.best.t = INFINITY; T.best.tri = -1; T.best.a = 0.0f; T.best.b = 0.0f;
-							T.cur = 0; T.sp = 0; T.leafI = 0;
-							if constexpr (WIDE == 3) {
-								// the root as a group of one: base 0, imask 1, its bit at the visiting position of slot 0
-								RaySetup8(T);
-								T.gx = 0u; T.gy = (1u << (24u + T.oct)) | 1u; T.tx = T.ty = T.tz = 0u;
-							}
-							mySlot = (int)slot;
-							pool[F_TRI][slot] = __int_as_float(T.anyhit ? Q_PENDING_SHADOW : Q_PENDING);
-							c.rays++;
-						}
-					}
-					nextSlot += (uint32_t)__popcll(idle);
-				}
-				const int nBusy = (int)__popcll(Ballot(T.cur != IDLE));
-				if (nBusy == 0) {
-					if (nextSlot >= (uint32_t)PP) break;
-					continue;
-				}
-				// all queries handed out and only a few long rays left: shade what is there, the stragglers go on next trip
-				const int cutAt = exhausted ? RL_POOL_CUT_EXH : RL_POOL_CUT;
-				if (nextSlot >= (uint32_t)PP && nBusy <= cutAt && finished > 0) break;
-				// one step for the larger (cost-weighted) party, lanes at inner nodes or lanes at leaves, until enough lanes
-				// have finished to make a fetch worth it
-				int nb;
-				do {
-					const bool atNode = (uint32_t)T.cur < (uint32_t)IDLE, atLeaf = T.cur < 0;
-					const int nN = (int)__popcll(Ballot(atNode)), nL = (int)__popcll(Ballot(atLeaf));
-					bool fin = false;
-					const bool nodeTurn = nN * (WIDE == 3 ? RL_POOL_WNODE8 : WIDE ? RL_POOL_WNODE4 : RL_POOL_WNODE) >= nL * (WIDE == 3 ? RL_POOL_WLEAF8 : WIDE ? RL_POOL_WLEAF4 : RL_POOL_WLEAF);
-					if constexpr (WIDE == 3) {
-#if RL_POOL_BOTH8
-						// both parties every turn: a lane at a node takes its node step, a lane at a leaf its triangle step (the wave runs either part only if some lane needs it)
-						(void)nodeTurn;
-						if (atNode) fin = NodeStep8(St, T, tMinC, stk, ovf, c, s_perm, s_top, G8, GMAX8);
-						else if (atLeaf) fin = LeafStep8<PRIMS>(S, T, P.rayTMin, stk, ovf, c, G8);
-#else
-						if (nodeTurn) { if (atNode) fin = NodeStep8(St, T, tMinC, stk, ovf, c, s_perm, s_top, G8, GMAX8); }
-						else { if (atLeaf) fin = LeafStep8<PRIMS>(S, T, P.rayTMin, stk, ovf, c, G8); }
-#endif
-					} else {
-						if (nodeTurn) { if (atNode) fin = WIDE ? NodeStep4<LSTACK, STACK>(St, T, tMinC, stk, ovf, c) : NodeStep<LSTACK, STACK>(S, T, tMinC, stk, ovf, c); }
-						else { if (atLeaf) fin = LeafStep<LSTACK, STACK, PRIMS>(S, T, P.rayTMin, stk, ovf, c); }
-					}
-					if (fin) {
-						const bool hit = T.best.tri >= 0;
-						int q = T.best.tri;
-						if (T.anyhit) q = hit ? Q_OCCLUDED : Q_CLEAR;
-						else if (!hit) q = Q_MISS;
-						pool[F_T][mySlot] = T.best.t; pool[F_TRI][mySlot] = __int_as_float(q);
-						pool[F_A][mySlot] = T.best.a; pool[F_B][mySlot] = T.best.b;
-						T.cur = IDLE;
-					}
-#ifdef RL_POOL_WATCHDOG
-					if (++wdSteps > 400000u) { if (lane == 0) atomicAdd(&counters[CNT_COUNT + 20], 1ull); T.cur = IDLE; wdAbort = true; }
-#endif
-					nb = (int)__popcll(Ballot(T.cur != IDLE));
-					finished += (uint32_t)(nN + nL - nb);   // whoever was busy and is not any more has finished its ray
-				} while (nb > (nextSlot < (uint32_t)PP ? RL_POOL_KEEP : (finished > 0 ? cutAt : 0)));
-			}
-			WaveLdsSync();
-		}
-		RL_PSTAMP(1);
-
-		// ---- shading (TraceScene after the accel->Hit call, reference render/renderer.cc:129-208) ----
-		// (1) the cheap outcomes are finished by the slot's home lane: a miss runs the sky lookup and (with a sun) turns
-		//     into an occlusion query, a returned occlusion query ends the path.  Hits are only LISTED.
-		uint32_t nHit = 0;
-		uint32_t hitIdx[K];
-		{
-		RL_ARGS();
-		#pragma unroll
-		for (int p = 0; p < K; ++p) {
-			const int slot = p * 64 + (int)lane;
-			const int q = __float_as_int(pool[F_TRI][slot]);
-			const bool isHit = stActive[p] && q >= 0;
-			if (stActive[p] && (q == Q_MISS || q == Q_CLEAR || q == Q_OCCLUDED)) {
-				const V3 d = v3(pool[F_DX][slot], pool[F_DY][slot], pool[F_DZ][slot]);
-				bool done = true;
-				V3 L;
-				if (q == Q_MISS) {
-					L = MissSky(S, R, d, c);
-					if (S.hasSun) {
-						// the sky part waits in the direction fields (the sun query brings its own direction)
-						pool[F_DX][slot] = L.x; pool[F_DY][slot] = L.y; pool[F_DZ][slot] = L.z;
-						pool[F_TRI][slot] = __int_as_float(Q_SHADOW);
-						done = false;
-					}
-				} else {
-					L = d;
-					if (q == Q_CLEAR) L = L + ld3(S.sunIlluminance);
-				}
-				if (done) {
-					L = FoldPath(pathStack, P.stackStride, homeBase + (uint32_t)p * RL_BLOCK, stDepth[p], L);
-					samples[stOut[p]] = make_sample(L.x, L.y, L.z);
-					stActive[p] = false;
-					pool[F_TRI][slot] = __int_as_float(Q_EMPTY);
-				}
-			}
-			const unsigned long long hm = Ballot(isHit);
-			hitIdx[p] = isHit ? nHit + (uint32_t)__popcll(hm & laneLt) : 0xffffffffu;
-			if (isHit) freeList[hitIdx[p]] = (unsigned char)slot;
-			nHit += (uint32_t)__popcll(hm);
-		}
-		}
-		WaveLdsSync();
-		// (2) hits are shaded 64 at a time by whichever lane: the expensive material code always runs with a full wave.
-		//     A remainder below 64 waits in its slots for the next trip's hits (until the job queue is empty).
-		//     The path registers come from the home lane by ds_bpermute and return through the slot's hit fields.
-		uint32_t shadedEnd = 0;
-		for (;;) {
-			RL_ARGS();
-			if (shadedEnd >= nHit) break;
-			if (nHit - shadedEnd < (uint32_t)RL_POOL_SHADE_MIN && !exhausted) break;   // once the job queue is empty no refill will top the list up: waiting only stretches the tail
-#ifdef RL_POOL_WATCHDOG
-			if (++wdSteps > 400000u) { if (lane == 0) atomicAdd(&counters[CNT_COUNT + 20], 1ull); wdAbort = true; break; }
-#endif
-			RL_WSTEP(7);   // (level-2 diagnostic build: rounds of hit shading, wave level)
-			const uint32_t idx = shadedEnd + lane;
-			const bool on = idx < nHit;
-			const int slot = on ? (int)freeList[idx] : 0;
-			const int h = slot & 63, pp = slot >> 6;
-			uint32_t rngLo = 0, rngHi = 0, outIndex = 0; int depth = 0;
-			#pragma unroll
-			for (int k = 0; k < K; ++k) {
-				const uint32_t a0 = (uint32_t)__shfl((int)(uint32_t)(stRng[k] & 0xffffffffull), h);
-				const uint32_t a1 = (uint32_t)__shfl((int)(uint32_t)(stRng[k] >> 32), h);
-				const uint32_t a2 = (uint32_t)__shfl((int)stOut[k], h);
-				const int a3 = __shfl(stDepth[k], h);
-				if (pp == k) { rngLo = a0; rngHi = a1; outIndex = a2; depth = a3; }
-			}
-			if (on) {
-				const V3 o = v3(pool[F_OX][slot], pool[F_OY][slot], pool[F_OZ][slot]);
-				const V3 d = v3(pool[F_DX][slot], pool[F_DY][slot], pool[F_DZ][slot]);
-				HitRec hr; hr.t = pool[F_T][slot]; hr.tri = __float_as_int(pool[F_TRI][slot]); hr.a = pool[F_A][slot]; hr.b = pool[F_B][slot];
-				const uint32_t home = blockIdx.x * (RL_BLOCK * K) + (uint32_t)pp * RL_BLOCK + wave * 64u + (uint32_t)h;
-				Rng g; g.s.state = (unsigned long long)rngLo | ((unsigned long long)rngHi << 32);
-				Surf sf;
-				const Mat m = LoadMat(S, BuildSurface<PRIMS>(S, o, d, hr, sf, true, c));
-				V3 refl = v3s(0.0f), outD = v3s(0.0f);
-				float pdf = 0.0f, sp = 0.0f;
-				const bool scattered = Scatter(S, m, d, sf, g, c, refl, outD, pdf, sp);
-				const V3 E = Emitted(S, m, sf, c);
-				bool done = false;
-				V3 L = v3s(0.0f);
-				if (scattered && pdf > 0.0f) {
-					float4* rec = (float4*)pathStack + ((size_t)depth * P.stackStride + home) * 2u;
-					rec[0] = make_float4(refl.x, refl.y, refl.z, sp);
-					rec[1] = make_float4(pdf, E.x, E.y, E.z);
-					depth++;
-					if (depth >= P.maxPathLength) done = true;   // the next TraceScene returns 0 at once (renderer.cc:120-123)
-					else {
-						pool[F_OX][slot] = sf.p.x; pool[F_OY][slot] = sf.p.y; pool[F_OZ][slot] = sf.p.z;
-						pool[F_DX][slot] = outD.x; pool[F_DY][slot] = outD.y; pool[F_DZ][slot] = outD.z;
-						pool[F_TRI][slot] = __int_as_float(Q_CLOSEST);
-					}
-				} else {
-					L = v3s(0.0f) + E;                            // radiance(0) += Emitted, renderer.cc:137,151
-					done = true;
-				}
-				if (done) {
-					L = FoldPath(pathStack, P.stackStride, home, depth, L);
-					samples[outIndex] = make_sample(L.x, L.y, L.z);
-					pool[F_TRI][slot] = __int_as_float(Q_EMPTY);
-				}
-				// back to the home lane: RNG state and depth (negative = the path has ended)
-				pool[F_T][slot] = __int_as_float((int)(uint32_t)(g.s.state & 0xffffffffull));
-				pool[F_A][slot] = __int_as_float((int)(uint32_t)(g.s.state >> 32));
-				pool[F_B][slot] = __int_as_float(done ? -1 : depth);
-			}
-			shadedEnd += 64u;
-		}
-		WaveLdsSync();
-		// (3) the home lanes take their registers back
-		#pragma unroll
-		for (int p = 0; p < K; ++p) {
-			if (hitIdx[p] < shadedEnd) {
-				const int slot = p * 64 + (int)lane;
-				stRng[p] = (unsigned long long)(uint32_t)__float_as_int(pool[F_T][slot]) | ((unsigned long long)(uint32_t)__float_as_int(pool[F_A][slot]) << 32);
-				const int dd = __float_as_int(pool[F_B][slot]);
-				if (dd < 0) stActive[p] = false; else stDepth[p] = dd;
-			}
-		}
-		RL_PSTAMP(2);
-	}
-
-	RL_ARGS();
-#ifdef RL_DIAG_STAMPS
-	if (lane == 0) for (int k = 0; k < 4; ++k) { atomicAdd(&counters[CNT_COUNT + k], stampAcc[k]); atomicAdd(&counters[CNT_COUNT + 12 + k], c.tAcc[k]); }
-#endif
-	RL_TIMELINE(2);
-	uint32_t vals[CNT_COUNT] = { c.rays, c.nodes, c.tris, c.shaded, c.texels, c.samples, c.trips };
-	for (int k = 0; k < CNT_COUNT; ++k) {
-		unsigned long long v = vals[k];
-		for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-		if (lane == 0 && v) atomicAdd(&counters[k], v);
-	}
-}
-#endif
+#define RL_VIEWS_TWIN 0
+#include "rl_k_trace_pool.inl"
+#undef RL_VIEWS_TWIN
+#define RL_VIEWS_TWIN 1
+#include "rl_k_trace_pool.inl"
+#undef RL_VIEWS_TWIN
 // The instances the runtime selects from (rl_runtime.inl KernelFor): defined in rl_render_pool.hip's translation unit, referenced from this one.
 #define RL_POOL_INSTANCES(X) \
 	X(16, false, 2, 16, 0) X(16, false, 3, 16, 0) X(16, false, 4, 16, 0) X(32, false, 2, 32, 0) X(32, false, 3, 32, 0) X(32, false, 4, 32, 0) \
 	X(32, false, 2, 4, 0) X(32, false, 2, RL_POOL_SHORT_LSTACK, 0) \
 	X(32, false, 2, 32, 1) X(64, false, 2, 32, 1) X(32, false, 2, RL_POOL_SHORT_LSTACK, 1) X(64, false, 2, RL_POOL_SHORT_LSTACK, 1) \
 	X(2 * RL_POOL8_MAXLEVELS, false, 2, RL_POOL8_LSTACK, 3)
+// (the twins first: the one-view instances keep their places at the end of the unit's code)
+#ifdef RL_TU_POOL
+#define RL_POOL_X(a, b, c, d, e) template __global__ void k_trace_pool_views<a, b, c, d, e>(const DRenderParams, const DSceneView, const SkyRot, SampleRGB* __restrict__, float* __restrict__, unsigned long long* __restrict__, unsigned int* __restrict__, const DViews);
+#else
+#define RL_POOL_X(a, b, c, d, e) extern template __global__ void k_trace_pool_views<a, b, c, d, e>(const DRenderParams, const DSceneView, const SkyRot, SampleRGB* __restrict__, float* __restrict__, unsigned long long* __restrict__, unsigned int* __restrict__, const DViews);
+#endif
+RL_POOL_INSTANCES(RL_POOL_X)
+#undef RL_POOL_X
 #ifdef RL_TU_POOL
 #define RL_POOL_X(a, b, c, d, e) template __global__ void k_trace_pool<a, b, c, d, e>(const DRenderParams, const DSceneView, const SkyRot, SampleRGB* __restrict__, float* __restrict__, unsigned long long* __restrict__, unsigned int* __restrict__);
 #else
@@ -2894,36 +2122,16 @@ __device__ __forceinline__ float4 SumSlotBatch(const DRenderParams& P, const DSc
 	return a;
 }
 
-// Sequential per-pixel sum of this batch's samples, then (last batch) the mean.
-// reference render/renderer.cc:244-248 + core/vec3.h:214-220 (operator/= multiplies by 1/SPP)
-__global__ void __launch_bounds__(RL_BLOCK)
-k_resolve(const DRenderParams P, const DSceneView S, const SkyRot R, const SampleRGB* __restrict__ samples, float4* __restrict__ accum, float4* __restrict__ out, int firstBatch, int lastBatch)
-{
-	RL_MATH_PROLOGUE();
-	const uint32_t numSlots = P.numLocalCells * 64u;
-	const uint32_t slot = blockIdx.x * RL_BLOCK + threadIdx.x;
-	if (slot >= numSlots) return;
-	const uint32_t p = slot & 63u, cellLocal = slot >> 6;
-	const uint32_t cell = P.cellFirst + cellLocal * P.cellStride;
-	const uint32_t x = (cell % P.cellsX) * 8u + (p & 7u), y = (cell / P.cellsX) * 8u + (p >> 3);
-	const bool valid = x < P.width && y < P.height;
-	float4 a = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-	if (valid) {
-		if (!firstBatch) a = accum[slot];
-		a = SumSlotBatch(P, S, R, samples, numSlots, slot, cellLocal, x, y, a, [](float, float, float) __attribute__((always_inline)) {});
-		if (lastBatch) {
-			const float k = rtm::rcp1_((float)P.spp);
-			a.x *= k; a.y *= k; a.z *= k; a.w = 1.0f;
-		} else {
-			accum[slot] = a;
-		}
-	}
-	if (lastBatch) {
-		if (P.rowMajorOutput) { if (valid) out[(size_t)y * P.width + x] = a; }
-		else out[slot] = valid ? a : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-	}
-}
+#ifndef RL_TU_VIEWS
+#define RL_VIEWS_TWIN 0
+#include "rl_k_resolve.inl"
+#undef RL_VIEWS_TWIN
+#endif
+#define RL_VIEWS_TWIN 1
+#include "rl_k_resolve.inl"
+#undef RL_VIEWS_TWIN
 
+#ifndef RL_TU_VIEWS   // (the views unit: the twins alone)
 // ---- progressive rendering (rl_runtime.inl ProgressiveSession; include/raylib_amd.h RaylibAMD_BeginProgressive) ----
 // What a session keeps on the device, cell-major (slot = cell * 64 + pixel of the cell): the running colour sum in sample order, the moments of y, and
 // per cell its samples so far and whether it has stopped.
@@ -3039,79 +2247,21 @@ k_progressive_compact(uint32_t* __restrict__ live, uint32_t* __restrict__ trace,
 	}
 }
 
-// Debug render modes (reference render/renderer.cc:62-111, :258-268): one unjittered sample.
-// Modes 3 and 6 read an uninitialised tangent frame in the reference; here it is built.
-template <int STACK, bool PRIMS>
-__global__ void __launch_bounds__(RL_BLOCK)
-k_aov(const DRenderParams P, const DSceneView S, float4* __restrict__ out, unsigned long long* __restrict__ counters)
-{
-	RL_TEX_PROLOGUE(S);
-	RL_MATH_PROLOGUE();
-	__shared__ int s_stack[STACK * RL_BLOCK];
-	int* stk = s_stack + threadIdx.x;
-	const uint32_t numSlots = P.numLocalCells * 64u;
-	const uint32_t slot = blockIdx.x * RL_BLOCK + threadIdx.x;
-	Counters c; c.rays = c.nodes = c.tris = c.shaded = c.texels = c.samples = c.trips = 0; RL_DIAG_BIND(c);
-	bool valid = false;
-	uint32_t x = 0, y = 0;
-	if (slot < numSlots) {
-		const uint32_t p = slot & 63u, cellLocal = slot >> 6;
-		const uint32_t cell = P.cellFirst + cellLocal * P.cellStride;
-		x = (cell % P.cellsX) * 8u + (p & 7u); y = (cell / P.cellsX) * 8u + (p >> 3);
-		valid = x < P.width && y < P.height;
-	}
-	V3 debugValue = v3s(0.0f);
-	if (valid) {
-		Rng g; g.s = raylib_rng_begin(P.seed, y * P.width + x, 0);
-		V3 o, d; float rayTime;
-		CameraRay(P.camera, (float)x / (float)P.width, (float)y / (float)P.height, g, o, d, rayTime);
-		c.samples++;
-		HitRec h;
-		if (Traverse<STACK, false, PRIMS>(S, o, d, rayTime, P.rayTMin, h, stk, c)) {
-			Surf s;
-			const Mat m = LoadMat(S, BuildSurface<PRIMS>(S, o, d, h, s, true, c));
-			const uint32_t mode = P.renderMode;
-			if (mode == RAYLIB_RENDERMODE_Albedo) {
-				debugValue = GetAlbedo(S, m, s.U, s.V, c);
-				if (IsMirrorLike(S, m, s.U, s.V, c)) {
-					HitRec h2;
-					const V3 d2 = reflect(d, s.n);
-					if (Traverse<STACK, false, PRIMS>(S, s.p, d2, rayTime, P.rayTMin, h2, stk, c)) {
-						Surf s2;
-						const Mat m2 = LoadMat(S, BuildSurface<PRIMS>(S, s.p, d2, h2, s2, false, c));
-						debugValue = GetAlbedo(S, m2, s2.U, s2.V, c);
-					}
-				}
-			} else if (mode == RAYLIB_RENDERMODE_SurfaceNormal) {
-				debugValue = v3s(0.5f) + 0.5f * s.n;
-			} else if (mode == RAYLIB_RENDERMODE_MicrosurfaceNormal) {
-				V3 N = GetMicrosurfaceNormal(S, m, s, c);
-				N = LocalToWorld(s, N);
-				debugValue = 0.5f * N + 0.5f;
-			} else if (mode == RAYLIB_RENDERMODE_Texcoord) {
-				debugValue = v3(s.U, s.V, 0.0f);
-			} else if (mode == RAYLIB_RENDERMODE_Emission) {
-				debugValue = Emitted(S, m, s, c);
-			} else if (mode == RAYLIB_RENDERMODE_Reflectance) {
-				V3 refl = v3(1.0f, 0.75f, 0.8f), outD; float pdf, sp;
-				Scatter(S, m, d, s, g, c, refl, outD, pdf, sp);
-				debugValue = refl;
-			}
-		}
-	}
-	if (slot < numSlots) {
-		const float4 px = make_float4(debugValue.x, debugValue.y, debugValue.z, 1.0f);
-		if (P.rowMajorOutput) { if (valid) out[(size_t)y * P.width + x] = px; }
-		else out[slot] = valid ? px : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-	}
-	const uint32_t lane = threadIdx.x & 63u;
-	uint32_t vals[CNT_COUNT] = { c.rays, c.nodes, c.tris, c.shaded, c.texels, c.samples, c.trips };
-	for (int k = 0; k < CNT_COUNT; ++k) {
-		unsigned long long v = vals[k];
-		for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-		if (lane == 0 && v) atomicAdd(&counters[k], v);
-	}
-}
+#endif   // RL_TU_VIEWS
+#define RL_VIEWS_TWIN 0
+#include "rl_k_aov.inl"
+#undef RL_VIEWS_TWIN
+#define RL_VIEWS_TWIN 1
+#include "rl_k_aov.inl"
+#undef RL_VIEWS_TWIN
+#ifdef RL_TU_VIEWS
+#define RL_AOV_X(a, b) template __global__ void k_aov_views<a, b>(const DRenderParams, const DSceneView, float4* __restrict__, unsigned long long* __restrict__, const DViews);
+#else
+#define RL_AOV_X(a, b) extern template __global__ void k_aov_views<a, b>(const DRenderParams, const DSceneView, float4* __restrict__, unsigned long long* __restrict__, const DViews);
+#endif
+RL_AOV_X(16, false) RL_AOV_X(32, false) RL_AOV_X(32, true) RL_AOV_X(64, false) RL_AOV_X(64, true)
+#undef RL_AOV_X
+#ifndef RL_TU_VIEWS
 
 struct DHitOut { int32_t hit; float t; float p[3]; float n[3]; float paramU, paramV; int32_t material; };
 
@@ -3364,10 +2514,11 @@ k_scatter_cells(const float4* __restrict__ gather, float4* __restrict__ out, uin
 	out[i] = gather[plan.offset[rank] + local * 64u + ((y & 7u) << 3) + (x & 7u)];
 }
 
+#endif   // RL_TU_VIEWS
 #endif   // RL_TU_POOL
 
 } // namespace rl
 
-#ifndef RL_TU_POOL
+#if !defined(RL_TU_POOL) && !defined(RL_TU_VIEWS)
 #include "rl_runtime.inl"
 #endif

@@ -579,6 +579,33 @@ static AovKernel AovKernelFor(const TracePlan& p)
 	if (p.stack == 32) return p.prims ? k_aov<32, true> : k_aov<32, false>;
 	return p.prims ? k_aov<64, true> : k_aov<64, false>;
 }
+// ... and their views twins (RaylibAMD_RenderViews): one for every instance above, so that a batch of views is never a loop of one-view launches
+typedef void (*TraceViewsKernel)(const DRenderParams, const DSceneView, const SkyRot, SampleRGB*, float*, unsigned long long*, unsigned int*, const DViews);
+typedef void (*AovViewsKernel)(const DRenderParams, const DSceneView, float4*, unsigned long long*, const DViews);
+template <int STACK, bool PRIMS>
+static TraceViewsKernel TraceViewsFor(bool floatBoxes) { return floatBoxes ? (TraceViewsKernel)k_trace_views<STACK, PRIMS, true> : (TraceViewsKernel)k_trace_views<STACK, PRIMS, false>; }
+static TraceViewsKernel ViewsKernelFor(const TracePlan& p)
+{
+	if (p.poolK > 0) {
+		const int wide = p.tree == TREE_WIDE8 ? 3 : p.tree == TREE_GRID4 ? 1 : 0;
+#define RL_POOL_PICK(a, b, c, d, e) if (p.stack == a && p.prims == b && p.poolK == c && p.lstack == d && wide == e) return (TraceViewsKernel)k_trace_pool_views<a, b, c, d, e>;
+		RL_POOL_INSTANCES(RL_POOL_PICK)
+#undef RL_POOL_PICK
+		return nullptr;
+	}
+	if (p.lds == 2) return p.plain ? (TraceViewsKernel)k_trace_views<16, false, true, 2, true> : (TraceViewsKernel)k_trace_views<16, false, true, 2>;
+	if (p.lds == 1) return (TraceViewsKernel)k_trace_views<16, false, true, 1>;
+	const bool full = p.tree == TREE_BOX4;
+	if (p.stack == 16) return TraceViewsFor<16, false>(full);
+	if (p.stack == 32) return p.prims ? TraceViewsFor<32, true>(full) : TraceViewsFor<32, false>(full);
+	return p.prims ? TraceViewsFor<64, true>(full) : TraceViewsFor<64, false>(full);
+}
+static AovViewsKernel AovViewsKernelFor(const TracePlan& p)
+{
+	if (p.stack == 16) return k_aov_views<16, false>;
+	if (p.stack == 32) return p.prims ? k_aov_views<32, true> : k_aov_views<32, false>;
+	return p.prims ? k_aov_views<64, true> : k_aov_views<64, false>;
+}
 static std::atomic<int32_t> g_lastTracePlain{0};   // RaylibAMD_LastTracePlain
 
 // What EnqueueRender leaves for FinishRender: everything is queued on the rank's stream, nothing has been waited for.
@@ -1096,6 +1123,170 @@ bool DeviceRender(Scene& sc, const RenderRequest& req, RaylibAMDStats& stats)
 }
 
 int32_t DeviceLastTracePlain() { return g_lastTracePlain.load(std::memory_order_relaxed); }
+
+// ---- several views of one scene (RaylibAMD_RenderViews): rank 0's device and stream, whatever RAYLIB_NUM_GPUS says, as a progressive session ----
+// The batch's output is ONE buffer, view-major (view v's row-major frame at v * W * H); the images get theirs by device-to-device copies behind the
+// resolve.  The cull's list and flags and the camera table go through buffers of their own: the one-view renders' cached lists (RankCtx::cullKey) are
+// never those of a batch, nor the reverse.
+namespace {
+struct ViewsBuffers {
+	unsigned char* host = nullptr; size_t hostBytes = 0;   // pinned staging: the camera table, the list of listed cells, the flags
+	unsigned char* dev = nullptr; size_t devBytes = 0;
+	float4* out = nullptr; size_t outBytes = 0;             // the library's own output (RaylibAMD_RenderViewsDevice with no buffer of the caller's, and the images')
+};
+ViewsBuffers g_views;
+}
+
+bool DeviceRenderViews(Scene& sc, const RenderRequest& req, const DCamera* cameras, uint32_t count, void* outDevice, void* const* imagePixels, RaylibAMDStats& stats)
+{
+	std::lock_guard<std::mutex> lk(g_rt.lock);
+	const auto t0 = std::chrono::steady_clock::now();
+	if (!EnsureRuntime() || count == 0 || count > RL_MAX_VIEWS) return false;
+	RankCtx& R = Rank0();
+	HIP_OK(hipSetDevice(R.device));
+	if (!UploadScene(sc) || !SyncSky(sc)) return false;
+	(void)DrainLocked();            // rank 0's slot-0 events, counter block and work buffers
+	g_deferredUnreported = false;   // (the numbers the caller reads next are this batch's)
+	DeviceScene* DS = sc.device;
+	DeviceSceneCopy* D = DS->copy[(size_t)R.devSlot];
+	const RendererSettings& st = req.settings;
+	const RenderKnobs knobs = ReadRenderKnobs();
+	const TracePlan plan = PlanTrace(sc, st, D->view.sky != nullptr, knobs);
+	if (!plan.ok) return false;
+	const uint32_t W = st.viewportWidth, H = st.viewportHeight;
+	const uint32_t cellsX = (W + 7) / 8, cellsY = (H + 7) / 8, cellsPerView = cellsX * cellsY, numCells = cellsPerView * count;
+	const uint32_t numSlots = numCells * 64u;
+	const uint32_t SPP = (uint32_t)(st.samplesPerPixel > 1 ? st.samplesPerPixel : 1);
+	const bool pathTrace = (st.renderMode == RAYLIB_RENDERMODE_Default);
+	const size_t viewBytes = (size_t)W * H * sizeof(float4);
+
+	DRenderParams P; memset(&P, 0, sizeof(P));
+	P.width = W; P.height = H; P.spp = SPP; P.maxPathLength = st.maxPathLength; P.rayTMin = st.rayTMin;
+	P.invWidth = 1.0f / (float)W; P.invHeight = 1.0f / (float)H;
+	P.renderMode = st.renderMode; P.seed = req.seed; P.cellsX = cellsX; P.cellsY = cellsY;
+	P.cellFirst = 0; P.cellStride = 1; P.numLocalCells = numCells;
+	P.rowMajorOutput = 0; P.camera = cameras[0];   // (the twins read every view's camera from the table)
+	P.seedMixed = raylib_rng_mix64(req.seed);
+	P.magicCellsX = cellsX > 1 ? (uint32_t)(0x100000000ull / cellsX) : 0xFFFFFFFFu;
+
+	// the kernel, its occupancy and the batch's job list: all of it decided before anything is enqueued
+	DSceneView traceView = D->view;
+	TraceViewsKernel traceKernel = nullptr;
+	ViewsPlan VP;
+	int blocksPerCU = 0;
+	if (pathTrace) {
+		traceKernel = ViewsKernelFor(plan);
+		if (!traceKernel) { Log("RaylibAMD_RenderViews: no megakernel instance for STACK %d, K %d, stack in LDS %d", plan.stack, plan.poolK, plan.lstack); return false; }
+		if (!EnsureWideTree(D, sc, plan.tree)) return false;
+		traceView = D->view;
+		if (!plan.keepNodes4) traceView.nodes4 = nullptr;
+		if (!plan.keepNodes4f) traceView.nodes4f = nullptr;
+		auto it = R.occupancy.find((const void*)traceKernel);
+		if (it == R.occupancy.end()) {
+			HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, traceKernel, RL_BLOCK, 0));
+			R.occupancy[(const void*)traceKernel] = blocksPerCU;
+		} else blocksPerCU = it->second;
+		CullScene cs;
+		for (int k = 0; k < 3; ++k) { cs.boundsMin[k] = DS->boundsMin[k]; cs.boundsMax[k] = DS->boundsMax[k]; cs.sunDirection[k] = traceView.sunDirection[k]; cs.sunIlluminance[k] = traceView.sunIlluminance[k]; }
+		cs.boundsValid = DS->boundsValid; cs.prims = plan.prims; cs.hasSky = traceView.sky != nullptr; cs.hasSun = traceView.hasSun != 0;
+		VP = PlanViews(cs, st, cameras, count, plan, R.numCUs, blocksPerCU, knobs);
+		if (!VP.ok) { Log("RaylibAMD_RenderViews: job count overflow"); return false; }
+	}
+	// the camera table, then (culled views) the list of listed cells and the flags, staged in pinned memory and copied in one go
+	const size_t camBytes = (size_t)count * sizeof(DCamera), listAt = (camBytes + 255) & ~(size_t)255;
+	const bool culled = pathTrace && VP.numActive < numCells;
+	const size_t flagsAt = listAt + (culled ? (size_t)numCells * sizeof(uint32_t) : 0), stageBytes = flagsAt + (culled ? numCells : 0);
+	if (g_views.hostBytes < stageBytes) {
+		if (g_views.host) (void)hipHostFree(g_views.host);
+		g_views.host = nullptr; g_views.hostBytes = 0;
+		HIP_OK(hipHostMalloc((void**)&g_views.host, stageBytes, hipHostMallocDefault));
+		g_views.hostBytes = stageBytes;
+	}
+	if (!Grow(g_views.dev, g_views.devBytes, stageBytes)) return false;
+	memcpy(g_views.host, cameras, camBytes);
+	if (culled) {
+		memcpy(g_views.host + listAt, VP.active.data(), VP.active.size() * sizeof(uint32_t));
+		memcpy(g_views.host + flagsAt, VP.empty.data(), numCells);
+	}
+	float4* out = (float4*)outDevice;
+	if (!out) { if (!Grow(g_views.out, g_views.outBytes, viewBytes * count)) return false; out = g_views.out; }
+	DViews V;
+	V.cameras = (const DCamera*)g_views.dev; V.cellsPerView = cellsPerView;
+	V.magicCellsPerView = cellsPerView > 1 ? (uint32_t)(0x100000000ull / cellsPerView) : 0xFFFFFFFFu;
+
+	PendingRender pend;
+	pend.ctx = &R; pend.pathTrace = pathTrace; pend.slot = 0; pend.cnt = R.cntHost[0];
+	pend.out = out; pend.outBytes = viewBytes * count;
+	HIP_OK(hipMemcpyAsync(g_views.dev, g_views.host, stageBytes, hipMemcpyHostToDevice, R.stream));
+	HIP_OK(hipMemsetAsync(R.counters, 0, (CNT_COUNT + 24 + RL_TIMELINE_SLOTS) * sizeof(unsigned long long), R.stream));
+	HIP_OK(hipEventRecord(R.ev[0][0], R.stream));
+	bool ok = true;
+	if (!pathTrace) {
+		hipLaunchKernelGGL(AovViewsKernelFor(plan), dim3((numSlots + RL_BLOCK - 1) / RL_BLOCK), dim3(RL_BLOCK), 0, R.stream, P, D->view, out, R.counters, V);
+		HIP_TRY(hipGetLastError());
+		pend.listedCells = numCells;
+	} else {
+		g_lastTracePlain.store(plan.plain ? 1 : 0, std::memory_order_relaxed);
+		pend.pathsPerWave = plan.pathsPerWave; pend.treeWidth = plan.treeWidth; pend.nodeBytes = plan.nodeBytes;
+		const uint32_t numActive = VP.numActive;
+		if (culled) {
+			P.activeCells = (const uint32_t*)(g_views.dev + listAt); P.cellEmpty = (const uint8_t*)(g_views.dev + flagsAt); P.numActiveCells = numActive;
+			P.emptyL[0] = VP.emptyL[0]; P.emptyL[1] = VP.emptyL[1]; P.emptyL[2] = VP.emptyL[2];
+			P.emptySky = traceView.sky ? 1u : 0u;
+			pend.culledSamples = VP.emptyPixels * (uint64_t)SPP; pend.culledRaysPerSample = VP.raysPerSample; pend.culledSkyTexels = traceView.sky ? 1u : 0u;
+		}
+		pend.culledCells = numCells - numActive; pend.listedCells = numActive;
+		const uint32_t batch = VP.launch.batch;
+		if (!Grow(R.samples, R.samplesBytes, (size_t)numSlots * sizeof(SampleRGB) * std::min(batch, SPP))) ok = false;
+		if (ok && batch < SPP && !Grow(R.accum, R.accumBytes, (size_t)numSlots * sizeof(float4))) ok = false;
+		const int depthSlots = st.maxPathLength > 1 ? st.maxPathLength : 1;
+		for (uint32_t s0 = 0; ok && s0 < SPP; s0 += batch) {
+			const LaunchPlan L = PlanLaunch(numCells, numActive, SPP, s0, R.numCUs, blocksPerCU, plan, VP.knobs);
+			const uint32_t cnt = L.sampleCount;
+			P.sampleBegin = s0; P.sampleCount = cnt;
+			P.magicSamples = cnt > 1 ? (uint32_t)(0x100000000ull / cnt) : 0xFFFFFFFFu;
+			P.numJobs = (uint32_t)L.jobs;
+			P.stackStride = L.stackStride; P.jobChunk = L.jobChunk;
+			P.numHeads = L.heads; P.jobsPerHead = L.jobsPerHead; P.guideShift = L.guideShift;
+			if (!Grow(R.pathStack, R.pathStackBytes, (size_t)depthSlots * 8 * P.stackStride * sizeof(float))) { ok = false; break; }
+			pend.jobHeads = L.heads;
+			HIP_TRY(hipMemsetAsync(R.jobCounter, 0, RL_MAX_HEADS * RL_HEAD_STRIDE * sizeof(unsigned int), R.stream));
+			HIP_TRY(hipEventRecord(R.ev[0][2], R.stream));
+			if (L.jobs > 0) {
+				hipLaunchKernelGGL(traceKernel, dim3(L.blocks), dim3(RL_BLOCK), 0, R.stream,
+				                   P, traceView, DS->skyRot, R.samples, R.pathStack, R.counters, R.jobCounter, V);
+				HIP_TRY(hipGetLastError());
+			}
+			HIP_TRY(hipEventRecord(R.ev[0][3], R.stream));
+			hipLaunchKernelGGL(k_resolve_views, dim3((numSlots + RL_BLOCK - 1) / RL_BLOCK), dim3(RL_BLOCK), 0, R.stream,
+			                   P, traceView, DS->skyRot, R.samples, R.accum, out, (int)(s0 == 0), (int)(s0 + cnt >= SPP), V);
+			HIP_TRY(hipGetLastError());
+			++pend.launches;
+			if (s0 + cnt < SPP) {
+				HIP_TRY(hipEventSynchronize(R.ev[0][3]));
+				float ms = 0.0f;
+				HIP_TRY(hipEventElapsedTime(&ms, R.ev[0][2], R.ev[0][3]));
+				pend.traceMs += ms;
+			} else pend.lastBatchPending = true;
+		}
+	}
+	if (!ok) { (void)hipStreamSynchronize(R.stream); return false; }
+	HIP_OK(hipEventRecord(R.ev[0][1], R.stream));
+	HIP_OK(hipMemcpyAsync(R.cntHost[0], R.counters, (CNT_COUNT + 24) * sizeof(unsigned long long), hipMemcpyDeviceToHost, R.stream));
+	HIP_OK(hipEventRecord(R.ev[0][7], R.stream));
+	pend.enqueuedToEnd = true;
+	if (imagePixels)
+		for (uint32_t v = 0; v < count; ++v) HIP_TRY(hipMemcpyAsync(imagePixels[v], (const char*)out + viewBytes * v, viewBytes, hipMemcpyDeviceToDevice, R.stream));
+	uint64_t px = 0;
+	for (uint32_t c = 0; c < cellsPerView; ++c) { const uint32_t cx = c % cellsX, cy = c / cellsX; px += (uint64_t)std::min(8u, W - cx * 8) * std::min(8u, H - cy * 8); }
+	pend.pixels = px * count;
+	ok = FinishRender(pend, stats) && ok;
+	HIP_TRY(hipStreamSynchronize(R.stream));   // (the images' copies)
+	stats.ranks = 1; stats.devices = 1;
+	stats.numNodes = (uint32_t)sc.bvh.nodes.size(); stats.numTriangles = (uint32_t)sc.triangles.size(); stats.bvhDepth = sc.bvh.depth;
+	stats.wallMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	return ok;
+}
 
 // Waits for whatever Raylib_Render left in flight.  True with `out` filled when that completed the LAST render call's numbers (counters, times)
 // that the call itself could not report yet.

@@ -172,7 +172,12 @@ _EXPORTS = {
     "RaylibAMD_EndProgressive": (C.c_int32, [C.c_size_t]),
     "RaylibAMD_ProgressiveDecideHost": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                                     C.POINTER(ProgressiveParams), C.POINTER(C.c_uint8)]),
+    "RaylibAMD_RenderViews": (C.c_int32, [C.POINTER(RendererSettings), C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)]),
+    "RaylibAMD_RenderViewsDevice": (C.c_int32, [C.POINTER(RendererSettings), C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p]),
+    "RaylibAMD_PlanViews": (C.c_int32, [C.c_void_p, C.POINTER(RendererSettings), C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                        C.POINTER(RenderPlan), C.POINTER(C.c_uint8)]),
 }
+MAX_VIEWS = 64   # RAYLIB_AMD_MAX_VIEWS
 RAYLIB_H_EXPORTS = [k for k in _EXPORTS if k.startswith("Raylib_")]
 RAYLIB_AMD_H_EXPORTS = [k for k in _EXPORTS if k.startswith("RaylibAMD_")]
 
@@ -195,6 +200,22 @@ def _fp(a):
 
 def _f3(v):
     return (C.c_float * 3)(*[float(x) for x in v])
+
+
+def create_camera(lib, origin, look_at, fov, aspect, aperture=0.0, focal=1.0, shutter=(0.0, 0.0)):
+    """A camera handle (Raylib_CreateCamera and its setters); the caller destroys it with Raylib_DestroyCamera."""
+    cam = lib.Raylib_CreateCamera()
+    lib.Raylib_CameraSetPosition(cam, *[float(x) for x in origin])
+    lib.Raylib_CameraSetLookAt(cam, *[float(x) for x in look_at])
+    lib.Raylib_CameraSetPerspective(cam, float(fov), float(aspect))
+    lib.Raylib_CameraSetLens(cam, float(aperture), float(focal))
+    lib.Raylib_CameraSetMotion(cam, float(shutter[0]), float(shutter[1]))
+    return cam
+
+
+def handle_array(handles):
+    """A C array of handles (CameraHandle / ImageHandle) for RaylibAMD_RenderViews and RaylibAMD_PlanViews."""
+    return (C.c_void_p * max(1, len(handles)))(*[h or None for h in handles])
 
 
 def create_material(lib, mat):
@@ -349,6 +370,23 @@ class SceneSession:
         out = np.zeros((h, w, 4), np.float32)
         lib.RaylibAMD_DumpImageRGBA(img, _fp(out))
         lib.Raylib_DestroyImage(img)
+        return out
+
+    def render_views(self, cameras, w, h, spp, max_path=5, tmin=1e-4, mode=RENDERMODE_DEFAULT):
+        """RaylibAMD_RenderViews of camera handles (create_camera) into fresh images; returns (N, H, W, 4) float32 RGBA, view i as
+        Raylib_Render of cameras[i] would give it."""
+        lib = self.lib
+        st = self.settings(w, h, spp, max_path, tmin, mode)
+        imgs = [lib.Raylib_CreateImage(w, h) for _ in cameras]
+        try:
+            if lib.RaylibAMD_RenderViews(C.byref(st), self.scene, handle_array(cameras), len(cameras), handle_array(imgs)) != 1:
+                raise RuntimeError("RaylibAMD_RenderViews failed")
+            out = np.zeros((len(cameras), h, w, 4), np.float32)
+            for i, ih in enumerate(imgs):
+                lib.RaylibAMD_DumpImageRGBA(ih, _fp(out[i]))
+        finally:
+            for ih in imgs:
+                lib.Raylib_DestroyImage(ih)
         return out
 
     def render_cells(self, w, h, spp, rank, world, max_path=5, tmin=1e-4, mode=RENDERMODE_DEFAULT):
