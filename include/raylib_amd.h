@@ -111,6 +111,51 @@ RAYLIB_API uint32_t RaylibAMD_NumCells(uint32_t width, uint32_t height);
  * {hit, t, p[3], n[3], paramU, paramV, material} as in oracle/flat_scene.h FlatHit). */
 RAYLIB_API int32_t RaylibAMD_ClosestHit(SceneHandle scene, const float* rays, int32_t n, float tMin, void* outHits);
 
+/* ---- batched ray queries ----------------------------------------------------------------------
+ * A ray's result is what the reference's Scene::Hit(ray, tMin, tMax) returns, under the renderer's own-box and tie rules:
+ * a triangle counts when tMin <= t <= tMax (Triangle::Hit), a sphere when tMin < t < tMax (Sphere::Hit), a cube when tMin <= t <= tMax (Cube::Hit).
+ * With tMax = FLT_MAX and rayTime = 0 a SURFACE record is RaylibAMD_ClosestHit's, byte for byte, on every tree -- with one exception: the wide trees'
+ * box tests replace an infinite 1/d by +-1e30, so a ray with a zero direction component whose other components are tiny (hits beyond about 1e20) may
+ * miss on the grid-4 or 8-wide tree what the binary tree finds (RAYLIB_QUERY_TREE=2 walks the binary tree).  A NaN bound gives a miss.  Cut-out
+ * triangles are alpha-tested during the walk, as in the render. */
+typedef struct RaylibAMDRay {          /* 32 bytes; on the device entry an array of them must be 16-byte aligned */
+	float org[3]; float tMin;
+	float dir[3]; float tMax;
+} RaylibAMDRay;
+typedef struct RaylibAMDHitT {         /* 16 bytes; a miss: prim = -1, t = b1 = b2 = 0 */
+	float t;
+	int32_t prim;                      /* the triangle's index in RaylibAMD_SceneExportTriangles order, RAYLIB_AMD_PRIM_SPHERE | k, or RAYLIB_AMD_PRIM_CUBE | k */
+	float b1, b2;                      /* the walk's barycentric pair: p = v0 + b1 (v1 - v0) + b2 (v2 - v0); 0 for spheres and cubes */
+} RaylibAMDHitT;
+#define RAYLIB_AMD_QUERY_ANY     0     /* out: uint32_t per ray, 1 when anything is hit in the interval (may stop at the first accepted candidate) */
+#define RAYLIB_AMD_QUERY_CLOSEST 1     /* out: RaylibAMDHitT per ray */
+#define RAYLIB_AMD_QUERY_SURFACE 2     /* out: the 44-byte record of RaylibAMD_ClosestHit per ray; outPrim (may be null): int32_t primitive per ray, -1 for a miss */
+#define RAYLIB_AMD_PRIM_SPHERE 0x10000000
+#define RAYLIB_AMD_PRIM_CUBE   0x20000000
+/* n rays from host memory, results to host memory; synchronous.  rayTime: the shutter time at which moving cubes are placed.  The library keeps its
+ * device staging buffers and grows them; a warm call allocates nothing.  Returns 1 (n == 0 included), or 0 with nothing written when a pointer is null with
+ * n > 0, n < 0, the scene is not finalized, the kind is unknown, rayTime is not finite, the scene's BVH is deeper than 64 levels, or there is no device.
+ * RaylibAMD_GetLastStats then reports rays, nodesVisited, trisTested, shadedHits, texFetches, kernelMs, wallMs and the tree walked. */
+RAYLIB_API int32_t RaylibAMD_TraceRays(SceneHandle scene, int32_t kind, const RaylibAMDRay* rays, int32_t n, float rayTime, void* out, int32_t* outPrim);
+/* The same on device pointers (rays, out, outPrim on rank 0's device; other pointers are refused).  rays must be 16-byte aligned, out 16-byte aligned for
+ * CLOSEST and 4-byte aligned otherwise, outPrim 4-byte aligned (refused otherwise).  stream == NULL: the library's stream, synchronous, with
+ * stats.  A non-null hipStream_t: the scene's upload (and a tree or table the query needs for the first time) happens first and synchronously, then the
+ * query is enqueued on that stream and the call returns; the stats are left alone.  With RAYLIB_NUM_GPUS > 1 queries run on rank 0's device. */
+RAYLIB_API int32_t RaylibAMD_TraceRaysDevice(SceneHandle scene, int32_t kind, const RaylibAMDRay* rays, int32_t n, float rayTime, void* out, int32_t* outPrim,
+        void* stream);
+/* Which tree and kernel instance a query of this kind would walk under the current environment (csrc/rl_plan.cc PlanQuery; RAYLIB_QUERY_TREE=2|4|8 forces a
+ * tree, and a tree the scene lacks falls back to the next of 8-wide, grid-4, binary).  No device needed.  Returns 1, -1 when the BVH is deeper than 64 levels,
+ * 0 for a bad argument, an unknown kind or a scene not finalized. */
+typedef struct RaylibAMDQueryPlan {
+	int32_t tree;             /* as RaylibAMDRenderPlan.tree: 1 binary, 3 4-wide grid nodes, 4 8-wide */
+	uint32_t treeWidth;       /* 2, 4 or 8 */
+	uint32_t nodeBytes;       /* bytes of one record counted in nodesVisited */
+	int32_t stack;            /* the instance's traversal stack */
+	int32_t prims;            /* the scene holds spheres or cubes */
+	int32_t early;            /* the occlusion query stops at its first accepted candidate */
+} RaylibAMDQueryPlan;
+RAYLIB_API int32_t RaylibAMD_PlanRayQuery(SceneHandle scene, int32_t kind, RaylibAMDQueryPlan* out);
+
 /* ---- procedural scene elements ----------------------------------------------------------
  * The reference's two procedural demo scenes (src/main.cc:913-984) `new` its C++ classes (Sphere, Cube, Triangle,
  * Lambertian, Metal, ...) in the application and pass the object pointers to Raylib_AddSceneElement.  A C ABI

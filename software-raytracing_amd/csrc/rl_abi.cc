@@ -724,6 +724,46 @@ int32_t RaylibAMD_ClosestHit(SceneHandle sh, const float* rays, int32_t n, float
 	return DeviceClosestHit(*s, rays, n, tMin, outHits) ? 1 : 0;
 }
 
+// RaylibAMD_TraceRays / RaylibAMD_TraceRaysDevice: the refusals of include/raylib_amd.h, then the device
+static int32_t TraceRaysInternal(const char* who, SceneHandle sh, int32_t kind, const RaylibAMDRay* rays, int32_t n, float rayTime, void* out, int32_t* outPrim,
+                                 bool hostMem, void* stream)
+{
+	Scene* s = (Scene*)sh;
+	if (!s || n < 0 || (n > 0 && (!rays || !out))) { Log("%s: null argument", who); return 0; }
+	if (!s->finalized) { Log("%s: scene was not finalized (Raylib_FinalizeScene)", who); return 0; }
+	if (kind < RAYLIB_AMD_QUERY_ANY || kind > RAYLIB_AMD_QUERY_SURFACE) { Log("%s: unknown query kind %d", who, kind); return 0; }
+	if (!std::isfinite(rayTime)) { Log("%s: ray time %g is not finite", who, rayTime); return 0; }
+	if (!DeviceAvailable()) return 0;
+	if (s->hasMovingCubes && !(rayTime >= s->accelT0 && rayTime <= s->accelT1)) {
+		// moving cubes: their boxes must cover the motion up to this ray time (as a render rebuilds them for its camera's shutter interval)
+		const float t0 = std::min(s->accelT0, rayTime), t1 = std::max(s->accelT1, rayTime);
+		if (s->device) { DeviceReleaseScene(s->device); s->device = nullptr; }
+		if (!s->BuildAccel(t0, t1)) { Log("%s: the acceleration structure could not be rebuilt for ray time %g", who, rayTime); return 0; }
+	}
+	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
+	if (!DeviceTraceRays(*s, kind, rays, n, rayTime, out, outPrim, hostMem, stream, stats)) return 0;
+	if (!stream) { std::lock_guard<std::mutex> lk(g_stateMu); g_lastStats = stats; }
+	return 1;
+}
+int32_t RaylibAMD_TraceRays(SceneHandle sh, int32_t kind, const RaylibAMDRay* rays, int32_t n, float rayTime, void* out, int32_t* outPrim)
+{
+	return TraceRaysInternal("RaylibAMD_TraceRays", sh, kind, rays, n, rayTime, out, outPrim, true, nullptr);
+}
+int32_t RaylibAMD_TraceRaysDevice(SceneHandle sh, int32_t kind, const RaylibAMDRay* rays, int32_t n, float rayTime, void* out, int32_t* outPrim, void* stream)
+{
+	return TraceRaysInternal("RaylibAMD_TraceRaysDevice", sh, kind, rays, n, rayTime, out, outPrim, false, stream);
+}
+int32_t RaylibAMD_PlanRayQuery(SceneHandle sh, int32_t kind, RaylibAMDQueryPlan* out)
+{
+	Scene* s = (Scene*)sh;
+	if (!s || !s->finalized || !out || kind < RAYLIB_AMD_QUERY_ANY || kind > RAYLIB_AMD_QUERY_SURFACE) return 0;
+	memset(out, 0, sizeof(*out));
+	const QueryPlan p = PlanQuery(*s, kind, ReadRenderKnobs());
+	if (!p.ok) return -1;
+	out->tree = p.tree; out->treeWidth = p.treeWidth; out->nodeBytes = p.nodeBytes; out->stack = p.stack; out->prims = p.prims; out->early = p.early;
+	return 1;
+}
+
 int32_t RaylibAMD_SceneNumTriangles(SceneHandle sh) { Scene* s = (Scene*)sh; return s ? (int32_t)s->triangles.size() : 0; }
 int32_t RaylibAMD_SceneNumMaterials(SceneHandle sh) { Scene* s = (Scene*)sh; return s ? (int32_t)s->materials.size() : 0; }
 int32_t RaylibAMD_SceneNumTextures(SceneHandle sh) { Scene* s = (Scene*)sh; return s ? (int32_t)s->textures.size() : 0; }

@@ -236,6 +236,10 @@ bool DeviceRenderViews(Scene& scene, const RenderRequest& req, const DCamera* ca
 int32_t DeviceLastTracePlain();   // 1: the last path-traced render's megakernel was the leaf-list kernel's plain instance (rl_plan.cc)
 bool DeviceDrain(RaylibAMDStats* outLastStats);   // waits for multi-rank frames in flight; true + stats when that completed the last render call's numbers
 bool DeviceClosestHit(Scene& scene, const float* rays, int32_t n, float tMin, void* outHits);
+// RaylibAMD_TraceRays (hostMem: rays / out / outPrim in host memory) and RaylibAMD_TraceRaysDevice (device pointers; stream null: the library's stream,
+// synchronous; else enqueued on that hipStream_t).  stats: filled by a synchronous call.  kind is valid, n >= 0, the scene finalized: the ABI checked.
+bool DeviceTraceRays(Scene& scene, int32_t kind, const void* rays, int32_t n, float rayTime, void* out, int32_t* outPrim, bool hostMem, void* stream,
+                     RaylibAMDStats& stats);
 bool DevicePostProcess(Image& img);          // Image2D::PostProcess on the device; false when no device
 bool DeviceDumpRGB(Image& img, float* outRGB);   // a device-resident frame packed to RGB on the device and copied to caller memory through pinned staging; false: not applicable
 bool DeviceReadback(Image& img);            // device copy -> img.rgba (the caller checked hostStale)

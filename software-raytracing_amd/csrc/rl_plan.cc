@@ -26,6 +26,7 @@ RenderKnobs ReadRenderKnobs()
 	if (const char* e = getenv("RAYLIB_GUIDED")) k.guided = atoi(e);
 	if (const char* e = getenv("RAYLIB_BLOCKS_PER_CU")) k.blocksPerCU = std::max(0, atoi(e));
 	if (const char* e = getenv("RAYLIB_CULL_CELLS")) k.cullCells = atoi(e);
+	if (const char* e = getenv("RAYLIB_QUERY_TREE")) { const int v = atoi(e); k.queryTree = (v == 2 || v == 4 || v == 8) ? v : 0; }
 	return k;
 }
 
@@ -122,6 +123,25 @@ TracePlan PlanTrace(const Scene& sc, const RendererSettings& st, bool hasSky, co
 {
 	TracePlan p = Pick(sc, st, hasSky, knobs, true);
 	p.eagerTree = EagerTree(sc);
+	return p;
+}
+
+QueryPlan PlanQuery(const Scene& sc, int32_t kind, const RenderKnobs& k)
+{
+	QueryPlan p;
+	const BVH& b = sc.bvh;
+	p.prims = !sc.spheres.empty() || !sc.cubes.empty();
+	if (b.depth > 64) { p.ok = false; return p; }
+	const int want = k.queryTree ? k.queryTree : 8;
+	if (want >= 8 && !p.prims && !b.nodes8.empty() && b.depth8 <= RL_POOL8_MAXLEVELS) {
+		p.tree = TREE_WIDE8; p.treeWidth = 8; p.nodeBytes = (uint32_t)sizeof(DNode8); p.stack = 2 * RL_POOL8_MAXLEVELS;
+	} else if (want >= 4 && !p.prims && !b.nodes4q.empty() && b.stackNeed4 <= 64) {
+		p.tree = TREE_GRID4; p.treeWidth = 4; p.stack = b.stackNeed4 <= 32 ? 32 : 64;
+	} else {
+		p.stack = b.depth <= 32 ? 32 : 64;
+	}
+	// spheres close an open interval after the walk (rl_k_query.inl): with them the occlusion query walks to the closest hit
+	p.early = kind == RAYLIB_AMD_QUERY_ANY && !p.prims;
 	return p;
 }
 

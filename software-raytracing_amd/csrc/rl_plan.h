@@ -23,6 +23,7 @@ struct RenderKnobs {
 	int guided = 0;                               // RAYLIB_GUIDED
 	int blocksPerCU = 0;                          // RAYLIB_BLOCKS_PER_CU (0: not set or not positive)
 	int cullCells = 1;                            // RAYLIB_CULL_CELLS (rl_cull.cc reads it for itself; the runtime keys its cached cell lists on it)
+	int queryTree = 0;                            // RAYLIB_QUERY_TREE: 2, 4 or 8 (RaylibAMD_TraceRays; any other value: 0, not set)
 };
 RenderKnobs ReadRenderKnobs();
 
@@ -55,6 +56,19 @@ struct LaunchPlan {
 // One launch of a path-traced render: numActive of the rank's numLocalCells cells are in the job list, samples from sampleBegin; workgroupsPerCU as the occupancy query gave it.
 LaunchPlan PlanLaunch(uint32_t numLocalCells, uint32_t numActive, uint32_t spp, uint32_t sampleBegin, int numCUs, int workgroupsPerCU,
                       const TracePlan& trace, const RenderKnobs& knobs);
+
+// Which tree and k_query instance a batch of ray queries walks (RaylibAMD_TraceRays, rl_k_query.inl): the 8-wide tree when the scene carries one of at most
+// RL_POOL8_MAXLEVELS levels and has no spheres or cubes; else the grid-4 tree when its worst-case stack fits 64 entries (no spheres or cubes either); else the
+// binary tree.  RAYLIB_QUERY_TREE=2|4|8 starts the list lower; a tree the scene lacks falls through to the next one.
+struct QueryPlan {
+	bool ok = true;             // false: the BVH is deeper than the binary walk's stack (64)
+	int32_t tree = TREE_BVH2;   // TREE_BVH2, TREE_GRID4 or TREE_WIDE8
+	uint32_t treeWidth = 2, nodeBytes = 64;
+	int stack = 32;             // the instance's STACK (the 8-wide tree: words, two per group)
+	bool prims = false;         // spheres or cubes
+	bool early = false;         // the occlusion query stops at its first accepted candidate
+};
+QueryPlan PlanQuery(const Scene& sc, int32_t kind, const RenderKnobs& knobs);
 
 // Several views of one scene in one launch per sample batch (RaylibAMD_RenderViews): the job list of the batch.  Cell c of view v is batch cell
 // v * cellsPerView + c; the list is every view's listed cells, view by view, each view culled on its own (CullCells), a view that is not eligible listing all

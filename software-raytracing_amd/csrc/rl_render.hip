@@ -510,13 +510,14 @@ __device__ __forceinline__ bool Barycentric(bool fast, float X, float Y, float d
 // "if inner else leaf" loop a wave pays node + leaf cost on every trip as soon as one lane is at a leaf, and
 // the ~4x dearer triangle code ran with a handful of lanes (measured: 14 % VALU lane utilisation on the
 // 298 k-triangle scene).
+// tBound: where the search starts, "best" before any hit (the ray queries: the float above their tMax, rl_k_query.inl).
 template <int STACK, bool ANYHIT, bool PRIMS>
-__device__ __forceinline__ bool Traverse(const DSceneView& S, V3 o, V3 d, float rayTime, float tMin, HitRec& best, int* stk, Counters& c)
+__device__ __forceinline__ bool Traverse(const DSceneView& S, V3 o, V3 d, float rayTime, float tMin, HitRec& best, int* stk, Counters& c, const float tBound = INFINITY)
 {
 	c.rays++;
 	const V3 inv = v3(rtm::rcp1_(d.x), rtm::rcp1_(d.y), rtm::rcp1_(d.z));
 	const bool nx = inv.x < 0.0f, ny = inv.y < 0.0f, nz = inv.z < 0.0f;
-	best.t = INFINITY; best.tri = -1; best.a = 0.0f; best.b = 0.0f;
+	best.t = tBound; best.tri = -1; best.a = 0.0f; best.b = 0.0f;
 	int sp = 0;
 	int cur = 0;                  // root is an inner node
 	const int DONE = 0x7fffffff;  // not a node index (nodes < 2^31 - 1), not negative
@@ -792,14 +793,15 @@ __device__ __forceinline__ bool TraverseLeafList(const DSceneView& S, V3 o, V3 d
 // The same closest-hit search on the BVH4 (DNode4): four slab tests per step, hit children ordered by entry distance.
 // FULL: float boxes (S.nodes4f), else the grid nodes (S.nodes4)
 template <int STACK, bool ANYHIT, bool PRIMS, bool FULL, int LDS = 0, bool PLAIN = false>
-__device__ __forceinline__ bool Traverse4(const DSceneView& S, V3 o, V3 d, float rayTime, float tMin, HitRec& best, int* stk, Counters& c, const float4* sm = nullptr)
+__device__ __forceinline__ bool Traverse4(const DSceneView& S, V3 o, V3 d, float rayTime, float tMin, HitRec& best, int* stk, Counters& c, const float4* sm = nullptr,
+                                          const float tBound = INFINITY /* as in Traverse */)
 {
 	if constexpr (LDS == 2) return TraverseLeafList<ANYHIT, PLAIN>(S, o, d, tMin, best, c, sm);
 	c.rays++;
 	V3 invb = v3(rtm::rcp1_(d.x), rtm::rcp1_(d.y), rtm::rcp1_(d.z));   // for the box tests (the candidate rule divides again: exact, and rare)
 	if (!FULL) invb = ClampInv(invb);
 	const bool nx = invb.x < 0.0f, ny = invb.y < 0.0f, nz = invb.z < 0.0f;
-	best.t = INFINITY; best.tri = -1; best.a = 0.0f; best.b = 0.0f;
+	best.t = tBound; best.tri = -1; best.a = 0.0f; best.b = 0.0f;
 	int sp = 0, cur = 0;
 	const int DONE = 0x7fffffff;
 	for (;;) {
@@ -2085,7 +2087,12 @@ RL_POOL_INSTANCES(RL_POOL_X)
 RL_POOL_INSTANCES(RL_POOL_X)
 #undef RL_POOL_X
 
-#ifndef RL_TU_POOL   // everything below belongs to the main translation unit alone
+// A hit record as RaylibAMD_ClosestHit and the surface query of RaylibAMD_TraceRays return it (oracle/flat_scene.h FlatHit)
+struct DHitOut { int32_t hit; float t; float p[3]; float n[3]; float paramU, paramV; int32_t material; };
+// The ray queries (RaylibAMD_TraceRays): defined in rl_query.hip's translation unit, declared in the others
+#include "rl_k_query.inl"
+
+#if !defined(RL_TU_POOL) && !defined(RL_TU_QUERY)   // everything below belongs to the main translation unit alone
 // One slot's samples of this batch added to `a` in sample order -- the megakernel's from the sample buffer, or, for a cell outside the scene's silhouette,
 // the miss shader's value every one of them comes to -- and each sample's RGB handed to `each` (k_resolve: nothing; k_progressive_resolve: the
 // luminance moments of its stopping rule).
@@ -2262,8 +2269,6 @@ k_progressive_compact(uint32_t* __restrict__ live, uint32_t* __restrict__ trace,
 RL_AOV_X(16, false) RL_AOV_X(32, false) RL_AOV_X(32, true) RL_AOV_X(64, false) RL_AOV_X(64, true)
 #undef RL_AOV_X
 #ifndef RL_TU_VIEWS
-
-struct DHitOut { int32_t hit; float t; float p[3]; float n[3]; float paramU, paramV; int32_t material; };
 
 template <int STACK, bool PRIMS>
 __global__ void __launch_bounds__(RL_BLOCK)
@@ -2515,10 +2520,10 @@ k_scatter_cells(const float4* __restrict__ gather, float4* __restrict__ out, uin
 }
 
 #endif   // RL_TU_VIEWS
-#endif   // RL_TU_POOL
+#endif   // RL_TU_POOL, RL_TU_QUERY
 
 } // namespace rl
 
-#if !defined(RL_TU_POOL) && !defined(RL_TU_VIEWS)
+#if !defined(RL_TU_POOL) && !defined(RL_TU_VIEWS) && !defined(RL_TU_QUERY)
 #include "rl_runtime.inl"
 #endif

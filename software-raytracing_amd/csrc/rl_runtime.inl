@@ -32,6 +32,7 @@ struct DeviceSceneCopy {
 	DNode* nodes = nullptr; DTriIsect* isect = nullptr; DTriShade* shade = nullptr; int32_t* alphaTex = nullptr;
 	DMaterial* materials = nullptr; DTexture* textures = nullptr; float* texels = nullptr;
 	DSphere* spheres = nullptr; DCube* cubes = nullptr;
+	int32_t* slotIndex = nullptr;   // triangle slot -> index in the scene's triangle order (the ray queries' primitive numbers), uploaded when a query first needs it
 	// the sky panorama is read when a render starts, as the reference does (renderer.cc:159-176 dereferences the handle per miss)
 	float4* sky = nullptr; size_t skyBytes = 0;
 	const Image* skyImage = nullptr; uint64_t skyVersion = 0;
@@ -107,6 +108,7 @@ struct Worker {
 	bool Wait() { std::unique_lock<std::mutex> lk(m); cv.wait(lk, [&] { return !pending; }); return result; }
 };
 
+#define RL_QUERY_RING 64   /* ray counters of the ray queries, used in turn (DeviceTraceRays) */
 struct RankCtx {
 	int rank = 0, device = 0, devSlot = 0, numCUs = 0;
 	hipStream_t stream = nullptr;
@@ -129,6 +131,14 @@ struct RankCtx {
 	uint32_t cullActive[2] = { 0, 0 }; uint64_t cullEmptyPixels[2] = { 0, 0 }; float cullL[2][3] = { { 0, 0, 0 }, { 0, 0, 0 } }; uint32_t cullRays[2] = { 1, 1 };
 	std::map<const void*, int> occupancy;   // blocks per CU, asked once per kernel
 	Worker* worker = nullptr;
+	// the ray queries (DeviceTraceRays): staging buffers of the host entry, kept and grown; a ring of ray counters, one per launch in turn, each with the
+	// event recorded behind its last launch (a slot is reused once that launch is done, whatever stream it ran on); the synchronous queries' counters and events
+	float4* qRays = nullptr; size_t qRaysBytes = 0;
+	void* qOut = nullptr; size_t qOutBytes = 0;
+	int32_t* qPrim = nullptr; size_t qPrimBytes = 0;
+	unsigned int* qRing = nullptr; hipEvent_t qRingEv[RL_QUERY_RING] = {}; bool qRingUsed[RL_QUERY_RING] = {}; uint32_t qRingNext = 0;
+	unsigned long long* qStats = nullptr; unsigned long long* qStatsHost = nullptr;
+	hipEvent_t qEv[2] = { nullptr, nullptr };
 };
 
 struct Runtime {
@@ -327,6 +337,7 @@ void FreeCopy(DeviceSceneCopy* C)
 	(void)hipFree(C->nodes); if (C->nodes4) (void)hipFree(C->nodes4); if (C->nodes4f) (void)hipFree(C->nodes4f); if (C->nodes8) (void)hipFree(C->nodes8); if (C->leafList) (void)hipFree(C->leafList); (void)hipFree(C->isect); (void)hipFree(C->shade); if (C->alphaTex) (void)hipFree(C->alphaTex);
 	(void)hipFree(C->materials); (void)hipFree(C->textures); (void)hipFree(C->texels); (void)hipFree(C->spheres); (void)hipFree(C->cubes);
 	if (C->sky) (void)hipFree(C->sky);
+	if (C->slotIndex) (void)hipFree(C->slotIndex);
 	delete C;
 }
 void FreeScene(DeviceScene* D)
@@ -1325,6 +1336,119 @@ bool DeviceClosestHit(Scene& sc, const float* rays, int32_t n, float tMin, void*
 	(void)hipFree(dRays); (void)hipFree(dOut);
 	if (!ok) Log("RaylibAMD_ClosestHit: a HIP call failed");
 	return ok;
+}
+
+typedef void (*QueryKernel)(const DSceneView, const float4*, uint32_t, float, void*, int32_t*, const int32_t*, unsigned int*, unsigned long long*);
+template <int KIND>
+static QueryKernel QueryKernelOfKind(const QueryPlan& p)
+{
+	if (p.tree == TREE_WIDE8) return (QueryKernel)k_query<8, KIND, 2 * RL_POOL8_MAXLEVELS, false>;
+	if (p.tree == TREE_GRID4) return p.stack <= 32 ? (QueryKernel)k_query<4, KIND, 32, false> : (QueryKernel)k_query<4, KIND, 64, false>;
+	if (p.stack <= 32) return p.prims ? (QueryKernel)k_query<2, KIND, 32, true> : (QueryKernel)k_query<2, KIND, 32, false>;
+	return p.prims ? (QueryKernel)k_query<2, KIND, 64, true> : (QueryKernel)k_query<2, KIND, 64, false>;
+}
+static_assert(RAYLIB_AMD_QUERY_ANY == RL_QK_ANY && RAYLIB_AMD_QUERY_CLOSEST == RL_QK_CLOSEST && RAYLIB_AMD_QUERY_SURFACE == RL_QK_SURFACE, "query kinds");
+static_assert(sizeof(RaylibAMDRay) == 32 && sizeof(RaylibAMDHitT) == sizeof(DQueryHit) && sizeof(DHitOut) == 44, "query records");
+
+// a device pointer the query may use: memory of rank 0's device
+static bool OnDevice(const void* p, int device)
+{
+	hipPointerAttribute_t a;
+	if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+	return (a.type == hipMemoryTypeDevice || a.isManaged) && a.device == device;
+}
+
+bool DeviceTraceRays(Scene& sc, int32_t kind, const void* rays, int32_t n, float rayTime, void* out, int32_t* outPrim, bool hostMem, void* stream,
+                     RaylibAMDStats& stats)
+{
+	const auto t0 = std::chrono::steady_clock::now();
+	std::lock_guard<std::mutex> lk(g_rt.lock);
+	if (!EnsureRuntime()) return false;
+	RankCtx& R = Rank0();
+	HIP_OK(hipSetDevice(R.device));
+	const QueryPlan plan = PlanQuery(sc, kind, ReadRenderKnobs());
+	if (!plan.ok) { Log("RaylibAMD_TraceRays: BVH depth %u exceeds the traversal stack (64)", sc.bvh.depth); return false; }
+	const size_t outBytes = (size_t)n * (kind == RAYLIB_AMD_QUERY_ANY ? sizeof(uint32_t) : kind == RAYLIB_AMD_QUERY_CLOSEST ? sizeof(DQueryHit) : sizeof(DHitOut));
+	if (!hostMem && n > 0) {
+		if (!OnDevice(rays, R.device) || !OnDevice(out, R.device) || (outPrim && kind == RAYLIB_AMD_QUERY_SURFACE && !OnDevice(outPrim, R.device))) {
+			Log("RaylibAMD_TraceRaysDevice: a pointer is not device memory of device %d", R.device);
+			return false;
+		}
+		// the kernel reads a ray as two 16-byte loads and writes a RaylibAMDHitT as one 16-byte store, the other records as 4-byte words
+		if (((uintptr_t)rays & 15u) != 0) { Log("RaylibAMD_TraceRaysDevice: the rays are not 16-byte aligned"); return false; }
+		const uintptr_t outAlign = kind == RAYLIB_AMD_QUERY_CLOSEST ? 15u : 3u;
+		if (((uintptr_t)out & outAlign) != 0 || ((uintptr_t)outPrim & 3u) != 0) { Log("RaylibAMD_TraceRaysDevice: the output is not %u-byte aligned", (unsigned)outAlign + 1u); return false; }
+	}
+	if (!UploadScene(sc)) return false;
+	DeviceSceneCopy* Cp = sc.device->copy[(size_t)R.devSlot];
+	if (!EnsureWideTree(Cp, sc, plan.tree)) return false;
+	const bool wantPrim = kind == RAYLIB_AMD_QUERY_CLOSEST || (kind == RAYLIB_AMD_QUERY_SURFACE && outPrim);
+	if (wantPrim && !Cp->slotIndex && !sc.bvh.triOrder.empty()) {
+		std::vector<int32_t> idx(sc.bvh.triOrder.begin(), sc.bvh.triOrder.end());
+		int32_t* p = nullptr;
+		if (!Upload(p, idx.data(), idx.size())) { if (p) (void)hipFree(p); return false; }
+		Cp->slotIndex = p;
+	}
+	const hipStream_t st = stream ? (hipStream_t)stream : R.stream;
+	const bool sync = !stream;
+	if (!R.qRing) {
+		HIP_OK(hipMalloc(&R.qRing, RL_QUERY_RING * sizeof(unsigned int)));
+		for (int k = 0; k < RL_QUERY_RING; ++k) HIP_OK(hipEventCreateWithFlags(&R.qRingEv[k], hipEventDisableTiming));
+	}
+	const uint32_t slot = R.qRingNext;
+	if (R.qRingUsed[slot]) HIP_OK(hipEventSynchronize(R.qRingEv[slot]));   // RL_QUERY_RING launches ago: long done, unless a caller's stream is that far behind
+	unsigned int* counter = R.qRing + slot;
+	if (sync && !R.qStats) {
+		HIP_OK(hipMalloc(&R.qStats, 8 * sizeof(unsigned long long)));
+		HIP_OK(hipHostMalloc(&R.qStatsHost, 8 * sizeof(unsigned long long), hipHostMallocDefault));
+		HIP_OK(hipEventCreate(&R.qEv[0])); HIP_OK(hipEventCreate(&R.qEv[1]));
+	}
+	memset(&stats, 0, sizeof(stats));
+	stats.treeWidth = plan.treeWidth; stats.nodeBytes = plan.nodeBytes; stats.ranks = 1; stats.devices = 1;
+	stats.numNodes = (uint32_t)sc.bvh.nodes.size(); stats.numTriangles = (uint32_t)sc.triangles.size(); stats.bvhDepth = sc.bvh.depth;
+	if (n == 0) return true;
+	const float4* dRays = (const float4*)rays; void* dOut = out; int32_t* dPrim = (kind == RAYLIB_AMD_QUERY_SURFACE) ? outPrim : nullptr;
+	if (hostMem) {
+		if (!Grow(R.qRays, R.qRaysBytes, (size_t)n * sizeof(RaylibAMDRay)) || !Grow(R.qOut, R.qOutBytes, outBytes)) return false;
+		if (dPrim && !Grow(R.qPrim, R.qPrimBytes, (size_t)n * sizeof(int32_t))) return false;
+		HIP_OK(hipMemcpyAsync(R.qRays, rays, (size_t)n * sizeof(RaylibAMDRay), hipMemcpyHostToDevice, st));
+		dRays = R.qRays; dOut = R.qOut; if (dPrim) dPrim = R.qPrim;
+	}
+	const QueryKernel kernel = kind == RAYLIB_AMD_QUERY_ANY ? QueryKernelOfKind<RL_QK_ANY>(plan) : kind == RAYLIB_AMD_QUERY_CLOSEST ? QueryKernelOfKind<RL_QK_CLOSEST>(plan)
+	                         : QueryKernelOfKind<RL_QK_SURFACE>(plan);
+	int blocksPerCU = 0;
+	{
+		auto it = R.occupancy.find((const void*)kernel);
+		if (it == R.occupancy.end()) {
+			HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, kernel, RL_BLOCK, 0));
+			R.occupancy[(const void*)kernel] = blocksPerCU;
+		} else blocksPerCU = it->second;
+	}
+	// enough workgroups to fill the device once; the waves take their rays from the counter (rl_k_query.inl)
+	const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)R.numCUs * (uint64_t)std::max(1, blocksPerCU), ((uint64_t)n + RL_BLOCK - 1) / RL_BLOCK));
+	const DSceneView view = Cp->view;
+	HIP_OK(hipMemsetAsync(counter, 0, sizeof(unsigned int), st));
+	if (sync) { HIP_OK(hipMemsetAsync(R.qStats, 0, 8 * sizeof(unsigned long long), st)); HIP_OK(hipEventRecord(R.qEv[0], st)); }
+	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RL_BLOCK), 0, st, view, dRays, (uint32_t)n, rayTime, dOut, dPrim, Cp->slotIndex, counter, sync ? R.qStats : nullptr);
+	HIP_OK(hipGetLastError());
+	HIP_OK(hipEventRecord(R.qRingEv[slot], st));
+	R.qRingUsed[slot] = true;
+	R.qRingNext = (slot + 1u) % RL_QUERY_RING;
+	if (!sync) return true;
+	HIP_OK(hipEventRecord(R.qEv[1], st));
+	HIP_OK(hipMemcpyAsync(R.qStatsHost, R.qStats, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+	if (hostMem) {
+		HIP_OK(hipMemcpyAsync(out, dOut, outBytes, hipMemcpyDeviceToHost, st));
+		if (dPrim) HIP_OK(hipMemcpyAsync(outPrim, dPrim, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+	}
+	HIP_OK(hipStreamSynchronize(st));
+	float ms = 0.0f;
+	HIP_OK(hipEventElapsedTime(&ms, R.qEv[0], R.qEv[1]));
+	stats.rays = R.qStatsHost[CNT_RAYS]; stats.nodesVisited = R.qStatsHost[CNT_NODES]; stats.trisTested = R.qStatsHost[CNT_TRIS];
+	stats.shadedHits = R.qStatsHost[CNT_SHADED]; stats.texFetches = R.qStatsHost[CNT_TEXELS];
+	stats.kernelMs = ms; stats.traceKernelMs = ms; stats.traceLaunches = 1;
+	stats.wallMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	return true;
 }
 
 // kind 0: scatter (in 16 / out 16 floats per record, a = material), 1: camera rays (in 2 / out 7), 2: texture (in 2 / out 4, a = texture, b = sRGB)

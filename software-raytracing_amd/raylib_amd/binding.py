@@ -71,6 +71,82 @@ class RenderPlan(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Ray(C.Structure):
+    """include/raylib_amd.h RaylibAMDRay (32 bytes): org, tMin, dir, tMax."""
+    _fields_ = [("org", C.c_float * 3), ("tMin", C.c_float), ("dir", C.c_float * 3), ("tMax", C.c_float)]
+
+
+class HitT(C.Structure):
+    """include/raylib_amd.h RaylibAMDHitT (16 bytes)."""
+    _fields_ = [("t", C.c_float), ("prim", C.c_int32), ("b1", C.c_float), ("b2", C.c_float)]
+
+
+class QueryPlan(C.Structure):
+    """include/raylib_amd.h RaylibAMDQueryPlan."""
+    _fields_ = [("tree", C.c_int32), ("treeWidth", C.c_uint32), ("nodeBytes", C.c_uint32), ("stack", C.c_int32), ("prims", C.c_int32), ("early", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+QUERY_ANY, QUERY_CLOSEST, QUERY_SURFACE = 0, 1, 2   # RAYLIB_AMD_QUERY_*
+PRIM_SPHERE, PRIM_CUBE = 0x10000000, 0x20000000     # RAYLIB_AMD_PRIM_*
+HITT_DTYPE = np.dtype([("t", "f4"), ("prim", "i4"), ("b1", "f4"), ("b2", "f4")])
+SURFACE_DTYPE = np.dtype([("hit", "i4"), ("t", "f4"), ("p", "f4", 3), ("n", "f4", 3), ("paramU", "f4"), ("paramV", "f4"), ("material", "i4")])   # = RaylibAMD_ClosestHit's
+_QUERY_DTYPES = {QUERY_ANY: np.dtype("u4"), QUERY_CLOSEST: HITT_DTYPE, QUERY_SURFACE: SURFACE_DTYPE}
+_TORCH_WORDS = {QUERY_ANY: 1, QUERY_CLOSEST: 4, QUERY_SURFACE: 11}
+
+
+def plan_ray_query(lib, scene, kind):
+    """RaylibAMD_PlanRayQuery: (return code, plan dict)."""
+    p = QueryPlan()
+    r = lib.RaylibAMD_PlanRayQuery(scene, int(kind), C.byref(p))
+    return r, p.as_dict()
+
+
+def trace_rays(lib, scene, rays, kind, ray_time=0.0, with_prim=False):
+    """Batched ray queries (RaylibAMD_TraceRays / RaylibAMD_TraceRaysDevice).
+
+    rays: an (n, 8) float32 array -- org xyz, tMin, dir xyz, tMax per row.  A NumPy array goes through the host entry and returns a NumPy array of
+    the kind's records (uint32 for QUERY_ANY, HITT_DTYPE, SURFACE_DTYPE).  A torch tensor on the device goes through the device entry, ordered after
+    the work already queued on torch.cuda.current_stream(): on a stream of the caller's the query is enqueued there and the call returns; on torch's
+    default stream (whose handle is 0, which the library reads as its own stream) that stream is synchronised first and the call is synchronous.  It
+    returns a tensor: (n,) int32 for QUERY_ANY (0 / 1), (n, 4) int32 words for QUERY_CLOSEST and (n, 11) int32 words for
+    QUERY_SURFACE (reinterpret with .view(torch.float32) or move to NumPy and .view(HITT_DTYPE / SURFACE_DTYPE)).  with_prim (QUERY_SURFACE): also
+    return the primitive of each ray as a second array / tensor.  Raises RuntimeError when the library refuses the call."""
+    kind = int(kind)
+    if kind not in _QUERY_DTYPES:
+        raise ValueError("unknown query kind %r" % kind)
+    if isinstance(rays, np.ndarray):
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        n = len(r)
+        out = np.zeros(n, _QUERY_DTYPES[kind])
+        prim = np.zeros(n, np.int32) if (with_prim and kind == QUERY_SURFACE) else None
+        ok = lib.RaylibAMD_TraceRays(scene, kind, r.ctypes.data_as(C.POINTER(Ray)), n, float(ray_time), out.ctypes.data,
+                                     prim.ctypes.data_as(C.POINTER(C.c_int32)) if prim is not None else None)
+        if ok != 1:
+            raise RuntimeError("RaylibAMD_TraceRays refused the query")
+        return (out, prim) if with_prim else out
+    import torch
+    if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.dtype == torch.float32):
+        raise TypeError("rays: a float32 NumPy array or a float32 torch tensor on the device")
+    r = rays.reshape(-1, 8).contiguous()
+    n = r.shape[0]
+    words = _TORCH_WORDS[kind]
+    out = torch.empty((n, words) if words > 1 else (n,), dtype=torch.int32, device=r.device)
+    prim = torch.empty(n, dtype=torch.int32, device=r.device) if (with_prim and kind == QUERY_SURFACE) else None
+    stream = torch.cuda.current_stream(r.device)
+    if stream.cuda_stream == 0:
+        # the library's stream is not ordered against torch's default stream: the rays (r may come from a copy just queued there) and the memory of
+        # out / prim must be ready before the library's stream touches them
+        stream.synchronize()
+    ok = lib.RaylibAMD_TraceRaysDevice(scene, kind, C.cast(C.c_void_p(r.data_ptr()), C.POINTER(Ray)), n, float(ray_time), C.c_void_p(out.data_ptr()),
+                                       C.cast(C.c_void_p(prim.data_ptr()), C.POINTER(C.c_int32)) if prim is not None else None, C.c_void_p(stream.cuda_stream))
+    if ok != 1:
+        raise RuntimeError("RaylibAMD_TraceRaysDevice refused the query")
+    return (out, prim) if with_prim else out
+
+
 # Per-ray / per-unit algorithmic byte constants of the flat layout (csrc/rl_device.h)
 NODE_B, TRI_B, SHADE_B, TEXEL_B, PIXEL_B = 64, 64, 64, 16, 16
 
@@ -137,6 +213,9 @@ _EXPORTS = {
     "RaylibAMD_EvalTexture": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float)]),
     "RaylibAMD_EvalDeviceMath": (C.c_int32, [C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float)]),
     "RaylibAMD_ClosestHit": (C.c_int32, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_void_p]),
+    "RaylibAMD_TraceRays": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(Ray), C.c_int32, C.c_float, C.c_void_p, C.POINTER(C.c_int32)]),
+    "RaylibAMD_TraceRaysDevice": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(Ray), C.c_int32, C.c_float, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "RaylibAMD_PlanRayQuery": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(QueryPlan)]),
     "RaylibAMD_VerifyExactMath": (C.c_int32, [C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "RaylibAMD_CullCells": (C.c_int32, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_float)]),
     "RaylibAMD_SceneNumTriangles": (C.c_int32, [C.c_void_p]),
