@@ -117,7 +117,10 @@ RAYLIB_API int32_t RaylibAMD_ClosestHit(SceneHandle scene, const float* rays, in
  * With tMax = FLT_MAX and rayTime = 0 a SURFACE record is RaylibAMD_ClosestHit's, byte for byte, on every tree -- with one exception: the wide trees'
  * box tests replace an infinite 1/d by +-1e30, so a ray with a zero direction component whose other components are tiny (hits beyond about 1e20) may
  * miss on the grid-4 or 8-wide tree what the binary tree finds (RAYLIB_QUERY_TREE=2 walks the binary tree).  A NaN bound gives a miss.  Cut-out
- * triangles are alpha-tested during the walk, as in the render. */
+ * triangles are alpha-tested during the walk, as in the render.
+ * A query never reports a hit behind the origin: tMin < 0 (-inf included) is read as +0, and -0.0 is 0; a NaN tMin stays a NaN.  (The slack of the own-box
+ * rule and of the walks' box tests is a factor above 1 and assumes t >= 0.)  A triangle at exactly tMin or exactly tMax counts, so [t, t] finds the surface at t;
+ * tMin > tMax is empty.  Checked against a loop over every primitive: tests/test_gpu_ray_query_intervals.py. */
 typedef struct RaylibAMDRay {          /* 32 bytes; on the device entry an array of them must be 16-byte aligned */
 	float org[3]; float tMin;
 	float dir[3]; float tMax;

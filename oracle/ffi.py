@@ -40,6 +40,10 @@ HIT_DTYPE = np.dtype([
 ])
 assert HIT_DTYPE.itemsize == 44
 
+INTERVAL_HIT_DTYPE = np.dtype([("t", "f4"), ("count", "i4"), ("prims", "i4", 8), ("nearerRejected", "i4")])
+assert INTERVAL_HIT_DTYPE.itemsize == 44
+PRIM_SPHERE, PRIM_CUBE = 0x10000000, 0x20000000   # RAYLIB_AMD_PRIM_*
+
 
 class FlatTexture(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("rgba", C.POINTER(C.c_float))]
@@ -153,6 +157,7 @@ class Checker:
         f("bvh_stats").argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         if prefix == "oracle_":
             lib.oracle_get_counters.argtypes = [C.c_void_p, C.POINTER(OracleCounters)]
+            lib.oracle_interval_hits.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_int32, C.c_void_p]
             lib.oracle_material_from_mtl.argtypes = [C.POINTER(C.c_float)] * 4 + [C.c_float, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_void_p]
             lib.oracle_postprocess.argtypes = [C.POINTER(C.c_float), C.c_int64]
             lib.oracle_write_obj.restype = C.c_int32
@@ -258,6 +263,13 @@ class Checker:
         return n.value, d.value
 
     # -- oracle-only -------------------------------------------------------------
+    def interval_hits(self, scene, rays8, ray_time=0.0, threads=None):
+        """Every primitive against each ray's own [tMin, tMax] (rays8: n x (org, tMin, dir, tMax)), no tree: INTERVAL_HIT_DTYPE records."""
+        rays8 = np.ascontiguousarray(rays8, np.float32).reshape(-1, 8)
+        out = np.zeros(len(rays8), INTERVAL_HIT_DTYPE)
+        self.lib.oracle_interval_hits(scene, _fp(rays8), len(rays8), float(ray_time), int(threads or min(16, os.cpu_count() or 1)), out.ctypes.data)
+        return out
+
     def material_from_mtl(self, Kd, Ks, Ke, Tf, Ns, Ni, illum, Pr, Pm, has_map_kd):
         arrs = [np.asarray(a, np.float32) for a in (Kd, Ks, Ke, Tf)]
         out = np.zeros(1, MAT_DTYPE)

@@ -22,6 +22,15 @@ typedef struct OracleCounters {
 	uint64_t hitsOutsideOwnBox; /* triangle hits accepted although the ray fails the box test of the triangle's own AABB (reachability depends on the tree) */
 } OracleCounters;
 
+/* One ray's answer from oracle_interval_hits.  prims: RaylibAMD_SceneExportTriangles indices (the flat order of FlatSceneDesc), or
+ * RAYLIB_AMD_PRIM_SPHERE|k (0x10000000) / RAYLIB_AMD_PRIM_CUBE|k (0x20000000); -1 where unused. */
+typedef struct OracleIntervalHit {
+	float   t;               /* the least accepted t; +inf when nothing is accepted */
+	int32_t count;           /* primitives accepted at exactly that t */
+	int32_t prims[8];        /* the first eight of them */
+	int32_t nearerRejected;  /* triangles TriangleHit accepts at a smaller t but the device's candidate rule rejects (information only) */
+} OracleIntervalHit;
+
 /* buildSeed != 0: the reference's BVH construction (random axis per node, drawn from the stream keyed by buildSeed);
  * buildSeed == 0: a median-split tree built in n log n -- for multi-million-triangle scenes' windows (see BuildBVHFast). */
 void*   oracle_scene_create(const FlatSceneDesc* desc, uint64_t buildSeed);
@@ -33,6 +42,9 @@ void    oracle_render_region(void* scene, const FlatCamera* cam, const FlatSetti
                              float* outRGBA, float* outSamples);
 void    oracle_get_counters(void* scene, OracleCounters* out);   /* counters of the last oracle_render */
 void    oracle_closest_hit(void* scene, const float* rays, int32_t n, float tMin, FlatHit* out);
+/* Oracle-only: every primitive against each ray's own [tMin, tMax], no tree and no box culling.  rays8: n x (org, tMin, dir, tMax).
+ * A triangle counts when TriangleHit accepts it and the device's candidate rule passes; a sphere by SphereHit; a cube by CubeHit at rayTime. */
+void    oracle_interval_hits(void* scene, const float* rays8, int32_t n, float rayTime, int32_t threads, OracleIntervalHit* out);
 void    oracle_aabb_hit(const float* boxes, const float* rays, int32_t n, float tMin, float tMax, int32_t* out);
 void    oracle_triangle_hit(const FlatTriangle* tris, const float* rays, int32_t n, float tMin, float tMax, FlatHit* out);
 void    oracle_onb(const float* normals, const float* vecs, int32_t n, float* outLocal, float* outWorld);

@@ -10,6 +10,7 @@
 // The interval [tMin, tMax]: the walk starts with "best" at the float above tMax, so the triangle test (t >= tMin, t < best) takes a hit at exactly tMax,
 // as Triangle::Hit does, and every box beyond tMax is culled.  A sphere's interval is open (Sphere::Hit: t_min < t < t_max): a sphere at exactly tMax is
 // dropped afterwards -- it can only have been the walk's result if nothing nearer was accepted.  A NaN bound makes every comparison false: a miss.
+// tMin < 0 is raised to +0 (QueryTMin).  A triangle at exactly tMin counts: this unit widens the candidate rule's "own box ends before tMin" (rl_render.hip OwnBoxPassBox).
 #ifndef RL_QUERY_CHUNK
 #define RL_QUERY_CHUNK 64u       /* rays a wave takes per atomic on the global counter */
 #endif
@@ -26,6 +27,11 @@ __device__ __forceinline__ float NextUpF(float x)
 	const int b = __float_as_int(x);
 	return __int_as_float(x > 0.0f ? b + 1 : b - 1);
 }
+
+// A query never reports a hit behind the origin: tMin < 0 is read as +0 (include/raylib_amd.h).  The slack of the candidate rule (t * RL_CANDIDATE_SLACK >= the
+// entry into the triangle's own box) and of the widened box tests (tf * widen < tn) is a factor above 1, which moves a negative t the wrong way.  A comparison,
+// not fmaxf: a NaN stays a NaN and gives a miss; -0.0 compares as 0.
+__device__ __forceinline__ float QueryTMin(float tMin) { return tMin < 0.0f ? 0.0f : tMin; }
 
 // the record of one finished ray
 template <int KIND, bool PRIMS>
@@ -88,7 +94,7 @@ k_query(const DSceneView S, const float4* __restrict__ rays, uint32_t n, float r
 					const float4* rp = rays + 2u * (size_t)i;   // (64-bit offset: n may reach 2^31 - 1)
 					const float4 r0 = GLoadF4(rp, 0), r1 = GLoadF4(rp, 1);
 					const V3 o = v3(r0.x, r0.y, r0.z), d = v3(r1.x, r1.y, r1.z);
-					const float tMin = r0.w, tMax = r1.w;
+					const float tMin = QueryTMin(r0.w), tMax = r1.w;
 					HitRec h;
 					if constexpr (TREE == 2) Traverse<STACK, EARLY, PRIMS>(S, o, d, rayTime, tMin, h, stk, c, NextUpF(tMax));
 					else Traverse4<STACK, EARLY, false, false>(S, o, d, rayTime, tMin, h, stk, c, nullptr, NextUpF(tMax));
@@ -136,7 +142,7 @@ k_query(const DSceneView S, const float4* __restrict__ rays, uint32_t n, float r
 						my = next + rank;
 						const float4* rp = rays + 2u * (size_t)my;
 						const float4 r0 = GLoadF4(rp, 0), r1 = GLoadF4(rp, 1);
-						T.o = v3(r0.x, r0.y, r0.z); T.d = v3(r1.x, r1.y, r1.z); tMin = r0.w;
+						T.o = v3(r0.x, r0.y, r0.z); T.d = v3(r1.x, r1.y, r1.z); tMin = QueryTMin(r0.w);
 						T.inv = ClampInv(v3(FastRcp(T.d.x), FastRcp(T.d.y), FastRcp(T.d.z)));
 						T.nx = T.inv.x < 0.0f; T.ny = T.inv.y < 0.0f; T.nz = T.inv.z < 0.0f;
 						T.best.t = NextUpF(r1.w); T.best.tri = -1; T.best.a = 0.0f; T.best.b = 0.0f;

@@ -347,6 +347,11 @@ __device__ __forceinline__ bool AlphaTestCandidate(const DSceneView& S, int tri,
 // same hit, and since every box of the reference's tree contains this AABB (and rounding is monotone) the reference accepts
 // whatever is accepted here.  (What it accepts beyond that -- a hit outside the triangle's own box but inside its random
 // parent's -- is tree-dependent on its side; the oracle counts those events so that tests can tell them from real mismatches.)
+// In the ray queries' translation unit (rl_query.hip) "the box's exit lies before tMin" is widened like the exit of every other box of a walk (Slab: tf * widen
+// < tn); the box's own entry against its own exit -- does the ray pass the box at all -- stays exact, so a query accepts what a render accepts.  A render starts
+// its rays at rayTMin, far from any surface the ray is meant to meet; a query's tMin is the caller's and may be a surface's own t (the point interval [t, t], or
+// tMin = the previous hit's t).  The box of a triangle that lies in an axis plane is flat, its exit (corner - o) * (1 / d) is the plane's t up to an ulp, and
+// unwidened "exit < tMin" then rejects, for about one such ray in ten, a hit with tMin <= t (tests/test_gpu_ray_query_intervals.py set 2).
 __device__ __forceinline__ bool OwnBoxPassBox(V3 mn, V3 mx, V3 o, V3 inv /* exact 1/d */, float tMin, float t);
 __device__ __forceinline__ bool OwnBoxPass(V3 a, V3 b, V3 c, V3 o, V3 inv /* exact 1/d */, float tMin, float t)
 {
@@ -364,7 +369,11 @@ __device__ __forceinline__ bool OwnBoxPassBox(V3 mn, V3 mx, V3 o, V3 inv /* exac
 {
 	// (lo = t0 > lo ? t0 : lo and hi = t1 < hi ? t1 : hi -- a NaN keeps the old bound -- are fmaxf(lo, t0) and fminf(hi, t1), one v_max / v_min each
 	// instead of a compare and a select; the sign of a zero, the one thing the two forms may disagree on, plays no part in the comparisons below)
+#ifdef RL_TU_QUERY
+	float lo = -INFINITY, hi = FLT_MAX;   // the box alone; tMin joins below
+#else
 	float lo = tMin, hi = FLT_MAX;
+#endif
 	{ float t0 = (mn.x - o.x) * inv.x, t1 = (mx.x - o.x) * inv.x; if (inv.x < 0.0f) { const float q = t0; t0 = t1; t1 = q; } lo = fmaxf(lo, t0); hi = fminf(hi, t1); }
 	bool ok = !(hi < lo);
 	{ float t0 = (mn.y - o.y) * inv.y, t1 = (mx.y - o.y) * inv.y; if (inv.y < 0.0f) { const float q = t0; t0 = t1; t1 = q; } lo = fmaxf(lo, t0); hi = fminf(hi, t1); }
@@ -372,7 +381,12 @@ __device__ __forceinline__ bool OwnBoxPassBox(V3 mn, V3 mx, V3 o, V3 inv /* exac
 	{ float t0 = (mn.z - o.z) * inv.z, t1 = (mx.z - o.z) * inv.z; if (inv.z < 0.0f) { const float q = t0; t0 = t1; t1 = q; } lo = fmaxf(lo, t0); hi = fminf(hi, t1); }
 	// ... and the candidate's t must not lie before the ray enters that box (by more than the slack the box tests are
 	// widened by): then "this box starts beyond the best hit so far" implies "nothing in it is closer", whatever the order
+#ifdef RL_TU_QUERY
+	// (hi only falls and lo only rises from axis to axis, so "hi < max(tMin, entries)" at any axis is "hi < tMin at the end, or hi < the entries at that axis")
+	return ok && !(hi < lo) && !(hi * RL_BOX_WIDEN < tMin) && t * RL_CANDIDATE_SLACK >= fmaxf(lo, tMin);
+#else
 	return ok && !(hi < lo) && t * RL_CANDIDATE_SLACK >= lo;
+#endif
 }
 
 // Slab test of one child box against [tMin, tMax] (reference geom/aabb.h:39-54:

@@ -275,3 +275,51 @@ def assert_same_outside_ties(img, want, ties, what):
 
 def golden(name):
     return np.load(os.path.join(GOLDEN, name + ".npz"))
+
+
+# ---- ray-query intervals (tests/test_ray_query_host.py, tests/test_gpu_ray_query_intervals.py) -------------------------------------------
+F32_MAX = np.float32(3.4028235e38)
+F32_DENORM = np.float32(1e-45)          # the least positive denormal
+
+
+def nextup(x):
+    return np.nextafter(np.asarray(x, np.float32), np.float32(np.inf))
+
+
+def nextdown(x):
+    return np.nextafter(np.asarray(x, np.float32), np.float32(-np.inf))
+
+
+def rays8(o, d, tmin=1e-4, tmax=F32_MAX):
+    """n x (org, tMin, dir, tMax), the layout of RaylibAMDRay"""
+    d = np.asarray(d, np.float32)
+    r = np.zeros((len(d), 8), np.float32)
+    r[:, 0:3] = o; r[:, 3] = tmin; r[:, 4:7] = d; r[:, 7] = tmax
+    return r
+
+
+def with_interval(rays, tmin=None, tmax=None):
+    r = np.array(rays, np.float32, copy=True)
+    if tmin is not None:
+        r[:, 3] = tmin
+    if tmax is not None:
+        r[:, 7] = tmax
+    return r
+
+
+def peel(oracle, scene, rays, layers, tmin0=0.0, ray_time=0.0):
+    """The first `layers` surfaces of each ray by the brute-force oracle alone: layer k+1 is interval_hits over [nextup(t_k), FLT_MAX].
+    Returns (layers, n) float32, +inf from the layer at which a ray runs out of surfaces."""
+    n = len(rays)
+    T = np.full((layers, n), np.inf, np.float32)
+    lo = np.full(n, tmin0, np.float32)
+    alive = np.ones(n, bool)
+    for k in range(layers):
+        idx = np.nonzero(alive)[0]
+        if not len(idx):
+            break
+        got = oracle.interval_hits(scene, with_interval(rays[idx], lo[idx], F32_MAX), ray_time)
+        T[k, idx] = got["t"]
+        alive[idx] = np.isfinite(got["t"])
+        lo[idx] = nextup(got["t"])
+    return T
