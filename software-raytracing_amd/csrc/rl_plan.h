@@ -88,7 +88,8 @@ struct ViewsPlan {
 };
 ViewsPlan PlanViews(const CullScene& cs, const RendererSettings& st, const DCamera* cameras, uint32_t count, const TracePlan& trace,
                     int numCUs, int workgroupsPerCU, const RenderKnobs& knobs);
-// The scene's box as the device upload takes it (the root node's two child boxes, rl_runtime.inl UploadScene): a CullScene without a device
+// What CullCells needs to know of a finalized scene, for the runtime's renders and the planner hooks alike: its box (the root node's two child boxes; valid for
+// triangle scenes with finite coordinates) and its sun
 CullScene SceneCullScene(const Scene& sc, bool hasSky);
 
 } // namespace rl

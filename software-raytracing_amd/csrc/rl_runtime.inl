@@ -41,8 +41,6 @@ struct DeviceSceneCopy {
 struct DeviceScene {
 	std::vector<DeviceSceneCopy*> copy;   // by device slot (Runtime::devices)
 	SkyRot skyRot;
-	double boundsMin[3] = { 0, 0, 0 }, boundsMax[3] = { 0, 0, 0 };   // of all triangle vertices (CullCells)
-	bool boundsValid = false;                                        // triangles only, every coordinate finite
 	uint64_t serial = 0;                                             // 1, 2, 3, ... per upload in this process: a progressive session notices a scene uploaded anew
 };
 
@@ -481,21 +479,6 @@ bool UploadScene(Scene& sc)
 		D->skyRot.m1[0] = -ch * sb + sh * sp * cb; D->skyRot.m1[1] = cb * cp; D->skyRot.m1[2] = sb * sh + ch * sp * cb;
 		D->skyRot.m2[0] = sh * cp; D->skyRot.m2[1] = -sp; D->skyRot.m2[2] = ch * cp;
 	}
-	{   // the scene's bounding box: the root node's two child boxes (CullCells)
-		D->boundsValid = false;
-		if (sc.spheres.empty() && sc.cubes.empty() && !sc.bvh.nodes.empty() && n > 0) {
-			const DNode& root = sc.bvh.nodes[0];
-			bool ok = true;
-			for (int k = 0; k < 3; ++k) {
-				double lo = 1e300, hi = -1e300;
-				if (root.left != DNODE_EMPTY) { lo = std::min(lo, (double)root.lmin[k]); hi = std::max(hi, (double)root.lmax[k]); }
-				if (root.right != DNODE_EMPTY) { lo = std::min(lo, (double)root.rmin[k]); hi = std::max(hi, (double)root.rmax[k]); }
-				if (!(lo <= hi) || !std::isfinite(lo) || !std::isfinite(hi)) ok = false;
-				D->boundsMin[k] = lo; D->boundsMax[k] = hi;
-			}
-			D->boundsValid = ok;
-		}
-	}
 	// the float-box wide nodes (and the leaf list) for scenes small enough to stay in the caches (k_trace's class); of the two wide trees the pool schedule can walk, the
 	// one the default plan walks goes to the device now, the other follows when a render asks for it (EnsureWideTree: the switches are read per render).  A 10 M-triangle
 	// scene keeps 190 MB of nodes per device instead of 290.
@@ -562,272 +545,313 @@ bool SyncSky(Scene& sc)
 	return true;
 }
 
+// The kernels a render launches go by address (hipLaunchKernel): a one-view kernel and its views twin (RaylibAMD_RenderViews) differ by the twin's trailing DViews.
 typedef void (*TraceKernel)(const DRenderParams, const DSceneView, const SkyRot, SampleRGB*, float*, unsigned long long*, unsigned int*);
+typedef void (*TraceViewsKernel)(const DRenderParams, const DSceneView, const SkyRot, SampleRGB*, float*, unsigned long long*, unsigned int*, const DViews);
 typedef void (*AovKernel)(const DRenderParams, const DSceneView, float4*, unsigned long long*);
+typedef void (*AovViewsKernel)(const DRenderParams, const DSceneView, float4*, unsigned long long*, const DViews);
 
-// The kernel instance of a plan (rl_plan.cc): the only code that names the instances of k_trace, k_trace_pool and k_aov a render launches.
+// The kernel instance of a plan (rl_plan.cc), or its views twin: the only code that names the instances of k_trace, k_trace_pool and k_aov a render launches.
+// Every instance has its twin, so that a batch of views is never a loop of one-view launches.
+template <int STACK, bool PRIMS, bool FULL, int LDS = 0, bool PLAIN = false>
+static const void* Trace(bool views)
+{
+	return views ? (const void*)(TraceViewsKernel)k_trace_views<STACK, PRIMS, FULL, LDS, PLAIN> : (const void*)(TraceKernel)k_trace<STACK, PRIMS, FULL, LDS, PLAIN>;
+}
 template <int STACK, bool PRIMS>
-static TraceKernel TraceFor(bool floatBoxes) { return floatBoxes ? (TraceKernel)k_trace<STACK, PRIMS, true> : (TraceKernel)k_trace<STACK, PRIMS, false>; }
-static TraceKernel KernelFor(const TracePlan& p)
+static const void* TraceFor(bool floatBoxes, bool views) { return floatBoxes ? Trace<STACK, PRIMS, true>(views) : Trace<STACK, PRIMS, false>(views); }
+template <int STACK, bool PRIMS>
+static const void* Aov(bool views) { return views ? (const void*)(AovViewsKernel)k_aov_views<STACK, PRIMS> : (const void*)(AovKernel)k_aov<STACK, PRIMS>; }
+static const void* KernelFor(const TracePlan& p, bool views)
 {
 	if (p.poolK > 0) {   // the instances rl_render_pool.hip defines: (STACK, PRIMS, K, LSTACK, WIDE), WIDE 0 the BVH2, 1 the grid nodes, 3 the 8-wide tree
 		const int wide = p.tree == TREE_WIDE8 ? 3 : p.tree == TREE_GRID4 ? 1 : 0;
-#define RL_POOL_PICK(a, b, c, d, e) if (p.stack == a && p.prims == b && p.poolK == c && p.lstack == d && wide == e) return (TraceKernel)k_trace_pool<a, b, c, d, e>;
+#define RL_POOL_PICK(a, b, c, d, e) if (p.stack == a && p.prims == b && p.poolK == c && p.lstack == d && wide == e) \
+			return views ? (const void*)(TraceViewsKernel)k_trace_pool_views<a, b, c, d, e> : (const void*)(TraceKernel)k_trace_pool<a, b, c, d, e>;
 		RL_POOL_INSTANCES(RL_POOL_PICK)
 #undef RL_POOL_PICK
 		return nullptr;
 	}
-	if (p.lds == 2) return p.plain ? (TraceKernel)k_trace<16, false, true, 2, true> : (TraceKernel)k_trace<16, false, true, 2>;
-	if (p.lds == 1) return (TraceKernel)k_trace<16, false, true, 1>;
+	if (p.lds == 2) return p.plain ? Trace<16, false, true, 2, true>(views) : Trace<16, false, true, 2>(views);
+	if (p.lds == 1) return Trace<16, false, true, 1>(views);
 	const bool full = p.tree == TREE_BOX4;
-	if (p.stack == 16) return TraceFor<16, false>(full);
-	if (p.stack == 32) return p.prims ? TraceFor<32, true>(full) : TraceFor<32, false>(full);
-	return p.prims ? TraceFor<64, true>(full) : TraceFor<64, false>(full);
+	if (p.stack == 16) return TraceFor<16, false>(full, views);
+	if (p.stack == 32) return p.prims ? TraceFor<32, true>(full, views) : TraceFor<32, false>(full, views);
+	return p.prims ? TraceFor<64, true>(full, views) : TraceFor<64, false>(full, views);
 }
-static AovKernel AovKernelFor(const TracePlan& p)
+static const void* AovKernelFor(const TracePlan& p, bool views)
 {
-	if (p.stack == 16) return k_aov<16, false>;
-	if (p.stack == 32) return p.prims ? k_aov<32, true> : k_aov<32, false>;
-	return p.prims ? k_aov<64, true> : k_aov<64, false>;
-}
-// ... and their views twins (RaylibAMD_RenderViews): one for every instance above, so that a batch of views is never a loop of one-view launches
-typedef void (*TraceViewsKernel)(const DRenderParams, const DSceneView, const SkyRot, SampleRGB*, float*, unsigned long long*, unsigned int*, const DViews);
-typedef void (*AovViewsKernel)(const DRenderParams, const DSceneView, float4*, unsigned long long*, const DViews);
-template <int STACK, bool PRIMS>
-static TraceViewsKernel TraceViewsFor(bool floatBoxes) { return floatBoxes ? (TraceViewsKernel)k_trace_views<STACK, PRIMS, true> : (TraceViewsKernel)k_trace_views<STACK, PRIMS, false>; }
-static TraceViewsKernel ViewsKernelFor(const TracePlan& p)
-{
-	if (p.poolK > 0) {
-		const int wide = p.tree == TREE_WIDE8 ? 3 : p.tree == TREE_GRID4 ? 1 : 0;
-#define RL_POOL_PICK(a, b, c, d, e) if (p.stack == a && p.prims == b && p.poolK == c && p.lstack == d && wide == e) return (TraceViewsKernel)k_trace_pool_views<a, b, c, d, e>;
-		RL_POOL_INSTANCES(RL_POOL_PICK)
-#undef RL_POOL_PICK
-		return nullptr;
-	}
-	if (p.lds == 2) return p.plain ? (TraceViewsKernel)k_trace_views<16, false, true, 2, true> : (TraceViewsKernel)k_trace_views<16, false, true, 2>;
-	if (p.lds == 1) return (TraceViewsKernel)k_trace_views<16, false, true, 1>;
-	const bool full = p.tree == TREE_BOX4;
-	if (p.stack == 16) return TraceViewsFor<16, false>(full);
-	if (p.stack == 32) return p.prims ? TraceViewsFor<32, true>(full) : TraceViewsFor<32, false>(full);
-	return p.prims ? TraceViewsFor<64, true>(full) : TraceViewsFor<64, false>(full);
-}
-static AovViewsKernel AovViewsKernelFor(const TracePlan& p)
-{
-	if (p.stack == 16) return k_aov_views<16, false>;
-	if (p.stack == 32) return p.prims ? k_aov_views<32, true> : k_aov_views<32, false>;
-	return p.prims ? k_aov_views<64, true> : k_aov_views<64, false>;
+	if (p.stack == 16) return Aov<16, false>(views);
+	if (p.stack == 32) return p.prims ? Aov<32, true>(views) : Aov<32, false>(views);
+	return p.prims ? Aov<64, true>(views) : Aov<64, false>(views);
 }
 static std::atomic<int32_t> g_lastTracePlain{0};   // RaylibAMD_LastTracePlain
 
-// What EnqueueRender leaves for FinishRender: everything is queued on the rank's stream, nothing has been waited for.
+// What EnqueueFrame leaves for FinishRender: everything is queued on the rank's stream, nothing has been waited for.
 struct PendingRender {
-	RankCtx* ctx = nullptr;
 	bool pathTrace = false, lastBatchPending = false;
 	float traceMs = 0.0f;
 	uint32_t launches = 0, jobHeads = 0, pathsPerWave = 64, treeWidth = 2, nodeBytes = 64;   // (the last three: TracePlan's)
 	uint64_t pixels = 0;
 	uint64_t culledSamples = 0; uint32_t culledRaysPerSample = 0, culledSkyTexels = 0;   // camera samples of cells outside the scene's silhouette: reported apart, not traced (CullCells)
 	uint32_t culledCells = 0, listedCells = 0;
-	bool enqueuedToEnd = false;                // EnqueueRender reached the ev[slot][7] record (FinishRender waits for it; otherwise for the whole stream)
+	bool enqueuedToEnd = false;                // EnqueueFrame reached the ev[slot][7] record (FinishRender waits for it; otherwise for the whole stream)
 	float4* out = nullptr; size_t outBytes = 0;
 	int slot = 0;                              // frame slot: which of the rank's event sets / pinned counter buffers this render uses
-	const unsigned long long* cnt = nullptr;   // -> ctx->cntHost[slot], valid once ev[slot][7] has fired
+	const unsigned long long* cnt = nullptr;   // -> the rank's cntHost[slot], valid once ev[slot][7] has fired
 };
 
-// One rank's share of a render, queued on its stream: counters reset, the megakernel (or k_aov) per sample batch, k_resolve,
-// end event, counter read-back.  `req.outDevice` receives the row-major frame (cellStride 1) or the rank's cells back to back.
-// With `prog` (rank 0, the whole frame): one pass of a progressive session -- the samples [prog->samples, prog->passEnd) of its live cells, its lists in place
-// of the cull's (seeded from the cull at its first pass), k_progressive_resolve in place of k_resolve, and k_progressive_compact behind the last batch.
-bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRender& pend, ProgressiveSession* prog = nullptr)
+// What differs between the frames the runtime queues -- a rank's share of a one-view render, a pass of a progressive session, a batch of views (EnqueueRender,
+// DeviceRenderViews): they fill this in, EnqueueFrame queues what it says.
+struct Frame {
+	RenderKnobs knobs;                   // what the launches are planned with (a batch of views: ViewsPlan::knobs, whose sampleBatch may be lowered)
+	TracePlan plan;
+	DSceneView view;                     // TraceView
+	DRenderParams P;                     // BaseParams and the job list (ListCells); EnqueueFrame sets the per-launch fields
+	uint32_t numLive = 0, numActive = 0; // of P.numLocalCells cells: those still sampled, and those of them in the job list (ListCells; else all)
+	uint32_t sBegin = 0, sEnd = 1;       // the samples to render
+	float4* out = nullptr;
+	const DViews* views = nullptr;       // a batch of views: the twins are launched, with this as their trailing argument
+	// behind every batch: k_resolve, k_resolve_views or k_progressive_resolve as resolve(P, view, skyRot, the rank's samples, resolveArgs...)
+	const void* resolve = nullptr;
+	void* resolveArgs[5] = {};
+	int firstBatch = 0, lastBatch = 0;   // (of the batch being queued: what resolveArgs may point at)
+	bool accum = true;                   // the resolve sums the batches in the rank's accum buffer: grown when there is more than one
+	ProgressiveSession* compact = nullptr;   // behind the last batch: k_progressive_compact on the session's lists, and its counts to pinned memory
+};
+
+// DRenderParams as far as settings, seed and cell geometry decide them: the frame's cells cellFirst, cellFirst + stride, ..., numLocalCells of them
+static DRenderParams BaseParams(const RendererSettings& st, uint64_t seed, const DCamera& camera, uint32_t cellFirst, uint32_t stride, uint32_t numLocalCells, bool rowMajor)
 {
-	DeviceScene* DS = sc.device;
-	DeviceSceneCopy* D = DS->copy[(size_t)R.devSlot];
-	const RendererSettings& st = req.settings;
-	const RenderKnobs knobs = ReadRenderKnobs();
-	const TracePlan plan = PlanTrace(sc, st, D->view.sky != nullptr, knobs);
-	if (!plan.ok) return false;
-	const uint32_t W = st.viewportWidth, H = st.viewportHeight;
-	const uint32_t cellsX = (W + 7) / 8, cellsY = (H + 7) / 8, numCells = cellsX * cellsY;
-	const uint32_t stride = req.cellStride ? req.cellStride : 1;
-	const uint32_t numLocalCells = req.cellFirst < numCells ? (numCells - req.cellFirst + stride - 1) / stride : 0;
-	const uint32_t numSlots = numLocalCells * 64u;
-	const bool rowMajor = (stride == 1 && req.cellFirst == 0 && !req.cellMajor);
-	const uint32_t SPP = (uint32_t)(st.samplesPerPixel > 1 ? st.samplesPerPixel : 1);
-	const uint32_t sBegin = prog ? prog->samples : 0u, sEnd = prog ? prog->passEnd : SPP;   // the samples this call renders
-	const bool pathTrace = (st.renderMode == RAYLIB_RENDERMODE_Default);
-	pend.ctx = &R; pend.pathTrace = pathTrace;
-	const int q = req.slot & 1;
-	pend.slot = q; pend.cnt = R.cntHost[q];
-
 	DRenderParams P; memset(&P, 0, sizeof(P));
-	P.width = W; P.height = H; P.spp = SPP; P.maxPathLength = st.maxPathLength; P.rayTMin = st.rayTMin;
+	const uint32_t W = st.viewportWidth, H = st.viewportHeight, cellsX = (W + 7) / 8;
+	P.width = W; P.height = H; P.spp = (uint32_t)(st.samplesPerPixel > 1 ? st.samplesPerPixel : 1); P.maxPathLength = st.maxPathLength; P.rayTMin = st.rayTMin;
 	P.invWidth = 1.0f / (float)W; P.invHeight = 1.0f / (float)H;   // correctly rounded (IEEE division on the host): rl_render.hip PixelUV
-	P.renderMode = st.renderMode; P.seed = req.seed; P.cellsX = cellsX; P.cellsY = cellsY;
-	P.cellFirst = req.cellFirst; P.cellStride = stride; P.numLocalCells = numLocalCells;
-	P.rowMajorOutput = rowMajor ? 1u : 0u; P.camera = req.camera;
-	P.seedMixed = raylib_rng_mix64(req.seed);
+	P.renderMode = st.renderMode; P.seed = seed; P.cellsX = cellsX; P.cellsY = (H + 7) / 8;
+	P.cellFirst = cellFirst; P.cellStride = stride; P.numLocalCells = numLocalCells;
+	P.rowMajorOutput = rowMajor ? 1u : 0u; P.camera = camera;
+	P.seedMixed = raylib_rng_mix64(seed);
 	P.magicCellsX = cellsX > 1 ? (uint32_t)(0x100000000ull / cellsX) : 0xFFFFFFFFu;
+	return P;
+}
 
-	const size_t outBytes = rowMajor ? (size_t)W * H * sizeof(float4) : (size_t)numSlots * sizeof(float4);
-	float4* out = (float4*)req.outDevice;
-	if (!out) { if (!Grow(R.image, R.imageBytes, outBytes ? outBytes : 16)) return false; out = R.image; }
-	pend.out = out; pend.outBytes = outBytes;
+// the valid pixels of the cells cellFirst, cellFirst + stride, ... (count of them) of a W x H frame
+static uint64_t CoveredPixels(uint32_t W, uint32_t H, uint32_t cellFirst, uint32_t stride, uint32_t count)
+{
+	const uint32_t cellsX = (W + 7) / 8;
+	uint64_t px = 0;
+	for (uint32_t k = 0; k < count; ++k) {
+		const uint32_t cell = cellFirst + k * stride, cx = cell % cellsX, cy = cell / cellsX;
+		px += (uint64_t)std::min(8u, W - cx * 8) * std::min(8u, H - cy * 8);
+	}
+	return px;
+}
 
+// the scene as a plan's kernels read it: the plan's wide tree is on the device (EnsureWideTree), the wide nodes it does not walk are out of the view (k_trace tells the tree
+// by which is set; a debug mode's plan keeps both)
+static bool TraceView(DeviceSceneCopy* D, const Scene& sc, const TracePlan& plan, DSceneView& view)
+{
+	if (!EnsureWideTree(D, sc, plan.tree)) return false;
+	view = D->view;
+	if (!plan.keepNodes4) view.nodes4 = nullptr;
+	if (!plan.keepNodes4f) view.nodes4f = nullptr;
+	return true;
+}
+
+// workgroups of `kernel` a CU holds, asked once per kernel and rank; -1: the query failed (logged).  RAYLIB_PRINT_OCCUPANCY: a megakernel's first answer is logged.
+static int OccupancyOf(RankCtx& R, const void* kernel, const TracePlan* megakernel = nullptr)
+{
+	auto it = R.occupancy.find(kernel);
+	if (it != R.occupancy.end()) return it->second;
+	int blocksPerCU = 0;
+	const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, kernel, RL_BLOCK, 0);
+	if (e != hipSuccess) { Log("HIP error %s: hipOccupancyMaxActiveBlocksPerMultiprocessor", hipGetErrorName(e)); return -1; }
+	R.occupancy[kernel] = blocksPerCU;
+	if (megakernel && getenv("RAYLIB_PRINT_OCCUPANCY")) Log("megakernel (%u paths per lane, tree width %u): %d workgroups per CU", megakernel->pathsPerWave / 64u, megakernel->treeWidth, blocksPerCU);
+	return blocksPerCU;
+}
+
+// The frame's job list (device memory): numListed of its numLive live cells, ascending, and a flag per cell for those outside the scene's silhouette, whose samples are
+// the constant L (plus their sky texel) and stand for emptyPixels pixels and raysPerSample rays each in the counters (CullCells).
+static void ListCells(Frame& F, PendingRender& pend, const uint32_t* list, const uint8_t* empty, uint32_t numListed, uint32_t numLive, const float* L, uint64_t emptyPixels, uint32_t raysPerSample)
+{
+	DRenderParams& P = F.P;
+	F.numLive = numLive; F.numActive = numListed;
+	P.activeCells = list; P.cellEmpty = empty; P.numActiveCells = numListed;
+	P.emptyL[0] = L[0]; P.emptyL[1] = L[1]; P.emptyL[2] = L[2];
+	P.emptySky = F.view.sky ? 1u : 0u;
+	pend.culledSamples = emptyPixels * (uint64_t)(F.sEnd - F.sBegin); pend.culledRaysPerSample = raysPerSample; pend.culledSkyTexels = F.view.sky ? 1u : 0u;
+}
+
+// The head of every frame on the rank's stream: the counters reset and the start event of frame slot q.
+static bool BeginFrame(RankCtx& R, int q, const Frame& F, size_t outBytes, PendingRender& pend)
+{
+	pend.pathTrace = F.plan.pathTrace; pend.slot = q; pend.cnt = R.cntHost[q];
+	pend.out = F.out; pend.outBytes = outBytes;
 	HIP_OK(hipMemsetAsync(R.counters, 0, (CNT_COUNT + 24 + RL_TIMELINE_SLOTS) * sizeof(unsigned long long), R.stream));
 	HIP_OK(hipEventRecord(R.ev[q][0], R.stream));
+	return true;
+}
+
+// The rest of the frame behind BeginFrame, queued and not waited for: the megakernel and the resolve per sample batch (or k_aov), what follows the last batch, the end
+// event and the counter read-back.  False (a HIP call failed, logged) leaves pend.enqueuedToEnd unset: FinishRender then drains the stream.
+static bool EnqueueFrame(RankCtx& R, int q, const DeviceScene& DS, Frame& F, PendingRender& pend)
+{
+	const TracePlan& plan = F.plan;
+	DRenderParams& P = F.P;
+	const uint32_t numCells = P.numLocalCells, numSlots = numCells * 64u;
+	const uint32_t rblocks = (numSlots + RL_BLOCK - 1) / RL_BLOCK;   // one thread per pixel slot: k_aov and the resolves
+	SkyRot skyRot = DS.skyRot;
 	if (numSlots == 0) {
 		// nothing to do for this rank
-	} else if (!pathTrace) {
-		const uint32_t blocks = (numSlots + RL_BLOCK - 1) / RL_BLOCK;
-		hipLaunchKernelGGL(AovKernelFor(plan), dim3(blocks), dim3(RL_BLOCK), 0, R.stream, P, D->view, out, R.counters);
-		HIP_OK(hipGetLastError());
+	} else if (!plan.pathTrace) {
+		void* args[] = { &P, &F.view, &F.out, &R.counters, (void*)F.views };
+		HIP_OK(hipLaunchKernel(AovKernelFor(plan, F.views != nullptr), dim3(rblocks), dim3(RL_BLOCK), args, 0, R.stream));
 	} else {
-		const TraceKernel traceKernel = KernelFor(plan);
+		const void* traceKernel = KernelFor(plan, F.views != nullptr);
 		if (!traceKernel) { Log("Raylib_Render: no megakernel instance for STACK %d, K %d, stack in LDS %d", plan.stack, plan.poolK, plan.lstack); return false; }
-		if (!EnsureWideTree(D, sc, plan.tree)) return false;
-		DSceneView traceView = D->view;
-		if (!plan.keepNodes4) traceView.nodes4 = nullptr;
-		if (!plan.keepNodes4f) traceView.nodes4f = nullptr;
+		const int blocksPerCU = OccupancyOf(R, traceKernel, &plan);
+		if (blocksPerCU < 0) return false;
 		g_lastTracePlain.store(plan.plain ? 1 : 0, std::memory_order_relaxed);
 		pend.pathsPerWave = plan.pathsPerWave; pend.treeWidth = plan.treeWidth; pend.nodeBytes = plan.nodeBytes;
-		// ---- cells that cannot see the scene leave the job list (CullCells) ----
-		uint32_t numActive = numLocalCells;
-		if (!prog || !prog->seeded) {
-			// what the decision depends on: an unchanged view keeps the lists the slot already holds on the device
-			std::vector<unsigned char> key;
-			auto put = [&](const void* ptr, size_t n) { const unsigned char* b = (const unsigned char*)ptr; key.insert(key.end(), b, b + n); };
-			const uint32_t geo[7] = { W, H, req.cellFirst, stride, numLocalCells, (uint32_t)st.maxPathLength, __builtin_bit_cast(uint32_t, st.rayTMin) };
-			const int flags[3] = { traceView.sky ? 1 : 0, traceView.hasSun, knobs.cullCells };
-			put(&req.camera, sizeof(req.camera)); put(geo, sizeof(geo)); put(flags, sizeof(flags)); put(traceView.sunDirection, sizeof(traceView.sunDirection));
-			put(traceView.sunIlluminance, sizeof(traceView.sunIlluminance)); put(DS->boundsMin, sizeof(DS->boundsMin)); put(DS->boundsMax, sizeof(DS->boundsMax));
-			const void* sceneId = DS; put(&sceneId, sizeof(sceneId));
-			if (key != R.cullKey[q]) {
-				CullResult cr;
-				CullScene cs;
-				for (int k = 0; k < 3; ++k) { cs.boundsMin[k] = DS->boundsMin[k]; cs.boundsMax[k] = DS->boundsMax[k]; cs.sunDirection[k] = traceView.sunDirection[k]; cs.sunIlluminance[k] = traceView.sunIlluminance[k]; }
-				cs.boundsValid = DS->boundsValid; cs.prims = plan.prims; cs.hasSky = traceView.sky != nullptr; cs.hasSun = traceView.hasSun != 0;
-				const bool culled = CullCells(cs, req.camera, st.maxPathLength, st.rayTMin, W, H, cellsX, req.cellFirst, stride, numLocalCells, cr);
-				R.cullKey[q].clear();   // (valid again once the slot's buffers hold this view)
-				R.cullActive[q] = numLocalCells; R.cullEmptyPixels[q] = 0;
-				if (culled) {
-					if (R.cellListCells[q] < numLocalCells) {
-						if (R.cellListHost[q]) { (void)hipHostFree(R.cellListHost[q]); R.cellListHost[q] = nullptr; }
-						if (R.cellList[q]) { (void)hipFree(R.cellList[q]); R.cellList[q] = nullptr; }
-						R.cellListCells[q] = 0;
-						// the list (uint32 per cell) and the flags (one byte per cell, behind it) in one buffer
-						HIP_OK(hipHostMalloc((void**)&R.cellListHost[q], (size_t)numLocalCells * 5 + 16, hipHostMallocDefault));
-						HIP_OK(hipMalloc((void**)&R.cellList[q], (size_t)numLocalCells * 5 + 16));
-						R.cellListCells[q] = numLocalCells;
-					}
-					// (the slot's staging buffer is free: the frame that used it last has been waited for -- FinishRender, or FinishInflight before a slot is re-used)
-					memcpy(R.cellListHost[q], cr.active.data(), cr.active.size() * sizeof(uint32_t));
-					memcpy((unsigned char*)(R.cellListHost[q] + R.cellListCells[q]), cr.empty.data(), numLocalCells);
-					HIP_OK(hipMemcpyAsync(R.cellList[q], R.cellListHost[q], (size_t)R.cellListCells[q] * 5, hipMemcpyHostToDevice, R.stream));
-					R.cullActive[q] = (uint32_t)cr.active.size(); R.cullEmptyPixels[q] = cr.emptyPixels;
-					R.cullL[q][0] = cr.L[0]; R.cullL[q][1] = cr.L[1]; R.cullL[q][2] = cr.L[2]; R.cullRays[q] = cr.raysPerSample;
-				}
-				R.cullKey[q] = key;
-			}
-			if (R.cullActive[q] < numLocalCells) {
-				numActive = R.cullActive[q];
-				P.activeCells = R.cellList[q]; P.cellEmpty = (const uint8_t*)(R.cellList[q] + R.cellListCells[q]); P.numActiveCells = numActive;
-				P.emptyL[0] = R.cullL[q][0]; P.emptyL[1] = R.cullL[q][1]; P.emptyL[2] = R.cullL[q][2];
-				P.emptySky = traceView.sky ? 1u : 0u;
-				pend.culledSamples = R.cullEmptyPixels[q] * (uint64_t)SPP; pend.culledRaysPerSample = R.cullRays[q]; pend.culledSkyTexels = traceView.sky ? 1u : 0u;
-			}
-			pend.culledCells = numLocalCells - numActive; pend.listedCells = numActive;
-		}
-		if (prog) {
-			if (!prog->seeded) {   // the session's first pass: its lists start from the cull's (every cell is live)
-				if (numActive < numLocalCells) {
-					HIP_OK(hipMemcpyAsync(prog->trace, R.cellList[q], (size_t)numActive * sizeof(uint32_t), hipMemcpyDeviceToDevice, R.stream));
-					HIP_OK(hipMemcpyAsync(prog->empty, R.cellList[q] + R.cellListCells[q], numLocalCells, hipMemcpyDeviceToDevice, R.stream));
-					prog->emptyLivePixels = R.cullEmptyPixels[q]; prog->culledRays = R.cullRays[q];
-					for (int k = 0; k < 3; ++k) prog->emptyL[k] = R.cullL[q][k];
-				}
-				prog->numLive = numLocalCells; prog->numTrace = numActive;
-				prog->seeded = true;
-			}
-			numActive = prog->numTrace;
-			P.activeCells = prog->trace; P.cellEmpty = prog->empty; P.numActiveCells = numActive;
-			P.emptyL[0] = prog->emptyL[0]; P.emptyL[1] = prog->emptyL[1]; P.emptyL[2] = prog->emptyL[2];
-			P.emptySky = traceView.sky ? 1u : 0u;
-			pend.culledSamples = prog->emptyLivePixels * (uint64_t)(sEnd - sBegin); pend.culledRaysPerSample = prog->culledRays; pend.culledSkyTexels = traceView.sky ? 1u : 0u;
-			pend.culledCells = prog->numLive - prog->numTrace; pend.listedCells = prog->numTrace;
-		}
-		int blocksPerCU = 0;
-		{
-			auto it = R.occupancy.find((const void*)traceKernel);
-			if (it == R.occupancy.end()) {
-				HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, traceKernel, RL_BLOCK, 0));
-				R.occupancy[(const void*)traceKernel] = blocksPerCU;
-				if (getenv("RAYLIB_PRINT_OCCUPANCY")) Log("megakernel (%u paths per lane, tree width %u): %d workgroups per CU", plan.pathsPerWave / 64u, plan.treeWidth, blocksPerCU);
-			} else blocksPerCU = it->second;
-		}
-		const uint32_t batch = PlanLaunch(numLocalCells, numActive, sEnd, sBegin, R.numCUs, blocksPerCU, plan, knobs).batch;
-		if (!Grow(R.samples, R.samplesBytes, (size_t)numSlots * sizeof(SampleRGB) * std::min(batch, sEnd - sBegin))) return false;
-		if (!prog && batch < SPP && !Grow(R.accum, R.accumBytes, (size_t)numSlots * sizeof(float4))) return false;
-		const int depthSlots = st.maxPathLength > 1 ? st.maxPathLength : 1;
-		for (uint32_t s0 = sBegin; s0 < sEnd; s0 += batch) {
-			const LaunchPlan L = PlanLaunch(numLocalCells, numActive, sEnd, s0, R.numCUs, blocksPerCU, plan, knobs);
+		pend.culledCells = F.numLive - F.numActive; pend.listedCells = F.numActive;
+		const uint32_t batch = PlanLaunch(numCells, F.numActive, F.sEnd, F.sBegin, R.numCUs, blocksPerCU, plan, F.knobs).batch;
+		if (!Grow(R.samples, R.samplesBytes, (size_t)numSlots * sizeof(SampleRGB) * std::min(batch, F.sEnd - F.sBegin))) return false;
+		if (F.accum && batch < P.spp && !Grow(R.accum, R.accumBytes, (size_t)numSlots * sizeof(float4))) return false;
+		const int depthSlots = P.maxPathLength > 1 ? P.maxPathLength : 1;
+		void* traceArgs[] = { &P, &F.view, &skyRot, &R.samples, &R.pathStack, &R.counters, &R.jobCounter, (void*)F.views };
+		void* resolveArgs[] = { &P, &F.view, &skyRot, &R.samples, F.resolveArgs[0], F.resolveArgs[1], F.resolveArgs[2], F.resolveArgs[3], F.resolveArgs[4] };
+		for (uint32_t s0 = F.sBegin; s0 < F.sEnd; s0 += batch) {
+			const LaunchPlan L = PlanLaunch(numCells, F.numActive, F.sEnd, s0, R.numCUs, blocksPerCU, plan, F.knobs);
 			const uint32_t cnt = L.sampleCount;
 			P.sampleBegin = s0; P.sampleCount = cnt;
 			P.magicSamples = cnt > 1 ? (uint32_t)(0x100000000ull / cnt) : 0xFFFFFFFFu;
 			if (L.jobs > 0xF0000000ull) { Log("Raylib_Render: job count overflow"); return false; }   // (a head overshoots its band by one chunk per wave and attempt)
 			P.numJobs = (uint32_t)L.jobs;
-			const uint32_t blocks = L.blocks;
 			P.stackStride = L.stackStride; P.jobChunk = L.jobChunk;
 			P.numHeads = L.heads; P.jobsPerHead = L.jobsPerHead; P.guideShift = L.guideShift;
 			if (!Grow(R.pathStack, R.pathStackBytes, (size_t)depthSlots * 8 * P.stackStride * sizeof(float))) return false;
 			pend.jobHeads = L.heads;
+			F.firstBatch = s0 == F.sBegin; F.lastBatch = s0 + cnt >= F.sEnd;
 			HIP_OK(hipMemsetAsync(R.jobCounter, 0, RL_MAX_HEADS * RL_HEAD_STRIDE * sizeof(unsigned int), R.stream));   // heads count from their band's first job: one memset
 			HIP_OK(hipEventRecord(R.ev[q][2], R.stream));
-			if (L.jobs > 0) {   // (no cell of this rank sees the scene: k_resolve has all it needs)
-				hipLaunchKernelGGL(traceKernel, dim3(blocks), dim3(RL_BLOCK), 0, R.stream,
-				                   P, traceView, DS->skyRot, R.samples, R.pathStack, R.counters, R.jobCounter);
-				HIP_OK(hipGetLastError());
-			}
+			if (L.jobs > 0)   // (else no cell of this frame sees the scene: the resolve has all it needs)
+				HIP_OK(hipLaunchKernel(traceKernel, dim3(L.blocks), dim3(RL_BLOCK), traceArgs, 0, R.stream));
 			HIP_OK(hipEventRecord(R.ev[q][3], R.stream));
-			const uint32_t rblocks = (numSlots + RL_BLOCK - 1) / RL_BLOCK;
-			if (prog) hipLaunchKernelGGL(k_progressive_resolve, dim3(rblocks), dim3(RL_BLOCK), 0, R.stream,
-			                             P, traceView, DS->skyRot, R.samples, prog->st, out, (int)(s0 + cnt >= sEnd));
-			else hipLaunchKernelGGL(k_resolve, dim3(rblocks), dim3(RL_BLOCK), 0, R.stream,
-			                        P, traceView, DS->skyRot, R.samples, R.accum, out, (int)(s0 == 0), (int)(s0 + cnt >= SPP));
-			HIP_OK(hipGetLastError());
+			HIP_OK(hipLaunchKernel(F.resolve, dim3(rblocks), dim3(RL_BLOCK), resolveArgs, 0, R.stream));
 			++pend.launches;
-			if (s0 + cnt < sEnd) {   // the event pair is reused by the next batch; the last batch's pair is read after the one final sync
+			if (!F.lastBatch) {   // the event pair is reused by the next batch; the last batch's pair is read after the one final sync
 				HIP_OK(hipEventSynchronize(R.ev[q][3]));
 				float ms = 0.0f;
 				HIP_OK(hipEventElapsedTime(&ms, R.ev[q][2], R.ev[q][3]));
 				pend.traceMs += ms;
 			} else pend.lastBatchPending = true;
 		}
-		if (prog) {   // the cells that stopped leave the lists; the counts go to pinned memory, where the session reads them once the pass is waited for
+		if (ProgressiveSession* S = F.compact) {   // the cells that stopped leave the lists; the counts go to pinned memory, where the session reads them once the pass is waited for
 			hipLaunchKernelGGL(k_progressive_compact, dim3(1), dim3(RL_COMPACT_BLOCK), 0, R.stream,
-			                   prog->live, prog->trace, (const uint8_t*)prog->st.stopped, (const uint8_t*)prog->empty, prog->numLive, W, H, cellsX, prog->counts);
+			                   S->live, S->trace, (const uint8_t*)S->st.stopped, (const uint8_t*)S->empty, S->numLive, P.width, P.height, P.cellsX, S->counts);
 			HIP_OK(hipGetLastError());
-			HIP_OK(hipMemcpyAsync(prog->countsHost, prog->counts, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, R.stream));
+			HIP_OK(hipMemcpyAsync(S->countsHost, S->counts, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, R.stream));
 		}
 	}
+	if (!plan.pathTrace) pend.listedCells = numCells;
 	HIP_OK(hipEventRecord(R.ev[q][1], R.stream));
 	HIP_OK(hipMemcpyAsync(R.cntHost[q], R.counters, (CNT_COUNT + 24) * sizeof(unsigned long long), hipMemcpyDeviceToHost, R.stream));
 	HIP_OK(hipEventRecord(R.ev[q][7], R.stream));
 	pend.enqueuedToEnd = true;
-	uint64_t px = 0;
-	for (uint32_t k = 0; k < numLocalCells; ++k) {
-		const uint32_t cell = req.cellFirst + k * stride, cx = cell % cellsX, cy = cell / cellsX;
-		px += (uint64_t)std::min(8u, W - cx * 8) * std::min(8u, H - cy * 8);
+	return true;
+}
+
+// One rank's share of a one-view render, queued on its stream (BeginFrame, EnqueueFrame).  `req.outDevice` receives the row-major frame (cellStride 1) or the rank's cells
+// back to back.  The job list is the cull's, cached per frame slot.
+// With `prog` (rank 0, the whole frame): one pass of a progressive session -- the samples [prog->samples, prog->passEnd) of its live cells, its lists in place
+// of the cull's (seeded from the cull at its first pass), k_progressive_resolve in place of k_resolve, and k_progressive_compact behind the last batch.
+bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRender& pend, ProgressiveSession* prog = nullptr)
+{
+	DeviceSceneCopy* D = sc.device->copy[(size_t)R.devSlot];
+	const RendererSettings& st = req.settings;
+	Frame F;
+	F.knobs = ReadRenderKnobs();
+	F.plan = PlanTrace(sc, st, D->view.sky != nullptr, F.knobs);
+	if (!F.plan.ok || !TraceView(D, sc, F.plan, F.view)) return false;
+	const uint32_t W = st.viewportWidth, H = st.viewportHeight;
+	const uint32_t cellsX = (W + 7) / 8, numCells = cellsX * ((H + 7) / 8);
+	const uint32_t stride = req.cellStride ? req.cellStride : 1;
+	const uint32_t numLocalCells = req.cellFirst < numCells ? (numCells - req.cellFirst + stride - 1) / stride : 0;
+	const bool rowMajor = (stride == 1 && req.cellFirst == 0 && !req.cellMajor);
+	const int q = req.slot & 1;
+	F.P = BaseParams(st, req.seed, req.camera, req.cellFirst, stride, numLocalCells, rowMajor);
+	F.numLive = F.numActive = numLocalCells;
+	F.sBegin = prog ? prog->samples : 0u; F.sEnd = prog ? prog->passEnd : F.P.spp;
+	const size_t outBytes = rowMajor ? (size_t)W * H * sizeof(float4) : (size_t)numLocalCells * 64u * sizeof(float4);
+	F.out = (float4*)req.outDevice;
+	if (!F.out) { if (!Grow(R.image, R.imageBytes, outBytes ? outBytes : 16)) return false; F.out = R.image; }
+	if (!BeginFrame(R, q, F, outBytes, pend)) return false;
+	if (F.plan.pathTrace && numLocalCells && (!prog || !prog->seeded)) {
+		// ---- cells that cannot see the scene leave the job list (CullCells) ----
+		// what the decision depends on: an unchanged view keeps the lists the slot already holds on the device
+		const CullScene cs = SceneCullScene(sc, F.view.sky != nullptr);
+		std::vector<unsigned char> key;
+		auto put = [&](const void* ptr, size_t n) { const unsigned char* b = (const unsigned char*)ptr; key.insert(key.end(), b, b + n); };
+		const uint32_t geo[7] = { W, H, req.cellFirst, stride, numLocalCells, (uint32_t)st.maxPathLength, __builtin_bit_cast(uint32_t, st.rayTMin) };
+		const int flags[3] = { cs.hasSky ? 1 : 0, cs.hasSun ? 1 : 0, F.knobs.cullCells };
+		put(&req.camera, sizeof(req.camera)); put(geo, sizeof(geo)); put(flags, sizeof(flags)); put(cs.sunDirection, sizeof(cs.sunDirection));
+		put(cs.sunIlluminance, sizeof(cs.sunIlluminance)); put(cs.boundsMin, sizeof(cs.boundsMin)); put(cs.boundsMax, sizeof(cs.boundsMax));
+		const void* sceneId = sc.device; put(&sceneId, sizeof(sceneId));
+		if (key != R.cullKey[q]) {
+			CullResult cr;
+			const bool culled = CullCells(cs, req.camera, st.maxPathLength, st.rayTMin, W, H, cellsX, req.cellFirst, stride, numLocalCells, cr);
+			R.cullKey[q].clear();   // (valid again once the slot's buffers hold this view)
+			R.cullActive[q] = numLocalCells; R.cullEmptyPixels[q] = 0;
+			if (culled) {
+				if (R.cellListCells[q] < numLocalCells) {
+					if (R.cellListHost[q]) { (void)hipHostFree(R.cellListHost[q]); R.cellListHost[q] = nullptr; }
+					if (R.cellList[q]) { (void)hipFree(R.cellList[q]); R.cellList[q] = nullptr; }
+					R.cellListCells[q] = 0;
+					// the list (uint32 per cell) and the flags (one byte per cell, behind it) in one buffer
+					HIP_OK(hipHostMalloc((void**)&R.cellListHost[q], (size_t)numLocalCells * 5 + 16, hipHostMallocDefault));
+					HIP_OK(hipMalloc((void**)&R.cellList[q], (size_t)numLocalCells * 5 + 16));
+					R.cellListCells[q] = numLocalCells;
+				}
+				// (the slot's staging buffer is free: the frame that used it last has been waited for -- FinishRender, or FinishInflight before a slot is re-used)
+				memcpy(R.cellListHost[q], cr.active.data(), cr.active.size() * sizeof(uint32_t));
+				memcpy((unsigned char*)(R.cellListHost[q] + R.cellListCells[q]), cr.empty.data(), numLocalCells);
+				HIP_OK(hipMemcpyAsync(R.cellList[q], R.cellListHost[q], (size_t)R.cellListCells[q] * 5, hipMemcpyHostToDevice, R.stream));
+				R.cullActive[q] = (uint32_t)cr.active.size(); R.cullEmptyPixels[q] = cr.emptyPixels;
+				R.cullL[q][0] = cr.L[0]; R.cullL[q][1] = cr.L[1]; R.cullL[q][2] = cr.L[2]; R.cullRays[q] = cr.raysPerSample;
+			}
+			R.cullKey[q] = key;
+		}
+		const uint32_t* list = R.cellList[q]; const uint8_t* empty = (const uint8_t*)(R.cellList[q] + R.cellListCells[q]);
+		if (!prog) {
+			if (R.cullActive[q] < numLocalCells) ListCells(F, pend, list, empty, R.cullActive[q], numLocalCells, R.cullL[q], R.cullEmptyPixels[q], R.cullRays[q]);
+		} else {   // the session's first pass: its lists start from the cull's (every cell is live)
+			if (R.cullActive[q] < numLocalCells) {
+				HIP_OK(hipMemcpyAsync(prog->trace, list, (size_t)R.cullActive[q] * sizeof(uint32_t), hipMemcpyDeviceToDevice, R.stream));
+				HIP_OK(hipMemcpyAsync(prog->empty, empty, numLocalCells, hipMemcpyDeviceToDevice, R.stream));
+				prog->emptyLivePixels = R.cullEmptyPixels[q]; prog->culledRays = R.cullRays[q];
+				for (int k = 0; k < 3; ++k) prog->emptyL[k] = R.cullL[q][k];
+			}
+			prog->numLive = numLocalCells; prog->numTrace = R.cullActive[q];
+			prog->seeded = true;
+		}
 	}
-	pend.pixels = px;
-	if (!pathTrace) pend.listedCells = numLocalCells;
+	if (prog) {
+		if (F.plan.pathTrace && numLocalCells) ListCells(F, pend, prog->trace, prog->empty, prog->numTrace, prog->numLive, prog->emptyL, prog->emptyLivePixels, prog->culledRays);
+		F.resolve = (const void*)k_progressive_resolve; F.resolveArgs[0] = &prog->st; F.resolveArgs[1] = &F.out; F.resolveArgs[2] = &F.lastBatch;
+		F.accum = false; F.compact = prog;
+	} else {
+		F.resolve = (const void*)k_resolve; F.resolveArgs[0] = &R.accum; F.resolveArgs[1] = &F.out; F.resolveArgs[2] = &F.firstBatch; F.resolveArgs[3] = &F.lastBatch;
+	}
+	if (!EnqueueFrame(R, q, *sc.device, F, pend)) return false;
+	pend.pixels = CoveredPixels(W, H, req.cellFirst, stride, numLocalCells);   // (counted while the device works)
 	return true;
 }
 
 // The one host synchronisation of a rank's render, then its numbers.  Adds to `stats` (counters are summed over ranks, times
 // are the slowest rank's).
-bool FinishRender(PendingRender& pend, RaylibAMDStats& stats)
+bool FinishRender(RankCtx& R, PendingRender& pend, RaylibAMDStats& stats)
 {
-	RankCtx& R = *pend.ctx;
 	const int q = pend.slot;
 	HIP_OK(hipSetDevice(R.device));
 	if (!pend.enqueuedToEnd) {
@@ -935,8 +959,7 @@ bool FinishInflight(int slot)
 	RankCtx& R0 = Rank0();
 	bool ok = F->ok;
 	for (int r = (int)F->pend.size() - 1; r >= 0; --r) {
-		if (F->pend[(size_t)r].ctx) ok = FinishRender(F->pend[(size_t)r], F->stats) && ok;
-		else { (void)hipSetDevice(R.ranks[(size_t)r]->device); (void)hipStreamSynchronize(R.ranks[(size_t)r]->stream); }
+		ok = FinishRender(*R.ranks[(size_t)r], F->pend[(size_t)r], F->stats) && ok;   // (a rank whose enqueue failed: its stream is drained)
 	}
 	(void)hipSetDevice(R0.device);
 	if (F->timed) {
@@ -1124,8 +1147,7 @@ bool DeviceRender(Scene& sc, const RenderRequest& req, RaylibAMDStats& stats)
 		PendingRender pend;
 		ok = EnqueueRender(Rank0(), sc, req, pend);
 		if (ok && req.outHostRGBA) HIP_OK(hipMemcpyAsync(req.outHostRGBA, pend.out, pend.outBytes, hipMemcpyDeviceToHost, Rank0().stream));
-		if (pend.ctx) ok = FinishRender(pend, stats) && ok;
-		else (void)hipStreamSynchronize(Rank0().stream);
+		ok = FinishRender(Rank0(), pend, stats) && ok;
 		stats.ranks = 1; stats.devices = 1;
 	}
 	stats.numNodes = (uint32_t)sc.bvh.nodes.size(); stats.numTriangles = (uint32_t)sc.triangles.size(); stats.bvhDepth = sc.bvh.depth;
@@ -1158,54 +1180,33 @@ bool DeviceRenderViews(Scene& sc, const RenderRequest& req, const DCamera* camer
 	if (!UploadScene(sc) || !SyncSky(sc)) return false;
 	(void)DrainLocked();            // rank 0's slot-0 events, counter block and work buffers
 	g_deferredUnreported = false;   // (the numbers the caller reads next are this batch's)
-	DeviceScene* DS = sc.device;
-	DeviceSceneCopy* D = DS->copy[(size_t)R.devSlot];
+	DeviceSceneCopy* D = sc.device->copy[(size_t)R.devSlot];
 	const RendererSettings& st = req.settings;
-	const RenderKnobs knobs = ReadRenderKnobs();
-	const TracePlan plan = PlanTrace(sc, st, D->view.sky != nullptr, knobs);
-	if (!plan.ok) return false;
+	Frame F;
+	F.knobs = ReadRenderKnobs();
+	F.plan = PlanTrace(sc, st, D->view.sky != nullptr, F.knobs);
+	if (!F.plan.ok || !TraceView(D, sc, F.plan, F.view)) return false;
 	const uint32_t W = st.viewportWidth, H = st.viewportHeight;
-	const uint32_t cellsX = (W + 7) / 8, cellsY = (H + 7) / 8, cellsPerView = cellsX * cellsY, numCells = cellsPerView * count;
-	const uint32_t numSlots = numCells * 64u;
-	const uint32_t SPP = (uint32_t)(st.samplesPerPixel > 1 ? st.samplesPerPixel : 1);
-	const bool pathTrace = (st.renderMode == RAYLIB_RENDERMODE_Default);
+	const uint32_t cellsPerView = ((W + 7) / 8) * ((H + 7) / 8), numCells = cellsPerView * count;
 	const size_t viewBytes = (size_t)W * H * sizeof(float4);
+	F.P = BaseParams(st, req.seed, cameras[0], 0, 1, numCells, false);   // (the twins read every view's camera from the table)
+	F.numLive = F.numActive = numCells;
+	F.sEnd = F.P.spp;
 
-	DRenderParams P; memset(&P, 0, sizeof(P));
-	P.width = W; P.height = H; P.spp = SPP; P.maxPathLength = st.maxPathLength; P.rayTMin = st.rayTMin;
-	P.invWidth = 1.0f / (float)W; P.invHeight = 1.0f / (float)H;
-	P.renderMode = st.renderMode; P.seed = req.seed; P.cellsX = cellsX; P.cellsY = cellsY;
-	P.cellFirst = 0; P.cellStride = 1; P.numLocalCells = numCells;
-	P.rowMajorOutput = 0; P.camera = cameras[0];   // (the twins read every view's camera from the table)
-	P.seedMixed = raylib_rng_mix64(req.seed);
-	P.magicCellsX = cellsX > 1 ? (uint32_t)(0x100000000ull / cellsX) : 0xFFFFFFFFu;
-
-	// the kernel, its occupancy and the batch's job list: all of it decided before anything is enqueued
-	DSceneView traceView = D->view;
-	TraceViewsKernel traceKernel = nullptr;
+	// the batch's job list: all of it decided before anything is enqueued
 	ViewsPlan VP;
-	int blocksPerCU = 0;
-	if (pathTrace) {
-		traceKernel = ViewsKernelFor(plan);
-		if (!traceKernel) { Log("RaylibAMD_RenderViews: no megakernel instance for STACK %d, K %d, stack in LDS %d", plan.stack, plan.poolK, plan.lstack); return false; }
-		if (!EnsureWideTree(D, sc, plan.tree)) return false;
-		traceView = D->view;
-		if (!plan.keepNodes4) traceView.nodes4 = nullptr;
-		if (!plan.keepNodes4f) traceView.nodes4f = nullptr;
-		auto it = R.occupancy.find((const void*)traceKernel);
-		if (it == R.occupancy.end()) {
-			HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, traceKernel, RL_BLOCK, 0));
-			R.occupancy[(const void*)traceKernel] = blocksPerCU;
-		} else blocksPerCU = it->second;
-		CullScene cs;
-		for (int k = 0; k < 3; ++k) { cs.boundsMin[k] = DS->boundsMin[k]; cs.boundsMax[k] = DS->boundsMax[k]; cs.sunDirection[k] = traceView.sunDirection[k]; cs.sunIlluminance[k] = traceView.sunIlluminance[k]; }
-		cs.boundsValid = DS->boundsValid; cs.prims = plan.prims; cs.hasSky = traceView.sky != nullptr; cs.hasSun = traceView.hasSun != 0;
-		VP = PlanViews(cs, st, cameras, count, plan, R.numCUs, blocksPerCU, knobs);
+	if (F.plan.pathTrace) {
+		const void* traceKernel = KernelFor(F.plan, true);
+		if (!traceKernel) { Log("RaylibAMD_RenderViews: no megakernel instance for STACK %d, K %d, stack in LDS %d", F.plan.stack, F.plan.poolK, F.plan.lstack); return false; }
+		const int blocksPerCU = OccupancyOf(R, traceKernel, &F.plan);
+		if (blocksPerCU < 0) return false;
+		VP = PlanViews(SceneCullScene(sc, F.view.sky != nullptr), st, cameras, count, F.plan, R.numCUs, blocksPerCU, F.knobs);
 		if (!VP.ok) { Log("RaylibAMD_RenderViews: job count overflow"); return false; }
+		F.knobs = VP.knobs;   // (RAYLIB_SAMPLE_BATCH lowered where the job count needs it)
 	}
 	// the camera table, then (culled views) the list of listed cells and the flags, staged in pinned memory and copied in one go
 	const size_t camBytes = (size_t)count * sizeof(DCamera), listAt = (camBytes + 255) & ~(size_t)255;
-	const bool culled = pathTrace && VP.numActive < numCells;
+	const bool culled = F.plan.pathTrace && VP.numActive < numCells;
 	const size_t flagsAt = listAt + (culled ? (size_t)numCells * sizeof(uint32_t) : 0), stageBytes = flagsAt + (culled ? numCells : 0);
 	if (g_views.hostBytes < stageBytes) {
 		if (g_views.host) (void)hipHostFree(g_views.host);
@@ -1215,84 +1216,32 @@ bool DeviceRenderViews(Scene& sc, const RenderRequest& req, const DCamera* camer
 	}
 	if (!Grow(g_views.dev, g_views.devBytes, stageBytes)) return false;
 	memcpy(g_views.host, cameras, camBytes);
+	PendingRender pend;
 	if (culled) {
 		memcpy(g_views.host + listAt, VP.active.data(), VP.active.size() * sizeof(uint32_t));
 		memcpy(g_views.host + flagsAt, VP.empty.data(), numCells);
+		ListCells(F, pend, (const uint32_t*)(g_views.dev + listAt), (const uint8_t*)(g_views.dev + flagsAt), VP.numActive, numCells, VP.emptyL, VP.emptyPixels, VP.raysPerSample);
 	}
-	float4* out = (float4*)outDevice;
-	if (!out) { if (!Grow(g_views.out, g_views.outBytes, viewBytes * count)) return false; out = g_views.out; }
+	F.out = (float4*)outDevice;
+	if (!F.out) { if (!Grow(g_views.out, g_views.outBytes, viewBytes * count)) return false; F.out = g_views.out; }
 	DViews V;
 	V.cameras = (const DCamera*)g_views.dev; V.cellsPerView = cellsPerView;
 	V.magicCellsPerView = cellsPerView > 1 ? (uint32_t)(0x100000000ull / cellsPerView) : 0xFFFFFFFFu;
+	F.views = &V;
+	F.resolve = (const void*)k_resolve_views;
+	F.resolveArgs[0] = &R.accum; F.resolveArgs[1] = &F.out; F.resolveArgs[2] = &F.firstBatch; F.resolveArgs[3] = &F.lastBatch; F.resolveArgs[4] = &V;
 
-	PendingRender pend;
-	pend.ctx = &R; pend.pathTrace = pathTrace; pend.slot = 0; pend.cnt = R.cntHost[0];
-	pend.out = out; pend.outBytes = viewBytes * count;
-	HIP_OK(hipMemcpyAsync(g_views.dev, g_views.host, stageBytes, hipMemcpyHostToDevice, R.stream));
-	HIP_OK(hipMemsetAsync(R.counters, 0, (CNT_COUNT + 24 + RL_TIMELINE_SLOTS) * sizeof(unsigned long long), R.stream));
-	HIP_OK(hipEventRecord(R.ev[0][0], R.stream));
-	bool ok = true;
-	if (!pathTrace) {
-		hipLaunchKernelGGL(AovViewsKernelFor(plan), dim3((numSlots + RL_BLOCK - 1) / RL_BLOCK), dim3(RL_BLOCK), 0, R.stream, P, D->view, out, R.counters, V);
-		HIP_TRY(hipGetLastError());
-		pend.listedCells = numCells;
-	} else {
-		g_lastTracePlain.store(plan.plain ? 1 : 0, std::memory_order_relaxed);
-		pend.pathsPerWave = plan.pathsPerWave; pend.treeWidth = plan.treeWidth; pend.nodeBytes = plan.nodeBytes;
-		const uint32_t numActive = VP.numActive;
-		if (culled) {
-			P.activeCells = (const uint32_t*)(g_views.dev + listAt); P.cellEmpty = (const uint8_t*)(g_views.dev + flagsAt); P.numActiveCells = numActive;
-			P.emptyL[0] = VP.emptyL[0]; P.emptyL[1] = VP.emptyL[1]; P.emptyL[2] = VP.emptyL[2];
-			P.emptySky = traceView.sky ? 1u : 0u;
-			pend.culledSamples = VP.emptyPixels * (uint64_t)SPP; pend.culledRaysPerSample = VP.raysPerSample; pend.culledSkyTexels = traceView.sky ? 1u : 0u;
-		}
-		pend.culledCells = numCells - numActive; pend.listedCells = numActive;
-		const uint32_t batch = VP.launch.batch;
-		if (!Grow(R.samples, R.samplesBytes, (size_t)numSlots * sizeof(SampleRGB) * std::min(batch, SPP))) ok = false;
-		if (ok && batch < SPP && !Grow(R.accum, R.accumBytes, (size_t)numSlots * sizeof(float4))) ok = false;
-		const int depthSlots = st.maxPathLength > 1 ? st.maxPathLength : 1;
-		for (uint32_t s0 = 0; ok && s0 < SPP; s0 += batch) {
-			const LaunchPlan L = PlanLaunch(numCells, numActive, SPP, s0, R.numCUs, blocksPerCU, plan, VP.knobs);
-			const uint32_t cnt = L.sampleCount;
-			P.sampleBegin = s0; P.sampleCount = cnt;
-			P.magicSamples = cnt > 1 ? (uint32_t)(0x100000000ull / cnt) : 0xFFFFFFFFu;
-			P.numJobs = (uint32_t)L.jobs;
-			P.stackStride = L.stackStride; P.jobChunk = L.jobChunk;
-			P.numHeads = L.heads; P.jobsPerHead = L.jobsPerHead; P.guideShift = L.guideShift;
-			if (!Grow(R.pathStack, R.pathStackBytes, (size_t)depthSlots * 8 * P.stackStride * sizeof(float))) { ok = false; break; }
-			pend.jobHeads = L.heads;
-			HIP_TRY(hipMemsetAsync(R.jobCounter, 0, RL_MAX_HEADS * RL_HEAD_STRIDE * sizeof(unsigned int), R.stream));
-			HIP_TRY(hipEventRecord(R.ev[0][2], R.stream));
-			if (L.jobs > 0) {
-				hipLaunchKernelGGL(traceKernel, dim3(L.blocks), dim3(RL_BLOCK), 0, R.stream,
-				                   P, traceView, DS->skyRot, R.samples, R.pathStack, R.counters, R.jobCounter, V);
-				HIP_TRY(hipGetLastError());
-			}
-			HIP_TRY(hipEventRecord(R.ev[0][3], R.stream));
-			hipLaunchKernelGGL(k_resolve_views, dim3((numSlots + RL_BLOCK - 1) / RL_BLOCK), dim3(RL_BLOCK), 0, R.stream,
-			                   P, traceView, DS->skyRot, R.samples, R.accum, out, (int)(s0 == 0), (int)(s0 + cnt >= SPP), V);
-			HIP_TRY(hipGetLastError());
-			++pend.launches;
-			if (s0 + cnt < SPP) {
-				HIP_TRY(hipEventSynchronize(R.ev[0][3]));
-				float ms = 0.0f;
-				HIP_TRY(hipEventElapsedTime(&ms, R.ev[0][2], R.ev[0][3]));
-				pend.traceMs += ms;
-			} else pend.lastBatchPending = true;
-		}
-	}
-	if (!ok) { (void)hipStreamSynchronize(R.stream); return false; }
-	HIP_OK(hipEventRecord(R.ev[0][1], R.stream));
-	HIP_OK(hipMemcpyAsync(R.cntHost[0], R.counters, (CNT_COUNT + 24) * sizeof(unsigned long long), hipMemcpyDeviceToHost, R.stream));
-	HIP_OK(hipEventRecord(R.ev[0][7], R.stream));
-	pend.enqueuedToEnd = true;
-	if (imagePixels)
-		for (uint32_t v = 0; v < count; ++v) HIP_TRY(hipMemcpyAsync(imagePixels[v], (const char*)out + viewBytes * v, viewBytes, hipMemcpyDeviceToDevice, R.stream));
-	uint64_t px = 0;
-	for (uint32_t c = 0; c < cellsPerView; ++c) { const uint32_t cx = c % cellsX, cy = c / cellsX; px += (uint64_t)std::min(8u, W - cx * 8) * std::min(8u, H - cy * 8); }
-	pend.pixels = px * count;
-	ok = FinishRender(pend, stats) && ok;
-	HIP_TRY(hipStreamSynchronize(R.stream));   // (the images' copies)
+	auto enqueue = [&]() -> bool {   // the staged tables, the frame, and behind it every image's copy of its view
+		HIP_OK(hipMemcpyAsync(g_views.dev, g_views.host, stageBytes, hipMemcpyHostToDevice, R.stream));
+		if (!BeginFrame(R, 0, F, viewBytes * count, pend) || !EnqueueFrame(R, 0, *sc.device, F, pend)) return false;
+		if (imagePixels)
+			for (uint32_t v = 0; v < count; ++v) HIP_OK(hipMemcpyAsync(imagePixels[v], (const char*)F.out + viewBytes * v, viewBytes, hipMemcpyDeviceToDevice, R.stream));
+		pend.pixels = CoveredPixels(W, H, 0, 1, cellsPerView) * count;
+		return true;
+	};
+	bool ok = enqueue();
+	ok = FinishRender(R, pend, stats) && ok;
+	HIP_OK(hipStreamSynchronize(R.stream));   // (the images' copies)
 	stats.ranks = 1; stats.devices = 1;
 	stats.numNodes = (uint32_t)sc.bvh.nodes.size(); stats.numTriangles = (uint32_t)sc.triangles.size(); stats.bvhDepth = sc.bvh.depth;
 	stats.wallMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1416,14 +1365,8 @@ bool DeviceTraceRays(Scene& sc, int32_t kind, const void* rays, int32_t n, float
 	}
 	const QueryKernel kernel = kind == RAYLIB_AMD_QUERY_ANY ? QueryKernelOfKind<RL_QK_ANY>(plan) : kind == RAYLIB_AMD_QUERY_CLOSEST ? QueryKernelOfKind<RL_QK_CLOSEST>(plan)
 	                         : QueryKernelOfKind<RL_QK_SURFACE>(plan);
-	int blocksPerCU = 0;
-	{
-		auto it = R.occupancy.find((const void*)kernel);
-		if (it == R.occupancy.end()) {
-			HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, kernel, RL_BLOCK, 0));
-			R.occupancy[(const void*)kernel] = blocksPerCU;
-		} else blocksPerCU = it->second;
-	}
+	const int blocksPerCU = OccupancyOf(R, (const void*)kernel);
+	if (blocksPerCU < 0) return false;
 	// enough workgroups to fill the device once; the waves take their rays from the counter (rl_k_query.inl)
 	const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)R.numCUs * (uint64_t)std::max(1, blocksPerCU), ((uint64_t)n + RL_BLOCK - 1) / RL_BLOCK));
 	const DSceneView view = Cp->view;
@@ -1742,8 +1685,7 @@ int32_t DeviceProgressiveStep(ProgressiveSession& S, uint32_t samples, void* out
 	req.outDevice = outDevice;
 	PendingRender pend;
 	bool ok = EnqueueRender(Rank0(), sc, req, pend, &S);
-	if (pend.ctx) ok = FinishRender(pend, stats) && ok;
-	else (void)hipStreamSynchronize(Rank0().stream);
+	ok = FinishRender(Rank0(), pend, stats) && ok;
 	if (!ok) return -1;
 	rendered = true;
 	S.samples += cnt; ++S.passes;
