@@ -57,7 +57,7 @@ typedef struct RaylibAMDStats {
 	                             1 RCCL grouped ncclSend / ncclRecv, 2 hipMemcpyPeerAsync pushes (RAYLIB_GATHER=peer, or RCCL could not be initialised) */
 	uint32_t rcclCommSize;    /* devices in the library's RCCL communicator (0: not initialised) */
 	uint32_t devices;         /* distinct physical devices the ranks ran on */
-	uint32_t jobHeads;        /* heads of the job list in the last megakernel launch: 8 = one per XCD (csrc/rl_render.hip TakeJobs), RAYLIB_JOB_HEADS overrides */
+	uint32_t jobHeads;        /* heads of the job list in the last megakernel launch: 8 = one per XCD (csrc/rl_dev_jobs.h TakeJobs), RAYLIB_JOB_HEADS overrides */
 	double   gatherMs;        /* on rank 0's stream: from the end of rank 0's own kernels until every rank's cells are on its device (waiting for slower ranks included) */
 	double   scatterMs;       /* k_scatter_cells: cell buffers -> row-major frame */
 	double   rankKernelMs[16];/* per rank: HIP-event time of all its kernels (kernelMs is their maximum) */
@@ -208,7 +208,7 @@ RAYLIB_API int32_t RaylibAMD_CullCells(CameraHandle camera, const float* bounds,
  * normalize and every reciprocal of the shading code -- against the compiler's IEEE expansions on ALL 2^32 float bit patterns, on the device.
  * which = 2: a / b with the divisor's correctly rounded reciprocal in hand (csrc/rl_math.h div_by_: the pixel -> [0, 1) divisions of a camera ray and the two
  * barycentric divisions of a triangle test) -- every bit pattern as numerator of a set of divisors and as divisor of a set of numerators, wherever the
- * sequence's stated conditions hold; which = 3: the triangle test's short barycentric form (csrc/rl_render.hip Barycentric) against the two divisions and
+ * sequence's stated conditions hold; which = 3: the triangle test's short barycentric form (csrc/rl_dev_walk.h Barycentric) against the two divisions and
  * the reference's test, every bit pattern in each of its three operands: same verdict, same quotients; which = 4: acosf and tanf with their divisions in the
  * short form (csrc/rl_glibc_math.h acosf_t / tanf_t, RL_EXACT_DIV bit 4) against the same functions with IEEE divisions, every bit pattern.
  * outMismatches: inputs whose results differ (a NaN may differ in payload); outFirstBits: the smallest such bit pattern.  Returns 1 when the sweep ran. */

@@ -781,7 +781,7 @@ void BuildBVH(const std::vector<PrimRef>& prims, BVH& out, const BVHBuildOptions
 				out.leafList.assign((cut.size() + 3) / 4, DNode4());
 				for (DNode4& nd : out.leafList) {
 					memset(&nd, 0, sizeof(nd));
-					// an unused slot is the box [+inf, -inf]: whatever the ray, one of its axes enters it at +inf (rl_render.hip TraverseLeafList has no other test for it)
+					// an unused slot is the box [+inf, -inf]: whatever the ray, one of its axes enters it at +inf (rl_dev_walk.h TraverseLeafList has no other test for it)
 					for (int k = 0; k < 4; ++k) { nd.lo[0][k] = nd.lo[1][k] = nd.lo[2][k] = INFINITY; nd.hi[0][k] = nd.hi[1][k] = nd.hi[2][k] = -INFINITY; nd.child[k] = DNODE_EMPTY; }
 				}
 				for (size_t at = 0; at < cut.size(); ++at) {
@@ -994,7 +994,7 @@ bool ValidateBVH8(const BVH& bvh, const std::vector<HostTriangle>& tris)
 	return depth <= bvh.depth8;
 }
 
-// The 8-wide walk of rl_render.hip (NodeStep8 / LeafStep8) on the host, operation by operation in float -- A = step * inv and B = (corner - o) * inv per axis, the
+// The 8-wide walk of rl_dev_pool.h (NodeStep8 / LeafStep8) on the host, operation by operation in float -- A = step * inv and B = (corner - o) * inv per axis, the
 // rounding bound E = (|B| + 255 |A|) 2^-21, one fma per 8-bit plane, the NEGATED entry distance, the sign of fma(exit, widen, -entry), groups of hit children in
 // visiting order, the stack of groups -- with the exit distance fixed at tMax[i] and every triangle of every leaf child reached tested by a tolerant
 // double-precision test: outT[i] = the least distance among them (FLT_MAX: none).  What the box arithmetic must never do is skip the leaf that holds the closest

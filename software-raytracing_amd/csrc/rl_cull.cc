@@ -21,7 +21,7 @@ bool CullCells(const CullScene& DS, const DCamera& cam, int32_t maxPathLength, f
                uint32_t cellsX, uint32_t cellFirst, uint32_t stride, uint32_t numLocalCells, CullResult& out)
 {
 	if (const char* e = getenv("RAYLIB_CULL_CELLS")) if (atoi(e) == 0) return false;
-	// (a sky panorama does not stand in the way: the dropped cells' samples then differ by their sky texel, and k_resolve looks it up per sample -- rl_render.hip)
+	// (a sky panorama does not stand in the way: the dropped cells' samples then differ by their sky texel, and k_resolve looks it up per sample -- rl_dev_jobs.h SumSlotBatch)
 	if (DS.prims || !DS.boundsValid || maxPathLength <= 0 || numLocalCells == 0) return false;
 	const double lensR = std::fabs((double)cam.lensRadius);   // the console front-end renders with aperture 0.01 (reference src/main.cc:24,421-425)
 	if (!std::isfinite(lensR)) return false;
@@ -33,7 +33,7 @@ bool CullCells(const CullScene& DS, const DCamera& cam, int32_t maxPathLength, f
 	const double O[3] = { cam.origin[0], cam.origin[1], cam.origin[2] }, TL[3] = { cam.top_left[0], cam.top_left[1], cam.top_left[2] };
 	const double Hh[3] = { cam.horizontal[0], cam.horizontal[1], cam.horizontal[2] }, Vv[3] = { cam.vertical[0], cam.vertical[1], cam.vertical[2] };
 	for (int k = 0; k < 3; ++k) if (!std::isfinite(O[k]) || !std::isfinite(TL[k]) || !std::isfinite(Hh[k]) || !std::isfinite(Vv[k])) return false;
-	// direction of sample (u, v): top_left + u H + (1 - v) V - origin = E + u H - v V with E = top_left + V - origin (rl_render.hip CameraRay)
+	// direction of sample (u, v): top_left + u H + (1 - v) V - origin = E + u H - v V with E = top_left + V - origin (rl_dev_jobs.h CameraRay)
 	double E[3]; sub3(TL, O, E); for (int k = 0; k < 3; ++k) E[k] += Vv[k];
 	double N[3] = { Hh[1] * Vv[2] - Hh[2] * Vv[1], Hh[2] * Vv[0] - Hh[0] * Vv[2], Hh[0] * Vv[1] - Hh[1] * Vv[0] };
 	const double hh = dot3(Hh, Hh), vv = dot3(Vv, Vv), nn = dot3(N, N);
@@ -83,7 +83,7 @@ bool CullCells(const CullScene& DS, const DCamera& cam, int32_t maxPathLength, f
 		}
 		if (!miss || !std::isfinite(D[0]) || !std::isfinite(D[1]) || !std::isfinite(D[2])) return false;
 		out.raysPerSample = 2;
-		// radiance = (0 + sunIlluminance), rl_render.hip MissShader
+		// radiance = (0 + sunIlluminance), rl_dev_shade.h MissShader
 		for (int k = 0; k < 3; ++k) out.L[k] = 0.0f + DS.sunIlluminance[k];
 	}
 	const uint32_t numCells = cellsX * ((H + 7) / 8);

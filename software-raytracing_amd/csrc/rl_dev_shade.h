@@ -1,0 +1,515 @@
+// Device library, part 4 of 6: shading -- the surface interaction, the microfacet BRDF and its sampler, the material lookups, Scatter, and the
+// miss shaders.
+#pragma once
+
+#include "rl_dev_walk.h"
+
+namespace rl {
+
+// ---------------------------------------------------------------------------
+// Surface interaction (reference geom/hit.h:16-36)
+struct Surf { float t; V3 p, n; float U, V; V3 tangent, bitangent; };
+
+// HitResult for the winning primitive (reference geom/triangle.cc:43-47, geom/sphere.cc:19-41, geom/cube.cc:24-38)
+// + the tangent frame (geom/hit.cc:6-18).  Returns the material index.
+template <bool PRIMS, int LDS = 0>
+__device__ __forceinline__ int BuildSurface(const DSceneView& S, V3 o, V3 d, const HitRec& h, Surf& s, bool basis, Counters& c, const float4* sm = nullptr)
+{
+	int material;
+	s.t = h.t;
+	s.p = o + h.t * d;
+	const uint32_t kind = PRIMS ? (((uint32_t)h.tri) >> 28) : 0u;
+	if (kind == 0u) {
+		const Shade sh = LDS ? ShadeFrom(sm + LdsAt<LDS>::SHADE + h.tri * RL_LDS_TSTRIDE) : LoadShade(S, h.tri);
+		c.shaded++;
+		const float a = h.a, b = h.b;
+		s.n = normalize((1 - a - b) * sh.n0 + a * sh.n1 + b * sh.n2);
+		s.U = (1 - a - b) * sh.s0 + a * sh.s1 + b * sh.s2;
+		s.V = (1 - a - b) * sh.t0 + a * sh.t1 + b * sh.t2;
+		material = sh.material;
+	} else if (kind == 1u) {
+		const float4* p = (const float4*)(S.spheres + (h.tri & 0x0fffffff));
+		const float4 q = p[0];
+		material = __float_as_int(p[1].x);
+		c.shaded++;
+		const V3 center = v3(q.x, q.y, q.z);
+		s.n = (s.p - center) / q.w;
+		const V3 op = s.p - center;
+		s.U = rtm::atan_(op.y / op.x);
+		s.V = rtm::acos_(op.z / q.w);
+	} else {
+		const float4* p = (const float4*)(S.cubes + (h.tri & 0x0fffffff));
+		material = __float_as_int(p[1].w);
+		c.shaded++;
+		const int face = __float_as_int(h.a);
+		s.n = (face == 0) ? v3(-1.0f, 0.0f, 0.0f) : (face == 1) ? v3(1.0f, 0.0f, 0.0f) : (face == 2) ? v3(0.0f, -1.0f, 0.0f)
+		    : (face == 3) ? v3(0.0f, 1.0f, 0.0f) : (face == 4) ? v3(0.0f, 0.0f, -1.0f) : (face == 5) ? v3(0.0f, 0.0f, 1.0f) : v3s(0.0f);
+		s.U = 0.0f; s.V = 0.0f;   // the reference leaves paramU / paramV unset for cubes
+	}
+	if (basis) {
+		V3 T = (fabsf(s.n.x) > 0.9f) ? v3(0.0f, 1.0f, 0.0f) : v3(1.0f, 0.0f, 0.0f);
+		V3 B = normalize(cross(T, s.n));
+		T = normalize(cross(s.n, B));
+		s.tangent = T; s.bitangent = B;
+	}
+	return material;
+}
+__device__ __forceinline__ V3 LocalToWorld(const Surf& s, V3 v)
+{
+	float wx = dot(v3(s.tangent.x, s.bitangent.x, s.n.x), v);
+	float wy = dot(v3(s.tangent.y, s.bitangent.y, s.n.y), v);
+	float wz = dot(v3(s.tangent.z, s.bitangent.z, s.n.z), v);
+	return v3(wx, wy, wz);
+}
+__device__ __forceinline__ V3 WorldToLocal(const Surf& s, V3 v) { return v3(dot(v, s.tangent), dot(v, s.bitangent), dot(v, s.n)); }
+
+// ---- microfacet BRDF pieces (reference render/brdf.h, render/material.cc:16-190) ----
+__device__ __forceinline__ float Clampf(float val, float lo, float hi) { return fmaxf(lo, fminf(hi, val)); }
+
+// (Inline since the end of round 3: as calls they measured better in round 2 (ErfInv / Erf inline 20.25 ms against 19.9), when the kernel had 400 SGPR reloads
+//  to place around every call; with the arguments re-read per part of the loop, ErfInv + Erf + acosf inline are 12.26 ms against 12.45, 36.9 against 37.2 ms
+//  on the 298 k frame.  powf stays a call: inline 12.65.)
+#ifndef RL_ERFINV_ATTR
+#define RL_ERFINV_ATTR __forceinline__
+#endif
+#ifndef RL_ERF_ATTR
+#define RL_ERF_ATTR __forceinline__
+#endif
+__device__ RL_ERFINV_ATTR float ErfInv(float x)
+{
+	float w, p;
+	x = Clampf(x, -.99999f, .99999f);
+	w = -rtm::log_((1 - x) * (1 + x));
+	if (w < 5) {
+		w = w - 2.5f;
+		p = 2.81022636e-08f;
+		p = 3.43273939e-07f + p * w;
+		p = -3.5233877e-06f + p * w;
+		p = -4.39150654e-06f + p * w;
+		p = 0.00021858087f + p * w;
+		p = -0.00125372503f + p * w;
+		p = -0.00417768164f + p * w;
+		p = 0.246640727f + p * w;
+		p = 1.50140941f + p * w;
+	} else {
+		w = rtm::sqrt_(w) - 3;
+		p = -0.000200214257f;
+		p = 0.000100950558f + p * w;
+		p = 0.00134934322f + p * w;
+		p = -0.00367342844f + p * w;
+		p = 0.00573950773f + p * w;
+		p = -0.0076224613f + p * w;
+		p = 0.00943887047f + p * w;
+		p = 1.00167406f + p * w;
+		p = 2.83297682f + p * w;
+	}
+	return p * x;
+}
+__device__ RL_ERF_ATTR float Erf(float x)
+{
+	const float a1 = 0.254829592f, a2 = -0.284496736f, a3 = 1.421413741f, a4 = -1.453152027f, a5 = 1.061405429f;
+	const float p = 0.3275911f;
+	int sign = 1;
+	if (x < 0) sign = -1;
+	x = fabsf(x);
+	float t = rtm::rcp1_(1 + p * x);
+	float y = 1 - (((((a5 * t + a4) * t) + a3) * t + a2) * t + a1) * t * rtm::exp_(-x * x);
+	return sign * y;
+}
+__device__ __forceinline__ float SinThetaL(V3 w) { return rtm::sqrt_(fmaxf(0.0f, 1.0f - w.z * w.z)); }
+
+// ---- the scattering event's divisions in the short form (RL_EXACT_DIV bits 1 and 2, rl_glibc_math.h) ----
+// (RL_EXACT_DIV is a translation unit's setting, made before its includes: the pool schedule's unit sets it to 0 and keeps every IEEE division, rl_render_pool.hip)
+// An IEEE division is 36 VALU issue cycles; y = RN(1 / b) without rcp1_'s guard is 13 and each quotient rtm::div_by_(a, b, y) 7 more, a compare 4.4 (tools/valu_calib.hip).
+// div_by_ is exact only under its conditions (rl_math.h): 2^-126 <= |b| < 2^126 here, |a| >= 2^-102 and a normal quotient.  The sites below take the short form where
+// the divisor's range is known and test what is not with compares that fail on NaN; if any lane fails, the whole wave takes the IEEE divisions in a branch on the
+// ballot (rarely taken: zero or tiny numerators, degenerate directions).  A site with nothing known about its divisor would pay two compares for it plus the
+// numerator's and the quotient's (>= 20 cycles of guard, 41 in all): DistributionBeckmann, the pdf and the Newton step keep their divisions.
+// |q| in [2^-91, 2^126): for a divisor in [2^-10, 8] this proves |a| >= 2^-102 and a normal quotient; a q computed from a zero, tiny, huge, infinite or NaN
+// numerator or a NaN divisor falls outside (those stay within a few ulps of, or as far out as, the true quotient)
+__device__ __forceinline__ bool QuotientInRange(float q) { return fabsf(q) >= 0x1p-91f && fabsf(q) < 0x1p126f; }
+// the specular term's vec3 / float: b = 4 |N.Wi| |N.Wo| + 0.001 lies in [0.001, 4.001] (unit vectors) -- or is NaN
+__device__ __forceinline__ V3 DivSpecular(V3 a, float b)
+{
+#if RL_EXACT_DIV & 1
+	const float y = rlm::rcp1_in_range_(b);
+	const V3 q = v3(rtm::div_by_(a.x, b, y), rtm::div_by_(a.y, b, y), rtm::div_by_(a.z, b, y));
+	if (rtm::wave_any_(!(QuotientInRange(q.x) && QuotientInRange(q.y) && QuotientInRange(q.z)))) return a / b;
+	return q;
+#else
+	return a / b;
+#endif
+}
+__device__ __forceinline__ float CosPhi(V3 w) { float s = SinThetaL(w); return (s == 0) ? 1 : Clampf(w.x / s, -1, 1); }
+__device__ __forceinline__ float SinPhi(V3 w) { float s = SinThetaL(w); return (s == 0) ? 0 : Clampf(w.y / s, -1, 1); }
+#if RL_EXACT_DIV & 1
+// CosPhi(w) and SinPhi(w) of one vector, sharing the divisor
+__device__ __forceinline__ void CosSinPhi(V3 w, float& cosPhi, float& sinPhi)
+{
+	const float s = SinThetaL(w);
+	// s is 0 or in [2^-12, 1] (1 - z z >= 2^-24 when it is positive), and |w.x|, |w.y| <= 1 + 2^-22: with numerators of at least 2^-102 every condition holds.  A zero
+	// numerator (its sign would come out wrong), a tiny one or NaN sends the wave to the divisions; lanes with s = 0 take the constants and do not count.
+	const float y = rlm::rcp1_in_range_(s);
+	float qx = rtm::div_by_(w.x, s, y), qy = rtm::div_by_(w.y, s, y);
+	if (rtm::wave_any_(!(s == 0 || (fabsf(w.x) >= 0x1p-102f && fabsf(w.y) >= 0x1p-102f)))) { qx = w.x / s; qy = w.y / s; }
+	cosPhi = (s == 0) ? 1 : Clampf(qx, -1, 1);
+	sinPhi = (s == 0) ? 0 : Clampf(qy, -1, 1);
+}
+#endif
+// dot(V, H) / dot(V, N) <= 0 (RL_EXACT_DIV bit 2).  n / d <= 0 holds exactly when the quotient is a zero, a negative number or -inf:
+//   n = +-0 with d neither zero nor NaN (+-0; 0 / 0 is NaN),
+//   n nonzero, neither NaN, with opposite sign bits (-inf when d = +-0, a negative number otherwise) --
+// except for a quotient that underflows to zero and d = +-inf, neither of which can happen here: d is the dot product of two unit vectors, |d| <= 1 + 2^-21, so it is
+// finite, and |n / d| > 2^-150 for every n != 0 (denormals included), which rounds to a nonzero quotient.
+__device__ __forceinline__ bool QuotientNotPositive(float n, float d)
+{
+#if RL_EXACT_DIV & 2
+	const bool opposite = (int32_t)(__float_as_uint(n) ^ __float_as_uint(d)) < 0;
+	return (n == 0.0f) ? __builtin_islessgreater(d, 0.0f) : (!__builtin_isunordered(n, d) && opposite);
+#else
+	return n / d <= 0.0f;
+#endif
+}
+
+// k_trace's PLAIN instance has fewer registers to place around a call (no texture, cut-out or sky code): there the tan_ of GeometryBeckmann and the pow_ of
+// the Fresnel term may be inlined, measured in DESIGN.md section 2.  Every other kernel keeps the calls.  (The sampler's pow_ stays a call everywhere: a template
+// parameter on BeckmannSample would change how the compiler inlines it into every other kernel.)
+#ifndef RL_PLAIN_INLINE_TAN
+#define RL_PLAIN_INLINE_TAN 0
+#endif
+#ifndef RL_PLAIN_INLINE_POW
+#define RL_PLAIN_INLINE_POW 0
+#endif
+template <bool INL> __device__ __forceinline__ float TanSel(float x) { return INL ? rtm::tan_inline_(x) : rtm::tan_(x); }
+template <bool INL> __device__ __forceinline__ float PowSel(float x, float y) { return INL ? rtm::pow_inline_(x, y) : rtm::pow_(x, y); }
+
+// reference render/material.cc:83-165
+// (__forceinline__ on the sampler and its caller below: the compiler inlined both into every kernel of its own accord until k_trace's PLAIN instance added
+//  one more call site, after which it kept BeckmannSample out of line in all of them)
+__device__ __forceinline__ void BeckmannSample11(float cosThetaI, float U1, float U2, float* slope_x, float* slope_y, Counters& cn)
+{
+	(void)cn;   // diagnostic builds count Newton iterations
+	const float Pi = RL_PI;
+	if ((double)cosThetaI > .9999) {
+		float r = rtm::sqrt_(-rtm::log_(1.0f - U1));
+		float sinPhi, cosPhi; rtm::sincos_(2 * Pi * U2, &sinPhi, &cosPhi);
+		*slope_x = r * cosPhi;
+		*slope_y = r * sinPhi;
+		return;
+	}
+	float sinThetaI = rtm::sqrt_(fmaxf((float)0, (float)1 - cosThetaI * cosThetaI));
+#if RL_EXACT_DIV & 1
+	// cosThetaI <= .9999 here, so sinThetaI is in [0.014, 1]; with 2^-126 <= cosThetaI < 1 the quotient is in [0.014, 2^126] and div_by_'s conditions hold.
+	// cosThetaI = +-0, tiny or NaN sends the wave to the division.
+	float tanThetaI = rtm::div_by_(sinThetaI, cosThetaI, rlm::rcp1_in_range_(cosThetaI));
+	if (rtm::wave_any_(!(cosThetaI >= 0x1p-126f))) tanThetaI = sinThetaI / cosThetaI;
+#else
+	float tanThetaI = sinThetaI / cosThetaI;
+#endif
+	float cotThetaI = rtm::rcp1_(tanThetaI);
+
+	float a = -1, c = Erf(cotThetaI);
+	float sample_x = fmaxf(U1, (float)1e-6f);
+
+	float thetaI = rtm::acos_(cosThetaI);
+	float fit = 1 + thetaI * (-0.876f + thetaI * (0.4265f - 0.0594f * thetaI));
+	float b = c - (1 + c) * rtm::pow_(1 - sample_x, fit);
+
+	const float SQRT_PI_INV = 1.f / sqrtf(Pi);
+	float normalization = rtm::rcp1_(1 + c + SQRT_PI_INV * tanThetaI * rtm::exp_(-cotThetaI * cotThetaI));
+
+	int it = 0;
+	float invErf = 0.0f;
+	bool converged = false;
+	// The compiler unrolls this loop nine times whatever `#pragma nounroll` says (its trip count is a constant): 12 KB of code of which two or three copies ever
+	// run.  Kept: with the limit hidden from the compiler (-DRL_NEWTON_ROLLED, round 5) the pool kernel is 10 KB shorter and every frame 0.6 - 1.1 % SLOWER
+	// (298 k room from inside 89.3 against 88.4 ms, from outside 35.4 against 35.1, Cornell 12.39 against 12.30: profiles/r05_newton_rolled_ab.log).
+	int newtonLimit = 10;
+#ifdef RL_NEWTON_ROLLED
+	asm volatile("" : "+s"(newtonLimit));
+	#pragma nounroll
+#endif
+	while (++it < newtonLimit) {
+		RL_WLSTEP(cn, 16, 17);
+		if (!(b >= a && b <= c)) b = 0.5f * (a + c);
+		invErf = ErfInv(b);
+		float value = normalization * (1 + b + SQRT_PI_INV * tanThetaI * rtm::exp_(-invErf * invErf)) - sample_x;
+		float derivative = normalization * (1 - invErf * tanThetaI);
+		if (fabsf(value) < 1e-5f) { converged = true; break; }
+		if (value > 0) c = b; else a = b;
+		b -= value / derivative;
+	}
+	// the reference evaluates ErfInv(b) once more here (material.cc:163); after the break b is still the argument invErf was computed from,
+	// so the value is in hand -- only a lane that used up its nine iterations has moved b since (a whole ErfInv per scattering event less)
+	*slope_x = converged ? invErf : ErfInv(b);
+	*slope_y = ErfInv(2.0f * fmaxf(U2, (float)1e-6f) - 1.0f);
+}
+// reference render/material.cc:166-190
+__device__ __forceinline__ V3 BeckmannSample(V3 wi, float alpha_x, float alpha_y, float U1, float U2, Counters& cn)
+{
+	V3 wiStretched = normalize(v3(alpha_x * wi.x, alpha_y * wi.y, wi.z));
+	float slope_x, slope_y;
+	BeckmannSample11(wiStretched.z, U1, U2, &slope_x, &slope_y, cn);
+#if RL_EXACT_DIV & 1
+	float cosPhi, sinPhi; CosSinPhi(wiStretched, cosPhi, sinPhi);
+	float tmp = cosPhi * slope_x - sinPhi * slope_y;
+	slope_y = sinPhi * slope_x + cosPhi * slope_y;
+#else
+	float tmp = CosPhi(wiStretched) * slope_x - SinPhi(wiStretched) * slope_y;
+	slope_y = SinPhi(wiStretched) * slope_x + CosPhi(wiStretched) * slope_y;
+#endif
+	slope_x = tmp;
+	slope_x = alpha_x * slope_x;
+	slope_y = alpha_y * slope_y;
+	return normalize(v3(-slope_x, -slope_y, 1.f));
+}
+// reference render/brdf.h:39-58
+__device__ __forceinline__ float DistributionBeckmann(V3 N, V3 H, float roughness)
+{
+	float cosH = dot(N, H);
+	if (roughness == 0.0f) return 1.0f;
+	if (H.z < 0.0f) cosH = -cosH;
+	float cosH2 = cosH * cosH;
+	float rr = roughness * roughness;
+	float exp_x = (1.0f - cosH2) / (rr * cosH);
+	float num = (cosH > 0.0f ? 1.0f : 0.0f) * rtm::exp_(-exp_x);
+	float denom = RL_PI * rr * cosH2 * cosH2;
+	return num / denom;
+}
+// reference render/brdf.h:74-93
+template <bool ITAN = false>
+__device__ __forceinline__ float GeometryBeckmann(V3 N, V3 H, V3 V, float roughness)
+{
+	float thetaV = rtm::acos_(dot(N, V));
+	float tanThetaV = TanSel<ITAN>(thetaV);
+	float a = rtm::rcp1_(roughness * tanThetaV);
+	float aa = a * a;
+	if (QuotientNotPositive(dot(V, H), dot(V, N))) return 0.0f;
+	if (a < 1.6f) {
+		float num = 3.535f * a + 2.181f * aa;
+		float denom = 1.0f + 2.276f * a + 2.577f * aa;
+		return num / denom;
+	}
+	return 1.0f;
+}
+
+// material texture lookups (reference render/material.cc:297-303,378-395,406-415)
+__device__ __forceinline__ V3 GetAlbedo(const DSceneView& S, const Mat& m, float U, float V, Counters& c)
+{
+	if (m.type == MAT_LAMBERTIAN || m.type == MAT_METAL) return m.albedo;
+	if (m.type == MAT_MICROFACET) {
+		V3 albedo = m.albedo;
+		if (m.tex0 >= 0) { float4 px = TexSample(S, m.tex0, false, U, V, c); albedo = v3(px.x, px.y, px.z) * px.w; }   // tex0: the pow(2.2) copy made at upload
+		return albedo;
+	}
+	return v3s(0.0f);
+}
+__device__ __forceinline__ float GetRoughness(const DSceneView& S, const Mat& m, float U, float V, Counters& c)
+{
+	float roughness = m.roughness;
+	if (m.tex2 >= 0) roughness = TexSample(S, m.tex2, false, U, V, c).x;
+	return roughness;
+}
+__device__ __forceinline__ V3 GetMicrosurfaceNormal(const DSceneView& S, const Mat& m, const Surf& s, Counters& c)
+{
+	if (m.type == MAT_MICROFACET && m.tex1 >= 0) {
+		float4 px = TexSample(S, m.tex1, false, s.U, s.V, c);
+		V3 N = v3(px.x, px.y, px.z);
+		N = normalize(2.0f * N - 1.0f);
+		return N;
+	}
+	return v3(0.0f, 0.0f, 1.0f);
+}
+__device__ __forceinline__ bool IsMirrorLike(const DSceneView& S, const Mat& m, float U, float V, Counters& c)
+{
+	if (m.type == MAT_DIELECTRIC || m.type == MAT_MIRROR) return true;
+	if (m.type == MAT_MICROFACET) return GetRoughness(S, m, U, V, c) < 0.1f;
+	return false;
+}
+// reference render/material.cc:342-350, material.h:67-69
+__device__ __forceinline__ V3 Emitted(const DSceneView& S, const Mat& m, const Surf& s, Counters& c)
+{
+	if (m.type == MAT_DIFFUSE_LIGHT) return m.albedo;
+	if (m.type == MAT_MICROFACET) {
+		V3 emit = m.emissive;
+		if (m.tex4 >= 0) { float4 px = TexSample(S, m.tex4, false, s.U, s.U, c); emit = v3s(px.z); }  // (U,U) and vec3(b): reference bugs kept
+		return emit;
+	}
+	return v3s(0.0f);
+}
+
+// One scattering event.  Returns false when the material does not scatter.
+// Outputs reflectance, new direction, pdf and ScatteringPdf (the value the
+// reference recomputes at renderer.cc:144).
+// PLAIN: k_trace's instance for plain scenes (MatFrom<true>), which takes the inlining choices above.
+template <bool PLAIN = false>
+__device__ __forceinline__ bool Scatter(const DSceneView& S, const Mat& m, V3 inD, const Surf& s, Rng& g, Counters& c,
+                                        V3& refl, V3& outD, float& pdf, float& sp)
+{
+	switch (m.type) {
+		case MAT_DIFFUSE_LIGHT: return false;
+		case MAT_LAMBERTIAN: {   // material.cc:195-219
+			V3 N = s.n;
+			V3 r = RandomInUnitSphere(g);
+			if ((double)dot(r, N) < 0.0) r = -r;
+			V3 Wi = normalize(r);
+			outD = Wi;
+			refl = m.albedo;
+			pdf = absDot(N, Wi) / RL_PI;
+			sp = fmaxf(0.0f, dot(s.n, Wi)) / RL_PI;
+			return true;
+		}
+		case MAT_METAL: {        // material.cc:225-239
+			V3 ud = normalize(inD);
+			V3 reflected = reflect(ud, s.n);
+			outD = reflected + m.fuzz * RandomInUnitSphere(g);
+			refl = m.albedo;
+			pdf = 1.0f;
+			sp = 1.0f / RL_PI;
+			return dot(outD, s.n) > 0.0f;
+		}
+		case MAT_MIRROR: {       // material.h:149-162
+			refl = m.albedo;
+			outD = reflect(inD, s.n);
+			pdf = 1.0f;
+			sp = 1.0f;
+			return true;
+		}
+		case MAT_DIELECTRIC: {   // material.cc:244-285
+			V3 outward_normal;
+			V3 reflected = reflect(inD, s.n);
+			float ni_over_nt;
+			refl = m.transmission;
+			V3 refracted = v3s(0.0f);
+			float reflect_prob, cosine;
+			if (dot(inD, s.n) > 0.0f) {
+				outward_normal = -s.n;
+				ni_over_nt = m.ior;
+				cosine = m.ior * dot(inD, s.n) / length(inD);
+			} else {
+				outward_normal = s.n;
+				ni_over_nt = rtm::rcp1_(m.ior);
+				cosine = -dot(inD, s.n) / length(inD);
+			}
+			bool bRefract;
+			{   // vec3.h:136-145
+				V3 uv = normalize(inD);
+				float dt = dot(uv, outward_normal);
+				float D = 1.0f - ni_over_nt * ni_over_nt * (1.0f - dt * dt);
+				bRefract = D > 0.0f;
+				if (bRefract) refracted = ni_over_nt * (uv - outward_normal * dt) - outward_normal * rtm::sqrt_(D);
+			}
+			if (bRefract) {
+				float r0 = (1.0f - m.ior) / (1.0f + m.ior);
+				r0 = r0 * r0;
+				reflect_prob = r0 + (1.0f - r0) * rtm::pow_((1.0f - cosine), 5.0f);
+			} else {
+				reflect_prob = 1.0f;
+			}
+			outD = (Next(g) < reflect_prob) ? reflected : refracted;
+			pdf = 1.0f;
+			sp = 1.0f / RL_PI;
+			return true;
+		}
+		default: {               // MicrofacetMaterial, material.cc:290-340,352-376,417-431
+			RL_CSTAMP_BEGIN(c);
+			RL_WLSTEP(c, 18, 19);
+			V3 baseColor = GetAlbedo(S, m, s.U, s.V, c);
+			float roughness = GetRoughness(S, m, s.U, s.V, c);
+			float metallic = m.metallic;
+			if (m.tex3 >= 0) metallic = TexSample(S, m.tex3, false, s.U, s.V, c).x;
+
+			V3 N = GetMicrosurfaceNormal(S, m, s, c);
+			V3 Wo = WorldToLocal(s, -inD);
+			float u0 = Next(g);
+			float u1 = Next(g);
+			bool bFlip = Wo.z < 0.0f;
+			RL_CSTAMP(c, 0);
+			V3 Wh = BeckmannSample(bFlip ? -Wo : Wo, roughness, roughness, u0, u1, c);
+			RL_CSTAMP(c, 1);
+			if (bFlip) Wh = -Wh;
+			V3 Wi = reflect(-Wo, Wh);
+			float NdotWi = absDot(N, Wi);
+
+			V3 F0 = v3s(0.04f);
+			F0 = mix(F0, baseColor, metallic);
+			V3 F = F0 + (1.0f - F0) * PowSel<PLAIN && RL_PLAIN_INLINE_POW>(1.0f - absDot(Wh, Wo), 5.0f);
+			float ggx2 = GeometryBeckmann<PLAIN && RL_PLAIN_INLINE_TAN>(N, Wh, Wo, roughness);
+			float ggx1 = GeometryBeckmann<PLAIN && RL_PLAIN_INLINE_TAN>(N, Wh, Wi, roughness);
+			float G = rtm::rcp1_(1.0f + ggx1 * ggx2);
+			float NDF = DistributionBeckmann(N, Wh, roughness);
+
+			V3 kS = F;
+			V3 kD = 1.0f - kS;
+			V3 diffuse = baseColor * (1.0f - metallic);
+			V3 specular = DivSpecular(F * G * NDF, 4.0f * NdotWi * absDot(N, Wo) + 0.001f);
+
+			V3 WiW = LocalToWorld(s, Wi);
+			outD = WiW;
+			refl = (kD * diffuse + kS * specular) * NdotWi;
+
+			// ScatteringPdf(hit, -inD, WiW), material.cc:352-376
+			V3 wo = WorldToLocal(s, -inD);
+			V3 wi = WorldToLocal(s, WiW);
+			V3 wh = normalize(wo + wi);
+			if (wh.z < 0.0f) wh.z = -wh.z;
+			float D = DistributionBeckmann(N, wh, roughness);
+			sp = D * absDot(wh, N);
+			pdf = sp / (4.0f * dot(Wo, Wh));
+			RL_CSTAMP(c, 2);
+			return true;
+		}
+	}
+}
+
+struct SkyRot { float m0[3], m1[3], m2[3]; };   // Rotator(yaw 90).rotate rows, computed on the host (renderer.cc:166-168)
+
+// Miss shader: sky panorama + sun (reference render/renderer.cc:155-199)
+// PLAIN: the launch has no sky image (rl_plan.cc), and the panorama lookup is compiled out
+template <int STACK, bool PRIMS, bool FULL, int LDS = 0, bool PLAIN = false>
+__device__ __forceinline__ V3 MissShader(const DSceneView& S, const SkyRot& R, V3 o, V3 d, float rayTime, float rayTMin, int* stk, Counters& c, const float4* sm = nullptr)
+{
+	V3 missResult = v3s(0.0f);
+	if (!PLAIN && S.sky) {
+		V3 dir = normalize(d);
+		V3 D = v3(dot(ld3(R.m0), dir), dot(ld3(R.m1), dir), dot(ld3(R.m2), dir));
+		float u = rtm::atan2_(D.z, D.x), v = rtm::asin_(D.y);
+		u *= 0.1591f; v *= 0.3183f;
+		u += 0.5f; v += 0.5f;
+		int x = (int)(u * (float)(uint32_t)(S.skyWidth - 1));
+		int y = (int)(v * (float)(uint32_t)(S.skyHeight - 1));
+		float4 px = ((const float4*)S.sky)[(uint32_t)(y * S.skyWidth + x)];
+		c.texels++;
+		missResult = missResult + v3(px.x, px.y, px.z);
+	}
+	if (S.hasSun) {
+		HitRec tmp;
+		bool occluded;
+		if constexpr (LDS != 0) occluded = Traverse4<STACK, true, PRIMS, FULL, LDS, PLAIN>(S, o, -ld3(S.sunDirection), rayTime, rayTMin, tmp, stk, c, sm);
+		else occluded = (!PRIMS && (FULL ? (const void*)S.nodes4f : (const void*)S.nodes4)) ? Traverse4<STACK, true, PRIMS, FULL, LDS>(S, o, -ld3(S.sunDirection), rayTime, rayTMin, tmp, stk, c, sm)
+		                                           : Traverse<STACK, true, PRIMS>(S, o, -ld3(S.sunDirection), rayTime, rayTMin, tmp, stk, c);
+		if (!occluded) missResult = missResult + ld3(S.sunIlluminance);
+	}
+	return missResult;
+}
+
+// sky part of the miss shader (reference render/renderer.cc:155-181)
+__device__ __forceinline__ V3 MissSky(const DSceneView& S, const SkyRot& R, V3 d, Counters& c)
+{
+	V3 missResult = v3s(0.0f);
+	if (S.sky) {
+		V3 dir = normalize(d);
+		V3 D = v3(dot(ld3(R.m0), dir), dot(ld3(R.m1), dir), dot(ld3(R.m2), dir));
+		float u = rtm::atan2_(D.z, D.x), v = rtm::asin_(D.y);
+		u *= 0.1591f; v *= 0.3183f;
+		u += 0.5f; v += 0.5f;
+		int x = (int)(u * (float)(uint32_t)(S.skyWidth - 1));
+		int y = (int)(v * (float)(uint32_t)(S.skyHeight - 1));
+		float4 px = ((const float4*)S.sky)[(uint32_t)(y * S.skyWidth + x)];
+		c.texels++;
+		missResult = missResult + v3(px.x, px.y, px.z);
+	}
+	return missResult;
+}
+
+} // namespace rl

@@ -39,7 +39,7 @@ static_assert(sizeof(DNode4) == 128, "DNode4");
 // The same node on an 8-bit grid, 64 B (half an L2 line; large scenes wait on node data, and this halves the lines a step touches).
 // Child k's box along axis a is [origin[a] + qlo_a,k * step_a, origin[a] + qhi_a,k * step_a], step_a = 2^(e_a - 127): the grid is
 // anchored at the minimum corner of the node's own box, lower planes are rounded down and upper planes up, so a child's grid box
-// CONTAINS its float box.  The closest hit does not depend on how tight a box is (candidate rule, rl_render.hip OwnBoxPass): the
+// CONTAINS its float box.  The closest hit does not depend on how tight a box is (candidate rule, rl_dev_walk.h OwnBoxPass): the
 // image stays bit-identical.  stepX / stepY / stepZ: the grid steps as floats (powers of two), in the fourth word of the three 16-byte rows (round 3:
 // one word of packed exponents before -- three shifts and three masks per node step to unpack, on a kernel that is bound by VALU issue).
 // qlo[a] / qhi[a]: byte k = child k.  An unused child has child[k] == DNODE_EMPTY (and an inverted grid box).
@@ -99,7 +99,7 @@ static_assert(sizeof(DNode8) == 80, "DNode8");
 // own operation order, so the per-ray arithmetic reproduces its t / barycentrics
 // bit for bit:  u = v1-v0, v = v2-v0, uv = dot(u,v), uu, vv, denom = uv*uv - uu*vv.
 // denom itself is three operations on values the record holds (the device forms it the way the host did); the sixteenth float is its correctly
-// rounded reciprocal, with which the two divisions by denom become six issue cycles each (rl_math.h div_by_, rl_render.hip Barycentric).
+// rounded reciprocal, with which the two divisions by denom become six issue cycles each (rl_math.h div_by_, rl_dev_walk.h Barycentric).
 struct alignas(64) DTriIsect {
 	float v0[3];
 	float n[3];      // unit geometric normal, normalize(cross(v1-v0, v2-v0)) (geom/triangle.h:34-38)
@@ -165,9 +165,9 @@ struct DCamera {
 // ... and at most this many triangles: 4.5 per leaf on average -- beyond, the leaves grow towards 8 triangles and the tree wins again (tools/gpu_leaflist.py)
 #define RL_LEAFLIST_MAXTRIS (RL_LEAFLIST_RECORDS * 18)
 
-// ---- launch limits the host plans against (rl_plan.cc) and the kernels are built for (rl_render.hip) ----
+// ---- launch limits the host plans against (rl_plan.cc) and the kernels are built for (rl_dev_*.h, rl_k_*.inl) ----
 #define RL_BLOCK 256   /* threads per workgroup of every kernel */
-// A scene small enough lives in LDS for the duration of a k_trace workgroup (rl_render.hip RL_LDS_*): at most this many wide nodes, triangles, materials
+// A scene small enough lives in LDS for the duration of a k_trace workgroup (rl_dev_scene.h RL_LDS_*): at most this many wide nodes, triangles, materials
 #ifndef RL_LDS_MAXNODES
 #define RL_LDS_MAXNODES 32
 #endif
@@ -184,7 +184,7 @@ struct DCamera {
 #ifndef RL_QUEUE_SHARED_CHUNK
 #define RL_QUEUE_SHARED_CHUNK 1   /* leaf-list kernel: the workgroup's waves share one job chunk (see the refill) */
 #endif
-#define RL_MAX_HEADS 8u           /* heads of the job list: one per XCD (rl_render.hip TakeJobs) */
+#define RL_MAX_HEADS 8u           /* heads of the job list: one per XCD (rl_dev_jobs.h TakeJobs) */
 // The pool schedule walks the 8-wide tree (when its levels fit RL_POOL8_MAXLEVELS) for scenes whose rays are expected to take at least this many node steps on
 // the 4-wide tree (BVH::sahNodes4); the builder splits leaves for the 8-wide plan only in those scenes (rl_host.h BVHBuildOptions::minSteps8)
 #define RL_BVH8_MIN_STEPS 40.0f
@@ -204,7 +204,7 @@ struct DSceneView {
 	                           // start its texel fetch from the triangle alone instead of triangle -> material -> texture (nullptr: no material of the scene has a map)
 	const DMaterial* materials;
 	const DTexture* textures;
-	int32_t numTextures;       // (incl. the converted copies of albedo maps) up to RL_LDS_TEXTURES descriptors are read from a copy in LDS: rl_render.hip TexTable
+	int32_t numTextures;       // (incl. the converted copies of albedo maps) up to RL_LDS_TEXTURES descriptors are read from a copy in LDS: rl_dev_scene.h TexTable
 	const float* texels;       // float4 pool
 	const DSphere* spheres;
 	const DCube* cubes;
@@ -238,11 +238,11 @@ struct DRenderParams {
 	uint32_t stackStride;      // threads in the grid (path-stack column count)
 	uint32_t rowMajorOutput;   // 1: out[y*W+x]; 0: out[localCell*64 + p]
 	uint32_t jobChunk;         // jobs a wave takes from a head of the job list per atomic
-	uint32_t numHeads;         // heads of the job list: 8 (one per XCD) or 1; head h covers jobs [h, h + 1) * jobsPerHead (rl_render.hip TakeJobs)
+	uint32_t numHeads;         // heads of the job list: 8 (one per XCD) or 1; head h covers jobs [h, h + 1) * jobsPerHead (rl_dev_jobs.h TakeJobs)
 	uint32_t jobsPerHead;      // whole cells: a multiple of 64 * sampleCount
 	uint32_t guideShift;       // 0: every draw asks for jobChunk jobs; s > 0: at most (jobs left in the band at the wave's previous draw) >> s (TakeJobs)
 	uint32_t padQueue;
-	float    invWidth, invHeight;   // RN(1 / (float)width), RN(1 / (float)height): the pixel -> [0, 1) divisions of GenerateCell (rl_render.hip PixelUV)
+	float    invWidth, invHeight;   // RN(1 / (float)width), RN(1 / (float)height): the pixel -> [0, 1) divisions of GenerateCell (rl_dev_jobs.h PixelUV)
 	// Cells no camera ray of which can meet the scene's bounding box (host, rl_runtime.inl CullCells: pinhole camera, no sky panorama, the frame's box on the
 	// image plane with a margin) are not in the job list: activeCells[i] is the i-th listed local cell (nullptr: all numLocalCells cells, in order), and
 	// k_resolve sums the constant every one of their samples would have come to -- emptyL, the sun's illuminance or nothing -- for cells flagged in cellEmpty.

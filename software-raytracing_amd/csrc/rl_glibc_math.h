@@ -86,11 +86,11 @@ RLM_FN float sqrtf_(float x) { return __builtin_sqrtf(x); }
 #endif
 RLM_FN float fabsf_(float x) { return __builtin_fabsf(x); }
 // Divisions in the short form of rl_math.h (rtm::div_by_ with y = rcp1_in_range_(b)), selected by the bits of RL_EXACT_DIV:
-//   1: the scattering event's quotients with one divisor for several numerators or divisors in a provable range (rl_render.hip)
-//   2: GeometryBeckmann's `dot(V, H) / dot(V, N) <= 0` as a predicate on signs, zeros and NaN (rl_render.hip)
+//   1: the scattering event's quotients with one divisor for several numerators or divisors in a provable range (rl_dev_shade.h)
+//   2: GeometryBeckmann's `dot(V, H) / dot(V, N) <= 0` as a predicate on signs, zeros and NaN (rl_dev_shade.h)
 //   4: the divisions inside acosf_ and tanf_ below, UNGUARDED: every one of their 2^32 inputs gives the bits of the IEEE form
 //      (RaylibAMD_VerifyExactMath mode 4 compares acosf_t<true> / tanf_t<true> with acosf_t<false> / tanf_t<false>, tests/test_exact_div.py)
-// RL_EXACT_DIV=0 keeps the compiler's IEEE expansions everywhere (the A/B baseline).  The pool kernel's unit keeps them too (rl_render.hip).
+// RL_EXACT_DIV=0 keeps the compiler's IEEE expansions everywhere (the A/B baseline).  The pool kernel's unit keeps them too (rl_render_pool.hip sets it before its includes).
 // Measured on the Cornell frame (k_trace, 3 interleaved runs of 100 steps each): 11.89 - 11.91 ms with none, bit 1 11.70 - 11.72,
 // bit 4 11.70 - 11.73, bit 2 11.86 - 11.94 (no gain beyond the noise: off by default), bits 1 + 2 + 4 11.49 - 11.56.
 #ifndef RL_EXACT_DIV

@@ -159,7 +159,7 @@ struct SceneElement {
 struct HostSphere { f3 center; float radius; int32_t material; };
 struct HostCube { f3 minBounds, maxBounds; float timeStartMove; f3 velocity; int32_t material; };
 
-struct DeviceScene;   // rl_render.hip
+struct DeviceScene;   // rl_runtime.inl
 
 struct Scene {
 	std::vector<OBJModel*> models;    // borrowed (reference raylib.cc:264-268)
@@ -203,7 +203,7 @@ void LogStart();
 void LogFlush();
 void LogStop();
 
-// device side (rl_render.hip)
+// device side (rl_runtime.inl, in rl_render.hip's unit)
 struct RenderRequest {
 	RendererSettings settings;
 	DCamera camera;

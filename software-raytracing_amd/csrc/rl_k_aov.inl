@@ -1,5 +1,6 @@
-// k_aov and its views twin (RaylibAMD_RenderViews), one source for both: rl_render.hip includes this file twice, the second time with
-// RL_VIEWS_TWIN 1.  The twin takes the view table (DViews) as one more trailing argument; everything under RL_VIEWS_TWIN is the twin's alone, so that the
+// k_aov and its views twin (RaylibAMD_RenderViews), one source for both: a translation unit includes this file with RL_VIEWS_TWIN 0 for the
+// one-view kernel (rl_render.hip) or 1 for the twin (rl_render_views.hip); prototypes and default template arguments: rl_kernels.h.  The twin takes the view table (DViews) as one more
+// trailing argument; everything under RL_VIEWS_TWIN is the twin's alone, so that the
 // one-view kernel is the token sequence it always was (a template flag would add an inlining level, which reorders the one-view kernel's code:
 // tools/isa_equivalence.py).
 

@@ -1,6 +1,6 @@
 // k_query: batched ray queries on a finalized scene (include/raylib_amd.h RaylibAMD_TraceRays), on the renderer's own walks -- Traverse (the binary
-// tree), Traverse4 (the 4-wide grid nodes) and NodeStep8 / LeafStep8 on the pool kernel's Trav state (the 8-wide tree).  rl_render.hip includes this file
-// in every translation unit; the kernels are defined in rl_query.hip's unit alone (RL_TU_QUERY) and only declared in the others, so that the render
+// tree), Traverse4 (the 4-wide grid nodes) and NodeStep8 / LeafStep8 on the pool kernel's Trav state (the 8-wide tree).  rl_query.hip includes this file
+// and instantiates the kernels; the other units see the declaration, the records and the instance list of rl_kernels.h, so that the render
 // kernels stay the code they were (tools/isa_equivalence.py).
 //
 // One ray per lane.  A wave takes RL_QUERY_CHUNK rays at a time from a global counter: incoherent rays differ in step counts by orders of magnitude, and a
@@ -10,15 +10,13 @@
 // The interval [tMin, tMax]: the walk starts with "best" at the float above tMax, so the triangle test (t >= tMin, t < best) takes a hit at exactly tMax,
 // as Triangle::Hit does, and every box beyond tMax is culled.  A sphere's interval is open (Sphere::Hit: t_min < t < t_max): a sphere at exactly tMax is
 // dropped afterwards -- it can only have been the walk's result if nothing nearer was accepted.  A NaN bound makes every comparison false: a miss.
-// tMin < 0 is raised to +0 (QueryTMin).  A triangle at exactly tMin counts: this unit widens the candidate rule's "own box ends before tMin" (rl_render.hip OwnBoxPassBox).
+// tMin < 0 is raised to +0 (QueryTMin).  A triangle at exactly tMin counts: this unit widens the candidate rule's "own box ends before tMin" (RL_OWN_BOX_WIDEN_TMIN, rl_dev_walk.h OwnBoxPassBox).
 #ifndef RL_QUERY_CHUNK
 #define RL_QUERY_CHUNK 64u       /* rays a wave takes per atomic on the global counter */
 #endif
 #ifndef RL_QUERY_REFILL
 #define RL_QUERY_REFILL 8        /* 8-wide walk: idle lanes of a wave before it hands out new rays between steps */
 #endif
-enum { RL_QK_ANY = 0, RL_QK_CLOSEST = 1, RL_QK_SURFACE = 2 };   // RAYLIB_AMD_QUERY_*
-struct DQueryHit { float t; int32_t prim; float b1, b2; };      // RaylibAMDHitT
 
 __device__ __forceinline__ float NextUpF(float x)
 {
@@ -62,15 +60,11 @@ __device__ __forceinline__ void QueryStore(const DSceneView& S, V3 o, V3 d, floa
 	if (outPrim) outPrim[i] = prim;
 }
 
-// TREE: 2 the binary tree (S.nodes), 4 the grid nodes (S.nodes4), 8 the 8-wide tree (S.nodes8).  STACK: the walk's stack (TREE 8: RL_POOL8_MAXLEVELS groups).
-// PRIMS: the scene holds spheres or cubes (binary tree only).  rays: n records of two float4 (org, tMin | dir, tMax).  counters: CNT_* sums, or null.
+// (template and kernel arguments: rl_kernels.h)
 template <int TREE, int KIND, int STACK, bool PRIMS>
 __global__ void __launch_bounds__(RL_BLOCK)
 k_query(const DSceneView S, const float4* __restrict__ rays, uint32_t n, float rayTime, void* __restrict__ out, int32_t* __restrict__ outPrim,
         const int32_t* __restrict__ slotIndex, unsigned int* __restrict__ rayCounter, unsigned long long* __restrict__ counters)
-#ifndef RL_TU_QUERY
-;   // defined in the translation unit of rl_query.hip; instances below
-#else
 {
 	static_assert(TREE == 2 || TREE == 4 || TREE == 8, "tree");
 	static_assert(TREE == 2 || !PRIMS, "spheres and cubes are walked on the binary tree only");
@@ -174,15 +168,3 @@ k_query(const DSceneView S, const float4* __restrict__ rays, uint32_t n, float r
 		}
 	}
 }
-#endif
-// The instances rl_runtime.inl QueryKernelFor selects from: (TREE, KIND, STACK, PRIMS)
-#define RL_QUERY_INSTANCES_K(X, K) \
-	X(2, K, 32, false) X(2, K, 32, true) X(2, K, 64, false) X(2, K, 64, true) X(4, K, 32, false) X(4, K, 64, false) X(8, K, 2 * RL_POOL8_MAXLEVELS, false)
-#define RL_QUERY_INSTANCES(X) RL_QUERY_INSTANCES_K(X, 0) RL_QUERY_INSTANCES_K(X, 1) RL_QUERY_INSTANCES_K(X, 2)
-#ifdef RL_TU_QUERY
-#define RL_QUERY_X(a, b, c, d) template __global__ void k_query<a, b, c, d>(const DSceneView, const float4* __restrict__, uint32_t, float, void* __restrict__, int32_t* __restrict__, const int32_t* __restrict__, unsigned int* __restrict__, unsigned long long* __restrict__);
-#else
-#define RL_QUERY_X(a, b, c, d) extern template __global__ void k_query<a, b, c, d>(const DSceneView, const float4* __restrict__, uint32_t, float, void* __restrict__, int32_t* __restrict__, const int32_t* __restrict__, unsigned int* __restrict__, unsigned long long* __restrict__);
-#endif
-RL_QUERY_INSTANCES(RL_QUERY_X)
-#undef RL_QUERY_X

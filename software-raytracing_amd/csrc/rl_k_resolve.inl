@@ -1,5 +1,6 @@
-// k_resolve and its views twin (RaylibAMD_RenderViews), one source for both: rl_render.hip includes this file twice, the second time with
-// RL_VIEWS_TWIN 1.  The twin takes the view table (DViews) as one more trailing argument; everything under RL_VIEWS_TWIN is the twin's alone, so that the
+// k_resolve and its views twin (RaylibAMD_RenderViews), one source for both: a translation unit includes this file with RL_VIEWS_TWIN 0 for the
+// one-view kernel (rl_render.hip) or 1 for the twin (rl_render_views.hip); prototypes and default template arguments: rl_kernels.h.  The twin takes the view table (DViews) as one more
+// trailing argument; everything under RL_VIEWS_TWIN is the twin's alone, so that the
 // one-view kernel is the token sequence it always was (a template flag would add an inlining level, which reorders the one-view kernel's code:
 // tools/isa_equivalence.py).
 
@@ -14,9 +15,6 @@ k_resolve_views(const DRenderParams Pb, const DSceneView S, const SkyRot R, cons
 #else
 k_resolve(const DRenderParams P, const DSceneView S, const SkyRot R, const SampleRGB* __restrict__ samples, float4* __restrict__ accum, float4* __restrict__ out, int firstBatch, int lastBatch)
 #endif
-#if RL_VIEWS_TWIN && !defined(RL_TU_VIEWS)
-;   // the twin is defined in the translation unit of rl_render_views.hip
-#else
 {
 	RL_MATH_PROLOGUE();
 #if RL_VIEWS_TWIN
@@ -56,4 +54,3 @@ k_resolve(const DRenderParams P, const DSceneView S, const SkyRot R, const Sampl
 #endif
 	}
 }
-#endif

@@ -1,9 +1,10 @@
-// k_trace, the megakernel of one path per lane, and its views twin (RaylibAMD_RenderViews), one source for both: rl_render.hip includes this file twice, the second time with
-// RL_VIEWS_TWIN 1.  The twin takes the view table (DViews) as one more trailing argument; everything under RL_VIEWS_TWIN is the twin's alone, so that the
+// k_trace, the megakernel of one path per lane, and its views twin (RaylibAMD_RenderViews), one source for both: a translation unit includes this file with RL_VIEWS_TWIN 0 for the
+// one-view kernel (rl_render.hip) or 1 for the twin (rl_render_views.hip); prototypes and default template arguments: rl_kernels.h.  The twin takes the view table (DViews) as one more
+// trailing argument; everything under RL_VIEWS_TWIN is the twin's alone, so that the
 // one-view kernel is the token sequence it always was (a template flag would add an inlining level, which reorders the one-view kernel's code:
 // tools/isa_equivalence.py).
 
-template <int STACK, bool PRIMS, bool FULL, int LDS = 0, bool PLAIN = false>
+template <int STACK, bool PRIMS, bool FULL, int LDS, bool PLAIN>
 __global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 2))
 #if RL_VIEWS_TWIN
 k_trace_views(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB* __restrict__ samplesK,

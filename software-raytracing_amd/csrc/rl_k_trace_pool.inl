@@ -1,9 +1,9 @@
-// k_trace_pool, the pool megakernel, and its views twin (RaylibAMD_RenderViews), one source for both: rl_render.hip includes this file twice, the second time with
-// RL_VIEWS_TWIN 1.  The twin takes the view table (DViews) as one more trailing argument; everything under RL_VIEWS_TWIN is the twin's alone, so that the
+// k_trace_pool, the pool megakernel, and its views twin (RaylibAMD_RenderViews), one source for both: rl_render_pool.hip includes this file twice, with RL_VIEWS_TWIN 1
+// and 0; prototypes and default template arguments: rl_kernels.h.  The twin takes the view table (DViews) as one more trailing argument; everything under RL_VIEWS_TWIN is the twin's alone, so that the
 // one-view kernel is the token sequence it always was (a template flag would add an inlining level, which reorders the one-view kernel's code:
 // tools/isa_equivalence.py).
 
-template <int STACK, bool PRIMS, int K, int LSTACK = STACK, int WIDE = 0>
+template <int STACK, bool PRIMS, int K, int LSTACK, int WIDE>
 __global__ void __launch_bounds__(RL_BLOCK, (PoolOcc<LSTACK, PRIMS, K>::kBlocks))
 #if RL_VIEWS_TWIN
 k_trace_pool_views(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB* __restrict__ samplesK,
@@ -12,9 +12,6 @@ k_trace_pool_views(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk,
 k_trace_pool(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB* __restrict__ samplesK,
              float* __restrict__ pathStackK, unsigned long long* __restrict__ countersK, unsigned int* __restrict__ jobCounterK)
 #endif
-#ifndef RL_TU_POOL
-;   // defined in the translation unit of rl_render_pool.hip: this same source, compiled with a scheduler strategy of its own (Makefile); instances below
-#else
 {
 	(void)Pk; (void)Sk; (void)Rk; (void)samplesK; (void)pathStackK; (void)countersK; (void)jobCounterK;   // read through RL_ARGS() where a part of the loop needs them (k_trace)
 	RL_TEX_PROLOGUE(Sk);
@@ -482,4 +479,3 @@ k_trace_pool(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, Sampl
 		if (lane == 0 && v) atomicAdd(&counters[k], v);
 	}
 }
-#endif

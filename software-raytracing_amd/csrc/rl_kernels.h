@@ -1,0 +1,96 @@
+// Every kernel that has a views twin or lives in a translation unit other than the one that launches it: its prototype, its instance list and the
+// explicit instantiation declarations, each written once.  A kernel's body is an .inl file that always defines it; the unit that includes the body owns the
+// kernel and follows it with the instantiation definitions (RL_..._INSTANCES(RL_K_...)), every other unit sees what is here.
+//   rl_render.hip        k_trace, k_resolve, k_aov (+ the small kernels and the host runtime, which launches everything)
+//   rl_render_views.hip  k_trace_views, k_resolve_views, k_aov_views: the views twins (RaylibAMD_RenderViews).  Instantiated beside the one-view kernels they
+//                        change how the helpers both call are inlined into those (tools/isa_equivalence.py)
+//   rl_render_pool.hip   k_trace_pool and its twin: a scheduler strategy of its own (Makefile POOLFLAGS)
+//   rl_query.hip         k_query (RaylibAMD_TraceRays): beside the render kernels it would change how the walks they share are inlined into those
+// A twin takes the view table (DViews) as one more trailing argument.  Default template arguments are given here and nowhere else.
+#pragma once
+
+#include "rl_dev_jobs.h"
+#include "rl_dev_pool.h"
+
+namespace rl {
+
+// ---------------------------------------------------------------------------
+// The megakernel.  samples: [sampleCount][numLocalCells*64] SampleRGB.
+// pathStack: [maxPathLength][stackStride] records of 2 float4 (refl.xyz, sp | pdf, E.xyz).
+#ifndef RL_QUEUE_SPIN_LIMIT
+// 0: a wave waits for the workgroup's chunk until the wave that is refilling it is done (microseconds: one global atomic).  N > 0: after N waits of 128
+// cycles it takes one batch straight from the global counter instead (1: test build that always does; parity-tested).  The bounded form is not the
+// default because its few instructions change the register allocation of the whole loop: 14.98 ms against 14.79 on the Cornell frame (same box, interleaved).
+#define RL_QUEUE_SPIN_LIMIT 0
+#endif
+#ifndef RL_TRACE_MIN_WAVES
+#define RL_TRACE_MIN_WAVES 4   /* 4 waves per SIMD = 4 workgroups per CU: caps the kernel at 128 VGPRs */
+#endif
+// PRIMS: the scene holds spheres / cubes (their leaf and shading code is compiled out of the triangle-only variant)
+// FULL: the wide tree, if the launch carries one, has float boxes (S.nodes4f) -- small scenes; else grid nodes (S.nodes4)
+// LDS (with FULL, triangle scenes within the RL_LDS_MAX* limits): the scene's records are copied to LDS at the start and read from there;
+//     LDS == 2: a scene of <= 16 leaves, walked through its leaf list (TraverseLeafList) instead of its tree
+// (STACK, PRIMS, FULL, LDS, PLAIN): every instance rl_runtime.inl KernelFor names.
+#define RL_TRACE_ARGS const DRenderParams, const DSceneView, const SkyRot, SampleRGB* __restrict__, float* __restrict__, unsigned long long* __restrict__, unsigned int* __restrict__
+template <int STACK, bool PRIMS, bool FULL, int LDS = 0, bool PLAIN = false>
+__global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 2)) k_trace(RL_TRACE_ARGS);
+template <int STACK, bool PRIMS, bool FULL, int LDS = 0, bool PLAIN = false>
+__global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 2)) k_trace_views(RL_TRACE_ARGS, const DViews);
+#define RL_TRACE_INSTANCES(X) \
+	X(16, false, false, 0, false) X(16, false, true, 0, false) X(16, false, true, 1, false) X(16, false, true, 2, false) X(16, false, true, 2, true) \
+	X(32, false, false, 0, false) X(32, false, true, 0, false) X(32, true, false, 0, false) X(32, true, true, 0, false) \
+	X(64, false, false, 0, false) X(64, false, true, 0, false) X(64, true, false, 0, false) X(64, true, true, 0, false)
+#define RL_K_TRACE_VIEWS(a, b, c, d, e) template __global__ void k_trace_views<a, b, c, d, e>(RL_TRACE_ARGS, const DViews);
+RL_TRACE_INSTANCES(extern RL_K_TRACE_VIEWS)   // (k_trace's own instances are the ones rl_runtime.inl names: implicit)
+
+// ---------------------------------------------------------------------------
+// The pool megakernel (rl_dev_pool.h, rl_k_trace_pool.inl): k_trace's arguments.
+// STACK: capacity of the traversal stack; LSTACK <= STACK: how much of it lives in LDS (the rest is private overflow)
+// WIDE: 0 the BVH2; 1 the BVH4 (S.nodes4: 64-byte grid nodes); 3 the 8-wide tree (S.nodes8; STACK / LSTACK then count words: two per group)
+template <int STACK, bool PRIMS, int K, int LSTACK = STACK, int WIDE = 0>
+__global__ void __launch_bounds__(RL_BLOCK, (PoolOcc<LSTACK, PRIMS, K>::kBlocks)) k_trace_pool(RL_TRACE_ARGS);
+template <int STACK, bool PRIMS, int K, int LSTACK = STACK, int WIDE = 0>
+__global__ void __launch_bounds__(RL_BLOCK, (PoolOcc<LSTACK, PRIMS, K>::kBlocks)) k_trace_pool_views(RL_TRACE_ARGS, const DViews);
+// The instances the runtime selects from (rl_runtime.inl KernelFor)
+#define RL_POOL_INSTANCES(X) \
+	X(16, false, 2, 16, 0) X(16, false, 3, 16, 0) X(16, false, 4, 16, 0) X(32, false, 2, 32, 0) X(32, false, 3, 32, 0) X(32, false, 4, 32, 0) \
+	X(32, false, 2, 4, 0) X(32, false, 2, RL_POOL_SHORT_LSTACK, 0) \
+	X(32, false, 2, 32, 1) X(64, false, 2, 32, 1) X(32, false, 2, RL_POOL_SHORT_LSTACK, 1) X(64, false, 2, RL_POOL_SHORT_LSTACK, 1) \
+	X(2 * RL_POOL8_MAXLEVELS, false, 2, RL_POOL8_LSTACK, 3)
+#define RL_K_TRACE_POOL(a, b, c, d, e) template __global__ void k_trace_pool<a, b, c, d, e>(RL_TRACE_ARGS);
+#define RL_K_TRACE_POOL_VIEWS(a, b, c, d, e) template __global__ void k_trace_pool_views<a, b, c, d, e>(RL_TRACE_ARGS, const DViews);
+RL_POOL_INSTANCES(extern RL_K_TRACE_POOL_VIEWS)
+RL_POOL_INSTANCES(extern RL_K_TRACE_POOL)
+
+// ---------------------------------------------------------------------------
+// k_resolve (rl_k_resolve.inl) and k_aov (rl_k_aov.inl)
+__global__ void __launch_bounds__(RL_BLOCK)
+k_resolve(const DRenderParams P, const DSceneView S, const SkyRot R, const SampleRGB* __restrict__ samples, float4* __restrict__ accum, float4* __restrict__ out, int firstBatch, int lastBatch);
+__global__ void __launch_bounds__(RL_BLOCK)
+k_resolve_views(const DRenderParams Pb, const DSceneView S, const SkyRot R, const SampleRGB* __restrict__ samples, float4* __restrict__ accum, float4* __restrict__ out,
+                int firstBatch, int lastBatch, const DViews V);
+#define RL_AOV_ARGS const DRenderParams, const DSceneView, float4* __restrict__, unsigned long long* __restrict__
+template <int STACK, bool PRIMS> __global__ void __launch_bounds__(RL_BLOCK) k_aov(RL_AOV_ARGS);
+template <int STACK, bool PRIMS> __global__ void __launch_bounds__(RL_BLOCK) k_aov_views(RL_AOV_ARGS, const DViews);
+#define RL_AOV_INSTANCES(X) X(16, false) X(32, false) X(32, true) X(64, false) X(64, true)
+#define RL_K_AOV_VIEWS(a, b) template __global__ void k_aov_views<a, b>(RL_AOV_ARGS, const DViews);
+RL_AOV_INSTANCES(extern RL_K_AOV_VIEWS)
+
+// ---------------------------------------------------------------------------
+// The ray queries (RaylibAMD_TraceRays; rl_k_query.inl)
+// A hit record as RaylibAMD_ClosestHit and the surface query of RaylibAMD_TraceRays return it (oracle/flat_scene.h FlatHit)
+struct DHitOut { int32_t hit; float t; float p[3]; float n[3]; float paramU, paramV; int32_t material; };
+enum { RL_QK_ANY = 0, RL_QK_CLOSEST = 1, RL_QK_SURFACE = 2 };   // RAYLIB_AMD_QUERY_*
+struct DQueryHit { float t; int32_t prim; float b1, b2; };      // RaylibAMDHitT
+// TREE: 2 the binary tree (S.nodes), 4 the grid nodes (S.nodes4), 8 the 8-wide tree (S.nodes8).  STACK: the walk's stack (TREE 8: RL_POOL8_MAXLEVELS groups).
+// PRIMS: the scene holds spheres or cubes (binary tree only).  rays: n records of two float4 (org, tMin | dir, tMax).  counters: CNT_* sums, or null.
+#define RL_QUERY_ARGS const DSceneView, const float4* __restrict__, uint32_t, float, void* __restrict__, int32_t* __restrict__, const int32_t* __restrict__, unsigned int* __restrict__, unsigned long long* __restrict__
+template <int TREE, int KIND, int STACK, bool PRIMS> __global__ void __launch_bounds__(RL_BLOCK) k_query(RL_QUERY_ARGS);
+// The instances rl_runtime.inl QueryKernelFor selects from: (TREE, KIND, STACK, PRIMS)
+#define RL_QUERY_INSTANCES_K(X, K) \
+	X(2, K, 32, false) X(2, K, 32, true) X(2, K, 64, false) X(2, K, 64, true) X(4, K, 32, false) X(4, K, 64, false) X(8, K, 2 * RL_POOL8_MAXLEVELS, false)
+#define RL_QUERY_INSTANCES(X) RL_QUERY_INSTANCES_K(X, 0) RL_QUERY_INSTANCES_K(X, 1) RL_QUERY_INSTANCES_K(X, 2)
+#define RL_K_QUERY(a, b, c, d) template __global__ void k_query<a, b, c, d>(RL_QUERY_ARGS);
+RL_QUERY_INSTANCES(extern RL_K_QUERY)
+
+} // namespace rl

@@ -56,7 +56,7 @@ __device__ __forceinline__ float tan_(float x)  { return rlm::tanf_(x); }
 RL_MATH_CALL float tan_(float x)  { return rlm::tanf_(x); }
 #endif
 #ifndef RL_MATH_INLINE_ACOS
-#define RL_MATH_INLINE_ACOS 1   /* round 3, with Erf / ErfInv: rl_render.hip */
+#define RL_MATH_INLINE_ACOS 1   /* round 3, with Erf / ErfInv: rl_dev_shade.h */
 #endif
 #if RL_MATH_INLINE_ACOS
 __device__ __forceinline__ float acos_(float x) { return rlm::acosf_(x); }
@@ -85,7 +85,7 @@ __device__ __forceinline__ void sincos_(float x, float* s, float* c) { const flo
 __device__ __forceinline__ void sincos_signs_(float x, bool* sn, bool* cn) { rlm::sincosf_signs(x, sn, cn); }
 #endif
 __device__ __forceinline__ float fmod1_(float x) { return fmodf(x, 1.0f); }
-// tanf and powf always inline, for the one kernel instance that may take them so (rl_render.hip RL_PLAIN_INLINE_TAN / _POW)
+// tanf and powf always inline, for the one kernel instance that may take them so (rl_dev_shade.h RL_PLAIN_INLINE_TAN / _POW)
 __device__ __forceinline__ float tan_inline_(float x)  { return rlm::tanf_(x); }
 __device__ __forceinline__ float pow_inline_(float x, float y) { return rlm::powf_(x, y); }
 

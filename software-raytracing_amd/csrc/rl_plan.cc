@@ -98,7 +98,7 @@ TracePlan Pick(const Scene& sc, const RendererSettings& st, bool hasSky, const R
 	if (p.stack == 16 && p.tree == TREE_BOX4 && k.ldsScene != 0 && b.nodes4.size() <= RL_LDS_MAXNODES && ntri <= RL_LDS_MAXTRIS && sc.materials.size() <= RL_LDS_MAXMATS) {
 		p.lds = 1;
 		// ... and a scene of few leaves without a tree (rl_bvh.cc "the leaf list"); RAYLIB_LEAF_LIST=0 walks its BVH4 instead.  Its sortable keys are entry
-		// distances, never negative (rl_render.hip TraverseLeafList): not with rayTMin < 0.
+		// distances, never negative (rl_dev_walk.h TraverseLeafList): not with rayTMin < 0.
 		if (!b.leafList.empty() && b.leafList.size() <= RL_LEAFLIST_RECORDS && ntri <= RL_LEAFLIST_MAXTRIS && k.leafList != 0 && st.rayTMin >= 0.0f) {
 			p.lds = 2; p.tree = TREE_NONE; p.treeWidth = 0;
 			// the instance without the texture, cut-out and sky code computes the same values in the same order for the scenes it takes: those without a texture
@@ -187,7 +187,7 @@ LaunchPlan PlanLaunch(uint32_t numLocalCells, uint32_t numActive, uint32_t spp, 
 		// bits of a band's job count) whatever the environment asked for
 		L.jobChunk = std::max(64u, L.jobChunk & ~63u);
 	}
-	{   // the job list in bands of whole cells, one head per XCD (rl_render.hip TakeJobs)
+	{   // the job list in bands of whole cells, one head per XCD (rl_dev_jobs.h TakeJobs)
 		uint32_t heads = k.jobHeads > 0 ? std::min<uint32_t>(RL_MAX_HEADS, (uint32_t)k.jobHeads) : RL_MAX_HEADS;
 		const uint32_t cellsPerHead = (std::max(1u, numActive) + heads - 1) / heads;
 		heads = (std::max(1u, numActive) + cellsPerHead - 1) / cellsPerHead;   // no empty band: every head's first job exists (and h * jobsPerHead < numJobs < 2^32)

@@ -1,6 +1,6 @@
 // Host runtime of the MI355X raylib: devices, streams, per-rank work buffers, scene upload, launches, and the frame
 // split over several GPUs behind Raylib_Render.  Included at the end of rl_render.hip (the kernels launched here are
-// templates defined there).
+// templates defined or declared there: rl_kernels.h).
 //
 // Ranks.  RAYLIB_NUM_GPUS = N (default 1) makes the library drive N devices from this one process: the frame's 8x8
 // cells are dealt round-robin to N logical ranks (rank r renders cells r, r + N, ...), every rank has its own
@@ -16,6 +16,17 @@
 // Which kernel instance a render launches, on which tree, and its job layout are decided in rl_plan.cc; this file launches what it says.
 
 #include "rl_plan.h"
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <condition_variable>
+#include <functional>
+#include <limits>
+#include <map>
+#include <mutex>
+#include <thread>
+#include <dlfcn.h>
 
 namespace rl {
 
@@ -367,7 +378,7 @@ bool UploadScene(Scene& sc)
 		I.v1[0] = t.v1.x; I.v1[1] = t.v1.y; I.v1[2] = t.v1.z;
 		I.v2[0] = t.v2.x; I.v2[1] = t.v2.y; I.v2[2] = t.v2.z;
 		I.uv = uv; I.uu = uu; I.vv = vv;
-		{   // the reciprocal of denom = uvuv - uuvv for the short barycentric divisions (rl_render.hip Barycentric, which states the conditions)
+		{   // the reciprocal of denom = uvuv - uuvv for the short barycentric divisions (rl_dev_walk.h Barycentric, which states the conditions)
 			const float denom = uvuv - uuvv, mag = fabsf(denom);
 			if (denom == 0.0f || denom != denom) I.rden = std::numeric_limits<float>::quiet_NaN();
 			else if (mag >= 0x1p-62f && mag <= 0x1p125f) I.rden = 1.0f / denom;
@@ -626,7 +637,7 @@ static DRenderParams BaseParams(const RendererSettings& st, uint64_t seed, const
 	DRenderParams P; memset(&P, 0, sizeof(P));
 	const uint32_t W = st.viewportWidth, H = st.viewportHeight, cellsX = (W + 7) / 8;
 	P.width = W; P.height = H; P.spp = (uint32_t)(st.samplesPerPixel > 1 ? st.samplesPerPixel : 1); P.maxPathLength = st.maxPathLength; P.rayTMin = st.rayTMin;
-	P.invWidth = 1.0f / (float)W; P.invHeight = 1.0f / (float)H;   // correctly rounded (IEEE division on the host): rl_render.hip PixelUV
+	P.invWidth = 1.0f / (float)W; P.invHeight = 1.0f / (float)H;   // correctly rounded (IEEE division on the host): rl_dev_jobs.h PixelUV
 	P.renderMode = st.renderMode; P.seed = seed; P.cellsX = cellsX; P.cellsY = (H + 7) / 8;
 	P.cellFirst = cellFirst; P.cellStride = stride; P.numLocalCells = numLocalCells;
 	P.rowMajorOutput = rowMajor ? 1u : 0u; P.camera = camera;

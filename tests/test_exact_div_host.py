@@ -1,4 +1,4 @@
-"""Host restatement of the short divisions of the scattering event (csrc/rl_math.h div_by_, csrc/rl_render.hip RL_EXACT_DIV bits 1 and 2):
+"""Host restatement of the short divisions of the scattering event (csrc/rl_math.h div_by_, csrc/rl_dev_shade.h RL_EXACT_DIV bits 1 and 2):
 q0 = a * y, q = fma(fma(-b, q0, a), y, q0) with y = RN(1 / b), evaluated here with exact rational arithmetic and one rounding per operation,
 and the sign predicate that replaces `dot(V, H) / dot(V, N) <= 0`.  Wherever a site's guard lets the short form through, it must be the
 IEEE quotient bit for bit; the edge cases are zeros of both signs, denormals, 2^-102 / 2^-103 numerators, divisors at 2^-126 and 2^126,
@@ -68,7 +68,7 @@ def rcp(b):
         return f32(1.0) / f32(b)
 
 
-def in_range(q):   # csrc/rl_render.hip QuotientInRange
+def in_range(q):   # csrc/rl_dev_shade.h QuotientInRange
     return abs(q) >= 2.0 ** -91 and abs(q) < 2.0 ** 126
 
 
@@ -132,7 +132,7 @@ def test_tan_theta_guard():
             assert same(div_by(a, c, rcp(c)), ieee(a, c)), (a, c)
 
 
-def not_positive(n, d):   # csrc/rl_render.hip QuotientNotPositive
+def not_positive(n, d):   # csrc/rl_dev_shade.h QuotientNotPositive
     n, d = f32(n), f32(d)
     opposite = bool(np.signbit(n)) != bool(np.signbit(d))
     if n == 0:

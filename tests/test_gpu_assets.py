@@ -120,7 +120,7 @@ def test_scene_with_tga_bmp_jpeg_png_hdr_maps_and_an_hdr_sky(gpu_lib, oracle, wo
 
 def test_more_textures_than_the_pool_kernel_keeps_in_lds(gpu_lib, oracle, workdir, monkeypatch):
     """64 materials with a map each (+ their 64 converted copies: 128 texture descriptors, RL_LDS_TEXTURES is 56): the pool kernel then reads descriptors from
-    global memory (rl_render.hip TexTable), a scene of four maps from its LDS copy -- both must give the oracle's image, and the pool kernel's frame must be
+    global memory (rl_dev_scene.h TexTable), a scene of four maps from its LDS copy -- both must give the oracle's image, and the pool kernel's frame must be
     k_trace's bit for bit.  Every second map has holes (alpha 0 texels): the cut-out test inside the walk takes its texture from the per-triangle table."""
     from raylib_amd import binding
     d = os.path.join(str(workdir), "many_maps"); os.makedirs(d, exist_ok=True)

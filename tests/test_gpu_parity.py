@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 
 def test_rays_through_vertices_and_along_edges_short_barycentrics_against_the_divisions(gpu_lib, workdir, oracle, monkeypatch):
-    """The triangle test's two divisions by `denom` run as six-cycle sequences with the reciprocal from the triangle record (csrc/rl_render.hip
+    """The triangle test's two divisions by `denom` run as six-cycle sequences with the reciprocal from the triangle record (csrc/rl_dev_walk.h
     Barycentric), and a quotient below 2^-38 -- a ray through a vertex, along an edge, or past one by a hair -- sends the lane to the divisions
     themselves.  Random rays never get there; these do: aimed at every vertex, at points ON every edge (exact in float for the axis-aligned
     Cornell walls) and a few ulps to either side.  The same scene uploaded with RAYLIB_FAST_BARY=0 (divisions only) must give the same records

@@ -214,7 +214,7 @@ def test_point_interval_at_a_surface_hits_it(gpu_lib, oracle, iscenes, monkeypat
     """Set 2: [t_k, t_k].  The device must give the oracle's answer, and every ray with a surface at t_k must hit it.  (With the render's candidate rule,
     whose own-box test rejects when the box's exit lies below tMin by as little as an ulp, the oracle and every tree of the device missed 117 of 956 first
     surfaces of the room, 318 of 3696 of the Cornell box and 236 of 2067 of the cut-out scene -- flat boxes of axis-aligned triangles; none of the soup.  The
-    query unit widens that one comparison, csrc/rl_render.hip OwnBoxPassBox, and oracle.cc CandidateRule follows it.)"""
+    query unit widens that one comparison, csrc/rl_dev_walk.h OwnBoxPassBox, and oracle.cc CandidateRule follows it.)"""
     sc, problems, missed = iscenes[name], [], []
     for label, rays, expect in _layer_sets(sc):
         if not label.startswith("2"):

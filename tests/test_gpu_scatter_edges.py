@@ -1,4 +1,4 @@
-"""The scattering event at its degenerate inputs (RaylibAMD_EvalScatter: Scatter / ScatteringPdf / Emitted, csrc/rl_render.hip) against
+"""The scattering event at its degenerate inputs (RaylibAMD_EvalScatter: Scatter / ScatteringPdf / Emitted, csrc/rl_dev_shade.h) against
 the oracle, bit for bit, and whole frames of the same materials on every schedule.
 
 In k_trace and the eval hook the event's divisions take a short exact form (rtm::div_by_) behind guards; when a lane fails its guard the
@@ -24,7 +24,7 @@ Each record set runs in three layouts: every family alone in whole waves of 64; 
 31 and 63; everything shuffled.  The stream of record i is (seed, i, 0) on both sides, so each layout is compared with the oracle run
 on the same array: a regular lane must not depend on the degenerate lane of its wave.
 
-CPU part: the float32 restatement of the frame k_eval_scatter builds (T, B, WorldToLocal in rl_render.hip's operation order) proves the
+CPU part: the float32 restatement of the frame k_eval_scatter builds (T, B, WorldToLocal in the operation order of rl_render.hip k_eval_scatter) proves the
 exact zeros the families promise, and the seeds' draws."""
 import ctypes as C
 import os
@@ -143,7 +143,7 @@ def _normalize(a):
 
 
 def frame(n):
-    """T, B of `n` ((N, 3) float32) with rl_render.hip's operations in its order: T0 = y if |n.x| > 0.9 else x, B = normalize(T0 x n),
+    """T, B of `n` ((N, 3) float32) with the operations of rl_render.hip k_eval_scatter in their order: T0 = y if |n.x| > 0.9 else x, B = normalize(T0 x n),
     T = normalize(n x B)."""
     n = np.asarray(n, F)
     t0 = np.where((np.abs(n[:, 0]) > F(0.9))[:, None], np.array([0, 1, 0], F), np.array([1, 0, 0], F)).astype(F)

@@ -1,4 +1,4 @@
-"""Texture2D::Sample at its edges (RaylibAMD_EvalTexture: TexFetch, csrc/rl_render.hip) against the oracle, bit for bit.
+"""Texture2D::Sample at its edges (RaylibAMD_EvalTexture: TexFetch, csrc/rl_dev_scene.h) against the oracle, bit for bit.
 
 Every lookup wraps its UVs with the device's fmodf (rtm::fmod1_ -- ocml's, not glibc's), adds 1 to a negative remainder, flips v and
 scales by (size - 1).  The known-answer test of the contract tier uses one 16 x 16 texture and UVs in [-3, 3]; here the textures are 1,

@@ -220,7 +220,7 @@ def test_larger_scenes_carry_a_valid_eight_wide_tree(lib, workdir, monkeypatch):
 @pytest.mark.parametrize("make,kw", [(scenes.cornell, dict(tess=24, displace_fraction=0.2)), (scenes.cornell, dict(tess=64, displace_fraction=0.2)),
                                       (scenes.soup, dict(n_tris=6000, seed=9)), (scenes.colonnade, dict(tess=3))], ids=["room_21k", "room_147k_split_leaves", "soup_6k", "colonnade_10k"])
 def test_eight_wide_walk_restated_on_the_host_never_skips_the_closest_hit(make, kw, lib, oracle, workdir, monkeypatch):
-    """The megakernel's 8-wide walk restated on the host (RaylibAMD_SceneWalk8Host: the same float operations as rl_render.hip NodeStep8 -- half-float planes
+    """The megakernel's 8-wide walk restated on the host (RaylibAMD_SceneWalk8Host: the same float operations as rl_dev_pool.h NodeStep8 -- half-float planes
     through one fma each, the ray's widened factors, visiting order, groups) against the oracle's closest hit: with the exit distance fixed just behind the
     oracle's hit the walk must reach the leaf that holds it, for rays in random directions AND for rays that lie IN the planes of the scene's walls -- second
     generation rays from hit points towards a sun whose direction has exact zero components (+0 and -0), origins exactly on a plane, where (corner - o) * inv is

@@ -91,7 +91,7 @@ def build_objects():
     os.makedirs(WORK, exist_ok=True)
     flags = "-std=c++17 -O3 -fPIC -ffp-contract=off -fno-slp-vectorize -fvisibility=hidden -DRAYLIB_EXPORTS=1 -I%s/../include -I%s/csrc --offload-arch=gfx950 --cuda-device-only -gline-tables-only" % (SRC, SRC)
     units = {"rl_render": "", "rl_render_pool": "-mllvm -amdgpu-sched-strategy=iterative-ilp -DRL_EXACT_FAST_RCP_SQRT=0"}
-    srcs = [os.path.join(SRC, "csrc", f) for f in os.listdir(os.path.join(SRC, "csrc")) if f.endswith((".hip", ".h", ".inl"))] + [os.path.join(ROOT, "include", "raylib_amd_rng.h")]
+    srcs = source_files() + [os.path.join(ROOT, "include", "raylib_amd_rng.h")]
     newest = max(os.path.getmtime(f) for f in srcs)
     out = {}
     for u, extra in units.items():
@@ -167,102 +167,139 @@ def symbolize(elf, addrs):
     return out
 
 
+def source_files():
+    d = os.path.join(SRC, "csrc")
+    return sorted(os.path.join(d, f) for f in os.listdir(d) if f.endswith((".hip", ".h", ".inl")))
+
+
+# the markers every region rule needs: a missing one would send its instructions to another region without a word
+REQUIRED = ("ll", "ll_from", "ll_tri", "ll_inner", "ll_tri_end", "b11", "newton", "newton_end", "LeafStep_inner", "LeafStep8_inner", "pool_hits", "pool_hits_end",
+            "pool_fetch", "pool_fetch_end", "pool_fin", "pool_fin_end", "scatter", "scatter_end")
+
+
 def source_markers():
-    """Line numbers the region rules hang on: the kernels' phase stamps and the loops inside TraverseLeafList / BeckmannSample11."""
-    src = open(os.path.join(SRC, "csrc", "rl_render.hip")).read().split("\n")
-    mk = {"stamp": [], "pstamp": []}
-    for i, l in enumerate(src, 1):
-        s = l.strip()
-        if re.match(r"RL_STAMP\(\d\);", s):
-            mk["stamp"].append(i)
-        if re.match(r"RL_PSTAMP\(\d\);", s):
-            mk["pstamp"].append(i)
-        if "bool TraverseLeafList(" in l:
-            mk["ll"] = i
-        if "ll" in mk and "ll_from" not in mk and s.startswith("uint32_t from = 0u;"):
-            mk["ll_from"] = i
-        if "ll_from" in mk and "ll_tri" not in mk and s.startswith("for (int i = 0; i < count; ++i) {"):
-            mk["ll_tri"] = i
-        if "ll_tri" in mk and "ll_inner" not in mk and s.startswith("const V3 p = o + t * d;"):
-            mk["ll_inner"] = i
-        if "ll_tri" in mk and "ll_tri_end" not in mk and i > mk["ll_tri"] and s.startswith("m = 0xffffffffu;"):
-            mk["ll_tri_end"] = i
-        if "void BeckmannSample11(" in l:
-            mk["b11"] = i
-        if "b11" in mk and "newton" not in mk and s.startswith("while (++it < "):
-            mk["newton"] = i
-        if "newton" in mk and "newton_end" not in mk and i > mk["newton"] and s.startswith("b -= value / derivative;"):
-            mk["newton_end"] = i + 1
-        m = re.search(r"bool (LeafStep8?)\(", l)
-        if m:
-            mk["_leaf"] = m.group(1)
-        if mk.get("_leaf") and s.startswith("const V3 pp = o + t * d;") and mk["_leaf"] + "_inner" not in mk:
-            mk[mk["_leaf"] + "_inner"] = (i, i + 9)
-        if "RL_WSTEP(7);" in l:
-            mk["pool_hits"] = i
-        if "pool_hits" in mk and "pool_hits_end" not in mk and s.startswith("shadedEnd += 64u;"):
-            mk["pool_hits_end"] = i
-        if "if (nextSlot < (uint32_t)PP) {" in l and "pool_fetch" not in mk:
-            mk["pool_fetch"] = i
-        if "pool_fetch" in mk and "pool_fetch_end" not in mk and s.startswith("nextSlot += (uint32_t)__popcll(idle);"):
-            mk["pool_fetch_end"] = i
-        if "if (fin) {" in l and "pool_fin" not in mk and "pool_fetch_end" in mk:
-            mk["pool_fin"] = i
-        if "pool_fin" in mk and "pool_fin_end" not in mk and s.startswith("T.cur = IDLE;"):
-            mk["pool_fin_end"] = i + 1
-        if "__device__ __forceinline__ bool Scatter(" in l:
-            mk["scatter"] = i; mk["arms"] = []
-        if "scatter" in mk and "scatter_end" not in mk:
-            m = re.match(r"(case (MAT_\w+)|default):", s)
+    """(file, line) pairs the region rules hang on, collected over every source of csrc: the kernels' phase stamps and the loops inside TraverseLeafList /
+    BeckmannSample11 / the pool kernel.  A marker is looked for after the one it follows IN THE SAME FILE.  Fails when one is not found."""
+    out = {"stamp": [], "pstamp": [], "arms": []}
+    for path in source_files():
+        fn = os.path.basename(path)
+        mk = {}   # this file's markers: name -> line
+        for i, l in enumerate(open(path).read().split("\n"), 1):
+            s = l.strip()
+            if re.match(r"RL_STAMP\(\d\);", s):
+                out["stamp"].append((fn, i))
+            if re.match(r"RL_PSTAMP\(\d\);", s):
+                out["pstamp"].append((fn, i))
+            if "bool TraverseLeafList(" in l:
+                mk["ll"] = i
+            if "ll" in mk and "ll_from" not in mk and s.startswith("uint32_t from = 0u;"):
+                mk["ll_from"] = i
+            if "ll_from" in mk and "ll_tri" not in mk and s.startswith("for (int i = 0; i < count; ++i) {"):
+                mk["ll_tri"] = i
+            if "ll_tri" in mk and "ll_inner" not in mk and s.startswith("const V3 p = o + t * d;"):
+                mk["ll_inner"] = i
+            if "ll_tri" in mk and "ll_tri_end" not in mk and i > mk["ll_tri"] and s.startswith("m = 0xffffffffu;"):
+                mk["ll_tri_end"] = i
+            if "void BeckmannSample11(" in l:
+                mk["b11"] = i
+            if "b11" in mk and "newton" not in mk and s.startswith("while (++it < "):
+                mk["newton"] = i
+            if "newton" in mk and "newton_end" not in mk and i > mk["newton"] and s.startswith("b -= value / derivative;"):
+                mk["newton_end"] = i + 1
+            m = re.search(r"bool (LeafStep8?)\(", l)
             if m:
-                mk["arms"].append((i, (m.group(2) or "MAT_MICROFACET").replace("MAT_", "").lower()))
-            if i > mk["scatter"] and l.startswith("}"):
-                mk["scatter_end"] = i
-    return mk
+                mk["_leaf"] = m.group(1)
+            if mk.get("_leaf") and s.startswith("const V3 pp = o + t * d;") and mk["_leaf"] + "_inner" not in mk:
+                mk[mk["_leaf"] + "_inner"] = i
+                mk[mk["_leaf"] + "_inner_end"] = i + 9
+            if "RL_WSTEP(7);" in l:
+                mk["pool_hits"] = i
+            if "pool_hits" in mk and "pool_hits_end" not in mk and s.startswith("shadedEnd += 64u;"):
+                mk["pool_hits_end"] = i
+            if "if (nextSlot < (uint32_t)PP) {" in l and "pool_fetch" not in mk:
+                mk["pool_fetch"] = i
+            if "pool_fetch" in mk and "pool_fetch_end" not in mk and s.startswith("nextSlot += (uint32_t)__popcll(idle);"):
+                mk["pool_fetch_end"] = i
+            if "if (fin) {" in l and "pool_fin" not in mk and "pool_fetch_end" in mk:
+                mk["pool_fin"] = i
+            if "pool_fin" in mk and "pool_fin_end" not in mk and s.startswith("T.cur = IDLE;"):
+                mk["pool_fin_end"] = i + 1
+            if "__device__ __forceinline__ bool Scatter(" in l:
+                mk["scatter"] = i
+            if "scatter" in mk and "scatter_end" not in mk:
+                m = re.match(r"(case (MAT_\w+)|default):", s)
+                if m:
+                    out["arms"].append((fn, i, (m.group(2) or "MAT_MICROFACET").replace("MAT_", "").lower()))
+                if i > mk["scatter"] and l.startswith("}"):
+                    mk["scatter_end"] = i
+        mk.pop("_leaf", None)
+        for k, line in mk.items():
+            if k in out:
+                raise SystemExit("dynamic_mix: marker %r found in %s:%d and in %s:%d" % (k, out[k][0], out[k][1], fn, line))
+            out[k] = (fn, line)
+    missing = [k for k in REQUIRED if k not in out]
+    if len(out["stamp"]) != 4 or len({f for f, _ in out["stamp"]}) != 1:
+        missing.append("4 x RL_STAMP(n); in one file (found %s)" % out["stamp"])
+    if len(out["pstamp"]) != 3 or len({f for f, _ in out["pstamp"]}) != 1:
+        missing.append("3 x RL_PSTAMP(n); in one file (found %s)" % out["pstamp"])
+    if len(out["arms"]) != 6:
+        missing.append("the six arms of Scatter's switch (found %s)" % out["arms"])
+    if missing:
+        raise SystemExit("dynamic_mix: source markers not found under %s/csrc: %s" % (SRC, "; ".join(missing)))
+    return out
+
+
+def between(mk, lo, hi, fn, line, before=0):
+    """fn:line lies in the closed range of the markers lo .. hi (of one file)"""
+    return mk[lo][0] == fn == mk[hi][0] and mk[lo][1] - before <= line <= mk[hi][1]
 
 
 def region_of(frames, pool, mk):
     names = [f for f, _, _ in frames]
-    for f, line, _ in frames:
-        if f == "BeckmannSample11" and mk.get("newton", 1 << 30) <= line <= mk.get("newton_end", 0):
+    for f, line, fn in frames:
+        if f == "BeckmannSample11" and between(mk, "newton", "newton_end", fn, line):
             return "newton iteration"
         if f in ("TexFetch", "TexSample", "AlphaTestCandidate", "AlphaTestCandidateNI"):
             return "texel fetch"
-    for f, line, _ in frames:
-        if f == "Scatter" and mk.get("arms"):
-            arm = [name for (l0, name) in mk["arms"] if l0 <= line]
+    for f, line, fn in frames:
+        if f == "Scatter":
+            arm = [name for (afn, l0, name) in mk["arms"] if afn == fn and l0 <= line]
             if arm:
                 return "scatter: " + arm[-1]
-    for f, line, _ in frames:
+    for f, line, fn in frames:
         if f in ("TraverseLeafList", "TraverseLeafListAny"):
+            if line and fn != mk["ll"][0]:   # (line 0: a merged location, its file means nothing; counts as the walk's set-up)
+                raise SystemExit("dynamic_mix: a frame of %s lies in %s, its markers in %s" % (f, fn, mk["ll"][0]))
             pre = "leaf list: " if f == "TraverseLeafList" else "sun query's leaf list: "
-            if line < mk["ll_from"]:
-                return pre + ("boxes" if line > mk["ll"] + 12 else "set-up")
-            if mk["ll_tri"] <= line < mk["ll_tri_end"]:
-                return pre + ("inside test" if line >= mk.get("ll_inner", 1 << 30) else "triangle step")
+            if line < mk["ll_from"][1]:
+                return pre + ("boxes" if line > mk["ll"][1] + 12 else "set-up")
+            if mk["ll_tri"][1] <= line < mk["ll_tri_end"][1]:
+                return pre + ("inside test" if line >= mk["ll_inner"][1] else "triangle step")
             return pre + "pick"
     if any(n.startswith("NodeStep") for n in names):
         return "node step"
-    for f, line, _ in frames:
-        if f.startswith("LeafStep"):
-            lo, hi = mk.get(f + "_inner", (1 << 30, 0))
-            return "triangle step: inside test" if lo <= line <= hi else "triangle step"
+    for f, line, fn in frames:
+        if f in ("LeafStep", "LeafStep8"):
+            return "triangle step: inside test" if between(mk, f + "_inner", f + "_inner_end", fn, line) else "triangle step"
     if any(n.startswith("LeafStep") for n in names):
         return "triangle step"
     if any(n in ("Traverse4", "Traverse") for n in names):
         return "tree walk"
-    kline = frames[-1][1]
+    # the kernel's own line, against the stamps of the kernel's file (an instruction without a line, compiler-made, counts as before the first stamp)
+    _, kline, kfn = frames[-1]
     stamps = mk["pstamp"] if pool else mk["stamp"]
-    phase = sum(1 for s in stamps if kline > s)
+    if kline and kfn != stamps[0][0]:
+        raise SystemExit("dynamic_mix: kernel-level line %s:%d is not in the file of the kernel's stamps (%s)" % (kfn, kline, stamps[0][0]))
+    phase = sum(1 for _, s in stamps if kline > s)
     if pool:
         if phase == 1:
-            if mk.get("pool_fetch", 1 << 30) <= kline <= mk.get("pool_fetch_end", 0):
+            if between(mk, "pool_fetch", "pool_fetch_end", kfn, kline):
                 return "fetch a ray"
-            if mk.get("pool_fin", 1 << 30) <= kline <= mk.get("pool_fin_end", 0):
+            if between(mk, "pool_fin", "pool_fin_end", kfn, kline):
                 return "traversal: a ray ends"
             return "traversal: turn"
         if phase == 2:
-            if mk.get("pool_hits", 1 << 30) - 12 <= kline <= mk.get("pool_hits_end", 0):
+            if between(mk, "pool_hits", "pool_hits_end", kfn, kline, before=12):
                 return "shade: a round of hits"
             return "shade: misses + hand-back"
         return ("refill", "traversal: turn", "shade", "epilogue")[min(phase, 3)]
@@ -294,11 +331,13 @@ def analyse(kernel_mangled, elf, measured):
         return h
 
     regions = collections.defaultdict(collections.Counter)
+    own = collections.Counter()   # the kernel's own instructions by region (the callees' come on top, once per call site)
     ktargets = calls[kname]
     for addr, op, _ in insts:
         fr = sym.get(addr) or [("?", 0, "?")]
         r = region_of(fr, pool, mk)
         regions[r][op] += 1
+        own[r] += 1
         if op == "s_swappc_b64" and ktargets.get(addr) in funcs:
             regions[r] += flat(ktargets[addr])
     # The compiler unrolls the Beckmann sampler's Newton loop (nine copies whatever `#pragma nounroll` says: its trip count is a constant); one RUN of the region
@@ -309,6 +348,8 @@ def analyse(kernel_mangled, elf, measured):
         if copies > 1:
             regions["newton iteration"] = collections.Counter({op: c / copies for op, c in nw.items()})
             print("   (the Newton loop is %d copies in the binary; a run of the region is one of them)" % copies)
+    print("   %s: %d instructions in %d regions: %s" % (kname.split("EvNS")[0], len(insts), len(own), ", ".join("%s %d" % kv for kv in sorted(own.items()))))
+    assert sum(own.values()) == len(insts)
     return kname, regions
 
 

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""Per-kernel device-code comparison of two builds of one HIP translation unit (gfx950).
+"""Per-function device-code comparison of two builds of one HIP translation unit (gfx950).
 
 usage: tools/isa_equivalence.py PARENT.o NEW.o
 
 For every kernel of PARENT.o: its instructions (PC-relative address arithmetic after s_getpc_b64 masked), its kernel descriptor (64 bytes
-minus the code-entry offset) and its metadata (registers, LDS, scratch, kernarg size).  Kernels only NEW.o has are listed apart.  Exit
-status 1 when a kernel of PARENT.o differs or is missing.  Needs the ROCm LLVM tools (llvm-objcopy, clang-offload-bundler, llvm-objdump,
+minus the code-entry offset) and its metadata (registers, LDS, scratch, kernarg size).  Kernels only NEW.o has are listed apart.  Then every
+other function symbol of the code object -- the out-of-line device functions the kernels call through those masked addresses -- by its
+instructions, normalised the same way; one that only PARENT.o or only NEW.o has counts as a difference.  Exit status 1 when a kernel of
+PARENT.o differs or is missing, or a function differs.  Needs the ROCm LLVM tools (llvm-objcopy, clang-offload-bundler, llvm-objdump,
 llvm-readelf); runs on the host, no device.
 """
 import os
@@ -74,6 +76,18 @@ def descriptors(co):
     return out
 
 
+def device_functions(co):
+    """the FUNC symbols that are not kernels (no <name>.kd beside them)"""
+    names, kds = set(), set()
+    for line in tool("llvm-readelf", "-s", "-W", co).splitlines():
+        p = line.split()
+        if len(p) >= 8 and p[-1].endswith(".kd"):
+            kds.add(p[-1][:-3])
+        elif len(p) >= 8 and p[3] == "FUNC" and p[6] != "UND":
+            names.add(p[-1])
+    return names - kds
+
+
 def metadata(co):
     """kernel -> sorted scalar metadata lines (.sgpr_count, .vgpr_count, LDS, scratch, ...)"""
     text = tool("llvm-readelf", "--notes", co)
@@ -93,6 +107,7 @@ def main():
         fa, fb = functions(a), functions(b)
         da, db = descriptors(a), descriptors(b)
         ma, mb = metadata(a), metadata(b)
+        na, nb = device_functions(a), device_functions(b)
     bad = 0
     for k in sorted(da):
         what = []
@@ -109,8 +124,13 @@ def main():
         print("%-8s %5d instructions  %s" % ("DIFFERS" if what else "same", len(fa.get(k, [])), k) + ("  (" + ", ".join(what) + ")" if what else ""))
     for k in sorted(set(db) - set(da)):
         print("new      %5d instructions  %s" % (len(fb.get(k, [])), k))
-    print("%d kernel(s) of the parent, %d differ" % (len(da), bad))
-    return 1 if bad else 0
+    badFn = 0
+    for k in sorted(na | nb):
+        what = "only in the parent" if k not in nb else "only in the new object" if k not in na else "instructions" if fa.get(k) != fb.get(k) else ""
+        badFn += bool(what)
+        print("%-8s %5d instructions  %s  [function]" % ("DIFFERS" if what else "same", len((fa if k in na else fb).get(k, [])), k) + ("  (" + what + ")" if what else ""))
+    print("%d kernel(s) of the parent, %d differ; %d other function(s), %d differ" % (len(da), bad, len(na | nb), badFn))
+    return 1 if bad or badFn else 0
 
 
 if __name__ == "__main__":

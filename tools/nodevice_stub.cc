@@ -1,4 +1,4 @@
-// Sanitizer harness only (tools/asan_host_check.sh): stands in for csrc/rl_render.hip so that the HOST side of the
+// Sanitizer harness only (tools/asan_host_check.sh): stands in for the unit of csrc/rl_render.hip (kernels and runtime) so that the HOST side of the
 // library (ABI, OBJ/MTL loader, BVH builder, codecs, registries) can be built with g++ -fsanitize=address,undefined
 // and run through tests/test_host_logic.py.  Never part of libraylib.so.
 #include "rl_host.h"

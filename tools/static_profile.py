@@ -1,6 +1,6 @@
 """Static cost profile of one kernel by SOURCE LINE: hipcc -gline-tables-only -S keeps a .loc in front of every instruction; each VALU instruction is
 priced with the measured issue cost of its opcode (tools/static_mix.py cost table = profiles/valu_calib.json) and charged to the source function it
-was inlined from (the line's enclosing function in rl_render.hip / rl_glibc_math.h ...).  Every instruction counts ONCE: loops and branches are not
+was inlined from (the line's enclosing function in the device library, csrc/rl_dev_*.h / rl_k_*.inl / rl_glibc_math.h ...).  Every instruction counts ONCE: loops and branches are not
 weighted, so this shows how dear one pass through each piece of code is, not how often it runs (wave-step counters give that: RL_DIAG_STAMPS=2).
 
 usage: python tools/static_profile.py <file.s from hipcc -gline-tables-only --cuda-device-only -S> <mangled kernel substring>"""
