@@ -242,6 +242,14 @@ RAYLIB_API int32_t RaylibAMD_SceneBVH8Info(SceneHandle scene, uint32_t* outNodes
  * arithmetic must never do -- skip the leaf of the closest hit -- is checked against the CPU oracle in `pytest -m "not gpu"`.  rays: count x (origin, direction).
  * Returns 1, 0 without such a tree, -1 on a malformed tree. */
 RAYLIB_API int32_t RaylibAMD_SceneWalk8Host(SceneHandle scene, const float* rays, int32_t count, float tMin, const float* tMax, float* outT, uint32_t* outSteps);
+/* The stack discipline of the device walks restated on the host (csrc/rl_bvh.cc WalkStackHost), with the stack's capacity as an argument.  tree 2: the binary
+ * tree (Traverse / NodeStep), 3: the 4-wide float boxes (Traverse4 of k_trace's FULL instances), 4: the 4-wide grid nodes (Traverse4 / NodeStep4), 8: the 8-wide tree (NodeStep8; capacity counts groups).  Box tests and child order
+ * in float as on the device, the exit distance shrinking with the best hit, and the device's guard: a push at sp == capacity is dropped.  outT[i] = the closest hit
+ * over [tMin, FLT_MAX] by the reference's triangle test and the ray queries' candidate rule (spheres and cubes, tree 2, at ray time 0; no cut-out test; INFINITY: none);
+ * outHighWater[i] (may be NULL) = the most entries ray i held.  At the capacity rl_plan.cc gives an instance every ray must get the brute-force answer; at one less a
+ * ray that fills the stack loses a subtree (tests/test_stack_edges_host.py).  rays: count x (origin, direction).  Returns 1, 0 for a bad argument or a scene
+ * without that tree, -1 on a malformed tree.  No device needed. */
+RAYLIB_API int32_t RaylibAMD_SceneWalkStackHost(SceneHandle scene, int32_t tree, const float* rays, int32_t count, float tMin, int32_t capacity, float* outT, uint32_t* outHighWater);
 /* The leaf list of a small scene (at most 24 leaves, 108 triangles): what k_trace walks instead of the tree when the scene is LDS-resident.
  * Returns the number of leaves (0 = the scene has none); the list's validity is part of RaylibAMD_SceneBVH4Info's check. */
 RAYLIB_API int32_t RaylibAMD_SceneLeafListInfo(SceneHandle scene, uint32_t* outMaxTrianglesPerLeaf);

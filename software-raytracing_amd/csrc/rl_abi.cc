@@ -823,6 +823,13 @@ int32_t RaylibAMD_SceneWalk8Host(SceneHandle sh, const float* rays, int32_t coun
 	if (!s || !s->finalized || s->bvh.nodes8.empty() || !rays || !tMax || !outT || count < 0) return 0;
 	return Walk8Host(s->bvh, s->triangles, rays, count, tMin, tMax, outT, outSteps) ? 1 : -1;
 }
+int32_t RaylibAMD_SceneWalkStackHost(SceneHandle sh, int32_t tree, const float* rays, int32_t count, float tMin, int32_t capacity, float* outT, uint32_t* outHighWater)
+{
+	Scene* s = (Scene*)sh;
+	if (!s || !s->finalized || !rays || !outT || count < 0 || capacity < 0 || (tree != 2 && tree != 3 && tree != 4 && tree != 8)) return 0;
+	if (tree == 2 ? s->bvh.nodes.empty() : tree == 3 ? s->bvh.nodes4.empty() : tree == 4 ? s->bvh.nodes4q.empty() : s->bvh.nodes8.empty()) return 0;
+	return WalkStackHost(s->bvh, s->triangles, s->spheres, s->cubes, tree, rays, count, tMin, capacity, outT, outHighWater) ? 1 : -1;
+}
 int32_t RaylibAMD_SceneLeafListInfo(SceneHandle sh, uint32_t* maxPerLeaf)
 {
 	Scene* s = (Scene*)sh;

@@ -1073,4 +1073,207 @@ bool Walk8Host(const BVH& bvh, const std::vector<HostTriangle>& tris, const floa
 	return true;
 }
 
+// The stack discipline of the device walks on the host, with the stack's capacity as an argument: Traverse (tree 2: rl_dev_walk.h, NodeStep of rl_dev_pool.h is the
+// same step), Traverse4 on the float boxes (tree 3: RL_WIDE_STEP_F) and on the grid nodes (tree 4: RL_WIDE_STEP_Q; NodeStep4 is the same step) with the 5-comparator sort and far-to-near pushes, and the walk of groups on
+// the 8-wide tree (tree 8: NodeStep8 / Push8; capacity in groups) -- the box arithmetic in float, operation by operation, the exit distance shrinking with the
+// best hit as on the device, and the device's guard: a push at sp == capacity is DROPPED, silently.  The triangle test is the reference's (geom/triangle.cc:18-58,
+// the host's f3 arithmetic is the device record's) with the ray queries' candidate rule (OwnBoxPassBox under RL_OWN_BOX_WIDEN_TMIN); spheres and cubes (tree 2) as
+// SphereHit / CubeHit at ray time 0; no cut-out test.  outT[i]: the closest accepted hit over [tMin, FLT_MAX] (INFINITY: none); outHighWater[i]: the largest sp
+// the ray reached, counting only pushes that were stored.  What a test proves with it: at the instance's capacity every ray gets the brute-force answer and some
+// ray fills the stack to the builder's reported need; at one entry less some ray loses its hit (tests/test_stack_edges_host.py).
+bool WalkStackHost(const BVH& bvh, const std::vector<HostTriangle>& tris, const std::vector<HostSphere>& spheres, const std::vector<HostCube>& cubes, int tree,
+                   const float* rays, int n, float tMin, int capacity, float* outT, uint32_t* outHighWater)
+{
+	if (capacity < 0 || (tree != 2 && tree != 3 && tree != 4 && tree != 8)) return false;
+	if (tree == 2 ? bvh.nodes.empty() : tree == 3 ? bvh.nodes4.empty() : tree == 4 ? bvh.nodes4q.empty() : bvh.nodes8.empty()) return false;
+	const float widen = 1.00001f, slack = 1.000009f;   // RL_BOX_WIDEN, RL_CANDIDATE_SLACK
+	auto clampInv = [](float x) { return std::isinf(x) ? copysignf(1e30f, x) : x; };
+	for (int r = 0; r < n; ++r) {
+		const float* ray = rays + 6 * (size_t)r;
+		const f3 o = F3(ray[0], ray[1], ray[2]), d = F3(ray[3], ray[4], ray[5]);
+		const float oa[3] = { o.x, o.y, o.z };
+		const float inv[3] = { 1.0f / d.x, 1.0f / d.y, 1.0f / d.z };                         // exact: the binary tree's boxes and the candidate rule
+		const float invc[3] = { clampInv(inv[0]), clampInv(inv[1]), clampInv(inv[2]) };      // the grid trees' boxes
+		float best = INFINITY;
+		// one triangle slot, as the leaf code of every walk tests it
+		auto triangle = [&](uint32_t slot) -> bool {
+			if (slot >= bvh.triOrder.size() || bvh.triOrder[slot] >= tris.size()) return false;
+			const HostTriangle& T = tris[bvh.triOrder[slot]];
+			const f3 nrm = normalize(cross(T.v1 - T.v0, T.v2 - T.v0));
+			const float t = dot((T.v0 - o), nrm) / dot(d, nrm);
+			if (!(t >= tMin && t <= FLT_MAX && t < best)) return true;
+			const f3 p = o + t * d;
+			const f3 u = T.v1 - T.v0, v = T.v2 - T.v0, w = p - T.v0;
+			const float uv = dot(u, v), wv = dot(w, v), uu = dot(u, u), vv = dot(v, v), wu = dot(w, u);
+			const float denom = uv * uv - uu * vv;
+			const float pa = (uv * wv - vv * wu) / denom, pb = (uv * wu - uu * wv) / denom;
+			if (!(0.0f <= pa && 0.0f <= pb && pa + pb <= 1.0f)) return true;
+			const f3 mn = fmin3(fmin3(T.v0, T.v1), T.v2), mx = fmax3(fmax3(T.v0, T.v1), T.v2);
+			const float mna[3] = { mn.x, mn.y, mn.z }, mxa[3] = { mx.x, mx.y, mx.z };
+			float lo = -INFINITY, hi = FLT_MAX; bool ok = true;
+			for (int a = 0; a < 3; ++a) {
+				float t0 = (mna[a] - oa[a]) * inv[a], t1 = (mxa[a] - oa[a]) * inv[a];
+				if (inv[a] < 0.0f) std::swap(t0, t1);
+				lo = fmaxf(lo, t0); hi = fminf(hi, t1);
+				if (hi < lo) ok = false;
+			}
+			if (ok && !(hi * widen < tMin) && t * slack >= fmaxf(lo, tMin)) best = t;
+			return true;
+		};
+		uint32_t high = 0;
+		if (tree == 2 || tree == 3 || tree == 4) {
+			std::vector<int32_t> stk((size_t)capacity + 1);
+			int sp = 0;
+			auto push = [&](int32_t v) { if (sp < capacity) { stk[(size_t)sp] = v; ++sp; high = std::max(high, (uint32_t)sp); } };
+			int32_t cur = 0;
+			const int32_t DONE = 0x7fffffff;
+			for (;;) {
+				while (cur >= 0 && cur != DONE) {
+					const float tmx = fminf(best, FLT_MAX);
+					if (tree == 2) {
+						if ((size_t)cur >= bvh.nodes.size()) return false;
+						const DNode& nd = bvh.nodes[(size_t)cur];
+						auto slab = [&](const float* mn, const float* mx, float& tNear) {
+							float tn = tMin, tf = tmx;
+							for (int a = 0; a < 3; ++a) {
+								const bool neg = inv[a] < 0.0f;
+								tn = fmaxf(tn, ((neg ? mx[a] : mn[a]) - oa[a]) * inv[a]); tf = fminf(tf, ((neg ? mn[a] : mx[a]) - oa[a]) * inv[a]);
+							}
+							tNear = tn;
+							return !(tf * widen < tn);
+						};
+						float tl, tr;
+						const bool hl = slab(nd.lmin, nd.lmax, tl) && nd.left != DNODE_EMPTY, hr = slab(nd.rmin, nd.rmax, tr) && nd.right != DNODE_EMPTY;
+						if (hl && hr) { const bool leftFirst = tl <= tr; push(leftFirst ? nd.right : nd.left); cur = leftFirst ? nd.left : nd.right; }
+						else if (hl) cur = nd.left;
+						else if (hr) cur = nd.right;
+						else if (sp == 0) cur = DONE;
+						else cur = stk[(size_t)--sp];
+					} else {
+						float t[4]; int32_t c[4];
+						if (tree == 3) {   // RL_WIDE_STEP_F: the float boxes, the exact reciprocals
+							if ((size_t)cur >= bvh.nodes4.size()) return false;
+							const DNode4& nd = bvh.nodes4[(size_t)cur];
+							for (int k = 0; k < 4; ++k) {
+								float tn = tMin, tf = tmx;
+								for (int a = 0; a < 3; ++a) {
+									const bool neg = inv[a] < 0.0f;
+									tn = fmaxf(tn, ((neg ? nd.hi[a][k] : nd.lo[a][k]) - oa[a]) * inv[a]); tf = fminf(tf, ((neg ? nd.lo[a][k] : nd.hi[a][k]) - oa[a]) * inv[a]);
+								}
+								c[k] = nd.child[k];
+								t[k] = (tf * widen < tn || c[k] == DNODE_EMPTY) ? INFINITY : tn;
+							}
+						} else {
+							if ((size_t)cur >= bvh.nodes4q.size()) return false;
+							const DNode4Q& nd = bvh.nodes4q[(size_t)cur];
+							const float step[3] = { nd.stepX, nd.stepY, nd.stepZ };
+							float A[3], Bn[3], Bf[3];
+							for (int a = 0; a < 3; ++a) {
+								A[a] = step[a] * invc[a];
+								const float B = (nd.origin[a] - oa[a]) * invc[a];
+								const float E = fabsf(A[a] * 1.21593475e-4f) + fabsf(B * 4.76837158e-7f);
+								Bn[a] = B - E; Bf[a] = B + E;
+							}
+							for (int k = 0; k < 4; ++k) {
+								float tn = tMin, tf = tmx;
+								for (int a = 0; a < 3; ++a) {
+									const bool neg = invc[a] < 0.0f;
+									const uint32_t qn = ((neg ? nd.qhi[a] : nd.qlo[a]) >> (8 * k)) & 0xffu, qf = ((neg ? nd.qlo[a] : nd.qhi[a]) >> (8 * k)) & 0xffu;
+									tn = fmaxf(tn, fmaf((float)qn, A[a], Bn[a])); tf = fminf(tf, fmaf((float)qf, A[a], Bf[a]));
+								}
+								c[k] = nd.child[k];
+								t[k] = (tf * widen < tn || c[k] == DNODE_EMPTY) ? INFINITY : tn;
+							}
+						}
+						auto cswap = [&](int i, int j) { if (t[j] < t[i]) { std::swap(t[i], t[j]); std::swap(c[i], c[j]); } };
+						cswap(0, 1); cswap(2, 3); cswap(0, 2); cswap(1, 3); cswap(1, 2);
+						if (!(t[0] < INFINITY)) { if (sp == 0) cur = DONE; else cur = stk[(size_t)--sp]; continue; }
+						if (t[3] < INFINITY) push(c[3]);
+						if (t[2] < INFINITY) push(c[2]);
+						if (t[1] < INFINITY) push(c[1]);
+						cur = c[0];
+					}
+				}
+				if (cur == DONE) break;
+				const uint32_t code = (uint32_t)~cur, first = code >> 6, count = (code & 7u) + 1u, kind = (code >> 4) & 3u;
+				if (kind == PRIM_TRIANGLE) {
+					for (uint32_t i = 0; i < count; ++i) if (!triangle(first + i)) return false;
+				} else if (kind == PRIM_SPHERE) {
+					if (first >= spheres.size()) return false;
+					const HostSphere& s = spheres[first];
+					const f3 oc = o - s.center;
+					const float a = dot(d, d), b = dot(oc, d), c = dot(oc, oc) - s.radius * s.radius;
+					if (b * b - a * c > 0.0f) {
+						float temp = (-b - sqrtf(b * b - a * c)) / a;
+						if (!(tMin < temp && temp < FLT_MAX)) temp = (-b + sqrtf(b * b - a * c)) / a;
+						if (tMin < temp && temp < FLT_MAX && temp < best) best = temp;
+					}
+				} else {
+					if (first >= cubes.size()) return false;
+					const HostCube& q = cubes[first];
+					const float mna[3] = { q.minBounds.x, q.minBounds.y, q.minBounds.z }, mxa[3] = { q.maxBounds.x, q.maxBounds.y, q.maxBounds.z }, da[3] = { d.x, d.y, d.z };
+					float t7 = 0.0f, t8 = 0.0f;
+					for (int a = 0; a < 3; ++a) {
+						const float t1 = (mna[a] - oa[a]) / da[a], t2 = (mxa[a] - oa[a]) / da[a];
+						const float lo = t2 < t1 ? t2 : t1, hi = t1 < t2 ? t2 : t1;
+						t7 = a == 0 ? lo : (t7 < lo ? lo : t7); t8 = a == 0 ? hi : (hi < t8 ? hi : t8);
+					}
+					if (!(t8 < 0 || t7 > t8) && tMin <= t7 && t7 <= FLT_MAX && t7 < best) best = t7;
+				}
+				if (sp == 0) break;
+				cur = stk[(size_t)--sp];
+			}
+		} else {
+			auto plane = [](const uint32_t q[2], int c) { return (float)((q[c >> 2] >> (8 * (c & 3))) & 255u); };
+			bool neg[3]; uint32_t oct = 0;
+			for (int a = 0; a < 3; ++a) { neg[a] = invc[a] < 0.0f; if (!neg[a]) oct |= 1u << a; }
+			const float ntMin = -tMin;
+			std::vector<std::pair<uint32_t, uint32_t>> stack;
+			uint32_t gx = 0, gy = (1u << (24 + oct)) | 1u;
+			for (;;) {
+				if ((gy >> 24) == 0u) { if (stack.empty()) break; gx = stack.back().first; gy = stack.back().second; stack.pop_back(); continue; }
+				const uint32_t pos = 31u - (uint32_t)__builtin_clz(gy);
+				gy &= ~(1u << pos);
+				const uint32_t slot = (pos - 24u) ^ oct;
+				const uint32_t node = gx + (uint32_t)__builtin_popcount(gy & 0xffu & ((1u << slot) - 1u));
+				if ((gy >> 24) != 0u && stack.size() < (size_t)capacity) { stack.push_back({ gx, gy }); high = std::max(high, (uint32_t)stack.size()); }   // Push8: sp < GMAX
+				if (node >= bvh.nodes8.size()) return false;
+				const DNode8& nd = bvh.nodes8[node];
+				const float tmx = fminf(best, FLT_MAX);
+				float A[3], nB[3], Bf[3];
+				for (int a = 0; a < 3; ++a) {
+					uint32_t sb = ((nd.meta >> (8 * a)) & 255u) << 23; float st; memcpy(&st, &sb, 4);
+					A[a] = st * invc[a];
+					const float B = (nd.origin[a] - oa[a]) * invc[a];
+					const float E = fabsf(A[a] * 1.21593475e-4f) + fabsf(B * 4.76837158e-7f);
+					nB[a] = E - B; Bf[a] = B + E;
+				}
+				uint32_t hit = 0;
+				const uint32_t imask = nd.meta >> 24;
+				for (int ch = 0; ch < 8; ++ch) {
+					float ntn = ntMin, tf = tmx;
+					for (int a = 0; a < 3; ++a) {
+						const float qn = plane(neg[a] ? nd.qhi[a] : nd.qlo[a], ch), qf = plane(neg[a] ? nd.qlo[a] : nd.qhi[a], ch);
+						ntn = std::min(ntn, fmaf(qn, -A[a], nB[a])); tf = std::min(tf, fmaf(qf, A[a], Bf[a]));
+					}
+					if (!std::signbit(fmaf(tf, widen, ntn))) hit |= 1u << ch;
+				}
+				uint32_t innerP = 0;
+				for (uint32_t b = 0; b < 8u; ++b) if (((hit & imask) >> b) & 1u) innerP |= 1u << (b ^ oct);
+				// the triangles of the hit leaf children, before any inner child is entered (Next8)
+				for (uint32_t ch = 0; ch < 8u; ++ch) {
+					if (!((hit & ~imask) >> ch & 1u)) continue;
+					const uint32_t nib = (nd.leafMask >> (4 * ch)) & 15u;
+					const uint32_t first = nd.triBase + (uint32_t)__builtin_popcount(nd.leafMask & ((1u << (4 * ch)) - 1u));
+					for (uint32_t k = 0; k < (uint32_t)__builtin_popcount(nib); ++k) if (!triangle(first + k)) return false;
+				}
+				gx = nd.childBase; gy = (innerP << 24) | imask;
+			}
+		}
+		outT[r] = best;
+		if (outHighWater) outHighWater[r] = high;
+	}
+	return true;
+}
+
 } // namespace rl

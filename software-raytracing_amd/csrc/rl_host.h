@@ -158,6 +158,9 @@ struct SceneElement {
 };
 struct HostSphere { f3 center; float radius; int32_t material; };
 struct HostCube { f3 minBounds, maxBounds; float timeStartMove; f3 velocity; int32_t material; };
+// the stack discipline of the binary, 4-wide float-box, 4-wide grid and 8-wide walks restated on the host with the capacity as an argument (rl_bvh.cc): closest t and the stack's high-water mark per ray
+bool WalkStackHost(const BVH& bvh, const std::vector<HostTriangle>& tris, const std::vector<HostSphere>& spheres, const std::vector<HostCube>& cubes, int tree,
+                   const float* rays, int n, float tMin, int capacity, float* outT, uint32_t* outHighWater);
 
 struct DeviceScene;   // rl_runtime.inl
 

@@ -236,6 +236,7 @@ _EXPORTS = {
     "RaylibAMD_LastTracePlain": (C.c_int32, []),
     "RaylibAMD_PlanRender": (C.c_int32, [C.c_void_p, C.POINTER(RendererSettings), C.c_int32, C.c_int32, C.c_int32, C.POINTER(RenderPlan)]),
     "RaylibAMD_SceneWalk8Host": (C.c_int32, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "RaylibAMD_SceneWalkStackHost": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "RaylibAMD_SceneBVHHash": (C.c_uint64, [C.c_void_p]),
     "RaylibAMD_CameraExport": (None, [C.c_void_p, C.POINTER(C.c_float)]),
     "RaylibAMD_CreateImageFromData": (C.c_void_p, [C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),

@@ -1,5 +1,6 @@
 """The choice of the megakernel instance, its tree and its job layout (csrc/rl_plan.cc), through RaylibAMD_PlanRender: every row of the choice table and
-every per-render switch of INTEGRATION.md, on the scenes the suite renders.  No device needed; tests/test_gpu_* check that a launch reports what the plan said."""
+every per-render switch of INTEGRATION.md, on the scenes the suite renders.  No device needed; tests/test_gpu_* check that a launch reports what the plan said --
+the rows with the 64-deep stacks in tests/test_gpu_stack_edges.py, on the scenes of tests/stack_edges.py."""
 import ctypes as C
 import os
 
