@@ -382,6 +382,14 @@ RAYLIB_API int32_t RaylibAMD_EndProgressive(RaylibAMDProgressiveHandle h);
  * Returns 1, or 0 for a null array or params out of range. */
 RAYLIB_API int32_t RaylibAMD_ProgressiveDecideHost(uint32_t width, uint32_t height, const uint32_t* cellSamples, const float* sumY,
                                                    const float* sumY2, const RaylibAMDProgressiveParams* params, uint8_t* outStop);
+/* Test hook: the kernel that rewrites a session's lists after a pass, on arrays of the caller's, launched as a pass launches it.  live: numLive cells of a
+ * width x height frame in ascending order (numCells = its 8x8 cells, row-major); stopped, emptyOrNull: one byte per cell (empty: outside the silhouette;
+ * NULL: no cell is).  outLive receives the entries of live whose cell has not stopped, in order; outTrace those of them that are not empty, in order; both
+ * have room for numLive entries and are written only up to their counts.  outCounts: [0] entries of outLive, [1] entries of outTrace, [2..3] the valid
+ * pixels of the kept empty cells, low and high word.  Returns 1; 0 -- and nothing is written -- without a device, for a null pointer other than emptyOrNull,
+ * numLive > numCells, a numCells that is not the frame's cell count (an empty frame included) or an entry of live >= numCells. */
+RAYLIB_API int32_t RaylibAMD_ProgressiveCompactTest(const uint32_t* live, uint32_t numLive, const uint8_t* stopped, const uint8_t* emptyOrNull, uint32_t numCells,
+                                                    uint32_t width, uint32_t height, uint32_t* outLive, uint32_t* outTrace, uint32_t outCounts[4]);
 
 #ifdef __cplusplus
 }

@@ -537,6 +537,15 @@ int32_t RaylibAMD_ProgressiveDecideHost(uint32_t width, uint32_t height, const u
 	return 1;
 }
 
+int32_t RaylibAMD_ProgressiveCompactTest(const uint32_t* live, uint32_t numLive, const uint8_t* stopped, const uint8_t* emptyOrNull, uint32_t numCells,
+                                         uint32_t width, uint32_t height, uint32_t* outLive, uint32_t* outTrace, uint32_t outCounts[4])
+{
+	if (!live || !stopped || !outLive || !outTrace || !outCounts) return 0;
+	if (width == 0 || height == 0 || (uint64_t)((width + 7ull) / 8) * ((height + 7ull) / 8) != numCells || numLive > numCells) return 0;
+	for (uint32_t i = 0; i < numLive; ++i) if (live[i] >= numCells) return 0;   // (the kernel indexes stopped and empty by the entries)
+	return DeviceProgressiveCompactTest(live, numLive, stopped, emptyOrNull, numCells, width, height, outLive, outTrace, outCounts) ? 1 : 0;
+}
+
 int32_t RaylibAMD_RenderViews(const RendererSettings* settings, SceneHandle scene, const CameraHandle* cameras, int32_t count, const ImageHandle* outImages)
 {
 	static const char* who = "RaylibAMD_RenderViews";

@@ -265,6 +265,10 @@ ProgressiveSession* DeviceProgressiveBegin(Scene& sc, const RenderRequest& req, 
 int32_t DeviceProgressiveStep(ProgressiveSession& S, uint32_t samples, void* outDevice, RaylibAMDStats& stats, bool& rendered);
 bool DeviceProgressiveExport(ProgressiveSession& S, uint32_t* cellSamples, uint8_t* cellStopped, float* sumY, float* sumY2);
 void DeviceProgressiveEnd(ProgressiveSession* S);
+// RaylibAMD_ProgressiveCompactTest: k_progressive_compact on uploaded copies of the lists, launched as a pass launches it; the ABI checked the arguments
+// (numLive <= numCells = the frame's cells, every entry of live < numCells).  false without a device or memory; outputs are written only on success.
+bool DeviceProgressiveCompactTest(const uint32_t* live, uint32_t numLive, const uint8_t* stopped, const uint8_t* emptyOrNull, uint32_t numCells,
+                                  uint32_t width, uint32_t height, uint32_t* outLive, uint32_t* outTrace, uint32_t outCounts[4]);
 
 // denoiser (rl_denoise.hip): the a-trous filter on the device and its host restatement; params checked by the caller (rl_abi.cc)
 void DenoiseHost(uint32_t width, uint32_t height, const float* color, bool hdr, const float* albedo, const float* normal,

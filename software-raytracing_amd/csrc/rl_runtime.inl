@@ -1736,6 +1736,39 @@ void DeviceProgressiveEnd(ProgressiveSession* S)
 	FreeProgressive(S);
 }
 
+// Test hook: the lists of a session after a pass, from arrays of the caller's.  The launch is EnqueueFrame's (one workgroup of RL_COMPACT_BLOCK threads on rank 0's
+// stream); the kernel writes live and trace in place, entries at indices <= their own, so numLive entries of each suffice.
+bool DeviceProgressiveCompactTest(const uint32_t* live, uint32_t numLive, const uint8_t* stopped, const uint8_t* emptyOrNull, uint32_t numCells,
+                                  uint32_t width, uint32_t height, uint32_t* outLive, uint32_t* outTrace, uint32_t outCounts[4])
+{
+	std::lock_guard<std::mutex> lk(g_rt.lock);
+	if (!EnsureRuntime()) return false;
+	RankCtx& R = Rank0();
+	HIP_OK(hipSetDevice(R.device));
+	// one allocation: live | trace | counts | stopped | empty, each from a multiple of 256 bytes
+	const size_t listBytes = (((size_t)numLive * sizeof(uint32_t)) + 255) & ~(size_t)255, cellBytes = ((size_t)numCells + 255) & ~(size_t)255;
+	char* d = nullptr;
+	if (hipMalloc((void**)&d, 2 * listBytes + 256 + 2 * cellBytes) != hipSuccess) return false;
+	uint32_t *dLive = (uint32_t*)d, *dTrace = (uint32_t*)(d + listBytes), *dCounts = (uint32_t*)(d + 2 * listBytes);
+	uint8_t *dStopped = (uint8_t*)(d + 2 * listBytes + 256), *dEmpty = emptyOrNull ? dStopped + cellBytes : nullptr;
+	uint32_t counts[4] = { 0, 0, 0, 0 };
+	bool ok = numLive == 0 || hipMemcpy(dLive, live, (size_t)numLive * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess;
+	ok = ok && hipMemcpy(dStopped, stopped, numCells, hipMemcpyHostToDevice) == hipSuccess;
+	ok = ok && (!emptyOrNull || hipMemcpy(dEmpty, emptyOrNull, numCells, hipMemcpyHostToDevice) == hipSuccess);
+	if (ok) {
+		hipLaunchKernelGGL(k_progressive_compact, dim3(1), dim3(RL_COMPACT_BLOCK), 0, R.stream,
+		                   dLive, dTrace, (const uint8_t*)dStopped, (const uint8_t*)dEmpty, numLive, width, height, (width + 7) / 8, dCounts);
+		ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(R.stream) == hipSuccess;
+		ok = ok && hipMemcpy(counts, dCounts, sizeof(counts), hipMemcpyDeviceToHost) == hipSuccess;
+		ok = ok && counts[1] <= counts[0] && counts[0] <= numLive;   // (nothing is copied past the caller's arrays, whatever the kernel says)
+		ok = ok && (counts[0] == 0 || hipMemcpy(outLive, dLive, (size_t)counts[0] * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess);
+		ok = ok && (counts[1] == 0 || hipMemcpy(outTrace, dTrace, (size_t)counts[1] * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess);
+		if (ok) memcpy(outCounts, counts, sizeof(counts));
+	}
+	(void)hipFree(d);
+	return ok;
+}
+
 void DeviceReleaseScene(DeviceScene* D)
 {
 	if (!D) return;

@@ -252,6 +252,8 @@ _EXPORTS = {
     "RaylibAMD_EndProgressive": (C.c_int32, [C.c_size_t]),
     "RaylibAMD_ProgressiveDecideHost": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                                     C.POINTER(ProgressiveParams), C.POINTER(C.c_uint8)]),
+    "RaylibAMD_ProgressiveCompactTest": (C.c_int32, [C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_uint32,
+                                                     C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "RaylibAMD_RenderViews": (C.c_int32, [C.POINTER(RendererSettings), C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)]),
     "RaylibAMD_RenderViewsDevice": (C.c_int32, [C.POINTER(RendererSettings), C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p]),
     "RaylibAMD_PlanViews": (C.c_int32, [C.c_void_p, C.POINTER(RendererSettings), C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -313,6 +315,25 @@ def progressive_decide_host(lib, width, height, cell_samples, sum_y, sum_y2, thr
     ok = lib.RaylibAMD_ProgressiveDecideHost(width, height, cells.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(s1), _fp(s2), prm,
                                              out.ctypes.data_as(C.POINTER(C.c_uint8)))
     return out.astype(bool) if ok == 1 else None
+
+
+COMPACT_SENTINEL = 0xDEADBEEF
+
+
+def progressive_compact_test(lib, width, height, live, stopped, empty=None, num_cells=None, pad=8):
+    """RaylibAMD_ProgressiveCompactTest: (return code, outLive, outTrace, counts).  The output arrays have len(live) + pad entries and the counts 4, all
+    filled with COMPACT_SENTINEL before the call: the caller sees what the library wrote and what it left alone."""
+    live = np.ascontiguousarray(live, np.uint32)
+    stopped = np.ascontiguousarray(stopped, np.uint8)
+    empty = None if empty is None else np.ascontiguousarray(empty, np.uint8)
+    n = ((width + 7) // 8) * ((height + 7) // 8) if num_cells is None else int(num_cells)
+    u32, u8 = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+    out_live = np.full(len(live) + pad, COMPACT_SENTINEL, np.uint32)
+    out_trace = np.full(len(live) + pad, COMPACT_SENTINEL, np.uint32)
+    counts = np.full(4, COMPACT_SENTINEL, np.uint32)
+    r = lib.RaylibAMD_ProgressiveCompactTest(live.ctypes.data_as(u32), len(live), stopped.ctypes.data_as(u8), None if empty is None else empty.ctypes.data_as(u8),
+                                             n, int(width), int(height), out_live.ctypes.data_as(u32), out_trace.ctypes.data_as(u32), counts.ctypes.data_as(u32))
+    return r, out_live, out_trace, counts
 
 
 class Progressive:

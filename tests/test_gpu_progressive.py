@@ -16,6 +16,7 @@ from helpers import bits
 pytestmark = pytest.mark.gpu
 
 W, H = 44, 36          # partial cells on the right and at the bottom
+BIG = (1445, 723)      # 16 471 cells: three trips of the compaction kernel
 STEPS = (1, 2, 5, 8, 48)
 
 
@@ -148,19 +149,26 @@ def _threshold_between(ses, w, h, n, quantile):
     return float(np.quantile(e[np.isfinite(e) & (e > 0)], quantile))   # (cells outside the silhouette have error 0)
 
 
-def _run_adaptive(lib, ses, w, h, cap, threshold, min_samples, step):
+def _run_adaptive(lib, ses, w, h, cap, threshold, min_samples, step, passes=None):
+    """passes: a list that receives (samples so far, live cells, traced samples, culled samples) of every pass"""
     binding = _binding()
     P = binding.Progressive(ses, w, h, cap, threshold=threshold, min_samples=min_samples)
     assert P.handle
     total, traced, n = 0, 0, 0
     px = _cell_px(w, h)
+    was_live = np.ones(px.shape, bool)
     while True:
         live = P.step(step)
         assert live >= 0
         st = ses.stats()
         total += _frame_samples(st); traced += st.cameraSamples
+        # the pass sampled exactly the cells that were live before it: the job list and the culled pixel count are the compaction's of the pass before
+        assert _frame_samples(st) == int(px[was_live].sum()) * (min(cap, n + step) - n), (n, _frame_samples(st))
         n = min(cap, n + step)
         cn, stopped, s1, s2 = P.export()
+        was_live = ~stopped
+        if passes is not None:
+            passes.append((n, live, int(st.cameraSamples), int(st.culledSamples)))
         # the device's stop set is the host rule's on the exported sums, after every pass
         assert np.array_equal(stopped, binding.progressive_decide_host(lib, w, h, cn, s1, s2, threshold, min_samples)), n
         assert (cn[~stopped] == n).all() and (cn[stopped] <= n).all()
@@ -174,12 +182,9 @@ def _run_adaptive(lib, ses, w, h, cap, threshold, min_samples, step):
     return frame, cn, stopped, traced
 
 
-@pytest.mark.parametrize("scene", ["cornell", "mid"])
-def test_p3_adaptive_mosaic(gpu_lib, sessions, mid_scene, scene):
-    ses = sessions["cornell"] if scene == "cornell" else mid_scene[0]
-    w, h = (W, H) if scene == "cornell" else (48, 32)
-    # a threshold that splits the cells: per cell the smallest error a uniform session shows at 4, 8, ... 20 samples; below the median of those the cell
-    # stops before 24, at or above it the cell reaches the cap (the adaptive session's sums are the uniform one's until the cell stops)
+def _splitting_threshold(ses, w, h):
+    """a threshold that splits the cells: per cell the smallest error a uniform session shows at 4, 8, ... 20 samples; below the median of those the cell
+    stops before 24, at or above it the cell reaches the cap (the adaptive session's sums are the uniform one's until the cell stops)"""
     U = _binding().Progressive(ses, w, h, 24)
     m = None
     for n in range(4, 24, 4):
@@ -188,14 +193,25 @@ def test_p3_adaptive_mosaic(gpu_lib, sessions, mid_scene, scene):
         e = _cell_errors(cn, s1, s2)
         m = e if m is None else np.minimum(m, e)
     U.close()
-    t = float(np.median(m[np.isfinite(m) & (m > 0)]))
-    frame, cn, stopped, _ = _run_adaptive(gpu_lib, ses, w, h, 24, t, 4, 4)
-    assert stopped.any() and (cn < 24).any() and (cn == 24).any(), np.unique(cn)   # some but not all cells stopped early
-    # every cell is the one-shot frame at its own count
+    return float(np.median(m[np.isfinite(m) & (m > 0)]))
+
+
+def _check_mosaic(ses, frame, cn, w, h, what):
+    """every cell is the one-shot frame at its own count"""
     for n in np.unique(cn):
         want = ses.render(w, h, int(n))
         mask = np.repeat(np.repeat(cn == n, 8, 0), 8, 1)[:h, :w]
-        assert np.array_equal(bits(frame)[mask], bits(want)[mask]), (scene, n)
+        assert np.array_equal(bits(frame)[mask], bits(want)[mask]), (what, n)
+
+
+@pytest.mark.parametrize("scene", ["cornell", "mid"])
+def test_p3_adaptive_mosaic(gpu_lib, sessions, mid_scene, scene):
+    ses = sessions["cornell"] if scene == "cornell" else mid_scene[0]
+    w, h = (W, H) if scene == "cornell" else (48, 32)
+    t = _splitting_threshold(ses, w, h)
+    frame, cn, stopped, _ = _run_adaptive(gpu_lib, ses, w, h, 24, t, 4, 4)
+    assert stopped.any() and (cn < 24).any() and (cn == 24).any(), np.unique(cn)   # some but not all cells stopped early
+    _check_mosaic(ses, frame, cn, w, h, scene)
     # threshold 0 is the uniform session
     P = _binding().Progressive(ses, w, h, 12, threshold=0.0, min_samples=2)
     Q = _binding().Progressive(ses, w, h, 12)
@@ -203,6 +219,37 @@ def test_p3_adaptive_mosaic(gpu_lib, sessions, mid_scene, scene):
         P.step(k); Q.step(k)
     assert np.array_equal(bits(P.frame()), bits(Q.frame())) and np.array_equal(bits(P.frame()), bits(ses.render(w, h, 12)))
     P.close(); Q.close()
+
+
+@pytest.mark.timeout(120)
+@pytest.mark.parametrize("scene", ["cornell", "cutout_sky"])
+def test_p3_sessions_of_three_compaction_trips(gpu_lib, workdir, scene):
+    """1445 x 723 is 181 x 91 = 16 471 cells, ragged on the right and at the bottom: k_progressive_compact (8192 entries per trip) takes three trips over a
+    session's lists, and the offsets it carries from trip to trip decide which cells the next pass renders.  From z = 12 most cells lie outside the silhouette.
+    cornell: those cells have error 0 and leave at the first decision, the first trip's entries vanish at once.  cutout_sky: they sample the panorama; where it
+    varies they keep an error and stay live, so the culled pixel count of the compaction is used pass after pass (measured: 13 635 cells of flat sky leave at the
+    first decision, 2836 cells go on)."""
+    w, h = BIG
+    px = _cell_px(w, h)
+    ses = helpers.session_for_case(gpu_lib, scene, workdir)
+    gpu_lib.Raylib_CameraSetPosition(ses.camera, 0.0, 1.0, 12.0)
+    try:
+        st = _check_uniform_previews(ses, w, h, cap=6, steps=(1, 2, 3), what=scene + " far")
+        assert 0 < st.culledCells < px.size and st.listedCells > 0, (st.culledCells, st.listedCells)   # cells outside the silhouette, and inside
+        t = _splitting_threshold(ses, w, h)
+        passes = []
+        frame, cn, stopped, _ = _run_adaptive(gpu_lib, ses, w, h, 24, t, 4, 4, passes)
+        print("\nprogressive %s %dx%d (%d cells, %d culled): threshold %.6g, cells by samples %s, passes (samples, live, traced, culled) %s"
+              % (scene, w, h, px.size, st.culledCells, t, dict(zip(*[a.tolist() for a in np.unique(cn, return_counts=True)])), passes))
+        assert (cn == 4).any() and (cn < 24).any() and (cn == 24).any(), np.unique(cn)   # cells that stopped at the first decision, early, and at the cap
+        assert len(passes) == 6 and (cn.reshape(-1)[8192:] > 4).any()                    # cells of the later trips survive the first, three-trip compaction
+        if scene == "cornell":
+            assert (cn == 4).sum() >= st.culledCells and all(p[3] == 0 for p in passes[1:])   # every cell outside the silhouette left at once
+        else:
+            assert all(p[3] > 0 for p in passes)                                         # culled samples in every pass: the compaction's pixel count at work
+        _check_mosaic(ses, frame, cn, w, h, scene + " far")
+    finally:
+        ses.close()
 
 
 def test_refusals_leave_the_image_alone(gpu_lib, sessions, workdir):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import helpers
+import postprocess_cases as pc
 from helpers import ffi, scenes
 
 INCLUDE = os.path.join(helpers.ROOT, "include")
@@ -379,6 +380,57 @@ def test_postprocess_matches_oracle(lib, oracle):
     want = oracle.postprocess(rgba)
     assert np.array_equal(helpers.bits(got), helpers.bits(want))
     lib.Raylib_DestroyImage(ih)
+
+
+@pytest.mark.parametrize("pixels", [pc.SMALL] + [(n,) for n in pc.LARGE], ids=["small"] + [str(n) for n in pc.LARGE])
+def test_postprocess_edge_images_match_oracle(lib, oracle, pixels):
+    """Raylib_PostProcess on images made from host pixels (PostProcessHost where there is no device) against the oracle, bit for bit: the white point found
+    at the first, the last and a far pixel, images that never raise it, the 1e-4 cut and the clamp at their boundaries, negative, NaN, infinite and
+    overflowing channels (tests/postprocess_cases.py; the device's kernels meet the same images in tests/test_gpu_frame_kernels.py)."""
+    for n in pixels:
+        assert pc.check_pixel_count(lib, oracle, n) >= 8
+
+
+def test_postprocess_oracle_answers_on_the_edge_pixels(oracle):
+    """What the reference's statement gives for the planted pixels: 0 at or below the cut, 1 for a NaN or +inf luminance (std::min(1, NaN) is 1), and a NaN only
+    where powf meets a negative channel."""
+    finite, infinite = pc.edge_pixels()
+    src = np.ones((1, len(finite + infinite), 4), np.float32)
+    src[0, :, :3] = [rgb for _, rgb in finite + infinite]
+    out = dict(zip([name for name, _ in finite + infinite], oracle.postprocess(src)[0, :, :3]))
+    for name in ("grey below 1e-4", "luminance 1e-4", "luminance below 1e-4", "zero", "minus zero", "negative grey", "small negative grey", "denormal", "largest denormal"):
+        assert (helpers.bits(out[name]) == 0).all(), name
+    for name in ("luminance above 1e-4", "grey 1.0001e-4"):
+        assert (out[name] > 0).all() and (out[name] < 1).all(), name
+    for name in ("nan red", "nan green", "nan blue", "nan all"):
+        assert (out[name] == 1.0).all(), name
+    assert np.isnan(out["negative red"]).tolist() == [True, False, False] and np.isnan(out["negative green"]).tolist() == [False, True, False]
+    assert np.isnan(out["negative blue"]).tolist() == [False, False, True]
+    assert np.isfinite(out["plus inf"]).all() and not np.isposinf(out["minus inf"]).any()
+
+
+def test_progressive_compact_test_refusals(lib):
+    """The argument checks of RaylibAMD_ProgressiveCompactTest come before the device: 0, and nothing written."""
+    from raylib_amd import binding
+    S = binding.COMPACT_SENTINEL
+    live, stopped = np.arange(30, dtype=np.uint32), np.zeros(30, np.uint8)
+    for what, args in (("numLive > numCells", dict(width=44, height=36, live=np.arange(31), stopped=np.zeros(31, np.uint8))),
+                       ("numCells of another frame", dict(width=44, height=36, live=live, stopped=stopped, num_cells=36)),
+                       ("an entry past the frame", dict(width=44, height=36, live=np.array([0, 5, 30]), stopped=stopped)),
+                       ("an empty frame", dict(width=0, height=36, live=live[:0], stopped=stopped, num_cells=0))):
+        r, out_live, out_trace, counts = binding.progressive_compact_test(lib, **args)
+        assert r == 0 and (out_live == S).all() and (out_trace == S).all() and (counts == S).all(), what
+    u32 = C.POINTER(C.c_uint32)
+    out = np.full(30, S, np.uint32)
+    cnt = np.full(4, S, np.uint32)
+    p_live, p_stop, p_out, p_cnt = live.ctypes.data_as(u32), stopped.ctypes.data_as(C.POINTER(C.c_uint8)), out.ctypes.data_as(u32), cnt.ctypes.data_as(u32)
+    for args in ((None, 30, p_stop, None, 30, 44, 36, p_out, p_out, p_cnt), (p_live, 30, None, None, 30, 44, 36, p_out, p_out, p_cnt),
+                 (p_live, 30, p_stop, None, 30, 44, 36, None, p_out, p_cnt), (p_live, 30, p_stop, None, 30, 44, 36, p_out, None, p_cnt),
+                 (p_live, 30, p_stop, None, 30, 44, 36, p_out, p_out, None)):
+        assert lib.RaylibAMD_ProgressiveCompactTest(*args) == 0 and (out == S).all() and (cnt == S).all()
+    if lib.RaylibAMD_DeviceAvailable() == 0:               # without a device a valid call is refused too, and writes nothing
+        r, out_live, out_trace, counts = binding.progressive_compact_test(lib, 44, 36, live, stopped, np.zeros(30, np.uint8))
+        assert r == 0 and (out_live == S).all() and (out_trace == S).all() and (counts == S).all()
 
 
 def test_procedural_elements_registry(lib):

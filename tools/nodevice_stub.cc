@@ -28,4 +28,5 @@ ProgressiveSession* DeviceProgressiveBegin(Scene&, const RenderRequest&, float, 
 int32_t DeviceProgressiveStep(ProgressiveSession&, uint32_t, void*, RaylibAMDStats&, bool& rendered) { rendered = false; return -1; }
 bool DeviceProgressiveExport(ProgressiveSession&, uint32_t*, uint8_t*, float*, float*) { return false; }
 void DeviceProgressiveEnd(ProgressiveSession*) {}
+bool DeviceProgressiveCompactTest(const uint32_t*, uint32_t, const uint8_t*, const uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t*, uint32_t*, uint32_t*) { return false; }
 }
