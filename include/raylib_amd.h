@@ -159,6 +159,53 @@ typedef struct RaylibAMDQueryPlan {
 } RaylibAMDQueryPlan;
 RAYLIB_API int32_t RaylibAMD_PlanRayQuery(SceneHandle scene, int32_t kind, RaylibAMDQueryPlan* out);
 
+/* ---- path-traced radiance along caller rays -----------------------------------------------------
+ * outRGBA[i] = (the mean over the samples of TraceScene(rays[i], depth 0, maxPathLength, rayTMin), 1): the reference's path tracer (render/renderer.cc:114-208)
+ * with the scene's sun and sky panorama as a render sees them, on rays that need not come from a camera.  The ray is used as given: neither normalised nor
+ * jittered (the caller owns the jitter).  The RGB is the float sum of the samples in sample order, from +0, times 1.0f / sampleCount -- the renderer's
+ * accumulation.
+ * The stream contract for caller rays (include/raylib_amd_rng.h): sample s of ray i draws from the stream (RaylibAMD_GetSeed() at the call, rays[i].stream,
+ * s) with its first skipDraws draws discarded; rays[i].stream stands where the contract has the pixel index.  Rays that share a stream value share their
+ * random numbers.  Hence: the rays a camera generates (RaylibAMD_EvalCameraRays), with stream = y * W + x, sampleFirst = s and skipDraws = 3 for s = 0 (2 lens
+ * draws, 1 shutter-time draw) or 5 for s >= 1 (2 jitter draws before them), give bit for bit the samples Raylib_Render accumulates for that pixel
+ * (tests/test_gpu_radiance.py).
+ * rayTMin is used as the render uses it: not raised, and a hit's own-box rule is not widened (the ray queries above differ in both).
+ * time: the shutter time of the ray, at which moving cubes are placed; every bounce of the path inherits it, as in the render. */
+typedef struct RaylibAMDPathRay {      /* 32 bytes; on the device entry an array of them must be 16-byte aligned (a ray is read as two 16-byte loads) */
+	float org[3]; float time;
+	float dir[3]; uint32_t stream;
+} RaylibAMDPathRay;
+typedef struct RaylibAMDRadianceParams {
+	int32_t  maxPathLength;            /* as RendererSettings.maxPathLength; 0: every result is (0, 0, 0, 1); at most 32768 */
+	float    rayTMin;                  /* as RendererSettings.rayTMin; finite and >= 0 */
+	uint32_t sampleFirst, sampleCount; /* ray i is traced sampleCount (>= 1) times: sample k on the stream (seed, rays[i].stream, sampleFirst + k) */
+	uint32_t skipDraws;                /* draws discarded from each stream before the first bounce (<= 64) */
+	float    timeMin, timeMax;         /* device entry only: the interval every ray's time lies in (a time outside it, or NaN, is clamped into it); the host entry
+	                                      scans the times itself and ignores these */
+} RaylibAMDRadianceParams;
+/* n rays from host memory, n x 4 floats to host memory; synchronous.  Moving cubes' boxes are rebuilt when the rays' times leave the interval they were built
+ * for (as RaylibAMD_TraceRays does for rayTime).  The library keeps its device staging buffers and grows them.  Returns 1 (n == 0 included), or 0 with
+ * nothing written when a pointer is null with n > 0, n < 0, the scene is not finalized, maxPathLength < 0 or > 32768, sampleCount == 0, skipDraws > 64, rayTMin is
+ * negative or not finite, a ray's time is not finite, the scene's BVH is deeper than 64 levels, or there is no device.
+ * RaylibAMD_GetLastStats then reports rays, nodesVisited, trisTested, shadedHits, texFetches, kernelMs, wallMs, treeWidth, nodeBytes and
+ * cameraSamples = n x sampleCount. */
+RAYLIB_API int32_t RaylibAMD_TraceRadiance(SceneHandle scene, const RaylibAMDRadianceParams* params, const RaylibAMDPathRay* rays, int32_t n, float* outRGBA);
+/* The same on device pointers (rank 0's device; both 16-byte aligned; refused otherwise).  Also refused: timeMin > timeMax or a bound that is not finite.
+ * stream == NULL: the library's stream, synchronous, with stats.  A non-null hipStream_t: uploads (the scene, a tree, the sky) happen first and synchronously,
+ * then the call is enqueued on that stream and returns; the stats are left alone.
+ * Scratch memory (the ray counter and the path stack: maxPathLength records of 32 bytes per resident lane of the grid, kept and grown) is one per
+ * library, guarded by an event chain: every launch records an event behind itself and waits, on its own stream, for the event of the launch before it, so two
+ * calls enqueued on two streams run one after the other on the device and never share the scratch.  Growing the path stack waits for the device.
+ * The path stack is held to 256 MiB: where the full grid's would be larger (maxPathLength above about 32 on a full device) the call runs on a smaller grid,
+ * with the same results. */
+RAYLIB_API int32_t RaylibAMD_TraceRadianceDevice(SceneHandle scene, const RaylibAMDRadianceParams* params, const RaylibAMDPathRay* rays, int32_t n, float* outRGBA,
+        void* stream);
+/* Which tree and kernel instance those calls would walk under the current environment (csrc/rl_plan.cc PlanRadiance): the grid-4 tree when the scene has one
+ * (triangles only, worst-case stack within 64), else the binary tree; RAYLIB_QUERY_TREE=2 forces the binary tree, =8 falls through to 4 (the 8-wide walk is not
+ * fused with shading).  No device needed.  Returns 1, -1 when the BVH is deeper than 64 levels, 0 for a null argument, a scene not finalized or params the
+ * calls above would refuse.  `early` is 0. */
+RAYLIB_API int32_t RaylibAMD_PlanRadiance(SceneHandle scene, const RaylibAMDRadianceParams* params, RaylibAMDQueryPlan* out);
+
 /* ---- procedural scene elements ----------------------------------------------------------
  * The reference's two procedural demo scenes (src/main.cc:913-984) `new` its C++ classes (Sphere, Cube, Triangle,
  * Lambertian, Metal, ...) in the application and pass the object pointers to Raylib_AddSceneElement.  A C ABI

@@ -773,6 +773,71 @@ int32_t RaylibAMD_PlanRayQuery(SceneHandle sh, int32_t kind, RaylibAMDQueryPlan*
 	return 1;
 }
 
+// RaylibAMD_TraceRadiance / RaylibAMD_TraceRadianceDevice / RaylibAMD_PlanRadiance: what of RaylibAMDRadianceParams needs no device and no rays
+static bool RadianceParamsValid(const char* who, const Scene* s, const RaylibAMDRadianceParams* p)
+{
+	if (!s || !p) { Log("%s: null argument", who); return false; }
+	if (!s->finalized) { Log("%s: scene was not finalized (Raylib_FinalizeScene)", who); return false; }
+	if (p->maxPathLength < 0) { Log("%s: maxPathLength %d is negative", who, p->maxPathLength); return false; }
+	if (p->maxPathLength > RL_RADIANCE_MAX_PATH) { Log("%s: maxPathLength %d exceeds %d", who, p->maxPathLength, RL_RADIANCE_MAX_PATH); return false; }
+	if (p->sampleCount == 0) { Log("%s: sampleCount is 0", who); return false; }
+	if (p->skipDraws > 64) { Log("%s: skipDraws %u exceeds 64", who, p->skipDraws); return false; }
+	if (!std::isfinite(p->rayTMin) || p->rayTMin < 0.0f) { Log("%s: rayTMin %g is negative or not finite", who, p->rayTMin); return false; }
+	return true;
+}
+static int32_t TraceRadianceInternal(const char* who, SceneHandle sh, const RaylibAMDRadianceParams* params, const RaylibAMDPathRay* rays, int32_t n, float* out,
+                                     bool hostMem, void* stream)
+{
+	Scene* s = (Scene*)sh;
+	if (n < 0 || (n > 0 && (!rays || !out))) { Log("%s: null argument", who); return 0; }
+	if (!RadianceParamsValid(who, s, params)) return 0;
+	RaylibAMDRadianceParams prm = *params;
+	if (hostMem) {
+		// the host entry scans the times itself (timeMin / timeMax are the device entry's)
+		prm.timeMin = prm.timeMax = n > 0 ? rays[0].time : 0.0f;
+		for (int32_t i = 0; i < n; ++i) {
+			const float t = rays[i].time;
+			if (!std::isfinite(t)) { Log("%s: ray %d has a time that is not finite", who, i); return 0; }
+			prm.timeMin = std::min(prm.timeMin, t); prm.timeMax = std::max(prm.timeMax, t);
+		}
+	} else if (!std::isfinite(prm.timeMin) || !std::isfinite(prm.timeMax) || prm.timeMin > prm.timeMax) {
+		Log("%s: the time interval [%g, %g] is empty or not finite", who, prm.timeMin, prm.timeMax);
+		return 0;
+	}
+	if (!DeviceAvailable()) return 0;
+	if (n > 0 && s->hasMovingCubes && !(prm.timeMin >= s->accelT0 && prm.timeMax <= s->accelT1)) {
+		// moving cubes: their boxes must cover the motion at every ray's time (as RaylibAMD_TraceRays rebuilds them for its rayTime)
+		const float t0 = std::min(s->accelT0, prm.timeMin), t1 = std::max(s->accelT1, prm.timeMax);
+		if (s->device) { DeviceReleaseScene(s->device); s->device = nullptr; }
+		if (!s->BuildAccel(t0, t1)) { Log("%s: the acceleration structure could not be rebuilt for the times [%g, %g]", who, prm.timeMin, prm.timeMax); return 0; }
+	}
+	if (s->sky && !g_images.contains(s->sky)) {
+		Log("%s: the scene's sky panorama was destroyed; tracing without it", who);   // as a render (PrepareRender)
+		s->sky = nullptr;
+	}
+	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
+	if (!DeviceTraceRadiance(*s, prm, CurrentSeed(), rays, n, out, hostMem, stream, stats)) return 0;
+	if (!stream) { std::lock_guard<std::mutex> lk(g_stateMu); g_lastStats = stats; }
+	return 1;
+}
+int32_t RaylibAMD_TraceRadiance(SceneHandle sh, const RaylibAMDRadianceParams* params, const RaylibAMDPathRay* rays, int32_t n, float* outRGBA)
+{
+	return TraceRadianceInternal("RaylibAMD_TraceRadiance", sh, params, rays, n, outRGBA, true, nullptr);
+}
+int32_t RaylibAMD_TraceRadianceDevice(SceneHandle sh, const RaylibAMDRadianceParams* params, const RaylibAMDPathRay* rays, int32_t n, float* outRGBA, void* stream)
+{
+	return TraceRadianceInternal("RaylibAMD_TraceRadianceDevice", sh, params, rays, n, outRGBA, false, stream);
+}
+int32_t RaylibAMD_PlanRadiance(SceneHandle sh, const RaylibAMDRadianceParams* params, RaylibAMDQueryPlan* out)
+{
+	if (!out || !RadianceParamsValid("RaylibAMD_PlanRadiance", (Scene*)sh, params)) return 0;
+	memset(out, 0, sizeof(*out));
+	const QueryPlan p = PlanRadiance(*(Scene*)sh, ReadRenderKnobs());
+	if (!p.ok) return -1;
+	out->tree = p.tree; out->treeWidth = p.treeWidth; out->nodeBytes = p.nodeBytes; out->stack = p.stack; out->prims = p.prims; out->early = 0;
+	return 1;
+}
+
 int32_t RaylibAMD_SceneNumTriangles(SceneHandle sh) { Scene* s = (Scene*)sh; return s ? (int32_t)s->triangles.size() : 0; }
 int32_t RaylibAMD_SceneNumMaterials(SceneHandle sh) { Scene* s = (Scene*)sh; return s ? (int32_t)s->materials.size() : 0; }
 int32_t RaylibAMD_SceneNumTextures(SceneHandle sh) { Scene* s = (Scene*)sh; return s ? (int32_t)s->textures.size() : 0; }

@@ -243,6 +243,14 @@ bool DeviceClosestHit(Scene& scene, const float* rays, int32_t n, float tMin, vo
 // synchronous; else enqueued on that hipStream_t).  stats: filled by a synchronous call.  kind is valid, n >= 0, the scene finalized: the ABI checked.
 bool DeviceTraceRays(Scene& scene, int32_t kind, const void* rays, int32_t n, float rayTime, void* out, int32_t* outPrim, bool hostMem, void* stream,
                      RaylibAMDStats& stats);
+// RaylibAMD_TraceRadiance (hostMem) and RaylibAMD_TraceRadianceDevice, as DeviceTraceRays; prm is valid (timeMin <= timeMax cover every ray's time and the
+// scene's boxes), seed is the library's: the ABI checked.
+// The path stack's budget: the grid is cut until its stack (32 bytes per bounce and resident lane) fits, and a maxPathLength at which one workgroup of 256
+// lanes does not fit is refused (RL_RADIANCE_STACK_BUDGET / (32 * 256)).
+constexpr uint64_t RL_RADIANCE_STACK_BUDGET = 256ull << 20;
+constexpr int32_t RL_RADIANCE_MAX_PATH = 32768;
+bool DeviceTraceRadiance(Scene& scene, const RaylibAMDRadianceParams& prm, uint64_t seed, const void* rays, int32_t n, float* out, bool hostMem, void* stream,
+                         RaylibAMDStats& stats);
 bool DevicePostProcess(Image& img);          // Image2D::PostProcess on the device; false when no device
 bool DeviceDumpRGB(Image& img, float* outRGB);   // a device-resident frame packed to RGB on the device and copied to caller memory through pinned staging; false: not applicable
 bool DeviceReadback(Image& img);            // device copy -> img.rgba (the caller checked hostStale)

@@ -11,9 +11,7 @@
 // as Triangle::Hit does, and every box beyond tMax is culled.  A sphere's interval is open (Sphere::Hit: t_min < t < t_max): a sphere at exactly tMax is
 // dropped afterwards -- it can only have been the walk's result if nothing nearer was accepted.  A NaN bound makes every comparison false: a miss.
 // tMin < 0 is raised to +0 (QueryTMin).  A triangle at exactly tMin counts: this unit widens the candidate rule's "own box ends before tMin" (RL_OWN_BOX_WIDEN_TMIN, rl_dev_walk.h OwnBoxPassBox).
-#ifndef RL_QUERY_CHUNK
-#define RL_QUERY_CHUNK 64u       /* rays a wave takes per atomic on the global counter */
-#endif
+// (RL_QUERY_CHUNK, the rays a wave takes per atomic on the global counter: rl_kernels.h)
 #ifndef RL_QUERY_REFILL
 #define RL_QUERY_REFILL 8        /* 8-wide walk: idle lanes of a wave before it hands out new rays between steps */
 #endif

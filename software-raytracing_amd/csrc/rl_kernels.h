@@ -6,6 +6,7 @@
 //                        change how the helpers both call are inlined into those (tools/isa_equivalence.py)
 //   rl_render_pool.hip   k_trace_pool and its twin: a scheduler strategy of its own (Makefile POOLFLAGS)
 //   rl_query.hip         k_query (RaylibAMD_TraceRays): beside the render kernels it would change how the walks they share are inlined into those
+//   rl_radiance.hip      k_radiance (RaylibAMD_TraceRadiance): the same reason, towards the render and the query kernels alike
 // A twin takes the view table (DViews) as one more trailing argument.  Default template arguments are given here and nowhere else.
 #pragma once
 
@@ -81,6 +82,10 @@ RL_AOV_INSTANCES(extern RL_K_AOV_VIEWS)
 // A hit record as RaylibAMD_ClosestHit and the surface query of RaylibAMD_TraceRays return it (oracle/flat_scene.h FlatHit)
 struct DHitOut { int32_t hit; float t; float p[3]; float n[3]; float paramU, paramV; int32_t material; };
 enum { RL_QK_ANY = 0, RL_QK_CLOSEST = 1, RL_QK_SURFACE = 2 };   // RAYLIB_AMD_QUERY_*
+// Rays (k_query) or jobs (k_radiance) a wave takes per atomic on the global counter: one value for both kernels
+#ifndef RL_QUERY_CHUNK
+#define RL_QUERY_CHUNK 64u
+#endif
 struct DQueryHit { float t; int32_t prim; float b1, b2; };      // RaylibAMDHitT
 // TREE: 2 the binary tree (S.nodes), 4 the grid nodes (S.nodes4), 8 the 8-wide tree (S.nodes8).  STACK: the walk's stack (TREE 8: RL_POOL8_MAXLEVELS groups).
 // PRIMS: the scene holds spheres or cubes (binary tree only).  rays: n records of two float4 (org, tMin | dir, tMax).  counters: CNT_* sums, or null.
@@ -92,5 +97,20 @@ template <int TREE, int KIND, int STACK, bool PRIMS> __global__ void __launch_bo
 #define RL_QUERY_INSTANCES(X) RL_QUERY_INSTANCES_K(X, 0) RL_QUERY_INSTANCES_K(X, 1) RL_QUERY_INSTANCES_K(X, 2)
 #define RL_K_QUERY(a, b, c, d) template __global__ void k_query<a, b, c, d>(RL_QUERY_ARGS);
 RL_QUERY_INSTANCES(extern RL_K_QUERY)
+
+// ---------------------------------------------------------------------------
+// Path-traced radiance along caller rays (RaylibAMD_TraceRadiance; rl_k_radiance.inl)
+// What RaylibAMDRadianceParams and the launch say: the seed mixed once (raylib_rng_mix64), the path stack's stride in lanes (the grid's size)
+struct DRadianceParams { unsigned long long seedMixed; int32_t maxPathLength; float rayTMin; uint32_t sampleFirst, sampleCount, skipDraws, stackStride; float timeMin, timeMax; };
+// TREE: 2 the binary tree (S.nodes), 4 the grid nodes (S.nodes4).  STACK: the walk's stack.  PRIMS: the scene holds spheres or cubes (binary tree only).
+// rays: n records of two float4 (org, time | dir, stream).  out: n float4.  pathStack: [maxPathLength][stackStride] records of 2 float4, as k_trace's.
+// counters: CNT_* sums, or null.
+#define RL_RADIANCE_ARGS const DSceneView, const SkyRot, const DRadianceParams, const float4* __restrict__, uint32_t, float4* __restrict__, float* __restrict__, unsigned int* __restrict__, unsigned long long* __restrict__
+template <int TREE, int STACK, bool PRIMS>
+__global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 2)) k_radiance(RL_RADIANCE_ARGS);
+// The instances rl_runtime.inl RadianceKernelFor selects from: (TREE, STACK, PRIMS)
+#define RL_RADIANCE_INSTANCES(X) X(2, 32, false) X(2, 32, true) X(2, 64, false) X(2, 64, true) X(4, 32, false) X(4, 64, false)
+#define RL_K_RADIANCE(a, b, c) template __global__ void k_radiance<a, b, c>(RL_RADIANCE_ARGS);
+RL_RADIANCE_INSTANCES(extern RL_K_RADIANCE)
 
 } // namespace rl

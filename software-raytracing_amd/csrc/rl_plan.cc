@@ -145,6 +145,21 @@ QueryPlan PlanQuery(const Scene& sc, int32_t kind, const RenderKnobs& k)
 	return p;
 }
 
+QueryPlan PlanRadiance(const Scene& sc, const RenderKnobs& k)
+{
+	QueryPlan p;
+	const BVH& b = sc.bvh;
+	p.prims = !sc.spheres.empty() || !sc.cubes.empty();
+	if (b.depth > 64) { p.ok = false; return p; }
+	const int want = k.queryTree ? k.queryTree : 4;
+	if (want >= 4 && !p.prims && !b.nodes4q.empty() && b.stackNeed4 <= 64) {
+		p.tree = TREE_GRID4; p.treeWidth = 4; p.stack = b.stackNeed4 <= 32 ? 32 : 64;
+	} else {
+		p.stack = b.depth <= 32 ? 32 : 64;
+	}
+	return p;
+}
+
 LaunchPlan PlanLaunch(uint32_t numLocalCells, uint32_t numActive, uint32_t spp, uint32_t sampleBegin, int numCUs, int workgroupsPerCU,
                       const TracePlan& trace, const RenderKnobs& k)
 {

@@ -23,7 +23,7 @@ struct RenderKnobs {
 	int guided = 0;                               // RAYLIB_GUIDED
 	int blocksPerCU = 0;                          // RAYLIB_BLOCKS_PER_CU (0: not set or not positive)
 	int cullCells = 1;                            // RAYLIB_CULL_CELLS (rl_cull.cc reads it for itself; the runtime keys its cached cell lists on it)
-	int queryTree = 0;                            // RAYLIB_QUERY_TREE: 2, 4 or 8 (RaylibAMD_TraceRays; any other value: 0, not set)
+	int queryTree = 0;                            // RAYLIB_QUERY_TREE: 2, 4 or 8 (RaylibAMD_TraceRays, RaylibAMD_TraceRadiance; any other value: 0, not set)
 };
 RenderKnobs ReadRenderKnobs();
 
@@ -69,6 +69,10 @@ struct QueryPlan {
 	bool early = false;         // the occlusion query stops at its first accepted candidate
 };
 QueryPlan PlanQuery(const Scene& sc, int32_t kind, const RenderKnobs& knobs);
+// Which tree and k_radiance instance a batch of caller rays is path-traced on (RaylibAMD_TraceRadiance, rl_k_radiance.inl): the grid-4 tree when the scene
+// carries one, has no spheres or cubes and its worst-case stack fits 64 entries; else the binary tree.  The 8-wide walk is a step walk and not fused with
+// shading here: RAYLIB_QUERY_TREE=8 falls through to 4, =2 walks the binary tree.  `early` is unused (false).
+QueryPlan PlanRadiance(const Scene& sc, const RenderKnobs& knobs);
 
 // Several views of one scene in one launch per sample batch (RaylibAMD_RenderViews): the job list of the batch.  Cell c of view v is batch cell
 // v * cellsPerView + c; the list is every view's listed cells, view by view, each view culled on its own (CullCells), a view that is not eligible listing all

@@ -148,6 +148,11 @@ struct RankCtx {
 	unsigned int* qRing = nullptr; hipEvent_t qRingEv[RL_QUERY_RING] = {}; bool qRingUsed[RL_QUERY_RING] = {}; uint32_t qRingNext = 0;
 	unsigned long long* qStats = nullptr; unsigned long long* qStatsHost = nullptr;
 	hipEvent_t qEv[2] = { nullptr, nullptr };
+	// path-traced caller rays (DeviceTraceRadiance): the ray counter and the path stack of the grid, kept and grown, and the event behind the last launch --
+	// every launch waits for it on its own stream, so that two calls on two streams never share the scratch at the same time
+	unsigned int* radCounter = nullptr;
+	float* radStack = nullptr; size_t radStackBytes = 0;
+	hipEvent_t radEv = nullptr; bool radEvUsed = false;
 };
 
 struct Runtime {
@@ -1400,6 +1405,97 @@ bool DeviceTraceRays(Scene& sc, int32_t kind, const void* rays, int32_t n, float
 	HIP_OK(hipEventElapsedTime(&ms, R.qEv[0], R.qEv[1]));
 	stats.rays = R.qStatsHost[CNT_RAYS]; stats.nodesVisited = R.qStatsHost[CNT_NODES]; stats.trisTested = R.qStatsHost[CNT_TRIS];
 	stats.shadedHits = R.qStatsHost[CNT_SHADED]; stats.texFetches = R.qStatsHost[CNT_TEXELS];
+	stats.kernelMs = ms; stats.traceKernelMs = ms; stats.traceLaunches = 1;
+	stats.wallMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	return true;
+}
+
+typedef void (*RadianceKernel)(const DSceneView, const SkyRot, const DRadianceParams, const float4*, uint32_t, float4*, float*, unsigned int*, unsigned long long*);
+static RadianceKernel RadianceKernelFor(const QueryPlan& p)
+{
+	if (p.tree == TREE_GRID4) return p.stack <= 32 ? (RadianceKernel)k_radiance<4, 32, false> : (RadianceKernel)k_radiance<4, 64, false>;
+	if (p.stack <= 32) return p.prims ? (RadianceKernel)k_radiance<2, 32, true> : (RadianceKernel)k_radiance<2, 32, false>;
+	return p.prims ? (RadianceKernel)k_radiance<2, 64, true> : (RadianceKernel)k_radiance<2, 64, false>;
+}
+static_assert(sizeof(RaylibAMDPathRay) == 32, "radiance records");
+static_assert(RL_RADIANCE_STACK_BUDGET / ((uint64_t)RL_RADIANCE_MAX_PATH * 8 * sizeof(float) * RL_BLOCK) >= 1, "one workgroup's path stack fits the budget");
+
+bool DeviceTraceRadiance(Scene& sc, const RaylibAMDRadianceParams& prm, uint64_t seed, const void* rays, int32_t n, float* out, bool hostMem, void* stream,
+                         RaylibAMDStats& stats)
+{
+	const auto t0 = std::chrono::steady_clock::now();
+	std::lock_guard<std::mutex> lk(g_rt.lock);
+	if (!EnsureRuntime()) return false;
+	RankCtx& R = Rank0();
+	HIP_OK(hipSetDevice(R.device));
+	const QueryPlan plan = PlanRadiance(sc, ReadRenderKnobs());
+	if (!plan.ok) { Log("RaylibAMD_TraceRadiance: BVH depth %u exceeds the traversal stack (64)", sc.bvh.depth); return false; }
+	if (!hostMem && n > 0) {
+		if (!OnDevice(rays, R.device) || !OnDevice(out, R.device)) { Log("RaylibAMD_TraceRadianceDevice: a pointer is not device memory of device %d", R.device); return false; }
+		// the kernel reads a ray as two 16-byte loads and writes a result as one 16-byte store
+		if (((uintptr_t)rays & 15u) != 0) { Log("RaylibAMD_TraceRadianceDevice: the rays are not 16-byte aligned"); return false; }
+		if (((uintptr_t)out & 15u) != 0) { Log("RaylibAMD_TraceRadianceDevice: the output is not 16-byte aligned"); return false; }
+	}
+	if (!UploadScene(sc) || !SyncSky(sc)) return false;
+	DeviceSceneCopy* Cp = sc.device->copy[(size_t)R.devSlot];
+	if (!EnsureWideTree(Cp, sc, plan.tree)) return false;
+	const hipStream_t st = stream ? (hipStream_t)stream : R.stream;
+	const bool sync = !stream;
+	if (!R.radCounter) HIP_OK(hipMalloc(&R.radCounter, sizeof(unsigned int)));
+	if (!R.radEv) HIP_OK(hipEventCreateWithFlags(&R.radEv, hipEventDisableTiming));
+	if (sync && !R.qStats) {
+		HIP_OK(hipMalloc(&R.qStats, 8 * sizeof(unsigned long long)));
+		HIP_OK(hipHostMalloc(&R.qStatsHost, 8 * sizeof(unsigned long long), hipHostMallocDefault));
+		HIP_OK(hipEventCreate(&R.qEv[0])); HIP_OK(hipEventCreate(&R.qEv[1]));
+	}
+	memset(&stats, 0, sizeof(stats));
+	stats.treeWidth = plan.treeWidth; stats.nodeBytes = plan.nodeBytes; stats.ranks = 1; stats.devices = 1;
+	stats.numNodes = (uint32_t)sc.bvh.nodes.size(); stats.numTriangles = (uint32_t)sc.triangles.size(); stats.bvhDepth = sc.bvh.depth;
+	if (n == 0) return true;
+	const RadianceKernel kernel = RadianceKernelFor(plan);
+	const int blocksPerCU = OccupancyOf(R, (const void*)kernel);
+	if (blocksPerCU < 0) return false;
+	// enough workgroups to fill the device once; the waves take their jobs from the counter (rl_k_radiance.inl)
+	uint64_t blocks64 = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)R.numCUs * (uint64_t)std::max(1, blocksPerCU), ((uint64_t)n + RL_BLOCK - 1) / RL_BLOCK));
+	// ... but no more than whose path stack (32 bytes per bounce and resident lane) fits RL_RADIANCE_STACK_BUDGET: long paths run on a smaller grid,
+	// which changes no result (a job's arithmetic does not depend on the lane that takes it)
+	const size_t depthSlots = (size_t)(prm.maxPathLength > 1 ? prm.maxPathLength : 1);
+	const uint64_t stackPerBlock = (uint64_t)depthSlots * 8 * sizeof(float) * RL_BLOCK;
+	blocks64 = std::min<uint64_t>(blocks64, RL_RADIANCE_STACK_BUDGET / stackPerBlock);   // (>= 1: RaylibAMD_TraceRadiance refuses a longer path)
+	const uint32_t blocks = (uint32_t)blocks64;
+	DRadianceParams Q; memset(&Q, 0, sizeof(Q));
+	Q.seedMixed = raylib_rng_mix64(seed); Q.maxPathLength = prm.maxPathLength; Q.rayTMin = prm.rayTMin;
+	Q.sampleFirst = prm.sampleFirst; Q.sampleCount = prm.sampleCount; Q.skipDraws = prm.skipDraws;
+	Q.stackStride = blocks * RL_BLOCK; Q.timeMin = prm.timeMin; Q.timeMax = prm.timeMax;
+	// the path stack of the grid: one record per bounce and resident lane.  The scratch is one per rank: a launch waits, on its stream, for the launch before it
+	// (whatever stream that ran on), and growing the stack frees it with hipFree, which waits for the device
+	if (!Grow(R.radStack, R.radStackBytes, depthSlots * 8 * Q.stackStride * sizeof(float))) return false;
+	const float4* dRays = (const float4*)rays; float4* dOut = (float4*)out;
+	const size_t outBytes = (size_t)n * sizeof(float4);
+	if (hostMem) {
+		if (!Grow(R.qRays, R.qRaysBytes, (size_t)n * sizeof(RaylibAMDPathRay)) || !Grow(R.qOut, R.qOutBytes, outBytes)) return false;
+		HIP_OK(hipMemcpyAsync(R.qRays, rays, (size_t)n * sizeof(RaylibAMDPathRay), hipMemcpyHostToDevice, st));
+		dRays = R.qRays; dOut = (float4*)R.qOut;
+	}
+	const DSceneView view = Cp->view;
+	const SkyRot skyRot = sc.device->skyRot;
+	if (R.radEvUsed) HIP_OK(hipStreamWaitEvent(st, R.radEv, 0));
+	HIP_OK(hipMemsetAsync(R.radCounter, 0, sizeof(unsigned int), st));
+	if (sync) { HIP_OK(hipMemsetAsync(R.qStats, 0, 8 * sizeof(unsigned long long), st)); HIP_OK(hipEventRecord(R.qEv[0], st)); }
+	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RL_BLOCK), 0, st, view, skyRot, Q, dRays, (uint32_t)n, dOut, R.radStack, R.radCounter, sync ? R.qStats : nullptr);
+	HIP_OK(hipGetLastError());
+	HIP_OK(hipEventRecord(R.radEv, st));
+	R.radEvUsed = true;
+	if (!sync) return true;
+	HIP_OK(hipEventRecord(R.qEv[1], st));
+	HIP_OK(hipMemcpyAsync(R.qStatsHost, R.qStats, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+	if (hostMem) HIP_OK(hipMemcpyAsync(out, dOut, outBytes, hipMemcpyDeviceToHost, st));
+	HIP_OK(hipStreamSynchronize(st));
+	float ms = 0.0f;
+	HIP_OK(hipEventElapsedTime(&ms, R.qEv[0], R.qEv[1]));
+	stats.rays = R.qStatsHost[CNT_RAYS]; stats.nodesVisited = R.qStatsHost[CNT_NODES]; stats.trisTested = R.qStatsHost[CNT_TRIS];
+	stats.shadedHits = R.qStatsHost[CNT_SHADED]; stats.texFetches = R.qStatsHost[CNT_TEXELS]; stats.cameraSamples = R.qStatsHost[CNT_SAMPLES];
+	stats.waveTrips = R.qStatsHost[CNT_TRIPS];
 	stats.kernelMs = ms; stats.traceKernelMs = ms; stats.traceLaunches = 1;
 	stats.wallMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 	return true;

@@ -147,6 +147,60 @@ def trace_rays(lib, scene, rays, kind, ray_time=0.0, with_prim=False):
     return (out, prim) if with_prim else out
 
 
+class PathRay(C.Structure):
+    """include/raylib_amd.h RaylibAMDPathRay (32 bytes): org, time, dir, stream."""
+    _fields_ = [("org", C.c_float * 3), ("time", C.c_float), ("dir", C.c_float * 3), ("stream", C.c_uint32)]
+
+
+class RadianceParams(C.Structure):
+    """include/raylib_amd.h RaylibAMDRadianceParams."""
+    _fields_ = [("maxPathLength", C.c_int32), ("rayTMin", C.c_float), ("sampleFirst", C.c_uint32), ("sampleCount", C.c_uint32),
+                ("skipDraws", C.c_uint32), ("timeMin", C.c_float), ("timeMax", C.c_float)]
+
+
+def plan_radiance(lib, scene, max_path=5, tmin=1e-4, sample_first=0, sample_count=1, skip_draws=3):
+    """RaylibAMD_PlanRadiance: (return code, plan dict)."""
+    prm = RadianceParams(int(max_path), float(tmin), int(sample_first), int(sample_count), int(skip_draws), 0.0, 0.0)
+    p = QueryPlan()
+    r = lib.RaylibAMD_PlanRadiance(scene, C.byref(prm), C.byref(p))
+    return r, p.as_dict()
+
+
+def trace_radiance(lib, scene, rays, max_path=5, tmin=1e-4, sample_first=0, sample_count=1, skip_draws=3):
+    """Path-traced radiance along caller rays (RaylibAMD_TraceRadiance / RaylibAMD_TraceRadianceDevice).
+
+    rays: (n, 8) float32 -- org xyz, time, dir xyz, and the stream index as the uint32 whose bits the last column holds (rays[:, 7].view(uint32)).
+    A NumPy array goes through the host entry and returns an (n, 4) float32 array.  A float32 torch tensor on the device goes through the device entry,
+    ordered after the work already queued on torch.cuda.current_stream() (on torch's default stream, whose handle the library reads as its own stream,
+    that stream is synchronised first and the call is synchronous); the time interval handed to the library is the tensor's own minimum and maximum.  It
+    returns an (n, 4) float32 tensor.  Raises RuntimeError when the library refuses the call."""
+    prm = RadianceParams(int(max_path), float(tmin), int(sample_first), int(sample_count), int(skip_draws), 0.0, 0.0)
+    if isinstance(rays, np.ndarray):
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        n = len(r)
+        out = np.zeros((n, 4), np.float32)
+        ok = lib.RaylibAMD_TraceRadiance(scene, C.byref(prm), r.ctypes.data_as(C.POINTER(PathRay)), n, out.ctypes.data_as(C.POINTER(C.c_float)))
+        if ok != 1:
+            raise RuntimeError("RaylibAMD_TraceRadiance refused the call")
+        return out
+    import torch
+    if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.dtype == torch.float32):
+        raise TypeError("rays: a float32 NumPy array or a float32 torch tensor on the device")
+    r = rays.reshape(-1, 8).contiguous()
+    n = r.shape[0]
+    out = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+    if n:
+        prm.timeMin, prm.timeMax = float(r[:, 3].min()), float(r[:, 3].max())
+    stream = torch.cuda.current_stream(r.device)
+    if stream.cuda_stream == 0:
+        stream.synchronize()   # (as trace_rays: the library's stream is not ordered against torch's default stream)
+    ok = lib.RaylibAMD_TraceRadianceDevice(scene, C.byref(prm), C.cast(C.c_void_p(r.data_ptr()), C.POINTER(PathRay)), n,
+                                           C.cast(C.c_void_p(out.data_ptr()), C.POINTER(C.c_float)), C.c_void_p(stream.cuda_stream))
+    if ok != 1:
+        raise RuntimeError("RaylibAMD_TraceRadianceDevice refused the call")
+    return out
+
+
 # Per-ray / per-unit algorithmic byte constants of the flat layout (csrc/rl_device.h)
 NODE_B, TRI_B, SHADE_B, TEXEL_B, PIXEL_B = 64, 64, 64, 16, 16
 
@@ -216,6 +270,9 @@ _EXPORTS = {
     "RaylibAMD_TraceRays": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(Ray), C.c_int32, C.c_float, C.c_void_p, C.POINTER(C.c_int32)]),
     "RaylibAMD_TraceRaysDevice": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(Ray), C.c_int32, C.c_float, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "RaylibAMD_PlanRayQuery": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(QueryPlan)]),
+    "RaylibAMD_TraceRadiance": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(PathRay), C.c_int32, C.POINTER(C.c_float)]),
+    "RaylibAMD_TraceRadianceDevice": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(PathRay), C.c_int32, C.POINTER(C.c_float), C.c_void_p]),
+    "RaylibAMD_PlanRadiance": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(QueryPlan)]),
     "RaylibAMD_VerifyExactMath": (C.c_int32, [C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "RaylibAMD_CullCells": (C.c_int32, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_float)]),
     "RaylibAMD_SceneNumTriangles": (C.c_int32, [C.c_void_p]),
