@@ -411,7 +411,7 @@ uint64_t RaylibAMD_GetSeed(void) { return CurrentSeed(); }
 void RaylibAMD_GetLastStats(RaylibAMDStats* out)
 {
 	if (!out) return;
-	// a whole-frame render over several ranks returns with the frame in flight (rl_runtime.inl RenderMulti): its counters and times arrive now
+	// a whole-frame render over several ranks returns with the frame in flight (rl_rt_render.hip RenderMulti): its counters and times arrive now
 	RaylibAMDStats late;
 	const bool have = DeviceDrain(&late);
 	std::lock_guard<std::mutex> lk(g_stateMu);
@@ -589,7 +589,7 @@ int32_t RaylibAMD_RenderDevice(const RendererSettings* settings, SceneHandle sce
                                uint32_t cellFirst, uint32_t cellStride, void* outDevice)
 {
 	if (!settings || settings->viewportWidth == 0 || settings->viewportHeight == 0) return 0;
-	// (a buffer of the caller's: nothing of the library's protects it while a frame is in flight, so this entry is synchronous on every path -- rl_runtime.inl RenderMulti)
+	// (a buffer of the caller's: nothing of the library's protects it while a frame is in flight, so this entry is synchronous on every path -- rl_rt_render.hip RenderMulti)
 	return RenderInternal(settings, (Scene*)scene, (Camera*)camera, cellFirst, cellStride ? cellStride : 1, outDevice, nullptr, outDevice != nullptr) ? 1 : 0;
 }
 

@@ -473,7 +473,7 @@ static void CollapseWide8(std::vector<TmpNode>& T, int32_t root, Wide8& W, bool 
 }
 
 // the expected node steps of a random ray through the 4-wide collapse of T (sum of the wide nodes' areas over the root's), without building it: what decides
-// whether a scene's rays walk the 8-wide tree by default (rl_runtime.inl RL_BVH8_MIN_STEPS) -- and only then are its leaves split for that tree
+// whether a scene's rays walk the 8-wide tree by default (rl_device.h RL_BVH8_MIN_STEPS) -- and only then are its leaves split for that tree
 static double ExpectedSteps4(const std::vector<TmpNode>& T, int32_t root)
 {
 	const double rootArea = std::max((double)T[root].box.halfArea(), 1e-30);

@@ -1,4 +1,4 @@
-// Host side of the "cells that cannot see the scene" rule (rl_runtime.inl EnqueueRender uses it per frame; RaylibAMD_CullCells exposes it to the tests).
+// Host side of the "cells that cannot see the scene" rule (rl_rt_frame.hip EnqueueRender uses it per frame; RaylibAMD_CullCells exposes it to the tests).
 #include "rl_host.h"
 
 #include <algorithm>

@@ -124,7 +124,7 @@ __device__ __forceinline__ Tri TriFrom(const float4* p)
 	t.v1 = v3(q1.z, q1.w, q2.x); t.v2 = v3(q2.y, q2.z, q2.w);
 	t.u = t.v1 - t.v0; t.v = t.v2 - t.v0;   // geom/triangle.cc:30-31
 	t.uv = q3.x; t.uu = q3.y; t.vv = q3.z; t.rden = q3.w;
-	t.denom = t.uv * t.uv - t.uu * t.vv;    // geom/triangle.cc:39-41, the host's own three operations (rl_runtime.inl UploadScene): the record's slot holds 1 / denom
+	t.denom = t.uv * t.uv - t.uu * t.vv;    // geom/triangle.cc:39-41, the host's own three operations (rl_scene.cc FlattenScene): the record's slot holds 1 / denom
 	return t;
 }
 __device__ __forceinline__ Tri LoadTri(const DSceneView& S, int i) { return TriFrom((const float4*)(S.isect + i)); }
@@ -147,7 +147,7 @@ __device__ __noinline__ int AlphaTestCandidateNI(const DTriShade* shade, const i
                                                  const float* texels, int tri, float a, float b)
 {
 	const float4* p = (const float4*)(shade + tri);
-	// the texture comes from the per-triangle table (rl_runtime.inl UploadScene), fetched beside the triangle's UVs: one dependent load fewer than through the material
+	// the texture comes from the per-triangle table (rl_scene.cc FlattenScene), fetched beside the triangle's UVs: one dependent load fewer than through the material
 	int tex = alphaTex ? alphaTex[tri] : 0;
 	const float4 q2 = p[2], q3 = p[3];
 	const float s0 = q2.y, t0 = q2.z, s1 = q2.w, t1 = q3.x, s2 = q3.y, t2 = q3.z;

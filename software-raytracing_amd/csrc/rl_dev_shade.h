@@ -462,8 +462,6 @@ __device__ __forceinline__ bool Scatter(const DSceneView& S, const Mat& m, V3 in
 	}
 }
 
-struct SkyRot { float m0[3], m1[3], m2[3]; };   // Rotator(yaw 90).rotate rows, computed on the host (renderer.cc:166-168)
-
 // Miss shader: sky panorama + sun (reference render/renderer.cc:155-199)
 // PLAIN: the launch has no sky image (rl_plan.cc), and the panorama lookup is compiled out
 template <int STACK, bool PRIMS, bool FULL, int LDS = 0, bool PLAIN = false>

@@ -220,6 +220,8 @@ struct DSceneView {
 	int32_t fastBary;          // every triangle's rden is usable (above): the barycentric divisions take the short form
 };
 
+struct SkyRot { float m0[3], m1[3], m2[3]; };   // Rotator(yaw 90).rotate rows, computed on the host (renderer.cc:166-168; rl_scene.cc FlattenScene)
+
 // Counters written by the kernels (one 64-bit atomic per wave and counter at exit).
 enum { CNT_RAYS = 0, CNT_NODES, CNT_TRIS, CNT_SHADED, CNT_TEXELS, CNT_SAMPLES, CNT_TRIPS, CNT_COUNT };
 
@@ -243,7 +245,7 @@ struct DRenderParams {
 	uint32_t guideShift;       // 0: every draw asks for jobChunk jobs; s > 0: at most (jobs left in the band at the wave's previous draw) >> s (TakeJobs)
 	uint32_t padQueue;
 	float    invWidth, invHeight;   // RN(1 / (float)width), RN(1 / (float)height): the pixel -> [0, 1) divisions of GenerateCell (rl_dev_jobs.h PixelUV)
-	// Cells no camera ray of which can meet the scene's bounding box (host, rl_runtime.inl CullCells: pinhole camera, no sky panorama, the frame's box on the
+	// Cells no camera ray of which can meet the scene's bounding box (host, rl_cull.cc CullCells: pinhole camera, no sky panorama, the frame's box on the
 	// image plane with a margin) are not in the job list: activeCells[i] is the i-th listed local cell (nullptr: all numLocalCells cells, in order), and
 	// k_resolve sums the constant every one of their samples would have come to -- emptyL, the sun's illuminance or nothing -- for cells flagged in cellEmpty.
 	const uint32_t* activeCells;
@@ -260,7 +262,7 @@ struct DRenderParams {
 // Several views of one scene in one launch (RaylibAMD_RenderViews): the views twins of the kernels (k_trace_views, k_trace_pool_views, k_resolve_views,
 // k_aov_views) take this as one extra trailing argument; DRenderParams then describes the batch -- numLocalCells = views * cellsPerView, batch cell
 // v * cellsPerView + c is cell c of view v -- and its `camera` is not read.  Everything else that could differ between views is the same for all of them
-// (the cull's constant: rl_runtime.inl RenderViewsLocked).
+// (the cull's constant: rl_rt_frame.hip DeviceRenderViews).
 #define RL_MAX_VIEWS 64
 struct DViews {
 	const DCamera* cameras;      // [views], on the device

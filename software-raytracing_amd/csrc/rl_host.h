@@ -77,7 +77,7 @@ struct Image {
 	// bumped whenever the pixels change (reallocation, a render into the image, PostProcess): a scene that uses the image as its
 	// sky panorama re-reads it at the next render, as the reference does through the handle (renderer.cc:159-176)
 	// The value is unique in the PROCESS, not per image (NextImageVersion): a new image that malloc puts at a destroyed image's address
-	// can never look like that image to a cache keyed on (pointer, version) -- the device copy of the sky, rl_runtime.inl SyncSky.
+	// can never look like that image to a cache keyed on (pointer, version) -- the device copy of the sky, rl_rt_scene.hip SyncSky.
 	uint64_t version = NextImageVersion();
 	void Touch() { version = NextImageVersion(); }
 	void SyncHost() const;
@@ -162,7 +162,7 @@ struct HostCube { f3 minBounds, maxBounds; float timeStartMove; f3 velocity; int
 bool WalkStackHost(const BVH& bvh, const std::vector<HostTriangle>& tris, const std::vector<HostSphere>& spheres, const std::vector<HostCube>& cubes, int tree,
                    const float* rays, int n, float tMin, int capacity, float* outT, uint32_t* outHighWater);
 
-struct DeviceScene;   // rl_runtime.inl
+struct DeviceScene;   // rl_rt.h
 
 struct Scene {
 	std::vector<OBJModel*> models;    // borrowed (reference raylib.cc:264-268)
@@ -193,6 +193,19 @@ struct Scene {
 // plain instance may render the scene (rl_plan.cc adds the per-render conditions)
 bool ScenePlain(const Scene& sc);
 
+// The scene as the devices hold it (rl_device.h), in leaf order (rl_scene.cc FlattenScene): triangle records -- rden is 1 / denom for the short barycentric
+// divisions, NaN where denom is 0 or NaN or outside [2^-62, 2^125], and the last case clears fastBary for the whole scene (RAYLIB_FAST_BARY=0 clears it whatever
+// the scene) --, materials, textures with a pow(texel, 2.2) copy of every map a microfacet material uses as albedo (the material points at the copy), the texel
+// pool, per triangle slot the texture its cut-out test reads (alphaTex; empty: no material has a map), spheres, cubes, and the sky panorama's rotation.
+struct FlatScene {
+	std::vector<DTriIsect> isect; std::vector<DTriShade> shade; std::vector<int32_t> alphaTex;
+	std::vector<DMaterial> materials; std::vector<DTexture> textures; std::vector<float> texels;
+	std::vector<DSphere> spheres; std::vector<DCube> cubes;
+	int32_t fastBary = 1;
+	SkyRot skyRot;
+};
+FlatScene FlattenScene(const Scene& sc);   // every texture's host pixels are current (Image::hostStale is not looked at)
+
 // loaders (rl_obj_loader.cc, rl_image_io.cc)
 bool LoadOBJ(const char* path, OBJModel& out);
 void TransformOBJ(OBJModel& m, float tx, float ty, float tz, float yaw, float pitch, float roll, float sx, float sy, float sz);
@@ -206,7 +219,7 @@ void LogStart();
 void LogFlush();
 void LogStop();
 
-// device side (rl_runtime.inl, in rl_render.hip's unit)
+// device side (the host runtime: rl_rt.h, rl_rt_*.hip)
 struct RenderRequest {
 	RendererSettings settings;
 	DCamera camera;
@@ -266,7 +279,7 @@ bool DeviceVerifyExactMath(int which, uint64_t* outMismatches, uint64_t* outFirs
 bool DeviceEvalHook(int kind, Scene* sc, const DCamera* cam, int a, int b, const float* in, int n, uint64_t seed, float* out);
 void DeviceReleaseScene(DeviceScene* dev);
 
-// Progressive rendering (include/raylib_amd.h RaylibAMD_BeginProgressive; rl_runtime.inl).  Begin: nullptr without a device or memory.  Step: the number of
+// Progressive rendering (include/raylib_amd.h RaylibAMD_BeginProgressive; rl_rt_render.hip).  Begin: nullptr without a device or memory.  Step: the number of
 // live cells after the pass (0: finished), -1 when refused or failed -- `rendered` tells whether a pass ran (and `stats` is its numbers).
 struct ProgressiveSession;
 ProgressiveSession* DeviceProgressiveBegin(Scene& sc, const RenderRequest& req, float threshold, uint32_t minSamples);

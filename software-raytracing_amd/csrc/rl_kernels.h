@@ -1,7 +1,8 @@
-// Every kernel that has a views twin or lives in a translation unit other than the one that launches it: its prototype, its instance list and the
-// explicit instantiation declarations, each written once.  A kernel's body is an .inl file that always defines it; the unit that includes the body owns the
-// kernel and follows it with the instantiation definitions (RL_..._INSTANCES(RL_K_...)), every other unit sees what is here.
-//   rl_render.hip        k_trace, k_resolve, k_aov (+ the small kernels and the host runtime, which launches everything)
+// Every kernel the host runtime (rl_rt_*.hip) launches: its prototype, its instance list and the explicit instantiation declarations, each written once, and
+// the structs a kernel shares with the host.  A kernel's body always defines it; the unit that holds the body owns the kernel and follows it with the
+// instantiation definitions (RL_..._INSTANCES(RL_K_...)), every other unit sees what is here.  No kernel lives in a runtime unit.
+//   rl_render.hip        k_trace, k_resolve, k_aov, k_closest_hit and the small kernels (progressive resolve and compaction, post-processing, RGB packing,
+//                        the multi-rank scatter, the test hooks)
 //   rl_render_views.hip  k_trace_views, k_resolve_views, k_aov_views: the views twins (RaylibAMD_RenderViews).  Instantiated beside the one-view kernels they
 //                        change how the helpers both call are inlined into those (tools/isa_equivalence.py)
 //   rl_render_pool.hip   k_trace_pool and its twin: a scheduler strategy of its own (Makefile POOLFLAGS)
@@ -31,7 +32,7 @@ namespace rl {
 // FULL: the wide tree, if the launch carries one, has float boxes (S.nodes4f) -- small scenes; else grid nodes (S.nodes4)
 // LDS (with FULL, triangle scenes within the RL_LDS_MAX* limits): the scene's records are copied to LDS at the start and read from there;
 //     LDS == 2: a scene of <= 16 leaves, walked through its leaf list (TraverseLeafList) instead of its tree
-// (STACK, PRIMS, FULL, LDS, PLAIN): every instance rl_runtime.inl KernelFor names.
+// (STACK, PRIMS, FULL, LDS, PLAIN): every instance rl_rt_frame.hip KernelFor names.
 #define RL_TRACE_ARGS const DRenderParams, const DSceneView, const SkyRot, SampleRGB* __restrict__, float* __restrict__, unsigned long long* __restrict__, unsigned int* __restrict__
 template <int STACK, bool PRIMS, bool FULL, int LDS = 0, bool PLAIN = false>
 __global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 2)) k_trace(RL_TRACE_ARGS);
@@ -41,8 +42,10 @@ __global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 
 	X(16, false, false, 0, false) X(16, false, true, 0, false) X(16, false, true, 1, false) X(16, false, true, 2, false) X(16, false, true, 2, true) \
 	X(32, false, false, 0, false) X(32, false, true, 0, false) X(32, true, false, 0, false) X(32, true, true, 0, false) \
 	X(64, false, false, 0, false) X(64, false, true, 0, false) X(64, true, false, 0, false) X(64, true, true, 0, false)
+#define RL_K_TRACE(a, b, c, d, e) template __global__ void k_trace<a, b, c, d, e>(RL_TRACE_ARGS);
 #define RL_K_TRACE_VIEWS(a, b, c, d, e) template __global__ void k_trace_views<a, b, c, d, e>(RL_TRACE_ARGS, const DViews);
-RL_TRACE_INSTANCES(extern RL_K_TRACE_VIEWS)   // (k_trace's own instances are the ones rl_runtime.inl names: implicit)
+RL_TRACE_INSTANCES(extern RL_K_TRACE)
+RL_TRACE_INSTANCES(extern RL_K_TRACE_VIEWS)
 
 // ---------------------------------------------------------------------------
 // The pool megakernel (rl_dev_pool.h, rl_k_trace_pool.inl): k_trace's arguments.
@@ -52,7 +55,7 @@ template <int STACK, bool PRIMS, int K, int LSTACK = STACK, int WIDE = 0>
 __global__ void __launch_bounds__(RL_BLOCK, (PoolOcc<LSTACK, PRIMS, K>::kBlocks)) k_trace_pool(RL_TRACE_ARGS);
 template <int STACK, bool PRIMS, int K, int LSTACK = STACK, int WIDE = 0>
 __global__ void __launch_bounds__(RL_BLOCK, (PoolOcc<LSTACK, PRIMS, K>::kBlocks)) k_trace_pool_views(RL_TRACE_ARGS, const DViews);
-// The instances the runtime selects from (rl_runtime.inl KernelFor)
+// The instances the runtime selects from (rl_rt_frame.hip KernelFor)
 #define RL_POOL_INSTANCES(X) \
 	X(16, false, 2, 16, 0) X(16, false, 3, 16, 0) X(16, false, 4, 16, 0) X(32, false, 2, 32, 0) X(32, false, 3, 32, 0) X(32, false, 4, 32, 0) \
 	X(32, false, 2, 4, 0) X(32, false, 2, RL_POOL_SHORT_LSTACK, 0) \
@@ -74,14 +77,52 @@ k_resolve_views(const DRenderParams Pb, const DSceneView S, const SkyRot R, cons
 template <int STACK, bool PRIMS> __global__ void __launch_bounds__(RL_BLOCK) k_aov(RL_AOV_ARGS);
 template <int STACK, bool PRIMS> __global__ void __launch_bounds__(RL_BLOCK) k_aov_views(RL_AOV_ARGS, const DViews);
 #define RL_AOV_INSTANCES(X) X(16, false) X(32, false) X(32, true) X(64, false) X(64, true)
+#define RL_K_AOV(a, b) template __global__ void k_aov<a, b>(RL_AOV_ARGS);
 #define RL_K_AOV_VIEWS(a, b) template __global__ void k_aov_views<a, b>(RL_AOV_ARGS, const DViews);
+RL_AOV_INSTANCES(extern RL_K_AOV)
 RL_AOV_INSTANCES(extern RL_K_AOV_VIEWS)
+
+// ---------------------------------------------------------------------------
+// Progressive rendering (rl_rt.h ProgressiveSession; include/raylib_amd.h RaylibAMD_BeginProgressive)
+// What a session keeps on the device, cell-major (slot = cell * 64 + pixel of the cell): the running colour sum in sample order, the moments of y, and
+// per cell its samples so far and whether it has stopped.
+struct ProgressiveState {
+	float4* sum;
+	float* s1;
+	float* s2;
+	uint32_t* cellSamples;
+	uint8_t* stopped;
+	float threshold;
+	uint32_t minSamples;
+};
+__global__ void __launch_bounds__(RL_BLOCK)
+k_progressive_resolve(const DRenderParams P, const DSceneView S, const SkyRot R, const SampleRGB* __restrict__ samples, const ProgressiveState st,
+                      float4* __restrict__ out, int lastBatch);
+#define RL_COMPACT_BLOCK 1024
+#define RL_COMPACT_PER 8
+__global__ void __launch_bounds__(RL_COMPACT_BLOCK)
+k_progressive_compact(uint32_t* __restrict__ live, uint32_t* __restrict__ trace, const uint8_t* __restrict__ stopped, const uint8_t* __restrict__ empty,
+                      uint32_t numLive, uint32_t width, uint32_t height, uint32_t cellsX, uint32_t* __restrict__ counts);
+
+// ---------------------------------------------------------------------------
+// Images (post-processing, the RGB dump) and the frame from the ranks' cell buffers (N > 1 behind Raylib_Render): cell c was rendered by rank c % N as its (c / N)-th cell
+__global__ void __launch_bounds__(RL_BLOCK) k_pp_max(const float4* __restrict__ px, size_t n, unsigned int* __restrict__ whiteBits);
+__global__ void __launch_bounds__(RL_BLOCK) k_pp_map(float4* __restrict__ px, size_t n, const unsigned int* __restrict__ whiteBits);
+__global__ void __launch_bounds__(RL_BLOCK) k_pack_rgb(const float4* __restrict__ px, float4* __restrict__ out, float* __restrict__ outTail, size_t n);
+struct ScatterPlan { uint32_t ranks; uint32_t offset[16]; };   // offset[r]: first float4 of rank r's cells in the gather buffer
+__global__ void __launch_bounds__(RL_BLOCK)
+k_scatter_cells(const float4* __restrict__ gather, float4* __restrict__ out, uint32_t width, uint32_t height, uint32_t cellsX, const ScatterPlan plan);
 
 // ---------------------------------------------------------------------------
 // The ray queries (RaylibAMD_TraceRays; rl_k_query.inl)
 // A hit record as RaylibAMD_ClosestHit and the surface query of RaylibAMD_TraceRays return it (oracle/flat_scene.h FlatHit)
 struct DHitOut { int32_t hit; float t; float p[3]; float n[3]; float paramU, paramV; int32_t material; };
 enum { RL_QK_ANY = 0, RL_QK_CLOSEST = 1, RL_QK_SURFACE = 2 };   // RAYLIB_AMD_QUERY_*
+// rays in (origin, direction: six floats) -> hit records out (RaylibAMD_ClosestHit, tests)
+template <int STACK, bool PRIMS>
+__global__ void __launch_bounds__(RL_BLOCK) k_closest_hit(const DSceneView S, const float* __restrict__ rays, int n, float tMin, DHitOut* __restrict__ out);
+extern template __global__ void k_closest_hit<32, true>(const DSceneView, const float* __restrict__, int, float, DHitOut* __restrict__);
+extern template __global__ void k_closest_hit<64, true>(const DSceneView, const float* __restrict__, int, float, DHitOut* __restrict__);
 // Rays (k_query) or jobs (k_radiance) a wave takes per atomic on the global counter: one value for both kernels
 #ifndef RL_QUERY_CHUNK
 #define RL_QUERY_CHUNK 64u
@@ -91,7 +132,7 @@ struct DQueryHit { float t; int32_t prim; float b1, b2; };      // RaylibAMDHitT
 // PRIMS: the scene holds spheres or cubes (binary tree only).  rays: n records of two float4 (org, tMin | dir, tMax).  counters: CNT_* sums, or null.
 #define RL_QUERY_ARGS const DSceneView, const float4* __restrict__, uint32_t, float, void* __restrict__, int32_t* __restrict__, const int32_t* __restrict__, unsigned int* __restrict__, unsigned long long* __restrict__
 template <int TREE, int KIND, int STACK, bool PRIMS> __global__ void __launch_bounds__(RL_BLOCK) k_query(RL_QUERY_ARGS);
-// The instances rl_runtime.inl QueryKernelFor selects from: (TREE, KIND, STACK, PRIMS)
+// The instances rl_rt_rays.hip QueryKernelOfKind selects from: (TREE, KIND, STACK, PRIMS)
 #define RL_QUERY_INSTANCES_K(X, K) \
 	X(2, K, 32, false) X(2, K, 32, true) X(2, K, 64, false) X(2, K, 64, true) X(4, K, 32, false) X(4, K, 64, false) X(8, K, 2 * RL_POOL8_MAXLEVELS, false)
 #define RL_QUERY_INSTANCES(X) RL_QUERY_INSTANCES_K(X, 0) RL_QUERY_INSTANCES_K(X, 1) RL_QUERY_INSTANCES_K(X, 2)
@@ -108,9 +149,17 @@ struct DRadianceParams { unsigned long long seedMixed; int32_t maxPathLength; fl
 #define RL_RADIANCE_ARGS const DSceneView, const SkyRot, const DRadianceParams, const float4* __restrict__, uint32_t, float4* __restrict__, float* __restrict__, unsigned int* __restrict__, unsigned long long* __restrict__
 template <int TREE, int STACK, bool PRIMS>
 __global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 2)) k_radiance(RL_RADIANCE_ARGS);
-// The instances rl_runtime.inl RadianceKernelFor selects from: (TREE, STACK, PRIMS)
+// The instances rl_rt_rays.hip RadianceKernelFor selects from: (TREE, STACK, PRIMS)
 #define RL_RADIANCE_INSTANCES(X) X(2, 32, false) X(2, 32, true) X(2, 64, false) X(2, 64, true) X(4, 32, false) X(4, 64, false)
 #define RL_K_RADIANCE(a, b, c) template __global__ void k_radiance<a, b, c>(RL_RADIANCE_ARGS);
 RL_RADIANCE_INSTANCES(extern RL_K_RADIANCE)
+
+// ---------------------------------------------------------------------------
+// Test hooks (rl_rt_hooks.hip): single functions of the hot path evaluated on arrays
+__global__ void __launch_bounds__(RL_BLOCK) k_eval_scatter(const DSceneView S, int material, const float* __restrict__ in, int n, unsigned long long seed, float* __restrict__ out);
+__global__ void __launch_bounds__(RL_BLOCK) k_eval_camera(const DCamera cam, const float* __restrict__ uv, int n, unsigned long long seed, float* __restrict__ out);
+__global__ void __launch_bounds__(RL_BLOCK) k_eval_texture(const DSceneView S, int tex, int srgb, const float* __restrict__ uv, int n, float* __restrict__ out);
+__global__ void __launch_bounds__(RL_BLOCK) k_eval_math(int fn, const float* __restrict__ x, const float* __restrict__ y, int n, float* __restrict__ out);
+__global__ void __launch_bounds__(RL_BLOCK) k_verify_exact_math(int which, unsigned long long* __restrict__ out);
 
 } // namespace rl

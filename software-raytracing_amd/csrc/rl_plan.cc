@@ -242,7 +242,7 @@ ViewsPlan PlanViews(const CullScene& cs, const RendererSettings& st, const DCame
 	}
 	V.numActive = (uint32_t)V.active.size();
 	const uint32_t spp = (uint32_t)(st.samplesPerPixel > 1 ? st.samplesPerPixel : 1);
-	// the job-count guard of a launch (rl_runtime.inl EnqueueFrame) splits samples into batches, never views
+	// the job-count guard of a launch (rl_rt_frame.hip EnqueueFrame) splits samples into batches, never views
 	const uint64_t perSample = (uint64_t)V.numActive * 64u;
 	const uint64_t maxBatch = perSample ? 0xF0000000ull / perSample : spp;
 	V.knobs = knobs;

@@ -1,5 +1,5 @@
 // Which megakernel instance a render launches, on which tree, and how its job list is laid out: host facts in, plain structs out,
-// no HIP calls (rl_plan.cc).  rl_runtime.inl launches what these say; RaylibAMD_PlanRender exposes them to the tests.
+// no HIP calls (rl_plan.cc).  The runtime (rl_rt_*.hip) launches what these say; RaylibAMD_PlanRender exposes them to the tests.
 #pragma once
 
 #include "rl_host.h"

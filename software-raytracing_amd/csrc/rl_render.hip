@@ -25,7 +25,7 @@
 // vertex back to the camera, so every rounding step is the reference's.
 //
 // The device library is rl_dev_*.h; a kernel's body is an rl_k_*.inl file, and rl_kernels.h says which translation unit owns which kernel.  This
-// unit owns the one-view k_trace, k_resolve and k_aov, the small kernels below, and the host runtime (rl_runtime.inl), which launches them all.
+// unit owns the one-view k_trace, k_resolve and k_aov and the small kernels below: kernels only.  The host runtime that launches them is rl_rt_*.hip.
 
 // ---- settings: this unit takes every default ----
 
@@ -39,19 +39,7 @@ namespace rl {
 #include "rl_k_trace.inl"
 #include "rl_k_resolve.inl"
 
-// ---- progressive rendering (rl_runtime.inl ProgressiveSession; include/raylib_amd.h RaylibAMD_BeginProgressive) ----
-// What a session keeps on the device, cell-major (slot = cell * 64 + pixel of the cell): the running colour sum in sample order, the moments of y, and
-// per cell its samples so far and whether it has stopped.
-struct ProgressiveState {
-	float4* sum;
-	float* s1;
-	float* s2;
-	uint32_t* cellSamples;
-	uint8_t* stopped;
-	float threshold;
-	uint32_t minSamples;
-};
-
+// ---- progressive rendering (rl_kernels.h ProgressiveState; include/raylib_amd.h RaylibAMD_BeginProgressive) ----
 // One pass's batch over EVERY cell of the frame (one wave = one 8x8 cell): a cell still sampled adds the batch's samples to its sums (the megakernel
 // traced it: P.activeCells holds the session's list; or it lies outside the silhouette: P.cellEmpty), exactly as k_resolve does.  The pass's last batch
 // then decides whether the cell stops (ProgressivePixelError, maximum over the wave) and writes every valid pixel of the row-major frame as its
@@ -99,8 +87,6 @@ k_progressive_resolve(const DRenderParams P, const DSceneView S, const SkyRot R,
 // The session's lists after a pass, in one workgroup: `live` (every cell still sampled, ascending) loses the cells that stopped, in place and in order,
 // and `trace` becomes the live cells inside the silhouette, in order -- the megakernel's job list of the next pass, bands of whole cells as before.
 // counts: [0] live cells, [1] listed cells, [2..3] valid pixels of the live cells outside the silhouette (64 bits; the next pass's culled samples per sample).
-#define RL_COMPACT_BLOCK 1024
-#define RL_COMPACT_PER 8
 __global__ void __launch_bounds__(RL_COMPACT_BLOCK)
 k_progressive_compact(uint32_t* __restrict__ live, uint32_t* __restrict__ trace, const uint8_t* __restrict__ stopped, const uint8_t* __restrict__ empty,
                       uint32_t numLive, uint32_t width, uint32_t height, uint32_t cellsX, uint32_t* __restrict__ counts)
@@ -393,8 +379,7 @@ k_pack_rgb(const float4* __restrict__ px, float4* __restrict__ out, float* __res
 	}
 }
 
-// The frame from the ranks' cell buffers (N > 1 behind Raylib_Render): cell c was rendered by rank c % N as its (c / N)-th cell.
-struct ScatterPlan { uint32_t ranks; uint32_t offset[16]; };   // offset[r]: first float4 of rank r's cells in the gather buffer
+// The frame from the ranks' cell buffers (N > 1 behind Raylib_Render): cell c was rendered by rank c % N as its (c / N)-th cell (rl_kernels.h ScatterPlan).
 __global__ void __launch_bounds__(RL_BLOCK)
 k_scatter_cells(const float4* __restrict__ gather, float4* __restrict__ out, uint32_t width, uint32_t height, uint32_t cellsX, const ScatterPlan plan)
 {
@@ -406,8 +391,10 @@ k_scatter_cells(const float4* __restrict__ gather, float4* __restrict__ out, uin
 	out[i] = gather[plan.offset[rank] + local * 64u + ((y & 7u) << 3) + (x & 7u)];
 }
 
-// ---- instances: the one-view kernels are instantiated where rl_runtime.inl names them (KernelFor, AovKernelFor) ----
+// ---- instances ----
+RL_TRACE_INSTANCES(RL_K_TRACE)
+RL_AOV_INSTANCES(RL_K_AOV)
+template __global__ void k_closest_hit<32, true>(const DSceneView, const float* __restrict__, int, float, DHitOut* __restrict__);
+template __global__ void k_closest_hit<64, true>(const DSceneView, const float* __restrict__, int, float, DHitOut* __restrict__);
 
 } // namespace rl
-
-#include "rl_runtime.inl"

@@ -3,7 +3,12 @@
 // re-stated for a flat device scene.
 #include "rl_host.h"
 
+#include <algorithm>
+#include <atomic>
 #include <chrono>
+#include <limits>
+#include <thread>
+#include <stdlib.h>
 #include <string.h>
 
 namespace rl {
@@ -216,6 +221,141 @@ void PostProcessHost(Image& img)
 		const float K = 1.0f / 2.2f;
 		p[0] = powf(rgb.x, K); p[1] = powf(rgb.y, K); p[2] = powf(rgb.z, K);
 	}
+}
+
+// Flatten the host scene into device records (leaf order): plain host code, no device involved (rl_rt_scene.hip UploadScene copies the result to every device in use).
+FlatScene FlattenScene(const Scene& sc)
+{
+	FlatScene F;
+	const size_t n = sc.triangles.size();
+	F.isect.resize(n);
+	std::vector<DTriIsect>& isect = F.isect;
+	std::atomic<int> fastBary(1);
+	if (const char* e = getenv("RAYLIB_FAST_BARY")) fastBary.store(atoi(e) != 0 ? 1 : 0);   // 0: the divisions, whatever the scene (parity tests compare the two)
+	F.shade.resize(n);
+	std::vector<DTriShade>& shade = F.shade;
+	auto flatten = [&](size_t k0, size_t k1) { for (size_t k = k0; k < k1; ++k) {
+		const HostTriangle& t = sc.triangles[sc.bvh.triOrder[k]];
+		DTriIsect& I = isect[k];
+		const f3 nrm = normalize(cross(t.v1 - t.v0, t.v2 - t.v0));   // geom/triangle.h:34-38
+		const f3 u = t.v1 - t.v0, v = t.v2 - t.v0;                   // geom/triangle.cc:30-31
+		const float uv = dot(u, v), uu = dot(u, u), vv = dot(v, v);  // :34-38
+		const float uvuv = uv * uv, uuvv = uu * vv;                  // :39-40
+		I.v0[0] = t.v0.x; I.v0[1] = t.v0.y; I.v0[2] = t.v0.z;
+		I.n[0] = nrm.x; I.n[1] = nrm.y; I.n[2] = nrm.z;
+		I.v1[0] = t.v1.x; I.v1[1] = t.v1.y; I.v1[2] = t.v1.z;
+		I.v2[0] = t.v2.x; I.v2[1] = t.v2.y; I.v2[2] = t.v2.z;
+		I.uv = uv; I.uu = uu; I.vv = vv;
+		{   // the reciprocal of denom = uvuv - uuvv for the short barycentric divisions (rl_dev_walk.h Barycentric, which states the conditions)
+			const float denom = uvuv - uuvv, mag = fabsf(denom);
+			if (denom == 0.0f || denom != denom) I.rden = std::numeric_limits<float>::quiet_NaN();
+			else if (mag >= 0x1p-62f && mag <= 0x1p125f) I.rden = 1.0f / denom;
+			else { I.rden = std::numeric_limits<float>::quiet_NaN(); fastBary.store(0, std::memory_order_relaxed); }
+		}
+		DTriShade& Sh = shade[k];
+		Sh.n0[0] = t.n0.x; Sh.n0[1] = t.n0.y; Sh.n0[2] = t.n0.z;
+		Sh.n1[0] = t.n1.x; Sh.n1[1] = t.n1.y; Sh.n1[2] = t.n1.z;
+		Sh.n2[0] = t.n2.x; Sh.n2[1] = t.n2.y; Sh.n2[2] = t.n2.z;
+		Sh.s0 = t.s0; Sh.t0 = t.t0; Sh.s1 = t.s1; Sh.t1 = t.t1; Sh.s2 = t.s2; Sh.t2 = t.t2;
+		Sh.material = t.material;
+	} };
+	{   // per-triangle records are independent: all host threads for large scenes (10 M triangles: 0.6 s on one thread)
+		unsigned threads = n >= (1u << 17) ? std::min(32u, std::max(1u, std::thread::hardware_concurrency())) : 1u;
+		if (const char* e = getenv("RAYLIB_BUILD_THREADS")) { int v = atoi(e); if (v > 0 && n >= (1u << 17)) threads = (unsigned)std::min(v, 32); }
+		std::vector<std::thread> pool;
+		const size_t per = (n + threads - 1) / threads;
+		for (unsigned t = 1; t < threads; ++t) { const size_t k0 = std::min(n, t * per), k1 = std::min(n, (t + 1) * per); if (k0 < k1) pool.emplace_back(flatten, k0, k1); }
+		flatten(0, std::min(n, per));
+		for (std::thread& th : pool) th.join();
+	}
+	F.fastBary = fastBary.load();
+	std::vector<DMaterial>& mats = F.materials;
+	mats.resize(sc.materials.size());
+	for (size_t i = 0; i < mats.size(); ++i) {
+		const HostMaterial& h = sc.materials[i];
+		DMaterial& m = mats[i]; memset(&m, 0, sizeof(m));
+		m.type = h.type;
+		memcpy(m.albedo, h.albedo, 12); m.roughness = h.roughness; m.metallic = h.metallic;
+		memcpy(m.emissive, h.emissive, 12); m.ior = h.ior; memcpy(m.transmission, h.transmission, 12);
+		m.fuzziness = h.fuzziness; memcpy(m.tex, h.tex, 20);
+	}
+	std::vector<DTexture>& texs = F.textures;
+	texs.resize(sc.textures.size());
+	std::vector<float>& pool = F.texels;
+	for (size_t i = 0; i < texs.size(); ++i) {
+		const Image& im = *sc.textures[i];
+		texs[i].offset = (uint32_t)(pool.size() / 4); texs[i].width = (int32_t)im.width; texs[i].height = (int32_t)im.height; texs[i].pad = 0;
+		// (a rendered image used as a texture has been fetched from the device by the caller: rl_rt_scene.hip UploadScene)
+		pool.insert(pool.end(), im.rgba.begin(), im.rgba.end());
+	}
+	// Albedo maps are read through Texture2D::Sample(bSRGB = true): nearest texel, then pow(texel, 2.2) on all four channels
+	// (reference render/texture.cc:44-50, material.cc:383,400) -- four powf per shading event and per alpha-tested candidate.
+	// The power of a texel does not depend on the ray: every texture some material uses as albedo gets a converted copy here
+	// (host powf = the reference's own function, the one csrc/rl_glibc_math.h restates), and the material points at the copy.
+	{
+		std::vector<int32_t> converted(texs.size(), -1);
+		for (DMaterial& m : mats) {
+			if (m.type != MAT_MICROFACET || m.tex[0] < 0 || (size_t)m.tex[0] >= converted.size()) continue;
+			const size_t src = (size_t)m.tex[0];
+			if (converted[src] < 0) {
+				DTexture t = texs[src];
+				const size_t count = (size_t)t.width * t.height * 4, from = (size_t)t.offset * 4;
+				t.offset = (uint32_t)(pool.size() / 4);
+				pool.resize(pool.size() + count);
+				float* dst = pool.data() + (size_t)t.offset * 4; const float* in = pool.data() + from;
+				unsigned threads = count >= (1u << 20) ? std::min(32u, std::max(1u, std::thread::hardware_concurrency())) : 1u;
+				std::vector<std::thread> workers;
+				const size_t per = (count + threads - 1) / threads;
+				auto run = [dst, in](size_t a, size_t b) { for (size_t i = a; i < b; ++i) dst[i] = powf(in[i], 2.2f); };
+				for (unsigned w = 1; w < threads; ++w) { const size_t a = std::min(count, w * per), b = std::min(count, (w + 1) * per); if (a < b) workers.emplace_back(run, a, b); }
+				run(0, std::min(count, per));
+				for (std::thread& th : workers) th.join();
+				converted[src] = (int32_t)texs.size();
+				texs.push_back(t);
+			}
+			m.tex[0] = converted[src];
+		}
+	}
+	// The cut-out test of a candidate (geom/triangle.cc:54 -> MicrofacetMaterial::AlphaTest) needs one texel of the triangle's material's albedo map: as a table per
+	// triangle slot the texture is known from the triangle alone, and the test's chain of dependent loads inside the walk is triangle -> texture -> texel instead
+	// of triangle -> material -> texture -> texel (round 5).
+	std::vector<int32_t>& alphaTex = F.alphaTex;
+	{
+		bool any = false;
+		for (const DMaterial& m : mats) if (m.type == MAT_MICROFACET && m.tex[0] >= 0) any = true;
+		if (any) {
+			alphaTex.resize(n);
+			for (size_t k = 0; k < n; ++k) {
+				const int32_t mi = shade[k].material;
+				alphaTex[k] = (mi >= 0 && (size_t)mi < mats.size() && mats[(size_t)mi].type == MAT_MICROFACET && mats[(size_t)mi].tex[0] >= 0) ? mats[(size_t)mi].tex[0] : -1;
+			}
+		}
+	}
+	std::vector<DSphere>& dsph = F.spheres;
+	dsph.resize(sc.spheres.size());
+	for (size_t i = 0; i < dsph.size(); ++i) {
+		memset(&dsph[i], 0, sizeof(DSphere));
+		dsph[i].center[0] = sc.spheres[i].center.x; dsph[i].center[1] = sc.spheres[i].center.y; dsph[i].center[2] = sc.spheres[i].center.z;
+		dsph[i].radius = sc.spheres[i].radius; dsph[i].material = sc.spheres[i].material;
+	}
+	std::vector<DCube>& dcub = F.cubes;
+	dcub.resize(sc.cubes.size());
+	for (size_t i = 0; i < dcub.size(); ++i) {
+		memset(&dcub[i], 0, sizeof(DCube));
+		const HostCube& h = sc.cubes[i];
+		dcub[i].minBounds[0] = h.minBounds.x; dcub[i].minBounds[1] = h.minBounds.y; dcub[i].minBounds[2] = h.minBounds.z; dcub[i].timeStartMove = h.timeStartMove;
+		dcub[i].maxBounds[0] = h.maxBounds.x; dcub[i].maxBounds[1] = h.maxBounds.y; dcub[i].maxBounds[2] = h.maxBounds.z; dcub[i].material = h.material;
+		dcub[i].velocity[0] = h.velocity.x; dcub[i].velocity[1] = h.velocity.y; dcub[i].velocity[2] = h.velocity.z;
+	}
+	{   // Rotator(yaw = 90).rotate rows, reference geom/transform.cc:47-65 (host libm, as the reference)
+		const float pi_f = (float)3.1415926535897932385;
+		const float ry = 90.0f * pi_f / 180.0f, rp = 0.0f * pi_f / 180.0f, rr = 0.0f * pi_f / 180.0f;
+		const float ch = cosf(ry), sh = sinf(ry), cp = cosf(rp), sp = sinf(rp), cb = cosf(rr), sb = sinf(rr);
+		F.skyRot.m0[0] = ch * cb + sh * sp * sb; F.skyRot.m0[1] = sb * cp; F.skyRot.m0[2] = -sh * cb + ch * sp * sb;
+		F.skyRot.m1[0] = -ch * sb + sh * sp * cb; F.skyRot.m1[1] = cb * cp; F.skyRot.m1[2] = sb * sh + ch * sp * cb;
+		F.skyRot.m2[0] = sh * cp; F.skyRot.m2[1] = -sp; F.skyRot.m2[2] = ch * cp;
+	}
+	return F;
 }
 
 } // namespace rl

@@ -36,7 +36,7 @@ def render_all(lib, workdir):
 def caller_buffer(lib, workdir):
     """RaylibAMD_RenderDevice(whole frame) into device memory of the CALLER's, read back at once with a plain hipMemcpy (the null stream does not
     wait for the library's non-blocking streams): the entry is documented as synchronous, also when the frame is assembled from several ranks
-    on the gather stream (csrc/rl_runtime.inl RenderMulti, RenderRequest::callerOwnsOut).  Then the buffer is freed straight away."""
+    on the gather stream (csrc/rl_rt_render.hip RenderMulti, RenderRequest::callerOwnsOut).  Then the buffer is freed straight away."""
     import ctypes as C
     hip = C.CDLL("libamdhip64.so")
     hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]; hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]; hip.hipFree.argtypes = [C.c_void_p]
@@ -61,7 +61,7 @@ def caller_buffer(lib, workdir):
 
 
 def back_to_back(lib, workdir):
-    """Calls that leave no time between them: with several ranks Raylib_Render returns with the frame still in flight (csrc/rl_runtime.inl
+    """Calls that leave no time between them: with several ranks Raylib_Render returns with the frame still in flight (csrc/rl_rt_render.hip
     RenderMulti), and whatever comes next -- another render into the same image, into another image, PostProcess, a destroyed image, the
     stats -- must see the finished frame.  The one-rank run of the same sequence is the reference."""
     import ctypes as C

@@ -280,7 +280,7 @@ def walk_host(lib, scene, tree, rays6, tmin, capacity):
 
 
 def instance_of(p):
-    """The kernel instance rl_runtime.inl KernelFor / AovKernelFor name for a RaylibAMDRenderPlan (as a dict): ("trace", (STACK, PRIMS, FULL, LDS, PLAIN)),
+    """The kernel instance rl_rt_frame.hip KernelFor / AovKernelFor name for a RaylibAMDRenderPlan (as a dict): ("trace", (STACK, PRIMS, FULL, LDS, PLAIN)),
     ("pool", (STACK, PRIMS, K, LSTACK, WIDE)) or ("aov", (STACK, PRIMS)).  Tree codes: 2 float boxes, 3 grid nodes, 4 the 8-wide tree."""
     if not p["pathTrace"]:
         return ("aov", (p["stack"], p["prims"]))

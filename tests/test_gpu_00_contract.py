@@ -230,7 +230,7 @@ def test_full_size_pool_schedule_bit_identical(full_size, monkeypatch):
 @pytest.mark.parametrize("shape", [(1920, 1080), (1, 1), (17, 1), (333, 127), (1283, 721)])
 def test_dump_image_data_from_a_device_resident_frame(shape, sessions, gpu_lib, monkeypatch):
     """Raylib_DumpImageData (reference raylib.h:90-93, render/image.cc:121-135: packed RGB float, row 0 on top) of a frame that Raylib_Render left on the
-    device: packed on the device and copied through pinned staging in chunks (csrc/rl_runtime.inl DeviceDumpRGB).  Must equal the RGB of the RGBA read-back
+    device: packed on the device and copied through pinned staging in chunks (csrc/rl_rt_scene.hip DeviceDumpRGB).  Must equal the RGB of the RGBA read-back
     and the plain path (RAYLIB_FAST_DUMP=0) bit for bit, for sizes that are not multiples of anything, twice in a row, and after Raylib_PostProcess."""
     w, h = shape
     ses = sessions["cornell_glass_sun"]
@@ -547,7 +547,7 @@ def test_small_scene_walks_agree(name, sessions, gpu_lib, monkeypatch):
     has_list = gpu_lib.RaylibAMD_SceneLeafListInfo(ses.scene, None) > 0
     assert has_list                                         # every fixture scene is that small
     # rayTMin 0 and a negative one too: hits behind the origin are then legal (t >= rayTMin, triangle.cc:37); the leaf list orders its leaves by
-    # entry distances that must not be negative, so the runtime walks the tree for such a frame (csrc/rl_runtime.inl)
+    # entry distances that must not be negative, so the runtime walks the tree for such a frame (csrc/rl_plan.cc)
     for mode, spp, tmin in ((0, 16, 1e-4), (1, 1, 1e-4), (4, 1, 1e-4), (0, 4, 0.0), (0, 4, -0.25)):
         base = ses.render(64, 64, spp, mode=mode, tmin=tmin)
         st0 = ses.stats().as_dict()

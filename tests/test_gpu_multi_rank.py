@@ -1,6 +1,6 @@
 """The frame split over N devices BEHIND the reference's entry point (north_star: "the image is tiled across the 8 GPUs
 ... behind raylib.h so the front-ends stay untouched").  RAYLIB_NUM_GPUS=N makes Raylib_Render deal the 8x8 cells to N ranks of
-this process, gather them on rank 0's device and scatter them into the frame (csrc/rl_runtime.inl).  A 1-GPU box covers the whole
+this process, gather them on rank 0's device and scatter them into the frame (csrc/rl_rt_render.hip).  A 1-GPU box covers the whole
 path by naming its one device N times in RAYLIB_GPU_MAP; the copy mechanisms between devices (RCCL grouped send / recv, peer
 copies) are exercised on rank 0's own cells with RAYLIB_GATHER_SELF=1.  Every frame must equal the one-rank frame bit for bit."""
 import os

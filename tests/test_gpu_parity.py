@@ -121,7 +121,7 @@ def test_triangles_too_small_or_too_large_for_the_short_barycentric_form(gpu_lib
 
 def test_cells_outside_the_scenes_silhouette_are_not_traced_and_nothing_changes(gpu_lib, workdir, oracle, monkeypatch):
     """With a pinhole camera and no sky panorama, cells whose pixels (jitter and margin included) lie outside the projected bounding box of the scene are
-    dropped from the megakernel's job list; k_resolve adds up the miss shader's constant for them (csrc/rl_runtime.inl CullCells).  The frame and the
+    dropped from the megakernel's job list; k_resolve adds up the miss shader's constant for them (csrc/rl_cull.cc CullCells).  The frame and the
     counters must be what they are with every cell traced (RAYLIB_CULL_CELLS=0) -- cameras far away (most cells dropped), close, inside the box's slab
     (nothing can be dropped), off-axis, with and without a sun -- and the oracle's on a window that straddles the silhouette."""
     from raylib_amd import binding

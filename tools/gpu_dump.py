@@ -1,5 +1,5 @@
 """Raylib_Render + Raylib_DumpImageData at 1080p: what a front-end sees of a frame (the reference's Raylib_Render returns with the pixels in host memory,
-render/renderer.cc:292-296).  The fast path (device packing + pinned, chunked staging: csrc/rl_runtime.inl DeviceDumpRGB) against the plain one."""
+render/renderer.cc:292-296).  The fast path (device packing + pinned, chunked staging: csrc/rl_rt_scene.hip DeviceDumpRGB) against the plain one."""
 import os, sys, time, ctypes as C
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "software-raytracing_amd"))

@@ -2,9 +2,11 @@
 """Per-function device-code comparison of two builds of one HIP translation unit (gfx950).
 
 usage: tools/isa_equivalence.py PARENT.o NEW.o
+       tools/isa_equivalence.py UNIT.o          (lists the kernels of one object: a host-runtime unit must have none)
 
-For every kernel of PARENT.o: its instructions (PC-relative address arithmetic after s_getpc_b64 masked), its kernel descriptor (64 bytes
-minus the code-entry offset) and its metadata (registers, LDS, scratch, kernarg size).  Kernels only NEW.o has are listed apart.  Then every
+For every kernel of PARENT.o: its instructions (PC-relative address arithmetic after s_getpc_b64 masked; the s_nop padding between a function's
+last instruction and the next symbol's alignment dropped -- it depends on which function the compiler places next, not on the function), its
+kernel descriptor (64 bytes minus the code-entry offset) and its metadata (registers, LDS, scratch, kernarg size).  Kernels only NEW.o has are listed apart.  Then every
 other function symbol of the code object -- the out-of-line device functions the kernels call through those masked addresses -- by its
 instructions, normalised the same way; one that only PARENT.o or only NEW.o has counts as a difference.  Exit status 1 when a kernel of
 PARENT.o differs or is missing, or a function differs.  Needs the ROCm LLVM tools (llvm-objcopy, clang-offload-bundler, llvm-objdump,
@@ -53,6 +55,9 @@ def functions(co):
             ins = ins.rsplit(",", 1)[0] + ", <pcrel>"
             pcrel -= 1
         cur.append(ins)
+    for body in out.values():   # alignment padding up to the next symbol ("...": zeros the disassembler elides)
+        while body and body[-1] in ("s_nop 0", "..."):
+            body.pop()
     return out
 
 
@@ -100,6 +105,14 @@ def metadata(co):
 
 
 def main():
+    if len(sys.argv) == 2:
+        with tempfile.TemporaryDirectory() as tmp:
+            try:
+                kernels = sorted(descriptors(code_object(sys.argv[1], tmp, "a")))
+            except subprocess.CalledProcessError:   # no .hip_fatbin section: the unit has no device code at all
+                kernels = []
+        print("\n".join(kernels + ["%d kernel(s) in %s" % (len(kernels), os.path.basename(sys.argv[1]))]))
+        return 0
     if len(sys.argv) != 3:
         sys.exit(__doc__)
     with tempfile.TemporaryDirectory() as tmp:

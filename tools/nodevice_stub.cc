@@ -1,6 +1,6 @@
-// Sanitizer harness only (tools/asan_host_check.sh): stands in for the unit of csrc/rl_render.hip (kernels and runtime) so that the HOST side of the
-// library (ABI, OBJ/MTL loader, BVH builder, codecs, registries) can be built with g++ -fsanitize=address,undefined
-// and run through tests/test_host_logic.py.  Never part of libraylib.so.
+// Sanitizer harness only (tools/asan_host_check.sh and the stand-alone *_host_check programs): stands in for the HIP units -- the kernels and the host runtime
+// that launches them (csrc/rl_rt_*.hip), every Device* entry of csrc/rl_host.h -- so that the HOST side of the library (ABI, OBJ/MTL loader, BVH builder,
+// scene flattening, planner, codecs, registries) can be built with g++ -fsanitize=address,undefined.  Never part of libraylib.so.
 #include "rl_host.h"
 namespace rl {
 bool DeviceAvailable() { return false; }
@@ -17,7 +17,6 @@ void DeviceFreePixels(void*) {}
 bool DeviceEvalMath(int, const float*, const float*, int, float*) { return false; }
 bool DeviceEvalHook(int, Scene*, const DCamera*, int, int, const float*, int, uint64_t, float*) { return false; }
 void DeviceReleaseScene(DeviceScene*) {}
-void DeviceShutdown() {}
 int DeviceNumRanks() { return 0; }
 bool DeviceDrain(RaylibAMDStats*) { return false; }
 int32_t DeviceLastTracePlain() { return 0; }
