@@ -73,6 +73,9 @@ typedef struct RaylibAMDStats {
 	uint32_t treeWidth;       /* children per node: 2, 4 (64-byte grid nodes), 8 (80-byte grid nodes, octant-ordered children; scenes whose rays are expected to take
 	                             many steps, RAYLIB_BVH8=0|1 overrides) or 0 = no tree (the leaf list of a scene of few leaves) */
 	uint32_t nodeBytes;       /* bytes of one record counted in nodesVisited: 64, or 80 for the 8-wide tree */
+	/* ---- the leaf-list kernel's lazy-reflectance instance (RaylibAMD_LastTraceLazy): 0 for every other kernel ---- */
+	uint64_t litPaths;        /* traced paths that ended with light in them (or met a vertex whose reflectance may not be skipped): the ones whose reflectances were evaluated */
+	uint64_t litFoldedInPlace;/* ... of them, those folded inside the megakernel instead of by k_fold_lit (the lit list was full, or the path had more vertices than an entry holds) */
 } RaylibAMDStats;
 
 /* Seed of the per-(pixel, sample) streams of include/raylib_amd_rng.h. */
@@ -260,6 +263,10 @@ RAYLIB_API int32_t RaylibAMD_CullCells(CameraHandle camera, const float* bounds,
  * short form (csrc/rl_glibc_math.h acosf_t / tanf_t, RL_EXACT_DIV bit 4) against the same functions with IEEE divisions, every bit pattern.
  * outMismatches: inputs whose results differ (a NaN may differ in payload); outFirstBits: the smallest such bit pattern.  Returns 1 when the sweep ran. */
 RAYLIB_API int32_t RaylibAMD_VerifyExactMath(int32_t which, uint64_t* outMismatches, uint64_t* outFirstBits);
+/* The lazy-reflectance instance's per-vertex guard, swept on the device over n scattering events made from edge and random inputs (csrc/rl_render_lazy.hip
+ * k_verify_lazy_refl): outUnsafe = events the guard passed although a component of the reflectance or the scattering pdf is not finite (must be 0),
+ * outGuardFailed = events it refused.  Returns 1 when the sweep ran. */
+RAYLIB_API int32_t RaylibAMD_VerifyLazyRefl(uint32_t n, uint64_t seed, uint64_t* outEvents, uint64_t* outUnsafe, uint64_t* outGuardFailed);
 
 /* ---- host-logic introspection (no GPU needed) ---------------------------------- */
 /* Flattened scene as the kernels see it.  Triangle record = 26 words, material record =
@@ -305,6 +312,12 @@ RAYLIB_API int32_t RaylibAMD_SceneLeafListInfo(SceneHandle scene, uint32_t* outM
 RAYLIB_API int32_t RaylibAMD_ScenePlain(SceneHandle scene);
 /* 1 when the megakernel of the last path-traced render on this process was the leaf-list kernel's plain instance, else 0. */
 RAYLIB_API int32_t RaylibAMD_LastTracePlain(void);
+/* 1 when the finalized scene may be rendered by the plain instance's lazy-reflectance form, which evaluates a vertex's reflectance only on paths that end with
+ * light in them (the same bits; csrc/rl_dev_shade.h): RaylibAMD_ScenePlain, triangles only, every material a triangle uses microfacet (emission finite,
+ * roughness in [2^-10, 1], |albedo| and |metallic| <= 16) or a mirror (|albedo| <= 16).  A render takes it when the plain instance's conditions hold and maxPathLength <= 4096; RAYLIB_LAZY_REFL=0 keeps the eager instance.  No device needed. */
+RAYLIB_API int32_t RaylibAMD_SceneLazyRefl(SceneHandle scene);
+/* 1 when the megakernel of the last path-traced render on this process was that lazy-reflectance instance (then RaylibAMD_LastTracePlain is 1 too), else 0. */
+RAYLIB_API int32_t RaylibAMD_LastTraceLazy(void);
 /* What a one-rank Raylib_Render of `settings` would launch under the current environment (csrc/rl_plan.cc): the kernel instance, its tree and the job
  * layout of its first launch over every cell of the frame, for a device of numCUs CUs on which the kernel fits workgroupsPerCU workgroups.  No device needed.
  * Returns 1, -1 when the scene's BVH is too deep to render (the plan is then not filled in further), 0 for a bad argument or a scene not finalized. */
@@ -321,6 +334,8 @@ typedef struct RaylibAMDRenderPlan {
 	int32_t eagerTree;        /* the wide tree the scene's upload puts on the device (tree code, 0: none) */
 	uint32_t batch, sampleCount, blocks, stackStride, jobChunk, heads, jobsPerHead, guideShift;
 	uint64_t jobs;
+	int32_t lazy;             /* the plain instance's lazy-reflectance form (k_trace_lazy + k_fold_lit); 0 for a batch of views, whose twin stays eager */
+	int32_t reserved;
 } RaylibAMDRenderPlan;
 RAYLIB_API int32_t RaylibAMD_PlanRender(SceneHandle scene, const RendererSettings* settings, int32_t hasSky, int32_t numCUs, int32_t workgroupsPerCU, RaylibAMDRenderPlan* out);
 /* ---- several views of one scene in one megakernel launch (INTEGRATION.md "Several views") ---- */

@@ -726,6 +726,16 @@ int32_t RaylibAMD_VerifyExactMath(int32_t which, uint64_t* outMismatches, uint64
 	return DeviceVerifyExactMath(which, outMismatches, outFirstBits) ? 1 : 0;
 }
 
+int32_t RaylibAMD_VerifyLazyRefl(uint32_t n, uint64_t seed, uint64_t* outEvents, uint64_t* outUnsafe, uint64_t* outGuardFailed)
+{
+	uint64_t out[3] = { 0, 0, 0 };
+	if (!DeviceVerifyLazyRefl(n, seed, out)) return 0;
+	if (outEvents) *outEvents = out[0];
+	if (outUnsafe) *outUnsafe = out[1];
+	if (outGuardFailed) *outGuardFailed = out[2];
+	return 1;
+}
+
 int32_t RaylibAMD_ClosestHit(SceneHandle sh, const float* rays, int32_t n, float tMin, void* outHits)
 {
 	Scene* s = (Scene*)sh;
@@ -919,6 +929,12 @@ int32_t RaylibAMD_ScenePlain(SceneHandle sh)
 	return (s && s->finalized && ScenePlain(*s)) ? 1 : 0;
 }
 int32_t RaylibAMD_LastTracePlain(void) { return DeviceLastTracePlain(); }
+int32_t RaylibAMD_SceneLazyRefl(SceneHandle sh)
+{
+	Scene* s = (Scene*)sh;
+	return (s && s->finalized && SceneLazyRefl(*s)) ? 1 : 0;
+}
+int32_t RaylibAMD_LastTraceLazy(void) { return DeviceLastTraceLazy(); }
 int32_t RaylibAMD_PlanRender(SceneHandle sh, const RendererSettings* settings, int32_t hasSky, int32_t numCUs, int32_t workgroupsPerCU, RaylibAMDRenderPlan* out)
 {
 	Scene* s = (Scene*)sh;
@@ -927,7 +943,7 @@ int32_t RaylibAMD_PlanRender(SceneHandle sh, const RendererSettings* settings, i
 	const RenderKnobs knobs = ReadRenderKnobs();
 	const TracePlan t = PlanTrace(*s, *settings, hasSky != 0, knobs);
 	if (!t.ok) return -1;
-	out->pathTrace = t.pathTrace; out->stack = t.stack; out->prims = t.prims; out->poolK = t.poolK; out->tree = t.tree; out->lstack = t.lstack; out->lds = t.lds; out->plain = t.plain;
+	out->pathTrace = t.pathTrace; out->stack = t.stack; out->prims = t.prims; out->poolK = t.poolK; out->tree = t.tree; out->lstack = t.lstack; out->lds = t.lds; out->plain = t.plain; out->lazy = t.lazy ? 1 : 0;
 	out->pathsPerWave = t.pathsPerWave; out->treeWidth = t.treeWidth; out->nodeBytes = t.nodeBytes;
 	out->keepNodes4 = t.keepNodes4; out->keepNodes4f = t.keepNodes4f; out->eagerTree = t.eagerTree;
 	const uint32_t cells = ((settings->viewportWidth + 7) / 8) * ((settings->viewportHeight + 7) / 8);
@@ -946,7 +962,7 @@ int32_t RaylibAMD_PlanViews(SceneHandle sh, const RendererSettings* settings, co
 	const RenderKnobs knobs = ReadRenderKnobs();
 	const TracePlan t = PlanTrace(*s, *settings, hasSky != 0, knobs);
 	if (!t.ok) return -1;
-	out->pathTrace = t.pathTrace; out->stack = t.stack; out->prims = t.prims; out->poolK = t.poolK; out->tree = t.tree; out->lstack = t.lstack; out->lds = t.lds; out->plain = t.plain;
+	out->pathTrace = t.pathTrace; out->stack = t.stack; out->prims = t.prims; out->poolK = t.poolK; out->tree = t.tree; out->lstack = t.lstack; out->lds = t.lds; out->plain = t.plain; out->lazy = 0;   // (the views twin of a lazy plan is the plain instance's)
 	out->pathsPerWave = t.pathsPerWave; out->treeWidth = t.treeWidth; out->nodeBytes = t.nodeBytes;
 	out->keepNodes4 = t.keepNodes4; out->keepNodes4f = t.keepNodes4f; out->eagerTree = t.eagerTree;
 	std::vector<DCamera> cams((size_t)count);

@@ -40,6 +40,7 @@ namespace rl {
 #ifndef RL_FOLD_PREFETCH
 #define RL_FOLD_PREFETCH 5
 #endif
+#define RL_LIT_STRIDE (2 * RL_FOLD_PREFETCH + 2)   /* float4 per entry of the lit list (rl_device.h DLitList) */
 #ifndef RL_FOLD_PREFETCH_POOL
 #define RL_FOLD_PREFETCH_POOL RL_FOLD_PREFETCH
 #endif
@@ -86,6 +87,9 @@ __device__ __forceinline__ bool isZero(V3 a) { return a.x == 0.0f && a.y == 0.0f
 #define RL_TIMELINE_SLOTS 0
 #define RL_TIMELINE(which)
 #endif
+// behind everything else in the counter block: the lazy instance's lit paths (list entries + folds in place) and, of them, the folds in place
+#define RL_CNT_LIT (CNT_COUNT + 24 + RL_TIMELINE_SLOTS)
+#define RL_CNT_BLOCK (RL_CNT_LIT + 2)   /* counters in the block */
 #ifdef RL_DIAG_STAMPS
 #define RL_DIAG_BIND(c) { (c).diag = nullptr; (c).tLast = 0; (c).tAcc[0] = (c).tAcc[1] = (c).tAcc[2] = (c).tAcc[3] = 0; }
 #else

@@ -275,6 +275,14 @@ struct KTraceViewsArgs { KTraceArgs A; DViews V; };
 #define RL_VIEWS() const DViews& VW = Vk; (void)VW
 #endif
 
+// The lazy instance's arguments: KTraceArgs and the lit list behind it
+struct KTraceLazyArgs { KTraceArgs A; DLitList LL; };
+#if RL_KARG_RELOAD
+#define RL_LIT_ARGS() const DLitList LL = KArg<DLitList>((uint32_t)offsetof(KTraceLazyArgs, LL)); (void)LL
+#else
+#define RL_LIT_ARGS() const DLitList& LL = LLk; (void)LL
+#endif
+
 // One slot's samples of this batch added to `a` in sample order -- the megakernel's from the sample buffer, or, for a cell outside the scene's silhouette,
 // the miss shader's value every one of them comes to -- and each sample's RGB handed to `each` (k_resolve: nothing; k_progressive_resolve: the
 // luminance moments of its stopping rule).

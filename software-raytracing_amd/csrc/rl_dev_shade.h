@@ -293,6 +293,33 @@ __device__ __forceinline__ float GeometryBeckmann(V3 N, V3 H, V3 V, float roughn
 	return 1.0f;
 }
 
+// ---- the reflectance of one microfacet scattering event (reference render/material.cc:306-333) ----
+// Its arithmetic is written once, here: from baseColor, roughness, metallic, N, Wo, Wh, Wi and NdotWi in scope, RL_REFLECTANCE_TERMS declares the terms in the
+// reference's statement order and RL_REFLECTANCE_VALUE is the reflectance.  ReflFromRecord is that arithmetic as a function of what a vertex record of k_trace's lazy
+// instance holds (FoldLazyVertex).  Scatter expands the same two macros in place and not through the function: the compiler simplifies an inlined callee on its own
+// first, where kD and diffuse sink below DivSpecular's branch, and every kernel that scatters eagerly would come out as a different instruction sequence
+// (tools/isa_equivalence.py: 19 kernels of the main unit alone).  The values are the same either way: no operation is reassociated or contracted.
+#define RL_REFLECTANCE_TERMS(PLAIN_) \
+	V3 F0 = v3s(0.04f); \
+	F0 = mix(F0, baseColor, metallic); \
+	V3 F = F0 + (1.0f - F0) * PowSel<PLAIN_ && RL_PLAIN_INLINE_POW>(1.0f - absDot(Wh, Wo), 5.0f); \
+	float ggx2 = GeometryBeckmann<PLAIN_ && RL_PLAIN_INLINE_TAN>(N, Wh, Wo, roughness); \
+	float ggx1 = GeometryBeckmann<PLAIN_ && RL_PLAIN_INLINE_TAN>(N, Wh, Wi, roughness); \
+	float G = rtm::rcp1_(1.0f + ggx1 * ggx2); \
+	float NDF = DistributionBeckmann(N, Wh, roughness); \
+	\
+	V3 kS = F; \
+	V3 kD = 1.0f - kS; \
+	V3 diffuse = baseColor * (1.0f - metallic); \
+	V3 specular = DivSpecular(F * G * NDF, 4.0f * NdotWi * absDot(N, Wo) + 0.001f)
+#define RL_REFLECTANCE_VALUE ((kD * diffuse + kS * specular) * NdotWi)
+template <bool PLAIN = false>
+__device__ __forceinline__ V3 ReflFromRecord(V3 baseColor, float roughness, float metallic, V3 N, V3 Wo, V3 Wh, V3 Wi, float NdotWi)
+{
+	RL_REFLECTANCE_TERMS(PLAIN);
+	return RL_REFLECTANCE_VALUE;
+}
+
 // material texture lookups (reference render/material.cc:297-303,378-395,406-415)
 __device__ __forceinline__ V3 GetAlbedo(const DSceneView& S, const Mat& m, float U, float V, Counters& c)
 {
@@ -431,22 +458,11 @@ __device__ __forceinline__ bool Scatter(const DSceneView& S, const Mat& m, V3 in
 			V3 Wi = reflect(-Wo, Wh);
 			float NdotWi = absDot(N, Wi);
 
-			V3 F0 = v3s(0.04f);
-			F0 = mix(F0, baseColor, metallic);
-			V3 F = F0 + (1.0f - F0) * PowSel<PLAIN && RL_PLAIN_INLINE_POW>(1.0f - absDot(Wh, Wo), 5.0f);
-			float ggx2 = GeometryBeckmann<PLAIN && RL_PLAIN_INLINE_TAN>(N, Wh, Wo, roughness);
-			float ggx1 = GeometryBeckmann<PLAIN && RL_PLAIN_INLINE_TAN>(N, Wh, Wi, roughness);
-			float G = rtm::rcp1_(1.0f + ggx1 * ggx2);
-			float NDF = DistributionBeckmann(N, Wh, roughness);
-
-			V3 kS = F;
-			V3 kD = 1.0f - kS;
-			V3 diffuse = baseColor * (1.0f - metallic);
-			V3 specular = DivSpecular(F * G * NDF, 4.0f * NdotWi * absDot(N, Wo) + 0.001f);
+			RL_REFLECTANCE_TERMS(PLAIN);
 
 			V3 WiW = LocalToWorld(s, Wi);
 			outD = WiW;
-			refl = (kD * diffuse + kS * specular) * NdotWi;
+			refl = RL_REFLECTANCE_VALUE;
 
 			// ScatteringPdf(hit, -inD, WiW), material.cc:352-376
 			V3 wo = WorldToLocal(s, -inD);
@@ -460,6 +476,93 @@ __device__ __forceinline__ bool Scatter(const DSceneView& S, const Mat& m, V3 in
 			return true;
 		}
 	}
+}
+
+// ---- k_trace's lazy-reflectance instance (rl_k_trace.inl RL_LAZY_REFL; rl_plan.cc TracePlan::lazy) ----
+// A sample is the fold L_k = (0 + refl_k * L_{k+1} * sp_k / pdf_k) + E_k back to the camera.  On a path whose terminal L and every E are +0 each refl_k is
+// multiplied by an exact zero: the sample is (+0, +0, +0) whatever the reflectances are -- as long as they and sp are finite (below).  The instance therefore
+// scatters without the reflectance (ScatterLazy: everything the continuation needs), records what the reflectance is a function of, and evaluates it
+// (FoldLazyVertex) for the paths with light in them alone.  Plain scenes whose triangles carry microfacet and mirror materials only (SceneLazyRefl): no
+// texture lookups, N = (0, 0, 1).  A mirror's reflectance is its albedo, a constant there is nothing to skip of; its record holds the material alone.
+// Scatter's mirror arm, or its microfacet arm without the reflectance: the same draws, the same statements, the same bits in Wo, Wh, outD, pdf and sp.
+__device__ __forceinline__ void ScatterLazy(const DSceneView& S, const Mat& m, V3 inD, const Surf& s, Rng& g, Counters& c, V3& Wo, V3& Wh, V3& outD, float& pdf, float& sp)
+{
+	if (m.type == MAT_MIRROR) {   // material.h:149-162
+		outD = reflect(inD, s.n);
+		pdf = 1.0f;
+		sp = 1.0f;
+		Wo = v3(0.0f, 0.0f, 1.0f); Wh = Wo;   // (LazyVertexSafe passes: the albedo is finite, SceneLazyRefl)
+		return;
+	}
+	RL_WLSTEP(c, 18, 19);
+	float roughness = GetRoughness(S, m, s.U, s.V, c);
+	V3 N = GetMicrosurfaceNormal(S, m, s, c);
+	Wo = WorldToLocal(s, -inD);
+	float u0 = Next(g);
+	float u1 = Next(g);
+	bool bFlip = Wo.z < 0.0f;
+	Wh = BeckmannSample(bFlip ? -Wo : Wo, roughness, roughness, u0, u1, c);
+	if (bFlip) Wh = -Wh;
+	V3 Wi = reflect(-Wo, Wh);
+	V3 WiW = LocalToWorld(s, Wi);
+	outD = WiW;
+
+	// ScatteringPdf(hit, -inD, WiW), material.cc:352-376
+	V3 wo = WorldToLocal(s, -inD);
+	V3 wi = WorldToLocal(s, WiW);
+	V3 wh = normalize(wo + wi);
+	if (wh.z < 0.0f) wh.z = -wh.z;
+	float D = DistributionBeckmann(N, wh, roughness);
+	sp = D * absDot(wh, N);
+	pdf = sp / (4.0f * dot(Wo, Wh));
+}
+// May the vertex's reflectance go unevaluated on an unlit path?  refl * 0 * sp / pdf is a zero, and (0 + that) + 0 is +0, only if every component of refl
+// and sp are finite (pdf > 0 is the caller's condition for a recorded vertex; a NaN or an infinity in refl makes the reference's sample NaN).  A vertex that
+// fails only marks its path lit: the exact evaluation then reproduces whatever the reference does.  All three compares fail on NaN.
+// Why passing, with roughness r in [2^-10, 1] and |albedo|, |metallic| <= 16 (SceneLazyRefl), implies a finite ReflFromRecord(Wo, Wh):
+//   Wo: camera directions are normalised, a reflection about a unit Wh and the orthonormal frames keep a length to a few ulps, so over at most RL_LAZY_MAX_PATH
+//       vertices |Wo|, |Wi| are within 2^-8 of 1.  Wh = +-normalize(-sx, -sy, 1): an infinite, NaN or overflowing slope leaves Wh.z = 0 or NaN and fails the first
+//       compare; otherwise Wh is a unit vector to a few ulps, all components finite.
+//   F:  |F0| = |0.04 (1 - metallic) + metallic albedo| < 2^9; 1 - |Wh.Wo| lies in [-2^-7, 1] and pow_(x, 5) is defined there, |.| <= 1: |F| < 2^11.
+//   G:  GeometryBeckmann is 0, 1 or num / denom with a = rcp1_(r tan(acos(V.z))) < 1.6 (a NaN a compares false and yields 1).  acos_ is 0 or at least 2^-12, and the
+//       floats next to pi / 2 and pi keep |tan| within [2^-24, 2^25], so r tan is +0 (a = +inf: 1 is returned) or at least 2^-34 in magnitude: a is finite or +inf,
+//       never -inf or the quotient of a -0 (what roughness 0 would give: num = -inf + inf), and aa <= 2^68 does not overflow.  denom = 1 + 2.276 a + 2.577 aa has a
+//       negative discriminant: >= 0.49 for every a, so the quotient lies in [-2.5, 1.1].  It is negative only for a < 0, that is V.z <= 0 together with V.Wh > 0
+//       (QuotientNotPositive returns 0 first otherwise) -- and then, unless V.z is a zero or rounds to pi / 2's tangent (a = -1 / (r 2.3e7): a quotient within 2^-12 of 0), V.Wh and
+//       V.z differ in sign and 0 was returned.  V = Wo: Wo.Wh >= 2^-10, the third compare.  V = Wi: Wi.Wh = Wo.Wh (2 |Wh|^2 - 1) >= 2^-11 as computed.  So both
+//       factors lie in [-2^-12, 1.1], 1 + ggx1 ggx2 in [0.99, 2.3], and G = rcp1_ of it in (0.4, 1.02).  (Without the third compare a product of exactly -1 and with it
+//       G = inf could not be excluded.)
+//   NDF: cosH = |Wh.z| in [2^-10, 1 + 2^-20]; rr in [2^-20, 1]; exp_x in [-2^-19, 2^30], exp_(-exp_x) in [0, 1.01]; denom = pi rr cosH^4 >= 2^-59 is a
+//       normal number: 0 <= NDF < 2^60.
+//   specular = F G NDF / b with b = 4 |Wi.z| |Wo.z| + 0.001 in [0.001, 4.1]: below 2^11 2^0.1 2^60 2^10 < 2^82; kS specular < 2^93; kD diffuse = (1 - F) albedo
+//       (1 - metallic) < 2^21; the sum times |Wi.z| <= 1.01 is finite.
+__device__ __forceinline__ bool LazyVertexSafe(V3 Wo, V3 Wh, float sp)
+{
+	return fabsf(Wh.z) >= 0x1p-10f && fabsf(sp) < INFINITY && dot(Wo, Wh) >= 0x1p-10f;
+}
+__device__ __forceinline__ bool AnyBitSet(V3 a) { return (__float_as_uint(a.x) | __float_as_uint(a.y) | __float_as_uint(a.z)) != 0u; }
+// One step of the fold at a recorded vertex (r0 = Wo, sp; r1 = Wh, material index; m = that material): the reflectance, the pdf as Scatter computes it from the
+// same values, the emission (plain scenes: the material's), and the fold's statement exactly as k_trace writes it.
+__device__ __forceinline__ V3 FoldLazyVertex(const Mat& m, float4 r0, float4 r1, V3 L)
+{
+	if (m.type == MAT_MIRROR) {   // refl = albedo, sp = pdf = 1, nothing emitted
+		V3 radiance = v3s(0.0f);
+		radiance = radiance + m.albedo * L * 1.0f / 1.0f;
+		radiance = radiance + v3s(0.0f);
+		return radiance;
+	}
+	const V3 Wo = v3(r0.x, r0.y, r0.z), Wh = v3(r1.x, r1.y, r1.z);
+	const float sp = r0.w;
+	const V3 N = v3(0.0f, 0.0f, 1.0f);
+	const V3 Wi = reflect(-Wo, Wh);
+	const float NdotWi = absDot(N, Wi);
+	const V3 refl = ReflFromRecord<true>(m.albedo, m.roughness, m.metallic, N, Wo, Wh, Wi, NdotWi);
+	const float pdf = sp / (4.0f * dot(Wo, Wh));
+	const V3 E = m.emissive;
+	V3 radiance = v3s(0.0f);
+	radiance = radiance + refl * L * sp / pdf;
+	radiance = radiance + E;
+	return radiance;
 }
 
 // Miss shader: sky panorama + sun (reference render/renderer.cc:155-199)

@@ -270,4 +270,22 @@ struct DViews {
 	uint32_t magicCellsPerView;  // floor(2^32 / cellsPerView): batch cell -> view by multiply-high (DecodeView)
 };
 
+// k_trace's lazy-reflectance instance (rl_k_trace.inl RL_LAZY_REFL; the planner's conditions: rl_plan.cc, rl_scene.cc SceneLazyRefl) skips a vertex's reflectance
+// and hands the paths that end with light in them to k_fold_lit through this list: entries of RL_LIT_STRIDE float4 (terminal L | outIndex; record count; then up
+// to RL_FOLD_PREFETCH vertex records of two float4, camera first), reserved by the waves in chunks of RL_LIT_CHUNK entries.
+//   ctl[0] chunks handed out so far (may pass numChunks: a wave that draws one beyond folds in place); ctl[RL_LIT_CTL + c] entries filled in chunk c
+// The interval of the materials the instance takes (closed; every scene of the repository lies inside): the bound argument is rl_dev_shade.h LazyVertexSafe's.
+#define RL_LIT_CHUNK 64u
+#define RL_LIT_CTL 16u
+#define RL_LAZY_ROUGHNESS_MIN 0x1p-10f
+#define RL_LAZY_ROUGHNESS_MAX 1.0f          /* what the loader and RaylibAMD_CreateMaterial saturate a microfacet roughness to */
+#define RL_LAZY_COLOR_MAX 16.0f      /* |albedo|, |metallic|, either sign (a mirror's albedo is not saturated) */
+#define RL_LAZY_MAX_PATH 4096        /* maxPathLength: a direction's length stays within 2^-8 of 1 over that many reflections */
+struct DLitList {
+	float* entries;              // float4 units
+	uint32_t* ctl;
+	uint32_t numChunks;          // 0: no list, every lit path folds in place
+	uint32_t pad;
+};
+
 } // namespace rl

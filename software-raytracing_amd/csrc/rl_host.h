@@ -192,6 +192,8 @@ struct Scene {
 // true when no material has a texture slot (>= 0) and no leaf of the leaf list carries the cut-out bit: the leaf-list kernel's
 // plain instance may render the scene (rl_plan.cc adds the per-render conditions)
 bool ScenePlain(const Scene& sc);
+// ... and k_trace's lazy-reflectance instance: plain, every material microfacet with parameters inside the instance's intervals (rl_scene.cc)
+bool SceneLazyRefl(const Scene& sc);
 
 // The scene as the devices hold it (rl_device.h), in leaf order (rl_scene.cc FlattenScene): triangle records -- rden is 1 / denom for the short barycentric
 // divisions, NaN where denom is 0 or NaN or outside [2^-62, 2^125], and the last case clears fastBary for the whole scene (RAYLIB_FAST_BARY=0 clears it whatever
@@ -249,6 +251,7 @@ bool DeviceRender(Scene& scene, const RenderRequest& req, RaylibAMDStats& stats)
 // RaylibAMD_RenderViews: `count` views (cameras[v]) of req.settings / req.seed into outDevice (view-major, count * W * H float4; nullptr: the library's
 // own buffer) and, when imagePixels is given, each view's frame copied into imagePixels[v] (W * H float4 on rank 0's device).  Synchronous.
 bool DeviceRenderViews(Scene& scene, const RenderRequest& req, const DCamera* cameras, uint32_t count, void* outDevice, void* const* imagePixels, RaylibAMDStats& stats);
+int32_t DeviceLastTraceLazy();    // 1: ... and of that, the lazy-reflectance instance (k_trace_lazy + k_fold_lit)
 int32_t DeviceLastTracePlain();   // 1: the last path-traced render's megakernel was the leaf-list kernel's plain instance (rl_plan.cc)
 bool DeviceDrain(RaylibAMDStats* outLastStats);   // waits for multi-rank frames in flight; true + stats when that completed the last render call's numbers
 bool DeviceClosestHit(Scene& scene, const float* rays, int32_t n, float tMin, void* outHits);
@@ -275,6 +278,7 @@ struct CullResult { std::vector<uint32_t> active; std::vector<unsigned char> emp
 bool CullCells(const CullScene& DS, const DCamera& cam, int32_t maxPathLength, float rayTMin, uint32_t W, uint32_t H,
                uint32_t cellsX, uint32_t cellFirst, uint32_t stride, uint32_t numLocalCells, CullResult& out);
 bool DeviceEvalMath(int fn, const float* x, const float* y, int n, float* out);
+bool DeviceVerifyLazyRefl(uint32_t n, uint64_t seed, uint64_t out[3]);   // k_verify_lazy_refl: events, guard passed with a non-finite refl or sp, guard failed
 bool DeviceVerifyExactMath(int which, uint64_t* outMismatches, uint64_t* outFirst);   // 0: rtm::rcp1_ vs 1.0f / x, 1: rtm::sqrt_ vs sqrtf, 2: rtm::div_by_ vs a / b, 3: Barycentric short vs divisions, 4: acosf_t / tanf_t short vs IEEE divisions; all 2^32 inputs
 bool DeviceEvalHook(int kind, Scene* sc, const DCamera* cam, int a, int b, const float* in, int n, uint64_t seed, float* out);
 void DeviceReleaseScene(DeviceScene* dev);

@@ -3,17 +3,29 @@
 // trailing argument; everything under RL_VIEWS_TWIN is the twin's alone, so that the
 // one-view kernel is the token sequence it always was (a template flag would add an inlining level, which reorders the one-view kernel's code:
 // tools/isa_equivalence.py).
+// RL_LAZY_REFL 1 (rl_render_lazy.hip): k_trace_lazy, the leaf-list kernel's PLAIN instance with the reflectance evaluated on lit paths only
+// (rl_dev_shade.h "lazy-reflectance instance"); it takes the lit list (DLitList) as one more trailing argument.  Everything under RL_LAZY_REFL is that instance's alone.
+#ifndef RL_LAZY_REFL
+#define RL_LAZY_REFL 0
+#endif
 
 template <int STACK, bool PRIMS, bool FULL, int LDS, bool PLAIN>
 __global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 2))
 #if RL_VIEWS_TWIN
 k_trace_views(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB* __restrict__ samplesK,
               float* __restrict__ pathStackK, unsigned long long* __restrict__ countersK, unsigned int* __restrict__ jobCounterK, const DViews Vk)
+#elif RL_LAZY_REFL
+k_trace_lazy(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB* __restrict__ samplesK,
+             float* __restrict__ pathStackK, unsigned long long* __restrict__ countersK, unsigned int* __restrict__ jobCounterK, const DLitList LLk)
 #else
 k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB* __restrict__ samplesK,
         float* __restrict__ pathStackK, unsigned long long* __restrict__ countersK, unsigned int* __restrict__ jobCounterK)
 #endif
 {
+#if RL_LAZY_REFL
+	static_assert(LDS == 2 && PLAIN && !PRIMS, "the lazy instance is the leaf-list kernel's PLAIN instance");
+	(void)LLk;
+#endif
 	(void)Pk; (void)Sk; (void)Rk; (void)samplesK; (void)pathStackK; (void)countersK; (void)jobCounterK;
 	RL_TEX_PROLOGUE(Sk);
 	RL_MATH_PROLOGUE();
@@ -62,6 +74,12 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 	uint32_t outIndex = 0;
 	bool active = false;
 	bool exhausted = false;
+#if RL_LAZY_REFL
+	bool lit = false;                          // the path has met light, or a vertex whose reflectance may not be skipped (LazyVertexSafe)
+	uint32_t litChunk = ~0u, litFill = RL_LIT_CHUNK;   // wave-uniform: the wave's chunk of the lit list and the entries filled in it (none yet: "full")
+	bool litFull = false;                      // wave-uniform: the list has no chunk left
+	uint32_t nLit = 0, nInPlace = 0;
+#endif
 
 	// Wave-local job range: the wave takes P.jobChunk (64..1024) consecutive jobs from the global counter
 	// with ONE atomic and deals them to its lanes itself.  (A returning atomic on one address
@@ -232,6 +250,9 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 					rayTime = 0.0f;   // leaf-list scenes are triangle scenes: nothing moves, the ray's time is not read
 					depth = 0;
 					active = true;
+#if RL_LAZY_REFL
+					lit = false;
+#endif
 				} else if (globalDone && chunkNext >= chunkEnd) exhausted = true;
 			}
 			qCount -= min(n, qCount);
@@ -317,6 +338,13 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 		}
 		RL_LANESTAMP(0, doTrace);
 		RL_STAMP(1);
+#if RL_LAZY_REFL
+		// what a lane whose path ended lit in this trip leaves for the wave-level part behind the block: its terminal L, and a last vertex that is recorded
+		// (it failed LazyVertexSafe) in registers, on top of the depth records of the path stack
+		bool finLit = false, finTop = false;
+		float4 finRec0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), finRec1 = finRec0;
+		V3 finL = v3s(0.0f);
+#endif
 		if (active) {
 			bool done = false, store = false;
 			float4 rec0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rec1 = rec0;
@@ -333,6 +361,34 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 				const int mi = BuildSurface<PRIMS, LDS>(S, o, d, h, s, true, c, sm);
 				const Mat m = LDS ? MatFrom<PLAIN>(sm + LdsAt<LDS>::MATS + mi * RL_LDS_MSTRIDE(PLAIN)) : LoadMat(S, mi);
 				RL_SUBSTAMP(0);
+#if RL_LAZY_REFL
+				V3 Wo = v3s(0.0f), Wh = v3s(0.0f), outD = v3s(0.0f);
+				float pdf = 0.0f, sp = 0.0f;
+				ScatterLazy(S, m, d, s, g, c, Wo, Wh, outD, pdf, sp);
+				RL_SUBSTAMP(1);
+				const V3 E = Emitted(S, m, s, c);
+				if (AnyBitSet(E)) lit = true;
+				if (pdf > 0.0f) {
+					const bool safe = LazyVertexSafe(Wo, Wh, sp);
+					if (!safe) lit = true;
+					const bool last = depth + 1 >= P.maxPathLength;
+					if (last && safe) {
+						// the path's last vertex (the eager instance's comment below): its finite reflectance meets L = 0, the step comes to (0 + +-0) + E
+						L = v3s(0.0f) + E;
+						done = true;
+					} else {
+						// the vertex record (Wo, sp | Wh, material): what ReflFromRecord, the pdf and the emission are functions of
+						store = true;
+						rec0 = make_float4(Wo.x, Wo.y, Wo.z, sp);
+						rec1 = make_float4(Wh.x, Wh.y, Wh.z, __int_as_float(mi));
+						if (last) done = true;   // (L = 0: the record is folded like every other, from the registers)
+						else { o = s.p; d = outD; }
+					}
+				} else {
+					L = v3s(0.0f) + E;
+					done = true;
+				}
+#else
 				V3 refl = v3s(0.0f), outD = v3s(0.0f);
 				float pdf = 0.0f, sp = 0.0f;
 				const bool scattered = Scatter<PLAIN>(S, m, d, s, g, c, refl, outD, pdf, sp);
@@ -360,6 +416,7 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 					L = v3s(0.0f) + E;                        // radiance(0) += Emitted, renderer.cc:137,151
 					done = true;
 				}
+#endif
 				RL_SUBSTAMP(2);
 				RL_LANESTAMP(1, true);
 			} else {
@@ -370,6 +427,80 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 				RL_LANESTAMP(2, true);
 			}
 			RL_STAMP(2);
+#if RL_LAZY_REFL
+			if (done) {
+				RL_ARGS();
+				if (AnyBitSet(L)) lit = true;
+				// an unlit path: every E and the terminal L are +0 and every vertex passed LazyVertexSafe, so every step of the fold is (0 + +-0) + 0 = +0
+				if (!lit) samples[outIndex] = make_sample(0.0f, 0.0f, 0.0f);
+				else { finLit = true; finTop = store; finRec0 = rec0; finRec1 = rec1; finL = L; }
+				active = false;
+			} else if (store) {
+				RL_ARGS();
+				float4* st = (float4*)pathStack + ((size_t)depth * P.stackStride + gtid) * 2u;
+				st[0] = rec0; st[1] = rec1;
+				depth++;
+			}
+		}
+		if (Ballot(finLit) != 0ull) {
+			// ---- the lit paths that ended in this trip, wave-wide: an entry of the lit list each (k_fold_lit folds them, in full waves), reserved in the wave's chunk
+			// and, when that is full, in one more (one global atomic per RL_LIT_CHUNK entries; a returning atomic per trip on one address would be the rate at
+			// which the job counter once bound this kernel).  A path with more records than an entry holds, or without an entry because the list is used up, folds
+			// in place: slow, rare, the same statements on the same values.
+			RL_ARGS();
+			RL_LIT_ARGS();
+			const int nrec = depth + (finTop ? 1 : 0);
+			const bool wantEntry = finLit && nrec <= RL_FOLD_PREFETCH;
+			const unsigned long long em = Ballot(wantEntry);
+			const uint32_t n = (uint32_t)__popcll(em), rank = (uint32_t)__popcll(em & ((1ull << lane) - 1ull)), room = RL_LIT_CHUNK - litFill;
+			uint32_t fresh = ~0u;
+			if (n > room && !litFull) {
+				if (lane == 0 && LL.numChunks != 0u) fresh = atomicAdd(&LL.ctl[0], 1u);
+				fresh = __shfl(fresh, 0);
+				if (fresh >= LL.numChunks) { fresh = ~0u; litFull = true; }
+			}
+			uint32_t entry = ~0u;
+			if (wantEntry) {
+				if (rank < room) entry = litChunk * RL_LIT_CHUNK + litFill + rank;
+				else if (fresh != ~0u) entry = fresh * RL_LIT_CHUNK + (rank - room);
+			}
+			if (n > room) {   // the wave's chunk is full now, and the fresh one (if any) is the wave's
+				if (lane == 0 && litChunk != ~0u) LL.ctl[RL_LIT_CTL + litChunk] = RL_LIT_CHUNK;
+				litChunk = fresh; litFill = fresh != ~0u ? n - room : RL_LIT_CHUNK;
+			} else litFill += n;
+			if (lane == 0 && litChunk != ~0u && n != 0u) LL.ctl[RL_LIT_CTL + litChunk] = litFill;
+			if (finLit) {
+				nLit++;
+				if (entry != ~0u) {
+					float4* e = (float4*)LL.entries + (size_t)entry * RL_LIT_STRIDE;
+					e[0] = make_float4(finL.x, finL.y, finL.z, __uint_as_float(outIndex));
+					e[1] = make_float4(__int_as_float(nrec), 0.0f, 0.0f, 0.0f);
+					#pragma unroll
+					for (int k = 0; k < RL_FOLD_PREFETCH; ++k) {
+						if (k < depth) {
+							const float4* st = (const float4*)pathStack + ((size_t)k * P.stackStride + gtid) * 2u;
+							e[2 + 2 * k] = st[0]; e[3 + 2 * k] = st[1];
+						} else if (k == depth && finTop) { e[2 + 2 * k] = finRec0; e[3 + 2 * k] = finRec1; }
+					}
+				} else {
+					nInPlace++;
+					V3 L = finL;
+					#pragma nounroll
+					for (int k = nrec - 1; k >= 0; --k) {
+						float4 r0 = finRec0, r1 = finRec1;
+						if (k < depth) {
+							const float4* st = (const float4*)pathStack + ((size_t)k * P.stackStride + gtid) * 2u;
+							r0 = st[0]; r1 = st[1];
+						}
+						const Mat m = MatFrom<PLAIN>(sm + LdsAt<LDS>::MATS + __float_as_int(r1.w) * RL_LDS_MSTRIDE(PLAIN));
+						L = FoldLazyVertex(m, r0, r1, L);
+					}
+					samples[outIndex] = make_sample(L.x, L.y, L.z);
+				}
+			}
+		}
+		{   // (a bare block: the eager branch below is still inside `if (active)`, and the brace behind #endif closes either)
+#else
 			if (done) {
 				RL_ARGS();
 				RL_LANEBEGIN();
@@ -420,6 +551,7 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 				st[0] = rec0; st[1] = rec1;
 				depth++;
 			}
+#endif
 		}
 		RL_STAMP(3);
 	}
@@ -436,5 +568,13 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 		for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
 		if (lane == 0 && v) atomicAdd(&counters[k], v);
 	}
+#if RL_LAZY_REFL
+	const uint32_t lz[2] = { nLit, nInPlace };
+	for (int k = 0; k < 2; ++k) {
+		unsigned long long v = lz[k];
+		for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+		if (lane == 0 && v) atomicAdd(&counters[RL_CNT_LIT + k], v);
+	}
+#endif
 }
 

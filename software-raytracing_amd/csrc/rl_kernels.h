@@ -5,6 +5,8 @@
 //                        the multi-rank scatter, the test hooks)
 //   rl_render_views.hip  k_trace_views, k_resolve_views, k_aov_views: the views twins (RaylibAMD_RenderViews).  Instantiated beside the one-view kernels they
 //                        change how the helpers both call are inlined into those (tools/isa_equivalence.py)
+//   rl_render_lazy.hip   k_trace_lazy, k_fold_lit, k_verify_lazy_refl: the leaf-list kernel's lazy-reflectance instance.  Beside the other k_trace instances it
+//                        changes how two loops of the eager PLAIN instance are scheduled
 //   rl_render_pool.hip   k_trace_pool and its twin: a scheduler strategy of its own (Makefile POOLFLAGS)
 //   rl_query.hip         k_query (RaylibAMD_TraceRays): beside the render kernels it would change how the walks they share are inlined into those
 //   rl_radiance.hip      k_radiance (RaylibAMD_TraceRadiance): the same reason, towards the render and the query kernels alike
@@ -46,6 +48,15 @@ __global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 
 #define RL_K_TRACE_VIEWS(a, b, c, d, e) template __global__ void k_trace_views<a, b, c, d, e>(RL_TRACE_ARGS, const DViews);
 RL_TRACE_INSTANCES(extern RL_K_TRACE)
 RL_TRACE_INSTANCES(extern RL_K_TRACE_VIEWS)
+// The lazy-reflectance instance of the leaf-list kernel's PLAIN instance (rl_k_trace.inl RL_LAZY_REFL, rl_dev_shade.h): a kernel name of its own with the lit list as
+// one more trailing argument, so that every other instance keeps its name and its code; and the kernel that folds the list's entries, one thread each, grid-stride over
+// the chunk counts on the device (the host never reads them).
+template <int STACK, bool PRIMS, bool FULL, int LDS, bool PLAIN>
+__global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 2)) k_trace_lazy(RL_TRACE_ARGS, const DLitList);
+#define RL_TRACE_LAZY_INSTANCES(X) X(16, false, true, 2, true)
+#define RL_K_TRACE_LAZY(a, b, c, d, e) template __global__ void k_trace_lazy<a, b, c, d, e>(RL_TRACE_ARGS, const DLitList);
+RL_TRACE_LAZY_INSTANCES(extern RL_K_TRACE_LAZY)
+__global__ void __launch_bounds__(RL_BLOCK) k_fold_lit(const DSceneView S, const DLitList LL, SampleRGB* __restrict__ samples);
 
 // ---------------------------------------------------------------------------
 // The pool megakernel (rl_dev_pool.h, rl_k_trace_pool.inl): k_trace's arguments.
@@ -161,5 +172,6 @@ __global__ void __launch_bounds__(RL_BLOCK) k_eval_camera(const DCamera cam, con
 __global__ void __launch_bounds__(RL_BLOCK) k_eval_texture(const DSceneView S, int tex, int srgb, const float* __restrict__ uv, int n, float* __restrict__ out);
 __global__ void __launch_bounds__(RL_BLOCK) k_eval_math(int fn, const float* __restrict__ x, const float* __restrict__ y, int n, float* __restrict__ out);
 __global__ void __launch_bounds__(RL_BLOCK) k_verify_exact_math(int which, unsigned long long* __restrict__ out);
+__global__ void __launch_bounds__(RL_BLOCK) k_verify_lazy_refl(uint32_t n, unsigned long long seed, unsigned long long* __restrict__ out);
 
 } // namespace rl

@@ -26,6 +26,8 @@ RenderKnobs ReadRenderKnobs()
 	if (const char* e = getenv("RAYLIB_GUIDED")) k.guided = atoi(e);
 	if (const char* e = getenv("RAYLIB_BLOCKS_PER_CU")) k.blocksPerCU = std::max(0, atoi(e));
 	if (const char* e = getenv("RAYLIB_CULL_CELLS")) k.cullCells = atoi(e);
+	k.lazyRefl = flag("RAYLIB_LAZY_REFL");
+	if (const char* e = getenv("RAYLIB_LIT_LIST")) k.litList = std::max(0ll, atoll(e));
 	if (const char* e = getenv("RAYLIB_QUERY_TREE")) { const int v = atoi(e); k.queryTree = (v == 2 || v == 4 || v == 8) ? v : 0; }
 	return k;
 }
@@ -104,6 +106,10 @@ TracePlan Pick(const Scene& sc, const RendererSettings& st, bool hasSky, const R
 			// the instance without the texture, cut-out and sky code computes the same values in the same order for the scenes it takes: those without a texture
 			// slot or a cut-out leaf (ScenePlain) rendered without a sky image.  RAYLIB_PLAIN_KERNEL=0 keeps the general instance.
 			p.plain = !hasSky && k.plainKernel != 0 && ScenePlain(sc);
+			// ... and the instance that evaluates a vertex's reflectance on lit paths only, for the scenes whose reflectances are provably finite wherever its
+			// per-vertex guard passes (SceneLazyRefl; rl_dev_shade.h LazyVertexSafe), on paths short enough for the guard's bound on a direction's length.
+			// The same bits as the eager instance (measured: DESIGN.md section 5).  RAYLIB_LAZY_REFL=0 keeps the eager instance.
+			p.lazy = p.plain && k.lazyRefl != 0 && st.maxPathLength <= RL_LAZY_MAX_PATH && SceneLazyRefl(sc);
 		}
 	}
 	return p;

@@ -24,6 +24,8 @@ struct RenderKnobs {
 	int blocksPerCU = 0;                          // RAYLIB_BLOCKS_PER_CU (0: not set or not positive)
 	int cullCells = 1;                            // RAYLIB_CULL_CELLS (rl_cull.cc reads it for itself; the runtime keys its cached cell lists on it)
 	int queryTree = 0;                            // RAYLIB_QUERY_TREE: 2, 4 or 8 (RaylibAMD_TraceRays, RaylibAMD_TraceRadiance; any other value: 0, not set)
+	int lazyRefl = -1;                            // RAYLIB_LAZY_REFL
+	long long litList = -1;                       // RAYLIB_LIT_LIST: entries of the lazy instance's lit list (0: every lit path folds in place); -1: not set
 };
 RenderKnobs ReadRenderKnobs();
 
@@ -39,6 +41,7 @@ struct TracePlan {
 	int lstack = 0;             // pool: entries of the traversal stack in LDS
 	int lds = 0;                // k_trace: 0, 1 = the scene in LDS, 2 = the leaf list
 	bool plain = false;         // the leaf-list kernel's instance without texture, cut-out and sky code
+	bool lazy = false;          // ... and of that, the lazy-reflectance instance (k_trace_lazy + k_fold_lit); the views twin of a lazy plan is the plain instance's
 	uint32_t pathsPerWave = 64, treeWidth = 2, nodeBytes = 64;   // RaylibAMDStats
 	bool keepNodes4 = true, keepNodes4f = true;   // the launch's view keeps the grid / float-box wide nodes (k_trace tells the tree by which is set)
 	int32_t eagerTree = TREE_NONE;   // the wide tree UploadScene puts on the device (TREE_GRID4, TREE_WIDE8 or none): the default plan's

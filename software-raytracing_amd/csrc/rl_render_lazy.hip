@@ -1,0 +1,103 @@
+// The leaf-list kernel's lazy-reflectance instance (k_trace_lazy), the kernel that finishes its lit paths (k_fold_lit) and the sweep of its guard, as a translation
+// unit of their own: instantiated beside the other k_trace instances, the lazy one changes how the compiler schedules two loops of the eager PLAIN instance, and
+// the eager kernels must stay what they are (tools/isa_equivalence.py) -- the reason the views twins have their unit.
+
+// ---- settings: this unit takes every default ----
+
+// ---- the device library ----
+#include "rl_kernels.h"
+
+namespace rl {
+
+// ---- the leaf-list kernel's lazy-reflectance instance and the kernel that finishes its lit paths (rl_dev_shade.h "lazy-reflectance instance") ----
+#define RL_VIEWS_TWIN 0
+#define RL_LAZY_REFL 1
+#include "rl_k_trace.inl"
+#undef RL_LAZY_REFL
+#undef RL_VIEWS_TWIN
+
+// One thread per entry of the lit list (rl_device.h DLitList): the path's vertex records, camera first, folded from the last back to the camera exactly as k_trace
+// folds -- each vertex's reflectance evaluated here, in full waves, instead of at its scattering event -- and the sample stored.
+__global__ void __launch_bounds__(RL_BLOCK)
+k_fold_lit(const DSceneView S, const DLitList LL, SampleRGB* __restrict__ samples)
+{
+	RL_MATH_PROLOGUE();
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t waves = gridDim.x * (RL_BLOCK / 64u);
+	const uint32_t used = min(LL.ctl[0], LL.numChunks);
+	for (uint32_t chunk = (blockIdx.x * RL_BLOCK + threadIdx.x) >> 6; chunk < used; chunk += waves) {
+		if (lane >= min(LL.ctl[RL_LIT_CTL + chunk], RL_LIT_CHUNK)) continue;
+		const float4* e = (const float4*)LL.entries + ((size_t)chunk * RL_LIT_CHUNK + lane) * RL_LIT_STRIDE;
+		const float4 h0 = e[0];
+		const int nrec = __float_as_int(e[1].x);   // (<= RL_FOLD_PREFETCH: k_trace_lazy folds longer paths in place)
+		V3 L = v3(h0.x, h0.y, h0.z);
+		#pragma nounroll
+		for (int k = nrec - 1; k >= 0; --k) {
+			const float4 r0 = e[2 + 2 * k], r1 = e[3 + 2 * k];
+			L = FoldLazyVertex(LoadMat(S, __float_as_int(r1.w)), r0, r1, L);
+		}
+		samples[__float_as_uint(h0.w)] = make_sample(L.x, L.y, L.z);
+	}
+}
+
+// Test hook: LazyVertexSafe's claim, swept inside the product library.  Every thread builds scattering events from edge and random inputs -- Wo.z at 0, +-2^-k and
+// +-1 and random directions, the sampler's draws at 0, 1e-6, 1 - 2^-24 and random, roughness at the ends of the lazy instance's interval and log-uniform between,
+// metallic 0, 1 and random -- runs the sampler and the ScatteringPdf part as ScatterLazy does, and evaluates the reflectance whatever the guard says.
+// out[0]: events; out[1]: events that pass the guard (with pdf > 0, the recorded ones) while a component of refl or sp is not finite -- must be 0;
+// out[2]: events with pdf > 0 that fail the guard.
+__global__ void __launch_bounds__(RL_BLOCK)
+k_verify_lazy_refl(uint32_t n, unsigned long long seed, unsigned long long* __restrict__ out)
+{
+	RL_MATH_PROLOGUE();
+	const uint32_t i0 = blockIdx.x * RL_BLOCK + threadIdx.x, stride = gridDim.x * RL_BLOCK;
+	Counters c; c.rays = c.nodes = c.tris = c.shaded = c.texels = c.samples = c.trips = 0; RL_DIAG_BIND(c);
+	unsigned long long events = 0, bad = 0, failed = 0;
+	for (uint32_t i = i0; i < n; i += stride) {
+		Rng g; g.s = raylib_rng_begin(seed, i, 0);
+		const uint32_t sel = i % 30030u;   // 2 * 3 * 5 * 7 * 11 * 13: the edge choices below cycle with coprime periods
+		// Wo: a unit vector with a chosen z
+		const uint32_t zk = sel % 11u;
+		float z = 2.0f * Next(g) - 1.0f;
+		if (zk < 8u) { const float e[8] = { 0.0f, 1.0f, -1.0f, 0x1p-1f, -0x1p-10f, 0x1p-24f, -0x1p-60f, 0x1p-126f }; z = e[zk]; }
+		const float phi = 2.0f * RL_PI * Next(g), rxy = rtm::sqrt_(fmaxf(0.0f, 1.0f - z * z));
+		float sphi, cphi; rtm::sincos_(phi, &sphi, &cphi);
+		const V3 Wo = v3(rxy * cphi, rxy * sphi, z);
+		const uint32_t uk = sel % 7u, vk = sel % 5u;
+		float u0 = Next(g), u1 = Next(g);
+		if (uk < 3u) u0 = uk == 0u ? 0.0f : uk == 1u ? 1e-6f : 1.0f - 0x1p-24f;
+		if (vk < 3u) u1 = vk == 0u ? 0.0f : vk == 1u ? 1e-6f : 1.0f - 0x1p-24f;
+		const uint32_t rk = sel % 3u;
+		const float rough = rk == 0u ? RL_LAZY_ROUGHNESS_MIN : rk == 1u ? RL_LAZY_ROUGHNESS_MAX : rtm::exp_(Next(g) * -10.0f * 0.69314718f);
+		const uint32_t mk = sel % 2u;
+		// metallic 0, 1, the planner's ends +-RL_LAZY_COLOR_MAX and random in between; albedo likewise, of either sign
+		const float mr = Next(g);
+		const float metallic = mk == 0u ? (mr < 0.25f ? 0.0f : mr < 0.5f ? 1.0f : mr < 0.75f ? RL_LAZY_COLOR_MAX : -RL_LAZY_COLOR_MAX) : RL_LAZY_COLOR_MAX * (2.0f * Next(g) - 1.0f);
+		const float ar = Next(g);
+		const V3 albedo = sel % 13u == 0u ? v3s(ar < 0.5f ? RL_LAZY_COLOR_MAX : -RL_LAZY_COLOR_MAX)
+		                                  : v3(Next(g), RL_LAZY_COLOR_MAX * (2.0f * Next(g) - 1.0f), ar < 0.5f ? -RL_LAZY_COLOR_MAX : RL_LAZY_COLOR_MAX * Next(g));
+		// the event, as ScatterLazy makes it (local frame = world frame)
+		const V3 N = v3(0.0f, 0.0f, 1.0f);
+		const bool bFlip = Wo.z < 0.0f;
+		V3 Wh = BeckmannSample(bFlip ? -Wo : Wo, rough, rough, u0, u1, c);
+		if (bFlip) Wh = -Wh;
+		const V3 Wi = reflect(-Wo, Wh);
+		V3 wh = normalize(Wo + Wi);
+		if (wh.z < 0.0f) wh.z = -wh.z;
+		const float sp = DistributionBeckmann(N, wh, rough) * absDot(wh, N);
+		const float pdf = sp / (4.0f * dot(Wo, Wh));
+		const V3 refl = ReflFromRecord<true>(albedo, rough, metallic, N, Wo, Wh, Wi, absDot(N, Wi));
+		++events;
+		if (pdf > 0.0f) {
+			const bool finite = fabsf(refl.x) < INFINITY && fabsf(refl.y) < INFINITY && fabsf(refl.z) < INFINITY && fabsf(sp) < INFINITY;
+			if (!LazyVertexSafe(Wo, Wh, sp)) ++failed;
+			else if (!finite) ++bad;
+		}
+	}
+	for (int off = 32; off > 0; off >>= 1) { events += __shfl_down(events, off); bad += __shfl_down(bad, off); failed += __shfl_down(failed, off); }
+	if ((threadIdx.x & 63u) == 0u) { atomicAdd(&out[0], events); if (bad) atomicAdd(&out[1], bad); if (failed) atomicAdd(&out[2], failed); }
+}
+
+// ---- instances ----
+RL_TRACE_LAZY_INSTANCES(RL_K_TRACE_LAZY)
+
+} // namespace rl

@@ -165,6 +165,7 @@ struct RankCtx {
 	DevBuf<float4> cells;   // N > 1: this rank's cells back to back, when they are not rendered into the gather buffer
 	DevBuf<unsigned long long> counters;
 	DevBuf<unsigned int> jobCounter;
+	DevBuf<float4> litList; DevBuf<uint32_t> litCtl;   // the lazy-reflectance instance's lit list and its chunk counts (rl_device.h DLitList), reset per sample batch
 	// cells outside the scene's silhouette (CullCells), per frame slot: the list of the others and a flag per cell, pinned on the host and on the device;
 	// cullKey = what they were computed from (camera, frame, cells, bounds): an unchanged view re-uses them without a copy
 	PinBuf<uint32_t> cellListHost[2]; DevBuf<uint32_t> cellList[2]; size_t cellListCells[2] = { 0, 0 };
@@ -214,6 +215,7 @@ struct PendingRender {
 	uint64_t pixels = 0;
 	uint64_t culledSamples = 0; uint32_t culledRaysPerSample = 0, culledSkyTexels = 0;   // camera samples of cells outside the scene's silhouette: reported apart, not traced (CullCells)
 	uint32_t culledCells = 0, listedCells = 0;
+	bool lazy = false;                         // the lazy-reflectance instance ran: the counter block's RL_CNT_LIT pair is read back too
 	bool enqueuedToEnd = false;                // EnqueueFrame reached the ev[slot][7] record (FinishRender waits for it; otherwise for the whole stream)
 	float4* out = nullptr; size_t outBytes = 0;
 	int slot = 0;                              // frame slot: which of the rank's event sets / pinned counter buffers this render uses

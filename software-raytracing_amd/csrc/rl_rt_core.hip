@@ -56,9 +56,9 @@ bool EnsureRuntime()
 		HIP_OK(hipStreamCreateWithFlags(&C->stream, hipStreamNonBlocking));
 		for (int q = 0; q < 2; ++q) {
 			for (int i = 0; i < 8; ++i) HIP_OK(hipEventCreate(&C->ev[q][i]));
-			if (!C->cntHost[q].Grow((CNT_COUNT + 24) * sizeof(unsigned long long))) return false;
+			if (!C->cntHost[q].Grow((CNT_COUNT + 24 + 2) * sizeof(unsigned long long))) return false;   // (+ the RL_CNT_LIT pair)
 		}
-		if (!C->counters.Grow((CNT_COUNT + 24 + RL_TIMELINE_SLOTS) * sizeof(unsigned long long))) return false;
+		if (!C->counters.Grow(RL_CNT_BLOCK * sizeof(unsigned long long))) return false;
 		if (!C->jobCounter.Grow(RL_MAX_HEADS * RL_HEAD_STRIDE * sizeof(unsigned int))) return false;   // the heads of the job list, one per XCD, 128 B apart
 		if (r > 0) { C->worker = new Worker; C->worker->Start(C->device); }
 		R.ranks.push_back(C);

@@ -9,6 +9,7 @@ namespace rl {
 // The kernels a render launches go by address (hipLaunchKernel): a one-view kernel and its views twin (RaylibAMD_RenderViews) differ by the twin's trailing DViews.
 typedef void (*TraceKernel)(const DRenderParams, const DSceneView, const SkyRot, SampleRGB*, float*, unsigned long long*, unsigned int*);
 typedef void (*TraceViewsKernel)(const DRenderParams, const DSceneView, const SkyRot, SampleRGB*, float*, unsigned long long*, unsigned int*, const DViews);
+typedef void (*TraceLazyKernel)(const DRenderParams, const DSceneView, const SkyRot, SampleRGB*, float*, unsigned long long*, unsigned int*, const DLitList);
 typedef void (*AovKernel)(const DRenderParams, const DSceneView, float4*, unsigned long long*);
 typedef void (*AovViewsKernel)(const DRenderParams, const DSceneView, float4*, unsigned long long*, const DViews);
 
@@ -33,6 +34,7 @@ static const void* KernelFor(const TracePlan& p, bool views)
 #undef RL_POOL_PICK
 		return nullptr;
 	}
+	if (p.lds == 2 && p.lazy && !views) return (const void*)(TraceLazyKernel)k_trace_lazy<16, false, true, 2, true>;   // (a batch of views stays eager: the plain twin)
 	if (p.lds == 2) return p.plain ? Trace<16, false, true, 2, true>(views) : Trace<16, false, true, 2>(views);
 	if (p.lds == 1) return Trace<16, false, true, 1>(views);
 	const bool full = p.tree == TREE_BOX4;
@@ -48,6 +50,8 @@ static const void* AovKernelFor(const TracePlan& p, bool views)
 }
 static std::atomic<int32_t> g_lastTracePlain{0};   // RaylibAMD_LastTracePlain: set by EnqueueFrame
 int32_t DeviceLastTracePlain() { return g_lastTracePlain.load(std::memory_order_relaxed); }
+static std::atomic<int32_t> g_lastTraceLazy{0};    // RaylibAMD_LastTraceLazy
+int32_t DeviceLastTraceLazy() { return g_lastTraceLazy.load(std::memory_order_relaxed); }
 
 // What differs between the frames the runtime queues -- a rank's share of a one-view render, a pass of a progressive session, a batch of views (EnqueueRender,
 // DeviceRenderViews): they fill this in, EnqueueFrame queues what it says.
@@ -123,7 +127,7 @@ static bool BeginFrame(RankCtx& R, int q, const Frame& F, size_t outBytes, Pendi
 {
 	pend.pathTrace = F.plan.pathTrace; pend.slot = q; pend.cnt = R.cntHost[q].ptr;
 	pend.out = F.out; pend.outBytes = outBytes;
-	HIP_OK(hipMemsetAsync(R.counters.ptr, 0, (CNT_COUNT + 24 + RL_TIMELINE_SLOTS) * sizeof(unsigned long long), R.stream));
+	HIP_OK(hipMemsetAsync(R.counters.ptr, 0, RL_CNT_BLOCK * sizeof(unsigned long long), R.stream));
 	HIP_OK(hipEventRecord(R.ev[q][0], R.stream));
 	return true;
 }
@@ -148,13 +152,18 @@ static bool EnqueueFrame(RankCtx& R, int q, const DeviceScene& DS, Frame& F, Pen
 		const int blocksPerCU = OccupancyOf(R, traceKernel, &plan);
 		if (blocksPerCU < 0) return false;
 		g_lastTracePlain.store(plan.plain ? 1 : 0, std::memory_order_relaxed);
+		const bool lazy = plan.lazy && !F.views;   // k_trace_lazy: the lit list is its trailing argument, and k_fold_lit follows it
+		g_lastTraceLazy.store(lazy ? 1 : 0, std::memory_order_relaxed);
+		pend.lazy = lazy;
+		DLitList LL = {};
 		pend.pathsPerWave = plan.pathsPerWave; pend.treeWidth = plan.treeWidth; pend.nodeBytes = plan.nodeBytes;
 		pend.culledCells = F.numLive - F.numActive; pend.listedCells = F.numActive;
 		const uint32_t batch = PlanLaunch(numCells, F.numActive, F.sEnd, F.sBegin, R.numCUs, blocksPerCU, plan, F.knobs).batch;
 		if (!R.samples.Grow((size_t)numSlots * sizeof(SampleRGB) * std::min(batch, F.sEnd - F.sBegin))) return false;
 		if (F.accum && batch < P.spp && !R.accum.Grow((size_t)numSlots * sizeof(float4))) return false;
 		const int depthSlots = P.maxPathLength > 1 ? P.maxPathLength : 1;
-		void* traceArgs[] = { &P, &F.view, &skyRot, &R.samples.ptr, &R.pathStack.ptr, &R.counters.ptr, &R.jobCounter.ptr, (void*)F.views };
+		void* traceArgs[] = { &P, &F.view, &skyRot, &R.samples.ptr, &R.pathStack.ptr, &R.counters.ptr, &R.jobCounter.ptr, lazy ? (void*)&LL : (void*)F.views };
+		void* foldArgs[] = { &F.view, &LL, &R.samples.ptr };
 		void* resolveArgs[] = { &P, &F.view, &skyRot, &R.samples.ptr, F.resolveArgs[0], F.resolveArgs[1], F.resolveArgs[2], F.resolveArgs[3], F.resolveArgs[4] };
 		for (uint32_t s0 = F.sBegin; s0 < F.sEnd; s0 += batch) {
 			const LaunchPlan L = PlanLaunch(numCells, F.numActive, F.sEnd, s0, R.numCUs, blocksPerCU, plan, F.knobs);
@@ -166,12 +175,26 @@ static bool EnqueueFrame(RankCtx& R, int q, const DeviceScene& DS, Frame& F, Pen
 			P.stackStride = L.stackStride; P.jobChunk = L.jobChunk;
 			P.numHeads = L.heads; P.jobsPerHead = L.jobsPerHead; P.guideShift = L.guideShift;
 			if (!R.pathStack.Grow((size_t)depthSlots * 8 * P.stackStride * sizeof(float))) return false;
+			if (lazy) {
+				// the lit list: an entry per 32 jobs of the launch (the Cornell frame lights 2 % of its traced paths, 0.7 % of its jobs; a scene that lights more folds the rest in
+				// place) and a chunk per wave on top, because every wave with a lit path holds a chunk of its own, unless RAYLIB_LIT_LIST says otherwise; in whole
+				// chunks; its head and chunk counts are reset behind the job counter
+				const uint64_t want = F.knobs.litList >= 0 ? (uint64_t)F.knobs.litList
+				                                           : std::max<uint64_t>(4096, L.jobs / 32) + (uint64_t)L.blocks * (RL_BLOCK / 64) * RL_LIT_CHUNK;
+				const uint32_t chunks = (uint32_t)std::min<uint64_t>(want / RL_LIT_CHUNK, 0x7FFFFFFFu / RL_LIT_CHUNK);
+				if (!R.litList.Grow(std::max<size_t>(1, chunks) * RL_LIT_CHUNK * RL_LIT_STRIDE * sizeof(float4))) return false;
+				if (!R.litCtl.Grow((RL_LIT_CTL + (size_t)chunks) * sizeof(uint32_t))) return false;
+				LL.entries = (float*)R.litList.ptr; LL.ctl = R.litCtl.ptr; LL.numChunks = chunks;
+				HIP_OK(hipMemsetAsync(R.litCtl.ptr, 0, (RL_LIT_CTL + (size_t)chunks) * sizeof(uint32_t), R.stream));
+			}
 			pend.jobHeads = L.heads;
 			F.firstBatch = s0 == F.sBegin; F.lastBatch = s0 + cnt >= F.sEnd;
 			HIP_OK(hipMemsetAsync(R.jobCounter.ptr, 0, RL_MAX_HEADS * RL_HEAD_STRIDE * sizeof(unsigned int), R.stream));   // heads count from their band's first job: one memset
 			HIP_OK(hipEventRecord(R.ev[q][2], R.stream));
 			if (L.jobs > 0)   // (else no cell of this frame sees the scene: the resolve has all it needs)
 				HIP_OK(hipLaunchKernel(traceKernel, dim3(L.blocks), dim3(RL_BLOCK), traceArgs, 0, R.stream));
+			if (L.jobs > 0 && lazy && LL.numChunks > 0)   // the lit paths' samples, before anything reads the sample buffer (traceKernelMs covers both kernels)
+				HIP_OK(hipLaunchKernel((const void*)k_fold_lit, dim3(std::min<uint32_t>((LL.numChunks + 3u) / 4u, (uint32_t)R.numCUs * 8u)), dim3(RL_BLOCK), foldArgs, 0, R.stream));
 			HIP_OK(hipEventRecord(R.ev[q][3], R.stream));
 			HIP_OK(hipLaunchKernel(F.resolve, dim3(rblocks), dim3(RL_BLOCK), resolveArgs, 0, R.stream));
 			++pend.launches;
@@ -192,6 +215,7 @@ static bool EnqueueFrame(RankCtx& R, int q, const DeviceScene& DS, Frame& F, Pen
 	if (!plan.pathTrace) pend.listedCells = numCells;
 	HIP_OK(hipEventRecord(R.ev[q][1], R.stream));
 	HIP_OK(hipMemcpyAsync(R.cntHost[q].ptr, R.counters.ptr, (CNT_COUNT + 24) * sizeof(unsigned long long), hipMemcpyDeviceToHost, R.stream));
+	if (pend.lazy) HIP_OK(hipMemcpyAsync(R.cntHost[q].ptr + CNT_COUNT + 24, R.counters.ptr + RL_CNT_LIT, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, R.stream));
 	HIP_OK(hipEventRecord(R.ev[q][7], R.stream));
 	pend.enqueuedToEnd = true;
 	return true;
@@ -363,6 +387,7 @@ bool FinishRender(RankCtx& R, PendingRender& pend, RaylibAMDStats& stats)
 	stats.culledSamples += pend.culledSamples; stats.culledRays += pend.culledSamples * pend.culledRaysPerSample;
 	stats.texFetches += pend.culledSamples * pend.culledSkyTexels;   // (k_resolve DOES look up the sky texel of every sample of a dropped cell: executed, counted)
 	stats.waveTrips += cnt[CNT_TRIPS];
+	if (pend.lazy) { stats.litPaths += cnt[CNT_COUNT + 24]; stats.litFoldedInPlace += cnt[CNT_COUNT + 24 + 1]; }
 	stats.pathsPerWave = pend.pathsPerWave; stats.treeWidth = pend.treeWidth; stats.nodeBytes = pend.nodeBytes;
 	stats.pixels += pend.pixels;
 	stats.kernelMs = std::max(stats.kernelMs, (double)totalMs);

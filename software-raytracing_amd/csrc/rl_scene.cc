@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <limits>
 #include <thread>
 #include <stdlib.h>
@@ -190,6 +191,32 @@ bool ScenePlain(const Scene& sc)
 	for (const DNode4& n : sc.bvh.leafList) for (int k = 0; k < 4; ++k) {
 		const int32_t ref = n.child[k];
 		if (ref < 0 && ref != DNODE_EMPTY && (((uint32_t)~ref) & 8u) != 0u) return false;
+	}
+	return true;
+}
+
+// The scene half of the choice of k_trace's lazy-reflectance instance: a plain scene of triangles whose materials are all microfacet or mirrors (a material no
+// triangle uses -- the OBJ loader's fallback -- does not count), with finite emission and with roughness, albedo and metallic inside the closed intervals for which
+// a vertex that passes the kernel's guard has a finite reflectance (rl_dev_shade.h LazyVertexSafe: roughness 0 is outside -- GeometryBeckmann's
+// a = rcp1_(-0) -- and every compare fails on NaN).  A mirror's reflectance is its albedo.
+bool SceneLazyRefl(const Scene& sc)
+{
+	if (!ScenePlain(sc) || sc.triangles.empty() || !sc.spheres.empty() || !sc.cubes.empty()) return false;
+	std::vector<char> used(sc.materials.size(), 0);
+	for (const HostTriangle& t : sc.triangles) {
+		if (t.material < 0 || (size_t)t.material >= sc.materials.size()) return false;
+		used[(size_t)t.material] = 1;
+	}
+	for (size_t i = 0; i < sc.materials.size(); ++i) {
+		if (!used[i]) continue;
+		const HostMaterial& m = sc.materials[i];
+		if (m.type == MAT_MIRROR) {
+			for (int k = 0; k < 3; ++k) if (!(std::fabs(m.albedo[k]) <= RL_LAZY_COLOR_MAX)) return false;
+			continue;
+		}
+		if (m.type != MAT_MICROFACET) return false;
+		if (!(m.roughness >= RL_LAZY_ROUGHNESS_MIN && m.roughness <= RL_LAZY_ROUGHNESS_MAX) || !(std::fabs(m.metallic) <= RL_LAZY_COLOR_MAX)) return false;
+		for (int k = 0; k < 3; ++k) if (!(std::fabs(m.albedo[k]) <= RL_LAZY_COLOR_MAX) || !std::isfinite(m.emissive[k])) return false;
 	}
 	return true;
 }

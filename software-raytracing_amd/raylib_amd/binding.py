@@ -42,7 +42,7 @@ class Stats(C.Structure):
                 ("gatherMode", C.c_uint32), ("rcclCommSize", C.c_uint32), ("devices", C.c_uint32), ("jobHeads", C.c_uint32),
                 ("gatherMs", C.c_double), ("scatterMs", C.c_double), ("rankKernelMs", C.c_double * 16), ("rankTraceMs", C.c_double * 16),
                 ("culledCells", C.c_uint32), ("listedCells", C.c_uint32), ("culledSamples", C.c_uint64), ("culledRays", C.c_uint64),
-                ("treeWidth", C.c_uint32), ("nodeBytes", C.c_uint32)]
+                ("treeWidth", C.c_uint32), ("nodeBytes", C.c_uint32), ("litPaths", C.c_uint64), ("litFoldedInPlace", C.c_uint64)]
 
     GATHER_MODES = {0: "none", 1: "rccl", 2: "peer"}
 
@@ -64,7 +64,7 @@ class RenderPlan(C.Structure):
                [(k, C.c_uint32) for k in ("pathsPerWave", "treeWidth", "nodeBytes")] + \
                [(k, C.c_int32) for k in ("keepNodes4", "keepNodes4f", "eagerTree")] + \
                [(k, C.c_uint32) for k in ("batch", "sampleCount", "blocks", "stackStride", "jobChunk", "heads", "jobsPerHead", "guideShift")] + \
-               [("jobs", C.c_uint64)]
+               [("jobs", C.c_uint64), ("lazy", C.c_int32), ("reserved", C.c_int32)]
     TREES = {0: "none", 1: "bvh2", 2: "box4", 3: "grid4", 4: "wide8"}
 
     def as_dict(self):
@@ -291,6 +291,9 @@ _EXPORTS = {
     "RaylibAMD_SceneLeafListInfo": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "RaylibAMD_ScenePlain": (C.c_int32, [C.c_void_p]),
     "RaylibAMD_LastTracePlain": (C.c_int32, []),
+    "RaylibAMD_SceneLazyRefl": (C.c_int32, [C.c_void_p]),
+    "RaylibAMD_LastTraceLazy": (C.c_int32, []),
+    "RaylibAMD_VerifyLazyRefl": (C.c_int32, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "RaylibAMD_PlanRender": (C.c_int32, [C.c_void_p, C.POINTER(RendererSettings), C.c_int32, C.c_int32, C.c_int32, C.POINTER(RenderPlan)]),
     "RaylibAMD_SceneWalk8Host": (C.c_int32, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "RaylibAMD_SceneWalkStackHost": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
