@@ -66,7 +66,6 @@ struct Task { uint32_t b, e, depth; };
 
 struct Ctx {
 	std::vector<TmpNode> tmp;
-	uint32_t maxDepth = 0;
 	std::vector<Task>* tasks = nullptr;   // only the top-level context spawns tasks
 };
 
@@ -79,20 +78,42 @@ struct BinSet {
 constexpr size_t kLeafListMax = 4 * RL_LEAFLIST_RECORDS;   // leaves of the leaf list (rl_device.h)
 constexpr uint32_t kMedianSplitDepth = 36;      // see build(): SAH splits above, median splits from here on -> depth <= 36 + 25 < 64
 constexpr uint32_t kParallelRange = 1u << 17;   // ranges at least this long are scanned by all threads
+// below these sizes a stage runs on the calling thread: the build (primitives), the grid copy of the 4-wide tree and the emission of the 8-wide one (nodes)
+constexpr size_t kThreadedBuild = 1u << 16, kThreadedQuantize = 1u << 16, kThreadedEmit8 = 1u << 15;
 
-template <typename F>
-void ParallelChunks(unsigned threads, uint32_t b, uint32_t e, F&& fn)
+// threads of a stage over `count` items: RAYLIB_BUILD_THREADS, else the host's (capped at 32; a host that does not say how many it has counts as one);
+// stages under their threshold run on the calling thread
+unsigned ThreadsFor(size_t count, size_t threshold)
 {
-	const uint32_t n = e - b;
-	if (threads <= 1 || n < kParallelRange) { fn(b, e, 0u); return; }
+	if (count < threshold) return 1u;
+	unsigned threads = std::thread::hardware_concurrency();
+	if (const char* e = getenv("RAYLIB_BUILD_THREADS")) { int v = atoi(e); if (v > 0) threads = (unsigned)v; }
+	return std::max(1u, std::min(32u, threads));
+}
+
+// fn(cb, ce, t) on the chunks of ceil(n / threads) items of [b, e), chunk t on thread t: chunk 0 on the caller, the others on threads that are joined before
+// this returns.  No caller's result depends on where the chunk boundaries fall.
+template <typename F>
+void ParallelFor(unsigned threads, size_t b, size_t e, F&& fn)
+{
+	const size_t n = e - b;
+	if (threads <= 1) { fn(b, e, 0u); return; }
 	std::vector<std::thread> pool;
-	const uint32_t per = (n + threads - 1) / threads;
+	const size_t per = (n + threads - 1) / threads;
 	for (unsigned t = 1; t < threads; ++t) {
-		const uint32_t cb = b + std::min(n, t * per), ce = b + std::min(n, (t + 1) * per);
+		const size_t cb = b + std::min(n, t * per), ce = b + std::min(n, (t + 1) * per);
 		if (cb < ce) pool.emplace_back([&fn, cb, ce, t]() { fn(cb, ce, t); });
 	}
 	fn(b, b + std::min(n, per), 0u);
 	for (std::thread& th : pool) th.join();
+}
+
+// build()'s scans: short ranges are not worth the threads
+template <typename F>
+void ParallelChunks(unsigned threads, uint32_t b, uint32_t e, F&& fn)
+{
+	if (e - b < kParallelRange) { fn(b, e, 0u); return; }
+	ParallelFor(threads, b, e, [&fn](size_t cb, size_t ce, unsigned t) { fn((uint32_t)cb, (uint32_t)ce, t); });
 }
 
 // a leaf is either <= kMaxLeaf triangles or exactly one analytic primitive
@@ -141,7 +162,6 @@ int32_t build(Shared& S, Ctx& C, uint32_t b, uint32_t e, uint32_t depth)
 
 	auto makeLeaf = [&]() {
 		C.tmp[self].first = b; C.tmp[self].count = n;
-		if (depth > C.maxDepth) C.maxDepth = depth;
 		return self;
 	};
 	if (n <= 1) return makeLeaf();
@@ -247,17 +267,13 @@ inline void storeBox(float* mn, float* mx, const Box& b) {
 }
 inline int32_t leafRef(uint32_t first, uint32_t kind, uint32_t count) { return ~(int32_t)((first << 6) | (kind << 4) | (count - 1)); }
 
-} // namespace
-
-// Leaf references keep the first primitive slot in 25 bits (DNode, rl_device.h): more primitives than that cannot be addressed.
-bool BVHCapacityOk(size_t numPrimitives) { return numPrimitives < ((size_t)1 << 25); }
-
 // nodes4 -> nodes4q (DNode4Q, rl_device.h).  Every decision is made in double, where origin + q * step is exact, so "the grid
 // box contains the float box" holds exactly.
 static void QuantizeWide(BVH& out)
 {
 	out.nodes4q.assign(out.nodes4.size(), DNode4Q());
-	auto run = [&](size_t i0, size_t i1) { for (size_t i = i0; i < i1; ++i) {
+	const size_t count = out.nodes4.size();
+	ParallelFor(ThreadsFor(count, kThreadedQuantize), 0, count, [&](size_t i0, size_t i1, unsigned) { for (size_t i = i0; i < i1; ++i) {
 		const DNode4& n = out.nodes4[i];
 		DNode4Q q; memset(&q, 0, sizeof(q));
 		float steps[3] = { 0.0f, 0.0f, 0.0f };
@@ -286,15 +302,7 @@ static void QuantizeWide(BVH& out)
 		q.stepX = steps[0]; q.stepY = steps[1]; q.stepZ = steps[2];
 		for (int k = 0; k < 4; ++k) q.child[k] = n.child[k];
 		out.nodes4q[i] = q;
-	} };
-	const size_t n = out.nodes4.size();
-	unsigned threads = n >= (1u << 16) ? std::max(1u, std::min(32u, std::thread::hardware_concurrency())) : 1u;
-	if (const char* e = getenv("RAYLIB_BUILD_THREADS")) { int v = atoi(e); if (v > 0 && n >= (1u << 16)) threads = (unsigned)std::min(v, 32); }
-	std::vector<std::thread> pool;
-	const size_t per = (n + threads - 1) / threads;
-	for (unsigned t = 1; t < threads; ++t) { const size_t a = std::min(n, t * per), b = std::min(n, (t + 1) * per); if (a < b) pool.emplace_back(run, a, b); }
-	run(0, std::min(n, per));
-	for (std::thread& th : pool) th.join();
+	} });
 }
 
 // ---- the 8-wide tree (DNode8, rl_device.h) ---------------------------------------------------------------------------------------------------------
@@ -365,6 +373,22 @@ static int PlannedChildren(std::vector<TmpNode>& T, const std::vector<WidePlan<W
 	return nk;
 }
 
+// The greedy collapse: starting from t's two children, the inner child with the largest surface area is replaced by its own two children until there are `width`
+// (or only leaves).  Returns their number.
+static int OpenLargestFirst(const std::vector<TmpNode>& T, int32_t t, int32_t* kids, int width)
+{
+	int nk = 0;
+	kids[nk++] = T[t].left; kids[nk++] = T[t].right;
+	while (nk < width) {
+		int best = -1; float bestArea = -1.0f;
+		for (int k = 0; k < nk; ++k) if (T[kids[k]].left >= 0) { const float a = T[kids[k]].box.halfArea(); if (a > bestArea) { bestArea = a; best = k; } }
+		if (best < 0) break;
+		const int32_t open = kids[best];
+		kids[best] = T[open].left; kids[nk++] = T[open].right;
+	}
+	return nk;
+}
+
 // Leaves of the binary tree hold up to kMaxLeaf triangles: below that the surface-area heuristic finds a node not worth its step.  In an 8-wide node a step tests
 // eight boxes whether or not eight children exist (5.4 did on the 298 k-triangle room), so a spare slot is a free box: every triangle leaf gets a binary split
 // of its triangles (sorted along the longest axis of their centroids; each range cut where the two halves' area x count is least) down to single triangles,
@@ -429,16 +453,7 @@ static void CollapseWide8(std::vector<TmpNode>& T, int32_t root, Wide8& W, bool 
 		W.sah += (double)T[it.tmp].box.halfArea() / rootArea;
 		int32_t kids[8]; int nk = 0;
 		if (!plan.empty()) nk = PlannedChildren<8>(T, plan, it.tmp, kids);
-		else {
-		kids[nk++] = T[it.tmp].left; kids[nk++] = T[it.tmp].right;
-		while (nk < 8) {
-			int best = -1; float bestArea = -1.0f;
-			for (int k = 0; k < nk; ++k) if (T[kids[k]].left >= 0) { const float a = T[kids[k]].box.halfArea(); if (a > bestArea) { bestArea = a; best = k; } }
-			if (best < 0) break;
-			const int32_t open = kids[best];
-			kids[best] = T[open].left; kids[nk++] = T[open].right;
-		}
-		}
+		else nk = OpenLargestFirst(T, it.tmp, kids, 8);
 		const Box& nb = T[it.tmp].box;
 		const double cx = 0.5 * ((double)nb.mn.x + nb.mx.x), cy = 0.5 * ((double)nb.mn.y + nb.mx.y), cz = 0.5 * ((double)nb.mn.z + nb.mx.z);
 		double cost[8][8];
@@ -482,15 +497,7 @@ static double ExpectedSteps4(const std::vector<TmpNode>& T, int32_t root)
 	while (!work.empty()) {
 		const int32_t t = work.back(); work.pop_back();
 		sum += (double)T[t].box.halfArea() / rootArea;
-		int32_t kids[4]; int nk = 0;
-		kids[nk++] = T[t].left; kids[nk++] = T[t].right;
-		while (nk < 4) {
-			int best = -1; float bestArea = -1.0f;
-			for (int k = 0; k < nk; ++k) if (T[kids[k]].left >= 0) { const float a = T[kids[k]].box.halfArea(); if (a > bestArea) { bestArea = a; best = k; } }
-			if (best < 0) break;
-			const int32_t open = kids[best];
-			kids[best] = T[open].left; kids[nk++] = T[open].right;
-		}
+		int32_t kids[4]; const int nk = OpenLargestFirst(T, t, kids, 4);
 		for (int k = 0; k < nk; ++k) if (T[kids[k]].left >= 0) work.push_back(kids[k]);
 	}
 	return sum;
@@ -501,7 +508,8 @@ static void EmitWide8(const std::vector<TmpNode>& T, const Wide8& W, const std::
 {
 	out.nodes8.assign(W.nodes.size(), DNode8());
 	out.depth8 = W.depth; out.sahNodes8 = (float)W.sah;
-	auto run = [&](size_t i0, size_t i1) { for (size_t i = i0; i < i1; ++i) {
+	const size_t count = W.nodes.size();
+	ParallelFor(ThreadsFor(count, kThreadedEmit8), 0, count, [&](size_t i0, size_t i1, unsigned) { for (size_t i = i0; i < i1; ++i) {
 		const Wide8Node& w = W.nodes[i];
 		DNode8 n; memset(&n, 0, sizeof(n));
 		uint32_t imask = 0, leafMask = 0, triBase = 0; bool haveTri = false;
@@ -539,32 +547,16 @@ static void EmitWide8(const std::vector<TmpNode>& T, const Wide8& W, const std::
 		n.meta = exps[0] | (exps[1] << 8) | (exps[2] << 16) | (imask << 24);
 		n.childBase = w.firstChild; n.triBase = triBase; n.leafMask = leafMask; n.alphaMask = 0;
 		out.nodes8[i] = n;
-	} };
-	const size_t n = W.nodes.size();
-	unsigned threads = n >= (1u << 15) ? std::max(1u, std::min(32u, std::thread::hardware_concurrency())) : 1u;
-	if (const char* e = getenv("RAYLIB_BUILD_THREADS")) { int v = atoi(e); if (v > 0 && n >= (1u << 15)) threads = (unsigned)std::min(v, 32); }
-	std::vector<std::thread> pool;
-	const size_t per = (n + threads - 1) / threads;
-	for (unsigned t = 1; t < threads; ++t) { const size_t a = std::min(n, t * per), b = std::min(n, (t + 1) * per); if (a < b) pool.emplace_back(run, a, b); }
-	run(0, std::min(n, per));
-	for (std::thread& th : pool) th.join();
+	} });
 }
 
-void BuildBVH(const std::vector<PrimRef>& prims, BVH& out, const BVHBuildOptions& opt)
+// The binary tree.  Reads the primitives' boxes and kinds; fills B (kinds, boxes, centroids and `order`, the primitives permuted so that every node's are one
+// range) and T, the tree's nodes in the pre-order a single-threaded build pushes them in, whatever the thread count; returns the root's index in T.  The top
+// levels are built by the caller with all threads scanning the long ranges, the sub-trees below B.taskSize primitives by the workers, one arena each, and
+// Splice puts them back in order.  RAYLIB_BUILD_TIMING=1 logs the three phases.
+int32_t BuildBinary(const std::vector<PrimRef>& prims, Shared& B, std::vector<TmpNode>& T)
 {
-	out.nodes.clear(); out.nodes4.clear(); out.nodes4q.clear(); out.nodes8.clear(); out.depth8 = 0; out.leafList.clear(); out.stackNeed4 = 0; out.triOrder.clear(); out.depth = 0; out.sahCost = 0.0f;
 	const uint32_t n = (uint32_t)prims.size();
-	Box empty; empty.mn = F3(FLT_MAX, FLT_MAX, FLT_MAX); empty.mx = F3(-FLT_MAX, -FLT_MAX, -FLT_MAX);
-
-	if (n == 0) {
-		DNode root; memset(&root, 0, sizeof(root));
-		storeBox(root.lmin, root.lmax, empty); storeBox(root.rmin, root.rmax, empty);
-		root.left = root.right = DNODE_EMPTY;
-		out.nodes.push_back(root);
-		return;
-	}
-
-	Shared B;
 	B.kind.resize(n); B.triBox.resize(n); B.centroid.resize(n); B.order.resize(n);
 	for (uint32_t i = 0; i < n; ++i) {
 		Box b; b.mn = prims[i].mn; b.mx = prims[i].mx;
@@ -574,10 +566,7 @@ void BuildBVH(const std::vector<PrimRef>& prims, BVH& out, const BVHBuildOptions
 		B.order[i] = i;
 	}
 	// threads: RAYLIB_BUILD_THREADS, else the host's (capped at 32); small scenes build on the calling thread
-	unsigned threads = std::thread::hardware_concurrency();
-	if (const char* e = getenv("RAYLIB_BUILD_THREADS")) { int v = atoi(e); if (v > 0) threads = (unsigned)v; }
-	threads = std::max(1u, std::min(32u, threads));
-	if (n < (1u << 16)) threads = 1;
+	const unsigned threads = ThreadsFor(n, kThreadedBuild);
 	B.threads = threads;
 	// sub-trees of at most this many primitives are tasks.  Not far below kParallelRange: between the two sizes a range is
 	// binned by ONE thread while the others wait (10 M triangles, 32 threads: 1.3 s of a 2.3 s build went there with n / 16T)
@@ -598,7 +587,7 @@ void BuildBVH(const std::vector<PrimRef>& prims, BVH& out, const BVHBuildOptions
 	std::vector<std::pair<uint32_t, int32_t>> where(tasks.size());   // task -> (arena, root index in it)
 	if (!tasks.empty()) {
 		std::atomic<size_t> nextTask{ 0 };
-		auto worker = [&](unsigned me) {
+		ParallelFor(threads, 0, threads, [&](size_t, size_t, unsigned me) {   // one chunk per thread: worker `me`
 			sub[me].tmp.reserve((size_t)n / threads);
 			for (;;) {
 				const size_t t = nextTask.fetch_add(1);
@@ -606,59 +595,48 @@ void BuildBVH(const std::vector<PrimRef>& prims, BVH& out, const BVHBuildOptions
 				const int32_t r = build(B, sub[me], tasks[t].b, tasks[t].e, tasks[t].depth);
 				where[t] = { me, r };
 			}
-		};
-		std::vector<std::thread> pool;
-		for (unsigned t = 1; t < threads; ++t) pool.emplace_back(worker, t);
-		worker(0u);
-		for (std::thread& th : pool) th.join();
+		});
 	}
 	const auto tb2 = std::chrono::steady_clock::now();
-	uint32_t maxDepth = top.maxDepth;
-	for (const Ctx& c : sub) maxDepth = std::max(maxDepth, c.maxDepth);
-	std::vector<TmpNode> merged;
 	int32_t root = topRoot;
 	if (!tasks.empty()) {
-		merged.reserve(2 * (size_t)n);
-		root = Splice(sub, where, top, topRoot, merged);
-		top.tmp.clear(); top.tmp.shrink_to_fit();
-		for (Ctx& c : sub) { c.tmp.clear(); c.tmp.shrink_to_fit(); }
+		T.reserve(2 * (size_t)n);
+		root = Splice(sub, where, top, topRoot, T);
 	} else {
-		merged.swap(top.tmp);
+		T.swap(top.tmp);
 	}
+	if (getenv("RAYLIB_BUILD_TIMING")) Log("BVH build: %u threads, %zu tasks; top levels %.3f s, tasks %.3f s, merge %.3f s", threads, tasks.size(),
+		std::chrono::duration<double>(tb1 - tb0).count(), std::chrono::duration<double>(tb2 - tb1).count(), std::chrono::duration<double>(std::chrono::steady_clock::now() - tb2).count());
+	return root;
+}
 
-	// Leaf references.  Triangle leaves index the triangle arrays in leaf order (out.triOrder lists the
-	// original triangle index of every slot); an analytic primitive's leaf carries its index in its own array.
-	std::vector<TmpNode>& T = merged;
-	// Triangle-only scenes of at least 8 triangles get the wide trees; the 8-wide one decides the order of the triangle slots (the leaf children of one of its
-	// nodes hold consecutive slots), every other format refers to the same slots through its leaf references.
-	bool trianglesOnly = true;
-	for (uint32_t i = 0; i < n && trianglesOnly; ++i) if (prims[i].kind != PRIM_TRIANGLE) trianglesOnly = false;
-	const bool wideTrees = n >= 8 && trianglesOnly && T[root].left >= 0;
-	// (not for the scenes small enough for the leaf list: its leaves are sub-trees of this tree, whose triangles must stay one range of slots -- the depth-first order)
-	const bool wide8 = wideTrees && n > RL_LEAFLIST_MAXTRIS;
-	Wide8 W8;
-	if (wide8) {
-		// leaves split for the 8-wide plan (SplitLeaves) where that tree is the one the scene's rays will walk
-		if (!opt.wideGreedy && opt.splitLeaves8 && ExpectedSteps4(T, root) >= opt.minSteps8) SplitLeaves(T, B);
-		CollapseWide8(T, root, W8, opt.wideGreedy, opt.triCost8);
-	}
+// Leaf references.  Triangle leaves index the triangle arrays in leaf order (triOrder lists the original triangle index of every slot); an analytic primitive's leaf carries its index in its own array.
+// Reads T's leaves -- those `order` lists, in its order (the 8-wide plan's W.leafOrder), else every leaf in T's order --, B and the primitives' indices; appends
+// to triOrder; returns the leaf reference of every node of T it visited (0 elsewhere).
+std::vector<int32_t> AssignLeafSlots(const std::vector<TmpNode>& T, const Shared& B, const std::vector<PrimRef>& prims, const std::vector<int32_t>* order, std::vector<uint32_t>& triOrder)
+{
 	std::vector<int32_t> leafCode(T.size(), 0);
 	auto codeLeaf = [&](size_t t) {
 		const uint32_t k = B.kind[B.order[T[t].first]];
 		if (k == PRIM_TRIANGLE) {
-			const uint32_t first = (uint32_t)out.triOrder.size();
-			for (uint32_t i = 0; i < T[t].count; ++i) out.triOrder.push_back(prims[B.order[T[t].first + i]].index);
+			const uint32_t first = (uint32_t)triOrder.size();
+			for (uint32_t i = 0; i < T[t].count; ++i) triOrder.push_back(prims[B.order[T[t].first + i]].index);
 			leafCode[t] = leafRef(first, PRIM_TRIANGLE, T[t].count);
 		} else {
 			leafCode[t] = leafRef(prims[B.order[T[t].first]].index, k, 1);
 		}
 	};
-	if (wide8) { for (int32_t t : W8.leafOrder) codeLeaf((size_t)t); }
+	if (order) { for (int32_t t : *order) codeLeaf((size_t)t); }
 	else for (size_t t = 0; t < T.size(); ++t) if (T[t].left < 0) codeLeaf(t);
+	return leafCode;
+}
 
-	// Emit two-box nodes in depth-first order.  A tree that is a single leaf still
-	// gets one inner node (left = the leaf, right = empty).
+// Emit two-box nodes in depth-first order.  A tree that is a single leaf still gets one inner node (left = the leaf, right = empty).
+// Reads T (skipping what CollapseWide8 marked dead) and the leaf references; writes out.nodes, out.depth and out.sahCost (the single-leaf tree: depth 1, no cost).
+void EmitBinary(const std::vector<TmpNode>& T, int32_t root, const std::vector<int32_t>& leafCode, BVH& out)
+{
 	if (T[root].left < 0) {
+		Box empty; empty.reset();
 		DNode nd; memset(&nd, 0, sizeof(nd));
 		storeBox(nd.lmin, nd.lmax, T[root].box); storeBox(nd.rmin, nd.rmax, empty);
 		nd.left = leafCode[root]; nd.right = DNODE_EMPTY;
@@ -668,10 +646,10 @@ void BuildBVH(const std::vector<PrimRef>& prims, BVH& out, const BVHBuildOptions
 	}
 	std::vector<int32_t> emitIndex(T.size(), -1);
 	int32_t next = 0;
+	uint32_t maxDepth = 0;
 	{
 		// (the depth is taken here, from the tree that is emitted: split leaves the 8-wide plan opened are inner nodes of it)
 		std::vector<std::pair<int32_t, uint32_t>> st; st.push_back({ root, 0u });
-		maxDepth = 0;
 		while (!st.empty()) {
 			const int32_t t = st.back().first; const uint32_t d = st.back().second; st.pop_back();
 			if (T[t].left < 0) { maxDepth = std::max(maxDepth, d); continue; }
@@ -692,109 +670,215 @@ void BuildBVH(const std::vector<PrimRef>& prims, BVH& out, const BVHBuildOptions
 		nd.right = (R.left < 0) ? leafCode[T[t].right] : emitIndex[T[t].right];
 		out.nodes[emitIndex[t]] = nd;
 	}
-	if (getenv("RAYLIB_BUILD_TIMING")) Log("BVH build: %u threads, %zu tasks; top levels %.3f s, tasks %.3f s, merge + emit %.3f s", threads, tasks.size(),
-		std::chrono::duration<double>(tb1 - tb0).count(), std::chrono::duration<double>(tb2 - tb1).count(), std::chrono::duration<double>(std::chrono::steady_clock::now() - tb2).count());
 	out.depth = maxDepth;     // leaves at depth d => at most d inner nodes above them
 	out.sahCost = (float)sah;
-
-	// ---- the wide tree: collapse to <= 4 children per node ----
-	// Starting from a node's two children, the inner child with the largest surface area is replaced by its own two
-	// children until there are four (or only leaves).  Only for scenes the pool schedule can run (triangles only, not tiny).
-	if (wideTrees) {
-		if (wide8) EmitWide8(T, W8, leafCode, out);
-		struct Item { int32_t tmp; int32_t slot; uint32_t need; };   // a BVH2 inner node that becomes wide node `slot`
-		std::vector<Item> work;
-		out.nodes4.clear();
-		out.nodes4.reserve(T.size() / 3 + 1);
-		out.nodes4.emplace_back();
-		work.push_back({ root, 0, 0u });
-		uint32_t needMax = 0;
-		double sah4 = 0.0; const double rootArea4 = std::max((double)T[root].box.halfArea(), 1e-30);
-		while (!work.empty()) {
-			const Item it = work.back(); work.pop_back();
-			sah4 += (double)T[it.tmp].box.halfArea() / rootArea4;
-			int32_t kids[4]; int nk = 0;
-			kids[nk++] = T[it.tmp].left; kids[nk++] = T[it.tmp].right;
-			while (nk < 4) {
-				int best = -1; float bestArea = -1.0f;
-				for (int k = 0; k < nk; ++k) if (T[kids[k]].left >= 0) { const float a = T[kids[k]].box.halfArea(); if (a > bestArea) { bestArea = a; best = k; } }
-				if (best < 0) break;
-				const int32_t open = kids[best];
-				kids[best] = T[open].left; kids[nk++] = T[open].right;
-			}
-			DNode4 nd; memset(&nd, 0, sizeof(nd));
-			const uint32_t need = it.need + (uint32_t)(nk - 1);   // entries this node can leave on the stack while one child is followed
-			if (need > needMax) needMax = need;
-			for (int k = 0; k < 4; ++k) {
-				if (k >= nk) {
-					nd.lo[0][k] = nd.lo[1][k] = nd.lo[2][k] = FLT_MAX; nd.hi[0][k] = nd.hi[1][k] = nd.hi[2][k] = -FLT_MAX;
-					nd.child[k] = DNODE_EMPTY;
-					continue;
-				}
-				const TmpNode& c = T[kids[k]];
-				nd.lo[0][k] = c.box.mn.x; nd.lo[1][k] = c.box.mn.y; nd.lo[2][k] = c.box.mn.z;
-				nd.hi[0][k] = c.box.mx.x; nd.hi[1][k] = c.box.mx.y; nd.hi[2][k] = c.box.mx.z;
-				if (c.left < 0) nd.child[k] = leafCode[kids[k]];
-				else {
-					const int32_t slot = (int32_t)out.nodes4.size();
-					out.nodes4.emplace_back();
-					nd.child[k] = slot;
-					work.push_back({ kids[k], slot, need });
-				}
-			}
-			out.nodes4[it.slot] = nd;
-		}
-		out.stackNeed4 = needMax; out.sahNodes4 = (float)sah4;
-		QuantizeWide(out);
-		// ---- the leaf list: a scene that 4 * RL_LEAFLIST_RECORDS leaves of <= 8 triangles can hold is walked without a tree ----
-		// Every ray tests every leaf's box once (4 records of 4 boxes, in lockstep across a wave: no stack, no divergence), then visits the
-		// leaves it touched nearest first.  In a tree this small a wave's rays take different turns at every node, and the wave pays for
-		// the union of their walks (Cornell frame: 10 node steps per wave and bounce for 3.5 per ray).  The leaves are a cut through the
-		// SAH tree: starting from the root, the sub-tree with the largest area x triangle count is opened until the list is full or only the tree's own leaves are left.
-		// Up to 4.5 triangles per leaf on average: beyond, the leaves of the cut grow towards 8 triangles and the tree wins again (tools/gpu_leaflist.py,
-		// leaf list / BVH4 walk, first version: 36 triangles 0.86, 72: 0.92, 84: 0.88, 96: 0.89, 108: 0.90, 120 (8-triangle leaves): 1.05; final version: 0.79, 0.80, 0.79,
-		// 0.77, 0.78 -- the limit is also what the kernel's LDS layout holds, rl_device.h RL_LEAFLIST_MAXTRIS).
-		if (n <= RL_LEAFLIST_MAXTRIS) {
-			std::vector<uint32_t> triFirst(T.size(), 0), triCount(T.size(), 0);
-			for (size_t t = T.size(); t-- > 0;) {   // children follow their parent in T (pre-order): a reverse sweep sees them first
-				if (T[t].left < 0) { triFirst[t] = ((uint32_t)~leafCode[t]) >> 6; triCount[t] = T[t].count; }
-				else { triFirst[t] = triFirst[T[t].left]; triCount[t] = triCount[T[t].left] + triCount[T[t].right]; }
-			}
-			std::vector<int32_t> cut; cut.push_back(root);
-			for (;;) {
-				int best = -1; double bestCost = -1.0; bool bestOver = false;
-				for (size_t k = 0; k < cut.size(); ++k) {
-					const int32_t t = cut[k];
-					if (T[t].left < 0) continue;
-					const bool over = triCount[t] > 8;   // too large for one leaf: goes first
-					const double cost = ((double)T[t].box.halfArea() + 1e-30) * triCount[t];
-					if (best < 0 || (over && !bestOver) || (over == bestOver && cost > bestCost)) { bestCost = cost; best = (int)k; bestOver = over; }
-				}
-				if (best < 0 || (cut.size() >= kLeafListMax && !bestOver)) break;
-				if (cut.size() >= kLeafListMax) { cut.clear(); break; }   // does not fit
-				const int32_t open = cut[(size_t)best];
-				cut[(size_t)best] = T[open].left; cut.push_back(T[open].right);
-			}
-			bool fits = !cut.empty();
-			for (int32_t t : cut) if (triCount[t] > 8) fits = false;
-			if (fits) {
-				out.leafList.assign((cut.size() + 3) / 4, DNode4());
-				for (DNode4& nd : out.leafList) {
-					memset(&nd, 0, sizeof(nd));
-					// an unused slot is the box [+inf, -inf]: whatever the ray, one of its axes enters it at +inf (rl_dev_walk.h TraverseLeafList has no other test for it)
-					for (int k = 0; k < 4; ++k) { nd.lo[0][k] = nd.lo[1][k] = nd.lo[2][k] = INFINITY; nd.hi[0][k] = nd.hi[1][k] = nd.hi[2][k] = -INFINITY; nd.child[k] = DNODE_EMPTY; }
-				}
-				for (size_t at = 0; at < cut.size(); ++at) {
-					const int32_t t = cut[at];
-					DNode4& nd = out.leafList[at / 4]; const int k = (int)(at % 4);
-					nd.lo[0][k] = T[t].box.mn.x; nd.lo[1][k] = T[t].box.mn.y; nd.lo[2][k] = T[t].box.mn.z;
-					nd.hi[0][k] = T[t].box.mx.x; nd.hi[1][k] = T[t].box.mx.y; nd.hi[2][k] = T[t].box.mx.z;
-					nd.child[k] = leafRef(triFirst[t], PRIM_TRIANGLE, triCount[t]);
-				}
-			}
-		}
-	} else { out.nodes4.clear(); out.nodes4q.clear(); out.nodes8.clear(); out.depth8 = 0; out.leafList.clear(); out.stackNeed4 = 0; }
 }
+
+// ---- the wide tree: collapse to <= 4 children per node ----
+// Starting from a node's two children, the inner child with the largest surface area is replaced by its own two children until there are four (or only leaves).  Only for scenes the pool schedule can run (triangles only, not tiny).
+// Reads T and the leaf references; writes out.nodes4, out.stackNeed4 (the entries a walk can leave on its stack along the worst path) and out.sahNodes4.
+void EmitWide4(const std::vector<TmpNode>& T, int32_t root, const std::vector<int32_t>& leafCode, BVH& out)
+{
+	struct Item { int32_t tmp; int32_t slot; uint32_t need; };   // a BVH2 inner node that becomes wide node `slot`
+	std::vector<Item> work;
+	out.nodes4.reserve(T.size() / 3 + 1);
+	out.nodes4.emplace_back();
+	work.push_back({ root, 0, 0u });
+	uint32_t needMax = 0;
+	double sah4 = 0.0; const double rootArea4 = std::max((double)T[root].box.halfArea(), 1e-30);
+	while (!work.empty()) {
+		const Item it = work.back(); work.pop_back();
+		sah4 += (double)T[it.tmp].box.halfArea() / rootArea4;
+		int32_t kids[4]; const int nk = OpenLargestFirst(T, it.tmp, kids, 4);
+		DNode4 nd; memset(&nd, 0, sizeof(nd));
+		const uint32_t need = it.need + (uint32_t)(nk - 1);   // entries this node can leave on the stack while one child is followed
+		if (need > needMax) needMax = need;
+		for (int k = 0; k < 4; ++k) {
+			if (k >= nk) {
+				nd.lo[0][k] = nd.lo[1][k] = nd.lo[2][k] = FLT_MAX; nd.hi[0][k] = nd.hi[1][k] = nd.hi[2][k] = -FLT_MAX;
+				nd.child[k] = DNODE_EMPTY;
+				continue;
+			}
+			const TmpNode& c = T[kids[k]];
+			nd.lo[0][k] = c.box.mn.x; nd.lo[1][k] = c.box.mn.y; nd.lo[2][k] = c.box.mn.z;
+			nd.hi[0][k] = c.box.mx.x; nd.hi[1][k] = c.box.mx.y; nd.hi[2][k] = c.box.mx.z;
+			if (c.left < 0) nd.child[k] = leafCode[kids[k]];
+			else {
+				const int32_t slot = (int32_t)out.nodes4.size();
+				out.nodes4.emplace_back();
+				nd.child[k] = slot;
+				work.push_back({ kids[k], slot, need });
+			}
+		}
+		out.nodes4[it.slot] = nd;
+	}
+	out.stackNeed4 = needMax; out.sahNodes4 = (float)sah4;
+}
+
+// ---- the leaf list: a scene that 4 * RL_LEAFLIST_RECORDS leaves of <= 8 triangles can hold is walked without a tree ----
+// Every ray tests every leaf's box once (4 records of 4 boxes, in lockstep across a wave: no stack, no divergence), then visits the
+// leaves it touched nearest first.  In a tree this small a wave's rays take different turns at every node, and the wave pays for
+// the union of their walks (Cornell frame: 10 node steps per wave and bounce for 3.5 per ray).  The leaves are a cut through the
+// SAH tree: starting from the root, the sub-tree with the largest area x triangle count is opened until the list is full or only the tree's own leaves are left.
+// Up to 4.5 triangles per leaf on average: beyond, the leaves of the cut grow towards 8 triangles and the tree wins again (tools/gpu_leaflist.py,
+// leaf list / BVH4 walk, first version: 36 triangles 0.86, 72: 0.92, 84: 0.88, 96: 0.89, 108: 0.90, 120 (8-triangle leaves): 1.05; final version: 0.79, 0.80, 0.79,
+// 0.77, 0.78 -- the limit is also what the kernel's LDS layout holds, rl_device.h RL_LEAFLIST_MAXTRIS).
+// Reads T and the leaf references of a scene of at most RL_LEAFLIST_MAXTRIS triangles, whose slots are in depth-first order (every sub-tree's triangles are
+// one range of slots); writes out.leafList, or leaves it empty where no cut fits.
+void EmitLeafList(const std::vector<TmpNode>& T, int32_t root, const std::vector<int32_t>& leafCode, BVH& out)
+{
+	std::vector<uint32_t> triFirst(T.size(), 0), triCount(T.size(), 0);
+	for (size_t t = T.size(); t-- > 0;) {   // children follow their parent in T (pre-order): a reverse sweep sees them first
+		if (T[t].left < 0) { triFirst[t] = ((uint32_t)~leafCode[t]) >> 6; triCount[t] = T[t].count; }
+		else { triFirst[t] = triFirst[T[t].left]; triCount[t] = triCount[T[t].left] + triCount[T[t].right]; }
+	}
+	std::vector<int32_t> cut; cut.push_back(root);
+	for (;;) {
+		int best = -1; double bestCost = -1.0; bool bestOver = false;
+		for (size_t k = 0; k < cut.size(); ++k) {
+			const int32_t t = cut[k];
+			if (T[t].left < 0) continue;
+			const bool over = triCount[t] > 8;   // too large for one leaf: goes first
+			const double cost = ((double)T[t].box.halfArea() + 1e-30) * triCount[t];
+			if (best < 0 || (over && !bestOver) || (over == bestOver && cost > bestCost)) { bestCost = cost; best = (int)k; bestOver = over; }
+		}
+		if (best < 0 || (cut.size() >= kLeafListMax && !bestOver)) break;
+		if (cut.size() >= kLeafListMax) { cut.clear(); break; }   // does not fit
+		const int32_t open = cut[(size_t)best];
+		cut[(size_t)best] = T[open].left; cut.push_back(T[open].right);
+	}
+	bool fits = !cut.empty();
+	for (int32_t t : cut) if (triCount[t] > 8) fits = false;
+	if (!fits) return;
+	out.leafList.assign((cut.size() + 3) / 4, DNode4());
+	for (DNode4& nd : out.leafList) {
+		memset(&nd, 0, sizeof(nd));
+		// an unused slot is the box [+inf, -inf]: whatever the ray, one of its axes enters it at +inf (rl_dev_walk.h TraverseLeafList has no other test for it)
+		for (int k = 0; k < 4; ++k) { nd.lo[0][k] = nd.lo[1][k] = nd.lo[2][k] = INFINITY; nd.hi[0][k] = nd.hi[1][k] = nd.hi[2][k] = -INFINITY; nd.child[k] = DNODE_EMPTY; }
+	}
+	for (size_t at = 0; at < cut.size(); ++at) {
+		const int32_t t = cut[at];
+		DNode4& nd = out.leafList[at / 4]; const int k = (int)(at % 4);
+		nd.lo[0][k] = T[t].box.mn.x; nd.lo[1][k] = T[t].box.mn.y; nd.lo[2][k] = T[t].box.mn.z;
+		nd.hi[0][k] = T[t].box.mx.x; nd.hi[1][k] = T[t].box.mx.y; nd.hi[2][k] = T[t].box.mx.z;
+		nd.child[k] = leafRef(triFirst[t], PRIM_TRIANGLE, triCount[t]);
+	}
+}
+
+} // namespace
+
+// Leaf references keep the first primitive slot in 25 bits (DNode, rl_device.h): more primitives than that cannot be addressed.
+bool BVHCapacityOk(size_t numPrimitives) { return numPrimitives < ((size_t)1 << 25); }
+
+void BuildBVH(const std::vector<PrimRef>& prims, BVH& out, const BVHBuildOptions& opt)
+{
+	// (sahNodes4 and sahNodes8 are written only with their trees: a scene rebuilt without them keeps the figures of its last build with them)
+	out.nodes.clear(); out.nodes4.clear(); out.nodes4q.clear(); out.nodes8.clear(); out.depth8 = 0; out.leafList.clear(); out.stackNeed4 = 0; out.triOrder.clear(); out.depth = 0; out.sahCost = 0.0f;
+	const uint32_t n = (uint32_t)prims.size();
+	if (n == 0) {
+		Box empty; empty.reset();
+		DNode root; memset(&root, 0, sizeof(root));
+		storeBox(root.lmin, root.lmax, empty); storeBox(root.rmin, root.rmax, empty);
+		root.left = root.right = DNODE_EMPTY;
+		out.nodes.push_back(root);
+		return;
+	}
+	Shared B;
+	std::vector<TmpNode> T;
+	const int32_t root = BuildBinary(prims, B, T);
+
+	// Triangle-only scenes of at least 8 triangles get the wide trees; the 8-wide one decides the order of the triangle slots (the leaf children of one of its
+	// nodes hold consecutive slots), every other format refers to the same slots through its leaf references.
+	bool trianglesOnly = true;
+	for (uint32_t i = 0; i < n && trianglesOnly; ++i) if (prims[i].kind != PRIM_TRIANGLE) trianglesOnly = false;
+	const bool wideTrees = n >= 8 && trianglesOnly && T[root].left >= 0;
+	// (not for the scenes small enough for the leaf list: its leaves are sub-trees of this tree, whose triangles must stay one range of slots -- the depth-first order)
+	const bool wide8 = wideTrees && n > RL_LEAFLIST_MAXTRIS;
+	Wide8 W8;
+	if (wide8) {
+		// leaves split for the 8-wide plan (SplitLeaves) where that tree is the one the scene's rays will walk
+		if (!opt.wideGreedy && opt.splitLeaves8 && ExpectedSteps4(T, root) >= opt.minSteps8) SplitLeaves(T, B);
+		CollapseWide8(T, root, W8, opt.wideGreedy, opt.triCost8);
+	}
+	const std::vector<int32_t> leafCode = AssignLeafSlots(T, B, prims, wide8 ? &W8.leafOrder : nullptr, out.triOrder);
+	EmitBinary(T, root, leafCode, out);
+	if (!wideTrees) return;
+	if (wide8) EmitWide8(T, W8, leafCode, out);
+	EmitWide4(T, root, leafCode, out);
+	QuantizeWide(out);
+	if (n <= RL_LEAFLIST_MAXTRIS) EmitLeafList(T, root, leafCode, out);
+}
+
+namespace {
+
+inline bool inside(const f3& p, const f3& mn, const f3& mx) { return p.x >= mn.x && p.y >= mn.y && p.z >= mn.z && p.x <= mx.x && p.y <= mx.y && p.z <= mx.z; }
+inline uint32_t leafKind(int32_t ref) { return ((uint32_t)~ref >> 4) & 3u; }
+// the triangle leaf `ref`: every slot in range, every triangle met for the first time (seen), all three vertices inside the box [mn, mx]
+bool LeafTrianglesInside(const BVH& bvh, const std::vector<HostTriangle>& tris, int32_t ref, const f3& mn, const f3& mx, std::vector<uint8_t>& seen)
+{
+	const uint32_t code = (uint32_t)~ref, first = code >> 6, count = (code & 7u) + 1;
+	for (uint32_t k = 0; k < count; ++k) {
+		if (first + k >= bvh.triOrder.size()) return false;
+		const uint32_t ti = bvh.triOrder[first + k];
+		if (ti >= tris.size() || seen[ti]) return false;
+		seen[ti] = 1;
+		const HostTriangle& t = tris[ti];
+		if (!inside(t.v0, mn, mx) || !inside(t.v1, mn, mx) || !inside(t.v2, mn, mx)) return false;
+	}
+	return true;
+}
+
+// The grid nodes' box arithmetic as the device does it (rl_dev_pool.h NodeStep4 / NodeStep8), operation by operation in float.  Per axis a ray meets plane q
+// of a node's grid at q * A + B, with A = step * inv and B = (origin - o) * inv; E bounds what rounding can have moved that distance by, so entry distances
+// are taken E early and exit distances E late.  Bn = B - E is what the 4-wide grid walk adds to q * A for the entry distance; the 8-wide step keeps the
+// NEGATED entry distance and adds nB = E - B to q * -A -- computed as the device computes it, not as -Bn (a zero's sign reaches the step's sign test).
+constexpr float kGridErrA = 1.21593475e-4f;   // 255 * 2^-21: the rounding of q * A, q <= 255
+constexpr float kGridErrB = 4.76837158e-7f;   // 2^-21: the rounding of B
+struct GridFactors { float A[3], Bn[3], nB[3], Bf[3]; };
+inline GridFactors MakeGridFactors(const float step[3], const float origin[3], const float o[3], const float inv[3])
+{
+	GridFactors F;
+	for (int a = 0; a < 3; ++a) {
+		F.A[a] = step[a] * inv[a];
+		const float B = (origin[a] - o[a]) * inv[a];
+		const float E = fabsf(F.A[a] * kGridErrA) + fabsf(B * kGridErrB);
+		F.Bn[a] = B - E; F.nB[a] = E - B; F.Bf[a] = B + E;
+	}
+	return F;
+}
+inline float clampInv(float x) { return std::isinf(x) ? copysignf(1e30f, x) : x; }   // the grid walks' reciprocal of a direction component that is zero
+constexpr float kBoxWiden = 1.00001f;   // RL_BOX_WIDEN
+
+// One 8-wide node against one ray (NodeStep8): the steps are the powers of two whose exponents the node holds, one fma per 8-bit plane, the negated entry
+// distance (least of ntMin and the planes'), the exit distance (least of tmx and the planes'), and a child is hit where fma(exit, widen, -entry) is not
+// negative.  neg[a]: the ray runs down axis a (it enters at the upper plane).  Returns the mask of hit children, by slot.
+uint32_t Step8Host(const DNode8& nd, const float o[3], const float inv[3], const bool neg[3], float ntMin, float tmx)
+{
+	float step[3];
+	for (int a = 0; a < 3; ++a) { const uint32_t sb = ((nd.meta >> (8 * a)) & 255u) << 23; memcpy(&step[a], &sb, 4); }
+	const GridFactors F = MakeGridFactors(step, nd.origin, o, inv);
+	auto plane = [](const uint32_t q[2], int c) { return (float)((q[c >> 2] >> (8 * (c & 3))) & 255u); };
+	uint32_t hit = 0;
+	for (int ch = 0; ch < 8; ++ch) {
+		float ntn = ntMin, tf = tmx;
+		for (int a = 0; a < 3; ++a) {
+			const float qn = plane(neg[a] ? nd.qhi[a] : nd.qlo[a], ch), qf = plane(neg[a] ? nd.qlo[a] : nd.qhi[a], ch);
+			ntn = std::min(ntn, fmaf(qn, -F.A[a], F.nB[a])); tf = std::min(tf, fmaf(qf, F.A[a], F.Bf[a]));
+		}
+		if (!std::signbit(fmaf(tf, kBoxWiden, ntn))) hit |= 1u << ch;
+	}
+	return hit;
+}
+// the hit inner children of a node as the next group's bits 24 ... 31: in visiting order, slot XOR octant
+inline uint32_t InnerInVisitOrder(uint32_t hitInner, uint32_t oct) { uint32_t p = 0; for (uint32_t b = 0; b < 8u; ++b) if ((hitInner >> b) & 1u) p |= 1u << (b ^ oct); return p; }
+// leaf child ch of an 8-wide node: the number of its triangles, and in `first` their first slot
+inline uint32_t Leaf8(const DNode8& nd, uint32_t ch, uint32_t& first)
+{
+	first = nd.triBase + (uint32_t)__builtin_popcount(nd.leafMask & ((1u << (4 * ch)) - 1u));
+	return (uint32_t)__builtin_popcount((nd.leafMask >> (4 * ch)) & 15u);
+}
+
+} // namespace
 
 bool ValidateBVH(const BVH& bvh, const std::vector<HostTriangle>& tris)
 {
@@ -805,23 +889,12 @@ bool ValidateBVH(const BVH& bvh, const std::vector<HostTriangle>& tris)
 	const DNode& r = bvh.nodes[0];
 	st.push_back({ r.left, F3(r.lmin[0], r.lmin[1], r.lmin[2]), F3(r.lmax[0], r.lmax[1], r.lmax[2]) });
 	st.push_back({ r.right, F3(r.rmin[0], r.rmin[1], r.rmin[2]), F3(r.rmax[0], r.rmax[1], r.rmax[2]) });
-	auto inside = [](const f3& p, const f3& mn, const f3& mx) {
-		return p.x >= mn.x && p.y >= mn.y && p.z >= mn.z && p.x <= mx.x && p.y <= mx.y && p.z <= mx.z;
-	};
 	while (!st.empty()) {
 		Item it = st.back(); st.pop_back();
 		if (it.ref == DNODE_EMPTY) continue;
 		if (it.ref < 0) {
-			uint32_t code = (uint32_t)~it.ref, first = code >> 6, count = (code & 7u) + 1;
-			if (((code >> 4) & 3u) != PRIM_TRIANGLE) continue;   // analytic primitive: nothing to check against triangles
-			for (uint32_t k = 0; k < count; ++k) {
-				if (first + k >= bvh.triOrder.size()) return false;
-				uint32_t ti = bvh.triOrder[first + k];
-				if (ti >= tris.size() || seen[ti]) return false;
-				seen[ti] = 1;
-				const HostTriangle& t = tris[ti];
-				if (!inside(t.v0, it.mn, it.mx) || !inside(t.v1, it.mn, it.mx) || !inside(t.v2, it.mn, it.mx)) return false;
-			}
+			if (leafKind(it.ref) != PRIM_TRIANGLE) continue;   // analytic primitive: nothing to check against triangles
+			if (!LeafTrianglesInside(bvh, tris, it.ref, it.mn, it.mx, seen)) return false;
 			continue;
 		}
 		if ((size_t)it.ref >= bvh.nodes.size()) return false;
@@ -846,22 +919,10 @@ bool ValidateBVH4(const BVH& bvh, const std::vector<HostTriangle>& tris)
 	struct Item { int32_t ref; f3 mn, mx; uint32_t need; bool haveBox; };
 	std::vector<Item> st;
 	st.push_back({ 0, F3(0, 0, 0), F3(0, 0, 0), 0u, false });
-	auto inside = [](const f3& p, const f3& mn, const f3& mx) {
-		return p.x >= mn.x && p.y >= mn.y && p.z >= mn.z && p.x <= mx.x && p.y <= mx.y && p.z <= mx.z;
-	};
 	while (!st.empty()) {
 		const Item it = st.back(); st.pop_back();
 		if (it.ref < 0) {
-			const uint32_t code = (uint32_t)~it.ref, first = code >> 6, count = (code & 7u) + 1;
-			if (((code >> 4) & 3u) != PRIM_TRIANGLE) return false;
-			for (uint32_t k = 0; k < count; ++k) {
-				if (first + k >= bvh.triOrder.size()) return false;
-				const uint32_t ti = bvh.triOrder[first + k];
-				if (ti >= tris.size() || seen[ti]) return false;
-				seen[ti] = 1;
-				const HostTriangle& t = tris[ti];
-				if (!inside(t.v0, it.mn, it.mx) || !inside(t.v1, it.mn, it.mx) || !inside(t.v2, it.mn, it.mx)) return false;
-			}
+			if (leafKind(it.ref) != PRIM_TRIANGLE || !LeafTrianglesInside(bvh, tris, it.ref, it.mn, it.mx, seen)) return false;   // (no analytic primitive in a wide tree)
 			continue;
 		}
 		if ((size_t)it.ref >= bvh.nodes4.size()) return false;
@@ -903,17 +964,8 @@ bool ValidateBVH4(const BVH& bvh, const std::vector<HostTriangle>& tris)
 				continue;
 			}
 			if (n.child[k] >= 0) return false;
-			const uint32_t code = (uint32_t)~n.child[k], first = code >> 6, count = (code & 7u) + 1;
-			if (((code >> 4) & 3u) != PRIM_TRIANGLE) return false;
 			const f3 mn = F3(n.lo[0][k], n.lo[1][k], n.lo[2][k]), mx = F3(n.hi[0][k], n.hi[1][k], n.hi[2][k]);
-			for (uint32_t i = 0; i < count; ++i) {
-				if (first + i >= bvh.triOrder.size()) return false;
-				const uint32_t ti = bvh.triOrder[first + i];
-				if (ti >= tris.size() || seen[ti]) return false;
-				seen[ti] = 1;
-				const HostTriangle& t = tris[ti];
-				if (!inside(t.v0, mn, mx) || !inside(t.v1, mn, mx) || !inside(t.v2, mn, mx)) return false;
-			}
+			if (leafKind(n.child[k]) != PRIM_TRIANGLE || !LeafTrianglesInside(bvh, tris, n.child[k], mn, mx, seen)) return false;
 		}
 		for (uint8_t v : seen) if (!v) return false;
 	}
@@ -972,7 +1024,7 @@ bool ValidateBVH8(const BVH& bvh, const std::vector<HostTriangle>& tris)
 			continue;
 		}
 		if (nib != 1u && nib != 3u && nib != 7u && nib != 15u) return false;
-		const uint32_t first = n.triBase + (uint32_t)__builtin_popcount(n.leafMask & ((1u << (4 * c)) - 1u)), count = (uint32_t)__builtin_popcount(nib);
+		uint32_t first; const uint32_t count = Leaf8(n, (uint32_t)c, first);
 		double glo[3], ghi[3]; gridBox(n, c, glo, ghi);
 		for (uint32_t k = 0; k < count; ++k) {
 			if (first + k >= bvh.triOrder.size() || seen[first + k]) return false;
@@ -1002,9 +1054,6 @@ bool ValidateBVH8(const BVH& bvh, const std::vector<HostTriangle>& tris)
 bool Walk8Host(const BVH& bvh, const std::vector<HostTriangle>& tris, const float* rays, int n, float tMin, const float* tMax, float* outT, uint32_t* outSteps)
 {
 	if (bvh.nodes8.empty()) return false;
-	const float widen = 1.00001f;
-	auto clampInv = [](float x) { return std::isinf(x) ? copysignf(1e30f, x) : x; };
-	auto plane = [](const uint32_t q[2], int c) { return (float)((q[c >> 2] >> (8 * (c & 3))) & 255u); };
 	for (int r = 0; r < n; ++r) {
 		const float* ray = rays + 6 * (size_t)r;
 		const float o[3] = { ray[0], ray[1], ray[2] }, d[3] = { ray[3], ray[4], ray[5] };
@@ -1020,35 +1069,15 @@ bool Walk8Host(const BVH& bvh, const std::vector<HostTriangle>& tris, const floa
 			gy &= ~(1u << pos);
 			const uint32_t slot = (pos - 24u) ^ oct;
 			const uint32_t node = gx + (uint32_t)__builtin_popcount(gy & 0xffu & ((1u << slot) - 1u));
-			if ((gy >> 24) != 0u) stack.push_back({ gx, gy });
+			if ((gy >> 24) != 0u) stack.push_back({ gx, gy });   // (every group is kept -- a walk past 64 of them is refused --, where WalkStackHost drops the pushes its capacity cannot hold)
 			if (node >= bvh.nodes8.size() || stack.size() > 64) return false;
 			const DNode8& nd = bvh.nodes8[node];
 			++steps;
-			float A[3], nB[3], Bf[3];
-			for (int a = 0; a < 3; ++a) {
-				uint32_t sb = ((nd.meta >> (8 * a)) & 255u) << 23; float st; memcpy(&st, &sb, 4);
-				A[a] = st * inv[a];
-				const float B = (nd.origin[a] - o[a]) * inv[a];
-				const float E = fabsf(A[a] * 1.21593475e-4f) + fabsf(B * 4.76837158e-7f);
-				nB[a] = E - B; Bf[a] = B + E;
-			}
-			uint32_t hit = 0;
-			const uint32_t imask = nd.meta >> 24;
-			for (int ch = 0; ch < 8; ++ch) {
-				float ntn = ntMin, tf = tmx;
-				for (int a = 0; a < 3; ++a) {
-					const float qn = plane(neg[a] ? nd.qhi[a] : nd.qlo[a], ch), qf = plane(neg[a] ? nd.qlo[a] : nd.qhi[a], ch);
-					ntn = std::min(ntn, fmaf(qn, -A[a], nB[a])); tf = std::min(tf, fmaf(qf, A[a], Bf[a]));
-				}
-				if (!std::signbit(fmaf(tf, widen, ntn))) hit |= 1u << ch;
-			}
-			uint32_t innerP = 0;
-			for (uint32_t b = 0; b < 8u; ++b) if (((hit & imask) >> b) & 1u) innerP |= 1u << (b ^ oct);
+			const uint32_t imask = nd.meta >> 24, hit = Step8Host(nd, o, inv, neg, ntMin, tmx);   // (the exit distance stays tMax[r]: no hit shortens this walk)
 			for (uint32_t ch = 0; ch < 8u; ++ch) {
 				if (!((hit & ~imask) >> ch & 1u)) continue;
-				const uint32_t nib = (nd.leafMask >> (4 * ch)) & 15u;
-				const uint32_t first = nd.triBase + (uint32_t)__builtin_popcount(nd.leafMask & ((1u << (4 * ch)) - 1u));
-				for (uint32_t k = 0; k < (uint32_t)__builtin_popcount(nib); ++k) {
+				uint32_t first; const uint32_t count = Leaf8(nd, ch, first);
+				for (uint32_t k = 0; k < count; ++k) {
 					if (first + k >= bvh.triOrder.size()) return false;
 					const HostTriangle& t = tris[bvh.triOrder[first + k]];
 					// tolerant double-precision test (edges and vertices count as inside by 1e-6): a superset of what the reference's float test accepts
@@ -1065,7 +1094,7 @@ bool Walk8Host(const BVH& bvh, const std::vector<HostTriangle>& tris, const floa
 					if (u >= -1e-6 && v >= -1e-6 && u + v <= 1.0 + 1e-6 && tt >= (double)tMin * 0.999 && tt < best) best = tt;
 				}
 			}
-			gx = nd.childBase; gy = (innerP << 24) | imask;
+			gx = nd.childBase; gy = (InnerInVisitOrder(hit & imask, oct) << 24) | imask;
 		}
 		outT[r] = best >= (double)FLT_MAX ? FLT_MAX : (float)best;
 		if (outSteps) outSteps[r] = steps;
@@ -1086,8 +1115,7 @@ bool WalkStackHost(const BVH& bvh, const std::vector<HostTriangle>& tris, const 
 {
 	if (capacity < 0 || (tree != 2 && tree != 3 && tree != 4 && tree != 8)) return false;
 	if (tree == 2 ? bvh.nodes.empty() : tree == 3 ? bvh.nodes4.empty() : tree == 4 ? bvh.nodes4q.empty() : bvh.nodes8.empty()) return false;
-	const float widen = 1.00001f, slack = 1.000009f;   // RL_BOX_WIDEN, RL_CANDIDATE_SLACK
-	auto clampInv = [](float x) { return std::isinf(x) ? copysignf(1e30f, x) : x; };
+	const float widen = kBoxWiden, slack = 1.000009f;   // RL_BOX_WIDEN, RL_CANDIDATE_SLACK
 	for (int r = 0; r < n; ++r) {
 		const float* ray = rays + 6 * (size_t)r;
 		const f3 o = F3(ray[0], ray[1], ray[2]), d = F3(ray[3], ray[4], ray[5]);
@@ -1130,18 +1158,19 @@ bool WalkStackHost(const BVH& bvh, const std::vector<HostTriangle>& tris, const 
 			for (;;) {
 				while (cur >= 0 && cur != DONE) {
 					const float tmx = fminf(best, FLT_MAX);
+					// the float boxes (trees 2 and 3): the exact reciprocals
+					auto slab = [&](const float* mn, const float* mx, float& tNear) {
+						float tn = tMin, tf = tmx;
+						for (int a = 0; a < 3; ++a) {
+							const bool neg = inv[a] < 0.0f;
+							tn = fmaxf(tn, ((neg ? mx[a] : mn[a]) - oa[a]) * inv[a]); tf = fminf(tf, ((neg ? mn[a] : mx[a]) - oa[a]) * inv[a]);
+						}
+						tNear = tn;
+						return !(tf * widen < tn);
+					};
 					if (tree == 2) {
 						if ((size_t)cur >= bvh.nodes.size()) return false;
 						const DNode& nd = bvh.nodes[(size_t)cur];
-						auto slab = [&](const float* mn, const float* mx, float& tNear) {
-							float tn = tMin, tf = tmx;
-							for (int a = 0; a < 3; ++a) {
-								const bool neg = inv[a] < 0.0f;
-								tn = fmaxf(tn, ((neg ? mx[a] : mn[a]) - oa[a]) * inv[a]); tf = fminf(tf, ((neg ? mn[a] : mx[a]) - oa[a]) * inv[a]);
-							}
-							tNear = tn;
-							return !(tf * widen < tn);
-						};
 						float tl, tr;
 						const bool hl = slab(nd.lmin, nd.lmax, tl) && nd.left != DNODE_EMPTY, hr = slab(nd.rmin, nd.rmax, tr) && nd.right != DNODE_EMPTY;
 						if (hl && hr) { const bool leftFirst = tl <= tr; push(leftFirst ? nd.right : nd.left); cur = leftFirst ? nd.left : nd.right; }
@@ -1155,31 +1184,23 @@ bool WalkStackHost(const BVH& bvh, const std::vector<HostTriangle>& tris, const 
 							if ((size_t)cur >= bvh.nodes4.size()) return false;
 							const DNode4& nd = bvh.nodes4[(size_t)cur];
 							for (int k = 0; k < 4; ++k) {
-								float tn = tMin, tf = tmx;
-								for (int a = 0; a < 3; ++a) {
-									const bool neg = inv[a] < 0.0f;
-									tn = fmaxf(tn, ((neg ? nd.hi[a][k] : nd.lo[a][k]) - oa[a]) * inv[a]); tf = fminf(tf, ((neg ? nd.lo[a][k] : nd.hi[a][k]) - oa[a]) * inv[a]);
-								}
+								const float mn[3] = { nd.lo[0][k], nd.lo[1][k], nd.lo[2][k] }, mx[3] = { nd.hi[0][k], nd.hi[1][k], nd.hi[2][k] };
+								float tn;
+								const bool hitBox = slab(mn, mx, tn);
 								c[k] = nd.child[k];
-								t[k] = (tf * widen < tn || c[k] == DNODE_EMPTY) ? INFINITY : tn;
+								t[k] = (!hitBox || c[k] == DNODE_EMPTY) ? INFINITY : tn;
 							}
 						} else {
 							if ((size_t)cur >= bvh.nodes4q.size()) return false;
 							const DNode4Q& nd = bvh.nodes4q[(size_t)cur];
 							const float step[3] = { nd.stepX, nd.stepY, nd.stepZ };
-							float A[3], Bn[3], Bf[3];
-							for (int a = 0; a < 3; ++a) {
-								A[a] = step[a] * invc[a];
-								const float B = (nd.origin[a] - oa[a]) * invc[a];
-								const float E = fabsf(A[a] * 1.21593475e-4f) + fabsf(B * 4.76837158e-7f);
-								Bn[a] = B - E; Bf[a] = B + E;
-							}
+							const GridFactors F = MakeGridFactors(step, nd.origin, oa, invc);
 							for (int k = 0; k < 4; ++k) {
 								float tn = tMin, tf = tmx;
 								for (int a = 0; a < 3; ++a) {
 									const bool neg = invc[a] < 0.0f;
 									const uint32_t qn = ((neg ? nd.qhi[a] : nd.qlo[a]) >> (8 * k)) & 0xffu, qf = ((neg ? nd.qlo[a] : nd.qhi[a]) >> (8 * k)) & 0xffu;
-									tn = fmaxf(tn, fmaf((float)qn, A[a], Bn[a])); tf = fminf(tf, fmaf((float)qf, A[a], Bf[a]));
+									tn = fmaxf(tn, fmaf((float)qn, F.A[a], F.Bn[a])); tf = fminf(tf, fmaf((float)qf, F.A[a], F.Bf[a]));
 								}
 								c[k] = nd.child[k];
 								t[k] = (tf * widen < tn || c[k] == DNODE_EMPTY) ? INFINITY : tn;
@@ -1224,7 +1245,6 @@ bool WalkStackHost(const BVH& bvh, const std::vector<HostTriangle>& tris, const 
 				cur = stk[(size_t)--sp];
 			}
 		} else {
-			auto plane = [](const uint32_t q[2], int c) { return (float)((q[c >> 2] >> (8 * (c & 3))) & 255u); };
 			bool neg[3]; uint32_t oct = 0;
 			for (int a = 0; a < 3; ++a) { neg[a] = invc[a] < 0.0f; if (!neg[a]) oct |= 1u << a; }
 			const float ntMin = -tMin;
@@ -1239,35 +1259,14 @@ bool WalkStackHost(const BVH& bvh, const std::vector<HostTriangle>& tris, const 
 				if ((gy >> 24) != 0u && stack.size() < (size_t)capacity) { stack.push_back({ gx, gy }); high = std::max(high, (uint32_t)stack.size()); }   // Push8: sp < GMAX
 				if (node >= bvh.nodes8.size()) return false;
 				const DNode8& nd = bvh.nodes8[node];
-				const float tmx = fminf(best, FLT_MAX);
-				float A[3], nB[3], Bf[3];
-				for (int a = 0; a < 3; ++a) {
-					uint32_t sb = ((nd.meta >> (8 * a)) & 255u) << 23; float st; memcpy(&st, &sb, 4);
-					A[a] = st * invc[a];
-					const float B = (nd.origin[a] - oa[a]) * invc[a];
-					const float E = fabsf(A[a] * 1.21593475e-4f) + fabsf(B * 4.76837158e-7f);
-					nB[a] = E - B; Bf[a] = B + E;
-				}
-				uint32_t hit = 0;
-				const uint32_t imask = nd.meta >> 24;
-				for (int ch = 0; ch < 8; ++ch) {
-					float ntn = ntMin, tf = tmx;
-					for (int a = 0; a < 3; ++a) {
-						const float qn = plane(neg[a] ? nd.qhi[a] : nd.qlo[a], ch), qf = plane(neg[a] ? nd.qlo[a] : nd.qhi[a], ch);
-						ntn = std::min(ntn, fmaf(qn, -A[a], nB[a])); tf = std::min(tf, fmaf(qf, A[a], Bf[a]));
-					}
-					if (!std::signbit(fmaf(tf, widen, ntn))) hit |= 1u << ch;
-				}
-				uint32_t innerP = 0;
-				for (uint32_t b = 0; b < 8u; ++b) if (((hit & imask) >> b) & 1u) innerP |= 1u << (b ^ oct);
+				const uint32_t imask = nd.meta >> 24, hit = Step8Host(nd, oa, invc, neg, ntMin, fminf(best, FLT_MAX));   // (the exit distance shrinks with the best hit)
 				// the triangles of the hit leaf children, before any inner child is entered (Next8)
 				for (uint32_t ch = 0; ch < 8u; ++ch) {
 					if (!((hit & ~imask) >> ch & 1u)) continue;
-					const uint32_t nib = (nd.leafMask >> (4 * ch)) & 15u;
-					const uint32_t first = nd.triBase + (uint32_t)__builtin_popcount(nd.leafMask & ((1u << (4 * ch)) - 1u));
-					for (uint32_t k = 0; k < (uint32_t)__builtin_popcount(nib); ++k) if (!triangle(first + k)) return false;
+					uint32_t first; const uint32_t count = Leaf8(nd, ch, first);
+					for (uint32_t k = 0; k < count; ++k) if (!triangle(first + k)) return false;
 				}
-				gx = nd.childBase; gy = (innerP << 24) | imask;
+				gx = nd.childBase; gy = (InnerInVisitOrder(hit & imask, oct) << 24) | imask;
 			}
 		}
 		outT[r] = best;
