@@ -209,6 +209,70 @@ RAYLIB_API int32_t RaylibAMD_TraceRadianceDevice(SceneHandle scene, const Raylib
  * calls above would refuse.  `early` is 0. */
 RAYLIB_API int32_t RaylibAMD_PlanRadiance(SceneHandle scene, const RaylibAMDRadianceParams* params, RaylibAMDQueryPlan* out);
 
+/* ---- irradiance and SH probes gathered at caller points ---------------------------------------------
+ * What a lightmap or probe baker does with RaylibAMD_TraceRadiance -- radiance integrated over a hemisphere or a sphere of directions at every point -- with the
+ * directions drawn on the device, n x sampleCount paths dealt to the lanes as (point, sample) pairs (1 point x 65536 samples fills the device as 65536 points
+ * x 1 sample do), and the mean and the projection taken there: no ray record is materialised and none of the sampling is restated on the host.
+ * Everything is float, without FMA.  Sample s of point i draws from the stream (RaylibAMD_GetSeed() at the call, points[i].stream, sampleFirst + s) after
+ * skipDraws draws have been discarded:
+ *   1. Direction.  w = RandomInUnitSphere(stream): two draws u1, u2; z = 1 - 2 u1, r = sqrt(max(0, 1 - z z)), phi = 2 * 3.141592f * u2, w = (r cos phi, r sin phi, z).
+ *        IRRADIANCE: if ((double)dot(w, N) < 0.0) w = -w; Wi = normalize(w) -- the Lambertian material's three statements (RaylibAMD_EvalScatter is its oracle).
+ *        SH9:        Wi = normalize(w); the normal is ignored.
+ *      (dot(a, b) = a.x b.x + a.y b.y + a.z b.z summed left to right; normalize(w) = w * (1.0f / sqrt(dot(w, w))).)
+ *   2. Radiance.  L = TraceScene(ray(pos, Wi, time), depth 0, maxPathLength, rayTMin), the bounces taking the stream's next draws: bit for bit the sample
+ *      RaylibAMD_TraceRadiance returns for the ray (pos, Wi, time, stream) with skipDraws + 2, sampleFirst + s and sampleCount 1.
+ *   3. Sample value.  IRRADIANCE: v = L * fmaxf(0.0f, dot(N, Wi)).  SH9: v_j = L * Y_j, with x, y, z = Wi and
+ *        Y0 = 0.282095f              Y1 = 0.488603f*y            Y2 = 0.488603f*z                          Y3 = 0.488603f*x         Y4 = 1.092548f*(x*y)
+ *        Y5 = 1.092548f*(y*z)        Y6 = 0.315392f*(3.0f*(z*z) - 1.0f)                                    Y7 = 1.092548f*(x*z)     Y8 = 0.546274f*(x*x - y*y)
+ *   4. Result.  The sum of the values in sample order, from +0; times 1.0f / (float)sampleCount; times the solid angle of the directions' domain: 6.2831855f
+ *      (bits 0x40C90FDB) for IRRADIANCE, 12.566371f (bits 0x41490FDB) for SH9.  The directions are uniform on the hemisphere about N or on the sphere, so
+ *      IRRADIANCE is the irradiance estimate and SH9 holds the radiance's coefficients in the real orthonormal basis above.
+ * The result does not depend on how the call is cut into launches (below). */
+typedef struct RaylibAMDGatherPoint {   /* 32 bytes; on the device entry an array of them must be 16-byte aligned */
+	float pos[3];    float time;        /* as RaylibAMDPathRay.org / .time */
+	float normal[3]; uint32_t stream;   /* the normal is used as given, not normalised; stream stands where the contract has the pixel index */
+} RaylibAMDGatherPoint;
+#define RAYLIB_AMD_GATHER_IRRADIANCE 0  /* out: 4 floats per point (E.r, E.g, E.b, 1) */
+#define RAYLIB_AMD_GATHER_SH9        1  /* out: 27 floats per point, out[27*i + 3*j + c], j = 0..8, c = r,g,b */
+typedef struct RaylibAMDGatherParams {
+	int32_t  kind;                                     /* RAYLIB_AMD_GATHER_* */
+	int32_t  maxPathLength; float rayTMin;             /* as RaylibAMDRadianceParams; maxPathLength 0: zeros (and alpha 1 for IRRADIANCE) */
+	uint32_t sampleFirst, sampleCount, skipDraws;      /* skipDraws <= 62 (the direction's two draws follow them) */
+	float    timeMin, timeMax;                         /* device entry only, as for radiance */
+} RaylibAMDGatherParams;
+/* n points from host memory, n x 4 or n x 27 floats to host memory; synchronous.  Returns 1 (n == 0 included), or 0 with nothing written for what
+ * RaylibAMD_TraceRadiance refuses (a point's time standing for a ray's), an unknown kind or skipDraws > 62; n == 0 is a success without a device too.  The tree and the kernel instance are those of
+ * RaylibAMD_PlanRadiance, which answers for a gather too.  RaylibAMD_GetLastStats reports what a radiance call reports, with cameraSamples = n x sampleCount,
+ * traceLaunches = the trace launches made, traceKernelMs their time and kernelMs the whole call's -- the resolves, the per-launch clearing of the ray counter
+ * and the gaps between the kernels included (calls of more than 4096 launches: both the whole call's). */
+RAYLIB_API int32_t RaylibAMD_Gather(SceneHandle scene, const RaylibAMDGatherParams* params, const RaylibAMDGatherPoint* points, int32_t n, float* out);
+/* The same on device pointers and a stream, under the rules of RaylibAMD_TraceRadianceDevice: points 16-byte aligned; out 16-byte aligned for IRRADIANCE, 4-byte
+ * for SH9.  Scratch: the radiance calls' counter and path stack, under the same event chain -- gather and radiance calls run one after the other on the
+ * device -- and a sample buffer (16 bytes per (point, sample) pair of a launch for IRRADIANCE, 32 for SH9) held to 256 MiB, with 3 or 27 floats of running sums
+ * per point of a launch.  A call with more pairs than the buffer holds runs as several launches over sample ranges, and over point ranges as well when one
+ * sample of every point does not fit; the sums carry from launch to launch, so the order of the sum is kept.  RAYLIB_GATHER_BATCH=<slots> (read at every
+ * call) sets the pairs per launch instead. */
+RAYLIB_API int32_t RaylibAMD_GatherDevice(SceneHandle scene, const RaylibAMDGatherParams* params, const RaylibAMDGatherPoint* points, int32_t n, float* out,
+        void* stream);
+/* Host only, no device: the direction Wi of sample `sample` of every point (statement 1 with the stream (seed, points[i].stream, sampleFirst + sample) and
+ * the host's sqrtf, sinf, cosf and 1.0f / x), n x 3 floats.  Returns 1, or 0 with nothing written for a null argument with n > 0, n < 0, an unknown kind or
+ * skipDraws > 62. */
+RAYLIB_API int32_t RaylibAMD_GatherDirectionsHost(const RaylibAMDGatherParams* params, const RaylibAMDGatherPoint* points, int32_t n, uint64_t seed, uint32_t sample,
+        float* outDirs);
+
+/* Host only, no device: how a call of n points under `params` would be cut into launches under the current environment (csrc/rl_plan.cc PlanGatherCut: the
+ * 256 MiB of sample buffer, or RAYLIB_GATHER_BATCH), and which points and samples launch `launchIndex` of it takes.  Launch k is sample range k % sampleRanges of
+ * point range k / sampleRanges.  sampleCount may be any uint32_t: the counts are 64-bit.  Returns 1; 0 with nothing written for a null argument, n <= 0,
+ * sampleCount == 0, an unknown kind or launchIndex >= launches. */
+typedef struct RaylibAMDGatherCut {
+	uint32_t pointsPerLaunch, samplesPerLaunch;        /* of a full launch; their product is at most the slots a launch holds */
+	uint64_t pointRanges, sampleRanges, launches;      /* launches = pointRanges x sampleRanges */
+	uint32_t pointFirst, numPoints;                    /* launch launchIndex: its points ... */
+	uint32_t sampleBase, numSamples;                   /* ... and its samples sampleBase .. sampleBase + numSamples - 1 of the call's sampleCount */
+	int32_t  first, last;                              /* it is the first / last sample range of its point range: the sums start from +0 / the result is written */
+} RaylibAMDGatherCut;
+RAYLIB_API int32_t RaylibAMD_PlanGatherCut(const RaylibAMDGatherParams* params, int32_t n, uint64_t launchIndex, RaylibAMDGatherCut* out);
+
 /* ---- procedural scene elements ----------------------------------------------------------
  * The reference's two procedural demo scenes (src/main.cc:913-984) `new` its C++ classes (Sphere, Cube, Triangle,
  * Lambertian, Metal, ...) in the application and pass the object pointers to Raylib_AddSceneElement.  A C ABI

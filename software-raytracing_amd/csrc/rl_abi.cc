@@ -7,7 +7,10 @@
 #include "rl_host.h"
 #include "rl_plan.h"
 #include "rl_progressive.h"
+#include "raylib_amd_rng.h"
 
+#include <math.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -795,6 +798,41 @@ static bool RadianceParamsValid(const char* who, const Scene* s, const RaylibAMD
 	if (!std::isfinite(p->rayTMin) || p->rayTMin < 0.0f) { Log("%s: rayTMin %g is negative or not finite", who, p->rayTMin); return false; }
 	return true;
 }
+// What a radiance call and a gather do between their own refusals and the device.  First the time interval: the host entry scans the records' times (word 3 of
+// each 32-byte record; `what` names a record in the log), the device entry is given it.  prm.timeMin / timeMax are set.
+static bool PathTimesValid(const char* who, const char* what, RaylibAMDRadianceParams& prm, const void* records, int32_t n, bool hostMem)
+{
+	if (hostMem) {
+		// the host entry scans the times itself (timeMin / timeMax are the device entry's)
+		const float* rec = (const float*)records;
+		prm.timeMin = prm.timeMax = n > 0 ? rec[3] : 0.0f;
+		for (int32_t i = 0; i < n; ++i) {
+			const float t = rec[(size_t)i * 8 + 3];
+			if (!std::isfinite(t)) { Log("%s: %s %d has a time that is not finite", who, what, i); return false; }
+			prm.timeMin = std::min(prm.timeMin, t); prm.timeMax = std::max(prm.timeMax, t);
+		}
+	} else if (!std::isfinite(prm.timeMin) || !std::isfinite(prm.timeMax) || prm.timeMin > prm.timeMax) {
+		Log("%s: the time interval [%g, %g] is empty or not finite", who, prm.timeMin, prm.timeMax);
+		return false;
+	}
+	return true;
+}
+// ... then, with a device: the boxes of moving cubes for that interval, and a sky panorama that was destroyed
+static bool PreparePathScene(const char* who, Scene* s, const RaylibAMDRadianceParams& prm, int32_t n)
+{
+	if (n > 0 && s->hasMovingCubes && !(prm.timeMin >= s->accelT0 && prm.timeMax <= s->accelT1)) {
+		// moving cubes: their boxes must cover the motion at every ray's time (as RaylibAMD_TraceRays rebuilds them for its rayTime)
+		const float t0 = std::min(s->accelT0, prm.timeMin), t1 = std::max(s->accelT1, prm.timeMax);
+		if (s->device) { DeviceReleaseScene(s->device); s->device = nullptr; }
+		if (!s->BuildAccel(t0, t1)) { Log("%s: the acceleration structure could not be rebuilt for the times [%g, %g]", who, prm.timeMin, prm.timeMax); return false; }
+	}
+	if (s->sky && !g_images.contains(s->sky)) {
+		Log("%s: the scene's sky panorama was destroyed; tracing without it", who);   // as a render (PrepareRender)
+		s->sky = nullptr;
+	}
+	return true;
+}
+static_assert(offsetof(RaylibAMDPathRay, time) == 12 && offsetof(RaylibAMDGatherPoint, time) == 12 && sizeof(RaylibAMDPathRay) == 32 && sizeof(RaylibAMDGatherPoint) == 32, "a record's time");
 static int32_t TraceRadianceInternal(const char* who, SceneHandle sh, const RaylibAMDRadianceParams* params, const RaylibAMDPathRay* rays, int32_t n, float* out,
                                      bool hostMem, void* stream)
 {
@@ -802,29 +840,9 @@ static int32_t TraceRadianceInternal(const char* who, SceneHandle sh, const Rayl
 	if (n < 0 || (n > 0 && (!rays || !out))) { Log("%s: null argument", who); return 0; }
 	if (!RadianceParamsValid(who, s, params)) return 0;
 	RaylibAMDRadianceParams prm = *params;
-	if (hostMem) {
-		// the host entry scans the times itself (timeMin / timeMax are the device entry's)
-		prm.timeMin = prm.timeMax = n > 0 ? rays[0].time : 0.0f;
-		for (int32_t i = 0; i < n; ++i) {
-			const float t = rays[i].time;
-			if (!std::isfinite(t)) { Log("%s: ray %d has a time that is not finite", who, i); return 0; }
-			prm.timeMin = std::min(prm.timeMin, t); prm.timeMax = std::max(prm.timeMax, t);
-		}
-	} else if (!std::isfinite(prm.timeMin) || !std::isfinite(prm.timeMax) || prm.timeMin > prm.timeMax) {
-		Log("%s: the time interval [%g, %g] is empty or not finite", who, prm.timeMin, prm.timeMax);
-		return 0;
-	}
+	if (!PathTimesValid(who, "ray", prm, rays, n, hostMem)) return 0;
 	if (!DeviceAvailable()) return 0;
-	if (n > 0 && s->hasMovingCubes && !(prm.timeMin >= s->accelT0 && prm.timeMax <= s->accelT1)) {
-		// moving cubes: their boxes must cover the motion at every ray's time (as RaylibAMD_TraceRays rebuilds them for its rayTime)
-		const float t0 = std::min(s->accelT0, prm.timeMin), t1 = std::max(s->accelT1, prm.timeMax);
-		if (s->device) { DeviceReleaseScene(s->device); s->device = nullptr; }
-		if (!s->BuildAccel(t0, t1)) { Log("%s: the acceleration structure could not be rebuilt for the times [%g, %g]", who, prm.timeMin, prm.timeMax); return 0; }
-	}
-	if (s->sky && !g_images.contains(s->sky)) {
-		Log("%s: the scene's sky panorama was destroyed; tracing without it", who);   // as a render (PrepareRender)
-		s->sky = nullptr;
-	}
+	if (!PreparePathScene(who, s, prm, n)) return 0;
 	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
 	if (!DeviceTraceRadiance(*s, prm, CurrentSeed(), rays, n, out, hostMem, stream, stats)) return 0;
 	if (!stream) { std::lock_guard<std::mutex> lk(g_stateMu); g_lastStats = stats; }
@@ -845,6 +863,74 @@ int32_t RaylibAMD_PlanRadiance(SceneHandle sh, const RaylibAMDRadianceParams* pa
 	const QueryPlan p = PlanRadiance(*(Scene*)sh, ReadRenderKnobs());
 	if (!p.ok) return -1;
 	out->tree = p.tree; out->treeWidth = p.treeWidth; out->nodeBytes = p.nodeBytes; out->stack = p.stack; out->prims = p.prims; out->early = 0;
+	return 1;
+}
+
+// RaylibAMD_Gather / RaylibAMD_GatherDevice / RaylibAMD_GatherDirectionsHost: a gather's own refusals; the rest are a radiance call's
+static bool GatherKindValid(const char* who, const RaylibAMDGatherParams* p)
+{
+	if (p->kind != RAYLIB_AMD_GATHER_IRRADIANCE && p->kind != RAYLIB_AMD_GATHER_SH9) { Log("%s: unknown gather kind %d", who, p->kind); return false; }
+	if (p->skipDraws > 62) { Log("%s: skipDraws %u exceeds 62", who, p->skipDraws); return false; }
+	return true;
+}
+static int32_t GatherInternal(const char* who, SceneHandle sh, const RaylibAMDGatherParams* params, const RaylibAMDGatherPoint* points, int32_t n, float* out,
+                              bool hostMem, void* stream)
+{
+	Scene* s = (Scene*)sh;
+	if (n < 0 || (n > 0 && (!points || !out))) { Log("%s: null argument", who); return 0; }
+	if (!s || !params) { Log("%s: null argument", who); return 0; }
+	RaylibAMDRadianceParams prm;
+	prm.maxPathLength = params->maxPathLength; prm.rayTMin = params->rayTMin; prm.sampleFirst = params->sampleFirst; prm.sampleCount = params->sampleCount;
+	prm.skipDraws = params->skipDraws; prm.timeMin = params->timeMin; prm.timeMax = params->timeMax;
+	if (!RadianceParamsValid(who, s, &prm) || !GatherKindValid(who, params)) return 0;
+	if (!PathTimesValid(who, "point", prm, points, n, hostMem)) return 0;
+	if (!DeviceAvailable()) return n == 0 ? 1 : 0;   // (no points: nothing to gather, with or without a device)
+	if (!PreparePathScene(who, s, prm, n)) return 0;
+	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
+	if (!DeviceGather(*s, params->kind, prm, CurrentSeed(), points, n, out, hostMem, stream, stats)) return 0;
+	if (!stream) { std::lock_guard<std::mutex> lk(g_stateMu); g_lastStats = stats; }
+	return 1;
+}
+int32_t RaylibAMD_Gather(SceneHandle sh, const RaylibAMDGatherParams* params, const RaylibAMDGatherPoint* points, int32_t n, float* out)
+{
+	return GatherInternal("RaylibAMD_Gather", sh, params, points, n, out, true, nullptr);
+}
+int32_t RaylibAMD_GatherDevice(SceneHandle sh, const RaylibAMDGatherParams* params, const RaylibAMDGatherPoint* points, int32_t n, float* out, void* stream)
+{
+	return GatherInternal("RaylibAMD_GatherDevice", sh, params, points, n, out, false, stream);
+}
+int32_t RaylibAMD_PlanGatherCut(const RaylibAMDGatherParams* params, int32_t n, uint64_t launchIndex, RaylibAMDGatherCut* out)
+{
+	const char* who = "RaylibAMD_PlanGatherCut";
+	if (!params || !out || n <= 0 || params->sampleCount == 0) { Log("%s: null argument, or nothing to cut", who); return 0; }
+	if (!GatherKindValid(who, params)) return 0;
+	const GatherCut c = PlanGatherCut((uint32_t)n, params->sampleCount, params->kind == RAYLIB_AMD_GATHER_SH9, ReadRenderKnobs());
+	if (launchIndex >= c.launches) { Log("%s: launch %llu of %llu", who, (unsigned long long)launchIndex, (unsigned long long)c.launches); return 0; }
+	const GatherLaunch L = GatherLaunchAt(c, (uint32_t)n, params->sampleCount, launchIndex);
+	out->pointsPerLaunch = c.pointsPer; out->samplesPerLaunch = c.samplesPer; out->pointRanges = c.pointRanges; out->sampleRanges = c.sampleRanges; out->launches = c.launches;
+	out->pointFirst = L.pointFirst; out->numPoints = L.numPoints; out->sampleBase = L.sampleBase; out->numSamples = L.numSamples; out->first = L.first; out->last = L.last;
+	return 1;
+}
+// statement 1 of the header's contract with the host's libm: csrc/rl_dev_core.h RandomInUnitSphere and normalize, csrc/rl_dev_shade.h's Lambertian flip
+int32_t RaylibAMD_GatherDirectionsHost(const RaylibAMDGatherParams* params, const RaylibAMDGatherPoint* points, int32_t n, uint64_t seed, uint32_t sample, float* outDirs)
+{
+	const char* who = "RaylibAMD_GatherDirectionsHost";
+	if (!params || n < 0 || (n > 0 && (!points || !outDirs))) { Log("%s: null argument", who); return 0; }
+	if (!GatherKindValid(who, params)) return 0;
+	for (int32_t i = 0; i < n; ++i) {
+		RaylibRngStream g = raylib_rng_begin(seed, points[i].stream, params->sampleFirst + sample);
+		for (uint32_t k = 0; k < params->skipDraws; ++k) (void)raylib_rng_next_u32(&g);
+		const float u1 = raylib_rng_next_float(&g);
+		const float u2 = raylib_rng_next_float(&g);
+		const float z = 1.0f - 2.0f * u1;
+		const float r = sqrtf(fmaxf(0.0f, 1.0f - z * z));
+		const float phi = 2.0f * 3.141592f * u2;
+		float w[3] = { r * cosf(phi), r * sinf(phi), z };
+		const float* N = points[i].normal;
+		if (params->kind == RAYLIB_AMD_GATHER_IRRADIANCE && (double)(w[0] * N[0] + w[1] * N[1] + w[2] * N[2]) < 0.0) { w[0] = -w[0]; w[1] = -w[1]; w[2] = -w[2]; }
+		const float k = 1.0f / sqrtf(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+		outDirs[3 * (size_t)i + 0] = w[0] * k; outDirs[3 * (size_t)i + 1] = w[1] * k; outDirs[3 * (size_t)i + 2] = w[2] * k;
+	}
 	return 1;
 }
 

@@ -267,6 +267,14 @@ constexpr uint64_t RL_RADIANCE_STACK_BUDGET = 256ull << 20;
 constexpr int32_t RL_RADIANCE_MAX_PATH = 32768;
 bool DeviceTraceRadiance(Scene& scene, const RaylibAMDRadianceParams& prm, uint64_t seed, const void* rays, int32_t n, float* out, bool hostMem, void* stream,
                          RaylibAMDStats& stats);
+// RaylibAMD_Gather (hostMem) and RaylibAMD_GatherDevice: kind is RAYLIB_AMD_GATHER_*, prm holds the gather's parameters as a radiance call's and is valid, as above.
+// The sample buffer of a launch is held to RL_GATHER_SAMPLE_BUDGET (RAYLIB_GATHER_BATCH: so many slots instead, at most RL_GATHER_MAX_SLOTS); a call of more
+// (point, sample) pairs runs as several launches.  A synchronous call times up to RL_GATHER_TIMED trace launches apart from their resolves.
+constexpr uint64_t RL_GATHER_SAMPLE_BUDGET = 256ull << 20;
+constexpr uint64_t RL_GATHER_MAX_SLOTS = 1ull << 28;
+constexpr uint64_t RL_GATHER_TIMED = 4096;
+bool DeviceGather(Scene& scene, int32_t kind, const RaylibAMDRadianceParams& prm, uint64_t seed, const void* points, int32_t n, float* out, bool hostMem, void* stream,
+                  RaylibAMDStats& stats);
 bool DevicePostProcess(Image& img);          // Image2D::PostProcess on the device; false when no device
 bool DeviceDumpRGB(Image& img, float* outRGB);   // a device-resident frame packed to RGB on the device and copied to caller memory through pinned staging; false: not applicable
 bool DeviceReadback(Image& img);            // device copy -> img.rgba (the caller checked hostStale)

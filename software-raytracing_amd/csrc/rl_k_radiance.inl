@@ -17,13 +17,34 @@
 // The path stack is the megakernel's: Q.maxPathLength records of two float4 per RESIDENT lane (not per ray), record k of lane g at
 // (k * Q.stackStride + g) * 2 -- a wave's 64 lanes write 2 KiB back to back per record index.
 // (RL_QUERY_CHUNK, the jobs a wave takes per atomic on the global counter: rl_kernels.h)
+//
+// One source for two kernels, as rl_k_resolve.inl is: a translation unit includes this file with RL_GATHER_TWIN 0 for k_radiance (rl_radiance.hip) or 1 for
+// k_gather (rl_gather.hip: RaylibAMD_Gather), whose generator template parameter GEN (RL_GEN_HEMISPHERE, RL_GEN_SPHERE) says how a job's ray is made.  The twin
+// differs in two places, both under RL_GATHER_TWIN:
+//   the `fresh` block   a job is one (point, sample) pair of a launch, sample-major (job = sample * J.numPoints + point, so that a wave's lanes hold
+//                       neighbouring points at one sample index); it loads the point and draws the direction from the sample's stream
+//   the `done` block    writes the sample's value to slot `job` of the launch's sample buffer instead of summing it -- k_gather_resolve sums the slots in
+//                       sample order
+// Walk, shading, miss shader, fold, refill and counters are the same lines.  Everything of the twin's is under the macro, so that k_radiance is the token
+// sequence it was (a generator parameter on a shared body adds an inlining level, which changes k_radiance's register allocation: tools/isa_equivalence.py).
 
 // (template and kernel arguments: rl_kernels.h)
+#if RL_GATHER_TWIN
+// points: the call's point records (two float4 each); n: the launch's jobs = J.numPoints * its samples; samples: 2 n float4 for the sphere (L | Wi), n for the hemisphere
+template <int TREE, int STACK, bool PRIMS, int GEN>
+__global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 2))
+k_gather(const DSceneView S, const SkyRot R, const DRadianceParams Q, const float4* __restrict__ rays, uint32_t n, const DGatherJobs J, float4* __restrict__ out,
+         float* __restrict__ pathStack, unsigned int* __restrict__ rayCounter, unsigned long long* __restrict__ counters)
+#else
 template <int TREE, int STACK, bool PRIMS>
 __global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 2))
 k_radiance(const DSceneView S, const SkyRot R, const DRadianceParams Q, const float4* __restrict__ rays, uint32_t n, float4* __restrict__ out,
            float* __restrict__ pathStack, unsigned int* __restrict__ rayCounter, unsigned long long* __restrict__ counters)
+#endif
 {
+#if RL_GATHER_TWIN
+	static_assert(GEN == RL_GEN_HEMISPHERE || GEN == RL_GEN_SPHERE, "generator");
+#endif
 	static_assert(TREE == 2 || TREE == 4, "tree");
 	static_assert(TREE == 2 || !PRIMS, "spheres and cubes are walked on the binary tree only");
 	RL_TEX_PROLOGUE(S);                      // (empty here: rl_radiance.hip leaves RL_LDS_TEXTURE_TABLE off, texture descriptors are read from global memory)
@@ -43,6 +64,9 @@ k_radiance(const DSceneView S, const SkyRot R, const DRadianceParams Q, const fl
 	V3 o = v3s(0.0f), d = v3s(0.0f);
 	float rayTime = 0.0f;
 	int depth = 0;
+#if RL_GATHER_TWIN
+	float weight = 0.0f;                     // RL_GEN_HEMISPHERE: max(0, dot(N, Wi)) of the sample's direction
+#endif
 	uint32_t next = 0u, end = 0u;            // the wave's chunk (wave-uniform)
 	bool drained = false;                    // the global counter is past n (wave-uniform)
 	for (;;) {
@@ -68,6 +92,24 @@ k_radiance(const DSceneView S, const SkyRot R, const DRadianceParams Q, const fl
 		if (lane == 0u) c.trips++;
 		if (my != NONE) {
 			if (fresh) {
+#if RL_GATHER_TWIN
+				// the job's (point, sample); the point's record (pos, time | normal, stream); the direction from the sample's first two draws behind the skipped
+				// ones (include/raylib_amd.h RaylibAMD_Gather, statement 1): the Lambertian case's three statements of rl_dev_shade.h for the hemisphere, the
+				// normalised draw for the sphere
+				const uint32_t sIdx = my / J.numPoints, pIdx = my - sIdx * J.numPoints;
+				const float4* pp = rays + 2u * ((size_t)J.pointFirst + pIdx);
+				const float4 r0 = GLoadF4(pp, 0), r1 = GLoadF4(pp, 1);
+				o = v3(r0.x, r0.y, r0.z);
+				const V3 N = v3(r1.x, r1.y, r1.z);
+				rayTime = fminf(fmaxf(r0.w, Q.timeMin), Q.timeMax);
+				g.s = raylib_rng_begin_mixed(Q.seedMixed, __float_as_uint(r1.w), Q.sampleFirst + J.sampleBase + sIdx);
+				for (uint32_t k = 0; k < Q.skipDraws; ++k) (void)raylib_rng_next_u32(&g.s);
+				V3 w = RandomInUnitSphere(g);
+				if constexpr (GEN == RL_GEN_HEMISPHERE) { if ((double)dot(w, N) < 0.0) w = -w; }
+				d = normalize(w);
+				if constexpr (GEN == RL_GEN_HEMISPHERE) weight = fmaxf(0.0f, dot(N, d));
+				else out[(size_t)n + my] = make_float4(d.x, d.y, d.z, 0.0f);   // the resolve's basis functions need Wi: the buffer's second plane
+#else
 				// the ray as given; its stream (seed, rays[i].stream, sampleFirst + sample) behind the draws the caller made for it
 				const float4* rp = rays + 2u * (size_t)my;   // (64-bit offset: n may reach 2^31 - 1)
 				const float4 r0 = GLoadF4(rp, 0), r1 = GLoadF4(rp, 1);
@@ -75,6 +117,7 @@ k_radiance(const DSceneView S, const SkyRot R, const DRadianceParams Q, const fl
 				rayTime = fminf(fmaxf(r0.w, Q.timeMin), Q.timeMax);   // (a NaN becomes timeMin: the boxes of moving cubes cover [timeMin, timeMax])
 				g.s = raylib_rng_begin_mixed(Q.seedMixed, __float_as_uint(r1.w), Q.sampleFirst + sample);
 				for (uint32_t k = 0; k < Q.skipDraws; ++k) (void)raylib_rng_next_u32(&g.s);
+#endif
 				depth = 0;
 				fresh = false;
 				c.samples++;
@@ -145,12 +188,19 @@ k_radiance(const DSceneView S, const SkyRot R, const DRadianceParams Q, const fl
 					radiance = radiance + E;
 					L = radiance;
 				}
+#if RL_GATHER_TWIN
+				// the sample's value (statement 3): L * max(0, dot(N, Wi)) for the hemisphere; L itself for the sphere, whose nine products the resolve forms
+				if constexpr (GEN == RL_GEN_HEMISPHERE) L = L * weight;
+				out[my] = make_float4(L.x, L.y, L.z, 0.0f);
+				my = NONE;
+#else
 				acc = acc + L;
 				if (++sample >= Q.sampleCount) {
 					const float k = rtm::rcp1_((float)Q.sampleCount);   // k_resolve's factor
 					out[my] = make_float4(acc.x * k, acc.y * k, acc.z * k, 1.0f);
 					my = NONE;
 				} else fresh = true;
+#endif
 			}
 			if (store) {
 				// path vertex record: 32 contiguous bytes per lane, two 16-byte stores
@@ -169,3 +219,4 @@ k_radiance(const DSceneView S, const SkyRot R, const DRadianceParams Q, const fl
 		}
 	}
 }
+

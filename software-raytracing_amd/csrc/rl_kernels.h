@@ -10,6 +10,8 @@
 //   rl_render_pool.hip   k_trace_pool and its twin: a scheduler strategy of its own (Makefile POOLFLAGS)
 //   rl_query.hip         k_query (RaylibAMD_TraceRays): beside the render kernels it would change how the walks they share are inlined into those
 //   rl_radiance.hip      k_radiance (RaylibAMD_TraceRadiance): the same reason, towards the render and the query kernels alike
+//   rl_gather.hip        k_gather (RaylibAMD_Gather: rl_k_radiance.inl's twin, the generator instances of its loop) and k_gather_resolve: beside k_radiance they would be
+//                        more callers of the walks and the shading it inlines
 // A twin takes the view table (DViews) as one more trailing argument.  Default template arguments are given here and nowhere else.
 #pragma once
 
@@ -154,6 +156,10 @@ RL_QUERY_INSTANCES(extern RL_K_QUERY)
 // Path-traced radiance along caller rays (RaylibAMD_TraceRadiance; rl_k_radiance.inl)
 // What RaylibAMDRadianceParams and the launch say: the seed mixed once (raylib_rng_mix64), the path stack's stride in lanes (the grid's size)
 struct DRadianceParams { unsigned long long seedMixed; int32_t maxPathLength; float rayTMin; uint32_t sampleFirst, sampleCount, skipDraws, stackStride; float timeMin, timeMax; };
+// k_gather's generator: how the twin of rl_k_radiance.inl makes a job's ray from the caller's point
+enum { RL_GEN_HEMISPHERE = 1, RL_GEN_SPHERE = 2 };   // the gather kinds + 1 (RAYLIB_AMD_GATHER_IRRADIANCE, RAYLIB_AMD_GATHER_SH9); k_radiance, whose rays are the caller's, has no generator
+// One launch of a gather: job j is sample sampleBase + j / numPoints of point pointFirst + j % numPoints
+struct DGatherJobs { uint32_t pointFirst, numPoints, sampleBase; };
 // TREE: 2 the binary tree (S.nodes), 4 the grid nodes (S.nodes4).  STACK: the walk's stack.  PRIMS: the scene holds spheres or cubes (binary tree only).
 // rays: n records of two float4 (org, time | dir, stream).  out: n float4.  pathStack: [maxPathLength][stackStride] records of 2 float4, as k_trace's.
 // counters: CNT_* sums, or null.
@@ -164,6 +170,26 @@ __global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 
 #define RL_RADIANCE_INSTANCES(X) X(2, 32, false) X(2, 32, true) X(2, 64, false) X(2, 64, true) X(4, 32, false) X(4, 64, false)
 #define RL_K_RADIANCE(a, b, c) template __global__ void k_radiance<a, b, c>(RL_RADIANCE_ARGS);
 RL_RADIANCE_INSTANCES(extern RL_K_RADIANCE)
+
+// ---------------------------------------------------------------------------
+// Irradiance and SH probes gathered at caller points (RaylibAMD_Gather; rl_k_radiance.inl, rl_gather.hip)
+// points: the call's records of two float4 (pos, time | normal, stream).  n: the launch's jobs.  samples: the launch's sample buffer, slot j = job j: one float4
+// (the sample's value) for the hemisphere; two planes of n float4 for the sphere (L, then Wi).
+#define RL_GATHER_ARGS const DSceneView, const SkyRot, const DRadianceParams, const float4* __restrict__, uint32_t, const DGatherJobs, float4* __restrict__, float* __restrict__, unsigned int* __restrict__, unsigned long long* __restrict__
+template <int TREE, int STACK, bool PRIMS, int GEN>
+__global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 2)) k_gather(RL_GATHER_ARGS);
+// The instances rl_rt_rays.hip GatherKernelFor selects from: k_radiance's (TREE, STACK, PRIMS), once per generator
+#define RL_GATHER_INSTANCES_G(X, G) X(2, 32, false, G) X(2, 32, true, G) X(2, 64, false, G) X(2, 64, true, G) X(4, 32, false, G) X(4, 64, false, G)
+#define RL_GATHER_INSTANCES(X) RL_GATHER_INSTANCES_G(X, RL_GEN_HEMISPHERE) RL_GATHER_INSTANCES_G(X, RL_GEN_SPHERE)
+#define RL_K_GATHER(a, b, c, d) template __global__ void k_gather<a, b, c, d>(RL_GATHER_ARGS);
+RL_GATHER_INSTANCES(extern RL_K_GATHER)
+// Folds a launch's sample values into per-point sums in sample order, one thread per point (GEN as above).  samples: as k_gather wrote them, numPoints x
+// numSamples slots.  acc: 3 (hemisphere) or 27 (sphere) planes of numPoints floats, read unless `first`, written unless `last`.  out: the call's output at the
+// launch's first point; written when `last`: sum * rcp1_(sampleCount) * the solid angle.
+#define RL_GATHER_RESOLVE_ARGS const float4* __restrict__, uint32_t, uint32_t, float* __restrict__, float* __restrict__, int, int, uint32_t
+template <int GEN> __global__ void __launch_bounds__(RL_BLOCK) k_gather_resolve(RL_GATHER_RESOLVE_ARGS);
+extern template __global__ void k_gather_resolve<RL_GEN_HEMISPHERE>(RL_GATHER_RESOLVE_ARGS);
+extern template __global__ void k_gather_resolve<RL_GEN_SPHERE>(RL_GATHER_RESOLVE_ARGS);
 
 // ---------------------------------------------------------------------------
 // Test hooks (rl_rt_hooks.hip): single functions of the hot path evaluated on arrays

@@ -29,6 +29,7 @@ RenderKnobs ReadRenderKnobs()
 	k.lazyRefl = flag("RAYLIB_LAZY_REFL");
 	if (const char* e = getenv("RAYLIB_LIT_LIST")) k.litList = std::max(0ll, atoll(e));
 	if (const char* e = getenv("RAYLIB_QUERY_TREE")) { const int v = atoi(e); k.queryTree = (v == 2 || v == 4 || v == 8) ? v : 0; }
+	if (const char* e = getenv("RAYLIB_GATHER_BATCH")) k.gatherBatch = std::max(0, atoi(e));
 	return k;
 }
 
@@ -164,6 +165,29 @@ QueryPlan PlanRadiance(const Scene& sc, const RenderKnobs& k)
 		p.stack = b.depth <= 32 ? 32 : 64;
 	}
 	return p;
+}
+
+GatherCut PlanGatherCut(uint32_t n, uint32_t sampleCount, bool sphere, const RenderKnobs& k)
+{
+	GatherCut c;
+	const uint64_t slotBytes = (sphere ? 2u : 1u) * 16u;   // one float4 (the hemisphere's weighted sample) or two (the sphere's L and Wi)
+	const uint64_t slots = k.gatherBatch > 0 ? std::min<uint64_t>((uint64_t)k.gatherBatch, RL_GATHER_MAX_SLOTS) : RL_GATHER_SAMPLE_BUDGET / slotBytes;
+	c.pointsPer = (uint32_t)std::min<uint64_t>(n, slots);
+	c.samplesPer = (uint32_t)std::min<uint64_t>(sampleCount, std::max<uint64_t>(1, slots / c.pointsPer));
+	c.pointRanges = ((uint64_t)n + c.pointsPer - 1) / c.pointsPer;
+	c.sampleRanges = ((uint64_t)sampleCount + c.samplesPer - 1) / c.samplesPer;
+	c.launches = c.pointRanges * c.sampleRanges;   // (< 2^31 * 2^32)
+	return c;
+}
+GatherLaunch GatherLaunchAt(const GatherCut& c, uint32_t n, uint32_t sampleCount, uint64_t k)
+{
+	GatherLaunch L;
+	const uint64_t pr = k / c.sampleRanges, sr = k % c.sampleRanges;
+	const uint64_t pf = pr * c.pointsPer, sb = sr * c.samplesPer;   // (pf < n, sb < sampleCount: both fit 32 bits; their successors may not)
+	L.pointFirst = (uint32_t)pf; L.numPoints = (uint32_t)std::min<uint64_t>(c.pointsPer, (uint64_t)n - pf);
+	L.sampleBase = (uint32_t)sb; L.numSamples = (uint32_t)std::min<uint64_t>(c.samplesPer, (uint64_t)sampleCount - sb);
+	L.first = sr == 0; L.last = sr + 1 == c.sampleRanges;
+	return L;
 }
 
 LaunchPlan PlanLaunch(uint32_t numLocalCells, uint32_t numActive, uint32_t spp, uint32_t sampleBegin, int numCUs, int workgroupsPerCU,

@@ -23,7 +23,8 @@ struct RenderKnobs {
 	int guided = 0;                               // RAYLIB_GUIDED
 	int blocksPerCU = 0;                          // RAYLIB_BLOCKS_PER_CU (0: not set or not positive)
 	int cullCells = 1;                            // RAYLIB_CULL_CELLS (rl_cull.cc reads it for itself; the runtime keys its cached cell lists on it)
-	int queryTree = 0;                            // RAYLIB_QUERY_TREE: 2, 4 or 8 (RaylibAMD_TraceRays, RaylibAMD_TraceRadiance; any other value: 0, not set)
+	int queryTree = 0;                            // RAYLIB_QUERY_TREE: 2, 4 or 8 (RaylibAMD_TraceRays, RaylibAMD_TraceRadiance, RaylibAMD_Gather; any other value: 0, not set)
+	int gatherBatch = 0;                          // RAYLIB_GATHER_BATCH: (point, sample) slots per launch of RaylibAMD_Gather (0: not set or not positive)
 	int lazyRefl = -1;                            // RAYLIB_LAZY_REFL
 	long long litList = -1;                       // RAYLIB_LIT_LIST: entries of the lazy instance's lit list (0: every lit path folds in place); -1: not set
 };
@@ -76,6 +77,16 @@ QueryPlan PlanQuery(const Scene& sc, int32_t kind, const RenderKnobs& knobs);
 // carries one, has no spheres or cubes and its worst-case stack fits 64 entries; else the binary tree.  The 8-wide walk is a step walk and not fused with
 // shading here: RAYLIB_QUERY_TREE=8 falls through to 4, =2 walks the binary tree.  `early` is unused (false).
 QueryPlan PlanRadiance(const Scene& sc, const RenderKnobs& knobs);
+
+// How RaylibAMD_Gather cuts n points x sampleCount samples into launches (rl_rt_rays.hip DeviceGather; RaylibAMD_PlanGatherCut): a launch holds at most `slots`
+// (point, sample) pairs -- RL_GATHER_SAMPLE_BUDGET over the slot's bytes (16 for IRRADIANCE, 32 for SH9), or RAYLIB_GATHER_BATCH, at most RL_GATHER_MAX_SLOTS.
+// While one sample of every point fits, a launch takes all the points and samplesPer samples; otherwise the points are cut into ranges of pointsPer as well, one
+// sample per launch.  Launch k of `launches` is sample range k % sampleRanges of point range k / sampleRanges: a point range runs through all its sample ranges
+// before the next begins, so one set of running sums serves.  sampleCount may be any uint32_t and n any positive int32_t: the counts and every product are 64-bit.
+struct GatherCut { uint32_t pointsPer = 0, samplesPer = 0; uint64_t pointRanges = 0, sampleRanges = 0, launches = 0; };
+struct GatherLaunch { uint32_t pointFirst, numPoints, sampleBase, numSamples; bool first, last; };   // first / last: of the point range's sample ranges
+GatherCut PlanGatherCut(uint32_t n, uint32_t sampleCount, bool sphere, const RenderKnobs& knobs);   // n, sampleCount >= 1
+GatherLaunch GatherLaunchAt(const GatherCut& c, uint32_t n, uint32_t sampleCount, uint64_t k);      // k < c.launches
 
 // Several views of one scene in one launch per sample batch (RaylibAMD_RenderViews): the job list of the batch.  Cell c of view v is batch cell
 // v * cellsPerView + c; the list is every view's listed cells, view by view, each view culled on its own (CullCells), a view that is not eligible listing all

@@ -12,6 +12,7 @@
 namespace rl {
 
 // ---- kernel bodies ----
+#define RL_GATHER_TWIN 0
 #include "rl_k_radiance.inl"
 
 // ---- instances ----

@@ -4,7 +4,7 @@
 //   rl_rt_scene.hip   a flattened scene (rl_scene.cc FlattenScene) to every device, its sky and wide trees; images: read-back, RGB dump, post-processing
 //   rl_rt_frame.hip   kernel selection and the one enqueue path of every render (EnqueueFrame), a rank's one-view render, a batch of views
 //   rl_rt_render.hip  whole frames over N ranks (gather, scatter, two frames in flight), DeviceRender, progressive sessions
-//   rl_rt_rays.hip    caller rays: DeviceTraceRays, DeviceTraceRadiance
+//   rl_rt_rays.hip    caller rays: DeviceTraceRays, DeviceTraceRadiance, DeviceGather
 //   rl_rt_hooks.hip   test hooks
 //
 // Ranks.  RAYLIB_NUM_GPUS = N (default 1) makes the library drive N devices from this one process: the frame's 8x8
@@ -186,6 +186,11 @@ struct RankCtx {
 	DevBuf<unsigned int> radCounter;
 	DevBuf<float> radStack;
 	hipEvent_t radEv = nullptr; bool radEvUsed = false;
+	// a gather's launches between those (DeviceGather), behind the same event: the launch's sample buffer, the per-point sums that carry from launch to launch,
+	// and the event pairs with which a synchronous call times its trace launches
+	DevBuf<float4> gSamples;
+	DevBuf<float> gAcc;
+	std::vector<hipEvent_t> gEv;
 };
 
 // The one runtime of the process (Rt()): never destroyed, so no buffer is freed behind the HIP runtime's back at exit.

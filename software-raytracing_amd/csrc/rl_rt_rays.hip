@@ -1,8 +1,10 @@
-// Host runtime: rays of the caller's -- the ray queries (RaylibAMD_TraceRays, k_query) and path-traced radiance (RaylibAMD_TraceRadiance, k_radiance) on
-// rank 0's device, from host memory or from device pointers, on the library's stream (synchronous, with stats) or enqueued on a stream of the caller's (rl_rt.h).
+// Host runtime: rays of the caller's -- the ray queries (RaylibAMD_TraceRays, k_query), path-traced radiance (RaylibAMD_TraceRadiance, k_radiance) and the
+// irradiance and SH probes gathered from it at caller points (RaylibAMD_Gather, k_gather + k_gather_resolve) on rank 0's device, from host memory or from device pointers, on the library's stream (synchronous, with stats) or enqueued on a stream of the caller's (rl_rt.h).
 // The two entries share the refusals of a device call's pointers, the synchronous call's counter block and event pair, the stats' header, the staging of a
 // host call through qRays / qOut, the grid that fills the device once, and the synchronous tail; each keeps its plan and kernel, its parameter block and the
 // discipline of its scratch: a ring of ray counters with an event per slot for the queries, one counter and one path stack ordered by radEv for radiance.
+// A gather is a radiance call with another generator: it shares that call's preparation (BeginPathCall, PathGrid), its counter, stack and event chain, and adds
+// the sample buffer and the per-point sums between its launches.
 #include "rl_rt.h"
 
 namespace rl {
@@ -27,6 +29,17 @@ static RadianceKernel RadianceKernelFor(const QueryPlan& p)
 	return p.prims ? (RadianceKernel)k_radiance<2, 64, true> : (RadianceKernel)k_radiance<2, 64, false>;
 }
 static_assert(sizeof(RaylibAMDPathRay) == sizeof(RaylibAMDRay), "radiance records");
+typedef void (*GatherKernel)(const DSceneView, const SkyRot, const DRadianceParams, const float4*, uint32_t, const DGatherJobs, float4*, float*, unsigned int*, unsigned long long*);
+template <int GEN>
+static GatherKernel GatherKernelOfKind(const QueryPlan& p)
+{
+	if (p.tree == TREE_GRID4) return p.stack <= 32 ? (GatherKernel)k_gather<4, 32, false, GEN> : (GatherKernel)k_gather<4, 64, false, GEN>;
+	if (p.stack <= 32) return p.prims ? (GatherKernel)k_gather<2, 32, true, GEN> : (GatherKernel)k_gather<2, 32, false, GEN>;
+	return p.prims ? (GatherKernel)k_gather<2, 64, true, GEN> : (GatherKernel)k_gather<2, 64, false, GEN>;
+}
+typedef void (*GatherResolveKernel)(const float4*, uint32_t, uint32_t, float*, float*, int, int, uint32_t);
+static_assert(RAYLIB_AMD_GATHER_IRRADIANCE + 1 == RL_GEN_HEMISPHERE && RAYLIB_AMD_GATHER_SH9 + 1 == RL_GEN_SPHERE, "gather kinds");
+static_assert(sizeof(RaylibAMDGatherPoint) == sizeof(RaylibAMDRay), "gather records");
 static_assert(RL_RADIANCE_STACK_BUDGET / ((uint64_t)RL_RADIANCE_MAX_PATH * 8 * sizeof(float) * RL_BLOCK) >= 1, "one workgroup's path stack fits the budget");
 
 // a device pointer a call may use: memory of rank 0's device
@@ -38,13 +51,13 @@ static bool OnDevice(const void* p, int device)
 }
 // The refusals of a device call (`api`): every pointer is memory of the device; the kernels read a ray as two 16-byte loads and write a 16-byte result as one
 // store (outAlign 15), the other records as 4-byte words (3).  outPrim, when given, is checked as device memory only where the call writes it (primUsed).
-static bool DevicePointersOk(const char* api, int device, const void* rays, const void* out, uintptr_t outAlign, const void* outPrim, bool primUsed)
+static bool DevicePointersOk(const char* api, const char* what, int device, const void* rays, const void* out, uintptr_t outAlign, const void* outPrim, bool primUsed)
 {
 	if (!OnDevice(rays, device) || !OnDevice(out, device) || (outPrim && primUsed && !OnDevice(outPrim, device))) {
 		Log("%s: a pointer is not device memory of device %d", api, device);
 		return false;
 	}
-	if (((uintptr_t)rays & 15u) != 0) { Log("%s: the rays are not 16-byte aligned", api); return false; }
+	if (((uintptr_t)rays & 15u) != 0) { Log("%s: the %s are not 16-byte aligned", api, what); return false; }
 	if (((uintptr_t)out & outAlign) != 0 || ((uintptr_t)outPrim & 3u) != 0) { Log("%s: the output is not %u-byte aligned", api, (unsigned)outAlign + 1u); return false; }
 	return true;
 }
@@ -72,11 +85,11 @@ static bool StageRays(RankCtx& R, const void* rays, int32_t n, size_t outBytes, 
 	return true;
 }
 // enough workgroups to fill the device once (the waves take their work from a counter: rl_k_query.inl, rl_k_radiance.inl); 0: the occupancy query failed (logged)
-static uint64_t FillingGrid(RankCtx& R, const void* kernel, int32_t n)
+static uint64_t FillingGrid(RankCtx& R, const void* kernel, uint64_t n)
 {
 	const int blocksPerCU = OccupancyOf(R, kernel);
 	if (blocksPerCU < 0) return 0;
-	return std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)R.numCUs * (uint64_t)std::max(1, blocksPerCU), ((uint64_t)n + RL_BLOCK - 1) / RL_BLOCK));
+	return std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)R.numCUs * (uint64_t)std::max(1, blocksPerCU), (n + RL_BLOCK - 1) / RL_BLOCK));
 }
 // A synchronous call on `st`, around its launch: the counters cleared and the first event in front of the kernel ...
 static bool BeginSync(RankCtx& R, hipStream_t st)
@@ -114,7 +127,7 @@ bool DeviceTraceRays(Scene& sc, int32_t kind, const void* rays, int32_t n, float
 	const QueryPlan plan = PlanQuery(sc, kind, ReadRenderKnobs());
 	if (!plan.ok) { Log("RaylibAMD_TraceRays: BVH depth %u exceeds the traversal stack (64)", sc.bvh.depth); return false; }
 	const size_t outBytes = (size_t)n * (kind == RAYLIB_AMD_QUERY_ANY ? sizeof(uint32_t) : kind == RAYLIB_AMD_QUERY_CLOSEST ? sizeof(DQueryHit) : sizeof(DHitOut));
-	if (!hostMem && n > 0 && !DevicePointersOk("RaylibAMD_TraceRaysDevice", R.device, rays, out, kind == RAYLIB_AMD_QUERY_CLOSEST ? 15u : 3u, outPrim, kind == RAYLIB_AMD_QUERY_SURFACE)) return false;
+	if (!hostMem && n > 0 && !DevicePointersOk("RaylibAMD_TraceRaysDevice", "rays", R.device, rays, out, kind == RAYLIB_AMD_QUERY_CLOSEST ? 15u : 3u, outPrim, kind == RAYLIB_AMD_QUERY_SURFACE)) return false;
 	if (!UploadScene(sc)) return false;
 	DeviceSceneCopy* Cp = sc.device->copy[(size_t)R.devSlot];
 	if (!EnsureWideTree(Cp, sc, plan.tree)) return false;
@@ -143,7 +156,7 @@ bool DeviceTraceRays(Scene& sc, int32_t kind, const void* rays, int32_t n, float
 	}
 	const QueryKernel kernel = kind == RAYLIB_AMD_QUERY_ANY ? QueryKernelOfKind<RL_QK_ANY>(plan) : kind == RAYLIB_AMD_QUERY_CLOSEST ? QueryKernelOfKind<RL_QK_CLOSEST>(plan)
 	                         : QueryKernelOfKind<RL_QK_SURFACE>(plan);
-	const uint32_t blocks = (uint32_t)FillingGrid(R, (const void*)kernel, n);
+	const uint32_t blocks = (uint32_t)FillingGrid(R, (const void*)kernel, (uint64_t)n);
 	if (!blocks) return false;
 	const DSceneView view = Cp->view;
 	HIP_OK(hipMemsetAsync(counter, 0, sizeof(unsigned int), st));
@@ -157,6 +170,53 @@ bool DeviceTraceRays(Scene& sc, int32_t kind, const void* rays, int32_t n, float
 	return FinishSync(R, st, { { hostMem ? out : nullptr, dOut, outBytes }, { hostMem && dPrim ? outPrim : nullptr, dPrim, (size_t)n * sizeof(int32_t) } }, t0, stats);
 }
 
+// ---- what a radiance call and a gather share ----
+// The call up to its first launch: the plan, the refusals of a device call's pointers, the scene, its sky and the plan's tree on the device, the stream, the
+// scratch's counter and event, a synchronous call's counter block, and the stats' header.  `api` / `apiDevice`: the entry's names in the log, `what` its input records' ("rays", "points").
+struct PathCall { QueryPlan plan; DeviceSceneCopy* Cp = nullptr; hipStream_t st = nullptr; bool sync = false; };
+static bool BeginPathCall(const char* api, const char* apiDevice, const char* what, Scene& sc, RankCtx& R, const RenderKnobs& knobs, const void* in, const void* out, uintptr_t outAlign,
+                          int32_t n, bool hostMem, void* stream, PathCall& U, RaylibAMDStats& stats)
+{
+	U.plan = PlanRadiance(sc, knobs);
+	if (!U.plan.ok) { Log("%s: BVH depth %u exceeds the traversal stack (64)", api, sc.bvh.depth); return false; }
+	if (!hostMem && n > 0 && !DevicePointersOk(apiDevice, what, R.device, in, out, outAlign, nullptr, false)) return false;
+	if (!UploadScene(sc) || !SyncSky(sc)) return false;
+	U.Cp = sc.device->copy[(size_t)R.devSlot];
+	if (!EnsureWideTree(U.Cp, sc, U.plan.tree)) return false;
+	U.st = stream ? (hipStream_t)stream : R.stream;
+	U.sync = !stream;
+	if (!R.radCounter.Grow(sizeof(unsigned int))) return false;
+	if (!R.radEv) HIP_OK(hipEventCreateWithFlags(&R.radEv, hipEventDisableTiming));
+	if (U.sync && !EnsureSyncStats(R)) return false;
+	StatsHeader(stats, U.plan, sc);
+	return true;
+}
+static DRadianceParams PathParams(const RaylibAMDRadianceParams& prm, uint64_t seed)
+{
+	DRadianceParams Q; memset(&Q, 0, sizeof(Q));
+	Q.seedMixed = raylib_rng_mix64(seed); Q.maxPathLength = prm.maxPathLength; Q.rayTMin = prm.rayTMin;
+	Q.sampleFirst = prm.sampleFirst; Q.sampleCount = prm.sampleCount; Q.skipDraws = prm.skipDraws;
+	Q.timeMin = prm.timeMin; Q.timeMax = prm.timeMax;
+	return Q;
+}
+// The grid of a launch of `jobs` jobs: enough workgroups to fill the device once ...
+static uint32_t PathGrid(RankCtx& R, const void* kernel, uint64_t jobs, DRadianceParams& Q)
+{
+	uint64_t blocks64 = FillingGrid(R, kernel, jobs);
+	if (!blocks64) return 0;
+	// ... but no more than whose path stack (32 bytes per bounce and resident lane) fits RL_RADIANCE_STACK_BUDGET: long paths run on a smaller grid,
+	// which changes no result (a job's arithmetic does not depend on the lane that takes it)
+	const size_t depthSlots = (size_t)(Q.maxPathLength > 1 ? Q.maxPathLength : 1);
+	const uint64_t stackPerBlock = (uint64_t)depthSlots * 8 * sizeof(float) * RL_BLOCK;
+	blocks64 = std::min<uint64_t>(blocks64, RL_RADIANCE_STACK_BUDGET / stackPerBlock);   // (>= 1: RaylibAMD_TraceRadiance refuses a longer path)
+	const uint32_t blocks = (uint32_t)blocks64;
+	Q.stackStride = blocks * RL_BLOCK;
+	// the path stack of the grid: one record per bounce and resident lane.  The scratch is one per rank: a launch waits, on its stream, for the launch before it
+	// (whatever stream that ran on), and growing the stack frees it with hipFree, which waits for the device
+	if (!R.radStack.Grow(depthSlots * 8 * Q.stackStride * sizeof(float))) return 0;
+	return blocks;
+}
+
 bool DeviceTraceRadiance(Scene& sc, const RaylibAMDRadianceParams& prm, uint64_t seed, const void* rays, int32_t n, float* out, bool hostMem, void* stream,
                          RaylibAMDStats& stats)
 {
@@ -165,52 +225,107 @@ bool DeviceTraceRadiance(Scene& sc, const RaylibAMDRadianceParams& prm, uint64_t
 	if (!EnsureRuntime()) return false;
 	RankCtx& R = Rank0();
 	HIP_OK(hipSetDevice(R.device));
-	const QueryPlan plan = PlanRadiance(sc, ReadRenderKnobs());
-	if (!plan.ok) { Log("RaylibAMD_TraceRadiance: BVH depth %u exceeds the traversal stack (64)", sc.bvh.depth); return false; }
-	if (!hostMem && n > 0 && !DevicePointersOk("RaylibAMD_TraceRadianceDevice", R.device, rays, out, 15u, nullptr, false)) return false;
-	if (!UploadScene(sc) || !SyncSky(sc)) return false;
-	DeviceSceneCopy* Cp = sc.device->copy[(size_t)R.devSlot];
-	if (!EnsureWideTree(Cp, sc, plan.tree)) return false;
-	const hipStream_t st = stream ? (hipStream_t)stream : R.stream;
-	const bool sync = !stream;
-	if (!R.radCounter.Grow(sizeof(unsigned int))) return false;
-	if (!R.radEv) HIP_OK(hipEventCreateWithFlags(&R.radEv, hipEventDisableTiming));
-	if (sync && !EnsureSyncStats(R)) return false;
-	StatsHeader(stats, plan, sc);
+	PathCall U;
+	if (!BeginPathCall("RaylibAMD_TraceRadiance", "RaylibAMD_TraceRadianceDevice", "rays", sc, R, ReadRenderKnobs(), rays, out, 15u, n, hostMem, stream, U, stats)) return false;
 	if (n == 0) return true;
-	const RadianceKernel kernel = RadianceKernelFor(plan);
-	uint64_t blocks64 = FillingGrid(R, (const void*)kernel, n);
-	if (!blocks64) return false;
-	// ... but no more than whose path stack (32 bytes per bounce and resident lane) fits RL_RADIANCE_STACK_BUDGET: long paths run on a smaller grid,
-	// which changes no result (a job's arithmetic does not depend on the lane that takes it)
-	const size_t depthSlots = (size_t)(prm.maxPathLength > 1 ? prm.maxPathLength : 1);
-	const uint64_t stackPerBlock = (uint64_t)depthSlots * 8 * sizeof(float) * RL_BLOCK;
-	blocks64 = std::min<uint64_t>(blocks64, RL_RADIANCE_STACK_BUDGET / stackPerBlock);   // (>= 1: RaylibAMD_TraceRadiance refuses a longer path)
-	const uint32_t blocks = (uint32_t)blocks64;
-	DRadianceParams Q; memset(&Q, 0, sizeof(Q));
-	Q.seedMixed = raylib_rng_mix64(seed); Q.maxPathLength = prm.maxPathLength; Q.rayTMin = prm.rayTMin;
-	Q.sampleFirst = prm.sampleFirst; Q.sampleCount = prm.sampleCount; Q.skipDraws = prm.skipDraws;
-	Q.stackStride = blocks * RL_BLOCK; Q.timeMin = prm.timeMin; Q.timeMax = prm.timeMax;
-	// the path stack of the grid: one record per bounce and resident lane.  The scratch is one per rank: a launch waits, on its stream, for the launch before it
-	// (whatever stream that ran on), and growing the stack frees it with hipFree, which waits for the device
-	if (!R.radStack.Grow(depthSlots * 8 * Q.stackStride * sizeof(float))) return false;
+	const hipStream_t st = U.st;
+	const RadianceKernel kernel = RadianceKernelFor(U.plan);
+	DRadianceParams Q = PathParams(prm, seed);
+	const uint32_t blocks = PathGrid(R, (const void*)kernel, (uint64_t)n, Q);
+	if (!blocks) return false;
 	const float4* dRays = (const float4*)rays; float4* dOut = (float4*)out;
 	const size_t outBytes = (size_t)n * sizeof(float4);
 	if (hostMem) {
 		if (!StageRays(R, rays, n, outBytes, st)) return false;
 		dRays = R.qRays.ptr; dOut = (float4*)R.qOut.ptr;
 	}
-	const DSceneView view = Cp->view;
+	const DSceneView view = U.Cp->view;
 	const SkyRot skyRot = sc.device->skyRot;
 	if (R.radEvUsed) HIP_OK(hipStreamWaitEvent(st, R.radEv, 0));
 	HIP_OK(hipMemsetAsync(R.radCounter.ptr, 0, sizeof(unsigned int), st));
-	if (sync && !BeginSync(R, st)) return false;
-	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RL_BLOCK), 0, st, view, skyRot, Q, dRays, (uint32_t)n, dOut, R.radStack.ptr, R.radCounter.ptr, sync ? R.qStats.ptr : nullptr);
+	if (U.sync && !BeginSync(R, st)) return false;
+	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RL_BLOCK), 0, st, view, skyRot, Q, dRays, (uint32_t)n, dOut, R.radStack.ptr, R.radCounter.ptr, U.sync ? R.qStats.ptr : nullptr);
 	HIP_OK(hipGetLastError());
 	HIP_OK(hipEventRecord(R.radEv, st));
 	R.radEvUsed = true;
-	if (!sync) return true;
+	if (!U.sync) return true;
 	return FinishSync(R, st, { { hostMem ? out : nullptr, dOut, outBytes } }, t0, stats);
+}
+
+// RaylibAMD_Gather: n points x prm.sampleCount samples as the launches of rl_plan.cc PlanGatherCut -- sample ranges of all the points while one sample of each
+// fits the sample buffer, point ranges too when not -- each followed by its resolve.  The sums of a point range carry from launch to launch in gAcc, so the
+// sum's order does not depend on how the call was cut.  The loop runs over the launch index, 64-bit, and ends at the cut's count.
+bool DeviceGather(Scene& sc, int32_t kind, const RaylibAMDRadianceParams& prm, uint64_t seed, const void* points, int32_t n, float* out, bool hostMem, void* stream,
+                  RaylibAMDStats& stats)
+{
+	const auto t0 = std::chrono::steady_clock::now();
+	std::lock_guard<std::mutex> lk(Rt().lock);
+	if (!EnsureRuntime()) return false;
+	RankCtx& R = Rank0();
+	HIP_OK(hipSetDevice(R.device));
+	const RenderKnobs knobs = ReadRenderKnobs();
+	const bool sphere = kind == RAYLIB_AMD_GATHER_SH9;
+	const uint32_t outFloats = sphere ? 27u : 4u, sums = sphere ? 27u : 3u;
+	PathCall U;
+	if (!BeginPathCall("RaylibAMD_Gather", "RaylibAMD_GatherDevice", "points", sc, R, knobs, points, out, sphere ? 3u : 15u, n, hostMem, stream, U, stats)) return false;
+	if (n == 0) return true;
+	const hipStream_t st = U.st;
+	const GatherKernel kernel = sphere ? GatherKernelOfKind<RL_GEN_SPHERE>(U.plan) : GatherKernelOfKind<RL_GEN_HEMISPHERE>(U.plan);
+	const GatherResolveKernel resolve = sphere ? (GatherResolveKernel)k_gather_resolve<RL_GEN_SPHERE> : (GatherResolveKernel)k_gather_resolve<RL_GEN_HEMISPHERE>;
+	// the cut (rl_plan.cc PlanGatherCut): the first launch is the largest, so its grid -- and the path stack of that grid -- serves every launch of the call; a
+	// smaller launch on it leaves waves that find the counter drained and end
+	const uint32_t N = (uint32_t)n;
+	const GatherCut cut = PlanGatherCut(N, prm.sampleCount, sphere, knobs);
+	const uint64_t slotBytes = (sphere ? 2u : 1u) * sizeof(float4);
+	if (!R.gSamples.Grow((size_t)cut.pointsPer * cut.samplesPer * slotBytes)) return false;   // (as the path stack: growing waits for the device)
+	if (cut.sampleRanges > 1 && !R.gAcc.Grow((size_t)cut.pointsPer * sums * sizeof(float))) return false;
+	DRadianceParams Q = PathParams(prm, seed);
+	const uint32_t blocks = PathGrid(R, (const void*)kernel, (uint64_t)cut.pointsPer * cut.samplesPer, Q);
+	if (!blocks) return false;
+	// a synchronous call times its trace launches apart from the rest (stats.traceKernelMs), with an event pair per launch -- up to RL_GATHER_TIMED launches
+	const bool timed = U.sync && cut.launches <= RL_GATHER_TIMED;
+	if (timed) while (R.gEv.size() < 2 * cut.launches) { hipEvent_t e; HIP_OK(hipEventCreate(&e)); R.gEv.push_back(e); }
+	const float4* dPoints = (const float4*)points; float* dOut = out;
+	const size_t outBytes = (size_t)n * outFloats * sizeof(float);
+	if (hostMem) {
+		if (!StageRays(R, points, n, outBytes, st)) return false;
+		dPoints = R.qRays.ptr; dOut = (float*)R.qOut.ptr;
+	}
+	const DSceneView view = U.Cp->view;
+	const SkyRot skyRot = sc.device->skyRot;
+	if (R.radEvUsed) HIP_OK(hipStreamWaitEvent(st, R.radEv, 0));
+	if (U.sync && !BeginSync(R, st)) return false;
+	auto enqueue = [&](uint64_t k) -> bool {
+		const GatherLaunch L = GatherLaunchAt(cut, N, prm.sampleCount, k);
+		const uint32_t jobs = L.numPoints * L.numSamples;   // (<= slots <= RL_GATHER_MAX_SLOTS: a launch's jobs fit 32 bits with room for the counter's overshoot)
+		DGatherJobs J; J.pointFirst = L.pointFirst; J.numPoints = L.numPoints; J.sampleBase = L.sampleBase;
+		HIP_OK(hipMemsetAsync(R.radCounter.ptr, 0, sizeof(unsigned int), st));
+		if (timed) HIP_OK(hipEventRecord(R.gEv[2 * k], st));
+		hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RL_BLOCK), 0, st, view, skyRot, Q, dPoints, jobs, J, R.gSamples.ptr, R.radStack.ptr, R.radCounter.ptr,
+		                   U.sync ? R.qStats.ptr : nullptr);
+		HIP_OK(hipGetLastError());
+		if (timed) HIP_OK(hipEventRecord(R.gEv[2 * k + 1], st));
+		hipLaunchKernelGGL(resolve, dim3((L.numPoints + RL_BLOCK - 1) / RL_BLOCK), dim3(RL_BLOCK), 0, st, (const float4*)R.gSamples.ptr, L.numPoints, L.numSamples,
+		                   R.gAcc.ptr, dOut + (size_t)L.pointFirst * outFloats, (int)L.first, (int)L.last, prm.sampleCount);
+		HIP_OK(hipGetLastError());
+		return true;
+	};
+	bool ok = true;
+	for (uint64_t k = 0; ok && k < cut.launches; ++k) ok = enqueue(k);
+	// the event behind whatever was enqueued, a failed call's launches included: the next call on any stream must wait for them before it touches the scratch
+	const hipError_t evErr = hipEventRecord(R.radEv, st);
+	if (evErr == hipSuccess) R.radEvUsed = true;
+	else { Log("HIP error %s recording the gather's event", hipGetErrorName(evErr)); (void)hipStreamSynchronize(st); }   // (no event: the scratch is free again only once the stream is idle)
+	if (!ok || evErr != hipSuccess) return false;
+	if (!U.sync) return true;
+	if (!FinishSync(R, st, { { hostMem ? out : nullptr, dOut, outBytes } }, t0, stats)) return false;
+	stats.traceLaunches = (uint32_t)std::min<uint64_t>(cut.launches, 0xffffffffull);
+	if (timed) {
+		double traceMs = 0.0;
+		for (uint64_t k = 0; k < cut.launches; ++k) { float ms = 0.0f; HIP_OK(hipEventElapsedTime(&ms, R.gEv[2 * k], R.gEv[2 * k + 1])); traceMs += ms; }
+		stats.traceKernelMs = traceMs;
+	}
+	return true;
 }
 
 } // namespace rl

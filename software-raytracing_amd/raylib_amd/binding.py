@@ -201,6 +201,84 @@ def trace_radiance(lib, scene, rays, max_path=5, tmin=1e-4, sample_first=0, samp
     return out
 
 
+class GatherPoint(C.Structure):
+    """include/raylib_amd.h RaylibAMDGatherPoint (32 bytes): pos, time, normal, stream."""
+    _fields_ = [("pos", C.c_float * 3), ("time", C.c_float), ("normal", C.c_float * 3), ("stream", C.c_uint32)]
+
+
+class GatherParams(C.Structure):
+    """include/raylib_amd.h RaylibAMDGatherParams."""
+    _fields_ = [("kind", C.c_int32), ("maxPathLength", C.c_int32), ("rayTMin", C.c_float), ("sampleFirst", C.c_uint32), ("sampleCount", C.c_uint32),
+                ("skipDraws", C.c_uint32), ("timeMin", C.c_float), ("timeMax", C.c_float)]
+
+
+class GatherCut(C.Structure):
+    """include/raylib_amd.h RaylibAMDGatherCut."""
+    _fields_ = [("pointsPerLaunch", C.c_uint32), ("samplesPerLaunch", C.c_uint32), ("pointRanges", C.c_uint64), ("sampleRanges", C.c_uint64), ("launches", C.c_uint64),
+                ("pointFirst", C.c_uint32), ("numPoints", C.c_uint32), ("sampleBase", C.c_uint32), ("numSamples", C.c_uint32), ("first", C.c_int32), ("last", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def plan_gather_cut(lib, kind, n, sample_count, launch=0):
+    """RaylibAMD_PlanGatherCut: the cut of n points x sample_count samples into launches and launch `launch` of it, as a dict; None when the call refuses."""
+    prm = GatherParams(int(kind), 5, 1e-4, 0, int(sample_count), 0, 0.0, 0.0)
+    c = GatherCut()
+    return c.as_dict() if lib.RaylibAMD_PlanGatherCut(C.byref(prm), int(n), int(launch), C.byref(c)) == 1 else None
+
+
+GATHER_IRRADIANCE, GATHER_SH9 = 0, 1                  # RAYLIB_AMD_GATHER_*
+_GATHER_FLOATS = {GATHER_IRRADIANCE: 4, GATHER_SH9: 27}
+
+
+def gather(lib, scene, points, kind, max_path=5, tmin=1e-4, sample_first=0, sample_count=1, skip_draws=0):
+    """Irradiance or SH9 probes gathered at points (RaylibAMD_Gather / RaylibAMD_GatherDevice).
+
+    points: (n, 8) float32 -- pos xyz, time, normal xyz, and the stream index as the uint32 whose bits the last column holds.  A NumPy array goes through the
+    host entry and returns an (n, 4) (GATHER_IRRADIANCE) or (n, 27) (GATHER_SH9) float32 array; a float32 torch tensor on the device goes through the device
+    entry under the rules of trace_radiance and returns a tensor of that shape.  Raises RuntimeError when the library refuses the call."""
+    kind = int(kind)
+    if kind not in _GATHER_FLOATS:
+        raise ValueError("unknown gather kind %r" % kind)
+    prm = GatherParams(kind, int(max_path), float(tmin), int(sample_first), int(sample_count), int(skip_draws), 0.0, 0.0)
+    if isinstance(points, np.ndarray):
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 8)
+        n = len(p)
+        out = np.zeros((n, _GATHER_FLOATS[kind]), np.float32)
+        ok = lib.RaylibAMD_Gather(scene, C.byref(prm), p.ctypes.data_as(C.POINTER(GatherPoint)), n, out.ctypes.data_as(C.POINTER(C.c_float)))
+        if ok != 1:
+            raise RuntimeError("RaylibAMD_Gather refused the call")
+        return out
+    import torch
+    if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float32):
+        raise TypeError("points: a float32 NumPy array or a float32 torch tensor on the device")
+    p = points.reshape(-1, 8).contiguous()
+    n = p.shape[0]
+    out = torch.empty((n, _GATHER_FLOATS[kind]), dtype=torch.float32, device=p.device)
+    if n:
+        prm.timeMin, prm.timeMax = float(p[:, 3].min()), float(p[:, 3].max())
+    stream = torch.cuda.current_stream(p.device)
+    if stream.cuda_stream == 0:
+        stream.synchronize()   # (as trace_rays: the library's stream is not ordered against torch's default stream)
+    ok = lib.RaylibAMD_GatherDevice(scene, C.byref(prm), C.cast(C.c_void_p(p.data_ptr()), C.POINTER(GatherPoint)), n,
+                                    C.cast(C.c_void_p(out.data_ptr()), C.POINTER(C.c_float)), C.c_void_p(stream.cuda_stream))
+    if ok != 1:
+        raise RuntimeError("RaylibAMD_GatherDevice refused the call")
+    return out
+
+
+def gather_directions_host(lib, points, kind, seed, sample=0, sample_first=0, skip_draws=0):
+    """RaylibAMD_GatherDirectionsHost: the direction of sample `sample` of every point, (n, 3) float32, with the host's libm; no device."""
+    prm = GatherParams(int(kind), 0, 0.0, int(sample_first), 1, int(skip_draws), 0.0, 0.0)
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 8)
+    out = np.zeros((len(p), 3), np.float32)
+    ok = lib.RaylibAMD_GatherDirectionsHost(C.byref(prm), p.ctypes.data_as(C.POINTER(GatherPoint)), len(p), int(seed), int(sample), out.ctypes.data_as(C.POINTER(C.c_float)))
+    if ok != 1:
+        raise RuntimeError("RaylibAMD_GatherDirectionsHost refused the call")
+    return out
+
+
 # Per-ray / per-unit algorithmic byte constants of the flat layout (csrc/rl_device.h)
 NODE_B, TRI_B, SHADE_B, TEXEL_B, PIXEL_B = 64, 64, 64, 16, 16
 
@@ -273,6 +351,10 @@ _EXPORTS = {
     "RaylibAMD_TraceRadiance": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(PathRay), C.c_int32, C.POINTER(C.c_float)]),
     "RaylibAMD_TraceRadianceDevice": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(PathRay), C.c_int32, C.POINTER(C.c_float), C.c_void_p]),
     "RaylibAMD_PlanRadiance": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(QueryPlan)]),
+    "RaylibAMD_Gather": (C.c_int32, [C.c_void_p, C.POINTER(GatherParams), C.POINTER(GatherPoint), C.c_int32, C.POINTER(C.c_float)]),
+    "RaylibAMD_GatherDevice": (C.c_int32, [C.c_void_p, C.POINTER(GatherParams), C.POINTER(GatherPoint), C.c_int32, C.POINTER(C.c_float), C.c_void_p]),
+    "RaylibAMD_GatherDirectionsHost": (C.c_int32, [C.POINTER(GatherParams), C.POINTER(GatherPoint), C.c_int32, C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]),
+    "RaylibAMD_PlanGatherCut": (C.c_int32, [C.POINTER(GatherParams), C.c_int32, C.c_uint64, C.POINTER(GatherCut)]),
     "RaylibAMD_VerifyExactMath": (C.c_int32, [C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "RaylibAMD_CullCells": (C.c_int32, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_float)]),
     "RaylibAMD_SceneNumTriangles": (C.c_int32, [C.c_void_p]),

@@ -9,6 +9,7 @@ bool DeviceRenderViews(Scene&, const RenderRequest&, const DCamera*, uint32_t, v
 bool DeviceClosestHit(Scene&, const float*, int32_t, float, void*) { return false; }
 bool DeviceTraceRays(Scene&, int32_t, const void*, int32_t, float, void*, int32_t*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceTraceRadiance(Scene&, const RaylibAMDRadianceParams&, uint64_t, const void*, int32_t, float*, bool, void*, RaylibAMDStats&) { return false; }
+bool DeviceGather(Scene&, int32_t, const RaylibAMDRadianceParams&, uint64_t, const void*, int32_t, float*, bool, void*, RaylibAMDStats&) { return false; }
 bool DevicePostProcess(Image&) { return false; }
 void* DeviceImagePixels(Image&) { return nullptr; }
 bool DeviceReadback(Image&) { return false; }
