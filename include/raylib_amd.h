@@ -331,6 +331,11 @@ RAYLIB_API int32_t RaylibAMD_VerifyExactMath(int32_t which, uint64_t* outMismatc
  * k_verify_lazy_refl): outUnsafe = events the guard passed although a component of the reflectance or the scattering pdf is not finite (must be 0),
  * outGuardFailed = events it refused.  Returns 1 when the sweep ran. */
 RAYLIB_API int32_t RaylibAMD_VerifyLazyRefl(uint32_t n, uint64_t seed, uint64_t* outEvents, uint64_t* outUnsafe, uint64_t* outGuardFailed);
+/* The same instance's decision to leave an event's scattering pdf unevaluated, swept over the same n events (csrc/rl_render_lazy.hip k_verify_lazy_pdf):
+ * outWrong = events decided "quick" whose pdf is not positive, whose ScatteringPdf value or recomputed half vector is not finite, or whose vertex record (of
+ * either form) does not give the fold the eagerly evaluated bits of both (must be 0), outRefused = events that evaluate the pdf after all.  Returns 1 when the
+ * sweep ran. */
+RAYLIB_API int32_t RaylibAMD_VerifyLazyPdf(uint32_t n, uint64_t seed, uint64_t* outEvents, uint64_t* outWrong, uint64_t* outRefused);
 
 /* ---- host-logic introspection (no GPU needed) ---------------------------------- */
 /* Flattened scene as the kernels see it.  Triangle record = 26 words, material record =

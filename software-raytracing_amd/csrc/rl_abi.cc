@@ -739,6 +739,16 @@ int32_t RaylibAMD_VerifyLazyRefl(uint32_t n, uint64_t seed, uint64_t* outEvents,
 	return 1;
 }
 
+int32_t RaylibAMD_VerifyLazyPdf(uint32_t n, uint64_t seed, uint64_t* outEvents, uint64_t* outWrong, uint64_t* outRefused)
+{
+	uint64_t out[3] = { 0, 0, 0 };
+	if (!DeviceVerifyLazyPdf(n, seed, out)) return 0;
+	if (outEvents) *outEvents = out[0];
+	if (outWrong) *outWrong = out[1];
+	if (outRefused) *outRefused = out[2];
+	return 1;
+}
+
 int32_t RaylibAMD_ClosestHit(SceneHandle sh, const float* rays, int32_t n, float tMin, void* outHits)
 {
 	Scene* s = (Scene*)sh;

@@ -478,6 +478,61 @@ __device__ __forceinline__ bool Scatter(const DSceneView& S, const Mat& m, V3 in
 	}
 }
 
+// ---- the ScatteringPdf part of a lazy event, decided without evaluating it ----
+// Scatter ends with D = DistributionBeckmann(N, wh, r), sp = D |wh.z|, pdf = sp / (4 Wo.Wh) of the recomputed half vector wh.  On an unlit path (98 % of the headline
+// frame's) the kernel reads two predicates of them and no value: pdf > 0 (does the path go on?) and |sp| < inf (LazyVertexSafe).  LazyPdfQuick decides both from the
+// floats DistributionBeckmann would divide -- c = wh.z (flipped: >= 0), A = 1 - c c, B = r r c -- and from w = Wo.Wh.  Every compare is false on NaN.
+// Why LazyPdfQuick, with r in [2^-10, 1] (SceneLazyRefl), implies 0 < pdf and 0 < sp < inf as Scatter computes them:
+//   wh:  wh = v rcp1_(|v|) with c = v.z k in [2^-10, 1 + 2^-20]: |v| is finite and not zero (k = 0 or k = inf leaves c a zero or NaN, a NaN length a NaN) and
+//        then every component of v is finite and at most |v| (1 + 2^-22) in magnitude: wh.x and wh.y are finite, within a few ulps of [-1, 1].  So dot(N, wh) with
+//        N = (0, 0, 1) is 0 wh.x + 0 wh.y + c = c exactly (c is not a zero), cosH = c, cosH2 = fl(c c), and DistributionBeckmann's operands are A and B.
+//   exp_x = fl(A / B): B = fl(rr c) >= 2^-30 is a positive normal number and 32 B is exact; A <= 32 B gives exp_x <= 32 (division is monotone, 32 a float).
+//        A < 0 needs c > 1, where c <= 1 + 2^-20 gives A >= -(2^-19 + 2^-40) and B >= rr >= 2^-20: exp_x >= -2.000002.  exp_x in [-2.1, 32].
+//   num = 1 * exp_(-exp_x) in [1.2e-14, 8.2]: a positive normal number (exp_ is within an ulp of e^x).
+//   denom = pi rr c^4 in [pi 2^-60, pi (1 + 2^-20)^4] = [2.7e-18, 3.2], positive and normal at every step (rr >= 2^-20, cosH2 >= 2^-20).
+//   D = num / denom in [3.9e-15, 3.1e18]; sp = D c in [3.8e-18, 3.1e18]: both positive, finite and far from the subnormals, whatever the last-bit roundings
+//        are.  4 w lies in (0, 8] (or is flushed to +0), and pdf = sp / (4 w) >= 4.7e-19: positive, +inf where w is tiny, never NaN or a zero.
+//   w:   only w > 0 is asked, not LazyVertexSafe's w >= 2^-10: an event between the two continues with the pdf's sign decided here, and fails that guard
+//        behind it as it always did.  (Of the device sweep's events 9.1 % have w <= 0 -- its Wo.z = 0 inputs, the event's pdf is not positive and the path ends --
+//        and 11.3 % lie in between; with w >= 2^-10 here every one of those would evaluate the pdf for nothing.)
+// A quick event therefore continues (pdf > 0) and passes LazyVertexSafe's sp compare without D, sp or pdf being computed; the record's sp slot holds c, and the
+// fold computes sp = DistributionBeckmann(N, (0, 0, c), r) |c| and pdf = sp / (4 Wo.Wh) -- the same operations on the same floats, dot(N, (0, 0, c)) being c as
+// above -- for the lit paths alone (LazyRecordPdf).  An event that is not quick (a grazing half vector, a sampled D below e^-32, Wo in or behind the microfacet's
+// plane, any NaN) evaluates the three as Scatter does and its record says so (RL_LAZY_REC_EXACT_SP).  RaylibAMD_VerifyLazyPdf sweeps the claim on the device.
+__device__ __forceinline__ bool LazyPdfQuick(float c, float roughness, float w)
+{
+	const float rr = roughness * roughness, A = 1.0f - c * c, B = rr * c;
+	return c >= 0x1p-10f && c <= 1.0f + 0x1p-20f && A <= 32.0f * B && w > 0.0f && w <= 2.0f;
+}
+// wh: the recomputed half vector, flipped to wh.z >= 0.  Returns whether sp and pdf are the event's values (false: sp holds wh.z, and pdf a stand-in that is
+// positive as the event's is).  The slow side is entered by the whole wave when one lane needs it (DivSpecular's form: no divergent region around the division
+// sequences), and changes nothing in a quick lane.
+__device__ __forceinline__ bool LazyScatterPdf(V3 N, V3 Wo, V3 Wh, V3 wh, float roughness, float& sp, float& pdf)
+{
+	const float w = dot(Wo, Wh);
+	const bool quick = LazyPdfQuick(wh.z, roughness, w);
+	sp = wh.z;
+	pdf = 1.0f;
+	if (rtm::wave_any_(!quick)) {
+		const float D = DistributionBeckmann(N, wh, roughness);
+		const float spExact = D * absDot(wh, N);
+		const float pdfExact = spExact / (4.0f * dot(Wo, Wh));
+		if (!quick) { sp = spExact; pdf = pdfExact; }
+	}
+	return !quick;
+}
+// sp and pdf of a recorded microfacet vertex (r0 = Wo, sp slot; r1 = Wh, material index and RL_LAZY_REC_EXACT_SP), bit for bit what Scatter computes at the event
+__device__ __forceinline__ void LazyRecordPdf(float4 r0, float4 r1, float roughness, float& sp, float& pdf)
+{
+	const V3 Wo = v3(r0.x, r0.y, r0.z), Wh = v3(r1.x, r1.y, r1.z);
+	sp = r0.w;
+	if ((__float_as_int(r1.w) & RL_LAZY_REC_EXACT_SP) == 0) {
+		const V3 N = v3(0.0f, 0.0f, 1.0f), wh = v3(0.0f, 0.0f, r0.w);
+		const float D = DistributionBeckmann(N, wh, roughness);
+		sp = D * absDot(wh, N);
+	}
+	pdf = sp / (4.0f * dot(Wo, Wh));
+}
 // ---- k_trace's lazy-reflectance instance (rl_k_trace.inl RL_LAZY_REFL; rl_plan.cc TracePlan::lazy) ----
 // A sample is the fold L_k = (0 + refl_k * L_{k+1} * sp_k / pdf_k) + E_k back to the camera.  On a path whose terminal L and every E are +0 each refl_k is
 // multiplied by an exact zero: the sample is (+0, +0, +0) whatever the reflectances are -- as long as they and sp are finite (below).  The instance therefore
@@ -485,12 +540,14 @@ __device__ __forceinline__ bool Scatter(const DSceneView& S, const Mat& m, V3 in
 // (FoldLazyVertex) for the paths with light in them alone.  Plain scenes whose triangles carry microfacet and mirror materials only (SceneLazyRefl): no
 // texture lookups, N = (0, 0, 1).  A mirror's reflectance is its albedo, a constant there is nothing to skip of; its record holds the material alone.
 // Scatter's mirror arm, or its microfacet arm without the reflectance: the same draws, the same statements, the same bits in Wo, Wh, outD, pdf and sp.
-__device__ __forceinline__ void ScatterLazy(const DSceneView& S, const Mat& m, V3 inD, const Surf& s, Rng& g, Counters& c, V3& Wo, V3& Wh, V3& outD, float& pdf, float& sp)
+// pdf and sp are what LazyScatterPdf (above) leaves: exactSp says which.
+__device__ __forceinline__ void ScatterLazy(const DSceneView& S, const Mat& m, V3 inD, const Surf& s, Rng& g, Counters& c, V3& Wo, V3& Wh, V3& outD, float& pdf, float& sp, bool& exactSp)
 {
 	if (m.type == MAT_MIRROR) {   // material.h:149-162
 		outD = reflect(inD, s.n);
 		pdf = 1.0f;
 		sp = 1.0f;
+		exactSp = false;                      // (a mirror's record is the material alone: FoldLazyVertex reads neither slot nor flag)
 		Wo = v3(0.0f, 0.0f, 1.0f); Wh = Wo;   // (LazyVertexSafe passes: the albedo is finite, SceneLazyRefl)
 		return;
 	}
@@ -512,9 +569,7 @@ __device__ __forceinline__ void ScatterLazy(const DSceneView& S, const Mat& m, V
 	V3 wi = WorldToLocal(s, WiW);
 	V3 wh = normalize(wo + wi);
 	if (wh.z < 0.0f) wh.z = -wh.z;
-	float D = DistributionBeckmann(N, wh, roughness);
-	sp = D * absDot(wh, N);
-	pdf = sp / (4.0f * dot(Wo, Wh));
+	exactSp = LazyScatterPdf(N, Wo, Wh, wh, roughness, sp, pdf);
 }
 // May the vertex's reflectance go unevaluated on an unlit path?  refl * 0 * sp / pdf is a zero, and (0 + that) + 0 is +0, only if every component of refl
 // and sp are finite (pdf > 0 is the caller's condition for a recorded vertex; a NaN or an infinity in refl makes the reference's sample NaN).  A vertex that
@@ -541,8 +596,8 @@ __device__ __forceinline__ bool LazyVertexSafe(V3 Wo, V3 Wh, float sp)
 	return fabsf(Wh.z) >= 0x1p-10f && fabsf(sp) < INFINITY && dot(Wo, Wh) >= 0x1p-10f;
 }
 __device__ __forceinline__ bool AnyBitSet(V3 a) { return (__float_as_uint(a.x) | __float_as_uint(a.y) | __float_as_uint(a.z)) != 0u; }
-// One step of the fold at a recorded vertex (r0 = Wo, sp; r1 = Wh, material index; m = that material): the reflectance, the pdf as Scatter computes it from the
-// same values, the emission (plain scenes: the material's), and the fold's statement exactly as k_trace writes it.
+// One step of the fold at a recorded vertex (r0 = Wo, sp slot; r1 = Wh, material index and flag; m = that material): the reflectance, sp and the pdf as Scatter
+// computes them from the same values (LazyRecordPdf), the emission (plain scenes: the material's), and the fold's statement exactly as k_trace writes it.
 __device__ __forceinline__ V3 FoldLazyVertex(const Mat& m, float4 r0, float4 r1, V3 L)
 {
 	if (m.type == MAT_MIRROR) {   // refl = albedo, sp = pdf = 1, nothing emitted
@@ -552,12 +607,12 @@ __device__ __forceinline__ V3 FoldLazyVertex(const Mat& m, float4 r0, float4 r1,
 		return radiance;
 	}
 	const V3 Wo = v3(r0.x, r0.y, r0.z), Wh = v3(r1.x, r1.y, r1.z);
-	const float sp = r0.w;
 	const V3 N = v3(0.0f, 0.0f, 1.0f);
 	const V3 Wi = reflect(-Wo, Wh);
 	const float NdotWi = absDot(N, Wi);
 	const V3 refl = ReflFromRecord<true>(m.albedo, m.roughness, m.metallic, N, Wo, Wh, Wi, NdotWi);
-	const float pdf = sp / (4.0f * dot(Wo, Wh));
+	float sp, pdf;
+	LazyRecordPdf(r0, r1, m.roughness, sp, pdf);
 	const V3 E = m.emissive;
 	V3 radiance = v3s(0.0f);
 	radiance = radiance + refl * L * sp / pdf;

@@ -281,6 +281,10 @@ struct DViews {
 #define RL_LAZY_ROUGHNESS_MAX 1.0f          /* what the loader and RaylibAMD_CreateMaterial saturate a microfacet roughness to */
 #define RL_LAZY_COLOR_MAX 16.0f      /* |albedo|, |metallic|, either sign (a mirror's albedo is not saturated) */
 #define RL_LAZY_MAX_PATH 4096        /* maxPathLength: a direction's length stays within 2^-8 of 1 over that many reflections */
+/* A vertex record's last word is the material index; this bit of it says what the record's sp slot holds (rl_dev_shade.h LazyScatterPdf): set, the event's
+ * ScatteringPdf value itself; clear, the half vector's z it is a function of (a mirror's record: clear, and its slot is not read). */
+#define RL_LAZY_REC_EXACT_SP 0x40000000
+#define RL_LAZY_REC_MAT(w) (__float_as_int(w) & ~RL_LAZY_REC_EXACT_SP)
 struct DLitList {
 	float* entries;              // float4 units
 	uint32_t* ctl;

@@ -364,12 +364,13 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 #if RL_LAZY_REFL
 				V3 Wo = v3s(0.0f), Wh = v3s(0.0f), outD = v3s(0.0f);
 				float pdf = 0.0f, sp = 0.0f;
-				ScatterLazy(S, m, d, s, g, c, Wo, Wh, outD, pdf, sp);
+				bool exactSp = false;
+				ScatterLazy(S, m, d, s, g, c, Wo, Wh, outD, pdf, sp, exactSp);
 				RL_SUBSTAMP(1);
 				const V3 E = Emitted(S, m, s, c);
 				if (AnyBitSet(E)) lit = true;
 				if (pdf > 0.0f) {
-					const bool safe = LazyVertexSafe(Wo, Wh, sp);
+					const bool safe = LazyVertexSafe(Wo, Wh, sp);   // (a quick event's sp slot holds wh.z, finite like the sp it stands for: LazyPdfQuick)
 					if (!safe) lit = true;
 					const bool last = depth + 1 >= P.maxPathLength;
 					if (last && safe) {
@@ -377,10 +378,10 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 						L = v3s(0.0f) + E;
 						done = true;
 					} else {
-						// the vertex record (Wo, sp | Wh, material): what ReflFromRecord, the pdf and the emission are functions of
+						// the vertex record (Wo, sp or wh.z | Wh, material and which of the two): what ReflFromRecord, sp, the pdf and the emission are functions of
 						store = true;
 						rec0 = make_float4(Wo.x, Wo.y, Wo.z, sp);
-						rec1 = make_float4(Wh.x, Wh.y, Wh.z, __int_as_float(mi));
+						rec1 = make_float4(Wh.x, Wh.y, Wh.z, __int_as_float(exactSp ? mi | RL_LAZY_REC_EXACT_SP : mi));
 						if (last) done = true;   // (L = 0: the record is folded like every other, from the registers)
 						else { o = s.p; d = outD; }
 					}
@@ -492,7 +493,7 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 							const float4* st = (const float4*)pathStack + ((size_t)k * P.stackStride + gtid) * 2u;
 							r0 = st[0]; r1 = st[1];
 						}
-						const Mat m = MatFrom<PLAIN>(sm + LdsAt<LDS>::MATS + __float_as_int(r1.w) * RL_LDS_MSTRIDE(PLAIN));
+						const Mat m = MatFrom<PLAIN>(sm + LdsAt<LDS>::MATS + RL_LAZY_REC_MAT(r1.w) * RL_LDS_MSTRIDE(PLAIN));
 						L = FoldLazyVertex(m, r0, r1, L);
 					}
 					samples[outIndex] = make_sample(L.x, L.y, L.z);

@@ -1,4 +1,4 @@
-// The leaf-list kernel's lazy-reflectance instance (k_trace_lazy), the kernel that finishes its lit paths (k_fold_lit) and the sweep of its guard, as a translation
+// The leaf-list kernel's lazy-reflectance instance (k_trace_lazy), the kernel that finishes its lit paths (k_fold_lit) and the sweeps of its guards, as a translation
 // unit of their own: instantiated beside the other k_trace instances, the lazy one changes how the compiler schedules two loops of the eager PLAIN instance, and
 // the eager kernels must stay what they are (tools/isa_equivalence.py) -- the reason the views twins have their unit.
 
@@ -34,10 +34,32 @@ k_fold_lit(const DSceneView S, const DLitList LL, SampleRGB* __restrict__ sample
 		#pragma nounroll
 		for (int k = nrec - 1; k >= 0; --k) {
 			const float4 r0 = e[2 + 2 * k], r1 = e[3 + 2 * k];
-			L = FoldLazyVertex(LoadMat(S, __float_as_int(r1.w)), r0, r1, L);
+			L = FoldLazyVertex(LoadMat(S, RL_LAZY_REC_MAT(r1.w)), r0, r1, L);
 		}
 		samples[__float_as_uint(h0.w)] = make_sample(L.x, L.y, L.z);
 	}
+}
+
+// The scattering events both sweeps below are made from: event i's generator, its outgoing direction, the sampler's two draws and the roughness.  Returns the
+// selector the edge choices cycle by.
+__device__ __forceinline__ uint32_t LazySweepEvent(unsigned long long seed, uint32_t i, Rng& g, V3& Wo, float& u0, float& u1, float& rough)
+{
+	g.s = raylib_rng_begin(seed, i, 0);
+	const uint32_t sel = i % 30030u;   // 2 * 3 * 5 * 7 * 11 * 13: the edge choices below cycle with coprime periods
+	// Wo: a unit vector with a chosen z
+	const uint32_t zk = sel % 11u;
+	float z = 2.0f * Next(g) - 1.0f;
+	if (zk < 8u) { const float e[8] = { 0.0f, 1.0f, -1.0f, 0x1p-1f, -0x1p-10f, 0x1p-24f, -0x1p-60f, 0x1p-126f }; z = e[zk]; }
+	const float phi = 2.0f * RL_PI * Next(g), rxy = rtm::sqrt_(fmaxf(0.0f, 1.0f - z * z));
+	float sphi, cphi; rtm::sincos_(phi, &sphi, &cphi);
+	Wo = v3(rxy * cphi, rxy * sphi, z);
+	const uint32_t uk = sel % 7u, vk = sel % 5u;
+	u0 = Next(g); u1 = Next(g);
+	if (uk < 3u) u0 = uk == 0u ? 0.0f : uk == 1u ? 1e-6f : 1.0f - 0x1p-24f;
+	if (vk < 3u) u1 = vk == 0u ? 0.0f : vk == 1u ? 1e-6f : 1.0f - 0x1p-24f;
+	const uint32_t rk = sel % 3u;
+	rough = rk == 0u ? RL_LAZY_ROUGHNESS_MIN : rk == 1u ? RL_LAZY_ROUGHNESS_MAX : rtm::exp_(Next(g) * -10.0f * 0.69314718f);
+	return sel;
 }
 
 // Test hook: LazyVertexSafe's claim, swept inside the product library.  Every thread builds scattering events from edge and random inputs -- Wo.z at 0, +-2^-k and
@@ -53,21 +75,8 @@ k_verify_lazy_refl(uint32_t n, unsigned long long seed, unsigned long long* __re
 	Counters c; c.rays = c.nodes = c.tris = c.shaded = c.texels = c.samples = c.trips = 0; RL_DIAG_BIND(c);
 	unsigned long long events = 0, bad = 0, failed = 0;
 	for (uint32_t i = i0; i < n; i += stride) {
-		Rng g; g.s = raylib_rng_begin(seed, i, 0);
-		const uint32_t sel = i % 30030u;   // 2 * 3 * 5 * 7 * 11 * 13: the edge choices below cycle with coprime periods
-		// Wo: a unit vector with a chosen z
-		const uint32_t zk = sel % 11u;
-		float z = 2.0f * Next(g) - 1.0f;
-		if (zk < 8u) { const float e[8] = { 0.0f, 1.0f, -1.0f, 0x1p-1f, -0x1p-10f, 0x1p-24f, -0x1p-60f, 0x1p-126f }; z = e[zk]; }
-		const float phi = 2.0f * RL_PI * Next(g), rxy = rtm::sqrt_(fmaxf(0.0f, 1.0f - z * z));
-		float sphi, cphi; rtm::sincos_(phi, &sphi, &cphi);
-		const V3 Wo = v3(rxy * cphi, rxy * sphi, z);
-		const uint32_t uk = sel % 7u, vk = sel % 5u;
-		float u0 = Next(g), u1 = Next(g);
-		if (uk < 3u) u0 = uk == 0u ? 0.0f : uk == 1u ? 1e-6f : 1.0f - 0x1p-24f;
-		if (vk < 3u) u1 = vk == 0u ? 0.0f : vk == 1u ? 1e-6f : 1.0f - 0x1p-24f;
-		const uint32_t rk = sel % 3u;
-		const float rough = rk == 0u ? RL_LAZY_ROUGHNESS_MIN : rk == 1u ? RL_LAZY_ROUGHNESS_MAX : rtm::exp_(Next(g) * -10.0f * 0.69314718f);
+		Rng g; V3 Wo; float u0, u1, rough;
+		const uint32_t sel = LazySweepEvent(seed, i, g, Wo, u0, u1, rough);
 		const uint32_t mk = sel % 2u;
 		// metallic 0, 1, the planner's ends +-RL_LAZY_COLOR_MAX and random in between; albedo likewise, of either sign
 		const float mr = Next(g);
@@ -95,6 +104,58 @@ k_verify_lazy_refl(uint32_t n, unsigned long long seed, unsigned long long* __re
 	}
 	for (int off = 32; off > 0; off >>= 1) { events += __shfl_down(events, off); bad += __shfl_down(bad, off); failed += __shfl_down(failed, off); }
 	if ((threadIdx.x & 63u) == 0u) { atomicAdd(&out[0], events); if (bad) atomicAdd(&out[1], bad); if (failed) atomicAdd(&out[2], failed); }
+}
+
+// Test hook: LazyPdfQuick's claim and the two record forms, swept over the events of k_verify_lazy_refl.  Every thread runs the sampler, evaluates sp and pdf
+// eagerly (Scatter's statements), takes what LazyScatterPdf leaves, makes the vertex record k_trace_lazy would store from it and recomputes sp and pdf from the
+// record as the fold does (LazyRecordPdf); then the same through the other record form (the exact sp, flagged), which every event may take.
+// out[0]: events; out[1]: events that are quick although pdf > 0 is false, sp, wh.x or wh.y is not finite, or whose record (of either form) gives back another
+// bit of sp or pdf than the eager evaluation; or that are not quick and whose flagged record does -- must be 0; out[2]: events that are not quick.
+__global__ void __launch_bounds__(RL_BLOCK)
+k_verify_lazy_pdf(uint32_t n, unsigned long long seed, unsigned long long* __restrict__ out)
+{
+	RL_MATH_PROLOGUE();
+	const uint32_t i0 = blockIdx.x * RL_BLOCK + threadIdx.x, stride = gridDim.x * RL_BLOCK;
+	Counters c; c.rays = c.nodes = c.tris = c.shaded = c.texels = c.samples = c.trips = 0; RL_DIAG_BIND(c);
+	unsigned long long events = 0, wrong = 0, refused = 0;
+	// (whole waves walk the loop together: LazyScatterPdf votes across the wave, and n is rounded up for the vote's sake alone)
+	for (uint32_t i = i0; i < ((n + 63u) & ~63u); i += stride) {
+		const bool live = i < n;
+		Rng g; V3 Wo; float u0, u1, rough;
+		LazySweepEvent(seed, live ? i : 0u, g, Wo, u0, u1, rough);
+		// the event, as ScatterLazy makes it (local frame = world frame)
+		const V3 N = v3(0.0f, 0.0f, 1.0f);
+		const bool bFlip = Wo.z < 0.0f;
+		V3 Wh = BeckmannSample(bFlip ? -Wo : Wo, rough, rough, u0, u1, c);
+		if (bFlip) Wh = -Wh;
+		const V3 Wi = reflect(-Wo, Wh);
+		V3 wh = normalize(Wo + Wi);
+		if (wh.z < 0.0f) wh.z = -wh.z;
+		// eager
+		const float spE = DistributionBeckmann(N, wh, rough) * absDot(wh, N);
+		const float pdfE = spE / (4.0f * dot(Wo, Wh));
+		// lazy: what the event leaves, the record made of it, and the fold's values from the record
+		float spSlot, pdfSeen;
+		const bool exactSp = LazyScatterPdf(N, Wo, Wh, wh, rough, spSlot, pdfSeen);
+		const int mi = (int)(i & 0xffffu);
+		const float4 r0 = make_float4(Wo.x, Wo.y, Wo.z, spSlot), r1 = make_float4(Wh.x, Wh.y, Wh.z, __int_as_float(exactSp ? mi | RL_LAZY_REC_EXACT_SP : mi));
+		float spR, pdfR;
+		LazyRecordPdf(r0, r1, rough, spR, pdfR);
+		bool bad = RL_LAZY_REC_MAT(r1.w) != mi || __float_as_uint(spR) != __float_as_uint(spE) || __float_as_uint(pdfR) != __float_as_uint(pdfE);
+		// the flagged form, whatever the event chose
+		const float4 f0 = make_float4(Wo.x, Wo.y, Wo.z, spE), f1 = make_float4(Wh.x, Wh.y, Wh.z, __int_as_float(mi | RL_LAZY_REC_EXACT_SP));
+		LazyRecordPdf(f0, f1, rough, spR, pdfR);
+		bad = bad || RL_LAZY_REC_MAT(f1.w) != mi || __float_as_uint(spR) != __float_as_uint(spE) || __float_as_uint(pdfR) != __float_as_uint(pdfE);
+		if (!exactSp) {
+			bad = bad || !(pdfE > 0.0f) || !(fabsf(spE) < INFINITY) || !(fabsf(wh.x) < INFINITY) || !(fabsf(wh.y) < INFINITY);
+			bad = bad || !(pdfSeen > 0.0f) || !(fabsf(spSlot) < INFINITY);   // what k_trace_lazy's two predicates read instead
+		} else {
+			bad = bad || (pdfSeen > 0.0f) != (pdfE > 0.0f) || __float_as_uint(spSlot) != __float_as_uint(spE);
+		}
+		if (live) { ++events; if (bad) ++wrong; if (exactSp) ++refused; }
+	}
+	for (int off = 32; off > 0; off >>= 1) { events += __shfl_down(events, off); wrong += __shfl_down(wrong, off); refused += __shfl_down(refused, off); }
+	if ((threadIdx.x & 63u) == 0u) { atomicAdd(&out[0], events); if (wrong) atomicAdd(&out[1], wrong); if (refused) atomicAdd(&out[2], refused); }
 }
 
 // ---- instances ----

@@ -77,7 +77,8 @@ bool DeviceVerifyExactMath(int which, uint64_t* outMismatches, uint64_t* outFirs
 	return ok;
 }
 
-bool DeviceVerifyLazyRefl(uint32_t n, uint64_t seed, uint64_t out[3])
+// the two sweeps of the lazy instance's guards: three counts each
+static bool VerifyLazySweep(void (*kernel)(uint32_t, unsigned long long, unsigned long long*), uint32_t n, uint64_t seed, uint64_t out[3])
 {
 	std::lock_guard<std::mutex> lk(Rt().lock);
 	if (!EnsureRuntime()) return false;
@@ -86,10 +87,12 @@ bool DeviceVerifyLazyRefl(uint32_t n, uint64_t seed, uint64_t out[3])
 	DevBuf<unsigned long long> d;
 	if (!d.Upload(h, 3)) return false;
 	const uint32_t blocks = std::max(1u, std::min(1024u, (n + RL_BLOCK - 1) / RL_BLOCK));
-	const bool ok = RunOnRank0(k_verify_lazy_refl, blocks, RL_BLOCK, n, (unsigned long long)seed, d.ptr) && Download(h, d.ptr, 3);
+	const bool ok = RunOnRank0(kernel, blocks, RL_BLOCK, n, (unsigned long long)seed, d.ptr) && Download(h, d.ptr, 3);
 	for (int k = 0; k < 3; ++k) out[k] = h[k];
 	return ok;
 }
+bool DeviceVerifyLazyRefl(uint32_t n, uint64_t seed, uint64_t out[3]) { return VerifyLazySweep(k_verify_lazy_refl, n, seed, out); }
+bool DeviceVerifyLazyPdf(uint32_t n, uint64_t seed, uint64_t out[3]) { return VerifyLazySweep(k_verify_lazy_pdf, n, seed, out); }
 
 // The lists of a progressive session after a pass, from arrays of the caller's.  The launch is EnqueueFrame's (one workgroup of RL_COMPACT_BLOCK threads on rank 0's
 // stream); the kernel writes live and trace in place, entries at indices <= their own, so numLive entries of each suffice.

@@ -23,6 +23,7 @@ bool DeviceDrain(RaylibAMDStats*) { return false; }
 int32_t DeviceLastTracePlain() { return 0; }
 int32_t DeviceLastTraceLazy() { return 0; }
 bool DeviceVerifyLazyRefl(uint32_t, uint64_t, uint64_t*) { return false; }
+bool DeviceVerifyLazyPdf(uint32_t, uint64_t, uint64_t*) { return false; }
 bool DeviceVerifyExactMath(int, uint64_t*, uint64_t*) { return false; }
 // rl_denoise.hip is a HIP unit too: the device filter fails, and its host restatement (RaylibAMD_DenoiseHost) is not part of this build
 bool DeviceDenoise(Image&, bool, Image*, Image*, Image&, const RaylibAMDDenoiseParams&) { return false; }
