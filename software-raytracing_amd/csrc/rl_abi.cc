@@ -1015,7 +1015,7 @@ int32_t RaylibAMD_SceneLeafListInfo(SceneHandle sh, uint32_t* maxPerLeaf)
 	Scene* s = (Scene*)sh;
 	if (!s || !s->finalized) return 0;
 	int32_t leaves = 0; uint32_t most = 0;
-	for (const DNode4& n : s->bvh.leafList) for (int k = 0; k < 4; ++k) if (n.child[k] != DNODE_EMPTY) { ++leaves; most = std::max(most, (((uint32_t)~n.child[k]) & 7u) + 1u); }
+	for (const DNode4& n : s->bvh.leafList) for (int k = 0; k < 4; ++k) if (n.child[k] != DNODE_EMPTY) { ++leaves; most = std::max(most, (((uint32_t)~n.child[k]) & LEAF_COUNT_MASK) + 1u); }
 	if (maxPerLeaf) *maxPerLeaf = most;
 	return leaves;
 }

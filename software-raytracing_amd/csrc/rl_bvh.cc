@@ -265,7 +265,7 @@ inline void storeBox(float* mn, float* mx, const Box& b) {
 	mn[0] = b.mn.x; mn[1] = b.mn.y; mn[2] = b.mn.z;
 	mx[0] = b.mx.x; mx[1] = b.mx.y; mx[2] = b.mx.z;
 }
-inline int32_t leafRef(uint32_t first, uint32_t kind, uint32_t count) { return ~(int32_t)((first << 6) | (kind << 4) | (count - 1)); }
+inline int32_t leafRef(uint32_t first, uint32_t kind, uint32_t count) { return ~(int32_t)((first << LEAF_FIRST_SHIFT) | (kind << LEAF_KIND_SHIFT) | (count - 1)); }
 
 // nodes4 -> nodes4q (DNode4Q, rl_device.h).  Every decision is made in double, where origin + q * step is exact, so "the grid
 // box contains the float box" holds exactly.
@@ -517,7 +517,7 @@ static void EmitWide8(const std::vector<TmpNode>& T, const Wide8& W, const std::
 			const int32_t k = w.kid[c];
 			if (k < 0) continue;
 			if (T[k].left >= 0) { imask |= 1u << c; continue; }
-			const uint32_t code = (uint32_t)~leafCode[k], first = code >> 6, count = (code & 7u) + 1;
+			const uint32_t code = (uint32_t)~leafCode[k], first = code >> LEAF_FIRST_SHIFT, count = (code & LEAF_COUNT_MASK) + 1;
 			leafMask |= ((1u << count) - 1u) << (4 * c);
 			if (!haveTri) { triBase = first; haveTri = true; }
 		}
@@ -729,7 +729,7 @@ void EmitLeafList(const std::vector<TmpNode>& T, int32_t root, const std::vector
 {
 	std::vector<uint32_t> triFirst(T.size(), 0), triCount(T.size(), 0);
 	for (size_t t = T.size(); t-- > 0;) {   // children follow their parent in T (pre-order): a reverse sweep sees them first
-		if (T[t].left < 0) { triFirst[t] = ((uint32_t)~leafCode[t]) >> 6; triCount[t] = T[t].count; }
+		if (T[t].left < 0) { triFirst[t] = ((uint32_t)~leafCode[t]) >> LEAF_FIRST_SHIFT; triCount[t] = T[t].count; }
 		else { triFirst[t] = triFirst[T[t].left]; triCount[t] = triCount[T[t].left] + triCount[T[t].right]; }
 	}
 	std::vector<int32_t> cut; cut.push_back(root);
@@ -812,11 +812,11 @@ void BuildBVH(const std::vector<PrimRef>& prims, BVH& out, const BVHBuildOptions
 namespace {
 
 inline bool inside(const f3& p, const f3& mn, const f3& mx) { return p.x >= mn.x && p.y >= mn.y && p.z >= mn.z && p.x <= mx.x && p.y <= mx.y && p.z <= mx.z; }
-inline uint32_t leafKind(int32_t ref) { return ((uint32_t)~ref >> 4) & 3u; }
+inline uint32_t leafKind(int32_t ref) { return ((uint32_t)~ref >> LEAF_KIND_SHIFT) & LEAF_KIND_MASK; }
 // the triangle leaf `ref`: every slot in range, every triangle met for the first time (seen), all three vertices inside the box [mn, mx]
 bool LeafTrianglesInside(const BVH& bvh, const std::vector<HostTriangle>& tris, int32_t ref, const f3& mn, const f3& mx, std::vector<uint8_t>& seen)
 {
-	const uint32_t code = (uint32_t)~ref, first = code >> 6, count = (code & 7u) + 1;
+	const uint32_t code = (uint32_t)~ref, first = code >> LEAF_FIRST_SHIFT, count = (code & LEAF_COUNT_MASK) + 1;
 	for (uint32_t k = 0; k < count; ++k) {
 		if (first + k >= bvh.triOrder.size()) return false;
 		const uint32_t ti = bvh.triOrder[first + k];
@@ -1216,7 +1216,7 @@ bool WalkStackHost(const BVH& bvh, const std::vector<HostTriangle>& tris, const 
 					}
 				}
 				if (cur == DONE) break;
-				const uint32_t code = (uint32_t)~cur, first = code >> 6, count = (code & 7u) + 1u, kind = (code >> 4) & 3u;
+				const uint32_t code = (uint32_t)~cur, first = code >> LEAF_FIRST_SHIFT, count = (code & LEAF_COUNT_MASK) + 1u, kind = (code >> LEAF_KIND_SHIFT) & LEAF_KIND_MASK;
 				if (kind == PRIM_TRIANGLE) {
 					for (uint32_t i = 0; i < count; ++i) if (!triangle(first + i)) return false;
 				} else if (kind == PRIM_SPHERE) {

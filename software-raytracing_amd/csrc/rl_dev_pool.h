@@ -162,9 +162,7 @@ __device__ __forceinline__ bool NodeStep4(const DSceneView& S, Trav& T, float tM
 	if (r1 == DNODE_EMPTY) t1 = INFINITY;
 	if (r2 == DNODE_EMPTY) t2 = INFINITY;
 	if (r3 == DNODE_EMPTY) t3 = INFINITY;
-	#define RL_CSWAP(ta, ra, tb, rb) { const bool sw = tb < ta; const float tt = sw ? tb : ta; tb = sw ? ta : tb; ta = tt; const int rr = sw ? rb : ra; rb = sw ? ra : rb; ra = rr; }
-	RL_CSWAP(t0, r0, t1, r1) RL_CSWAP(t2, r2, t3, r3) RL_CSWAP(t0, r0, t2, r2) RL_CSWAP(t1, r1, t3, r3) RL_CSWAP(t1, r1, t2, r2)
-	#undef RL_CSWAP
+	RL_SORT4(t0, r0, t1, r1, t2, r2, t3, r3)
 	T.leafI = 0;
 	if (!(t0 < INFINITY)) return PopOrFinish<LSTACK, STACK>(T, stk, ovf);
 	if (t3 < INFINITY) StackPush<LSTACK, STACK>(T, stk, ovf, r3);
@@ -178,40 +176,15 @@ template <int LSTACK, int STACK, bool PRIMS>
 __device__ __forceinline__ bool LeafStep(const DSceneView& S, Trav& T, float tMin, int* stk, int* ovf, Counters& c)
 {
 	RL_WSTEP(5);
-	const uint32_t code = (uint32_t)~T.cur;
-	const int first = (int)(code >> 6);
-	const int count = (int)(code & 7u) + 1;
-	const bool alpha = (code & 8u) != 0;
-	const uint32_t kind = (code >> 4) & 3u;
+	const LeafRef L = DecodeLeaf(T.cur);
 	const V3 o = T.o, d = T.d;
 	c.tris++;
-	if (!PRIMS || kind == 0u) {
-		const int i = first + T.leafI;
+	if (!PRIMS || L.kind == 0u) {
+		const int i = L.first + T.leafI;
 		const Tri TT = LoadTri(S, i);
-		// reference geom/triangle.cc:22-27
-		const float t = dot((TT.v0 - o), TT.n) / dot(d, TT.n);
-		if (t >= tMin && t <= FLT_MAX && (t < T.best.t || (t == T.best.t && i < T.best.tri))) {   // ties: the lower slot, as in Traverse()
-			const V3 pp = o + t * d;
-			const V3 w = pp - TT.v0;
-			const float wv = dot(w, TT.v), wu = dot(w, TT.u);
-			float pa, pb;
-			if (Barycentric(S.fastBary != 0, TT.uv * wv - TT.vv * wu, TT.uv * wu - TT.uu * wv, TT.denom, TT.rden, pa, pb) && OwnBoxPass(TT.v0, TT.v1, TT.v2, o, v3(rtm::rcp1_(d.x), rtm::rcp1_(d.y), rtm::rcp1_(d.z)), tMin, t)) {
-				if (!alpha || AlphaTestCandidate(S, i, pa, pb, c)) {
-					T.best.t = t; T.best.a = pa; T.best.b = pb; T.best.tri = i;
-					if (T.anyhit) return true;
-				}
-			}
-		}
-	} else {
-		float2 r;
-		if (kind == 1u) r = make_float2(SphereHit(S.spheres, first, o, d, tMin, T.best.t), 0.0f);
-		else r = CubeHit(S.cubes, first, o, d, T.rayTime, tMin, T.best.t);
-		if (r.x == r.x) {   // not NaN: a hit
-			T.best.t = r.x; T.best.a = r.y; T.best.b = 0.0f; T.best.tri = (int)((kind << 28) | (uint32_t)first);
-			if (T.anyhit) return true;
-		}
-	}
-	if (++T.leafI < count) return false;
+		RL_TRIANGLE_TEST(S, TT, i, o, d, tMin, T.best, L.alpha, OwnBoxPass(TT.v0, TT.v1, TT.v2, o, ExactInv(d), tMin, t), T.anyhit, c, RL_NESTED)
+	} else RL_PRIMITIVE_LEAF(S, L.kind, L.first, o, d, T.rayTime, tMin, T.best, T.anyhit)
+	if (++T.leafI < L.count) return false;
 	return PopOrFinish<LSTACK, STACK>(T, stk, ovf);
 }
 
@@ -295,8 +268,7 @@ __device__ __forceinline__ bool NodeStep8(const DSceneView& S, Trav& T, float tM
 	}
 	const float Ax_ = __uint_as_float((h_.w & 0xffu) << 23) * T.inv.x, Ay_ = __uint_as_float(((h_.w >> 8) & 0xffu) << 23) * T.inv.y, Az_ = __uint_as_float(((h_.w >> 16) & 0xffu) << 23) * T.inv.z;
 	const float Bx_ = (__uint_as_float(h_.x) - T.o.x) * T.inv.x, By_ = (__uint_as_float(h_.y) - T.o.y) * T.inv.y, Bz_ = (__uint_as_float(h_.z) - T.o.z) * T.inv.z;
-	// (|B| + 255 |A|) * 2^-21, as in RL_WIDE_STEP_Q: four times the rounding of q * A + B against the reference's (bound - o) * inv; -(B - E) and B + E
-	const float Ex_ = fabsf(Ax_ * 1.21593475e-4f) + fabsf(Bx_ * 4.76837158e-7f), Ey_ = fabsf(Ay_ * 1.21593475e-4f) + fabsf(By_ * 4.76837158e-7f), Ez_ = fabsf(Az_ * 1.21593475e-4f) + fabsf(Bz_ * 4.76837158e-7f);
+	const float Ex_ = RL_GRID_ERR(Ax_, Bx_), Ey_ = RL_GRID_ERR(Ay_, By_), Ez_ = RL_GRID_ERR(Az_, Bz_);   // -(B - E) and B + E below
 	const float nBx_ = Ex_ - Bx_, Bfx_ = Bx_ + Ex_, nBy_ = Ey_ - By_, Bfy_ = By_ + Ey_, nBz_ = Ez_ - Bz_, Bfz_ = Bz_ + Ez_;
 	// planes: p0 = qlo x (children 0-3, 4-7), qlo y (0-3, 4-7); p1 = qlo z (0-3, 4-7), qhi x (0-3, 4-7); p2 = qhi y (0-3, 4-7), qhi z (0-3, 4-7)
 	const uint32_t nX0 = RL_SEL8(p1_.z, p0_.x, T.m8x), fX0 = RL_SEL8(p0_.x, p1_.z, T.m8x), nX1 = RL_SEL8(p1_.w, p0_.y, T.m8x), fX1 = RL_SEL8(p0_.y, p1_.w, T.m8x);
@@ -330,20 +302,7 @@ __device__ __forceinline__ bool LeafStep8(const DSceneView& S, Trav& T, float tM
 	const V3 o = T.o, d = T.d;
 	c.tris++;
 	const Tri TT = LoadTri(S, i);
-	// reference geom/triangle.cc:22-27
-	const float t = dot((TT.v0 - o), TT.n) / dot(d, TT.n);
-	if (t >= tMin && t <= FLT_MAX && (t < T.best.t || (t == T.best.t && i < T.best.tri))) {   // ties: the lower slot, as in Traverse()
-		const V3 pp = o + t * d;
-		const V3 w = pp - TT.v0;
-		const float wv = dot(w, TT.v), wu = dot(w, TT.u);
-		float pa, pb;
-		if (Barycentric(S.fastBary != 0, TT.uv * wv - TT.vv * wu, TT.uv * wu - TT.uu * wv, TT.denom, TT.rden, pa, pb) && OwnBoxPass(TT.v0, TT.v1, TT.v2, o, v3(rtm::rcp1_(d.x), rtm::rcp1_(d.y), rtm::rcp1_(d.z)), tMin, t)) {
-			if (!alpha || AlphaTestCandidate(S, i, pa, pb, c)) {
-				T.best.t = t; T.best.a = pa; T.best.b = pb; T.best.tri = i;
-				if (T.anyhit) return true;
-			}
-		}
-	}
+	RL_TRIANGLE_TEST(S, TT, i, o, d, tMin, T.best, alpha, OwnBoxPass(TT.v0, TT.v1, TT.v2, o, ExactInv(d), tMin, t), T.anyhit, c, RL_NESTED)
 	return Next8(T, stk, ovf, G);
 }
 

@@ -1,4 +1,4 @@
-// Device library, part 3 of 6: the closest-hit walks -- the box rules, the slab test, the analytic primitives, the barycentric test, and the three
+// Device library, part 3 of 6: the closest-hit walks -- the box rules, the slab test, the analytic primitives, the one triangle test, and the three
 // whole walks: Traverse (binary tree), TraverseLeafList (the leaf list in LDS) and Traverse4 (the 4-wide trees).
 #pragma once
 
@@ -85,6 +85,8 @@ __device__ __forceinline__ bool Slab(float mnx, float mny, float mnz, float mxx,
 // v_rcp_f32 (1 ulp) is enough for the slab test's 1/d when the test is widened to 6 ulp (RL_POOL_WIDEN) instead of 3:
 // Slab() is only asked to be conservative.  0 -> inf and the sign of a zero survive, as with the division.
 __device__ __forceinline__ float FastRcp(float x) { return __builtin_amdgcn_rcpf(x); }
+// ... and the exact one, RN(1 / d) per axis: what the candidate rule and the reference's own box test divide by
+__device__ __forceinline__ V3 ExactInv(V3 d) { return v3(rtm::rcp1_(d.x), rtm::rcp1_(d.y), rtm::rcp1_(d.z)); }
 
 // First traversal step only: true when the ray misses both child boxes of the root node.
 template <int LDS = 0>
@@ -95,7 +97,7 @@ __device__ __forceinline__ bool RootMiss(const DSceneView& S, V3 o, V3 d, float 
 #if RL_ROOTMISS_RCP
 	const V3 inv = v3(FastRcp(d.x), FastRcp(d.y), FastRcp(d.z));
 #else
-	const V3 inv = v3(rtm::rcp1_(d.x), rtm::rcp1_(d.y), rtm::rcp1_(d.z));
+	const V3 inv = ExactInv(d);
 #endif
 	const bool nx = inv.x < 0.0f, ny = inv.y < 0.0f, nz = inv.z < 0.0f;
 	const float4* np = LDS ? sm + RL_LDS_ROOT : (const float4*)(S.nodes);
@@ -195,6 +197,54 @@ __device__ __forceinline__ bool Barycentric(bool fast, float X, float Y, float d
 #define RL_WSTEP(k)
 #endif
 
+// A leaf reference (rl_device.h, DNode): ~ref = (first << 6) | (kind << 4) | (alphaTested << 3) | (count - 1).
+struct LeafRef { int first, count; uint32_t kind; bool alpha; };
+__device__ __forceinline__ LeafRef DecodeLeaf(int ref)
+{
+	const uint32_t code = (uint32_t)~ref;
+	return { (int)(code >> LEAF_FIRST_SHIFT), (int)(code & LEAF_COUNT_MASK) + 1, (code >> LEAF_KIND_SHIFT) & LEAF_KIND_MASK, (code & LEAF_ALPHA_BIT) != 0u };
+}
+
+// The triangle test of every closest-hit search here, written once: Traverse, TraverseLeafList and Traverse4 below, LeafStep and LeafStep8 of the pool
+// schedule (rl_dev_pool.h).  Which hit a ray gets is a property of the ray and the triangle alone, never of the tree, its width or the schedule -- and that
+// holds only while all five apply the same rules: the tie rule, the barycentric test, the candidate rule, then the cut-out test.
+//   T_       the triangle: a Tri, or anything with its v0, n, u, v, uv, uu, vv, denom, rden (the leaf list's LDS record)
+//   slot_    its slot; best_ the search's HitRec; alpha_ whether its leaf runs the cut-out test (a compile-time false stays one); c_ the Counters
+//   ownbox_  the candidate rule, OwnBoxPass / OwnBoxPassMnMx above, on the triangle's own box (the plane hit is `t` in it); anyhit_ leave the function with
+//            `true` at the first accepted hit: a template argument in the walks, Trav's flag in the pool steps
+//   ONLY_IF_ how a failed condition ends the test.  RL_ELSE_CONTINUE: the test is the body of a walk's loop over a leaf's triangles; RL_NESTED: one triangle per
+//            call, the step's tail follows.  The same thing twice, but not to the compiler: with each kind of site in the form it was written in, every kernel is,
+//            instruction for instruction, the one it was as five copies; one form for all, or a function, is not (profiles/r18_walk_dedup_isa_equivalence.log).
+#define RL_ELSE_CONTINUE(ok_) if (!(ok_)) continue;
+#define RL_NESTED(ok_) if (ok_)
+#define RL_TRIANGLE_TEST(S_, T_, slot_, o_, d_, tMin_, best_, alpha_, ownbox_, anyhit_, c_, ONLY_IF_) { \
+	/* the plane hit, reference geom/triangle.cc:22-27 */ \
+	const float t = dot(((T_).v0 - (o_)), (T_).n) / dot((d_), (T_).n); \
+	/* closer, or exactly as far with a lower slot: which of two surfaces at the same t wins must not depend on the order a traversal tests them in (the reference's answer depends on its random tree, SURVEY A) */ \
+	ONLY_IF_(t >= (tMin_) && t <= FLT_MAX && (t < (best_).t || (t == (best_).t && (slot_) < (best_).tri))) { \
+		const V3 p_ = (o_) + t * (d_); \
+		const V3 w_ = p_ - (T_).v0; \
+		const float wv_ = dot(w_, (T_).v), wu_ = dot(w_, (T_).u); \
+		float pa_, pb_; \
+		if (Barycentric((S_).fastBary != 0, (T_).uv * wv_ - (T_).vv * wu_, (T_).uv * wu_ - (T_).uu * wv_, (T_).denom, (T_).rden, pa_, pb_) && (ownbox_)) { \
+			ONLY_IF_(!(alpha_) || AlphaTestCandidate(S_, slot_, pa_, pb_, c_)) { \
+				(best_).t = t; (best_).a = pa_; (best_).b = pb_; (best_).tri = (slot_); \
+				if (anyhit_) return true; \
+			} \
+		} \
+	} \
+}
+// The leaf of one analytic primitive (kind 1: sphere, 2: cube: `first_` is its number), for Traverse and LeafStep; a macro for the same reason.
+#define RL_PRIMITIVE_LEAF(S_, kind_, first_, o_, d_, rayTime_, tMin_, best_, anyhit_) { \
+	float2 r_; \
+	if ((kind_) == 1u) r_ = make_float2(SphereHit((S_).spheres, first_, o_, d_, tMin_, (best_).t), 0.0f); \
+	else r_ = CubeHit((S_).cubes, first_, o_, d_, rayTime_, tMin_, (best_).t); \
+	if (r_.x == r_.x) {   /* not NaN: a hit */ \
+		(best_).t = r_.x; (best_).a = r_.y; (best_).b = 0.0f; (best_).tri = (int)(((kind_) << 28) | (uint32_t)(first_)); \
+		if (anyhit_) return true; \
+	} \
+}
+
 // "while-while" traversal: every lane first descends through inner nodes until it holds a leaf (cheap steps:
 // one 64-byte record, two slab tests), THEN the wave intersects leaves together.  With a single
 // "if inner else leaf" loop a wave pays node + leaf cost on every trip as soon as one lane is at a leaf, and
@@ -205,7 +255,7 @@ template <int STACK, bool ANYHIT, bool PRIMS>
 __device__ __forceinline__ bool Traverse(const DSceneView& S, V3 o, V3 d, float rayTime, float tMin, HitRec& best, int* stk, Counters& c, const float tBound = INFINITY)
 {
 	c.rays++;
-	const V3 inv = v3(rtm::rcp1_(d.x), rtm::rcp1_(d.y), rtm::rcp1_(d.z));
+	const V3 inv = ExactInv(d);
 	const bool nx = inv.x < 0.0f, ny = inv.y < 0.0f, nz = inv.z < 0.0f;
 	best.t = tBound; best.tri = -1; best.a = 0.0f; best.b = 0.0f;
 	int sp = 0;
@@ -239,41 +289,15 @@ __device__ __forceinline__ bool Traverse(const DSceneView& S, V3 o, V3 d, float 
 		// ---- leaf: <= 4 triangles stored back to back, or one analytic primitive ----
 		{
 			RL_WSTEP(6);
-			const uint32_t code = (uint32_t)~cur;
-			const int first = (int)(code >> 6);
-			const int count = (int)(code & 7u) + 1;
-			const bool alpha = (code & 8u) != 0;
-			const uint32_t kind = (code >> 4) & 3u;
-			if (!PRIMS || kind == 0u) {
-				for (int i = 0; i < count; ++i) {
+			const LeafRef L = DecodeLeaf(cur);
+			if (!PRIMS || L.kind == 0u) {
+				for (int i = 0; i < L.count; ++i) {
 					RL_WSTEP(5);
-					const Tri T = LoadTri(S, first + i);
+					const Tri T = LoadTri(S, L.first + i);
 					c.tris++;
-					// reference geom/triangle.cc:22-27
-					const float t = dot((T.v0 - o), T.n) / dot(d, T.n);
-					// closer, or exactly as far with a lower slot: which of two surfaces at the same t wins must not depend on the
-					// order a traversal happens to test them in (the reference's answer there depends on its random tree, SURVEY A)
-					if (!(t >= tMin && t <= FLT_MAX && (t < best.t || (t == best.t && first + i < best.tri)))) continue;
-					const V3 p = o + t * d;
-					const V3 w = p - T.v0;
-					const float wv = dot(w, T.v), wu = dot(w, T.u);
-					float pa, pb;
-					if (Barycentric(S.fastBary != 0, T.uv * wv - T.vv * wu, T.uv * wu - T.uu * wv, T.denom, T.rden, pa, pb) && OwnBoxPass(T.v0, T.v1, T.v2, o, inv, tMin, t)) {
-						if (alpha && !AlphaTestCandidate(S, first + i, pa, pb, c)) continue;
-						best.t = t; best.a = pa; best.b = pb; best.tri = first + i;
-						if (ANYHIT) return true;
-					}
+					RL_TRIANGLE_TEST(S, T, L.first + i, o, d, tMin, best, L.alpha, OwnBoxPass(T.v0, T.v1, T.v2, o, inv, tMin, t), ANYHIT, c, RL_ELSE_CONTINUE)
 				}
-			} else {
-				c.tris++;
-				float2 r;
-				if (kind == 1u) r = make_float2(SphereHit(S.spheres, first, o, d, tMin, best.t), 0.0f);
-				else r = CubeHit(S.cubes, first, o, d, rayTime, tMin, best.t);
-				if (r.x == r.x) {   // not NaN: a hit
-					best.t = r.x; best.a = r.y; best.b = 0.0f; best.tri = (int)((kind << 28) | (uint32_t)first);
-					if (ANYHIT) return true;
-				}
-			}
+			} else { c.tris++; RL_PRIMITIVE_LEAF(S, L.kind, L.first, o, d, rayTime, tMin, best, ANYHIT) }
 		}
 		if (sp == 0) break;
 		--sp;
@@ -299,6 +323,12 @@ typedef float rl_v4f __attribute__((ext_vector_type(4)));
 typedef uint32_t rl_v4u __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 GLoadF4(const void* p, int i) { const rl_v4f v = ((const __attribute__((address_space(1))) rl_v4f*)p)[i]; return make_float4(v.x, v.y, v.z, v.w); }
 __device__ __forceinline__ uint4 GLoadU4(const void* p, int i) { const rl_v4u v = ((const __attribute__((address_space(1))) rl_v4u*)p)[i]; return make_uint4(v.x, v.y, v.z, v.w); }
+// the rounding of a grid node's fused plane parameters, four times over (above): (|B| + 255 |A|) * 2^-21 as |A * c1| + |B * c2| -- two multiplies by literals and an add with |.|
+// modifiers, 2 issue cycles each; as an fma with 255 the constant sat in an SGPR (the three-operand encoding takes no literal) next to the |.| modifiers, and an SGPR operand makes it 4
+#define RL_GRID_ERR(A_, B_) (fabsf((A_) * 1.21593475e-4f) + fabsf((B_) * 4.76837158e-7f))
+// four children (entry distance, reference) in ascending order of entry distance: the five-comparator network
+#define RL_SORT4_STEP(ta, ra, tb, rb) { const bool sw = tb < ta; const float tt = sw ? tb : ta; tb = sw ? ta : tb; ta = tt; const int rr = sw ? rb : ra; rb = sw ? ra : rb; ra = rr; }
+#define RL_SORT4(t0, r0, t1, r1, t2, r2, t3, r3) RL_SORT4_STEP(t0, r0, t1, r1) RL_SORT4_STEP(t2, r2, t3, r3) RL_SORT4_STEP(t0, r0, t2, r2) RL_SORT4_STEP(t1, r1, t3, r3) RL_SORT4_STEP(t1, r1, t2, r2)
 #define RL_WIDE_STEP_Q(S_, cur_, o_, inv_, nx_, ny_, nz_, tMin_, tmx_, widen_, t0, t1, t2, t3, ch) \
 	/* (the loads spell the global address space out: the pool kernel keeps the base in a VGPR pair behind an empty asm statement, which hides where it */ \
 	/*  points -- and a flat_load counts against the LDS counter as well and waits for both) */ \
@@ -307,9 +337,7 @@ __device__ __forceinline__ uint4 GLoadU4(const void* p, int i) { const rl_v4u v 
 	const uint4 chu_ = GLoadU4(np_, 3); const int4 ch = make_int4((int)chu_.x, (int)chu_.y, (int)chu_.z, (int)chu_.w); \
 	const float Ax_ = h0_.w * (inv_).x, Ay_ = __uint_as_float(l_.w) * (inv_).y, Az_ = __uint_as_float(u_.w) * (inv_).z; \
 	const float Bx_ = (h0_.x - (o_).x) * (inv_).x, By_ = (h0_.y - (o_).y) * (inv_).y, Bz_ = (h0_.z - (o_).z) * (inv_).z; \
-	/* (|B| + 255 |A|) * 2^-21 as |A * c1| + |B * c2|: two multiplies by literals and an add with |.| modifiers, 2 issue cycles each -- as an fma with 255 the */ \
-	/* constant sat in an SGPR (the three-operand encoding takes no literal) next to the |.| modifiers, and an SGPR operand makes it 4 */ \
-	const float Ex_ = fabsf(Ax_ * 1.21593475e-4f) + fabsf(Bx_ * 4.76837158e-7f), Ey_ = fabsf(Ay_ * 1.21593475e-4f) + fabsf(By_ * 4.76837158e-7f), Ez_ = fabsf(Az_ * 1.21593475e-4f) + fabsf(Bz_ * 4.76837158e-7f); \
+	const float Ex_ = RL_GRID_ERR(Ax_, Bx_), Ey_ = RL_GRID_ERR(Ay_, By_), Ez_ = RL_GRID_ERR(Az_, Bz_); \
 	const float Bnx_ = Bx_ - Ex_, Bfx_ = Bx_ + Ex_, Bny_ = By_ - Ey_, Bfy_ = By_ + Ey_, Bnz_ = Bz_ - Ez_, Bfz_ = Bz_ + Ez_; \
 	const uint32_t nX_ = (nx_) ? u_.x : l_.x, fX_ = (nx_) ? l_.x : u_.x, nY_ = (ny_) ? u_.y : l_.y, fY_ = (ny_) ? l_.y : u_.y, nZ_ = (nz_) ? u_.z : l_.z, fZ_ = (nz_) ? l_.z : u_.z; \
 	const float tMinL_ = (tMin_), tmxL_ = (tmx_), widenL_ = (widen_); \
@@ -357,7 +385,7 @@ template <bool ANYHIT, bool PLAIN = false>
 __device__ __forceinline__ bool TraverseLeafList(const DSceneView& S, V3 o, V3 d, float tMin, HitRec& best, Counters& c, const float4* sm)
 {
 	c.rays++;
-	const V3 invb = v3(rtm::rcp1_(d.x), rtm::rcp1_(d.y), rtm::rcp1_(d.z));
+	const V3 invb = ExactInv(d);
 	const bool nx = invb.x < 0.0f, ny = invb.y < 0.0f, nz = invb.z < 0.0f;
 	best.t = INFINITY; best.tri = -1; best.a = 0.0f; best.b = 0.0f;
 	uint32_t key[4 * RL_LEAFLIST_RECORDS];
@@ -437,41 +465,27 @@ __device__ __forceinline__ bool TraverseLeafList(const DSceneView& S, V3 o, V3 d
 		from = m + 1u;
 		RL_WSTEP(6);
 		const uint32_t j = m & 31u;
-		const int ref = ((const int*)(sm + LdsAt<2>::NODES + (j >> 2) * RL_LDS_NSTRIDE + 6))[j & 3u];
-		const uint32_t code = (uint32_t)~ref;
-		const int first = (int)(code >> 6);
-		const int count = (int)(code & 7u) + 1;
-		const bool alpha = !PLAIN && (code & 8u) != 0;
+		const LeafRef L = DecodeLeaf(((const int*)(sm + LdsAt<2>::NODES + (j >> 2) * RL_LDS_NSTRIDE + 6))[j & 3u]);
 #if defined(RL_DIAG_STAMPS) && RL_DIAG_STAMPS >= 2
 		// diagnostic build: what regrouping the (ray, triangle) pairs of this round across the wave could save at best.  The lanes that visit a leaf in this
 		// round test `count` triangles each; dealt evenly to 64 lanes the round's pairs would take ceil(pairs / 64) wave steps instead of max(count) -- and no
 		// fewer than one, because a ray's next leaf depends on what this one yields (the nearest-first cut).  Summed in slot 7 next to the steps taken (slot 5).
 		{
 			uint32_t pairs = 0;
-			for (int cc = 1; cc <= 8; ++cc) pairs += (uint32_t)cc * (uint32_t)__popcll(Ballot(count == cc));
+			for (int cc = 1; cc <= 8; ++cc) pairs += (uint32_t)cc * (uint32_t)__popcll(Ballot(L.count == cc));
 			const unsigned long long em_ = Ballot(true);
 			if (c.diag && (threadIdx.x & 63u) == (uint32_t)__ffsll((long long)em_) - 1u) atomicAdd(&c.diag[CNT_COUNT + 7], (unsigned long long)((pairs + 63u) / 64u));
 		}
 #endif
-		for (int i = 0; i < count; ++i) {
-			const float4* tr = sm + LdsAt<2>::ISECT + (first + i) * 6;
+		for (int i = 0; i < L.count; ++i) {
+			const float4* tr = sm + LdsAt<2>::ISECT + (L.first + i) * 6;
 			const float4 q0 = tr[0], q1 = tr[1], q2 = tr[2], q3 = tr[3];
 			struct { V3 v0, n, u, v; float uv, uu, vv, denom, rden; } T;
 			T.v0 = v3(q0.x, q0.y, q0.z); T.n = v3(q0.w, q1.x, q1.y); T.u = v3(q1.z, q1.w, q2.x); T.v = v3(q2.y, q2.z, q2.w);
 			T.uv = q3.x; T.uu = q3.y; T.vv = q3.z; T.denom = q3.w; T.rden = tr[5].z;
 			c.tris++;
 			RL_WSTEP(5);
-			const float t = dot((T.v0 - o), T.n) / dot(d, T.n);
-			if (!(t >= tMin && t <= FLT_MAX && (t < best.t || (t == best.t && first + i < best.tri)))) continue;
-			const V3 p = o + t * d;
-			const V3 w = p - T.v0;
-			const float wv = dot(w, T.v), wu = dot(w, T.u);
-			float pa, pb;
-			if (Barycentric(S.fastBary != 0, T.uv * wv - T.vv * wu, T.uv * wu - T.uu * wv, T.denom, T.rden, pa, pb) && OwnBoxPassMnMx(tr, o, v3(rtm::rcp1_(d.x), rtm::rcp1_(d.y), rtm::rcp1_(d.z)), tMin, t)) {
-				if (alpha && !AlphaTestCandidate(S, first + i, pa, pb, c)) continue;
-				best.t = t; best.a = pa; best.b = pb; best.tri = first + i;
-				if (ANYHIT) return true;
-			}
+			RL_TRIANGLE_TEST(S, T, L.first + i, o, d, tMin, best, !PLAIN && L.alpha, OwnBoxPassMnMx(tr, o, ExactInv(d), tMin, t), ANYHIT, c, RL_ELSE_CONTINUE)
 		}
 		m = 0xffffffffu;
 		#pragma unroll
@@ -484,11 +498,11 @@ __device__ __forceinline__ bool TraverseLeafList(const DSceneView& S, V3 o, V3 d
 // FULL: float boxes (S.nodes4f), else the grid nodes (S.nodes4)
 template <int STACK, bool ANYHIT, bool PRIMS, bool FULL, int LDS = 0, bool PLAIN = false>
 __device__ __forceinline__ bool Traverse4(const DSceneView& S, V3 o, V3 d, float rayTime, float tMin, HitRec& best, int* stk, Counters& c, const float4* sm = nullptr,
-                                          const float tBound = INFINITY /* as in Traverse */)
+                                          const float tBound = INFINITY)
 {
 	if constexpr (LDS == 2) return TraverseLeafList<ANYHIT, PLAIN>(S, o, d, tMin, best, c, sm);
 	c.rays++;
-	V3 invb = v3(rtm::rcp1_(d.x), rtm::rcp1_(d.y), rtm::rcp1_(d.z));   // for the box tests (the candidate rule divides again: exact, and rare)
+	V3 invb = ExactInv(d);   // for the box tests (the candidate rule divides again: exact, and rare)
 	if (!FULL) invb = ClampInv(invb);
 	const bool nx = invb.x < 0.0f, ny = invb.y < 0.0f, nz = invb.z < 0.0f;
 	best.t = tBound; best.tri = -1; best.a = 0.0f; best.b = 0.0f;
@@ -506,9 +520,7 @@ __device__ __forceinline__ bool Traverse4(const DSceneView& S, V3 o, V3 d, float
 			if (r1 == DNODE_EMPTY) t1 = INFINITY;
 			if (r2 == DNODE_EMPTY) t2 = INFINITY;
 			if (r3 == DNODE_EMPTY) t3 = INFINITY;
-			#define RL_CSWAPB(ta, ra, tb, rb) { const bool sw = tb < ta; const float tt = sw ? tb : ta; tb = sw ? ta : tb; ta = tt; const int rr = sw ? rb : ra; rb = sw ? ra : rb; ra = rr; }
-			RL_CSWAPB(t0, r0, t1, r1) RL_CSWAPB(t2, r2, t3, r3) RL_CSWAPB(t0, r0, t2, r2) RL_CSWAPB(t1, r1, t3, r3) RL_CSWAPB(t1, r1, t2, r2)
-			#undef RL_CSWAPB
+			RL_SORT4(t0, r0, t1, r1, t2, r2, t3, r3)
 			if (!(t0 < INFINITY)) { if (sp == 0) cur = DONE; else { --sp; cur = stk[sp * RL_BLOCK]; } continue; }
 			if (t3 < INFINITY && sp < STACK) { stk[sp * RL_BLOCK] = r3; ++sp; }
 			if (t2 < INFINITY && sp < STACK) { stk[sp * RL_BLOCK] = r2; ++sp; }
@@ -517,26 +529,13 @@ __device__ __forceinline__ bool Traverse4(const DSceneView& S, V3 o, V3 d, float
 		}
 		if (cur == DONE) break;
 		{
-			const uint32_t code = (uint32_t)~cur;
-			const int first = (int)(code >> 6);
-			const int count = (int)(code & 7u) + 1;
-			const bool alpha = (code & 8u) != 0;
+			const LeafRef L = DecodeLeaf(cur);
 			RL_WSTEP(6);
-			for (int i = 0; i < count; ++i) {
-				const Tri T = LDS ? TriFrom(sm + RL_LDS_ISECT + (first + i) * RL_LDS_TSTRIDE) : LoadTri(S, first + i);
+			for (int i = 0; i < L.count; ++i) {
+				const Tri T = LDS ? TriFrom(sm + RL_LDS_ISECT + (L.first + i) * RL_LDS_TSTRIDE) : LoadTri(S, L.first + i);
 				c.tris++;
 				RL_WSTEP(5);
-				const float t = dot((T.v0 - o), T.n) / dot(d, T.n);
-				if (!(t >= tMin && t <= FLT_MAX && (t < best.t || (t == best.t && first + i < best.tri)))) continue;
-				const V3 p = o + t * d;
-				const V3 w = p - T.v0;
-				const float wv = dot(w, T.v), wu = dot(w, T.u);
-				float pa, pb;
-				if (Barycentric(S.fastBary != 0, T.uv * wv - T.vv * wu, T.uv * wu - T.uu * wv, T.denom, T.rden, pa, pb) && OwnBoxPass(T.v0, T.v1, T.v2, o, v3(rtm::rcp1_(d.x), rtm::rcp1_(d.y), rtm::rcp1_(d.z)), tMin, t)) {
-					if (alpha && !AlphaTestCandidate(S, first + i, pa, pb, c)) continue;
-					best.t = t; best.a = pa; best.b = pb; best.tri = first + i;
-					if (ANYHIT) return true;
-				}
+				RL_TRIANGLE_TEST(S, T, L.first + i, o, d, tMin, best, L.alpha, OwnBoxPass(T.v0, T.v1, T.v2, o, ExactInv(d), tMin, t), ANYHIT, c, RL_ELSE_CONTINUE)
 			}
 		}
 		if (sp == 0) break;

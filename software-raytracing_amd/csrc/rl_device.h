@@ -16,6 +16,8 @@ namespace rl {
 //                           kind 0: `count` (<= 4) triangles from `first`; kind 1 / 2: sphere / cube number `first`
 //   child == DNODE_EMPTY  : nothing (box is inverted, never hit)
 #define DNODE_EMPTY ((int32_t)0x80000000)
+// the leaf reference's fields: the host's leafRef / leafKind (rl_bvh.cc) and the walks' DecodeLeaf (rl_dev_walk.h) are written with these
+enum : uint32_t { LEAF_FIRST_SHIFT = 6, LEAF_KIND_SHIFT = 4, LEAF_KIND_MASK = 3u, LEAF_ALPHA_BIT = 8u, LEAF_COUNT_MASK = 7u };
 struct alignas(64) DNode {
 	float lmin[3], lmax[3];
 	float rmin[3], rmax[3];

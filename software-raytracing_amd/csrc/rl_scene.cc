@@ -154,9 +154,9 @@ bool Scene::BuildAccel(float t0, float t1)
 	if (any) {
 		auto patch = [&](int32_t& ref) {
 			if (ref >= 0 || ref == DNODE_EMPTY) return;
-			uint32_t code = (uint32_t)~ref, first = code >> 6, count = (code & 7u) + 1;
-			if (((code >> 4) & 3u) != PRIM_TRIANGLE) return;
-			for (uint32_t k = 0; k < count; ++k) if (alpha[bvh.triOrder[first + k]]) { code |= 8u; break; }
+			uint32_t code = (uint32_t)~ref, first = code >> LEAF_FIRST_SHIFT, count = (code & LEAF_COUNT_MASK) + 1;
+			if (((code >> LEAF_KIND_SHIFT) & LEAF_KIND_MASK) != PRIM_TRIANGLE) return;
+			for (uint32_t k = 0; k < count; ++k) if (alpha[bvh.triOrder[first + k]]) { code |= LEAF_ALPHA_BIT; break; }
 			ref = ~(int32_t)code;
 		};
 		for (DNode& n : bvh.nodes) { patch(n.left); patch(n.right); }
