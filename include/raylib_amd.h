@@ -273,6 +273,60 @@ typedef struct RaylibAMDGatherCut {
 } RaylibAMDGatherCut;
 RAYLIB_API int32_t RaylibAMD_PlanGatherCut(const RaylibAMDGatherParams* params, int32_t n, uint64_t launchIndex, RaylibAMDGatherCut* out);
 
+/* ---- lightmaps baked on the device: UV-space texels into RaylibAMD_Gather ------------------------------
+ * The step in front of RaylibAMD_Gather and the two behind it: the triangles of a range are rasterised in lightmap-UV space into one gather point per covered
+ * texel of a width x height atlas, the points are gathered, and the values go back into the atlas, whose gutters are filled by dilation.
+ * uv: six floats per triangle of the range, (u0, v0, u1, v1, u2, v2), entry k for triangle triFirst + k; NULL: the triangles' own s0, t0 ... s2, t2.
+ * Everything integer is exact, everything float is without FMA, 1.0f / x and sqrtf are the IEEE values.
+ *   1. Snap.  Per vertex fx = (u * (float)width) * 256.0f, fy = (v * (float)height) * 256.0f; X = (int32_t)floorf(fx + 0.5f), Y likewise: 8 sub-texel bits, no
+ *      flip, no wrap.  A triangle is skipped when any of its six values is not finite or |f| > 16777216.0f.
+ *   2. Area.  A2 = (X1-X0)*(Y2-Y0) - (Y1-Y0)*(X2-X0) in int64; a triangle with A2 == 0 is skipped; s = sign(A2).
+ *   3. Coverage.  Texel (x, y) has the centre P = (256x + 128, 256y + 128).  orient(Q,R,P) = (Rx-Qx)*(Py-Qy) - (Ry-Qy)*(Px-Qx) in int64;
+ *      wA = s*orient(B,C,P), wB = s*orient(C,A,P), wC = s*orient(A,B,P).  The triangle covers the texel when all three are >= 0 (edges are inclusive).  A
+ *      texel's owner is the lowest-indexed triangle of the range that covers it.
+ *   4. Barycentrics.  b1 = (float)((double)wB / (double)|A2|), b2 = (float)((double)wC / (double)|A2|).
+ *   5. Point.  e1 = v1 - v0, e2 = v2 - v0; pos = (v0 + b1*e1) + b2*e2; n = (n0 + b1*(n1-n0)) + b2*(n2-n0), d = dot(n, n) (section 3f's dot).  If d is not
+ *      finite or not > 0: n = cross(e1, e2), cross(a,b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x), and d its dot.  If d is still not finite or
+ *      not > 0, or a component of pos is not finite, the texel is empty (it does not pass to the next triangle).  Otherwise normal = n * (1.0f / sqrtf(d)),
+ *      time = params.time and stream = y*width + x.
+ *   6. Order.  The points are the non-empty owned texels in ascending y*width + x.
+ *   7. Gather.  The covered texels' values are, bit for bit, RaylibAMD_Gather(scene, &params.gather, thosePoints, count, ...).
+ *   8. Atlas.  A covered texel receives its value and coverage 1; every other texel +0 in all C channels (C = 4 or 27) and coverage 0.
+ *   9. Dilation.  Pass k = 1 .. dilate reads the atlas and the coverage as they were before the pass.  A texel of coverage 0 looks at its neighbours inside the
+ *      atlas in the order (-1,-1) (0,-1) (1,-1) (-1,0) (1,0) (-1,1) (0,1) (1,1); m = how many of them have coverage != 0.  If m > 0 each channel becomes (their sum
+ *      in that order, from +0) * (1.0f / (float)m), channel 3 of an IRRADIANCE texel becomes 1.0f, and the texel's coverage becomes 1 + k.
+ * The stream is the texel's index, not the point's rank: a texel draws the same paths whatever else is in the atlas. */
+typedef struct RaylibAMDLightmapParams {
+	int32_t width, height;        /* the atlas, 1 .. 16384 each */
+	int32_t triFirst, triCount;   /* triangles triFirst .. triFirst + triCount - 1 in RaylibAMD_SceneExportTriangles order; triCount -1: to the end */
+	int32_t dilate;               /* gutter passes, 0 .. 64 */
+	float   time;                 /* every point's time */
+	RaylibAMDGatherParams gather; /* kind IRRADIANCE or SH9 and the rest, as for RaylibAMD_Gather; its timeMin / timeMax are ignored (both are `time`) */
+} RaylibAMDLightmapParams;
+/* Statements 1 to 6 alone, on the device (rank 0's): the gather points of the atlas' covered texels in ascending texel index and (outTexel may be null) each
+ * one's texel index y * width + x, to host memory.  Returns the number of covered texels -- which may exceed capacity: min(count, capacity) records are
+ * written; outPoints may be null when capacity is 0 --, or -1 with nothing written for: a null scene or params, a scene not finalized, width or height outside
+ * 1 .. 16384, dilate outside 0 .. 64, a triangle range that is empty or not inside the scene, a time that is not finite, a negative capacity, more than 2^36 (triangle, texel-of-its-clipped-
+ * bounding-box) pairs to test -- thousands of triangles whose boxes span a large atlas: bake them in ranges --, anything
+ * RaylibAMD_Gather refuses of params.gather, no device or no memory.  The stats are left alone. */
+RAYLIB_API int64_t RaylibAMD_LightmapPoints(SceneHandle scene, const RaylibAMDLightmapParams* params, const float* uv, RaylibAMDGatherPoint* outPoints, uint32_t* outTexel,
+        int64_t capacity);
+/* The same on the host, no device needed: the oracle of statements 1 to 6. */
+RAYLIB_API int64_t RaylibAMD_LightmapPointsHost(SceneHandle scene, const RaylibAMDLightmapParams* params, const float* uv, RaylibAMDGatherPoint* outPoints, uint32_t* outTexel,
+        int64_t capacity);
+/* The whole bake, statements 1 to 9, from and to host memory; synchronous.  out: width * height * C floats, texel-major; outCoverage (may be null): one byte per
+ * texel.  Returns 1 -- an atlas without a covered texel is a success: zeros, coverage 0 --, or 0 with nothing written for the refusals above (out null
+ * included).  RaylibAMD_GetLastStats reports what the gather reports, with pixels = the covered texels and kernelMs the whole call's: the raster stages, the
+ * gather, the scatter and the dilation. */
+RAYLIB_API int32_t RaylibAMD_BakeLightmap(SceneHandle scene, const RaylibAMDLightmapParams* params, const float* uv, float* out, uint8_t* outCoverage);
+/* The same with uv, out and outCoverage in memory of rank 0's device (uv and out 4-byte aligned; refused otherwise), under the rules of RaylibAMD_GatherDevice.
+ * A non-null hipStream_t: the raster stages and the read-back of the count run first, on the library's stream -- ordered behind whatever that hipStream_t
+ * holds at the call, so a uv still being written there is read complete --, and are waited for, as uploads are; the gather,
+ * the scatter, the dilation and the copies into out and outCoverage are then enqueued on that stream and the call returns; the stats are left alone.
+ * Scratch, kept and grown by the library under the radiance calls' event chain: the owner map (4 bytes per texel), the ranks (4 per texel), 40 bytes per
+ * triangle of the range, the points and their values, and two atlases with their coverage for the dilation's ping-pong. */
+RAYLIB_API int32_t RaylibAMD_BakeLightmapDevice(SceneHandle scene, const RaylibAMDLightmapParams* params, const float* uv, float* out, uint8_t* outCoverage, void* stream);
+
 /* ---- procedural scene elements ----------------------------------------------------------
  * The reference's two procedural demo scenes (src/main.cc:913-984) `new` its C++ classes (Sphere, Cube, Triangle,
  * Lambertian, Metal, ...) in the application and pass the object pointers to Raylib_AddSceneElement.  A C ABI

@@ -7,6 +7,7 @@
 #include "rl_host.h"
 #include "rl_plan.h"
 #include "rl_progressive.h"
+#include "rl_lightmap.h"
 #include "raylib_amd_rng.h"
 
 #include <math.h>
@@ -942,6 +943,68 @@ int32_t RaylibAMD_GatherDirectionsHost(const RaylibAMDGatherParams* params, cons
 		outDirs[3 * (size_t)i + 0] = w[0] * k; outDirs[3 * (size_t)i + 1] = w[1] * k; outDirs[3 * (size_t)i + 2] = w[2] * k;
 	}
 	return 1;
+}
+
+// RaylibAMD_LightmapPoints / RaylibAMD_LightmapPointsHost / RaylibAMD_BakeLightmap / RaylibAMD_BakeLightmapDevice: what the four refuse alike.  Sets the triangle
+// range (triCount -1 resolved) and the gather's parameters as a radiance call's, with both ends of the time interval at the lightmap's time.
+static bool LightmapArgsValid(const char* who, const Scene* s, const RaylibAMDLightmapParams* p, int32_t& triFirst, int32_t& triCount, RaylibAMDRadianceParams& prm)
+{
+	if (!s || !p) { Log("%s: null argument", who); return false; }
+	if (!s->finalized) { Log("%s: scene was not finalized (Raylib_FinalizeScene)", who); return false; }
+	if (p->width < 1 || p->width > RL_LM_MAX_SIZE || p->height < 1 || p->height > RL_LM_MAX_SIZE) { Log("%s: the atlas %d x %d is outside 1 .. %d", who, p->width, p->height, RL_LM_MAX_SIZE); return false; }
+	if (p->dilate < 0 || p->dilate > RL_LM_MAX_DILATE) { Log("%s: dilate %d is outside 0 .. %d", who, p->dilate, RL_LM_MAX_DILATE); return false; }
+	const int64_t numTris = (int64_t)s->triangles.size();
+	triFirst = p->triFirst;
+	triCount = p->triCount == -1 ? (int32_t)std::max<int64_t>(0, numTris - (int64_t)p->triFirst) : p->triCount;
+	if (triFirst < 0 || triCount <= 0 || (int64_t)triFirst + (int64_t)triCount > numTris) {
+		Log("%s: triangles %d .. %d + %d are not a non-empty range of the scene's %lld", who, p->triFirst, p->triFirst, p->triCount, (long long)numTris);
+		return false;
+	}
+	if (!std::isfinite(p->time)) { Log("%s: the time is not finite", who); return false; }
+	const RaylibAMDGatherParams& g = p->gather;
+	prm.maxPathLength = g.maxPathLength; prm.rayTMin = g.rayTMin; prm.sampleFirst = g.sampleFirst; prm.sampleCount = g.sampleCount; prm.skipDraws = g.skipDraws;
+	prm.timeMin = prm.timeMax = p->time;
+	return RadianceParamsValid(who, s, &prm) && GatherKindValid(who, &g);
+}
+static int64_t LightmapPointsInternal(const char* who, SceneHandle sh, const RaylibAMDLightmapParams* params, const float* uv, RaylibAMDGatherPoint* outPoints, uint32_t* outTexel,
+                                      int64_t capacity, bool device)
+{
+	Scene* s = (Scene*)sh;
+	int32_t triFirst = 0, triCount = 0; RaylibAMDRadianceParams prm;
+	if (!LightmapArgsValid(who, s, params, triFirst, triCount, prm)) return -1;
+	if (capacity < 0 || (capacity > 0 && !outPoints)) { Log("%s: a negative capacity, or no room for the points", who); return -1; }
+	if (!device) return LightmapPointsHost(*s, *params, triFirst, triCount, uv, outPoints, outTexel, capacity);
+	if (!DeviceAvailable()) return -1;
+	return DeviceLightmapPoints(*s, *params, triFirst, triCount, uv, outPoints, outTexel, capacity);
+}
+int64_t RaylibAMD_LightmapPoints(SceneHandle sh, const RaylibAMDLightmapParams* params, const float* uv, RaylibAMDGatherPoint* outPoints, uint32_t* outTexel, int64_t capacity)
+{
+	return LightmapPointsInternal("RaylibAMD_LightmapPoints", sh, params, uv, outPoints, outTexel, capacity, true);
+}
+int64_t RaylibAMD_LightmapPointsHost(SceneHandle sh, const RaylibAMDLightmapParams* params, const float* uv, RaylibAMDGatherPoint* outPoints, uint32_t* outTexel, int64_t capacity)
+{
+	return LightmapPointsInternal("RaylibAMD_LightmapPointsHost", sh, params, uv, outPoints, outTexel, capacity, false);
+}
+static int32_t BakeLightmapInternal(const char* who, SceneHandle sh, const RaylibAMDLightmapParams* params, const float* uv, float* out, uint8_t* outCoverage, bool hostMem, void* stream)
+{
+	Scene* s = (Scene*)sh;
+	int32_t triFirst = 0, triCount = 0; RaylibAMDRadianceParams prm;
+	if (!out) { Log("%s: null argument", who); return 0; }
+	if (!LightmapArgsValid(who, s, params, triFirst, triCount, prm)) return 0;
+	if (!DeviceAvailable()) return 0;
+	if (!PreparePathScene(who, s, prm, 1)) return 0;
+	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
+	if (!DeviceBakeLightmap(*s, *params, triFirst, triCount, prm, CurrentSeed(), uv, out, outCoverage, hostMem, stream, stats)) return 0;
+	if (!stream) { std::lock_guard<std::mutex> lk(g_stateMu); g_lastStats = stats; }
+	return 1;
+}
+int32_t RaylibAMD_BakeLightmap(SceneHandle sh, const RaylibAMDLightmapParams* params, const float* uv, float* out, uint8_t* outCoverage)
+{
+	return BakeLightmapInternal("RaylibAMD_BakeLightmap", sh, params, uv, out, outCoverage, true, nullptr);
+}
+int32_t RaylibAMD_BakeLightmapDevice(SceneHandle sh, const RaylibAMDLightmapParams* params, const float* uv, float* out, uint8_t* outCoverage, void* stream)
+{
+	return BakeLightmapInternal("RaylibAMD_BakeLightmapDevice", sh, params, uv, out, outCoverage, false, stream);
 }
 
 int32_t RaylibAMD_SceneNumTriangles(SceneHandle sh) { Scene* s = (Scene*)sh; return s ? (int32_t)s->triangles.size() : 0; }

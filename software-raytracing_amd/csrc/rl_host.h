@@ -275,6 +275,17 @@ constexpr uint64_t RL_GATHER_MAX_SLOTS = 1ull << 28;
 constexpr uint64_t RL_GATHER_TIMED = 4096;
 bool DeviceGather(Scene& scene, int32_t kind, const RaylibAMDRadianceParams& prm, uint64_t seed, const void* points, int32_t n, float* out, bool hostMem, void* stream,
                   RaylibAMDStats& stats);
+// Lightmaps (include/raylib_amd.h RaylibAMD_BakeLightmap).  The ABI checked the arguments: the atlas' size, the dilation, the time, triFirst / triCount a non-empty
+// range of the scene's triangles, capacity >= 0, prm the gather's parameters as a radiance call's with timeMin = timeMax = the time.
+// LightmapPointsHost (rl_lightmap_host.cc): the oracle of the raster stages; -1 without memory.
+int64_t LightmapPointsHost(const Scene& scene, const RaylibAMDLightmapParams& P, int32_t triFirst, int32_t triCount, const float* uv,
+                           RaylibAMDGatherPoint* outPoints, uint32_t* outTexel, int64_t capacity);
+// DeviceLightmapPoints: the raster stages on rank 0's device (rl_lightmap.hip's kernels), uv and the outputs in host memory; the count, or -1.
+int64_t DeviceLightmapPoints(Scene& scene, const RaylibAMDLightmapParams& P, int32_t triFirst, int32_t triCount, const float* uv,
+                             RaylibAMDGatherPoint* outPoints, uint32_t* outTexel, int64_t capacity);
+// DeviceBakeLightmap: raster, gather, scatter, dilation.  hostMem: uv / out / outCoverage in host memory (stream is null), else device pointers; stream as DeviceGather's.
+bool DeviceBakeLightmap(Scene& scene, const RaylibAMDLightmapParams& P, int32_t triFirst, int32_t triCount, const RaylibAMDRadianceParams& prm, uint64_t seed,
+                        const float* uv, float* out, uint8_t* outCoverage, bool hostMem, void* stream, RaylibAMDStats& stats);
 bool DevicePostProcess(Image& img);          // Image2D::PostProcess on the device; false when no device
 bool DeviceDumpRGB(Image& img, float* outRGB);   // a device-resident frame packed to RGB on the device and copied to caller memory through pinned staging; false: not applicable
 bool DeviceReadback(Image& img);            // device copy -> img.rgba (the caller checked hostStale)

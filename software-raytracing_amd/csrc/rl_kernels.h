@@ -12,6 +12,7 @@
 //   rl_radiance.hip      k_radiance (RaylibAMD_TraceRadiance): the same reason, towards the render and the query kernels alike
 //   rl_gather.hip        k_gather (RaylibAMD_Gather: rl_k_radiance.inl's twin, the generator instances of its loop) and k_gather_resolve: beside k_radiance they would be
 //                        more callers of the walks and the shading it inlines
+//   rl_lightmap.hip      k_lm_*: the lightmap rasteriser, its scans and the atlas stages (RaylibAMD_BakeLightmap); no walk, no shading
 // A twin takes the view table (DViews) as one more trailing argument.  Default template arguments are given here and nowhere else.
 #pragma once
 
@@ -190,6 +191,50 @@ RL_GATHER_INSTANCES(extern RL_K_GATHER)
 template <int GEN> __global__ void __launch_bounds__(RL_BLOCK) k_gather_resolve(RL_GATHER_RESOLVE_ARGS);
 extern template __global__ void k_gather_resolve<RL_GEN_HEMISPHERE>(RL_GATHER_RESOLVE_ARGS);
 extern template __global__ void k_gather_resolve<RL_GEN_SPHERE>(RL_GATHER_RESOLVE_ARGS);
+
+// ---------------------------------------------------------------------------
+// Lightmaps (RaylibAMD_BakeLightmap; rl_lightmap.hip, arithmetic of rl_lightmap.h).  tris: the range's records of 26 floats (rl_host.h HostTriangle); uv: six
+// floats per triangle, or null for the records' own.  A triangle's raster record: its snapped corners and the rectangle of texel centres in its box (rw 0: skipped).
+struct DLmTri { int32_t X[3], Y[3]; uint32_t lo; uint32_t rw; };   // lo: the rectangle's first column | its first row << 16
+static_assert(sizeof(DLmTri) == 32, "raster record");
+// one thread per triangle: the record, and the rectangle's texel count into counts[k]
+__global__ void __launch_bounds__(RL_BLOCK)
+k_lm_setup(const float* __restrict__ tris, const float* __restrict__ uv, uint32_t numTris, int32_t width, int32_t height, DLmTri* __restrict__ rec, unsigned long long* __restrict__ counts);
+// one thread per (triangle, rectangle texel) pair base + i, i < pairs: the triangle by binary search in the scanned counts offs[0 .. numTris], statement 3, atomicMin into owner
+__global__ void __launch_bounds__(RL_BLOCK)
+k_lm_cover(const DLmTri* __restrict__ rec, const unsigned long long* __restrict__ offs, uint32_t numTris, unsigned long long base, uint32_t pairs, int32_t width, uint32_t numTexels, uint32_t* __restrict__ owner);
+// one thread per texel, statements 3 to 5 from the owner.  WRITE false: rank[i] = the texel has a point.  WRITE true, rank scanned (rank[numTexels] the count): the
+// point of a texel whose rank is below capacity into points[rank] (two float4) and its index into texel[rank] (may be null)
+template <bool WRITE> __global__ void __launch_bounds__(RL_BLOCK)
+k_lm_points(const DLmTri* __restrict__ rec, const float* __restrict__ tris, const uint32_t* __restrict__ owner, uint32_t* __restrict__ rank, int32_t width, uint32_t numTexels,
+            float time, float4* __restrict__ points, uint32_t* __restrict__ texel, unsigned long long capacity);
+extern template __global__ void k_lm_points<false>(const DLmTri* __restrict__, const float* __restrict__, const uint32_t* __restrict__, uint32_t* __restrict__, int32_t, uint32_t, float, float4* __restrict__, uint32_t* __restrict__, unsigned long long);
+extern template __global__ void k_lm_points<true>(const DLmTri* __restrict__, const float* __restrict__, const uint32_t* __restrict__, uint32_t* __restrict__, int32_t, uint32_t, float, float4* __restrict__, uint32_t* __restrict__, unsigned long long);
+// The exclusive scan of n values in place, data[n] receiving the total, as reduce, scan, add over tiles of RL_SCAN_TILE values: k_lm_scan_reduce (a block per tile)
+// leaves the tiles' sums, k_lm_scan_sums (one block) scans them in place with sums[numTiles] the total, k_lm_scan_add (a block per tile) scans each tile from its sum.
+#define RL_SCAN_PER 8
+#define RL_SCAN_TILE (RL_BLOCK * RL_SCAN_PER)
+#define RL_SCAN_SUMS_BLOCK 1024
+template <typename T> __global__ void __launch_bounds__(RL_BLOCK) k_lm_scan_reduce(const T* __restrict__ data, unsigned long long n, T* __restrict__ sums);
+template <typename T> __global__ void __launch_bounds__(RL_SCAN_SUMS_BLOCK) k_lm_scan_sums(T* __restrict__ sums, uint32_t numTiles);
+template <typename T> __global__ void __launch_bounds__(RL_BLOCK) k_lm_scan_add(T* __restrict__ data, unsigned long long n, const T* __restrict__ sums, uint32_t numTiles);
+#define RL_LM_SCAN_INSTANCES(X, T) \
+	X template __global__ void k_lm_scan_reduce<T>(const T* __restrict__, unsigned long long, T* __restrict__); \
+	X template __global__ void k_lm_scan_sums<T>(T* __restrict__, uint32_t); \
+	X template __global__ void k_lm_scan_add<T>(T* __restrict__, unsigned long long, const T* __restrict__, uint32_t);
+RL_LM_SCAN_INSTANCES(extern, uint32_t)
+RL_LM_SCAN_INSTANCES(extern, unsigned long long)
+// statement 8, one thread per texel: a texel with a point (rank[i + 1] != rank[i]) takes values[rank[i]] (C floats) and coverage 1, every other +0 and 0
+template <int C> __global__ void __launch_bounds__(RL_BLOCK)
+k_lm_scatter(const uint32_t* __restrict__ rank, const float* __restrict__ values, uint32_t numTexels, float* __restrict__ atlas, uint8_t* __restrict__ coverage);
+// statement 9, one pass, one thread per texel: src -> dst
+template <int C> __global__ void __launch_bounds__(RL_BLOCK)
+k_lm_dilate(const float* __restrict__ src, const uint8_t* __restrict__ srcCov, float* __restrict__ dst, uint8_t* __restrict__ dstCov, int32_t width, int32_t height, int32_t pass);
+#define RL_LM_ATLAS_INSTANCES(X, C) \
+	X template __global__ void k_lm_scatter<C>(const uint32_t* __restrict__, const float* __restrict__, uint32_t, float* __restrict__, uint8_t* __restrict__); \
+	X template __global__ void k_lm_dilate<C>(const float* __restrict__, const uint8_t* __restrict__, float* __restrict__, uint8_t* __restrict__, int32_t, int32_t, int32_t);
+RL_LM_ATLAS_INSTANCES(extern, 4)
+RL_LM_ATLAS_INSTANCES(extern, 27)
 
 // ---------------------------------------------------------------------------
 // Test hooks (rl_rt_hooks.hip): single functions of the hot path evaluated on arrays

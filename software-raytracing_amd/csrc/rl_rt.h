@@ -5,6 +5,7 @@
 //   rl_rt_frame.hip   kernel selection and the one enqueue path of every render (EnqueueFrame), a rank's one-view render, a batch of views
 //   rl_rt_render.hip  whole frames over N ranks (gather, scatter, two frames in flight), DeviceRender, progressive sessions
 //   rl_rt_rays.hip    caller rays: DeviceTraceRays, DeviceTraceRadiance, DeviceGather
+//   rl_rt_lightmap.hip  lightmaps: DeviceLightmapPoints, DeviceBakeLightmap (the raster stages, then DeviceGather's body, then the atlas stages)
 //   rl_rt_hooks.hip   test hooks
 //
 // Ranks.  RAYLIB_NUM_GPUS = N (default 1) makes the library drive N devices from this one process: the frame's 8x8
@@ -77,6 +78,7 @@ struct DeviceSceneCopy {
 	DevBuf<DNode> nodes; DevBuf<DTriIsect> isect; DevBuf<DTriShade> shade; DevBuf<int32_t> alphaTex;
 	DevBuf<DMaterial> materials; DevBuf<DTexture> textures; DevBuf<float> texels;
 	DevBuf<DSphere> spheres; DevBuf<DCube> cubes;
+	DevBuf<float> lmTris;        // the scene's triangles in RaylibAMD_SceneExportTriangles order (26 floats each), uploaded when a lightmap call first needs them
 	DevBuf<int32_t> slotIndex;   // triangle slot -> index in the scene's triangle order (the ray queries' primitive numbers), uploaded when a query first needs it
 	// the sky panorama is read when a render starts, as the reference does (renderer.cc:159-176 dereferences the handle per miss)
 	DevBuf<float4> sky;
@@ -191,6 +193,14 @@ struct RankCtx {
 	DevBuf<float4> gSamples;
 	DevBuf<float> gAcc;
 	std::vector<hipEvent_t> gEv;
+	// a lightmap bake's scratch (rl_rt_lightmap.hip), kept and grown, behind the same event: the raster records and the counts of the range's triangles with
+	// the scans' tile sums, a host call's uv, the owner map and the ranks (one word per texel each), the points, their texel indices and values, the two
+	// atlases and coverage maps of the dilation's ping-pong; the pinned word the counts are read back through and the events around the stages
+	DevBuf<DLmTri> lmRec; DevBuf<unsigned long long> lmCounts, lmSums; DevBuf<float> lmUv;
+	DevBuf<uint32_t> lmOwner, lmRank, lmTexel; DevBuf<float4> lmPoints; DevBuf<float> lmValues, lmAtlas[2]; DevBuf<uint8_t> lmCov[2];
+	PinBuf<unsigned long long> lmHost;
+	hipEvent_t lmEv[5] = {};
+	hipEvent_t lmInEv = nullptr;   // recorded on a caller's stream when a bake enters: the raster stages, on the library's stream, wait for it before they read the caller's uv
 };
 
 // The one runtime of the process (Rt()): never destroyed, so no buffer is freed behind the HIP runtime's back at exit.
@@ -237,6 +247,9 @@ bool EnsureWideTree(DeviceSceneCopy* C, const Scene& sc, int32_t tree);
 bool ReadbackLocked(Image& img);                       // device copy -> img.rgba
 bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRender& pend, ProgressiveSession* prog = nullptr);   // rl_rt_frame.hip
 bool FinishRender(RankCtx& R, PendingRender& pend, RaylibAMDStats& stats);
+bool OnDevice(const void* p, int device);              // rl_rt_rays.hip: p is memory of that device
+bool GatherLocked(Scene& sc, RankCtx& R, int32_t kind, const RaylibAMDRadianceParams& prm, uint64_t seed, const void* points, int32_t n, float* out, bool hostMem, void* stream,
+                  std::chrono::steady_clock::time_point t0, RaylibAMDStats& stats);   // DeviceGather behind its entry; R's device is current
 bool DrainLocked();                                    // rl_rt_render.hip: waits for the multi-rank frames in flight (RenderMulti)
 
 // what every call reports beside its counters: the scene's size, (one rank's calls) one rank on one device, and the call's time on the host's clock

@@ -43,7 +43,7 @@ static_assert(sizeof(RaylibAMDGatherPoint) == sizeof(RaylibAMDRay), "gather reco
 static_assert(RL_RADIANCE_STACK_BUDGET / ((uint64_t)RL_RADIANCE_MAX_PATH * 8 * sizeof(float) * RL_BLOCK) >= 1, "one workgroup's path stack fits the budget");
 
 // a device pointer a call may use: memory of rank 0's device
-static bool OnDevice(const void* p, int device)
+bool OnDevice(const void* p, int device)
 {
 	hipPointerAttribute_t a;
 	if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
@@ -263,6 +263,13 @@ bool DeviceGather(Scene& sc, int32_t kind, const RaylibAMDRadianceParams& prm, u
 	if (!EnsureRuntime()) return false;
 	RankCtx& R = Rank0();
 	HIP_OK(hipSetDevice(R.device));
+	return GatherLocked(sc, R, kind, prm, seed, points, n, out, hostMem, stream, t0, stats);
+}
+// ... the call behind its locked entry: the runtime lock is held and R's device is current.  A lightmap bake (rl_rt_lightmap.hip) enters here with its points
+// on the device.
+bool GatherLocked(Scene& sc, RankCtx& R, int32_t kind, const RaylibAMDRadianceParams& prm, uint64_t seed, const void* points, int32_t n, float* out, bool hostMem, void* stream,
+                  std::chrono::steady_clock::time_point t0, RaylibAMDStats& stats)
+{
 	const RenderKnobs knobs = ReadRenderKnobs();
 	const bool sphere = kind == RAYLIB_AMD_GATHER_SH9;
 	const uint32_t outFloats = sphere ? 27u : 4u, sums = sphere ? 27u : 3u;

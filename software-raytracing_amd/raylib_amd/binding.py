@@ -279,6 +279,79 @@ def gather_directions_host(lib, points, kind, seed, sample=0, sample_first=0, sk
     return out
 
 
+class LightmapParams(C.Structure):
+    """include/raylib_amd.h RaylibAMDLightmapParams."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("triFirst", C.c_int32), ("triCount", C.c_int32), ("dilate", C.c_int32), ("time", C.c_float),
+                ("gather", GatherParams)]
+
+
+def lightmap_params(w, h, kind=GATHER_IRRADIANCE, tri_first=0, tri_count=-1, dilate=0, time=0.0, max_path=5, tmin=1e-4, sample_first=0, sample_count=1, skip_draws=0):
+    return LightmapParams(int(w), int(h), int(tri_first), int(tri_count), int(dilate), float(time),
+                          GatherParams(int(kind), int(max_path), float(tmin), int(sample_first), int(sample_count), int(skip_draws), 0.0, 0.0))
+
+
+def _uv_host(uv):
+    if uv is None:
+        return None, None
+    a = np.ascontiguousarray(uv, np.float32).reshape(-1, 6)
+    return a, a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def lightmap_points(lib, scene, w, h, uv=None, tri_first=0, tri_count=-1, time=0.0, host=False, capacity=None):
+    """The gather points of the atlas' covered texels (RaylibAMD_LightmapPoints, or with host=True the oracle RaylibAMD_LightmapPointsHost).
+
+    uv: None (the triangles' own) or (triangles of the range, 6) float32.  Returns (points (n, 8) float32 as binding.gather takes them, texel indices (n,) uint32,
+    count); n = min(count, capacity), capacity defaulting to the atlas' texels.  Raises RuntimeError when the library refuses the call."""
+    prm = lightmap_params(w, h, tri_first=tri_first, tri_count=tri_count, time=time)
+    cap = int(w) * int(h) if capacity is None else int(capacity)
+    keep, uvp = _uv_host(uv)
+    pts = np.zeros((max(cap, 1), 8), np.float32)
+    tex = np.zeros(max(cap, 1), np.uint32)
+    fn = lib.RaylibAMD_LightmapPointsHost if host else lib.RaylibAMD_LightmapPoints
+    n = fn(scene, C.byref(prm), uvp, pts.ctypes.data_as(C.POINTER(GatherPoint)), tex.ctypes.data_as(C.POINTER(C.c_uint32)), cap)
+    if n < 0:
+        raise RuntimeError("%s refused the call" % ("RaylibAMD_LightmapPointsHost" if host else "RaylibAMD_LightmapPoints"))
+    k = min(int(n), cap)
+    return pts[:k], tex[:k], int(n)
+
+
+def bake_lightmap(lib, scene, w, h, uv=None, kind=GATHER_IRRADIANCE, tri_first=0, tri_count=-1, dilate=0, time=0.0, max_path=5, tmin=1e-4, sample_first=0,
+                  sample_count=1, skip_draws=0, device=None):
+    """A lightmap of the scene's triangles (RaylibAMD_BakeLightmap / RaylibAMD_BakeLightmapDevice): (atlas (H, W, C) float32, coverage (H, W) uint8), C = 4 or 27.
+
+    uv: None, a NumPy array (triangles of the range, 6) -- the host entry, NumPy results -- or a float32 torch tensor on the device -- the device entry on
+    torch's current stream, torch results.  device: a torch device, for the device entry with uv=None.  Raises RuntimeError when the library refuses the call."""
+    kind = int(kind)
+    if kind not in _GATHER_FLOATS:
+        raise ValueError("unknown gather kind %r" % kind)
+    c = _GATHER_FLOATS[kind]
+    prm = lightmap_params(w, h, kind, tri_first, tri_count, dilate, time, max_path, tmin, sample_first, sample_count, skip_draws)
+    if device is None and (uv is None or isinstance(uv, np.ndarray)):
+        keep, uvp = _uv_host(uv)
+        out = np.zeros((int(h), int(w), c), np.float32)
+        cov = np.zeros((int(h), int(w)), np.uint8)
+        if lib.RaylibAMD_BakeLightmap(scene, C.byref(prm), uvp, out.ctypes.data_as(C.POINTER(C.c_float)), cov.ctypes.data_as(C.POINTER(C.c_uint8))) != 1:
+            raise RuntimeError("RaylibAMD_BakeLightmap refused the call")
+        return out, cov
+    import torch
+    if uv is not None:
+        if not (isinstance(uv, torch.Tensor) and uv.is_cuda and uv.dtype == torch.float32):
+            raise TypeError("uv: None, a float32 NumPy array or a float32 torch tensor on the device")
+        uv = uv.reshape(-1, 6).contiguous()
+        device = uv.device
+    out = torch.empty((int(h), int(w), c), dtype=torch.float32, device=device)
+    cov = torch.empty((int(h), int(w)), dtype=torch.uint8, device=device)
+    stream = torch.cuda.current_stream(out.device)
+    if stream.cuda_stream == 0:
+        stream.synchronize()   # (as gather: the library's stream is not ordered against torch's default stream)
+    uvp = C.cast(C.c_void_p(uv.data_ptr()), C.POINTER(C.c_float)) if uv is not None else None
+    ok = lib.RaylibAMD_BakeLightmapDevice(scene, C.byref(prm), uvp, C.cast(C.c_void_p(out.data_ptr()), C.POINTER(C.c_float)),
+                                          C.cast(C.c_void_p(cov.data_ptr()), C.POINTER(C.c_uint8)), C.c_void_p(stream.cuda_stream))
+    if ok != 1:
+        raise RuntimeError("RaylibAMD_BakeLightmapDevice refused the call")
+    return out, cov
+
+
 # Per-ray / per-unit algorithmic byte constants of the flat layout (csrc/rl_device.h)
 NODE_B, TRI_B, SHADE_B, TEXEL_B, PIXEL_B = 64, 64, 64, 16, 16
 
@@ -355,6 +428,10 @@ _EXPORTS = {
     "RaylibAMD_GatherDevice": (C.c_int32, [C.c_void_p, C.POINTER(GatherParams), C.POINTER(GatherPoint), C.c_int32, C.POINTER(C.c_float), C.c_void_p]),
     "RaylibAMD_GatherDirectionsHost": (C.c_int32, [C.POINTER(GatherParams), C.POINTER(GatherPoint), C.c_int32, C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]),
     "RaylibAMD_PlanGatherCut": (C.c_int32, [C.POINTER(GatherParams), C.c_int32, C.c_uint64, C.POINTER(GatherCut)]),
+    "RaylibAMD_LightmapPoints": (C.c_int64, [C.c_void_p, C.POINTER(LightmapParams), C.POINTER(C.c_float), C.POINTER(GatherPoint), C.POINTER(C.c_uint32), C.c_int64]),
+    "RaylibAMD_LightmapPointsHost": (C.c_int64, [C.c_void_p, C.POINTER(LightmapParams), C.POINTER(C.c_float), C.POINTER(GatherPoint), C.POINTER(C.c_uint32), C.c_int64]),
+    "RaylibAMD_BakeLightmap": (C.c_int32, [C.c_void_p, C.POINTER(LightmapParams), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint8)]),
+    "RaylibAMD_BakeLightmapDevice": (C.c_int32, [C.c_void_p, C.POINTER(LightmapParams), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.c_void_p]),
     "RaylibAMD_VerifyExactMath": (C.c_int32, [C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "RaylibAMD_CullCells": (C.c_int32, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_float)]),
     "RaylibAMD_SceneNumTriangles": (C.c_int32, [C.c_void_p]),

@@ -6,6 +6,6 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=${TMPDIR:-/tmp}/flatten_host_check
 SRC="$ROOT/software-raytracing_amd/csrc"
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -ffp-contract=off -DRAYLIB_EXPORTS=1 \
-    -I"$ROOT/include" -I"$SRC" "$ROOT/tools/flatten_host_check.cc" "$SRC"/rl_abi.cc "$SRC"/rl_scene.cc "$SRC"/rl_bvh.cc "$SRC"/rl_cull.cc "$SRC"/rl_plan.cc "$SRC"/rl_obj_loader.cc \
+    -I"$ROOT/include" -I"$SRC" "$ROOT/tools/flatten_host_check.cc" "$SRC"/rl_abi.cc "$SRC"/rl_scene.cc "$SRC"/rl_bvh.cc "$SRC"/rl_cull.cc "$SRC"/rl_plan.cc "$SRC"/rl_lightmap_host.cc "$SRC"/rl_obj_loader.cc \
     "$SRC"/rl_image_io.cc "$SRC"/rl_jpeg.cc "$SRC"/rl_log.cc "$ROOT/tools/nodevice_stub.cc" -o "$OUT" -lz -lpthread
 RAYLIB_QUIET=1 ASAN_OPTIONS=detect_leaks=0:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 "$OUT"

@@ -10,6 +10,8 @@ bool DeviceClosestHit(Scene&, const float*, int32_t, float, void*) { return fals
 bool DeviceTraceRays(Scene&, int32_t, const void*, int32_t, float, void*, int32_t*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceTraceRadiance(Scene&, const RaylibAMDRadianceParams&, uint64_t, const void*, int32_t, float*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceGather(Scene&, int32_t, const RaylibAMDRadianceParams&, uint64_t, const void*, int32_t, float*, bool, void*, RaylibAMDStats&) { return false; }
+int64_t DeviceLightmapPoints(Scene&, const RaylibAMDLightmapParams&, int32_t, int32_t, const float*, RaylibAMDGatherPoint*, uint32_t*, int64_t) { return -1; }
+bool DeviceBakeLightmap(Scene&, const RaylibAMDLightmapParams&, int32_t, int32_t, const RaylibAMDRadianceParams&, uint64_t, const float*, float*, uint8_t*, bool, void*, RaylibAMDStats&) { return false; }
 bool DevicePostProcess(Image&) { return false; }
 void* DeviceImagePixels(Image&) { return nullptr; }
 bool DeviceReadback(Image&) { return false; }
