@@ -327,6 +327,55 @@ RAYLIB_API int32_t RaylibAMD_BakeLightmap(SceneHandle scene, const RaylibAMDLigh
  * triangle of the range, the points and their values, and two atlases with their coverage for the dilation's ping-pong. */
 RAYLIB_API int32_t RaylibAMD_BakeLightmapDevice(SceneHandle scene, const RaylibAMDLightmapParams* params, const float* uv, float* out, uint8_t* outCoverage, void* stream);
 
+/* ---- an edge-avoiding filter over the atlas' covered texels, between statements 8 and 9 ---------------
+ * An a-trous filter (Dammertz et al. 2010) guided by each covered texel's gather point -- its world position and normal -- and by the values themselves: it
+ * never reads a gutter, and charts that are neighbours in the atlas and apart in the world do not blend.  Everything is float, without FMA, the divisions are
+ * IEEE and expf is csrc/rl_glibc_math.h's expf_ (glibc's, bit for bit).
+ *   F1. Channels.  C = 4 (IRRADIANCE) or 27 (SH9).  The key channels are 0, 1, 2 in both kinds: E.rgb, or the rgb of coefficient 0.  The filtered channels are
+ *       0 .. 2 for IRRADIANCE and 0 .. 26 for SH9.
+ *   F2. Participants.  Only the texels of coverage 1 after statement 8 take part, as centres and as taps; every other texel stays +0 with coverage 0 until
+ *       statement 9.
+ *   F3. Preparation.  I_0 = the texel's value with every channel that is not finite read as 0.  The guides are the texel's gather point: P = pos, n = normal.
+ *   F4. Constants, computed once on the host and handed to both paths as they are, for i = 0 .. K-1 (K = iterations):
+ *         invC_i = (float)(1u << (2*i)) / (sigmaColor * sigmaColor)      invN = 1.0f / (sigmaNormal * sigmaNormal)
+ *         sp = sigmaPosition * (float)(1u << i); invP_i = 1.0f / (sp * sp)
+ *   F5. Iteration i, step s = 2^i.  The taps of texel p = (x, y) are q = p + s*(dx, dy), dy outer, dx inner, both -2 .. 2; a tap outside the atlas or whose
+ *       coverage is not 1 is skipped.  With g(v) = c / (1.0f + c), c = v > 0 ? v : 0, and Dist2(a, b) = d0*d0 + d1*d1 + d2*d2 of the three differences a - b,
+ *       summed left to right:
+ *         dc = (g(I_i(q)[0]) - g(I_i(p)[0]))^2 + (... [1])^2 + (... [2])^2, as a Dist2;  dn = Dist2(n(q), n(p));  dp = Dist2(P(q), P(p))
+ *         w  = (k[dx+2] * k[dy+2]) * expf(-(dc*invC_i + dn*invN + dp*invP_i)),  k = {1/16, 1/4, 3/8, 1/4, 1/16}
+ *         I_{i+1}(p)[c] = (sum of w * I_i(q)[c]) / (sum of w) for every filtered channel c, both sums in tap order from +0, the same w for every channel.
+ *       The centre tap always counts (its w is 9/64), so the divisor is >= 9/64.
+ *   F6. Result.  I_K; channel 3 of an IRRADIANCE texel is written 1.0f.
+ * The filter sees neither params.dilate nor how the gather was cut into launches. */
+typedef struct RaylibAMDLightmapFilterParams {
+	int32_t iterations;      /* K, 1 .. 8: steps 1, 2, 4 ... 2^(K-1) texels apart */
+	float   sigmaColor;      /* tolerance of the colour distance; halves per step */
+	float   sigmaNormal;     /* ... of the normal distance */
+	float   sigmaPosition;   /* world-space distance tolerated between texels ONE texel apart; doubles per step */
+} RaylibAMDLightmapFilterParams;   /* each sigma finite and in [1e-3, 1e3]; there are no defaults: the position's scale is the caller's */
+/* RaylibAMD_BakeLightmap / RaylibAMD_BakeLightmapDevice with statement F between statements 8 and 9.  Refusals, memory rules, stream rules and stats are theirs
+ * (kernelMs includes the filter); refused as well, with nothing written: a null filter, iterations outside 1 .. 8, a sigma that is not finite or outside
+ * [1e-3, 1e3].  Scratch beside the bakes': a second array of the points' values (the iterations' ping-pong). */
+RAYLIB_API int32_t RaylibAMD_BakeLightmapFiltered(SceneHandle scene, const RaylibAMDLightmapParams* params, const RaylibAMDLightmapFilterParams* filter, const float* uv,
+        float* out, uint8_t* outCoverage);
+RAYLIB_API int32_t RaylibAMD_BakeLightmapFilteredDevice(SceneHandle scene, const RaylibAMDLightmapParams* params, const RaylibAMDLightmapFilterParams* filter, const float* uv,
+        float* out, uint8_t* outCoverage, void* stream);
+/* An atlas the caller already has -- a raw bake made with dilate 0 and kept -- filtered again without tracing a path: statements 1 to 6 for the ownership and the
+ * guides, then `in`'s value at every covered texel (whatever `in` holds elsewhere is ignored), statement F, and statement 9 with params.dilate.  in and out:
+ * width * height * C floats; out may be in.  params.gather is checked as a bake checks it; only its kind is used.  Refusals as above, a null `in` included;
+ * memory and stream rules as the bakes' (`in` as `out`).  The stats of the host entry: pixels = the covered texels, kernelMs the whole call's, no rays. */
+RAYLIB_API int32_t RaylibAMD_FilterLightmap(SceneHandle scene, const RaylibAMDLightmapParams* params, const RaylibAMDLightmapFilterParams* filter, const float* uv,
+        const float* in, float* out, uint8_t* outCoverage);
+RAYLIB_API int32_t RaylibAMD_FilterLightmapDevice(SceneHandle scene, const RaylibAMDLightmapParams* params, const RaylibAMDLightmapFilterParams* filter, const float* uv,
+        const float* in, float* out, uint8_t* outCoverage, void* stream);
+/* Statement F alone on the host, without a device or a scene: the oracle.  It works in compacted form, on what RaylibAMD_LightmapPointsHost and RaylibAMD_Gather
+ * return: points and texel (strictly ascending texel indices y * width + x) of `count` covered texels, values and outValues count x C floats; outValues may be
+ * values.  Returns 1 (count == 0 included), or 0 with nothing written for a null pointer with count > 0, count < 0, an unknown kind, filter params as refused
+ * above, width or height outside 1 .. 16384, a texel array that is not strictly ascending or has an entry >= width * height, or no memory. */
+RAYLIB_API int32_t RaylibAMD_FilterLightmapHost(int32_t width, int32_t height, int32_t kind, const RaylibAMDLightmapFilterParams* filter, const RaylibAMDGatherPoint* points,
+        const uint32_t* texel, int64_t count, const float* values, float* outValues);
+
 /* ---- procedural scene elements ----------------------------------------------------------
  * The reference's two procedural demo scenes (src/main.cc:913-984) `new` its C++ classes (Sphere, Cube, Triangle,
  * Lambertian, Metal, ...) in the application and pass the object pointers to Raylib_AddSceneElement.  A C ABI

@@ -985,16 +985,28 @@ int64_t RaylibAMD_LightmapPointsHost(SceneHandle sh, const RaylibAMDLightmapPara
 {
 	return LightmapPointsInternal("RaylibAMD_LightmapPointsHost", sh, params, uv, outPoints, outTexel, capacity, false);
 }
-static int32_t BakeLightmapInternal(const char* who, SceneHandle sh, const RaylibAMDLightmapParams* params, const float* uv, float* out, uint8_t* outCoverage, bool hostMem, void* stream)
+// RaylibAMD_BakeLightmapFiltered* / RaylibAMD_FilterLightmap*: the filter's own refusals
+static bool LightmapFilterValid(const char* who, const RaylibAMDLightmapFilterParams* f)
+{
+	if (!f) { Log("%s: null filter", who); return false; }
+	if (f->iterations < 1 || f->iterations > 8) { Log("%s: %d filter iterations are outside 1 .. 8", who, f->iterations); return false; }
+	for (const float sigma : { f->sigmaColor, f->sigmaNormal, f->sigmaPosition })
+		if (!(std::isfinite(sigma) && sigma >= 1e-3f && sigma <= 1e3f)) { Log("%s: a filter sigma (%g) is not finite or outside [1e-3, 1e3]", who, sigma); return false; }
+	return true;
+}
+// filtered: the entry takes a filter (checked here); in: RaylibAMD_FilterLightmap's atlas (wantIn: the entry takes one)
+static int32_t BakeLightmapInternal(const char* who, SceneHandle sh, const RaylibAMDLightmapParams* params, const float* uv, float* out, uint8_t* outCoverage, bool hostMem, void* stream,
+                                    bool filtered = false, const RaylibAMDLightmapFilterParams* filter = nullptr, bool wantIn = false, const float* in = nullptr)
 {
 	Scene* s = (Scene*)sh;
 	int32_t triFirst = 0, triCount = 0; RaylibAMDRadianceParams prm;
-	if (!out) { Log("%s: null argument", who); return 0; }
+	if (!out || (wantIn && !in)) { Log("%s: null argument", who); return 0; }
 	if (!LightmapArgsValid(who, s, params, triFirst, triCount, prm)) return 0;
+	if (filtered && !LightmapFilterValid(who, filter)) return 0;
 	if (!DeviceAvailable()) return 0;
 	if (!PreparePathScene(who, s, prm, 1)) return 0;
 	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
-	if (!DeviceBakeLightmap(*s, *params, triFirst, triCount, prm, CurrentSeed(), uv, out, outCoverage, hostMem, stream, stats)) return 0;
+	if (!DeviceBakeLightmap(*s, *params, triFirst, triCount, prm, CurrentSeed(), uv, out, outCoverage, hostMem, stream, stats, filter, in)) return 0;
 	if (!stream) { std::lock_guard<std::mutex> lk(g_stateMu); g_lastStats = stats; }
 	return 1;
 }
@@ -1005,6 +1017,36 @@ int32_t RaylibAMD_BakeLightmap(SceneHandle sh, const RaylibAMDLightmapParams* pa
 int32_t RaylibAMD_BakeLightmapDevice(SceneHandle sh, const RaylibAMDLightmapParams* params, const float* uv, float* out, uint8_t* outCoverage, void* stream)
 {
 	return BakeLightmapInternal("RaylibAMD_BakeLightmapDevice", sh, params, uv, out, outCoverage, false, stream);
+}
+int32_t RaylibAMD_BakeLightmapFiltered(SceneHandle sh, const RaylibAMDLightmapParams* params, const RaylibAMDLightmapFilterParams* filter, const float* uv, float* out, uint8_t* outCoverage)
+{
+	return BakeLightmapInternal("RaylibAMD_BakeLightmapFiltered", sh, params, uv, out, outCoverage, true, nullptr, true, filter);
+}
+int32_t RaylibAMD_BakeLightmapFilteredDevice(SceneHandle sh, const RaylibAMDLightmapParams* params, const RaylibAMDLightmapFilterParams* filter, const float* uv, float* out,
+                                             uint8_t* outCoverage, void* stream)
+{
+	return BakeLightmapInternal("RaylibAMD_BakeLightmapFilteredDevice", sh, params, uv, out, outCoverage, false, stream, true, filter);
+}
+int32_t RaylibAMD_FilterLightmap(SceneHandle sh, const RaylibAMDLightmapParams* params, const RaylibAMDLightmapFilterParams* filter, const float* uv, const float* in, float* out,
+                                 uint8_t* outCoverage)
+{
+	return BakeLightmapInternal("RaylibAMD_FilterLightmap", sh, params, uv, out, outCoverage, true, nullptr, true, filter, true, in);
+}
+int32_t RaylibAMD_FilterLightmapDevice(SceneHandle sh, const RaylibAMDLightmapParams* params, const RaylibAMDLightmapFilterParams* filter, const float* uv, const float* in, float* out,
+                                       uint8_t* outCoverage, void* stream)
+{
+	return BakeLightmapInternal("RaylibAMD_FilterLightmapDevice", sh, params, uv, out, outCoverage, false, stream, true, filter, true, in);
+}
+int32_t RaylibAMD_FilterLightmapHost(int32_t width, int32_t height, int32_t kind, const RaylibAMDLightmapFilterParams* filter, const RaylibAMDGatherPoint* points, const uint32_t* texel,
+                                     int64_t count, const float* values, float* outValues)
+{
+	const char* who = "RaylibAMD_FilterLightmapHost";
+	if (count < 0 || (count > 0 && (!points || !texel || !values || !outValues))) { Log("%s: null argument, or a negative count", who); return 0; }
+	if (kind != RAYLIB_AMD_GATHER_IRRADIANCE && kind != RAYLIB_AMD_GATHER_SH9) { Log("%s: unknown gather kind %d", who, kind); return 0; }
+	if (!LightmapFilterValid(who, filter)) return 0;
+	if (width < 1 || width > RL_LM_MAX_SIZE || height < 1 || height > RL_LM_MAX_SIZE) { Log("%s: the atlas %d x %d is outside 1 .. %d", who, width, height, RL_LM_MAX_SIZE); return 0; }
+	if (count > (int64_t)width * (int64_t)height) { Log("%s: %lld points are more than the atlas' texels", who, (long long)count); return 0; }
+	return FilterLightmapHost(width, height, kind, *filter, points, texel, count, values, outValues) ? 1 : 0;
 }
 
 int32_t RaylibAMD_SceneNumTriangles(SceneHandle sh) { Scene* s = (Scene*)sh; return s ? (int32_t)s->triangles.size() : 0; }

@@ -284,8 +284,17 @@ int64_t LightmapPointsHost(const Scene& scene, const RaylibAMDLightmapParams& P,
 int64_t DeviceLightmapPoints(Scene& scene, const RaylibAMDLightmapParams& P, int32_t triFirst, int32_t triCount, const float* uv,
                              RaylibAMDGatherPoint* outPoints, uint32_t* outTexel, int64_t capacity);
 // DeviceBakeLightmap: raster, gather, scatter, dilation.  hostMem: uv / out / outCoverage in host memory (stream is null), else device pointers; stream as DeviceGather's.
+// filter (may be null; checked by the ABI): statement F between the gather and the scatter.  in (with a filter only; memory as out's, may be out): the covered
+// texels take their values from that atlas instead of a gather (RaylibAMD_FilterLightmap).
 bool DeviceBakeLightmap(Scene& scene, const RaylibAMDLightmapParams& P, int32_t triFirst, int32_t triCount, const RaylibAMDRadianceParams& prm, uint64_t seed,
-                        const float* uv, float* out, uint8_t* outCoverage, bool hostMem, void* stream, RaylibAMDStats& stats);
+                        const float* uv, float* out, uint8_t* outCoverage, bool hostMem, void* stream, RaylibAMDStats& stats,
+                        const RaylibAMDLightmapFilterParams* filter = nullptr, const float* in = nullptr);
+// Statement F's constants (F4), computed once on the host for both paths, and the statement on the host (rl_lightmap_filter.hip): the oracle of k_lm_filter.
+// The ABI checked the arguments but the texel array; false: that array is not strictly ascending inside the atlas, or no memory (nothing written).
+struct LmFilterInv { float invC[8], invN, invP[8]; };
+LmFilterInv MakeLmFilterInv(const RaylibAMDLightmapFilterParams& F);
+bool FilterLightmapHost(int32_t width, int32_t height, int32_t kind, const RaylibAMDLightmapFilterParams& F, const RaylibAMDGatherPoint* points, const uint32_t* texel,
+                        int64_t count, const float* values, float* outValues);
 bool DevicePostProcess(Image& img);          // Image2D::PostProcess on the device; false when no device
 bool DeviceDumpRGB(Image& img, float* outRGB);   // a device-resident frame packed to RGB on the device and copied to caller memory through pinned staging; false: not applicable
 bool DeviceReadback(Image& img);            // device copy -> img.rgba (the caller checked hostStale)

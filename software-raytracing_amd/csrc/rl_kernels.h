@@ -13,6 +13,7 @@
 //   rl_gather.hip        k_gather (RaylibAMD_Gather: rl_k_radiance.inl's twin, the generator instances of its loop) and k_gather_resolve: beside k_radiance they would be
 //                        more callers of the walks and the shading it inlines
 //   rl_lightmap.hip      k_lm_*: the lightmap rasteriser, its scans and the atlas stages (RaylibAMD_BakeLightmap); no walk, no shading
+//   rl_lightmap_filter.hip  k_lm_filter, k_lm_take: the atlas filter (RaylibAMD_BakeLightmapFiltered) and its host oracle, which share one per-texel function
 // A twin takes the view table (DViews) as one more trailing argument.  Default template arguments are given here and nowhere else.
 #pragma once
 
@@ -235,6 +236,21 @@ k_lm_dilate(const float* __restrict__ src, const uint8_t* __restrict__ srcCov, f
 	X template __global__ void k_lm_dilate<C>(const float* __restrict__, const uint8_t* __restrict__, float* __restrict__, uint8_t* __restrict__, int32_t, int32_t, int32_t);
 RL_LM_ATLAS_INSTANCES(extern, 4)
 RL_LM_ATLAS_INSTANCES(extern, 27)
+// The atlas filter (RaylibAMD_BakeLightmapFiltered, statement F; rl_lightmap_filter.hip), on the points in compacted form, in front of the scatter.
+// One iteration, one thread per point i < count: its texel is texel[i], a tap's point is found through rank (scanned: a texel has a point when rank[q + 1] !=
+// rank[q]), src -> dst (count x C floats each).  prep: the first iteration, which reads a value that is not finite as 0.
+template <int C> __global__ void __launch_bounds__(RL_BLOCK)
+k_lm_filter(const uint32_t* __restrict__ rank, const uint32_t* __restrict__ texel, const float4* __restrict__ points, const float* __restrict__ src, float* __restrict__ dst,
+            uint32_t count, int32_t width, int32_t height, int32_t step, float invC, float invN, float invP, int32_t prep);
+// RaylibAMD_FilterLightmap: one thread per texel, a texel with a point hands its C floats of `atlas` to values[rank[i]]
+template <int C> __global__ void __launch_bounds__(RL_BLOCK)
+k_lm_take(const uint32_t* __restrict__ rank, const float* __restrict__ atlas, uint32_t numTexels, float* __restrict__ values);
+#define RL_LM_FILTER_INSTANCES(X, C) \
+	X template __global__ void k_lm_filter<C>(const uint32_t* __restrict__, const uint32_t* __restrict__, const float4* __restrict__, const float* __restrict__, float* __restrict__, \
+	                                          uint32_t, int32_t, int32_t, int32_t, float, float, float, int32_t); \
+	X template __global__ void k_lm_take<C>(const uint32_t* __restrict__, const float* __restrict__, uint32_t, float* __restrict__);
+RL_LM_FILTER_INSTANCES(extern, 4)
+RL_LM_FILTER_INSTANCES(extern, 27)
 
 // ---------------------------------------------------------------------------
 // Test hooks (rl_rt_hooks.hip): single functions of the hot path evaluated on arrays

@@ -5,7 +5,7 @@
 //   rl_rt_frame.hip   kernel selection and the one enqueue path of every render (EnqueueFrame), a rank's one-view render, a batch of views
 //   rl_rt_render.hip  whole frames over N ranks (gather, scatter, two frames in flight), DeviceRender, progressive sessions
 //   rl_rt_rays.hip    caller rays: DeviceTraceRays, DeviceTraceRadiance, DeviceGather
-//   rl_rt_lightmap.hip  lightmaps: DeviceLightmapPoints, DeviceBakeLightmap (the raster stages, then DeviceGather's body, then the atlas stages)
+//   rl_rt_lightmap.hip  lightmaps: DeviceLightmapPoints, DeviceBakeLightmap (the raster stages, then DeviceGather's body or the caller's atlas, the filter, the atlas stages)
 //   rl_rt_hooks.hip   test hooks
 //
 // Ranks.  RAYLIB_NUM_GPUS = N (default 1) makes the library drive N devices from this one process: the frame's 8x8
@@ -196,10 +196,11 @@ struct RankCtx {
 	// a lightmap bake's scratch (rl_rt_lightmap.hip), kept and grown, behind the same event: the raster records and the counts of the range's triangles with
 	// the scans' tile sums, a host call's uv, the owner map and the ranks (one word per texel each), the points, their texel indices and values, the two
 	// atlases and coverage maps of the dilation's ping-pong; the pinned word the counts are read back through and the events around the stages
+	// (lmEv[5]: behind the filter).  lmFilt: the values again, the other half of the filter iterations' ping-pong (a filtered bake, RaylibAMD_FilterLightmap)
 	DevBuf<DLmTri> lmRec; DevBuf<unsigned long long> lmCounts, lmSums; DevBuf<float> lmUv;
-	DevBuf<uint32_t> lmOwner, lmRank, lmTexel; DevBuf<float4> lmPoints; DevBuf<float> lmValues, lmAtlas[2]; DevBuf<uint8_t> lmCov[2];
+	DevBuf<uint32_t> lmOwner, lmRank, lmTexel; DevBuf<float4> lmPoints; DevBuf<float> lmValues, lmFilt, lmAtlas[2]; DevBuf<uint8_t> lmCov[2];
 	PinBuf<unsigned long long> lmHost;
-	hipEvent_t lmEv[5] = {};
+	hipEvent_t lmEv[6] = {};
 	hipEvent_t lmInEv = nullptr;   // recorded on a caller's stream when a bake enters: the raster stages, on the library's stream, wait for it before they read the caller's uv
 };
 

@@ -1,8 +1,11 @@
 // Host runtime: lightmaps (RaylibAMD_LightmapPoints, RaylibAMD_BakeLightmap, RaylibAMD_BakeLightmapDevice; include/raylib_amd.h) on rank 0's device.
 // The raster stages (rl_lightmap.hip: setup, the counts' scan, cover, the flags, their scan, the points) run on the library's stream and are waited for -- the
 // host must know the number of points before it can plan the gather --; a bake then enters DeviceGather's body (rl_rt_rays.hip GatherLocked) with the points
-// on the device, and puts the scatter, the dilation's passes and the copies into the caller's memory behind it, on the call's stream.  The scratch is the
-// rank's (rl_rt.h RankCtx lm*), ordered by the radiance calls' event: a call waits for it before its first kernel and records it behind its last.
+// on the device, and puts the scatter, the dilation's passes and the copies into the caller's memory behind it, on the call's stream.  A filtered bake
+// (RaylibAMD_BakeLightmapFiltered) puts statement F's iterations (rl_lightmap_filter.hip) between the gather and the scatter, on the points' values in compacted
+// form; RaylibAMD_FilterLightmap takes those values from the caller's atlas instead of a gather.  The scratch is the rank's (rl_rt.h RankCtx lm*: the raster's
+// records, counts and maps, the points, their texels and values, the filter's second array of values, the two atlases and coverage maps), ordered by the
+// radiance calls' event: a call waits for it before its first kernel and records it behind its last.
 #include "rl_rt.h"
 #include "rl_lightmap.h"
 
@@ -117,10 +120,26 @@ int64_t DeviceLightmapPoints(Scene& sc, const RaylibAMDLightmapParams& P, int32_
 	return (int64_t)r.count;
 }
 
+// statement F on the points' values, K iterations between R.lmValues and R.lmFilt (rl_lightmap_filter.hip); `values`: where the last one left them
 template <int C>
-static bool EnqueueAtlas(RankCtx& R, const RaylibAMDLightmapParams& P, uint32_t nTex, hipStream_t st, int& last)
+static bool EnqueueFilter(RankCtx& R, const RaylibAMDLightmapParams& P, const RaylibAMDLightmapFilterParams& F, uint32_t count, hipStream_t st, const float*& values)
 {
-	hipLaunchKernelGGL(k_lm_scatter<C>, dim3(BlocksFor(nTex)), dim3(RL_BLOCK), 0, st, (const uint32_t*)R.lmRank.ptr, (const float*)R.lmValues.ptr, nTex, R.lmAtlas[0].ptr, R.lmCov[0].ptr);
+	const LmFilterInv inv = MakeLmFilterInv(F);
+	float* buf[2] = { R.lmValues.ptr, R.lmFilt.ptr };
+	int cur = 0;
+	for (int32_t i = 0; i < F.iterations && count; ++i, cur ^= 1) {
+		hipLaunchKernelGGL(k_lm_filter<C>, dim3(BlocksFor(count)), dim3(RL_BLOCK), 0, st, (const uint32_t*)R.lmRank.ptr, (const uint32_t*)R.lmTexel.ptr, (const float4*)R.lmPoints.ptr,
+		                   (const float*)buf[cur], buf[cur ^ 1], count, P.width, P.height, 1 << i, inv.invC[i], inv.invN, inv.invP[i], i == 0 ? 1 : 0);
+		HIP_OK(hipGetLastError());
+	}
+	values = buf[cur];
+	return true;
+}
+
+template <int C>
+static bool EnqueueAtlas(RankCtx& R, const RaylibAMDLightmapParams& P, uint32_t nTex, hipStream_t st, const float* values, int& last)
+{
+	hipLaunchKernelGGL(k_lm_scatter<C>, dim3(BlocksFor(nTex)), dim3(RL_BLOCK), 0, st, (const uint32_t*)R.lmRank.ptr, values, nTex, R.lmAtlas[0].ptr, R.lmCov[0].ptr);
 	HIP_OK(hipGetLastError());
 	last = 0;
 	for (int32_t k = 1; k <= P.dilate; ++k) {
@@ -132,22 +151,40 @@ static bool EnqueueAtlas(RankCtx& R, const RaylibAMDLightmapParams& P, uint32_t 
 	return true;
 }
 
+// RaylibAMD_FilterLightmap's statement 7: the covered texels' values from the caller's atlas.  A host atlas goes through R.lmAtlas[0], which the scatter
+// overwrites only behind this on the same stream; a device atlas is read where it is, before the call's last copy writes `out` (which may be `in`).
+template <int C>
+static bool EnqueueTake(RankCtx& R, uint32_t nTex, const float* in, bool hostMem, hipStream_t st)
+{
+	const float* src = in;
+	if (hostMem) {
+		HIP_OK(hipMemcpyAsync(R.lmAtlas[0].ptr, in, (size_t)nTex * C * sizeof(float), hipMemcpyHostToDevice, st));
+		src = R.lmAtlas[0].ptr;
+	}
+	hipLaunchKernelGGL(k_lm_take<C>, dim3(BlocksFor(nTex)), dim3(RL_BLOCK), 0, st, (const uint32_t*)R.lmRank.ptr, src, nTex, R.lmValues.ptr);
+	HIP_OK(hipGetLastError());
+	return true;
+}
+
 bool DeviceBakeLightmap(Scene& sc, const RaylibAMDLightmapParams& P, int32_t triFirst, int32_t triCount, const RaylibAMDRadianceParams& prm, uint64_t seed,
-                        const float* uv, float* out, uint8_t* outCoverage, bool hostMem, void* stream, RaylibAMDStats& stats)
+                        const float* uv, float* out, uint8_t* outCoverage, bool hostMem, void* stream, RaylibAMDStats& stats,
+                        const RaylibAMDLightmapFilterParams* filter, const float* in)
 {
 	const auto t0 = std::chrono::steady_clock::now();
 	std::lock_guard<std::mutex> lk(Rt().lock);
 	if (!EnsureRuntime()) return false;
 	RankCtx& R = Rank0();
 	HIP_OK(hipSetDevice(R.device));
+	const char* who = in ? (hostMem ? "RaylibAMD_FilterLightmap" : "RaylibAMD_FilterLightmapDevice") : !filter ? (hostMem ? "RaylibAMD_BakeLightmap" : "RaylibAMD_BakeLightmapDevice")
+	                     : (hostMem ? "RaylibAMD_BakeLightmapFiltered" : "RaylibAMD_BakeLightmapFilteredDevice");
 	const bool sphere = P.gather.kind == RAYLIB_AMD_GATHER_SH9;
 	const uint32_t C = sphere ? 27u : 4u, nTex = (uint32_t)P.width * (uint32_t)P.height;
 	if (!hostMem) {
-		if (!OnDevice(out, R.device) || (uv && !OnDevice(uv, R.device)) || (outCoverage && !OnDevice(outCoverage, R.device))) {
-			Log("RaylibAMD_BakeLightmapDevice: a pointer is not device memory of device %d", R.device);
+		if (!OnDevice(out, R.device) || (uv && !OnDevice(uv, R.device)) || (outCoverage && !OnDevice(outCoverage, R.device)) || (in && !OnDevice(in, R.device))) {
+			Log("%s: a pointer is not device memory of device %d", who, R.device);
 			return false;
 		}
-		if (((uintptr_t)out & 3u) != 0 || ((uintptr_t)uv & 3u) != 0) { Log("RaylibAMD_BakeLightmapDevice: uv or the output is not 4-byte aligned"); return false; }
+		if (((uintptr_t)out & 3u) != 0 || ((uintptr_t)uv & 3u) != 0 || ((uintptr_t)in & 3u) != 0) { Log("%s: uv, the input or the output is not 4-byte aligned", who); return false; }
 	}
 	const bool sync = !stream;
 	const size_t atlasBytes = (size_t)nTex * C * sizeof(float);
@@ -156,15 +193,26 @@ bool DeviceBakeLightmap(Scene& sc, const RaylibAMDLightmapParams& P, int32_t tri
 	if (P.dilate > 0 && (!R.lmAtlas[1].Grow(atlasBytes) || !R.lmCov[1].Grow(nTex))) return false;
 	LmRaster r;
 	if (!Raster(sc, R, P, triFirst, triCount, uv, hostMem, 0, true, sync, (hipStream_t)stream, r)) return false;
-	if (!R.lmValues.Grow(std::max<size_t>(1, (size_t)r.count) * C * sizeof(float))) return false;
-	// statement 7: DeviceGather's body on the points, on the call's stream; a synchronous call returns from it with the gather's stats and an idle stream
-	if (!GatherLocked(sc, R, P.gather.kind, prm, seed, R.lmPoints.ptr, (int32_t)r.count, R.lmValues.ptr, false, stream, t0, stats)) return false;
+	const size_t valueBytes = std::max<size_t>(1, (size_t)r.count) * C * sizeof(float);
+	if (!R.lmValues.Grow(valueBytes) || (filter && !R.lmFilt.Grow(valueBytes))) return false;
 	const hipStream_t st = stream ? (hipStream_t)stream : R.stream;
 	bool ok = true;
-	if (sync) HIP_TRY(hipEventRecord(R.lmEv[3], st));
-	int last = 0;
-	ok = ok && (sphere ? EnqueueAtlas<27>(R, P, nTex, st, last) : EnqueueAtlas<4>(R, P, nTex, st, last));
+	if (!in) {
+		// statement 7: DeviceGather's body on the points, on the call's stream; a synchronous call returns from it with the gather's stats and an idle stream
+		if (!GatherLocked(sc, R, P.gather.kind, prm, seed, R.lmPoints.ptr, (int32_t)r.count, R.lmValues.ptr, false, stream, t0, stats)) return false;
+	} else {
+		// ... or the caller's atlas.  (The raster waited for the scratch's event and for its own stream: nothing else holds the scratch now.)
+		memset(&stats, 0, sizeof(stats));
+		OneRankStats(stats, sc);
+		ok = sphere ? EnqueueTake<27>(R, nTex, in, hostMem, st) : EnqueueTake<4>(R, nTex, in, hostMem, st);
+	}
+	if (ok && sync) HIP_TRY(hipEventRecord(R.lmEv[3], st));
+	const float* values = R.lmValues.ptr;
+	if (ok && filter) ok = sphere ? EnqueueFilter<27>(R, P, *filter, (uint32_t)r.count, st, values) : EnqueueFilter<4>(R, P, *filter, (uint32_t)r.count, st, values);
 	if (ok && sync) HIP_TRY(hipEventRecord(R.lmEv[4], st));
+	int last = 0;
+	ok = ok && (sphere ? EnqueueAtlas<27>(R, P, nTex, st, values, last) : EnqueueAtlas<4>(R, P, nTex, st, values, last));
+	if (ok && sync) HIP_TRY(hipEventRecord(R.lmEv[5], st));
 	const hipMemcpyKind kind = hostMem ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
 	if (ok) HIP_TRY(hipMemcpyAsync(out, R.lmAtlas[last].ptr, atlasBytes, kind, st));
 	if (ok && outCoverage) HIP_TRY(hipMemcpyAsync(outCoverage, R.lmCov[last].ptr, nTex, kind, st));
@@ -175,17 +223,21 @@ bool DeviceBakeLightmap(Scene& sc, const RaylibAMDLightmapParams& P, int32_t tri
 	if (!ok || evErr != hipSuccess) return false;
 	if (!sync) return true;
 	HIP_OK(hipStreamSynchronize(st));
-	float ms[4] = { 0, 0, 0, 0 }, whole = 0.0f;
-	for (int k = 0; k < 4; ++k) HIP_OK(hipEventElapsedTime(&ms[k], R.lmEv[k], R.lmEv[k + 1]));
-	HIP_OK(hipEventElapsedTime(&whole, R.lmEv[0], R.lmEv[4]));
+	// setup + scan + cover, points + compaction, gather (or the atlas taken), filter, scatter + dilate
+	float ms[5] = { 0, 0, 0, 0, 0 }, whole = 0.0f;
+	for (int k = 0; k < 5; ++k) HIP_OK(hipEventElapsedTime(&ms[k], R.lmEv[k], R.lmEv[k + 1]));
+	HIP_OK(hipEventElapsedTime(&whole, R.lmEv[0], R.lmEv[5]));
 	stats.pixels = r.count;
 	stats.kernelMs = whole;
 	stats.wallMs = MsSince(t0);
 	const char* e = getenv("RAYLIB_LIGHTMAP_LOG");
-	if (e && atoi(e) != 0)
-		Log("RaylibAMD_BakeLightmap: %d x %d, %d triangles, %llu pairs in %llu launches of one pair per lane, %llu points | setup + scan + cover %.3f ms, points + compaction %.3f ms, "
-		    "gather %.3f ms, scatter + dilate %.3f ms, whole %.3f ms", P.width, P.height, triCount, (unsigned long long)r.pairs,
-		    (unsigned long long)((r.pairs + RL_LM_COVER_PAIRS - 1) / RL_LM_COVER_PAIRS), (unsigned long long)r.count, ms[0], ms[1], ms[2], ms[3], whole);
+	if (e && atoi(e) != 0) {
+		char filt[64] = "";
+		if (filter) snprintf(filt, sizeof(filt), "filter (%d iterations) %.3f ms, ", filter->iterations, ms[3]);
+		Log("%s: %d x %d, %d triangles, %llu pairs in %llu launches of one pair per lane, %llu points | setup + scan + cover %.3f ms, points + compaction %.3f ms, "
+		    "%s %.3f ms, %sscatter + dilate %.3f ms, whole %.3f ms", who, P.width, P.height, triCount, (unsigned long long)r.pairs,
+		    (unsigned long long)((r.pairs + RL_LM_COVER_PAIRS - 1) / RL_LM_COVER_PAIRS), (unsigned long long)r.count, ms[0], ms[1], in ? "atlas taken" : "gather", ms[2], filt, ms[4], whole);
+	}
 	return true;
 }
 

@@ -11,7 +11,10 @@ bool DeviceTraceRays(Scene&, int32_t, const void*, int32_t, float, void*, int32_
 bool DeviceTraceRadiance(Scene&, const RaylibAMDRadianceParams&, uint64_t, const void*, int32_t, float*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceGather(Scene&, int32_t, const RaylibAMDRadianceParams&, uint64_t, const void*, int32_t, float*, bool, void*, RaylibAMDStats&) { return false; }
 int64_t DeviceLightmapPoints(Scene&, const RaylibAMDLightmapParams&, int32_t, int32_t, const float*, RaylibAMDGatherPoint*, uint32_t*, int64_t) { return -1; }
-bool DeviceBakeLightmap(Scene&, const RaylibAMDLightmapParams&, int32_t, int32_t, const RaylibAMDRadianceParams&, uint64_t, const float*, float*, uint8_t*, bool, void*, RaylibAMDStats&) { return false; }
+bool DeviceBakeLightmap(Scene&, const RaylibAMDLightmapParams&, int32_t, int32_t, const RaylibAMDRadianceParams&, uint64_t, const float*, float*, uint8_t*, bool, void*, RaylibAMDStats&,
+                        const RaylibAMDLightmapFilterParams*, const float*) { return false; }
+// rl_lightmap_filter.hip is a HIP unit too: its host restatement (RaylibAMD_FilterLightmapHost) is not part of this build
+bool FilterLightmapHost(int32_t, int32_t, int32_t, const RaylibAMDLightmapFilterParams&, const RaylibAMDGatherPoint*, const uint32_t*, int64_t, const float*, float*) { return false; }
 bool DevicePostProcess(Image&) { return false; }
 void* DeviceImagePixels(Image&) { return nullptr; }
 bool DeviceReadback(Image&) { return false; }
