@@ -82,7 +82,12 @@ typedef struct RaylibAMDStats {
 RAYLIB_API void     RaylibAMD_SetSeed(uint64_t seed);
 RAYLIB_API uint64_t RaylibAMD_GetSeed(void);
 
-/* Stats of the last Raylib_Render / RaylibAMD_RenderDevice on this thread's library state. */
+/* Stats of the last call that reports them: Raylib_Render, RaylibAMD_RenderDevice, RaylibAMD_RenderCellsHost, RaylibAMD_RenderViews, a RaylibAMD_ProgressiveStep
+ * that rendered, and the synchronous RaylibAMD_TraceRays, RaylibAMD_TraceRadiance, RaylibAMD_Gather, RaylibAMD_BakeLightmap, RaylibAMD_BakeLightmapFiltered and
+ * RaylibAMD_FilterLightmap (the host entries, and the ...Device entries with a null stream).  A ...Device entry on a caller's stream reports nothing and leaves
+ * the previous call's numbers in place.  With several ranks a Raylib_Render returns with its frame in flight: this call waits for it, and reports its counters
+ * and times complete -- unless one of the synchronous calls above came after the render: then the numbers are that call's (ranks = 1), whenever the frame
+ * completes.  One state per process. */
 RAYLIB_API void RaylibAMD_GetLastStats(RaylibAMDStats* outStats);
 
 /* 1 when a gfx950-capable HIP device is present and the kernels are loadable. */

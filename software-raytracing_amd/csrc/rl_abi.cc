@@ -109,6 +109,15 @@ bool RenderInternal(const RendererSettings* settings, Scene* scene, Camera* came
 	return ok;
 }
 
+// The numbers of a synchronous query, radiance call, gather or bake become RaylibAMD_GetLastStats': those calls do not wait for a multi-rank frame in flight,
+// whose numbers, completed later, must not replace them (rl_rt_render.hip FinishInflight).  A call on a caller's stream reports nothing and does not come here.
+void ReportOwnStats(const RaylibAMDStats& stats)
+{
+	DeviceOwnStats();
+	std::lock_guard<std::mutex> lk(g_stateMu);
+	g_lastStats = stats;
+}
+
 // A progressive session as the ABI hands it out: the device session and the handles it was begun with.
 struct Progressive {
 	Scene* scene;
@@ -775,7 +784,7 @@ static int32_t TraceRaysInternal(const char* who, SceneHandle sh, int32_t kind, 
 	}
 	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
 	if (!DeviceTraceRays(*s, kind, rays, n, rayTime, out, outPrim, hostMem, stream, stats)) return 0;
-	if (!stream) { std::lock_guard<std::mutex> lk(g_stateMu); g_lastStats = stats; }
+	if (!stream) ReportOwnStats(stats);
 	return 1;
 }
 int32_t RaylibAMD_TraceRays(SceneHandle sh, int32_t kind, const RaylibAMDRay* rays, int32_t n, float rayTime, void* out, int32_t* outPrim)
@@ -856,7 +865,7 @@ static int32_t TraceRadianceInternal(const char* who, SceneHandle sh, const Rayl
 	if (!PreparePathScene(who, s, prm, n)) return 0;
 	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
 	if (!DeviceTraceRadiance(*s, prm, CurrentSeed(), rays, n, out, hostMem, stream, stats)) return 0;
-	if (!stream) { std::lock_guard<std::mutex> lk(g_stateMu); g_lastStats = stats; }
+	if (!stream) ReportOwnStats(stats);
 	return 1;
 }
 int32_t RaylibAMD_TraceRadiance(SceneHandle sh, const RaylibAMDRadianceParams* params, const RaylibAMDPathRay* rays, int32_t n, float* outRGBA)
@@ -899,7 +908,7 @@ static int32_t GatherInternal(const char* who, SceneHandle sh, const RaylibAMDGa
 	if (!PreparePathScene(who, s, prm, n)) return 0;
 	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
 	if (!DeviceGather(*s, params->kind, prm, CurrentSeed(), points, n, out, hostMem, stream, stats)) return 0;
-	if (!stream) { std::lock_guard<std::mutex> lk(g_stateMu); g_lastStats = stats; }
+	if (!stream) ReportOwnStats(stats);
 	return 1;
 }
 int32_t RaylibAMD_Gather(SceneHandle sh, const RaylibAMDGatherParams* params, const RaylibAMDGatherPoint* points, int32_t n, float* out)
@@ -1007,7 +1016,7 @@ static int32_t BakeLightmapInternal(const char* who, SceneHandle sh, const Rayli
 	if (!PreparePathScene(who, s, prm, 1)) return 0;
 	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
 	if (!DeviceBakeLightmap(*s, *params, triFirst, triCount, prm, CurrentSeed(), uv, out, outCoverage, hostMem, stream, stats, filter, in)) return 0;
-	if (!stream) { std::lock_guard<std::mutex> lk(g_stateMu); g_lastStats = stats; }
+	if (!stream) ReportOwnStats(stats);
 	return 1;
 }
 int32_t RaylibAMD_BakeLightmap(SceneHandle sh, const RaylibAMDLightmapParams* params, const float* uv, float* out, uint8_t* outCoverage)

@@ -254,6 +254,7 @@ bool DeviceRenderViews(Scene& scene, const RenderRequest& req, const DCamera* ca
 int32_t DeviceLastTraceLazy();    // 1: ... and of that, the lazy-reflectance instance (k_trace_lazy + k_fold_lit)
 int32_t DeviceLastTracePlain();   // 1: the last path-traced render's megakernel was the leaf-list kernel's plain instance (rl_plan.cc)
 bool DeviceDrain(RaylibAMDStats* outLastStats);   // waits for multi-rank frames in flight; true + stats when that completed the last render call's numbers
+void DeviceOwnStats();                            // the caller reports a synchronous call's own numbers: a frame still in flight, or completed inside that call, is no longer the last call
 bool DeviceClosestHit(Scene& scene, const float* rays, int32_t n, float tMin, void* outHits);
 // RaylibAMD_TraceRays (hostMem: rays / out / outPrim in host memory) and RaylibAMD_TraceRaysDevice (device pointers; stream null: the library's stream,
 // synchronous; else enqueued on that hipStream_t).  stats: filled by a synchronous call.  kind is valid, n >= 0, the scene finalized: the ABI checked.

@@ -217,6 +217,8 @@ struct Runtime {
 	Inflight* inflight[2] = { nullptr, nullptr };        // enqueued, not yet waited for (oldest first by frameNo)
 	RaylibAMDStats deferredStats = {};                   // of the last frame in flight that was completed (FinishInflight)
 	bool deferredUnreported = false;                     // ... and no caller has read them yet (DeviceDrain)
+	uint64_t statsSerial = 0;                            // bumped by every call whose numbers the caller reads next: a frame in flight carries the value it was enqueued
+	                                                     // under, and its numbers are reported late only while no such call has come since (FinishInflight, DeviceOwnStats)
 	RcclApi rccl;
 	std::mutex lock;
 };

@@ -185,4 +185,15 @@ bool DeviceDrain(RaylibAMDStats* out)
 	return true;
 }
 
+// A synchronous call on rank 0's stream that does not drain (the ray queries, radiance, gathers, lightmap bakes) has returned its own numbers, which the caller
+// stores as the last call's: a frame still in flight behind it is no longer the last call (FinishInflight compares the serial), and neither is one that a drain
+// inside the call (SyncSky) completed.
+void DeviceOwnStats()
+{
+	Runtime& R = Rt();
+	std::lock_guard<std::mutex> lk(R.lock);
+	++R.statsSerial;
+	R.deferredUnreported = false;
+}
+
 } // namespace rl

@@ -13,6 +13,7 @@ struct Runtime::Inflight {
 	std::vector<PendingRender> pend;
 	RaylibAMDStats stats;                 // what is known when the frame is enqueued; FinishInflight adds counters and times
 	int slot = 0;
+	uint64_t serial = 0;                  // Runtime::statsSerial when the frame was enqueued
 	bool ok = true, timed = false;
 	std::chrono::steady_clock::time_point t0;
 };
@@ -36,7 +37,9 @@ static bool FinishInflight(int slot)
 		if (hipEventElapsedTime(&sc, R0.ev[slot][5], R0.ev[slot][6]) == hipSuccess) F->stats.scatterMs = (double)sc;
 	} else if (R.gatherStream) (void)hipStreamSynchronize(R.gatherStream);
 	F->stats.wallMs = MsSince(F->t0);
-	R.deferredStats = F->stats; R.deferredUnreported = true;
+	// the last call's numbers, to be reported late -- unless a synchronous query, gather or bake has reported its own since the frame was enqueued
+	// (they do not drain: RaylibAMD_GetLastStats is theirs then, and this frame's numbers go unreported as an overwritten frame's do)
+	if (F->serial == R.statsSerial) { R.deferredStats = F->stats; R.deferredUnreported = true; }
 	delete F;
 	return ok;
 }
@@ -91,6 +94,7 @@ static bool RenderMulti(Scene& sc, const RenderRequest& req, RaylibAMDStats& sta
 	Runtime::Inflight* F = new Runtime::Inflight;
 	F->pend.resize((size_t)N);
 	F->slot = b; F->t0 = std::chrono::steady_clock::now();
+	F->serial = ++R.statsSerial;
 	memset(&F->stats, 0, sizeof(F->stats));
 	std::vector<PendingRender>& pend = F->pend;
 	float4* gather = R.gather[b].ptr;

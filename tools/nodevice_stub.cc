@@ -25,6 +25,7 @@ bool DeviceEvalHook(int, Scene*, const DCamera*, int, int, const float*, int, ui
 void DeviceReleaseScene(DeviceScene*) {}
 int DeviceNumRanks() { return 0; }
 bool DeviceDrain(RaylibAMDStats*) { return false; }
+void DeviceOwnStats() {}
 int32_t DeviceLastTracePlain() { return 0; }
 int32_t DeviceLastTraceLazy() { return 0; }
 bool DeviceVerifyLazyRefl(uint32_t, uint64_t, uint64_t*) { return false; }
