@@ -495,6 +495,10 @@ RAYLIB_API int32_t RaylibAMD_LastTracePlain(void);
 RAYLIB_API int32_t RaylibAMD_SceneLazyRefl(SceneHandle scene);
 /* 1 when the megakernel of the last path-traced render on this process was that lazy-reflectance instance (then RaylibAMD_LastTracePlain is 1 too), else 0. */
 RAYLIB_API int32_t RaylibAMD_LastTraceLazy(void);
+/* 1 when that lazy-reflectance launch kept a lit-sample mask (csrc/rl_lit_mask.h): samples that are all zero bits were neither stored nor summed, the same bits.
+ * A one-view render that is not progressive takes it for launches of at most 256 samples per pixel, without a sun; RAYLIB_LIT_MASK=0 keeps every sample stored,
+ * =1 takes the mask with a sun too.  Else 0. */
+RAYLIB_API int32_t RaylibAMD_LastLitMask(void);
 /* What a one-rank Raylib_Render of `settings` would launch under the current environment (csrc/rl_plan.cc): the kernel instance, its tree and the job
  * layout of its first launch over every cell of the frame, for a device of numCUs CUs on which the kernel fits workgroupsPerCU workgroups.  No device needed.
  * Returns 1, -1 when the scene's BVH is too deep to render (the plan is then not filled in further), 0 for a bad argument or a scene not finalized. */

@@ -1145,6 +1145,7 @@ int32_t RaylibAMD_SceneLazyRefl(SceneHandle sh)
 	return (s && s->finalized && SceneLazyRefl(*s)) ? 1 : 0;
 }
 int32_t RaylibAMD_LastTraceLazy(void) { return DeviceLastTraceLazy(); }
+int32_t RaylibAMD_LastLitMask(void) { return DeviceLastLitMask(); }
 int32_t RaylibAMD_PlanRender(SceneHandle sh, const RendererSettings* settings, int32_t hasSky, int32_t numCUs, int32_t workgroupsPerCU, RaylibAMDRenderPlan* out)
 {
 	Scene* s = (Scene*)sh;

@@ -287,11 +287,16 @@ struct DViews {
  * ScatteringPdf value itself; clear, the half vector's z it is a function of (a mirror's record: clear, and its slot is not read). */
 #define RL_LAZY_REC_EXACT_SP 0x40000000
 #define RL_LAZY_REC_MAT(w) (__float_as_int(w) & ~RL_LAZY_REC_EXACT_SP)
+// The lit-sample mask (rl_lit_mask.h): a bit per sample of the batch, word-major -- bit s & 31 of mask[(s >> 5) * numSlots + slot] for sample s of a slot --, zeroed per
+// batch.  With a mask, a sample whose three words are all zero bits is neither stored nor flagged; every other sample is stored and its bit set (atomicOr), and
+// k_resolve_lit sums a slot's flagged samples alone.  Without one (mask null) every sample is stored and k_resolve sums them all.
+#define RL_LIT_MASK_MAX_WORDS 8u     /* a launch of more than 256 samples per slot keeps the unmasked path */
 struct DLitList {
 	float* entries;              // float4 units
 	uint32_t* ctl;
 	uint32_t numChunks;          // 0: no list, every lit path folds in place
-	uint32_t pad;
+	uint32_t maskWords;          // words per slot of the mask: ceil(sampleCount / 32)
+	uint32_t* mask;              // null: no mask
 };
 
 } // namespace rl

@@ -222,7 +222,16 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 								DSceneView Sq = S; Sq.hasSun = 0;
 								V3 L = MissShader<STACK, PRIMS, FULL, LDS, PLAIN>(Sq, R, qo, qd, qTime, P.rayTMin, stk, c, sm);
 								if (S.hasSun) { c.rays++; c.nodes++; L = L + ld3(S.sunIlluminance); }
+#if RL_LAZY_REFL
+								RL_LIT_ARGS();
+								if (!LL.mask) samples[qOut] = make_sample(L.x, L.y, L.z);
+								else if (AnyBitSet(L)) {   // the lit-sample mask's rule (rl_lit_mask.h): all zero bits, neither stored nor flagged
+									samples[qOut] = make_sample(L.x, L.y, L.z);
+									atomicOr(&LL.mask[LitMaskWord(j.sample, numSlots, j.slot)], LitMaskBit(j.sample));
+								}
+#else
 								samples[qOut] = make_sample(L.x, L.y, L.z);
+#endif
 								survive = false;
 							}
 						}
@@ -433,7 +442,8 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 				RL_ARGS();
 				if (AnyBitSet(L)) lit = true;
 				// an unlit path: every E and the terminal L are +0 and every vertex passed LazyVertexSafe, so every step of the fold is (0 + +-0) + 0 = +0
-				if (!lit) samples[outIndex] = make_sample(0.0f, 0.0f, 0.0f);
+				// (with a lit-sample mask it is neither stored nor flagged: rl_lit_mask.h)
+				if (!lit) { RL_LIT_ARGS(); if (!LL.mask) samples[outIndex] = make_sample(0.0f, 0.0f, 0.0f); }
 				else { finLit = true; finTop = store; finRec0 = rec0; finRec1 = rec1; finL = L; }
 				active = false;
 			} else if (store) {
@@ -496,7 +506,12 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 						const Mat m = MatFrom<PLAIN>(sm + LdsAt<LDS>::MATS + RL_LAZY_REC_MAT(r1.w) * RL_LDS_MSTRIDE(PLAIN));
 						L = FoldLazyVertex(m, r0, r1, L);
 					}
-					samples[outIndex] = make_sample(L.x, L.y, L.z);
+					if (!LL.mask) samples[outIndex] = make_sample(L.x, L.y, L.z);
+					else if (AnyBitSet(L)) {
+						const uint32_t s = outIndex / numSlots;
+						samples[outIndex] = make_sample(L.x, L.y, L.z);
+						atomicOr(&LL.mask[LitMaskWord(s, numSlots, outIndex - s * numSlots)], LitMaskBit(s));
+					}
 				}
 			}
 		}

@@ -60,7 +60,11 @@ __global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 
 #define RL_TRACE_LAZY_INSTANCES(X) X(16, false, true, 2, true)
 #define RL_K_TRACE_LAZY(a, b, c, d, e) template __global__ void k_trace_lazy<a, b, c, d, e>(RL_TRACE_ARGS, const DLitList);
 RL_TRACE_LAZY_INSTANCES(extern RL_K_TRACE_LAZY)
-__global__ void __launch_bounds__(RL_BLOCK) k_fold_lit(const DSceneView S, const DLitList LL, SampleRGB* __restrict__ samples);
+__global__ void __launch_bounds__(RL_BLOCK) k_fold_lit(const DSceneView S, const DLitList LL, SampleRGB* __restrict__ samples, uint32_t numSlots);
+// k_resolve for a batch of the lazy instance with a lit-sample mask (rl_lit_mask.h): the slot's flagged samples alone
+__global__ void __launch_bounds__(RL_BLOCK)
+k_resolve_lit(const DRenderParams P, const DSceneView S, const SkyRot R, const SampleRGB* __restrict__ samples, float4* __restrict__ accum, float4* __restrict__ out,
+              int firstBatch, int lastBatch, const DLitList LL);
 
 // ---------------------------------------------------------------------------
 // The pool megakernel (rl_dev_pool.h, rl_k_trace_pool.inl): k_trace's arguments.

@@ -28,6 +28,7 @@ RenderKnobs ReadRenderKnobs()
 	if (const char* e = getenv("RAYLIB_CULL_CELLS")) k.cullCells = atoi(e);
 	k.lazyRefl = flag("RAYLIB_LAZY_REFL");
 	if (const char* e = getenv("RAYLIB_LIT_LIST")) k.litList = std::max(0ll, atoll(e));
+	k.litMask = flag("RAYLIB_LIT_MASK");
 	if (const char* e = getenv("RAYLIB_QUERY_TREE")) { const int v = atoi(e); k.queryTree = (v == 2 || v == 4 || v == 8) ? v : 0; }
 	if (const char* e = getenv("RAYLIB_GATHER_BATCH")) k.gatherBatch = std::max(0, atoi(e));
 	return k;

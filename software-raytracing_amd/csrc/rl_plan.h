@@ -27,6 +27,7 @@ struct RenderKnobs {
 	int gatherBatch = 0;                          // RAYLIB_GATHER_BATCH: (point, sample) slots per launch of RaylibAMD_Gather (0: not set or not positive)
 	int lazyRefl = -1;                            // RAYLIB_LAZY_REFL
 	long long litList = -1;                       // RAYLIB_LIT_LIST: entries of the lazy instance's lit list (0: every lit path folds in place); -1: not set
+	int litMask = -1;                             // RAYLIB_LIT_MASK: 0 keeps every sample stored and k_resolve; 1 takes the lit-sample mask with a sun too
 };
 RenderKnobs ReadRenderKnobs();
 

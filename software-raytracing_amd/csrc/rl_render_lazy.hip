@@ -6,6 +6,7 @@
 
 // ---- the device library ----
 #include "rl_kernels.h"
+#include "rl_lit_mask.h"
 
 namespace rl {
 
@@ -17,9 +18,10 @@ namespace rl {
 #undef RL_VIEWS_TWIN
 
 // One thread per entry of the lit list (rl_device.h DLitList): the path's vertex records, camera first, folded from the last back to the camera exactly as k_trace
-// folds -- each vertex's reflectance evaluated here, in full waves, instead of at its scattering event -- and the sample stored.
+// folds -- each vertex's reflectance evaluated here, in full waves, instead of at its scattering event -- and the sample stored; with a lit-sample mask
+// (rl_lit_mask.h) by its rule: all zero bits, neither stored nor flagged.  numSlots splits the entry's outIndex into sample and slot.
 __global__ void __launch_bounds__(RL_BLOCK)
-k_fold_lit(const DSceneView S, const DLitList LL, SampleRGB* __restrict__ samples)
+k_fold_lit(const DSceneView S, const DLitList LL, SampleRGB* __restrict__ samples, uint32_t numSlots)
 {
 	RL_MATH_PROLOGUE();
 	const uint32_t lane = threadIdx.x & 63u;
@@ -36,7 +38,45 @@ k_fold_lit(const DSceneView S, const DLitList LL, SampleRGB* __restrict__ sample
 			const float4 r0 = e[2 + 2 * k], r1 = e[3 + 2 * k];
 			L = FoldLazyVertex(LoadMat(S, RL_LAZY_REC_MAT(r1.w)), r0, r1, L);
 		}
-		samples[__float_as_uint(h0.w)] = make_sample(L.x, L.y, L.z);
+		const uint32_t outIndex = __float_as_uint(h0.w);
+		if (!LL.mask) samples[outIndex] = make_sample(L.x, L.y, L.z);
+		else if (AnyBitSet(L)) {
+			const uint32_t s = outIndex / numSlots;
+			samples[outIndex] = make_sample(L.x, L.y, L.z);
+			atomicOr(&LL.mask[LitMaskWord(s, numSlots, outIndex - s * numSlots)], LitMaskBit(s));
+		}
+	}
+}
+
+// k_resolve (rl_k_resolve.inl) for a batch with a lit-sample mask: the same contract, one thread per slot.  A culled cell takes SumSlotBatch's branch as it is;
+// every other slot adds its flagged samples, in sample order (LitMaskSum) -- the samples the mask leaves out are +0 and were never stored.
+__global__ void __launch_bounds__(RL_BLOCK)
+k_resolve_lit(const DRenderParams P, const DSceneView S, const SkyRot R, const SampleRGB* __restrict__ samples, float4* __restrict__ accum, float4* __restrict__ out,
+              int firstBatch, int lastBatch, const DLitList LL)
+{
+	RL_MATH_PROLOGUE();
+	const uint32_t numSlots = P.numLocalCells * 64u;
+	const uint32_t slot = blockIdx.x * RL_BLOCK + threadIdx.x;
+	if (slot >= numSlots) return;
+	const uint32_t p = slot & 63u, cellLocal = slot >> 6;
+	const uint32_t cell = P.cellFirst + cellLocal * P.cellStride;
+	const uint32_t x = (cell % P.cellsX) * 8u + (p & 7u), y = (cell / P.cellsX) * 8u + (p >> 3);
+	const bool valid = x < P.width && y < P.height;
+	float4 a = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+	if (valid) {
+		if (!firstBatch) a = accum[slot];
+		if (P.cellEmpty && P.cellEmpty[cellLocal]) a = SumSlotBatch(P, S, R, samples, numSlots, slot, cellLocal, x, y, a, [](float, float, float) __attribute__((always_inline)) {});
+		else LitMaskSum(LL.mask, LL.maskWords, (const float*)samples, numSlots, slot, a.x, a.y, a.z);
+		if (lastBatch) {
+			const float k = rtm::rcp1_((float)P.spp);
+			a.x *= k; a.y *= k; a.z *= k; a.w = 1.0f;
+		} else {
+			accum[slot] = a;
+		}
+	}
+	if (lastBatch) {
+		if (P.rowMajorOutput) { if (valid) out[(size_t)y * P.width + x] = a; }
+		else out[slot] = valid ? a : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 	}
 }
 

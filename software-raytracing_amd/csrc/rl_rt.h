@@ -168,6 +168,7 @@ struct RankCtx {
 	DevBuf<unsigned long long> counters;
 	DevBuf<unsigned int> jobCounter;
 	DevBuf<float4> litList; DevBuf<uint32_t> litCtl;   // the lazy-reflectance instance's lit list and its chunk counts (rl_device.h DLitList), reset per sample batch
+	DevBuf<uint32_t> litMask;   // ... and its lit-sample mask (rl_lit_mask.h), zeroed per sample batch
 	// cells outside the scene's silhouette (CullCells), per frame slot: the list of the others and a flag per cell, pinned on the host and on the device;
 	// cullKey = what they were computed from (camera, frame, cells, bounds): an unchanged view re-uses them without a copy
 	PinBuf<uint32_t> cellListHost[2]; DevBuf<uint32_t> cellList[2]; size_t cellListCells[2] = { 0, 0 };

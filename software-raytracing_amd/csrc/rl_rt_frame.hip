@@ -52,6 +52,8 @@ static std::atomic<int32_t> g_lastTracePlain{0};   // RaylibAMD_LastTracePlain: 
 int32_t DeviceLastTracePlain() { return g_lastTracePlain.load(std::memory_order_relaxed); }
 static std::atomic<int32_t> g_lastTraceLazy{0};    // RaylibAMD_LastTraceLazy
 int32_t DeviceLastTraceLazy() { return g_lastTraceLazy.load(std::memory_order_relaxed); }
+static std::atomic<int32_t> g_lastLitMask{0};      // RaylibAMD_LastLitMask
+int32_t DeviceLastLitMask() { return g_lastLitMask.load(std::memory_order_relaxed); }
 
 // What differs between the frames the runtime queues -- a rank's share of a one-view render, a pass of a progressive session, a batch of views (EnqueueRender,
 // DeviceRenderViews): they fill this in, EnqueueFrame queues what it says.
@@ -161,10 +163,16 @@ static bool EnqueueFrame(RankCtx& R, int q, const DeviceScene& DS, Frame& F, Pen
 		const uint32_t batch = PlanLaunch(numCells, F.numActive, F.sEnd, F.sBegin, R.numCUs, blocksPerCU, plan, F.knobs).batch;
 		if (!R.samples.Grow((size_t)numSlots * sizeof(SampleRGB) * std::min(batch, F.sEnd - F.sBegin))) return false;
 		if (F.accum && batch < P.spp && !R.accum.Grow((size_t)numSlots * sizeof(float4))) return false;
+		// the lit-sample mask (rl_lit_mask.h): a lazy launch behind which k_resolve runs (not a progressive pass, not a batch of views) whose samples fit the mask's
+		// words.  With a sun most samples are lit and would pay an atomic each: not there, unless RAYLIB_LIT_MASK=1 asks for it.  RAYLIB_LIT_MASK=0: never.
+		const bool masked = lazy && F.resolve == (const void*)k_resolve && F.knobs.litMask != 0 && (F.knobs.litMask > 0 || !F.view.hasSun) &&
+		                    (std::min(batch, F.sEnd - F.sBegin) + 31u) / 32u <= RL_LIT_MASK_MAX_WORDS;
+		g_lastLitMask.store(masked ? 1 : 0, std::memory_order_relaxed);
+		const void* resolveKernel = masked ? (const void*)k_resolve_lit : F.resolve;
 		const int depthSlots = P.maxPathLength > 1 ? P.maxPathLength : 1;
 		void* traceArgs[] = { &P, &F.view, &skyRot, &R.samples.ptr, &R.pathStack.ptr, &R.counters.ptr, &R.jobCounter.ptr, lazy ? (void*)&LL : (void*)F.views };
-		void* foldArgs[] = { &F.view, &LL, &R.samples.ptr };
-		void* resolveArgs[] = { &P, &F.view, &skyRot, &R.samples.ptr, F.resolveArgs[0], F.resolveArgs[1], F.resolveArgs[2], F.resolveArgs[3], F.resolveArgs[4] };
+		void* foldArgs[] = { &F.view, &LL, &R.samples.ptr, (void*)&numSlots };
+		void* resolveArgs[] = { &P, &F.view, &skyRot, &R.samples.ptr, F.resolveArgs[0], F.resolveArgs[1], F.resolveArgs[2], F.resolveArgs[3], masked ? (void*)&LL : F.resolveArgs[4] };
 		for (uint32_t s0 = F.sBegin; s0 < F.sEnd; s0 += batch) {
 			const LaunchPlan L = PlanLaunch(numCells, F.numActive, F.sEnd, s0, R.numCUs, blocksPerCU, plan, F.knobs);
 			const uint32_t cnt = L.sampleCount;
@@ -186,6 +194,13 @@ static bool EnqueueFrame(RankCtx& R, int q, const DeviceScene& DS, Frame& F, Pen
 				if (!R.litCtl.Grow((RL_LIT_CTL + (size_t)chunks) * sizeof(uint32_t))) return false;
 				LL.entries = (float*)R.litList.ptr; LL.ctl = R.litCtl.ptr; LL.numChunks = chunks;
 				HIP_OK(hipMemsetAsync(R.litCtl.ptr, 0, (RL_LIT_CTL + (size_t)chunks) * sizeof(uint32_t), R.stream));
+				if (masked) {   // a bit per sample of this batch, zeroed behind the resolve that read the last batch's
+					const uint32_t words = (cnt + 31u) / 32u;
+					const size_t bytes = (size_t)words * numSlots * sizeof(uint32_t);
+					if (!R.litMask.Grow(bytes)) return false;
+					LL.mask = R.litMask.ptr; LL.maskWords = words;
+					HIP_OK(hipMemsetAsync(R.litMask.ptr, 0, bytes, R.stream));
+				}
 			}
 			pend.jobHeads = L.heads;
 			F.firstBatch = s0 == F.sBegin; F.lastBatch = s0 + cnt >= F.sEnd;
@@ -196,7 +211,7 @@ static bool EnqueueFrame(RankCtx& R, int q, const DeviceScene& DS, Frame& F, Pen
 			if (L.jobs > 0 && lazy && LL.numChunks > 0)   // the lit paths' samples, before anything reads the sample buffer (traceKernelMs covers both kernels)
 				HIP_OK(hipLaunchKernel((const void*)k_fold_lit, dim3(std::min<uint32_t>((LL.numChunks + 3u) / 4u, (uint32_t)R.numCUs * 8u)), dim3(RL_BLOCK), foldArgs, 0, R.stream));
 			HIP_OK(hipEventRecord(R.ev[q][3], R.stream));
-			HIP_OK(hipLaunchKernel(F.resolve, dim3(rblocks), dim3(RL_BLOCK), resolveArgs, 0, R.stream));
+			HIP_OK(hipLaunchKernel(resolveKernel, dim3(rblocks), dim3(RL_BLOCK), resolveArgs, 0, R.stream));
 			++pend.launches;
 			if (!F.lastBatch) {   // the event pair is reused by the next batch; the last batch's pair is read after the one final sync
 				HIP_OK(hipEventSynchronize(R.ev[q][3]));

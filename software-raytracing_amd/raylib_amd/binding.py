@@ -554,6 +554,7 @@ _EXPORTS = {
     "RaylibAMD_LastTracePlain": (C.c_int32, []),
     "RaylibAMD_SceneLazyRefl": (C.c_int32, [C.c_void_p]),
     "RaylibAMD_LastTraceLazy": (C.c_int32, []),
+    "RaylibAMD_LastLitMask": (C.c_int32, []),
     "RaylibAMD_VerifyLazyRefl": (C.c_int32, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "RaylibAMD_VerifyLazyPdf": (C.c_int32, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "RaylibAMD_PlanRender": (C.c_int32, [C.c_void_p, C.POINTER(RendererSettings), C.c_int32, C.c_int32, C.c_int32, C.POINTER(RenderPlan)]),
