@@ -83,8 +83,8 @@ RAYLIB_API void     RaylibAMD_SetSeed(uint64_t seed);
 RAYLIB_API uint64_t RaylibAMD_GetSeed(void);
 
 /* Stats of the last call that reports them: Raylib_Render, RaylibAMD_RenderDevice, RaylibAMD_RenderCellsHost, RaylibAMD_RenderViews, a RaylibAMD_ProgressiveStep
- * that rendered, and the synchronous RaylibAMD_TraceRays, RaylibAMD_TraceRadiance, RaylibAMD_Gather, RaylibAMD_BakeLightmap, RaylibAMD_BakeLightmapFiltered and
- * RaylibAMD_FilterLightmap (the host entries, and the ...Device entries with a null stream).  A ...Device entry on a caller's stream reports nothing and leaves
+ * that rendered, and the synchronous RaylibAMD_TraceRays, RaylibAMD_TraceRadiance, RaylibAMD_Gather, RaylibAMD_GatherAdaptive, RaylibAMD_BakeLightmap,
+ * RaylibAMD_BakeLightmapAdaptive, RaylibAMD_BakeLightmapFiltered and RaylibAMD_FilterLightmap (the host entries, and the ...Device entries with a null stream).  A ...Device entry on a caller's stream reports nothing and leaves
  * the previous call's numbers in place.  With several ranks a Raylib_Render returns with its frame in flight: this call waits for it, and reports its counters
  * and times complete -- unless one of the synchronous calls above came after the render: then the numbers are that call's (ranks = 1), whenever the frame
  * completes.  One state per process. */
@@ -278,6 +278,55 @@ typedef struct RaylibAMDGatherCut {
 } RaylibAMDGatherCut;
 RAYLIB_API int32_t RaylibAMD_PlanGatherCut(const RaylibAMDGatherParams* params, int32_t n, uint64_t launchIndex, RaylibAMDGatherCut* out);
 
+/* ---- adaptive gather: points stop sampling once their estimate has converged --------------------------
+ * RaylibAMD_Gather in passes of samples, with the stopping rule of progressive rendering (RaylibAMD_BeginProgressive) per point.  params.sampleCount is the cap:
+ * no point takes more samples.  The estimator is statements 1 to 4 above, unchanged: the live points of a pass are compacted into a contiguous array and traced
+ * by the gather's own kernel -- a point's random numbers hang on its `stream` field, not on its place in memory.
+ *   A1. Passes.  P = ceil(cap / passSamples).  Pass p = 1 .. P gives every live point the samples sampleFirst + (p - 1) * passSamples .. up to n_p = min(cap,
+ *       p * passSamples) samples in all.  All live points therefore hold the same count.  P > 4096 is refused: the host reads one count back per pass.
+ *   A2. Key and moments.  The key of a sample is the three floats the sample buffer's first plane holds for it: statement 3's v = L * max(0, dot(N, Wi)) for
+ *       IRRADIANCE; L itself -- not a product with Y_j -- for SH9.  lum = dot(key, (0.2126f, 0.7152f, 0.0722f)) with statement 1's left-to-right dot;
+ *       y = lum / (1.0f + lum); S1 += y; S2 += y * y.  Both sums are float, run in sample order and start from +0: the progressive renderer's statement.  A key
+ *       that is not finite is not replaced.
+ *   A3. Decision.  After pass p a live point's error is the progressive rule's standard error of the mean (csrc/rl_progressive.h ProgressivePixelError(S1, S2,
+ *       n_p): sqrt(max(0, (S2 - S1 * S1 / n) / (n - 1)) / n), +inf when a sum or the value is not finite).  The point stops when n_p == cap, or when
+ *       n_p >= minSamples && error < threshold.  Stopping is final.
+ *   A4. Result.  A point that stops with n samples receives, bit for bit, what RaylibAMD_Gather returns for that point with sampleCount = n and everything else
+ *       equal: the sum from +0 in sample order, times 1.0f / (float)n, times the solid angle, alpha 1 for IRRADIANCE.  outSamples[i] = n (outSamples may be null).
+ *   A5. Independence.  Neither out nor outSamples depends on how a pass is cut into launches (RAYLIB_GATHER_BATCH, the 256 MiB of sample buffer: point ranges and
+ *       sample ranges), on the tree walked, or on which other points are in the call. */
+typedef struct RaylibAMDGatherAdaptiveParams {
+	float    threshold;    /* a point stops when its error (A3) is < threshold; 0: never early; finite, >= 0 */
+	uint32_t minSamples;   /* samples a point takes before it may stop early; >= 2 */
+	uint32_t passSamples;  /* samples per live point and pass; >= 1 */
+} RaylibAMDGatherAdaptiveParams;
+/* n points from host memory; n x 4 or n x 27 floats and (outSamples may be null) n counts to host memory; synchronous.  Returns 1 (n == 0 included, with or
+ * without a device), or 0 with nothing written for everything RaylibAMD_Gather refuses, a null `adaptive`, a threshold that is negative or not finite,
+ * minSamples < 2, passSamples == 0 or more than 4096 passes.  RaylibAMD_GetLastStats reports the gather's counters with cameraSamples = the sum of outSamples,
+ * traceLaunches = the trace launches made over all passes, kernelMs the whole call's time -- resolves, compactions and the per-pass read-backs of the live count
+ * included -- and traceKernelMs the trace launches' (calls of more than 4096 launches: both the whole call's). */
+RAYLIB_API int32_t RaylibAMD_GatherAdaptive(SceneHandle scene, const RaylibAMDGatherParams* params, const RaylibAMDGatherAdaptiveParams* adaptive,
+        const RaylibAMDGatherPoint* points, int32_t n, float* out, uint32_t* outSamples);
+/* The same on device pointers and a stream, under the pointer and alignment rules of RaylibAMD_GatherDevice; outSamples (may be null) is 4-byte aligned memory of
+ * rank 0's device (refused otherwise).  With a non-null hipStream_t the work runs on that stream under the radiance calls' event chain, and the stats are left
+ * alone -- but the call is NOT fire-and-forget: the host must know the live count to plan the next pass, so the call waits for that stream once per pass and
+ * returns when the last pass is complete, out and outSamples written.  Work the caller enqueued on the stream before the call is waited for with it.
+ * Scratch beyond the gather's, kept and grown under the same event chain: 5 or 29 floats and a flag per point of the call (the sums, S1, S2), and, when there is
+ * more than one pass, two index lists and two arrays of 32-byte records of the call's size, between which the live set is compacted in order behind each pass. */
+RAYLIB_API int32_t RaylibAMD_GatherAdaptiveDevice(SceneHandle scene, const RaylibAMDGatherParams* params, const RaylibAMDGatherAdaptiveParams* adaptive,
+        const RaylibAMDGatherPoint* points, int32_t n, float* out, uint32_t* outSamples, void* stream);
+/* Host only, no device: statements A1 to A3 on keys of the caller's -- count x cap x 3 floats, point-major, in sample order -- giving the n at which each point
+ * stops.  cap stands for params.sampleCount.  Built without FMA from csrc/rl_progressive.h, as RaylibAMD_ProgressiveDecideHost is: the device's oracle.
+ * Returns 1, or 0 with nothing written for a null argument (keys and outSamples may be null when count == 0), count < 0, cap == 0 and the refusals of
+ * `adaptive` above. */
+RAYLIB_API int32_t RaylibAMD_GatherAdaptiveDecideHost(const RaylibAMDGatherAdaptiveParams* adaptive, uint32_t cap, const float* keys, int64_t count, uint32_t* outSamples);
+/* Test hook: the compaction behind a pass, launched as a pass launches it.  live: numLive strictly ascending indices < numPoints; stopped: one byte per original
+ * point; points: the numPoints original records (the hook hands the kernels the live ones' records, contiguous, as a pass holds them).  outLive / outPoints
+ * receive the entries of live whose point has not stopped, in order, and their records -- *outCount of them, nothing behind.  Returns 1, or 0 with nothing
+ * written for a null argument, numLive > numPoints, a list that is not strictly ascending below numPoints, or no device. */
+RAYLIB_API int32_t RaylibAMD_GatherCompactTest(const uint32_t* live, uint32_t numLive, const uint8_t* stopped, const RaylibAMDGatherPoint* points, uint32_t numPoints,
+        uint32_t* outLive, RaylibAMDGatherPoint* outPoints, uint32_t* outCount);
+
 /* ---- lightmaps baked on the device: UV-space texels into RaylibAMD_Gather ------------------------------
  * The step in front of RaylibAMD_Gather and the two behind it: the triangles of a range are rasterised in lightmap-UV space into one gather point per covered
  * texel of a width x height atlas, the points are gathered, and the values go back into the atlas, whose gutters are filled by dilation.
@@ -331,6 +380,16 @@ RAYLIB_API int32_t RaylibAMD_BakeLightmap(SceneHandle scene, const RaylibAMDLigh
  * Scratch, kept and grown by the library under the radiance calls' event chain: the owner map (4 bytes per texel), the ranks (4 per texel), 40 bytes per
  * triangle of the range, the points and their values, and two atlases with their coverage for the dilation's ping-pong. */
 RAYLIB_API int32_t RaylibAMD_BakeLightmapDevice(SceneHandle scene, const RaylibAMDLightmapParams* params, const float* uv, float* out, uint8_t* outCoverage, void* stream);
+/* The adaptive bake: statements 1 to 9 with statement 7 replaced by RaylibAMD_GatherAdaptive's A1 to A5 on the covered texels (params.gather.sampleCount is the
+ * cap).  outSamples (may be null): a width x height atlas of uint32_t holding the texel's sample count n where the coverage is 1 and 0 elsewhere; it is not
+ * dilated.  Refusals: RaylibAMD_BakeLightmap's and RaylibAMD_GatherAdaptive's.  The stats are the adaptive gather's, with pixels and kernelMs as for a bake.
+ * There is no filtered variant: a raw adaptive bake with dilate 0 followed by RaylibAMD_FilterLightmap is the pipeline. */
+RAYLIB_API int32_t RaylibAMD_BakeLightmapAdaptive(SceneHandle scene, const RaylibAMDLightmapParams* params, const RaylibAMDGatherAdaptiveParams* adaptive, const float* uv,
+        float* out, uint8_t* outCoverage, uint32_t* outSamples);
+/* The same on device pointers, under the rules of RaylibAMD_BakeLightmapDevice (outSamples 4-byte aligned memory of rank 0's device).  With a non-null stream the
+ * call waits for that stream once per pass, as RaylibAMD_GatherAdaptiveDevice does; the scatter, the dilation and the copies are enqueued behind the last pass. */
+RAYLIB_API int32_t RaylibAMD_BakeLightmapAdaptiveDevice(SceneHandle scene, const RaylibAMDLightmapParams* params, const RaylibAMDGatherAdaptiveParams* adaptive,
+        const float* uv, float* out, uint8_t* outCoverage, uint32_t* outSamples, void* stream);
 
 /* ---- an edge-avoiding filter over the atlas' covered texels, between statements 8 and 9 ---------------
  * An a-trous filter (Dammertz et al. 2010) guided by each covered texel's gather point -- its world position and normal -- and by the values themselves: it

@@ -919,6 +919,79 @@ int32_t RaylibAMD_GatherDevice(SceneHandle sh, const RaylibAMDGatherParams* para
 {
 	return GatherInternal("RaylibAMD_GatherDevice", sh, params, points, n, out, false, stream);
 }
+// RaylibAMD_GatherAdaptive / ...Device / ...DecideHost / RaylibAMD_BakeLightmapAdaptive*: the refusals of the adaptive parameters under the cap `cap`
+static bool GatherAdaptiveValid(const char* who, const RaylibAMDGatherAdaptiveParams* a, uint32_t cap)
+{
+	if (!a) { Log("%s: null adaptive parameters", who); return false; }
+	if (!(a->threshold >= 0.0f && a->threshold <= 3.40282347e+38f)) { Log("%s: the threshold %g is negative or not finite", who, a->threshold); return false; }
+	if (a->minSamples < 2) { Log("%s: minSamples %u is below 2", who, a->minSamples); return false; }
+	if (a->passSamples == 0) { Log("%s: passSamples is 0", who); return false; }
+	if (((uint64_t)cap + a->passSamples - 1) / a->passSamples > RL_GATHER_ADAPTIVE_MAX_PASSES) {
+		Log("%s: %u samples in passes of %u are more than %u passes", who, cap, a->passSamples, RL_GATHER_ADAPTIVE_MAX_PASSES);
+		return false;
+	}
+	return true;
+}
+static int32_t GatherAdaptiveInternal(const char* who, SceneHandle sh, const RaylibAMDGatherParams* params, const RaylibAMDGatherAdaptiveParams* adaptive,
+                                      const RaylibAMDGatherPoint* points, int32_t n, float* out, uint32_t* outSamples, bool hostMem, void* stream)
+{
+	Scene* s = (Scene*)sh;
+	if (n < 0 || (n > 0 && (!points || !out))) { Log("%s: null argument", who); return 0; }
+	if (!s || !params) { Log("%s: null argument", who); return 0; }
+	RaylibAMDRadianceParams prm;
+	prm.maxPathLength = params->maxPathLength; prm.rayTMin = params->rayTMin; prm.sampleFirst = params->sampleFirst; prm.sampleCount = params->sampleCount;
+	prm.skipDraws = params->skipDraws; prm.timeMin = params->timeMin; prm.timeMax = params->timeMax;
+	if (!RadianceParamsValid(who, s, &prm) || !GatherKindValid(who, params) || !GatherAdaptiveValid(who, adaptive, params->sampleCount)) return 0;
+	if (!PathTimesValid(who, "point", prm, points, n, hostMem)) return 0;
+	if (!DeviceAvailable()) return n == 0 ? 1 : 0;   // (no points: nothing to gather, with or without a device)
+	if (!PreparePathScene(who, s, prm, n)) return 0;
+	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
+	if (!DeviceGatherAdaptive(*s, params->kind, prm, *adaptive, CurrentSeed(), points, n, out, outSamples, hostMem, stream, stats)) return 0;
+	if (!stream) ReportOwnStats(stats);
+	return 1;
+}
+int32_t RaylibAMD_GatherAdaptive(SceneHandle sh, const RaylibAMDGatherParams* params, const RaylibAMDGatherAdaptiveParams* adaptive, const RaylibAMDGatherPoint* points,
+                                 int32_t n, float* out, uint32_t* outSamples)
+{
+	return GatherAdaptiveInternal("RaylibAMD_GatherAdaptive", sh, params, adaptive, points, n, out, outSamples, true, nullptr);
+}
+int32_t RaylibAMD_GatherAdaptiveDevice(SceneHandle sh, const RaylibAMDGatherParams* params, const RaylibAMDGatherAdaptiveParams* adaptive, const RaylibAMDGatherPoint* points,
+                                       int32_t n, float* out, uint32_t* outSamples, void* stream)
+{
+	return GatherAdaptiveInternal("RaylibAMD_GatherAdaptiveDevice", sh, params, adaptive, points, n, out, outSamples, false, stream);
+}
+// statements A1 to A3 on the caller's keys: the oracle of k_gather_adaptive_resolve's moments and decision (csrc/rl_progressive.h, built without FMA)
+int32_t RaylibAMD_GatherAdaptiveDecideHost(const RaylibAMDGatherAdaptiveParams* adaptive, uint32_t cap, const float* keys, int64_t count, uint32_t* outSamples)
+{
+	const char* who = "RaylibAMD_GatherAdaptiveDecideHost";
+	if (count < 0 || (count > 0 && (!keys || !outSamples))) { Log("%s: null argument, or a negative count", who); return 0; }
+	if (cap == 0) { Log("%s: the cap is 0", who); return 0; }
+	if (!GatherAdaptiveValid(who, adaptive, cap)) return 0;
+	for (int64_t i = 0; i < count; ++i) {
+		const float* key = keys + (size_t)i * cap * 3;
+		float s1 = 0.0f, s2 = 0.0f;
+		uint32_t n = 0;
+		for (;;) {
+			const uint32_t now = (uint32_t)std::min<uint64_t>(cap, (uint64_t)n + adaptive->passSamples);
+			for (; n < now; ++n) {
+				const float lum = key[3 * (size_t)n] * 0.2126f + key[3 * (size_t)n + 1] * 0.7152f + key[3 * (size_t)n + 2] * 0.0722f;
+				const float y = lum / (1.0f + lum);
+				s1 += y; s2 += y * y;
+			}
+			if (n == cap || ProgressiveCellStops(ProgressivePixelError(s1, s2, n), n, adaptive->threshold, adaptive->minSamples)) break;
+		}
+		outSamples[i] = n;
+	}
+	return 1;
+}
+int32_t RaylibAMD_GatherCompactTest(const uint32_t* live, uint32_t numLive, const uint8_t* stopped, const RaylibAMDGatherPoint* points, uint32_t numPoints,
+                                    uint32_t* outLive, RaylibAMDGatherPoint* outPoints, uint32_t* outCount)
+{
+	if (!live || !stopped || !points || !outLive || !outPoints || !outCount) return 0;
+	if (numLive > numPoints) return 0;
+	for (uint32_t i = 0; i < numLive; ++i) if (live[i] >= numPoints || (i > 0 && live[i] <= live[i - 1])) return 0;   // (the kernels index stopped by the entries)
+	return DeviceGatherCompactTest(live, numLive, stopped, points, numPoints, outLive, outPoints, outCount) ? 1 : 0;
+}
 int32_t RaylibAMD_PlanGatherCut(const RaylibAMDGatherParams* params, int32_t n, uint64_t launchIndex, RaylibAMDGatherCut* out)
 {
 	const char* who = "RaylibAMD_PlanGatherCut";
@@ -1005,17 +1078,19 @@ static bool LightmapFilterValid(const char* who, const RaylibAMDLightmapFilterPa
 }
 // filtered: the entry takes a filter (checked here); in: RaylibAMD_FilterLightmap's atlas (wantIn: the entry takes one)
 static int32_t BakeLightmapInternal(const char* who, SceneHandle sh, const RaylibAMDLightmapParams* params, const float* uv, float* out, uint8_t* outCoverage, bool hostMem, void* stream,
-                                    bool filtered = false, const RaylibAMDLightmapFilterParams* filter = nullptr, bool wantIn = false, const float* in = nullptr)
+                                    bool filtered = false, const RaylibAMDLightmapFilterParams* filter = nullptr, bool wantIn = false, const float* in = nullptr,
+                                    bool wantAdaptive = false, const RaylibAMDGatherAdaptiveParams* adaptive = nullptr, uint32_t* outSamples = nullptr)
 {
 	Scene* s = (Scene*)sh;
 	int32_t triFirst = 0, triCount = 0; RaylibAMDRadianceParams prm;
 	if (!out || (wantIn && !in)) { Log("%s: null argument", who); return 0; }
 	if (!LightmapArgsValid(who, s, params, triFirst, triCount, prm)) return 0;
 	if (filtered && !LightmapFilterValid(who, filter)) return 0;
+	if (wantAdaptive && !GatherAdaptiveValid(who, adaptive, prm.sampleCount)) return 0;
 	if (!DeviceAvailable()) return 0;
 	if (!PreparePathScene(who, s, prm, 1)) return 0;
 	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
-	if (!DeviceBakeLightmap(*s, *params, triFirst, triCount, prm, CurrentSeed(), uv, out, outCoverage, hostMem, stream, stats, filter, in)) return 0;
+	if (!DeviceBakeLightmap(*s, *params, triFirst, triCount, prm, CurrentSeed(), uv, out, outCoverage, hostMem, stream, stats, filter, in, adaptive, outSamples)) return 0;
 	if (!stream) ReportOwnStats(stats);
 	return 1;
 }
@@ -1026,6 +1101,16 @@ int32_t RaylibAMD_BakeLightmap(SceneHandle sh, const RaylibAMDLightmapParams* pa
 int32_t RaylibAMD_BakeLightmapDevice(SceneHandle sh, const RaylibAMDLightmapParams* params, const float* uv, float* out, uint8_t* outCoverage, void* stream)
 {
 	return BakeLightmapInternal("RaylibAMD_BakeLightmapDevice", sh, params, uv, out, outCoverage, false, stream);
+}
+int32_t RaylibAMD_BakeLightmapAdaptive(SceneHandle sh, const RaylibAMDLightmapParams* params, const RaylibAMDGatherAdaptiveParams* adaptive, const float* uv, float* out,
+                                       uint8_t* outCoverage, uint32_t* outSamples)
+{
+	return BakeLightmapInternal("RaylibAMD_BakeLightmapAdaptive", sh, params, uv, out, outCoverage, true, nullptr, false, nullptr, false, nullptr, true, adaptive, outSamples);
+}
+int32_t RaylibAMD_BakeLightmapAdaptiveDevice(SceneHandle sh, const RaylibAMDLightmapParams* params, const RaylibAMDGatherAdaptiveParams* adaptive, const float* uv, float* out,
+                                             uint8_t* outCoverage, uint32_t* outSamples, void* stream)
+{
+	return BakeLightmapInternal("RaylibAMD_BakeLightmapAdaptiveDevice", sh, params, uv, out, outCoverage, false, stream, false, nullptr, false, nullptr, true, adaptive, outSamples);
 }
 int32_t RaylibAMD_BakeLightmapFiltered(SceneHandle sh, const RaylibAMDLightmapParams* params, const RaylibAMDLightmapFilterParams* filter, const float* uv, float* out, uint8_t* outCoverage)
 {

@@ -277,6 +277,15 @@ constexpr uint64_t RL_GATHER_MAX_SLOTS = 1ull << 28;
 constexpr uint64_t RL_GATHER_TIMED = 4096;
 bool DeviceGather(Scene& scene, int32_t kind, const RaylibAMDRadianceParams& prm, uint64_t seed, const void* points, int32_t n, float* out, bool hostMem, void* stream,
                   RaylibAMDStats& stats);
+// RaylibAMD_GatherAdaptive (hostMem) and RaylibAMD_GatherAdaptiveDevice: DeviceGather in passes with per-point stopping (statements A1 to A5); prm.sampleCount is the
+// cap, A is valid and gives at most RL_GATHER_ADAPTIVE_MAX_PASSES passes.  outSamples may be null; memory as out's.  With a stream the call waits for it once per pass.
+constexpr uint32_t RL_GATHER_ADAPTIVE_MAX_PASSES = 4096;
+bool DeviceGatherAdaptive(Scene& scene, int32_t kind, const RaylibAMDRadianceParams& prm, const RaylibAMDGatherAdaptiveParams& A, uint64_t seed, const void* points, int32_t n,
+                          float* out, uint32_t* outSamples, bool hostMem, void* stream, RaylibAMDStats& stats);
+// RaylibAMD_GatherCompactTest: the compaction behind a pass on uploaded copies, launched as a pass launches it; the ABI checked the arguments (live strictly
+// ascending below numPoints).  false without a device or memory; outputs are written only on success.
+bool DeviceGatherCompactTest(const uint32_t* live, uint32_t numLive, const uint8_t* stopped, const RaylibAMDGatherPoint* points, uint32_t numPoints,
+                             uint32_t* outLive, RaylibAMDGatherPoint* outPoints, uint32_t* outCount);
 // Lightmaps (include/raylib_amd.h RaylibAMD_BakeLightmap).  The ABI checked the arguments: the atlas' size, the dilation, the time, triFirst / triCount a non-empty
 // range of the scene's triangles, capacity >= 0, prm the gather's parameters as a radiance call's with timeMin = timeMax = the time.
 // LightmapPointsHost (rl_lightmap_host.cc): the oracle of the raster stages; -1 without memory.
@@ -288,9 +297,12 @@ int64_t DeviceLightmapPoints(Scene& scene, const RaylibAMDLightmapParams& P, int
 // DeviceBakeLightmap: raster, gather, scatter, dilation.  hostMem: uv / out / outCoverage in host memory (stream is null), else device pointers; stream as DeviceGather's.
 // filter (may be null; checked by the ABI): statement F between the gather and the scatter.  in (with a filter only; memory as out's, may be out): the covered
 // texels take their values from that atlas instead of a gather (RaylibAMD_FilterLightmap).
+// adaptive (may be null; checked by the ABI; without filter and in): statement 7 is DeviceGatherAdaptive's passes, and outSamples (may be null; memory as out's)
+// receives the atlas of the texels' sample counts.
 bool DeviceBakeLightmap(Scene& scene, const RaylibAMDLightmapParams& P, int32_t triFirst, int32_t triCount, const RaylibAMDRadianceParams& prm, uint64_t seed,
                         const float* uv, float* out, uint8_t* outCoverage, bool hostMem, void* stream, RaylibAMDStats& stats,
-                        const RaylibAMDLightmapFilterParams* filter = nullptr, const float* in = nullptr);
+                        const RaylibAMDLightmapFilterParams* filter = nullptr, const float* in = nullptr,
+                        const RaylibAMDGatherAdaptiveParams* adaptive = nullptr, uint32_t* outSamples = nullptr);
 // Statement F's constants (F4), computed once on the host for both paths, and the statement on the host (rl_lightmap_filter.hip): the oracle of k_lm_filter.
 // The ABI checked the arguments but the texel array; false: that array is not strictly ascending inside the atlas, or no memory (nothing written).
 struct LmFilterInv { float invC[8], invN, invP[8]; };

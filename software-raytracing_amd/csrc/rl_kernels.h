@@ -12,6 +12,8 @@
 //   rl_radiance.hip      k_radiance (RaylibAMD_TraceRadiance): the same reason, towards the render and the query kernels alike
 //   rl_gather.hip        k_gather (RaylibAMD_Gather: rl_k_radiance.inl's twin, the generator instances of its loop) and k_gather_resolve: beside k_radiance they would be
 //                        more callers of the walks and the shading it inlines
+//   rl_gather_adaptive.hip  k_gather_adaptive_resolve, k_gather_compact_*, k_gather_scatter_counts (RaylibAMD_GatherAdaptive): behind the unchanged k_gather; apart
+//                        from rl_gather.hip so that its kernels stay the code they are
 //   rl_lightmap.hip      k_lm_*: the lightmap rasteriser, its scans and the atlas stages (RaylibAMD_BakeLightmap); no walk, no shading
 //   rl_lightmap_filter.hip  k_lm_filter, k_lm_take: the atlas filter (RaylibAMD_BakeLightmapFiltered) and its host oracle, which share one per-texel function
 // A twin takes the view table (DViews) as one more trailing argument.  Default template arguments are given here and nowhere else.
@@ -196,6 +198,41 @@ RL_GATHER_INSTANCES(extern RL_K_GATHER)
 template <int GEN> __global__ void __launch_bounds__(RL_BLOCK) k_gather_resolve(RL_GATHER_RESOLVE_ARGS);
 extern template __global__ void k_gather_resolve<RL_GEN_HEMISPHERE>(RL_GATHER_RESOLVE_ARGS);
 extern template __global__ void k_gather_resolve<RL_GEN_SPHERE>(RL_GATHER_RESOLVE_ARGS);
+
+// ---------------------------------------------------------------------------
+// Adaptive gather (RaylibAMD_GatherAdaptive, statements A1 to A5; rl_gather_adaptive.hip)
+// What a call keeps on the device, indexed by the point's index in the call (its "original" index): the running sums in sample order (3 or 27 planes of
+// numPoints floats), the moments of y, and whether the point has stopped -- all cleared when the call begins -- with the rule's parameters.
+struct GatherAdaptiveState {
+	float* sum;
+	float* s1;
+	float* s2;
+	uint8_t* stopped;
+	uint32_t numPoints, cap;
+	float threshold;
+	uint32_t minSamples;
+};
+// k_gather_resolve for a launch of a pass: slot p of the launch is the point live[pointFirst + p] (live null: pointFirst + p).  decide: the pass's last sample
+// range -- the points then hold samplesNow samples; one that stops by A3 writes out / outSamples (may be null) at its original index and sets its flag.
+#define RL_GATHER_ADAPTIVE_RESOLVE_ARGS const float4* __restrict__, uint32_t, uint32_t, const uint32_t* __restrict__, uint32_t, const GatherAdaptiveState, int, uint32_t, float* __restrict__, uint32_t* __restrict__
+template <int GEN> __global__ void __launch_bounds__(RL_BLOCK) k_gather_adaptive_resolve(RL_GATHER_ADAPTIVE_RESOLVE_ARGS);
+extern template __global__ void k_gather_adaptive_resolve<RL_GEN_HEMISPHERE>(RL_GATHER_ADAPTIVE_RESOLVE_ARGS);
+extern template __global__ void k_gather_adaptive_resolve<RL_GEN_SPHERE>(RL_GATHER_ADAPTIVE_RESOLVE_ARGS);
+// The ordered compaction of the live set behind a pass, three launches: count (a workgroup per tile of the list: blockCounts[tile] = the entries it keeps), scan
+// (one workgroup: the counts scanned in place, the total into blockCounts[numTiles] and *count), move (a workgroup per tile: the kept entries of live -- null: the
+// identity -- into outLive, ascending as they were, and each one's record from slot i of points into outPoints).  blockCounts: numTiles + 1 words.
+#define RL_GATHER_COMPACT_PER 8
+#define RL_GATHER_COMPACT_TILE (RL_BLOCK * RL_GATHER_COMPACT_PER)
+#define RL_GATHER_COMPACT_SCAN_BLOCK 1024
+__global__ void __launch_bounds__(RL_BLOCK)
+k_gather_compact_count(const uint32_t* __restrict__ live, const uint8_t* __restrict__ stopped, uint32_t numLive, uint32_t* __restrict__ blockCounts);
+__global__ void __launch_bounds__(RL_GATHER_COMPACT_SCAN_BLOCK) k_gather_compact_scan(uint32_t* __restrict__ blockCounts, uint32_t numTiles, uint32_t* __restrict__ count);
+__global__ void __launch_bounds__(RL_BLOCK)
+k_gather_compact_move(const uint32_t* __restrict__ live, const uint8_t* __restrict__ stopped, uint32_t numLive, const uint32_t* __restrict__ blockCounts,
+                      const float4* __restrict__ points, uint32_t* __restrict__ outLive, float4* __restrict__ outPoints);
+// a bake's per-point sample counts into the atlas through the scanned ranks (k_lm_scatter's rule): 0 where no point is
+__global__ void __launch_bounds__(RL_BLOCK)
+k_gather_scatter_counts(const uint32_t* __restrict__ rank, const uint32_t* __restrict__ counts, uint32_t numTexels, uint32_t* __restrict__ atlas);
 
 // ---------------------------------------------------------------------------
 // Lightmaps (RaylibAMD_BakeLightmap; rl_lightmap.hip, arithmetic of rl_lightmap.h).  tris: the range's records of 26 floats (rl_host.h HostTriangle); uv: six

@@ -4,7 +4,7 @@
 //   rl_rt_scene.hip   a flattened scene (rl_scene.cc FlattenScene) to every device, its sky and wide trees; images: read-back, RGB dump, post-processing
 //   rl_rt_frame.hip   kernel selection and the one enqueue path of every render (EnqueueFrame), a rank's one-view render, a batch of views
 //   rl_rt_render.hip  whole frames over N ranks (gather, scatter, two frames in flight), DeviceRender, progressive sessions
-//   rl_rt_rays.hip    caller rays: DeviceTraceRays, DeviceTraceRadiance, DeviceGather
+//   rl_rt_rays.hip    caller rays: DeviceTraceRays, DeviceTraceRadiance, DeviceGather, DeviceGatherAdaptive
 //   rl_rt_lightmap.hip  lightmaps: DeviceLightmapPoints, DeviceBakeLightmap (the raster stages, then DeviceGather's body or the caller's atlas, the filter, the atlas stages)
 //   rl_rt_hooks.hip   test hooks
 //
@@ -194,6 +194,14 @@ struct RankCtx {
 	DevBuf<float4> gSamples;
 	DevBuf<float> gAcc;
 	std::vector<hipEvent_t> gEv;
+	// an adaptive gather's state between its passes (GatherAdaptiveLocked), behind the same event: the sums and the two moments per point of the call, the stop
+	// flags, a host call's sample counts, the two live lists and the two arrays of live points' records of the compaction's ping-pong, the tiles' counts with
+	// the live count behind them, and the pinned word that count is read back through
+	DevBuf<float> gaState;
+	DevBuf<uint8_t> gaStopped;
+	DevBuf<uint32_t> gaCounts, gaLive[2], gaTiles;
+	DevBuf<float4> gaPoints[2];
+	PinBuf<uint32_t> gaHost;
 	// a lightmap bake's scratch (rl_rt_lightmap.hip), kept and grown, behind the same event: the raster records and the counts of the range's triangles with
 	// the scans' tile sums, a host call's uv, the owner map and the ranks (one word per texel each), the points, their texel indices and values, the two
 	// atlases and coverage maps of the dilation's ping-pong; the pinned word the counts are read back through and the events around the stages
@@ -202,6 +210,7 @@ struct RankCtx {
 	DevBuf<uint32_t> lmOwner, lmRank, lmTexel; DevBuf<float4> lmPoints; DevBuf<float> lmValues, lmFilt, lmAtlas[2]; DevBuf<uint8_t> lmCov[2];
 	PinBuf<unsigned long long> lmHost;
 	hipEvent_t lmEv[6] = {};
+	DevBuf<uint32_t> lmSamples, lmSampleAtlas;   // an adaptive bake's sample counts: per point, and scattered into the atlas
 	hipEvent_t lmInEv = nullptr;   // recorded on a caller's stream when a bake enters: the raster stages, on the library's stream, wait for it before they read the caller's uv
 };
 
@@ -254,6 +263,13 @@ bool FinishRender(RankCtx& R, PendingRender& pend, RaylibAMDStats& stats);
 bool OnDevice(const void* p, int device);              // rl_rt_rays.hip: p is memory of that device
 bool GatherLocked(Scene& sc, RankCtx& R, int32_t kind, const RaylibAMDRadianceParams& prm, uint64_t seed, const void* points, int32_t n, float* out, bool hostMem, void* stream,
                   std::chrono::steady_clock::time_point t0, RaylibAMDStats& stats);   // DeviceGather behind its entry; R's device is current
+// DeviceGatherAdaptive behind its entry, as GatherLocked: statements A1 to A5 in passes.  outSamples (may be null) is host memory with hostMem, else device memory.
+bool GatherAdaptiveLocked(Scene& sc, RankCtx& R, int32_t kind, const RaylibAMDRadianceParams& prm, const RaylibAMDGatherAdaptiveParams& A, uint64_t seed, const void* points,
+                          int32_t n, float* out, uint32_t* outSamples, bool hostMem, void* stream, std::chrono::steady_clock::time_point t0, RaylibAMDStats& stats);
+// the compaction behind a pass (rl_gather_adaptive.hip), enqueued on st: the entries of live (null: the identity) whose points have not stopped into outLive, their
+// records from slot i of points into outPoints, the count into tiles[numTiles] (tiles: ceil(numLive / RL_GATHER_COMPACT_TILE) + 1 words) and from there into *countHost (pinned)
+bool EnqueueGatherCompact(const uint32_t* live, uint32_t numLive, const uint8_t* stopped, const float4* points, uint32_t* outLive, float4* outPoints, uint32_t* tiles,
+                          uint32_t* countHost, hipStream_t st);
 bool DrainLocked();                                    // rl_rt_render.hip: waits for the multi-rank frames in flight (RenderMulti)
 
 // what every call reports beside its counters: the scene's size, (one rank's calls) one rank on one device, and the call's time on the host's clock

@@ -114,4 +114,31 @@ bool DeviceProgressiveCompactTest(const uint32_t* live, uint32_t numLive, const 
 	return ok;
 }
 
+// The live set of an adaptive gather after a pass, from arrays of the caller's.  The launches are GatherAdaptiveLocked's (EnqueueGatherCompact on rank 0's stream): the
+// live points' records go up contiguous, record i beside live[i], as a pass holds them.  The output buffers on the device have numLive entries -- the kernels write
+// count <= numLive of them.
+bool DeviceGatherCompactTest(const uint32_t* live, uint32_t numLive, const uint8_t* stopped, const RaylibAMDGatherPoint* points, uint32_t numPoints,
+                             uint32_t* outLive, RaylibAMDGatherPoint* outPoints, uint32_t* outCount)
+{
+	std::lock_guard<std::mutex> lk(Rt().lock);
+	if (!EnsureRuntime()) return false;
+	HIP_OK(hipSetDevice(Rank0().device));
+	if (numLive == 0) { *outCount = 0; return true; }
+	std::vector<RaylibAMDGatherPoint> rec(numLive);
+	for (uint32_t i = 0; i < numLive; ++i) rec[i] = points[live[i]];
+	DevBuf<uint32_t> dLive, dOutLive, dTiles; DevBuf<uint8_t> dStopped; DevBuf<float4> dPoints, dOutPoints; PinBuf<uint32_t> count;
+	const uint32_t numTiles = (uint32_t)(((uint64_t)numLive + RL_GATHER_COMPACT_TILE - 1) / RL_GATHER_COMPACT_TILE);
+	if (!dLive.Upload(live, numLive) || !dStopped.Upload(stopped, numPoints) || !dPoints.Upload((const float4*)rec.data(), (size_t)numLive * 2)) return false;
+	if (!dOutLive.Grow((size_t)numLive * sizeof(uint32_t)) || !dOutPoints.Grow((size_t)numLive * 2 * sizeof(float4)) || !dTiles.Grow(((size_t)numTiles + 1) * sizeof(uint32_t))
+	    || !count.Grow(sizeof(uint32_t))) return false;
+	const hipStream_t st = Rank0().stream;
+	bool ok = EnqueueGatherCompact(dLive.ptr, numLive, dStopped.ptr, dPoints.ptr, dOutLive.ptr, dOutPoints.ptr, dTiles.ptr, count.ptr, st);
+	ok = (hipStreamSynchronize(st) == hipSuccess) && ok;
+	const uint32_t c = ok ? count.ptr[0] : 0u;
+	ok = ok && c <= numLive;   // (nothing is copied past the caller's arrays, whatever the kernels say)
+	ok = ok && (c == 0 || (Download(outLive, dOutLive.ptr, c) && Download((float4*)outPoints, (const float4*)dOutPoints.ptr, (size_t)c * 2)));
+	if (ok) *outCount = c;
+	return ok;
+}
+
 } // namespace rl

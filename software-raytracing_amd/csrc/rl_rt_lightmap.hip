@@ -3,7 +3,8 @@
 // host must know the number of points before it can plan the gather --; a bake then enters DeviceGather's body (rl_rt_rays.hip GatherLocked) with the points
 // on the device, and puts the scatter, the dilation's passes and the copies into the caller's memory behind it, on the call's stream.  A filtered bake
 // (RaylibAMD_BakeLightmapFiltered) puts statement F's iterations (rl_lightmap_filter.hip) between the gather and the scatter, on the points' values in compacted
-// form; RaylibAMD_FilterLightmap takes those values from the caller's atlas instead of a gather.  The scratch is the rank's (rl_rt.h RankCtx lm*: the raster's
+// form; RaylibAMD_FilterLightmap takes those values from the caller's atlas instead of a gather; RaylibAMD_BakeLightmapAdaptive gathers them in passes with
+// per-texel stopping (GatherAdaptiveLocked) and scatters the texels' sample counts into an atlas of their own.  The scratch is the rank's (rl_rt.h RankCtx lm*: the raster's
 // records, counts and maps, the points, their texels and values, the filter's second array of values, the two atlases and coverage maps), ordered by the
 // radiance calls' event: a call waits for it before its first kernel and records it behind its last.
 #include "rl_rt.h"
@@ -168,36 +169,51 @@ static bool EnqueueTake(RankCtx& R, uint32_t nTex, const float* in, bool hostMem
 
 bool DeviceBakeLightmap(Scene& sc, const RaylibAMDLightmapParams& P, int32_t triFirst, int32_t triCount, const RaylibAMDRadianceParams& prm, uint64_t seed,
                         const float* uv, float* out, uint8_t* outCoverage, bool hostMem, void* stream, RaylibAMDStats& stats,
-                        const RaylibAMDLightmapFilterParams* filter, const float* in)
+                        const RaylibAMDLightmapFilterParams* filter, const float* in, const RaylibAMDGatherAdaptiveParams* adaptive, uint32_t* outSamples)
 {
 	const auto t0 = std::chrono::steady_clock::now();
 	std::lock_guard<std::mutex> lk(Rt().lock);
 	if (!EnsureRuntime()) return false;
 	RankCtx& R = Rank0();
 	HIP_OK(hipSetDevice(R.device));
-	const char* who = in ? (hostMem ? "RaylibAMD_FilterLightmap" : "RaylibAMD_FilterLightmapDevice") : !filter ? (hostMem ? "RaylibAMD_BakeLightmap" : "RaylibAMD_BakeLightmapDevice")
+	const char* who = adaptive ? (hostMem ? "RaylibAMD_BakeLightmapAdaptive" : "RaylibAMD_BakeLightmapAdaptiveDevice")
+	                : in ? (hostMem ? "RaylibAMD_FilterLightmap" : "RaylibAMD_FilterLightmapDevice") : !filter ? (hostMem ? "RaylibAMD_BakeLightmap" : "RaylibAMD_BakeLightmapDevice")
 	                     : (hostMem ? "RaylibAMD_BakeLightmapFiltered" : "RaylibAMD_BakeLightmapFilteredDevice");
 	const bool sphere = P.gather.kind == RAYLIB_AMD_GATHER_SH9;
 	const uint32_t C = sphere ? 27u : 4u, nTex = (uint32_t)P.width * (uint32_t)P.height;
 	if (!hostMem) {
-		if (!OnDevice(out, R.device) || (uv && !OnDevice(uv, R.device)) || (outCoverage && !OnDevice(outCoverage, R.device)) || (in && !OnDevice(in, R.device))) {
+		if (!OnDevice(out, R.device) || (uv && !OnDevice(uv, R.device)) || (outCoverage && !OnDevice(outCoverage, R.device)) || (in && !OnDevice(in, R.device))
+		    || (outSamples && !OnDevice(outSamples, R.device))) {
 			Log("%s: a pointer is not device memory of device %d", who, R.device);
 			return false;
 		}
-		if (((uintptr_t)out & 3u) != 0 || ((uintptr_t)uv & 3u) != 0 || ((uintptr_t)in & 3u) != 0) { Log("%s: uv, the input or the output is not 4-byte aligned", who); return false; }
+		if (((uintptr_t)out & 3u) != 0 || ((uintptr_t)uv & 3u) != 0 || ((uintptr_t)in & 3u) != 0 || ((uintptr_t)outSamples & 3u) != 0) {
+			Log("%s: uv, the input or an output is not 4-byte aligned", who);
+			return false;
+		}
 	}
 	const bool sync = !stream;
 	const size_t atlasBytes = (size_t)nTex * C * sizeof(float);
 	// everything the call allocates, before anything is enqueued (growing frees, and hipFree waits for the device)
 	if (!R.lmAtlas[0].Grow(atlasBytes) || !R.lmCov[0].Grow(nTex)) return false;
 	if (P.dilate > 0 && (!R.lmAtlas[1].Grow(atlasBytes) || !R.lmCov[1].Grow(nTex))) return false;
+	if (adaptive && outSamples && !R.lmSampleAtlas.Grow((size_t)nTex * sizeof(uint32_t))) return false;
 	LmRaster r;
 	if (!Raster(sc, R, P, triFirst, triCount, uv, hostMem, 0, true, sync, (hipStream_t)stream, r)) return false;
 	const size_t valueBytes = std::max<size_t>(1, (size_t)r.count) * C * sizeof(float);
 	if (!R.lmValues.Grow(valueBytes) || (filter && !R.lmFilt.Grow(valueBytes))) return false;
+	if (adaptive && outSamples && !R.lmSamples.Grow(std::max<size_t>(1, (size_t)r.count) * sizeof(uint32_t))) return false;
 	const hipStream_t st = stream ? (hipStream_t)stream : R.stream;
 	bool ok = true;
-	if (!in) {
+	if (adaptive) {
+		// statement 7 as A1 to A5: DeviceGatherAdaptive's body on the points; it returns with the last pass complete, a synchronous call with its stats as well
+		if (!GatherAdaptiveLocked(sc, R, P.gather.kind, prm, *adaptive, seed, R.lmPoints.ptr, (int32_t)r.count, R.lmValues.ptr, outSamples ? R.lmSamples.ptr : nullptr, false, stream, t0, stats)) return false;
+		if (outSamples) {
+			// the counts through the ranks into their atlas, undilated: 0 where no point is
+			hipLaunchKernelGGL(k_gather_scatter_counts, dim3(BlocksFor(nTex)), dim3(RL_BLOCK), 0, st, (const uint32_t*)R.lmRank.ptr, (const uint32_t*)R.lmSamples.ptr, nTex, R.lmSampleAtlas.ptr);
+			HIP_TRY(hipGetLastError());
+		}
+	} else if (!in) {
 		// statement 7: DeviceGather's body on the points, on the call's stream; a synchronous call returns from it with the gather's stats and an idle stream
 		if (!GatherLocked(sc, R, P.gather.kind, prm, seed, R.lmPoints.ptr, (int32_t)r.count, R.lmValues.ptr, false, stream, t0, stats)) return false;
 	} else {
@@ -216,6 +232,7 @@ bool DeviceBakeLightmap(Scene& sc, const RaylibAMDLightmapParams& P, int32_t tri
 	const hipMemcpyKind kind = hostMem ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
 	if (ok) HIP_TRY(hipMemcpyAsync(out, R.lmAtlas[last].ptr, atlasBytes, kind, st));
 	if (ok && outCoverage) HIP_TRY(hipMemcpyAsync(outCoverage, R.lmCov[last].ptr, nTex, kind, st));
+	if (ok && adaptive && outSamples) HIP_TRY(hipMemcpyAsync(outSamples, R.lmSampleAtlas.ptr, (size_t)nTex * sizeof(uint32_t), kind, st));
 	// the event behind whatever was enqueued: the next call on any stream waits for it before it touches the scratch
 	const hipError_t evErr = hipEventRecord(R.radEv, st);
 	if (evErr == hipSuccess) R.radEvUsed = true;
@@ -236,7 +253,7 @@ bool DeviceBakeLightmap(Scene& sc, const RaylibAMDLightmapParams& P, int32_t tri
 		if (filter) snprintf(filt, sizeof(filt), "filter (%d iterations) %.3f ms, ", filter->iterations, ms[3]);
 		Log("%s: %d x %d, %d triangles, %llu pairs in %llu launches of one pair per lane, %llu points | setup + scan + cover %.3f ms, points + compaction %.3f ms, "
 		    "%s %.3f ms, %sscatter + dilate %.3f ms, whole %.3f ms", who, P.width, P.height, triCount, (unsigned long long)r.pairs,
-		    (unsigned long long)((r.pairs + RL_LM_COVER_PAIRS - 1) / RL_LM_COVER_PAIRS), (unsigned long long)r.count, ms[0], ms[1], in ? "atlas taken" : "gather", ms[2], filt, ms[4], whole);
+		    (unsigned long long)((r.pairs + RL_LM_COVER_PAIRS - 1) / RL_LM_COVER_PAIRS), (unsigned long long)r.count, ms[0], ms[1], in ? "atlas taken" : adaptive ? "adaptive gather" : "gather", ms[2], filt, ms[4], whole);
 	}
 	return true;
 }

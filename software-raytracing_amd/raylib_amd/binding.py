@@ -445,6 +445,122 @@ def filter_lightmap_host(lib, w, h, kind, filter, points, texel, values, in_plac
     return out
 
 
+class GatherAdaptiveParams(C.Structure):
+    """include/raylib_amd.h RaylibAMDGatherAdaptiveParams."""
+    _fields_ = [("threshold", C.c_float), ("minSamples", C.c_uint32), ("passSamples", C.c_uint32)]
+
+
+def gather_adaptive(lib, scene, points, kind, threshold, min_samples=4, pass_samples=4, max_path=5, tmin=1e-4, sample_first=0, sample_count=1, skip_draws=0,
+                    want_samples=True):
+    """Probes gathered in passes with per-point stopping (RaylibAMD_GatherAdaptive / RaylibAMD_GatherAdaptiveDevice; sample_count is the cap): (values, samples).
+
+    points as for gather: a NumPy array goes through the host entry and returns ((n, 4) or (n, 27) float32, (n,) uint32); a float32 torch tensor on the device
+    goes through the device entry on torch's current stream -- which the call waits for once per pass -- and returns tensors (samples as int32, holding the
+    counts).  want_samples False passes a null outSamples and returns None in its place.  Raises RuntimeError when the library refuses the call."""
+    kind = int(kind)
+    if kind not in _GATHER_FLOATS:
+        raise ValueError("unknown gather kind %r" % kind)
+    prm = GatherParams(kind, int(max_path), float(tmin), int(sample_first), int(sample_count), int(skip_draws), 0.0, 0.0)
+    ada = GatherAdaptiveParams(float(threshold), int(min_samples), int(pass_samples))
+    u32 = C.POINTER(C.c_uint32)
+    if isinstance(points, np.ndarray):
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 8)
+        n = len(p)
+        out = np.zeros((n, _GATHER_FLOATS[kind]), np.float32)
+        cnt = np.zeros(n, np.uint32) if want_samples else None
+        ok = lib.RaylibAMD_GatherAdaptive(scene, C.byref(prm), C.byref(ada), p.ctypes.data_as(C.POINTER(GatherPoint)), n, out.ctypes.data_as(C.POINTER(C.c_float)),
+                                          cnt.ctypes.data_as(u32) if want_samples else None)
+        if ok != 1:
+            raise RuntimeError("RaylibAMD_GatherAdaptive refused the call")
+        return out, cnt
+    import torch
+    if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float32):
+        raise TypeError("points: a float32 NumPy array or a float32 torch tensor on the device")
+    p = points.reshape(-1, 8).contiguous()
+    n = p.shape[0]
+    out = torch.empty((n, _GATHER_FLOATS[kind]), dtype=torch.float32, device=p.device)
+    cnt = torch.zeros((n,), dtype=torch.int32, device=p.device) if want_samples else None
+    if n:
+        prm.timeMin, prm.timeMax = float(p[:, 3].min()), float(p[:, 3].max())
+    stream = torch.cuda.current_stream(p.device)
+    if stream.cuda_stream == 0:
+        stream.synchronize()   # (as gather: the library's stream is not ordered against torch's default stream)
+    ok = lib.RaylibAMD_GatherAdaptiveDevice(scene, C.byref(prm), C.byref(ada), C.cast(C.c_void_p(p.data_ptr()), C.POINTER(GatherPoint)), n,
+                                            C.cast(C.c_void_p(out.data_ptr()), C.POINTER(C.c_float)),
+                                            C.cast(C.c_void_p(cnt.data_ptr()), u32) if want_samples else None, C.c_void_p(stream.cuda_stream))
+    if ok != 1:
+        raise RuntimeError("RaylibAMD_GatherAdaptiveDevice refused the call")
+    return out, cnt
+
+
+def gather_adaptive_decide_host(lib, keys, threshold, min_samples=4, pass_samples=4, cap=None):
+    """RaylibAMD_GatherAdaptiveDecideHost: statements A1 to A3 on keys (count, cap, 3) float32 -- the n at which each point stops, (count,) uint32; no device.
+    cap defaults to keys' second dimension.  None when the call refuses."""
+    k = np.ascontiguousarray(keys, np.float32)
+    cap = k.shape[1] if cap is None else int(cap)
+    count = k.shape[0]
+    out = np.zeros(count, np.uint32)
+    ada = GatherAdaptiveParams(float(threshold), int(min_samples), int(pass_samples))
+    ok = lib.RaylibAMD_GatherAdaptiveDecideHost(C.byref(ada), cap, _fp(k), count, out.ctypes.data_as(C.POINTER(C.c_uint32)))
+    return out if ok == 1 else None
+
+
+def gather_compact_test(lib, live, stopped, points, pad=8):
+    """RaylibAMD_GatherCompactTest: (return code, outLive, outPoints, count).  live: ascending original indices; stopped: a byte per original point; points: the
+    (numPoints, 8) float32 original records.  The output arrays have len(live) + pad entries, filled with COMPACT_SENTINEL (the records: its bits in every word)
+    before the call, and the count is a 1-element array filled likewise: the caller sees what the library wrote and what it left alone."""
+    live = np.ascontiguousarray(live, np.uint32)
+    stopped = np.ascontiguousarray(stopped, np.uint8)
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 8)
+    u32, u8 = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+    out_live = np.full(len(live) + pad, COMPACT_SENTINEL, np.uint32)
+    out_points = np.full((len(live) + pad, 8), COMPACT_SENTINEL, np.uint32)
+    count = np.full(1, COMPACT_SENTINEL, np.uint32)
+    r = lib.RaylibAMD_GatherCompactTest(live.ctypes.data_as(u32), len(live), stopped.ctypes.data_as(u8), pts.ctypes.data_as(C.POINTER(GatherPoint)), len(pts),
+                                        out_live.ctypes.data_as(u32), out_points.ctypes.data_as(C.POINTER(GatherPoint)), count.ctypes.data_as(u32))
+    return r, out_live, out_points, count
+
+
+def bake_lightmap_adaptive(lib, scene, w, h, threshold, min_samples=4, pass_samples=4, uv=None, kind=GATHER_IRRADIANCE, tri_first=0, tri_count=-1, dilate=0, time=0.0,
+                           max_path=5, tmin=1e-4, sample_first=0, sample_count=1, skip_draws=0, device=None, want_samples=True):
+    """An adaptive bake (RaylibAMD_BakeLightmapAdaptive / RaylibAMD_BakeLightmapAdaptiveDevice; sample_count is the cap): (atlas (H, W, C) float32, coverage (H, W)
+    uint8, samples (H, W) uint32 -- int32 as a torch tensor -- or None).  uv and device as for bake_lightmap.  Raises RuntimeError when the library refuses."""
+    kind = int(kind)
+    if kind not in _GATHER_FLOATS:
+        raise ValueError("unknown gather kind %r" % kind)
+    c = _GATHER_FLOATS[kind]
+    prm = lightmap_params(w, h, kind, tri_first, tri_count, dilate, time, max_path, tmin, sample_first, sample_count, skip_draws)
+    ada = GatherAdaptiveParams(float(threshold), int(min_samples), int(pass_samples))
+    u32 = C.POINTER(C.c_uint32)
+    if device is None and (uv is None or isinstance(uv, np.ndarray)):
+        keep, uvp = _uv_host(uv)
+        out = np.zeros((int(h), int(w), c), np.float32)
+        cov = np.zeros((int(h), int(w)), np.uint8)
+        cnt = np.zeros((int(h), int(w)), np.uint32) if want_samples else None
+        if lib.RaylibAMD_BakeLightmapAdaptive(scene, C.byref(prm), C.byref(ada), uvp, out.ctypes.data_as(C.POINTER(C.c_float)), cov.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                              cnt.ctypes.data_as(u32) if want_samples else None) != 1:
+            raise RuntimeError("RaylibAMD_BakeLightmapAdaptive refused the call")
+        return out, cov, cnt
+    import torch
+    if uv is not None:
+        if not (isinstance(uv, torch.Tensor) and uv.is_cuda and uv.dtype == torch.float32):
+            raise TypeError("uv: None, a float32 NumPy array or a float32 torch tensor on the device")
+        uv = uv.reshape(-1, 6).contiguous()
+        device = uv.device
+    out = torch.empty((int(h), int(w), c), dtype=torch.float32, device=device)
+    cov = torch.empty((int(h), int(w)), dtype=torch.uint8, device=device)
+    cnt = torch.empty((int(h), int(w)), dtype=torch.int32, device=device) if want_samples else None
+    stream = torch.cuda.current_stream(out.device)
+    if stream.cuda_stream == 0:
+        stream.synchronize()   # (as gather: the library's stream is not ordered against torch's default stream)
+    uvp = C.cast(C.c_void_p(uv.data_ptr()), C.POINTER(C.c_float)) if uv is not None else None
+    if lib.RaylibAMD_BakeLightmapAdaptiveDevice(scene, C.byref(prm), C.byref(ada), uvp, C.cast(C.c_void_p(out.data_ptr()), C.POINTER(C.c_float)),
+                                                C.cast(C.c_void_p(cov.data_ptr()), C.POINTER(C.c_uint8)),
+                                                C.cast(C.c_void_p(cnt.data_ptr()), u32) if want_samples else None, C.c_void_p(stream.cuda_stream)) != 1:
+        raise RuntimeError("RaylibAMD_BakeLightmapAdaptiveDevice refused the call")
+    return out, cov, cnt
+
+
 # Per-ray / per-unit algorithmic byte constants of the flat layout (csrc/rl_device.h)
 NODE_B, TRI_B, SHADE_B, TEXEL_B, PIXEL_B = 64, 64, 64, 16, 16
 
@@ -521,6 +637,17 @@ _EXPORTS = {
     "RaylibAMD_GatherDevice": (C.c_int32, [C.c_void_p, C.POINTER(GatherParams), C.POINTER(GatherPoint), C.c_int32, C.POINTER(C.c_float), C.c_void_p]),
     "RaylibAMD_GatherDirectionsHost": (C.c_int32, [C.POINTER(GatherParams), C.POINTER(GatherPoint), C.c_int32, C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]),
     "RaylibAMD_PlanGatherCut": (C.c_int32, [C.POINTER(GatherParams), C.c_int32, C.c_uint64, C.POINTER(GatherCut)]),
+    "RaylibAMD_GatherAdaptive": (C.c_int32, [C.c_void_p, C.POINTER(GatherParams), C.POINTER(GatherAdaptiveParams), C.POINTER(GatherPoint), C.c_int32, C.POINTER(C.c_float),
+                                             C.POINTER(C.c_uint32)]),
+    "RaylibAMD_GatherAdaptiveDevice": (C.c_int32, [C.c_void_p, C.POINTER(GatherParams), C.POINTER(GatherAdaptiveParams), C.POINTER(GatherPoint), C.c_int32, C.POINTER(C.c_float),
+                                                   C.POINTER(C.c_uint32), C.c_void_p]),
+    "RaylibAMD_GatherAdaptiveDecideHost": (C.c_int32, [C.POINTER(GatherAdaptiveParams), C.c_uint32, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_uint32)]),
+    "RaylibAMD_GatherCompactTest": (C.c_int32, [C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint8), C.POINTER(GatherPoint), C.c_uint32, C.POINTER(C.c_uint32),
+                                                C.POINTER(GatherPoint), C.POINTER(C.c_uint32)]),
+    "RaylibAMD_BakeLightmapAdaptive": (C.c_int32, [C.c_void_p, C.POINTER(LightmapParams), C.POINTER(GatherAdaptiveParams), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                   C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)]),
+    "RaylibAMD_BakeLightmapAdaptiveDevice": (C.c_int32, [C.c_void_p, C.POINTER(LightmapParams), C.POINTER(GatherAdaptiveParams), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                         C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.c_void_p]),
     "RaylibAMD_LightmapPoints": (C.c_int64, [C.c_void_p, C.POINTER(LightmapParams), C.POINTER(C.c_float), C.POINTER(GatherPoint), C.POINTER(C.c_uint32), C.c_int64]),
     "RaylibAMD_LightmapPointsHost": (C.c_int64, [C.c_void_p, C.POINTER(LightmapParams), C.POINTER(C.c_float), C.POINTER(GatherPoint), C.POINTER(C.c_uint32), C.c_int64]),
     "RaylibAMD_BakeLightmap": (C.c_int32, [C.c_void_p, C.POINTER(LightmapParams), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint8)]),
