@@ -503,6 +503,17 @@ RAYLIB_API int32_t RaylibAMD_VerifyLazyRefl(uint32_t n, uint64_t seed, uint64_t*
  * either form) does not give the fold the eagerly evaluated bits of both (must be 0), outRefused = events that evaluate the pdf after all.  Returns 1 when the
  * sweep ran. */
 RAYLIB_API int32_t RaylibAMD_VerifyLazyPdf(uint32_t n, uint64_t seed, uint64_t* outEvents, uint64_t* outWrong, uint64_t* outRefused);
+/* The same instance's Beckmann sampler calls logf, expf, sqrtf and 1 / x without their special-case guards where its arguments cannot reach them (csrc/rl_dev_shade.h
+ * "the ranged sampler").  Every such piece is a function of one float, compared here with the general form on ALL 2^32 bit patterns of it, on the device
+ * (csrc/rl_render_lazy.hip k_verify_sampler_ranged).  mode 0: the Newton loop's body, ErfInv(b) and expf of minus its square; mode 1: the prologue (tanThetaI, Erf of
+ * the cotangent, the fit exponent, the normalization) as a function of cosThetaI, for every cosThetaI below the sampler's .9999 branch; mode 2: that branch as a
+ * float compare against the (double) compare; mode 3: csrc/rl_glibc_math.h logf_in_range_, expf_in_range_ and sqrtf_in_range_ against the general functions, each over
+ * its stated domain.  outMismatches: inputs whose results differ (a NaN may differ in payload; mode 1: inside [C_MIN, .9999] only) -- must be 0; outFirstBits: the
+ * smallest such bit pattern.  Mode 1 also fills outInterval[3] with bit patterns: the ends of the interval below the branch on which the two prologues agree
+ * everywhere (one pattern above the largest positive cosThetaI at which they differ, and the last float below the branch) and the C_MIN the library was
+ * built with, which must lie inside; and outOutside: the differing inputs outside [C_MIN, .9999], which the sampler sends through the general prologue.  Any output
+ * may be NULL.  Returns 1 when the sweep ran. */
+RAYLIB_API int32_t RaylibAMD_VerifySamplerRanged(int32_t mode, uint64_t* outMismatches, uint64_t* outFirstBits, uint32_t* outInterval, uint64_t* outOutside);
 
 /* ---- host-logic introspection (no GPU needed) ---------------------------------- */
 /* Flattened scene as the kernels see it.  Triangle record = 26 words, material record =

@@ -739,6 +739,19 @@ int32_t RaylibAMD_VerifyExactMath(int32_t which, uint64_t* outMismatches, uint64
 	return DeviceVerifyExactMath(which, outMismatches, outFirstBits) ? 1 : 0;
 }
 
+// outInterval: lo, hi and the compiled RL_SAMPLER_C_MIN as bit patterns (the agreeing interval begins one pattern above the largest differing one and ends one below the branch's threshold)
+int32_t RaylibAMD_VerifySamplerRanged(int32_t mode, uint64_t* outMismatches, uint64_t* outFirstBits, uint32_t* outInterval, uint64_t* outOutside)
+{
+	if (mode < 0 || mode > 3) return 0;
+	uint64_t out[6] = { 0, 0, 0, 0, 0, 0 };
+	if (!DeviceVerifySamplerRanged(mode, out)) return 0;
+	if (outMismatches) *outMismatches = out[0];
+	if (outFirstBits) *outFirstBits = out[1];
+	if (outInterval) { outInterval[0] = (uint32_t)out[2] + 1u; outInterval[1] = (uint32_t)out[5] - 1u; outInterval[2] = (uint32_t)out[4]; }
+	if (outOutside) *outOutside = out[3];
+	return 1;
+}
+
 int32_t RaylibAMD_VerifyLazyRefl(uint32_t n, uint64_t seed, uint64_t* outEvents, uint64_t* outUnsafe, uint64_t* outGuardFailed)
 {
 	uint64_t out[3] = { 0, 0, 0 };

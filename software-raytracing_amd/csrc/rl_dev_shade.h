@@ -183,6 +183,105 @@ __device__ __forceinline__ bool QuotientNotPositive(float n, float d)
 template <bool INL> __device__ __forceinline__ float TanSel(float x) { return INL ? rtm::tan_inline_(x) : rtm::tan_(x); }
 template <bool INL> __device__ __forceinline__ float PowSel(float x, float y) { return INL ? rtm::pow_inline_(x, y) : rtm::pow_(x, y); }
 
+// ---- the ranged sampler (RL_SAMPLER_RANGED) ----
+// A translation unit's setting, made before its includes as RL_EXACT_DIV is; off by default, and only the lazy instance's unit turns it on (rl_render_lazy.hip).
+// BeckmannSample11 calls logf, expf, sqrtf and 1 / x with arguments that cannot reach those functions' special cases; with the setting on it calls their
+// guard-free forms (rl_glibc_math.h *_in_range_) there.  Nothing is argued on paper: every piece is a function of ONE float, and RaylibAMD_VerifySamplerRanged
+// (k_verify_sampler_ranged, rl_render_lazy.hip) compares it with the general form on all 2^32 bit patterns of that float.
+//   the loop body, a function of b:  ErfInv clamps its argument to +-0.99999 (a NaN too: fminf and fmaxf drop it), so log_ sees (1 - x)(1 + x) in [2e-5, 1],
+//       the tail's sqrt_ w in [5, 10.9], and exp_(-invErf invErf) an exponent in [-9.8, 0];
+//   the prologue, a function of cosThetaI on [RL_SAMPLER_C_MIN, 0.9999]:  sinThetaI in [0.014, 1], tanThetaI in [0.014, 2^126], cotThetaI in [2^-126, 71],
+//       1 + p cot >= 1, the normalization's argument in [1, 2^126): sqrt_, the tan division, both reciprocals and Erf's reciprocal lose their guards.  cotThetaI >= 0
+//       there, so Erf takes no sign and its exp_(-x x) is the normalization's exp_(-cot cot): evaluated once.  That exp_ KEEPS its guard (its argument passes -88
+//       at cotThetaI = 9.4, cosThetaI = 0.994, well inside the interval), and so does acos_.  Below C_MIN, at zero, negative or NaN the whole wave takes the
+//       general prologue behind one vote (DivSpecular's form);
+//   the branch on cosThetaI:  (double)cosThetaI > .9999 is cosThetaI >= RL_SAMPLER_COS_NEAR_ONE, the smallest float whose double exceeds .9999 (float(.9999)
+//       itself rounds below it), for every bit pattern.
+// pow_ (two inputs) and the Newton step's division (a divisor of unknown range) stay as they are.
+#ifndef RL_SAMPLER_RANGED
+#define RL_SAMPLER_RANGED 0
+#endif
+#define RL_SAMPLER_COS_NEAR_ONE 0x1.fff2e6p-1f   /* bits 0x3f7ff973; float(.9999) is 0x3f7ff972 = 0x1.fff2e4p-1 < .9999 */
+// What the sweep yields: the two prologues agree on every float of [2^-126, 0x1.fff2e4p-1] and differ at the largest subnormal (the short reciprocal of cosThetaI
+// leaves its range there) -- the bound the general form's tan division votes on already.
+#define RL_SAMPLER_C_MIN 0x1p-126f
+__device__ __forceinline__ float ErfInvRanged(float x)
+{
+	float w, p;
+	x = Clampf(x, -.99999f, .99999f);
+	w = -rtm::log_in_range_((1 - x) * (1 + x));
+	if (w < 5) {
+		w = w - 2.5f;
+		p = 2.81022636e-08f;
+		p = 3.43273939e-07f + p * w;
+		p = -3.5233877e-06f + p * w;
+		p = -4.39150654e-06f + p * w;
+		p = 0.00021858087f + p * w;
+		p = -0.00125372503f + p * w;
+		p = -0.00417768164f + p * w;
+		p = 0.246640727f + p * w;
+		p = 1.50140941f + p * w;
+	} else {
+		w = rtm::sqrt_in_range_(w) - 3;
+		p = -0.000200214257f;
+		p = 0.000100950558f + p * w;
+		p = 0.00134934322f + p * w;
+		p = -0.00367342844f + p * w;
+		p = 0.00573950773f + p * w;
+		p = -0.0076224613f + p * w;
+		p = 0.00943887047f + p * w;
+		p = 1.00167406f + p * w;
+		p = 2.83297682f + p * w;
+	}
+	return p * x;
+}
+// the Newton loop's two transcendentals of b: invErf = ErfInv(b) and exp_(-invErf invErf)
+__device__ __forceinline__ void SamplerLoopTerms(float b, float& invErf, float& expTerm)
+{
+	invErf = ErfInv(b);
+	expTerm = rtm::exp_(-invErf * invErf);
+}
+__device__ __forceinline__ void SamplerLoopTermsRanged(float b, float& invErf, float& expTerm)
+{
+	invErf = ErfInvRanged(b);
+	expTerm = rtm::exp_in_range_(-invErf * invErf);
+}
+// the sampler's prologue below the .9999 branch, a function of cosThetaI: BeckmannSample11's statements (those of a unit without the setting)
+__device__ __forceinline__ void SamplerPrologue(float cosThetaI, float& tanThetaI, float& c, float& fit, float& normalization)
+{
+	const float SQRT_PI_INV = 1.f / sqrtf(RL_PI);
+	float sinThetaI = rtm::sqrt_(fmaxf((float)0, (float)1 - cosThetaI * cosThetaI));
+#if RL_EXACT_DIV & 1
+	tanThetaI = rtm::div_by_(sinThetaI, cosThetaI, rlm::rcp1_in_range_(cosThetaI));
+	if (rtm::wave_any_(!(cosThetaI >= 0x1p-126f))) tanThetaI = sinThetaI / cosThetaI;
+#else
+	tanThetaI = sinThetaI / cosThetaI;
+#endif
+	float cotThetaI = rtm::rcp1_(tanThetaI);
+	c = Erf(cotThetaI);
+	float thetaI = rtm::acos_(cosThetaI);
+	fit = 1 + thetaI * (-0.876f + thetaI * (0.4265f - 0.0594f * thetaI));
+	normalization = rtm::rcp1_(1 + c + SQRT_PI_INV * tanThetaI * rtm::exp_(-cotThetaI * cotThetaI));
+}
+// ... and for RL_SAMPLER_C_MIN <= cosThetaI <= .9999 (the caller's to guarantee): the same bits
+__device__ __forceinline__ void SamplerPrologueRanged(float cosThetaI, float& tanThetaI, float& c, float& fit, float& normalization)
+{
+	const float SQRT_PI_INV = 1.f / sqrtf(RL_PI);
+	float sinThetaI = rtm::sqrt_in_range_((float)1 - cosThetaI * cosThetaI);   // (fmaxf(0, .) of a value >= 0.0002 is the value)
+	tanThetaI = rtm::div_by_(sinThetaI, cosThetaI, rlm::rcp1_in_range_(cosThetaI));
+	float cotThetaI = rlm::rcp1_in_range_(tanThetaI);
+	const float expCot = rtm::exp_(-cotThetaI * cotThetaI);   // guarded: it underflows from cotThetaI = 9.4 on
+	{	// Erf(cotThetaI) for cotThetaI >= 0
+		const float a1 = 0.254829592f, a2 = -0.284496736f, a3 = 1.421413741f, a4 = -1.453152027f, a5 = 1.061405429f;
+		const float p = 0.3275911f;
+		float t = rlm::rcp1_in_range_(1 + p * cotThetaI);
+		c = 1 - (((((a5 * t + a4) * t) + a3) * t + a2) * t + a1) * t * expCot;
+	}
+	float thetaI = rtm::acos_(cosThetaI);
+	fit = 1 + thetaI * (-0.876f + thetaI * (0.4265f - 0.0594f * thetaI));
+	normalization = rlm::rcp1_in_range_(1 + c + SQRT_PI_INV * tanThetaI * expCot);
+}
+
 // reference render/material.cc:83-165
 // (__forceinline__ on the sampler and its caller below: the compiler inlined both into every kernel of its own accord until k_trace's PLAIN instance added
 //  one more call site, after which it kept BeckmannSample out of line in all of them)
@@ -190,13 +289,27 @@ __device__ __forceinline__ void BeckmannSample11(float cosThetaI, float U1, floa
 {
 	(void)cn;   // diagnostic builds count Newton iterations
 	const float Pi = RL_PI;
+#if RL_SAMPLER_RANGED
+	if (cosThetaI >= RL_SAMPLER_COS_NEAR_ONE) {
+#else
 	if ((double)cosThetaI > .9999) {
+#endif
 		float r = rtm::sqrt_(-rtm::log_(1.0f - U1));
 		float sinPhi, cosPhi; rtm::sincos_(2 * Pi * U2, &sinPhi, &cosPhi);
 		*slope_x = r * cosPhi;
 		*slope_y = r * sinPhi;
 		return;
 	}
+#if RL_SAMPLER_RANGED
+	// the ranged prologue for the wave; a lane outside its interval (tiny, zero, negative, NaN) sends the whole wave through the general one
+	float tanThetaI, c, fit, normalization;
+	SamplerPrologueRanged(cosThetaI, tanThetaI, c, fit, normalization);
+	if (rtm::wave_any_(!(cosThetaI >= RL_SAMPLER_C_MIN))) SamplerPrologue(cosThetaI, tanThetaI, c, fit, normalization);
+	float a = -1;
+	float sample_x = fmaxf(U1, (float)1e-6f);
+	float b = c - (1 + c) * rtm::pow_(1 - sample_x, fit);
+	const float SQRT_PI_INV = 1.f / sqrtf(Pi);
+#else
 	float sinThetaI = rtm::sqrt_(fmaxf((float)0, (float)1 - cosThetaI * cosThetaI));
 #if RL_EXACT_DIV & 1
 	// cosThetaI <= .9999 here, so sinThetaI is in [0.014, 1]; with 2^-126 <= cosThetaI < 1 the quotient is in [0.014, 2^126] and div_by_'s conditions hold.
@@ -217,6 +330,7 @@ __device__ __forceinline__ void BeckmannSample11(float cosThetaI, float U1, floa
 
 	const float SQRT_PI_INV = 1.f / sqrtf(Pi);
 	float normalization = rtm::rcp1_(1 + c + SQRT_PI_INV * tanThetaI * rtm::exp_(-cotThetaI * cotThetaI));
+#endif
 
 	int it = 0;
 	float invErf = 0.0f;
@@ -232,8 +346,13 @@ __device__ __forceinline__ void BeckmannSample11(float cosThetaI, float U1, floa
 	while (++it < newtonLimit) {
 		RL_WLSTEP(cn, 16, 17);
 		if (!(b >= a && b <= c)) b = 0.5f * (a + c);
+#if RL_SAMPLER_RANGED
+		float expTerm; SamplerLoopTermsRanged(b, invErf, expTerm);
+		float value = normalization * (1 + b + SQRT_PI_INV * tanThetaI * expTerm) - sample_x;
+#else
 		invErf = ErfInv(b);
 		float value = normalization * (1 + b + SQRT_PI_INV * tanThetaI * rtm::exp_(-invErf * invErf)) - sample_x;
+#endif
 		float derivative = normalization * (1 - invErf * tanThetaI);
 		if (fabsf(value) < 1e-5f) { converged = true; break; }
 		if (value > 0) c = b; else a = b;
@@ -241,8 +360,13 @@ __device__ __forceinline__ void BeckmannSample11(float cosThetaI, float U1, floa
 	}
 	// the reference evaluates ErfInv(b) once more here (material.cc:163); after the break b is still the argument invErf was computed from,
 	// so the value is in hand -- only a lane that used up its nine iterations has moved b since (a whole ErfInv per scattering event less)
+#if RL_SAMPLER_RANGED
+	*slope_x = converged ? invErf : ErfInvRanged(b);
+	*slope_y = ErfInvRanged(2.0f * fmaxf(U2, (float)1e-6f) - 1.0f);
+#else
 	*slope_x = converged ? invErf : ErfInv(b);
 	*slope_y = ErfInv(2.0f * fmaxf(U2, (float)1e-6f) - 1.0f);
+#endif
 }
 // reference render/material.cc:166-190
 __device__ __forceinline__ V3 BeckmannSample(V3 wi, float alpha_x, float alpha_y, float U1, float U2, Counters& cn)

@@ -57,6 +57,18 @@ __device__ __forceinline__ static float rcp1_in_range_(float x)
 #else
 RLM_FN float rcp1_in_range_(float x) { return 1.0f / x; }
 #endif
+// the short square root without its guard (device): RN(sqrt(x)) for 2^-101 <= x <= FLT_MAX, the caller's to guarantee
+// (RaylibAMD_VerifySamplerRanged mode 3 compares it with sqrtf on every bit pattern of that domain)
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ static float sqrtf_in_range_(float x)
+{
+	const float y = __builtin_amdgcn_rsqf(x);
+	const float g = x * y, h = 0.5f * y;
+	return __builtin_fmaf(__builtin_fmaf(-g, g, x), h, g);
+}
+#else
+RLM_FN float sqrtf_in_range_(float x) { return __builtin_sqrtf(x); }
+#endif
 #if defined(__HIP_DEVICE_COMPILE__) && RL_EXACT_FAST_RCP_SQRT
 // (the out-of-range path inline: as a call -- __noinline__ -- every one of the ~45 sites constrains the register allocation around it, and the Cornell
 // frame took 14.75 ms instead of 14.00; measured, round 3)
@@ -196,6 +208,35 @@ RLM_FN float expf_(float x)
 	y = y * s;
 	return (float)y;
 }
+// expf_ without its special-case block (device): the main path, statement for statement.  Domain: |x| < 88 (the inputs whose abstop is below 88.0f's; zeros and
+// subnormals included), the caller's to guarantee -- no infinity, NaN, overflow or underflow.  On the host the general function.
+// (RaylibAMD_VerifySamplerRanged mode 3 compares the two on every bit pattern of the domain)
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ static float expf_in_range_(float x)
+{
+	RLM_DECL_EXP2F_TABLE
+	const double SHIFT = 0x1.8p+52, InvLn2N = 0x1.71547652b82fep+5;
+	const double C0 = 0x1.c6af84b912394p-20, C2 = 0x1.62e42ff0c52d6p-6;
+	RLM_LOCAL_CONST(C1, 0x1.ebfce50fac4f3p-13);
+	double xd = (double)x;
+	double kd = fma_(InvLn2N, xd, SHIFT);
+	uint64_t ki = asuint64(kd);
+	kd -= SHIFT;
+	double r = fma_(InvLn2N, xd, -kd);
+	double z;
+	uint64_t t = RLM_EXP2F_AT(ki % 32);
+	t += ki << (52 - 5);
+	double s = asdouble(t);
+	z = fma_(C0, r, C1);
+	double r2 = r * r;
+	double y = fma_(C2, r, 1.0);
+	y = fma_(z, r2, y);
+	y = y * s;
+	return (float)y;
+}
+#else
+RLM_FN float expf_in_range_(float x) { return expf_(x); }
+#endif
 
 // logf  (glibc sysdeps/ieee754/flt-32/e_logf.c, FMA-contracted)
 RLM_FN float logf_(float x)
@@ -227,6 +268,34 @@ RLM_FN float logf_(float x)
 	y = fma_(y, r2, y0 + r);
 	return (float)y;
 }
+// logf_ without its special cases (device): the main path, statement for statement.  Domain: 2^-126 <= x <= FLT_MAX (positive and normal), the caller's to
+// guarantee -- no zero, subnormal, negative number, infinity or NaN.  x = 1 needs no test of its own: the main path gives it r = 0, y0 = 0 and +0 (in the sweep).
+// On the host the general function.  (RaylibAMD_VerifySamplerRanged mode 3 compares the two on every bit pattern of the domain)
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ static float logf_in_range_(float x)
+{
+	RLM_DECL_LOGF_TABLES
+	const double Ln2 = 0x1.62e42fefa39efp-1;
+	const double A0 = -0x1.00ea348b88334p-2, A1 = 0x1.5575b0be00b6ap-2;
+	RLM_LOCAL_CONST(A2, -0x1.ffffef20a4123p-2);
+	uint32_t ix = asuint(x);
+	uint32_t tmp = ix - 0x3f330000u;
+	int i = (tmp >> (23 - 4)) % 16;
+	int k = (int32_t)tmp >> 23;
+	uint32_t iz = ix - (tmp & (0x1ffu << 23));
+	double invc = RLM_INVC(i), logc = RLM_LOGF_LOGC_AT(i);
+	double z = (double)asfloat(iz);
+	double r = fma_(z, invc, -1.0);
+	double y0 = fma_((double)k, Ln2, logc);
+	double r2 = r * r;
+	double y = fma_(A1, r, A2);
+	y = fma_(A0, r2, y);
+	y = fma_(y, r2, y0 + r);
+	return (float)y;
+}
+#else
+RLM_FN float logf_in_range_(float x) { return logf_(x); }
+#endif
 
 // powf  (glibc sysdeps/ieee754/flt-32/e_powf.c, non-TOINT path, FMA-contracted)
 RLM_FN int powf_checkint(uint32_t iy)

@@ -84,6 +84,14 @@ __device__ __forceinline__ void sincos_(float x, float* s, float* c) { const flo
 // sign bits of sinf(x), cosf(x) for 0 <= x < 120 without evaluating them
 __device__ __forceinline__ void sincos_signs_(float x, bool* sn, bool* cn) { rlm::sincosf_signs(x, sn, cn); }
 #endif
+// exp_ and log_ for arguments the caller has proved ordinary (rl_glibc_math.h expf_in_range_ / logf_in_range_: the same bits without the special-case blocks)
+#if defined(RAYLIB_OCML_MATH)
+__device__ __forceinline__ float exp_in_range_(float x) { return expf(x); }
+__device__ __forceinline__ float log_in_range_(float x) { return logf(x); }
+#else
+__device__ __forceinline__ float exp_in_range_(float x) { return rlm::expf_in_range_(x); }
+__device__ __forceinline__ float log_in_range_(float x) { return rlm::logf_in_range_(x); }
+#endif
 __device__ __forceinline__ float fmod1_(float x) { return fmodf(x, 1.0f); }
 // tanf and powf always inline, for the one kernel instance that may take them so (rl_dev_shade.h RL_PLAIN_INLINE_TAN / _POW)
 __device__ __forceinline__ float tan_inline_(float x)  { return rlm::tanf_(x); }
@@ -102,6 +110,7 @@ __device__ __forceinline__ float pow_inline_(float x, float y) { return rlm::pow
 // (tests/test_math_exact.py).  20 and 22 issue cycles instead of 36 and 57.  The sequences live in rl_glibc_math.h (its acosf / asinf take square roots too).
 __device__ __forceinline__ float rcp1_(float x) { return rlm::rcp1_(x); }
 __device__ __forceinline__ float sqrt_(float x) { return rlm::sqrtf_(x); }
+__device__ __forceinline__ float sqrt_in_range_(float x) { return rlm::sqrtf_in_range_(x); }   // 2^-101 <= x <= FLT_MAX, the caller's to guarantee
 
 // ---- a / b when y = RN(1 / b) is in hand (a divisor fixed per launch, per triangle ...) ---------------------------------------------------------
 //   q0 = a * y;  q = fma(fma(-b, q0, a), y, q0)

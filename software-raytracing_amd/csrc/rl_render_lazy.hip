@@ -2,7 +2,10 @@
 // unit of their own: instantiated beside the other k_trace instances, the lazy one changes how the compiler schedules two loops of the eager PLAIN instance, and
 // the eager kernels must stay what they are (tools/isa_equivalence.py) -- the reason the views twins have their unit.
 
-// ---- settings: this unit takes every default ----
+// ---- settings: every default but the sampler's ----
+// The Beckmann sampler with the guard-free forms of logf, expf, sqrtf and 1 / x where its arguments cannot reach the guards (rl_dev_shade.h "the ranged sampler";
+// swept by k_verify_sampler_ranged below).  Measured on this unit's kernel only: every other unit keeps the general sampler.
+#define RL_SAMPLER_RANGED 1
 
 // ---- the device library ----
 #include "rl_kernels.h"
@@ -196,6 +199,57 @@ k_verify_lazy_pdf(uint32_t n, unsigned long long seed, unsigned long long* __res
 	}
 	for (int off = 32; off > 0; off >>= 1) { events += __shfl_down(events, off); wrong += __shfl_down(wrong, off); refused += __shfl_down(refused, off); }
 	if ((threadIdx.x & 63u) == 0u) { atomicAdd(&out[0], events); if (wrong) atomicAdd(&out[1], wrong); if (refused) atomicAdd(&out[2], refused); }
+}
+
+// Test hook: the ranged sampler's claims (rl_dev_shade.h "the ranged sampler"), each a function of one float and swept over ALL 2^32 bit patterns of it.
+//   mode 0: the loop body -- ErfInvRanged(b) and exp_in_range_ of minus its square against ErfInv(b) and exp_;
+//   mode 1: the prologue -- SamplerPrologueRanged against SamplerPrologue (tanThetaI, c, fit, normalization) for every cosThetaI that does not take the .9999
+//           branch.  Counted: the mismatches inside [RL_SAMPLER_C_MIN, .9999] (must be 0) and those outside; out[2] keeps the largest positive bit pattern below the
+//           branch at which the two differ -- the agreeing interval begins one pattern above it and ends at the last one below the branch;
+//   mode 2: the branch -- cosThetaI >= RL_SAMPLER_COS_NEAR_ONE against (double)cosThetaI > .9999;
+//   mode 3: logf_in_range_, expf_in_range_ and sqrtf_in_range_ (rl_glibc_math.h) against logf_, expf_ and sqrtf, each over its stated domain.
+// out[0]: mismatches (a NaN may meet a NaN of another payload); out[1]: the smallest mismatching bit pattern; out[2]: see mode 1 (0: none); out[3]: mode 1's
+// mismatches outside the interval; out[4], out[5]: the bits of RL_SAMPLER_C_MIN and RL_SAMPLER_COS_NEAR_ONE as compiled.
+__device__ __forceinline__ bool SameBitsOrNaN(float a, float b) { return __float_as_uint(a) == __float_as_uint(b) || (a != a && b != b); }
+__global__ void __launch_bounds__(RL_BLOCK)
+k_verify_sampler_ranged(int mode, unsigned long long* __restrict__ out)
+{
+	RL_MATH_PROLOGUE();
+	const unsigned long long tid = (unsigned long long)blockIdx.x * RL_BLOCK + threadIdx.x, n = (unsigned long long)gridDim.x * RL_BLOCK;
+	unsigned long long bad = 0, first = ~0ull, outside = 0, top = 0;
+	// (every thread of a launch of whole workgroups makes the same number of trips: the general prologue votes across the wave)
+	for (unsigned long long b = tid; b < (1ull << 32); b += n) {
+		const uint32_t bits = (uint32_t)b;
+		const float x = __uint_as_float(bits);
+		bool differs = false;
+		if (mode == 0) {
+			float ig, eg, ir, er;
+			SamplerLoopTerms(x, ig, eg);
+			SamplerLoopTermsRanged(x, ir, er);
+			differs = !SameBitsOrNaN(ig, ir) || !SameBitsOrNaN(eg, er);
+		} else if (mode == 1) {
+			if (!(x >= RL_SAMPLER_COS_NEAR_ONE)) {
+				float tg, cg, fg, ng, tr, cr, fr, nr;
+				SamplerPrologue(x, tg, cg, fg, ng);
+				SamplerPrologueRanged(x, tr, cr, fr, nr);
+				const bool d = !SameBitsOrNaN(tg, tr) || !SameBitsOrNaN(cg, cr) || !SameBitsOrNaN(fg, fr) || !SameBitsOrNaN(ng, nr);
+				if (x >= RL_SAMPLER_C_MIN) differs = d;
+				else if (d) ++outside;
+				if (d && bits - 1u < 0x7f7fffffu) top = max(top, (unsigned long long)bits);   // positive and finite
+			}
+		} else if (mode == 2) {
+			differs = (x >= RL_SAMPLER_COS_NEAR_ONE) != ((double)x > .9999);
+		} else {
+			if (bits - 0x00800000u < 0x7f800000u - 0x00800000u) differs = differs || !SameBitsOrNaN(rlm::logf_in_range_(x), rlm::logf_(x));
+			if (((bits >> 20) & 0x7ffu) < ((rlm::asuint(88.0f) >> 20) & 0x7ffu)) differs = differs || !SameBitsOrNaN(rlm::expf_in_range_(x), rlm::expf_(x));
+			if (bits - 0x0d000000u < 0x7f800000u - 0x0d000000u) differs = differs || !SameBitsOrNaN(rlm::sqrtf_in_range_(x), __builtin_sqrtf(x));
+		}
+		if (differs) { ++bad; first = min(first, b); }
+	}
+	if (bad) { atomicAdd(&out[0], bad); atomicMin(&out[1], first); }
+	if (top) atomicMax(&out[2], top);
+	if (outside) atomicAdd(&out[3], outside);
+	if (tid == 0) { out[4] = __float_as_uint(RL_SAMPLER_C_MIN); out[5] = __float_as_uint(RL_SAMPLER_COS_NEAR_ONE); }   // the constants this build was compiled with
 }
 
 // ---- instances ----

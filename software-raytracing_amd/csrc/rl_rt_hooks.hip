@@ -77,6 +77,20 @@ bool DeviceVerifyExactMath(int which, uint64_t* outMismatches, uint64_t* outFirs
 	return ok;
 }
 
+// the ranged sampler's sweeps (rl_render_lazy.hip): all 2^32 bit patterns in one launch, as DeviceVerifyExactMath's
+bool DeviceVerifySamplerRanged(int mode, uint64_t out[6])
+{
+	std::lock_guard<std::mutex> lk(Rt().lock);
+	if (!EnsureRuntime()) return false;
+	HIP_OK(hipSetDevice(Rank0().device));
+	unsigned long long h[6] = { 0ull, ~0ull, 0ull, 0ull, 0ull, 0ull };
+	DevBuf<unsigned long long> d;
+	if (!d.Upload(h, 6)) return false;
+	const bool ok = RunOnRank0(k_verify_sampler_ranged, 4096, RL_BLOCK, mode, d.ptr) && Download(h, d.ptr, 6);
+	for (int k = 0; k < 6; ++k) out[k] = h[k];
+	return ok;
+}
+
 // the two sweeps of the lazy instance's guards: three counts each
 static bool VerifyLazySweep(void (*kernel)(uint32_t, unsigned long long, unsigned long long*), uint32_t n, uint64_t seed, uint64_t out[3])
 {
