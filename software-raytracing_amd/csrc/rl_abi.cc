@@ -906,31 +906,13 @@ static bool GatherKindValid(const char* who, const RaylibAMDGatherParams* p)
 	if (p->skipDraws > 62) { Log("%s: skipDraws %u exceeds 62", who, p->skipDraws); return false; }
 	return true;
 }
-static int32_t GatherInternal(const char* who, SceneHandle sh, const RaylibAMDGatherParams* params, const RaylibAMDGatherPoint* points, int32_t n, float* out,
-                              bool hostMem, void* stream)
+// a gather's parameters as a radiance call's
+static RaylibAMDRadianceParams RadianceParamsOf(const RaylibAMDGatherParams& g)
 {
-	Scene* s = (Scene*)sh;
-	if (n < 0 || (n > 0 && (!points || !out))) { Log("%s: null argument", who); return 0; }
-	if (!s || !params) { Log("%s: null argument", who); return 0; }
 	RaylibAMDRadianceParams prm;
-	prm.maxPathLength = params->maxPathLength; prm.rayTMin = params->rayTMin; prm.sampleFirst = params->sampleFirst; prm.sampleCount = params->sampleCount;
-	prm.skipDraws = params->skipDraws; prm.timeMin = params->timeMin; prm.timeMax = params->timeMax;
-	if (!RadianceParamsValid(who, s, &prm) || !GatherKindValid(who, params)) return 0;
-	if (!PathTimesValid(who, "point", prm, points, n, hostMem)) return 0;
-	if (!DeviceAvailable()) return n == 0 ? 1 : 0;   // (no points: nothing to gather, with or without a device)
-	if (!PreparePathScene(who, s, prm, n)) return 0;
-	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
-	if (!DeviceGather(*s, params->kind, prm, CurrentSeed(), points, n, out, hostMem, stream, stats)) return 0;
-	if (!stream) ReportOwnStats(stats);
-	return 1;
-}
-int32_t RaylibAMD_Gather(SceneHandle sh, const RaylibAMDGatherParams* params, const RaylibAMDGatherPoint* points, int32_t n, float* out)
-{
-	return GatherInternal("RaylibAMD_Gather", sh, params, points, n, out, true, nullptr);
-}
-int32_t RaylibAMD_GatherDevice(SceneHandle sh, const RaylibAMDGatherParams* params, const RaylibAMDGatherPoint* points, int32_t n, float* out, void* stream)
-{
-	return GatherInternal("RaylibAMD_GatherDevice", sh, params, points, n, out, false, stream);
+	prm.maxPathLength = g.maxPathLength; prm.rayTMin = g.rayTMin; prm.sampleFirst = g.sampleFirst; prm.sampleCount = g.sampleCount;
+	prm.skipDraws = g.skipDraws; prm.timeMin = g.timeMin; prm.timeMax = g.timeMax;
+	return prm;
 }
 // RaylibAMD_GatherAdaptive / ...Device / ...DecideHost / RaylibAMD_BakeLightmapAdaptive*: the refusals of the adaptive parameters under the cap `cap`
 static bool GatherAdaptiveValid(const char* who, const RaylibAMDGatherAdaptiveParams* a, uint32_t cap)
@@ -945,33 +927,44 @@ static bool GatherAdaptiveValid(const char* who, const RaylibAMDGatherAdaptivePa
 	}
 	return true;
 }
-static int32_t GatherAdaptiveInternal(const char* who, SceneHandle sh, const RaylibAMDGatherParams* params, const RaylibAMDGatherAdaptiveParams* adaptive,
-                                      const RaylibAMDGatherPoint* points, int32_t n, float* out, uint32_t* outSamples, bool hostMem, void* stream)
+// the four gather entries; adaptive: what an adaptive entry was given (its parameters, which may not be null, and outSamples), null for a plain entry
+struct GatherAdaptiveArgs { const RaylibAMDGatherAdaptiveParams* params; uint32_t* outSamples; };
+static int32_t GatherInternal(const char* who, SceneHandle sh, const RaylibAMDGatherParams* params, const RaylibAMDGatherPoint* points, int32_t n, float* out,
+                              bool hostMem, void* stream, const GatherAdaptiveArgs* adaptive)
 {
 	Scene* s = (Scene*)sh;
 	if (n < 0 || (n > 0 && (!points || !out))) { Log("%s: null argument", who); return 0; }
 	if (!s || !params) { Log("%s: null argument", who); return 0; }
-	RaylibAMDRadianceParams prm;
-	prm.maxPathLength = params->maxPathLength; prm.rayTMin = params->rayTMin; prm.sampleFirst = params->sampleFirst; prm.sampleCount = params->sampleCount;
-	prm.skipDraws = params->skipDraws; prm.timeMin = params->timeMin; prm.timeMax = params->timeMax;
-	if (!RadianceParamsValid(who, s, &prm) || !GatherKindValid(who, params) || !GatherAdaptiveValid(who, adaptive, params->sampleCount)) return 0;
+	RaylibAMDRadianceParams prm = RadianceParamsOf(*params);
+	if (!RadianceParamsValid(who, s, &prm) || !GatherKindValid(who, params)) return 0;
+	if (adaptive && !GatherAdaptiveValid(who, adaptive->params, params->sampleCount)) return 0;
 	if (!PathTimesValid(who, "point", prm, points, n, hostMem)) return 0;
 	if (!DeviceAvailable()) return n == 0 ? 1 : 0;   // (no points: nothing to gather, with or without a device)
 	if (!PreparePathScene(who, s, prm, n)) return 0;
 	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
-	if (!DeviceGatherAdaptive(*s, params->kind, prm, *adaptive, CurrentSeed(), points, n, out, outSamples, hostMem, stream, stats)) return 0;
+	if (!DeviceGather(*s, params->kind, prm, CurrentSeed(), points, n, out, hostMem, stream, stats, adaptive ? adaptive->params : nullptr, adaptive ? adaptive->outSamples : nullptr)) return 0;
 	if (!stream) ReportOwnStats(stats);
 	return 1;
+}
+int32_t RaylibAMD_Gather(SceneHandle sh, const RaylibAMDGatherParams* params, const RaylibAMDGatherPoint* points, int32_t n, float* out)
+{
+	return GatherInternal("RaylibAMD_Gather", sh, params, points, n, out, true, nullptr, nullptr);
+}
+int32_t RaylibAMD_GatherDevice(SceneHandle sh, const RaylibAMDGatherParams* params, const RaylibAMDGatherPoint* points, int32_t n, float* out, void* stream)
+{
+	return GatherInternal("RaylibAMD_GatherDevice", sh, params, points, n, out, false, stream, nullptr);
 }
 int32_t RaylibAMD_GatherAdaptive(SceneHandle sh, const RaylibAMDGatherParams* params, const RaylibAMDGatherAdaptiveParams* adaptive, const RaylibAMDGatherPoint* points,
                                  int32_t n, float* out, uint32_t* outSamples)
 {
-	return GatherAdaptiveInternal("RaylibAMD_GatherAdaptive", sh, params, adaptive, points, n, out, outSamples, true, nullptr);
+	const GatherAdaptiveArgs a = { adaptive, outSamples };
+	return GatherInternal("RaylibAMD_GatherAdaptive", sh, params, points, n, out, true, nullptr, &a);
 }
 int32_t RaylibAMD_GatherAdaptiveDevice(SceneHandle sh, const RaylibAMDGatherParams* params, const RaylibAMDGatherAdaptiveParams* adaptive, const RaylibAMDGatherPoint* points,
                                        int32_t n, float* out, uint32_t* outSamples, void* stream)
 {
-	return GatherAdaptiveInternal("RaylibAMD_GatherAdaptiveDevice", sh, params, adaptive, points, n, out, outSamples, false, stream);
+	const GatherAdaptiveArgs a = { adaptive, outSamples };
+	return GatherInternal("RaylibAMD_GatherAdaptiveDevice", sh, params, points, n, out, false, stream, &a);
 }
 // statements A1 to A3 on the caller's keys: the oracle of k_gather_adaptive_resolve's moments and decision (csrc/rl_progressive.h, built without FMA)
 int32_t RaylibAMD_GatherAdaptiveDecideHost(const RaylibAMDGatherAdaptiveParams* adaptive, uint32_t cap, const float* keys, int64_t count, uint32_t* outSamples)
@@ -1056,10 +1049,9 @@ static bool LightmapArgsValid(const char* who, const Scene* s, const RaylibAMDLi
 		return false;
 	}
 	if (!std::isfinite(p->time)) { Log("%s: the time is not finite", who); return false; }
-	const RaylibAMDGatherParams& g = p->gather;
-	prm.maxPathLength = g.maxPathLength; prm.rayTMin = g.rayTMin; prm.sampleFirst = g.sampleFirst; prm.sampleCount = g.sampleCount; prm.skipDraws = g.skipDraws;
+	prm = RadianceParamsOf(p->gather);
 	prm.timeMin = prm.timeMax = p->time;
-	return RadianceParamsValid(who, s, &prm) && GatherKindValid(who, &g);
+	return RadianceParamsValid(who, s, &prm) && GatherKindValid(who, &p->gather);
 }
 static int64_t LightmapPointsInternal(const char* who, SceneHandle sh, const RaylibAMDLightmapParams* params, const float* uv, RaylibAMDGatherPoint* outPoints, uint32_t* outTexel,
                                       int64_t capacity, bool device)
@@ -1089,60 +1081,68 @@ static bool LightmapFilterValid(const char* who, const RaylibAMDLightmapFilterPa
 		if (!(std::isfinite(sigma) && sigma >= 1e-3f && sigma <= 1e3f)) { Log("%s: a filter sigma (%g) is not finite or outside [1e-3, 1e3]", who, sigma); return false; }
 	return true;
 }
-// filtered: the entry takes a filter (checked here); in: RaylibAMD_FilterLightmap's atlas (wantIn: the entry takes one)
+// What a bake entry takes beside the atlas' arguments: a filter, the filter's input atlas, adaptive parameters (takes*: the entry has the argument, and a null
+// pointer is refused), with the pointers it was given
+struct BakeEntry {
+	bool takesFilter, takesIn, takesAdaptive;
+	const RaylibAMDLightmapFilterParams* filter; const float* in; const RaylibAMDGatherAdaptiveParams* adaptive; uint32_t* outSamples;
+	static BakeEntry Plain() { return { false, false, false, nullptr, nullptr, nullptr, nullptr }; }
+	static BakeEntry Filtered(const RaylibAMDLightmapFilterParams* filter) { return { true, false, false, filter, nullptr, nullptr, nullptr }; }
+	static BakeEntry FilterOf(const RaylibAMDLightmapFilterParams* filter, const float* in) { return { true, true, false, filter, in, nullptr, nullptr }; }
+	static BakeEntry Adaptive(const RaylibAMDGatherAdaptiveParams* adaptive, uint32_t* outSamples) { return { false, false, true, nullptr, nullptr, adaptive, outSamples }; }
+};
 static int32_t BakeLightmapInternal(const char* who, SceneHandle sh, const RaylibAMDLightmapParams* params, const float* uv, float* out, uint8_t* outCoverage, bool hostMem, void* stream,
-                                    bool filtered = false, const RaylibAMDLightmapFilterParams* filter = nullptr, bool wantIn = false, const float* in = nullptr,
-                                    bool wantAdaptive = false, const RaylibAMDGatherAdaptiveParams* adaptive = nullptr, uint32_t* outSamples = nullptr)
+                                    const BakeEntry& e)
 {
 	Scene* s = (Scene*)sh;
 	int32_t triFirst = 0, triCount = 0; RaylibAMDRadianceParams prm;
-	if (!out || (wantIn && !in)) { Log("%s: null argument", who); return 0; }
+	if (!out || (e.takesIn && !e.in)) { Log("%s: null argument", who); return 0; }
 	if (!LightmapArgsValid(who, s, params, triFirst, triCount, prm)) return 0;
-	if (filtered && !LightmapFilterValid(who, filter)) return 0;
-	if (wantAdaptive && !GatherAdaptiveValid(who, adaptive, prm.sampleCount)) return 0;
+	if (e.takesFilter && !LightmapFilterValid(who, e.filter)) return 0;
+	if (e.takesAdaptive && !GatherAdaptiveValid(who, e.adaptive, prm.sampleCount)) return 0;
 	if (!DeviceAvailable()) return 0;
 	if (!PreparePathScene(who, s, prm, 1)) return 0;
 	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
-	if (!DeviceBakeLightmap(*s, *params, triFirst, triCount, prm, CurrentSeed(), uv, out, outCoverage, hostMem, stream, stats, filter, in, adaptive, outSamples)) return 0;
+	if (!DeviceBakeLightmap(who, *s, *params, triFirst, triCount, prm, CurrentSeed(), uv, out, outCoverage, hostMem, stream, stats, e.filter, e.in, e.adaptive, e.outSamples)) return 0;
 	if (!stream) ReportOwnStats(stats);
 	return 1;
 }
 int32_t RaylibAMD_BakeLightmap(SceneHandle sh, const RaylibAMDLightmapParams* params, const float* uv, float* out, uint8_t* outCoverage)
 {
-	return BakeLightmapInternal("RaylibAMD_BakeLightmap", sh, params, uv, out, outCoverage, true, nullptr);
+	return BakeLightmapInternal("RaylibAMD_BakeLightmap", sh, params, uv, out, outCoverage, true, nullptr, BakeEntry::Plain());
 }
 int32_t RaylibAMD_BakeLightmapDevice(SceneHandle sh, const RaylibAMDLightmapParams* params, const float* uv, float* out, uint8_t* outCoverage, void* stream)
 {
-	return BakeLightmapInternal("RaylibAMD_BakeLightmapDevice", sh, params, uv, out, outCoverage, false, stream);
+	return BakeLightmapInternal("RaylibAMD_BakeLightmapDevice", sh, params, uv, out, outCoverage, false, stream, BakeEntry::Plain());
 }
 int32_t RaylibAMD_BakeLightmapAdaptive(SceneHandle sh, const RaylibAMDLightmapParams* params, const RaylibAMDGatherAdaptiveParams* adaptive, const float* uv, float* out,
                                        uint8_t* outCoverage, uint32_t* outSamples)
 {
-	return BakeLightmapInternal("RaylibAMD_BakeLightmapAdaptive", sh, params, uv, out, outCoverage, true, nullptr, false, nullptr, false, nullptr, true, adaptive, outSamples);
+	return BakeLightmapInternal("RaylibAMD_BakeLightmapAdaptive", sh, params, uv, out, outCoverage, true, nullptr, BakeEntry::Adaptive(adaptive, outSamples));
 }
 int32_t RaylibAMD_BakeLightmapAdaptiveDevice(SceneHandle sh, const RaylibAMDLightmapParams* params, const RaylibAMDGatherAdaptiveParams* adaptive, const float* uv, float* out,
                                              uint8_t* outCoverage, uint32_t* outSamples, void* stream)
 {
-	return BakeLightmapInternal("RaylibAMD_BakeLightmapAdaptiveDevice", sh, params, uv, out, outCoverage, false, stream, false, nullptr, false, nullptr, true, adaptive, outSamples);
+	return BakeLightmapInternal("RaylibAMD_BakeLightmapAdaptiveDevice", sh, params, uv, out, outCoverage, false, stream, BakeEntry::Adaptive(adaptive, outSamples));
 }
 int32_t RaylibAMD_BakeLightmapFiltered(SceneHandle sh, const RaylibAMDLightmapParams* params, const RaylibAMDLightmapFilterParams* filter, const float* uv, float* out, uint8_t* outCoverage)
 {
-	return BakeLightmapInternal("RaylibAMD_BakeLightmapFiltered", sh, params, uv, out, outCoverage, true, nullptr, true, filter);
+	return BakeLightmapInternal("RaylibAMD_BakeLightmapFiltered", sh, params, uv, out, outCoverage, true, nullptr, BakeEntry::Filtered(filter));
 }
 int32_t RaylibAMD_BakeLightmapFilteredDevice(SceneHandle sh, const RaylibAMDLightmapParams* params, const RaylibAMDLightmapFilterParams* filter, const float* uv, float* out,
                                              uint8_t* outCoverage, void* stream)
 {
-	return BakeLightmapInternal("RaylibAMD_BakeLightmapFilteredDevice", sh, params, uv, out, outCoverage, false, stream, true, filter);
+	return BakeLightmapInternal("RaylibAMD_BakeLightmapFilteredDevice", sh, params, uv, out, outCoverage, false, stream, BakeEntry::Filtered(filter));
 }
 int32_t RaylibAMD_FilterLightmap(SceneHandle sh, const RaylibAMDLightmapParams* params, const RaylibAMDLightmapFilterParams* filter, const float* uv, const float* in, float* out,
                                  uint8_t* outCoverage)
 {
-	return BakeLightmapInternal("RaylibAMD_FilterLightmap", sh, params, uv, out, outCoverage, true, nullptr, true, filter, true, in);
+	return BakeLightmapInternal("RaylibAMD_FilterLightmap", sh, params, uv, out, outCoverage, true, nullptr, BakeEntry::FilterOf(filter, in));
 }
 int32_t RaylibAMD_FilterLightmapDevice(SceneHandle sh, const RaylibAMDLightmapParams* params, const RaylibAMDLightmapFilterParams* filter, const float* uv, const float* in, float* out,
                                        uint8_t* outCoverage, void* stream)
 {
-	return BakeLightmapInternal("RaylibAMD_FilterLightmapDevice", sh, params, uv, out, outCoverage, false, stream, true, filter, true, in);
+	return BakeLightmapInternal("RaylibAMD_FilterLightmapDevice", sh, params, uv, out, outCoverage, false, stream, BakeEntry::FilterOf(filter, in));
 }
 int32_t RaylibAMD_FilterLightmapHost(int32_t width, int32_t height, int32_t kind, const RaylibAMDLightmapFilterParams* filter, const RaylibAMDGatherPoint* points, const uint32_t* texel,
                                      int64_t count, const float* values, float* outValues)

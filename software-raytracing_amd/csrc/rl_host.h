@@ -275,13 +275,12 @@ bool DeviceTraceRadiance(Scene& scene, const RaylibAMDRadianceParams& prm, uint6
 constexpr uint64_t RL_GATHER_SAMPLE_BUDGET = 256ull << 20;
 constexpr uint64_t RL_GATHER_MAX_SLOTS = 1ull << 28;
 constexpr uint64_t RL_GATHER_TIMED = 4096;
-bool DeviceGather(Scene& scene, int32_t kind, const RaylibAMDRadianceParams& prm, uint64_t seed, const void* points, int32_t n, float* out, bool hostMem, void* stream,
-                  RaylibAMDStats& stats);
-// RaylibAMD_GatherAdaptive (hostMem) and RaylibAMD_GatherAdaptiveDevice: DeviceGather in passes with per-point stopping (statements A1 to A5); prm.sampleCount is the
-// cap, A is valid and gives at most RL_GATHER_ADAPTIVE_MAX_PASSES passes.  outSamples may be null; memory as out's.  With a stream the call waits for it once per pass.
+// With A, RaylibAMD_GatherAdaptive (hostMem) and RaylibAMD_GatherAdaptiveDevice: the gather in passes with per-point stopping (statements A1 to A5); prm.sampleCount
+// is the cap, A is valid and gives at most RL_GATHER_ADAPTIVE_MAX_PASSES passes.  outSamples (with A only) may be null; memory as out's.  With a stream the call waits
+// for it once per pass.
 constexpr uint32_t RL_GATHER_ADAPTIVE_MAX_PASSES = 4096;
-bool DeviceGatherAdaptive(Scene& scene, int32_t kind, const RaylibAMDRadianceParams& prm, const RaylibAMDGatherAdaptiveParams& A, uint64_t seed, const void* points, int32_t n,
-                          float* out, uint32_t* outSamples, bool hostMem, void* stream, RaylibAMDStats& stats);
+bool DeviceGather(Scene& scene, int32_t kind, const RaylibAMDRadianceParams& prm, uint64_t seed, const void* points, int32_t n, float* out, bool hostMem, void* stream,
+                  RaylibAMDStats& stats, const RaylibAMDGatherAdaptiveParams* A = nullptr, uint32_t* outSamples = nullptr);
 // RaylibAMD_GatherCompactTest: the compaction behind a pass on uploaded copies, launched as a pass launches it; the ABI checked the arguments (live strictly
 // ascending below numPoints).  false without a device or memory; outputs are written only on success.
 bool DeviceGatherCompactTest(const uint32_t* live, uint32_t numLive, const uint8_t* stopped, const RaylibAMDGatherPoint* points, uint32_t numPoints,
@@ -294,12 +293,13 @@ int64_t LightmapPointsHost(const Scene& scene, const RaylibAMDLightmapParams& P,
 // DeviceLightmapPoints: the raster stages on rank 0's device (rl_lightmap.hip's kernels), uv and the outputs in host memory; the count, or -1.
 int64_t DeviceLightmapPoints(Scene& scene, const RaylibAMDLightmapParams& P, int32_t triFirst, int32_t triCount, const float* uv,
                              RaylibAMDGatherPoint* outPoints, uint32_t* outTexel, int64_t capacity);
-// DeviceBakeLightmap: raster, gather, scatter, dilation.  hostMem: uv / out / outCoverage in host memory (stream is null), else device pointers; stream as DeviceGather's.
+// DeviceBakeLightmap: raster, gather, scatter, dilation.  who: the entry's name in the log.  hostMem: uv / out / outCoverage in host memory (stream is null), else
+// device pointers; stream as DeviceGather's.
 // filter (may be null; checked by the ABI): statement F between the gather and the scatter.  in (with a filter only; memory as out's, may be out): the covered
 // texels take their values from that atlas instead of a gather (RaylibAMD_FilterLightmap).
-// adaptive (may be null; checked by the ABI; without filter and in): statement 7 is DeviceGatherAdaptive's passes, and outSamples (may be null; memory as out's)
+// adaptive (may be null; checked by the ABI; without filter and in): statement 7 is the adaptive DeviceGather's passes, and outSamples (may be null; memory as out's)
 // receives the atlas of the texels' sample counts.
-bool DeviceBakeLightmap(Scene& scene, const RaylibAMDLightmapParams& P, int32_t triFirst, int32_t triCount, const RaylibAMDRadianceParams& prm, uint64_t seed,
+bool DeviceBakeLightmap(const char* who, Scene& scene, const RaylibAMDLightmapParams& P, int32_t triFirst, int32_t triCount, const RaylibAMDRadianceParams& prm, uint64_t seed,
                         const float* uv, float* out, uint8_t* outCoverage, bool hostMem, void* stream, RaylibAMDStats& stats,
                         const RaylibAMDLightmapFilterParams* filter = nullptr, const float* in = nullptr,
                         const RaylibAMDGatherAdaptiveParams* adaptive = nullptr, uint32_t* outSamples = nullptr);

@@ -11,7 +11,8 @@
 //   rl_query.hip         k_query (RaylibAMD_TraceRays): beside the render kernels it would change how the walks they share are inlined into those
 //   rl_radiance.hip      k_radiance (RaylibAMD_TraceRadiance): the same reason, towards the render and the query kernels alike
 //   rl_gather.hip        k_gather (RaylibAMD_Gather: rl_k_radiance.inl's twin, the generator instances of its loop) and k_gather_resolve: beside k_radiance they would be
-//                        more callers of the walks and the shading it inlines
+//                        more callers of the walks and the shading it inlines.  k_gather_resolve and k_gather_adaptive_resolve are one source, rl_k_gather_resolve.inl,
+//                        which each of the two units includes (RL_GATHER_ADAPTIVE 0 / 1)
 //   rl_gather_adaptive.hip  k_gather_adaptive_resolve, k_gather_compact_*, k_gather_scatter_counts (RaylibAMD_GatherAdaptive): behind the unchanged k_gather; apart
 //                        from rl_gather.hip so that its kernels stay the code they are
 //   rl_lightmap.hip      k_lm_*: the lightmap rasteriser, its scans and the atlas stages (RaylibAMD_BakeLightmap); no walk, no shading

@@ -4,7 +4,7 @@
 //   rl_rt_scene.hip   a flattened scene (rl_scene.cc FlattenScene) to every device, its sky and wide trees; images: read-back, RGB dump, post-processing
 //   rl_rt_frame.hip   kernel selection and the one enqueue path of every render (EnqueueFrame), a rank's one-view render, a batch of views
 //   rl_rt_render.hip  whole frames over N ranks (gather, scatter, two frames in flight), DeviceRender, progressive sessions
-//   rl_rt_rays.hip    caller rays: DeviceTraceRays, DeviceTraceRadiance, DeviceGather, DeviceGatherAdaptive
+//   rl_rt_rays.hip    caller rays: DeviceTraceRays, DeviceTraceRadiance, DeviceGather (plain and adaptive: one driver, GatherLocked)
 //   rl_rt_lightmap.hip  lightmaps: DeviceLightmapPoints, DeviceBakeLightmap (the raster stages, then DeviceGather's body or the caller's atlas, the filter, the atlas stages)
 //   rl_rt_hooks.hip   test hooks
 //
@@ -194,7 +194,7 @@ struct RankCtx {
 	DevBuf<float4> gSamples;
 	DevBuf<float> gAcc;
 	std::vector<hipEvent_t> gEv;
-	// an adaptive gather's state between its passes (GatherAdaptiveLocked), behind the same event: the sums and the two moments per point of the call, the stop
+	// an adaptive gather's state between its passes (GatherLocked with adaptive parameters), behind the same event: the sums and the two moments per point of the call, the stop
 	// flags, a host call's sample counts, the two live lists and the two arrays of live points' records of the compaction's ping-pong, the tiles' counts with
 	// the live count behind them, and the pinned word that count is read back through
 	DevBuf<float> gaState;
@@ -261,11 +261,10 @@ bool ReadbackLocked(Image& img);                       // device copy -> img.rgb
 bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRender& pend, ProgressiveSession* prog = nullptr);   // rl_rt_frame.hip
 bool FinishRender(RankCtx& R, PendingRender& pend, RaylibAMDStats& stats);
 bool OnDevice(const void* p, int device);              // rl_rt_rays.hip: p is memory of that device
+// DeviceGather behind its entry; R's device is current.  A (null: the plain gather): statements A1 to A5 in passes, and outSamples (may be null) is host memory
+// with hostMem, else device memory.
 bool GatherLocked(Scene& sc, RankCtx& R, int32_t kind, const RaylibAMDRadianceParams& prm, uint64_t seed, const void* points, int32_t n, float* out, bool hostMem, void* stream,
-                  std::chrono::steady_clock::time_point t0, RaylibAMDStats& stats);   // DeviceGather behind its entry; R's device is current
-// DeviceGatherAdaptive behind its entry, as GatherLocked: statements A1 to A5 in passes.  outSamples (may be null) is host memory with hostMem, else device memory.
-bool GatherAdaptiveLocked(Scene& sc, RankCtx& R, int32_t kind, const RaylibAMDRadianceParams& prm, const RaylibAMDGatherAdaptiveParams& A, uint64_t seed, const void* points,
-                          int32_t n, float* out, uint32_t* outSamples, bool hostMem, void* stream, std::chrono::steady_clock::time_point t0, RaylibAMDStats& stats);
+                  std::chrono::steady_clock::time_point t0, RaylibAMDStats& stats, const RaylibAMDGatherAdaptiveParams* A = nullptr, uint32_t* outSamples = nullptr);
 // the compaction behind a pass (rl_gather_adaptive.hip), enqueued on st: the entries of live (null: the identity) whose points have not stopped into outLive, their
 // records from slot i of points into outPoints, the count into tiles[numTiles] (tiles: ceil(numLive / RL_GATHER_COMPACT_TILE) + 1 words) and from there into *countHost (pinned)
 bool EnqueueGatherCompact(const uint32_t* live, uint32_t numLive, const uint8_t* stopped, const float4* points, uint32_t* outLive, float4* outPoints, uint32_t* tiles,

@@ -128,7 +128,7 @@ bool DeviceProgressiveCompactTest(const uint32_t* live, uint32_t numLive, const 
 	return ok;
 }
 
-// The live set of an adaptive gather after a pass, from arrays of the caller's.  The launches are GatherAdaptiveLocked's (EnqueueGatherCompact on rank 0's stream): the
+// The live set of an adaptive gather after a pass, from arrays of the caller's.  The launches are an adaptive GatherLocked's (EnqueueGatherCompact on rank 0's stream): the
 // live points' records go up contiguous, record i beside live[i], as a pass holds them.  The output buffers on the device have numLive entries -- the kernels write
 // count <= numLive of them.
 bool DeviceGatherCompactTest(const uint32_t* live, uint32_t numLive, const uint8_t* stopped, const RaylibAMDGatherPoint* points, uint32_t numPoints,

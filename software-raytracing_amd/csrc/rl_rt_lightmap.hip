@@ -4,7 +4,7 @@
 // on the device, and puts the scatter, the dilation's passes and the copies into the caller's memory behind it, on the call's stream.  A filtered bake
 // (RaylibAMD_BakeLightmapFiltered) puts statement F's iterations (rl_lightmap_filter.hip) between the gather and the scatter, on the points' values in compacted
 // form; RaylibAMD_FilterLightmap takes those values from the caller's atlas instead of a gather; RaylibAMD_BakeLightmapAdaptive gathers them in passes with
-// per-texel stopping (GatherAdaptiveLocked) and scatters the texels' sample counts into an atlas of their own.  The scratch is the rank's (rl_rt.h RankCtx lm*: the raster's
+// per-texel stopping (GatherLocked with the adaptive parameters) and scatters the texels' sample counts into an atlas of their own.  The scratch is the rank's (rl_rt.h RankCtx lm*: the raster's
 // records, counts and maps, the points, their texels and values, the filter's second array of values, the two atlases and coverage maps), ordered by the
 // radiance calls' event: a call waits for it before its first kernel and records it behind its last.
 #include "rl_rt.h"
@@ -167,7 +167,7 @@ static bool EnqueueTake(RankCtx& R, uint32_t nTex, const float* in, bool hostMem
 	return true;
 }
 
-bool DeviceBakeLightmap(Scene& sc, const RaylibAMDLightmapParams& P, int32_t triFirst, int32_t triCount, const RaylibAMDRadianceParams& prm, uint64_t seed,
+bool DeviceBakeLightmap(const char* who, Scene& sc, const RaylibAMDLightmapParams& P, int32_t triFirst, int32_t triCount, const RaylibAMDRadianceParams& prm, uint64_t seed,
                         const float* uv, float* out, uint8_t* outCoverage, bool hostMem, void* stream, RaylibAMDStats& stats,
                         const RaylibAMDLightmapFilterParams* filter, const float* in, const RaylibAMDGatherAdaptiveParams* adaptive, uint32_t* outSamples)
 {
@@ -176,9 +176,6 @@ bool DeviceBakeLightmap(Scene& sc, const RaylibAMDLightmapParams& P, int32_t tri
 	if (!EnsureRuntime()) return false;
 	RankCtx& R = Rank0();
 	HIP_OK(hipSetDevice(R.device));
-	const char* who = adaptive ? (hostMem ? "RaylibAMD_BakeLightmapAdaptive" : "RaylibAMD_BakeLightmapAdaptiveDevice")
-	                : in ? (hostMem ? "RaylibAMD_FilterLightmap" : "RaylibAMD_FilterLightmapDevice") : !filter ? (hostMem ? "RaylibAMD_BakeLightmap" : "RaylibAMD_BakeLightmapDevice")
-	                     : (hostMem ? "RaylibAMD_BakeLightmapFiltered" : "RaylibAMD_BakeLightmapFilteredDevice");
 	const bool sphere = P.gather.kind == RAYLIB_AMD_GATHER_SH9;
 	const uint32_t C = sphere ? 27u : 4u, nTex = (uint32_t)P.width * (uint32_t)P.height;
 	if (!hostMem) {
@@ -205,17 +202,15 @@ bool DeviceBakeLightmap(Scene& sc, const RaylibAMDLightmapParams& P, int32_t tri
 	if (adaptive && outSamples && !R.lmSamples.Grow(std::max<size_t>(1, (size_t)r.count) * sizeof(uint32_t))) return false;
 	const hipStream_t st = stream ? (hipStream_t)stream : R.stream;
 	bool ok = true;
-	if (adaptive) {
-		// statement 7 as A1 to A5: DeviceGatherAdaptive's body on the points; it returns with the last pass complete, a synchronous call with its stats as well
-		if (!GatherAdaptiveLocked(sc, R, P.gather.kind, prm, *adaptive, seed, R.lmPoints.ptr, (int32_t)r.count, R.lmValues.ptr, outSamples ? R.lmSamples.ptr : nullptr, false, stream, t0, stats)) return false;
-		if (outSamples) {
+	if (!in) {
+		// statement 7: DeviceGather's body on the points, on the call's stream -- with `adaptive` as A1 to A5 --; a synchronous call returns from it with the gather's
+		// stats and an idle stream, an adaptive one with the last pass complete
+		if (!GatherLocked(sc, R, P.gather.kind, prm, seed, R.lmPoints.ptr, (int32_t)r.count, R.lmValues.ptr, false, stream, t0, stats, adaptive, adaptive && outSamples ? R.lmSamples.ptr : nullptr)) return false;
+		if (adaptive && outSamples) {
 			// the counts through the ranks into their atlas, undilated: 0 where no point is
 			hipLaunchKernelGGL(k_gather_scatter_counts, dim3(BlocksFor(nTex)), dim3(RL_BLOCK), 0, st, (const uint32_t*)R.lmRank.ptr, (const uint32_t*)R.lmSamples.ptr, nTex, R.lmSampleAtlas.ptr);
 			HIP_TRY(hipGetLastError());
 		}
-	} else if (!in) {
-		// statement 7: DeviceGather's body on the points, on the call's stream; a synchronous call returns from it with the gather's stats and an idle stream
-		if (!GatherLocked(sc, R, P.gather.kind, prm, seed, R.lmPoints.ptr, (int32_t)r.count, R.lmValues.ptr, false, stream, t0, stats)) return false;
 	} else {
 		// ... or the caller's atlas.  (The raster waited for the scratch's event and for its own stream: nothing else holds the scratch now.)
 		memset(&stats, 0, sizeof(stats));

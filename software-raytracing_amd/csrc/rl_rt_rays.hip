@@ -5,7 +5,9 @@
 // discipline of its scratch: a ring of ray counters with an event per slot for the queries, one counter and one path stack ordered by radEv for radiance.
 // A gather is a radiance call with another generator: it shares that call's preparation (BeginPathCall, PathGrid), its counter, stack and event chain, and adds
 // the sample buffer and the per-point sums between its launches.  An adaptive gather (RaylibAMD_GatherAdaptive) is that gather in passes over a shrinking,
-// compacted set of live points: the same trace kernel, a resolve that also decides which points stop, and the compaction behind each pass.
+// compacted set of live points: the same trace kernel, a resolve that also decides which points stop, and the compaction behind each pass.  Both are one
+// driver (GatherLocked): one prologue, one launch -- counter, event pair, k_gather, the launch's resolve --, one tail; a plain call loops over its cut's launches,
+// an adaptive call over its passes.
 #include "rl_rt.h"
 
 namespace rl {
@@ -253,90 +255,7 @@ bool DeviceTraceRadiance(Scene& sc, const RaylibAMDRadianceParams& prm, uint64_t
 	return FinishSync(R, st, { { hostMem ? out : nullptr, dOut, outBytes } }, t0, stats);
 }
 
-// RaylibAMD_Gather: n points x prm.sampleCount samples as the launches of rl_plan.cc PlanGatherCut -- sample ranges of all the points while one sample of each
-// fits the sample buffer, point ranges too when not -- each followed by its resolve.  The sums of a point range carry from launch to launch in gAcc, so the
-// sum's order does not depend on how the call was cut.  The loop runs over the launch index, 64-bit, and ends at the cut's count.
-bool DeviceGather(Scene& sc, int32_t kind, const RaylibAMDRadianceParams& prm, uint64_t seed, const void* points, int32_t n, float* out, bool hostMem, void* stream,
-                  RaylibAMDStats& stats)
-{
-	const auto t0 = std::chrono::steady_clock::now();
-	std::lock_guard<std::mutex> lk(Rt().lock);
-	if (!EnsureRuntime()) return false;
-	RankCtx& R = Rank0();
-	HIP_OK(hipSetDevice(R.device));
-	return GatherLocked(sc, R, kind, prm, seed, points, n, out, hostMem, stream, t0, stats);
-}
-// ... the call behind its locked entry: the runtime lock is held and R's device is current.  A lightmap bake (rl_rt_lightmap.hip) enters here with its points
-// on the device.
-bool GatherLocked(Scene& sc, RankCtx& R, int32_t kind, const RaylibAMDRadianceParams& prm, uint64_t seed, const void* points, int32_t n, float* out, bool hostMem, void* stream,
-                  std::chrono::steady_clock::time_point t0, RaylibAMDStats& stats)
-{
-	const RenderKnobs knobs = ReadRenderKnobs();
-	const bool sphere = kind == RAYLIB_AMD_GATHER_SH9;
-	const uint32_t outFloats = sphere ? 27u : 4u, sums = sphere ? 27u : 3u;
-	PathCall U;
-	if (!BeginPathCall("RaylibAMD_Gather", "RaylibAMD_GatherDevice", "points", sc, R, knobs, points, out, sphere ? 3u : 15u, n, hostMem, stream, U, stats)) return false;
-	if (n == 0) return true;
-	const hipStream_t st = U.st;
-	const GatherKernel kernel = sphere ? GatherKernelOfKind<RL_GEN_SPHERE>(U.plan) : GatherKernelOfKind<RL_GEN_HEMISPHERE>(U.plan);
-	const GatherResolveKernel resolve = sphere ? (GatherResolveKernel)k_gather_resolve<RL_GEN_SPHERE> : (GatherResolveKernel)k_gather_resolve<RL_GEN_HEMISPHERE>;
-	// the cut (rl_plan.cc PlanGatherCut): the first launch is the largest, so its grid -- and the path stack of that grid -- serves every launch of the call; a
-	// smaller launch on it leaves waves that find the counter drained and end
-	const uint32_t N = (uint32_t)n;
-	const GatherCut cut = PlanGatherCut(N, prm.sampleCount, sphere, knobs);
-	const uint64_t slotBytes = (sphere ? 2u : 1u) * sizeof(float4);
-	if (!R.gSamples.Grow((size_t)cut.pointsPer * cut.samplesPer * slotBytes)) return false;   // (as the path stack: growing waits for the device)
-	if (cut.sampleRanges > 1 && !R.gAcc.Grow((size_t)cut.pointsPer * sums * sizeof(float))) return false;
-	DRadianceParams Q = PathParams(prm, seed);
-	const uint32_t blocks = PathGrid(R, (const void*)kernel, (uint64_t)cut.pointsPer * cut.samplesPer, Q);
-	if (!blocks) return false;
-	// a synchronous call times its trace launches apart from the rest (stats.traceKernelMs), with an event pair per launch -- up to RL_GATHER_TIMED launches
-	const bool timed = U.sync && cut.launches <= RL_GATHER_TIMED;
-	if (timed) while (R.gEv.size() < 2 * cut.launches) { hipEvent_t e; HIP_OK(hipEventCreate(&e)); R.gEv.push_back(e); }
-	const float4* dPoints = (const float4*)points; float* dOut = out;
-	const size_t outBytes = (size_t)n * outFloats * sizeof(float);
-	if (hostMem) {
-		if (!StageRays(R, points, n, outBytes, st)) return false;
-		dPoints = R.qRays.ptr; dOut = (float*)R.qOut.ptr;
-	}
-	const DSceneView view = U.Cp->view;
-	const SkyRot skyRot = sc.device->skyRot;
-	if (R.radEvUsed) HIP_OK(hipStreamWaitEvent(st, R.radEv, 0));
-	if (U.sync && !BeginSync(R, st)) return false;
-	auto enqueue = [&](uint64_t k) -> bool {
-		const GatherLaunch L = GatherLaunchAt(cut, N, prm.sampleCount, k);
-		const uint32_t jobs = L.numPoints * L.numSamples;   // (<= slots <= RL_GATHER_MAX_SLOTS: a launch's jobs fit 32 bits with room for the counter's overshoot)
-		DGatherJobs J; J.pointFirst = L.pointFirst; J.numPoints = L.numPoints; J.sampleBase = L.sampleBase;
-		HIP_OK(hipMemsetAsync(R.radCounter.ptr, 0, sizeof(unsigned int), st));
-		if (timed) HIP_OK(hipEventRecord(R.gEv[2 * k], st));
-		hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RL_BLOCK), 0, st, view, skyRot, Q, dPoints, jobs, J, R.gSamples.ptr, R.radStack.ptr, R.radCounter.ptr,
-		                   U.sync ? R.qStats.ptr : nullptr);
-		HIP_OK(hipGetLastError());
-		if (timed) HIP_OK(hipEventRecord(R.gEv[2 * k + 1], st));
-		hipLaunchKernelGGL(resolve, dim3((L.numPoints + RL_BLOCK - 1) / RL_BLOCK), dim3(RL_BLOCK), 0, st, (const float4*)R.gSamples.ptr, L.numPoints, L.numSamples,
-		                   R.gAcc.ptr, dOut + (size_t)L.pointFirst * outFloats, (int)L.first, (int)L.last, prm.sampleCount);
-		HIP_OK(hipGetLastError());
-		return true;
-	};
-	bool ok = true;
-	for (uint64_t k = 0; ok && k < cut.launches; ++k) ok = enqueue(k);
-	// the event behind whatever was enqueued, a failed call's launches included: the next call on any stream must wait for them before it touches the scratch
-	const hipError_t evErr = hipEventRecord(R.radEv, st);
-	if (evErr == hipSuccess) R.radEvUsed = true;
-	else { Log("HIP error %s recording the gather's event", hipGetErrorName(evErr)); (void)hipStreamSynchronize(st); }   // (no event: the scratch is free again only once the stream is idle)
-	if (!ok || evErr != hipSuccess) return false;
-	if (!U.sync) return true;
-	if (!FinishSync(R, st, { { hostMem ? out : nullptr, dOut, outBytes } }, t0, stats)) return false;
-	stats.traceLaunches = (uint32_t)std::min<uint64_t>(cut.launches, 0xffffffffull);
-	if (timed) {
-		double traceMs = 0.0;
-		for (uint64_t k = 0; k < cut.launches; ++k) { float ms = 0.0f; HIP_OK(hipEventElapsedTime(&ms, R.gEv[2 * k], R.gEv[2 * k + 1])); traceMs += ms; }
-		stats.traceKernelMs = traceMs;
-	}
-	return true;
-}
-
-// ---- the adaptive gather (include/raylib_amd.h RaylibAMD_GatherAdaptive, statements A1 to A5; kernels of rl_gather_adaptive.hip) ----
+// ---- the gathers: RaylibAMD_Gather and RaylibAMD_GatherAdaptive (include/raylib_amd.h statements A1 to A5; kernels of rl_gather_adaptive.hip), one driver ----
 typedef void (*GatherAdaptiveResolveKernel)(const float4*, uint32_t, uint32_t, const uint32_t*, uint32_t, const GatherAdaptiveState, int, uint32_t, float*, uint32_t*);
 static uint32_t CompactTiles(uint32_t numLive) { return (uint32_t)(((uint64_t)numLive + RL_GATHER_COMPACT_TILE - 1) / RL_GATHER_COMPACT_TILE); }
 
@@ -354,52 +273,64 @@ bool EnqueueGatherCompact(const uint32_t* live, uint32_t numLive, const uint8_t*
 	return true;
 }
 
-bool DeviceGatherAdaptive(Scene& sc, int32_t kind, const RaylibAMDRadianceParams& prm, const RaylibAMDGatherAdaptiveParams& A, uint64_t seed, const void* points, int32_t n,
-                          float* out, uint32_t* outSamples, bool hostMem, void* stream, RaylibAMDStats& stats)
+bool DeviceGather(Scene& sc, int32_t kind, const RaylibAMDRadianceParams& prm, uint64_t seed, const void* points, int32_t n, float* out, bool hostMem, void* stream,
+                  RaylibAMDStats& stats, const RaylibAMDGatherAdaptiveParams* A, uint32_t* outSamples)
 {
 	const auto t0 = std::chrono::steady_clock::now();
 	std::lock_guard<std::mutex> lk(Rt().lock);
 	if (!EnsureRuntime()) return false;
 	RankCtx& R = Rank0();
 	HIP_OK(hipSetDevice(R.device));
-	return GatherAdaptiveLocked(sc, R, kind, prm, A, seed, points, n, out, outSamples, hostMem, stream, t0, stats);
+	return GatherLocked(sc, R, kind, prm, seed, points, n, out, hostMem, stream, t0, stats, A, outSamples);
 }
-// The call in passes.  Pass p traces the samples [(p - 1) * passSamples, n_p) of the live points: the launches of PlanGatherCut over (numLive, the pass's samples),
-// each k_gather launch followed by its adaptive resolve, which decides behind the pass's last sample range; then, unless the pass was the last, the compaction
-// into the other list and point array, and the wait for the live count.  The first pass reads the caller's points with no list (the identity).
-// Everything is allocated before anything is enqueued; the sample buffer, the grid and the path stack are sized for the largest launch any pass can make (no
-// launch holds more slots than the first pass's points x samples, nor more than the cut's slots per launch).
-bool GatherAdaptiveLocked(Scene& sc, RankCtx& R, int32_t kind, const RaylibAMDRadianceParams& prm, const RaylibAMDGatherAdaptiveParams& A, uint64_t seed, const void* points,
-                          int32_t n, float* out, uint32_t* outSamples, bool hostMem, void* stream, std::chrono::steady_clock::time_point t0, RaylibAMDStats& stats)
+// ... the call behind its locked entry: the runtime lock is held and R's device is current.  A lightmap bake (rl_rt_lightmap.hip) enters here with its points
+// on the device.
+// The plain call (A null): n points x prm.sampleCount samples as the launches of rl_plan.cc PlanGatherCut -- sample ranges of all the points while one sample of
+// each fits the sample buffer, point ranges too when not -- each k_gather launch followed by its resolve.  The sums of a point range carry from launch to launch
+// in gAcc, so the sum's order does not depend on how the call was cut.  The loop runs over the launch index, 64-bit, and ends at the cut's count.
+// The adaptive call (A given) runs in passes.  Pass p traces the samples [(p - 1) * passSamples, n_p) of the live points: the launches of PlanGatherCut over
+// (numLive, the pass's samples), each followed by the adaptive resolve, which decides behind the pass's last sample range; then, unless the pass was the last,
+// the compaction into the other list and point array, and the wait for the live count.  The first pass reads the caller's points with no list (the identity).
+// Everything is allocated before anything is enqueued; the sample buffer, the grid and the path stack are sized for the largest launch of the call.
+bool GatherLocked(Scene& sc, RankCtx& R, int32_t kind, const RaylibAMDRadianceParams& prm, uint64_t seed, const void* points, int32_t n, float* out, bool hostMem, void* stream,
+                  std::chrono::steady_clock::time_point t0, RaylibAMDStats& stats, const RaylibAMDGatherAdaptiveParams* A, uint32_t* outSamples)
 {
 	const RenderKnobs knobs = ReadRenderKnobs();
 	const bool sphere = kind == RAYLIB_AMD_GATHER_SH9;
 	const uint32_t outFloats = sphere ? 27u : 4u, sums = sphere ? 27u : 3u;
+	const char* api = A ? "RaylibAMD_GatherAdaptive" : "RaylibAMD_Gather";
+	const char* apiDevice = A ? "RaylibAMD_GatherAdaptiveDevice" : "RaylibAMD_GatherDevice";
 	PathCall U;
-	if (!BeginPathCall("RaylibAMD_GatherAdaptive", "RaylibAMD_GatherAdaptiveDevice", "points", sc, R, knobs, points, out, sphere ? 3u : 15u, n, hostMem, stream, U, stats)) return false;
+	if (!BeginPathCall(api, apiDevice, "points", sc, R, knobs, points, out, sphere ? 3u : 15u, n, hostMem, stream, U, stats)) return false;
 	if (!hostMem && n > 0 && outSamples && (!OnDevice(outSamples, R.device) || ((uintptr_t)outSamples & 3u) != 0)) {
-		Log("RaylibAMD_GatherAdaptiveDevice: outSamples is not 4-byte aligned memory of device %d", R.device);
+		Log("%s: outSamples is not 4-byte aligned memory of device %d", apiDevice, R.device);
 		return false;
 	}
 	if (n == 0) return true;
 	const hipStream_t st = U.st;
 	const GatherKernel kernel = sphere ? GatherKernelOfKind<RL_GEN_SPHERE>(U.plan) : GatherKernelOfKind<RL_GEN_HEMISPHERE>(U.plan);
-	const GatherAdaptiveResolveKernel resolve = sphere ? (GatherAdaptiveResolveKernel)k_gather_adaptive_resolve<RL_GEN_SPHERE>
-	                                                   : (GatherAdaptiveResolveKernel)k_gather_adaptive_resolve<RL_GEN_HEMISPHERE>;
+	const GatherResolveKernel resolve = sphere ? (GatherResolveKernel)k_gather_resolve<RL_GEN_SPHERE> : (GatherResolveKernel)k_gather_resolve<RL_GEN_HEMISPHERE>;
+	const GatherAdaptiveResolveKernel resolveAdaptive = sphere ? (GatherAdaptiveResolveKernel)k_gather_adaptive_resolve<RL_GEN_SPHERE>
+	                                                           : (GatherAdaptiveResolveKernel)k_gather_adaptive_resolve<RL_GEN_HEMISPHERE>;
 	const uint32_t N = (uint32_t)n, cap = prm.sampleCount;
-	const uint32_t perPass = std::min(A.passSamples, cap);
+	const uint32_t perPass = A ? std::min(A->passSamples, cap) : cap;
 	const uint32_t passes = (uint32_t)(((uint64_t)cap + perPass - 1) / perPass);   // (<= 4096: the ABI refused more)
-	// the slots of the largest launch: a cut's launch holds at most pointsPer x samplesPer <= the slots per launch (what a cut of very many points gives each launch)
-	const uint64_t slotsPer = PlanGatherCut(0xffffffffu, 1u, sphere, knobs).pointsPer;
-	const uint64_t maxSlots = std::min<uint64_t>(slotsPer, (uint64_t)N * perPass);
+	// the plain call's cut (rl_plan.cc PlanGatherCut): the first launch is the largest, so its grid -- and the path stack of that grid -- serves every launch of the
+	// call; a smaller launch on it leaves waves that find the counter drained and end.  No launch of an adaptive call holds more slots than the first pass's points x
+	// samples, nor more than the slots per launch (what a cut of very many points gives each launch)
+	const GatherCut cut = PlanGatherCut(N, cap, sphere, knobs);
+	const uint64_t maxSlots = A ? std::min<uint64_t>(PlanGatherCut(0xffffffffu, 1u, sphere, knobs).pointsPer, (uint64_t)N * perPass) : (uint64_t)cut.pointsPer * cut.samplesPer;
 	const uint64_t slotBytes = (sphere ? 2u : 1u) * sizeof(float4);
 	if (!R.gSamples.Grow((size_t)(maxSlots * slotBytes))) return false;   // (as the path stack: growing waits for the device)
-	if (!R.gaState.Grow((size_t)N * (sums + 2u) * sizeof(float)) || !R.gaStopped.Grow(N) || !R.gaHost.Grow(sizeof(uint32_t))) return false;
-	if (passes > 1) {
-		for (int k = 0; k < 2; ++k) if (!R.gaLive[k].Grow((size_t)N * sizeof(uint32_t)) || !R.gaPoints[k].Grow((size_t)N * 2 * sizeof(float4))) return false;
-		if (!R.gaTiles.Grow(((size_t)CompactTiles(N) + 1) * sizeof(uint32_t))) return false;
+	if (!A && cut.sampleRanges > 1 && !R.gAcc.Grow((size_t)cut.pointsPer * sums * sizeof(float))) return false;
+	if (A) {
+		if (!R.gaState.Grow((size_t)N * (sums + 2u) * sizeof(float)) || !R.gaStopped.Grow(N) || !R.gaHost.Grow(sizeof(uint32_t))) return false;
+		if (passes > 1) {
+			for (int k = 0; k < 2; ++k) if (!R.gaLive[k].Grow((size_t)N * sizeof(uint32_t)) || !R.gaPoints[k].Grow((size_t)N * 2 * sizeof(float4))) return false;
+			if (!R.gaTiles.Grow(((size_t)CompactTiles(N) + 1) * sizeof(uint32_t))) return false;
+		}
+		if (hostMem && outSamples && !R.gaCounts.Grow((size_t)N * sizeof(uint32_t))) return false;
 	}
-	if (hostMem && outSamples && !R.gaCounts.Grow((size_t)N * sizeof(uint32_t))) return false;
 	DRadianceParams Q = PathParams(prm, seed);
 	const uint32_t blocks = PathGrid(R, (const void*)kernel, maxSlots, Q);
 	if (!blocks) return false;
@@ -409,63 +340,76 @@ bool GatherAdaptiveLocked(Scene& sc, RankCtx& R, int32_t kind, const RaylibAMDRa
 		if (!StageRays(R, points, n, outBytes, st)) return false;
 		dPoints = R.qRays.ptr; dOut = (float*)R.qOut.ptr; if (outSamples) dCounts = R.gaCounts.ptr;
 	}
-	GatherAdaptiveState S;
-	S.sum = R.gaState.ptr; S.s1 = R.gaState.ptr + (size_t)N * sums; S.s2 = S.s1 + N; S.stopped = R.gaStopped.ptr;
-	S.numPoints = N; S.cap = cap; S.threshold = A.threshold; S.minSamples = A.minSamples;
+	GatherAdaptiveState S = {};
+	if (A) {
+		S.sum = R.gaState.ptr; S.s1 = R.gaState.ptr + (size_t)N * sums; S.s2 = S.s1 + N; S.stopped = R.gaStopped.ptr;
+		S.numPoints = N; S.cap = cap; S.threshold = A->threshold; S.minSamples = A->minSamples;
+	}
 	const DSceneView view = U.Cp->view;
 	const SkyRot skyRot = sc.device->skyRot;
 	if (R.radEvUsed) HIP_OK(hipStreamWaitEvent(st, R.radEv, 0));
 	if (U.sync && !BeginSync(R, st)) return false;
-	// a synchronous call times its trace launches with an event pair each, up to RL_GATHER_TIMED of them; the number of launches is known only as the passes go
-	bool timed = U.sync;
+	// a synchronous call times its trace launches apart from the rest (stats.traceKernelMs), with an event pair per launch -- up to RL_GATHER_TIMED launches: a
+	// plain call of more does not begin, an adaptive call, which knows its launches only as the passes go, stops when it gets there
+	bool timed = U.sync && (A || cut.launches <= RL_GATHER_TIMED);
 	uint64_t launches = 0;
-	bool ok = true;
-	HIP_TRY(hipMemsetAsync(R.gaState.ptr, 0, (size_t)N * (sums + 2u) * sizeof(float), st));   // +0 in every sum
-	HIP_TRY(hipMemsetAsync(R.gaStopped.ptr, 0, N, st));
-	const uint32_t* live = nullptr;   // the pass's list (null: the identity) and its points
-	const float4* passPoints = dPoints;
-	uint32_t numLive = N, done = 0;
-	for (uint32_t p = 1; ok && p <= passes && numLive; ++p) {
-		const uint32_t now = (uint32_t)std::min<uint64_t>(cap, (uint64_t)p * perPass), take = now - done;
-		const GatherCut cut = PlanGatherCut(numLive, take, sphere, knobs);
-		for (uint64_t k = 0; ok && k < cut.launches; ++k, ++launches) {
-			const GatherLaunch L = GatherLaunchAt(cut, numLive, take, k);
-			const uint32_t jobs = L.numPoints * L.numSamples;   // (<= maxSlots)
-			DGatherJobs J; J.pointFirst = L.pointFirst; J.numPoints = L.numPoints; J.sampleBase = done + L.sampleBase;
-			if (timed && launches >= RL_GATHER_TIMED) timed = false;
-			if (timed) while (ok && R.gEv.size() < 2 * (launches + 1)) { hipEvent_t e = nullptr; HIP_TRY(hipEventCreate(&e)); if (ok) R.gEv.push_back(e); }
-			if (!ok) break;
-			HIP_TRY(hipMemsetAsync(R.radCounter.ptr, 0, sizeof(unsigned int), st));
-			if (timed) HIP_TRY(hipEventRecord(R.gEv[2 * launches], st));
-			hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RL_BLOCK), 0, st, view, skyRot, Q, passPoints, jobs, J, R.gSamples.ptr, R.radStack.ptr, R.radCounter.ptr,
-			                   U.sync ? R.qStats.ptr : nullptr);
-			HIP_TRY(hipGetLastError());
-			if (timed) HIP_TRY(hipEventRecord(R.gEv[2 * launches + 1], st));
-			hipLaunchKernelGGL(resolve, dim3((L.numPoints + RL_BLOCK - 1) / RL_BLOCK), dim3(RL_BLOCK), 0, st, (const float4*)R.gSamples.ptr, L.numPoints, L.numSamples,
-			                   live, L.pointFirst, S, (int)L.last, now, dOut, dCounts);
-			HIP_TRY(hipGetLastError());
+	// one launch, L of the cut of `pts` (the pass's points, listed by `live`; its samples begin at `done` and end the point's first `now`), and its resolve
+	auto enqueue = [&](const float4* pts, const uint32_t* live, const GatherLaunch& L, uint32_t done, uint32_t now) -> bool {
+		const uint32_t jobs = L.numPoints * L.numSamples;   // (<= maxSlots <= RL_GATHER_MAX_SLOTS: a launch's jobs fit 32 bits with room for the counter's overshoot)
+		DGatherJobs J; J.pointFirst = L.pointFirst; J.numPoints = L.numPoints; J.sampleBase = done + L.sampleBase;
+		if (launches >= RL_GATHER_TIMED) timed = false;
+		if (timed) while (R.gEv.size() < 2 * (launches + 1)) { hipEvent_t e = nullptr; HIP_OK(hipEventCreate(&e)); R.gEv.push_back(e); }
+		HIP_OK(hipMemsetAsync(R.radCounter.ptr, 0, sizeof(unsigned int), st));
+		if (timed) HIP_OK(hipEventRecord(R.gEv[2 * launches], st));
+		hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RL_BLOCK), 0, st, view, skyRot, Q, pts, jobs, J, R.gSamples.ptr, R.radStack.ptr, R.radCounter.ptr,
+		                   U.sync ? R.qStats.ptr : nullptr);
+		HIP_OK(hipGetLastError());
+		if (timed) HIP_OK(hipEventRecord(R.gEv[2 * launches + 1], st));
+		const dim3 grid((L.numPoints + RL_BLOCK - 1) / RL_BLOCK);
+		if (A) {
+			hipLaunchKernelGGL(resolveAdaptive, grid, dim3(RL_BLOCK), 0, st, (const float4*)R.gSamples.ptr, L.numPoints, L.numSamples, live, L.pointFirst, S, (int)L.last, now, dOut, dCounts);
+		} else {
+			hipLaunchKernelGGL(resolve, grid, dim3(RL_BLOCK), 0, st, (const float4*)R.gSamples.ptr, L.numPoints, L.numSamples, R.gAcc.ptr, dOut + (size_t)L.pointFirst * outFloats,
+			                   (int)L.first, (int)L.last, cap);
 		}
-		done = now;
-		if (!ok) break;
-		if (p == passes) {
-			// every live point stopped at the cap; the call returns when the pass is complete
-			if (!U.sync) HIP_TRY(hipStreamSynchronize(st));
-			numLive = 0;
-			break;
+		HIP_OK(hipGetLastError());
+		++launches;
+		return true;
+	};
+	auto enqueueAll = [&]() -> bool {
+		if (!A) {
+			for (uint64_t k = 0; k < cut.launches; ++k) if (!enqueue(dPoints, nullptr, GatherLaunchAt(cut, N, cap, k), 0u, cap)) return false;
+			return true;
 		}
-		const int to = (int)(p & 1u);
-		ok = EnqueueGatherCompact(live, numLive, R.gaStopped.ptr, passPoints, R.gaLive[to].ptr, R.gaPoints[to].ptr, R.gaTiles.ptr, R.gaHost.ptr, st);
-		if (ok) HIP_TRY(hipStreamSynchronize(st));
-		if (ok) {
+		HIP_OK(hipMemsetAsync(R.gaState.ptr, 0, (size_t)N * (sums + 2u) * sizeof(float), st));   // +0 in every sum
+		HIP_OK(hipMemsetAsync(R.gaStopped.ptr, 0, N, st));
+		const uint32_t* live = nullptr;   // the pass's list (null: the identity) and its points
+		const float4* passPoints = dPoints;
+		uint32_t numLive = N, done = 0;
+		for (uint32_t p = 1; numLive; ++p) {
+			const uint32_t now = (uint32_t)std::min<uint64_t>(cap, (uint64_t)p * perPass), take = now - done;
+			const GatherCut pc = PlanGatherCut(numLive, take, sphere, knobs);
+			for (uint64_t k = 0; k < pc.launches; ++k) if (!enqueue(passPoints, live, GatherLaunchAt(pc, numLive, take, k), done, now)) return false;
+			done = now;
+			if (p == passes) {
+				// every live point stopped at the cap; the call returns when the pass is complete
+				if (!U.sync) HIP_OK(hipStreamSynchronize(st));
+				break;
+			}
+			const int to = (int)(p & 1u);
+			if (!EnqueueGatherCompact(live, numLive, R.gaStopped.ptr, passPoints, R.gaLive[to].ptr, R.gaPoints[to].ptr, R.gaTiles.ptr, R.gaHost.ptr, st)) return false;
+			HIP_OK(hipStreamSynchronize(st));
 			const uint32_t next = R.gaHost.ptr[0];
-			if (next > numLive) { Log("RaylibAMD_GatherAdaptive: the live set grew from %u to %u points", numLive, next); ok = false; break; }
+			if (next > numLive) { Log("RaylibAMD_GatherAdaptive: the live set grew from %u to %u points", numLive, next); return false; }
 			numLive = next; live = R.gaLive[to].ptr; passPoints = R.gaPoints[to].ptr;
 		}
-	}
+		return true;
+	};
+	const bool ok = enqueueAll();
 	// the event behind whatever was enqueued, a failed call's launches included: the next call on any stream must wait for them before it touches the scratch
 	const hipError_t evErr = hipEventRecord(R.radEv, st);
 	if (evErr == hipSuccess) R.radEvUsed = true;
-	else { Log("HIP error %s recording the gather's event", hipGetErrorName(evErr)); (void)hipStreamSynchronize(st); }
+	else { Log("HIP error %s recording the gather's event", hipGetErrorName(evErr)); (void)hipStreamSynchronize(st); }   // (no event: the scratch is free again only once the stream is idle)
 	if (!ok || evErr != hipSuccess) return false;
 	if (!U.sync) return true;
 	if (!FinishSync(R, st, { { hostMem ? out : nullptr, dOut, outBytes }, { hostMem ? outSamples : nullptr, dCounts, (size_t)n * sizeof(uint32_t) } }, t0, stats)) return false;

@@ -222,6 +222,27 @@ def test_several_launches(gpu_lib, cases, monkeypatch, kind):
         assert st.traceLaunches == launches > 1 and st.cameraSamples == 100 * 33, (batch, st.traceLaunches)
 
 
+@pytest.mark.parametrize("count", [33, 37, 41])
+def test_timing_of_many_launches(gpu_lib, cases, monkeypatch, count):
+    """RAYLIB_GATHER_BATCH=1 makes 100 x count launches.  Up to RL_GATHER_TIMED = 4096 of them the trace launches are timed apart: their sum lies below the
+    whole call's time, which holds the resolves and the gaps between launches too.  A call of more launches reports the whole span as its trace time."""
+    from raylib_amd import binding
+    ses, pts = cases["cutout_sky"]
+    pts = np.ascontiguousarray(pts[:100])
+    want = binding.gather(gpu_lib, ses.scene, pts, gc.IRRADIANCE, sample_count=count)
+    assert _stats(gpu_lib).traceLaunches == 1
+    monkeypatch.setenv("RAYLIB_GATHER_BATCH", "1")
+    got = binding.gather(gpu_lib, ses.scene, pts, gc.IRRADIANCE, sample_count=count)
+    st = _stats(gpu_lib)
+    print("count %d: traceLaunches %d, traceKernelMs %.6f, kernelMs %.6f, wallMs %.6f" % (count, st.traceLaunches, st.traceKernelMs, st.kernelMs, st.wallMs))
+    _same_bits(got, want, "%d samples, one pair per launch" % count)
+    assert st.traceLaunches == 100 * count and st.cameraSamples == 100 * count
+    if 100 * count <= 4096:
+        assert 0 < st.traceKernelMs < st.kernelMs <= st.wallMs
+    else:
+        assert st.traceKernelMs == st.kernelMs > 0
+
+
 def test_device_entry(gpu_lib, cases):
     """Torch tensors through the device entry: on a stream of torch's and on torch's default stream they give the host entry's bytes; two calls enqueued on two
     streams give the bytes of the same calls one after the other (the event chain orders them on the shared scratch); misaligned and host pointers are refused

@@ -351,6 +351,27 @@ def test_stats(gpu_lib, cases, reference, monkeypatch, batch):
         assert 0 < st.traceKernelMs <= st.kernelMs <= st.wallMs
 
 
+@pytest.mark.parametrize("count", [33, 41])
+def test_timing_of_many_launches(gpu_lib, cases, monkeypatch, count):
+    """One pass of `count` samples at threshold 0, cut by RAYLIB_GATHER_BATCH=1 into 100 x count launches.  Up to RL_GATHER_TIMED = 4096 of them the trace launches
+    are timed apart, and their sum lies below the whole call's time; a call that goes past the limit reports the whole span as its trace time."""
+    ses, pts = cases[OTHER]
+    pts = np.ascontiguousarray(pts[:100])
+    want_v, want_c = _adaptive(gpu_lib, ses, pts, gc.IRRADIANCE, 0.0, pass_samples=count, sample_count=count)
+    assert _stats(gpu_lib).traceLaunches == 1 and (want_c == count).all()
+    monkeypatch.setenv("RAYLIB_GATHER_BATCH", "1")
+    values, counts = _adaptive(gpu_lib, ses, pts, gc.IRRADIANCE, 0.0, pass_samples=count, sample_count=count)
+    st = _stats(gpu_lib)
+    print("count %d: traceLaunches %d, traceKernelMs %.6f, kernelMs %.6f, wallMs %.6f" % (count, st.traceLaunches, st.traceKernelMs, st.kernelMs, st.wallMs))
+    assert counts.tolist() == want_c.tolist()
+    _same_bits(values, want_v, "%d samples, one pair per launch" % count)
+    assert st.traceLaunches == 100 * count and st.cameraSamples == 100 * count
+    if 100 * count <= 4096:
+        assert 0 < st.traceKernelMs < st.kernelMs <= st.wallMs
+    else:
+        assert st.traceKernelMs == st.kernelMs > 0
+
+
 # ---- 7. the lightmap ----
 LM_W = LM_H = 32
 

@@ -9,12 +9,11 @@ bool DeviceRenderViews(Scene&, const RenderRequest&, const DCamera*, uint32_t, v
 bool DeviceClosestHit(Scene&, const float*, int32_t, float, void*) { return false; }
 bool DeviceTraceRays(Scene&, int32_t, const void*, int32_t, float, void*, int32_t*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceTraceRadiance(Scene&, const RaylibAMDRadianceParams&, uint64_t, const void*, int32_t, float*, bool, void*, RaylibAMDStats&) { return false; }
-bool DeviceGather(Scene&, int32_t, const RaylibAMDRadianceParams&, uint64_t, const void*, int32_t, float*, bool, void*, RaylibAMDStats&) { return false; }
+bool DeviceGather(Scene&, int32_t, const RaylibAMDRadianceParams&, uint64_t, const void*, int32_t, float*, bool, void*, RaylibAMDStats&, const RaylibAMDGatherAdaptiveParams*,
+                  uint32_t*) { return false; }
 int64_t DeviceLightmapPoints(Scene&, const RaylibAMDLightmapParams&, int32_t, int32_t, const float*, RaylibAMDGatherPoint*, uint32_t*, int64_t) { return -1; }
-bool DeviceBakeLightmap(Scene&, const RaylibAMDLightmapParams&, int32_t, int32_t, const RaylibAMDRadianceParams&, uint64_t, const float*, float*, uint8_t*, bool, void*, RaylibAMDStats&,
+bool DeviceBakeLightmap(const char*, Scene&, const RaylibAMDLightmapParams&, int32_t, int32_t, const RaylibAMDRadianceParams&, uint64_t, const float*, float*, uint8_t*, bool, void*, RaylibAMDStats&,
                         const RaylibAMDLightmapFilterParams*, const float*, const RaylibAMDGatherAdaptiveParams*, uint32_t*) { return false; }
-bool DeviceGatherAdaptive(Scene&, int32_t, const RaylibAMDRadianceParams&, const RaylibAMDGatherAdaptiveParams&, uint64_t, const void*, int32_t, float*, uint32_t*, bool, void*,
-                          RaylibAMDStats&) { return false; }
 bool DeviceGatherCompactTest(const uint32_t*, uint32_t, const uint8_t*, const RaylibAMDGatherPoint*, uint32_t, uint32_t*, RaylibAMDGatherPoint*, uint32_t*) { return false; }
 // rl_lightmap_filter.hip is a HIP unit too: its host restatement (RaylibAMD_FilterLightmapHost) is not part of this build
 bool FilterLightmapHost(int32_t, int32_t, int32_t, const RaylibAMDLightmapFilterParams&, const RaylibAMDGatherPoint*, const uint32_t*, int64_t, const float*, float*) { return false; }
