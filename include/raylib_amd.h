@@ -565,6 +565,10 @@ RAYLIB_API int32_t RaylibAMD_LastTracePlain(void);
 RAYLIB_API int32_t RaylibAMD_SceneLazyRefl(SceneHandle scene);
 /* 1 when the megakernel of the last path-traced render on this process was that lazy-reflectance instance (then RaylibAMD_LastTracePlain is 1 too), else 0. */
 RAYLIB_API int32_t RaylibAMD_LastTraceLazy(void);
+/* 1 when that lazy-reflectance launch was the instance's hit-queue form (k_trace_lazy_hitq: idle lanes take camera rays that have been traced already, so every
+ * lane enters the shading part with a hit; the same bits and the same work counters, RaylibAMDStats::waveTrips aside).  A lazy render with maxPathLength >= 1
+ * takes it; RAYLIB_HIT_QUEUE=0 keeps the ray-queue instance.  Else 0. */
+RAYLIB_API int32_t RaylibAMD_LastHitQueue(void);
 /* 1 when that lazy-reflectance launch kept a lit-sample mask (csrc/rl_lit_mask.h): samples that are all zero bits were neither stored nor summed, the same bits.
  * A one-view render that is not progressive takes it for launches of at most 256 samples per pixel, without a sun; RAYLIB_LIT_MASK=0 keeps every sample stored,
  * =1 takes the mask with a sun too.  Else 0. */
@@ -586,7 +590,7 @@ typedef struct RaylibAMDRenderPlan {
 	uint32_t batch, sampleCount, blocks, stackStride, jobChunk, heads, jobsPerHead, guideShift;
 	uint64_t jobs;
 	int32_t lazy;             /* the plain instance's lazy-reflectance form (k_trace_lazy + k_fold_lit); 0 for a batch of views, whose twin stays eager */
-	int32_t reserved;
+	int32_t hitQueue;         /* ... and of that, its hit-queue form (k_trace_lazy_hitq); the field was `reserved`, always 0 */
 } RaylibAMDRenderPlan;
 RAYLIB_API int32_t RaylibAMD_PlanRender(SceneHandle scene, const RendererSettings* settings, int32_t hasSky, int32_t numCUs, int32_t workgroupsPerCU, RaylibAMDRenderPlan* out);
 /* ---- several views of one scene in one megakernel launch (INTEGRATION.md "Several views") ---- */

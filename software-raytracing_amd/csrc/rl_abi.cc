@@ -1243,6 +1243,7 @@ int32_t RaylibAMD_SceneLazyRefl(SceneHandle sh)
 	return (s && s->finalized && SceneLazyRefl(*s)) ? 1 : 0;
 }
 int32_t RaylibAMD_LastTraceLazy(void) { return DeviceLastTraceLazy(); }
+int32_t RaylibAMD_LastHitQueue(void) { return DeviceLastHitQueue(); }
 int32_t RaylibAMD_LastLitMask(void) { return DeviceLastLitMask(); }
 int32_t RaylibAMD_PlanRender(SceneHandle sh, const RendererSettings* settings, int32_t hasSky, int32_t numCUs, int32_t workgroupsPerCU, RaylibAMDRenderPlan* out)
 {
@@ -1252,7 +1253,7 @@ int32_t RaylibAMD_PlanRender(SceneHandle sh, const RendererSettings* settings, i
 	const RenderKnobs knobs = ReadRenderKnobs();
 	const TracePlan t = PlanTrace(*s, *settings, hasSky != 0, knobs);
 	if (!t.ok) return -1;
-	out->pathTrace = t.pathTrace; out->stack = t.stack; out->prims = t.prims; out->poolK = t.poolK; out->tree = t.tree; out->lstack = t.lstack; out->lds = t.lds; out->plain = t.plain; out->lazy = t.lazy ? 1 : 0;
+	out->pathTrace = t.pathTrace; out->stack = t.stack; out->prims = t.prims; out->poolK = t.poolK; out->tree = t.tree; out->lstack = t.lstack; out->lds = t.lds; out->plain = t.plain; out->lazy = t.lazy ? 1 : 0; out->hitQueue = t.hitQueue ? 1 : 0;
 	out->pathsPerWave = t.pathsPerWave; out->treeWidth = t.treeWidth; out->nodeBytes = t.nodeBytes;
 	out->keepNodes4 = t.keepNodes4; out->keepNodes4f = t.keepNodes4f; out->eagerTree = t.eagerTree;
 	const uint32_t cells = ((settings->viewportWidth + 7) / 8) * ((settings->viewportHeight + 7) / 8);

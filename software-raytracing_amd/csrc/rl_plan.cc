@@ -26,7 +26,7 @@ RenderKnobs ReadRenderKnobs()
 	if (const char* e = getenv("RAYLIB_GUIDED")) k.guided = atoi(e);
 	if (const char* e = getenv("RAYLIB_BLOCKS_PER_CU")) k.blocksPerCU = std::max(0, atoi(e));
 	if (const char* e = getenv("RAYLIB_CULL_CELLS")) k.cullCells = atoi(e);
-	k.lazyRefl = flag("RAYLIB_LAZY_REFL");
+	k.lazyRefl = flag("RAYLIB_LAZY_REFL"); k.hitQueue = flag("RAYLIB_HIT_QUEUE");
 	if (const char* e = getenv("RAYLIB_LIT_LIST")) k.litList = std::max(0ll, atoll(e));
 	k.litMask = flag("RAYLIB_LIT_MASK");
 	if (const char* e = getenv("RAYLIB_QUERY_TREE")) { const int v = atoi(e); k.queryTree = (v == 2 || v == 4 || v == 8) ? v : 0; }
@@ -112,6 +112,10 @@ TracePlan Pick(const Scene& sc, const RendererSettings& st, bool hasSky, const R
 			// per-vertex guard passes (SceneLazyRefl; rl_dev_shade.h LazyVertexSafe), on paths short enough for the guard's bound on a direction's length.
 			// The same bits as the eager instance (measured: DESIGN.md section 5).  RAYLIB_LAZY_REFL=0 keeps the eager instance.
 			p.lazy = p.plain && k.lazyRefl != 0 && st.maxPathLength <= RL_LAZY_MAX_PATH && SceneLazyRefl(sc);
+			// ... and of that, the form whose idle lanes take camera rays that have been traced already, so that every lane enters the shading part with a hit
+			// (rl_k_trace_hitq.inl).  The same bits and the same work counters, waveTrips aside.  It traces a camera ray before its path has a depth to test: not
+			// with maxPathLength < 1.  RAYLIB_HIT_QUEUE=0|1 overrides the default (measured: DESIGN.md section 5).
+			p.hitQueue = p.lazy && st.maxPathLength >= 1 && (k.hitQueue >= 0 ? k.hitQueue != 0 : RL_HIT_QUEUE_DEFAULT != 0);
 		}
 	}
 	return p;

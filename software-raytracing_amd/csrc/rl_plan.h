@@ -7,7 +7,8 @@
 namespace rl {
 
 #define RL_POOL_DEFAULT_MIN_TRIS 256u   /* triangles from which the pool schedule is the default (RAYLIB_POOL_MIN_TRIS) */
-#define RL_FLOAT_BOX_MAX_TRIS 4096u     /* scenes below this many triangles carry the float-box wide nodes (and the leaf list) on the device */
+#define RL_HIT_QUEUE_DEFAULT 1          /* a lazy plan takes the hit-queue form (k_trace_lazy_hitq) unless RAYLIB_HIT_QUEUE=0 */
+#define RL_FLOAT_BOX_MAX_TRIS 4096u    /* scenes below this many triangles carry the float-box wide nodes (and the leaf list) on the device */
 
 // The per-render switches of INTEGRATION.md, read from the environment by ReadRenderKnobs() on every render (tests change them between renders).
 // A default-constructed RenderKnobs is "nothing set".  -1: not set; the 0 / 1 switches hold atoi(value) != 0.
@@ -26,6 +27,7 @@ struct RenderKnobs {
 	int queryTree = 0;                            // RAYLIB_QUERY_TREE: 2, 4 or 8 (RaylibAMD_TraceRays, RaylibAMD_TraceRadiance, RaylibAMD_Gather; any other value: 0, not set)
 	int gatherBatch = 0;                          // RAYLIB_GATHER_BATCH: (point, sample) slots per launch of RaylibAMD_Gather (0: not set or not positive)
 	int lazyRefl = -1;                            // RAYLIB_LAZY_REFL
+	int hitQueue = -1;                            // RAYLIB_HIT_QUEUE
 	long long litList = -1;                       // RAYLIB_LIT_LIST: entries of the lazy instance's lit list (0: every lit path folds in place); -1: not set
 	int litMask = -1;                             // RAYLIB_LIT_MASK: 0 keeps every sample stored and k_resolve; 1 takes the lit-sample mask with a sun too
 };
@@ -44,6 +46,7 @@ struct TracePlan {
 	int lds = 0;                // k_trace: 0, 1 = the scene in LDS, 2 = the leaf list
 	bool plain = false;         // the leaf-list kernel's instance without texture, cut-out and sky code
 	bool lazy = false;          // ... and of that, the lazy-reflectance instance (k_trace_lazy + k_fold_lit); the views twin of a lazy plan is the plain instance's
+	bool hitQueue = false;      // ... and of that, its hit-queue form (k_trace_lazy_hitq): idle lanes take camera rays that have been traced already
 	uint32_t pathsPerWave = 64, treeWidth = 2, nodeBytes = 64;   // RaylibAMDStats
 	bool keepNodes4 = true, keepNodes4f = true;   // the launch's view keeps the grid / float-box wide nodes (k_trace tells the tree by which is set)
 	int32_t eagerTree = TREE_NONE;   // the wide tree UploadScene puts on the device (TREE_GRID4, TREE_WIDE8 or none): the default plan's

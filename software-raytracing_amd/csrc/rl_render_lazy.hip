@@ -1,4 +1,4 @@
-// The leaf-list kernel's lazy-reflectance instance (k_trace_lazy), the kernel that finishes its lit paths (k_fold_lit) and the sweeps of its guards, as a translation
+// The leaf-list kernel's lazy-reflectance instance (k_trace_lazy), its hit-queue form (k_trace_lazy_hitq), the kernel that finishes their lit paths (k_fold_lit) and the sweeps of its guards, as a translation
 // unit of their own: instantiated beside the other k_trace instances, the lazy one changes how the compiler schedules two loops of the eager PLAIN instance, and
 // the eager kernels must stay what they are (tools/isa_equivalence.py) -- the reason the views twins have their unit.
 
@@ -19,6 +19,9 @@ namespace rl {
 #include "rl_k_trace.inl"
 #undef RL_LAZY_REFL
 #undef RL_VIEWS_TWIN
+
+// ---- its hit-queue form (k_trace_lazy_hitq): the idle lanes take camera rays that have been traced already.  In this unit, whose settings it shares ----
+#include "rl_k_trace_hitq.inl"
 
 // One thread per entry of the lit list (rl_device.h DLitList): the path's vertex records, camera first, folded from the last back to the camera exactly as k_trace
 // folds -- each vertex's reflectance evaluated here, in full waves, instead of at its scattering event -- and the sample stored; with a lit-sample mask
@@ -254,5 +257,6 @@ k_verify_sampler_ranged(int mode, unsigned long long* __restrict__ out)
 
 // ---- instances ----
 RL_TRACE_LAZY_INSTANCES(RL_K_TRACE_LAZY)
+RL_TRACE_LAZY_INSTANCES(RL_K_TRACE_LAZY_HITQ)
 
 } // namespace rl

@@ -34,6 +34,7 @@ static const void* KernelFor(const TracePlan& p, bool views)
 #undef RL_POOL_PICK
 		return nullptr;
 	}
+	if (p.lds == 2 && p.lazy && p.hitQueue && !views) return (const void*)(TraceLazyKernel)k_trace_lazy_hitq<16, false, true, 2, true>;
 	if (p.lds == 2 && p.lazy && !views) return (const void*)(TraceLazyKernel)k_trace_lazy<16, false, true, 2, true>;   // (a batch of views stays eager: the plain twin)
 	if (p.lds == 2) return p.plain ? Trace<16, false, true, 2, true>(views) : Trace<16, false, true, 2>(views);
 	if (p.lds == 1) return Trace<16, false, true, 1>(views);
@@ -52,6 +53,8 @@ static std::atomic<int32_t> g_lastTracePlain{0};   // RaylibAMD_LastTracePlain: 
 int32_t DeviceLastTracePlain() { return g_lastTracePlain.load(std::memory_order_relaxed); }
 static std::atomic<int32_t> g_lastTraceLazy{0};    // RaylibAMD_LastTraceLazy
 int32_t DeviceLastTraceLazy() { return g_lastTraceLazy.load(std::memory_order_relaxed); }
+static std::atomic<int32_t> g_lastHitQueue{0};     // RaylibAMD_LastHitQueue
+int32_t DeviceLastHitQueue() { return g_lastHitQueue.load(std::memory_order_relaxed); }
 static std::atomic<int32_t> g_lastLitMask{0};      // RaylibAMD_LastLitMask
 int32_t DeviceLastLitMask() { return g_lastLitMask.load(std::memory_order_relaxed); }
 
@@ -156,6 +159,7 @@ static bool EnqueueFrame(RankCtx& R, int q, const DeviceScene& DS, Frame& F, Pen
 		g_lastTracePlain.store(plan.plain ? 1 : 0, std::memory_order_relaxed);
 		const bool lazy = plan.lazy && !F.views;   // k_trace_lazy: the lit list is its trailing argument, and k_fold_lit follows it
 		g_lastTraceLazy.store(lazy ? 1 : 0, std::memory_order_relaxed);
+		g_lastHitQueue.store(lazy && plan.hitQueue ? 1 : 0, std::memory_order_relaxed);
 		pend.lazy = lazy;
 		DLitList LL = {};
 		pend.pathsPerWave = plan.pathsPerWave; pend.treeWidth = plan.treeWidth; pend.nodeBytes = plan.nodeBytes;

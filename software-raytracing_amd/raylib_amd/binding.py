@@ -64,7 +64,7 @@ class RenderPlan(C.Structure):
                [(k, C.c_uint32) for k in ("pathsPerWave", "treeWidth", "nodeBytes")] + \
                [(k, C.c_int32) for k in ("keepNodes4", "keepNodes4f", "eagerTree")] + \
                [(k, C.c_uint32) for k in ("batch", "sampleCount", "blocks", "stackStride", "jobChunk", "heads", "jobsPerHead", "guideShift")] + \
-               [("jobs", C.c_uint64), ("lazy", C.c_int32), ("reserved", C.c_int32)]
+               [("jobs", C.c_uint64), ("lazy", C.c_int32), ("hitQueue", C.c_int32)]
     TREES = {0: "none", 1: "bvh2", 2: "box4", 3: "grid4", 4: "wide8"}
 
     def as_dict(self):
@@ -681,6 +681,7 @@ _EXPORTS = {
     "RaylibAMD_LastTracePlain": (C.c_int32, []),
     "RaylibAMD_SceneLazyRefl": (C.c_int32, [C.c_void_p]),
     "RaylibAMD_LastTraceLazy": (C.c_int32, []),
+    "RaylibAMD_LastHitQueue": (C.c_int32, []),
     "RaylibAMD_LastLitMask": (C.c_int32, []),
     "RaylibAMD_VerifyLazyRefl": (C.c_int32, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "RaylibAMD_VerifyLazyPdf": (C.c_int32, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

@@ -30,6 +30,7 @@ bool DeviceDrain(RaylibAMDStats*) { return false; }
 void DeviceOwnStats() {}
 int32_t DeviceLastTracePlain() { return 0; }
 int32_t DeviceLastTraceLazy() { return 0; }
+int32_t DeviceLastHitQueue() { return 0; }
 int32_t DeviceLastLitMask() { return 0; }
 bool DeviceVerifyLazyRefl(uint32_t, uint64_t, uint64_t*) { return false; }
 bool DeviceVerifyLazyPdf(uint32_t, uint64_t, uint64_t*) { return false; }

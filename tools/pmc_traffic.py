@@ -2,7 +2,7 @@
 
 usage: ROUND_TAG=r03 python tools/pmc_traffic.py <workload>=<pmc out dir> [...]
 
-Per workload, for the dominant kernel (k_trace / k_trace_lazy / k_trace_pool), mean per launch:
+Per workload, for the dominant kernel (k_trace / k_trace_lazy / k_trace_lazy_hitq / k_trace_pool), mean per launch:
   * HBM bytes = 2 x FETCH_SIZE (KB; the gfx950 correction of MI355X_MICROARCH.md's HBM section) + WRITE_SIZE (KB), each from its own pass;
   * VALU instructions by class (SQ_INSTS_VALU_{ADD,MUL,FMA}_F32 / _F64, TRANS_F32 / _F64, INT32, INT64, CVT; the rest = SQ_INSTS_VALU minus
     those) priced with the issue costs measured by tools/valu_calib.hip under rocprofv3 (profiles/valu_calib.json: 2 cycles per wave64 for
@@ -45,7 +45,7 @@ for arg in sys.argv[1:]:
     cycles = m["GRBM_GUI_ACTIVE"] / 8.0
     # static mix of this instantiation: "void rl::k_trace<16, false, true, 2>" -> "k_traceILi16ELb0ELb1ELi2E"
     args = kern.strip().split("<", 1)[1].rstrip(">").split(",")
-    mangled = ("k_trace_pool" if "k_trace_pool" in kern else "k_trace_lazy" if "k_trace_lazy" in kern else "k_trace") + "I" + "".join(("Lb1" if a.strip() == "true" else "Lb0" if a.strip() == "false" else "Li" + a.strip()) + "E" for a in args)
+    mangled = next(n for n in ("k_trace_pool", "k_trace_lazy_hitq", "k_trace_lazy", "k_trace") if n in kern) + "I" + "".join(("Lb1" if a.strip() == "true" else "Lb0" if a.strip() == "false" else "Li" + a.strip()) + "E" for a in args)
     assert mangled in MIX, (mangled, list(MIX)[:4])
     mix = MIX[mangled]["mean_cost"]
     counts = {c: m.get("SQ_INSTS_VALU_" + c, 0.0) for c in ("ADD_F32", "MUL_F32", "FMA_F32", "ADD_F64", "MUL_F64", "FMA_F64", "TRANS_F32", "TRANS_F64", "CVT", "INT32", "INT64")}
