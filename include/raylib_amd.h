@@ -515,6 +515,48 @@ RAYLIB_API int32_t RaylibAMD_VerifyLazyPdf(uint32_t n, uint64_t seed, uint64_t* 
  * may be NULL.  Returns 1 when the sweep ran. */
 RAYLIB_API int32_t RaylibAMD_VerifySamplerRanged(int32_t mode, uint64_t* outMismatches, uint64_t* outFirstBits, uint32_t* outInterval, uint64_t* outOutside);
 
+/* ---- a finalized scene's triangles moved; its trees refitted on the device ---------------------------
+ * Triangles [first, first + count) in RaylibAMD_SceneExportTriangles order take new vertices -- positions: count x 9 floats (v0 v1 v2) -- and, when normals is
+ * not NULL, new shading normals (count x 9 floats, n0 n1 n2; NULL keeps them).  Materials, UVs, cut-out flags, spheres and cubes are untouched, a query's
+ * primitive index stays the triangle's index.  Every later call on the scene -- Raylib_Render, RaylibAMD_RenderDevice, RenderViews, RenderCellsHost, TraceRays,
+ * TraceRadiance, Gather*, BakeLightmap*, LightmapPoints* -- returns what that call returns on a scene created from the moved triangles and finalized: the same
+ * bits (the closest hit depends neither on how tight a box is nor on the order in which boxes that contain it are tested: DESIGN.md section 4).
+ * Topology: the trees keep their shape and the triangles their slots; every box of every format the device holds (binary, 4-wide float and grid, 8-wide, leaf
+ * list) is refitted, whole tree.  RaylibAMD_SceneBVHInfo's SAH cost is then that of the refitted binary tree, so a caller sees the trees degrade and may call
+ * RaylibAMD_SceneRebuild.  RaylibAMD_SceneTopologyHash is unchanged by a move.  RaylibAMD_SceneBVHHash covers the node records with their boxes: a move changes it, and
+ * after RaylibAMD_SceneRebuild both are the hashes of a scene created from the moved triangles.  (RaylibAMD_SceneBVH8Info's expected steps stay those of the last build.)
+ * Host copies: the host entry updates the host's triangles at once; after the device entry they are stale, and after either entry so are the host's copies of
+ * the trees' boxes but the root's.  One read-back brings them up to date the first time one of these needs them: RaylibAMD_SceneExportTriangles,
+ * RaylibAMD_LightmapPointsHost, the lightmap calls' triangle table, RaylibAMD_SceneBVHInfo / BVH4Info / BVH8Info / BVHHash / ExportBVHNodes, RaylibAMD_SceneWalk8Host,
+ * RaylibAMD_SceneWalkStackHost, RaylibAMD_PlanViews, RaylibAMD_SceneCheckTrees, RaylibAMD_SceneRebuild, the first upload of a wide tree the device does not hold yet,
+ * and whatever drops the scene's device copy for a new upload (Raylib_SetSunIlluminance, Raylib_SetSunDirection, a call that rebuilds a scene of moving cubes for
+ * another time interval).
+ * Scene bounds: the silhouette cull takes them from the root's boxes (48 bytes), which every move copies to pinned memory with its status; the NEXT call on the
+ * scene, whichever it is, waits for that copy before it plans anything -- the device entry itself does not wait.  The same wait applies DSceneView::fastBary as a
+ * fresh scene would have it (a count of the triangles whose divisor lies outside [2^-62, 2^125] is kept on the device).
+ * Ordering: the host entry is synchronous.  The device entry with stream == NULL runs on the library's stream, synchronously; with a hipStream_t it is enqueued
+ * there behind the scene's synchronous first upload and returns.  Either waits for multi-rank frames in flight and goes behind the library's work in flight on
+ * other streams (the ray queries' ring, the path calls' event); the library's later work on the scene is ordered behind the move by the move's event, which the next
+ * call on the scene waits for ON THE HOST, whatever stream it is given: a RaylibAMD_TraceRaysDevice enqueued right behind a move returns once the move has completed
+ * (the caller writes no synchronisation between the two; the library makes one).  Work of the caller's own is ordered by the caller's stream.  With RAYLIB_NUM_GPUS > 1
+ * every device's copy of the scene is moved: the same kernels on a stream of each device, a device entry's values peer-copied from rank 0's device behind an event on the
+ * call's stream, which in turn waits for those copies (the caller may overwrite the values behind the call).
+ * Returns 1 (count == 0 included), or 0 with nothing changed for: a scene unknown or not finalized; first < 0, count < 0 or a range past
+ * RaylibAMD_SceneNumTriangles; NULL positions with count > 0; a progressive session open on the scene (its sums would mix two scenes); no device; a value
+ * that is not finite (host entry: scanned before anything is touched); device entry: a pointer that is not memory of rank 0's device or not 4-byte aligned.
+ * The device entry's values are scanned by a kernel in front of the one that writes the records: a value that is not finite raises a flag, the records kernel then
+ * writes nothing and the refit behind it reproduces the boxes that were there.  With stream == NULL the call returns 0; on a caller's stream it has returned 1
+ * already, and the next call on the scene logs "that move was NOT applied" and goes on with the unmoved scene. */
+RAYLIB_API int32_t RaylibAMD_SceneMoveTriangles(SceneHandle scene, int32_t first, int32_t count, const float* positions, const float* normals);
+RAYLIB_API int32_t RaylibAMD_SceneMoveTrianglesDevice(SceneHandle scene, int32_t first, int32_t count, const float* positions, const float* normals, void* stream);
+/* The existing host build on the current triangles (read back first where the host's are stale) and a fresh upload at the next call: restores the trees'
+ * quality after large moves.  Results keep their bits.  Returns 1, or 0 for a scene unknown or not finalized. */
+RAYLIB_API int32_t RaylibAMD_SceneRebuild(SceneHandle scene);
+/* Test hook: reads the trees and the triangle records the device holds back and runs the builder's validity checks (RaylibAMD_SceneBVHInfo / BVH4Info / BVH8Info's)
+ * on them against the current triangles.  Returns 1 when all pass; else 0 with *outFailedTree (may be NULL) = 2, 4 or 8 for the first tree that failed, or 0
+ * when the check could not run (no device, scene unknown or not finalized). */
+RAYLIB_API int32_t RaylibAMD_SceneCheckTrees(SceneHandle scene, uint32_t* outFailedTree);
+
 /* ---- host-logic introspection (no GPU needed) ---------------------------------- */
 /* Flattened scene as the kernels see it.  Triangle record = 26 words, material record =
  * 19 words, both laid out as oracle/flat_scene.h FlatTriangle / FlatMaterial. */
@@ -623,6 +665,12 @@ RAYLIB_API int32_t RaylibAMD_PlanViews(SceneHandle scene, const RendererSettings
 /* FNV-1a of the flat BVH (node records + leaf order): the multi-threaded build (RAYLIB_BUILD_THREADS, default = host
  * threads, <= 32) must give the tree of the single-threaded one. */
 RAYLIB_API uint64_t RaylibAMD_SceneBVHHash(SceneHandle scene);
+/* FNV-1a of the trees' topology alone -- child references, leaf order, the 8-wide nodes' masks and bases, no box: unchanged by
+ * RaylibAMD_SceneMoveTriangles (the "same topology" signal), changed by RaylibAMD_SceneRebuild whenever the build comes out differently.  No device needed. */
+RAYLIB_API uint64_t RaylibAMD_SceneTopologyHash(SceneHandle scene);
+/* The binary tree's nodes as the host holds them (read back first after a move), 64 bytes each: lmin[3] lmax[3] rmin[3] rmax[3] (float), left, right (int32: >= 0 an
+ * inner node's index, < 0 a leaf reference or 0x80000000 for none), two words of padding; node 0 is the root.  out may be NULL.  Returns the number of nodes. */
+RAYLIB_API int32_t RaylibAMD_SceneExportBVHNodes(SceneHandle scene, void* out);
 /* Camera derived state: 19 floats origin(3) lensRadius top_left(3) horizontal(3) vertical(3) u(3) v(3)
  * (reference render/camera.h:55-78). */
 RAYLIB_API void    RaylibAMD_CameraExport(CameraHandle camera, float out[19]);

@@ -73,6 +73,15 @@ uint64_t CurrentSeed()
 	return g_seed;
 }
 
+// The scene's device copy goes (the next call uploads the host's scene again): had its triangles moved on the device, the host's copies are brought up to date
+// first (RaylibAMD_SceneMoveTriangles)
+void ReleaseDeviceCopy(Scene* s)
+{
+	if (!s->device) return;
+	if (!DeviceSyncMovedScene(*s)) Log("the scene's moved triangles could not be read back: its next upload is of the triangles the host holds");
+	DeviceReleaseScene(s->device); s->device = nullptr;
+}
+
 // What every render checks and prepares before it reaches the device (Raylib_Render and RaylibAMD_BeginProgressive; `who` names the caller in the log).
 bool PrepareRender(const char* who, const RendererSettings* settings, Scene* scene, Camera* camera)
 {
@@ -81,7 +90,7 @@ bool PrepareRender(const char* who, const RendererSettings* settings, Scene* sce
 	if (settings->renderMode >= RAYLIB_RENDERMODE_MAX) { Log("%s: invalid render mode %u", who, settings->renderMode); return false; }
 	if (scene->hasMovingCubes && (scene->accelT0 != camera->beginTime || scene->accelT1 != camera->endTime)) {
 		// moving cubes: their boxes must cover the motion over THIS camera's shutter interval
-		if (scene->device) { DeviceReleaseScene(scene->device); scene->device = nullptr; }
+		ReleaseDeviceCopy(scene);
 		if (!scene->BuildAccel(camera->beginTime, camera->endTime)) { Log("%s: the acceleration structure could not be rebuilt for this camera's shutter interval", who); return false; }
 	}
 	if (scene->sky && !g_images.contains(scene->sky)) {
@@ -338,14 +347,14 @@ void Raylib_SetSunIlluminance(SceneHandle sh, float r, float g, float b)
 	Scene* s = (Scene*)sh;
 	if (!s) return;
 	s->sunIlluminance = F3(r, g, b);
-	if (s->device) { DeviceReleaseScene(s->device); s->device = nullptr; }
+	ReleaseDeviceCopy(s);
 }
 void Raylib_SetSunDirection(SceneHandle sh, float x, float y, float z)
 {
 	Scene* s = (Scene*)sh;
 	if (!s) return;
 	s->sunDirection = normalize(F3(x, y, z));   // reference geom/scene.h:20
-	if (s->device) { DeviceReleaseScene(s->device); s->device = nullptr; }
+	ReleaseDeviceCopy(s);
 }
 void Raylib_FinalizeScene(SceneHandle sh)
 {
@@ -792,7 +801,7 @@ static int32_t TraceRaysInternal(const char* who, SceneHandle sh, int32_t kind, 
 	if (s->hasMovingCubes && !(rayTime >= s->accelT0 && rayTime <= s->accelT1)) {
 		// moving cubes: their boxes must cover the motion up to this ray time (as a render rebuilds them for its camera's shutter interval)
 		const float t0 = std::min(s->accelT0, rayTime), t1 = std::max(s->accelT1, rayTime);
-		if (s->device) { DeviceReleaseScene(s->device); s->device = nullptr; }
+		ReleaseDeviceCopy(s);
 		if (!s->BuildAccel(t0, t1)) { Log("%s: the acceleration structure could not be rebuilt for ray time %g", who, rayTime); return 0; }
 	}
 	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
@@ -856,7 +865,7 @@ static bool PreparePathScene(const char* who, Scene* s, const RaylibAMDRadianceP
 	if (n > 0 && s->hasMovingCubes && !(prm.timeMin >= s->accelT0 && prm.timeMax <= s->accelT1)) {
 		// moving cubes: their boxes must cover the motion at every ray's time (as RaylibAMD_TraceRays rebuilds them for its rayTime)
 		const float t0 = std::min(s->accelT0, prm.timeMin), t1 = std::max(s->accelT1, prm.timeMax);
-		if (s->device) { DeviceReleaseScene(s->device); s->device = nullptr; }
+		ReleaseDeviceCopy(s);
 		if (!s->BuildAccel(t0, t1)) { Log("%s: the acceleration structure could not be rebuilt for the times [%g, %g]", who, prm.timeMin, prm.timeMax); return false; }
 	}
 	if (s->sky && !g_images.contains(s->sky)) {
@@ -1060,7 +1069,7 @@ static int64_t LightmapPointsInternal(const char* who, SceneHandle sh, const Ray
 	int32_t triFirst = 0, triCount = 0; RaylibAMDRadianceParams prm;
 	if (!LightmapArgsValid(who, s, params, triFirst, triCount, prm)) return -1;
 	if (capacity < 0 || (capacity > 0 && !outPoints)) { Log("%s: a negative capacity, or no room for the points", who); return -1; }
-	if (!device) return LightmapPointsHost(*s, *params, triFirst, triCount, uv, outPoints, outTexel, capacity);
+	if (!device) return DeviceSyncMovedScene(*s) ? LightmapPointsHost(*s, *params, triFirst, triCount, uv, outPoints, outTexel, capacity) : -1;
 	if (!DeviceAvailable()) return -1;
 	return DeviceLightmapPoints(*s, *params, triFirst, triCount, uv, outPoints, outTexel, capacity);
 }
@@ -1159,7 +1168,7 @@ int32_t RaylibAMD_FilterLightmapHost(int32_t width, int32_t height, int32_t kind
 int32_t RaylibAMD_SceneNumTriangles(SceneHandle sh) { Scene* s = (Scene*)sh; return s ? (int32_t)s->triangles.size() : 0; }
 int32_t RaylibAMD_SceneNumMaterials(SceneHandle sh) { Scene* s = (Scene*)sh; return s ? (int32_t)s->materials.size() : 0; }
 int32_t RaylibAMD_SceneNumTextures(SceneHandle sh) { Scene* s = (Scene*)sh; return s ? (int32_t)s->textures.size() : 0; }
-void RaylibAMD_SceneExportTriangles(SceneHandle sh, void* out) { Scene* s = (Scene*)sh; if (s && out && !s->triangles.empty()) memcpy(out, s->triangles.data(), s->triangles.size() * sizeof(HostTriangle)); }
+void RaylibAMD_SceneExportTriangles(SceneHandle sh, void* out) { Scene* s = (Scene*)sh; if (s && out && !s->triangles.empty() && DeviceSyncMovedScene(*s)) memcpy(out, s->triangles.data(), s->triangles.size() * sizeof(HostTriangle)); }
 void RaylibAMD_SceneExportMaterials(SceneHandle sh, void* out) { Scene* s = (Scene*)sh; if (s && out && !s->materials.empty()) memcpy(out, s->materials.data(), s->materials.size() * sizeof(HostMaterial)); }
 void RaylibAMD_SceneTextureSize(SceneHandle sh, int32_t i, int32_t* w, int32_t* h)
 {
@@ -1185,7 +1194,7 @@ void RaylibAMD_SceneGetSun(SceneHandle sh, float ill[3], float dir[3])
 int32_t RaylibAMD_SceneBVHInfo(SceneHandle sh, uint32_t* nodes, uint32_t* depth, float* sah)
 {
 	Scene* s = (Scene*)sh;
-	if (!s || !s->finalized) return 0;
+	if (!s || !s->finalized || !DeviceSyncMovedScene(*s)) return 0;
 	if (nodes) *nodes = (uint32_t)s->bvh.nodes.size();
 	if (depth) *depth = s->bvh.depth;
 	if (sah) *sah = s->bvh.sahCost;
@@ -1194,7 +1203,7 @@ int32_t RaylibAMD_SceneBVHInfo(SceneHandle sh, uint32_t* nodes, uint32_t* depth,
 int32_t RaylibAMD_SceneBVH4Info(SceneHandle sh, uint32_t* nodes4, uint32_t* stackNeed)
 {
 	Scene* s = (Scene*)sh;
-	if (!s || !s->finalized || s->bvh.nodes4.empty()) return 0;
+	if (!s || !s->finalized || s->bvh.nodes4.empty() || !DeviceSyncMovedScene(*s)) return 0;
 	if (nodes4) *nodes4 = (uint32_t)s->bvh.nodes4.size();
 	if (stackNeed) *stackNeed = s->bvh.stackNeed4;
 	return (ValidateBVH4(s->bvh, s->triangles) && ValidateBVH8(s->bvh, s->triangles)) ? 1 : -1;   // (the 8-wide tree, where the scene has one, is part of the check)
@@ -1202,7 +1211,7 @@ int32_t RaylibAMD_SceneBVH4Info(SceneHandle sh, uint32_t* nodes4, uint32_t* stac
 int32_t RaylibAMD_SceneBVH8Info(SceneHandle sh, uint32_t* nodes8, uint32_t* levels, float* steps4, float* steps8)
 {
 	Scene* s = (Scene*)sh;
-	if (!s || !s->finalized || s->bvh.nodes8.empty()) return 0;
+	if (!s || !s->finalized || s->bvh.nodes8.empty() || !DeviceSyncMovedScene(*s)) return 0;
 	if (nodes8) *nodes8 = (uint32_t)s->bvh.nodes8.size();
 	if (levels) *levels = s->bvh.depth8;
 	if (steps4) *steps4 = s->bvh.sahNodes4;
@@ -1212,7 +1221,7 @@ int32_t RaylibAMD_SceneBVH8Info(SceneHandle sh, uint32_t* nodes8, uint32_t* leve
 int32_t RaylibAMD_SceneWalk8Host(SceneHandle sh, const float* rays, int32_t count, float tMin, const float* tMax, float* outT, uint32_t* outSteps)
 {
 	Scene* s = (Scene*)sh;
-	if (!s || !s->finalized || s->bvh.nodes8.empty() || !rays || !tMax || !outT || count < 0) return 0;
+	if (!s || !s->finalized || s->bvh.nodes8.empty() || !rays || !tMax || !outT || count < 0 || !DeviceSyncMovedScene(*s)) return 0;
 	return Walk8Host(s->bvh, s->triangles, rays, count, tMin, tMax, outT, outSteps) ? 1 : -1;
 }
 int32_t RaylibAMD_SceneWalkStackHost(SceneHandle sh, int32_t tree, const float* rays, int32_t count, float tMin, int32_t capacity, float* outT, uint32_t* outHighWater)
@@ -1220,6 +1229,7 @@ int32_t RaylibAMD_SceneWalkStackHost(SceneHandle sh, int32_t tree, const float* 
 	Scene* s = (Scene*)sh;
 	if (!s || !s->finalized || !rays || !outT || count < 0 || capacity < 0 || (tree != 2 && tree != 3 && tree != 4 && tree != 8)) return 0;
 	if (tree == 2 ? s->bvh.nodes.empty() : tree == 3 ? s->bvh.nodes4.empty() : tree == 4 ? s->bvh.nodes4q.empty() : s->bvh.nodes8.empty()) return 0;
+	if (!DeviceSyncMovedScene(*s)) return 0;
 	return WalkStackHost(s->bvh, s->triangles, s->spheres, s->cubes, tree, rays, count, tMin, capacity, outT, outHighWater) ? 1 : -1;
 }
 int32_t RaylibAMD_SceneLeafListInfo(SceneHandle sh, uint32_t* maxPerLeaf)
@@ -1277,6 +1287,7 @@ int32_t RaylibAMD_PlanViews(SceneHandle sh, const RendererSettings* settings, co
 	out->keepNodes4 = t.keepNodes4; out->keepNodes4f = t.keepNodes4f; out->eagerTree = t.eagerTree;
 	std::vector<DCamera> cams((size_t)count);
 	for (int32_t v = 0; v < count; ++v) cams[(size_t)v] = ((Camera*)cameras[v])->ToDevice();
+	if (!DeviceSyncMovedScene(*s)) return 0;   // (the cull's bounds: the root's boxes)
 	const ViewsPlan V = PlanViews(SceneCullScene(*s, hasSky != 0), *settings, cams.data(), (uint32_t)count, t, numCUs, workgroupsPerCU, knobs);
 	if (!V.ok) return 0;
 	if (outCellEmpty) memcpy(outCellEmpty, V.empty.data(), V.empty.size());
@@ -1288,7 +1299,7 @@ int32_t RaylibAMD_PlanViews(SceneHandle sh, const RendererSettings* settings, co
 uint64_t RaylibAMD_SceneBVHHash(SceneHandle sh)
 {
 	Scene* s = (Scene*)sh;
-	if (!s || !s->finalized) return 0;
+	if (!s || !s->finalized || !DeviceSyncMovedScene(*s)) return 0;
 	uint64_t h = 1469598103934665603ull;   // FNV-1a over the node records and the leaf order
 	auto feed = [&h](const void* p, size_t n) { const unsigned char* b = (const unsigned char*)p; for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; } };
 	feed(s->bvh.nodes.data(), s->bvh.nodes.size() * sizeof(DNode));
@@ -1297,6 +1308,66 @@ uint64_t RaylibAMD_SceneBVHHash(SceneHandle sh)
 	feed(s->bvh.nodes4q.data(), s->bvh.nodes4q.size() * sizeof(DNode4Q));
 	feed(s->bvh.leafList.data(), s->bvh.leafList.size() * sizeof(DNode4));
 	feed(s->bvh.nodes8.data(), s->bvh.nodes8.size() * sizeof(DNode8));
+	return h;
+}
+// ---- a finalized scene's triangles moved (include/raylib_amd.h; rl_rt_move.hip) ----
+static int32_t MoveTrianglesInternal(const char* who, SceneHandle sh, int32_t first, int32_t count, const float* positions, const float* normals, bool hostMem, void* stream)
+{
+	Scene* s = (Scene*)sh;
+	if (!s || !g_scenes.contains(s)) { Log("%s: unknown scene", who); return 0; }
+	if (!s->finalized) { Log("%s: scene was not finalized (Raylib_FinalizeScene)", who); return 0; }
+	if (first < 0 || count < 0 || (int64_t)first + (int64_t)count > (int64_t)s->triangles.size()) { Log("%s: triangles [%d, %d + %d) are not the scene's", who, first, first, count); return 0; }
+	if (count == 0) return 1;
+	if (!positions) { Log("%s: null positions", who); return 0; }
+	{
+		std::lock_guard<std::mutex> lk(g_progressive.mu);
+		for (const Progressive* p : g_progressive.items) if (p->scene == s) { Log("%s: a progressive session is open on the scene", who); return 0; }
+	}
+	if (hostMem) {
+		for (size_t i = 0; i < (size_t)count * 9; ++i) if (!std::isfinite(positions[i]) || (normals && !std::isfinite(normals[i]))) { Log("%s: a position or normal is not finite", who); return 0; }
+	}
+	return DeviceMoveTriangles(*s, first, count, positions, normals, hostMem, stream) ? 1 : 0;
+}
+int32_t RaylibAMD_SceneMoveTriangles(SceneHandle sh, int32_t first, int32_t count, const float* positions, const float* normals)
+{
+	return MoveTrianglesInternal("RaylibAMD_SceneMoveTriangles", sh, first, count, positions, normals, true, nullptr);
+}
+int32_t RaylibAMD_SceneMoveTrianglesDevice(SceneHandle sh, int32_t first, int32_t count, const float* positions, const float* normals, void* stream)
+{
+	return MoveTrianglesInternal("RaylibAMD_SceneMoveTrianglesDevice", sh, first, count, positions, normals, false, stream);
+}
+int32_t RaylibAMD_SceneRebuild(SceneHandle sh)
+{
+	Scene* s = (Scene*)sh;
+	if (!s || !g_scenes.contains(s) || !s->finalized) { Log("RaylibAMD_SceneRebuild: unknown scene, or not finalized"); return 0; }
+	ReleaseDeviceCopy(s);   // (a progressive session notices the new upload and ends: rl_rt_render.hip)
+	return s->BuildAccel(s->accelT0, s->accelT1) ? 1 : 0;
+}
+int32_t RaylibAMD_SceneCheckTrees(SceneHandle sh, uint32_t* outFailedTree)
+{
+	Scene* s = (Scene*)sh;
+	if (outFailedTree) *outFailedTree = 0;
+	if (!s || !g_scenes.contains(s) || !s->finalized) return 0;
+	return DeviceCheckTrees(*s, outFailedTree) ? 1 : 0;
+}
+int32_t RaylibAMD_SceneExportBVHNodes(SceneHandle sh, void* out)
+{
+	Scene* s = (Scene*)sh;
+	if (!s || !s->finalized || !DeviceSyncMovedScene(*s)) return 0;
+	if (out) memcpy(out, s->bvh.nodes.data(), s->bvh.nodes.size() * sizeof(DNode));
+	return (int32_t)s->bvh.nodes.size();
+}
+uint64_t RaylibAMD_SceneTopologyHash(SceneHandle sh)
+{
+	Scene* s = (Scene*)sh;
+	if (!s || !s->finalized) return 0;
+	uint64_t h = 1469598103934665603ull;   // FNV-1a over what a move keeps: child references, leaf order, the 8-wide nodes' masks and bases -- no box
+	auto feed = [&h](const void* p, size_t n) { const unsigned char* b = (const unsigned char*)p; for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; } };
+	for (const DNode& n : s->bvh.nodes) { feed(&n.left, 4); feed(&n.right, 4); }
+	feed(s->bvh.triOrder.data(), s->bvh.triOrder.size() * sizeof(uint32_t));
+	for (const DNode4& n : s->bvh.nodes4) feed(n.child, 16);
+	for (const DNode4& n : s->bvh.leafList) feed(n.child, 16);
+	for (const DNode8& n : s->bvh.nodes8) { const uint32_t imask = n.meta >> 24; feed(&imask, 4); feed(&n.childBase, 16); }   // childBase, triBase, leafMask, alphaMask
 	return h;
 }
 void RaylibAMD_CameraExport(CameraHandle h, float out[19])

@@ -10,6 +10,7 @@
 // ray), <= 4 triangles per leaf stored contiguously, both child boxes in the
 // parent so a lane decides two children per 64-byte fetch.
 #include "rl_host.h"
+#include "rl_grid.h"
 
 #include <algorithm>
 #include <atomic>
@@ -267,41 +268,13 @@ inline void storeBox(float* mn, float* mx, const Box& b) {
 }
 inline int32_t leafRef(uint32_t first, uint32_t kind, uint32_t count) { return ~(int32_t)((first << LEAF_FIRST_SHIFT) | (kind << LEAF_KIND_SHIFT) | (count - 1)); }
 
-// nodes4 -> nodes4q (DNode4Q, rl_device.h).  Every decision is made in double, where origin + q * step is exact, so "the grid
-// box contains the float box" holds exactly.
+// nodes4 -> nodes4q (DNode4Q, rl_device.h) by rl_grid.h's rule.
 static void QuantizeWide(BVH& out)
 {
 	out.nodes4q.assign(out.nodes4.size(), DNode4Q());
 	const size_t count = out.nodes4.size();
 	ParallelFor(ThreadsFor(count, kThreadedQuantize), 0, count, [&](size_t i0, size_t i1, unsigned) { for (size_t i = i0; i < i1; ++i) {
-		const DNode4& n = out.nodes4[i];
-		DNode4Q q; memset(&q, 0, sizeof(q));
-		float steps[3] = { 0.0f, 0.0f, 0.0f };
-		for (int a = 0; a < 3; ++a) {
-			float lo = FLT_MAX, hi = -FLT_MAX;
-			for (int k = 0; k < 4; ++k) if (n.child[k] != DNODE_EMPTY) { lo = std::min(lo, n.lo[a][k]); hi = std::max(hi, n.hi[a][k]); }
-			if (!(lo <= hi)) { lo = hi = 0.0f; }
-			q.origin[a] = lo;
-			// the smallest power of two whose 255 steps span the node
-			const double extent = (double)hi - (double)lo;
-			int e = 1;   // biased exponent; 1 = 2^-126, the smallest normal
-			if (extent > 0.0) { int x; (void)frexp(extent / 255.0, &x); e = std::max(1, std::min(254, x + 127)); }   // 2^x >= extent / 255
-			double step = ldexp(1.0, e - 127);
-			while (255.0 * step < extent && e < 254) { ++e; step *= 2.0; }
-			steps[a] = (float)step;   // a power of two between 2^-126 and 2^127: exact
-			for (int k = 0; k < 4; ++k) {
-				if (n.child[k] == DNODE_EMPTY) { q.qlo[a] |= 255u << (8 * k); continue; }   // inverted: lower 255, upper 0
-				double l = floor(((double)n.lo[a][k] - (double)lo) / step), h = ceil(((double)n.hi[a][k] - (double)lo) / step);
-				l = std::max(0.0, std::min(255.0, l)); h = std::max(0.0, std::min(255.0, h));
-				while (l > 0.0 && (double)lo + l * step > (double)n.lo[a][k]) l -= 1.0;
-				while (h < 255.0 && (double)lo + h * step < (double)n.hi[a][k]) h += 1.0;
-				q.qlo[a] |= (uint32_t)l << (8 * k);
-				q.qhi[a] |= (uint32_t)h << (8 * k);
-			}
-		}
-		q.stepX = steps[0]; q.stepY = steps[1]; q.stepZ = steps[2];
-		for (int k = 0; k < 4; ++k) q.child[k] = n.child[k];
-		out.nodes4q[i] = q;
+		out.nodes4q[i] = QuantizeNode4(out.nodes4[i]);
 	} });
 }
 
@@ -503,10 +476,12 @@ static double ExpectedSteps4(const std::vector<TmpNode>& T, int32_t root)
 	return sum;
 }
 
-// W + the leaf references (first triangle slot, count) -> out.nodes8.  Grid boxes as in QuantizeWide: every decision in double.
-static void EmitWide8(const std::vector<TmpNode>& T, const Wide8& W, const std::vector<int32_t>& leafCode, BVH& out)
+// W + the leaf references (first triangle slot, count) -> out.nodes8, and per child the binary tree's box it came from (boxId: EmitBinary's) -> out.boxOf8.
+// Grid boxes as in QuantizeWide.
+static void EmitWide8(const std::vector<TmpNode>& T, const Wide8& W, const std::vector<int32_t>& leafCode, const std::vector<int32_t>& boxId, BVH& out)
 {
 	out.nodes8.assign(W.nodes.size(), DNode8());
+	out.boxOf8.assign(8 * W.nodes.size(), -1);
 	out.depth8 = W.depth; out.sahNodes8 = (float)W.sah;
 	const size_t count = W.nodes.size();
 	ParallelFor(ThreadsFor(count, kThreadedEmit8), 0, count, [&](size_t i0, size_t i1, unsigned) { for (size_t i = i0; i < i1; ++i) {
@@ -521,30 +496,16 @@ static void EmitWide8(const std::vector<TmpNode>& T, const Wide8& W, const std::
 			leafMask |= ((1u << count) - 1u) << (4 * c);
 			if (!haveTri) { triBase = first; haveTri = true; }
 		}
-		uint32_t exps[3] = { 0, 0, 0 };
-		for (int a = 0; a < 3; ++a) {
-			float lo = FLT_MAX, hi = -FLT_MAX;
-			for (int c = 0; c < 8; ++c) if (w.kid[c] >= 0) { lo = std::min(lo, axisOf(T[w.kid[c]].box.mn, a)); hi = std::max(hi, axisOf(T[w.kid[c]].box.mx, a)); }
-			if (!(lo <= hi)) { lo = hi = 0.0f; }
-			n.origin[a] = lo;
-			const double extent = (double)hi - (double)lo;
-			int e = 1;
-			if (extent > 0.0) { int x; (void)frexp(extent / 255.0, &x); e = std::max(1, std::min(254, x + 127)); }
-			double step = ldexp(1.0, e - 127);
-			while (255.0 * step < extent && e < 254) { ++e; step *= 2.0; }
-			exps[a] = (uint32_t)e;
-			for (int c = 0; c < 8; ++c) {
-				if (w.kid[c] < 0) { n.qlo[a][c >> 2] |= 255u << (8 * (c & 3)); continue; }   // inverted: lower 255, upper 0
-				const double blo = axisOf(T[w.kid[c]].box.mn, a), bhi = axisOf(T[w.kid[c]].box.mx, a);
-				double l = floor((blo - (double)lo) / step), h = ceil((bhi - (double)lo) / step);
-				l = std::max(0.0, std::min(255.0, l)); h = std::max(0.0, std::min(255.0, h));
-				while (l > 0.0 && (double)lo + l * step > blo) l -= 1.0;
-				while (h < 255.0 && (double)lo + h * step < bhi) h += 1.0;
-				n.qlo[a][c >> 2] |= (uint32_t)l << (8 * (c & 3));
-				n.qhi[a][c >> 2] |= (uint32_t)h << (8 * (c & 3));
-			}
+		float lo[3][8], hi[3][8]; uint32_t used = 0;
+		for (int c = 0; c < 8; ++c) {
+			out.boxOf8[8 * i + (size_t)c] = w.kid[c] < 0 ? -1 : boxId[w.kid[c]];
+			if (w.kid[c] < 0) continue;
+			used |= 1u << c;
+			const Box& b = T[w.kid[c]].box;
+			for (int a = 0; a < 3; ++a) { lo[a][c] = axisOf(b.mn, a); hi[a][c] = axisOf(b.mx, a); }
 		}
-		n.meta = exps[0] | (exps[1] << 8) | (exps[2] << 16) | (imask << 24);
+		n.meta = imask << 24;
+		QuantizeNode8(lo, hi, used, n);
 		n.childBase = w.firstChild; n.triBase = triBase; n.leafMask = leafMask; n.alphaMask = 0;
 		out.nodes8[i] = n;
 	} });
@@ -633,8 +594,10 @@ std::vector<int32_t> AssignLeafSlots(const std::vector<TmpNode>& T, const Shared
 
 // Emit two-box nodes in depth-first order.  A tree that is a single leaf still gets one inner node (left = the leaf, right = empty).
 // Reads T (skipping what CollapseWide8 marked dead) and the leaf references; writes out.nodes, out.depth and out.sahCost (the single-leaf tree: depth 1, no cost).
-void EmitBinary(const std::vector<TmpNode>& T, int32_t root, const std::vector<int32_t>& leafCode, BVH& out)
+// Returns, per node of T but the root, the id of the box out.nodes keeps for it (rl_grid.h BoxOfId; -1: none): what the wide formats record per child.
+std::vector<int32_t> EmitBinary(const std::vector<TmpNode>& T, int32_t root, const std::vector<int32_t>& leafCode, BVH& out)
 {
+	std::vector<int32_t> boxId(T.size(), -1);
 	if (T[root].left < 0) {
 		Box empty; empty.reset();
 		DNode nd; memset(&nd, 0, sizeof(nd));
@@ -642,7 +605,7 @@ void EmitBinary(const std::vector<TmpNode>& T, int32_t root, const std::vector<i
 		nd.left = leafCode[root]; nd.right = DNODE_EMPTY;
 		out.nodes.push_back(nd);
 		out.depth = 1;
-		return;
+		return boxId;
 	}
 	std::vector<int32_t> emitIndex(T.size(), -1);
 	int32_t next = 0;
@@ -669,15 +632,17 @@ void EmitBinary(const std::vector<TmpNode>& T, int32_t root, const std::vector<i
 		nd.left = (L.left < 0) ? leafCode[T[t].left] : emitIndex[T[t].left];
 		nd.right = (R.left < 0) ? leafCode[T[t].right] : emitIndex[T[t].right];
 		out.nodes[emitIndex[t]] = nd;
+		boxId[T[t].left] = 2 * emitIndex[t]; boxId[T[t].right] = 2 * emitIndex[t] + 1;
 	}
 	out.depth = maxDepth;     // leaves at depth d => at most d inner nodes above them
 	out.sahCost = (float)sah;
+	return boxId;
 }
 
 // ---- the wide tree: collapse to <= 4 children per node ----
 // Starting from a node's two children, the inner child with the largest surface area is replaced by its own two children until there are four (or only leaves).  Only for scenes the pool schedule can run (triangles only, not tiny).
-// Reads T and the leaf references; writes out.nodes4, out.stackNeed4 (the entries a walk can leave on its stack along the worst path) and out.sahNodes4.
-void EmitWide4(const std::vector<TmpNode>& T, int32_t root, const std::vector<int32_t>& leafCode, BVH& out)
+// Reads T, the leaf references and the boxes' ids; writes out.nodes4, out.boxOf4, out.stackNeed4 (the entries a walk can leave on its stack along the worst path) and out.sahNodes4.
+void EmitWide4(const std::vector<TmpNode>& T, int32_t root, const std::vector<int32_t>& leafCode, const std::vector<int32_t>& boxId, BVH& out)
 {
 	struct Item { int32_t tmp; int32_t slot; uint32_t need; };   // a BVH2 inner node that becomes wide node `slot`
 	std::vector<Item> work;
@@ -711,6 +676,8 @@ void EmitWide4(const std::vector<TmpNode>& T, int32_t root, const std::vector<in
 			}
 		}
 		out.nodes4[it.slot] = nd;
+		out.boxOf4.resize(4 * out.nodes4.size(), -1);
+		for (int k = 0; k < nk; ++k) out.boxOf4[4 * (size_t)it.slot + (size_t)k] = boxId[kids[k]];
 	}
 	out.stackNeed4 = needMax; out.sahNodes4 = (float)sah4;
 }
@@ -724,8 +691,8 @@ void EmitWide4(const std::vector<TmpNode>& T, int32_t root, const std::vector<in
 // leaf list / BVH4 walk, first version: 36 triangles 0.86, 72: 0.92, 84: 0.88, 96: 0.89, 108: 0.90, 120 (8-triangle leaves): 1.05; final version: 0.79, 0.80, 0.79,
 // 0.77, 0.78 -- the limit is also what the kernel's LDS layout holds, rl_device.h RL_LEAFLIST_MAXTRIS).
 // Reads T and the leaf references of a scene of at most RL_LEAFLIST_MAXTRIS triangles, whose slots are in depth-first order (every sub-tree's triangles are
-// one range of slots); writes out.leafList, or leaves it empty where no cut fits.
-void EmitLeafList(const std::vector<TmpNode>& T, int32_t root, const std::vector<int32_t>& leafCode, BVH& out)
+// one range of slots); writes out.leafList and out.boxOfLeafList, or leaves them empty where no cut fits.
+void EmitLeafList(const std::vector<TmpNode>& T, int32_t root, const std::vector<int32_t>& leafCode, const std::vector<int32_t>& boxId, BVH& out)
 {
 	std::vector<uint32_t> triFirst(T.size(), 0), triCount(T.size(), 0);
 	for (size_t t = T.size(); t-- > 0;) {   // children follow their parent in T (pre-order): a reverse sweep sees them first
@@ -751,6 +718,7 @@ void EmitLeafList(const std::vector<TmpNode>& T, int32_t root, const std::vector
 	for (int32_t t : cut) if (triCount[t] > 8) fits = false;
 	if (!fits) return;
 	out.leafList.assign((cut.size() + 3) / 4, DNode4());
+	out.boxOfLeafList.assign(4 * out.leafList.size(), -1);
 	for (DNode4& nd : out.leafList) {
 		memset(&nd, 0, sizeof(nd));
 		// an unused slot is the box [+inf, -inf]: whatever the ray, one of its axes enters it at +inf (rl_dev_walk.h TraverseLeafList has no other test for it)
@@ -762,6 +730,7 @@ void EmitLeafList(const std::vector<TmpNode>& T, int32_t root, const std::vector
 		nd.lo[0][k] = T[t].box.mn.x; nd.lo[1][k] = T[t].box.mn.y; nd.lo[2][k] = T[t].box.mn.z;
 		nd.hi[0][k] = T[t].box.mx.x; nd.hi[1][k] = T[t].box.mx.y; nd.hi[2][k] = T[t].box.mx.z;
 		nd.child[k] = leafRef(triFirst[t], PRIM_TRIANGLE, triCount[t]);
+		out.boxOfLeafList[at] = boxId[t];
 	}
 }
 
@@ -773,7 +742,7 @@ bool BVHCapacityOk(size_t numPrimitives) { return numPrimitives < ((size_t)1 << 
 void BuildBVH(const std::vector<PrimRef>& prims, BVH& out, const BVHBuildOptions& opt)
 {
 	// (sahNodes4 and sahNodes8 are written only with their trees: a scene rebuilt without them keeps the figures of its last build with them)
-	out.nodes.clear(); out.nodes4.clear(); out.nodes4q.clear(); out.nodes8.clear(); out.depth8 = 0; out.leafList.clear(); out.stackNeed4 = 0; out.triOrder.clear(); out.depth = 0; out.sahCost = 0.0f;
+	out.nodes.clear(); out.nodes4.clear(); out.nodes4q.clear(); out.nodes8.clear(); out.depth8 = 0; out.leafList.clear(); out.boxOf4.clear(); out.boxOf8.clear(); out.boxOfLeafList.clear(); out.stackNeed4 = 0; out.triOrder.clear(); out.depth = 0; out.sahCost = 0.0f;
 	const uint32_t n = (uint32_t)prims.size();
 	if (n == 0) {
 		Box empty; empty.reset();
@@ -801,12 +770,37 @@ void BuildBVH(const std::vector<PrimRef>& prims, BVH& out, const BVHBuildOptions
 		CollapseWide8(T, root, W8, opt.wideGreedy, opt.triCost8);
 	}
 	const std::vector<int32_t> leafCode = AssignLeafSlots(T, B, prims, wide8 ? &W8.leafOrder : nullptr, out.triOrder);
-	EmitBinary(T, root, leafCode, out);
+	const std::vector<int32_t> boxId = EmitBinary(T, root, leafCode, out);
 	if (!wideTrees) return;
-	if (wide8) EmitWide8(T, W8, leafCode, out);
-	EmitWide4(T, root, leafCode, out);
+	if (wide8) EmitWide8(T, W8, leafCode, boxId, out);
+	EmitWide4(T, root, leafCode, boxId, out);
 	QuantizeWide(out);
-	if (n <= RL_LEAFLIST_MAXTRIS) EmitLeafList(T, root, leafCode, out);
+	if (n <= RL_LEAFLIST_MAXTRIS) EmitLeafList(T, root, leafCode, boxId, out);
+}
+
+// The boxes of bvh.nodes have been refitted (RaylibAMD_SceneMoveTriangles: read back from the device): the wide formats from them by the rule the device
+// applied (rl_grid.h), and the binary tree's SAH cost, its terms summed in the order EmitBinary sums them -- node, left sub-tree, right sub-tree.
+void RefitWideFromBinary(BVH& bvh)
+{
+	const DNode* nodes = bvh.nodes.data();
+	for (size_t i = 0; i < bvh.nodes4.size(); ++i) { RefitNode4(nodes, &bvh.boxOf4[4 * i], bvh.nodes4[i]); bvh.nodes4q[i] = QuantizeNode4(bvh.nodes4[i]); }
+	for (size_t i = 0; i < bvh.nodes8.size(); ++i) RefitNode8(nodes, &bvh.boxOf8[8 * i], bvh.nodes8[i]);
+	for (size_t i = 0; i < bvh.leafList.size(); ++i) RefitNode4(nodes, &bvh.boxOfLeafList[4 * i], bvh.leafList[i]);
+	if (bvh.nodes.empty() || bvh.nodes[0].right == DNODE_EMPTY) return;   // no primitive, or the single-leaf tree: no cost
+	auto boxOf = [&](int32_t id) { Box b; float mn[3], mx[3]; BoxOfId(nodes, id, mn, mx); b.mn = F3(mn[0], mn[1], mn[2]); b.mx = F3(mx[0], mx[1], mx[2]); return b; };
+	Box rootBox = boxOf(0); rootBox.grow(boxOf(1));
+	const float rootArea = std::max(rootBox.halfArea(), 1e-30f);
+	double sah = kCostTraverse * rootBox.halfArea() / rootArea;
+	std::vector<int32_t> st; st.push_back(1); st.push_back(0);   // box ids, the left one on top
+	while (!st.empty()) {
+		const int32_t id = st.back(); st.pop_back();
+		const int32_t ref = (id & 1) ? nodes[id >> 1].right : nodes[id >> 1].left;
+		if (ref == DNODE_EMPTY) continue;
+		if (ref < 0) { sah += kCostTri * ((((uint32_t)~ref) & LEAF_COUNT_MASK) + 1u) * boxOf(id).halfArea() / rootArea; continue; }   // (an analytic primitive's leaf: count 1)
+		sah += kCostTraverse * boxOf(id).halfArea() / rootArea;
+		st.push_back(2 * ref + 1); st.push_back(2 * ref);
+	}
+	bvh.sahCost = (float)sah;
 }
 
 namespace {

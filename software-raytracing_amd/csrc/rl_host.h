@@ -120,6 +120,9 @@ struct BVH {
 	float sahNodes4 = 0.0f, sahNodes8 = 0.0f;   // sum over the wide tree's nodes of (node's surface area / root's): the expected node steps of a random ray through either tree
 	std::vector<DNode4> leafList;     // scenes of <= 4 * RL_LEAFLIST_RECORDS leaves: every leaf's box, four to a record, no inner nodes (k_trace's flat walk; empty otherwise)
 	std::vector<uint32_t> triOrder;   // leaf order -> index into the flat triangle array
+	// per child of every nodes4 (4), nodes8 (8) and leafList (4) record: the box of `nodes` it was emitted from, 2 * node + (0 left, 1 right); -1: unused
+	// (rl_grid.h BoxOfId).  What a refit re-derives the wide formats from after the scene's triangles have moved.
+	std::vector<int32_t> boxOf4, boxOf8, boxOfLeafList;
 	uint32_t depth = 0;
 	float sahCost = 0.0f;
 };
@@ -137,6 +140,7 @@ struct PrimRef { f3 mn, mx; uint8_t kind; uint32_t index; };
 struct BVHBuildOptions { bool wideGreedy = false; bool splitLeaves8 = false; float triCost8 = 0.5f; float minSteps8 = RL_BVH8_MIN_STEPS; };
 void BuildBVH(const std::vector<PrimRef>& prims, BVH& out, const BVHBuildOptions& opt = BVHBuildOptions());
 bool BVHCapacityOk(size_t numPrimitives);   // a leaf reference addresses 2^25 primitive slots
+void RefitWideFromBinary(BVH& bvh);         // nodes' boxes were refitted: nodes4, nodes4q, nodes8 and leafList from them, and sahCost
 bool ValidateBVH(const BVH& bvh, const std::vector<HostTriangle>& tris);
 bool ValidateBVH4(const BVH& bvh, const std::vector<HostTriangle>& tris);
 bool ValidateBVH8(const BVH& bvh, const std::vector<HostTriangle>& tris);   // true also when the scene has no 8-wide tree
@@ -183,6 +187,10 @@ struct Scene {
 
 	bool hasMovingCubes = false;
 	float accelT0 = 0.0f, accelT1 = 0.0f;   // shutter interval the BVH boxes cover
+
+	// RaylibAMD_SceneMoveTriangles: the device's copy is ahead of `triangles` (after the device entry) / of bvh's boxes but the root's (after either entry) until
+	// DeviceSyncMovedScene reads them back; whoever reads them on the host calls it first
+	bool hostTrisStale = false, hostTreesStale = false;
 
 	Scene();
 	~Scene();
@@ -327,6 +335,12 @@ bool DeviceVerifySamplerRanged(int mode, uint64_t out[6]);   // k_verify_sampler
 bool DeviceVerifyExactMath(int which, uint64_t* outMismatches, uint64_t* outFirst);   // 0: rtm::rcp1_ vs 1.0f / x, 1: rtm::sqrt_ vs sqrtf, 2: rtm::div_by_ vs a / b, 3: Barycentric short vs divisions, 4: acosf_t / tanf_t short vs IEEE divisions; all 2^32 inputs
 bool DeviceEvalHook(int kind, Scene* sc, const DCamera* cam, int a, int b, const float* in, int n, uint64_t seed, float* out);
 void DeviceReleaseScene(DeviceScene* dev);
+// RaylibAMD_SceneMoveTriangles (hostMem) / RaylibAMD_SceneMoveTrianglesDevice (rl_rt_move.hip); the ABI checked the scene, the range and a host call's values.
+bool DeviceMoveTriangles(Scene& scene, int32_t first, int32_t count, const float* positions, const float* normals, bool hostMem, void* stream);
+// the host copies of a moved scene (triangles, trees) current again: one read-back where they are stale, nothing otherwise
+bool DeviceSyncMovedScene(Scene& scene);
+// RaylibAMD_SceneCheckTrees: rl_bvh.cc's checks on what the device holds; *outFailedTree: 0, or 2 / 4 / 8 for the first tree that failed
+bool DeviceCheckTrees(Scene& scene, uint32_t* outFailedTree);
 
 // Progressive rendering (include/raylib_amd.h RaylibAMD_BeginProgressive; rl_rt_render.hip).  Begin: nullptr without a device or memory.  Step: the number of
 // live cells after the pass (0: finished), -1 when refused or failed -- `rendered` tells whether a pass ran (and `stats` is its numbers).

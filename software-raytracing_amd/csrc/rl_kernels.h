@@ -17,6 +17,7 @@
 //                        from rl_gather.hip so that its kernels stay the code they are
 //   rl_lightmap.hip      k_lm_*: the lightmap rasteriser, its scans and the atlas stages (RaylibAMD_BakeLightmap); no walk, no shading
 //   rl_lightmap_filter.hip  k_lm_filter, k_lm_take: the atlas filter (RaylibAMD_BakeLightmapFiltered) and its host oracle, which share one per-texel function
+//   rl_refit.hip         k_move_*, k_refit_*: a finalized scene's triangles moved and its trees refitted (RaylibAMD_SceneMoveTriangles); no walk, no shading
 // A twin takes the view table (DViews) as one more trailing argument.  Default template arguments are given here and nowhere else.
 #pragma once
 
@@ -299,6 +300,23 @@ k_lm_take(const uint32_t* __restrict__ rank, const float* __restrict__ atlas, ui
 	X template __global__ void k_lm_take<C>(const uint32_t* __restrict__, const float* __restrict__, uint32_t, float* __restrict__);
 RL_LM_FILTER_INSTANCES(extern, 4)
 RL_LM_FILTER_INSTANCES(extern, 27)
+
+// ---------------------------------------------------------------------------
+// A move of a finalized scene's triangles and the refit of its trees (rl_refit.hip, bodies in rl_k_refit.inl; launched by rl_rt_move.hip): no walk, no shading.
+// The status block of a scene's moves: word RL_MOVE_NONFINITE is raised by k_move_scan when a value is not finite (k_move_records then writes nothing), word
+// RL_MOVE_BAD_DENOM counts the triangles whose divisor lies outside [2^-62, 2^125] (none: DSceneView::fastBary may stand).
+enum { RL_MOVE_NONFINITE = 0, RL_MOVE_BAD_DENOM = 1, RL_MOVE_WORDS = 4 };
+__global__ void __launch_bounds__(RL_BLOCK) k_move_count(const DTriIsect* __restrict__ isect, uint32_t numTris, uint32_t* __restrict__ status);
+__global__ void __launch_bounds__(RL_BLOCK) k_move_scan(const float* __restrict__ positions, const float* __restrict__ normals, uint32_t floats, uint32_t* __restrict__ status);
+__global__ void __launch_bounds__(RL_BLOCK)
+k_move_records(DTriIsect* __restrict__ isect, DTriShade* __restrict__ shade, const int32_t* __restrict__ slotOf, uint32_t first, uint32_t count, uint32_t numTris,
+               const float* __restrict__ positions, const float* __restrict__ normals, uint32_t* __restrict__ status);
+__global__ void __launch_bounds__(RL_BLOCK)
+k_refit_level(DNode* nodes, const DTriIsect* __restrict__ isect, const uint32_t* __restrict__ levelNodes, uint32_t count, uint32_t numNodes, uint32_t numTris);
+__global__ void __launch_bounds__(RL_BLOCK)
+k_refit_wide4(const DNode* __restrict__ nodes, uint32_t numNodes, const int32_t* __restrict__ boxOf, DNode4* __restrict__ nodes4f, DNode4Q* __restrict__ nodes4q, uint32_t count);
+__global__ void __launch_bounds__(RL_BLOCK)
+k_refit_wide8(const DNode* __restrict__ nodes, uint32_t numNodes, const int32_t* __restrict__ boxOf, DNode8* __restrict__ nodes8, uint32_t count);
 
 // ---------------------------------------------------------------------------
 // Test hooks (rl_rt_hooks.hip): single functions of the hot path evaluated on arrays

@@ -6,6 +6,7 @@
 //   rl_rt_render.hip  whole frames over N ranks (gather, scatter, two frames in flight), DeviceRender, progressive sessions
 //   rl_rt_rays.hip    caller rays: DeviceTraceRays, DeviceTraceRadiance, DeviceGather (plain and adaptive: one driver, GatherLocked)
 //   rl_rt_lightmap.hip  lightmaps: DeviceLightmapPoints, DeviceBakeLightmap (the raster stages, then DeviceGather's body or the caller's atlas, the filter, the atlas stages)
+//   rl_rt_move.hip    RaylibAMD_SceneMoveTriangles: the moved records and the refit of every tree on the device, the host copies' read-back, RaylibAMD_SceneCheckTrees
 //   rl_rt_hooks.hip   test hooks
 //
 // Ranks.  RAYLIB_NUM_GPUS = N (default 1) makes the library drive N devices from this one process: the frame's 8x8
@@ -84,6 +85,20 @@ struct DeviceSceneCopy {
 	DevBuf<float4> sky;
 	const Image* skyImage = nullptr; uint64_t skyVersion = 0;
 	DSceneView view;
+	// What moves of the scene's triangles need beside the scene (rl_rt_move.hip), made at the first move: the inverse of triOrder, the binary nodes sorted by
+	// level (levelStart[d] ... levelStart[d + 1]: level d), the wide records' box ids (rl_host.h BVH::boxOf*), a host call's values, the status block
+	// (rl_kernels.h RL_MOVE_*) and the pinned copy of it and of the root node (16 words behind the block) that the last move's event guards.
+	struct Move {
+		DevBuf<int32_t> slotOf, boxOf4, boxOf8, boxOfLeafList; DevBuf<uint32_t> levelNodes; std::vector<uint32_t> levelStart;
+		DevBuf<float> staging; DevBuf<uint32_t> status; PinBuf<uint32_t> statusHost;
+		hipEvent_t ev = nullptr;
+		hipEvent_t inEv = nullptr, copiedEv = nullptr;   // several devices, a device call: the values are ready on the call's stream / have reached this device
+		bool pending = false;        // a move has been enqueued and its status not yet read (SettleMove)
+		int32_t fastBaryBase = 1;    // RAYLIB_FAST_BARY as a fresh upload reads it
+	};
+	Move* move = nullptr;
+	bool lmTrisStale = false;    // lmTris predates a move: uploaded again when a lightmap call next needs it
+	~DeviceSceneCopy() { if (move) { for (hipEvent_t e : { move->ev, move->inEv, move->copiedEv }) if (e) (void)hipEventDestroy(e); delete move; } }
 };
 struct DeviceScene {
 	std::vector<DeviceSceneCopy*> copy;   // by device slot (Runtime::devices)
@@ -256,7 +271,9 @@ bool EnsureRccl();
 int OccupancyOf(RankCtx& R, const void* kernel, const TracePlan* megakernel = nullptr);
 bool UploadScene(Scene& sc);                           // rl_rt_scene.hip
 bool SyncSky(Scene& sc);
-bool EnsureWideTree(DeviceSceneCopy* C, const Scene& sc, int32_t tree);
+bool EnsureWideTree(DeviceSceneCopy* C, Scene& sc, int32_t tree);
+bool SettleMove(Scene& sc);                            // rl_rt_move.hip: a move in flight is complete and its status applied (the scene is on the device)
+bool SyncMovedLocked(Scene& sc);                       // DeviceSyncMovedScene behind its entry
 bool ReadbackLocked(Image& img);                       // device copy -> img.rgba
 bool EnqueueRender(RankCtx& R, Scene& sc, const RenderRequest& req, PendingRender& pend, ProgressiveSession* prog = nullptr);   // rl_rt_frame.hip
 bool FinishRender(RankCtx& R, PendingRender& pend, RaylibAMDStats& stats);

@@ -106,7 +106,7 @@ static uint64_t CoveredPixels(uint32_t W, uint32_t H, uint32_t cellFirst, uint32
 
 // the scene as a plan's kernels read it: the plan's wide tree is on the device (EnsureWideTree), the wide nodes it does not walk are out of the view (k_trace tells the tree
 // by which is set; a debug mode's plan keeps both)
-static bool TraceView(DeviceSceneCopy* D, const Scene& sc, const TracePlan& plan, DSceneView& view)
+static bool TraceView(DeviceSceneCopy* D, Scene& sc, const TracePlan& plan, DSceneView& view)
 {
 	if (!EnsureWideTree(D, sc, plan.tree)) return false;
 	view = D->view;

@@ -42,7 +42,8 @@ static bool Raster(Scene& sc, RankCtx& R, const RaylibAMDLightmapParams& P, int3
 {
 	if (!UploadScene(sc)) return false;
 	DeviceSceneCopy* Cp = sc.device->copy[(size_t)R.devSlot];
-	if (!Cp->lmTris.ptr && !Cp->lmTris.Upload((const float*)sc.triangles.data(), sc.triangles.size() * 26)) { Cp->lmTris.Free(); return false; }
+	if ((!Cp->lmTris.ptr || Cp->lmTrisStale) && (!SyncMovedLocked(sc) || !Cp->lmTris.Upload((const float*)sc.triangles.data(), sc.triangles.size() * 26))) { Cp->lmTris.Free(); return false; }
+	Cp->lmTrisStale = false;
 	const hipStream_t st = R.stream;
 	const uint32_t nTri = (uint32_t)triCount, nTex = (uint32_t)P.width * (uint32_t)P.height;   // (<= 2^28)
 	if (!R.lmRec.Grow((size_t)nTri * sizeof(DLmTri)) || !R.lmCounts.Grow(((size_t)nTri + 1) * sizeof(unsigned long long)) || !R.lmHost.Grow(2 * sizeof(unsigned long long))) return false;

@@ -14,8 +14,10 @@ static bool UploadOnce(DevBuf<T>& have, const T*& inView, const std::vector<T>& 
 	inView = have.ptr;
 	return true;
 }
-bool EnsureWideTree(DeviceSceneCopy* C, const Scene& sc, int32_t tree)
+bool EnsureWideTree(DeviceSceneCopy* C, Scene& sc, int32_t tree)
 {
+	// (after a move the host's wide trees are behind the device's binary tree: they are re-derived before one of them is uploaded for the first time)
+	if ((tree == TREE_WIDE8 ? !C->nodes8.ptr : tree == TREE_GRID4 ? !C->nodes4.ptr : false) && !SyncMovedLocked(sc)) return false;
 	if (tree == TREE_WIDE8) return UploadOnce(C->nodes8, C->view.nodes8, sc.bvh.nodes8);
 	if (tree == TREE_GRID4) return UploadOnce(C->nodes4, C->view.nodes4, sc.bvh.nodes4q);
 	return true;
@@ -31,7 +33,7 @@ static void FreeScene(DeviceScene* D)
 // A copy of the flattened scene (device records in leaf order) to every device in use.
 bool UploadScene(Scene& sc)
 {
-	if (sc.device) return true;
+	if (sc.device) return SettleMove(sc);
 	for (size_t i = 0; i < sc.textures.size(); ++i) {
 		Image& im = *sc.textures[i];
 		if (!im.hostStale) continue;   // a rendered image used as a texture: fetch it

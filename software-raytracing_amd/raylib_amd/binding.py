@@ -147,6 +147,34 @@ def trace_rays(lib, scene, rays, kind, ray_time=0.0, with_prim=False):
     return (out, prim) if with_prim else out
 
 
+def move_triangles(lib, scene, first, positions, normals=None):
+    """Move triangles [first, first + n) of a finalized scene (RaylibAMD_SceneMoveTriangles / RaylibAMD_SceneMoveTrianglesDevice).
+
+    positions: (n, 9) float32 -- v0 v1 v2 per triangle, RaylibAMD_SceneExportTriangles order; normals: the same shape (n0 n1 n2), or None to keep the shading
+    normals.  NumPy arrays go through the host entry (synchronous).  float32 torch tensors on the device go through the device entry on
+    torch.cuda.current_stream(), as trace_rays: enqueued on a stream of the caller's, synchronous on torch's default stream (synchronised first).
+    Returns the library's answer: 1, or 0 when it refuses the move (nothing changed)."""
+    if isinstance(positions, np.ndarray):
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 9)
+        nr = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 9)
+        if nr is not None and len(nr) != len(p):
+            raise ValueError("normals: one row per row of positions")
+        return lib.RaylibAMD_SceneMoveTriangles(scene, int(first), len(p), _fp(p), None if nr is None else _fp(nr))
+    import torch
+    ok = lambda t: isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
+    if not ok(positions) or not (normals is None or ok(normals)):
+        raise TypeError("positions / normals: float32 NumPy arrays, or float32 torch tensors on the device")
+    p = positions.reshape(-1, 9).contiguous()
+    nr = None if normals is None else normals.reshape(-1, 9).contiguous()
+    if nr is not None and nr.shape[0] != p.shape[0]:
+        raise ValueError("normals: one row per row of positions")
+    stream = torch.cuda.current_stream(p.device)
+    if stream.cuda_stream == 0:
+        stream.synchronize()   # (the library's stream is not ordered against torch's default stream: trace_rays)
+    return lib.RaylibAMD_SceneMoveTrianglesDevice(scene, int(first), p.shape[0], C.c_void_p(p.data_ptr()), None if nr is None else C.c_void_p(nr.data_ptr()),
+                                                  C.c_void_p(stream.cuda_stream))
+
+
 class PathRay(C.Structure):
     """include/raylib_amd.h RaylibAMDPathRay (32 bytes): org, time, dir, stream."""
     _fields_ = [("org", C.c_float * 3), ("time", C.c_float), ("dir", C.c_float * 3), ("stream", C.c_uint32)]
@@ -690,6 +718,12 @@ _EXPORTS = {
     "RaylibAMD_SceneWalk8Host": (C.c_int32, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "RaylibAMD_SceneWalkStackHost": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "RaylibAMD_SceneBVHHash": (C.c_uint64, [C.c_void_p]),
+    "RaylibAMD_SceneTopologyHash": (C.c_uint64, [C.c_void_p]),
+    "RaylibAMD_SceneExportBVHNodes": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "RaylibAMD_SceneMoveTriangles": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "RaylibAMD_SceneMoveTrianglesDevice": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_SceneRebuild": (C.c_int32, [C.c_void_p]),
+    "RaylibAMD_SceneCheckTrees": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "RaylibAMD_CameraExport": (None, [C.c_void_p, C.POINTER(C.c_float)]),
     "RaylibAMD_CreateImageFromData": (C.c_void_p, [C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
     "RaylibAMD_DumpImageRGBA": (None, [C.c_void_p, C.POINTER(C.c_float)]),

@@ -25,6 +25,9 @@ void DeviceFreePixels(void*) {}
 bool DeviceEvalMath(int, const float*, const float*, int, float*) { return false; }
 bool DeviceEvalHook(int, Scene*, const DCamera*, int, int, const float*, int, uint64_t, float*) { return false; }
 void DeviceReleaseScene(DeviceScene*) {}
+bool DeviceMoveTriangles(Scene&, int32_t, int32_t, const float*, const float*, bool, void*) { return false; }
+bool DeviceSyncMovedScene(Scene&) { return true; }   // (never uploaded: the host's copies are the scene)
+bool DeviceCheckTrees(Scene&, uint32_t*) { return false; }
 int DeviceNumRanks() { return 0; }
 bool DeviceDrain(RaylibAMDStats*) { return false; }
 void DeviceOwnStats() {}
