@@ -167,6 +167,58 @@ typedef struct RaylibAMDQueryPlan {
 } RaylibAMDQueryPlan;
 RAYLIB_API int32_t RaylibAMD_PlanRayQuery(SceneHandle scene, int32_t kind, RaylibAMDQueryPlan* out);
 
+/* ---- batched nearest-point queries ---------------------------------------------------------------
+ * Which triangle of the scene is nearest to a point, how far away, and where on it -- for contact and collision behind RaylibAMD_SceneMoveTriangles, distance
+ * fields, snapping points onto geometry, attribute transfer.  The result equals a loop over every triangle bit for bit, with no slack factor anywhere, on
+ * every tree, fresh or refitted (csrc/rl_nearest.h holds the statements for the host oracle and the kernel alike; csrc/rl_k_nearest.inl is the walk).
+ * Everything is float, without FMA.  1.0f / x and a / b are the IEEE values.  dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+ * For point p and triangle k, in RaylibAMD_SceneExportTriangles order, with vertices v0 v1 v2:
+ *   N1. Closest point (Ericson's regions; the first condition that holds decides):
+ *        ab = v1 - v0, ac = v2 - v0, ap = p - v0; d1 = dot(ab, ap), d2 = dot(ac, ap).  If d1 <= 0 && d2 <= 0: (b1, b2) = (0, 0).
+ *        bp = p - v1; d3 = dot(ab, bp), d4 = dot(ac, bp).  If d3 >= 0 && d4 <= d3: (1, 0).
+ *        vc = d1*d4 - d3*d2.  If vc <= 0 && d1 >= 0 && d3 <= 0: (d1 / (d1 - d3), 0).
+ *        cp = p - v2; d5 = dot(ab, cp), d6 = dot(ac, cp).  If d6 >= 0 && d5 <= d6: (0, 1).
+ *        vb = d5*d2 - d1*d6.  If vb <= 0 && d2 >= 0 && d6 <= 0: (0, d2 / (d2 - d6)).
+ *        va = d3*d6 - d5*d4; e = d4 - d3, g = d5 - d6.  If va <= 0 && e >= 0 && g >= 0: w = e / (e + g), (1.0f - w, w).
+ *        Otherwise den = 1.0f / ((va + vb) + vc), (vb*den, vc*den).
+ *        q = (v0 + b1*ab) + b2*ac; r = p - q; E = dot(r, r).
+ *   N2. Own box.  lo, hi are the componentwise least and greatest of the three vertices, found by comparisons.  Per axis: t = lo - p, u = p - hi,
+ *        d = t > 0 ? t : (u > 0 ? u : 0).  B = (dx*dx + dy*dy) + dz*dz.
+ *   N3. The triangle's distance.  D = (E >= B) ? E : B.  A NaN E from a degenerate triangle therefore yields B.
+ *        In exact arithmetic E >= B always holds, so the rule only moves D at rounding level.  It buys this: the binary tree's float boxes are nested exactly
+ *        (a parent is the min / max of its children), the grid boxes of the 4-wide nodes contain them exactly (csrc/rl_grid.h), and statement N2 is monotone
+ *        under nesting because every operation rounds monotonically -- hence a node whose N2 distance exceeds the best D found so far cannot hold a winner, and
+ *        no widening factor is needed.  (Without N3 a tight leaf box can drop the true nearest triangle: its E may round below its own box's B.)
+ *   N4. Result.  A point takes part when every pos component is finite and maxDist >= 0 (+inf is allowed; NaN and negative values are not; -0.0 is 0).
+ *        R2 = maxDist * maxDist.  Triangle k is a candidate when D_k <= R2.  CLOSEST returns the candidate with the least (D, k) in lexicographic order -- ties go
+ *        to the lower export index, whatever the tree -- and writes {D, k, b1, b2} of that triangle.  WITHIN returns 1 exactly when a candidate exists.  A point
+ *        that does not take part, or has no candidate, misses.
+ *   N5. Independence.  The result does not depend on the tree walked, the order of the walk, how the call is cut into waves, or whether the trees were built
+ *        fresh or refitted by RaylibAMD_SceneMoveTriangles.  After a move the query sees the moved triangles, as every other call on the scene does; the host
+ *        oracle refreshes the host's stale copies first.
+ * Refusals (0, nothing written): a null pointer with n > 0; n < 0; an unknown kind; a scene that is not finalized; a scene that holds spheres or cubes (out
+ * of scope here, and refused rather than silently ignored); a BVH deeper than 64 levels; no device (the device and plain entries); on the device entry a pointer
+ * off rank 0's device, points not 16-byte aligned, out not 16-byte aligned for CLOSEST or not 4-byte aligned for WITHIN.  n == 0 returns 1.
+ * Checked against a loop over every triangle: tests/test_nearest_host.py, tests/test_gpu_nearest.py. */
+typedef struct RaylibAMDNearestQuery { float pos[3]; float maxDist; } RaylibAMDNearestQuery;        /* 16 bytes, one 16-byte load */
+typedef struct RaylibAMDNearestHit   { float dist2; int32_t prim; float b1, b2; } RaylibAMDNearestHit; /* 16 bytes; a miss: dist2 = b1 = b2 = 0, prim = -1 */
+#define RAYLIB_AMD_NEAREST_WITHIN  0   /* out: uint32_t per point, 1 when a triangle lies within maxDist (may stop at the first one) */
+#define RAYLIB_AMD_NEAREST_CLOSEST 1   /* out: RaylibAMDNearestHit per point */
+/* n points from host memory, results to host memory; synchronous, on the device.  The library keeps its device staging buffers and grows them.
+ * RaylibAMD_GetLastStats then reports rays (= points), nodesVisited, trisTested, kernelMs, wallMs and the tree walked. */
+RAYLIB_API int32_t RaylibAMD_NearestPoints(SceneHandle scene, int32_t kind, const RaylibAMDNearestQuery* points, int32_t n, void* out);
+/* The same on device pointers (rank 0's device).  The stream, stats and multi-rank rules are RaylibAMD_TraceRaysDevice's: stream == NULL is the library's
+ * stream, synchronous, with stats; a non-null hipStream_t gets the call enqueued behind the synchronous uploads (the scene, a tree or table needed for the first
+ * time) and the stats are left alone.  The call is ordered behind a move of the scene's triangles and behind multi-rank frames in flight as a ray query is. */
+RAYLIB_API int32_t RaylibAMD_NearestPointsDevice(SceneHandle scene, int32_t kind, const RaylibAMDNearestQuery* points, int32_t n, void* out, void* stream);
+/* The oracle: statements N1 to N4 over every triangle, no tree, no device. */
+RAYLIB_API int32_t RaylibAMD_NearestPointsHost(SceneHandle scene, int32_t kind, const RaylibAMDNearestQuery* points, int32_t n, void* out);
+/* Which tree and kernel instance those calls would walk under the current environment (csrc/rl_plan.cc PlanNearest): the grid-4 tree when the scene has one
+ * (worst-case stack within 64), else the binary tree; RAYLIB_QUERY_TREE=2 forces the binary tree, =8 falls through to 4 (there is no 8-wide nearest walk yet).
+ * `early` is 1 for WITHIN.  No device needed.  Returns 1, -1 when the BVH is deeper than 64 levels, 0 for a null argument, an unknown kind, a scene not
+ * finalized or one that holds spheres or cubes. */
+RAYLIB_API int32_t RaylibAMD_PlanNearest(SceneHandle scene, int32_t kind, RaylibAMDQueryPlan* out);
+
 /* ---- path-traced radiance along caller rays -----------------------------------------------------
  * outRGBA[i] = (the mean over the samples of TraceScene(rays[i], depth 0, maxPathLength, rayTMin), 1): the reference's path tracer (render/renderer.cc:114-208)
  * with the scene's sun and sky panorama as a render sees them, on rays that need not come from a camera.  The ray is used as given: neither normalised nor

@@ -8,6 +8,7 @@
 #include "rl_plan.h"
 #include "rl_progressive.h"
 #include "rl_lightmap.h"
+#include "rl_nearest.h"
 #include "raylib_amd_rng.h"
 
 #include <math.h>
@@ -825,6 +826,72 @@ int32_t RaylibAMD_PlanRayQuery(SceneHandle sh, int32_t kind, RaylibAMDQueryPlan*
 	const QueryPlan p = PlanQuery(*s, kind, ReadRenderKnobs());
 	if (!p.ok) return -1;
 	out->tree = p.tree; out->treeWidth = p.treeWidth; out->nodeBytes = p.nodeBytes; out->stack = p.stack; out->prims = p.prims; out->early = p.early;
+	return 1;
+}
+
+// RaylibAMD_NearestPoints / RaylibAMD_NearestPointsDevice / RaylibAMD_NearestPointsHost / RaylibAMD_PlanNearest: the refusals every entry shares
+static bool NearestArgsValid(const char* who, const Scene* s, int32_t kind, const void* points, int32_t n, const void* out)
+{
+	if (!s || n < 0 || (n > 0 && (!points || !out))) { Log("%s: null argument", who); return false; }
+	if (!s->finalized) { Log("%s: scene was not finalized (Raylib_FinalizeScene)", who); return false; }
+	if (kind != RAYLIB_AMD_NEAREST_WITHIN && kind != RAYLIB_AMD_NEAREST_CLOSEST) { Log("%s: unknown nearest kind %d", who, kind); return false; }
+	if (!s->spheres.empty() || !s->cubes.empty()) { Log("%s: the scene holds spheres or cubes; nearest-point queries are defined on triangles", who); return false; }
+	if (s->bvh.depth > 64) { Log("%s: BVH depth %u exceeds the traversal stack (64)", who, s->bvh.depth); return false; }
+	return true;
+}
+static int32_t NearestPointsInternal(const char* who, SceneHandle sh, int32_t kind, const RaylibAMDNearestQuery* points, int32_t n, void* out, bool hostMem, void* stream)
+{
+	Scene* s = (Scene*)sh;
+	if (!NearestArgsValid(who, s, kind, points, n, out)) return 0;
+	if (!DeviceAvailable()) return 0;
+	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
+	if (!DeviceNearestPoints(*s, kind, points, n, out, hostMem, stream, stats)) return 0;
+	if (!stream) ReportOwnStats(stats);
+	return 1;
+}
+int32_t RaylibAMD_NearestPoints(SceneHandle sh, int32_t kind, const RaylibAMDNearestQuery* points, int32_t n, void* out)
+{
+	return NearestPointsInternal("RaylibAMD_NearestPoints", sh, kind, points, n, out, true, nullptr);
+}
+int32_t RaylibAMD_NearestPointsDevice(SceneHandle sh, int32_t kind, const RaylibAMDNearestQuery* points, int32_t n, void* out, void* stream)
+{
+	return NearestPointsInternal("RaylibAMD_NearestPointsDevice", sh, kind, points, n, out, false, stream);
+}
+// the oracle: statements N1 to N4 (rl_nearest.h, the kernel's own source) over every triangle in export order
+int32_t RaylibAMD_NearestPointsHost(SceneHandle sh, int32_t kind, const RaylibAMDNearestQuery* points, int32_t n, void* out)
+{
+	Scene* s = (Scene*)sh;
+	if (!NearestArgsValid("RaylibAMD_NearestPointsHost", s, kind, points, n, out)) return 0;
+	if (!DeviceSyncMovedScene(*s)) return 0;
+	const size_t numTris = s->triangles.size();
+	for (int32_t i = 0; i < n; ++i) {
+		const RaylibAMDNearestQuery& Q = points[i];
+		RaylibAMDNearestHit best = { 0.0f, -1, 0.0f, 0.0f };
+		if (NearestTakesPart(Q.pos[0], Q.pos[1], Q.pos[2], Q.maxDist)) {
+			const float R2 = Q.maxDist * Q.maxDist;
+			for (size_t k = 0; k < numTris; ++k) {
+				const HostTriangle& t = s->triangles[k];
+				float b1, b2;
+				const float E = NearestTriangleE(Q.pos, &t.v0.x, &t.v1.x, &t.v2.x, b1, b2);
+				const float D = NearestTriangleD(E, NearestOwnBoxDist2(Q.pos, &t.v0.x, &t.v1.x, &t.v2.x));
+				if (!(D <= R2) || (best.prim >= 0 && !(D < best.dist2))) continue;   // (ascending k: an equal D keeps the lower index)
+				best.dist2 = D; best.prim = (int32_t)k; best.b1 = b1; best.b2 = b2;
+				if (kind == RAYLIB_AMD_NEAREST_WITHIN) break;
+			}
+		}
+		if (kind == RAYLIB_AMD_NEAREST_WITHIN) ((uint32_t*)out)[i] = best.prim >= 0 ? 1u : 0u;
+		else ((RaylibAMDNearestHit*)out)[i] = best.prim >= 0 ? best : RaylibAMDNearestHit{ 0.0f, -1, 0.0f, 0.0f };
+	}
+	return 1;
+}
+int32_t RaylibAMD_PlanNearest(SceneHandle sh, int32_t kind, RaylibAMDQueryPlan* out)
+{
+	Scene* s = (Scene*)sh;
+	if (!s || !s->finalized || !out || (kind != RAYLIB_AMD_NEAREST_WITHIN && kind != RAYLIB_AMD_NEAREST_CLOSEST) || !s->spheres.empty() || !s->cubes.empty()) return 0;
+	memset(out, 0, sizeof(*out));
+	const QueryPlan p = PlanNearest(*s, kind, ReadRenderKnobs());
+	if (!p.ok) return -1;
+	out->tree = p.tree; out->treeWidth = p.treeWidth; out->nodeBytes = p.nodeBytes; out->stack = p.stack; out->prims = 0; out->early = p.early;
 	return 1;
 }
 

@@ -270,6 +270,8 @@ bool DeviceClosestHit(Scene& scene, const float* rays, int32_t n, float tMin, vo
 // synchronous; else enqueued on that hipStream_t).  stats: filled by a synchronous call.  kind is valid, n >= 0, the scene finalized: the ABI checked.
 bool DeviceTraceRays(Scene& scene, int32_t kind, const void* rays, int32_t n, float rayTime, void* out, int32_t* outPrim, bool hostMem, void* stream,
                      RaylibAMDStats& stats);
+// RaylibAMD_NearestPoints (hostMem) and RaylibAMD_NearestPointsDevice, as DeviceTraceRays; the scene holds triangles only: the ABI checked.
+bool DeviceNearestPoints(Scene& scene, int32_t kind, const void* points, int32_t n, void* out, bool hostMem, void* stream, RaylibAMDStats& stats);
 // RaylibAMD_TraceRadiance (hostMem) and RaylibAMD_TraceRadianceDevice, as DeviceTraceRays; prm is valid (timeMin <= timeMax cover every ray's time and the
 // scene's boxes), seed is the library's: the ABI checked.
 // The path stack's budget: the grid is cut until its stack (32 bytes per bounce and resident lane) fits, and a maxPathLength at which one workgroup of 256

@@ -9,6 +9,8 @@
 //                        changes how two loops of the eager PLAIN instance are scheduled
 //   rl_render_pool.hip   k_trace_pool and its twin: a scheduler strategy of its own (Makefile POOLFLAGS)
 //   rl_query.hip         k_query (RaylibAMD_TraceRays): beside the render kernels it would change how the walks they share are inlined into those
+//   rl_nearest.hip       k_nearest (RaylibAMD_NearestPoints): a walk of its own (point-to-box distances, no ray), which shares with the others the records and the
+//                        child sort alone; apart so that every other unit stays the code it is
 //   rl_radiance.hip      k_radiance (RaylibAMD_TraceRadiance): the same reason, towards the render and the query kernels alike
 //   rl_gather.hip        k_gather (RaylibAMD_Gather: rl_k_radiance.inl's twin, the generator instances of its loop) and k_gather_resolve: beside k_radiance they would be
 //                        more callers of the walks and the shading it inlines.  k_gather_resolve and k_gather_adaptive_resolve are one source, rl_k_gather_resolve.inl,
@@ -167,6 +169,20 @@ template <int TREE, int KIND, int STACK, bool PRIMS> __global__ void __launch_bo
 #define RL_QUERY_INSTANCES(X) RL_QUERY_INSTANCES_K(X, 0) RL_QUERY_INSTANCES_K(X, 1) RL_QUERY_INSTANCES_K(X, 2)
 #define RL_K_QUERY(a, b, c, d) template __global__ void k_query<a, b, c, d>(RL_QUERY_ARGS);
 RL_QUERY_INSTANCES(extern RL_K_QUERY)
+
+// ---------------------------------------------------------------------------
+// The nearest-point queries (RaylibAMD_NearestPoints; rl_k_nearest.inl, arithmetic of rl_nearest.h)
+enum { RL_NK_WITHIN = 0, RL_NK_CLOSEST = 1 };   // RAYLIB_AMD_NEAREST_*
+struct DNearestHit { float dist2; int32_t prim; float b1, b2; };   // RaylibAMDNearestHit
+// TREE: 2 the binary tree (S.nodes), 4 the grid nodes (S.nodes4).  STACK: the walk's stack.  points: n float4 (pos, maxDist).  out: uint32_t (WITHIN) or
+// DNearestHit (CLOSEST) per point.  slotIndex: triangle slot -> export index (null: the identity).  counters: CNT_RAYS (points), CNT_NODES, CNT_TRIS sums, or null.
+#define RL_NEAREST_ARGS const DSceneView, const float4* __restrict__, uint32_t, void* __restrict__, const int32_t* __restrict__, unsigned int* __restrict__, unsigned long long* __restrict__
+template <int TREE, int KIND, int STACK> __global__ void __launch_bounds__(RL_BLOCK) k_nearest(RL_NEAREST_ARGS);
+// The instances rl_rt_rays.hip NearestKernelOfKind selects from: (TREE, KIND, STACK)
+#define RL_NEAREST_INSTANCES_K(X, K) X(2, K, 32) X(2, K, 64) X(4, K, 32) X(4, K, 64)
+#define RL_NEAREST_INSTANCES(X) RL_NEAREST_INSTANCES_K(X, 0) RL_NEAREST_INSTANCES_K(X, 1)
+#define RL_K_NEAREST(a, b, c) template __global__ void k_nearest<a, b, c>(RL_NEAREST_ARGS);
+RL_NEAREST_INSTANCES(extern RL_K_NEAREST)
 
 // ---------------------------------------------------------------------------
 // Path-traced radiance along caller rays (RaylibAMD_TraceRadiance; rl_k_radiance.inl)

@@ -172,6 +172,13 @@ QueryPlan PlanRadiance(const Scene& sc, const RenderKnobs& k)
 	return p;
 }
 
+QueryPlan PlanNearest(const Scene& sc, int32_t kind, const RenderKnobs& k)
+{
+	QueryPlan p = PlanRadiance(sc, k);   // the same trees under the same switch
+	p.early = kind == RAYLIB_AMD_NEAREST_WITHIN;
+	return p;
+}
+
 GatherCut PlanGatherCut(uint32_t n, uint32_t sampleCount, bool sphere, const RenderKnobs& k)
 {
 	GatherCut c;

@@ -81,6 +81,11 @@ QueryPlan PlanQuery(const Scene& sc, int32_t kind, const RenderKnobs& knobs);
 // carries one, has no spheres or cubes and its worst-case stack fits 64 entries; else the binary tree.  The 8-wide walk is a step walk and not fused with
 // shading here: RAYLIB_QUERY_TREE=8 falls through to 4, =2 walks the binary tree.  `early` is unused (false).
 QueryPlan PlanRadiance(const Scene& sc, const RenderKnobs& knobs);
+// Which tree and k_nearest instance a batch of nearest-point queries walks (RaylibAMD_NearestPoints, rl_k_nearest.inl): the grid-4 tree when the scene carries
+// one and its worst-case stack fits 64 entries; else the binary tree.  The walk pushes at most (children - 1) references per level, as the ray walks do, so
+// their stack bounds are its bounds.  There is no 8-wide nearest walk: RAYLIB_QUERY_TREE=8 falls through to 4, =2 walks the binary tree.  `early`: the kind is
+// WITHIN.  The scene holds triangles only (the entries refuse spheres and cubes before they plan).
+QueryPlan PlanNearest(const Scene& sc, int32_t kind, const RenderKnobs& knobs);
 
 // How RaylibAMD_Gather cuts n points x sampleCount samples into launches (rl_rt_rays.hip DeviceGather; RaylibAMD_PlanGatherCut): a launch holds at most `slots`
 // (point, sample) pairs -- RL_GATHER_SAMPLE_BUDGET over the slot's bytes (16 for IRRADIANCE, 32 for SH9), or RAYLIB_GATHER_BATCH, at most RL_GATHER_MAX_SLOTS.

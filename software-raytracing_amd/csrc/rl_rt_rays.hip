@@ -1,4 +1,4 @@
-// Host runtime: rays of the caller's -- the ray queries (RaylibAMD_TraceRays, k_query), path-traced radiance (RaylibAMD_TraceRadiance, k_radiance) and the
+// Host runtime: rays of the caller's -- the ray queries (RaylibAMD_TraceRays, k_query), the nearest-point queries that share their call (RaylibAMD_NearestPoints, k_nearest), path-traced radiance (RaylibAMD_TraceRadiance, k_radiance) and the
 // irradiance and SH probes gathered from it at caller points (RaylibAMD_Gather, k_gather + k_gather_resolve) on rank 0's device, from host memory or from device pointers, on the library's stream (synchronous, with stats) or enqueued on a stream of the caller's (rl_rt.h).
 // The two entries share the refusals of a device call's pointers, the synchronous call's counter block and event pair, the stats' header, the staging of a
 // host call through qRays / qOut, the grid that fills the device once, and the synchronous tail; each keeps its plan and kernel, its parameter block and the
@@ -23,6 +23,16 @@ static QueryKernel QueryKernelOfKind(const QueryPlan& p)
 }
 static_assert(RAYLIB_AMD_QUERY_ANY == RL_QK_ANY && RAYLIB_AMD_QUERY_CLOSEST == RL_QK_CLOSEST && RAYLIB_AMD_QUERY_SURFACE == RL_QK_SURFACE, "query kinds");
 static_assert(sizeof(RaylibAMDRay) == 32 && sizeof(RaylibAMDHitT) == sizeof(DQueryHit) && sizeof(DHitOut) == 44, "query records");
+
+typedef void (*NearestKernel)(const DSceneView, const float4*, uint32_t, void*, const int32_t*, unsigned int*, unsigned long long*);
+template <int KIND>
+static NearestKernel NearestKernelOfKind(const QueryPlan& p)
+{
+	if (p.tree == TREE_GRID4) return p.stack <= 32 ? (NearestKernel)k_nearest<4, KIND, 32> : (NearestKernel)k_nearest<4, KIND, 64>;
+	return p.stack <= 32 ? (NearestKernel)k_nearest<2, KIND, 32> : (NearestKernel)k_nearest<2, KIND, 64>;
+}
+static_assert(RAYLIB_AMD_NEAREST_WITHIN == RL_NK_WITHIN && RAYLIB_AMD_NEAREST_CLOSEST == RL_NK_CLOSEST, "nearest kinds");
+static_assert(sizeof(RaylibAMDNearestQuery) == 16 && sizeof(RaylibAMDNearestHit) == sizeof(DNearestHit), "nearest records");
 
 typedef void (*RadianceKernel)(const DSceneView, const SkyRot, const DRadianceParams, const float4*, uint32_t, float4*, float*, unsigned int*, unsigned long long*);
 static RadianceKernel RadianceKernelFor(const QueryPlan& p)
@@ -80,11 +90,39 @@ static void StatsHeader(RaylibAMDStats& stats, const QueryPlan& plan, const Scen
 	stats.treeWidth = plan.treeWidth; stats.nodeBytes = plan.nodeBytes;
 	OneRankStats(stats, sc);
 }
-// a host call's rays (n records of 32 bytes) into the rank's staging buffer, behind whatever `st` holds; its results go through qOut
-static bool StageRays(RankCtx& R, const void* rays, int32_t n, size_t outBytes, hipStream_t st)
+// a host call's rays (n records of 32 bytes; a nearest query's points: 16) into the rank's staging buffer, behind whatever `st` holds; its results go through qOut
+static bool StageRays(RankCtx& R, const void* rays, int32_t n, size_t outBytes, hipStream_t st, size_t recordBytes = sizeof(RaylibAMDRay))
 {
-	if (!R.qRays.Grow((size_t)n * sizeof(RaylibAMDRay)) || !R.qOut.Grow(outBytes)) return false;
-	HIP_OK(hipMemcpyAsync(R.qRays.ptr, rays, (size_t)n * sizeof(RaylibAMDRay), hipMemcpyHostToDevice, st));
+	if (!R.qRays.Grow((size_t)n * recordBytes) || !R.qOut.Grow(outBytes)) return false;
+	HIP_OK(hipMemcpyAsync(R.qRays.ptr, rays, (size_t)n * recordBytes, hipMemcpyHostToDevice, st));
+	return true;
+}
+// triangle slot -> index in the scene's triangle order, on the device when a call first needs it
+static bool EnsureSlotIndex(DeviceSceneCopy* Cp, const Scene& sc)
+{
+	if (Cp->slotIndex.ptr || sc.bvh.triOrder.empty()) return true;
+	std::vector<int32_t> idx(sc.bvh.triOrder.begin(), sc.bvh.triOrder.end());
+	if (!Cp->slotIndex.Upload(idx.data(), idx.size())) { Cp->slotIndex.Free(); return false; }
+	return true;
+}
+// The ring of work counters the queries' launches take in turn: the next slot, free again (RL_QUERY_RING launches ago: long done, unless a caller's stream is that
+// far behind) ...
+static bool TakeRingCounter(RankCtx& R, uint32_t& slot)
+{
+	if (!R.qRing.ptr) {
+		if (!R.qRing.Grow(RL_QUERY_RING * sizeof(unsigned int))) return false;
+		for (int k = 0; k < RL_QUERY_RING; ++k) HIP_OK(hipEventCreateWithFlags(&R.qRingEv[k], hipEventDisableTiming));
+	}
+	slot = R.qRingNext;
+	if (R.qRingUsed[slot]) HIP_OK(hipEventSynchronize(R.qRingEv[slot]));
+	return true;
+}
+// ... and the event behind the launch that used it
+static bool ReleaseRingCounter(RankCtx& R, uint32_t slot, hipStream_t st)
+{
+	HIP_OK(hipEventRecord(R.qRingEv[slot], st));
+	R.qRingUsed[slot] = true;
+	R.qRingNext = (slot + 1u) % RL_QUERY_RING;
 	return true;
 }
 // enough workgroups to fill the device once (the waves take their work from a counter: rl_k_query.inl, rl_k_radiance.inl); 0: the occupancy query failed (logged)
@@ -135,18 +173,11 @@ bool DeviceTraceRays(Scene& sc, int32_t kind, const void* rays, int32_t n, float
 	DeviceSceneCopy* Cp = sc.device->copy[(size_t)R.devSlot];
 	if (!EnsureWideTree(Cp, sc, plan.tree)) return false;
 	const bool wantPrim = kind == RAYLIB_AMD_QUERY_CLOSEST || (kind == RAYLIB_AMD_QUERY_SURFACE && outPrim);
-	if (wantPrim && !Cp->slotIndex.ptr && !sc.bvh.triOrder.empty()) {
-		std::vector<int32_t> idx(sc.bvh.triOrder.begin(), sc.bvh.triOrder.end());
-		if (!Cp->slotIndex.Upload(idx.data(), idx.size())) { Cp->slotIndex.Free(); return false; }
-	}
+	if (wantPrim && !EnsureSlotIndex(Cp, sc)) return false;
 	const hipStream_t st = stream ? (hipStream_t)stream : R.stream;
 	const bool sync = !stream;
-	if (!R.qRing.ptr) {
-		if (!R.qRing.Grow(RL_QUERY_RING * sizeof(unsigned int))) return false;
-		for (int k = 0; k < RL_QUERY_RING; ++k) HIP_OK(hipEventCreateWithFlags(&R.qRingEv[k], hipEventDisableTiming));
-	}
-	const uint32_t slot = R.qRingNext;
-	if (R.qRingUsed[slot]) HIP_OK(hipEventSynchronize(R.qRingEv[slot]));   // RL_QUERY_RING launches ago: long done, unless a caller's stream is that far behind
+	uint32_t slot = 0;
+	if (!TakeRingCounter(R, slot)) return false;
 	unsigned int* counter = R.qRing.ptr + slot;
 	if (sync && !EnsureSyncStats(R)) return false;
 	StatsHeader(stats, plan, sc);
@@ -166,11 +197,53 @@ bool DeviceTraceRays(Scene& sc, int32_t kind, const void* rays, int32_t n, float
 	if (sync && !BeginSync(R, st)) return false;
 	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RL_BLOCK), 0, st, view, dRays, (uint32_t)n, rayTime, dOut, dPrim, Cp->slotIndex.ptr, counter, sync ? R.qStats.ptr : nullptr);
 	HIP_OK(hipGetLastError());
-	HIP_OK(hipEventRecord(R.qRingEv[slot], st));
-	R.qRingUsed[slot] = true;
-	R.qRingNext = (slot + 1u) % RL_QUERY_RING;
+	if (!ReleaseRingCounter(R, slot, st)) return false;
 	if (!sync) return true;
 	return FinishSync(R, st, { { hostMem ? out : nullptr, dOut, outBytes }, { hostMem && dPrim ? outPrim : nullptr, dPrim, (size_t)n * sizeof(int32_t) } }, t0, stats);
+}
+
+// A nearest-point call is a ray query's call with another plan and kernel: the same refusals of a device call's pointers, staging buffers, counter ring,
+// synchronous tail, and the same order behind a move (UploadScene settles it) and behind frames in flight (rank 0's stream, or the caller's behind the uploads).
+bool DeviceNearestPoints(Scene& sc, int32_t kind, const void* points, int32_t n, void* out, bool hostMem, void* stream, RaylibAMDStats& stats)
+{
+	const auto t0 = std::chrono::steady_clock::now();
+	std::lock_guard<std::mutex> lk(Rt().lock);
+	if (!EnsureRuntime()) return false;
+	RankCtx& R = Rank0();
+	HIP_OK(hipSetDevice(R.device));
+	const QueryPlan plan = PlanNearest(sc, kind, ReadRenderKnobs());
+	if (!plan.ok) { Log("RaylibAMD_NearestPoints: BVH depth %u exceeds the traversal stack (64)", sc.bvh.depth); return false; }
+	const bool closest = kind == RAYLIB_AMD_NEAREST_CLOSEST;
+	const size_t outBytes = (size_t)n * (closest ? sizeof(DNearestHit) : sizeof(uint32_t));
+	if (!hostMem && n > 0 && !DevicePointersOk("RaylibAMD_NearestPointsDevice", "points", R.device, points, out, closest ? 15u : 3u, nullptr, false)) return false;
+	if (!UploadScene(sc)) return false;
+	DeviceSceneCopy* Cp = sc.device->copy[(size_t)R.devSlot];
+	if (!EnsureWideTree(Cp, sc, plan.tree)) return false;
+	if (closest && !EnsureSlotIndex(Cp, sc)) return false;
+	const hipStream_t st = stream ? (hipStream_t)stream : R.stream;
+	const bool sync = !stream;
+	uint32_t slot = 0;
+	if (!TakeRingCounter(R, slot)) return false;
+	unsigned int* counter = R.qRing.ptr + slot;
+	if (sync && !EnsureSyncStats(R)) return false;
+	StatsHeader(stats, plan, sc);
+	if (n == 0) return true;
+	const float4* dPoints = (const float4*)points; void* dOut = out;
+	if (hostMem) {
+		if (!StageRays(R, points, n, outBytes, st, sizeof(RaylibAMDNearestQuery))) return false;
+		dPoints = R.qRays.ptr; dOut = R.qOut.ptr;
+	}
+	const NearestKernel kernel = closest ? NearestKernelOfKind<RL_NK_CLOSEST>(plan) : NearestKernelOfKind<RL_NK_WITHIN>(plan);
+	const uint32_t blocks = (uint32_t)FillingGrid(R, (const void*)kernel, (uint64_t)n);
+	if (!blocks) return false;
+	const DSceneView view = Cp->view;
+	HIP_OK(hipMemsetAsync(counter, 0, sizeof(unsigned int), st));
+	if (sync && !BeginSync(R, st)) return false;
+	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RL_BLOCK), 0, st, view, dPoints, (uint32_t)n, dOut, Cp->slotIndex.ptr, counter, sync ? R.qStats.ptr : nullptr);
+	HIP_OK(hipGetLastError());
+	if (!ReleaseRingCounter(R, slot, st)) return false;
+	if (!sync) return true;
+	return FinishSync(R, st, { { hostMem ? out : nullptr, dOut, outBytes } }, t0, stats);
 }
 
 // ---- what a radiance call and a gather share ----

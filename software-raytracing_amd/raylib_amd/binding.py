@@ -147,6 +147,49 @@ def trace_rays(lib, scene, rays, kind, ray_time=0.0, with_prim=False):
     return (out, prim) if with_prim else out
 
 
+NEAREST_WITHIN, NEAREST_CLOSEST = 0, 1              # RAYLIB_AMD_NEAREST_*
+NEAREST_QUERY_DTYPE = np.dtype([("pos", "f4", 3), ("maxDist", "f4")])                          # RaylibAMDNearestQuery
+NEAREST_DTYPE = np.dtype([("dist2", "f4"), ("prim", "i4"), ("b1", "f4"), ("b2", "f4")])        # RaylibAMDNearestHit
+
+
+def plan_nearest(lib, scene, kind):
+    """RaylibAMD_PlanNearest: (return code, plan dict)."""
+    p = QueryPlan()
+    r = lib.RaylibAMD_PlanNearest(scene, int(kind), C.byref(p))
+    return r, p.as_dict()
+
+
+def nearest_points(lib, scene, points, kind, host=False):
+    """Batched nearest-point queries (RaylibAMD_NearestPoints / RaylibAMD_NearestPointsDevice / RaylibAMD_NearestPointsHost).
+
+    points: an (n, 4) float32 array -- pos xyz, maxDist per row.  A NumPy array goes through the host entry (host=True: through the oracle, which needs no
+    device) and returns a NumPy array: uint32 for NEAREST_WITHIN, NEAREST_DTYPE for NEAREST_CLOSEST.  A float32 torch tensor on the device goes through the
+    device entry on torch.cuda.current_stream(), as trace_rays: enqueued on a stream of the caller's, synchronous on torch's default stream (synchronised
+    first).  It returns a tensor: (n,) int32 for WITHIN (0 / 1), (n, 4) int32 words for CLOSEST.  Raises RuntimeError when the library refuses the call."""
+    kind = int(kind)
+    if kind not in (NEAREST_WITHIN, NEAREST_CLOSEST):
+        raise ValueError("unknown nearest kind %r" % kind)
+    if isinstance(points, np.ndarray):
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+        out = np.zeros(len(p), NEAREST_DTYPE if kind == NEAREST_CLOSEST else np.dtype("u4"))
+        name = "RaylibAMD_NearestPointsHost" if host else "RaylibAMD_NearestPoints"
+        if getattr(lib, name)(scene, kind, p.ctypes.data, len(p), out.ctypes.data) != 1:
+            raise RuntimeError(name + " refused the query")
+        return out
+    import torch
+    if host or not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float32):
+        raise TypeError("points: a float32 NumPy array, or a float32 torch tensor on the device (host=False)")
+    p = points.reshape(-1, 4).contiguous()
+    n = p.shape[0]
+    out = torch.empty((n, 4) if kind == NEAREST_CLOSEST else (n,), dtype=torch.int32, device=p.device)
+    stream = torch.cuda.current_stream(p.device)
+    if stream.cuda_stream == 0:
+        stream.synchronize()   # (the library's stream is not ordered against torch's default stream: trace_rays)
+    if lib.RaylibAMD_NearestPointsDevice(scene, kind, C.c_void_p(p.data_ptr()), n, C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)) != 1:
+        raise RuntimeError("RaylibAMD_NearestPointsDevice refused the query")
+    return out
+
+
 def move_triangles(lib, scene, first, positions, normals=None):
     """Move triangles [first, first + n) of a finalized scene (RaylibAMD_SceneMoveTriangles / RaylibAMD_SceneMoveTrianglesDevice).
 
@@ -661,6 +704,10 @@ _EXPORTS = {
     "RaylibAMD_TraceRadiance": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(PathRay), C.c_int32, C.POINTER(C.c_float)]),
     "RaylibAMD_TraceRadianceDevice": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(PathRay), C.c_int32, C.POINTER(C.c_float), C.c_void_p]),
     "RaylibAMD_PlanRadiance": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(QueryPlan)]),
+    "RaylibAMD_NearestPoints": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "RaylibAMD_NearestPointsDevice": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_NearestPointsHost": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "RaylibAMD_PlanNearest": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(QueryPlan)]),
     "RaylibAMD_Gather": (C.c_int32, [C.c_void_p, C.POINTER(GatherParams), C.POINTER(GatherPoint), C.c_int32, C.POINTER(C.c_float)]),
     "RaylibAMD_GatherDevice": (C.c_int32, [C.c_void_p, C.POINTER(GatherParams), C.POINTER(GatherPoint), C.c_int32, C.POINTER(C.c_float), C.c_void_p]),
     "RaylibAMD_GatherDirectionsHost": (C.c_int32, [C.POINTER(GatherParams), C.POINTER(GatherPoint), C.c_int32, C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]),
