@@ -167,6 +167,46 @@ typedef struct RaylibAMDQueryPlan {
 } RaylibAMDQueryPlan;
 RAYLIB_API int32_t RaylibAMD_PlanRayQuery(SceneHandle scene, int32_t kind, RaylibAMDQueryPlan* out);
 
+/* ---- ordered multi-hit ray queries -------------------------------------------------------------
+ * The first maxHits surfaces a ray crosses, in order, and how many it crosses in all: ordered transparency and depth peeling, thickness and x-ray views,
+ * shell and CSG tests, the inside / outside parity of a point -- in one walk of the tree, where peeling with CLOSEST walks it once per layer.
+ * RaylibAMD_TraceRays keeps refusing kind 3; these are entries of their own (csrc/rl_k_multihit.inl is the walk, RaylibAMD_TraceRaysAllHost the oracle).
+ *   M1. Accepted set.  Triangle k is accepted for a ray exactly when a CLOSEST query on [tMin, tMax] could return it: its plane t lies in [max(tMin, 0), tMax]
+ *        (tMin < 0 is read as +0, as above), the barycentric test passes, the renderer's own-box rule passes under the ray's own tMin (with the ray queries'
+ *        widened "own box ends before tMin"), and the cut-out test passes.  The set is a property of the ray and the triangle alone.  A NaN bound or
+ *        tMin > tMax gives the empty set.
+ *   M2. Order.  The accepted triangles are sorted by (t, slot) ascending, slot being the triangle's place in the scene's leaf order -- the key CLOSEST breaks
+ *        ties with.  Row i of outHits holds the first min(maxHits, |set|) of them as {t, prim, b1, b2}, prim the index in RaylibAMD_SceneExportTriangles order,
+ *        and behind them miss records {0, -1, 0, 0}.  So outHits[i * maxHits] is CLOSEST's record byte for byte, and maxHits == 1 is CLOSEST.  Within an
+ *        exact-t tie the order follows the slots: the same on every tree of one build; it may change with RaylibAMD_SceneRebuild, as CLOSEST's winner does.
+ *   M3. Count.  With outCount non-null, outCount[i] = |set|: every crossing of the interval, however small maxHits is.  With outCount null the walk may
+ *        prune with its maxHits-th key and visits less.
+ *   M4. Independence.  The result does not depend on the tree walked, the order of the walk, how the call is cut into waves, or whether the trees were built
+ *        fresh or refitted by RaylibAMD_SceneMoveTriangles (the host oracle refreshes the host's triangles after a move first).
+ *   M5. Refusals (0, nothing written): rays or outHits null with n > 0; n < 0; maxHits outside 1 .. RAYLIB_AMD_MAX_HITS; a rayTime that is not finite; a scene
+ *        that is not finalized; a scene that holds spheres or cubes (a sphere has two crossings and the walk's sphere test reports one: out of scope, and
+ *        refused rather than answered in part); a BVH deeper than 64 levels; n * maxHits above 2^31 - 1; no device (the plain and the device entry; the host
+ *        entry needs none); on the device entry a pointer off rank 0's device, rays or outHits not 16-byte aligned, outCount not 4-byte aligned.  n == 0 returns 1.
+ * Still out: spheres and cubes, more than RAYLIB_AMD_MAX_HITS records per ray (the count is complete all the same), a walk on the grid-4 tree.
+ * Checked against peeling through the brute-force oracle: tests/test_ray_query_all_host.py, tests/test_gpu_ray_query_all.py. */
+#define RAYLIB_AMD_MAX_HITS 16
+/* n rays from host memory, results to host memory; synchronous, on the device.  outHits: n * maxHits RaylibAMDHitT, row i = ray i; outCount: n uint32_t, or null.
+ * rayTime is checked and otherwise unused (triangles do not move with the shutter).  RaylibAMD_GetLastStats then reports rays, nodesVisited, trisTested,
+ * kernelMs, wallMs and the tree walked. */
+RAYLIB_API int32_t RaylibAMD_TraceRaysAll(SceneHandle scene, const RaylibAMDRay* rays, int32_t n, float rayTime, int32_t maxHits, RaylibAMDHitT* outHits, uint32_t* outCount);
+/* The same on device pointers, with the pointer, alignment, stream, stats and multi-rank rules of RaylibAMD_TraceRaysDevice: stream == NULL is the library's
+ * stream, synchronous, with stats; a non-null hipStream_t gets the call enqueued behind the synchronous uploads.  The call is ordered behind a move of the
+ * scene's triangles and behind multi-rank frames in flight as a ray query is. */
+RAYLIB_API int32_t RaylibAMD_TraceRaysAllDevice(SceneHandle scene, const RaylibAMDRay* rays, int32_t n, float rayTime, int32_t maxHits, RaylibAMDHitT* outHits, uint32_t* outCount,
+        void* stream);
+/* The oracle: statements M1 to M3 over every triangle, no tree, no device. */
+RAYLIB_API int32_t RaylibAMD_TraceRaysAllHost(SceneHandle scene, const RaylibAMDRay* rays, int32_t n, float rayTime, int32_t maxHits, RaylibAMDHitT* outHits, uint32_t* outCount);
+/* Which tree and kernel instance those calls would walk under the current environment (csrc/rl_plan.cc PlanQueryAll): the 8-wide tree where PlanRayQuery
+ * would take it, else the binary tree -- there is no grid-4 instance, so RAYLIB_QUERY_TREE=4 gives the binary tree as =2 does.  wantCount (outCount non-null)
+ * selects the instance that never prunes; the tree is the same.  `early` is 0.  No device needed.  Returns 1, -1 when the BVH is deeper than 64 levels, 0 for a
+ * null argument, maxHits outside 1 .. RAYLIB_AMD_MAX_HITS, a scene not finalized or one that holds spheres or cubes. */
+RAYLIB_API int32_t RaylibAMD_PlanRayQueryAll(SceneHandle scene, int32_t maxHits, int32_t wantCount, RaylibAMDQueryPlan* out);
+
 /* ---- batched nearest-point queries ---------------------------------------------------------------
  * Which triangle of the scene is nearest to a point, how far away, and where on it -- for contact and collision behind RaylibAMD_SceneMoveTriangles, distance
  * fields, snapping points onto geometry, attribute transfer.  The result equals a loop over every triangle bit for bit, with no slack factor anywhere, on
@@ -617,6 +657,9 @@ RAYLIB_API int32_t RaylibAMD_SceneNumMaterials(SceneHandle scene);
 RAYLIB_API int32_t RaylibAMD_SceneNumTextures(SceneHandle scene);
 RAYLIB_API void    RaylibAMD_SceneExportTriangles(SceneHandle scene, void* outTriangles);
 RAYLIB_API void    RaylibAMD_SceneExportMaterials(SceneHandle scene, void* outMaterials);
+/* The finalized scene's leaf order: outOrder[slot] = the RaylibAMD_SceneExportTriangles index of the triangle in slot `slot` (RaylibAMD_SceneNumTriangles words).
+ * The slot is what ray queries break exact-t ties with (statement M2).  Returns 1, 0 for a null argument or a scene not finalized. */
+RAYLIB_API int32_t RaylibAMD_SceneExportTriOrder(SceneHandle scene, uint32_t* outOrder);
 RAYLIB_API void    RaylibAMD_SceneTextureSize(SceneHandle scene, int32_t index, int32_t* outW, int32_t* outH);
 RAYLIB_API void    RaylibAMD_SceneExportTexture(SceneHandle scene, int32_t index, float* outRGBA);
 RAYLIB_API void    RaylibAMD_SceneGetSun(SceneHandle scene, float outIlluminance[3], float outDirection[3]);

@@ -11,6 +11,7 @@
 #include "rl_nearest.h"
 #include "raylib_amd_rng.h"
 
+#include <float.h>
 #include <math.h>
 #include <stddef.h>
 #include <stdio.h>
@@ -829,6 +830,118 @@ int32_t RaylibAMD_PlanRayQuery(SceneHandle sh, int32_t kind, RaylibAMDQueryPlan*
 	return 1;
 }
 
+// RaylibAMD_TraceRaysAll / RaylibAMD_TraceRaysAllDevice / RaylibAMD_TraceRaysAllHost / RaylibAMD_PlanRayQueryAll (statements M1 to M5): the refusals every entry shares
+static bool TraceRaysAllArgsValid(const char* who, const Scene* s, const void* rays, int32_t n, float rayTime, int32_t maxHits, const void* outHits)
+{
+	if (!s || n < 0 || (n > 0 && (!rays || !outHits))) { Log("%s: null argument", who); return false; }
+	if (maxHits < 1 || maxHits > RAYLIB_AMD_MAX_HITS) { Log("%s: maxHits %d is outside 1..%d", who, maxHits, RAYLIB_AMD_MAX_HITS); return false; }
+	if (!std::isfinite(rayTime)) { Log("%s: ray time %g is not finite", who, rayTime); return false; }
+	if (!s->finalized) { Log("%s: scene was not finalized (Raylib_FinalizeScene)", who); return false; }
+	if (!s->spheres.empty() || !s->cubes.empty()) { Log("%s: the scene holds spheres or cubes; multi-hit queries are defined on triangles", who); return false; }
+	if (s->bvh.depth > 64) { Log("%s: BVH depth %u exceeds the traversal stack (64)", who, s->bvh.depth); return false; }
+	if ((int64_t)n * maxHits > 0x7fffffffll) { Log("%s: %d rays x %d hits exceed 2^31 - 1 records", who, n, maxHits); return false; }
+	return true;
+}
+static int32_t TraceRaysAllInternal(const char* who, SceneHandle sh, const RaylibAMDRay* rays, int32_t n, float rayTime, int32_t maxHits, RaylibAMDHitT* outHits, uint32_t* outCount,
+                                    bool hostMem, void* stream)
+{
+	Scene* s = (Scene*)sh;
+	if (!TraceRaysAllArgsValid(who, s, rays, n, rayTime, maxHits, outHits)) return 0;
+	if (!DeviceAvailable()) return 0;
+	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
+	if (!DeviceTraceRaysAll(*s, rays, n, maxHits, outHits, outCount, hostMem, stream, stats)) return 0;
+	if (!stream) ReportOwnStats(stats);
+	return 1;
+}
+int32_t RaylibAMD_TraceRaysAll(SceneHandle sh, const RaylibAMDRay* rays, int32_t n, float rayTime, int32_t maxHits, RaylibAMDHitT* outHits, uint32_t* outCount)
+{
+	return TraceRaysAllInternal("RaylibAMD_TraceRaysAll", sh, rays, n, rayTime, maxHits, outHits, outCount, true, nullptr);
+}
+int32_t RaylibAMD_TraceRaysAllDevice(SceneHandle sh, const RaylibAMDRay* rays, int32_t n, float rayTime, int32_t maxHits, RaylibAMDHitT* outHits, uint32_t* outCount, void* stream)
+{
+	return TraceRaysAllInternal("RaylibAMD_TraceRaysAllDevice", sh, rays, n, rayTime, maxHits, outHits, outCount, false, stream);
+}
+// The oracle: every triangle slot in turn with the statements of WalkStackHost's `triangle` (rl_bvh.cc: the plane t, the barycentrics, the own box with the widened
+// tMin clause, the slack) and the cut-out test (rl_dev_scene.h AlphaTestCandidateNI / TexFetch on the material's albedo map, whose converted copy on the device is
+// this powf of each texel), on the ray's own [QueryTMin(tMin), tMax]; the accepted ones sorted by (t, slot).
+int32_t RaylibAMD_TraceRaysAllHost(SceneHandle sh, const RaylibAMDRay* rays, int32_t n, float rayTime, int32_t maxHits, RaylibAMDHitT* outHits, uint32_t* outCount)
+{
+	Scene* s = (Scene*)sh;
+	if (!TraceRaysAllArgsValid("RaylibAMD_TraceRaysAllHost", s, rays, n, rayTime, maxHits, outHits)) return 0;
+	if (!DeviceSyncMovedScene(*s)) return 0;
+	const float widen = 1.00001f, slack = 1.000009f;   // RL_BOX_WIDEN, RL_CANDIDATE_SLACK
+	const std::vector<uint32_t>& order = s->bvh.triOrder;
+	struct Key { float t; uint32_t slot; float b1, b2; };
+	std::vector<Key> keys;
+	for (int32_t i = 0; i < n; ++i) {
+		const RaylibAMDRay& Q = rays[i];
+		const f3 o = F3(Q.org[0], Q.org[1], Q.org[2]), d = F3(Q.dir[0], Q.dir[1], Q.dir[2]);
+		const float oa[3] = { o.x, o.y, o.z }, inv[3] = { 1.0f / d.x, 1.0f / d.y, 1.0f / d.z };
+		const float tMin = Q.tMin < 0.0f ? 0.0f : Q.tMin, tMax = Q.tMax;   // (a NaN bound fails every comparison below)
+		keys.clear();
+		for (uint32_t slot = 0; slot < (uint32_t)order.size(); ++slot) {
+			if (order[slot] >= s->triangles.size()) continue;
+			const HostTriangle& T = s->triangles[order[slot]];
+			const f3 nrm = normalize(cross(T.v1 - T.v0, T.v2 - T.v0));
+			const float t = dot((T.v0 - o), nrm) / dot(d, nrm);
+			if (!(t >= tMin && t <= FLT_MAX && t <= tMax)) continue;
+			const f3 p = o + t * d;
+			const f3 u = T.v1 - T.v0, v = T.v2 - T.v0, w = p - T.v0;
+			const float uv = dot(u, v), wv = dot(w, v), uu = dot(u, u), vv = dot(v, v), wu = dot(w, u);
+			const float denom = uv * uv - uu * vv;
+			const float pa = (uv * wv - vv * wu) / denom, pb = (uv * wu - uu * wv) / denom;
+			if (!(0.0f <= pa && 0.0f <= pb && pa + pb <= 1.0f)) continue;
+			const f3 mn = fmin3(fmin3(T.v0, T.v1), T.v2), mx = fmax3(fmax3(T.v0, T.v1), T.v2);
+			const float mna[3] = { mn.x, mn.y, mn.z }, mxa[3] = { mx.x, mx.y, mx.z };
+			float lo = -INFINITY, hi = FLT_MAX; bool ok = true;
+			for (int a = 0; a < 3; ++a) {
+				float t0 = (mna[a] - oa[a]) * inv[a], t1 = (mxa[a] - oa[a]) * inv[a];
+				if (inv[a] < 0.0f) std::swap(t0, t1);
+				lo = fmaxf(lo, t0); hi = fminf(hi, t1);
+				if (hi < lo) ok = false;
+			}
+			if (!(ok && !(hi * widen < tMin) && t * slack >= fmaxf(lo, tMin))) continue;
+			// the cut-out test: a triangle whose material is a microfacet one with an albedo map
+			if (T.material >= 0 && (size_t)T.material < s->materials.size()) {
+				const HostMaterial& M = s->materials[(size_t)T.material];
+				if (M.type == MAT_MICROFACET && M.tex[0] >= 0 && (size_t)M.tex[0] < s->textures.size()) {
+					const Image& im = *s->textures[(size_t)M.tex[0]];
+					im.SyncHost();
+					float U = (1 - pa - pb) * T.s0 + pa * T.s1 + pb * T.s2;
+					float V = (1 - pa - pb) * T.t0 + pa * T.t1 + pb * T.t2;
+					U = fmodf(U, 1.0f); if (U < 0.0f) U += 1.0f;
+					V = fmodf(V, 1.0f); if (V < 0.0f) V += 1.0f; V = 1.0f - V;
+					if (std::isnan(U) || std::isinf(U)) U = 0.0f;
+					if (std::isnan(V) || std::isinf(V)) V = 0.0f;
+					const int x = (int)((float)(uint32_t)(im.width - 1) * U), y = (int)((float)(uint32_t)(im.height - 1) * V);
+					const float alpha = powf(im.rgba[4 * ((size_t)y * im.width + (size_t)x) + 3], 2.2f);
+					if (!(alpha >= 0.5f)) continue;
+				}
+			}
+			keys.push_back({ t, slot, pa, pb });
+		}
+		std::sort(keys.begin(), keys.end(), [](const Key& a, const Key& b) { return a.t < b.t || (a.t == b.t && a.slot < b.slot); });
+		RaylibAMDHitT* row = outHits + (size_t)i * (size_t)maxHits;
+		for (int32_t k = 0; k < maxHits; ++k) {
+			if ((size_t)k < keys.size()) { row[k].t = keys[(size_t)k].t; row[k].prim = (int32_t)order[keys[(size_t)k].slot]; row[k].b1 = keys[(size_t)k].b1; row[k].b2 = keys[(size_t)k].b2; }
+			else { row[k].t = 0.0f; row[k].prim = -1; row[k].b1 = 0.0f; row[k].b2 = 0.0f; }
+		}
+		if (outCount) outCount[i] = (uint32_t)keys.size();
+	}
+	return 1;
+}
+int32_t RaylibAMD_PlanRayQueryAll(SceneHandle sh, int32_t maxHits, int32_t wantCount, RaylibAMDQueryPlan* out)
+{
+	Scene* s = (Scene*)sh;
+	if (!s || !s->finalized || !out || maxHits < 1 || maxHits > RAYLIB_AMD_MAX_HITS || !s->spheres.empty() || !s->cubes.empty()) return 0;
+	memset(out, 0, sizeof(*out));
+	const QueryPlan p = PlanQueryAll(*s, ReadRenderKnobs());
+	if (!p.ok) return -1;
+	(void)wantCount;   // (the count changes the kernel's instance and what it may prune, not the tree)
+	out->tree = p.tree; out->treeWidth = p.treeWidth; out->nodeBytes = p.nodeBytes; out->stack = p.stack; out->prims = 0; out->early = 0;
+	return 1;
+}
+
 // RaylibAMD_NearestPoints / RaylibAMD_NearestPointsDevice / RaylibAMD_NearestPointsHost / RaylibAMD_PlanNearest: the refusals every entry shares
 static bool NearestArgsValid(const char* who, const Scene* s, int32_t kind, const void* points, int32_t n, const void* out)
 {
@@ -1243,6 +1356,13 @@ void RaylibAMD_SceneTextureSize(SceneHandle sh, int32_t i, int32_t* w, int32_t* 
 	if (!s || i < 0 || i >= (int32_t)s->textures.size()) { if (w) *w = 0; if (h) *h = 0; return; }
 	if (w) *w = (int32_t)s->textures[i]->width;
 	if (h) *h = (int32_t)s->textures[i]->height;
+}
+int32_t RaylibAMD_SceneExportTriOrder(SceneHandle sh, uint32_t* out)
+{
+	Scene* s = (Scene*)sh;
+	if (!s || !s->finalized || !out) return 0;
+	std::copy(s->bvh.triOrder.begin(), s->bvh.triOrder.end(), out);
+	return 1;
 }
 void RaylibAMD_SceneExportTexture(SceneHandle sh, int32_t i, float* out)
 {

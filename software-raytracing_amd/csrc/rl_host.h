@@ -270,6 +270,9 @@ bool DeviceClosestHit(Scene& scene, const float* rays, int32_t n, float tMin, vo
 // synchronous; else enqueued on that hipStream_t).  stats: filled by a synchronous call.  kind is valid, n >= 0, the scene finalized: the ABI checked.
 bool DeviceTraceRays(Scene& scene, int32_t kind, const void* rays, int32_t n, float rayTime, void* out, int32_t* outPrim, bool hostMem, void* stream,
                      RaylibAMDStats& stats);
+// RaylibAMD_TraceRaysAll (hostMem) and RaylibAMD_TraceRaysAllDevice, as DeviceTraceRays: outHits holds n rows of maxHits records, outCount (may be null) n words.
+// The scene holds triangles only, 1 <= maxHits <= RAYLIB_AMD_MAX_HITS and n * maxHits fits an int32_t: the ABI checked.
+bool DeviceTraceRaysAll(Scene& scene, const void* rays, int32_t n, int32_t maxHits, void* outHits, uint32_t* outCount, bool hostMem, void* stream, RaylibAMDStats& stats);
 // RaylibAMD_NearestPoints (hostMem) and RaylibAMD_NearestPointsDevice, as DeviceTraceRays; the scene holds triangles only: the ABI checked.
 bool DeviceNearestPoints(Scene& scene, int32_t kind, const void* points, int32_t n, void* out, bool hostMem, void* stream, RaylibAMDStats& stats);
 // RaylibAMD_TraceRadiance (hostMem) and RaylibAMD_TraceRadianceDevice, as DeviceTraceRays; prm is valid (timeMin <= timeMax cover every ray's time and the

@@ -9,6 +9,8 @@
 //                        changes how two loops of the eager PLAIN instance are scheduled
 //   rl_render_pool.hip   k_trace_pool and its twin: a scheduler strategy of its own (Makefile POOLFLAGS)
 //   rl_query.hip         k_query (RaylibAMD_TraceRays): beside the render kernels it would change how the walks they share are inlined into those
+//   rl_multihit.hip      k_query_all (RaylibAMD_TraceRaysAll): the binary and the 8-wide walk again with a sorted list behind the triangle test, written on the
+//                        shared steps; apart so that k_query and every other unit stay the code they are
 //   rl_nearest.hip       k_nearest (RaylibAMD_NearestPoints): a walk of its own (point-to-box distances, no ray), which shares with the others the records and the
 //                        child sort alone; apart so that every other unit stays the code it is
 //   rl_radiance.hip      k_radiance (RaylibAMD_TraceRadiance): the same reason, towards the render and the query kernels alike
@@ -169,6 +171,20 @@ template <int TREE, int KIND, int STACK, bool PRIMS> __global__ void __launch_bo
 #define RL_QUERY_INSTANCES(X) RL_QUERY_INSTANCES_K(X, 0) RL_QUERY_INSTANCES_K(X, 1) RL_QUERY_INSTANCES_K(X, 2)
 #define RL_K_QUERY(a, b, c, d) template __global__ void k_query<a, b, c, d>(RL_QUERY_ARGS);
 RL_QUERY_INSTANCES(extern RL_K_QUERY)
+
+// ---------------------------------------------------------------------------
+// The ordered multi-hit ray queries (RaylibAMD_TraceRaysAll; rl_k_multihit.inl)
+#define RL_MAX_HITS 16   /* RAYLIB_AMD_MAX_HITS */
+// TREE: 2 the binary tree (S.nodes), 8 the 8-wide tree (S.nodes8).  STACK: as k_query's.  COUNT: outCount[i] = every accepted triangle of ray i's interval (the walk
+// then never prunes with its K-th key).  rays: as k_query's.  maxHits: 1 .. RL_MAX_HITS, and the launch carries 2 * maxHits * RL_BLOCK words of dynamic LDS
+// (the lanes' lists).  outHits: n rows of maxHits DQueryHit.  outCount: n words (COUNT) or null.  slotIndex, rayCounter, counters: as k_query's.
+#define RL_QUERY_ALL_ARGS const DSceneView, const float4* __restrict__, uint32_t, uint32_t, float4* __restrict__, uint32_t* __restrict__, const int32_t* __restrict__, unsigned int* __restrict__, unsigned long long* __restrict__
+template <int TREE, int STACK, bool COUNT> __global__ void __launch_bounds__(RL_BLOCK) k_query_all(RL_QUERY_ALL_ARGS);
+// The instances rl_rt_rays.hip QueryAllKernelFor selects from: (TREE, STACK, COUNT)
+#define RL_QUERY_ALL_INSTANCES_C(X, C) X(2, 32, C) X(2, 64, C) X(8, 2 * RL_POOL8_MAXLEVELS, C)
+#define RL_QUERY_ALL_INSTANCES(X) RL_QUERY_ALL_INSTANCES_C(X, false) RL_QUERY_ALL_INSTANCES_C(X, true)
+#define RL_K_QUERY_ALL(a, b, c) template __global__ void k_query_all<a, b, c>(RL_QUERY_ALL_ARGS);
+RL_QUERY_ALL_INSTANCES(extern RL_K_QUERY_ALL)
 
 // ---------------------------------------------------------------------------
 // The nearest-point queries (RaylibAMD_NearestPoints; rl_k_nearest.inl, arithmetic of rl_nearest.h)

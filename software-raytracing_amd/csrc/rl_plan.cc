@@ -157,6 +157,21 @@ QueryPlan PlanQuery(const Scene& sc, int32_t kind, const RenderKnobs& k)
 	return p;
 }
 
+QueryPlan PlanQueryAll(const Scene& sc, const RenderKnobs& k)
+{
+	QueryPlan p;
+	const BVH& b = sc.bvh;
+	p.prims = !sc.spheres.empty() || !sc.cubes.empty();
+	if (b.depth > 64) { p.ok = false; return p; }
+	const int want = k.queryTree ? k.queryTree : 8;
+	if (want >= 8 && !p.prims && !b.nodes8.empty() && b.depth8 <= RL_POOL8_MAXLEVELS) {
+		p.tree = TREE_WIDE8; p.treeWidth = 8; p.nodeBytes = (uint32_t)sizeof(DNode8); p.stack = 2 * RL_POOL8_MAXLEVELS;
+	} else {
+		p.stack = b.depth <= 32 ? 32 : 64;   // (no grid-4 instance of k_query_all: 4 asked for, or no 8-wide tree, is the binary tree)
+	}
+	return p;
+}
+
 QueryPlan PlanRadiance(const Scene& sc, const RenderKnobs& k)
 {
 	QueryPlan p;

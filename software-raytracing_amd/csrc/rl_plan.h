@@ -77,6 +77,10 @@ struct QueryPlan {
 	bool early = false;         // the occlusion query stops at its first accepted candidate
 };
 QueryPlan PlanQuery(const Scene& sc, int32_t kind, const RenderKnobs& knobs);
+// Which tree and k_query_all instance a batch of ordered multi-hit queries walks (RaylibAMD_TraceRaysAll, rl_k_multihit.inl): the 8-wide tree under PlanQuery's
+// conditions, else the binary tree.  There is no grid-4 instance: RAYLIB_QUERY_TREE=4 falls through to the binary tree, =2 selects it, =8 is the default.
+// `early` is unused (false).  The scene holds triangles only (the entries refuse spheres and cubes before they plan).
+QueryPlan PlanQueryAll(const Scene& sc, const RenderKnobs& knobs);
 // Which tree and k_radiance instance a batch of caller rays is path-traced on (RaylibAMD_TraceRadiance, rl_k_radiance.inl): the grid-4 tree when the scene
 // carries one, has no spheres or cubes and its worst-case stack fits 64 entries; else the binary tree.  The 8-wide walk is a step walk and not fused with
 // shading here: RAYLIB_QUERY_TREE=8 falls through to 4, =2 walks the binary tree.  `early` is unused (false).

@@ -1,4 +1,4 @@
-// Host runtime: rays of the caller's -- the ray queries (RaylibAMD_TraceRays, k_query), the nearest-point queries that share their call (RaylibAMD_NearestPoints, k_nearest), path-traced radiance (RaylibAMD_TraceRadiance, k_radiance) and the
+// Host runtime: rays of the caller's -- the ray queries (RaylibAMD_TraceRays, k_query), the ordered multi-hit queries (RaylibAMD_TraceRaysAll, k_query_all) and the nearest-point queries (RaylibAMD_NearestPoints, k_nearest) that share their call (BeginQueryCall), path-traced radiance (RaylibAMD_TraceRadiance, k_radiance) and the
 // irradiance and SH probes gathered from it at caller points (RaylibAMD_Gather, k_gather + k_gather_resolve) on rank 0's device, from host memory or from device pointers, on the library's stream (synchronous, with stats) or enqueued on a stream of the caller's (rl_rt.h).
 // The two entries share the refusals of a device call's pointers, the synchronous call's counter block and event pair, the stats' header, the staging of a
 // host call through qRays / qOut, the grid that fills the device once, and the synchronous tail; each keeps its plan and kernel, its parameter block and the
@@ -157,6 +157,25 @@ static bool FinishSync(RankCtx& R, hipStream_t st, std::initializer_list<CopyBac
 	return true;
 }
 
+// What the ray queries, the multi-hit queries and the nearest-point queries do between the refusals of their pointers and their first enqueue: the scene on
+// the device (which orders the call behind a move and behind multi-rank frames in flight), the plan's tree and, where the call writes export indices, the slot
+// table; the stream; the ring's next counter; a synchronous call's counter block; the stats' header.
+struct QueryCall { DeviceSceneCopy* Cp = nullptr; hipStream_t st = nullptr; bool sync = false; uint32_t slot = 0; unsigned int* counter = nullptr; };
+static bool BeginQueryCall(Scene& sc, RankCtx& R, const QueryPlan& plan, bool wantSlotIndex, void* stream, QueryCall& U, RaylibAMDStats& stats)
+{
+	if (!UploadScene(sc)) return false;
+	U.Cp = sc.device->copy[(size_t)R.devSlot];
+	if (!EnsureWideTree(U.Cp, sc, plan.tree)) return false;
+	if (wantSlotIndex && !EnsureSlotIndex(U.Cp, sc)) return false;
+	U.st = stream ? (hipStream_t)stream : R.stream;
+	U.sync = !stream;
+	if (!TakeRingCounter(R, U.slot)) return false;
+	U.counter = R.qRing.ptr + U.slot;
+	if (U.sync && !EnsureSyncStats(R)) return false;
+	StatsHeader(stats, plan, sc);
+	return true;
+}
+
 bool DeviceTraceRays(Scene& sc, int32_t kind, const void* rays, int32_t n, float rayTime, void* out, int32_t* outPrim, bool hostMem, void* stream,
                      RaylibAMDStats& stats)
 {
@@ -169,18 +188,10 @@ bool DeviceTraceRays(Scene& sc, int32_t kind, const void* rays, int32_t n, float
 	if (!plan.ok) { Log("RaylibAMD_TraceRays: BVH depth %u exceeds the traversal stack (64)", sc.bvh.depth); return false; }
 	const size_t outBytes = (size_t)n * (kind == RAYLIB_AMD_QUERY_ANY ? sizeof(uint32_t) : kind == RAYLIB_AMD_QUERY_CLOSEST ? sizeof(DQueryHit) : sizeof(DHitOut));
 	if (!hostMem && n > 0 && !DevicePointersOk("RaylibAMD_TraceRaysDevice", "rays", R.device, rays, out, kind == RAYLIB_AMD_QUERY_CLOSEST ? 15u : 3u, outPrim, kind == RAYLIB_AMD_QUERY_SURFACE)) return false;
-	if (!UploadScene(sc)) return false;
-	DeviceSceneCopy* Cp = sc.device->copy[(size_t)R.devSlot];
-	if (!EnsureWideTree(Cp, sc, plan.tree)) return false;
 	const bool wantPrim = kind == RAYLIB_AMD_QUERY_CLOSEST || (kind == RAYLIB_AMD_QUERY_SURFACE && outPrim);
-	if (wantPrim && !EnsureSlotIndex(Cp, sc)) return false;
-	const hipStream_t st = stream ? (hipStream_t)stream : R.stream;
-	const bool sync = !stream;
-	uint32_t slot = 0;
-	if (!TakeRingCounter(R, slot)) return false;
-	unsigned int* counter = R.qRing.ptr + slot;
-	if (sync && !EnsureSyncStats(R)) return false;
-	StatsHeader(stats, plan, sc);
+	QueryCall U;
+	if (!BeginQueryCall(sc, R, plan, wantPrim, stream, U, stats)) return false;
+	DeviceSceneCopy* Cp = U.Cp; const hipStream_t st = U.st; const bool sync = U.sync; const uint32_t slot = U.slot; unsigned int* counter = U.counter;
 	if (n == 0) return true;
 	const float4* dRays = (const float4*)rays; void* dOut = out; int32_t* dPrim = (kind == RAYLIB_AMD_QUERY_SURFACE) ? outPrim : nullptr;
 	if (hostMem) {
@@ -202,6 +213,54 @@ bool DeviceTraceRays(Scene& sc, int32_t kind, const void* rays, int32_t n, float
 	return FinishSync(R, st, { { hostMem ? out : nullptr, dOut, outBytes }, { hostMem && dPrim ? outPrim : nullptr, dPrim, (size_t)n * sizeof(int32_t) } }, t0, stats);
 }
 
+// An ordered multi-hit call (RaylibAMD_TraceRaysAll) is a ray query's call with another plan, kernel and output size: rows of maxHits records and, when asked
+// for, a count per ray; the launch carries the lanes' lists as dynamic LDS (2 * maxHits * RL_BLOCK words), which its grid's occupancy accounts for.
+typedef void (*QueryAllKernel)(const DSceneView, const float4*, uint32_t, uint32_t, float4*, uint32_t*, const int32_t*, unsigned int*, unsigned long long*);
+template <bool COUNT>
+static QueryAllKernel QueryAllKernelOf(const QueryPlan& p)
+{
+	if (p.tree == TREE_WIDE8) return (QueryAllKernel)k_query_all<8, 2 * RL_POOL8_MAXLEVELS, COUNT>;
+	return p.stack <= 32 ? (QueryAllKernel)k_query_all<2, 32, COUNT> : (QueryAllKernel)k_query_all<2, 64, COUNT>;
+}
+static_assert(RAYLIB_AMD_MAX_HITS == RL_MAX_HITS, "multi-hit capacity");
+bool DeviceTraceRaysAll(Scene& sc, const void* rays, int32_t n, int32_t maxHits, void* outHits, uint32_t* outCount, bool hostMem, void* stream, RaylibAMDStats& stats)
+{
+	const auto t0 = std::chrono::steady_clock::now();
+	std::lock_guard<std::mutex> lk(Rt().lock);
+	if (!EnsureRuntime()) return false;
+	RankCtx& R = Rank0();
+	HIP_OK(hipSetDevice(R.device));
+	const QueryPlan plan = PlanQueryAll(sc, ReadRenderKnobs());
+	if (!plan.ok) { Log("RaylibAMD_TraceRaysAll: BVH depth %u exceeds the traversal stack (64)", sc.bvh.depth); return false; }
+	const size_t hitBytes = (size_t)n * (size_t)maxHits * sizeof(DQueryHit), countBytes = outCount ? (size_t)n * sizeof(uint32_t) : 0;
+	if (!hostMem && n > 0 && !DevicePointersOk("RaylibAMD_TraceRaysAllDevice", "rays", R.device, rays, outHits, 15u, (const int32_t*)outCount, outCount != nullptr)) return false;
+	QueryCall U;
+	if (!BeginQueryCall(sc, R, plan, true, stream, U, stats)) return false;
+	if (n == 0) return true;
+	const hipStream_t st = U.st;
+	const float4* dRays = (const float4*)rays; float4* dHits = (float4*)outHits; uint32_t* dCount = outCount;
+	if (hostMem) {
+		if (outCount && !R.qPrim.Grow((size_t)n * sizeof(int32_t))) return false;
+		if (!StageRays(R, rays, n, hitBytes, st)) return false;
+		dRays = R.qRays.ptr; dHits = (float4*)R.qOut.ptr; if (outCount) dCount = (uint32_t*)R.qPrim.ptr;
+	}
+	const QueryAllKernel kernel = outCount ? QueryAllKernelOf<true>(plan) : QueryAllKernelOf<false>(plan);
+	const size_t listBytes = 2u * (size_t)maxHits * RL_BLOCK * sizeof(uint32_t);
+	int blocksPerCU = 0;
+	HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, (const void*)kernel, RL_BLOCK, listBytes));
+	if (blocksPerCU < 1) { Log("RaylibAMD_TraceRaysAll: no workgroup of the kernel fits a compute unit with %zu bytes of list", listBytes); return false; }
+	const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)R.numCUs * (uint64_t)blocksPerCU, ((uint64_t)n + RL_BLOCK - 1) / RL_BLOCK));
+	const DSceneView view = U.Cp->view;
+	HIP_OK(hipMemsetAsync(U.counter, 0, sizeof(unsigned int), st));
+	if (U.sync && !BeginSync(R, st)) return false;
+	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RL_BLOCK), (uint32_t)listBytes, st, view, dRays, (uint32_t)n, (uint32_t)maxHits, dHits, dCount, (const int32_t*)U.Cp->slotIndex.ptr, U.counter,
+	                   U.sync ? R.qStats.ptr : nullptr);
+	HIP_OK(hipGetLastError());
+	if (!ReleaseRingCounter(R, U.slot, st)) return false;
+	if (!U.sync) return true;
+	return FinishSync(R, st, { { hostMem ? outHits : nullptr, dHits, hitBytes }, { hostMem ? (void*)outCount : nullptr, dCount, countBytes } }, t0, stats);
+}
+
 // A nearest-point call is a ray query's call with another plan and kernel: the same refusals of a device call's pointers, staging buffers, counter ring,
 // synchronous tail, and the same order behind a move (UploadScene settles it) and behind frames in flight (rank 0's stream, or the caller's behind the uploads).
 bool DeviceNearestPoints(Scene& sc, int32_t kind, const void* points, int32_t n, void* out, bool hostMem, void* stream, RaylibAMDStats& stats)
@@ -216,17 +275,9 @@ bool DeviceNearestPoints(Scene& sc, int32_t kind, const void* points, int32_t n,
 	const bool closest = kind == RAYLIB_AMD_NEAREST_CLOSEST;
 	const size_t outBytes = (size_t)n * (closest ? sizeof(DNearestHit) : sizeof(uint32_t));
 	if (!hostMem && n > 0 && !DevicePointersOk("RaylibAMD_NearestPointsDevice", "points", R.device, points, out, closest ? 15u : 3u, nullptr, false)) return false;
-	if (!UploadScene(sc)) return false;
-	DeviceSceneCopy* Cp = sc.device->copy[(size_t)R.devSlot];
-	if (!EnsureWideTree(Cp, sc, plan.tree)) return false;
-	if (closest && !EnsureSlotIndex(Cp, sc)) return false;
-	const hipStream_t st = stream ? (hipStream_t)stream : R.stream;
-	const bool sync = !stream;
-	uint32_t slot = 0;
-	if (!TakeRingCounter(R, slot)) return false;
-	unsigned int* counter = R.qRing.ptr + slot;
-	if (sync && !EnsureSyncStats(R)) return false;
-	StatsHeader(stats, plan, sc);
+	QueryCall U;
+	if (!BeginQueryCall(sc, R, plan, closest, stream, U, stats)) return false;
+	DeviceSceneCopy* Cp = U.Cp; const hipStream_t st = U.st; const bool sync = U.sync; const uint32_t slot = U.slot; unsigned int* counter = U.counter;
 	if (n == 0) return true;
 	const float4* dPoints = (const float4*)points; void* dOut = out;
 	if (hostMem) {

@@ -147,6 +147,74 @@ def trace_rays(lib, scene, rays, kind, ray_time=0.0, with_prim=False):
     return (out, prim) if with_prim else out
 
 
+MAX_HITS = 16                                       # RAYLIB_AMD_MAX_HITS
+
+
+def plan_ray_query_all(lib, scene, max_hits, count=False):
+    """RaylibAMD_PlanRayQueryAll: (return code, plan dict)."""
+    p = QueryPlan()
+    r = lib.RaylibAMD_PlanRayQueryAll(scene, int(max_hits), int(bool(count)), C.byref(p))
+    return r, p.as_dict()
+
+
+def trace_rays_all(lib, scene, rays, max_hits, count=False, tree=None, device=False, host=False, ray_time=0.0):
+    """Ordered multi-hit ray queries (RaylibAMD_TraceRaysAll / RaylibAMD_TraceRaysAllDevice / RaylibAMD_TraceRaysAllHost, statements M1 to M5).
+
+    rays: an (n, 8) float32 array -- org xyz, tMin, dir xyz, tMax per row.  Returns the (n, max_hits) records, and with count=True the pair (records, counts).
+    A NumPy array goes through the host-memory entry (host=True: through the oracle, which needs no device) and returns NumPy arrays: HITT_DTYPE records, uint32
+    counts.  A float32 torch tensor on the device -- or a NumPy array with device=True, which is copied there and whose results are copied back -- goes through
+    the device entry on torch.cuda.current_stream(), as trace_rays: enqueued on a stream of the caller's, synchronous on torch's default stream (synchronised
+    first); a tensor in gives tensors out, (n, max_hits, 4) int32 words and (n,) int32 counts.  tree: RAYLIB_QUERY_TREE for this call (2, 4 or 8; None leaves the
+    environment alone).  Raises RuntimeError when the library refuses the call."""
+    max_hits = int(max_hits)
+    saved = os.environ.get("RAYLIB_QUERY_TREE")
+    if tree is not None:
+        os.environ["RAYLIB_QUERY_TREE"] = str(int(tree))
+    try:
+        if isinstance(rays, np.ndarray) and not device:
+            r = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+            n = len(r)
+            hits = np.zeros((n, max(max_hits, 0)), HITT_DTYPE)
+            counts = np.zeros(n, np.uint32) if count else None
+            name = "RaylibAMD_TraceRaysAllHost" if host else "RaylibAMD_TraceRaysAll"
+            ok = getattr(lib, name)(scene, r.ctypes.data_as(C.POINTER(Ray)), n, float(ray_time), max_hits, C.cast(C.c_void_p(hits.ctypes.data), C.POINTER(HitT)),
+                                    counts.ctypes.data_as(C.POINTER(C.c_uint32)) if count else None)
+            if ok != 1:
+                raise RuntimeError(name + " refused the query")
+            return (hits, counts) if count else hits
+        import torch
+        if host:
+            raise TypeError("host=True takes a NumPy array and no device")
+        as_numpy = isinstance(rays, np.ndarray)
+        if as_numpy:
+            rays = torch.from_numpy(np.ascontiguousarray(rays, np.float32).reshape(-1, 8)).cuda()
+        if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.dtype == torch.float32):
+            raise TypeError("rays: a float32 NumPy array or a float32 torch tensor on the device")
+        r = rays.reshape(-1, 8).contiguous()
+        n = r.shape[0]
+        hits = torch.empty((n, max(max_hits, 0), 4), dtype=torch.int32, device=r.device)
+        counts = torch.empty(n, dtype=torch.int32, device=r.device) if count else None
+        stream = torch.cuda.current_stream(r.device)
+        if stream.cuda_stream == 0:
+            stream.synchronize()   # (the library's stream is not ordered against torch's default stream: trace_rays)
+        ok = lib.RaylibAMD_TraceRaysAllDevice(scene, C.cast(C.c_void_p(r.data_ptr()), C.POINTER(Ray)), n, float(ray_time), max_hits,
+                                              C.cast(C.c_void_p(hits.data_ptr()), C.POINTER(HitT)),
+                                              C.cast(C.c_void_p(counts.data_ptr()), C.POINTER(C.c_uint32)) if count else None, C.c_void_p(stream.cuda_stream))
+        if ok != 1:
+            raise RuntimeError("RaylibAMD_TraceRaysAllDevice refused the query")
+        if as_numpy:
+            stream.synchronize()
+            hits = hits.cpu().numpy().view(HITT_DTYPE).reshape(n, max_hits)
+            counts = counts.cpu().numpy().view(np.uint32) if count else None
+        return (hits, counts) if count else hits
+    finally:
+        if tree is not None:
+            if saved is None:
+                os.environ.pop("RAYLIB_QUERY_TREE", None)
+            else:
+                os.environ["RAYLIB_QUERY_TREE"] = saved
+
+
 NEAREST_WITHIN, NEAREST_CLOSEST = 0, 1              # RAYLIB_AMD_NEAREST_*
 NEAREST_QUERY_DTYPE = np.dtype([("pos", "f4", 3), ("maxDist", "f4")])                          # RaylibAMDNearestQuery
 NEAREST_DTYPE = np.dtype([("dist2", "f4"), ("prim", "i4"), ("b1", "f4"), ("b2", "f4")])        # RaylibAMDNearestHit
@@ -704,6 +772,10 @@ _EXPORTS = {
     "RaylibAMD_TraceRadiance": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(PathRay), C.c_int32, C.POINTER(C.c_float)]),
     "RaylibAMD_TraceRadianceDevice": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(PathRay), C.c_int32, C.POINTER(C.c_float), C.c_void_p]),
     "RaylibAMD_PlanRadiance": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(QueryPlan)]),
+    "RaylibAMD_TraceRaysAll": (C.c_int32, [C.c_void_p, C.POINTER(Ray), C.c_int32, C.c_float, C.c_int32, C.POINTER(HitT), C.POINTER(C.c_uint32)]),
+    "RaylibAMD_TraceRaysAllDevice": (C.c_int32, [C.c_void_p, C.POINTER(Ray), C.c_int32, C.c_float, C.c_int32, C.POINTER(HitT), C.POINTER(C.c_uint32), C.c_void_p]),
+    "RaylibAMD_TraceRaysAllHost": (C.c_int32, [C.c_void_p, C.POINTER(Ray), C.c_int32, C.c_float, C.c_int32, C.POINTER(HitT), C.POINTER(C.c_uint32)]),
+    "RaylibAMD_PlanRayQueryAll": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(QueryPlan)]),
     "RaylibAMD_NearestPoints": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "RaylibAMD_NearestPointsDevice": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "RaylibAMD_NearestPointsHost": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
@@ -742,6 +814,7 @@ _EXPORTS = {
     "RaylibAMD_SceneNumMaterials": (C.c_int32, [C.c_void_p]),
     "RaylibAMD_SceneNumTextures": (C.c_int32, [C.c_void_p]),
     "RaylibAMD_SceneExportTriangles": (None, [C.c_void_p, C.c_void_p]),
+    "RaylibAMD_SceneExportTriOrder": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "RaylibAMD_SceneExportMaterials": (None, [C.c_void_p, C.c_void_p]),
     "RaylibAMD_SceneTextureSize": (None, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "RaylibAMD_SceneExportTexture": (None, [C.c_void_p, C.c_int32, C.POINTER(C.c_float)]),
