@@ -648,6 +648,14 @@ RAYLIB_API int32_t RaylibAMD_SceneRebuild(SceneHandle scene);
  * on them against the current triangles.  Returns 1 when all pass; else 0 with *outFailedTree (may be NULL) = 2, 4 or 8 for the first tree that failed, or 0
  * when the check could not run (no device, scene unknown or not finalized). */
 RAYLIB_API int32_t RaylibAMD_SceneCheckTrees(SceneHandle scene, uint32_t* outFailedTree);
+/* Test hook: the VALUES of the wide formats the device holds.  Per device copy of the scene, its binary nodes are read back and the host's statement of the
+ * refit rule (csrc/rl_grid.h through rl_bvh.cc RefitWideFromBinary: the double-precision grid of the 4-wide and 8-wide nodes) is applied to them on the host;
+ * the result is compared byte for byte with the float-4, grid-4, leaf-list and 8-wide arrays that copy holds (a format it does not hold is not compared), and
+ * the copy's triangle records with those of rank 0's copy.  Holds for a scene that was never moved too: the builder quantises with the same rule from the same
+ * boxes.  Returns 1 when all are equal; else 0 with *outDiffMask (may be NULL) = a bit per format that differs -- 1 float-4, 2 grid-4, 4 leaf list, 8 8-wide,
+ * 16 records --, or 0 when the check could not run (no device, scene unknown or not finalized, a failed read-back).  Like every call on the scene it waits for
+ * a move in flight; it changes nothing in the scene, the host's copies and whether they are stale included. */
+RAYLIB_API int32_t RaylibAMD_SceneCompareTrees(SceneHandle scene, uint32_t* outDiffMask);
 
 /* ---- host-logic introspection (no GPU needed) ---------------------------------- */
 /* Flattened scene as the kernels see it.  Triangle record = 26 words, material record =

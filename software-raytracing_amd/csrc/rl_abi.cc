@@ -1537,6 +1537,13 @@ int32_t RaylibAMD_SceneCheckTrees(SceneHandle sh, uint32_t* outFailedTree)
 	if (!s || !g_scenes.contains(s) || !s->finalized) return 0;
 	return DeviceCheckTrees(*s, outFailedTree) ? 1 : 0;
 }
+int32_t RaylibAMD_SceneCompareTrees(SceneHandle sh, uint32_t* outDiffMask)
+{
+	Scene* s = (Scene*)sh;
+	if (outDiffMask) *outDiffMask = 0;
+	if (!s || !g_scenes.contains(s) || !s->finalized) return 0;
+	return DeviceCompareTrees(*s, outDiffMask) ? 1 : 0;
+}
 int32_t RaylibAMD_SceneExportBVHNodes(SceneHandle sh, void* out)
 {
 	Scene* s = (Scene*)sh;

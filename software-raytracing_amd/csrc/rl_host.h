@@ -346,6 +346,9 @@ bool DeviceMoveTriangles(Scene& scene, int32_t first, int32_t count, const float
 bool DeviceSyncMovedScene(Scene& scene);
 // RaylibAMD_SceneCheckTrees: rl_bvh.cc's checks on what the device holds; *outFailedTree: 0, or 2 / 4 / 8 for the first tree that failed
 bool DeviceCheckTrees(Scene& scene, uint32_t* outFailedTree);
+// RaylibAMD_SceneCompareTrees: the wide formats every device's copy holds against RefitWideFromBinary of that copy's own binary nodes, and its records against
+// rank 0's; *outDiffMask: 1 float-4, 2 grid-4, 4 leaf list, 8 8-wide, 16 records.  false with the mask untouched when the check could not run.
+bool DeviceCompareTrees(Scene& scene, uint32_t* outDiffMask);
 
 // Progressive rendering (include/raylib_amd.h RaylibAMD_BeginProgressive; rl_rt_render.hip).  Begin: nullptr without a device or memory.  Step: the number of
 // live cells after the pass (0: finished), -1 when refused or failed -- `rendered` tells whether a pass ran (and `stats` is its numbers).

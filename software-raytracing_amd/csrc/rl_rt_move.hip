@@ -1,6 +1,6 @@
 // Host runtime: a finalized scene's triangles moved (RaylibAMD_SceneMoveTriangles / ...Device, include/raylib_amd.h) -- the moved records and the refit of every
-// tree the device holds (rl_refit.hip's kernels), the status a move leaves behind, the read-back that brings the host's copies up to date, and the test hook
-// that runs the builder's validity checks on what the device holds (rl_rt.h).
+// tree the device holds (rl_refit.hip's kernels), the status a move leaves behind, the read-back that brings the host's copies up to date, and the two test
+// hooks: the builder's validity checks on what the device holds, and the device's wide formats against the host's rule on the device's binary boxes (rl_rt.h).
 //
 // Schedule of a move on stream st: k_move_scan, k_move_records; k_refit_level once per level of the binary tree, deepest first, each launch reading what the one
 // before wrote; then k_refit_wide4 / k_refit_wide8 for the wide formats that are on the device; the status block and the root node to pinned memory; the event.
@@ -253,6 +253,47 @@ bool DeviceCheckTrees(Scene& sc, uint32_t* outFailedTree)
 	HIP_OK(hipSetDevice(R.device));
 	if (outFailedTree) *outFailedTree = failed;
 	return failed == 0;
+}
+
+// whether n records on the device are, byte for byte, the host's; false: the read-back failed
+template <typename T> static bool SameOnDevice(const T* dev, const T* host, size_t n, bool& same)
+{
+	std::vector<T> got(n);
+	if (n) HIP_OK(hipMemcpy(got.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost));
+	same = n == 0 || memcmp(got.data(), host, n * sizeof(T)) == 0;
+	return true;
+}
+
+// The wide formats as the device holds them against the host's rule on the device's own binary boxes: per copy, its binary nodes read back into a copy of the
+// host's BVH (whose topology a move keeps; a stale box of it is overwritten or, under an unused child, the builder's on both sides), RefitWideFromBinary on that
+// copy, and the bytes of every wide array the copy holds beside it.  The host's copies and their staleness flags are neither read for their boxes nor touched.
+bool DeviceCompareTrees(Scene& sc, uint32_t* outDiffMask)
+{
+	std::lock_guard<std::mutex> lk(Rt().lock);
+	if (!EnsureRuntime()) return false;
+	RankCtx& R = Rank0();
+	HIP_OK(hipSetDevice(R.device));
+	if (!UploadScene(sc)) return false;   // (settles a move in flight)
+	uint32_t diff = 0;
+	const size_t n = sc.triangles.size();
+	std::vector<DTriIsect> isect0(n);
+	if (n) HIP_OK(hipMemcpy(isect0.data(), sc.device->copy[(size_t)R.devSlot]->isect.ptr, n * sizeof(DTriIsect), hipMemcpyDeviceToHost));
+	for (DeviceSceneCopy* C : sc.device->copy) {   // every device's copy
+		HIP_OK(hipSetDevice(C->device));
+		BVH B = sc.bvh;
+		HIP_OK(hipMemcpy(B.nodes.data(), C->nodes.ptr, B.nodes.size() * sizeof(DNode), hipMemcpyDeviceToHost));
+		RefitWideFromBinary(B);
+		bool same = true;
+		if (C->nodes4f.ptr) { if (!SameOnDevice(C->nodes4f.ptr, B.nodes4.data(), B.nodes4.size(), same)) return false; if (!same) diff |= 1u; }
+		if (C->nodes4.ptr) { if (!SameOnDevice(C->nodes4.ptr, B.nodes4q.data(), B.nodes4q.size(), same)) return false; if (!same) diff |= 2u; }
+		if (C->leafList.ptr) { if (!SameOnDevice(C->leafList.ptr, B.leafList.data(), B.leafList.size(), same)) return false; if (!same) diff |= 4u; }
+		if (C->nodes8.ptr) { if (!SameOnDevice(C->nodes8.ptr, B.nodes8.data(), B.nodes8.size(), same)) return false; if (!same) diff |= 8u; }
+		if (!SameOnDevice(C->isect.ptr, isect0.data(), n, same)) return false;
+		if (!same) diff |= 16u;
+	}
+	HIP_OK(hipSetDevice(R.device));
+	if (outDiffMask) *outDiffMask = diff;
+	return diff == 0;
 }
 
 } // namespace rl

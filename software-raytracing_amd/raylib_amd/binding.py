@@ -286,6 +286,13 @@ def move_triangles(lib, scene, first, positions, normals=None):
                                                   C.c_void_p(stream.cuda_stream))
 
 
+def compare_trees(lib, scene):
+    """RaylibAMD_SceneCompareTrees: (the library's answer, the mask of formats that differ -- 1 float-4, 2 grid-4, 4 leaf list, 8 8-wide, 16 records).
+    (1, 0): every wide tree the device holds is, byte for byte, what the host's rule makes of the device's binary boxes; (0, 0): the check could not run."""
+    mask = C.c_uint32(0)
+    return lib.RaylibAMD_SceneCompareTrees(scene, C.byref(mask)), mask.value
+
+
 class PathRay(C.Structure):
     """include/raylib_amd.h RaylibAMDPathRay (32 bytes): org, time, dir, stream."""
     _fields_ = [("org", C.c_float * 3), ("time", C.c_float), ("dir", C.c_float * 3), ("stream", C.c_uint32)]
@@ -844,6 +851,7 @@ _EXPORTS = {
     "RaylibAMD_SceneMoveTrianglesDevice": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "RaylibAMD_SceneRebuild": (C.c_int32, [C.c_void_p]),
     "RaylibAMD_SceneCheckTrees": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "RaylibAMD_SceneCompareTrees": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "RaylibAMD_CameraExport": (None, [C.c_void_p, C.POINTER(C.c_float)]),
     "RaylibAMD_CreateImageFromData": (C.c_void_p, [C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
     "RaylibAMD_DumpImageRGBA": (None, [C.c_void_p, C.POINTER(C.c_float)]),

@@ -46,6 +46,7 @@ def main():
         out["frame_" + tag] = got
         lib.Raylib_DestroyImage(A)
         out["trees_" + tag] = np.asarray(mc.check_trees(lib, ses.scene), np.int64)
+        out["wide_" + tag] = np.asarray(mc.compare_trees(lib, ses.scene), np.int64)      # every copy's wide formats and records, as values
         if rc == 1:
             assert mc.move_to(lib, ses, origin, device)[0] == 1
         out["back_" + tag] = ses.render(mc.W, mc.H, mc.SPP)

@@ -76,8 +76,13 @@ def rays():
     return mc.query_rays()
 
 
-def assert_trees(lib, ses):
+def assert_trees(lib, ses, refitted=True):
+    """What the device holds of a moved scene: the builder's validity checks pass on it (containment); every wide format is, byte for byte, the host's rule
+    applied to the device's binary boxes (RaylibAMD_SceneCompareTrees); and the binary boxes are move_cases.refit_boxes of the moved triangles -- bit for bit
+    where the device's refit wrote them last (refitted), as values behind a rebuild."""
     assert mc.check_trees(lib, ses.scene) == (1, 0)
+    mc.assert_wide_trees_exact(lib, ses.scene)
+    mc.assert_refit_exact(lib, ses, bits=refitted)
 
 
 # ---- case 1: a rigid move of a contiguous third, through either entry, on every structure ----
@@ -461,7 +466,7 @@ def test_rebuild_after_a_move(gpu_lib, workdir, soup, rays, device):
     ok, n2, d2, sah = mc.bvh_info(gpu_lib, ses.scene)
     assert ok == 1 and (n2, d2) == (nodes, depth) and F(sah).tobytes() == F(fresh_sah).tobytes()
     assert mc.same_bits(render_on(gpu_lib, ses), want) and queries_on(gpu_lib, ses, rays) == want_q
-    assert_trees(gpu_lib, ses)
+    assert_trees(gpu_lib, ses, refitted=False)
     ses.close(); fresh.close()
 
 

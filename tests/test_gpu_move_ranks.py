@@ -45,6 +45,6 @@ def test_move_behind_a_frame_in_flight(gpu_lib, workdir, layout):
     assert not same(A["want_moved"], A["want_origin"])
     for tag in ("host", "device"):
         assert same(A["frame_" + tag], A["frame"]), "the frame in flight lost pixels to the move (%s entry)" % tag
-        assert int(A["rc_" + tag]) == 1 and tuple(A["trees_" + tag]) == (1, 0)
+        assert int(A["rc_" + tag]) == 1 and tuple(A["trees_" + tag]) == (1, 0) and tuple(A["wide_" + tag]) == (1, 0)
         assert same(A["moved_" + tag], A["want_moved"]), tag
         assert same(A["back_" + tag], A["want_origin"]), tag

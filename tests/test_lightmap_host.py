@@ -230,9 +230,14 @@ def test_refusals(lib, cornells):
     unfinished = lib.Raylib_CreateScene()
     assert calls(unfinished, prm()) == refused
     lib.Raylib_DestroyScene(unfinished)
-    assert calls(ses.scene, prm(), points=None)[:2] == [-1, -1]          # no room for the points
-    assert calls(ses.scene, prm(), capacity=-1)[:2] == [-1, -1]
     g = prm()
+    for points, capacity in ((None, 64), (pp, -1)):                      # no room for the points: the two points calls alone (the parameters are a valid bake's)
+        assert lib.RaylibAMD_LightmapPoints(ses.scene, C.byref(g), None, points, tp, capacity) == -1
+        assert lib.RaylibAMD_LightmapPointsHost(ses.scene, C.byref(g), None, points, tp, capacity) == -1
+    if lib.RaylibAMD_DeviceAvailable():                                  # ... which, with a device, bakes: into buffers of its own
+        out2 = np.full((8, 8, 27), 7.0, F); cov2 = np.full((8, 8), 7, np.uint8)
+        assert lib.RaylibAMD_BakeLightmap(ses.scene, C.byref(g), None, out2.ctypes.data_as(C.POINTER(C.c_float)), cov2.ctypes.data_as(C.POINTER(C.c_uint8))) == 1
+        assert not (cov2 == 7).any()                                     # (every texel's coverage byte is written: 0, 1 or 2)
     assert lib.RaylibAMD_BakeLightmap(ses.scene, C.byref(g), None, None, cp) == 0 and lib.RaylibAMD_BakeLightmapDevice(ses.scene, C.byref(g), None, None, cp, None) == 0
     scene, close = _triangle_scene(lib, [])                              # a scene without triangles: every range is empty
     assert calls(scene, prm()) == refused

@@ -9,6 +9,7 @@ import numpy as np
 
 import helpers
 import move_cases as mc
+import stack_edges
 from raylib_amd import binding
 
 ROOT = helpers.ROOT
@@ -66,6 +67,39 @@ def test_a_rebuild_of_an_unmoved_scene_is_the_same_tree(lib, workdir):
     assert (lib.RaylibAMD_SceneBVHHash(ses.scene), lib.RaylibAMD_SceneTopologyHash(ses.scene), mc.bvh_nodes(lib, ses.scene).tobytes()) == (h0, t0, n0)
     assert lib.RaylibAMD_SceneTopologyHash(0) == 0 and lib.RaylibAMD_SceneExportBVHNodes(0, None) == 0
     ses.close()
+
+
+def _fresh_scenes(lib, workdir):
+    """(name, session) of freshly finalized scenes: a 300-triangle soup, the Cornell box, and the deepest tree the suite builds (stack_edges.deepest_triangles)."""
+    yield "soup", mc.soup_session(lib, workdir, "restate_soup", mc.soup_triangles(300, seed=12))
+    obj, _ = helpers.build_case("cornell", os.path.join(str(workdir), "restate_cornell"))
+    yield "cornell", mc.case_session(lib, "cornell", obj)
+    yield "deepest", mc.soup_session(lib, workdir, "restate_deepest", stack_edges.deepest_triangles())
+
+
+def test_the_refit_restated_reproduces_the_builders_boxes(lib, workdir):
+    """move_cases.refit_boxes (csrc/rl_k_refit.inl k_refit_level in NumPy), applied to the builder's own nodes of a fresh scene, gives the builder's boxes back
+    as values: the restatement is held to an independent implementation before the device is held to the restatement (tests/test_gpu_move.py assert_trees,
+    tests/test_gpu_refit_exact.py).  Compared with ==: the builder grows an inner node's box over its primitives, the refit over its two child boxes, and on a
+    face that holds zeros of both signs the two may pick different ones.  And the restatement is not the identity: with one triangle moved it changes the boxes
+    on that triangle's path and no other."""
+    for name, ses in _fresh_scenes(lib, workdir):
+        nodes, tris, order = mc.bvh_nodes(lib, ses.scene), mc.export(ses), mc.tri_order(lib, ses.scene)
+        assert sorted(order.tolist()) == list(range(len(tris))), name
+        if name == "deepest":
+            assert mc.bvh_info(lib, ses.scene)[2] == stack_edges.DEEPEST_DEPTH
+        want = mc.refit_boxes(nodes, tris, order)
+        for k in mc.BOXES:
+            assert (nodes[k] == want[k]).all(), (name, k, np.nonzero(~(nodes[k] == want[k]).all(1))[0][:4])
+        assert all(nodes[k].tobytes() == want[k].tobytes() for k in ("left", "right", "pad")), name
+        moved = tris.copy()
+        moved["v1"][len(tris) // 2] = np.float32(2.0 ** 40)           # far outside every box: each box on the path to it grows, the root's included
+        got = mc.refit_boxes(nodes, moved, order)
+        changed = np.zeros(len(nodes), bool)
+        for k in mc.BOXES:
+            changed |= (got[k] != nodes[k]).any(1)
+        assert changed[0] and 1 <= changed.sum() <= mc.node_levels(nodes).max() + 1, (name, changed.sum())
+        ses.close()
 
 
 NO_DEVICE_CHILD = """

@@ -30,6 +30,7 @@ void DeviceReleaseScene(DeviceScene*) {}
 bool DeviceMoveTriangles(Scene&, int32_t, int32_t, const float*, const float*, bool, void*) { return false; }
 bool DeviceSyncMovedScene(Scene&) { return true; }   // (never uploaded: the host's copies are the scene)
 bool DeviceCheckTrees(Scene&, uint32_t*) { return false; }
+bool DeviceCompareTrees(Scene&, uint32_t*) { return false; }
 int DeviceNumRanks() { return 0; }
 bool DeviceDrain(RaylibAMDStats*) { return false; }
 void DeviceOwnStats() {}
