@@ -259,6 +259,69 @@ RAYLIB_API int32_t RaylibAMD_NearestPointsHost(SceneHandle scene, int32_t kind, 
  * finalized or one that holds spheres or cubes. */
 RAYLIB_API int32_t RaylibAMD_PlanNearest(SceneHandle scene, int32_t kind, RaylibAMDQueryPlan* out);
 
+/* ---- batched triangle-overlap queries -------------------------------------------------------------
+ * Which triangles of the scene does a triangle intersect -- the question a collision step asks behind RaylibAMD_SceneMoveTriangles, and, with a mesh's own
+ * triangles as the queries, whether the mesh intersects itself (cloth, skinned characters, lightmap charts that fold over).  The result equals a loop over
+ * every triangle bit for bit, with no slack anywhere, on every tree, fresh or refitted (csrc/rl_overlap.h holds the statements for the host oracle and the
+ * kernel alike; csrc/rl_k_overlap.inl is the walk).
+ * Everything is float, single IEEE operations without FMA.  dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.  cross(a, b) is the lightmap section's:
+ * (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x).  The least and greatest of three values (a, b, c) are found by comparisons, in this order:
+ * m = b < a ? b : a, then c < m ? c : m for the least; m = a < b ? b : a, then m < c ? c : m for the greatest.
+ * For query Q = (q0, q1, q2) and scene triangle T = (v0, v1, v2), in RaylibAMD_SceneExportTriangles order:
+ *   O1. Taking part.  A query takes part when all nine of its floats are finite.  One that does not gets 0 (ANY), or a row of -1 with count 0 (LIST), without a
+ *        walk.
+ *   O2. Own boxes.  lo and hi of each triangle are the componentwise least and greatest of its vertices (v0, v1, v2 in that order).  The boxes meet when, on
+ *        every axis, loQ <= hiT && loT <= hiQ (closed).  If they do not meet, T is not accepted.
+ *   O3. Shared vertices.  With RAYLIB_AMD_OVERLAP_SKIP_SHARED set, T is not accepted when one of its vertices equals one of Q's.  A vertex equals another when
+ *        all three components compare ==, so -0 == +0.  This is the self-intersection rule: a mesh's own triangle, passed as a query, reports neither itself
+ *        nor its neighbours across an edge or a vertex.
+ *   O4. Separating axes.  Edges: eQ0 = q1 - q0, eQ1 = q2 - q1, eQ2 = q0 - q2, and eT0..2 likewise.  Normals: nQ = cross(eQ0, eQ1), nT = cross(eT0, eT1).
+ *        The 17 axes, in this order: nQ; nT; cross(eQi, eTj) with i outer and j inner; cross(nQ, eQi); cross(nT, eTj).
+ *        For an axis a, Q projects to {+0, dot(a, q1 - q0), dot(a, q2 - q0)} and T projects to {dot(a, v0 - q0), dot(a, v1 - q0), dot(a, v2 - q0)}; least and
+ *        greatest of each triple as above.  The axis separates when maxQ < minT || maxT < minQ.  T is accepted when no axis separates.
+ *        Touching counts as meeting.  Coplanar pairs are decided by the last six axes.  A NaN projection, from a degenerate triangle or an overflow, compares
+ *        false and separates nothing.  The verdict is a property of (Q, T) alone; it is not promised to be symmetric in Q and T at rounding level (every
+ *        projection is taken relative to q0).
+ *   O5. Result.  ANY: 1 exactly when some T is accepted.  LIST: the accepted triangles' export indices ascending, the first min(maxHits, count) of them, with
+ *        -1 behind them; outCount[i] is the number of all accepted triangles, however small maxHits is.
+ *   O6. Independence.  The result does not depend on the tree walked, the order of the walk, how the call is cut into waves, or whether the trees were built
+ *        fresh or refitted by RaylibAMD_SceneMoveTriangles.  O2 is pure comparisons, a triangle's own box lies in its leaf's box, a binary node's boxes are the
+ *        min / max of its children's and a decoded grid box contains the float box it was quantised from (csrc/rl_grid.h): a node whose box does not meet Q's
+ *        box under the same closed comparison holds no triangle whose own box does, so the walk needs no widening.
+ * Refusals (0, nothing written): q or out null with n > 0; n < 0; an unknown kind; a flag bit other than bit 0; LIST with maxHits outside
+ * 1 .. RAYLIB_AMD_MAX_OVERLAPS or n * maxHits above 2^31 - 1; ANY with a non-null outCount (maxHits is not read); a scene that is not finalized; a scene that
+ * holds spheres or cubes; a BVH deeper than 64 levels; no device (the plain and the device entry; the host entry needs none); on the device entry a pointer
+ * off rank 0's device, q not 16-byte aligned, out or outCount not 4-byte aligned.  n == 0 returns 1.
+ * Still out: spheres and cubes; more than RAYLIB_AMD_MAX_OVERLAPS indices per query (the count is complete all the same); an 8-wide walk; query primitives
+ * other than triangles; the contact geometry (intersection segment, penetration depth), a later entry built on the index pairs this one returns.
+ * Checked against a loop over every triangle and an edge-piercing reference in double precision: tests/test_overlap_host.py, tests/test_gpu_overlap.py. */
+typedef struct RaylibAMDOverlapQuery {      /* 48 bytes, three 16-byte loads; 16-byte aligned on the device entry */
+	float v0[3]; uint32_t reserved0;        /* the reserved words are not read */
+	float v1[3]; uint32_t reserved1;
+	float v2[3]; uint32_t reserved2;
+} RaylibAMDOverlapQuery;
+#define RAYLIB_AMD_OVERLAP_ANY   0          /* out: uint32_t per query, 1 when some scene triangle is accepted (may stop at the first) */
+#define RAYLIB_AMD_OVERLAP_LIST  1          /* out: maxHits int32_t per query, row i = query i; outCount (may be NULL): uint32_t per query */
+#define RAYLIB_AMD_OVERLAP_SKIP_SHARED 1u   /* flags bit 0, statement O3 */
+#define RAYLIB_AMD_MAX_OVERLAPS 16
+/* n queries from host memory, results to host memory; synchronous, on the device.  RaylibAMD_GetLastStats then reports rays (= queries), nodesVisited,
+ * trisTested, kernelMs, wallMs and the tree walked. */
+RAYLIB_API int32_t RaylibAMD_OverlapTriangles(SceneHandle scene, int32_t kind, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, void* out,
+        uint32_t* outCount);
+/* The same on device pointers (rank 0's device), with the stream, stats, move-ordering and multi-rank rules of RaylibAMD_NearestPointsDevice: stream == NULL
+ * is the library's stream, synchronous, with stats; a non-null hipStream_t gets the call enqueued behind the synchronous uploads and the stats are left alone. */
+RAYLIB_API int32_t RaylibAMD_OverlapTrianglesDevice(SceneHandle scene, int32_t kind, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, void* out,
+        uint32_t* outCount, void* stream);
+/* The oracle: statements O1 to O5 over every triangle, no tree, no device.  After a move it refreshes the host's stale triangles first. */
+RAYLIB_API int32_t RaylibAMD_OverlapTrianglesHost(SceneHandle scene, int32_t kind, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, void* out,
+        uint32_t* outCount);
+/* Which tree and kernel instance those calls would walk under the current environment (csrc/rl_plan.cc PlanOverlap): the grid-4 tree when the scene has one and
+ * its worst-case stack is within 32, else the binary tree, which the self-intersection pass walks faster than the 64-deep grid instance;
+ * RAYLIB_QUERY_TREE=2 forces the binary tree, =4 the grid-4 tree up to a worst-case stack of 64, =8 falls through to 4 (there is no 8-wide overlap walk).
+ * `early` is 1 for ANY.  No device needed.  Returns 1, -1 when the BVH is deeper than 64 levels, 0 for a null argument, an unknown kind, a scene not finalized or one that
+ * holds spheres or cubes. */
+RAYLIB_API int32_t RaylibAMD_PlanOverlap(SceneHandle scene, int32_t kind, RaylibAMDQueryPlan* out);
+
 /* ---- path-traced radiance along caller rays -----------------------------------------------------
  * outRGBA[i] = (the mean over the samples of TraceScene(rays[i], depth 0, maxPathLength, rayTMin), 1): the reference's path tracer (render/renderer.cc:114-208)
  * with the scene's sun and sky panorama as a render sees them, on rays that need not come from a camera.  The ray is used as given: neither normalised nor

@@ -9,6 +9,7 @@
 #include "rl_progressive.h"
 #include "rl_lightmap.h"
 #include "rl_nearest.h"
+#include "rl_overlap.h"
 #include "raylib_amd_rng.h"
 
 #include <float.h>
@@ -1003,6 +1004,82 @@ int32_t RaylibAMD_PlanNearest(SceneHandle sh, int32_t kind, RaylibAMDQueryPlan* 
 	if (!s || !s->finalized || !out || (kind != RAYLIB_AMD_NEAREST_WITHIN && kind != RAYLIB_AMD_NEAREST_CLOSEST) || !s->spheres.empty() || !s->cubes.empty()) return 0;
 	memset(out, 0, sizeof(*out));
 	const QueryPlan p = PlanNearest(*s, kind, ReadRenderKnobs());
+	if (!p.ok) return -1;
+	out->tree = p.tree; out->treeWidth = p.treeWidth; out->nodeBytes = p.nodeBytes; out->stack = p.stack; out->prims = 0; out->early = p.early;
+	return 1;
+}
+
+// RaylibAMD_OverlapTriangles / RaylibAMD_OverlapTrianglesDevice / RaylibAMD_OverlapTrianglesHost (statements O1 to O6): the refusals every entry shares
+static bool OverlapArgsValid(const char* who, const Scene* s, int32_t kind, uint32_t flags, const void* q, int32_t n, int32_t maxHits, const void* out, const uint32_t* outCount)
+{
+	if (!s || n < 0 || (n > 0 && (!q || !out))) { Log("%s: null argument", who); return false; }
+	if (kind != RAYLIB_AMD_OVERLAP_ANY && kind != RAYLIB_AMD_OVERLAP_LIST) { Log("%s: unknown overlap kind %d", who, kind); return false; }
+	if ((flags & ~RAYLIB_AMD_OVERLAP_SKIP_SHARED) != 0u) { Log("%s: unknown flag bits 0x%x", who, flags); return false; }
+	if (kind == RAYLIB_AMD_OVERLAP_LIST) {
+		if (maxHits < 1 || maxHits > RAYLIB_AMD_MAX_OVERLAPS) { Log("%s: maxHits %d is outside 1..%d", who, maxHits, RAYLIB_AMD_MAX_OVERLAPS); return false; }
+		if ((int64_t)n * maxHits > 0x7fffffffll) { Log("%s: %d queries x %d indices exceed 2^31 - 1 words", who, n, maxHits); return false; }
+	} else if (outCount) { Log("%s: outCount belongs to RAYLIB_AMD_OVERLAP_LIST", who); return false; }
+	if (!s->finalized) { Log("%s: scene was not finalized (Raylib_FinalizeScene)", who); return false; }
+	if (!s->spheres.empty() || !s->cubes.empty()) { Log("%s: the scene holds spheres or cubes; overlap queries are defined on triangles", who); return false; }
+	if (s->bvh.depth > 64) { Log("%s: BVH depth %u exceeds the traversal stack (64)", who, s->bvh.depth); return false; }
+	return true;
+}
+static int32_t OverlapTrianglesInternal(const char* who, SceneHandle sh, int32_t kind, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, void* out, uint32_t* outCount,
+                                        bool hostMem, void* stream)
+{
+	Scene* s = (Scene*)sh;
+	if (!OverlapArgsValid(who, s, kind, flags, q, n, maxHits, out, outCount)) return 0;
+	if (!DeviceAvailable()) return 0;
+	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
+	if (!DeviceOverlapTriangles(*s, kind, flags, q, n, maxHits, out, outCount, hostMem, stream, stats)) return 0;
+	if (!stream) ReportOwnStats(stats);
+	return 1;
+}
+int32_t RaylibAMD_OverlapTriangles(SceneHandle sh, int32_t kind, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, void* out, uint32_t* outCount)
+{
+	return OverlapTrianglesInternal("RaylibAMD_OverlapTriangles", sh, kind, flags, q, n, maxHits, out, outCount, true, nullptr);
+}
+int32_t RaylibAMD_OverlapTrianglesDevice(SceneHandle sh, int32_t kind, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, void* out, uint32_t* outCount, void* stream)
+{
+	return OverlapTrianglesInternal("RaylibAMD_OverlapTrianglesDevice", sh, kind, flags, q, n, maxHits, out, outCount, false, stream);
+}
+// the oracle: statements O1 to O5 (rl_overlap.h, the kernel's own source) over every triangle in export order
+int32_t RaylibAMD_OverlapTrianglesHost(SceneHandle sh, int32_t kind, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, void* out, uint32_t* outCount)
+{
+	Scene* s = (Scene*)sh;
+	if (!OverlapArgsValid("RaylibAMD_OverlapTrianglesHost", s, kind, flags, q, n, maxHits, out, outCount)) return 0;
+	if (!DeviceSyncMovedScene(*s)) return 0;
+	const size_t numTris = s->triangles.size();
+	const bool list = kind == RAYLIB_AMD_OVERLAP_LIST, skipShared = (flags & RAYLIB_AMD_OVERLAP_SKIP_SHARED) != 0u;
+	for (int32_t i = 0; i < n; ++i) {
+		const RaylibAMDOverlapQuery& Q = q[i];
+		int32_t* row = list ? (int32_t*)out + (size_t)i * (size_t)maxHits : nullptr;
+		uint32_t count = 0;
+		if (OverlapTakesPart(Q.v0, Q.v1, Q.v2)) {
+			float lo[3], hi[3];
+			OverlapOwnBox(Q.v0, Q.v1, Q.v2, lo, hi);
+			for (size_t k = 0; k < numTris; ++k) {
+				const HostTriangle& t = s->triangles[k];
+				if (!OverlapAccepts(Q.v0, Q.v1, Q.v2, lo, hi, &t.v0.x, &t.v1.x, &t.v2.x, skipShared)) continue;
+				if (list && count < (uint32_t)maxHits) row[count] = (int32_t)k;   // (ascending k)
+				++count;
+				if (!list) break;
+			}
+		}
+		if (!list) ((uint32_t*)out)[i] = count ? 1u : 0u;
+		else {
+			for (uint32_t e = count; e < (uint32_t)maxHits; ++e) row[e] = -1;
+			if (outCount) outCount[i] = count;
+		}
+	}
+	return 1;
+}
+int32_t RaylibAMD_PlanOverlap(SceneHandle sh, int32_t kind, RaylibAMDQueryPlan* out)
+{
+	Scene* s = (Scene*)sh;
+	if (!s || !s->finalized || !out || (kind != RAYLIB_AMD_OVERLAP_ANY && kind != RAYLIB_AMD_OVERLAP_LIST) || !s->spheres.empty() || !s->cubes.empty()) return 0;
+	memset(out, 0, sizeof(*out));
+	const QueryPlan p = PlanOverlap(*s, kind, ReadRenderKnobs());
 	if (!p.ok) return -1;
 	out->tree = p.tree; out->treeWidth = p.treeWidth; out->nodeBytes = p.nodeBytes; out->stack = p.stack; out->prims = 0; out->early = p.early;
 	return 1;

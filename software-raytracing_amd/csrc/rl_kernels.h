@@ -13,6 +13,8 @@
 //                        shared steps; apart so that k_query and every other unit stay the code they are
 //   rl_nearest.hip       k_nearest (RaylibAMD_NearestPoints): a walk of its own (point-to-box distances, no ray), which shares with the others the records and the
 //                        child sort alone; apart so that every other unit stays the code it is
+//   rl_overlap.hip       k_overlap (RaylibAMD_OverlapTriangles): a walk of its own again (box against box, no ray, no distance) with a per-lane index list; apart for
+//                        the same reason
 //   rl_radiance.hip      k_radiance (RaylibAMD_TraceRadiance): the same reason, towards the render and the query kernels alike
 //   rl_gather.hip        k_gather (RaylibAMD_Gather: rl_k_radiance.inl's twin, the generator instances of its loop) and k_gather_resolve: beside k_radiance they would be
 //                        more callers of the walks and the shading it inlines.  k_gather_resolve and k_gather_adaptive_resolve are one source, rl_k_gather_resolve.inl,
@@ -199,6 +201,23 @@ template <int TREE, int KIND, int STACK> __global__ void __launch_bounds__(RL_BL
 #define RL_NEAREST_INSTANCES(X) RL_NEAREST_INSTANCES_K(X, 0) RL_NEAREST_INSTANCES_K(X, 1)
 #define RL_K_NEAREST(a, b, c) template __global__ void k_nearest<a, b, c>(RL_NEAREST_ARGS);
 RL_NEAREST_INSTANCES(extern RL_K_NEAREST)
+
+// ---------------------------------------------------------------------------
+// The triangle-overlap queries (RaylibAMD_OverlapTriangles; rl_k_overlap.inl, arithmetic of rl_overlap.h)
+enum { RL_OK_ANY = 0, RL_OK_LIST = 1 };   // RAYLIB_AMD_OVERLAP_*
+#define RL_OVERLAP_SKIP_SHARED 1u         /* RAYLIB_AMD_OVERLAP_SKIP_SHARED */
+#define RL_MAX_OVERLAPS 16                /* RAYLIB_AMD_MAX_OVERLAPS */
+// TREE: 2 the binary tree (S.nodes), 4 the grid nodes (S.nodes4).  STACK: the walk's stack.  queries: n records of three float4 (a vertex and a word that is not
+// read, each).  flags: RL_OVERLAP_SKIP_SHARED or 0.  maxHits: 1 .. RL_MAX_OVERLAPS for LIST, and the launch then carries maxHits * RL_BLOCK words of dynamic LDS
+// (the lanes' lists); not read for ANY.  out: uint32_t per query (ANY) or a row of maxHits int32_t (LIST).  outCount: n words or null (LIST).  slotIndex:
+// triangle slot -> export index (null: the identity).  counters: CNT_RAYS (queries), CNT_NODES, CNT_TRIS sums, or null.
+#define RL_OVERLAP_ARGS const DSceneView, const float4* __restrict__, uint32_t, uint32_t, uint32_t, void* __restrict__, uint32_t* __restrict__, const int32_t* __restrict__, unsigned int* __restrict__, unsigned long long* __restrict__
+template <int TREE, int KIND, int STACK> __global__ void __launch_bounds__(RL_BLOCK) k_overlap(RL_OVERLAP_ARGS);
+// The instances rl_rt_rays.hip OverlapKernelOfKind selects from: (TREE, KIND, STACK)
+#define RL_OVERLAP_INSTANCES_K(X, K) X(2, K, 32) X(2, K, 64) X(4, K, 32) X(4, K, 64)
+#define RL_OVERLAP_INSTANCES(X) RL_OVERLAP_INSTANCES_K(X, 0) RL_OVERLAP_INSTANCES_K(X, 1)
+#define RL_K_OVERLAP(a, b, c) template __global__ void k_overlap<a, b, c>(RL_OVERLAP_ARGS);
+RL_OVERLAP_INSTANCES(extern RL_K_OVERLAP)
 
 // ---------------------------------------------------------------------------
 // Path-traced radiance along caller rays (RaylibAMD_TraceRadiance; rl_k_radiance.inl)

@@ -194,6 +194,19 @@ QueryPlan PlanNearest(const Scene& sc, int32_t kind, const RenderKnobs& k)
 	return p;
 }
 
+QueryPlan PlanOverlap(const Scene& sc, int32_t kind, const RenderKnobs& k)
+{
+	// Unless RAYLIB_QUERY_TREE says otherwise: the grid-4 tree while its walk is the 32-deep instance, else the binary tree.  Measured (DESIGN.md section 2,
+	// profiles/overlap.json): on Cornell, both instances 32 deep, the grid walk is 0 - 8 % faster; on the 298 k-triangle room the grid walk is the 64-deep
+	// instance, 2 waves per SIMD for the binary walk's 5, and the self-intersection pass -- queries on the surface, which walk down to many leaves -- takes
+	// 0.84 of its time on the binary tree.  (Queries in empty space, which end high in the tree and cost half of that, are faster on the grid nodes even there.)
+	RenderKnobs asked = k;
+	if (!asked.queryTree) asked.queryTree = (!sc.bvh.nodes4q.empty() && sc.bvh.stackNeed4 <= 32) ? 4 : 2;
+	QueryPlan p = PlanRadiance(sc, asked);   // the same trees under the same switch
+	p.early = kind == RAYLIB_AMD_OVERLAP_ANY;
+	return p;
+}
+
 GatherCut PlanGatherCut(uint32_t n, uint32_t sampleCount, bool sphere, const RenderKnobs& k)
 {
 	GatherCut c;

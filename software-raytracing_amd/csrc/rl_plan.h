@@ -90,6 +90,13 @@ QueryPlan PlanRadiance(const Scene& sc, const RenderKnobs& knobs);
 // their stack bounds are its bounds.  There is no 8-wide nearest walk: RAYLIB_QUERY_TREE=8 falls through to 4, =2 walks the binary tree.  `early`: the kind is
 // WITHIN.  The scene holds triangles only (the entries refuse spheres and cubes before they plan).
 QueryPlan PlanNearest(const Scene& sc, int32_t kind, const RenderKnobs& knobs);
+// Which tree and k_overlap instance a batch of triangle-overlap queries walks (RaylibAMD_OverlapTriangles, rl_k_overlap.inl): PlanNearest's trees under the same
+// switch, with a default of its own: the grid-4 tree when the scene carries one and its worst-case stack fits the 32-deep instance, else the binary tree,
+// which the self-intersection pass on the 298 k-triangle room walks faster than the 64-deep grid instance (measured: DESIGN.md section 2).
+// RAYLIB_QUERY_TREE=4 takes the grid-4 tree up to a worst-case stack of 64 entries, =8 falls through to 4 (no 8-wide walk), =2 walks the binary tree.  At most
+// (children - 1) pushes per level, so the ray walks' stack bounds hold.  `early`: the kind is ANY.  The scene holds triangles
+// only (the entries refuse spheres and cubes before they plan).
+QueryPlan PlanOverlap(const Scene& sc, int32_t kind, const RenderKnobs& knobs);
 
 // How RaylibAMD_Gather cuts n points x sampleCount samples into launches (rl_rt_rays.hip DeviceGather; RaylibAMD_PlanGatherCut): a launch holds at most `slots`
 // (point, sample) pairs -- RL_GATHER_SAMPLE_BUDGET over the slot's bytes (16 for IRRADIANCE, 32 for SH9), or RAYLIB_GATHER_BATCH, at most RL_GATHER_MAX_SLOTS.

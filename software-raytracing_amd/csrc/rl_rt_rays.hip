@@ -1,4 +1,4 @@
-// Host runtime: rays of the caller's -- the ray queries (RaylibAMD_TraceRays, k_query), the ordered multi-hit queries (RaylibAMD_TraceRaysAll, k_query_all) and the nearest-point queries (RaylibAMD_NearestPoints, k_nearest) that share their call (BeginQueryCall), path-traced radiance (RaylibAMD_TraceRadiance, k_radiance) and the
+// Host runtime: rays of the caller's -- the ray queries (RaylibAMD_TraceRays, k_query), the ordered multi-hit queries (RaylibAMD_TraceRaysAll, k_query_all) the nearest-point queries (RaylibAMD_NearestPoints, k_nearest) and the triangle-overlap queries (RaylibAMD_OverlapTriangles, k_overlap) that share their call (BeginQueryCall), path-traced radiance (RaylibAMD_TraceRadiance, k_radiance) and the
 // irradiance and SH probes gathered from it at caller points (RaylibAMD_Gather, k_gather + k_gather_resolve) on rank 0's device, from host memory or from device pointers, on the library's stream (synchronous, with stats) or enqueued on a stream of the caller's (rl_rt.h).
 // The two entries share the refusals of a device call's pointers, the synchronous call's counter block and event pair, the stats' header, the staging of a
 // host call through qRays / qOut, the grid that fills the device once, and the synchronous tail; each keeps its plan and kernel, its parameter block and the
@@ -33,6 +33,16 @@ static NearestKernel NearestKernelOfKind(const QueryPlan& p)
 }
 static_assert(RAYLIB_AMD_NEAREST_WITHIN == RL_NK_WITHIN && RAYLIB_AMD_NEAREST_CLOSEST == RL_NK_CLOSEST, "nearest kinds");
 static_assert(sizeof(RaylibAMDNearestQuery) == 16 && sizeof(RaylibAMDNearestHit) == sizeof(DNearestHit), "nearest records");
+
+typedef void (*OverlapKernel)(const DSceneView, const float4*, uint32_t, uint32_t, uint32_t, void*, uint32_t*, const int32_t*, unsigned int*, unsigned long long*);
+template <int KIND>
+static OverlapKernel OverlapKernelOfKind(const QueryPlan& p)
+{
+	if (p.tree == TREE_GRID4) return p.stack <= 32 ? (OverlapKernel)k_overlap<4, KIND, 32> : (OverlapKernel)k_overlap<4, KIND, 64>;
+	return p.stack <= 32 ? (OverlapKernel)k_overlap<2, KIND, 32> : (OverlapKernel)k_overlap<2, KIND, 64>;
+}
+static_assert(RAYLIB_AMD_OVERLAP_ANY == RL_OK_ANY && RAYLIB_AMD_OVERLAP_LIST == RL_OK_LIST && RAYLIB_AMD_OVERLAP_SKIP_SHARED == RL_OVERLAP_SKIP_SHARED, "overlap kinds and flags");
+static_assert(sizeof(RaylibAMDOverlapQuery) == 48 && RAYLIB_AMD_MAX_OVERLAPS == RL_MAX_OVERLAPS, "overlap records");
 
 typedef void (*RadianceKernel)(const DSceneView, const SkyRot, const DRadianceParams, const float4*, uint32_t, float4*, float*, unsigned int*, unsigned long long*);
 static RadianceKernel RadianceKernelFor(const QueryPlan& p)
@@ -90,7 +100,7 @@ static void StatsHeader(RaylibAMDStats& stats, const QueryPlan& plan, const Scen
 	stats.treeWidth = plan.treeWidth; stats.nodeBytes = plan.nodeBytes;
 	OneRankStats(stats, sc);
 }
-// a host call's rays (n records of 32 bytes; a nearest query's points: 16) into the rank's staging buffer, behind whatever `st` holds; its results go through qOut
+// a host call's rays (n records of 32 bytes; a nearest query's points: 16; an overlap query's triangles: 48) into the rank's staging buffer, behind whatever `st` holds; its results go through qOut
 static bool StageRays(RankCtx& R, const void* rays, int32_t n, size_t outBytes, hipStream_t st, size_t recordBytes = sizeof(RaylibAMDRay))
 {
 	if (!R.qRays.Grow((size_t)n * recordBytes) || !R.qOut.Grow(outBytes)) return false;
@@ -295,6 +305,48 @@ bool DeviceNearestPoints(Scene& sc, int32_t kind, const void* points, int32_t n,
 	if (!ReleaseRingCounter(R, slot, st)) return false;
 	if (!sync) return true;
 	return FinishSync(R, st, { { hostMem ? out : nullptr, dOut, outBytes } }, t0, stats);
+}
+
+// A triangle-overlap call is a nearest-point call with a 48-byte record, rows of maxHits indices and, when asked for, a count per query (staged through qPrim, as
+// the multi-hit call's); a LIST launch carries the lanes' lists as dynamic LDS (maxHits * RL_BLOCK words), which its grid's occupancy accounts for.
+bool DeviceOverlapTriangles(Scene& sc, int32_t kind, uint32_t flags, const void* queries, int32_t n, int32_t maxHits, void* out, uint32_t* outCount, bool hostMem, void* stream,
+                            RaylibAMDStats& stats)
+{
+	const auto t0 = std::chrono::steady_clock::now();
+	std::lock_guard<std::mutex> lk(Rt().lock);
+	if (!EnsureRuntime()) return false;
+	RankCtx& R = Rank0();
+	HIP_OK(hipSetDevice(R.device));
+	const QueryPlan plan = PlanOverlap(sc, kind, ReadRenderKnobs());
+	if (!plan.ok) { Log("RaylibAMD_OverlapTriangles: BVH depth %u exceeds the traversal stack (64)", sc.bvh.depth); return false; }
+	const bool list = kind == RAYLIB_AMD_OVERLAP_LIST;
+	const size_t outBytes = list ? (size_t)n * (size_t)maxHits * sizeof(int32_t) : (size_t)n * sizeof(uint32_t), countBytes = outCount ? (size_t)n * sizeof(uint32_t) : 0;
+	if (!hostMem && n > 0 && !DevicePointersOk("RaylibAMD_OverlapTrianglesDevice", "queries", R.device, queries, out, 3u, (const int32_t*)outCount, outCount != nullptr)) return false;
+	QueryCall U;
+	if (!BeginQueryCall(sc, R, plan, list, stream, U, stats)) return false;
+	if (n == 0) return true;
+	const hipStream_t st = U.st;
+	const float4* dQueries = (const float4*)queries; void* dOut = out; uint32_t* dCount = outCount;
+	if (hostMem) {
+		if (outCount && !R.qPrim.Grow((size_t)n * sizeof(int32_t))) return false;
+		if (!StageRays(R, queries, n, outBytes, st, sizeof(RaylibAMDOverlapQuery))) return false;
+		dQueries = R.qRays.ptr; dOut = R.qOut.ptr; if (outCount) dCount = (uint32_t*)R.qPrim.ptr;
+	}
+	const OverlapKernel kernel = list ? OverlapKernelOfKind<RL_OK_LIST>(plan) : OverlapKernelOfKind<RL_OK_ANY>(plan);
+	const size_t listBytes = list ? (size_t)maxHits * RL_BLOCK * sizeof(uint32_t) : 0;
+	int blocksPerCU = 0;
+	HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, (const void*)kernel, RL_BLOCK, listBytes));
+	if (blocksPerCU < 1) { Log("RaylibAMD_OverlapTriangles: no workgroup of the kernel fits a compute unit with %zu bytes of list", listBytes); return false; }
+	const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)R.numCUs * (uint64_t)blocksPerCU, ((uint64_t)n + RL_BLOCK - 1) / RL_BLOCK));
+	const DSceneView view = U.Cp->view;
+	HIP_OK(hipMemsetAsync(U.counter, 0, sizeof(unsigned int), st));
+	if (U.sync && !BeginSync(R, st)) return false;
+	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RL_BLOCK), (uint32_t)listBytes, st, view, dQueries, (uint32_t)n, flags, (uint32_t)(list ? maxHits : 0), dOut, dCount,
+	                   (const int32_t*)U.Cp->slotIndex.ptr, U.counter, U.sync ? R.qStats.ptr : nullptr);
+	HIP_OK(hipGetLastError());
+	if (!ReleaseRingCounter(R, U.slot, st)) return false;
+	if (!U.sync) return true;
+	return FinishSync(R, st, { { hostMem ? out : nullptr, dOut, outBytes }, { hostMem ? (void*)outCount : nullptr, dCount, countBytes } }, t0, stats);
 }
 
 // ---- what a radiance call and a gather share ----

@@ -258,6 +258,65 @@ def nearest_points(lib, scene, points, kind, host=False):
     return out
 
 
+OVERLAP_ANY, OVERLAP_LIST = 0, 1                    # RAYLIB_AMD_OVERLAP_*
+OVERLAP_SKIP_SHARED = 1                             # RAYLIB_AMD_OVERLAP_SKIP_SHARED
+MAX_OVERLAPS = 16                                   # RAYLIB_AMD_MAX_OVERLAPS
+OVERLAP_QUERY_DTYPE = np.dtype([("v0", "f4", 3), ("reserved0", "u4"), ("v1", "f4", 3), ("reserved1", "u4"), ("v2", "f4", 3), ("reserved2", "u4")])   # RaylibAMDOverlapQuery
+
+
+def overlap_queries(v0, v1, v2):
+    """OVERLAP_QUERY_DTYPE records from three (n, 3) vertex arrays."""
+    q = np.zeros(len(v0), OVERLAP_QUERY_DTYPE)
+    q["v0"], q["v1"], q["v2"] = v0, v1, v2
+    return q
+
+
+def plan_overlap(lib, scene, kind):
+    """RaylibAMD_PlanOverlap: (return code, plan dict)."""
+    p = QueryPlan()
+    r = lib.RaylibAMD_PlanOverlap(scene, int(kind), C.byref(p))
+    return r, p.as_dict()
+
+
+def overlap_triangles(lib, scene, queries, kind, flags=0, max_hits=MAX_OVERLAPS, host=False, count=True):
+    """Batched triangle-overlap queries (RaylibAMD_OverlapTriangles / RaylibAMD_OverlapTrianglesDevice / RaylibAMD_OverlapTrianglesHost, statements O1 to O6).
+
+    queries: OVERLAP_QUERY_DTYPE records (or an (n, 12) float32 array of the same 48 bytes).  A NumPy array goes through the host entry (host=True: through the
+    oracle, which needs no device) and returns NumPy arrays: uint32 words for OVERLAP_ANY; for OVERLAP_LIST the (n, max_hits) int32 rows, and with count=True the
+    pair (rows, uint32 counts).  An (n, 12) float32 torch tensor on the device goes through the device entry on torch.cuda.current_stream(), as nearest_points:
+    enqueued on a stream of the caller's, synchronous on torch's default stream (synchronised first); it returns int32 tensors of the same shapes.  Raises
+    RuntimeError when the library refuses the call."""
+    kind, flags, max_hits = int(kind), int(flags), int(max_hits)
+    if kind not in (OVERLAP_ANY, OVERLAP_LIST):
+        raise ValueError("unknown overlap kind %r" % kind)
+    lst = kind == OVERLAP_LIST
+    want_count = lst and count
+    if isinstance(queries, np.ndarray):
+        q = np.ascontiguousarray(queries)
+        q = q.view(np.uint8).reshape(-1, 48) if q.dtype == OVERLAP_QUERY_DTYPE else np.ascontiguousarray(q, np.float32).reshape(-1, 12)
+        n = len(q)
+        out = np.zeros((n, max(max_hits, 0)), np.int32) if lst else np.zeros(n, np.uint32)
+        counts = np.zeros(n, np.uint32) if want_count else None
+        name = "RaylibAMD_OverlapTrianglesHost" if host else "RaylibAMD_OverlapTriangles"
+        if getattr(lib, name)(scene, kind, flags, q.ctypes.data, n, max_hits, out.ctypes.data, counts.ctypes.data if want_count else None) != 1:
+            raise RuntimeError(name + " refused the query")
+        return (out, counts) if want_count else out
+    import torch
+    if host or not (isinstance(queries, torch.Tensor) and queries.is_cuda and queries.dtype == torch.float32):
+        raise TypeError("queries: a NumPy array, or a float32 torch tensor on the device (host=False)")
+    q = queries.reshape(-1, 12).contiguous()
+    n = q.shape[0]
+    out = torch.empty((n, max(max_hits, 0)) if lst else (n,), dtype=torch.int32, device=q.device)
+    counts = torch.empty(n, dtype=torch.int32, device=q.device) if want_count else None
+    stream = torch.cuda.current_stream(q.device)
+    if stream.cuda_stream == 0:
+        stream.synchronize()   # (the library's stream is not ordered against torch's default stream: trace_rays)
+    if lib.RaylibAMD_OverlapTrianglesDevice(scene, kind, flags, C.c_void_p(q.data_ptr()), n, max_hits, C.c_void_p(out.data_ptr()),
+                                            C.c_void_p(counts.data_ptr()) if want_count else None, C.c_void_p(stream.cuda_stream)) != 1:
+        raise RuntimeError("RaylibAMD_OverlapTrianglesDevice refused the query")
+    return (out, counts) if want_count else out
+
+
 def move_triangles(lib, scene, first, positions, normals=None):
     """Move triangles [first, first + n) of a finalized scene (RaylibAMD_SceneMoveTriangles / RaylibAMD_SceneMoveTrianglesDevice).
 
@@ -787,6 +846,10 @@ _EXPORTS = {
     "RaylibAMD_NearestPointsDevice": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "RaylibAMD_NearestPointsHost": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "RaylibAMD_PlanNearest": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(QueryPlan)]),
+    "RaylibAMD_OverlapTriangles": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_OverlapTrianglesDevice": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_OverlapTrianglesHost": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_PlanOverlap": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(QueryPlan)]),
     "RaylibAMD_Gather": (C.c_int32, [C.c_void_p, C.POINTER(GatherParams), C.POINTER(GatherPoint), C.c_int32, C.POINTER(C.c_float)]),
     "RaylibAMD_GatherDevice": (C.c_int32, [C.c_void_p, C.POINTER(GatherParams), C.POINTER(GatherPoint), C.c_int32, C.POINTER(C.c_float), C.c_void_p]),
     "RaylibAMD_GatherDirectionsHost": (C.c_int32, [C.POINTER(GatherParams), C.POINTER(GatherPoint), C.c_int32, C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]),
