@@ -293,7 +293,8 @@ RAYLIB_API int32_t RaylibAMD_PlanNearest(SceneHandle scene, int32_t kind, Raylib
  * holds spheres or cubes; a BVH deeper than 64 levels; no device (the plain and the device entry; the host entry needs none); on the device entry a pointer
  * off rank 0's device, q not 16-byte aligned, out or outCount not 4-byte aligned.  n == 0 returns 1.
  * Still out: spheres and cubes; more than RAYLIB_AMD_MAX_OVERLAPS indices per query (the count is complete all the same); an 8-wide walk; query primitives
- * other than triangles; the contact geometry (intersection segment, penetration depth), a later entry built on the index pairs this one returns.
+ * other than triangles.  The contact geometry of the listed pairs (the intersection segment) is the next section's, RaylibAMD_OverlapContacts; penetration depth
+ * is not a property of a triangle pair in a soup and stays out.
  * Checked against a loop over every triangle and an edge-piercing reference in double precision: tests/test_overlap_host.py, tests/test_gpu_overlap.py. */
 typedef struct RaylibAMDOverlapQuery {      /* 48 bytes, three 16-byte loads; 16-byte aligned on the device entry */
 	float v0[3]; uint32_t reserved0;        /* the reserved words are not read */
@@ -321,6 +322,60 @@ RAYLIB_API int32_t RaylibAMD_OverlapTrianglesHost(SceneHandle scene, int32_t kin
  * `early` is 1 for ANY.  No device needed.  Returns 1, -1 when the BVH is deeper than 64 levels, 0 for a null argument, an unknown kind, a scene not finalized or one that
  * holds spheres or cubes. */
 RAYLIB_API int32_t RaylibAMD_PlanOverlap(SceneHandle scene, int32_t kind, RaylibAMDQueryPlan* out);
+
+/* ---- contact segments of the overlapping pairs -----------------------------------------------------
+ * RAYLIB_AMD_OVERLAP_LIST says that query i meets scene triangle k; this entry also says where: for every pair a LIST query reports, the segment along which
+ * the two triangles cross, computed on the device in the same launch (csrc/rl_contact.h holds the statements for the host oracle and the kernel alike).
+ * Everything is float, single IEEE operations without FMA; dot and cross are the section's above, a / b is the IEEE quotient.
+ * For a pair (Q, T) that O1 to O4 accept under the call's flags:
+ *   C1. Plane values.  nQ = cross(eQ0, eQ1) and nT = cross(eT0, eT1), as in O4.  a_k = dot(nT, q_k - v0) and b_k = dot(nQ, v_k - q0), for k = 0..2.
+ *   C2. Crossing edges.  Q's edge i (q_i to q_j, j = (i + 1) mod 3) crosses T's plane when (a_i <= 0 && 0 < a_j) || (a_j <= 0 && 0 < a_i); T's edges
+ *        likewise with b.  A vertex exactly on the plane counts with the non-positive side, so a sign change is counted once.  Without a NaN a triangle has
+ *        0 or 2 crossing edges.  If either triangle does not have exactly 2, the pair is NO_CROSSING: coplanar pairs, a touch from the non-positive side of
+ *        the plane (a touch from the positive side has two crossing edges that meet at the touching vertex, and gives a segment of one point), a degenerate
+ *        triangle or an overflow that gives NaN.
+ *   C3. Piercing points.  For a crossing edge: w = a_i / (a_i - a_j) and p = q_i + w * (q_j - q_i), componentwise; the difference is the edge vector of O4
+ *        (eQ0 = q1 - q0, eQ1 = q2 - q1, eQ2 = q0 - q2).  The denominator cannot be 0, and 0 <= w <= 1 holds in float because the subtraction rounds
+ *        monotonically.  Q gives PQ[0] and PQ[1], the lower edge index first; T gives PT[0] and PT[1] likewise.  A point's feature: 0..2 Q's edge i, 3..5 T's
+ *        edge j.
+ *   C4. Parameter axis.  d = cross(nQ, nT).  m = 0 if |d.x| >= |d.y| && |d.x| >= |d.z|, else 1 if |d.y| >= |d.z|, else 2 (a NaN therefore falls to 2).  A
+ *        point's parameter is its m-th coordinate.
+ *   C5. Clip by selection.  Each triangle's two points ordered by parameter, swapped when param(P[1]) < param(P[0]): (loQ, hiQ) and (loT, hiT).
+ *        start = param(loT) > param(loQ) ? loT : loQ.  end = param(hiT) < param(hiQ) ? hiT : hiQ.  A NaN compares false and keeps Q's point.  The kind is
+ *        SEGMENT when param(start) <= param(end), else GAP: both triangles straddle each other's plane and O4 accepted the pair, but at rounding level the
+ *        two intervals on the common line miss; the two facing ends are still written.  No endpoint is interpolated a second time: each is one of the four
+ *        piercing points, carried with its feature.
+ *   C6. Record.  p0 = start, p1 = end, features = feature(p0) | feature(p1) << 8.  NO_CROSSING: points +0, features 0.  A row entry behind the count
+ *        (outIndex -1): kind NONE, all 32 bytes zero.
+ * Promises.  The index rows and counts are RAYLIB_AMD_OVERLAP_LIST's, byte for byte, for the same arguments.  Entry e of row i describes the pair (query i,
+ * outIndex[i * maxHits + e]).  A record is a property of the ordered pair (Q, T) alone: no tree, walk order, wave cut, or refit versus rebuild shows in it (as
+ * O6).  After RaylibAMD_SceneMoveTriangles the records are those of the moved triangles.  Every endpoint of a SEGMENT or GAP lies on the edge its feature
+ * names, with w in [0, 1].  It is not promised that (T, Q) gives the mirrored record.
+ * Refusals (0, nothing written): those of RAYLIB_AMD_OVERLAP_LIST, outIndex in the place of out; outContact null with n > 0; on the device entry outContact
+ * not 16-byte aligned or off rank 0's device.  n == 0 returns 1.
+ * Still out: penetration depth; contact normals beyond what nT gives the caller; a symmetric verdict for (T, Q); spheres and cubes; more than
+ * RAYLIB_AMD_MAX_OVERLAPS pairs per query.
+ * Checked against a NumPy restatement byte for byte and an edge-piercing reference in double precision: tests/test_contact_host.py, tests/test_gpu_contact.py. */
+typedef struct RaylibAMDContact {           /* 32 bytes, written as two 16-byte stores; 16-byte aligned on the device entry */
+	float p0[3]; uint32_t kind;             /* RAYLIB_AMD_CONTACT_* */
+	float p1[3]; uint32_t features;         /* feature(p0) | feature(p1) << 8 */
+} RaylibAMDContact;
+#define RAYLIB_AMD_CONTACT_NONE        0    /* a row entry behind the count: all 32 bytes zero */
+#define RAYLIB_AMD_CONTACT_SEGMENT     1
+#define RAYLIB_AMD_CONTACT_GAP         2
+#define RAYLIB_AMD_CONTACT_NO_CROSSING 3    /* points +0, features 0 */
+/* n queries from host memory, results to host memory; synchronous, on the device; stats as RaylibAMD_OverlapTriangles.  outIndex: n * maxHits int32_t, outContact:
+ * n * maxHits records, outCount (may be NULL): n uint32_t. */
+RAYLIB_API int32_t RaylibAMD_OverlapContacts(SceneHandle scene, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, int32_t* outIndex,
+        RaylibAMDContact* outContact, uint32_t* outCount);
+/* The same on device pointers, with the stream, stats, move-ordering and multi-rank rules of RaylibAMD_OverlapTrianglesDevice. */
+RAYLIB_API int32_t RaylibAMD_OverlapContactsDevice(SceneHandle scene, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, int32_t* outIndex,
+        RaylibAMDContact* outContact, uint32_t* outCount, void* stream);
+/* The oracle: O1 to O5 then C1 to C6 over every triangle, no tree, no device.  After a move it refreshes the host's stale triangles first. */
+RAYLIB_API int32_t RaylibAMD_OverlapContactsHost(SceneHandle scene, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, int32_t* outIndex,
+        RaylibAMDContact* outContact, uint32_t* outCount);
+/* RaylibAMD_PlanOverlap's answer for RAYLIB_AMD_OVERLAP_LIST: the same tree and stack; the instance walked is the contacts one (k_overlap_contacts). */
+RAYLIB_API int32_t RaylibAMD_PlanOverlapContacts(SceneHandle scene, RaylibAMDQueryPlan* out);
 
 /* ---- path-traced radiance along caller rays -----------------------------------------------------
  * outRGBA[i] = (the mean over the samples of TraceScene(rays[i], depth 0, maxPathLength, rayTMin), 1): the reference's path tracer (render/renderer.cc:114-208)

@@ -10,6 +10,7 @@
 #include "rl_lightmap.h"
 #include "rl_nearest.h"
 #include "rl_overlap.h"
+#include "rl_contact.h"
 #include "raylib_amd_rng.h"
 
 #include <float.h>
@@ -1084,6 +1085,71 @@ int32_t RaylibAMD_PlanOverlap(SceneHandle sh, int32_t kind, RaylibAMDQueryPlan* 
 	out->tree = p.tree; out->treeWidth = p.treeWidth; out->nodeBytes = p.nodeBytes; out->stack = p.stack; out->prims = 0; out->early = p.early;
 	return 1;
 }
+
+// RaylibAMD_OverlapContacts / ...Device / ...Host (statements C1 to C6): LIST's refusals, and the records' own
+static_assert(sizeof(RaylibAMDContact) == 32 && sizeof(ContactRecord) == 32, "contact records");
+static_assert(RAYLIB_AMD_CONTACT_NONE == RL_CONTACT_NONE && RAYLIB_AMD_CONTACT_SEGMENT == RL_CONTACT_SEGMENT && RAYLIB_AMD_CONTACT_GAP == RL_CONTACT_GAP &&
+              RAYLIB_AMD_CONTACT_NO_CROSSING == RL_CONTACT_NO_CROSSING, "contact kinds");
+static bool ContactArgsValid(const char* who, const Scene* s, uint32_t flags, const void* q, int32_t n, int32_t maxHits, const void* outIndex, const void* outContact, const uint32_t* outCount)
+{
+	if (n > 0 && !outContact) { Log("%s: null argument", who); return false; }
+	return OverlapArgsValid(who, s, RAYLIB_AMD_OVERLAP_LIST, flags, q, n, maxHits, outIndex, outCount);
+}
+static int32_t OverlapContactsInternal(const char* who, SceneHandle sh, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, int32_t* outIndex,
+                                       RaylibAMDContact* outContact, uint32_t* outCount, bool hostMem, void* stream)
+{
+	Scene* s = (Scene*)sh;
+	if (!ContactArgsValid(who, s, flags, q, n, maxHits, outIndex, outContact, outCount)) return 0;
+	if (!DeviceAvailable()) return 0;
+	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
+	if (!DeviceOverlapTriangles(*s, RAYLIB_AMD_OVERLAP_LIST, flags, q, n, maxHits, outIndex, outCount, hostMem, stream, stats, outContact, true)) return 0;
+	if (!stream) ReportOwnStats(stats);
+	return 1;
+}
+int32_t RaylibAMD_OverlapContacts(SceneHandle sh, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, int32_t* outIndex, RaylibAMDContact* outContact,
+                                  uint32_t* outCount)
+{
+	return OverlapContactsInternal("RaylibAMD_OverlapContacts", sh, flags, q, n, maxHits, outIndex, outContact, outCount, true, nullptr);
+}
+int32_t RaylibAMD_OverlapContactsDevice(SceneHandle sh, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, int32_t* outIndex, RaylibAMDContact* outContact,
+                                        uint32_t* outCount, void* stream)
+{
+	return OverlapContactsInternal("RaylibAMD_OverlapContactsDevice", sh, flags, q, n, maxHits, outIndex, outContact, outCount, false, stream);
+}
+// the oracle: O1 to O5 as RaylibAMD_OverlapTrianglesHost, then C1 to C6 (rl_contact.h, the kernel's own source) for every listed pair
+int32_t RaylibAMD_OverlapContactsHost(SceneHandle sh, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, int32_t* outIndex, RaylibAMDContact* outContact,
+                                      uint32_t* outCount)
+{
+	Scene* s = (Scene*)sh;
+	if (!ContactArgsValid("RaylibAMD_OverlapContactsHost", s, flags, q, n, maxHits, outIndex, outContact, outCount)) return 0;
+	if (!DeviceSyncMovedScene(*s)) return 0;
+	const size_t numTris = s->triangles.size();
+	const bool skipShared = (flags & RAYLIB_AMD_OVERLAP_SKIP_SHARED) != 0u;
+	for (int32_t i = 0; i < n; ++i) {
+		const RaylibAMDOverlapQuery& Q = q[i];
+		int32_t* row = outIndex + (size_t)i * (size_t)maxHits;
+		RaylibAMDContact* rec = outContact + (size_t)i * (size_t)maxHits;
+		uint32_t count = 0;
+		if (OverlapTakesPart(Q.v0, Q.v1, Q.v2)) {
+			float lo[3], hi[3];
+			OverlapOwnBox(Q.v0, Q.v1, Q.v2, lo, hi);
+			for (size_t k = 0; k < numTris; ++k) {
+				const HostTriangle& t = s->triangles[k];
+				if (!OverlapAccepts(Q.v0, Q.v1, Q.v2, lo, hi, &t.v0.x, &t.v1.x, &t.v2.x, skipShared)) continue;
+				if (count < (uint32_t)maxHits) {   // (ascending k)
+					row[count] = (int32_t)k;
+					const ContactRecord R = ContactOfPair(Q.v0, Q.v1, Q.v2, &t.v0.x, &t.v1.x, &t.v2.x);
+					memcpy(&rec[count], &R, sizeof(R));
+				}
+				++count;
+			}
+		}
+		for (uint32_t e = count; e < (uint32_t)maxHits; ++e) { row[e] = -1; memset(&rec[e], 0, sizeof(rec[e])); }
+		if (outCount) outCount[i] = count;
+	}
+	return 1;
+}
+int32_t RaylibAMD_PlanOverlapContacts(SceneHandle sh, RaylibAMDQueryPlan* out) { return RaylibAMD_PlanOverlap(sh, RAYLIB_AMD_OVERLAP_LIST, out); }
 
 // RaylibAMD_TraceRadiance / RaylibAMD_TraceRadianceDevice / RaylibAMD_PlanRadiance: what of RaylibAMDRadianceParams needs no device and no rays
 static bool RadianceParamsValid(const char* who, const Scene* s, const RaylibAMDRadianceParams* p)

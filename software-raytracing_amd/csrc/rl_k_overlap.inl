@@ -14,7 +14,14 @@
 // maxHits * RL_BLOCK words, entry k of lane l at word k * RL_BLOCK + l: the lanes of a wave touch consecutive words whatever k each of them is at, so no
 // two lanes of a 32-lane half share a bank.  A candidate above a full list's last entry only counts.  Every slot sits in exactly one leaf: no index comes
 // twice.  The list orders by export index, which says nothing about where a triangle lies, so a full list prunes nothing and LIST always walks to the end.
+// The contacts kind (k_overlap_contacts: RaylibAMD_OverlapContacts) is LIST up to write-out; there every held entry gets its record (rl_contact.h, statements C1
+// to C6).  It carries two more arguments, so it is a kernel of its own name, and it is this file's text a second time: rl_overlap.hip includes the file once
+// plainly, which gives k_overlap exactly as it was before there were contacts, and once under RL_OVERLAP_CONTACTS_PASS, which gives k_overlap_contacts.  (A body
+// shared through an inlined function would be one text too, but the compiler schedules the eight older instances differently then; this way they stay the
+// code they are.)  The list is keyed by export index and the record needs the triangle's slot: a table, export index -> slot, beside slotIndex (4 bytes per
+// triangle) gives it, so the dynamic LDS and with it the occupancy stay LIST's.
 
+#ifndef RL_OVERLAP_CONTACTS_PASS
 // One leaf: `count` triangles from slot `first`.  True: an ANY query has found its triangle.
 template <int KIND>
 __device__ __forceinline__ bool OverlapLeaf(const DSceneView& S, const float q0[3], const float q1[3], const float q2[3], const float loQ[3], const float hiQ[3], bool skipShared,
@@ -45,7 +52,10 @@ __device__ __forceinline__ bool OverlapLeaf(const DSceneView& S, const float q0[
 	return false;
 }
 
+#endif
+
 // (template and kernel arguments: rl_kernels.h)
+#ifndef RL_OVERLAP_CONTACTS_PASS
 template <int TREE, int KIND, int STACK>
 __global__ void __launch_bounds__(RL_BLOCK)
 k_overlap(const DSceneView S, const float4* __restrict__ queries, uint32_t n, uint32_t flags, uint32_t maxHits, void* __restrict__ out, uint32_t* __restrict__ outCount,
@@ -53,6 +63,16 @@ k_overlap(const DSceneView S, const float4* __restrict__ queries, uint32_t n, ui
 {
 	static_assert(TREE == 2 || TREE == 4, "tree");
 	static_assert(KIND == RL_OK_ANY || KIND == RL_OK_LIST, "kind");
+#else
+template <int TREE, int STACK>
+__global__ void __launch_bounds__(RL_BLOCK)
+k_overlap_contacts(const DSceneView S, const float4* __restrict__ queries, uint32_t n, uint32_t flags, uint32_t maxHits, void* __restrict__ out, uint32_t* __restrict__ outCount,
+                   const int32_t* __restrict__ slotIndex, unsigned int* __restrict__ queryCounter, unsigned long long* __restrict__ counters,
+                   float4* __restrict__ outContact, const int32_t* __restrict__ exportSlot)
+{
+	static_assert(TREE == 2 || TREE == 4, "tree");
+	constexpr int KIND = RL_OK_LIST;   // the walk, the list and the rows are LIST's
+#endif
 	__shared__ int s_stack[STACK * RL_BLOCK];
 	extern __shared__ uint32_t s_overlap_list[];   // LIST: maxHits * RL_BLOCK words (the launch's dynamic LDS); ANY: none, never touched
 	int* stk = s_stack + threadIdx.x;
@@ -130,6 +150,23 @@ k_overlap(const DSceneView S, const float4* __restrict__ queries, uint32_t n, ui
 				int32_t* row = (int32_t*)out + (size_t)i * K;   // (64-bit: n * maxHits may reach 2^31 - 1)
 				for (uint32_t e = 0; e < K; ++e) row[e] = e < held ? (int32_t)list[e * RL_BLOCK] : -1;
 				if (outCount) outCount[i] = total;
+#ifdef RL_OVERLAP_CONTACTS_PASS
+				// a record per row entry: Q is still in registers, T is read again from the entry's 64-byte record; behind the count, 32 zero bytes
+				float4* rec = outContact + 2u * ((size_t)i * K);   // (64-bit: the records of n * maxHits entries pass 2^31 bytes long before the rows do)
+				for (uint32_t e = 0; e < K; ++e) {
+					float4 c0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c1 = c0;
+					if (e < held) {
+						const int32_t idx = (int32_t)list[e * RL_BLOCK];
+						const float4* tp = (const float4*)(S.isect + (exportSlot ? exportSlot[idx] : idx));
+						const float4 r0 = GLoadF4(tp, 0), r1 = GLoadF4(tp, 1), r2 = GLoadF4(tp, 2);
+						const float v0[3] = { r0.x, r0.y, r0.z }, v1[3] = { r1.z, r1.w, r2.x }, v2[3] = { r2.y, r2.z, r2.w };
+						const ContactRecord R = ContactOfPair(q0, q1, q2, v0, v1, v2);
+						c0 = make_float4(R.p0[0], R.p0[1], R.p0[2], __uint_as_float(R.kind));
+						c1 = make_float4(R.p1[0], R.p1[1], R.p1[2], __uint_as_float(R.features));
+					}
+					rec[2u * e] = c0; rec[2u * e + 1u] = c1;
+				}
+#endif
 			}
 		}
 	}

@@ -218,6 +218,14 @@ template <int TREE, int KIND, int STACK> __global__ void __launch_bounds__(RL_BL
 #define RL_OVERLAP_INSTANCES(X) RL_OVERLAP_INSTANCES_K(X, 0) RL_OVERLAP_INSTANCES_K(X, 1)
 #define RL_K_OVERLAP(a, b, c) template __global__ void k_overlap<a, b, c>(RL_OVERLAP_ARGS);
 RL_OVERLAP_INSTANCES(extern RL_K_OVERLAP)
+// The contacts kind (RaylibAMD_OverlapContacts; statements C1 to C6, rl_contact.h): k_overlap's text as LIST (rl_k_overlap.inl, its second pass), and at write-out a 32-byte record per held entry.
+// Two more arguments -- outContact: n * maxHits records of two float4, 16-byte aligned; exportSlot: export index -> triangle slot, the inverse of slotIndex
+// (null: the identity) -- so it is a kernel of its own name and the eight instances above keep their arguments.  The same dynamic LDS as LIST.
+#define RL_OVERLAP_CONTACTS_ARGS RL_OVERLAP_ARGS, float4* __restrict__, const int32_t* __restrict__
+template <int TREE, int STACK> __global__ void __launch_bounds__(RL_BLOCK) k_overlap_contacts(RL_OVERLAP_CONTACTS_ARGS);
+#define RL_OVERLAP_CONTACTS_INSTANCES(X) X(2, 32) X(2, 64) X(4, 32) X(4, 64)
+#define RL_K_OVERLAP_CONTACTS(a, b) template __global__ void k_overlap_contacts<a, b>(RL_OVERLAP_CONTACTS_ARGS);
+RL_OVERLAP_CONTACTS_INSTANCES(extern RL_K_OVERLAP_CONTACTS)
 
 // ---------------------------------------------------------------------------
 // Path-traced radiance along caller rays (RaylibAMD_TraceRadiance; rl_k_radiance.inl)

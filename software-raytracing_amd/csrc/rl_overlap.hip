@@ -7,13 +7,18 @@
 // ---- the device library ----
 #include "rl_kernels.h"
 #include "rl_overlap.h"
+#include "rl_contact.h"
 
 namespace rl {
 
 // ---- kernel bodies ----
 #include "rl_k_overlap.inl"
+#define RL_OVERLAP_CONTACTS_PASS   // the same text again, as k_overlap_contacts
+#include "rl_k_overlap.inl"
+#undef RL_OVERLAP_CONTACTS_PASS
 
 // ---- instances ----
 RL_OVERLAP_INSTANCES(RL_K_OVERLAP)
+RL_OVERLAP_CONTACTS_INSTANCES(RL_K_OVERLAP_CONTACTS)
 
 } // namespace rl

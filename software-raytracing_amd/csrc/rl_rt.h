@@ -4,7 +4,7 @@
 //   rl_rt_scene.hip   a flattened scene (rl_scene.cc FlattenScene) to every device, its sky and wide trees; images: read-back, RGB dump, post-processing
 //   rl_rt_frame.hip   kernel selection and the one enqueue path of every render (EnqueueFrame), a rank's one-view render, a batch of views
 //   rl_rt_render.hip  whole frames over N ranks (gather, scatter, two frames in flight), DeviceRender, progressive sessions
-//   rl_rt_rays.hip    caller rays and points: DeviceTraceRays, DeviceTraceRaysAll, DeviceNearestPoints, DeviceOverlapTriangles, DeviceTraceRadiance, DeviceGather (plain and adaptive: one driver, GatherLocked)
+//   rl_rt_rays.hip    caller rays and points: DeviceTraceRays, DeviceTraceRaysAll, DeviceNearestPoints, DeviceOverlapTriangles (and its contacts), DeviceTraceRadiance, DeviceGather (plain and adaptive: one driver, GatherLocked)
 //   rl_rt_lightmap.hip  lightmaps: DeviceLightmapPoints, DeviceBakeLightmap (the raster stages, then DeviceGather's body or the caller's atlas, the filter, the atlas stages)
 //   rl_rt_move.hip    RaylibAMD_SceneMoveTriangles: the moved records and the refit of every tree on the device, the host copies' read-back, RaylibAMD_SceneCheckTrees
 //   rl_rt_hooks.hip   test hooks
@@ -81,6 +81,7 @@ struct DeviceSceneCopy {
 	DevBuf<DSphere> spheres; DevBuf<DCube> cubes;
 	DevBuf<float> lmTris;        // the scene's triangles in RaylibAMD_SceneExportTriangles order (26 floats each), uploaded when a lightmap call first needs them
 	DevBuf<int32_t> slotIndex;   // triangle slot -> index in the scene's triangle order (the ray queries' primitive numbers), uploaded when a query first needs it
+	DevBuf<int32_t> exportSlot;  // its inverse, index in the scene's triangle order -> slot: uploaded when a contacts query first needs it (made, and remade, where slotIndex is)
 	// the sky panorama is read when a render starts, as the reference does (renderer.cc:159-176 dereferences the handle per miss)
 	DevBuf<float4> sky;
 	const Image* skyImage = nullptr; uint64_t skyVersion = 0;
@@ -196,6 +197,7 @@ struct RankCtx {
 	DevBuf<float4> qRays;
 	DevBuf<void> qOut;
 	DevBuf<int32_t> qPrim;
+	DevBuf<float4> qContact;   // a host contacts call's records (RaylibAMD_OverlapContacts), staged as qPrim is
 	DevBuf<unsigned int> qRing; hipEvent_t qRingEv[RL_QUERY_RING] = {}; bool qRingUsed[RL_QUERY_RING] = {}; uint32_t qRingNext = 0;
 	DevBuf<unsigned long long> qStats; PinBuf<unsigned long long> qStatsHost;
 	hipEvent_t qEv[2] = { nullptr, nullptr };

@@ -43,6 +43,14 @@ static OverlapKernel OverlapKernelOfKind(const QueryPlan& p)
 }
 static_assert(RAYLIB_AMD_OVERLAP_ANY == RL_OK_ANY && RAYLIB_AMD_OVERLAP_LIST == RL_OK_LIST && RAYLIB_AMD_OVERLAP_SKIP_SHARED == RL_OVERLAP_SKIP_SHARED, "overlap kinds and flags");
 static_assert(sizeof(RaylibAMDOverlapQuery) == 48 && RAYLIB_AMD_MAX_OVERLAPS == RL_MAX_OVERLAPS, "overlap records");
+typedef void (*OverlapContactsKernel)(const DSceneView, const float4*, uint32_t, uint32_t, uint32_t, void*, uint32_t*, const int32_t*, unsigned int*, unsigned long long*, float4*,
+                                      const int32_t*);
+static OverlapContactsKernel OverlapContactsKernelOf(const QueryPlan& p)
+{
+	if (p.tree == TREE_GRID4) return p.stack <= 32 ? (OverlapContactsKernel)k_overlap_contacts<4, 32> : (OverlapContactsKernel)k_overlap_contacts<4, 64>;
+	return p.stack <= 32 ? (OverlapContactsKernel)k_overlap_contacts<2, 32> : (OverlapContactsKernel)k_overlap_contacts<2, 64>;
+}
+static_assert(sizeof(RaylibAMDContact) == 2 * sizeof(float4), "contact records");
 
 typedef void (*RadianceKernel)(const DSceneView, const SkyRot, const DRadianceParams, const float4*, uint32_t, float4*, float*, unsigned int*, unsigned long long*);
 static RadianceKernel RadianceKernelFor(const QueryPlan& p)
@@ -113,6 +121,20 @@ static bool EnsureSlotIndex(DeviceSceneCopy* Cp, const Scene& sc)
 	if (Cp->slotIndex.ptr || sc.bvh.triOrder.empty()) return true;
 	std::vector<int32_t> idx(sc.bvh.triOrder.begin(), sc.bvh.triOrder.end());
 	if (!Cp->slotIndex.Upload(idx.data(), idx.size())) { Cp->slotIndex.Free(); return false; }
+	return true;
+}
+// its inverse, index in the scene's triangle order -> triangle slot, for the call that reads a listed triangle again (the contacts kind of k_overlap)
+static bool EnsureExportSlot(DeviceSceneCopy* Cp, const Scene& sc)
+{
+	if (Cp->exportSlot.ptr || sc.bvh.triOrder.empty()) return true;
+	const size_t m = sc.bvh.triOrder.size();
+	std::vector<int32_t> inv(m, 0);
+	for (size_t slot = 0; slot < m; ++slot) {
+		const size_t k = (size_t)sc.bvh.triOrder[slot];
+		if (k >= m) { Log("RaylibAMD_OverlapContacts: triangle slot %zu names triangle %zu of %zu", slot, k, m); return false; }
+		inv[k] = (int32_t)slot;
+	}
+	if (!Cp->exportSlot.Upload(inv.data(), inv.size())) { Cp->exportSlot.Free(); return false; }
 	return true;
 }
 // The ring of work counters the queries' launches take in turn: the next slot, free again (RL_QUERY_RING launches ago: long done, unless a caller's stream is that
@@ -257,7 +279,7 @@ bool DeviceTraceRaysAll(Scene& sc, const void* rays, int32_t n, int32_t maxHits,
 	const QueryAllKernel kernel = outCount ? QueryAllKernelOf<true>(plan) : QueryAllKernelOf<false>(plan);
 	const size_t listBytes = 2u * (size_t)maxHits * RL_BLOCK * sizeof(uint32_t);
 	int blocksPerCU = 0;
-	HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, (const void*)kernel, RL_BLOCK, listBytes));
+	HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, kernel, RL_BLOCK, listBytes));
 	if (blocksPerCU < 1) { Log("RaylibAMD_TraceRaysAll: no workgroup of the kernel fits a compute unit with %zu bytes of list", listBytes); return false; }
 	const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)R.numCUs * (uint64_t)blocksPerCU, ((uint64_t)n + RL_BLOCK - 1) / RL_BLOCK));
 	const DSceneView view = U.Cp->view;
@@ -309,8 +331,10 @@ bool DeviceNearestPoints(Scene& sc, int32_t kind, const void* points, int32_t n,
 
 // A triangle-overlap call is a nearest-point call with a 48-byte record, rows of maxHits indices and, when asked for, a count per query (staged through qPrim, as
 // the multi-hit call's); a LIST launch carries the lanes' lists as dynamic LDS (maxHits * RL_BLOCK words), which its grid's occupancy accounts for.
+// `contacts` (RaylibAMD_OverlapContacts): kind is LIST, the kernel is the contacts instance of the same plan, and a third output, n * maxHits records of 32
+// bytes, is refused as the rows are (16-byte aligned: two float4 stores each) and staged through qContact.
 bool DeviceOverlapTriangles(Scene& sc, int32_t kind, uint32_t flags, const void* queries, int32_t n, int32_t maxHits, void* out, uint32_t* outCount, bool hostMem, void* stream,
-                            RaylibAMDStats& stats)
+                            RaylibAMDStats& stats, void* outContact, bool contacts)
 {
 	const auto t0 = std::chrono::steady_clock::now();
 	std::lock_guard<std::mutex> lk(Rt().lock);
@@ -321,32 +345,43 @@ bool DeviceOverlapTriangles(Scene& sc, int32_t kind, uint32_t flags, const void*
 	if (!plan.ok) { Log("RaylibAMD_OverlapTriangles: BVH depth %u exceeds the traversal stack (64)", sc.bvh.depth); return false; }
 	const bool list = kind == RAYLIB_AMD_OVERLAP_LIST;
 	const size_t outBytes = list ? (size_t)n * (size_t)maxHits * sizeof(int32_t) : (size_t)n * sizeof(uint32_t), countBytes = outCount ? (size_t)n * sizeof(uint32_t) : 0;
-	if (!hostMem && n > 0 && !DevicePointersOk("RaylibAMD_OverlapTrianglesDevice", "queries", R.device, queries, out, 3u, (const int32_t*)outCount, outCount != nullptr)) return false;
+	const char* api = contacts ? "RaylibAMD_OverlapContactsDevice" : "RaylibAMD_OverlapTrianglesDevice";
+	const size_t contactBytes = contacts ? (size_t)n * (size_t)maxHits * sizeof(RaylibAMDContact) : 0;
+	if (!hostMem && n > 0 && !DevicePointersOk(api, "queries", R.device, queries, out, 3u, (const int32_t*)outCount, outCount != nullptr)) return false;
+	if (!hostMem && n > 0 && contacts && !DevicePointersOk(api, "queries", R.device, queries, outContact, 15u, nullptr, false)) return false;
 	QueryCall U;
 	if (!BeginQueryCall(sc, R, plan, list, stream, U, stats)) return false;
+	if (contacts && !EnsureExportSlot(U.Cp, sc)) return false;
 	if (n == 0) return true;
 	const hipStream_t st = U.st;
-	const float4* dQueries = (const float4*)queries; void* dOut = out; uint32_t* dCount = outCount;
+	const float4* dQueries = (const float4*)queries; void* dOut = out; uint32_t* dCount = outCount; float4* dContact = (float4*)outContact;
 	if (hostMem) {
 		if (outCount && !R.qPrim.Grow((size_t)n * sizeof(int32_t))) return false;
+		if (contacts && !R.qContact.Grow(contactBytes)) return false;
 		if (!StageRays(R, queries, n, outBytes, st, sizeof(RaylibAMDOverlapQuery))) return false;
 		dQueries = R.qRays.ptr; dOut = R.qOut.ptr; if (outCount) dCount = (uint32_t*)R.qPrim.ptr;
+		if (contacts) dContact = R.qContact.ptr;
 	}
-	const OverlapKernel kernel = list ? OverlapKernelOfKind<RL_OK_LIST>(plan) : OverlapKernelOfKind<RL_OK_ANY>(plan);
+	const void* kernel = contacts ? (const void*)OverlapContactsKernelOf(plan) : (const void*)(list ? OverlapKernelOfKind<RL_OK_LIST>(plan) : OverlapKernelOfKind<RL_OK_ANY>(plan));
 	const size_t listBytes = list ? (size_t)maxHits * RL_BLOCK * sizeof(uint32_t) : 0;
 	int blocksPerCU = 0;
-	HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, (const void*)kernel, RL_BLOCK, listBytes));
+	HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, kernel, RL_BLOCK, listBytes));
 	if (blocksPerCU < 1) { Log("RaylibAMD_OverlapTriangles: no workgroup of the kernel fits a compute unit with %zu bytes of list", listBytes); return false; }
 	const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)R.numCUs * (uint64_t)blocksPerCU, ((uint64_t)n + RL_BLOCK - 1) / RL_BLOCK));
 	const DSceneView view = U.Cp->view;
 	HIP_OK(hipMemsetAsync(U.counter, 0, sizeof(unsigned int), st));
 	if (U.sync && !BeginSync(R, st)) return false;
-	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RL_BLOCK), (uint32_t)listBytes, st, view, dQueries, (uint32_t)n, flags, (uint32_t)(list ? maxHits : 0), dOut, dCount,
-	                   (const int32_t*)U.Cp->slotIndex.ptr, U.counter, U.sync ? R.qStats.ptr : nullptr);
+	if (contacts)
+		hipLaunchKernelGGL((OverlapContactsKernel)kernel, dim3(blocks), dim3(RL_BLOCK), (uint32_t)listBytes, st, view, dQueries, (uint32_t)n, flags, (uint32_t)maxHits, dOut, dCount,
+		                   (const int32_t*)U.Cp->slotIndex.ptr, U.counter, U.sync ? R.qStats.ptr : nullptr, dContact, (const int32_t*)U.Cp->exportSlot.ptr);
+	else
+		hipLaunchKernelGGL((OverlapKernel)kernel, dim3(blocks), dim3(RL_BLOCK), (uint32_t)listBytes, st, view, dQueries, (uint32_t)n, flags, (uint32_t)(list ? maxHits : 0), dOut, dCount,
+		                   (const int32_t*)U.Cp->slotIndex.ptr, U.counter, U.sync ? R.qStats.ptr : nullptr);
 	HIP_OK(hipGetLastError());
 	if (!ReleaseRingCounter(R, U.slot, st)) return false;
 	if (!U.sync) return true;
-	return FinishSync(R, st, { { hostMem ? out : nullptr, dOut, outBytes }, { hostMem ? (void*)outCount : nullptr, dCount, countBytes } }, t0, stats);
+	return FinishSync(R, st, { { hostMem ? out : nullptr, dOut, outBytes }, { hostMem ? (void*)outCount : nullptr, dCount, countBytes },
+	                           { hostMem ? outContact : nullptr, dContact, contactBytes } }, t0, stats);
 }
 
 // ---- what a radiance call and a gather share ----

@@ -317,6 +317,54 @@ def overlap_triangles(lib, scene, queries, kind, flags=0, max_hits=MAX_OVERLAPS,
     return (out, counts) if want_count else out
 
 
+CONTACT_NONE, CONTACT_SEGMENT, CONTACT_GAP, CONTACT_NO_CROSSING = 0, 1, 2, 3        # RAYLIB_AMD_CONTACT_*
+CONTACT_DTYPE = np.dtype([("p0", "f4", 3), ("kind", "u4"), ("p1", "f4", 3), ("features", "u4")])   # RaylibAMDContact
+
+
+def plan_overlap_contacts(lib, scene):
+    """RaylibAMD_PlanOverlapContacts: (return code, plan dict)."""
+    p = QueryPlan()
+    r = lib.RaylibAMD_PlanOverlapContacts(scene, C.byref(p))
+    return r, p.as_dict()
+
+
+def overlap_contacts(lib, scene, queries, flags=0, max_hits=MAX_OVERLAPS, host=False, count=True):
+    """The overlapping pairs of OVERLAP_LIST and the segment along which each pair crosses (RaylibAMD_OverlapContacts / RaylibAMD_OverlapContactsDevice /
+    RaylibAMD_OverlapContactsHost, statements C1 to C6).
+
+    queries: as overlap_triangles.  A NumPy array goes through the host entry (host=True: through the oracle, which needs no device) and returns
+    (rows, contacts, counts): (n, max_hits) int32, (n, max_hits) CONTACT_DTYPE records, n uint32 (None with count=False).  An (n, 12) float32 torch tensor on the
+    device goes through the device entry on torch.cuda.current_stream(), as overlap_triangles; the contacts are then an (n, max_hits, 8) float32 tensor of the
+    same 32 bytes per record (kind and features: .view(torch.int32)[..., 3] and [..., 7]).  Raises RuntimeError when the library refuses the call."""
+    flags, max_hits = int(flags), int(max_hits)
+    if isinstance(queries, np.ndarray):
+        q = np.ascontiguousarray(queries)
+        q = q.view(np.uint8).reshape(-1, 48) if q.dtype == OVERLAP_QUERY_DTYPE else np.ascontiguousarray(q, np.float32).reshape(-1, 12)
+        n = len(q)
+        rows = np.zeros((n, max(max_hits, 0)), np.int32)
+        recs = np.zeros((n, max(max_hits, 0)), CONTACT_DTYPE)
+        counts = np.zeros(n, np.uint32) if count else None
+        name = "RaylibAMD_OverlapContactsHost" if host else "RaylibAMD_OverlapContacts"
+        if getattr(lib, name)(scene, flags, q.ctypes.data, n, max_hits, rows.ctypes.data, recs.ctypes.data, counts.ctypes.data if count else None) != 1:
+            raise RuntimeError(name + " refused the query")
+        return rows, recs, counts
+    import torch
+    if host or not (isinstance(queries, torch.Tensor) and queries.is_cuda and queries.dtype == torch.float32):
+        raise TypeError("queries: a NumPy array, or a float32 torch tensor on the device (host=False)")
+    q = queries.reshape(-1, 12).contiguous()
+    n = q.shape[0]
+    rows = torch.empty((n, max(max_hits, 0)), dtype=torch.int32, device=q.device)
+    recs = torch.empty((n, max(max_hits, 0), 8), dtype=torch.float32, device=q.device)
+    counts = torch.empty(n, dtype=torch.int32, device=q.device) if count else None
+    stream = torch.cuda.current_stream(q.device)
+    if stream.cuda_stream == 0:
+        stream.synchronize()   # (the library's stream is not ordered against torch's default stream: trace_rays)
+    if lib.RaylibAMD_OverlapContactsDevice(scene, flags, C.c_void_p(q.data_ptr()), n, max_hits, C.c_void_p(rows.data_ptr()), C.c_void_p(recs.data_ptr()),
+                                           C.c_void_p(counts.data_ptr()) if count else None, C.c_void_p(stream.cuda_stream)) != 1:
+        raise RuntimeError("RaylibAMD_OverlapContactsDevice refused the query")
+    return rows, recs, counts
+
+
 def move_triangles(lib, scene, first, positions, normals=None):
     """Move triangles [first, first + n) of a finalized scene (RaylibAMD_SceneMoveTriangles / RaylibAMD_SceneMoveTrianglesDevice).
 
@@ -850,6 +898,10 @@ _EXPORTS = {
     "RaylibAMD_OverlapTrianglesDevice": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "RaylibAMD_OverlapTrianglesHost": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "RaylibAMD_PlanOverlap": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(QueryPlan)]),
+    "RaylibAMD_OverlapContacts": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_OverlapContactsDevice": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_OverlapContactsHost": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_PlanOverlapContacts": (C.c_int32, [C.c_void_p, C.POINTER(QueryPlan)]),
     "RaylibAMD_Gather": (C.c_int32, [C.c_void_p, C.POINTER(GatherParams), C.POINTER(GatherPoint), C.c_int32, C.POINTER(C.c_float)]),
     "RaylibAMD_GatherDevice": (C.c_int32, [C.c_void_p, C.POINTER(GatherParams), C.POINTER(GatherPoint), C.c_int32, C.POINTER(C.c_float), C.c_void_p]),
     "RaylibAMD_GatherDirectionsHost": (C.c_int32, [C.POINTER(GatherParams), C.POINTER(GatherPoint), C.c_int32, C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]),
