@@ -259,6 +259,44 @@ RAYLIB_API int32_t RaylibAMD_NearestPointsHost(SceneHandle scene, int32_t kind, 
  * finalized or one that holds spheres or cubes. */
 RAYLIB_API int32_t RaylibAMD_PlanNearest(SceneHandle scene, int32_t kind, RaylibAMDQueryPlan* out);
 
+/* ---- the K nearest triangles and the count in range ------------------------------------------------
+ * Every triangle within a point's radius, the nearest first, and how many there are: the contact step behind RaylibAMD_SceneMoveTriangles (all triangles
+ * within a particle's radius), attribute transfer and smooth distance fields (a blend over the K nearest), a sphere broad phase (the count) -- in one walk of
+ * the tree.  CLOSEST cannot be peeled into this: a point query has no lower bound to raise, and an exact-distance tie would be lost.  RaylibAMD_NearestPoints
+ * keeps refusing kinds other than 0 and 1; these are entries of their own (csrc/rl_k_nearest_all.inl is the walk, RaylibAMD_NearestPointsAllHost the oracle).
+ *   K1. Set.  For a point that takes part (N4), triangle k is in the set exactly when D_k <= R2, with D_k of N1 to N3 and R2 = maxDist * maxDist.  A point
+ *        that does not take part has the empty set, and no walk is made for it.  Membership depends on the point and the triangle alone.
+ *   K2. Order.  The set is sorted by (D, k) ascending, k being the index in RaylibAMD_SceneExportTriangles order -- the key CLOSEST breaks ties with.  Row i of
+ *        outHits holds the first min(maxHits, |set|) triangles as {D, k, b1, b2}, with b1, b2 of N1 for that triangle, and behind them miss records
+ *        {0, -1, 0, 0}.  So outHits[i * maxHits] is CLOSEST's record byte for byte, and maxHits == 1 is CLOSEST.  The order inside an exact-D tie follows the
+ *        export index: RaylibAMD_SceneRebuild does not change it, unlike the multi-hit ray queries' slot order.
+ *   K3. Count.  With outCount non-null, outCount[i] = |set|, however small maxHits is.  With outCount null the walk may prune with its maxHits-th key once the
+ *        list is full, and visits less.  A count with maxDist = +inf visits every triangle of the scene for every point: a loop over the scene, on the device.
+ *   K4. Independence.  The result does not depend on the tree walked, the order of the walk, how the call is cut into waves, or whether the trees were built
+ *        fresh or refitted by RaylibAMD_SceneMoveTriangles (as N5).  After a move the host oracle refreshes the host's stale triangles first.
+ *   K5. Refusals (0, nothing written): points or outHits null with n > 0; n < 0; maxHits outside 1 .. RAYLIB_AMD_MAX_NEAREST; n * maxHits above 2^31 - 1; a
+ *        scene that is not finalized; a scene that holds spheres or cubes; a BVH deeper than 64 levels; no device (the plain and the device entry; the host
+ *        entry needs none); on the device entry a pointer off rank 0's device, points or outHits not 16-byte aligned, outCount not 4-byte aligned.
+ *        n == 0 returns 1.
+ * Still out: spheres and cubes, more than RAYLIB_AMD_MAX_NEAREST records per point (the count is complete all the same), an 8-wide walk, signed distance,
+ * query primitives other than points.
+ * Checked against a loop over every triangle: tests/test_nearest_all_host.py, tests/test_gpu_nearest_all.py. */
+#define RAYLIB_AMD_MAX_NEAREST 16
+/* n points from host memory, results to host memory; synchronous, on the device.  outHits: n * maxHits RaylibAMDNearestHit, row i = point i; outCount: n
+ * uint32_t, or null.  RaylibAMD_GetLastStats then reports rays (= points), nodesVisited, trisTested, kernelMs, wallMs and the tree walked. */
+RAYLIB_API int32_t RaylibAMD_NearestPointsAll(SceneHandle scene, const RaylibAMDNearestQuery* points, int32_t n, int32_t maxHits, RaylibAMDNearestHit* outHits, uint32_t* outCount);
+/* The same on device pointers (rank 0's device), with the stream, stats, move-ordering and multi-rank rules of RaylibAMD_NearestPointsDevice: stream == NULL
+ * is the library's stream, synchronous, with stats; a non-null hipStream_t gets the call enqueued behind the synchronous uploads and the stats are left alone. */
+RAYLIB_API int32_t RaylibAMD_NearestPointsAllDevice(SceneHandle scene, const RaylibAMDNearestQuery* points, int32_t n, int32_t maxHits, RaylibAMDNearestHit* outHits, uint32_t* outCount,
+        void* stream);
+/* The oracle: statements K1 to K3 over every triangle, no tree, no device. */
+RAYLIB_API int32_t RaylibAMD_NearestPointsAllHost(SceneHandle scene, const RaylibAMDNearestQuery* points, int32_t n, int32_t maxHits, RaylibAMDNearestHit* outHits, uint32_t* outCount);
+/* Which tree and kernel instance those calls would walk under the current environment (csrc/rl_plan.cc PlanNearestAll): the tree and the stack
+ * RaylibAMD_PlanNearest gives CLOSEST.  wantCount (outCount non-null) selects the instance that never prunes with the list; the tree is the same.  `early` is 0.
+ * No device needed.  Returns 1, -1 when the BVH is deeper than 64 levels, 0 for a null argument, maxHits outside 1 .. RAYLIB_AMD_MAX_NEAREST, a scene not
+ * finalized or one that holds spheres or cubes. */
+RAYLIB_API int32_t RaylibAMD_PlanNearestAll(SceneHandle scene, int32_t maxHits, int32_t wantCount, RaylibAMDQueryPlan* out);
+
 /* ---- batched triangle-overlap queries -------------------------------------------------------------
  * Which triangles of the scene does a triangle intersect -- the question a collision step asks behind RaylibAMD_SceneMoveTriangles, and, with a mesh's own
  * triangles as the queries, whether the mesh intersects itself (cloth, skinned characters, lightmap charts that fold over).  The result equals a loop over

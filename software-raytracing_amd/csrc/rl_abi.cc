@@ -1010,6 +1010,78 @@ int32_t RaylibAMD_PlanNearest(SceneHandle sh, int32_t kind, RaylibAMDQueryPlan* 
 	return 1;
 }
 
+// RaylibAMD_NearestPointsAll / RaylibAMD_NearestPointsAllDevice / RaylibAMD_NearestPointsAllHost / RaylibAMD_PlanNearestAll (statements K1 to K5): the refusals every entry shares
+static bool NearestAllArgsValid(const char* who, const Scene* s, const void* points, int32_t n, int32_t maxHits, const void* outHits)
+{
+	if (!s || n < 0 || (n > 0 && (!points || !outHits))) { Log("%s: null argument", who); return false; }
+	if (maxHits < 1 || maxHits > RAYLIB_AMD_MAX_NEAREST) { Log("%s: maxHits %d is outside 1..%d", who, maxHits, RAYLIB_AMD_MAX_NEAREST); return false; }
+	if (!s->finalized) { Log("%s: scene was not finalized (Raylib_FinalizeScene)", who); return false; }
+	if (!s->spheres.empty() || !s->cubes.empty()) { Log("%s: the scene holds spheres or cubes; nearest-point queries are defined on triangles", who); return false; }
+	if (s->bvh.depth > 64) { Log("%s: BVH depth %u exceeds the traversal stack (64)", who, s->bvh.depth); return false; }
+	if ((int64_t)n * maxHits > 0x7fffffffll) { Log("%s: %d points x %d records exceed 2^31 - 1 records", who, n, maxHits); return false; }
+	return true;
+}
+static int32_t NearestPointsAllInternal(const char* who, SceneHandle sh, const RaylibAMDNearestQuery* points, int32_t n, int32_t maxHits, RaylibAMDNearestHit* outHits, uint32_t* outCount,
+                                        bool hostMem, void* stream)
+{
+	Scene* s = (Scene*)sh;
+	if (!NearestAllArgsValid(who, s, points, n, maxHits, outHits)) return 0;
+	if (!DeviceAvailable()) return 0;
+	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
+	if (!DeviceNearestPointsAll(*s, points, n, maxHits, outHits, outCount, hostMem, stream, stats)) return 0;
+	if (!stream) ReportOwnStats(stats);
+	return 1;
+}
+int32_t RaylibAMD_NearestPointsAll(SceneHandle sh, const RaylibAMDNearestQuery* points, int32_t n, int32_t maxHits, RaylibAMDNearestHit* outHits, uint32_t* outCount)
+{
+	return NearestPointsAllInternal("RaylibAMD_NearestPointsAll", sh, points, n, maxHits, outHits, outCount, true, nullptr);
+}
+int32_t RaylibAMD_NearestPointsAllDevice(SceneHandle sh, const RaylibAMDNearestQuery* points, int32_t n, int32_t maxHits, RaylibAMDNearestHit* outHits, uint32_t* outCount, void* stream)
+{
+	return NearestPointsAllInternal("RaylibAMD_NearestPointsAllDevice", sh, points, n, maxHits, outHits, outCount, false, stream);
+}
+// the oracle: statements K1 to K3 on N1 to N4 (rl_nearest.h, the kernel's own source) over every triangle in export order; the set sorted by (D, k)
+int32_t RaylibAMD_NearestPointsAllHost(SceneHandle sh, const RaylibAMDNearestQuery* points, int32_t n, int32_t maxHits, RaylibAMDNearestHit* outHits, uint32_t* outCount)
+{
+	Scene* s = (Scene*)sh;
+	if (!NearestAllArgsValid("RaylibAMD_NearestPointsAllHost", s, points, n, maxHits, outHits)) return 0;
+	if (!DeviceSyncMovedScene(*s)) return 0;
+	const size_t numTris = s->triangles.size();
+	std::vector<RaylibAMDNearestHit> set;
+	for (int32_t i = 0; i < n; ++i) {
+		const RaylibAMDNearestQuery& Q = points[i];
+		set.clear();
+		if (NearestTakesPart(Q.pos[0], Q.pos[1], Q.pos[2], Q.maxDist)) {
+			const float R2 = Q.maxDist * Q.maxDist;
+			for (size_t k = 0; k < numTris; ++k) {
+				const HostTriangle& t = s->triangles[k];
+				float b1, b2;
+				const float E = NearestTriangleE(Q.pos, &t.v0.x, &t.v1.x, &t.v2.x, b1, b2);
+				const float D = NearestTriangleD(E, NearestOwnBoxDist2(Q.pos, &t.v0.x, &t.v1.x, &t.v2.x));
+				if (D <= R2) set.push_back({ D, (int32_t)k, b1, b2 });
+			}
+		}
+		const size_t listed = std::min(set.size(), (size_t)maxHits);
+		std::partial_sort(set.begin(), set.begin() + (ptrdiff_t)listed, set.end(),
+		                  [](const RaylibAMDNearestHit& a, const RaylibAMDNearestHit& b) { return a.dist2 < b.dist2 || (a.dist2 == b.dist2 && a.prim < b.prim); });
+		RaylibAMDNearestHit* row = outHits + (size_t)i * (size_t)maxHits;
+		for (size_t k = 0; k < (size_t)maxHits; ++k) row[k] = k < listed ? set[k] : RaylibAMDNearestHit{ 0.0f, -1, 0.0f, 0.0f };
+		if (outCount) outCount[i] = (uint32_t)set.size();
+	}
+	return 1;
+}
+int32_t RaylibAMD_PlanNearestAll(SceneHandle sh, int32_t maxHits, int32_t wantCount, RaylibAMDQueryPlan* out)
+{
+	Scene* s = (Scene*)sh;
+	if (!s || !s->finalized || !out || maxHits < 1 || maxHits > RAYLIB_AMD_MAX_NEAREST || !s->spheres.empty() || !s->cubes.empty()) return 0;
+	memset(out, 0, sizeof(*out));
+	const QueryPlan p = PlanNearestAll(*s, ReadRenderKnobs());
+	if (!p.ok) return -1;
+	(void)wantCount;   // (the count changes the kernel's instance and what it may prune, not the tree)
+	out->tree = p.tree; out->treeWidth = p.treeWidth; out->nodeBytes = p.nodeBytes; out->stack = p.stack; out->prims = 0; out->early = 0;
+	return 1;
+}
+
 // RaylibAMD_OverlapTriangles / RaylibAMD_OverlapTrianglesDevice / RaylibAMD_OverlapTrianglesHost (statements O1 to O6): the refusals every entry shares
 static bool OverlapArgsValid(const char* who, const Scene* s, int32_t kind, uint32_t flags, const void* q, int32_t n, int32_t maxHits, const void* out, const uint32_t* outCount)
 {

@@ -275,6 +275,9 @@ bool DeviceTraceRays(Scene& scene, int32_t kind, const void* rays, int32_t n, fl
 bool DeviceTraceRaysAll(Scene& scene, const void* rays, int32_t n, int32_t maxHits, void* outHits, uint32_t* outCount, bool hostMem, void* stream, RaylibAMDStats& stats);
 // RaylibAMD_NearestPoints (hostMem) and RaylibAMD_NearestPointsDevice, as DeviceTraceRays; the scene holds triangles only: the ABI checked.
 bool DeviceNearestPoints(Scene& scene, int32_t kind, const void* points, int32_t n, void* out, bool hostMem, void* stream, RaylibAMDStats& stats);
+// RaylibAMD_NearestPointsAll (hostMem) and RaylibAMD_NearestPointsAllDevice, as DeviceTraceRaysAll: outHits holds n rows of maxHits records, outCount (may be
+// null) n words.  The scene holds triangles only, 1 <= maxHits <= RAYLIB_AMD_MAX_NEAREST and n * maxHits fits an int32_t: the ABI checked.
+bool DeviceNearestPointsAll(Scene& scene, const void* points, int32_t n, int32_t maxHits, void* outHits, uint32_t* outCount, bool hostMem, void* stream, RaylibAMDStats& stats);
 // RaylibAMD_OverlapTriangles (hostMem) and RaylibAMD_OverlapTrianglesDevice, as DeviceNearestPoints; kind, flags and (for LIST) maxHits are valid, outCount is
 // null for ANY, n * maxHits fits 2^31 - 1: the ABI checked.
 // contacts: RaylibAMD_OverlapContacts (Device) -- kind is LIST and outContact takes n * maxHits 32-byte records (non-null when n > 0).

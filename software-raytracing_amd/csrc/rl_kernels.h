@@ -12,7 +12,8 @@
 //   rl_multihit.hip      k_query_all (RaylibAMD_TraceRaysAll): the binary and the 8-wide walk again with a sorted list behind the triangle test, written on the
 //                        shared steps; apart so that k_query and every other unit stay the code they are
 //   rl_nearest.hip       k_nearest (RaylibAMD_NearestPoints): a walk of its own (point-to-box distances, no ray), which shares with the others the records and the
-//                        child sort alone; apart so that every other unit stays the code it is
+//                        child sort alone; apart so that every other unit stays the code it is.  k_nearest_all (RaylibAMD_NearestPointsAll): that walk again with
+//                        a sorted list behind the triangle test
 //   rl_overlap.hip       k_overlap (RaylibAMD_OverlapTriangles): a walk of its own again (box against box, no ray, no distance) with a per-lane index list; apart for
 //                        the same reason
 //   rl_radiance.hip      k_radiance (RaylibAMD_TraceRadiance): the same reason, towards the render and the query kernels alike
@@ -201,6 +202,18 @@ template <int TREE, int KIND, int STACK> __global__ void __launch_bounds__(RL_BL
 #define RL_NEAREST_INSTANCES(X) RL_NEAREST_INSTANCES_K(X, 0) RL_NEAREST_INSTANCES_K(X, 1)
 #define RL_K_NEAREST(a, b, c) template __global__ void k_nearest<a, b, c>(RL_NEAREST_ARGS);
 RL_NEAREST_INSTANCES(extern RL_K_NEAREST)
+// The K nearest triangles and the count in range (RaylibAMD_NearestPointsAll; rl_k_nearest_all.inl, the same arithmetic)
+#define RL_MAX_NEAREST 16   /* RAYLIB_AMD_MAX_NEAREST */
+// TREE, STACK, points, slotIndex, counters: as k_nearest's.  COUNT: outCount[i] = every triangle within maxDist of point i (the walk then never prunes with its
+// K-th key).  maxHits: 1 .. RL_MAX_NEAREST, and the launch carries 2 * maxHits * RL_BLOCK words of dynamic LDS (the lanes' lists).  outHits: n rows of maxHits
+// DNearestHit.  outCount: n words (COUNT) or null.
+#define RL_NEAREST_ALL_ARGS const DSceneView, const float4* __restrict__, uint32_t, uint32_t, float4* __restrict__, uint32_t* __restrict__, const int32_t* __restrict__, unsigned int* __restrict__, unsigned long long* __restrict__
+template <int TREE, int STACK, bool COUNT> __global__ void __launch_bounds__(RL_BLOCK) k_nearest_all(RL_NEAREST_ALL_ARGS);
+// The instances rl_rt_rays.hip NearestAllKernelOf selects from: (TREE, STACK, COUNT)
+#define RL_NEAREST_ALL_INSTANCES_C(X, C) X(2, 32, C) X(2, 64, C) X(4, 32, C) X(4, 64, C)
+#define RL_NEAREST_ALL_INSTANCES(X) RL_NEAREST_ALL_INSTANCES_C(X, false) RL_NEAREST_ALL_INSTANCES_C(X, true)
+#define RL_K_NEAREST_ALL(a, b, c) template __global__ void k_nearest_all<a, b, c>(RL_NEAREST_ALL_ARGS);
+RL_NEAREST_ALL_INSTANCES(extern RL_K_NEAREST_ALL)
 
 // ---------------------------------------------------------------------------
 // The triangle-overlap queries (RaylibAMD_OverlapTriangles; rl_k_overlap.inl, arithmetic of rl_overlap.h)

@@ -1,5 +1,5 @@
-// The nearest-point queries of RaylibAMD_NearestPoints (k_nearest, rl_k_nearest.inl) as a translation unit of their own: a new walk beside the ray walks, and
-// every other unit stays the code it is (tools/isa_equivalence.py).
+// The nearest-point queries of RaylibAMD_NearestPoints (k_nearest, rl_k_nearest.inl) and of RaylibAMD_NearestPointsAll (k_nearest_all, rl_k_nearest_all.inl) as
+// a translation unit of their own: walks of their own beside the ray walks, and every other unit stays the code it is (tools/isa_equivalence.py).
 
 // ---- settings ----
 // None: single float operations without FMA (the Makefile's -ffp-contract=off) and the compiler's correctly rounded divisions, as the host oracle that
@@ -13,8 +13,10 @@ namespace rl {
 
 // ---- kernel bodies ----
 #include "rl_k_nearest.inl"
+#include "rl_k_nearest_all.inl"
 
 // ---- instances ----
 RL_NEAREST_INSTANCES(RL_K_NEAREST)
+RL_NEAREST_ALL_INSTANCES(RL_K_NEAREST_ALL)
 
 } // namespace rl

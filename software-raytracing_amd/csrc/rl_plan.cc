@@ -194,6 +194,11 @@ QueryPlan PlanNearest(const Scene& sc, int32_t kind, const RenderKnobs& k)
 	return p;
 }
 
+QueryPlan PlanNearestAll(const Scene& sc, const RenderKnobs& k)
+{
+	return PlanNearest(sc, RAYLIB_AMD_NEAREST_CLOSEST, k);   // k_nearest_all is CLOSEST's walk: its tree, its stack, no early exit
+}
+
 QueryPlan PlanOverlap(const Scene& sc, int32_t kind, const RenderKnobs& k)
 {
 	// Unless RAYLIB_QUERY_TREE says otherwise: the grid-4 tree while its walk is the 32-deep instance, else the binary tree.  Measured (DESIGN.md section 2,

@@ -90,6 +90,9 @@ QueryPlan PlanRadiance(const Scene& sc, const RenderKnobs& knobs);
 // their stack bounds are its bounds.  There is no 8-wide nearest walk: RAYLIB_QUERY_TREE=8 falls through to 4, =2 walks the binary tree.  `early`: the kind is
 // WITHIN.  The scene holds triangles only (the entries refuse spheres and cubes before they plan).
 QueryPlan PlanNearest(const Scene& sc, int32_t kind, const RenderKnobs& knobs);
+// Which tree and k_nearest_all instance a batch of K-nearest queries walks (RaylibAMD_NearestPointsAll, rl_k_nearest_all.inl): what PlanNearest gives CLOSEST --
+// the walk and its pushes are the same, so is the stack.  `early` is false.  maxHits and the count choose the launch's list bytes and the COUNT instance, not the plan.
+QueryPlan PlanNearestAll(const Scene& sc, const RenderKnobs& knobs);
 // Which tree and k_overlap instance a batch of triangle-overlap queries walks (RaylibAMD_OverlapTriangles, rl_k_overlap.inl): PlanNearest's trees under the same
 // switch, with a default of its own: the grid-4 tree when the scene carries one and its worst-case stack fits the 32-deep instance, else the binary tree,
 // which the self-intersection pass on the 298 k-triangle room walks faster than the 64-deep grid instance (measured: DESIGN.md section 2).

@@ -4,7 +4,7 @@
 //   rl_rt_scene.hip   a flattened scene (rl_scene.cc FlattenScene) to every device, its sky and wide trees; images: read-back, RGB dump, post-processing
 //   rl_rt_frame.hip   kernel selection and the one enqueue path of every render (EnqueueFrame), a rank's one-view render, a batch of views
 //   rl_rt_render.hip  whole frames over N ranks (gather, scatter, two frames in flight), DeviceRender, progressive sessions
-//   rl_rt_rays.hip    caller rays and points: DeviceTraceRays, DeviceTraceRaysAll, DeviceNearestPoints, DeviceOverlapTriangles (and its contacts), DeviceTraceRadiance, DeviceGather (plain and adaptive: one driver, GatherLocked)
+//   rl_rt_rays.hip    caller rays and points: DeviceTraceRays, DeviceTraceRaysAll, DeviceNearestPoints, DeviceNearestPointsAll, DeviceOverlapTriangles (and its contacts), DeviceTraceRadiance, DeviceGather (plain and adaptive: one driver, GatherLocked)
 //   rl_rt_lightmap.hip  lightmaps: DeviceLightmapPoints, DeviceBakeLightmap (the raster stages, then DeviceGather's body or the caller's atlas, the filter, the atlas stages)
 //   rl_rt_move.hip    RaylibAMD_SceneMoveTriangles: the moved records and the refit of every tree on the device, the host copies' read-back, RaylibAMD_SceneCheckTrees
 //   rl_rt_hooks.hip   test hooks

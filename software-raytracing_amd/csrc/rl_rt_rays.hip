@@ -1,4 +1,4 @@
-// Host runtime: rays of the caller's -- the ray queries (RaylibAMD_TraceRays, k_query), the ordered multi-hit queries (RaylibAMD_TraceRaysAll, k_query_all) the nearest-point queries (RaylibAMD_NearestPoints, k_nearest) and the triangle-overlap queries (RaylibAMD_OverlapTriangles, k_overlap) that share their call (BeginQueryCall), path-traced radiance (RaylibAMD_TraceRadiance, k_radiance) and the
+// Host runtime: rays of the caller's -- the ray queries (RaylibAMD_TraceRays, k_query), the ordered multi-hit queries (RaylibAMD_TraceRaysAll, k_query_all) the nearest-point queries (RaylibAMD_NearestPoints, k_nearest; RaylibAMD_NearestPointsAll, k_nearest_all) and the triangle-overlap queries (RaylibAMD_OverlapTriangles, k_overlap) that share their call (BeginQueryCall), path-traced radiance (RaylibAMD_TraceRadiance, k_radiance) and the
 // irradiance and SH probes gathered from it at caller points (RaylibAMD_Gather, k_gather + k_gather_resolve) on rank 0's device, from host memory or from device pointers, on the library's stream (synchronous, with stats) or enqueued on a stream of the caller's (rl_rt.h).
 // The two entries share the refusals of a device call's pointers, the synchronous call's counter block and event pair, the stats' header, the staging of a
 // host call through qRays / qOut, the grid that fills the device once, and the synchronous tail; each keeps its plan and kernel, its parameter block and the
@@ -327,6 +327,55 @@ bool DeviceNearestPoints(Scene& sc, int32_t kind, const void* points, int32_t n,
 	if (!ReleaseRingCounter(R, slot, st)) return false;
 	if (!sync) return true;
 	return FinishSync(R, st, { { hostMem ? out : nullptr, dOut, outBytes } }, t0, stats);
+}
+
+// A K-nearest call (RaylibAMD_NearestPointsAll) is a nearest-point call with the multi-hit call's outputs: rows of maxHits records and, when asked for, a count
+// per point (staged through qPrim); the launch carries the lanes' lists as dynamic LDS (2 * maxHits * RL_BLOCK words) beside the instance's stack and packed
+// distances (48 KB or 96 KB), which its grid's occupancy accounts for.
+typedef void (*NearestAllKernel)(const DSceneView, const float4*, uint32_t, uint32_t, float4*, uint32_t*, const int32_t*, unsigned int*, unsigned long long*);
+template <bool COUNT>
+static NearestAllKernel NearestAllKernelOf(const QueryPlan& p)
+{
+	if (p.tree == TREE_GRID4) return p.stack <= 32 ? (NearestAllKernel)k_nearest_all<4, 32, COUNT> : (NearestAllKernel)k_nearest_all<4, 64, COUNT>;
+	return p.stack <= 32 ? (NearestAllKernel)k_nearest_all<2, 32, COUNT> : (NearestAllKernel)k_nearest_all<2, 64, COUNT>;
+}
+static_assert(RAYLIB_AMD_MAX_NEAREST == RL_MAX_NEAREST, "K-nearest capacity");
+bool DeviceNearestPointsAll(Scene& sc, const void* points, int32_t n, int32_t maxHits, void* outHits, uint32_t* outCount, bool hostMem, void* stream, RaylibAMDStats& stats)
+{
+	const auto t0 = std::chrono::steady_clock::now();
+	std::lock_guard<std::mutex> lk(Rt().lock);
+	if (!EnsureRuntime()) return false;
+	RankCtx& R = Rank0();
+	HIP_OK(hipSetDevice(R.device));
+	const QueryPlan plan = PlanNearestAll(sc, ReadRenderKnobs());
+	if (!plan.ok) { Log("RaylibAMD_NearestPointsAll: BVH depth %u exceeds the traversal stack (64)", sc.bvh.depth); return false; }
+	const size_t hitBytes = (size_t)n * (size_t)maxHits * sizeof(DNearestHit), countBytes = outCount ? (size_t)n * sizeof(uint32_t) : 0;
+	if (!hostMem && n > 0 && !DevicePointersOk("RaylibAMD_NearestPointsAllDevice", "points", R.device, points, outHits, 15u, (const int32_t*)outCount, outCount != nullptr)) return false;
+	QueryCall U;
+	if (!BeginQueryCall(sc, R, plan, true, stream, U, stats)) return false;
+	if (n == 0) return true;
+	const hipStream_t st = U.st;
+	const float4* dPoints = (const float4*)points; float4* dHits = (float4*)outHits; uint32_t* dCount = outCount;
+	if (hostMem) {
+		if (outCount && !R.qPrim.Grow((size_t)n * sizeof(int32_t))) return false;
+		if (!StageRays(R, points, n, hitBytes, st, sizeof(RaylibAMDNearestQuery))) return false;
+		dPoints = R.qRays.ptr; dHits = (float4*)R.qOut.ptr; if (outCount) dCount = (uint32_t*)R.qPrim.ptr;
+	}
+	const NearestAllKernel kernel = outCount ? NearestAllKernelOf<true>(plan) : NearestAllKernelOf<false>(plan);
+	const size_t listBytes = 2u * (size_t)maxHits * RL_BLOCK * sizeof(uint32_t);
+	int blocksPerCU = 0;
+	HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, kernel, RL_BLOCK, listBytes));
+	if (blocksPerCU < 1) { Log("RaylibAMD_NearestPointsAll: no workgroup of the kernel fits a compute unit with %zu bytes of list", listBytes); return false; }
+	const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)R.numCUs * (uint64_t)blocksPerCU, ((uint64_t)n + RL_BLOCK - 1) / RL_BLOCK));
+	const DSceneView view = U.Cp->view;
+	HIP_OK(hipMemsetAsync(U.counter, 0, sizeof(unsigned int), st));
+	if (U.sync && !BeginSync(R, st)) return false;
+	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RL_BLOCK), (uint32_t)listBytes, st, view, dPoints, (uint32_t)n, (uint32_t)maxHits, dHits, dCount, (const int32_t*)U.Cp->slotIndex.ptr, U.counter,
+	                   U.sync ? R.qStats.ptr : nullptr);
+	HIP_OK(hipGetLastError());
+	if (!ReleaseRingCounter(R, U.slot, st)) return false;
+	if (!U.sync) return true;
+	return FinishSync(R, st, { { hostMem ? outHits : nullptr, dHits, hitBytes }, { hostMem ? (void*)outCount : nullptr, dCount, countBytes } }, t0, stats);
 }
 
 // A triangle-overlap call is a nearest-point call with a 48-byte record, rows of maxHits indices and, when asked for, a count per query (staged through qPrim, as

@@ -258,6 +258,50 @@ def nearest_points(lib, scene, points, kind, host=False):
     return out
 
 
+MAX_NEAREST = 16                                    # RAYLIB_AMD_MAX_NEAREST
+
+
+def plan_nearest_all(lib, scene, max_hits, count=False):
+    """RaylibAMD_PlanNearestAll: (return code, plan dict)."""
+    p = QueryPlan()
+    r = lib.RaylibAMD_PlanNearestAll(scene, int(max_hits), int(bool(count)), C.byref(p))
+    return r, p.as_dict()
+
+
+def nearest_points_all(lib, scene, points, max_hits, count=False, host=False):
+    """The K nearest triangles and the count in range (RaylibAMD_NearestPointsAll / RaylibAMD_NearestPointsAllDevice / RaylibAMD_NearestPointsAllHost,
+    statements K1 to K5).
+
+    points: as nearest_points'.  Returns the (n, max_hits) rows, and with count=True the pair (rows, counts).  A NumPy array goes through the host entry
+    (host=True: through the oracle, which needs no device) and returns NumPy arrays: NEAREST_DTYPE records, uint32 counts.  A float32 torch tensor on the
+    device goes through the device entry on torch.cuda.current_stream(), as nearest_points; it returns tensors: (n, max_hits, 4) int32 words and (n,) int32
+    counts.  Raises RuntimeError when the library refuses the call."""
+    max_hits = int(max_hits)
+    if isinstance(points, np.ndarray):
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+        n = len(p)
+        rows = np.zeros((n, max(max_hits, 0)), NEAREST_DTYPE)
+        counts = np.zeros(n, np.uint32) if count else None
+        name = "RaylibAMD_NearestPointsAllHost" if host else "RaylibAMD_NearestPointsAll"
+        if getattr(lib, name)(scene, p.ctypes.data, n, max_hits, rows.ctypes.data, counts.ctypes.data if count else None) != 1:
+            raise RuntimeError(name + " refused the query")
+        return (rows, counts) if count else rows
+    import torch
+    if host or not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float32):
+        raise TypeError("points: a float32 NumPy array, or a float32 torch tensor on the device (host=False)")
+    p = points.reshape(-1, 4).contiguous()
+    n = p.shape[0]
+    rows = torch.empty((n, max(max_hits, 0), 4), dtype=torch.int32, device=p.device)
+    counts = torch.empty(n, dtype=torch.int32, device=p.device) if count else None
+    stream = torch.cuda.current_stream(p.device)
+    if stream.cuda_stream == 0:
+        stream.synchronize()   # (the library's stream is not ordered against torch's default stream: trace_rays)
+    if lib.RaylibAMD_NearestPointsAllDevice(scene, C.c_void_p(p.data_ptr()), n, max_hits, C.c_void_p(rows.data_ptr()), C.c_void_p(counts.data_ptr()) if count else None,
+                                            C.c_void_p(stream.cuda_stream)) != 1:
+        raise RuntimeError("RaylibAMD_NearestPointsAllDevice refused the query")
+    return (rows, counts) if count else rows
+
+
 OVERLAP_ANY, OVERLAP_LIST = 0, 1                    # RAYLIB_AMD_OVERLAP_*
 OVERLAP_SKIP_SHARED = 1                             # RAYLIB_AMD_OVERLAP_SKIP_SHARED
 MAX_OVERLAPS = 16                                   # RAYLIB_AMD_MAX_OVERLAPS
@@ -894,6 +938,10 @@ _EXPORTS = {
     "RaylibAMD_NearestPointsDevice": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "RaylibAMD_NearestPointsHost": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "RaylibAMD_PlanNearest": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(QueryPlan)]),
+    "RaylibAMD_NearestPointsAll": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_NearestPointsAllDevice": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_NearestPointsAllHost": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_PlanNearestAll": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(QueryPlan)]),
     "RaylibAMD_OverlapTriangles": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "RaylibAMD_OverlapTrianglesDevice": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "RaylibAMD_OverlapTrianglesHost": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
