@@ -278,8 +278,8 @@ RAYLIB_API int32_t RaylibAMD_PlanNearest(SceneHandle scene, int32_t kind, Raylib
  *        scene that is not finalized; a scene that holds spheres or cubes; a BVH deeper than 64 levels; no device (the plain and the device entry; the host
  *        entry needs none); on the device entry a pointer off rank 0's device, points or outHits not 16-byte aligned, outCount not 4-byte aligned.
  *        n == 0 returns 1.
- * Still out: spheres and cubes, more than RAYLIB_AMD_MAX_NEAREST records per point (the count is complete all the same), an 8-wide walk, signed distance,
- * query primitives other than points.
+ * Still out: spheres and cubes, more than RAYLIB_AMD_MAX_NEAREST records per point (the count is complete all the same), an 8-wide walk, query primitives
+ * other than points.  (Signed distance is RaylibAMD_BakeDistanceField's, below.)
  * Checked against a loop over every triangle: tests/test_nearest_all_host.py, tests/test_gpu_nearest_all.py. */
 #define RAYLIB_AMD_MAX_NEAREST 16
 /* n points from host memory, results to host memory; synchronous, on the device.  outHits: n * maxHits RaylibAMDNearestHit, row i = point i; outCount: n
@@ -296,6 +296,65 @@ RAYLIB_API int32_t RaylibAMD_NearestPointsAllHost(SceneHandle scene, const Rayli
  * No device needed.  Returns 1, -1 when the BVH is deeper than 64 levels, 0 for a null argument, maxHits outside 1 .. RAYLIB_AMD_MAX_NEAREST, a scene not
  * finalized or one that holds spheres or cubes. */
 RAYLIB_API int32_t RaylibAMD_PlanNearestAll(SceneHandle scene, int32_t maxHits, int32_t wantCount, RaylibAMDQueryPlan* out);
+
+/* ---- signed distance fields baked on the device ------------------------------------------------------
+ * A regular grid of distances to the scene's triangles, with the sign of inside / outside: collision against a moved mesh, sphere tracing, offsetting, torch
+ * pipelines that consume an SDF grid.  It is RaylibAMD_NearestPoints CLOSEST at every voxel centre and the parity of RaylibAMD_TraceRaysAll's crossing count
+ * along one ray per ROW of voxels, put together on the device: no point, ray or result record is materialised (a 256^3 volume would take 268 MB of points,
+ * as many bytes of results and 537 MB of rays), and a voxel costs 4 bytes of output (8 with outPrim).  Every output bit is fixed by the statements below; the
+ * result equals the host oracle, a loop over every triangle, byte for byte (csrc/rl_k_sdf.inl holds the kernels).  Everything is float, without FMA.
+ *   V1. Centres.  Per axis a and index i: t_a(i) = ((float)i + 0.5f) * spacing[a] and c_a(i) = origin[a] + t_a(i).  (float)i rounds to nearest; t_a and c_a do
+ *        not decrease in i, because every operation rounds monotonically.
+ *   V2. Distance.  The voxel's point is (c_x(i), c_y(j), c_z(k)), its radius maxDist (-0.0 is read as +0.0).  {D, prim} is what RAYLIB_AMD_NEAREST_CLOSEST
+ *        returns for that point under N1 to N4, tie rule included.  On a hit m = sqrt(D), the correctly rounded IEEE square root (sqrt(+inf) = +inf).  On a
+ *        miss -- outside the band, a point that does not take part, an empty scene -- m = maxDist.  outPrim, when given, is prim, or -1 on a miss.
+ *   V3. Row rays.  For sign axis a there is one ray per pair of indices on the other two axes b < c: origin[a] on axis a and the centres c_b, c_c on the others;
+ *        the direction is the unit vector of axis a; tMin = 0, tMax = FLT_MAX.  Its accepted set is M1's, exactly -- the plane t, the barycentric test, the
+ *        own-box rule and the cut-out test -- so a cut-out card is open where the renderer sees through it.
+ *   V4. Inside bit.  Voxel i of the row is inside along axis a exactly when the number of accepted crossings with t > t_a(i) is odd.  The ray's point at
+ *        parameter t_a(i) is c_a(i) by the same expression, so a crossing exactly at a centre is not "ahead" of it.  t_a does not decrease in i, so a crossing
+ *        is ahead of a prefix of the row, i < #{i : t_a(i) < t}, and toggles that prefix -- which is how the device computes the bits.
+ *   V5. Value.  UNSIGNED: outDist = m.  SIGN_X, SIGN_Y, SIGN_Z: outDist = inside ? -m : m along that axis.  SIGN_MAJORITY: inside when at least two of the
+ *        three axes say so.  Where m == 0 and the voxel is inside the value is -0.0f; a miss inside is -maxDist (-inf for an unbounded band).
+ *   V6. Independence.  The result does not depend on the trees walked, the order of the walks, how voxels and rows are dealt to lanes and waves, or whether the
+ *        trees were built fresh or refitted by RaylibAMD_SceneMoveTriangles (as N5 and M4).  After a move the bake sees the moved triangles; the host oracle
+ *        refreshes the host's stale copies first.
+ *   V7. Refusals (0, nothing written): a null scene, params or outDist; a dim < 1 or a voxel count above 2^31 - 1; a spacing that is not finite or <= 0; an
+ *        origin that is not finite; a last centre c_a(dims[a] - 1) that is not finite; maxDist NaN or negative; an unknown sign; a scene that is not finalized;
+ *        a scene that holds spheres or cubes; a BVH deeper than 64 levels; no device (the plain and the device entry; the host entry needs none); on the
+ *        device entry outDist or outPrim off rank 0's device or not 4-byte aligned.
+ * The sign is a property of these statements, not of the mesh's topology.  On a closed, consistently tessellated surface the parity is the inside.  An open
+ * mesh, or a row ray that grazes an edge two triangles share (the reference's barycentric test is not watertight: such a ray may be accepted by both, or by
+ * neither), gives whatever parity V3 and V4 give, for the whole prefix of that row.  SIGN_MAJORITY exists to outvote one such axis; it costs three sets of rows.
+ * Still out: spheres and cubes; generalized winding numbers or pseudo-normal signs for open meshes; sparse or narrow-band storage (the band bounds the walk,
+ * not the memory); gradients; seeding a voxel's bound from its neighbour's distance (no slack-free form of it is known).
+ * Checked against a loop over every triangle: tests/test_sdf_host.py, tests/test_gpu_sdf.py. */
+#define RAYLIB_AMD_SDF_UNSIGNED      0
+#define RAYLIB_AMD_SDF_SIGN_X        1
+#define RAYLIB_AMD_SDF_SIGN_Y        2
+#define RAYLIB_AMD_SDF_SIGN_Z        3
+#define RAYLIB_AMD_SDF_SIGN_MAJORITY 4
+typedef struct RaylibAMDDistanceFieldParams {
+    float    origin[3];    /* the lower corner of voxel (0, 0, 0) */
+    float    spacing[3];   /* voxel size per axis, finite and > 0 */
+    int32_t  dims[3];      /* nx, ny, nz, each >= 1; nx * ny * nz <= 2^31 - 1 */
+    float    maxDist;      /* the band, as N4's maxDist: >= 0, +inf allowed, -0.0 is 0 */
+    int32_t  sign;         /* RAYLIB_AMD_SDF_* */
+} RaylibAMDDistanceFieldParams;
+/* Host memory out: outDist, and outPrim when non-null, hold nx * ny * nz words, voxel (i, j, k) at (k * ny + j) * nx + i.  Synchronous, on the device.  The
+ * library keeps its staging buffers and the bit volumes of the sign axes (ceil((n_a + 1) / 32) words per row of axis a) and grows them.
+ * RaylibAMD_GetLastStats then reports rays (= voxels + row rays), nodesVisited, trisTested (both walks together), kernelMs, wallMs and the distance walk's tree. */
+RAYLIB_API int32_t RaylibAMD_BakeDistanceField(SceneHandle scene, const RaylibAMDDistanceFieldParams* params, float* outDist, int32_t* outPrim);
+/* The same on device pointers (rank 0's device), with the stream, stats, move-ordering and multi-rank rules of RaylibAMD_NearestPointsDevice: stream == NULL
+ * is the library's stream, synchronous, with stats; a non-null hipStream_t gets the kernels enqueued behind the synchronous uploads and the stats are left
+ * alone.  The bit volumes are the library's: a bake enqueued on one stream waits for the bake before it, whatever stream that one ran on. */
+RAYLIB_API int32_t RaylibAMD_BakeDistanceFieldDevice(SceneHandle scene, const RaylibAMDDistanceFieldParams* params, float* outDist, int32_t* outPrim, void* stream);
+/* The oracle: statements V1 to V5 over every triangle, no tree, no device. */
+RAYLIB_API int32_t RaylibAMD_BakeDistanceFieldHost(SceneHandle scene, const RaylibAMDDistanceFieldParams* params, float* outDist, int32_t* outPrim);
+/* Which trees and kernel instances a bake would walk under the current environment: outNearest is RaylibAMD_PlanNearest's CLOSEST plan (the distance
+ * kernel: the grid-4 or the binary tree), outRows RaylibAMD_PlanRayQueryAll's (the row kernel: the 8-wide or the binary tree; filled for UNSIGNED too, which
+ * traces no row).  Either may be null.  No device needed.  Returns 1, -1 when the BVH is deeper than 64 levels, 0 for what V7 refuses before it. */
+RAYLIB_API int32_t RaylibAMD_PlanDistanceField(SceneHandle scene, const RaylibAMDDistanceFieldParams* params, RaylibAMDQueryPlan* outNearest, RaylibAMDQueryPlan* outRows);
 
 /* ---- batched triangle-overlap queries -------------------------------------------------------------
  * Which triangles of the scene does a triangle intersect -- the question a collision step asks behind RaylibAMD_SceneMoveTriangles, and, with a mesh's own

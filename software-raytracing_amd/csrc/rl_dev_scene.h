@@ -142,8 +142,12 @@ __device__ __forceinline__ Shade ShadeFrom(const float4* p)
 __device__ __forceinline__ Shade LoadShade(const DSceneView& S, int i) { return ShadeFrom((const float4*)(S.shade + i)); }
 
 // MicrofacetMaterial::AlphaTest for a candidate (reference render/material.cc:397-404 via geom/triangle.cc:48-54).
-// Returns bit 0 = passes, bit 1 = a texel was fetched.  Out of line: only leaves flagged as textured reach it.
-__device__ __noinline__ int AlphaTestCandidateNI(const DTriShade* shade, const int32_t* alphaTex, const DMaterial* materials, const DTexture* textures,
+// Returns bit 0 = passes, bit 1 = a texel was fetched.  Out of line: only leaves flagged as textured reach it.  (RL_ALPHA_TEST_ATTR: a unit whose kernels are to
+// keep no call frame -- rl_sdf.hip -- takes it inline; the statements are the same.)
+#ifndef RL_ALPHA_TEST_ATTR
+#define RL_ALPHA_TEST_ATTR __noinline__
+#endif
+__device__ RL_ALPHA_TEST_ATTR int AlphaTestCandidateNI(const DTriShade* shade, const int32_t* alphaTex, const DMaterial* materials, const DTexture* textures,
                                                  const float* texels, int tri, float a, float b)
 {
 	const float4* p = (const float4*)(shade + tri);

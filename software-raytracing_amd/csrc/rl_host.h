@@ -278,6 +278,9 @@ bool DeviceNearestPoints(Scene& scene, int32_t kind, const void* points, int32_t
 // RaylibAMD_NearestPointsAll (hostMem) and RaylibAMD_NearestPointsAllDevice, as DeviceTraceRaysAll: outHits holds n rows of maxHits records, outCount (may be
 // null) n words.  The scene holds triangles only, 1 <= maxHits <= RAYLIB_AMD_MAX_NEAREST and n * maxHits fits an int32_t: the ABI checked.
 bool DeviceNearestPointsAll(Scene& scene, const void* points, int32_t n, int32_t maxHits, void* outHits, uint32_t* outCount, bool hostMem, void* stream, RaylibAMDStats& stats);
+// RaylibAMD_BakeDistanceField (hostMem) and RaylibAMD_BakeDistanceFieldDevice, as DeviceNearestPoints: outDist and outPrim (may be null) hold a word per voxel.
+// grid is valid (statement V7) with maxDist >= +0, the scene holds triangles only: the ABI checked.
+bool DeviceBakeDistanceField(Scene& scene, const RaylibAMDDistanceFieldParams& grid, float* outDist, int32_t* outPrim, bool hostMem, void* stream, RaylibAMDStats& stats);
 // RaylibAMD_OverlapTriangles (hostMem) and RaylibAMD_OverlapTrianglesDevice, as DeviceNearestPoints; kind, flags and (for LIST) maxHits are valid, outCount is
 // null for ANY, n * maxHits fits 2^31 - 1: the ABI checked.
 // contacts: RaylibAMD_OverlapContacts (Device) -- kind is LIST and outContact takes n * maxHits 32-byte records (non-null when n > 0).

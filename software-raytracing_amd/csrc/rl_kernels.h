@@ -16,6 +16,8 @@
 //                        a sorted list behind the triangle test
 //   rl_overlap.hip       k_overlap (RaylibAMD_OverlapTriangles): a walk of its own again (box against box, no ray, no distance) with a per-lane index list; apart for
 //                        the same reason
+//   rl_sdf.hip           k_sdf_rows, k_sdf_parity, k_sdf_dist (RaylibAMD_BakeDistanceField): k_query_all's counting walks and k_nearest's closest walk written again on
+//                        generated rays and points, with a bit volume between them; apart for the same reason
 //   rl_radiance.hip      k_radiance (RaylibAMD_TraceRadiance): the same reason, towards the render and the query kernels alike
 //   rl_gather.hip        k_gather (RaylibAMD_Gather: rl_k_radiance.inl's twin, the generator instances of its loop) and k_gather_resolve: beside k_radiance they would be
 //                        more callers of the walks and the shading it inlines.  k_gather_resolve and k_gather_adaptive_resolve are one source, rl_k_gather_resolve.inl,
@@ -239,6 +241,31 @@ template <int TREE, int STACK> __global__ void __launch_bounds__(RL_BLOCK) k_ove
 #define RL_OVERLAP_CONTACTS_INSTANCES(X) X(2, 32) X(2, 64) X(4, 32) X(4, 64)
 #define RL_K_OVERLAP_CONTACTS(a, b) template __global__ void k_overlap_contacts<a, b>(RL_OVERLAP_CONTACTS_ARGS);
 RL_OVERLAP_CONTACTS_INSTANCES(extern RL_K_OVERLAP_CONTACTS)
+
+// ---------------------------------------------------------------------------
+// Distance-field bakes (RaylibAMD_BakeDistanceField; rl_k_sdf.inl, statements V1 to V7 of include/raylib_amd.h)
+// The grid and the bit volumes of the sign axes.  axes: bit a set when axis a's rows are traced and its inside bits read.  The rows of a launch are numbered
+// axis by axis: axis a's end at rowEnd[a] (an axis not traced ends where its predecessor does); row r of axis x is (j, k) -> k * ny + j, of y (i, k) -> k * nx + i,
+// of z (i, j) -> j * nx + i.  Row r of axis a owns words[a] = ceil((dims[a] + 1) / 32) words from word wordBase[a] + r * words[a]: toggle bits 1 .. dims[a]
+// behind k_sdf_rows, inside bits 0 .. dims[a] - 1 behind k_sdf_parity.
+struct DSdfGrid { float origin[3], spacing[3]; uint32_t dims[3]; float maxDist; uint32_t axes, rowEnd[3], words[3]; unsigned long long wordBase[3]; };
+// TREE: 2 the binary tree (S.nodes), 8 the 8-wide tree (S.nodes8).  STACK: as k_query's.  n: the launch's rows.  bits: the zeroed volumes.  rowCounter,
+// counters: as k_query's.
+#define RL_SDF_ROWS_ARGS const DSceneView, const DSdfGrid, uint32_t, uint32_t* __restrict__, unsigned int* __restrict__, unsigned long long* __restrict__
+template <int TREE, int STACK> __global__ void __launch_bounds__(RL_BLOCK) k_sdf_rows(RL_SDF_ROWS_ARGS);
+#define RL_SDF_ROWS_INSTANCES(X) X(2, 32) X(2, 64) X(8, 2 * RL_POOL8_MAXLEVELS)
+#define RL_K_SDF_ROWS(a, b) template __global__ void k_sdf_rows<a, b>(RL_SDF_ROWS_ARGS);
+RL_SDF_ROWS_INSTANCES(extern RL_K_SDF_ROWS)
+// one thread per row of the launch (n rows)
+__global__ void __launch_bounds__(RL_BLOCK) k_sdf_parity(const DSdfGrid, uint32_t, uint32_t* __restrict__);
+// TREE: 2 the binary tree, 4 the grid nodes.  STACK: the walk's stack.  SIGNED: the value's sign comes from the volumes of G.axes (bits).  outDist, outPrim
+// (may be null): a word per voxel, voxel (i, j, k) at (k * ny + j) * nx + i.  slotIndex, counters: as k_nearest's.  brickCounter: the next 4 x 4 x 4 brick.
+#define RL_SDF_DIST_ARGS const DSceneView, const DSdfGrid, float* __restrict__, int32_t* __restrict__, const uint32_t* __restrict__, const int32_t* __restrict__, unsigned int* __restrict__, unsigned long long* __restrict__
+template <int TREE, int STACK, bool SIGNED> __global__ void __launch_bounds__(RL_BLOCK) k_sdf_dist(RL_SDF_DIST_ARGS);
+#define RL_SDF_DIST_INSTANCES_S(X, S) X(2, 32, S) X(2, 64, S) X(4, 32, S) X(4, 64, S)
+#define RL_SDF_DIST_INSTANCES(X) RL_SDF_DIST_INSTANCES_S(X, false) RL_SDF_DIST_INSTANCES_S(X, true)
+#define RL_K_SDF_DIST(a, b, c) template __global__ void k_sdf_dist<a, b, c>(RL_SDF_DIST_ARGS);
+RL_SDF_DIST_INSTANCES(extern RL_K_SDF_DIST)
 
 // ---------------------------------------------------------------------------
 // Path-traced radiance along caller rays (RaylibAMD_TraceRadiance; rl_k_radiance.inl)

@@ -199,6 +199,14 @@ QueryPlan PlanNearestAll(const Scene& sc, const RenderKnobs& k)
 	return PlanNearest(sc, RAYLIB_AMD_NEAREST_CLOSEST, k);   // k_nearest_all is CLOSEST's walk: its tree, its stack, no early exit
 }
 
+DistanceFieldPlan PlanDistanceField(const Scene& sc, const RenderKnobs& k)
+{
+	DistanceFieldPlan p;
+	p.nearest = PlanNearest(sc, RAYLIB_AMD_NEAREST_CLOSEST, k);   // k_sdf_dist is CLOSEST's walk
+	p.rows = PlanQueryAll(sc, k);                                 // k_sdf_rows is k_query_all's counting walk
+	return p;
+}
+
 QueryPlan PlanOverlap(const Scene& sc, int32_t kind, const RenderKnobs& k)
 {
 	// Unless RAYLIB_QUERY_TREE says otherwise: the grid-4 tree while its walk is the 32-deep instance, else the binary tree.  Measured (DESIGN.md section 2,

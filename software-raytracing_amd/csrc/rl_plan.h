@@ -93,6 +93,10 @@ QueryPlan PlanNearest(const Scene& sc, int32_t kind, const RenderKnobs& knobs);
 // Which tree and k_nearest_all instance a batch of K-nearest queries walks (RaylibAMD_NearestPointsAll, rl_k_nearest_all.inl): what PlanNearest gives CLOSEST --
 // the walk and its pushes are the same, so is the stack.  `early` is false.  maxHits and the count choose the launch's list bytes and the COUNT instance, not the plan.
 QueryPlan PlanNearestAll(const Scene& sc, const RenderKnobs& knobs);
+// Which trees a distance-field bake walks (RaylibAMD_BakeDistanceField, rl_k_sdf.inl): the distance kernel is k_nearest's CLOSEST walk, so its plan is
+// PlanNearest's; the row kernel is k_query_all's counting walk, so its plan is PlanQueryAll's.  One RAYLIB_QUERY_TREE steers both.
+struct DistanceFieldPlan { QueryPlan nearest, rows; };
+DistanceFieldPlan PlanDistanceField(const Scene& sc, const RenderKnobs& knobs);
 // Which tree and k_overlap instance a batch of triangle-overlap queries walks (RaylibAMD_OverlapTriangles, rl_k_overlap.inl): PlanNearest's trees under the same
 // switch, with a default of its own: the grid-4 tree when the scene carries one and its worst-case stack fits the 32-deep instance, else the binary tree,
 // which the self-intersection pass on the 298 k-triangle room walks faster than the 64-deep grid instance (measured: DESIGN.md section 2).

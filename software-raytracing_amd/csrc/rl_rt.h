@@ -198,6 +198,10 @@ struct RankCtx {
 	DevBuf<void> qOut;
 	DevBuf<int32_t> qPrim;
 	DevBuf<float4> qContact;   // a host contacts call's records (RaylibAMD_OverlapContacts), staged as qPrim is
+	// a distance-field bake's bit volumes (DeviceBakeDistanceField), kept and grown, and the event behind the last bake's last kernel -- every bake waits for it
+	// on its own stream, so that two bakes on two streams never share the volumes at the same time
+	DevBuf<uint32_t> sdfBits;
+	hipEvent_t sdfEv = nullptr; bool sdfEvUsed = false;
 	DevBuf<unsigned int> qRing; hipEvent_t qRingEv[RL_QUERY_RING] = {}; bool qRingUsed[RL_QUERY_RING] = {}; uint32_t qRingNext = 0;
 	DevBuf<unsigned long long> qStats; PinBuf<unsigned long long> qStatsHost;
 	hipEvent_t qEv[2] = { nullptr, nullptr };

@@ -1,4 +1,4 @@
-// Host runtime: rays of the caller's -- the ray queries (RaylibAMD_TraceRays, k_query), the ordered multi-hit queries (RaylibAMD_TraceRaysAll, k_query_all) the nearest-point queries (RaylibAMD_NearestPoints, k_nearest; RaylibAMD_NearestPointsAll, k_nearest_all) and the triangle-overlap queries (RaylibAMD_OverlapTriangles, k_overlap) that share their call (BeginQueryCall), path-traced radiance (RaylibAMD_TraceRadiance, k_radiance) and the
+// Host runtime: rays of the caller's -- the ray queries (RaylibAMD_TraceRays, k_query), the ordered multi-hit queries (RaylibAMD_TraceRaysAll, k_query_all) the nearest-point queries (RaylibAMD_NearestPoints, k_nearest; RaylibAMD_NearestPointsAll, k_nearest_all) the triangle-overlap queries (RaylibAMD_OverlapTriangles, k_overlap) and the distance-field bakes (RaylibAMD_BakeDistanceField, k_sdf_*) that share their call (BeginQueryCall), path-traced radiance (RaylibAMD_TraceRadiance, k_radiance) and the
 // irradiance and SH probes gathered from it at caller points (RaylibAMD_Gather, k_gather + k_gather_resolve) on rank 0's device, from host memory or from device pointers, on the library's stream (synchronous, with stats) or enqueued on a stream of the caller's (rl_rt.h).
 // The two entries share the refusals of a device call's pointers, the synchronous call's counter block and event pair, the stats' header, the staging of a
 // host call through qRays / qOut, the grid that fills the device once, and the synchronous tail; each keeps its plan and kernel, its parameter block and the
@@ -376,6 +376,105 @@ bool DeviceNearestPointsAll(Scene& sc, const void* points, int32_t n, int32_t ma
 	if (!ReleaseRingCounter(R, U.slot, st)) return false;
 	if (!U.sync) return true;
 	return FinishSync(R, st, { { hostMem ? outHits : nullptr, dHits, hitBytes }, { hostMem ? (void*)outCount : nullptr, dCount, countBytes } }, t0, stats);
+}
+
+// A distance-field bake (RaylibAMD_BakeDistanceField) is a nearest-point call without points and a multi-hit call without rays: up to three launches on one
+// stream -- k_sdf_rows into the zeroed bit volumes and k_sdf_parity over them (a signed bake), then k_sdf_dist -- each walk on its own plan's tree, each with a
+// ring counter of its own.  The volumes are the rank's (sdfBits), ordered between bakes by sdfEv as the radiance scratch is by radEv.  A host call's outputs
+// go through qOut and qPrim.
+typedef void (*SdfRowsKernel)(const DSceneView, const DSdfGrid, uint32_t, uint32_t*, unsigned int*, unsigned long long*);
+static SdfRowsKernel SdfRowsKernelOf(const QueryPlan& p)
+{
+	if (p.tree == TREE_WIDE8) return (SdfRowsKernel)k_sdf_rows<8, 2 * RL_POOL8_MAXLEVELS>;
+	return p.stack <= 32 ? (SdfRowsKernel)k_sdf_rows<2, 32> : (SdfRowsKernel)k_sdf_rows<2, 64>;
+}
+typedef void (*SdfDistKernel)(const DSceneView, const DSdfGrid, float*, int32_t*, const uint32_t*, const int32_t*, unsigned int*, unsigned long long*);
+template <bool SIGNED>
+static SdfDistKernel SdfDistKernelOf(const QueryPlan& p)
+{
+	if (p.tree == TREE_GRID4) return p.stack <= 32 ? (SdfDistKernel)k_sdf_dist<4, 32, SIGNED> : (SdfDistKernel)k_sdf_dist<4, 64, SIGNED>;
+	return p.stack <= 32 ? (SdfDistKernel)k_sdf_dist<2, 32, SIGNED> : (SdfDistKernel)k_sdf_dist<2, 64, SIGNED>;
+}
+bool DeviceBakeDistanceField(Scene& sc, const RaylibAMDDistanceFieldParams& prm, float* outDist, int32_t* outPrim, bool hostMem, void* stream, RaylibAMDStats& stats)
+{
+	const auto t0 = std::chrono::steady_clock::now();
+	std::lock_guard<std::mutex> lk(Rt().lock);
+	if (!EnsureRuntime()) return false;
+	RankCtx& R = Rank0();
+	HIP_OK(hipSetDevice(R.device));
+	const DistanceFieldPlan plan = PlanDistanceField(sc, ReadRenderKnobs());
+	if (!plan.nearest.ok || !plan.rows.ok) { Log("RaylibAMD_BakeDistanceField: BVH depth %u exceeds the traversal stack (64)", sc.bvh.depth); return false; }
+	if (!hostMem) {
+		if (!OnDevice(outDist, R.device) || (outPrim && !OnDevice(outPrim, R.device))) { Log("RaylibAMD_BakeDistanceFieldDevice: a pointer is not device memory of device %d", R.device); return false; }
+		if ((((uintptr_t)outDist | (uintptr_t)outPrim) & 3u) != 0) { Log("RaylibAMD_BakeDistanceFieldDevice: the output is not 4-byte aligned"); return false; }
+	}
+	// the grid, and the rows and bit volumes of the sign axes
+	DSdfGrid G; memset(&G, 0, sizeof(G));
+	for (int a = 0; a < 3; ++a) { G.origin[a] = prm.origin[a]; G.spacing[a] = prm.spacing[a]; G.dims[a] = (uint32_t)prm.dims[a]; }
+	G.maxDist = prm.maxDist;
+	G.axes = prm.sign == RAYLIB_AMD_SDF_UNSIGNED ? 0u : prm.sign == RAYLIB_AMD_SDF_SIGN_MAJORITY ? 7u : 1u << (prm.sign - RAYLIB_AMD_SDF_SIGN_X);
+	const uint64_t voxels = (uint64_t)G.dims[0] * G.dims[1] * G.dims[2];
+	uint64_t rows = 0, words = 0;
+	for (int a = 0; a < 3; ++a) {
+		const uint64_t rowsA = ((G.axes >> a) & 1u) ? voxels / G.dims[a] : 0u;   // the product of the other two dims
+		G.words[a] = (G.dims[a] + 1u + 31u) / 32u;
+		G.wordBase[a] = words;
+		rows += rowsA; words += rowsA * G.words[a];
+		G.rowEnd[a] = (uint32_t)rows;   // (three axes of at most 2^31 - 1 voxels: at most 2^32 - 1 rows; the launches below are cut at 2^31 - 1)
+	}
+	QueryCall U;
+	if (!BeginQueryCall(sc, R, plan.nearest, true, stream, U, stats)) return false;
+	if (G.axes && !EnsureWideTree(U.Cp, sc, plan.rows.tree)) return false;
+	const hipStream_t st = U.st;
+	if (G.axes && !R.sdfBits.Grow((size_t)words * sizeof(uint32_t))) return false;
+	if (!R.sdfEv) HIP_OK(hipEventCreateWithFlags(&R.sdfEv, hipEventDisableTiming));
+	float* dDist = outDist; int32_t* dPrim = outPrim;
+	if (hostMem) {
+		if (!R.qOut.Grow((size_t)voxels * sizeof(float)) || (outPrim && !R.qPrim.Grow((size_t)voxels * sizeof(int32_t)))) return false;
+		dDist = (float*)R.qOut.ptr; if (outPrim) dPrim = R.qPrim.ptr;
+	}
+	const SdfDistKernel distKernel = G.axes ? SdfDistKernelOf<true>(plan.nearest) : SdfDistKernelOf<false>(plan.nearest);
+	const uint64_t bricks = (uint64_t)((G.dims[0] + 3u) / 4u) * ((G.dims[1] + 3u) / 4u) * ((G.dims[2] + 3u) / 4u);
+	const uint32_t distBlocks = (uint32_t)FillingGrid(R, (const void*)distKernel, bricks * 64u);
+	if (!distBlocks) return false;
+	const DSceneView view = U.Cp->view;
+	if (R.sdfEvUsed) HIP_OK(hipStreamWaitEvent(st, R.sdfEv, 0));   // a bake enqueued on a caller's stream may still be using the volumes
+	if (U.sync && !BeginSync(R, st)) return false;
+	unsigned long long* counters = U.sync ? R.qStats.ptr : nullptr;
+	uint32_t slot = U.slot;
+	if (G.axes) HIP_OK(hipMemsetAsync(R.sdfBits.ptr, 0, (size_t)words * sizeof(uint32_t), st));
+	if (G.axes && !sc.triangles.empty()) {   // (an empty scene has no crossing: the zeroed volumes are its inside bits)
+		const SdfRowsKernel rowsKernel = SdfRowsKernelOf(plan.rows);
+		// one launch for all the axes' rows, or, past 2^31 - 1 of them (the row counter runs ahead of n by a chunk per wave), one per axis
+		const bool cut = rows > 0x7fffffffull;
+		for (int a = 0; a < (cut ? 3 : 1); ++a) {
+			DSdfGrid L = G;
+			uint64_t n = rows;
+			if (cut) {
+				if (!((G.axes >> a) & 1u)) continue;
+				n = voxels / G.dims[a];
+				for (int b = 0; b < 3; ++b) L.rowEnd[b] = b < a ? 0u : (uint32_t)n;
+			}
+			const uint32_t blocks = (uint32_t)FillingGrid(R, (const void*)rowsKernel, n);
+			if (!blocks) return false;
+			unsigned int* counter = R.qRing.ptr + slot;
+			HIP_OK(hipMemsetAsync(counter, 0, sizeof(unsigned int), st));
+			hipLaunchKernelGGL(rowsKernel, dim3(blocks), dim3(RL_BLOCK), 0, st, view, L, (uint32_t)n, R.sdfBits.ptr, counter, counters);
+			HIP_OK(hipGetLastError());
+			hipLaunchKernelGGL(k_sdf_parity, dim3((uint32_t)((n + RL_BLOCK - 1) / RL_BLOCK)), dim3(RL_BLOCK), 0, st, L, (uint32_t)n, R.sdfBits.ptr);
+			HIP_OK(hipGetLastError());
+			if (!ReleaseRingCounter(R, slot, st) || !TakeRingCounter(R, slot)) return false;
+		}
+	}
+	unsigned int* counter = R.qRing.ptr + slot;
+	HIP_OK(hipMemsetAsync(counter, 0, sizeof(unsigned int), st));
+	hipLaunchKernelGGL(distKernel, dim3(distBlocks), dim3(RL_BLOCK), 0, st, view, G, dDist, dPrim, (const uint32_t*)R.sdfBits.ptr, (const int32_t*)U.Cp->slotIndex.ptr, counter, counters);
+	HIP_OK(hipGetLastError());
+	if (!ReleaseRingCounter(R, slot, st)) return false;
+	HIP_OK(hipEventRecord(R.sdfEv, st));
+	R.sdfEvUsed = true;
+	if (!U.sync) return true;
+	return FinishSync(R, st, { { hostMem ? outDist : nullptr, dDist, (size_t)voxels * sizeof(float) }, { hostMem && outPrim ? outPrim : nullptr, dPrim, (size_t)voxels * sizeof(int32_t) } }, t0, stats);
 }
 
 // A triangle-overlap call is a nearest-point call with a 48-byte record, rows of maxHits indices and, when asked for, a count per query (staged through qPrim, as

@@ -302,6 +302,64 @@ def nearest_points_all(lib, scene, points, max_hits, count=False, host=False):
     return (rows, counts) if count else rows
 
 
+SDF_UNSIGNED, SDF_SIGN_X, SDF_SIGN_Y, SDF_SIGN_Z, SDF_SIGN_MAJORITY = 0, 1, 2, 3, 4   # RAYLIB_AMD_SDF_*
+
+
+class DistanceFieldParams(C.Structure):
+    """include/raylib_amd.h RaylibAMDDistanceFieldParams."""
+    _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("dims", C.c_int32 * 3), ("maxDist", C.c_float), ("sign", C.c_int32)]
+
+
+def distance_field_params(origin, spacing, dims, max_dist, sign):
+    p = DistanceFieldParams()
+    p.origin[:] = [float(x) for x in origin]
+    p.spacing[:] = [float(x) for x in spacing]
+    p.dims[:] = [int(x) for x in dims]
+    p.maxDist = float(max_dist)
+    p.sign = int(sign)
+    return p
+
+
+def plan_distance_field(lib, scene, origin, spacing, dims, max_dist, sign):
+    """RaylibAMD_PlanDistanceField: (return code, the distance kernel's plan dict, the row kernel's plan dict)."""
+    near, rows = QueryPlan(), QueryPlan()
+    r = lib.RaylibAMD_PlanDistanceField(scene, C.byref(distance_field_params(origin, spacing, dims, max_dist, sign)), C.byref(near), C.byref(rows))
+    return r, near.as_dict(), rows.as_dict()
+
+
+def bake_distance_field(lib, scene, origin, spacing, dims, max_dist, sign, prim=False, host=False, device=False, stream=None):
+    """A signed distance field on a regular grid (RaylibAMD_BakeDistanceField / RaylibAMD_BakeDistanceFieldDevice / RaylibAMD_BakeDistanceFieldHost, statements
+    V1 to V7).
+
+    dims = (nx, ny, nz); the result is indexed [k, j, i] (voxel (i, j, k) at (k * ny + j) * nx + i).  Returns the float32 distances, and with prim=True the pair
+    (distances, int32 nearest-triangle indices).  By default the host-memory entry runs on the device and NumPy arrays come back; host=True goes through the
+    oracle, which needs no device.  device=True goes through the device entry on torch tensors it allocates on the current device and returns them: enqueued on
+    `stream` (a torch stream; None: torch.cuda.current_stream()), synchronous on torch's default stream (synchronised first), as nearest_points.  Raises
+    RuntimeError when the library refuses the call."""
+    p = distance_field_params(origin, spacing, dims, max_dist, sign)
+    nx, ny, nz = (int(x) for x in dims)
+    shape = (max(nz, 0), max(ny, 0), max(nx, 0))
+    if not device:
+        dist = np.zeros(shape, np.float32)
+        prims = np.zeros(shape, np.int32) if prim else None
+        name = "RaylibAMD_BakeDistanceFieldHost" if host else "RaylibAMD_BakeDistanceField"
+        if getattr(lib, name)(scene, C.byref(p), dist.ctypes.data, prims.ctypes.data if prim else None) != 1:
+            raise RuntimeError(name + " refused the bake")
+        return (dist, prims) if prim else dist
+    import torch
+    if host:
+        raise TypeError("host=True runs the oracle: no device entry")
+    st = stream if stream is not None else torch.cuda.current_stream()
+    with torch.cuda.stream(st):
+        dist = torch.empty(shape, dtype=torch.float32, device="cuda")
+        prims = torch.empty(shape, dtype=torch.int32, device="cuda") if prim else None
+    if st.cuda_stream == 0:
+        st.synchronize()   # (the library's stream is not ordered against torch's default stream: trace_rays)
+    if lib.RaylibAMD_BakeDistanceFieldDevice(scene, C.byref(p), C.c_void_p(dist.data_ptr()), C.c_void_p(prims.data_ptr()) if prim else None, C.c_void_p(st.cuda_stream)) != 1:
+        raise RuntimeError("RaylibAMD_BakeDistanceFieldDevice refused the bake")
+    return (dist, prims) if prim else dist
+
+
 OVERLAP_ANY, OVERLAP_LIST = 0, 1                    # RAYLIB_AMD_OVERLAP_*
 OVERLAP_SKIP_SHARED = 1                             # RAYLIB_AMD_OVERLAP_SKIP_SHARED
 MAX_OVERLAPS = 16                                   # RAYLIB_AMD_MAX_OVERLAPS
@@ -942,6 +1000,10 @@ _EXPORTS = {
     "RaylibAMD_NearestPointsAllDevice": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "RaylibAMD_NearestPointsAllHost": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "RaylibAMD_PlanNearestAll": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(QueryPlan)]),
+    "RaylibAMD_BakeDistanceField": (C.c_int32, [C.c_void_p, C.POINTER(DistanceFieldParams), C.c_void_p, C.c_void_p]),
+    "RaylibAMD_BakeDistanceFieldDevice": (C.c_int32, [C.c_void_p, C.POINTER(DistanceFieldParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_BakeDistanceFieldHost": (C.c_int32, [C.c_void_p, C.POINTER(DistanceFieldParams), C.c_void_p, C.c_void_p]),
+    "RaylibAMD_PlanDistanceField": (C.c_int32, [C.c_void_p, C.POINTER(DistanceFieldParams), C.POINTER(QueryPlan), C.POINTER(QueryPlan)]),
     "RaylibAMD_OverlapTriangles": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "RaylibAMD_OverlapTrianglesDevice": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "RaylibAMD_OverlapTrianglesHost": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -11,6 +11,7 @@ bool DeviceTraceRays(Scene&, int32_t, const void*, int32_t, float, void*, int32_
 bool DeviceTraceRaysAll(Scene&, const void*, int32_t, int32_t, void*, uint32_t*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceNearestPoints(Scene&, int32_t, const void*, int32_t, void*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceNearestPointsAll(Scene&, const void*, int32_t, int32_t, void*, uint32_t*, bool, void*, RaylibAMDStats&) { return false; }
+bool DeviceBakeDistanceField(Scene&, const RaylibAMDDistanceFieldParams&, float*, int32_t*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceOverlapTriangles(Scene&, int32_t, uint32_t, const void*, int32_t, int32_t, void*, uint32_t*, bool, void*, RaylibAMDStats&, void*, bool) { return false; }
 bool DeviceTraceRadiance(Scene&, const RaylibAMDRadianceParams&, uint64_t, const void*, int32_t, float*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceGather(Scene&, int32_t, const RaylibAMDRadianceParams&, uint64_t, const void*, int32_t, float*, bool, void*, RaylibAMDStats&, const RaylibAMDGatherAdaptiveParams*,
