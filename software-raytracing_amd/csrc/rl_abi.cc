@@ -132,6 +132,41 @@ void ReportOwnStats(const RaylibAMDStats& stats)
 	g_lastStats = stats;
 }
 
+// ---- what the query entries share ----
+// An accepted call's way to the device: `call` runs the Device* function on the zeroed stats block; a synchronous call's numbers are the last call's
+template <typename Call>
+int32_t RunOnDevice(void* stream, Call call)
+{
+	if (!DeviceAvailable()) return 0;
+	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
+	if (!call(stats)) return 0;
+	if (!stream) ReportOwnStats(stats);
+	return 1;
+}
+// The refusals of the queries on triangles (`family`: what the log calls them), for device entries and oracles alike: the arguments, a finalized scene of
+// triangles only whose tree fits the walk's stack, and, for a call that writes rows (`rows`), maxHits within the family's capacity and n * maxHits in 2^31 - 1.
+struct QueryRows { int32_t maxHits, cap; const char *inputs, *items, *unit; };   // the last three: the log's words, "%d <inputs> x %d <items> exceed 2^31 - 1 <unit>"
+bool TriangleQueryArgsValid(const char* who, const char* family, const Scene* s, const void* in, int32_t n, const void* out, const QueryRows* rows = nullptr)
+{
+	if (!s || n < 0 || (n > 0 && (!in || !out))) { Log("%s: null argument", who); return false; }
+	if (rows) {
+		if (rows->maxHits < 1 || rows->maxHits > rows->cap) { Log("%s: maxHits %d is outside 1..%d", who, rows->maxHits, rows->cap); return false; }
+		if ((int64_t)n * rows->maxHits > 0x7fffffffll) { Log("%s: %d %s x %d %s exceed 2^31 - 1 %s", who, n, rows->inputs, rows->maxHits, rows->items, rows->unit); return false; }
+	}
+	if (!s->finalized) { Log("%s: scene was not finalized (Raylib_FinalizeScene)", who); return false; }
+	if (!s->spheres.empty() || !s->cubes.empty()) { Log("%s: the scene holds spheres or cubes; %s are defined on triangles", who, family); return false; }
+	if (s->bvh.depth > 64) { Log("%s: BVH depth %u exceeds the traversal stack (64)", who, s->bvh.depth); return false; }
+	return true;
+}
+// A planner's answer as the ABI reports it: -1 with `out` zeroed when the tree is too deep, else 1.  prims, early: what the entry reports of them (0: not the family's)
+int32_t ExportPlan(const QueryPlan& p, int32_t prims, int32_t early, RaylibAMDQueryPlan* out)
+{
+	memset(out, 0, sizeof(*out));
+	if (!p.ok) return -1;
+	out->tree = p.tree; out->treeWidth = p.treeWidth; out->nodeBytes = p.nodeBytes; out->stack = p.stack; out->prims = prims; out->early = early;
+	return 1;
+}
+
 // A progressive session as the ABI hands it out: the device session and the handles it was begun with.
 struct Progressive {
 	Scene* scene;
@@ -793,7 +828,7 @@ int32_t RaylibAMD_ClosestHit(SceneHandle sh, const float* rays, int32_t n, float
 	return DeviceClosestHit(*s, rays, n, tMin, outHits) ? 1 : 0;
 }
 
-// RaylibAMD_TraceRays / RaylibAMD_TraceRaysDevice: the refusals of include/raylib_amd.h, then the device
+// RaylibAMD_TraceRays / RaylibAMD_TraceRaysDevice: the refusals of include/raylib_amd.h (ray queries take spheres and cubes too), then the device
 static int32_t TraceRaysInternal(const char* who, SceneHandle sh, int32_t kind, const RaylibAMDRay* rays, int32_t n, float rayTime, void* out, int32_t* outPrim,
                                  bool hostMem, void* stream)
 {
@@ -802,17 +837,15 @@ static int32_t TraceRaysInternal(const char* who, SceneHandle sh, int32_t kind, 
 	if (!s->finalized) { Log("%s: scene was not finalized (Raylib_FinalizeScene)", who); return 0; }
 	if (kind < RAYLIB_AMD_QUERY_ANY || kind > RAYLIB_AMD_QUERY_SURFACE) { Log("%s: unknown query kind %d", who, kind); return 0; }
 	if (!std::isfinite(rayTime)) { Log("%s: ray time %g is not finite", who, rayTime); return 0; }
-	if (!DeviceAvailable()) return 0;
-	if (s->hasMovingCubes && !(rayTime >= s->accelT0 && rayTime <= s->accelT1)) {
-		// moving cubes: their boxes must cover the motion up to this ray time (as a render rebuilds them for its camera's shutter interval)
-		const float t0 = std::min(s->accelT0, rayTime), t1 = std::max(s->accelT1, rayTime);
-		ReleaseDeviceCopy(s);
-		if (!s->BuildAccel(t0, t1)) { Log("%s: the acceleration structure could not be rebuilt for ray time %g", who, rayTime); return 0; }
-	}
-	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
-	if (!DeviceTraceRays(*s, kind, rays, n, rayTime, out, outPrim, hostMem, stream, stats)) return 0;
-	if (!stream) ReportOwnStats(stats);
-	return 1;
+	return RunOnDevice(stream, [&](RaylibAMDStats& stats) {
+		if (s->hasMovingCubes && !(rayTime >= s->accelT0 && rayTime <= s->accelT1)) {
+			// moving cubes: their boxes must cover the motion up to this ray time (as a render rebuilds them for its camera's shutter interval)
+			const float t0 = std::min(s->accelT0, rayTime), t1 = std::max(s->accelT1, rayTime);
+			ReleaseDeviceCopy(s);
+			if (!s->BuildAccel(t0, t1)) { Log("%s: the acceleration structure could not be rebuilt for ray time %g", who, rayTime); return false; }
+		}
+		return DeviceTraceRays(*s, kind, rays, n, rayTime, out, outPrim, hostMem, stream, stats);
+	});
 }
 int32_t RaylibAMD_TraceRays(SceneHandle sh, int32_t kind, const RaylibAMDRay* rays, int32_t n, float rayTime, void* out, int32_t* outPrim)
 {
@@ -826,23 +859,16 @@ int32_t RaylibAMD_PlanRayQuery(SceneHandle sh, int32_t kind, RaylibAMDQueryPlan*
 {
 	Scene* s = (Scene*)sh;
 	if (!s || !s->finalized || !out || kind < RAYLIB_AMD_QUERY_ANY || kind > RAYLIB_AMD_QUERY_SURFACE) return 0;
-	memset(out, 0, sizeof(*out));
 	const QueryPlan p = PlanQuery(*s, kind, ReadRenderKnobs());
-	if (!p.ok) return -1;
-	out->tree = p.tree; out->treeWidth = p.treeWidth; out->nodeBytes = p.nodeBytes; out->stack = p.stack; out->prims = p.prims; out->early = p.early;
-	return 1;
+	return ExportPlan(p, p.prims, p.early, out);
 }
 
 // RaylibAMD_TraceRaysAll / RaylibAMD_TraceRaysAllDevice / RaylibAMD_TraceRaysAllHost / RaylibAMD_PlanRayQueryAll (statements M1 to M5): the refusals every entry shares
 static bool TraceRaysAllArgsValid(const char* who, const Scene* s, const void* rays, int32_t n, float rayTime, int32_t maxHits, const void* outHits)
 {
-	if (!s || n < 0 || (n > 0 && (!rays || !outHits))) { Log("%s: null argument", who); return false; }
-	if (maxHits < 1 || maxHits > RAYLIB_AMD_MAX_HITS) { Log("%s: maxHits %d is outside 1..%d", who, maxHits, RAYLIB_AMD_MAX_HITS); return false; }
+	const QueryRows rows = { maxHits, RAYLIB_AMD_MAX_HITS, "rays", "hits", "records" };
+	if (!TriangleQueryArgsValid(who, "multi-hit queries", s, rays, n, outHits, &rows)) return false;
 	if (!std::isfinite(rayTime)) { Log("%s: ray time %g is not finite", who, rayTime); return false; }
-	if (!s->finalized) { Log("%s: scene was not finalized (Raylib_FinalizeScene)", who); return false; }
-	if (!s->spheres.empty() || !s->cubes.empty()) { Log("%s: the scene holds spheres or cubes; multi-hit queries are defined on triangles", who); return false; }
-	if (s->bvh.depth > 64) { Log("%s: BVH depth %u exceeds the traversal stack (64)", who, s->bvh.depth); return false; }
-	if ((int64_t)n * maxHits > 0x7fffffffll) { Log("%s: %d rays x %d hits exceed 2^31 - 1 records", who, n, maxHits); return false; }
 	return true;
 }
 static int32_t TraceRaysAllInternal(const char* who, SceneHandle sh, const RaylibAMDRay* rays, int32_t n, float rayTime, int32_t maxHits, RaylibAMDHitT* outHits, uint32_t* outCount,
@@ -850,11 +876,7 @@ static int32_t TraceRaysAllInternal(const char* who, SceneHandle sh, const Rayli
 {
 	Scene* s = (Scene*)sh;
 	if (!TraceRaysAllArgsValid(who, s, rays, n, rayTime, maxHits, outHits)) return 0;
-	if (!DeviceAvailable()) return 0;
-	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
-	if (!DeviceTraceRaysAll(*s, rays, n, maxHits, outHits, outCount, hostMem, stream, stats)) return 0;
-	if (!stream) ReportOwnStats(stats);
-	return 1;
+	return RunOnDevice(stream, [&](RaylibAMDStats& stats) { return DeviceTraceRaysAll(*s, rays, n, maxHits, outHits, outCount, hostMem, stream, stats); });
 }
 int32_t RaylibAMD_TraceRaysAll(SceneHandle sh, const RaylibAMDRay* rays, int32_t n, float rayTime, int32_t maxHits, RaylibAMDHitT* outHits, uint32_t* outCount)
 {
@@ -943,33 +965,21 @@ int32_t RaylibAMD_PlanRayQueryAll(SceneHandle sh, int32_t maxHits, int32_t wantC
 {
 	Scene* s = (Scene*)sh;
 	if (!s || !s->finalized || !out || maxHits < 1 || maxHits > RAYLIB_AMD_MAX_HITS || !s->spheres.empty() || !s->cubes.empty()) return 0;
-	memset(out, 0, sizeof(*out));
-	const QueryPlan p = PlanQueryAll(*s, ReadRenderKnobs());
-	if (!p.ok) return -1;
 	(void)wantCount;   // (the count changes the kernel's instance and what it may prune, not the tree)
-	out->tree = p.tree; out->treeWidth = p.treeWidth; out->nodeBytes = p.nodeBytes; out->stack = p.stack; out->prims = 0; out->early = 0;
-	return 1;
+	return ExportPlan(PlanQueryAll(*s, ReadRenderKnobs()), 0, 0, out);
 }
 
 // RaylibAMD_NearestPoints / RaylibAMD_NearestPointsDevice / RaylibAMD_NearestPointsHost / RaylibAMD_PlanNearest: the refusals every entry shares
 static bool NearestArgsValid(const char* who, const Scene* s, int32_t kind, const void* points, int32_t n, const void* out)
 {
-	if (!s || n < 0 || (n > 0 && (!points || !out))) { Log("%s: null argument", who); return false; }
-	if (!s->finalized) { Log("%s: scene was not finalized (Raylib_FinalizeScene)", who); return false; }
 	if (kind != RAYLIB_AMD_NEAREST_WITHIN && kind != RAYLIB_AMD_NEAREST_CLOSEST) { Log("%s: unknown nearest kind %d", who, kind); return false; }
-	if (!s->spheres.empty() || !s->cubes.empty()) { Log("%s: the scene holds spheres or cubes; nearest-point queries are defined on triangles", who); return false; }
-	if (s->bvh.depth > 64) { Log("%s: BVH depth %u exceeds the traversal stack (64)", who, s->bvh.depth); return false; }
-	return true;
+	return TriangleQueryArgsValid(who, "nearest-point queries", s, points, n, out);
 }
 static int32_t NearestPointsInternal(const char* who, SceneHandle sh, int32_t kind, const RaylibAMDNearestQuery* points, int32_t n, void* out, bool hostMem, void* stream)
 {
 	Scene* s = (Scene*)sh;
 	if (!NearestArgsValid(who, s, kind, points, n, out)) return 0;
-	if (!DeviceAvailable()) return 0;
-	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
-	if (!DeviceNearestPoints(*s, kind, points, n, out, hostMem, stream, stats)) return 0;
-	if (!stream) ReportOwnStats(stats);
-	return 1;
+	return RunOnDevice(stream, [&](RaylibAMDStats& stats) { return DeviceNearestPoints(*s, kind, points, n, out, hostMem, stream, stats); });
 }
 int32_t RaylibAMD_NearestPoints(SceneHandle sh, int32_t kind, const RaylibAMDNearestQuery* points, int32_t n, void* out)
 {
@@ -1010,34 +1020,22 @@ int32_t RaylibAMD_PlanNearest(SceneHandle sh, int32_t kind, RaylibAMDQueryPlan* 
 {
 	Scene* s = (Scene*)sh;
 	if (!s || !s->finalized || !out || (kind != RAYLIB_AMD_NEAREST_WITHIN && kind != RAYLIB_AMD_NEAREST_CLOSEST) || !s->spheres.empty() || !s->cubes.empty()) return 0;
-	memset(out, 0, sizeof(*out));
 	const QueryPlan p = PlanNearest(*s, kind, ReadRenderKnobs());
-	if (!p.ok) return -1;
-	out->tree = p.tree; out->treeWidth = p.treeWidth; out->nodeBytes = p.nodeBytes; out->stack = p.stack; out->prims = 0; out->early = p.early;
-	return 1;
+	return ExportPlan(p, 0, p.early, out);
 }
 
 // RaylibAMD_NearestPointsAll / RaylibAMD_NearestPointsAllDevice / RaylibAMD_NearestPointsAllHost / RaylibAMD_PlanNearestAll (statements K1 to K5): the refusals every entry shares
 static bool NearestAllArgsValid(const char* who, const Scene* s, const void* points, int32_t n, int32_t maxHits, const void* outHits)
 {
-	if (!s || n < 0 || (n > 0 && (!points || !outHits))) { Log("%s: null argument", who); return false; }
-	if (maxHits < 1 || maxHits > RAYLIB_AMD_MAX_NEAREST) { Log("%s: maxHits %d is outside 1..%d", who, maxHits, RAYLIB_AMD_MAX_NEAREST); return false; }
-	if (!s->finalized) { Log("%s: scene was not finalized (Raylib_FinalizeScene)", who); return false; }
-	if (!s->spheres.empty() || !s->cubes.empty()) { Log("%s: the scene holds spheres or cubes; nearest-point queries are defined on triangles", who); return false; }
-	if (s->bvh.depth > 64) { Log("%s: BVH depth %u exceeds the traversal stack (64)", who, s->bvh.depth); return false; }
-	if ((int64_t)n * maxHits > 0x7fffffffll) { Log("%s: %d points x %d records exceed 2^31 - 1 records", who, n, maxHits); return false; }
-	return true;
+	const QueryRows rows = { maxHits, RAYLIB_AMD_MAX_NEAREST, "points", "records", "records" };
+	return TriangleQueryArgsValid(who, "nearest-point queries", s, points, n, outHits, &rows);
 }
 static int32_t NearestPointsAllInternal(const char* who, SceneHandle sh, const RaylibAMDNearestQuery* points, int32_t n, int32_t maxHits, RaylibAMDNearestHit* outHits, uint32_t* outCount,
                                         bool hostMem, void* stream)
 {
 	Scene* s = (Scene*)sh;
 	if (!NearestAllArgsValid(who, s, points, n, maxHits, outHits)) return 0;
-	if (!DeviceAvailable()) return 0;
-	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
-	if (!DeviceNearestPointsAll(*s, points, n, maxHits, outHits, outCount, hostMem, stream, stats)) return 0;
-	if (!stream) ReportOwnStats(stats);
-	return 1;
+	return RunOnDevice(stream, [&](RaylibAMDStats& stats) { return DeviceNearestPointsAll(*s, points, n, maxHits, outHits, outCount, hostMem, stream, stats); });
 }
 int32_t RaylibAMD_NearestPointsAll(SceneHandle sh, const RaylibAMDNearestQuery* points, int32_t n, int32_t maxHits, RaylibAMDNearestHit* outHits, uint32_t* outCount)
 {
@@ -1081,39 +1079,26 @@ int32_t RaylibAMD_PlanNearestAll(SceneHandle sh, int32_t maxHits, int32_t wantCo
 {
 	Scene* s = (Scene*)sh;
 	if (!s || !s->finalized || !out || maxHits < 1 || maxHits > RAYLIB_AMD_MAX_NEAREST || !s->spheres.empty() || !s->cubes.empty()) return 0;
-	memset(out, 0, sizeof(*out));
-	const QueryPlan p = PlanNearestAll(*s, ReadRenderKnobs());
-	if (!p.ok) return -1;
 	(void)wantCount;   // (the count changes the kernel's instance and what it may prune, not the tree)
-	out->tree = p.tree; out->treeWidth = p.treeWidth; out->nodeBytes = p.nodeBytes; out->stack = p.stack; out->prims = 0; out->early = 0;
-	return 1;
+	return ExportPlan(PlanNearestAll(*s, ReadRenderKnobs()), 0, 0, out);
 }
 
 // RaylibAMD_OverlapTriangles / RaylibAMD_OverlapTrianglesDevice / RaylibAMD_OverlapTrianglesHost (statements O1 to O6): the refusals every entry shares
 static bool OverlapArgsValid(const char* who, const Scene* s, int32_t kind, uint32_t flags, const void* q, int32_t n, int32_t maxHits, const void* out, const uint32_t* outCount)
 {
-	if (!s || n < 0 || (n > 0 && (!q || !out))) { Log("%s: null argument", who); return false; }
 	if (kind != RAYLIB_AMD_OVERLAP_ANY && kind != RAYLIB_AMD_OVERLAP_LIST) { Log("%s: unknown overlap kind %d", who, kind); return false; }
 	if ((flags & ~RAYLIB_AMD_OVERLAP_SKIP_SHARED) != 0u) { Log("%s: unknown flag bits 0x%x", who, flags); return false; }
-	if (kind == RAYLIB_AMD_OVERLAP_LIST) {
-		if (maxHits < 1 || maxHits > RAYLIB_AMD_MAX_OVERLAPS) { Log("%s: maxHits %d is outside 1..%d", who, maxHits, RAYLIB_AMD_MAX_OVERLAPS); return false; }
-		if ((int64_t)n * maxHits > 0x7fffffffll) { Log("%s: %d queries x %d indices exceed 2^31 - 1 words", who, n, maxHits); return false; }
-	} else if (outCount) { Log("%s: outCount belongs to RAYLIB_AMD_OVERLAP_LIST", who); return false; }
-	if (!s->finalized) { Log("%s: scene was not finalized (Raylib_FinalizeScene)", who); return false; }
-	if (!s->spheres.empty() || !s->cubes.empty()) { Log("%s: the scene holds spheres or cubes; overlap queries are defined on triangles", who); return false; }
-	if (s->bvh.depth > 64) { Log("%s: BVH depth %u exceeds the traversal stack (64)", who, s->bvh.depth); return false; }
-	return true;
+	const bool list = kind == RAYLIB_AMD_OVERLAP_LIST;
+	if (!list && outCount) { Log("%s: outCount belongs to RAYLIB_AMD_OVERLAP_LIST", who); return false; }
+	const QueryRows rows = { maxHits, RAYLIB_AMD_MAX_OVERLAPS, "queries", "indices", "words" };
+	return TriangleQueryArgsValid(who, "overlap queries", s, q, n, out, list ? &rows : nullptr);
 }
 static int32_t OverlapTrianglesInternal(const char* who, SceneHandle sh, int32_t kind, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, void* out, uint32_t* outCount,
                                         bool hostMem, void* stream)
 {
 	Scene* s = (Scene*)sh;
 	if (!OverlapArgsValid(who, s, kind, flags, q, n, maxHits, out, outCount)) return 0;
-	if (!DeviceAvailable()) return 0;
-	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
-	if (!DeviceOverlapTriangles(*s, kind, flags, q, n, maxHits, out, outCount, hostMem, stream, stats)) return 0;
-	if (!stream) ReportOwnStats(stats);
-	return 1;
+	return RunOnDevice(stream, [&](RaylibAMDStats& stats) { return DeviceOverlapTriangles(*s, kind, flags, q, n, maxHits, out, outCount, hostMem, stream, stats); });
 }
 int32_t RaylibAMD_OverlapTriangles(SceneHandle sh, int32_t kind, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, void* out, uint32_t* outCount)
 {
@@ -1158,11 +1143,8 @@ int32_t RaylibAMD_PlanOverlap(SceneHandle sh, int32_t kind, RaylibAMDQueryPlan* 
 {
 	Scene* s = (Scene*)sh;
 	if (!s || !s->finalized || !out || (kind != RAYLIB_AMD_OVERLAP_ANY && kind != RAYLIB_AMD_OVERLAP_LIST) || !s->spheres.empty() || !s->cubes.empty()) return 0;
-	memset(out, 0, sizeof(*out));
 	const QueryPlan p = PlanOverlap(*s, kind, ReadRenderKnobs());
-	if (!p.ok) return -1;
-	out->tree = p.tree; out->treeWidth = p.treeWidth; out->nodeBytes = p.nodeBytes; out->stack = p.stack; out->prims = 0; out->early = p.early;
-	return 1;
+	return ExportPlan(p, 0, p.early, out);
 }
 
 // RaylibAMD_OverlapContacts / ...Device / ...Host (statements C1 to C6): LIST's refusals, and the records' own
@@ -1179,11 +1161,9 @@ static int32_t OverlapContactsInternal(const char* who, SceneHandle sh, uint32_t
 {
 	Scene* s = (Scene*)sh;
 	if (!ContactArgsValid(who, s, flags, q, n, maxHits, outIndex, outContact, outCount)) return 0;
-	if (!DeviceAvailable()) return 0;
-	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
-	if (!DeviceOverlapTriangles(*s, RAYLIB_AMD_OVERLAP_LIST, flags, q, n, maxHits, outIndex, outCount, hostMem, stream, stats, outContact, true)) return 0;
-	if (!stream) ReportOwnStats(stats);
-	return 1;
+	return RunOnDevice(stream, [&](RaylibAMDStats& stats) {
+		return DeviceOverlapTriangles(*s, RAYLIB_AMD_OVERLAP_LIST, flags, q, n, maxHits, outIndex, outCount, hostMem, stream, stats, outContact, true);
+	});
 }
 int32_t RaylibAMD_OverlapContacts(SceneHandle sh, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, int32_t* outIndex, RaylibAMDContact* outContact,
                                   uint32_t* outCount)
@@ -1258,11 +1238,7 @@ static int32_t BakeDistanceFieldInternal(const char* who, SceneHandle sh, const 
 	Scene* s = (Scene*)sh;
 	RaylibAMDDistanceFieldParams grid;
 	if (!DistanceFieldArgsValid(who, s, params, outDist, true, grid)) return 0;
-	if (!DeviceAvailable()) return 0;
-	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
-	if (!DeviceBakeDistanceField(*s, grid, outDist, outPrim, hostMem, stream, stats)) return 0;
-	if (!stream) ReportOwnStats(stats);
-	return 1;
+	return RunOnDevice(stream, [&](RaylibAMDStats& stats) { return DeviceBakeDistanceField(*s, grid, outDist, outPrim, hostMem, stream, stats); });
 }
 int32_t RaylibAMD_BakeDistanceField(SceneHandle sh, const RaylibAMDDistanceFieldParams* params, float* outDist, int32_t* outPrim)
 {
@@ -1342,13 +1318,8 @@ int32_t RaylibAMD_PlanDistanceField(SceneHandle sh, const RaylibAMDDistanceField
 	if (!DistanceFieldArgsValid("RaylibAMD_PlanDistanceField", s, params, nullptr, false, grid)) return 0;
 	const DistanceFieldPlan p = PlanDistanceField(*s, ReadRenderKnobs());
 	if (!p.nearest.ok || !p.rows.ok) return -1;
-	const QueryPlan* from[2] = { &p.nearest, &p.rows };
-	RaylibAMDQueryPlan* to[2] = { outNearest, outRows };
-	for (int k = 0; k < 2; ++k) {
-		if (!to[k]) continue;
-		memset(to[k], 0, sizeof(*to[k]));
-		to[k]->tree = from[k]->tree; to[k]->treeWidth = from[k]->treeWidth; to[k]->nodeBytes = from[k]->nodeBytes; to[k]->stack = from[k]->stack; to[k]->prims = 0; to[k]->early = 0;
-	}
+	if (outNearest) ExportPlan(p.nearest, 0, 0, outNearest);
+	if (outRows) ExportPlan(p.rows, 0, 0, outRows);
 	return 1;
 }
 
@@ -1425,11 +1396,8 @@ int32_t RaylibAMD_TraceRadianceDevice(SceneHandle sh, const RaylibAMDRadiancePar
 int32_t RaylibAMD_PlanRadiance(SceneHandle sh, const RaylibAMDRadianceParams* params, RaylibAMDQueryPlan* out)
 {
 	if (!out || !RadianceParamsValid("RaylibAMD_PlanRadiance", (Scene*)sh, params)) return 0;
-	memset(out, 0, sizeof(*out));
 	const QueryPlan p = PlanRadiance(*(Scene*)sh, ReadRenderKnobs());
-	if (!p.ok) return -1;
-	out->tree = p.tree; out->treeWidth = p.treeWidth; out->nodeBytes = p.nodeBytes; out->stack = p.stack; out->prims = p.prims; out->early = 0;
-	return 1;
+	return ExportPlan(p, p.prims, 0, out);
 }
 
 // RaylibAMD_Gather / RaylibAMD_GatherDevice / RaylibAMD_GatherDirectionsHost: a gather's own refusals; the rest are a radiance call's

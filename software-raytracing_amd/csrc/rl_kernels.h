@@ -185,7 +185,7 @@ RL_QUERY_INSTANCES(extern RL_K_QUERY)
 // (the lanes' lists).  outHits: n rows of maxHits DQueryHit.  outCount: n words (COUNT) or null.  slotIndex, rayCounter, counters: as k_query's.
 #define RL_QUERY_ALL_ARGS const DSceneView, const float4* __restrict__, uint32_t, uint32_t, float4* __restrict__, uint32_t* __restrict__, const int32_t* __restrict__, unsigned int* __restrict__, unsigned long long* __restrict__
 template <int TREE, int STACK, bool COUNT> __global__ void __launch_bounds__(RL_BLOCK) k_query_all(RL_QUERY_ALL_ARGS);
-// The instances rl_rt_rays.hip QueryAllKernelFor selects from: (TREE, STACK, COUNT)
+// The instances rl_rt_rays.hip QueryAllKernelOf selects from: (TREE, STACK, COUNT)
 #define RL_QUERY_ALL_INSTANCES_C(X, C) X(2, 32, C) X(2, 64, C) X(8, 2 * RL_POOL8_MAXLEVELS, C)
 #define RL_QUERY_ALL_INSTANCES(X) RL_QUERY_ALL_INSTANCES_C(X, false) RL_QUERY_ALL_INSTANCES_C(X, true)
 #define RL_K_QUERY_ALL(a, b, c) template __global__ void k_query_all<a, b, c>(RL_QUERY_ALL_ARGS);
@@ -293,7 +293,7 @@ RL_RADIANCE_INSTANCES(extern RL_K_RADIANCE)
 #define RL_GATHER_ARGS const DSceneView, const SkyRot, const DRadianceParams, const float4* __restrict__, uint32_t, const DGatherJobs, float4* __restrict__, float* __restrict__, unsigned int* __restrict__, unsigned long long* __restrict__
 template <int TREE, int STACK, bool PRIMS, int GEN>
 __global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 2)) k_gather(RL_GATHER_ARGS);
-// The instances rl_rt_rays.hip GatherKernelFor selects from: k_radiance's (TREE, STACK, PRIMS), once per generator
+// The instances rl_rt_rays.hip GatherKernelOfKind selects from: k_radiance's (TREE, STACK, PRIMS), once per generator
 #define RL_GATHER_INSTANCES_G(X, G) X(2, 32, false, G) X(2, 32, true, G) X(2, 64, false, G) X(2, 64, true, G) X(4, 32, false, G) X(4, 64, false, G)
 #define RL_GATHER_INSTANCES(X) RL_GATHER_INSTANCES_G(X, RL_GEN_HEMISPHERE) RL_GATHER_INSTANCES_G(X, RL_GEN_SPHERE)
 #define RL_K_GATHER(a, b, c, d) template __global__ void k_gather<a, b, c, d>(RL_GATHER_ARGS);

@@ -4,7 +4,8 @@
 //   rl_rt_scene.hip   a flattened scene (rl_scene.cc FlattenScene) to every device, its sky and wide trees; images: read-back, RGB dump, post-processing
 //   rl_rt_frame.hip   kernel selection and the one enqueue path of every render (EnqueueFrame), a rank's one-view render, a batch of views
 //   rl_rt_render.hip  whole frames over N ranks (gather, scatter, two frames in flight), DeviceRender, progressive sessions
-//   rl_rt_rays.hip    caller rays and points: DeviceTraceRays, DeviceTraceRaysAll, DeviceNearestPoints, DeviceNearestPointsAll, DeviceOverlapTriangles (and its contacts), DeviceTraceRadiance, DeviceGather (plain and adaptive: one driver, GatherLocked)
+//   rl_rt_rays.hip    caller rays, points and triangles: the queries (DeviceTraceRays, DeviceTraceRaysAll, DeviceNearestPoints, DeviceNearestPointsAll, DeviceOverlapTriangles
+//                     and its contacts: one driver, RunQuery), DeviceBakeDistanceField on the same pieces, DeviceTraceRadiance, DeviceGather (plain and adaptive: one driver, GatherLocked)
 //   rl_rt_lightmap.hip  lightmaps: DeviceLightmapPoints, DeviceBakeLightmap (the raster stages, then DeviceGather's body or the caller's atlas, the filter, the atlas stages)
 //   rl_rt_move.hip    RaylibAMD_SceneMoveTriangles: the moved records and the refit of every tree on the device, the host copies' read-back, RaylibAMD_SceneCheckTrees
 //   rl_rt_hooks.hip   test hooks
@@ -168,7 +169,7 @@ struct Worker {
 	bool Wait() { std::unique_lock<std::mutex> lk(m); cv.wait(lk, [&] { return !pending; }); return result; }
 };
 
-#define RL_QUERY_RING 64   /* ray counters of the ray queries, used in turn (DeviceTraceRays) */
+#define RL_QUERY_RING 64   /* work counters of the queries and the distance-field bakes, used in turn (rl_rt_rays.hip LaunchOnRing) */
 struct RankCtx {
 	int rank = 0, device = 0, devSlot = 0, numCUs = 0;
 	hipStream_t stream = nullptr;
@@ -192,12 +193,11 @@ struct RankCtx {
 	uint32_t cullActive[2] = { 0, 0 }; uint64_t cullEmptyPixels[2] = { 0, 0 }; float cullL[2][3] = { { 0, 0, 0 }, { 0, 0, 0 } }; uint32_t cullRays[2] = { 1, 1 };
 	std::map<const void*, int> occupancy;   // blocks per CU, asked once per kernel
 	Worker* worker = nullptr;
-	// the ray queries (DeviceTraceRays): staging buffers of the host entry, kept and grown; a ring of ray counters, one per launch in turn, each with the
+	// the queries (rl_rt_rays.hip RunQuery): staging buffers of the host entries, kept and grown; a ring of work counters, one per launch in turn, each with the
 	// event recorded behind its last launch (a slot is reused once that launch is done, whatever stream it ran on); the synchronous queries' counters and events
 	DevBuf<float4> qRays;
-	DevBuf<void> qOut;
-	DevBuf<int32_t> qPrim;
-	DevBuf<float4> qContact;   // a host contacts call's records (RaylibAMD_OverlapContacts), staged as qPrim is
+	DevBuf<void> qOut, qPrim;  // a host call's first output; its second (primitives, counts)
+	DevBuf<void> qContact;     // a host contacts call's records (RaylibAMD_OverlapContacts), staged as qPrim is
 	// a distance-field bake's bit volumes (DeviceBakeDistanceField), kept and grown, and the event behind the last bake's last kernel -- every bake waits for it
 	// on its own stream, so that two bakes on two streams never share the volumes at the same time
 	DevBuf<uint32_t> sdfBits;

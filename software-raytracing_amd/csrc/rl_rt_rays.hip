@@ -1,13 +1,13 @@
-// Host runtime: rays of the caller's -- the ray queries (RaylibAMD_TraceRays, k_query), the ordered multi-hit queries (RaylibAMD_TraceRaysAll, k_query_all) the nearest-point queries (RaylibAMD_NearestPoints, k_nearest; RaylibAMD_NearestPointsAll, k_nearest_all) the triangle-overlap queries (RaylibAMD_OverlapTriangles, k_overlap) and the distance-field bakes (RaylibAMD_BakeDistanceField, k_sdf_*) that share their call (BeginQueryCall), path-traced radiance (RaylibAMD_TraceRadiance, k_radiance) and the
-// irradiance and SH probes gathered from it at caller points (RaylibAMD_Gather, k_gather + k_gather_resolve) on rank 0's device, from host memory or from device pointers, on the library's stream (synchronous, with stats) or enqueued on a stream of the caller's (rl_rt.h).
-// The two entries share the refusals of a device call's pointers, the synchronous call's counter block and event pair, the stats' header, the staging of a
-// host call through qRays / qOut, the grid that fills the device once, and the synchronous tail; each keeps its plan and kernel, its parameter block and the
-// discipline of its scratch: a ring of ray counters with an event per slot for the queries, one counter and one path stack ordered by radEv for radiance.
-// A gather is a radiance call with another generator: it shares that call's preparation (BeginPathCall, PathGrid), its counter, stack and event chain, and adds
-// the sample buffer and the per-point sums between its launches.  An adaptive gather (RaylibAMD_GatherAdaptive) is that gather in passes over a shrinking,
-// compacted set of live points: the same trace kernel, a resolve that also decides which points stop, and the compaction behind each pass.  Both are one
-// driver (GatherLocked): one prologue, one launch -- counter, event pair, k_gather, the launch's resolve --, one tail; a plain call loops over its cut's launches,
-// an adaptive call over its passes.
+// Host runtime: calls on rays, points and triangles of the caller's, on rank 0's device -- from host memory or from device pointers, on the library's stream
+// (synchronous, with stats) or enqueued on a stream of the caller's (rl_host.h).  Two families and what they share:
+//   The queries -- ray, ordered multi-hit, nearest-point, K-nearest and triangle-overlap queries with their contacts -- are one call (RunQuery) that each entry
+//   describes by data (QueryDesc: plan, kernel, input records, outputs, dynamic LDS) and gives its launch; a distance-field bake is several launches on the
+//   same pieces.  Their scratch is a ring of work counters with an event per slot (LaunchOnRing).
+//   The path calls -- radiance along caller rays, and the gathers, which are that call with another generator -- share BeginPathCall and PathGrid, one counter
+//   and one path stack ordered by radEv.  A plain and an adaptive gather are one driver (GatherLocked): one prologue, one launch -- counter, event pair,
+//   k_gather, the launch's resolve --, one tail; a plain call loops over its cut's launches, an adaptive call over its passes of a shrinking, compacted set.
+//   Both share the refusals of a device call's pointers (DevicePointersOk), the staging of a host call through qRays / qOut, the grid that fills the device
+//   once (FillingGrid), the stats' header, and a synchronous call's counter block, event pair and tail (BeginSync, FinishSync).
 #include "rl_rt.h"
 
 namespace rl {
@@ -73,6 +73,36 @@ static_assert(RAYLIB_AMD_GATHER_IRRADIANCE + 1 == RL_GEN_HEMISPHERE && RAYLIB_AM
 static_assert(sizeof(RaylibAMDGatherPoint) == sizeof(RaylibAMDRay), "gather records");
 static_assert(RL_RADIANCE_STACK_BUDGET / ((uint64_t)RL_RADIANCE_MAX_PATH * 8 * sizeof(float) * RL_BLOCK) >= 1, "one workgroup's path stack fits the budget");
 
+typedef void (*QueryAllKernel)(const DSceneView, const float4*, uint32_t, uint32_t, float4*, uint32_t*, const int32_t*, unsigned int*, unsigned long long*);
+template <bool COUNT>
+static QueryAllKernel QueryAllKernelOf(const QueryPlan& p)
+{
+	if (p.tree == TREE_WIDE8) return (QueryAllKernel)k_query_all<8, 2 * RL_POOL8_MAXLEVELS, COUNT>;
+	return p.stack <= 32 ? (QueryAllKernel)k_query_all<2, 32, COUNT> : (QueryAllKernel)k_query_all<2, 64, COUNT>;
+}
+static_assert(RAYLIB_AMD_MAX_HITS == RL_MAX_HITS, "multi-hit capacity");
+typedef void (*NearestAllKernel)(const DSceneView, const float4*, uint32_t, uint32_t, float4*, uint32_t*, const int32_t*, unsigned int*, unsigned long long*);
+template <bool COUNT>
+static NearestAllKernel NearestAllKernelOf(const QueryPlan& p)
+{
+	if (p.tree == TREE_GRID4) return p.stack <= 32 ? (NearestAllKernel)k_nearest_all<4, 32, COUNT> : (NearestAllKernel)k_nearest_all<4, 64, COUNT>;
+	return p.stack <= 32 ? (NearestAllKernel)k_nearest_all<2, 32, COUNT> : (NearestAllKernel)k_nearest_all<2, 64, COUNT>;
+}
+static_assert(RAYLIB_AMD_MAX_NEAREST == RL_MAX_NEAREST, "K-nearest capacity");
+typedef void (*SdfRowsKernel)(const DSceneView, const DSdfGrid, uint32_t, uint32_t*, unsigned int*, unsigned long long*);
+static SdfRowsKernel SdfRowsKernelOf(const QueryPlan& p)
+{
+	if (p.tree == TREE_WIDE8) return (SdfRowsKernel)k_sdf_rows<8, 2 * RL_POOL8_MAXLEVELS>;
+	return p.stack <= 32 ? (SdfRowsKernel)k_sdf_rows<2, 32> : (SdfRowsKernel)k_sdf_rows<2, 64>;
+}
+typedef void (*SdfDistKernel)(const DSceneView, const DSdfGrid, float*, int32_t*, const uint32_t*, const int32_t*, unsigned int*, unsigned long long*);
+template <bool SIGNED>
+static SdfDistKernel SdfDistKernelOf(const QueryPlan& p)
+{
+	if (p.tree == TREE_GRID4) return p.stack <= 32 ? (SdfDistKernel)k_sdf_dist<4, 32, SIGNED> : (SdfDistKernel)k_sdf_dist<4, 64, SIGNED>;
+	return p.stack <= 32 ? (SdfDistKernel)k_sdf_dist<2, 32, SIGNED> : (SdfDistKernel)k_sdf_dist<2, 64, SIGNED>;
+}
+
 // a device pointer a call may use: memory of rank 0's device
 bool OnDevice(const void* p, int device)
 {
@@ -80,16 +110,32 @@ bool OnDevice(const void* p, int device)
 	if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
 	return (a.type == hipMemoryTypeDevice || a.isManaged) && a.device == device;
 }
-// The refusals of a device call (`api`): every pointer is memory of the device; the kernels read a ray as two 16-byte loads and write a 16-byte result as one
-// store (outAlign 15), the other records as 4-byte words (3).  outPrim, when given, is checked as device memory only where the call writes it (primUsed).
-static bool DevicePointersOk(const char* api, const char* what, int device, const void* rays, const void* out, uintptr_t outAlign, const void* outPrim, bool primUsed)
+// An output of a call: the caller's pointer; the bytes the call writes there (0: it writes none -- the pointer was not given, or is not this kind's); the mask
+// of its alignment (15: records stored as one 16-byte word, 3: 4-byte words); the rank's buffer a host call stages it through; and, once StageOutputs has run,
+// the device pointer the kernel gets (null for an output that is not written).
+struct QueryOut { void* user = nullptr; size_t bytes = 0; uintptr_t align = 3u; DevBuf<void> RankCtx::* stage = nullptr; void* dev = nullptr; };
+// The refusals of a device call (`api`): the input (`what` names its records; null: the call has none) and every output the call writes are memory of the
+// device; the kernels read an input record as 16-byte loads; every output pointer given, written or not, is aligned as its records are stored.
+static bool DevicePointersOk(const char* api, const char* what, int device, const void* in, const QueryOut* outs, size_t numOuts)
 {
-	if (!OnDevice(rays, device) || !OnDevice(out, device) || (outPrim && primUsed && !OnDevice(outPrim, device))) {
-		Log("%s: a pointer is not device memory of device %d", api, device);
-		return false;
+	bool onDevice = !what || OnDevice(in, device);
+	for (size_t k = 0; k < numOuts; ++k) if (outs[k].bytes && !OnDevice(outs[k].user, device)) onDevice = false;
+	if (!onDevice) { Log("%s: a pointer is not device memory of device %d", api, device); return false; }
+	if (what && ((uintptr_t)in & 15u) != 0) { Log("%s: the %s are not 16-byte aligned", api, what); return false; }
+	for (size_t k = 0; k < numOuts; ++k)
+		if (((uintptr_t)outs[k].user & outs[k].align) != 0) { Log("%s: the output is not %u-byte aligned", api, (unsigned)outs[k].align + 1u); return false; }
+	return true;
+}
+// where the kernel writes each output: the caller's memory, or, for a host call, the staging buffer grown to it
+static bool StageOutputs(RankCtx& R, QueryOut* outs, size_t numOuts, bool hostMem)
+{
+	for (size_t k = 0; k < numOuts; ++k) {
+		QueryOut& o = outs[k];
+		o.dev = o.bytes ? o.user : nullptr;
+		if (!o.bytes || !hostMem) continue;
+		if (!(R.*o.stage).Grow(o.bytes)) return false;
+		o.dev = (R.*o.stage).ptr;
 	}
-	if (((uintptr_t)rays & 15u) != 0) { Log("%s: the %s are not 16-byte aligned", api, what); return false; }
-	if (((uintptr_t)out & outAlign) != 0 || ((uintptr_t)outPrim & 3u) != 0) { Log("%s: the output is not %u-byte aligned", api, (unsigned)outAlign + 1u); return false; }
 	return true;
 }
 
@@ -108,11 +154,11 @@ static void StatsHeader(RaylibAMDStats& stats, const QueryPlan& plan, const Scen
 	stats.treeWidth = plan.treeWidth; stats.nodeBytes = plan.nodeBytes;
 	OneRankStats(stats, sc);
 }
-// a host call's rays (n records of 32 bytes; a nearest query's points: 16; an overlap query's triangles: 48) into the rank's staging buffer, behind whatever `st` holds; its results go through qOut
-static bool StageRays(RankCtx& R, const void* rays, int32_t n, size_t outBytes, hipStream_t st, size_t recordBytes = sizeof(RaylibAMDRay))
+// a host path call's rays or points (n records of 32 bytes) into the rank's staging buffer, behind whatever `st` holds; its results go through qOut
+static bool StageRays(RankCtx& R, const void* rays, int32_t n, size_t outBytes, hipStream_t st)
 {
-	if (!R.qRays.Grow((size_t)n * recordBytes) || !R.qOut.Grow(outBytes)) return false;
-	HIP_OK(hipMemcpyAsync(R.qRays.ptr, rays, (size_t)n * recordBytes, hipMemcpyHostToDevice, st));
+	if (!R.qRays.Grow((size_t)n * sizeof(RaylibAMDRay)) || !R.qOut.Grow(outBytes)) return false;
+	HIP_OK(hipMemcpyAsync(R.qRays.ptr, rays, (size_t)n * sizeof(RaylibAMDRay), hipMemcpyHostToDevice, st));
 	return true;
 }
 // triangle slot -> index in the scene's triangle order, on the device when a call first needs it
@@ -149,20 +195,35 @@ static bool TakeRingCounter(RankCtx& R, uint32_t& slot)
 	if (R.qRingUsed[slot]) HIP_OK(hipEventSynchronize(R.qRingEv[slot]));
 	return true;
 }
-// ... and the event behind the launch that used it
-static bool ReleaseRingCounter(RankCtx& R, uint32_t slot, hipStream_t st)
+// ... and one launch on it: the counter cleared on `st`, what `launch` enqueues there (it gets the counter; false: it failed, and said so), the launch's error,
+// and the event behind it, with which the slot is the ring's last
+template <typename Launch>
+static bool LaunchOnRing(RankCtx& R, uint32_t slot, hipStream_t st, Launch launch)
 {
+	unsigned int* counter = R.qRing.ptr + slot;
+	HIP_OK(hipMemsetAsync(counter, 0, sizeof(unsigned int), st));
+	if (!launch(counter)) return false;
+	HIP_OK(hipGetLastError());
 	HIP_OK(hipEventRecord(R.qRingEv[slot], st));
 	R.qRingUsed[slot] = true;
 	R.qRingNext = (slot + 1u) % RL_QUERY_RING;
 	return true;
 }
-// enough workgroups to fill the device once (the waves take their work from a counter: rl_k_query.inl, rl_k_radiance.inl); 0: the occupancy query failed (logged)
-static uint64_t FillingGrid(RankCtx& R, const void* kernel, uint64_t n)
+// Enough workgroups to fill the device once (the waves take their work from a counter: rl_k_query.inl, rl_k_radiance.inl), n jobs at most a lane each; 0: refused
+// or failed (logged).  A kernel without dynamic LDS is asked for its occupancy once; with `ldsBytes` of it the answer depends on the call (`api`), which is
+// refused when no workgroup fits.
+static uint64_t FillingGrid(RankCtx& R, const void* kernel, uint64_t n, size_t ldsBytes = 0, const char* api = "")
 {
-	const int blocksPerCU = OccupancyOf(R, kernel);
-	if (blocksPerCU < 0) return 0;
-	return std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)R.numCUs * (uint64_t)std::max(1, blocksPerCU), (n + RL_BLOCK - 1) / RL_BLOCK));
+	int blocksPerCU = 0;
+	if (!ldsBytes) {
+		blocksPerCU = OccupancyOf(R, kernel);
+		if (blocksPerCU < 0) return 0;
+		blocksPerCU = std::max(1, blocksPerCU);
+	} else {
+		HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, kernel, RL_BLOCK, ldsBytes));
+		if (blocksPerCU < 1) { Log("%s: no workgroup of the kernel fits a compute unit with %zu bytes of list", api, ldsBytes); return 0; }
+	}
+	return std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)R.numCUs * (uint64_t)blocksPerCU, (n + RL_BLOCK - 1) / RL_BLOCK));
 }
 // A synchronous call on `st`, around its launch: the counters cleared and the first event in front of the kernel ...
 static bool BeginSync(RankCtx& R, hipStream_t st)
@@ -172,7 +233,11 @@ static bool BeginSync(RankCtx& R, hipStream_t st)
 	return true;
 }
 // ... and behind it the second event, the counters and a host call's results (`back`: those with a host address) on their way to the host, the one wait, the numbers
-struct CopyBack { void* host; const void* dev; size_t bytes; };
+struct CopyBack {
+	void* host; const void* dev; size_t bytes;
+	CopyBack(void* host_, const void* dev_, size_t bytes_) : host(host_), dev(dev_), bytes(bytes_) {}
+	CopyBack(const QueryOut& o, bool hostMem) : host(hostMem && o.bytes ? o.user : nullptr), dev(o.dev), bytes(o.bytes) {}   // (only an output the caller gave)
+};
 static bool FinishSync(RankCtx& R, hipStream_t st, std::initializer_list<CopyBack> back, std::chrono::steady_clock::time_point t0, RaylibAMDStats& stats)
 {
 	HIP_OK(hipEventRecord(R.qEv[1], st));
@@ -189,10 +254,10 @@ static bool FinishSync(RankCtx& R, hipStream_t st, std::initializer_list<CopyBac
 	return true;
 }
 
-// What the ray queries, the multi-hit queries and the nearest-point queries do between the refusals of their pointers and their first enqueue: the scene on
-// the device (which orders the call behind a move and behind multi-rank frames in flight), the plan's tree and, where the call writes export indices, the slot
-// table; the stream; the ring's next counter; a synchronous call's counter block; the stats' header.
-struct QueryCall { DeviceSceneCopy* Cp = nullptr; hipStream_t st = nullptr; bool sync = false; uint32_t slot = 0; unsigned int* counter = nullptr; };
+// What a query and a distance-field bake do between the refusals of their pointers and their first enqueue: the scene on the device (which orders the call
+// behind a move and behind multi-rank frames in flight), the plan's tree and, where the call writes export indices, the slot table; the stream; the ring's next
+// counter; a synchronous call's counter block; the stats' header.
+struct QueryCall { DeviceSceneCopy* Cp = nullptr; hipStream_t st = nullptr; bool sync = false; uint32_t slot = 0; };
 static bool BeginQueryCall(Scene& sc, RankCtx& R, const QueryPlan& plan, bool wantSlotIndex, void* stream, QueryCall& U, RaylibAMDStats& stats)
 {
 	if (!UploadScene(sc)) return false;
@@ -202,199 +267,170 @@ static bool BeginQueryCall(Scene& sc, RankCtx& R, const QueryPlan& plan, bool wa
 	U.st = stream ? (hipStream_t)stream : R.stream;
 	U.sync = !stream;
 	if (!TakeRingCounter(R, U.slot)) return false;
-	U.counter = R.qRing.ptr + U.slot;
 	if (U.sync && !EnsureSyncStats(R)) return false;
 	StatsHeader(stats, plan, sc);
 	return true;
 }
 
+// ---- the queries: one call, described by data ----
+// What an entry says of its call.  It is made first in the entry: the clock starts and the runtime lock is taken there, so the entry plans under the lock.
+// api / apiDevice: the entry's names in the log, `what` its input records'; recordBytes: 32 (rays), 16 (points) or 48 (triangles); out: the outputs in the
+// order of the kernel's arguments; slotIndex / exportSlot: the call needs that table of the scene's on the device; ldsBytes: the launch's dynamic LDS.
+struct QueryDesc {
+	const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+	const std::lock_guard<std::mutex> lock{ Rt().lock };
+	const char *api, *apiDevice, *what;
+	const void* in; size_t recordBytes; int32_t n; bool hostMem; void* stream;
+	QueryPlan plan;
+	QueryOut out[3];
+	bool slotIndex = false, exportSlot = false;
+	const void* kernel = nullptr; size_t ldsBytes = 0;
+	QueryDesc(const char* api_, const char* apiDevice_, const char* what_, const void* in_, size_t recordBytes_, int32_t n_, bool hostMem_, void* stream_)
+		: api(api_), apiDevice(apiDevice_), what(what_), in(in_), recordBytes(recordBytes_), n(n_), hostMem(hostMem_), stream(stream_) {}
+};
+// what the entry's launch gets: the scene, the input and the outputs on the device (null: not written), the work counter, a synchronous call's counter block
+// (else null), the grid and the stream
+struct QueryLaunch {
+	const DSceneView& view; const int32_t* slotIndex; const int32_t* exportSlot;
+	const float4* in; void* out[3];
+	unsigned int* counter; unsigned long long* stats;
+	dim3 grid; hipStream_t st;
+};
+// The call.  The refusals -- the plan's, then a device call's pointers' -- come before the scene is touched; an empty call still brings the scene, the plan's
+// tree and the tables to the device and fills the stats' header; every buffer is grown before anything is enqueued; the input of a host call is copied on the
+// call's stream; a synchronous call's event pair brackets the kernel alone (the counter is cleared in front of it); the outputs of a host call are copied back
+// where the caller gave them.
+template <typename Launch>
+static bool RunQuery(Scene& sc, QueryDesc& D, RaylibAMDStats& stats, Launch launch)
+{
+	if (!EnsureRuntime()) return false;
+	RankCtx& R = Rank0();
+	HIP_OK(hipSetDevice(R.device));
+	if (!D.plan.ok) { Log("%s: BVH depth %u exceeds the traversal stack (64)", D.api, sc.bvh.depth); return false; }
+	if (!D.hostMem && D.n > 0 && !DevicePointersOk(D.apiDevice, D.what, R.device, D.in, D.out, 3)) return false;
+	QueryCall U;
+	if (!BeginQueryCall(sc, R, D.plan, D.slotIndex, D.stream, U, stats)) return false;
+	if (D.exportSlot && !EnsureExportSlot(U.Cp, sc)) return false;
+	if (D.n == 0) return true;
+	const hipStream_t st = U.st;
+	const size_t inBytes = (size_t)D.n * D.recordBytes;
+	if (!StageOutputs(R, D.out, 3, D.hostMem)) return false;
+	if (D.hostMem) {
+		if (!R.qRays.Grow(inBytes)) return false;
+		HIP_OK(hipMemcpyAsync(R.qRays.ptr, D.in, inBytes, hipMemcpyHostToDevice, st));
+	}
+	const uint32_t blocks = (uint32_t)FillingGrid(R, D.kernel, (uint64_t)D.n, D.ldsBytes, D.api);
+	if (!blocks) return false;
+	const bool launched = LaunchOnRing(R, U.slot, st, [&](unsigned int* counter) -> bool {
+		if (U.sync && !BeginSync(R, st)) return false;
+		launch(QueryLaunch{ U.Cp->view, U.Cp->slotIndex.ptr, U.Cp->exportSlot.ptr, D.hostMem ? R.qRays.ptr : (const float4*)D.in, { D.out[0].dev, D.out[1].dev, D.out[2].dev },
+		                    counter, U.sync ? R.qStats.ptr : nullptr, dim3(blocks), st });
+		return true;
+	});
+	if (!launched || !U.sync) return launched;
+	return FinishSync(R, st, { CopyBack(D.out[0], D.hostMem), CopyBack(D.out[1], D.hostMem), CopyBack(D.out[2], D.hostMem) }, D.t0, stats);
+}
+
 bool DeviceTraceRays(Scene& sc, int32_t kind, const void* rays, int32_t n, float rayTime, void* out, int32_t* outPrim, bool hostMem, void* stream,
                      RaylibAMDStats& stats)
 {
-	const auto t0 = std::chrono::steady_clock::now();
-	std::lock_guard<std::mutex> lk(Rt().lock);
-	if (!EnsureRuntime()) return false;
-	RankCtx& R = Rank0();
-	HIP_OK(hipSetDevice(R.device));
-	const QueryPlan plan = PlanQuery(sc, kind, ReadRenderKnobs());
-	if (!plan.ok) { Log("RaylibAMD_TraceRays: BVH depth %u exceeds the traversal stack (64)", sc.bvh.depth); return false; }
-	const size_t outBytes = (size_t)n * (kind == RAYLIB_AMD_QUERY_ANY ? sizeof(uint32_t) : kind == RAYLIB_AMD_QUERY_CLOSEST ? sizeof(DQueryHit) : sizeof(DHitOut));
-	if (!hostMem && n > 0 && !DevicePointersOk("RaylibAMD_TraceRaysDevice", "rays", R.device, rays, out, kind == RAYLIB_AMD_QUERY_CLOSEST ? 15u : 3u, outPrim, kind == RAYLIB_AMD_QUERY_SURFACE)) return false;
-	const bool wantPrim = kind == RAYLIB_AMD_QUERY_CLOSEST || (kind == RAYLIB_AMD_QUERY_SURFACE && outPrim);
-	QueryCall U;
-	if (!BeginQueryCall(sc, R, plan, wantPrim, stream, U, stats)) return false;
-	DeviceSceneCopy* Cp = U.Cp; const hipStream_t st = U.st; const bool sync = U.sync; const uint32_t slot = U.slot; unsigned int* counter = U.counter;
-	if (n == 0) return true;
-	const float4* dRays = (const float4*)rays; void* dOut = out; int32_t* dPrim = (kind == RAYLIB_AMD_QUERY_SURFACE) ? outPrim : nullptr;
-	if (hostMem) {
-		if (dPrim && !R.qPrim.Grow((size_t)n * sizeof(int32_t))) return false;
-		if (!StageRays(R, rays, n, outBytes, st)) return false;
-		dRays = R.qRays.ptr; dOut = R.qOut.ptr; if (dPrim) dPrim = R.qPrim.ptr;
-	}
-	const QueryKernel kernel = kind == RAYLIB_AMD_QUERY_ANY ? QueryKernelOfKind<RL_QK_ANY>(plan) : kind == RAYLIB_AMD_QUERY_CLOSEST ? QueryKernelOfKind<RL_QK_CLOSEST>(plan)
-	                         : QueryKernelOfKind<RL_QK_SURFACE>(plan);
-	const uint32_t blocks = (uint32_t)FillingGrid(R, (const void*)kernel, (uint64_t)n);
-	if (!blocks) return false;
-	const DSceneView view = Cp->view;
-	HIP_OK(hipMemsetAsync(counter, 0, sizeof(unsigned int), st));
-	if (sync && !BeginSync(R, st)) return false;
-	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RL_BLOCK), 0, st, view, dRays, (uint32_t)n, rayTime, dOut, dPrim, Cp->slotIndex.ptr, counter, sync ? R.qStats.ptr : nullptr);
-	HIP_OK(hipGetLastError());
-	if (!ReleaseRingCounter(R, slot, st)) return false;
-	if (!sync) return true;
-	return FinishSync(R, st, { { hostMem ? out : nullptr, dOut, outBytes }, { hostMem && dPrim ? outPrim : nullptr, dPrim, (size_t)n * sizeof(int32_t) } }, t0, stats);
+	QueryDesc D("RaylibAMD_TraceRays", "RaylibAMD_TraceRaysDevice", "rays", rays, sizeof(RaylibAMDRay), n, hostMem, stream);
+	D.plan = PlanQuery(sc, kind, ReadRenderKnobs());
+	const bool closest = kind == RAYLIB_AMD_QUERY_CLOSEST, surface = kind == RAYLIB_AMD_QUERY_SURFACE;
+	const QueryKernel kernel = surface ? QueryKernelOfKind<RL_QK_SURFACE>(D.plan) : closest ? QueryKernelOfKind<RL_QK_CLOSEST>(D.plan) : QueryKernelOfKind<RL_QK_ANY>(D.plan);
+	D.kernel = (const void*)kernel;
+	D.out[0] = { out, (size_t)n * (surface ? sizeof(DHitOut) : closest ? sizeof(DQueryHit) : sizeof(uint32_t)), closest ? 15u : 3u, &RankCtx::qOut };
+	D.out[1] = { outPrim, surface && outPrim ? (size_t)n * sizeof(int32_t) : 0, 3u, &RankCtx::qPrim };   // (written by SURFACE alone)
+	D.slotIndex = closest || (surface && outPrim);
+	return RunQuery(sc, D, stats, [&](const QueryLaunch& L) {
+		hipLaunchKernelGGL(kernel, L.grid, dim3(RL_BLOCK), 0, L.st, L.view, L.in, (uint32_t)n, rayTime, L.out[0], (int32_t*)L.out[1], L.slotIndex, L.counter, L.stats);
+	});
 }
 
-// An ordered multi-hit call (RaylibAMD_TraceRaysAll) is a ray query's call with another plan, kernel and output size: rows of maxHits records and, when asked
-// for, a count per ray; the launch carries the lanes' lists as dynamic LDS (2 * maxHits * RL_BLOCK words), which its grid's occupancy accounts for.
-typedef void (*QueryAllKernel)(const DSceneView, const float4*, uint32_t, uint32_t, float4*, uint32_t*, const int32_t*, unsigned int*, unsigned long long*);
-template <bool COUNT>
-static QueryAllKernel QueryAllKernelOf(const QueryPlan& p)
-{
-	if (p.tree == TREE_WIDE8) return (QueryAllKernel)k_query_all<8, 2 * RL_POOL8_MAXLEVELS, COUNT>;
-	return p.stack <= 32 ? (QueryAllKernel)k_query_all<2, 32, COUNT> : (QueryAllKernel)k_query_all<2, 64, COUNT>;
-}
-static_assert(RAYLIB_AMD_MAX_HITS == RL_MAX_HITS, "multi-hit capacity");
+// An ordered multi-hit call: rows of maxHits records and, when asked for, a count per ray (staged through qPrim); the launch carries the lanes' lists as
+// dynamic LDS (2 * maxHits * RL_BLOCK words), which its grid's occupancy accounts for.
 bool DeviceTraceRaysAll(Scene& sc, const void* rays, int32_t n, int32_t maxHits, void* outHits, uint32_t* outCount, bool hostMem, void* stream, RaylibAMDStats& stats)
 {
-	const auto t0 = std::chrono::steady_clock::now();
-	std::lock_guard<std::mutex> lk(Rt().lock);
-	if (!EnsureRuntime()) return false;
-	RankCtx& R = Rank0();
-	HIP_OK(hipSetDevice(R.device));
-	const QueryPlan plan = PlanQueryAll(sc, ReadRenderKnobs());
-	if (!plan.ok) { Log("RaylibAMD_TraceRaysAll: BVH depth %u exceeds the traversal stack (64)", sc.bvh.depth); return false; }
-	const size_t hitBytes = (size_t)n * (size_t)maxHits * sizeof(DQueryHit), countBytes = outCount ? (size_t)n * sizeof(uint32_t) : 0;
-	if (!hostMem && n > 0 && !DevicePointersOk("RaylibAMD_TraceRaysAllDevice", "rays", R.device, rays, outHits, 15u, (const int32_t*)outCount, outCount != nullptr)) return false;
-	QueryCall U;
-	if (!BeginQueryCall(sc, R, plan, true, stream, U, stats)) return false;
-	if (n == 0) return true;
-	const hipStream_t st = U.st;
-	const float4* dRays = (const float4*)rays; float4* dHits = (float4*)outHits; uint32_t* dCount = outCount;
-	if (hostMem) {
-		if (outCount && !R.qPrim.Grow((size_t)n * sizeof(int32_t))) return false;
-		if (!StageRays(R, rays, n, hitBytes, st)) return false;
-		dRays = R.qRays.ptr; dHits = (float4*)R.qOut.ptr; if (outCount) dCount = (uint32_t*)R.qPrim.ptr;
-	}
-	const QueryAllKernel kernel = outCount ? QueryAllKernelOf<true>(plan) : QueryAllKernelOf<false>(plan);
-	const size_t listBytes = 2u * (size_t)maxHits * RL_BLOCK * sizeof(uint32_t);
-	int blocksPerCU = 0;
-	HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, kernel, RL_BLOCK, listBytes));
-	if (blocksPerCU < 1) { Log("RaylibAMD_TraceRaysAll: no workgroup of the kernel fits a compute unit with %zu bytes of list", listBytes); return false; }
-	const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)R.numCUs * (uint64_t)blocksPerCU, ((uint64_t)n + RL_BLOCK - 1) / RL_BLOCK));
-	const DSceneView view = U.Cp->view;
-	HIP_OK(hipMemsetAsync(U.counter, 0, sizeof(unsigned int), st));
-	if (U.sync && !BeginSync(R, st)) return false;
-	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RL_BLOCK), (uint32_t)listBytes, st, view, dRays, (uint32_t)n, (uint32_t)maxHits, dHits, dCount, (const int32_t*)U.Cp->slotIndex.ptr, U.counter,
-	                   U.sync ? R.qStats.ptr : nullptr);
-	HIP_OK(hipGetLastError());
-	if (!ReleaseRingCounter(R, U.slot, st)) return false;
-	if (!U.sync) return true;
-	return FinishSync(R, st, { { hostMem ? outHits : nullptr, dHits, hitBytes }, { hostMem ? (void*)outCount : nullptr, dCount, countBytes } }, t0, stats);
+	QueryDesc D("RaylibAMD_TraceRaysAll", "RaylibAMD_TraceRaysAllDevice", "rays", rays, sizeof(RaylibAMDRay), n, hostMem, stream);
+	D.plan = PlanQueryAll(sc, ReadRenderKnobs());
+	const QueryAllKernel kernel = outCount ? QueryAllKernelOf<true>(D.plan) : QueryAllKernelOf<false>(D.plan);
+	D.kernel = (const void*)kernel;
+	D.ldsBytes = 2u * (size_t)maxHits * RL_BLOCK * sizeof(uint32_t);
+	D.out[0] = { outHits, (size_t)n * (size_t)maxHits * sizeof(DQueryHit), 15u, &RankCtx::qOut };
+	D.out[1] = { outCount, outCount ? (size_t)n * sizeof(uint32_t) : 0, 3u, &RankCtx::qPrim };
+	D.slotIndex = true;
+	return RunQuery(sc, D, stats, [&](const QueryLaunch& L) {
+		hipLaunchKernelGGL(kernel, L.grid, dim3(RL_BLOCK), (uint32_t)D.ldsBytes, L.st, L.view, L.in, (uint32_t)n, (uint32_t)maxHits, (float4*)L.out[0], (uint32_t*)L.out[1], L.slotIndex, L.counter,
+		                   L.stats);
+	});
 }
 
-// A nearest-point call is a ray query's call with another plan and kernel: the same refusals of a device call's pointers, staging buffers, counter ring,
-// synchronous tail, and the same order behind a move (UploadScene settles it) and behind frames in flight (rank 0's stream, or the caller's behind the uploads).
+// A nearest-point call: 16-byte records in, a word (WITHIN) or a record (CLOSEST) per point out.
 bool DeviceNearestPoints(Scene& sc, int32_t kind, const void* points, int32_t n, void* out, bool hostMem, void* stream, RaylibAMDStats& stats)
 {
-	const auto t0 = std::chrono::steady_clock::now();
-	std::lock_guard<std::mutex> lk(Rt().lock);
-	if (!EnsureRuntime()) return false;
-	RankCtx& R = Rank0();
-	HIP_OK(hipSetDevice(R.device));
-	const QueryPlan plan = PlanNearest(sc, kind, ReadRenderKnobs());
-	if (!plan.ok) { Log("RaylibAMD_NearestPoints: BVH depth %u exceeds the traversal stack (64)", sc.bvh.depth); return false; }
+	QueryDesc D("RaylibAMD_NearestPoints", "RaylibAMD_NearestPointsDevice", "points", points, sizeof(RaylibAMDNearestQuery), n, hostMem, stream);
+	D.plan = PlanNearest(sc, kind, ReadRenderKnobs());
 	const bool closest = kind == RAYLIB_AMD_NEAREST_CLOSEST;
-	const size_t outBytes = (size_t)n * (closest ? sizeof(DNearestHit) : sizeof(uint32_t));
-	if (!hostMem && n > 0 && !DevicePointersOk("RaylibAMD_NearestPointsDevice", "points", R.device, points, out, closest ? 15u : 3u, nullptr, false)) return false;
-	QueryCall U;
-	if (!BeginQueryCall(sc, R, plan, closest, stream, U, stats)) return false;
-	DeviceSceneCopy* Cp = U.Cp; const hipStream_t st = U.st; const bool sync = U.sync; const uint32_t slot = U.slot; unsigned int* counter = U.counter;
-	if (n == 0) return true;
-	const float4* dPoints = (const float4*)points; void* dOut = out;
-	if (hostMem) {
-		if (!StageRays(R, points, n, outBytes, st, sizeof(RaylibAMDNearestQuery))) return false;
-		dPoints = R.qRays.ptr; dOut = R.qOut.ptr;
-	}
-	const NearestKernel kernel = closest ? NearestKernelOfKind<RL_NK_CLOSEST>(plan) : NearestKernelOfKind<RL_NK_WITHIN>(plan);
-	const uint32_t blocks = (uint32_t)FillingGrid(R, (const void*)kernel, (uint64_t)n);
-	if (!blocks) return false;
-	const DSceneView view = Cp->view;
-	HIP_OK(hipMemsetAsync(counter, 0, sizeof(unsigned int), st));
-	if (sync && !BeginSync(R, st)) return false;
-	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RL_BLOCK), 0, st, view, dPoints, (uint32_t)n, dOut, Cp->slotIndex.ptr, counter, sync ? R.qStats.ptr : nullptr);
-	HIP_OK(hipGetLastError());
-	if (!ReleaseRingCounter(R, slot, st)) return false;
-	if (!sync) return true;
-	return FinishSync(R, st, { { hostMem ? out : nullptr, dOut, outBytes } }, t0, stats);
+	const NearestKernel kernel = closest ? NearestKernelOfKind<RL_NK_CLOSEST>(D.plan) : NearestKernelOfKind<RL_NK_WITHIN>(D.plan);
+	D.kernel = (const void*)kernel;
+	D.out[0] = { out, (size_t)n * (closest ? sizeof(DNearestHit) : sizeof(uint32_t)), closest ? 15u : 3u, &RankCtx::qOut };
+	D.slotIndex = closest;
+	return RunQuery(sc, D, stats, [&](const QueryLaunch& L) {
+		hipLaunchKernelGGL(kernel, L.grid, dim3(RL_BLOCK), 0, L.st, L.view, L.in, (uint32_t)n, L.out[0], L.slotIndex, L.counter, L.stats);
+	});
 }
 
-// A K-nearest call (RaylibAMD_NearestPointsAll) is a nearest-point call with the multi-hit call's outputs: rows of maxHits records and, when asked for, a count
-// per point (staged through qPrim); the launch carries the lanes' lists as dynamic LDS (2 * maxHits * RL_BLOCK words) beside the instance's stack and packed
-// distances (48 KB or 96 KB), which its grid's occupancy accounts for.
-typedef void (*NearestAllKernel)(const DSceneView, const float4*, uint32_t, uint32_t, float4*, uint32_t*, const int32_t*, unsigned int*, unsigned long long*);
-template <bool COUNT>
-static NearestAllKernel NearestAllKernelOf(const QueryPlan& p)
-{
-	if (p.tree == TREE_GRID4) return p.stack <= 32 ? (NearestAllKernel)k_nearest_all<4, 32, COUNT> : (NearestAllKernel)k_nearest_all<4, 64, COUNT>;
-	return p.stack <= 32 ? (NearestAllKernel)k_nearest_all<2, 32, COUNT> : (NearestAllKernel)k_nearest_all<2, 64, COUNT>;
-}
-static_assert(RAYLIB_AMD_MAX_NEAREST == RL_MAX_NEAREST, "K-nearest capacity");
+// A K-nearest call: a nearest-point call's input with the multi-hit call's outputs; the lanes' lists (2 * maxHits * RL_BLOCK words of dynamic LDS) lie beside
+// the instance's stack and packed distances (48 KB or 96 KB), which its grid's occupancy accounts for.
 bool DeviceNearestPointsAll(Scene& sc, const void* points, int32_t n, int32_t maxHits, void* outHits, uint32_t* outCount, bool hostMem, void* stream, RaylibAMDStats& stats)
 {
-	const auto t0 = std::chrono::steady_clock::now();
-	std::lock_guard<std::mutex> lk(Rt().lock);
-	if (!EnsureRuntime()) return false;
-	RankCtx& R = Rank0();
-	HIP_OK(hipSetDevice(R.device));
-	const QueryPlan plan = PlanNearestAll(sc, ReadRenderKnobs());
-	if (!plan.ok) { Log("RaylibAMD_NearestPointsAll: BVH depth %u exceeds the traversal stack (64)", sc.bvh.depth); return false; }
-	const size_t hitBytes = (size_t)n * (size_t)maxHits * sizeof(DNearestHit), countBytes = outCount ? (size_t)n * sizeof(uint32_t) : 0;
-	if (!hostMem && n > 0 && !DevicePointersOk("RaylibAMD_NearestPointsAllDevice", "points", R.device, points, outHits, 15u, (const int32_t*)outCount, outCount != nullptr)) return false;
-	QueryCall U;
-	if (!BeginQueryCall(sc, R, plan, true, stream, U, stats)) return false;
-	if (n == 0) return true;
-	const hipStream_t st = U.st;
-	const float4* dPoints = (const float4*)points; float4* dHits = (float4*)outHits; uint32_t* dCount = outCount;
-	if (hostMem) {
-		if (outCount && !R.qPrim.Grow((size_t)n * sizeof(int32_t))) return false;
-		if (!StageRays(R, points, n, hitBytes, st, sizeof(RaylibAMDNearestQuery))) return false;
-		dPoints = R.qRays.ptr; dHits = (float4*)R.qOut.ptr; if (outCount) dCount = (uint32_t*)R.qPrim.ptr;
-	}
-	const NearestAllKernel kernel = outCount ? NearestAllKernelOf<true>(plan) : NearestAllKernelOf<false>(plan);
-	const size_t listBytes = 2u * (size_t)maxHits * RL_BLOCK * sizeof(uint32_t);
-	int blocksPerCU = 0;
-	HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, kernel, RL_BLOCK, listBytes));
-	if (blocksPerCU < 1) { Log("RaylibAMD_NearestPointsAll: no workgroup of the kernel fits a compute unit with %zu bytes of list", listBytes); return false; }
-	const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)R.numCUs * (uint64_t)blocksPerCU, ((uint64_t)n + RL_BLOCK - 1) / RL_BLOCK));
-	const DSceneView view = U.Cp->view;
-	HIP_OK(hipMemsetAsync(U.counter, 0, sizeof(unsigned int), st));
-	if (U.sync && !BeginSync(R, st)) return false;
-	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RL_BLOCK), (uint32_t)listBytes, st, view, dPoints, (uint32_t)n, (uint32_t)maxHits, dHits, dCount, (const int32_t*)U.Cp->slotIndex.ptr, U.counter,
-	                   U.sync ? R.qStats.ptr : nullptr);
-	HIP_OK(hipGetLastError());
-	if (!ReleaseRingCounter(R, U.slot, st)) return false;
-	if (!U.sync) return true;
-	return FinishSync(R, st, { { hostMem ? outHits : nullptr, dHits, hitBytes }, { hostMem ? (void*)outCount : nullptr, dCount, countBytes } }, t0, stats);
+	QueryDesc D("RaylibAMD_NearestPointsAll", "RaylibAMD_NearestPointsAllDevice", "points", points, sizeof(RaylibAMDNearestQuery), n, hostMem, stream);
+	D.plan = PlanNearestAll(sc, ReadRenderKnobs());
+	const NearestAllKernel kernel = outCount ? NearestAllKernelOf<true>(D.plan) : NearestAllKernelOf<false>(D.plan);
+	D.kernel = (const void*)kernel;
+	D.ldsBytes = 2u * (size_t)maxHits * RL_BLOCK * sizeof(uint32_t);
+	D.out[0] = { outHits, (size_t)n * (size_t)maxHits * sizeof(DNearestHit), 15u, &RankCtx::qOut };
+	D.out[1] = { outCount, outCount ? (size_t)n * sizeof(uint32_t) : 0, 3u, &RankCtx::qPrim };
+	D.slotIndex = true;
+	return RunQuery(sc, D, stats, [&](const QueryLaunch& L) {
+		hipLaunchKernelGGL(kernel, L.grid, dim3(RL_BLOCK), (uint32_t)D.ldsBytes, L.st, L.view, L.in, (uint32_t)n, (uint32_t)maxHits, (float4*)L.out[0], (uint32_t*)L.out[1], L.slotIndex, L.counter,
+		                   L.stats);
+	});
+}
+
+// A triangle-overlap call: 48-byte records in; a word per query (ANY), or rows of maxHits indices and, when asked for, a count per query (LIST), whose launch
+// carries the lanes' lists as dynamic LDS (maxHits * RL_BLOCK words).  `contacts` (RaylibAMD_OverlapContacts): kind is LIST, the kernel is the contacts
+// instance of the same plan, which reads a listed triangle again through exportSlot, and a third output, n * maxHits records of 32 bytes (two float4 stores
+// each), is staged through qContact.
+bool DeviceOverlapTriangles(Scene& sc, int32_t kind, uint32_t flags, const void* queries, int32_t n, int32_t maxHits, void* out, uint32_t* outCount, bool hostMem, void* stream,
+                            RaylibAMDStats& stats, void* outContact, bool contacts)
+{
+	QueryDesc D("RaylibAMD_OverlapTriangles", contacts ? "RaylibAMD_OverlapContactsDevice" : "RaylibAMD_OverlapTrianglesDevice", "queries", queries, sizeof(RaylibAMDOverlapQuery), n,
+	            hostMem, stream);
+	D.plan = PlanOverlap(sc, kind, ReadRenderKnobs());
+	const bool list = kind == RAYLIB_AMD_OVERLAP_LIST;
+	const OverlapKernel kernel = list ? OverlapKernelOfKind<RL_OK_LIST>(D.plan) : OverlapKernelOfKind<RL_OK_ANY>(D.plan);
+	const OverlapContactsKernel contactsKernel = OverlapContactsKernelOf(D.plan);
+	D.kernel = contacts ? (const void*)contactsKernel : (const void*)kernel;
+	D.ldsBytes = list ? (size_t)maxHits * RL_BLOCK * sizeof(uint32_t) : 0;
+	D.out[0] = { out, list ? (size_t)n * (size_t)maxHits * sizeof(int32_t) : (size_t)n * sizeof(uint32_t), 3u, &RankCtx::qOut };
+	D.out[1] = { outCount, outCount ? (size_t)n * sizeof(uint32_t) : 0, 3u, &RankCtx::qPrim };
+	if (contacts) D.out[2] = { outContact, (size_t)n * (size_t)maxHits * sizeof(RaylibAMDContact), 15u, &RankCtx::qContact };
+	D.slotIndex = list; D.exportSlot = contacts;
+	return RunQuery(sc, D, stats, [&](const QueryLaunch& L) {
+		if (contacts)
+			hipLaunchKernelGGL(contactsKernel, L.grid, dim3(RL_BLOCK), (uint32_t)D.ldsBytes, L.st, L.view, L.in, (uint32_t)n, flags, (uint32_t)maxHits, L.out[0], (uint32_t*)L.out[1], L.slotIndex,
+			                   L.counter, L.stats, (float4*)L.out[2], L.exportSlot);
+		else
+			hipLaunchKernelGGL(kernel, L.grid, dim3(RL_BLOCK), (uint32_t)D.ldsBytes, L.st, L.view, L.in, (uint32_t)n, flags, (uint32_t)(list ? maxHits : 0), L.out[0], (uint32_t*)L.out[1], L.slotIndex,
+			                   L.counter, L.stats);
+	});
 }
 
 // A distance-field bake (RaylibAMD_BakeDistanceField) is a nearest-point call without points and a multi-hit call without rays: up to three launches on one
 // stream -- k_sdf_rows into the zeroed bit volumes and k_sdf_parity over them (a signed bake), then k_sdf_dist -- each walk on its own plan's tree, each with a
-// ring counter of its own.  The volumes are the rank's (sdfBits), ordered between bakes by sdfEv as the radiance scratch is by radEv.  A host call's outputs
-// go through qOut and qPrim.
-typedef void (*SdfRowsKernel)(const DSceneView, const DSdfGrid, uint32_t, uint32_t*, unsigned int*, unsigned long long*);
-static SdfRowsKernel SdfRowsKernelOf(const QueryPlan& p)
-{
-	if (p.tree == TREE_WIDE8) return (SdfRowsKernel)k_sdf_rows<8, 2 * RL_POOL8_MAXLEVELS>;
-	return p.stack <= 32 ? (SdfRowsKernel)k_sdf_rows<2, 32> : (SdfRowsKernel)k_sdf_rows<2, 64>;
-}
-typedef void (*SdfDistKernel)(const DSceneView, const DSdfGrid, float*, int32_t*, const uint32_t*, const int32_t*, unsigned int*, unsigned long long*);
-template <bool SIGNED>
-static SdfDistKernel SdfDistKernelOf(const QueryPlan& p)
-{
-	if (p.tree == TREE_GRID4) return p.stack <= 32 ? (SdfDistKernel)k_sdf_dist<4, 32, SIGNED> : (SdfDistKernel)k_sdf_dist<4, 64, SIGNED>;
-	return p.stack <= 32 ? (SdfDistKernel)k_sdf_dist<2, 32, SIGNED> : (SdfDistKernel)k_sdf_dist<2, 64, SIGNED>;
-}
+// ring counter of its own (LaunchOnRing).  The volumes are the rank's (sdfBits), ordered between bakes by sdfEv as the radiance scratch is by radEv.  A host
+// call's outputs go through qOut and qPrim, as a query's.
 bool DeviceBakeDistanceField(Scene& sc, const RaylibAMDDistanceFieldParams& prm, float* outDist, int32_t* outPrim, bool hostMem, void* stream, RaylibAMDStats& stats)
 {
 	const auto t0 = std::chrono::steady_clock::now();
@@ -404,10 +440,6 @@ bool DeviceBakeDistanceField(Scene& sc, const RaylibAMDDistanceFieldParams& prm,
 	HIP_OK(hipSetDevice(R.device));
 	const DistanceFieldPlan plan = PlanDistanceField(sc, ReadRenderKnobs());
 	if (!plan.nearest.ok || !plan.rows.ok) { Log("RaylibAMD_BakeDistanceField: BVH depth %u exceeds the traversal stack (64)", sc.bvh.depth); return false; }
-	if (!hostMem) {
-		if (!OnDevice(outDist, R.device) || (outPrim && !OnDevice(outPrim, R.device))) { Log("RaylibAMD_BakeDistanceFieldDevice: a pointer is not device memory of device %d", R.device); return false; }
-		if ((((uintptr_t)outDist | (uintptr_t)outPrim) & 3u) != 0) { Log("RaylibAMD_BakeDistanceFieldDevice: the output is not 4-byte aligned"); return false; }
-	}
 	// the grid, and the rows and bit volumes of the sign axes
 	DSdfGrid G; memset(&G, 0, sizeof(G));
 	for (int a = 0; a < 3; ++a) { G.origin[a] = prm.origin[a]; G.spacing[a] = prm.spacing[a]; G.dims[a] = (uint32_t)prm.dims[a]; }
@@ -422,17 +454,15 @@ bool DeviceBakeDistanceField(Scene& sc, const RaylibAMDDistanceFieldParams& prm,
 		rows += rowsA; words += rowsA * G.words[a];
 		G.rowEnd[a] = (uint32_t)rows;   // (three axes of at most 2^31 - 1 voxels: at most 2^32 - 1 rows; the launches below are cut at 2^31 - 1)
 	}
+	QueryOut outs[2] = { { outDist, (size_t)voxels * sizeof(float), 3u, &RankCtx::qOut }, { outPrim, outPrim ? (size_t)voxels * sizeof(int32_t) : 0, 3u, &RankCtx::qPrim } };
+	if (!hostMem && !DevicePointersOk("RaylibAMD_BakeDistanceFieldDevice", nullptr, R.device, nullptr, outs, 2)) return false;
 	QueryCall U;
 	if (!BeginQueryCall(sc, R, plan.nearest, true, stream, U, stats)) return false;
 	if (G.axes && !EnsureWideTree(U.Cp, sc, plan.rows.tree)) return false;
 	const hipStream_t st = U.st;
 	if (G.axes && !R.sdfBits.Grow((size_t)words * sizeof(uint32_t))) return false;
 	if (!R.sdfEv) HIP_OK(hipEventCreateWithFlags(&R.sdfEv, hipEventDisableTiming));
-	float* dDist = outDist; int32_t* dPrim = outPrim;
-	if (hostMem) {
-		if (!R.qOut.Grow((size_t)voxels * sizeof(float)) || (outPrim && !R.qPrim.Grow((size_t)voxels * sizeof(int32_t)))) return false;
-		dDist = (float*)R.qOut.ptr; if (outPrim) dPrim = R.qPrim.ptr;
-	}
+	if (!StageOutputs(R, outs, 2, hostMem)) return false;
 	const SdfDistKernel distKernel = G.axes ? SdfDistKernelOf<true>(plan.nearest) : SdfDistKernelOf<false>(plan.nearest);
 	const uint64_t bricks = (uint64_t)((G.dims[0] + 3u) / 4u) * ((G.dims[1] + 3u) / 4u) * ((G.dims[2] + 3u) / 4u);
 	const uint32_t distBlocks = (uint32_t)FillingGrid(R, (const void*)distKernel, bricks * 64u);
@@ -457,79 +487,25 @@ bool DeviceBakeDistanceField(Scene& sc, const RaylibAMDDistanceFieldParams& prm,
 			}
 			const uint32_t blocks = (uint32_t)FillingGrid(R, (const void*)rowsKernel, n);
 			if (!blocks) return false;
-			unsigned int* counter = R.qRing.ptr + slot;
-			HIP_OK(hipMemsetAsync(counter, 0, sizeof(unsigned int), st));
-			hipLaunchKernelGGL(rowsKernel, dim3(blocks), dim3(RL_BLOCK), 0, st, view, L, (uint32_t)n, R.sdfBits.ptr, counter, counters);
-			HIP_OK(hipGetLastError());
-			hipLaunchKernelGGL(k_sdf_parity, dim3((uint32_t)((n + RL_BLOCK - 1) / RL_BLOCK)), dim3(RL_BLOCK), 0, st, L, (uint32_t)n, R.sdfBits.ptr);
-			HIP_OK(hipGetLastError());
-			if (!ReleaseRingCounter(R, slot, st) || !TakeRingCounter(R, slot)) return false;
+			const bool launched = LaunchOnRing(R, slot, st, [&](unsigned int* counter) -> bool {
+				hipLaunchKernelGGL(rowsKernel, dim3(blocks), dim3(RL_BLOCK), 0, st, view, L, (uint32_t)n, R.sdfBits.ptr, counter, counters);
+				HIP_OK(hipGetLastError());
+				hipLaunchKernelGGL(k_sdf_parity, dim3((uint32_t)((n + RL_BLOCK - 1) / RL_BLOCK)), dim3(RL_BLOCK), 0, st, L, (uint32_t)n, R.sdfBits.ptr);
+				return true;
+			});
+			if (!launched || !TakeRingCounter(R, slot)) return false;
 		}
 	}
-	unsigned int* counter = R.qRing.ptr + slot;
-	HIP_OK(hipMemsetAsync(counter, 0, sizeof(unsigned int), st));
-	hipLaunchKernelGGL(distKernel, dim3(distBlocks), dim3(RL_BLOCK), 0, st, view, G, dDist, dPrim, (const uint32_t*)R.sdfBits.ptr, (const int32_t*)U.Cp->slotIndex.ptr, counter, counters);
-	HIP_OK(hipGetLastError());
-	if (!ReleaseRingCounter(R, slot, st)) return false;
+	const bool launched = LaunchOnRing(R, slot, st, [&](unsigned int* counter) -> bool {
+		hipLaunchKernelGGL(distKernel, dim3(distBlocks), dim3(RL_BLOCK), 0, st, view, G, (float*)outs[0].dev, (int32_t*)outs[1].dev, (const uint32_t*)R.sdfBits.ptr,
+		                   (const int32_t*)U.Cp->slotIndex.ptr, counter, counters);
+		return true;
+	});
+	if (!launched) return false;
 	HIP_OK(hipEventRecord(R.sdfEv, st));
 	R.sdfEvUsed = true;
 	if (!U.sync) return true;
-	return FinishSync(R, st, { { hostMem ? outDist : nullptr, dDist, (size_t)voxels * sizeof(float) }, { hostMem && outPrim ? outPrim : nullptr, dPrim, (size_t)voxels * sizeof(int32_t) } }, t0, stats);
-}
-
-// A triangle-overlap call is a nearest-point call with a 48-byte record, rows of maxHits indices and, when asked for, a count per query (staged through qPrim, as
-// the multi-hit call's); a LIST launch carries the lanes' lists as dynamic LDS (maxHits * RL_BLOCK words), which its grid's occupancy accounts for.
-// `contacts` (RaylibAMD_OverlapContacts): kind is LIST, the kernel is the contacts instance of the same plan, and a third output, n * maxHits records of 32
-// bytes, is refused as the rows are (16-byte aligned: two float4 stores each) and staged through qContact.
-bool DeviceOverlapTriangles(Scene& sc, int32_t kind, uint32_t flags, const void* queries, int32_t n, int32_t maxHits, void* out, uint32_t* outCount, bool hostMem, void* stream,
-                            RaylibAMDStats& stats, void* outContact, bool contacts)
-{
-	const auto t0 = std::chrono::steady_clock::now();
-	std::lock_guard<std::mutex> lk(Rt().lock);
-	if (!EnsureRuntime()) return false;
-	RankCtx& R = Rank0();
-	HIP_OK(hipSetDevice(R.device));
-	const QueryPlan plan = PlanOverlap(sc, kind, ReadRenderKnobs());
-	if (!plan.ok) { Log("RaylibAMD_OverlapTriangles: BVH depth %u exceeds the traversal stack (64)", sc.bvh.depth); return false; }
-	const bool list = kind == RAYLIB_AMD_OVERLAP_LIST;
-	const size_t outBytes = list ? (size_t)n * (size_t)maxHits * sizeof(int32_t) : (size_t)n * sizeof(uint32_t), countBytes = outCount ? (size_t)n * sizeof(uint32_t) : 0;
-	const char* api = contacts ? "RaylibAMD_OverlapContactsDevice" : "RaylibAMD_OverlapTrianglesDevice";
-	const size_t contactBytes = contacts ? (size_t)n * (size_t)maxHits * sizeof(RaylibAMDContact) : 0;
-	if (!hostMem && n > 0 && !DevicePointersOk(api, "queries", R.device, queries, out, 3u, (const int32_t*)outCount, outCount != nullptr)) return false;
-	if (!hostMem && n > 0 && contacts && !DevicePointersOk(api, "queries", R.device, queries, outContact, 15u, nullptr, false)) return false;
-	QueryCall U;
-	if (!BeginQueryCall(sc, R, plan, list, stream, U, stats)) return false;
-	if (contacts && !EnsureExportSlot(U.Cp, sc)) return false;
-	if (n == 0) return true;
-	const hipStream_t st = U.st;
-	const float4* dQueries = (const float4*)queries; void* dOut = out; uint32_t* dCount = outCount; float4* dContact = (float4*)outContact;
-	if (hostMem) {
-		if (outCount && !R.qPrim.Grow((size_t)n * sizeof(int32_t))) return false;
-		if (contacts && !R.qContact.Grow(contactBytes)) return false;
-		if (!StageRays(R, queries, n, outBytes, st, sizeof(RaylibAMDOverlapQuery))) return false;
-		dQueries = R.qRays.ptr; dOut = R.qOut.ptr; if (outCount) dCount = (uint32_t*)R.qPrim.ptr;
-		if (contacts) dContact = R.qContact.ptr;
-	}
-	const void* kernel = contacts ? (const void*)OverlapContactsKernelOf(plan) : (const void*)(list ? OverlapKernelOfKind<RL_OK_LIST>(plan) : OverlapKernelOfKind<RL_OK_ANY>(plan));
-	const size_t listBytes = list ? (size_t)maxHits * RL_BLOCK * sizeof(uint32_t) : 0;
-	int blocksPerCU = 0;
-	HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, kernel, RL_BLOCK, listBytes));
-	if (blocksPerCU < 1) { Log("RaylibAMD_OverlapTriangles: no workgroup of the kernel fits a compute unit with %zu bytes of list", listBytes); return false; }
-	const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)R.numCUs * (uint64_t)blocksPerCU, ((uint64_t)n + RL_BLOCK - 1) / RL_BLOCK));
-	const DSceneView view = U.Cp->view;
-	HIP_OK(hipMemsetAsync(U.counter, 0, sizeof(unsigned int), st));
-	if (U.sync && !BeginSync(R, st)) return false;
-	if (contacts)
-		hipLaunchKernelGGL((OverlapContactsKernel)kernel, dim3(blocks), dim3(RL_BLOCK), (uint32_t)listBytes, st, view, dQueries, (uint32_t)n, flags, (uint32_t)maxHits, dOut, dCount,
-		                   (const int32_t*)U.Cp->slotIndex.ptr, U.counter, U.sync ? R.qStats.ptr : nullptr, dContact, (const int32_t*)U.Cp->exportSlot.ptr);
-	else
-		hipLaunchKernelGGL((OverlapKernel)kernel, dim3(blocks), dim3(RL_BLOCK), (uint32_t)listBytes, st, view, dQueries, (uint32_t)n, flags, (uint32_t)(list ? maxHits : 0), dOut, dCount,
-		                   (const int32_t*)U.Cp->slotIndex.ptr, U.counter, U.sync ? R.qStats.ptr : nullptr);
-	HIP_OK(hipGetLastError());
-	if (!ReleaseRingCounter(R, U.slot, st)) return false;
-	if (!U.sync) return true;
-	return FinishSync(R, st, { { hostMem ? out : nullptr, dOut, outBytes }, { hostMem ? (void*)outCount : nullptr, dCount, countBytes },
-	                           { hostMem ? outContact : nullptr, dContact, contactBytes } }, t0, stats);
+	return FinishSync(R, st, { CopyBack(outs[0], hostMem), CopyBack(outs[1], hostMem) }, t0, stats);
 }
 
 // ---- what a radiance call and a gather share ----
@@ -541,7 +517,8 @@ static bool BeginPathCall(const char* api, const char* apiDevice, const char* wh
 {
 	U.plan = PlanRadiance(sc, knobs);
 	if (!U.plan.ok) { Log("%s: BVH depth %u exceeds the traversal stack (64)", api, sc.bvh.depth); return false; }
-	if (!hostMem && n > 0 && !DevicePointersOk(apiDevice, what, R.device, in, out, outAlign, nullptr, false)) return false;
+	const QueryOut result = { const_cast<void*>(out), (size_t)(n > 0), outAlign };   // (written whenever the call has input)
+	if (!hostMem && n > 0 && !DevicePointersOk(apiDevice, what, R.device, in, &result, 1)) return false;
 	if (!UploadScene(sc) || !SyncSky(sc)) return false;
 	U.Cp = sc.device->copy[(size_t)R.devSlot];
 	if (!EnsureWideTree(U.Cp, sc, U.plan.tree)) return false;

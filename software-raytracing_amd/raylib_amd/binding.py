@@ -97,11 +97,72 @@ _QUERY_DTYPES = {QUERY_ANY: np.dtype("u4"), QUERY_CLOSEST: HITT_DTYPE, QUERY_SUR
 _TORCH_WORDS = {QUERY_ANY: 1, QUERY_CLOSEST: 4, QUERY_SURFACE: 11}
 
 
+def _plan(lib, entry, scene, *args):
+    """A RaylibAMD_Plan* entry whose last argument is the plan: (return code, plan dict)."""
+    p = QueryPlan()
+    r = getattr(lib, entry)(scene, *args, C.byref(p))
+    return r, p.as_dict()
+
+
+def _ordered(stream):
+    """The handle of a torch stream for a device entry.  The library reads handle 0 -- torch's default stream -- as its own stream, which is not ordered against
+    torch's: that stream is synchronised first (the inputs may come from a copy just queued there, and the outputs' memory must be ready), and the call is synchronous."""
+    if stream.cuda_stream == 0:
+        stream.synchronize()
+    return C.c_void_p(stream.cuda_stream)
+
+
+def _query(lib, scene, data, cols, entry, specs, pre=(), mid=(), host=False, device=False, records=None, type_error="", host_error=None):
+    """One query call, behind the public wrappers.  data: the input, `cols` float32 columns per record (a NumPy array of dtype `records` is taken as it stands).
+    entry: the host-memory entry's name; entry + "Host" is its oracle and entry + "Device" the device entry, and all three take (scene, *pre, input, n, *mid,
+    *outputs) -- the device entry then the stream.  specs(n): the outputs as (shape, NumPy dtype) pairs, None for one not asked for; a tensor has the shape with
+    the record's 4-byte words as a last axis, int32 (float32 where a third element of the spec is True).
+    A NumPy array goes through the host-memory entry (host=True: the oracle) and NumPy outputs come back; with device=True it is copied to the device, goes through
+    the device entry, and the outputs are copied back.  A float32 torch tensor on the device goes through the device entry on torch.cuda.current_stream() and
+    tensors come back: enqueued on a stream of the caller's, synchronous on torch's default stream (_ordered).  Returns the list of outputs; raises TypeError
+    (type_error; host_error for host=True without a host array) and RuntimeError when the library refuses the call."""
+    if isinstance(data, np.ndarray) and not device:
+        d = np.ascontiguousarray(data)
+        d = d.view(np.uint8).reshape(-1, records.itemsize) if records is not None and d.dtype == records else np.ascontiguousarray(d, np.float32).reshape(-1, cols)
+        n = len(d)
+        outs = [None if s is None else np.zeros(s[0], s[1]) for s in specs(n)]
+        name = entry + "Host" if host else entry
+        if getattr(lib, name)(scene, *pre, d.ctypes.data, n, *mid, *[None if o is None else o.ctypes.data for o in outs]) != 1:
+            raise RuntimeError(name + " refused the query")
+        return outs
+    import torch
+    if host:
+        raise TypeError(host_error or type_error)
+    as_numpy = isinstance(data, np.ndarray)
+    if as_numpy:
+        data = torch.from_numpy(np.ascontiguousarray(data, np.float32).reshape(-1, cols)).cuda()
+    if not (isinstance(data, torch.Tensor) and data.is_cuda and data.dtype == torch.float32):
+        raise TypeError(type_error)
+    d = data.reshape(-1, cols).contiguous()
+    n = d.shape[0]
+    specs = specs(n)
+    outs = []
+    for s in specs:
+        words = 0 if s is None else np.dtype(s[1]).itemsize // 4
+        shape = None if s is None else (s[0] if isinstance(s[0], tuple) else (s[0],)) + ((words,) if words > 1 else ())
+        outs.append(None if s is None else torch.empty(shape, dtype=torch.float32 if len(s) > 2 and s[2] else torch.int32, device=d.device))
+    stream = torch.cuda.current_stream(d.device)
+    if getattr(lib, entry + "Device")(scene, *pre, C.c_void_p(d.data_ptr()), n, *mid, *[None if o is None else C.c_void_p(o.data_ptr()) for o in outs], _ordered(stream)) != 1:
+        raise RuntimeError(entry + "Device refused the query")
+    if as_numpy:
+        stream.synchronize()
+        outs = [None if o is None else o.cpu().numpy().view(s[1]).reshape(s[0]) for o, s in zip(outs, specs)]
+    return outs
+
+
+_RAYS_TYPE_ERROR = "rays: a float32 NumPy array or a float32 torch tensor on the device"
+_POINTS_TYPE_ERROR = "points: a float32 NumPy array, or a float32 torch tensor on the device (host=False)"
+_QUERIES_TYPE_ERROR = "queries: a NumPy array, or a float32 torch tensor on the device (host=False)"
+
+
 def plan_ray_query(lib, scene, kind):
     """RaylibAMD_PlanRayQuery: (return code, plan dict)."""
-    p = QueryPlan()
-    r = lib.RaylibAMD_PlanRayQuery(scene, int(kind), C.byref(p))
-    return r, p.as_dict()
+    return _plan(lib, "RaylibAMD_PlanRayQuery", scene, int(kind))
 
 
 def trace_rays(lib, scene, rays, kind, ray_time=0.0, with_prim=False):
@@ -117,33 +178,9 @@ def trace_rays(lib, scene, rays, kind, ray_time=0.0, with_prim=False):
     kind = int(kind)
     if kind not in _QUERY_DTYPES:
         raise ValueError("unknown query kind %r" % kind)
-    if isinstance(rays, np.ndarray):
-        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
-        n = len(r)
-        out = np.zeros(n, _QUERY_DTYPES[kind])
-        prim = np.zeros(n, np.int32) if (with_prim and kind == QUERY_SURFACE) else None
-        ok = lib.RaylibAMD_TraceRays(scene, kind, r.ctypes.data_as(C.POINTER(Ray)), n, float(ray_time), out.ctypes.data,
-                                     prim.ctypes.data_as(C.POINTER(C.c_int32)) if prim is not None else None)
-        if ok != 1:
-            raise RuntimeError("RaylibAMD_TraceRays refused the query")
-        return (out, prim) if with_prim else out
-    import torch
-    if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.dtype == torch.float32):
-        raise TypeError("rays: a float32 NumPy array or a float32 torch tensor on the device")
-    r = rays.reshape(-1, 8).contiguous()
-    n = r.shape[0]
-    words = _TORCH_WORDS[kind]
-    out = torch.empty((n, words) if words > 1 else (n,), dtype=torch.int32, device=r.device)
-    prim = torch.empty(n, dtype=torch.int32, device=r.device) if (with_prim and kind == QUERY_SURFACE) else None
-    stream = torch.cuda.current_stream(r.device)
-    if stream.cuda_stream == 0:
-        # the library's stream is not ordered against torch's default stream: the rays (r may come from a copy just queued there) and the memory of
-        # out / prim must be ready before the library's stream touches them
-        stream.synchronize()
-    ok = lib.RaylibAMD_TraceRaysDevice(scene, kind, C.cast(C.c_void_p(r.data_ptr()), C.POINTER(Ray)), n, float(ray_time), C.c_void_p(out.data_ptr()),
-                                       C.cast(C.c_void_p(prim.data_ptr()), C.POINTER(C.c_int32)) if prim is not None else None, C.c_void_p(stream.cuda_stream))
-    if ok != 1:
-        raise RuntimeError("RaylibAMD_TraceRaysDevice refused the query")
+    want_prim = with_prim and kind == QUERY_SURFACE
+    out, prim = _query(lib, scene, rays, 8, "RaylibAMD_TraceRays", lambda n: [(n, _QUERY_DTYPES[kind]), (n, np.int32) if want_prim else None],
+                       pre=(kind,), mid=(float(ray_time),), type_error=_RAYS_TYPE_ERROR)
     return (out, prim) if with_prim else out
 
 
@@ -152,9 +189,13 @@ MAX_HITS = 16                                       # RAYLIB_AMD_MAX_HITS
 
 def plan_ray_query_all(lib, scene, max_hits, count=False):
     """RaylibAMD_PlanRayQueryAll: (return code, plan dict)."""
-    p = QueryPlan()
-    r = lib.RaylibAMD_PlanRayQueryAll(scene, int(max_hits), int(bool(count)), C.byref(p))
-    return r, p.as_dict()
+    return _plan(lib, "RaylibAMD_PlanRayQueryAll", scene, int(max_hits), int(bool(count)))
+
+
+def _rows(max_hits, dtype, count, *more):
+    """The outputs of a call that writes rows: (n, max_hits) records, whatever `more` gives per row entry, and the count per input when asked for."""
+    k = max(max_hits, 0)
+    return lambda n: [((n, k), dtype)] + [((n, k),) + m for m in more] + [(n, np.uint32) if count else None]
 
 
 def trace_rays_all(lib, scene, rays, max_hits, count=False, tree=None, device=False, host=False, ray_time=0.0):
@@ -171,41 +212,8 @@ def trace_rays_all(lib, scene, rays, max_hits, count=False, tree=None, device=Fa
     if tree is not None:
         os.environ["RAYLIB_QUERY_TREE"] = str(int(tree))
     try:
-        if isinstance(rays, np.ndarray) and not device:
-            r = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
-            n = len(r)
-            hits = np.zeros((n, max(max_hits, 0)), HITT_DTYPE)
-            counts = np.zeros(n, np.uint32) if count else None
-            name = "RaylibAMD_TraceRaysAllHost" if host else "RaylibAMD_TraceRaysAll"
-            ok = getattr(lib, name)(scene, r.ctypes.data_as(C.POINTER(Ray)), n, float(ray_time), max_hits, C.cast(C.c_void_p(hits.ctypes.data), C.POINTER(HitT)),
-                                    counts.ctypes.data_as(C.POINTER(C.c_uint32)) if count else None)
-            if ok != 1:
-                raise RuntimeError(name + " refused the query")
-            return (hits, counts) if count else hits
-        import torch
-        if host:
-            raise TypeError("host=True takes a NumPy array and no device")
-        as_numpy = isinstance(rays, np.ndarray)
-        if as_numpy:
-            rays = torch.from_numpy(np.ascontiguousarray(rays, np.float32).reshape(-1, 8)).cuda()
-        if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.dtype == torch.float32):
-            raise TypeError("rays: a float32 NumPy array or a float32 torch tensor on the device")
-        r = rays.reshape(-1, 8).contiguous()
-        n = r.shape[0]
-        hits = torch.empty((n, max(max_hits, 0), 4), dtype=torch.int32, device=r.device)
-        counts = torch.empty(n, dtype=torch.int32, device=r.device) if count else None
-        stream = torch.cuda.current_stream(r.device)
-        if stream.cuda_stream == 0:
-            stream.synchronize()   # (the library's stream is not ordered against torch's default stream: trace_rays)
-        ok = lib.RaylibAMD_TraceRaysAllDevice(scene, C.cast(C.c_void_p(r.data_ptr()), C.POINTER(Ray)), n, float(ray_time), max_hits,
-                                              C.cast(C.c_void_p(hits.data_ptr()), C.POINTER(HitT)),
-                                              C.cast(C.c_void_p(counts.data_ptr()), C.POINTER(C.c_uint32)) if count else None, C.c_void_p(stream.cuda_stream))
-        if ok != 1:
-            raise RuntimeError("RaylibAMD_TraceRaysAllDevice refused the query")
-        if as_numpy:
-            stream.synchronize()
-            hits = hits.cpu().numpy().view(HITT_DTYPE).reshape(n, max_hits)
-            counts = counts.cpu().numpy().view(np.uint32) if count else None
+        hits, counts = _query(lib, scene, rays, 8, "RaylibAMD_TraceRaysAll", _rows(max_hits, HITT_DTYPE, count), mid=(float(ray_time), max_hits), host=host, device=device,
+                              type_error=_RAYS_TYPE_ERROR, host_error="host=True takes a NumPy array and no device")
         return (hits, counts) if count else hits
     finally:
         if tree is not None:
@@ -222,9 +230,7 @@ NEAREST_DTYPE = np.dtype([("dist2", "f4"), ("prim", "i4"), ("b1", "f4"), ("b2", 
 
 def plan_nearest(lib, scene, kind):
     """RaylibAMD_PlanNearest: (return code, plan dict)."""
-    p = QueryPlan()
-    r = lib.RaylibAMD_PlanNearest(scene, int(kind), C.byref(p))
-    return r, p.as_dict()
+    return _plan(lib, "RaylibAMD_PlanNearest", scene, int(kind))
 
 
 def nearest_points(lib, scene, points, kind, host=False):
@@ -237,25 +243,8 @@ def nearest_points(lib, scene, points, kind, host=False):
     kind = int(kind)
     if kind not in (NEAREST_WITHIN, NEAREST_CLOSEST):
         raise ValueError("unknown nearest kind %r" % kind)
-    if isinstance(points, np.ndarray):
-        p = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
-        out = np.zeros(len(p), NEAREST_DTYPE if kind == NEAREST_CLOSEST else np.dtype("u4"))
-        name = "RaylibAMD_NearestPointsHost" if host else "RaylibAMD_NearestPoints"
-        if getattr(lib, name)(scene, kind, p.ctypes.data, len(p), out.ctypes.data) != 1:
-            raise RuntimeError(name + " refused the query")
-        return out
-    import torch
-    if host or not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float32):
-        raise TypeError("points: a float32 NumPy array, or a float32 torch tensor on the device (host=False)")
-    p = points.reshape(-1, 4).contiguous()
-    n = p.shape[0]
-    out = torch.empty((n, 4) if kind == NEAREST_CLOSEST else (n,), dtype=torch.int32, device=p.device)
-    stream = torch.cuda.current_stream(p.device)
-    if stream.cuda_stream == 0:
-        stream.synchronize()   # (the library's stream is not ordered against torch's default stream: trace_rays)
-    if lib.RaylibAMD_NearestPointsDevice(scene, kind, C.c_void_p(p.data_ptr()), n, C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)) != 1:
-        raise RuntimeError("RaylibAMD_NearestPointsDevice refused the query")
-    return out
+    dtype = NEAREST_DTYPE if kind == NEAREST_CLOSEST else np.dtype("u4")
+    return _query(lib, scene, points, 4, "RaylibAMD_NearestPoints", lambda n: [(n, dtype)], pre=(kind,), host=host, type_error=_POINTS_TYPE_ERROR)[0]
 
 
 MAX_NEAREST = 16                                    # RAYLIB_AMD_MAX_NEAREST
@@ -263,9 +252,7 @@ MAX_NEAREST = 16                                    # RAYLIB_AMD_MAX_NEAREST
 
 def plan_nearest_all(lib, scene, max_hits, count=False):
     """RaylibAMD_PlanNearestAll: (return code, plan dict)."""
-    p = QueryPlan()
-    r = lib.RaylibAMD_PlanNearestAll(scene, int(max_hits), int(bool(count)), C.byref(p))
-    return r, p.as_dict()
+    return _plan(lib, "RaylibAMD_PlanNearestAll", scene, int(max_hits), int(bool(count)))
 
 
 def nearest_points_all(lib, scene, points, max_hits, count=False, host=False):
@@ -277,28 +264,7 @@ def nearest_points_all(lib, scene, points, max_hits, count=False, host=False):
     device goes through the device entry on torch.cuda.current_stream(), as nearest_points; it returns tensors: (n, max_hits, 4) int32 words and (n,) int32
     counts.  Raises RuntimeError when the library refuses the call."""
     max_hits = int(max_hits)
-    if isinstance(points, np.ndarray):
-        p = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
-        n = len(p)
-        rows = np.zeros((n, max(max_hits, 0)), NEAREST_DTYPE)
-        counts = np.zeros(n, np.uint32) if count else None
-        name = "RaylibAMD_NearestPointsAllHost" if host else "RaylibAMD_NearestPointsAll"
-        if getattr(lib, name)(scene, p.ctypes.data, n, max_hits, rows.ctypes.data, counts.ctypes.data if count else None) != 1:
-            raise RuntimeError(name + " refused the query")
-        return (rows, counts) if count else rows
-    import torch
-    if host or not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float32):
-        raise TypeError("points: a float32 NumPy array, or a float32 torch tensor on the device (host=False)")
-    p = points.reshape(-1, 4).contiguous()
-    n = p.shape[0]
-    rows = torch.empty((n, max(max_hits, 0), 4), dtype=torch.int32, device=p.device)
-    counts = torch.empty(n, dtype=torch.int32, device=p.device) if count else None
-    stream = torch.cuda.current_stream(p.device)
-    if stream.cuda_stream == 0:
-        stream.synchronize()   # (the library's stream is not ordered against torch's default stream: trace_rays)
-    if lib.RaylibAMD_NearestPointsAllDevice(scene, C.c_void_p(p.data_ptr()), n, max_hits, C.c_void_p(rows.data_ptr()), C.c_void_p(counts.data_ptr()) if count else None,
-                                            C.c_void_p(stream.cuda_stream)) != 1:
-        raise RuntimeError("RaylibAMD_NearestPointsAllDevice refused the query")
+    rows, counts = _query(lib, scene, points, 4, "RaylibAMD_NearestPointsAll", _rows(max_hits, NEAREST_DTYPE, count), mid=(max_hits,), host=host, type_error=_POINTS_TYPE_ERROR)
     return (rows, counts) if count else rows
 
 
@@ -353,9 +319,7 @@ def bake_distance_field(lib, scene, origin, spacing, dims, max_dist, sign, prim=
     with torch.cuda.stream(st):
         dist = torch.empty(shape, dtype=torch.float32, device="cuda")
         prims = torch.empty(shape, dtype=torch.int32, device="cuda") if prim else None
-    if st.cuda_stream == 0:
-        st.synchronize()   # (the library's stream is not ordered against torch's default stream: trace_rays)
-    if lib.RaylibAMD_BakeDistanceFieldDevice(scene, C.byref(p), C.c_void_p(dist.data_ptr()), C.c_void_p(prims.data_ptr()) if prim else None, C.c_void_p(st.cuda_stream)) != 1:
+    if lib.RaylibAMD_BakeDistanceFieldDevice(scene, C.byref(p), C.c_void_p(dist.data_ptr()), C.c_void_p(prims.data_ptr()) if prim else None, _ordered(st)) != 1:
         raise RuntimeError("RaylibAMD_BakeDistanceFieldDevice refused the bake")
     return (dist, prims) if prim else dist
 
@@ -375,9 +339,7 @@ def overlap_queries(v0, v1, v2):
 
 def plan_overlap(lib, scene, kind):
     """RaylibAMD_PlanOverlap: (return code, plan dict)."""
-    p = QueryPlan()
-    r = lib.RaylibAMD_PlanOverlap(scene, int(kind), C.byref(p))
-    return r, p.as_dict()
+    return _plan(lib, "RaylibAMD_PlanOverlap", scene, int(kind))
 
 
 def overlap_triangles(lib, scene, queries, kind, flags=0, max_hits=MAX_OVERLAPS, host=False, count=True):
@@ -391,31 +353,10 @@ def overlap_triangles(lib, scene, queries, kind, flags=0, max_hits=MAX_OVERLAPS,
     kind, flags, max_hits = int(kind), int(flags), int(max_hits)
     if kind not in (OVERLAP_ANY, OVERLAP_LIST):
         raise ValueError("unknown overlap kind %r" % kind)
-    lst = kind == OVERLAP_LIST
-    want_count = lst and count
-    if isinstance(queries, np.ndarray):
-        q = np.ascontiguousarray(queries)
-        q = q.view(np.uint8).reshape(-1, 48) if q.dtype == OVERLAP_QUERY_DTYPE else np.ascontiguousarray(q, np.float32).reshape(-1, 12)
-        n = len(q)
-        out = np.zeros((n, max(max_hits, 0)), np.int32) if lst else np.zeros(n, np.uint32)
-        counts = np.zeros(n, np.uint32) if want_count else None
-        name = "RaylibAMD_OverlapTrianglesHost" if host else "RaylibAMD_OverlapTriangles"
-        if getattr(lib, name)(scene, kind, flags, q.ctypes.data, n, max_hits, out.ctypes.data, counts.ctypes.data if want_count else None) != 1:
-            raise RuntimeError(name + " refused the query")
-        return (out, counts) if want_count else out
-    import torch
-    if host or not (isinstance(queries, torch.Tensor) and queries.is_cuda and queries.dtype == torch.float32):
-        raise TypeError("queries: a NumPy array, or a float32 torch tensor on the device (host=False)")
-    q = queries.reshape(-1, 12).contiguous()
-    n = q.shape[0]
-    out = torch.empty((n, max(max_hits, 0)) if lst else (n,), dtype=torch.int32, device=q.device)
-    counts = torch.empty(n, dtype=torch.int32, device=q.device) if want_count else None
-    stream = torch.cuda.current_stream(q.device)
-    if stream.cuda_stream == 0:
-        stream.synchronize()   # (the library's stream is not ordered against torch's default stream: trace_rays)
-    if lib.RaylibAMD_OverlapTrianglesDevice(scene, kind, flags, C.c_void_p(q.data_ptr()), n, max_hits, C.c_void_p(out.data_ptr()),
-                                            C.c_void_p(counts.data_ptr()) if want_count else None, C.c_void_p(stream.cuda_stream)) != 1:
-        raise RuntimeError("RaylibAMD_OverlapTrianglesDevice refused the query")
+    want_count = kind == OVERLAP_LIST and count
+    specs = _rows(max_hits, np.int32, want_count) if kind == OVERLAP_LIST else (lambda n: [(n, np.uint32), None])
+    out, counts = _query(lib, scene, queries, 12, "RaylibAMD_OverlapTriangles", specs, pre=(kind, flags), mid=(max_hits,), host=host, records=OVERLAP_QUERY_DTYPE,
+                         type_error=_QUERIES_TYPE_ERROR)
     return (out, counts) if want_count else out
 
 
@@ -425,9 +366,7 @@ CONTACT_DTYPE = np.dtype([("p0", "f4", 3), ("kind", "u4"), ("p1", "f4", 3), ("fe
 
 def plan_overlap_contacts(lib, scene):
     """RaylibAMD_PlanOverlapContacts: (return code, plan dict)."""
-    p = QueryPlan()
-    r = lib.RaylibAMD_PlanOverlapContacts(scene, C.byref(p))
-    return r, p.as_dict()
+    return _plan(lib, "RaylibAMD_PlanOverlapContacts", scene)
 
 
 def overlap_contacts(lib, scene, queries, flags=0, max_hits=MAX_OVERLAPS, host=False, count=True):
@@ -439,32 +378,8 @@ def overlap_contacts(lib, scene, queries, flags=0, max_hits=MAX_OVERLAPS, host=F
     device goes through the device entry on torch.cuda.current_stream(), as overlap_triangles; the contacts are then an (n, max_hits, 8) float32 tensor of the
     same 32 bytes per record (kind and features: .view(torch.int32)[..., 3] and [..., 7]).  Raises RuntimeError when the library refuses the call."""
     flags, max_hits = int(flags), int(max_hits)
-    if isinstance(queries, np.ndarray):
-        q = np.ascontiguousarray(queries)
-        q = q.view(np.uint8).reshape(-1, 48) if q.dtype == OVERLAP_QUERY_DTYPE else np.ascontiguousarray(q, np.float32).reshape(-1, 12)
-        n = len(q)
-        rows = np.zeros((n, max(max_hits, 0)), np.int32)
-        recs = np.zeros((n, max(max_hits, 0)), CONTACT_DTYPE)
-        counts = np.zeros(n, np.uint32) if count else None
-        name = "RaylibAMD_OverlapContactsHost" if host else "RaylibAMD_OverlapContacts"
-        if getattr(lib, name)(scene, flags, q.ctypes.data, n, max_hits, rows.ctypes.data, recs.ctypes.data, counts.ctypes.data if count else None) != 1:
-            raise RuntimeError(name + " refused the query")
-        return rows, recs, counts
-    import torch
-    if host or not (isinstance(queries, torch.Tensor) and queries.is_cuda and queries.dtype == torch.float32):
-        raise TypeError("queries: a NumPy array, or a float32 torch tensor on the device (host=False)")
-    q = queries.reshape(-1, 12).contiguous()
-    n = q.shape[0]
-    rows = torch.empty((n, max(max_hits, 0)), dtype=torch.int32, device=q.device)
-    recs = torch.empty((n, max(max_hits, 0), 8), dtype=torch.float32, device=q.device)
-    counts = torch.empty(n, dtype=torch.int32, device=q.device) if count else None
-    stream = torch.cuda.current_stream(q.device)
-    if stream.cuda_stream == 0:
-        stream.synchronize()   # (the library's stream is not ordered against torch's default stream: trace_rays)
-    if lib.RaylibAMD_OverlapContactsDevice(scene, flags, C.c_void_p(q.data_ptr()), n, max_hits, C.c_void_p(rows.data_ptr()), C.c_void_p(recs.data_ptr()),
-                                           C.c_void_p(counts.data_ptr()) if count else None, C.c_void_p(stream.cuda_stream)) != 1:
-        raise RuntimeError("RaylibAMD_OverlapContactsDevice refused the query")
-    return rows, recs, counts
+    return tuple(_query(lib, scene, queries, 12, "RaylibAMD_OverlapContacts", _rows(max_hits, np.int32, count, (CONTACT_DTYPE, True)), pre=(flags,), mid=(max_hits,),
+                        host=host, records=OVERLAP_QUERY_DTYPE, type_error=_QUERIES_TYPE_ERROR))
 
 
 def move_triangles(lib, scene, first, positions, normals=None):
@@ -516,9 +431,7 @@ class RadianceParams(C.Structure):
 def plan_radiance(lib, scene, max_path=5, tmin=1e-4, sample_first=0, sample_count=1, skip_draws=3):
     """RaylibAMD_PlanRadiance: (return code, plan dict)."""
     prm = RadianceParams(int(max_path), float(tmin), int(sample_first), int(sample_count), int(skip_draws), 0.0, 0.0)
-    p = QueryPlan()
-    r = lib.RaylibAMD_PlanRadiance(scene, C.byref(prm), C.byref(p))
-    return r, p.as_dict()
+    return _plan(lib, "RaylibAMD_PlanRadiance", scene, C.byref(prm))
 
 
 def trace_radiance(lib, scene, rays, max_path=5, tmin=1e-4, sample_first=0, sample_count=1, skip_draws=3):
@@ -982,15 +895,15 @@ _EXPORTS = {
     "RaylibAMD_EvalTexture": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float)]),
     "RaylibAMD_EvalDeviceMath": (C.c_int32, [C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float)]),
     "RaylibAMD_ClosestHit": (C.c_int32, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_void_p]),
-    "RaylibAMD_TraceRays": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(Ray), C.c_int32, C.c_float, C.c_void_p, C.POINTER(C.c_int32)]),
-    "RaylibAMD_TraceRaysDevice": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(Ray), C.c_int32, C.c_float, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "RaylibAMD_TraceRays": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_TraceRaysDevice": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "RaylibAMD_PlanRayQuery": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(QueryPlan)]),
     "RaylibAMD_TraceRadiance": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(PathRay), C.c_int32, C.POINTER(C.c_float)]),
     "RaylibAMD_TraceRadianceDevice": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(PathRay), C.c_int32, C.POINTER(C.c_float), C.c_void_p]),
     "RaylibAMD_PlanRadiance": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(QueryPlan)]),
-    "RaylibAMD_TraceRaysAll": (C.c_int32, [C.c_void_p, C.POINTER(Ray), C.c_int32, C.c_float, C.c_int32, C.POINTER(HitT), C.POINTER(C.c_uint32)]),
-    "RaylibAMD_TraceRaysAllDevice": (C.c_int32, [C.c_void_p, C.POINTER(Ray), C.c_int32, C.c_float, C.c_int32, C.POINTER(HitT), C.POINTER(C.c_uint32), C.c_void_p]),
-    "RaylibAMD_TraceRaysAllHost": (C.c_int32, [C.c_void_p, C.POINTER(Ray), C.c_int32, C.c_float, C.c_int32, C.POINTER(HitT), C.POINTER(C.c_uint32)]),
+    "RaylibAMD_TraceRaysAll": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_TraceRaysAllDevice": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_TraceRaysAllHost": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p]),
     "RaylibAMD_PlanRayQueryAll": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(QueryPlan)]),
     "RaylibAMD_NearestPoints": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "RaylibAMD_NearestPointsDevice": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -2,9 +2,11 @@
 """Standalone ray-query rates (RaylibAMD_TraceRaysDevice on device-resident rays, the library's stream, HIP-event time of the kernel) for each query kind
 and tree, against RaylibAMD_ClosestHit (the test hook: host rays, its own allocations and copies; wall time).
 
-usage: python tools/gpu_ray_query.py [--scenes cornell,room] [--width 1920] [--height 1080] [--runs 5] [--timeout 600] [--json PATH]
+usage: python tools/gpu_ray_query.py [--scenes cornell,room] [--width 1920] [--height 1080] [--runs 5] [--timeout 600] [--lib PATH] [--json PATH]
+       python tools/gpu_ray_query.py --overhead --lib PATH [--runs 5]
 Two ray sets per scene: the camera rays of a width x height pinhole view (coherent), and one cosine-distributed ray leaving each surface point those camera
 rays hit (incoherent, as a diffuse bounce).  Each scene is measured in a child process under its own time limit; one table row per (scene, rays, tree, kind).
+--lib: another build of the library.  --overhead: the host path of a synchronous call, the tree's library against --lib's in one process (overhead()).
 """
 import argparse
 import ctypes as C
@@ -50,11 +52,52 @@ def bounce_rays(np, surf, seed=1):
     return rays
 
 
+def overhead(args):
+    """--overhead: what a synchronous call costs beside its kernel -- wallMs - kernelMs of its stats, in microseconds -- for CLOSEST queries of 1 ray and of
+    width x height camera rays on the Cornell box, and for a CLOSEST nearest-point call on the rays' origins: the tree's library and --lib's (another build, e.g.
+    the parent commit's) take turns call by call in this one process, --runs calls each after 3 warm-up calls.  Per build the median, the least and the greatest;
+    the tree's median is then placed against the other build's spread."""
+    import numpy as np
+    import torch
+    from raylib_amd import binding, scenes
+    d = tempfile.mkdtemp()
+    obj, _ = scenes.cornell(os.path.join(d, "cornell.obj"))
+    cam = ((0, 1, 4), (0, 1, -1), 45.0)
+    builds = {}
+    for name, path in (("tree", None), ("other", args.lib)):
+        lib = binding.load(path) if path else binding.load()
+        assert lib.Raylib_Initialize() == 1
+        builds[name] = (lib, binding.SceneSession(lib, obj, cam[0], cam[1], cam[2], 1.0))
+    all_rays = torch.from_numpy(camera_rays(np, args.width, args.height, *cam)).cuda()
+    print("%-8s %-6s %9s %-17s %10s %10s %10s" % ("call", "build", "n", "id", "median us", "least", "greatest"))
+    for n in (1, len(all_rays)):
+        rays = all_rays[:n].contiguous()
+        points = rays[:, :4].contiguous(); points[:, 3] = float("inf")
+        out = torch.empty((n, 4), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        calls = {"rays": lambda lib, ses: lib.RaylibAMD_TraceRaysDevice(ses.scene, 1, C.c_void_p(rays.data_ptr()), n, 0.0, C.c_void_p(out.data_ptr()), None, None),
+                 "nearest": lambda lib, ses: lib.RaylibAMD_NearestPointsDevice(ses.scene, 1, C.c_void_p(points.data_ptr()), n, C.c_void_p(out.data_ptr()), None)}
+        for what, call in calls.items():
+            us = {name: [] for name in builds}
+            for k in range(args.runs + 3):
+                for name, (lib, ses) in builds.items():
+                    assert call(lib, ses) == 1
+                    st = binding.Stats(); lib.RaylibAMD_GetLastStats(C.byref(st))
+                    if k >= 3:
+                        us[name].append((st.wallMs - st.kernelMs) * 1e3)
+            for name, (lib, _) in builds.items():
+                print("%-8s %-6s %9d %-17s %10.1f %10.1f %10.1f" % (what, name, n, lib.RaylibAMD_BuildId().decode(), np.median(us[name]), min(us[name]), max(us[name])))
+            inside = min(us["other"]) <= np.median(us["tree"]) <= max(us["other"])
+            print("%-8s n %d: the tree's median is %s the other build's spread" % (what, n, "within" if inside else "below" if np.median(us["tree"]) < min(us["other"]) else "ABOVE"))
+    for _, ses in builds.values():
+        ses.close()
+
+
 def child(args):
     import numpy as np
     import torch
     from raylib_amd import binding, scenes
-    lib = binding.load()
+    lib = binding.load(args.lib) if args.lib else binding.load()
     assert lib.Raylib_Initialize() == 1
     d = tempfile.mkdtemp()
     if args.scene == "cornell":
@@ -113,14 +156,22 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--timeout", type=int, default=600)
     ap.add_argument("--json")
+    ap.add_argument("--lib")
+    ap.add_argument("--overhead", action="store_true")
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--scene")
     args = ap.parse_args()
+    if args.overhead:
+        if not args.lib:
+            ap.error("--overhead compares the tree's library with --lib's")
+        return overhead(args)
     if args.child:
         return child(args)
     rows = []
     for name in args.scenes.split(","):
         cmd = [sys.executable, os.path.abspath(__file__), "--child", "--scene", name, "--width", str(args.width), "--height", str(args.height), "--runs", str(args.runs)]
+        if args.lib:
+            cmd += ["--lib", args.lib]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
         except subprocess.TimeoutExpired:
