@@ -380,6 +380,12 @@ __device__ __forceinline__ uint4 GLoadU4(const void* p, int i) { const rl_v4u v 
 // test, with an out-of-line walk that applies it per candidate for the lane whose winner fails it.  Sound -- the search finds the nearest of a larger set, and
 // a winner that passes the rule is the nearest of the smaller one too -- and 0.5 % faster, but the call made the register allocator keep the 24 keys in
 // scratch memory: 28 GB of spill traffic per frame, three times everything else the kernel moves.)
+// The candidate rule takes invb, the reciprocal of the box loop: the same bits as ExactInv(d).  Written as a second ExactInv(d) at the triangle test -- as the
+// tree walks write it, where the reciprocal of the box tests may be a clamped one -- the compiler did not fold the two: behind the first pick it ran three
+// whole IEEE expansions of 1 / x (v_div_scale x 2, v_rcp, five fma, v_div_fmas, v_div_fixup each) on every lane of every walk with a candidate, in each of the
+// four walks the hit-queue kernel inlines: 0.137 G of its 5.97 G VALU instructions a frame and 3.3 % of its time ("one reciprocal per walk").
+// (Measured there and not kept: the record count as a template argument, which takes the six scalar branches and little else out of the box loop -- the
+// compiler had sunk the key presets into the branch not taken -- and the leaf count of the last record on top of it.)
 // PLAIN: no leaf carries the cut-out bit (rl_plan.cc), so the walk does not test it.
 template <bool ANYHIT, bool PLAIN = false>
 __device__ __forceinline__ bool TraverseLeafList(const DSceneView& S, V3 o, V3 d, float tMin, HitRec& best, Counters& c, const float4* sm)
@@ -485,7 +491,7 @@ __device__ __forceinline__ bool TraverseLeafList(const DSceneView& S, V3 o, V3 d
 			T.uv = q3.x; T.uu = q3.y; T.vv = q3.z; T.denom = q3.w; T.rden = tr[5].z;
 			c.tris++;
 			RL_WSTEP(5);
-			RL_TRIANGLE_TEST(S, T, L.first + i, o, d, tMin, best, !PLAIN && L.alpha, OwnBoxPassMnMx(tr, o, ExactInv(d), tMin, t), ANYHIT, c, RL_ELSE_CONTINUE)
+			RL_TRIANGLE_TEST(S, T, L.first + i, o, d, tMin, best, !PLAIN && L.alpha, OwnBoxPassMnMx(tr, o, invb, tMin, t), ANYHIT, c, RL_ELSE_CONTINUE)
 		}
 		m = 0xffffffffu;
 		#pragma unroll
