@@ -128,7 +128,8 @@ RAYLIB_API int32_t RaylibAMD_ClosestHit(SceneHandle scene, const float* rays, in
  * triangles are alpha-tested during the walk, as in the render.
  * A query never reports a hit behind the origin: tMin < 0 (-inf included) is read as +0, and -0.0 is 0; a NaN tMin stays a NaN.  (The slack of the own-box
  * rule and of the walks' box tests is a factor above 1 and assumes t >= 0.)  A triangle at exactly tMin or exactly tMax counts, so [t, t] finds the surface at t;
- * tMin > tMax is empty.  Checked against a loop over every primitive: tests/test_gpu_ray_query_intervals.py. */
+ * tMin > tMax is empty.  Each primitive is held to its own interval: a sphere at exactly tMax is out of range and hides nothing, so a cube or a triangle at
+ * that same t is reported.  Checked against a loop over every primitive: tests/test_gpu_ray_query_intervals.py, tests/test_gpu_analytic_edges.py. */
 typedef struct RaylibAMDRay {          /* 32 bytes; on the device entry an array of them must be 16-byte aligned */
 	float org[3]; float tMin;
 	float dir[3]; float tMax;

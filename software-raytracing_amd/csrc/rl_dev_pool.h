@@ -183,7 +183,7 @@ __device__ __forceinline__ bool LeafStep(const DSceneView& S, Trav& T, float tMi
 		const int i = L.first + T.leafI;
 		const Tri TT = LoadTri(S, i);
 		RL_TRIANGLE_TEST(S, TT, i, o, d, tMin, T.best, L.alpha, OwnBoxPass(TT.v0, TT.v1, TT.v2, o, ExactInv(d), tMin, t), T.anyhit, c, RL_NESTED)
-	} else RL_PRIMITIVE_LEAF(S, L.kind, L.first, o, d, T.rayTime, tMin, T.best, T.anyhit)
+	} else RL_PRIMITIVE_LEAF(S, L.kind, L.first, o, d, T.rayTime, tMin, T.best, T.anyhit, false, FLT_MAX)
 	if (++T.leafI < L.count) return false;
 	return PopOrFinish<LSTACK, STACK>(T, stk, ovf);
 }

@@ -114,8 +114,10 @@ __device__ __forceinline__ bool RootMiss(const DSceneView& S, V3 o, V3 d, float 
 // stk: this lane's column of the LDS stack; entry k at stk[k * RL_BLOCK].
 // Sphere::Hit (reference geom/sphere.cc:3-45): open interval (t_min, t_max); the near root if it is inside, else the
 // far root.  t_max is the current best t (the reference compares all hits afterwards; same closest hit).
+// tOpen: the interval's open upper end -- FLT_MAX for a render; a ray query's own tMax (SphereHitBelow).  A root outside (t_min, tOpen) is no root at all: it
+// must not be returned and dropped later, or it shadows a cube at that same t, whose interval is closed and whose test asks "t < best".
 // Returns t, or NaN for a miss (results by value: an out-parameter of an out-of-line function would live in scratch).
-__device__ __noinline__ float SphereHit(const DSphere* spheres, int index, V3 o, V3 d, float t_min, float tBest)
+__device__ __forceinline__ float SphereRoots(const DSphere* spheres, int index, V3 o, V3 d, float t_min, float tBest, const float tOpen)
 {
 	const float4 q = ((const float4*)(spheres + index))[0];
 	const V3 center = v3(q.x, q.y, q.z); const float radius = q.w;
@@ -126,11 +128,19 @@ __device__ __noinline__ float SphereHit(const DSphere* spheres, int index, V3 o,
 	float D = b * b - a * c;
 	if (D > 0.0f) {
 		float temp = (-b - rtm::sqrt_(b * b - a * c)) / a;
-		if (t_min < temp && temp < FLT_MAX) return (temp < tBest) ? temp : NAN;   // the reference takes this root and compares later
+		if (t_min < temp && temp < tOpen) return (temp < tBest) ? temp : NAN;   // the reference takes this root and compares later
 		temp = (-b + rtm::sqrt_(b * b - a * c)) / a;
-		if (t_min < temp && temp < FLT_MAX) return (temp < tBest) ? temp : NAN;
+		if (t_min < temp && temp < tOpen) return (temp < tBest) ? temp : NAN;
 	}
 	return NAN;
+}
+__device__ __noinline__ float SphereHit(const DSphere* spheres, int index, V3 o, V3 d, float t_min, float tBest)
+{
+	return SphereRoots(spheres, index, o, d, t_min, tBest, FLT_MAX);
+}
+__device__ __noinline__ float SphereHitBelow(const DSphere* spheres, int index, V3 o, V3 d, float t_min, float tBest, float tOpen)
+{
+	return SphereRoots(spheres, index, o, d, t_min, tBest, tOpen);
 }
 // Cube::Hit (reference geom/cube.cc:3-43): slab box moving with velocity * max(0, rayTime - timeStartMove); closed
 // interval [t_min, t_max]; entry face by the reference's float == chain (outFace 0..5 = -x +x -y +y -z +z, 6 = none matched).
@@ -235,9 +245,10 @@ __device__ __forceinline__ LeafRef DecodeLeaf(int ref)
 	} \
 }
 // The leaf of one analytic primitive (kind 1: sphere, 2: cube: `first_` is its number), for Traverse and LeafStep; a macro for the same reason.
-#define RL_PRIMITIVE_LEAF(S_, kind_, first_, o_, d_, rayTime_, tMin_, best_, anyhit_) { \
+// open_ (a compile-time constant): a sphere's interval ends at tOpen_ instead of FLT_MAX.
+#define RL_PRIMITIVE_LEAF(S_, kind_, first_, o_, d_, rayTime_, tMin_, best_, anyhit_, open_, tOpen_) { \
 	float2 r_; \
-	if ((kind_) == 1u) r_ = make_float2(SphereHit((S_).spheres, first_, o_, d_, tMin_, (best_).t), 0.0f); \
+	if ((kind_) == 1u) r_ = make_float2((open_) ? SphereHitBelow((S_).spheres, first_, o_, d_, tMin_, (best_).t, tOpen_) : SphereHit((S_).spheres, first_, o_, d_, tMin_, (best_).t), 0.0f); \
 	else r_ = CubeHit((S_).cubes, first_, o_, d_, rayTime_, tMin_, (best_).t); \
 	if (r_.x == r_.x) {   /* not NaN: a hit */ \
 		(best_).t = r_.x; (best_).a = r_.y; (best_).b = 0.0f; (best_).tri = (int)(((kind_) << 28) | (uint32_t)(first_)); \
@@ -251,8 +262,10 @@ __device__ __forceinline__ LeafRef DecodeLeaf(int ref)
 // the ~4x dearer triangle code ran with a handful of lanes (measured: 14 % VALU lane utilisation on the
 // 298 k-triangle scene).
 // tBound: where the search starts, "best" before any hit (the ray queries: the float above their tMax, rl_k_query.inl).
-template <int STACK, bool ANYHIT, bool PRIMS>
-__device__ __forceinline__ bool Traverse(const DSceneView& S, V3 o, V3 d, float rayTime, float tMin, HitRec& best, int* stk, Counters& c, const float tBound = INFINITY)
+// OPEN, tOpen: the open end of a sphere's interval is tOpen instead of FLT_MAX (the ray queries with spheres: their tMax).
+template <int STACK, bool ANYHIT, bool PRIMS, bool OPEN = false>
+__device__ __forceinline__ bool Traverse(const DSceneView& S, V3 o, V3 d, float rayTime, float tMin, HitRec& best, int* stk, Counters& c, const float tBound = INFINITY,
+                                         const float tOpen = FLT_MAX)
 {
 	c.rays++;
 	const V3 inv = ExactInv(d);
@@ -297,7 +310,7 @@ __device__ __forceinline__ bool Traverse(const DSceneView& S, V3 o, V3 d, float 
 					c.tris++;
 					RL_TRIANGLE_TEST(S, T, L.first + i, o, d, tMin, best, L.alpha, OwnBoxPass(T.v0, T.v1, T.v2, o, inv, tMin, t), ANYHIT, c, RL_ELSE_CONTINUE)
 				}
-			} else { c.tris++; RL_PRIMITIVE_LEAF(S, L.kind, L.first, o, d, rayTime, tMin, best, ANYHIT) }
+			} else { c.tris++; RL_PRIMITIVE_LEAF(S, L.kind, L.first, o, d, rayTime, tMin, best, ANYHIT, OPEN, tOpen) }
 		}
 		if (sp == 0) break;
 		--sp;

@@ -8,8 +8,10 @@
 // ray to its end (Traverse / Traverse4 are whole walks); on the 8-wide tree a lane whose ray is done takes the chunk's next ray between two steps.
 //
 // The interval [tMin, tMax]: the walk starts with "best" at the float above tMax, so the triangle test (t >= tMin, t < best) takes a hit at exactly tMax,
-// as Triangle::Hit does, and every box beyond tMax is culled.  A sphere's interval is open (Sphere::Hit: t_min < t < t_max): a sphere at exactly tMax is
-// dropped afterwards -- it can only have been the walk's result if nothing nearer was accepted.  A NaN bound makes every comparison false: a miss.
+// as Triangle::Hit does, and every box beyond tMax is culled.  A sphere's interval is open (Sphere::Hit: t_min < t < t_max): the walk hands its sphere test
+// tMax as that open end (Traverse's OPEN, SphereHitBelow), so a sphere at exactly tMax is never a candidate.  (Accepting it and dropping it after the walk lost
+// a cube at that same t, which is in range -- a cube's interval is closed -- but is taken only if nearer than the best so far:
+// tests/test_gpu_analytic_edges.py.)  A NaN bound makes every comparison false: a miss.
 // tMin < 0 is raised to +0 (QueryTMin).  A triangle at exactly tMin counts: this unit widens the candidate rule's "own box ends before tMin" (RL_OWN_BOX_WIDEN_TMIN, rl_dev_walk.h OwnBoxPassBox).
 // (RL_QUERY_CHUNK, the rays a wave takes per atomic on the global counter: rl_kernels.h)
 #ifndef RL_QUERY_REFILL
@@ -31,12 +33,11 @@ __device__ __forceinline__ float QueryTMin(float tMin) { return tMin < 0.0f ? 0.
 
 // the record of one finished ray
 template <int KIND, bool PRIMS>
-__device__ __forceinline__ void QueryStore(const DSceneView& S, V3 o, V3 d, float tMax, const HitRec& h, uint32_t i, void* __restrict__ out,
+__device__ __forceinline__ void QueryStore(const DSceneView& S, V3 o, V3 d, const HitRec& h, uint32_t i, void* __restrict__ out,
                                            int32_t* __restrict__ outPrim, const int32_t* __restrict__ slotIndex, Counters& c)
 {
 	const uint32_t kind = PRIMS ? ((uint32_t)h.tri) >> 28 : 0u;
-	bool hit = h.tri >= 0;
-	if (PRIMS && hit && kind == 1u && !(h.t < tMax)) hit = false;   // a sphere at exactly tMax (open interval)
+	const bool hit = h.tri >= 0;
 	if (KIND == RL_QK_ANY) { ((uint32_t*)out)[i] = hit ? 1u : 0u; return; }
 	const int32_t prim = !hit ? -1 : kind != 0u ? h.tri : slotIndex ? slotIndex[h.tri] : h.tri;
 	if (KIND == RL_QK_CLOSEST) {
@@ -68,7 +69,7 @@ k_query(const DSceneView S, const float4* __restrict__ rays, uint32_t n, float r
 	static_assert(TREE == 2 || !PRIMS, "spheres and cubes are walked on the binary tree only");
 	RL_TEX_PROLOGUE(S);
 	RL_MATH_PROLOGUE();
-	// ANY stops at the first accepted candidate -- not with spheres, whose open interval is applied after the walk (above)
+	// ANY stops at the first accepted candidate -- not in the instances with spheres and cubes (RaylibAMDQueryPlan's `early`, csrc/rl_plan.cc)
 	constexpr bool EARLY = KIND == RL_QK_ANY && !PRIMS;
 	__shared__ int s_stack[(TREE == 8 ? RL_POOL8_LSTACK : STACK) * RL_BLOCK];
 	int* stk = s_stack + threadIdx.x;
@@ -88,9 +89,9 @@ k_query(const DSceneView S, const float4* __restrict__ rays, uint32_t n, float r
 					const V3 o = v3(r0.x, r0.y, r0.z), d = v3(r1.x, r1.y, r1.z);
 					const float tMin = QueryTMin(r0.w), tMax = r1.w;
 					HitRec h;
-					if constexpr (TREE == 2) Traverse<STACK, EARLY, PRIMS>(S, o, d, rayTime, tMin, h, stk, c, NextUpF(tMax));
+					if constexpr (TREE == 2) Traverse<STACK, EARLY, PRIMS, PRIMS>(S, o, d, rayTime, tMin, h, stk, c, NextUpF(tMax), tMax < FLT_MAX ? tMax : FLT_MAX);   // (a NaN tMax: FLT_MAX, and nothing is below the NaN bound)
 					else Traverse4<STACK, EARLY, false, false>(S, o, d, rayTime, tMin, h, stk, c, nullptr, NextUpF(tMax));
-					QueryStore<KIND, PRIMS>(S, o, d, tMax, h, i, out, outPrim, slotIndex, c);
+					QueryStore<KIND, PRIMS>(S, o, d, h, i, out, outPrim, slotIndex, c);
 				}
 			}
 		}
@@ -153,7 +154,7 @@ k_query(const DSceneView S, const float4* __restrict__ rays, uint32_t n, float r
 				bool fin;
 				if (T.cur >= 0) fin = NodeStep8(S, T, tMin, stk, ovf, c, s_perm, nullptr, G8, GMAX8);
 				else fin = LeafStep8<false>(S, T, tMin, stk, ovf, c, G8);
-				if (fin) { QueryStore<KIND, false>(S, T.o, T.d, INFINITY, T.best, my, out, outPrim, slotIndex, c); my = NONE; }
+				if (fin) { QueryStore<KIND, false>(S, T.o, T.d, T.best, my, out, outPrim, slotIndex, c); my = NONE; }
 			}
 		}
 	}

@@ -152,7 +152,7 @@ QueryPlan PlanQuery(const Scene& sc, int32_t kind, const RenderKnobs& k)
 	} else {
 		p.stack = b.depth <= 32 ? 32 : 64;
 	}
-	// spheres close an open interval after the walk (rl_k_query.inl): with them the occlusion query walks to the closest hit
+	// the instances with spheres and cubes have no early exit: with them the occlusion query walks to the closest hit (rl_k_query.inl, EARLY)
 	p.early = kind == RAYLIB_AMD_QUERY_ANY && !p.prims;
 	return p;
 }

@@ -185,6 +185,16 @@ def main(only=None):
             print("long_paths mirror_hall", depth, float(np.nanmean(out["mirror_hall_len%d" % depth][..., :3])))
         np.savez_compressed(os.path.join(HERE, "long_paths.npz"), **out)
 
+    # ---- spheres and cubes at their degenerate rays (tests/analytic_cases.py): the reference's closest-hit records ------------------------
+    # Per family and tMin: the records of a fixed subsample, and a SHA-256 of the records of every ray; per family a SHA-256 of the rays' bytes.
+    # Data only -- the rays are regenerated by analytic_cases.  NaNs are stored as 0x7fc00000 (helpers.same).  Cube::Hit leaves paramU / paramV
+    # unset (geom/cube.cc): whatever the reference's record holds there is stored as 0, what the oracle and the device write.
+    if want("analytic_edges"):
+        import analytic_cases as ac
+        out = ac.recorded(ref, ffi)
+        np.savez_compressed(os.path.join(HERE, "analytic_edges.npz"), **out)
+        print("analytic_edges done:", len(out), "arrays,", os.path.getsize(os.path.join(HERE, "analytic_edges.npz")), "bytes")
+
     if only is not None and not (want("procedural") or want("kat") or want("soup")):
         return
     # ---- procedural scene: spheres, a moving cube, Metal / DiffuseLight / Dielectric / Mirror -----------------------
