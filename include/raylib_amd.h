@@ -168,6 +168,56 @@ typedef struct RaylibAMDQueryPlan {
 } RaylibAMDQueryPlan;
 RAYLIB_API int32_t RaylibAMD_PlanRayQuery(SceneHandle scene, int32_t kind, RaylibAMDQueryPlan* out);
 
+/* ---- primary-hit G-buffer ----------------------------------------------------------------------------
+ * What is in each pixel: depth, primitive, barycentrics, world position, normal and material index, and the five deterministic debug modes as planes, from ONE
+ * walk of each pixel's camera ray on the tree the ray queries prefer (csrc/rl_k_gbuffer.inl; k_aov walks the binary tree once per mode).
+ * G1  Ray.  Pixel (x, y) of a W x H frame uses the ray the debug render modes use: the stream is raylib_rng_begin(seed, y * W + x, 0) and the ray is
+ *     CameraRay(camera, (float)x / (float)W, (float)y / (float)H, stream) -- origin, direction and shutter time; not jittered.  The seed is RaylibAMD_GetSeed()
+ *     at the call.  It is what RaylibAMD_EvalCameraRays returns for record i = y * W + x with uv = (x / W, y / H).
+ * G2  Hit.  The closest hit the render finds for that ray, with settings->rayTMin used as the render uses it: not raised to 0 and without the ray queries'
+ *     widened own-box rule (the two agree wherever no surface lies within rayTMin of the camera).  Cut-outs are alpha-tested in the walk; spheres and cubes
+ *     are placed at the ray's time.  The hit does not depend on the tree walked, with the ray queries' caveat for the wide trees'
+ *     +-1e30 reciprocal (hits beyond about 1e20).
+ * G3  Planes, row-major, W * H records each; any subset may be asked for (a null pointer: not asked for, nothing written):
+ *       hit            16 bytes  RaylibAMDHitT {t, prim, b1, b2}: prim in RaylibAMD_SceneExportTriangles order, RAYLIB_AMD_PRIM_SPHERE | k or
+ *                                RAYLIB_AMD_PRIM_CUBE | k; a miss is {0, -1, 0, 0}
+ *       surface        44 bytes  the RaylibAMD_ClosestHit record {hit, t, p[3], n[3], paramU, paramV, material}; a miss is zeros with material -1
+ *       albedo         16 bytes  what Raylib_Render writes for the pixel in RAYLIB_RENDERMODE_Albedo, bit for bit, alpha 1 -- the second walk along the
+ *                                reflection off a mirror-like surface included; a miss is (0, 0, 0, 1)
+ *       surfaceNormal, microNormal, texcoord, emission   16 bytes each: as Raylib_Render in RAYLIB_RENDERMODE_SurfaceNormal, _MicrosurfaceNormal, _Texcoord,
+ *                                _Emission, bit for bit, alpha 1; a miss is (0, 0, 0, 1)
+ *     "Raylib_Render" means the same settings apart from renderMode, the same scene, camera and seed.  The surface record and the colour planes come from one
+ *     surface interaction: the debug modes build it with its tangent frame and RaylibAMD_ClosestHit without, and the frame changes no other field.
+ * G4  samplesPerPixel, maxPathLength and renderMode of the settings are not read: the debug modes are one sample.
+ * G5  No output bit depends on the tree walked, on how pixels are dealt to lanes and waves, on which other planes were asked for, or on whether the trees are
+ *     fresh or refitted by RaylibAMD_SceneMoveTriangles; after a move the call sees the moved triangles.
+ * G6  Refused (0, nothing written): a null settings, scene, camera or planes struct; no plane asked for; W or H equal to 0, or W * H above 2^31 - 1; a rayTMin
+ *     that is not finite; a scene that is not finalized; a BVH deeper than 64 levels; no device; on the device entry a plane pointer off rank 0's device, a
+ *     16-byte plane that is not 16-byte aligned or `surface` not 4-byte aligned; on the images entry a handle that is unknown, or the same image twice.
+ * Still out: the Reflectance mode (it draws random numbers behind the camera's, and the reference reads an uninitialised frame there); jittered samples
+ * s >= 1; a views-batch twin; splitting the frame over ranks; a depth or position guide for RaylibAMD_Denoise (it would change the filter's statement). */
+typedef struct RaylibAMDGBufferPlanes {
+	RaylibAMDHitT* hit; void* surface;
+	float *albedo, *surfaceNormal, *microNormal, *texcoord, *emission;   /* 4 floats per pixel each */
+} RaylibAMDGBufferPlanes;
+/* Planes in host memory; synchronous.  The library keeps its device staging buffers and grows them, as the query entries do.  RaylibAMD_GetLastStats then
+ * reports rays (the albedo plane's mirror follow-ups included), nodesVisited, trisTested, shadedHits, texFetches, cameraSamples = pixels = W * H, kernelMs,
+ * wallMs, treeWidth, nodeBytes and ranks = 1. */
+RAYLIB_API int32_t RaylibAMD_RenderGBuffer(const RendererSettings* settings, SceneHandle scene, CameraHandle camera, const RaylibAMDGBufferPlanes* hostPlanes);
+/* The same on device pointers, under RaylibAMD_TraceRaysDevice's rules: stream == NULL is the library's stream, synchronous, with stats; with a hipStream_t the
+ * uploads (the scene with its textures, a tree or the slot table needed for the first time) happen first and synchronously, then the launch is enqueued on that
+ * stream -- behind a RaylibAMD_SceneMoveTrianglesDevice enqueued there -- and the call returns; the stats are left alone.  With RAYLIB_NUM_GPUS > 1 it runs on
+ * rank 0's device, behind frames in flight. */
+RAYLIB_API int32_t RaylibAMD_RenderGBufferDevice(const RendererSettings* settings, SceneHandle scene, CameraHandle camera, const RaylibAMDGBufferPlanes* devicePlanes,
+        void* stream);
+/* The denoiser's two guides in one launch: each image given is resized to the viewport as Raylib_Render does and holds its plane on the device afterwards, as
+ * after Raylib_Render in that mode -- Raylib_Denoise, RaylibAMD_Denoise, Raylib_PostProcess and Raylib_DumpImageData work on it unchanged.  Either handle may
+ * be 0, not both.  Synchronous, with stats. */
+RAYLIB_API int32_t RaylibAMD_RenderGuides(const RendererSettings* settings, SceneHandle scene, CameraHandle camera, ImageHandle albedo, ImageHandle microNormal);
+/* The tree and instance a G-buffer would walk: RaylibAMD_PlanRayQuery's answer for RAYLIB_AMD_QUERY_SURFACE under the current environment (one planner,
+ * csrc/rl_plan.cc), early = 0.  No device needed.  Returns 1, -1 when the BVH is deeper than 64 levels, 0 for a null argument or a scene not finalized. */
+RAYLIB_API int32_t RaylibAMD_PlanGBuffer(SceneHandle scene, RaylibAMDQueryPlan* out);
+
 /* ---- ordered multi-hit ray queries -------------------------------------------------------------
  * The first maxHits surfaces a ray crosses, in order, and how many it crosses in all: ordered transparency and depth peeling, thickness and x-ray views,
  * shell and CSG tests, the inside / outside parity of a point -- in one walk of the tree, where peeling with CLOSEST walks it once per layer.

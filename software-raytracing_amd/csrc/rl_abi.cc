@@ -87,17 +87,23 @@ void ReleaseDeviceCopy(Scene* s)
 	DeviceReleaseScene(s->device); s->device = nullptr;
 }
 
+// Moving cubes: their boxes must cover the motion over THIS camera's shutter interval (a render, and a G-buffer of the camera's rays)
+bool PrepareShutter(const char* who, Scene* scene, const Camera* camera)
+{
+	if (scene->hasMovingCubes && (scene->accelT0 != camera->beginTime || scene->accelT1 != camera->endTime)) {
+		ReleaseDeviceCopy(scene);
+		if (!scene->BuildAccel(camera->beginTime, camera->endTime)) { Log("%s: the acceleration structure could not be rebuilt for this camera's shutter interval", who); return false; }
+	}
+	return true;
+}
+
 // What every render checks and prepares before it reaches the device (Raylib_Render and RaylibAMD_BeginProgressive; `who` names the caller in the log).
 bool PrepareRender(const char* who, const RendererSettings* settings, Scene* scene, Camera* camera)
 {
 	if (!settings || !scene || !camera) { Log("%s: null argument", who); return false; }
 	if (!scene->finalized) { Log("%s: scene was not finalized (Raylib_FinalizeScene)", who); return false; }
 	if (settings->renderMode >= RAYLIB_RENDERMODE_MAX) { Log("%s: invalid render mode %u", who, settings->renderMode); return false; }
-	if (scene->hasMovingCubes && (scene->accelT0 != camera->beginTime || scene->accelT1 != camera->endTime)) {
-		// moving cubes: their boxes must cover the motion over THIS camera's shutter interval
-		ReleaseDeviceCopy(scene);
-		if (!scene->BuildAccel(camera->beginTime, camera->endTime)) { Log("%s: the acceleration structure could not be rebuilt for this camera's shutter interval", who); return false; }
-	}
+	if (!PrepareShutter(who, scene, camera)) return false;
 	if (scene->sky && !g_images.contains(scene->sky)) {
 		// the reference would read freed memory here; a destroyed panorama is treated as none
 		Log("%s: the scene's sky panorama was destroyed; rendering without it", who);
@@ -861,6 +867,75 @@ int32_t RaylibAMD_PlanRayQuery(SceneHandle sh, int32_t kind, RaylibAMDQueryPlan*
 	if (!s || !s->finalized || !out || kind < RAYLIB_AMD_QUERY_ANY || kind > RAYLIB_AMD_QUERY_SURFACE) return 0;
 	const QueryPlan p = PlanQuery(*s, kind, ReadRenderKnobs());
 	return ExportPlan(p, p.prims, p.early, out);
+}
+
+// RaylibAMD_RenderGBuffer / RaylibAMD_RenderGBufferDevice / RaylibAMD_RenderGuides / RaylibAMD_PlanGBuffer (statements G1 to G6): the refusals every entry
+// shares (G6; samplesPerPixel, maxPathLength and renderMode are not read), then, as a render, the scene's boxes for the camera's shutter interval, then the device
+static bool GBufferArgsValid(const char* who, const RendererSettings* settings, const Scene* s, const Camera* c)
+{
+	if (!settings || !s || !c) { Log("%s: null argument", who); return false; }
+	const uint64_t pixels = (uint64_t)settings->viewportWidth * settings->viewportHeight;
+	if (pixels == 0 || pixels > 0x7fffffffull) { Log("%s: a frame of %u x %u pixels (1 .. 2^31 - 1)", who, settings->viewportWidth, settings->viewportHeight); return false; }
+	if (!std::isfinite(settings->rayTMin)) { Log("%s: rayTMin %g is not finite", who, settings->rayTMin); return false; }
+	if (!s->finalized) { Log("%s: scene was not finalized (Raylib_FinalizeScene)", who); return false; }
+	if (s->bvh.depth > 64) { Log("%s: BVH depth %u exceeds the traversal stack (64)", who, s->bvh.depth); return false; }
+	return true;
+}
+static int32_t RenderGBufferInternal(const char* who, const RendererSettings* settings, SceneHandle sh, CameraHandle ch, const RaylibAMDGBufferPlanes* planes, bool hostMem,
+                                     void* stream)
+{
+	Scene* s = (Scene*)sh; Camera* c = (Camera*)ch;
+	if (!planes) { Log("%s: null argument", who); return 0; }
+	if (!GBufferArgsValid(who, settings, s, c)) return 0;
+	if (!planes->hit && !planes->surface && !planes->albedo && !planes->surfaceNormal && !planes->microNormal && !planes->texcoord && !planes->emission) {
+		Log("%s: no plane asked for", who); return 0;
+	}
+	return RunOnDevice(stream, [&](RaylibAMDStats& stats) {
+		if (!PrepareShutter(who, s, c)) return false;
+		return DeviceRenderGBuffer(*s, *settings, c->ToDevice(), CurrentSeed(), *planes, hostMem, stream, stats);
+	});
+}
+int32_t RaylibAMD_RenderGBuffer(const RendererSettings* settings, SceneHandle scene, CameraHandle camera, const RaylibAMDGBufferPlanes* hostPlanes)
+{
+	return RenderGBufferInternal("RaylibAMD_RenderGBuffer", settings, scene, camera, hostPlanes, true, nullptr);
+}
+int32_t RaylibAMD_RenderGBufferDevice(const RendererSettings* settings, SceneHandle scene, CameraHandle camera, const RaylibAMDGBufferPlanes* devicePlanes, void* stream)
+{
+	return RenderGBufferInternal("RaylibAMD_RenderGBufferDevice", settings, scene, camera, devicePlanes, false, stream);
+}
+int32_t RaylibAMD_RenderGuides(const RendererSettings* settings, SceneHandle scene, CameraHandle camera, ImageHandle albedo, ImageHandle microNormal)
+{
+	static const char* who = "RaylibAMD_RenderGuides";
+	Image* imgs[2] = { (Image*)albedo, (Image*)microNormal };
+	if (!imgs[0] && !imgs[1]) { Log("%s: no image given", who); return 0; }
+	if (imgs[0] == imgs[1]) { Log("%s: the same image given twice", who); return 0; }
+	for (Image* img : imgs) if (img && !g_images.contains(img)) { Log("%s: unknown image", who); return 0; }
+	if (!GBufferArgsValid(who, settings, (Scene*)scene, (Camera*)camera)) return 0;   // (before an image is touched)
+	if (!DeviceAvailable()) return 0;
+	// a whole-frame render over several ranks may still be writing one of these images: wait for it, and keep its numbers for RaylibAMD_GetLastStats
+	RaylibAMDStats late;
+	if (DeviceDrain(&late)) { std::lock_guard<std::mutex> lk(g_stateMu); g_lastStats = late; }
+	void* dev[2] = { nullptr, nullptr };
+	for (int k = 0; k < 2; ++k) {
+		Image* img = imgs[k];
+		if (!img) continue;
+		if (settings->viewportWidth != img->width || settings->viewportHeight != img->height)
+			img->Reallocate(settings->viewportWidth, settings->viewportHeight, 0.0f, 0.0f, 0.0f, 1.0f);   // as Raylib_Render
+		dev[k] = DeviceImagePixels(*img);
+		if (!dev[k]) { Log("%s: no device storage for an image", who); return 0; }
+	}
+	RaylibAMDGBufferPlanes planes; memset(&planes, 0, sizeof(planes));
+	planes.albedo = (float*)dev[0]; planes.microNormal = (float*)dev[1];
+	if (!RenderGBufferInternal(who, settings, scene, camera, &planes, false, nullptr)) return 0;
+	for (Image* img : imgs) if (img) { img->devValid = true; img->hostStale = true; img->Touch(); }
+	return 1;
+}
+int32_t RaylibAMD_PlanGBuffer(SceneHandle sh, RaylibAMDQueryPlan* out)
+{
+	Scene* s = (Scene*)sh;
+	if (!s || !s->finalized || !out) return 0;
+	const QueryPlan p = PlanGBuffer(*s, ReadRenderKnobs());
+	return ExportPlan(p, p.prims, 0, out);
 }
 
 // RaylibAMD_TraceRaysAll / RaylibAMD_TraceRaysAllDevice / RaylibAMD_TraceRaysAllHost / RaylibAMD_PlanRayQueryAll (statements M1 to M5): the refusals every entry shares

@@ -270,6 +270,11 @@ bool DeviceClosestHit(Scene& scene, const float* rays, int32_t n, float tMin, vo
 // synchronous; else enqueued on that hipStream_t).  stats: filled by a synchronous call.  kind is valid, n >= 0, the scene finalized: the ABI checked.
 bool DeviceTraceRays(Scene& scene, int32_t kind, const void* rays, int32_t n, float rayTime, void* out, int32_t* outPrim, bool hostMem, void* stream,
                      RaylibAMDStats& stats);
+// RaylibAMD_RenderGBuffer (hostMem: the planes are host memory) and RaylibAMD_RenderGBufferDevice, as DeviceTraceRays: the planes asked for (non-null) of the
+// settings' frame, from the camera's sample-0 rays under `seed`.  The frame has 1 .. 2^31 - 1 pixels, a plane is asked for, rayTMin is finite, the scene
+// finalized and its boxes built for the camera's shutter interval: the ABI checked.
+bool DeviceRenderGBuffer(Scene& scene, const RendererSettings& settings, const DCamera& camera, uint64_t seed, const RaylibAMDGBufferPlanes& planes, bool hostMem, void* stream,
+                         RaylibAMDStats& stats);
 // RaylibAMD_TraceRaysAll (hostMem) and RaylibAMD_TraceRaysAllDevice, as DeviceTraceRays: outHits holds n rows of maxHits records, outCount (may be null) n words.
 // The scene holds triangles only, 1 <= maxHits <= RAYLIB_AMD_MAX_HITS and n * maxHits fits an int32_t: the ABI checked.
 bool DeviceTraceRaysAll(Scene& scene, const void* rays, int32_t n, int32_t maxHits, void* outHits, uint32_t* outCount, bool hostMem, void* stream, RaylibAMDStats& stats);

@@ -9,6 +9,8 @@
 //                        changes how two loops of the eager PLAIN instance are scheduled
 //   rl_render_pool.hip   k_trace_pool and its twin: a scheduler strategy of its own (Makefile POOLFLAGS)
 //   rl_query.hip         k_query (RaylibAMD_TraceRays): beside the render kernels it would change how the walks they share are inlined into those
+//   rl_gbuffer.hip       k_gbuffer (RaylibAMD_RenderGBuffer): k_aov's camera rays and debug modes on k_query's driver and walks, with the render's hit rule -- the
+//                        query unit widens the candidate rule, so this one is apart from it, and from the render kernels for k_query's reason
 //   rl_multihit.hip      k_query_all (RaylibAMD_TraceRaysAll): the binary and the 8-wide walk again with a sorted list behind the triangle test, written on the
 //                        shared steps; apart so that k_query and every other unit stay the code they are
 //   rl_nearest.hip       k_nearest (RaylibAMD_NearestPoints): a walk of its own (point-to-box distances, no ray), which shares with the others the records and the
@@ -176,6 +178,30 @@ template <int TREE, int KIND, int STACK, bool PRIMS> __global__ void __launch_bo
 #define RL_QUERY_INSTANCES(X) RL_QUERY_INSTANCES_K(X, 0) RL_QUERY_INSTANCES_K(X, 1) RL_QUERY_INSTANCES_K(X, 2)
 #define RL_K_QUERY(a, b, c, d) template __global__ void k_query<a, b, c, d>(RL_QUERY_ARGS);
 RL_QUERY_INSTANCES(extern RL_K_QUERY)
+
+// ---------------------------------------------------------------------------
+// The primary-hit G-buffer (RaylibAMD_RenderGBuffer, statements G1 to G6; rl_k_gbuffer.inl)
+// The planes a launch writes (mask; a plane not asked for has a null pointer and is not touched), row-major, width * height records each: hit (DQueryHit as one
+// float4), surface (DHitOut), and the five colour planes k_aov's debug modes give (float4, alpha 1).  The frame, its 8 x 8 cells, rayTMin as the render uses it,
+// the camera and the seed of the pixels' streams.
+enum { RL_GB_HIT = 1u, RL_GB_SURFACE = 2u, RL_GB_ALBEDO = 4u, RL_GB_SURFACE_NORMAL = 8u, RL_GB_MICRO_NORMAL = 16u, RL_GB_TEXCOORD = 32u, RL_GB_EMISSION = 64u,
+       RL_GB_COLOUR = RL_GB_ALBEDO | RL_GB_SURFACE_NORMAL | RL_GB_MICRO_NORMAL | RL_GB_TEXCOORD | RL_GB_EMISSION };
+struct DGBuffer {
+	DCamera camera;
+	unsigned long long seed;
+	uint32_t width, height, cellsX, numCells, mask;
+	float rayTMin;
+	float4* hit; DHitOut* surface;
+	float4 *albedo, *surfaceNormal, *microNormal, *texcoord, *emission;
+};
+// TREE, STACK, PRIMS: as k_query's.  slotIndex: as k_query's (read for the hit plane).  cellCounter: the next cell (a wave takes RL_QUERY_CHUNK / 64 of them per
+// atomic).  counters: CNT_* sums, or null.
+#define RL_GBUFFER_ARGS const DSceneView, const DGBuffer, const int32_t* __restrict__, unsigned int* __restrict__, unsigned long long* __restrict__
+template <int TREE, int STACK, bool PRIMS> __global__ void __launch_bounds__(RL_BLOCK) k_gbuffer(RL_GBUFFER_ARGS);
+// The instances rl_rt_rays.hip GBufferKernelOf selects from, one per CLOSEST instance of k_query: (TREE, STACK, PRIMS)
+#define RL_GBUFFER_INSTANCES(X) X(2, 32, false) X(2, 32, true) X(2, 64, false) X(2, 64, true) X(4, 32, false) X(4, 64, false) X(8, 2 * RL_POOL8_MAXLEVELS, false)
+#define RL_K_GBUFFER(a, b, c) template __global__ void k_gbuffer<a, b, c>(RL_GBUFFER_ARGS);
+RL_GBUFFER_INSTANCES(extern RL_K_GBUFFER)
 
 // ---------------------------------------------------------------------------
 // The ordered multi-hit ray queries (RaylibAMD_TraceRaysAll; rl_k_multihit.inl)

@@ -157,6 +157,11 @@ QueryPlan PlanQuery(const Scene& sc, int32_t kind, const RenderKnobs& k)
 	return p;
 }
 
+QueryPlan PlanGBuffer(const Scene& sc, const RenderKnobs& k)
+{
+	return PlanQuery(sc, RAYLIB_AMD_QUERY_SURFACE, k);   // a pixel is a closest-hit query with its surface: that kind's tree, stack and instance
+}
+
 QueryPlan PlanQueryAll(const Scene& sc, const RenderKnobs& k)
 {
 	QueryPlan p;

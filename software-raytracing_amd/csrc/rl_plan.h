@@ -77,6 +77,9 @@ struct QueryPlan {
 	bool early = false;         // the occlusion query stops at its first accepted candidate
 };
 QueryPlan PlanQuery(const Scene& sc, int32_t kind, const RenderKnobs& knobs);
+// Which tree and k_gbuffer instance a G-buffer walks (RaylibAMD_RenderGBuffer, rl_k_gbuffer.inl): k_gbuffer has an instance per CLOSEST instance of k_query
+// and its pixels are the SURFACE query's rays, so this is PlanQuery's answer for that kind.  `early` is false.
+QueryPlan PlanGBuffer(const Scene& sc, const RenderKnobs& knobs);
 // Which tree and k_query_all instance a batch of ordered multi-hit queries walks (RaylibAMD_TraceRaysAll, rl_k_multihit.inl): the 8-wide tree under PlanQuery's
 // conditions, else the binary tree.  There is no grid-4 instance: RAYLIB_QUERY_TREE=4 falls through to the binary tree, =2 selects it, =8 is the default.
 // `early` is unused (false).  The scene holds triangles only (the entries refuse spheres and cubes before they plan).

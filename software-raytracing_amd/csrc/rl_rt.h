@@ -4,7 +4,7 @@
 //   rl_rt_scene.hip   a flattened scene (rl_scene.cc FlattenScene) to every device, its sky and wide trees; images: read-back, RGB dump, post-processing
 //   rl_rt_frame.hip   kernel selection and the one enqueue path of every render (EnqueueFrame), a rank's one-view render, a batch of views
 //   rl_rt_render.hip  whole frames over N ranks (gather, scatter, two frames in flight), DeviceRender, progressive sessions
-//   rl_rt_rays.hip    caller rays, points and triangles: the queries (DeviceTraceRays, DeviceTraceRaysAll, DeviceNearestPoints, DeviceNearestPointsAll, DeviceOverlapTriangles
+//   rl_rt_rays.hip    caller rays, points and triangles, and the camera's pixels: the queries (DeviceRenderGBuffer, DeviceTraceRays, DeviceTraceRaysAll, DeviceNearestPoints, DeviceNearestPointsAll, DeviceOverlapTriangles
 //                     and its contacts: one driver, RunQuery), DeviceBakeDistanceField on the same pieces, DeviceTraceRadiance, DeviceGather (plain and adaptive: one driver, GatherLocked)
 //   rl_rt_lightmap.hip  lightmaps: DeviceLightmapPoints, DeviceBakeLightmap (the raster stages, then DeviceGather's body or the caller's atlas, the filter, the atlas stages)
 //   rl_rt_move.hip    RaylibAMD_SceneMoveTriangles: the moved records and the refit of every tree on the device, the host copies' read-back, RaylibAMD_SceneCheckTrees
@@ -198,6 +198,7 @@ struct RankCtx {
 	DevBuf<float4> qRays;
 	DevBuf<void> qOut, qPrim;  // a host call's first output; its second (primitives, counts)
 	DevBuf<void> qContact;     // a host contacts call's records (RaylibAMD_OverlapContacts), staged as qPrim is
+	DevBuf<void> qPlane3, qPlane4, qPlane5, qPlane6;   // a host G-buffer call's fourth to seventh plane (RaylibAMD_RenderGBuffer), staged as qPrim is
 	// a distance-field bake's bit volumes (DeviceBakeDistanceField), kept and grown, and the event behind the last bake's last kernel -- every bake waits for it
 	// on its own stream, so that two bakes on two streams never share the volumes at the same time
 	DevBuf<uint32_t> sdfBits;

@@ -1,6 +1,6 @@
 // Host runtime: calls on rays, points and triangles of the caller's, on rank 0's device -- from host memory or from device pointers, on the library's stream
 // (synchronous, with stats) or enqueued on a stream of the caller's (rl_host.h).  Two families and what they share:
-//   The queries -- ray, ordered multi-hit, nearest-point, K-nearest and triangle-overlap queries with their contacts -- are one call (RunQuery) that each entry
+//   The queries -- the camera's G-buffer, ray, ordered multi-hit, nearest-point, K-nearest and triangle-overlap queries with their contacts -- are one call (RunQuery) that each entry
 //   describes by data (QueryDesc: plan, kernel, input records, outputs, dynamic LDS) and gives its launch; a distance-field bake is several launches on the
 //   same pieces.  Their scratch is a ring of work counters with an event per slot (LaunchOnRing).
 //   The path calls -- radiance along caller rays, and the gathers, which are that call with another generator -- share BeginPathCall and PathGrid, one counter
@@ -113,6 +113,7 @@ bool OnDevice(const void* p, int device)
 // An output of a call: the caller's pointer; the bytes the call writes there (0: it writes none -- the pointer was not given, or is not this kind's); the mask
 // of its alignment (15: records stored as one 16-byte word, 3: 4-byte words); the rank's buffer a host call stages it through; and, once StageOutputs has run,
 // the device pointer the kernel gets (null for an output that is not written).
+#define RL_QUERY_OUTS 7   /* the outputs a call may have: a G-buffer's planes (most calls have one to three) */
 struct QueryOut { void* user = nullptr; size_t bytes = 0; uintptr_t align = 3u; DevBuf<void> RankCtx::* stage = nullptr; void* dev = nullptr; };
 // The refusals of a device call (`api`): the input (`what` names its records; null: the call has none) and every output the call writes are memory of the
 // device; the kernels read an input record as 16-byte loads; every output pointer given, written or not, is aligned as its records are stored.
@@ -238,7 +239,7 @@ struct CopyBack {
 	CopyBack(void* host_, const void* dev_, size_t bytes_) : host(host_), dev(dev_), bytes(bytes_) {}
 	CopyBack(const QueryOut& o, bool hostMem) : host(hostMem && o.bytes ? o.user : nullptr), dev(o.dev), bytes(o.bytes) {}   // (only an output the caller gave)
 };
-static bool FinishSync(RankCtx& R, hipStream_t st, std::initializer_list<CopyBack> back, std::chrono::steady_clock::time_point t0, RaylibAMDStats& stats)
+static bool FinishSync(RankCtx& R, hipStream_t st, const std::vector<CopyBack>& back, std::chrono::steady_clock::time_point t0, RaylibAMDStats& stats)
 {
 	HIP_OK(hipEventRecord(R.qEv[1], st));
 	HIP_OK(hipMemcpyAsync(R.qStatsHost.ptr, R.qStats.ptr, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
@@ -282,7 +283,7 @@ struct QueryDesc {
 	const char *api, *apiDevice, *what;
 	const void* in; size_t recordBytes; int32_t n; bool hostMem; void* stream;
 	QueryPlan plan;
-	QueryOut out[3];
+	QueryOut out[RL_QUERY_OUTS];
 	bool slotIndex = false, exportSlot = false;
 	const void* kernel = nullptr; size_t ldsBytes = 0;
 	QueryDesc(const char* api_, const char* apiDevice_, const char* what_, const void* in_, size_t recordBytes_, int32_t n_, bool hostMem_, void* stream_)
@@ -292,7 +293,7 @@ struct QueryDesc {
 // (else null), the grid and the stream
 struct QueryLaunch {
 	const DSceneView& view; const int32_t* slotIndex; const int32_t* exportSlot;
-	const float4* in; void* out[3];
+	const float4* in; void* out[RL_QUERY_OUTS];
 	unsigned int* counter; unsigned long long* stats;
 	dim3 grid; hipStream_t st;
 };
@@ -307,15 +308,15 @@ static bool RunQuery(Scene& sc, QueryDesc& D, RaylibAMDStats& stats, Launch laun
 	RankCtx& R = Rank0();
 	HIP_OK(hipSetDevice(R.device));
 	if (!D.plan.ok) { Log("%s: BVH depth %u exceeds the traversal stack (64)", D.api, sc.bvh.depth); return false; }
-	if (!D.hostMem && D.n > 0 && !DevicePointersOk(D.apiDevice, D.what, R.device, D.in, D.out, 3)) return false;
+	if (!D.hostMem && D.n > 0 && !DevicePointersOk(D.apiDevice, D.what, R.device, D.in, D.out, RL_QUERY_OUTS)) return false;
 	QueryCall U;
 	if (!BeginQueryCall(sc, R, D.plan, D.slotIndex, D.stream, U, stats)) return false;
 	if (D.exportSlot && !EnsureExportSlot(U.Cp, sc)) return false;
 	if (D.n == 0) return true;
 	const hipStream_t st = U.st;
 	const size_t inBytes = (size_t)D.n * D.recordBytes;
-	if (!StageOutputs(R, D.out, 3, D.hostMem)) return false;
-	if (D.hostMem) {
+	if (!StageOutputs(R, D.out, RL_QUERY_OUTS, D.hostMem)) return false;
+	if (D.hostMem && inBytes) {
 		if (!R.qRays.Grow(inBytes)) return false;
 		HIP_OK(hipMemcpyAsync(R.qRays.ptr, D.in, inBytes, hipMemcpyHostToDevice, st));
 	}
@@ -323,12 +324,15 @@ static bool RunQuery(Scene& sc, QueryDesc& D, RaylibAMDStats& stats, Launch laun
 	if (!blocks) return false;
 	const bool launched = LaunchOnRing(R, U.slot, st, [&](unsigned int* counter) -> bool {
 		if (U.sync && !BeginSync(R, st)) return false;
-		launch(QueryLaunch{ U.Cp->view, U.Cp->slotIndex.ptr, U.Cp->exportSlot.ptr, D.hostMem ? R.qRays.ptr : (const float4*)D.in, { D.out[0].dev, D.out[1].dev, D.out[2].dev },
-		                    counter, U.sync ? R.qStats.ptr : nullptr, dim3(blocks), st });
+		QueryLaunch L{ U.Cp->view, U.Cp->slotIndex.ptr, U.Cp->exportSlot.ptr, D.hostMem ? R.qRays.ptr : (const float4*)D.in, {}, counter, U.sync ? R.qStats.ptr : nullptr, dim3(blocks), st };
+		for (int k = 0; k < RL_QUERY_OUTS; ++k) L.out[k] = D.out[k].dev;
+		launch(L);
 		return true;
 	});
 	if (!launched || !U.sync) return launched;
-	return FinishSync(R, st, { CopyBack(D.out[0], D.hostMem), CopyBack(D.out[1], D.hostMem), CopyBack(D.out[2], D.hostMem) }, D.t0, stats);
+	std::vector<CopyBack> back;
+	for (const QueryOut& o : D.out) back.emplace_back(o, D.hostMem);
+	return FinishSync(R, st, back, D.t0, stats);
 }
 
 bool DeviceTraceRays(Scene& sc, int32_t kind, const void* rays, int32_t n, float rayTime, void* out, int32_t* outPrim, bool hostMem, void* stream,
@@ -346,6 +350,50 @@ bool DeviceTraceRays(Scene& sc, int32_t kind, const void* rays, int32_t n, float
 		hipLaunchKernelGGL(kernel, L.grid, dim3(RL_BLOCK), 0, L.st, L.view, L.in, (uint32_t)n, rayTime, L.out[0], (int32_t*)L.out[1], L.slotIndex, L.counter, L.stats);
 	});
 }
+
+// A G-buffer call (RaylibAMD_RenderGBuffer, statements G1 to G6): a query without input records -- the kernel generates the camera's rays -- and with up to
+// seven outputs, the planes asked for, in the order of RaylibAMDGBufferPlanes.  The plan is the SURFACE query's (PlanGBuffer); the call's size, for the grid
+// and the refusals, is the frame's pixels.  The kernel counts no camera samples: a synchronous call reports the frame's pixels as both.
+typedef void (*GBufferKernel)(const DSceneView, const DGBuffer, const int32_t*, unsigned int*, unsigned long long*);
+static GBufferKernel GBufferKernelOf(const QueryPlan& p)
+{
+	if (p.tree == TREE_WIDE8) return (GBufferKernel)k_gbuffer<8, 2 * RL_POOL8_MAXLEVELS, false>;
+	if (p.tree == TREE_GRID4) return p.stack <= 32 ? (GBufferKernel)k_gbuffer<4, 32, false> : (GBufferKernel)k_gbuffer<4, 64, false>;
+	if (p.stack <= 32) return p.prims ? (GBufferKernel)k_gbuffer<2, 32, true> : (GBufferKernel)k_gbuffer<2, 32, false>;
+	return p.prims ? (GBufferKernel)k_gbuffer<2, 64, true> : (GBufferKernel)k_gbuffer<2, 64, false>;
+}
+static_assert(sizeof(RaylibAMDGBufferPlanes) == 7 * sizeof(void*) && RL_QUERY_OUTS >= 7, "a G-buffer's planes are the call's outputs");
+bool DeviceRenderGBuffer(Scene& sc, const RendererSettings& settings, const DCamera& camera, uint64_t seed, const RaylibAMDGBufferPlanes& planes, bool hostMem, void* stream,
+                         RaylibAMDStats& stats)
+{
+	const uint32_t W = settings.viewportWidth, H = settings.viewportHeight;
+	const size_t pixels = (size_t)W * H;   // (1 .. 2^31 - 1: the ABI checked)
+	QueryDesc D("RaylibAMD_RenderGBuffer", "RaylibAMD_RenderGBufferDevice", nullptr, nullptr, 0, (int32_t)pixels, hostMem, stream);
+	D.plan = PlanGBuffer(sc, ReadRenderKnobs());
+	const GBufferKernel kernel = GBufferKernelOf(D.plan);
+	D.kernel = (const void*)kernel;
+	void* const user[7] = { planes.hit, planes.surface, planes.albedo, planes.surfaceNormal, planes.microNormal, planes.texcoord, planes.emission };
+	DevBuf<void> RankCtx::* const stage[7] = { &RankCtx::qOut, &RankCtx::qPrim, &RankCtx::qContact, &RankCtx::qPlane3, &RankCtx::qPlane4, &RankCtx::qPlane5, &RankCtx::qPlane6 };
+	DGBuffer G; memset(&G, 0, sizeof(G));
+	for (int k = 0; k < 7; ++k) {
+		const bool surface = k == 1;
+		D.out[k] = { user[k], user[k] ? pixels * (surface ? sizeof(DHitOut) : sizeof(float4)) : 0, surface ? 3u : 15u, stage[k] };
+		if (user[k]) G.mask |= 1u << k;
+	}
+	D.slotIndex = planes.hit != nullptr;
+	G.camera = camera; G.seed = seed;
+	G.width = W; G.height = H; G.cellsX = (W + 7u) / 8u; G.numCells = G.cellsX * ((H + 7u) / 8u);
+	G.rayTMin = settings.rayTMin;
+	const bool ok = RunQuery(sc, D, stats, [&](const QueryLaunch& L) {
+		G.hit = (float4*)L.out[0]; G.surface = (DHitOut*)L.out[1];
+		G.albedo = (float4*)L.out[2]; G.surfaceNormal = (float4*)L.out[3]; G.microNormal = (float4*)L.out[4]; G.texcoord = (float4*)L.out[5]; G.emission = (float4*)L.out[6];
+		hipLaunchKernelGGL(kernel, L.grid, dim3(RL_BLOCK), 0, L.st, L.view, G, L.slotIndex, L.counter, L.stats);
+	});
+	if (ok && !stream) { stats.cameraSamples = pixels; stats.pixels = pixels; }
+	return ok;
+}
+static_assert(RL_GB_HIT == 1u && RL_GB_SURFACE == 2u && RL_GB_ALBEDO == 4u && RL_GB_SURFACE_NORMAL == 8u && RL_GB_MICRO_NORMAL == 16u && RL_GB_TEXCOORD == 32u && RL_GB_EMISSION == 64u,
+              "the plane mask's bits are in the order of RaylibAMDGBufferPlanes");
 
 // An ordered multi-hit call: rows of maxHits records and, when asked for, a count per ray (staged through qPrim); the launch carries the lanes' lists as
 // dynamic LDS (2 * maxHits * RL_BLOCK words), which its grid's occupancy accounts for.

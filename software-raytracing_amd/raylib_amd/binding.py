@@ -184,6 +184,69 @@ def trace_rays(lib, scene, rays, kind, ray_time=0.0, with_prim=False):
     return (out, prim) if with_prim else out
 
 
+class GBufferPlanes(C.Structure):
+    """include/raylib_amd.h RaylibAMDGBufferPlanes: a null pointer is a plane not asked for."""
+    _fields_ = [(k, C.c_void_p) for k in ("hit", "surface", "albedo", "surfaceNormal", "microNormal", "texcoord", "emission")]
+
+
+GBUFFER_PLANES = tuple(k for k, _ in GBufferPlanes._fields_)
+_GBUFFER_DTYPES = {k: np.dtype("f4") for k in GBUFFER_PLANES}
+_GBUFFER_DTYPES.update(hit=HITT_DTYPE, surface=SURFACE_DTYPE)
+
+
+def plan_gbuffer(lib, scene):
+    """RaylibAMD_PlanGBuffer: (return code, plan dict)."""
+    return _plan(lib, "RaylibAMD_PlanGBuffer", scene)
+
+
+def _gbuffer_names(planes):
+    names = tuple(planes)
+    for k in names:
+        if k not in GBUFFER_PLANES:
+            raise ValueError("unknown G-buffer plane %r" % (k,))
+    return names
+
+
+def gbuffer(lib, scene, camera, w, h, tmin=1e-4, planes=GBUFFER_PLANES):
+    """The primary-hit G-buffer through the host entry (RaylibAMD_RenderGBuffer, statements G1 to G6): a dict of NumPy arrays, one per plane named in `planes` --
+    hit (h, w) HITT_DTYPE, surface (h, w) SURFACE_DTYPE, the colour planes (h, w, 4) float32.  Raises RuntimeError when the library refuses the call."""
+    names = _gbuffer_names(planes)
+    out = {k: np.zeros((h, w) if k in ("hit", "surface") else (h, w, 4), _GBUFFER_DTYPES[k]) for k in names}
+    st = RendererSettings(int(w), int(h), 1, 1, float(tmin), RENDERMODE_DEFAULT)
+    p = GBufferPlanes(**{k: out[k].ctypes.data for k in names})
+    if lib.RaylibAMD_RenderGBuffer(C.byref(st), scene, camera, C.byref(p)) != 1:
+        raise RuntimeError("RaylibAMD_RenderGBuffer refused the call")
+    return out
+
+
+def gbuffer_device(lib, scene, camera, w, h, tmin=1e-4, planes=GBUFFER_PLANES, out=None):
+    """The same through the device entry (RaylibAMD_RenderGBufferDevice) on torch.cuda.current_stream(), as trace_rays: enqueued on a stream of the caller's,
+    synchronous on torch's default stream (synchronised first).  Returns a dict of tensors on the device: hit (h, w, 4) and surface (h, w, 11) int32 words
+    (reinterpret with .view(torch.float32), or move to NumPy and .view(HITT_DTYPE / SURFACE_DTYPE)), the colour planes (h, w, 4) float32.  out: tensors of the
+    caller's to write into, by plane name (contiguous, on the device).  Raises RuntimeError when the library refuses the call."""
+    import torch
+    names = _gbuffer_names(planes)
+    res = {}
+    for k in names:
+        if out is not None and k in out:
+            res[k] = out[k]
+        elif k in ("hit", "surface"):
+            res[k] = torch.empty((h, w, _GBUFFER_DTYPES[k].itemsize // 4), dtype=torch.int32, device="cuda")
+        else:
+            res[k] = torch.empty((h, w, 4), dtype=torch.float32, device="cuda")
+    st = RendererSettings(int(w), int(h), 1, 1, float(tmin), RENDERMODE_DEFAULT)
+    p = GBufferPlanes(**{k: res[k].data_ptr() for k in names})
+    if lib.RaylibAMD_RenderGBufferDevice(C.byref(st), scene, camera, C.byref(p), _ordered(torch.cuda.current_stream())) != 1:
+        raise RuntimeError("RaylibAMD_RenderGBufferDevice refused the call")
+    return res
+
+
+def render_guides(lib, scene, camera, w, h, albedo, micro_normal, tmin=1e-4):
+    """RaylibAMD_RenderGuides into image handles (either may be 0 / None): the denoiser's two guides in one launch.  Returns the library's return code."""
+    st = RendererSettings(int(w), int(h), 1, 1, float(tmin), RENDERMODE_DEFAULT)
+    return lib.RaylibAMD_RenderGuides(C.byref(st), scene, camera, albedo or None, micro_normal or None)
+
+
 MAX_HITS = 16                                       # RAYLIB_AMD_MAX_HITS
 
 
@@ -898,6 +961,10 @@ _EXPORTS = {
     "RaylibAMD_TraceRays": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     "RaylibAMD_TraceRaysDevice": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "RaylibAMD_PlanRayQuery": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(QueryPlan)]),
+    "RaylibAMD_RenderGBuffer": (C.c_int32, [C.POINTER(RendererSettings), C.c_void_p, C.c_void_p, C.POINTER(GBufferPlanes)]),
+    "RaylibAMD_RenderGBufferDevice": (C.c_int32, [C.POINTER(RendererSettings), C.c_void_p, C.c_void_p, C.POINTER(GBufferPlanes), C.c_void_p]),
+    "RaylibAMD_RenderGuides": (C.c_int32, [C.POINTER(RendererSettings), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_PlanGBuffer": (C.c_int32, [C.c_void_p, C.POINTER(QueryPlan)]),
     "RaylibAMD_TraceRadiance": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(PathRay), C.c_int32, C.POINTER(C.c_float)]),
     "RaylibAMD_TraceRadianceDevice": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(PathRay), C.c_int32, C.POINTER(C.c_float), C.c_void_p]),
     "RaylibAMD_PlanRadiance": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(QueryPlan)]),
@@ -1241,6 +1308,14 @@ class SceneSession:
             for ih in imgs:
                 lib.Raylib_DestroyImage(ih)
         return out
+
+    def gbuffer(self, w, h, tmin=1e-4, planes=GBUFFER_PLANES):
+        """RaylibAMD_RenderGBuffer of the session's scene and camera: a dict of NumPy arrays (gbuffer above)."""
+        return gbuffer(self.lib, self.scene, self.camera, w, h, tmin, planes)
+
+    def gbuffer_device(self, w, h, tmin=1e-4, planes=GBUFFER_PLANES, out=None):
+        """RaylibAMD_RenderGBufferDevice on torch's current stream: a dict of tensors (gbuffer_device above)."""
+        return gbuffer_device(self.lib, self.scene, self.camera, w, h, tmin, planes, out)
 
     def render_cells(self, w, h, spp, rank, world, max_path=5, tmin=1e-4, mode=RENDERMODE_DEFAULT):
         """What rank `rank` of `world` renders: its cells back to back, (n_cells*64, 4) float32."""

@@ -8,6 +8,7 @@ bool DeviceRender(Scene&, const RenderRequest&, RaylibAMDStats&) { return false;
 bool DeviceRenderViews(Scene&, const RenderRequest&, const DCamera*, uint32_t, void*, void* const*, RaylibAMDStats&) { return false; }
 bool DeviceClosestHit(Scene&, const float*, int32_t, float, void*) { return false; }
 bool DeviceTraceRays(Scene&, int32_t, const void*, int32_t, float, void*, int32_t*, bool, void*, RaylibAMDStats&) { return false; }
+bool DeviceRenderGBuffer(Scene&, const RendererSettings&, const DCamera&, uint64_t, const RaylibAMDGBufferPlanes&, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceTraceRaysAll(Scene&, const void*, int32_t, int32_t, void*, uint32_t*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceNearestPoints(Scene&, int32_t, const void*, int32_t, void*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceNearestPointsAll(Scene&, const void*, int32_t, int32_t, void*, uint32_t*, bool, void*, RaylibAMDStats&) { return false; }
