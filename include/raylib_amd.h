@@ -218,6 +218,80 @@ RAYLIB_API int32_t RaylibAMD_RenderGuides(const RendererSettings* settings, Scen
  * csrc/rl_plan.cc), early = 0.  No device needed.  Returns 1, -1 when the BVH is deeper than 64 levels, 0 for a null argument or a scene not finalized. */
 RAYLIB_API int32_t RaylibAMD_PlanGBuffer(SceneHandle scene, RaylibAMDQueryPlan* out);
 
+/* ---- temporal reprojection: per-pixel motion and an accumulated history ---------------------------------
+ * Where each pixel's surface point was in the previous frame (a motion plane, a finish stage on the G-buffer's walk: csrc/rl_k_motion.inl), and a blend of
+ * this frame's colour with what the previous result holds there, rejected where the surface differs (csrc/rl_temporal.hip).  The library remembers nothing:
+ * the caller holds last frame's positions (it gave them to RaylibAMD_SceneMoveTriangles), last frame's camera and last frame's outputs.
+ * Arithmetic: float, single IEEE operations without FMA, a / b and sqrt correctly rounded; dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z;
+ * cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x); one source for the device and the host (csrc/rl_motion.h, csrc/rl_temporal.h).
+ * T1  Ray and hit.  G1 and G2 unchanged: the `hit` plane is RaylibAMD_RenderGBuffer's `hit` plane byte for byte, on every tree.
+ * T2  Previous point.  A hit on triangle i of [first, first + count) with the walk's pair (b1, b2), on the vertices p0, p1, p2 = prevPositions + 9 (i - first):
+ *     P' = (p0 + b1 * (p1 - p0)) + b2 * (p2 - p0) per component, and e = P' - o'.  Every other hit (a triangle outside the range, a sphere, a cube -- a
+ *     moving cube is taken where the ray found it): P' = o + t * d with the ray's own origin, and e = P' - o'.  A miss: the point at infinity, e = d.
+ * T3  Projection.  The previous camera's origin, top_left, horizontal, vertical as RaylibAMD_CameraExport gives them (o', c, h, v); a thin-lens camera is
+ *     projected through its lens centre o'.  w = cross(h, v), a = c - o', lambda = dot(a, w) / dot(e, w), q = lambda * e - a,
+ *     s = dot(q, h) / dot(h, h), u = dot(q, v) / dot(v, v), prevX = s * (float)W, prevY = (1.0f - u) * (float)H: the units in which pixel x has s = x / W
+ *     (G1), so an unmoved point lands on its own integer coordinates, up to rounding.  prevT = sqrt(dot(e, e)) for a hit -- the t the previous frame's hit
+ *     plane holds there --, 0 for a miss.
+ * T4  Status.  RAYLIB_AMD_MOTION_NONE with the three floats +0 when lambda is not finite or not > 0 (the point is behind or in the plane of the previous
+ *     camera); else RAYLIB_AMD_MOTION_SURFACE for a hit, RAYLIB_AMD_MOTION_SKY for a miss.  prevX, prevY may lie outside the frame: the consumer decides.
+ * T5  No bit of the motion plane depends on the tree walked, on the lanes, on whether `hit` was asked for, or on fresh against refitted trees.
+ * T6  Refused (0, nothing written): G6's list; both planes null; first < 0, count < 0 or first + count past the scene's triangles; count > 0 with null
+ *     positions; on the host entry a previous position that is not finite (scanned first); a prevCamera that is not a camera; on the device entry a plane or
+ *     the positions off rank 0's device, a plane not 16-byte aligned, positions not 4-byte aligned.
+ * T7  Accumulation, per pixel p = (x, y) with motion record m and hit record c.  Reset -- outColour = (colour.rgb, 1), outLength = 1 -- when m.status is
+ *     NONE, when there is no history, when floor(prevX) or floor(prevY) is outside [-1, 2^31], or when Wsum below is 0.  Else fx = floor(m.prevX),
+ *     wx = m.prevX - fx, ox = 1 - wx, likewise y; the taps (fx + i, fy + j) in the order (0,0), (1,0), (0,1), (1,1) with weights ox * oy, wx * oy, ox * wy,
+ *     wx * wy.  A tap counts when it lies in the frame, its weight is > 0, history.length > 0 there, history.hit.prim == c.prim (-1, the sky, matches -1),
+ *     and, for SURFACE, |history.hit.t - m.prevT| <= depthTolerance * m.prevT.  In tap order from 0: Wsum += w, S.rgb += w * history.colour.rgb,
+ *     L += w * history.length.  hist = S / Wsum, n = L / Wsum, n' = min(n + 1, maxLength), outColour.rgb = hist + (colour - hist) / n', alpha 1,
+ *     outLength = n'.  With identity motion this is the running mean of the frames bit for bit; after a disocclusion it restarts.
+ * T8  Accumulation refused (0, nothing written): a null params, colour, hit, motion, outColour or outLength; a history with a null member; W or H equal to 0 or
+ *     W * H above 2^31 - 1; depthTolerance not finite or < 0; maxLength not finite or < 1; an output plane that is one of the history's planes (the taps read
+ *     neighbours, so in place is a race); no device; on the device entry a pointer off rank 0's device, a colour, hit or motion plane not 16-byte aligned or
+ *     a length plane not 4-byte aligned.
+ * Still out: variance / moment planes and neighbourhood colour clamping; an ImageHandle entry; a views-batch twin; motion for spheres and moving cubes;
+ * splitting over ranks. */
+typedef struct RaylibAMDMotion { float prevX, prevY, prevT; uint32_t status; } RaylibAMDMotion;   /* 16 bytes */
+#define RAYLIB_AMD_MOTION_NONE    0   /* no previous position: zeros */
+#define RAYLIB_AMD_MOTION_SURFACE 1
+#define RAYLIB_AMD_MOTION_SKY     2
+typedef struct RaylibAMDMotionPlanes { RaylibAMDHitT* hit; RaylibAMDMotion* motion; } RaylibAMDMotionPlanes;   /* either may be NULL, not both */
+typedef struct RaylibAMDMotionParams {
+	CameraHandle prevCamera;          /* 0: the current camera */
+	int32_t first, count;             /* triangles [first, first + count) in RaylibAMD_SceneExportTriangles order had other vertices last frame */
+	const float* prevPositions;       /* count x 9 floats, RaylibAMD_SceneMoveTriangles' layout; host memory on the host entry, rank 0's device memory on the
+	                                     device entry; NULL with count == 0 */
+} RaylibAMDMotionParams;
+/* Planes and previous positions in host memory; synchronous, with RaylibAMD_RenderGBuffer's stats (rays, cameraSamples = pixels = W * H, kernelMs, ...). */
+RAYLIB_API int32_t RaylibAMD_RenderMotion(const RendererSettings* settings, SceneHandle scene, CameraHandle camera, const RaylibAMDMotionParams* params,
+        const RaylibAMDMotionPlanes* hostPlanes);
+/* The same on device pointers, under RaylibAMD_RenderGBufferDevice's rules for the stream, the ordering behind a move enqueued there, the stats and the ranks. */
+RAYLIB_API int32_t RaylibAMD_RenderMotionDevice(const RendererSettings* settings, SceneHandle scene, CameraHandle camera, const RaylibAMDMotionParams* params,
+        const RaylibAMDMotionPlanes* devicePlanes, void* stream);
+/* T2 to T4 on the host, without a device and without a walk: `rays` holds W * H records of 7 floats as RaylibAMD_EvalCameraRays returns them (origin,
+ * direction, time; the time is not read) and `hit` the frame's hit plane.  `camera` is the previous camera when params->prevCamera is 0.  The scene gives the
+ * range its bound and nothing else.  Refusals: T6's that need no device. */
+RAYLIB_API int32_t RaylibAMD_MotionHost(uint32_t width, uint32_t height, SceneHandle scene, CameraHandle camera, const RaylibAMDMotionParams* params,
+        const float* rays, const RaylibAMDHitT* hit, RaylibAMDMotion* outMotion);
+/* RaylibAMD_PlanGBuffer's answer: the motion launch walks what the G-buffer walks. */
+RAYLIB_API int32_t RaylibAMD_PlanMotion(SceneHandle scene, RaylibAMDQueryPlan* out);
+
+typedef struct RaylibAMDTemporalParams { float depthTolerance; float maxLength; } RaylibAMDTemporalParams;   /* relative, finite, >= 0;  >= 1, finite */
+typedef struct RaylibAMDTemporalFrame { const float* colour; const RaylibAMDHitT* hit; const float* length; } RaylibAMDTemporalFrame;   /* W*H*4 floats, W*H records, W*H floats */
+/* T7 on arrays in host memory; synchronous, with stats (pixels = W * H, kernelMs, wallMs, ranks = 1).  colour: W * H * 4 floats (what RaylibAMD_RenderDevice
+ * leaves at cellFirst 0, cellStride 1, or any such plane); history: the previous call's outColour, that frame's hit plane and its outLength, or NULL for the
+ * first frame. */
+RAYLIB_API int32_t RaylibAMD_TemporalAccumulate(uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
+        const RaylibAMDMotion* motion, const RaylibAMDTemporalFrame* history, float* outColour, float* outLength);
+/* The same on pointers of rank 0's device: stream == NULL is the library's stream, synchronous, with stats; with a hipStream_t the launch is enqueued there --
+ * behind a RaylibAMD_RenderMotionDevice enqueued there, with no host synchronisation between them -- and the stats are left alone. */
+RAYLIB_API int32_t RaylibAMD_TemporalAccumulateDevice(uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
+        const RaylibAMDMotion* motion, const RaylibAMDTemporalFrame* history, float* outColour, float* outLength, void* stream);
+/* The host oracle: the same arrays, no device. */
+RAYLIB_API int32_t RaylibAMD_TemporalAccumulateHost(uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
+        const RaylibAMDMotion* motion, const RaylibAMDTemporalFrame* history, float* outColour, float* outLength);
+
 /* ---- ordered multi-hit ray queries -------------------------------------------------------------
  * The first maxHits surfaces a ray crosses, in order, and how many it crosses in all: ordered transparency and depth peeling, thickness and x-ray views,
  * shell and CSG tests, the inside / outside parity of a point -- in one walk of the tree, where peeling with CLOSEST walks it once per layer.

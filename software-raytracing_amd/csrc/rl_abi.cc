@@ -12,6 +12,8 @@
 #include "rl_sdf.h"
 #include "rl_overlap.h"
 #include "rl_contact.h"
+#include "rl_motion.h"
+#include "rl_temporal.h"
 #include "raylib_amd_rng.h"
 
 #include <float.h>
@@ -936,6 +938,137 @@ int32_t RaylibAMD_PlanGBuffer(SceneHandle sh, RaylibAMDQueryPlan* out)
 	if (!s || !s->finalized || !out) return 0;
 	const QueryPlan p = PlanGBuffer(*s, ReadRenderKnobs());
 	return ExportPlan(p, p.prims, 0, out);
+}
+
+// RaylibAMD_RenderMotion / RaylibAMD_RenderMotionDevice / RaylibAMD_MotionHost / RaylibAMD_PlanMotion (statements T1 to T6): what the params add to the
+// G-buffer's refusals -- the range, the positions (a host call's are scanned) and the previous camera, which is `camera` when the params name none
+static bool MotionParamsValid(const char* who, const Scene* s, const RaylibAMDMotionParams* p, bool hostMem)
+{
+	if (!p) { Log("%s: null argument", who); return false; }
+	if (p->first < 0 || p->count < 0 || (int64_t)p->first + (int64_t)p->count > (int64_t)s->triangles.size()) {
+		Log("%s: triangles [%d, %d + %d) are not the scene's", who, p->first, p->first, p->count); return false;
+	}
+	if (p->count > 0 && !p->prevPositions) { Log("%s: null previous positions", who); return false; }
+	if (hostMem) for (size_t i = 0; i < (size_t)p->count * 9; ++i) if (!std::isfinite(p->prevPositions[i])) { Log("%s: a previous position is not finite", who); return false; }
+	if (p->prevCamera && !g_cameras.contains((Camera*)p->prevCamera)) { Log("%s: unknown previous camera", who); return false; }
+	return true;
+}
+static int32_t RenderMotionInternal(const char* who, const RendererSettings* settings, SceneHandle sh, CameraHandle ch, const RaylibAMDMotionParams* params,
+                                    const RaylibAMDMotionPlanes* planes, bool hostMem, void* stream)
+{
+	Scene* s = (Scene*)sh; Camera* c = (Camera*)ch;
+	if (!planes) { Log("%s: null argument", who); return 0; }
+	if (!GBufferArgsValid(who, settings, s, c)) return 0;
+	if (!planes->hit && !planes->motion) { Log("%s: no plane asked for", who); return 0; }
+	if (!MotionParamsValid(who, s, params, hostMem)) return 0;
+	const Camera* pc = params->prevCamera ? (const Camera*)params->prevCamera : c;
+	return RunOnDevice(stream, [&](RaylibAMDStats& stats) {
+		if (!PrepareShutter(who, s, c)) return false;
+		return DeviceRenderMotion(*s, *settings, c->ToDevice(), pc->ToDevice(), CurrentSeed(), params->first, params->count, params->prevPositions, *planes, hostMem, stream, stats);
+	});
+}
+int32_t RaylibAMD_RenderMotion(const RendererSettings* settings, SceneHandle scene, CameraHandle camera, const RaylibAMDMotionParams* params, const RaylibAMDMotionPlanes* hostPlanes)
+{
+	return RenderMotionInternal("RaylibAMD_RenderMotion", settings, scene, camera, params, hostPlanes, true, nullptr);
+}
+int32_t RaylibAMD_RenderMotionDevice(const RendererSettings* settings, SceneHandle scene, CameraHandle camera, const RaylibAMDMotionParams* params,
+                                     const RaylibAMDMotionPlanes* devicePlanes, void* stream)
+{
+	return RenderMotionInternal("RaylibAMD_RenderMotionDevice", settings, scene, camera, params, devicePlanes, false, stream);
+}
+int32_t RaylibAMD_MotionHost(uint32_t width, uint32_t height, SceneHandle sh, CameraHandle ch, const RaylibAMDMotionParams* params, const float* rays, const RaylibAMDHitT* hit,
+                             RaylibAMDMotion* outMotion)
+{
+	static const char* who = "RaylibAMD_MotionHost";
+	Scene* s = (Scene*)sh; Camera* c = (Camera*)ch;
+	if (!s || !c || !rays || !hit || !outMotion) { Log("%s: null argument", who); return 0; }
+	const uint64_t pixels = (uint64_t)width * height;
+	if (pixels == 0 || pixels > 0x7fffffffull) { Log("%s: a frame of %u x %u pixels (1 .. 2^31 - 1)", who, width, height); return 0; }
+	if (!s->finalized) { Log("%s: scene was not finalized (Raylib_FinalizeScene)", who); return 0; }
+	if (!MotionParamsValid(who, s, params, true)) return 0;
+	const DCamera pc = (params->prevCamera ? (const Camera*)params->prevCamera : c)->ToDevice();
+	for (size_t p = 0; p < (size_t)pixels; ++p) {
+		const float* r = rays + 7 * p;
+		RaylibAMDHitT h; memcpy(&h, hit + p, sizeof(h));
+		const bool isHit = h.prim >= 0;
+		float P[3] = { r[3], r[4], r[5] };
+		if (isHit) {
+			const int64_t k = (int64_t)h.prim - params->first;
+			if (h.prim < RAYLIB_AMD_PRIM_SPHERE && k >= 0 && k < params->count) MotionTrianglePoint(params->prevPositions + 9 * (size_t)k, h.b1, h.b2, P);
+			else MotionRayPoint(r, r + 3, h.t, P);
+		}
+		float o[3];
+		RaylibAMDMotion m;
+		m.status = MotionProject(pc.origin, pc.top_left, pc.horizontal, pc.vertical, (float)width, (float)height, isHit, P, o);
+		m.prevX = o[0]; m.prevY = o[1]; m.prevT = o[2];
+		memcpy(outMotion + p, &m, sizeof(m));
+	}
+	return 1;
+}
+int32_t RaylibAMD_PlanMotion(SceneHandle scene, RaylibAMDQueryPlan* out) { return RaylibAMD_PlanGBuffer(scene, out); }
+
+// RaylibAMD_TemporalAccumulate / ...Device / ...Host (statements T7 and T8): the refusals every entry shares
+static bool TemporalArgsValid(const char* who, uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
+                              const RaylibAMDMotion* motion, const RaylibAMDTemporalFrame* history, const float* outColour, const float* outLength)
+{
+	if (!params || !colour || !hit || !motion || !outColour || !outLength || (history && (!history->colour || !history->hit || !history->length))) {
+		Log("%s: null argument", who); return false;
+	}
+	const uint64_t pixels = (uint64_t)width * height;
+	if (pixels == 0 || pixels > 0x7fffffffull) { Log("%s: a frame of %u x %u pixels (1 .. 2^31 - 1)", who, width, height); return false; }
+	if (!std::isfinite(params->depthTolerance) || params->depthTolerance < 0.0f) { Log("%s: depthTolerance %g is not a finite number >= 0", who, params->depthTolerance); return false; }
+	if (!std::isfinite(params->maxLength) || params->maxLength < 1.0f) { Log("%s: maxLength %g is not a finite number >= 1", who, params->maxLength); return false; }
+	if (history && (outColour == history->colour || outLength == history->length)) {
+		Log("%s: an output plane is one of the history's: the taps read neighbours, in place is a race", who); return false;
+	}
+	return true;
+}
+static int32_t TemporalInternal(const char* who, uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
+                                const RaylibAMDMotion* motion, const RaylibAMDTemporalFrame* history, float* outColour, float* outLength, bool hostMem, void* stream)
+{
+	if (!TemporalArgsValid(who, width, height, params, colour, hit, motion, history, outColour, outLength)) return 0;
+	return RunOnDevice(stream, [&](RaylibAMDStats& stats) {
+		return DeviceTemporalAccumulate(width, height, *params, colour, hit, motion, history, outColour, outLength, hostMem, stream, stats);
+	});
+}
+int32_t RaylibAMD_TemporalAccumulate(uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
+                                     const RaylibAMDMotion* motion, const RaylibAMDTemporalFrame* history, float* outColour, float* outLength)
+{
+	return TemporalInternal("RaylibAMD_TemporalAccumulate", width, height, params, colour, hit, motion, history, outColour, outLength, true, nullptr);
+}
+int32_t RaylibAMD_TemporalAccumulateDevice(uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
+                                           const RaylibAMDMotion* motion, const RaylibAMDTemporalFrame* history, float* outColour, float* outLength, void* stream)
+{
+	return TemporalInternal("RaylibAMD_TemporalAccumulateDevice", width, height, params, colour, hit, motion, history, outColour, outLength, false, stream);
+}
+namespace {
+// the oracle's reads: arrays of any alignment
+struct HostTaps {
+	const float* colour; const RaylibAMDHitT* hit; const float* length;
+	bool Has() const { return colour != nullptr; }
+	TemporalTap Read(size_t q) const
+	{
+		TemporalTap t; RaylibAMDHitT h;
+		memcpy(&h, hit + q, sizeof(h));
+		memcpy(&t.r, colour + 4 * q, 3 * sizeof(float));
+		t.t = h.t; t.prim = h.prim; memcpy(&t.length, length + q, sizeof(float));
+		return t;
+	}
+};
+}
+int32_t RaylibAMD_TemporalAccumulateHost(uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
+                                         const RaylibAMDMotion* motion, const RaylibAMDTemporalFrame* history, float* outColour, float* outLength)
+{
+	if (!TemporalArgsValid("RaylibAMD_TemporalAccumulateHost", width, height, params, colour, hit, motion, history, outColour, outLength)) return 0;
+	const HostTaps taps = { history ? history->colour : nullptr, history ? history->hit : nullptr, history ? history->length : nullptr };
+	for (size_t p = 0; p < (size_t)width * height; ++p) {
+		RaylibAMDHitT h; RaylibAMDMotion m; float c[3], o[4], len;
+		memcpy(&h, hit + p, sizeof(h)); memcpy(&m, motion + p, sizeof(m)); memcpy(c, colour + 4 * p, sizeof(c));
+		TemporalPixel(width, height, c, h.prim, m.prevX, m.prevY, m.prevT, m.status, params->depthTolerance, params->maxLength, taps, o, len);
+		o[3] = 1.0f;
+		memcpy(outColour + 4 * p, o, sizeof(o)); memcpy(outLength + p, &len, sizeof(len));
+	}
+	return 1;
 }
 
 // RaylibAMD_TraceRaysAll / RaylibAMD_TraceRaysAllDevice / RaylibAMD_TraceRaysAllHost / RaylibAMD_PlanRayQueryAll (statements M1 to M5): the refusals every entry shares

@@ -275,6 +275,15 @@ bool DeviceTraceRays(Scene& scene, int32_t kind, const void* rays, int32_t n, fl
 // finalized and its boxes built for the camera's shutter interval: the ABI checked.
 bool DeviceRenderGBuffer(Scene& scene, const RendererSettings& settings, const DCamera& camera, uint64_t seed, const RaylibAMDGBufferPlanes& planes, bool hostMem, void* stream,
                          RaylibAMDStats& stats);
+// RaylibAMD_RenderMotion (hostMem: the planes and the previous positions are host memory) and RaylibAMD_RenderMotionDevice, as DeviceRenderGBuffer: the hit
+// and the motion plane, whichever was asked for, with the previous camera and the previous positions of triangles [first, first + count).  What
+// DeviceRenderGBuffer expects of the ABI, and: a plane is asked for, the range lies in the scene's triangles, positions are given when count > 0.
+bool DeviceRenderMotion(Scene& scene, const RendererSettings& settings, const DCamera& camera, const DCamera& prevCamera, uint64_t seed, int32_t first, int32_t count,
+                        const float* prevPositions, const RaylibAMDMotionPlanes& planes, bool hostMem, void* stream, RaylibAMDStats& stats);
+// RaylibAMD_TemporalAccumulate (hostMem) and RaylibAMD_TemporalAccumulateDevice on rank 0's device, behind frames in flight (stream: as DeviceTraceRays).  history
+// is null or has three planes; the frame has 1 .. 2^31 - 1 pixels, the parameters are in range, no output is a history plane: the ABI checked.
+bool DeviceTemporalAccumulate(uint32_t width, uint32_t height, const RaylibAMDTemporalParams& params, const float* colour, const RaylibAMDHitT* hit, const RaylibAMDMotion* motion,
+                              const RaylibAMDTemporalFrame* history, float* outColour, float* outLength, bool hostMem, void* stream, RaylibAMDStats& stats);
 // RaylibAMD_TraceRaysAll (hostMem) and RaylibAMD_TraceRaysAllDevice, as DeviceTraceRays: outHits holds n rows of maxHits records, outCount (may be null) n words.
 // The scene holds triangles only, 1 <= maxHits <= RAYLIB_AMD_MAX_HITS and n * maxHits fits an int32_t: the ABI checked.
 bool DeviceTraceRaysAll(Scene& scene, const void* rays, int32_t n, int32_t maxHits, void* outHits, uint32_t* outCount, bool hostMem, void* stream, RaylibAMDStats& stats);

@@ -11,6 +11,9 @@
 //   rl_query.hip         k_query (RaylibAMD_TraceRays): beside the render kernels it would change how the walks they share are inlined into those
 //   rl_gbuffer.hip       k_gbuffer (RaylibAMD_RenderGBuffer): k_aov's camera rays and debug modes on k_query's driver and walks, with the render's hit rule -- the
 //                        query unit widens the candidate rule, so this one is apart from it, and from the render kernels for k_query's reason
+//   rl_motion.hip        k_motion (RaylibAMD_RenderMotion): k_gbuffer's pixels, rays and walks with another finish -- the hit plane and the motion plane
+//                        (rl_motion.h); apart so that k_gbuffer and every other unit stay the code they are
+//   rl_temporal.hip      k_temporal (RaylibAMD_TemporalAccumulate): a streaming kernel on planes (rl_temporal.h); no scene, no walk
 //   rl_multihit.hip      k_query_all (RaylibAMD_TraceRaysAll): the binary and the 8-wide walk again with a sorted list behind the triangle test, written on the
 //                        shared steps; apart so that k_query and every other unit stay the code they are
 //   rl_nearest.hip       k_nearest (RaylibAMD_NearestPoints): a walk of its own (point-to-box distances, no ray), which shares with the others the records and the
@@ -202,6 +205,34 @@ template <int TREE, int STACK, bool PRIMS> __global__ void __launch_bounds__(RL_
 #define RL_GBUFFER_INSTANCES(X) X(2, 32, false) X(2, 32, true) X(2, 64, false) X(2, 64, true) X(4, 32, false) X(4, 64, false) X(8, 2 * RL_POOL8_MAXLEVELS, false)
 #define RL_K_GBUFFER(a, b, c) template __global__ void k_gbuffer<a, b, c>(RL_GBUFFER_ARGS);
 RL_GBUFFER_INSTANCES(extern RL_K_GBUFFER)
+
+// ---------------------------------------------------------------------------
+// The motion plane (RaylibAMD_RenderMotion, statements T1 to T6; rl_k_motion.inl).  The launch is a G-buffer's (DGBuffer: the frame, the camera, the seed,
+// rayTMin, and of the planes `hit` alone, mask RL_GB_HIT or 0) with the previous frame beside it: the previous camera, the range of triangles that had other
+// vertices, their previous positions (nine floats each; null with count 0) and the motion plane (float4 {prevX, prevY, prevT, status}; null: not asked for).
+struct DMotion {
+	DCamera prevCamera;
+	int32_t first, count;
+	const float* prevPositions;
+	float4* motion;
+};
+#define RL_MOTION_ARGS const DSceneView, const DGBuffer, const DMotion, const int32_t* __restrict__, unsigned int* __restrict__, unsigned long long* __restrict__
+template <int TREE, int STACK, bool PRIMS> __global__ void __launch_bounds__(RL_BLOCK) k_motion(RL_MOTION_ARGS);
+// one instance per instance of k_gbuffer (rl_rt_rays.hip MotionKernelOf)
+#define RL_K_MOTION(a, b, c) template __global__ void k_motion<a, b, c>(RL_MOTION_ARGS);
+RL_GBUFFER_INSTANCES(extern RL_K_MOTION)
+
+// ---------------------------------------------------------------------------
+// The temporal accumulation (RaylibAMD_TemporalAccumulate, statements T7 and T8; rl_temporal.hip).  Planes of width * height records: this frame's colour, hit
+// and motion (float4 each), the history's colour, hit (float4) and length (float) -- all three null on the first frame --, and the two outputs.
+struct DTemporal {
+	uint32_t width, height, cellsX, numCells;
+	float depthTolerance, maxLength;
+	const float4 *colour, *hit, *motion;
+	const float4 *histColour, *histHit; const float* histLength;
+	float4* outColour; float* outLength;
+};
+__global__ void __launch_bounds__(RL_BLOCK) k_temporal(const DTemporal);
 
 // ---------------------------------------------------------------------------
 // The ordered multi-hit ray queries (RaylibAMD_TraceRaysAll; rl_k_multihit.inl)

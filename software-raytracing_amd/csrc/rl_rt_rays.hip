@@ -116,13 +116,14 @@ bool OnDevice(const void* p, int device)
 #define RL_QUERY_OUTS 7   /* the outputs a call may have: a G-buffer's planes (most calls have one to three) */
 struct QueryOut { void* user = nullptr; size_t bytes = 0; uintptr_t align = 3u; DevBuf<void> RankCtx::* stage = nullptr; void* dev = nullptr; };
 // The refusals of a device call (`api`): the input (`what` names its records; null: the call has none) and every output the call writes are memory of the
-// device; the kernels read an input record as 16-byte loads; every output pointer given, written or not, is aligned as its records are stored.
-static bool DevicePointersOk(const char* api, const char* what, int device, const void* in, const QueryOut* outs, size_t numOuts)
+// device; the kernels read an input record as 16-byte loads (inAlign 15; 3: as 4-byte words); every output pointer given, written or not, is aligned as its
+// records are stored.
+static bool DevicePointersOk(const char* api, const char* what, int device, const void* in, const QueryOut* outs, size_t numOuts, uintptr_t inAlign = 15u)
 {
 	bool onDevice = !what || OnDevice(in, device);
 	for (size_t k = 0; k < numOuts; ++k) if (outs[k].bytes && !OnDevice(outs[k].user, device)) onDevice = false;
 	if (!onDevice) { Log("%s: a pointer is not device memory of device %d", api, device); return false; }
-	if (what && ((uintptr_t)in & 15u) != 0) { Log("%s: the %s are not 16-byte aligned", api, what); return false; }
+	if (what && ((uintptr_t)in & inAlign) != 0) { Log("%s: the %s are not %u-byte aligned", api, what, (unsigned)inAlign + 1u); return false; }
 	for (size_t k = 0; k < numOuts; ++k)
 		if (((uintptr_t)outs[k].user & outs[k].align) != 0) { Log("%s: the output is not %u-byte aligned", api, (unsigned)outs[k].align + 1u); return false; }
 	return true;
@@ -277,17 +278,19 @@ static bool BeginQueryCall(Scene& sc, RankCtx& R, const QueryPlan& plan, bool wa
 // What an entry says of its call.  It is made first in the entry: the clock starts and the runtime lock is taken there, so the entry plans under the lock.
 // api / apiDevice: the entry's names in the log, `what` its input records'; recordBytes: 32 (rays), 16 (points) or 48 (triangles); out: the outputs in the
 // order of the kernel's arguments; slotIndex / exportSlot: the call needs that table of the scene's on the device; ldsBytes: the launch's dynamic LDS.
+// inBytes / inAlign: n records of recordBytes read as 16-byte loads, unless the entry says otherwise (a motion call's input is not a record per pixel).
 struct QueryDesc {
 	const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
 	const std::lock_guard<std::mutex> lock{ Rt().lock };
 	const char *api, *apiDevice, *what;
 	const void* in; size_t recordBytes; int32_t n; bool hostMem; void* stream;
+	size_t inBytes; uintptr_t inAlign = 15u;
 	QueryPlan plan;
 	QueryOut out[RL_QUERY_OUTS];
 	bool slotIndex = false, exportSlot = false;
 	const void* kernel = nullptr; size_t ldsBytes = 0;
 	QueryDesc(const char* api_, const char* apiDevice_, const char* what_, const void* in_, size_t recordBytes_, int32_t n_, bool hostMem_, void* stream_)
-		: api(api_), apiDevice(apiDevice_), what(what_), in(in_), recordBytes(recordBytes_), n(n_), hostMem(hostMem_), stream(stream_) {}
+		: api(api_), apiDevice(apiDevice_), what(what_), in(in_), recordBytes(recordBytes_), n(n_), hostMem(hostMem_), stream(stream_), inBytes((size_t)n_ * recordBytes_) {}
 };
 // what the entry's launch gets: the scene, the input and the outputs on the device (null: not written), the work counter, a synchronous call's counter block
 // (else null), the grid and the stream
@@ -308,13 +311,13 @@ static bool RunQuery(Scene& sc, QueryDesc& D, RaylibAMDStats& stats, Launch laun
 	RankCtx& R = Rank0();
 	HIP_OK(hipSetDevice(R.device));
 	if (!D.plan.ok) { Log("%s: BVH depth %u exceeds the traversal stack (64)", D.api, sc.bvh.depth); return false; }
-	if (!D.hostMem && D.n > 0 && !DevicePointersOk(D.apiDevice, D.what, R.device, D.in, D.out, RL_QUERY_OUTS)) return false;
+	if (!D.hostMem && D.n > 0 && !DevicePointersOk(D.apiDevice, D.what, R.device, D.in, D.out, RL_QUERY_OUTS, D.inAlign)) return false;
 	QueryCall U;
 	if (!BeginQueryCall(sc, R, D.plan, D.slotIndex, D.stream, U, stats)) return false;
 	if (D.exportSlot && !EnsureExportSlot(U.Cp, sc)) return false;
 	if (D.n == 0) return true;
 	const hipStream_t st = U.st;
-	const size_t inBytes = (size_t)D.n * D.recordBytes;
+	const size_t inBytes = D.inBytes;
 	if (!StageOutputs(R, D.out, RL_QUERY_OUTS, D.hostMem)) return false;
 	if (D.hostMem && inBytes) {
 		if (!R.qRays.Grow(inBytes)) return false;
@@ -394,6 +397,113 @@ bool DeviceRenderGBuffer(Scene& sc, const RendererSettings& settings, const DCam
 }
 static_assert(RL_GB_HIT == 1u && RL_GB_SURFACE == 2u && RL_GB_ALBEDO == 4u && RL_GB_SURFACE_NORMAL == 8u && RL_GB_MICRO_NORMAL == 16u && RL_GB_TEXCOORD == 32u && RL_GB_EMISSION == 64u,
               "the plane mask's bits are in the order of RaylibAMDGBufferPlanes");
+
+// A motion call (RaylibAMD_RenderMotion, statements T1 to T6): a G-buffer call with two outputs, the hit plane and the motion plane, and with an input -- the
+// previous positions of the moved range, count * 9 floats read as 4-byte words, none when count is 0.  The plan is the G-buffer's; the slot table is always
+// needed (the range is in the scene's triangle order).
+typedef void (*MotionKernel)(const DSceneView, const DGBuffer, const DMotion, const int32_t*, unsigned int*, unsigned long long*);
+static MotionKernel MotionKernelOf(const QueryPlan& p)
+{
+	if (p.tree == TREE_WIDE8) return (MotionKernel)k_motion<8, 2 * RL_POOL8_MAXLEVELS, false>;
+	if (p.tree == TREE_GRID4) return p.stack <= 32 ? (MotionKernel)k_motion<4, 32, false> : (MotionKernel)k_motion<4, 64, false>;
+	if (p.stack <= 32) return p.prims ? (MotionKernel)k_motion<2, 32, true> : (MotionKernel)k_motion<2, 32, false>;
+	return p.prims ? (MotionKernel)k_motion<2, 64, true> : (MotionKernel)k_motion<2, 64, false>;
+}
+static_assert(sizeof(RaylibAMDMotion) == sizeof(float4), "motion records");
+bool DeviceRenderMotion(Scene& sc, const RendererSettings& settings, const DCamera& camera, const DCamera& prevCamera, uint64_t seed, int32_t first, int32_t count,
+                        const float* prevPositions, const RaylibAMDMotionPlanes& planes, bool hostMem, void* stream, RaylibAMDStats& stats)
+{
+	const uint32_t W = settings.viewportWidth, H = settings.viewportHeight;
+	const size_t pixels = (size_t)W * H;   // (1 .. 2^31 - 1: the ABI checked)
+	QueryDesc D("RaylibAMD_RenderMotion", "RaylibAMD_RenderMotionDevice", count > 0 ? "previous positions" : nullptr, count > 0 ? prevPositions : nullptr, 0, (int32_t)pixels,
+	            hostMem, stream);
+	D.inBytes = (size_t)count * 9u * sizeof(float); D.inAlign = 3u;
+	D.plan = PlanGBuffer(sc, ReadRenderKnobs());
+	const MotionKernel kernel = MotionKernelOf(D.plan);
+	D.kernel = (const void*)kernel;
+	D.out[0] = { planes.hit, planes.hit ? pixels * sizeof(float4) : 0, 15u, &RankCtx::qOut };
+	D.out[1] = { planes.motion, planes.motion ? pixels * sizeof(float4) : 0, 15u, &RankCtx::qPrim };
+	D.slotIndex = true;
+	DGBuffer G; memset(&G, 0, sizeof(G));
+	G.mask = planes.hit ? RL_GB_HIT : 0u;
+	G.camera = camera; G.seed = seed;
+	G.width = W; G.height = H; G.cellsX = (W + 7u) / 8u; G.numCells = G.cellsX * ((H + 7u) / 8u);
+	G.rayTMin = settings.rayTMin;
+	DMotion M; memset(&M, 0, sizeof(M));
+	M.prevCamera = prevCamera; M.first = first; M.count = count;
+	const bool ok = RunQuery(sc, D, stats, [&](const QueryLaunch& L) {
+		G.hit = (float4*)L.out[0];
+		M.motion = (float4*)L.out[1]; M.prevPositions = count > 0 ? (const float*)L.in : nullptr;
+		hipLaunchKernelGGL(kernel, L.grid, dim3(RL_BLOCK), 0, L.st, L.view, G, M, L.slotIndex, L.counter, L.stats);
+	});
+	if (ok && !stream) { stats.cameraSamples = pixels; stats.pixels = pixels; }
+	return ok;
+}
+
+// A temporal accumulation (RaylibAMD_TemporalAccumulate, statements T7 and T8): no scene, no plan, no work counter -- planes in, planes out, on rank 0's
+// device.  A host call stages its inputs back to back in qRays (every plane's size is a multiple of 16 bytes but the length plane's, which comes last) and
+// its outputs through qOut and qPrim.  A synchronous call brackets the kernel with the queries' event pair.
+static_assert(sizeof(RaylibAMDHitT) == sizeof(float4), "hit records");
+bool DeviceTemporalAccumulate(uint32_t W, uint32_t H, const RaylibAMDTemporalParams& params, const float* colour, const RaylibAMDHitT* hit, const RaylibAMDMotion* motion,
+                              const RaylibAMDTemporalFrame* history, float* outColour, float* outLength, bool hostMem, void* stream, RaylibAMDStats& stats)
+{
+	static const char* api = "RaylibAMD_TemporalAccumulate";
+	const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+	const std::lock_guard<std::mutex> lock{ Rt().lock };
+	if (!EnsureRuntime()) return false;
+	RankCtx& R = Rank0();
+	HIP_OK(hipSetDevice(R.device));
+	const size_t pixels = (size_t)W * H, plane = pixels * sizeof(float4), lengths = pixels * sizeof(float);
+	const void* in[6] = { colour, hit, motion, history ? history->colour : nullptr, history ? (const void*)history->hit : nullptr, history ? history->length : nullptr };
+	const size_t inBytes[6] = { plane, plane, plane, history ? plane : 0, history ? plane : 0, history ? lengths : 0 };
+	QueryOut out[2] = { { outColour, plane, 15u, &RankCtx::qOut }, { outLength, lengths, 3u, &RankCtx::qPrim } };
+	if (!hostMem) {
+		bool onDevice = true;
+		for (int k = 0; k < 6; ++k) if (inBytes[k] && !OnDevice(in[k], R.device)) onDevice = false;
+		if (!onDevice) { Log("%sDevice: a pointer is not device memory of device %d", api, R.device); return false; }
+		for (int k = 0; k < 6; ++k)
+			if (inBytes[k] && ((uintptr_t)in[k] & (k == 5 ? 3u : 15u)) != 0) { Log("%sDevice: an input plane is not %u-byte aligned", api, k == 5 ? 4u : 16u); return false; }
+		if (!DevicePointersOk("RaylibAMD_TemporalAccumulateDevice", nullptr, R.device, nullptr, out, 2)) return false;
+	}
+	const hipStream_t st = stream ? (hipStream_t)stream : R.stream;
+	const bool sync = !stream;
+	if (sync && !EnsureSyncStats(R)) return false;
+	memset(&stats, 0, sizeof(stats));
+	stats.ranks = 1; stats.devices = 1;
+	if (!StageOutputs(R, out, 2, hostMem)) return false;
+	const void* dev[6];
+	if (hostMem) {
+		size_t total = 0;
+		for (int k = 0; k < 6; ++k) total += inBytes[k];
+		if (!R.qRays.Grow(total)) return false;
+		size_t at = 0;
+		for (int k = 0; k < 6; ++k) {
+			dev[k] = inBytes[k] ? (const char*)R.qRays.ptr + at : nullptr;
+			if (inBytes[k]) HIP_OK(hipMemcpyAsync((void*)dev[k], in[k], inBytes[k], hipMemcpyHostToDevice, st));
+			at += inBytes[k];
+		}
+	} else {
+		for (int k = 0; k < 6; ++k) dev[k] = in[k];
+	}
+	DTemporal T; memset(&T, 0, sizeof(T));
+	T.width = W; T.height = H; T.cellsX = (W + 7u) / 8u; T.numCells = T.cellsX * ((H + 7u) / 8u);
+	T.depthTolerance = params.depthTolerance; T.maxLength = params.maxLength;
+	T.colour = (const float4*)dev[0]; T.hit = (const float4*)dev[1]; T.motion = (const float4*)dev[2];
+	T.histColour = (const float4*)dev[3]; T.histHit = (const float4*)dev[4]; T.histLength = (const float*)dev[5];
+	T.outColour = (float4*)out[0].dev; T.outLength = (float*)out[1].dev;
+	// a wave per cell at a time: workgroups enough for the cells, at most the device filled once at the kernel's occupancy
+	const int perCU = OccupancyOf(R, (const void*)k_temporal);
+	if (perCU < 0) return false;
+	const uint64_t cellBlocks = ((uint64_t)T.numCells + RL_BLOCK / 64u - 1u) / (RL_BLOCK / 64u);
+	const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)R.numCUs * (uint64_t)std::max(1, perCU), cellBlocks));
+	if (sync && !BeginSync(R, st)) return false;
+	hipLaunchKernelGGL(k_temporal, dim3(blocks), dim3(RL_BLOCK), 0, st, T);
+	HIP_OK(hipGetLastError());
+	if (!sync) return true;
+	const bool ok = FinishSync(R, st, { CopyBack(out[0], hostMem), CopyBack(out[1], hostMem) }, t0, stats);
+	if (ok) stats.pixels = pixels;
+	return ok;
+}
 
 // An ordered multi-hit call: rows of maxHits records and, when asked for, a count per ray (staged through qPrim); the launch carries the lanes' lists as
 // dynamic LDS (2 * maxHits * RL_BLOCK words), which its grid's occupancy accounts for.

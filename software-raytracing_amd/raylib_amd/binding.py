@@ -247,6 +247,126 @@ def render_guides(lib, scene, camera, w, h, albedo, micro_normal, tmin=1e-4):
     return lib.RaylibAMD_RenderGuides(C.byref(st), scene, camera, albedo or None, micro_normal or None)
 
 
+MOTION_NONE, MOTION_SURFACE, MOTION_SKY = 0, 1, 2   # RAYLIB_AMD_MOTION_*
+MOTION_DTYPE = np.dtype([("prevX", "f4"), ("prevY", "f4"), ("prevT", "f4"), ("status", "u4")])
+
+
+class MotionPlanes(C.Structure):
+    """include/raylib_amd.h RaylibAMDMotionPlanes: a null pointer is a plane not asked for."""
+    _fields_ = [("hit", C.c_void_p), ("motion", C.c_void_p)]
+
+
+class MotionParams(C.Structure):
+    """include/raylib_amd.h RaylibAMDMotionParams."""
+    _fields_ = [("prevCamera", C.c_void_p), ("first", C.c_int32), ("count", C.c_int32), ("prevPositions", C.c_void_p)]
+
+
+class TemporalParams(C.Structure):
+    """include/raylib_amd.h RaylibAMDTemporalParams."""
+    _fields_ = [("depthTolerance", C.c_float), ("maxLength", C.c_float)]
+
+
+class TemporalFrame(C.Structure):
+    """include/raylib_amd.h RaylibAMDTemporalFrame: the previous call's colour, that frame's hit plane, its length plane."""
+    _fields_ = [("colour", C.c_void_p), ("hit", C.c_void_p), ("length", C.c_void_p)]
+
+
+def plan_motion(lib, scene):
+    """RaylibAMD_PlanMotion: (return code, plan dict)."""
+    return _plan(lib, "RaylibAMD_PlanMotion", scene)
+
+
+def _motion_names(planes):
+    names = tuple(planes)
+    for k in names:
+        if k not in ("hit", "motion"):
+            raise ValueError("unknown motion plane %r" % (k,))
+    return names
+
+
+def motion(lib, scene, camera, w, h, prev_camera=None, first=0, prev_positions=None, tmin=1e-4, planes=("hit", "motion")):
+    """The motion plane and / or the hit plane through the host entry (RaylibAMD_RenderMotion, statements T1 to T6): a dict of NumPy arrays, hit (h, w) HITT_DTYPE
+    and motion (h, w) MOTION_DTYPE.  prev_positions: (count, 9) float32, last frame's vertices of triangles [first, first + count), or None.  Raises
+    RuntimeError when the library refuses the call."""
+    names = _motion_names(planes)
+    out = {k: np.zeros((h, w), HITT_DTYPE if k == "hit" else MOTION_DTYPE) for k in names}
+    pp = None if prev_positions is None else np.ascontiguousarray(prev_positions, np.float32).reshape(-1, 9)
+    prm = MotionParams(prev_camera or None, int(first), 0 if pp is None else len(pp), None if pp is None else pp.ctypes.data)
+    st = RendererSettings(int(w), int(h), 1, 1, float(tmin), RENDERMODE_DEFAULT)
+    p = MotionPlanes(**{k: out[k].ctypes.data for k in names})
+    if lib.RaylibAMD_RenderMotion(C.byref(st), scene, camera, C.byref(prm), C.byref(p)) != 1:
+        raise RuntimeError("RaylibAMD_RenderMotion refused the call")
+    return out
+
+
+def motion_device(lib, scene, camera, w, h, prev_camera=None, first=0, prev_positions=None, tmin=1e-4, planes=("hit", "motion"), out=None):
+    """The same through the device entry (RaylibAMD_RenderMotionDevice) on torch.cuda.current_stream(), as gbuffer_device.  prev_positions: a contiguous float32
+    tensor of count * 9 elements on the device, or None.  Returns a dict of (h, w, 4) int32 tensors on the device (move to NumPy and .view(HITT_DTYPE /
+    MOTION_DTYPE)); out: tensors of the caller's to write into, by plane name.  Raises RuntimeError when the library refuses the call."""
+    import torch
+    names = _motion_names(planes)
+    res = {k: out[k] if out is not None and k in out else torch.empty((h, w, 4), dtype=torch.int32, device="cuda") for k in names}
+    count = 0 if prev_positions is None else prev_positions.numel() // 9
+    prm = MotionParams(prev_camera or None, int(first), int(count), None if prev_positions is None else prev_positions.data_ptr())
+    st = RendererSettings(int(w), int(h), 1, 1, float(tmin), RENDERMODE_DEFAULT)
+    p = MotionPlanes(**{k: res[k].data_ptr() for k in names})
+    if lib.RaylibAMD_RenderMotionDevice(C.byref(st), scene, camera, C.byref(prm), C.byref(p), _ordered(torch.cuda.current_stream())) != 1:
+        raise RuntimeError("RaylibAMD_RenderMotionDevice refused the call")
+    return res
+
+
+def motion_host(lib, scene, camera, w, h, rays, hit, prev_camera=None, first=0, prev_positions=None):
+    """RaylibAMD_MotionHost, the oracle of the motion plane: no device, no walk.  rays: (w * h, 7) float32 as RaylibAMD_EvalCameraRays returns them; hit: the
+    frame's hit plane (HITT_DTYPE).  Returns (h, w) MOTION_DTYPE.  Raises RuntimeError when the library refuses the call."""
+    rays = np.ascontiguousarray(rays, np.float32)
+    hit = np.ascontiguousarray(hit, HITT_DTYPE)
+    assert rays.size == w * h * 7 and hit.size == w * h
+    out = np.zeros((h, w), MOTION_DTYPE)
+    pp = None if prev_positions is None else np.ascontiguousarray(prev_positions, np.float32).reshape(-1, 9)
+    prm = MotionParams(prev_camera or None, int(first), 0 if pp is None else len(pp), None if pp is None else pp.ctypes.data)
+    if lib.RaylibAMD_MotionHost(int(w), int(h), scene, camera, C.byref(prm), rays.ctypes.data, hit.ctypes.data, out.ctypes.data) != 1:
+        raise RuntimeError("RaylibAMD_MotionHost refused the call")
+    return out
+
+
+def temporal_accumulate(lib, colour, hit, motion, history=None, depth_tolerance=0.02, max_length=32.0, host=False):
+    """RaylibAMD_TemporalAccumulate on NumPy arrays (host=True: RaylibAMD_TemporalAccumulateHost, the oracle, no device): colour (h, w, 4) float32, hit (h, w)
+    HITT_DTYPE, motion (h, w) MOTION_DTYPE, history None or the (colour, hit, length) of the previous frame.  Returns (outColour (h, w, 4), outLength (h, w)).
+    Raises RuntimeError when the library refuses the call."""
+    colour = np.ascontiguousarray(colour, np.float32)
+    h, w = colour.shape[:2]
+    hit = np.ascontiguousarray(hit, HITT_DTYPE)
+    motion = np.ascontiguousarray(motion, MOTION_DTYPE)
+    assert colour.shape == (h, w, 4) and hit.size == w * h and motion.size == w * h
+    keep = None
+    hist = None
+    if history is not None:
+        keep = (np.ascontiguousarray(history[0], np.float32), np.ascontiguousarray(history[1], HITT_DTYPE), np.ascontiguousarray(history[2], np.float32))
+        assert keep[0].size == w * h * 4 and keep[1].size == w * h and keep[2].size == w * h
+        hist = C.byref(TemporalFrame(*[a.ctypes.data for a in keep]))
+    out_c, out_l = np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.float32)
+    entry = "RaylibAMD_TemporalAccumulateHost" if host else "RaylibAMD_TemporalAccumulate"
+    prm = TemporalParams(float(depth_tolerance), float(max_length))
+    if getattr(lib, entry)(int(w), int(h), C.byref(prm), colour.ctypes.data, hit.ctypes.data, motion.ctypes.data, hist, out_c.ctypes.data, out_l.ctypes.data) != 1:
+        raise RuntimeError(entry + " refused the call")
+    return out_c, out_l
+
+
+def temporal_accumulate_device(lib, colour, hit, motion, history=None, depth_tolerance=0.02, max_length=32.0, out=None):
+    """RaylibAMD_TemporalAccumulateDevice on torch.cuda.current_stream(), as gbuffer_device: colour (h, w, 4) float32, hit and motion (h, w, 4) int32 as
+    motion_device returns them, history None or (colour, hit, length) tensors of the previous frame; all contiguous, on the device.  out: (outColour, outLength)
+    tensors to write into.  Returns (outColour (h, w, 4) float32, outLength (h, w) float32).  Raises RuntimeError when the library refuses the call."""
+    import torch
+    h, w = colour.shape[:2]
+    out_c, out_l = out if out is not None else (torch.empty((h, w, 4), dtype=torch.float32, device="cuda"), torch.empty((h, w), dtype=torch.float32, device="cuda"))
+    hist = None if history is None else C.byref(TemporalFrame(*[t.data_ptr() for t in history]))
+    prm = TemporalParams(float(depth_tolerance), float(max_length))
+    if lib.RaylibAMD_TemporalAccumulateDevice(int(w), int(h), C.byref(prm), colour.data_ptr(), hit.data_ptr(), motion.data_ptr(), hist, out_c.data_ptr(), out_l.data_ptr(),
+                                              _ordered(torch.cuda.current_stream())) != 1:
+        raise RuntimeError("RaylibAMD_TemporalAccumulateDevice refused the call")
+    return out_c, out_l
+
+
 MAX_HITS = 16                                       # RAYLIB_AMD_MAX_HITS
 
 
@@ -965,6 +1085,13 @@ _EXPORTS = {
     "RaylibAMD_RenderGBufferDevice": (C.c_int32, [C.POINTER(RendererSettings), C.c_void_p, C.c_void_p, C.POINTER(GBufferPlanes), C.c_void_p]),
     "RaylibAMD_RenderGuides": (C.c_int32, [C.POINTER(RendererSettings), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "RaylibAMD_PlanGBuffer": (C.c_int32, [C.c_void_p, C.POINTER(QueryPlan)]),
+    "RaylibAMD_RenderMotion": (C.c_int32, [C.POINTER(RendererSettings), C.c_void_p, C.c_void_p, C.POINTER(MotionParams), C.POINTER(MotionPlanes)]),
+    "RaylibAMD_RenderMotionDevice": (C.c_int32, [C.POINTER(RendererSettings), C.c_void_p, C.c_void_p, C.POINTER(MotionParams), C.POINTER(MotionPlanes), C.c_void_p]),
+    "RaylibAMD_MotionHost": (C.c_int32, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(MotionParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_PlanMotion": (C.c_int32, [C.c_void_p, C.POINTER(QueryPlan)]),
+    "RaylibAMD_TemporalAccumulate": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(TemporalParams)] + [C.c_void_p] * 3 + [C.POINTER(TemporalFrame)] + [C.c_void_p] * 2),
+    "RaylibAMD_TemporalAccumulateDevice": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(TemporalParams)] + [C.c_void_p] * 3 + [C.POINTER(TemporalFrame)] + [C.c_void_p] * 3),
+    "RaylibAMD_TemporalAccumulateHost": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(TemporalParams)] + [C.c_void_p] * 3 + [C.POINTER(TemporalFrame)] + [C.c_void_p] * 2),
     "RaylibAMD_TraceRadiance": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(PathRay), C.c_int32, C.POINTER(C.c_float)]),
     "RaylibAMD_TraceRadianceDevice": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(PathRay), C.c_int32, C.POINTER(C.c_float), C.c_void_p]),
     "RaylibAMD_PlanRadiance": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(QueryPlan)]),
@@ -1316,6 +1443,26 @@ class SceneSession:
     def gbuffer_device(self, w, h, tmin=1e-4, planes=GBUFFER_PLANES, out=None):
         """RaylibAMD_RenderGBufferDevice on torch's current stream: a dict of tensors (gbuffer_device above)."""
         return gbuffer_device(self.lib, self.scene, self.camera, w, h, tmin, planes, out)
+
+    def motion(self, w, h, prev_camera=None, first=0, prev_positions=None, tmin=1e-4, planes=("hit", "motion")):
+        """RaylibAMD_RenderMotion of the session's scene and camera: a dict of NumPy arrays (motion above)."""
+        return motion(self.lib, self.scene, self.camera, w, h, prev_camera, first, prev_positions, tmin, planes)
+
+    def motion_device(self, w, h, prev_camera=None, first=0, prev_positions=None, tmin=1e-4, planes=("hit", "motion"), out=None):
+        """RaylibAMD_RenderMotionDevice on torch's current stream: a dict of tensors (motion_device above)."""
+        return motion_device(self.lib, self.scene, self.camera, w, h, prev_camera, first, prev_positions, tmin, planes, out)
+
+    def motion_host(self, w, h, rays, hit, prev_camera=None, first=0, prev_positions=None):
+        """RaylibAMD_MotionHost for the session's scene and camera (motion_host above)."""
+        return motion_host(self.lib, self.scene, self.camera, w, h, rays, hit, prev_camera, first, prev_positions)
+
+    def temporal_accumulate(self, colour, hit, motion, history=None, depth_tolerance=0.02, max_length=32.0, host=False):
+        """RaylibAMD_TemporalAccumulate / ...Host on NumPy arrays (temporal_accumulate above; the call needs no scene)."""
+        return temporal_accumulate(self.lib, colour, hit, motion, history, depth_tolerance, max_length, host)
+
+    def temporal_accumulate_device(self, colour, hit, motion, history=None, depth_tolerance=0.02, max_length=32.0, out=None):
+        """RaylibAMD_TemporalAccumulateDevice on torch's current stream (temporal_accumulate_device above)."""
+        return temporal_accumulate_device(self.lib, colour, hit, motion, history, depth_tolerance, max_length, out)
 
     def render_cells(self, w, h, spp, rank, world, max_path=5, tmin=1e-4, mode=RENDERMODE_DEFAULT):
         """What rank `rank` of `world` renders: its cells back to back, (n_cells*64, 4) float32."""
