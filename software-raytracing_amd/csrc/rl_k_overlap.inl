@@ -16,9 +16,14 @@
 // twice.  The list orders by export index, which says nothing about where a triangle lies, so a full list prunes nothing and LIST always walks to the end.
 // The contacts kind (k_overlap_contacts: RaylibAMD_OverlapContacts) is LIST up to write-out; there every held entry gets its record (rl_contact.h, statements C1
 // to C6).  It carries two more arguments, so it is a kernel of its own name, and it is this file's text a second time: rl_overlap.hip includes the file once
-// plainly, which gives k_overlap exactly as it was before there were contacts, and once under RL_OVERLAP_CONTACTS_PASS, which gives k_overlap_contacts.  (A body
-// shared through an inlined function would be one text too, but the compiler schedules the eight older instances differently then; this way they stay the
-// code they are.)  The list is keyed by export index and the record needs the triangle's slot: a table, export index -> slot, beside slotIndex (4 bytes per
+// plainly, which gives k_overlap, and once under RL_OVERLAP_CONTACTS_PASS, which gives k_overlap_contacts.
+// The walk stays written here, and so do the grid node's decode in it and the counter fold; only the isect record's vertices and the chunk claim come from
+// rl_dev_boxwalk.h.  Measured (profiles/box_walk_ab.log): with the walk as a function of that header which both kernels called -- one
+// inclusion, no pass macro -- every instance compiled to another schedule, and k_overlap<4, ANY> ran 1.004 to 1.012 of the parent's time in every job, over
+// the run-to-run spread; one body for both kernels with the walk inside it brought that to 1.003 - 1.007, still over it in two rows of four.  Even the fold as
+// a function changes all twelve schedules.  With what is shared now the twelve instances are the parent's, instruction for instruction
+// (profiles/box_walk_isa_equivalence.log).
+// The list is keyed by export index and the record needs the triangle's slot: a table, export index -> slot, beside slotIndex (4 bytes per
 // triangle) gives it, so the dynamic LDS and with it the occupancy stay LIST's.
 
 #ifndef RL_OVERLAP_CONTACTS_PASS
@@ -30,9 +35,8 @@ __device__ __forceinline__ bool OverlapLeaf(const DSceneView& S, const float q0[
 {
 	for (int i = 0; i < count; ++i) {
 		const int slot = first + i;
-		const float4* tp = (const float4*)(S.isect + slot);
-		const float4 r0 = GLoadF4(tp, 0), r1 = GLoadF4(tp, 1), r2 = GLoadF4(tp, 2);
-		const float v0[3] = { r0.x, r0.y, r0.z }, v1[3] = { r1.z, r1.w, r2.x }, v2[3] = { r2.y, r2.z, r2.w };
+		float v0[3], v1[3], v2[3];
+		IsectVertices(S, slot, v0, v1, v2);
 		++tris;
 		if (!OverlapAccepts(q0, q1, q2, loQ, hiQ, v0, v1, v2, skipShared)) continue;
 		if (KIND == RL_OK_ANY) return true;
@@ -84,9 +88,7 @@ k_overlap_contacts(const DSceneView S, const float4* __restrict__ queries, uint3
 	uint32_t cQueries = 0u, cNodes = 0u, cTris = 0u;
 	const int DONE = 0x7fffffff;   // not a node index, not negative
 	for (;;) {
-		uint32_t base = 0u;
-		if (lane == 0u) base = atomicAdd(queryCounter, RL_QUERY_CHUNK);
-		base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+		const uint32_t base = ClaimChunk(queryCounter, RL_QUERY_CHUNK, lane);
 		if (base >= n) break;
 		for (uint32_t k = 0; k < RL_QUERY_CHUNK; k += 64u) {
 			const uint32_t i = base + k + lane;
@@ -157,9 +159,9 @@ k_overlap_contacts(const DSceneView S, const float4* __restrict__ queries, uint3
 					float4 c0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c1 = c0;
 					if (e < held) {
 						const int32_t idx = (int32_t)list[e * RL_BLOCK];
-						const float4* tp = (const float4*)(S.isect + (exportSlot ? exportSlot[idx] : idx));
-						const float4 r0 = GLoadF4(tp, 0), r1 = GLoadF4(tp, 1), r2 = GLoadF4(tp, 2);
-						const float v0[3] = { r0.x, r0.y, r0.z }, v1[3] = { r1.z, r1.w, r2.x }, v2[3] = { r2.y, r2.z, r2.w };
+						const int slot = exportSlot ? exportSlot[idx] : idx;
+						float v0[3], v1[3], v2[3];
+						IsectVertices(S, slot, v0, v1, v2);
 						const ContactRecord R = ContactOfPair(q0, q1, q2, v0, v1, v2);
 						c0 = make_float4(R.p0[0], R.p0[1], R.p0[2], __uint_as_float(R.kind));
 						c1 = make_float4(R.p1[0], R.p1[1], R.p1[2], __uint_as_float(R.features));

@@ -1,13 +1,13 @@
 // k_sdf_rows, k_sdf_parity, k_sdf_dist: a signed distance field baked on the device (include/raylib_amd.h RaylibAMD_BakeDistanceField, statements V1 to V7).
-// rl_sdf.hip includes this file behind rl_k_query.inl (NextUpF, QueryTMin and k_query's schedule are that file's) and instantiates the kernels; every other
-// unit stays the code it is.  No point, ray or result record exists: a voxel's point and a row's ray are made from their indices (SdfCentre, V1), a lane
+// rl_sdf.hip includes this file behind rl_k_query.inl (NextUpF, QueryTMin and k_query's schedule are that file's) and rl_dev_boxwalk.h (the distance kernel's
+// walk and its leaf test) and instantiates the kernels.  No point, ray or result record exists: a voxel's point and a row's ray are made from their indices (SdfCentre, V1), a lane
 // writes its 4-byte value (and 4 bytes of outPrim), and the only scratch is the bit volumes of the sign axes.
 //
 //   k_sdf_rows    one row ray per lane (V3), k_query_all's COUNT walks without a list: the bound stays {NextUpF(tMax), -1}, every accepted crossing comes once,
 //                 and each toggles, in the row's words, bit m = #{i : t_a(i) < t} -- the voxels it lies ahead of are the prefix i < m (t_a is monotone in i),
 //                 so bit m flips the inside bits of that prefix once the parity kernel has run.  m == 0 lies ahead of no voxel and toggles nothing.
 //   k_sdf_parity  per row, in place: bit i becomes the XOR of the toggle bits above i (V4), by the shift-XOR suffix within a word and a carry over the words.
-//   k_sdf_dist    k_nearest's CLOSEST walk with its LDS stack and half-distance column, one 4 x 4 x 4 brick of voxels per wave (partial bricks masked) so
+//   k_sdf_dist    the point walk with k_nearest's CLOSEST leaves, its LDS stack and half-distance column, one 4 x 4 x 4 brick of voxels per wave (partial bricks masked) so
 //                 that a wave's lanes walk the same nodes; a claim is RL_QUERY_CHUNK voxels' worth of bricks from one counter.  V2 and V5 at the store.
 
 // (V1 -- SdfT, SdfCentre -- is rl_sdf.h's, which the host oracle compiles too)
@@ -229,46 +229,13 @@ k_sdf_parity(const DSdfGrid G, uint32_t n, uint32_t* __restrict__ bits)
 	}
 }
 
-// ---- the distance walk: rl_k_nearest.inl's, CLOSEST, on generated points ----
+// ---- the distance walk: rl_dev_boxwalk.h's, with k_nearest's CLOSEST leaf test (the barycentrics it keeps are never read), on generated points ----
 #ifndef RL_SDF_DIST32
 #define RL_SDF_DIST32 2   /* bytes of box distance per stack entry, as RL_NEAREST_DIST32 / 64: the upper half of the float */
 #endif
 #ifndef RL_SDF_DIST64
 #define RL_SDF_DIST64 2
 #endif
-template <int BYTES> struct SdfDist;
-template <> struct SdfDist<0> { typedef float T; static __device__ __forceinline__ T Pack(float) { return 0.0f; } static __device__ __forceinline__ float Unpack(T) { return 0.0f; } };
-template <> struct SdfDist<4> { typedef float T; static __device__ __forceinline__ T Pack(float d) { return d; } static __device__ __forceinline__ float Unpack(T v) { return v; } };
-template <> struct SdfDist<2> {
-	typedef unsigned short T;
-	static __device__ __forceinline__ T Pack(float d) { return (T)(__float_as_uint(d) >> 16); }
-	static __device__ __forceinline__ float Unpack(T v) { return __uint_as_float((uint32_t)v << 16); }
-};
-
-// the walk's state of one voxel: the least D so far and its slot (a distance field keeps no barycentrics)
-struct SdfBest { float d; int slot; };
-
-// one leaf: `count` triangles from slot `first`
-__device__ __forceinline__ void SdfLeaf(const DSceneView& S, const float p[3], int first, int count, SdfBest& best, const int32_t* __restrict__ slotIndex, uint32_t& tris)
-{
-	for (int i = 0; i < count; ++i) {
-		const int slot = first + i;
-		const float4* tp = (const float4*)(S.isect + slot);
-		const float4 q0 = GLoadF4(tp, 0), q1 = GLoadF4(tp, 1), q2 = GLoadF4(tp, 2);
-		const float v0[3] = { q0.x, q0.y, q0.z }, v1[3] = { q1.z, q1.w, q2.x }, v2[3] = { q2.y, q2.z, q2.w };
-		++tris;
-		const float B = NearestOwnBoxDist2(p, v0, v1, v2);
-		if (B > best.d) continue;   // D >= B: not a candidate, and E need not be known
-		float b1, b2;
-		const float D = NearestTriangleD(NearestTriangleE(p, v0, v1, v2, b1, b2), B);
-		if (D > best.d) continue;
-		if (D == best.d && best.slot >= 0) {
-			const int mine = slotIndex ? slotIndex[slot] : slot, theirs = slotIndex ? slotIndex[best.slot] : best.slot;
-			if (mine > theirs) continue;
-		}
-		best.d = D; best.slot = slot;
-	}
-}
 
 // (template and kernel arguments: rl_kernels.h)
 template <int TREE, int STACK, bool SIGNED>
@@ -276,25 +243,20 @@ __global__ void __launch_bounds__(RL_BLOCK)
 k_sdf_dist(const DSceneView S, const DSdfGrid G, float* __restrict__ outDist, int32_t* __restrict__ outPrim, const uint32_t* __restrict__ bits,
            const int32_t* __restrict__ slotIndex, unsigned int* __restrict__ brickCounter, unsigned long long* __restrict__ counters)
 {
-	static_assert(TREE == 2 || TREE == 4, "tree");
 	__shared__ int s_stack[STACK * RL_BLOCK];
 	int* stk = s_stack + threadIdx.x;
-	typedef SdfDist<(STACK <= 32 ? RL_SDF_DIST32 : RL_SDF_DIST64)> Dist;
-	constexpr bool POPD = (STACK <= 32 ? RL_SDF_DIST32 : RL_SDF_DIST64) != 0;
-	__shared__ typename Dist::T s_dist[POPD ? STACK * RL_BLOCK : 1];
-	typename Dist::T* dstk = s_dist + (POPD ? threadIdx.x : 0u);
-#define RL_SDF_PUSH(ref_, d_) { if (sp < STACK) { stk[sp * RL_BLOCK] = (ref_); if constexpr (POPD) dstk[sp * RL_BLOCK] = Dist::Pack(d_); ++sp; } }
+	constexpr int DBYTES = STACK <= 32 ? RL_SDF_DIST32 : RL_SDF_DIST64;
+	typedef NearestDist<DBYTES> Dist;
+	__shared__ typename Dist::T s_dist[DBYTES != 0 ? STACK * RL_BLOCK : 1];
+	typename Dist::T* dstk = s_dist + (DBYTES != 0 ? threadIdx.x : 0u);
 	const uint32_t lane = threadIdx.x & 63u;
 	uint32_t cPoints = 0u, cNodes = 0u, cTris = 0u;
-	const int DONE = 0x7fffffff;   // not a node index, not negative
 	const uint32_t bricksX = (G.dims[0] + 3u) >> 2, bricksY = (G.dims[1] + 3u) >> 2, bricksZ = (G.dims[2] + 3u) >> 2;
 	const uint32_t numBricks = bricksX * bricksY * bricksZ;   // (<= 2^31 - 1 voxels: at most 2^29 + ... bricks, the ABI checked the product)
 	constexpr uint32_t CLAIM = RL_QUERY_CHUNK / 64u;
 	const bool takesPart = G.maxDist >= 0.0f && S.numTriangles > 0;   // (V7 refused a centre that is not finite)
 	for (;;) {
-		uint32_t base = 0u;
-		if (lane == 0u) base = atomicAdd(brickCounter, CLAIM);
-		base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+		const uint32_t base = ClaimChunk(brickCounter, CLAIM, lane);
 		if (base >= numBricks) break;
 		for (uint32_t kb = 0; kb < CLAIM; ++kb) {
 			const uint32_t brick = base + kb;
@@ -304,72 +266,10 @@ k_sdf_dist(const DSceneView S, const DSdfGrid G, float* __restrict__ outDist, in
 			if (vi >= G.dims[0] || vj >= G.dims[1] || vk >= G.dims[2]) continue;   // a partial brick's lanes outside the grid
 			++cPoints;
 			const float p[3] = { SdfCentre(G.origin[0], G.spacing[0], vi), SdfCentre(G.origin[1], G.spacing[1], vj), SdfCentre(G.origin[2], G.spacing[2], vk) };
-			SdfBest best; best.d = G.maxDist * G.maxDist; best.slot = -1;
-			if (takesPart) {
-				int sp = 0, cur = 0;   // the root is an inner node
-				for (;;) {
-					// ---- descend: inner nodes until this lane holds a leaf or has nothing left ----
-					while (cur >= 0 && cur != DONE) {
-						++cNodes;
-						if constexpr (TREE == 2) {
-							const float4* np = (const float4*)(S.nodes + cur);
-							const float4 q0 = GLoadF4(np, 0), q1 = GLoadF4(np, 1), q2 = GLoadF4(np, 2);
-							const uint4 ku = GLoadU4(np, 3);
-							const int kl = (int)ku.x, kr = (int)ku.y;
-							const float dl = NearestBoxDist2(p[0], p[1], p[2], q0.x, q0.y, q0.z, q0.w, q1.x, q1.y);
-							const float dr = NearestBoxDist2(p[0], p[1], p[2], q1.z, q1.w, q2.x, q2.y, q2.z, q2.w);
-							const bool hl = kl != DNODE_EMPTY && !(dl > best.d), hr = kr != DNODE_EMPTY && !(dr > best.d);
-							if (hl && hr) {
-								const bool leftFirst = dl <= dr;
-								RL_SDF_PUSH(leftFirst ? kr : kl, leftFirst ? dr : dl)
-								cur = leftFirst ? kl : kr;
-							} else if (hl) cur = kl;
-							else if (hr) cur = kr;
-							else cur = DONE;
-						} else {
-							// the 64-byte grid node, decoded as k_nearest decodes it: the decoded box contains the float box its planes were rounded outwards from (rl_grid.h)
-							const DNode4Q* np = S.nodes4 + cur;
-							const float4 h0 = GLoadF4(np, 0); const uint4 l = GLoadU4(np, 1), u = GLoadU4(np, 2), chu = GLoadU4(np, 3);
-							const float sx = h0.w, sy = __uint_as_float(l.w), sz = __uint_as_float(u.w);
-							float t0, t1, t2, t3;
-							int r0 = (int)chu.x, r1 = (int)chu.y, r2 = (int)chu.z, r3 = (int)chu.w;
-#define RL_SDF_QBOX(sh, tk, rk) { \
-	const float lox = h0.x + (float)((l.x >> sh) & 0xffu) * sx, hix = h0.x + (float)((u.x >> sh) & 0xffu) * sx; \
-	const float loy = h0.y + (float)((l.y >> sh) & 0xffu) * sy, hiy = h0.y + (float)((u.y >> sh) & 0xffu) * sy; \
-	const float loz = h0.z + (float)((l.z >> sh) & 0xffu) * sz, hiz = h0.z + (float)((u.z >> sh) & 0xffu) * sz; \
-	tk = NearestBoxDist2(p[0], p[1], p[2], lox, loy, loz, hix, hiy, hiz); \
-	/* a dropped child: no reference, behind every kept one */ \
-	if (rk == DNODE_EMPTY || tk > best.d) { rk = DNODE_EMPTY; tk = INFINITY; } }
-							RL_SDF_QBOX(0, t0, r0) RL_SDF_QBOX(8, t1, r1) RL_SDF_QBOX(16, t2, r2) RL_SDF_QBOX(24, t3, r3)
-#undef RL_SDF_QBOX
-							RL_SORT4(t0, r0, t1, r1, t2, r2, t3, r3)
-							// from the farthest to the nearest: the nearest kept child is walked next, the others are pushed farthest first
-							int nr = r3; float nt = t3;
-#define RL_SDF_TAKE(tk, rk) if (rk != DNODE_EMPTY) { if (nr != DNODE_EMPTY) RL_SDF_PUSH(nr, nt) nr = rk; nt = tk; }
-							RL_SDF_TAKE(t2, r2) RL_SDF_TAKE(t1, r1) RL_SDF_TAKE(t0, r0)
-#undef RL_SDF_TAKE
-							cur = nr != DNODE_EMPTY ? nr : DONE;
-						}
-						// nothing kept: the stack's next entry that the best has not passed since it was pushed
-						while (cur == DONE && sp > 0) {
-							--sp;
-							if constexpr (POPD) if (Dist::Unpack(dstk[sp * RL_BLOCK]) > best.d) continue;
-							cur = stk[sp * RL_BLOCK];
-						}
-					}
-					if (cur == DONE) break;
-					// ---- leaf: <= 4 triangles stored back to back ----
-					const LeafRef L = DecodeLeaf(cur);
-					SdfLeaf(S, p, L.first, L.count, best, slotIndex, cTris);
-					cur = DONE;
-					while (cur == DONE && sp > 0) {
-						--sp;
-						if constexpr (POPD) if (Dist::Unpack(dstk[sp * RL_BLOCK]) > best.d) continue;
-						cur = stk[sp * RL_BLOCK];
-					}
-					if (cur == DONE) break;
-				}
-			}
+			NearestBest best; best.d = G.maxDist * G.maxDist; best.slot = -1; best.b1 = best.b2 = 0.0f;
+			if (takesPart)
+				PointWalk<TREE, STACK, DBYTES>(S, p, best.d, stk, dstk, cNodes,
+				                               [&](int first, int count) { return NearestLeaf<RL_NK_CLOSEST>(S, p, first, count, best, slotIndex, cTris); });
 			// V2, V5: the magnitude, then the sign from the inside-bit volumes of the sign axes
 			float m = best.slot < 0 ? G.maxDist : rlm::sqrtf_(best.d);
 			if constexpr (SIGNED) {
@@ -388,13 +288,5 @@ k_sdf_dist(const DSceneView S, const DSdfGrid G, float* __restrict__ outDist, in
 			if (outPrim) outPrim[at] = best.slot < 0 ? -1 : slotIndex ? slotIndex[best.slot] : best.slot;
 		}
 	}
-#undef RL_SDF_PUSH
-	if (counters) {   // wave reduction, one atomic per wave and counter
-		const uint32_t vals[3] = { cPoints, cNodes, cTris };
-		for (int k = 0; k < 3; ++k) {
-			unsigned long long v = vals[k];
-			for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-			if (lane == 0u && v) atomicAdd(&counters[CNT_RAYS + k], v);
-		}
-	}
+	FoldWaveCounters(counters, cPoints, cNodes, cTris, lane);
 }

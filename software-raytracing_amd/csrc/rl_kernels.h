@@ -17,11 +17,11 @@
 //   rl_multihit.hip      k_query_all (RaylibAMD_TraceRaysAll): the binary and the 8-wide walk again with a sorted list behind the triangle test, written on the
 //                        shared steps; apart so that k_query and every other unit stay the code they are
 //   rl_nearest.hip       k_nearest (RaylibAMD_NearestPoints): a walk of its own (point-to-box distances, no ray), which shares with the others the records and the
-//                        child sort alone; apart so that every other unit stays the code it is.  k_nearest_all (RaylibAMD_NearestPointsAll): that walk again with
-//                        a sorted list behind the triangle test
+//                        child sort alone; apart so that every other unit stays the code it is.  k_nearest_all (RaylibAMD_NearestPointsAll): that walk (rl_dev_boxwalk.h
+//                        PointWalk, which this unit, rl_overlap.hip and rl_sdf.hip include) with a sorted list behind the triangle test
 //   rl_overlap.hip       k_overlap (RaylibAMD_OverlapTriangles): a walk of its own again (box against box, no ray, no distance) with a per-lane index list; apart for
 //                        the same reason
-//   rl_sdf.hip           k_sdf_rows, k_sdf_parity, k_sdf_dist (RaylibAMD_BakeDistanceField): k_query_all's counting walks and k_nearest's closest walk written again on
+//   rl_sdf.hip           k_sdf_rows, k_sdf_parity, k_sdf_dist (RaylibAMD_BakeDistanceField): k_query_all's counting walks written again and k_nearest's closest walk (PointWalk) on
 //                        generated rays and points, with a bit volume between them; apart for the same reason
 //   rl_radiance.hip      k_radiance (RaylibAMD_TraceRadiance): the same reason, towards the render and the query kernels alike
 //   rl_gather.hip        k_gather (RaylibAMD_Gather: rl_k_radiance.inl's twin, the generator instances of its loop) and k_gather_resolve: beside k_radiance they would be

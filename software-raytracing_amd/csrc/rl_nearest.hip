@@ -1,5 +1,5 @@
 // The nearest-point queries of RaylibAMD_NearestPoints (k_nearest, rl_k_nearest.inl) and of RaylibAMD_NearestPointsAll (k_nearest_all, rl_k_nearest_all.inl) as
-// a translation unit of their own: walks of their own beside the ray walks, and every other unit stays the code it is (tools/isa_equivalence.py).
+// a translation unit of their own, beside the ray walks: both run the point walk of rl_dev_boxwalk.h.
 
 // ---- settings ----
 // None: single float operations without FMA (the Makefile's -ffp-contract=off) and the compiler's correctly rounded divisions, as the host oracle that
@@ -8,6 +8,7 @@
 // ---- the device library ----
 #include "rl_kernels.h"
 #include "rl_nearest.h"
+#include "rl_dev_boxwalk.h"
 
 namespace rl {
 

@@ -1,5 +1,5 @@
-// The triangle-overlap queries of RaylibAMD_OverlapTriangles (k_overlap, rl_k_overlap.inl) as a translation unit of their own: a new walk beside the ray walks
-// and the nearest-point walk, and every other unit stays the code it is (tools/isa_equivalence.py).
+// The triangle-overlap queries of RaylibAMD_OverlapTriangles and RaylibAMD_OverlapContacts (k_overlap, k_overlap_contacts; rl_k_overlap.inl) as a translation
+// unit of their own, beside the ray walks: a walk of their own (box against box), with the shared pieces of rl_dev_boxwalk.h.
 
 // ---- settings ----
 // None: single float operations without FMA (the Makefile's -ffp-contract=off), as the host oracle that compiles the same statements (rl_overlap.h).
@@ -8,6 +8,7 @@
 #include "rl_kernels.h"
 #include "rl_overlap.h"
 #include "rl_contact.h"
+#include "rl_dev_boxwalk.h"
 
 namespace rl {
 

@@ -1,6 +1,5 @@
 // The distance-field bake of RaylibAMD_BakeDistanceField (k_sdf_rows, k_sdf_parity, k_sdf_dist; rl_k_sdf.inl) as a translation unit of its own: the counting ray
-// walks and the closest-point walk written again on the pieces the other walks share, on rays and points made from voxel indices.  Apart so that the render,
-// query, multi-hit, nearest, overlap, radiance and gather units stay the code they are (tools/isa_equivalence.py).
+// walks written on the pieces the ray walks share, and the point walk of rl_dev_boxwalk.h with k_nearest's leaf test, on rays and points made from voxel indices.
 
 // ---- settings ----
 // The candidate rule's "own box ends before tMin" is widened as in the ray queries' units: a row ray's accepted set is M1's (rl_dev_walk.h OwnBoxPassBox).
@@ -13,6 +12,7 @@
 #include "rl_kernels.h"
 #include "rl_nearest.h"
 #include "rl_sdf.h"
+#include "rl_dev_boxwalk.h"
 
 namespace rl {
 

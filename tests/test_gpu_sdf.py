@@ -2,7 +2,7 @@
 oracle RaylibAMD_BakeDistanceFieldHost -- a loop over every triangle, itself pinned by tests/test_sdf_host.py -- BYTE FOR BYTE, with no tolerance: in every
 sign mode, with and without outPrim, on every tree either walk can take, on grids whose rows spill into a second word and whose bricks are partial, for
 bands that cut nothing, something and everything, on a caller's stream, back to back on the library's bit volumes, after the scene's triangles have moved
-and its trees were refitted or rebuilt, and behind a multi-rank frame in flight."""
+and its trees were refitted or rebuilt, at the capacity edges of the distance kernel's stacks, and behind a multi-rank frame in flight."""
 import ctypes as C
 import os
 import subprocess
@@ -16,6 +16,7 @@ import helpers
 from helpers import scenes
 import move_cases as mc
 import sdf_cases as sc
+import stack_edges as se
 from raylib_amd import binding
 
 pytestmark = pytest.mark.gpu
@@ -229,6 +230,57 @@ def test_stats(gpu_lib, S, monkeypatch):
             st = binding.Stats(); gpu_lib.RaylibAMD_GetLastStats(C.byref(st))
             assert st.rays == nx * ny * nz + rows[sign], (sign, st.as_dict())
             assert st.nodesVisited > 0 and st.trisTested > 0 and st.kernelMs > 0 and st.wallMs >= st.kernelMs and st.treeWidth == near_width, st.as_dict()
+
+
+# the stacks' capacity edges (tests/stack_edges.py): tests/test_gpu_nearest.py's EDGES that plan a walk for the distance kernel -- (scene, RAYLIB_QUERY_TREE, the
+# tree and the stack the planner must pick for it)
+EDGES = [("cone_d32", 2, 2, 32), ("cone_d33", 2, 2, 64), ("cone_d32", 4, 4, 32), ("cone_d33", 4, 4, 64), ("cone_n64", 4, 4, 64), ("chain_l16", 2, 2, 32),
+         ("chain_l17", 2, 2, 64)]
+EDGE_DIMS, EDGE_APEX = (5, 6, 7), (2, 2, 3)
+
+
+def edge_grid(spec):
+    """5 x 6 x 7 voxels (partial bricks on every axis) of a power-of-two spacing near the scene's smallest triangle, voxel EDGE_APEX's centre exactly at the origin
+    -- the apex, where every level's boxes are equally far, nothing is culled before the first leaf and the far child is pushed at every level.  Every operand of
+    V1 is a small multiple of the spacing: each step is exact."""
+    if spec["kind"] == "cone":
+        spacing = 2.0 ** round(float(np.log2(se.cone_scales(spec["n"], spec["ratio"], spec["pace"], spec["size"])[-1])))
+    else:
+        spacing = 2.0 ** -spec["n_chain"]
+    origin = np.array([-(k + 0.5) * spacing for k in EDGE_APEX], np.float32)
+    return origin, np.full(3, spacing, np.float32), EDGE_DIMS
+
+
+@pytest.mark.parametrize("name,env,width,stack", EDGES, ids=["%s-tree%d" % (e[0], e[1]) for e in EDGES])
+def test_stack_capacity_edges(gpu_lib, workdir, monkeypatch, name, env, width, stack):
+    """The distance kernel with its stack exactly full, and one past on the next size: a dropped push shows as a difference from the oracle.  The same voxel centres
+    sent as points are k_nearest's CLOSEST answers, and -- one walk on the same points, however the lanes are cut into bricks or chunks -- its node and
+    triangle counts (an UNSIGNED bake launches the distance kernel alone: test_stats)."""
+    spec = se.SCENES[name]
+    ses, _ = se.make_session(gpu_lib, spec, os.path.join(str(workdir), "sdf_edges"), name)
+    try:
+        tn = se.tree_numbers(gpu_lib, ses.scene)
+        assert (tn["depth"], tn["need4"]) == (spec["depth"], spec["need4"]), tn
+        grid = edge_grid(spec)
+        cen = sc.centres(*grid)
+        k, j, i = EDGE_APEX[2], EDGE_APEX[1], EDGE_APEX[0]
+        assert cen.shape == (7, 6, 5, 3) and not cen[k, j, i].any() and np.isfinite(cen).all(), cen[k, j, i]
+        monkeypatch.setenv("RAYLIB_QUERY_TREE", str(env))
+        rc, near, _ = binding.plan_distance_field(gpu_lib, ses.scene, grid[0], grid[1], grid[2], INF, sc.UNSIGNED)
+        assert rc == 1 and (near["treeWidth"], near["stack"]) == (width, stack), near
+        want = _oracle(gpu_lib, ses, grid, INF, sc.UNSIGNED)
+        assert (want[1] >= 0).all(), "maxDist +inf: every voxel finds a triangle"
+        _same(_device(gpu_lib, ses, grid, INF, sc.UNSIGNED), want, "%s tree %d" % (name, env))
+        baked = binding.Stats(); gpu_lib.RaylibAMD_GetLastStats(C.byref(baked))
+        pts = np.concatenate([cen.reshape(-1, 3), np.full((cen.size // 3, 1), np.inf, np.float32)], 1).astype(np.float32)
+        got = binding.nearest_points(gpu_lib, ses.scene, pts, binding.NEAREST_CLOSEST)
+        asked = binding.Stats(); gpu_lib.RaylibAMD_GetLastStats(C.byref(asked))
+        assert got["prim"].tobytes() == want[1].tobytes(), "%d voxels' triangles are not the nearest query's" % int((got["prim"] != want[1].ravel()).sum())
+        assert np.sqrt(got["dist2"]).tobytes() == want[0].tobytes(), "the magnitude is the exact root of the nearest query's dist2"
+        assert baked.rays == asked.rays == len(pts) and baked.treeWidth == asked.treeWidth == width, (baked.as_dict(), asked.as_dict())
+        assert (baked.nodesVisited, baked.trisTested) == (asked.nodesVisited, asked.trisTested) and baked.nodesVisited > 0, (baked.as_dict(), asked.as_dict())
+    finally:
+        ses.close()
 
 
 def test_behind_a_multi_rank_frame_in_flight(gpu_lib, workdir):
