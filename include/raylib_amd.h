@@ -599,6 +599,59 @@ RAYLIB_API int32_t RaylibAMD_OverlapContactsHost(SceneHandle scene, uint32_t fla
 /* RaylibAMD_PlanOverlap's answer for RAYLIB_AMD_OVERLAP_LIST: the same tree and stack; the instance walked is the contacts one (k_overlap_contacts). */
 RAYLIB_API int32_t RaylibAMD_PlanOverlapContacts(SceneHandle scene, RaylibAMDQueryPlan* out);
 
+/* ---- swept-sphere queries: the first time of impact ------------------------------------------------
+ * The continuous member of the collision family: a sphere of radius r moves from origin to origin + delta, and the call says when, where and on which
+ * triangle it first touches the scene -- the "sphere cast" or "sweep test" of physics and navigation layers, for particles, probes and character spheres that
+ * move farther in a step than their radius.  The result equals a loop over every triangle bit for bit, with no slack factor anywhere, on every tree, fresh or
+ * refitted (csrc/rl_sweep.h holds the statements for the host oracle and the kernel alike, with every operation spelled out; csrc/rl_k_sweep.inl is the walk).
+ * Everything is float, without FMA; a / b, 1.0f / x and sqrt are the IEEE values; dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.  c(t) = origin + t * delta.
+ *   W1. Who takes part.  origin, delta and radius are finite and radius >= 0 (-0.0 is 0).  The reciprocal of each delta component is taken once; a component
+ *        whose reciprocal is not finite (0, or a denormal below 2^-128) is read as 0 everywhere.  Every other query misses.
+ *   W2. The time bound of a box, Bt(lo, hi): the entry time of c's path into the box grown by radius, by slabs -- per axis with delta != 0 near / far =
+ *        ((lo - r) - o) * inv and ((hi + r) - o) * inv, the pair picked by delta's sign; an axis with delta == 0 passes when (lo - r) <= o && o <= (hi + r).
+ *        entry = max(0, nears), exit = min(fars), Bt = every such axis passes && entry <= exit ? entry : +inf.  Every operation rounds monotonically, so a
+ *        box that contains another has Bt no larger, and an outer miss implies an inner miss: the walk culls by time with no widening factor.
+ *   W3. Touching at the start.  With D of N1 to N3 (the nearest-point statements above) at p = origin: when D <= r * r, t = 0, feature 7, and point is N1's q.
+ *   W4. The first impact otherwise: the least t in [0, 1] over seven features in a fixed order, the lower feature number winning ties.  The face: with
+ *        n = cross(ab, ac), len = sqrt(dot(n, n)), s = dot(n, o - v0), a candidate when |s| > r * len and the centre approaches the plane, at
+ *        t = (|s| - r * len) / |dot(n, delta)|; the point is c(t) moved r along the unit normal towards the plane, accepted when it passes the three edge
+ *        functions.  The edges: the ray against the infinite cylinder of radius r about the edge, the smaller root (-b - sqrt(disc)) / a when a > 0 && disc >= 0,
+ *        accepted when the axial parameter lies in [0, 1]; the point is that point of the edge.  The vertices: the ray against the sphere of radius r, the same
+ *        root; the point is the vertex.  (disc is formed from the closest-approach vector, where the difference does not cancel: csrc/rl_sweep.h.)  A NaN
+ *        anywhere (a degenerate triangle) fails its comparison and drops that feature only.  delta == 0 leaves W3 alone.
+ *   W5. The triangle's time.  T = t >= Bt(own box) ? t : Bt(own box), the own box as in N2.  Triangle k is a candidate when T <= 1.  In exact arithmetic
+ *        t >= Bt always holds; the rule moves T at rounding level only and buys that a node with Bt > the best T holds no winner.
+ *   W6. Result.  CLOSEST returns the candidate with the least (T, k) -- ties go to the lower export index -- and writes {T, k, feature, point}.  ANY returns 1
+ *        exactly when a candidate exists.  feature: 0 the face; 1, 2, 3 the edges v0v1, v1v2, v2v0; 4, 5, 6 the vertices v0, v1, v2; 7 the sphere touches at
+ *        the start.  point is the point of the triangle that is touched; the contact normal is (origin + T * delta - point) / radius, the caller's division.
+ *   W7. Independence.  The result does not depend on the tree walked, the order of the walk, how the call is cut into waves, or whether the trees were built
+ *        fresh or refitted by RaylibAMD_SceneMoveTriangles.  After a move the query sees the moved triangles; the host oracle refreshes the host's stale copies first.
+ * radius == 0 is accepted: a segment test whose edge and vertex features are degenerate.  It carries no watertightness promise; RaylibAMD_TraceRays is the
+ * entry for rays.  A zero move answers as RAYLIB_AMD_NEAREST_WITHIN with maxDist = radius does, up to W5 at rounding level.
+ * Refusals (0, nothing written): those of RaylibAMD_NearestPoints, word for word -- a null pointer with n > 0; n < 0; an unknown kind; a scene that is not
+ * finalized; a scene that holds spheres or cubes; a BVH deeper than 64 levels; no device (the device and plain entries); on the device entry a pointer off
+ * rank 0's device, queries not 16-byte aligned, out not 16-byte aligned for CLOSEST or not 4-byte aligned for ANY.  n == 0 returns 1.
+ * Out of scope: capsules and swept triangles; spheres and cubes as targets; moving targets (a sweep against a scene mid-move is the caller's change of frame);
+ * every impact along the move; slide or depenetration response; the 8-wide tree; spreading a batch over devices.
+ * Checked against a loop over every triangle and a float64 geometry check: tests/test_sweep_host.py, tests/test_gpu_sweep.py. */
+typedef struct RaylibAMDSweepQuery { float origin[3]; float radius; float delta[3]; uint32_t reserved; } RaylibAMDSweepQuery; /* 32 bytes, two 16-byte loads; reserved is not read */
+typedef struct RaylibAMDSweepHit   { float t; int32_t prim; int32_t feature; uint32_t reserved0; float point[3]; uint32_t reserved1; } RaylibAMDSweepHit; /* 32 bytes; a miss: prim = -1, every other word 0 */
+#define RAYLIB_AMD_SWEEP_ANY     0   /* out: uint32_t per query, 1 when the move touches a triangle (may stop at the first) */
+#define RAYLIB_AMD_SWEEP_CLOSEST 1   /* out: RaylibAMDSweepHit per query: the first impact */
+/* n queries from host memory, results to host memory; synchronous, on the device.  RaylibAMD_GetLastStats then reports rays (= queries), nodesVisited,
+ * trisTested, kernelMs, wallMs and the tree walked. */
+RAYLIB_API int32_t RaylibAMD_SweepSpheres(SceneHandle scene, int32_t kind, const RaylibAMDSweepQuery* q, int32_t n, void* out);
+/* The same on device pointers (rank 0's device), with the stream, stats, move-ordering and multi-rank rules of RaylibAMD_NearestPointsDevice: stream == NULL
+ * is the library's stream, synchronous, with stats; a non-null hipStream_t gets the call enqueued behind the synchronous uploads and the stats are left alone. */
+RAYLIB_API int32_t RaylibAMD_SweepSpheresDevice(SceneHandle scene, int32_t kind, const RaylibAMDSweepQuery* q, int32_t n, void* out, void* stream);
+/* The oracle: statements W1 to W6 over every triangle, no tree, no device. */
+RAYLIB_API int32_t RaylibAMD_SweepSpheresHost(SceneHandle scene, int32_t kind, const RaylibAMDSweepQuery* q, int32_t n, void* out);
+/* Which tree and kernel instance those calls would walk under the current environment (csrc/rl_plan.cc PlanSweep): RaylibAMD_PlanNearest's trees and stacks
+ * under the same RAYLIB_QUERY_TREE, with RaylibAMD_PlanOverlap's default -- the grid-4 tree while its worst-case stack fits the 32-deep instance, else the
+ * binary tree (measured: profiles/sweep_time.log).  `early` is 1 for ANY.  No device needed.  Returns 1, -1 when the BVH is deeper than 64 levels, 0 for a null argument, an
+ * unknown kind, a scene not finalized or one that holds spheres or cubes. */
+RAYLIB_API int32_t RaylibAMD_PlanSweep(SceneHandle scene, int32_t kind, RaylibAMDQueryPlan* out);
+
 /* ---- path-traced radiance along caller rays -----------------------------------------------------
  * outRGBA[i] = (the mean over the samples of TraceScene(rays[i], depth 0, maxPathLength, rayTMin), 1): the reference's path tracer (render/renderer.cc:114-208)
  * with the scene's sun and sky panorama as a render sees them, on rays that need not come from a camera.  The ray is used as given: neither normalised nor

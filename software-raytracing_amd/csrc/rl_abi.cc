@@ -9,6 +9,7 @@
 #include "rl_progressive.h"
 #include "rl_lightmap.h"
 #include "rl_nearest.h"
+#include "rl_sweep.h"
 #include "rl_sdf.h"
 #include "rl_overlap.h"
 #include "rl_contact.h"
@@ -1229,6 +1230,61 @@ int32_t RaylibAMD_PlanNearest(SceneHandle sh, int32_t kind, RaylibAMDQueryPlan* 
 	Scene* s = (Scene*)sh;
 	if (!s || !s->finalized || !out || (kind != RAYLIB_AMD_NEAREST_WITHIN && kind != RAYLIB_AMD_NEAREST_CLOSEST) || !s->spheres.empty() || !s->cubes.empty()) return 0;
 	const QueryPlan p = PlanNearest(*s, kind, ReadRenderKnobs());
+	return ExportPlan(p, 0, p.early, out);
+}
+
+// RaylibAMD_SweepSpheres / RaylibAMD_SweepSpheresDevice / RaylibAMD_SweepSpheresHost / RaylibAMD_PlanSweep (statements W1 to W7): the refusals every entry shares
+static bool SweepArgsValid(const char* who, const Scene* s, int32_t kind, const void* q, int32_t n, const void* out)
+{
+	if (kind != RAYLIB_AMD_SWEEP_ANY && kind != RAYLIB_AMD_SWEEP_CLOSEST) { Log("%s: unknown sweep kind %d", who, kind); return false; }
+	return TriangleQueryArgsValid(who, "swept-sphere queries", s, q, n, out);
+}
+static int32_t SweepSpheresInternal(const char* who, SceneHandle sh, int32_t kind, const RaylibAMDSweepQuery* q, int32_t n, void* out, bool hostMem, void* stream)
+{
+	Scene* s = (Scene*)sh;
+	if (!SweepArgsValid(who, s, kind, q, n, out)) return 0;
+	return RunOnDevice(stream, [&](RaylibAMDStats& stats) { return DeviceSweepSpheres(*s, kind, q, n, out, hostMem, stream, stats); });
+}
+int32_t RaylibAMD_SweepSpheres(SceneHandle sh, int32_t kind, const RaylibAMDSweepQuery* q, int32_t n, void* out)
+{
+	return SweepSpheresInternal("RaylibAMD_SweepSpheres", sh, kind, q, n, out, true, nullptr);
+}
+int32_t RaylibAMD_SweepSpheresDevice(SceneHandle sh, int32_t kind, const RaylibAMDSweepQuery* q, int32_t n, void* out, void* stream)
+{
+	return SweepSpheresInternal("RaylibAMD_SweepSpheresDevice", sh, kind, q, n, out, false, stream);
+}
+// the oracle: statements W1 to W6 (rl_sweep.h, the kernel's own source) over every triangle in export order
+int32_t RaylibAMD_SweepSpheresHost(SceneHandle sh, int32_t kind, const RaylibAMDSweepQuery* q, int32_t n, void* out)
+{
+	Scene* s = (Scene*)sh;
+	if (!SweepArgsValid("RaylibAMD_SweepSpheresHost", s, kind, q, n, out)) return 0;
+	if (!DeviceSyncMovedScene(*s)) return 0;
+	const size_t numTris = s->triangles.size();
+	for (int32_t i = 0; i < n; ++i) {
+		const RaylibAMDSweepQuery& Q = q[i];
+		RaylibAMDSweepHit best; memset(&best, 0, sizeof(best)); best.prim = -1;
+		SweepMove M;
+		if (SweepTakesPart(Q.origin, Q.delta, Q.radius, M)) {
+			for (size_t k = 0; k < numTris; ++k) {
+				const HostTriangle& tr = s->triangles[k];
+				float t, p[3]; int feature;
+				if (!SweepTriangle(M, &tr.v0.x, &tr.v1.x, &tr.v2.x, t, feature, p)) continue;
+				const float T = SweepTriangleT(t, SweepOwnBoxTime(M, &tr.v0.x, &tr.v1.x, &tr.v2.x));
+				if (!(T <= 1.0f) || (best.prim >= 0 && !(T < best.t))) continue;   // (ascending k: an equal T keeps the lower index)
+				best.t = T; best.prim = (int32_t)k; best.feature = feature; best.point[0] = p[0]; best.point[1] = p[1]; best.point[2] = p[2];
+				if (kind == RAYLIB_AMD_SWEEP_ANY) break;
+			}
+		}
+		if (kind == RAYLIB_AMD_SWEEP_ANY) ((uint32_t*)out)[i] = best.prim >= 0 ? 1u : 0u;
+		else ((RaylibAMDSweepHit*)out)[i] = best;
+	}
+	return 1;
+}
+int32_t RaylibAMD_PlanSweep(SceneHandle sh, int32_t kind, RaylibAMDQueryPlan* out)
+{
+	Scene* s = (Scene*)sh;
+	if (!s || !s->finalized || !out || (kind != RAYLIB_AMD_SWEEP_ANY && kind != RAYLIB_AMD_SWEEP_CLOSEST) || !s->spheres.empty() || !s->cubes.empty()) return 0;
+	const QueryPlan p = PlanSweep(*s, kind, ReadRenderKnobs());
 	return ExportPlan(p, 0, p.early, out);
 }
 

@@ -292,6 +292,8 @@ bool DeviceNearestPoints(Scene& scene, int32_t kind, const void* points, int32_t
 // RaylibAMD_NearestPointsAll (hostMem) and RaylibAMD_NearestPointsAllDevice, as DeviceTraceRaysAll: outHits holds n rows of maxHits records, outCount (may be
 // null) n words.  The scene holds triangles only, 1 <= maxHits <= RAYLIB_AMD_MAX_NEAREST and n * maxHits fits an int32_t: the ABI checked.
 bool DeviceNearestPointsAll(Scene& scene, const void* points, int32_t n, int32_t maxHits, void* outHits, uint32_t* outCount, bool hostMem, void* stream, RaylibAMDStats& stats);
+// RaylibAMD_SweepSpheres (hostMem) and RaylibAMD_SweepSpheresDevice, as DeviceNearestPoints: 32-byte queries, a word (ANY) or a 32-byte record (CLOSEST) out.
+bool DeviceSweepSpheres(Scene& scene, int32_t kind, const void* queries, int32_t n, void* out, bool hostMem, void* stream, RaylibAMDStats& stats);
 // RaylibAMD_BakeDistanceField (hostMem) and RaylibAMD_BakeDistanceFieldDevice, as DeviceNearestPoints: outDist and outPrim (may be null) hold a word per voxel.
 // grid is valid (statement V7) with maxDist >= +0, the scene holds triangles only: the ABI checked.
 bool DeviceBakeDistanceField(Scene& scene, const RaylibAMDDistanceFieldParams& grid, float* outDist, int32_t* outPrim, bool hostMem, void* stream, RaylibAMDStats& stats);

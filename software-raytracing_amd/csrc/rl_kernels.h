@@ -19,6 +19,8 @@
 //   rl_nearest.hip       k_nearest (RaylibAMD_NearestPoints): a walk of its own (point-to-box distances, no ray), which shares with the others the records and the
 //                        child sort alone; apart so that every other unit stays the code it is.  k_nearest_all (RaylibAMD_NearestPointsAll): that walk (rl_dev_boxwalk.h
 //                        PointWalk, which this unit, rl_overlap.hip and rl_sdf.hip include) with a sorted list behind the triangle test
+//   rl_sweep.hip         k_sweep (RaylibAMD_SweepSpheres): the point walk's shape with a time bound in the place of the distance (the entry time of the centre's
+//                        path into a box grown by the radius) and the largest narrow phase of the family; its walk is its own text, so every other unit stays the code it is
 //   rl_overlap.hip       k_overlap (RaylibAMD_OverlapTriangles): a walk of its own again (box against box, no ray, no distance) with a per-lane index list; apart for
 //                        the same reason
 //   rl_sdf.hip           k_sdf_rows, k_sdf_parity, k_sdf_dist (RaylibAMD_BakeDistanceField): k_query_all's counting walks written again and k_nearest's closest walk (PointWalk) on
@@ -273,6 +275,20 @@ template <int TREE, int STACK, bool COUNT> __global__ void __launch_bounds__(RL_
 #define RL_NEAREST_ALL_INSTANCES(X) RL_NEAREST_ALL_INSTANCES_C(X, false) RL_NEAREST_ALL_INSTANCES_C(X, true)
 #define RL_K_NEAREST_ALL(a, b, c) template __global__ void k_nearest_all<a, b, c>(RL_NEAREST_ALL_ARGS);
 RL_NEAREST_ALL_INSTANCES(extern RL_K_NEAREST_ALL)
+
+// ---------------------------------------------------------------------------
+// The swept-sphere queries (RaylibAMD_SweepSpheres; rl_k_sweep.inl, arithmetic of rl_sweep.h)
+enum { RL_SK_ANY = 0, RL_SK_CLOSEST = 1 };   // RAYLIB_AMD_SWEEP_*
+struct DSweepHit { float t; int32_t prim; int32_t feature; uint32_t reserved0; float point[3]; uint32_t reserved1; };   // RaylibAMDSweepHit
+// TREE: 2 the binary tree (S.nodes), 4 the grid nodes (S.nodes4).  STACK: the walk's stack.  queries: n records of two float4 (origin, radius | delta, a word
+// that is not read).  out: uint32_t (ANY) or DSweepHit (CLOSEST, two float4 stores) per query.  slotIndex, counters: as k_nearest's.
+#define RL_SWEEP_ARGS const DSceneView, const float4* __restrict__, uint32_t, void* __restrict__, const int32_t* __restrict__, unsigned int* __restrict__, unsigned long long* __restrict__
+template <int TREE, int KIND, int STACK> __global__ void __launch_bounds__(RL_BLOCK) k_sweep(RL_SWEEP_ARGS);
+// The instances rl_rt_rays.hip SweepKernelOfKind selects from: (TREE, KIND, STACK)
+#define RL_SWEEP_INSTANCES_K(X, K) X(2, K, 32) X(2, K, 64) X(4, K, 32) X(4, K, 64)
+#define RL_SWEEP_INSTANCES(X) RL_SWEEP_INSTANCES_K(X, 0) RL_SWEEP_INSTANCES_K(X, 1)
+#define RL_K_SWEEP(a, b, c) template __global__ void k_sweep<a, b, c>(RL_SWEEP_ARGS);
+RL_SWEEP_INSTANCES(extern RL_K_SWEEP)
 
 // ---------------------------------------------------------------------------
 // The triangle-overlap queries (RaylibAMD_OverlapTriangles; rl_k_overlap.inl, arithmetic of rl_overlap.h)

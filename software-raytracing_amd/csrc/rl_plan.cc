@@ -204,6 +204,19 @@ QueryPlan PlanNearestAll(const Scene& sc, const RenderKnobs& k)
 	return PlanNearest(sc, RAYLIB_AMD_NEAREST_CLOSEST, k);   // k_nearest_all is CLOSEST's walk: its tree, its stack, no early exit
 }
 
+QueryPlan PlanSweep(const Scene& sc, int32_t kind, const RenderKnobs& k)
+{
+	// PlanNearest's trees and stack bounds (k_sweep is the point walk's shape: at most children - 1 pushes per level) with PlanOverlap's default: the grid-4 tree
+	// while its walk is the 32-deep instance, else the binary tree.  Measured on the 298 k-triangle room (profiles/sweep_time.log), where the grid walk is the
+	// 64-deep instance -- 96 KB of LDS, one workgroup per CU for the binary walk's three: 1 M CLOSEST sweeps of 0.1 extents take 2.2 ms on the binary tree and
+	// 4.8 ms on the grid nodes, ANY 1.1 and 2.4 ms, for half the node visits.
+	RenderKnobs asked = k;
+	if (!asked.queryTree) asked.queryTree = (!sc.bvh.nodes4q.empty() && sc.bvh.stackNeed4 <= 32) ? 4 : 2;
+	QueryPlan p = PlanNearest(sc, RAYLIB_AMD_NEAREST_CLOSEST, asked);
+	p.early = kind == RAYLIB_AMD_SWEEP_ANY;
+	return p;
+}
+
 DistanceFieldPlan PlanDistanceField(const Scene& sc, const RenderKnobs& k)
 {
 	DistanceFieldPlan p;

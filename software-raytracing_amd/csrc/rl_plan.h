@@ -96,6 +96,12 @@ QueryPlan PlanNearest(const Scene& sc, int32_t kind, const RenderKnobs& knobs);
 // Which tree and k_nearest_all instance a batch of K-nearest queries walks (RaylibAMD_NearestPointsAll, rl_k_nearest_all.inl): what PlanNearest gives CLOSEST --
 // the walk and its pushes are the same, so is the stack.  `early` is false.  maxHits and the count choose the launch's list bytes and the COUNT instance, not the plan.
 QueryPlan PlanNearestAll(const Scene& sc, const RenderKnobs& knobs);
+// Which tree and k_sweep instance a batch of swept-sphere queries walks (RaylibAMD_SweepSpheres, rl_k_sweep.inl): PlanNearest's trees and stack bounds under the
+// same switch -- the walk pushes at most (children - 1) references per level, as the point walk does -- with PlanOverlap's default: the grid-4 tree when the
+// scene carries one and its worst-case stack fits the 32-deep instance, else the binary tree, which the 298 k-triangle room's sweeps walk in half the time of
+// the 64-deep grid instance (measured: profiles/sweep_time.log).  RAYLIB_QUERY_TREE=4 takes the grid-4 tree up to a worst-case stack of 64 entries, =8 falls
+// through to 4, =2 walks the binary tree.  `early`: the kind is ANY.  The scene holds triangles only.
+QueryPlan PlanSweep(const Scene& sc, int32_t kind, const RenderKnobs& knobs);
 // Which trees a distance-field bake walks (RaylibAMD_BakeDistanceField, rl_k_sdf.inl): the distance kernel is k_nearest's CLOSEST walk, so its plan is
 // PlanNearest's; the row kernel is k_query_all's counting walk, so its plan is PlanQueryAll's.  One RAYLIB_QUERY_TREE steers both.
 struct DistanceFieldPlan { QueryPlan nearest, rows; };

@@ -4,7 +4,7 @@
 //   rl_rt_scene.hip   a flattened scene (rl_scene.cc FlattenScene) to every device, its sky and wide trees; images: read-back, RGB dump, post-processing
 //   rl_rt_frame.hip   kernel selection and the one enqueue path of every render (EnqueueFrame), a rank's one-view render, a batch of views
 //   rl_rt_render.hip  whole frames over N ranks (gather, scatter, two frames in flight), DeviceRender, progressive sessions
-//   rl_rt_rays.hip    caller rays, points and triangles, and the camera's pixels: the queries (DeviceRenderGBuffer, DeviceRenderMotion, DeviceTraceRays, DeviceTraceRaysAll, DeviceNearestPoints, DeviceNearestPointsAll, DeviceOverlapTriangles
+//   rl_rt_rays.hip    caller rays, points and triangles, and the camera's pixels: the queries (DeviceRenderGBuffer, DeviceRenderMotion, DeviceTraceRays, DeviceTraceRaysAll, DeviceNearestPoints, DeviceNearestPointsAll, DeviceSweepSpheres, DeviceOverlapTriangles
 //                     and its contacts: one driver, RunQuery), DeviceBakeDistanceField on the same pieces, DeviceTraceRadiance, DeviceGather (plain and adaptive: one driver, GatherLocked),
 //                     DeviceTemporalAccumulate (planes in, planes out: no scene)
 //   rl_rt_lightmap.hip  lightmaps: DeviceLightmapPoints, DeviceBakeLightmap (the raster stages, then DeviceGather's body or the caller's atlas, the filter, the atlas stages)

@@ -1,6 +1,6 @@
 // Host runtime: calls on rays, points and triangles of the caller's, on rank 0's device -- from host memory or from device pointers, on the library's stream
 // (synchronous, with stats) or enqueued on a stream of the caller's (rl_host.h).  Two families and what they share:
-//   The queries -- the camera's G-buffer, ray, ordered multi-hit, nearest-point, K-nearest and triangle-overlap queries with their contacts -- are one call (RunQuery) that each entry
+//   The queries -- the camera's G-buffer, ray, ordered multi-hit, nearest-point, K-nearest, swept-sphere and triangle-overlap queries with their contacts -- are one call (RunQuery) that each entry
 //   describes by data (QueryDesc: plan, kernel, input records, outputs, dynamic LDS) and gives its launch; a distance-field bake is several launches on the
 //   same pieces.  Their scratch is a ring of work counters with an event per slot (LaunchOnRing).
 //   The path calls -- radiance along caller rays, and the gathers, which are that call with another generator -- share BeginPathCall and PathGrid, one counter
@@ -33,6 +33,16 @@ static NearestKernel NearestKernelOfKind(const QueryPlan& p)
 }
 static_assert(RAYLIB_AMD_NEAREST_WITHIN == RL_NK_WITHIN && RAYLIB_AMD_NEAREST_CLOSEST == RL_NK_CLOSEST, "nearest kinds");
 static_assert(sizeof(RaylibAMDNearestQuery) == 16 && sizeof(RaylibAMDNearestHit) == sizeof(DNearestHit), "nearest records");
+
+typedef void (*SweepKernel)(const DSceneView, const float4*, uint32_t, void*, const int32_t*, unsigned int*, unsigned long long*);
+template <int KIND>
+static SweepKernel SweepKernelOfKind(const QueryPlan& p)
+{
+	if (p.tree == TREE_GRID4) return p.stack <= 32 ? (SweepKernel)k_sweep<4, KIND, 32> : (SweepKernel)k_sweep<4, KIND, 64>;
+	return p.stack <= 32 ? (SweepKernel)k_sweep<2, KIND, 32> : (SweepKernel)k_sweep<2, KIND, 64>;
+}
+static_assert(RAYLIB_AMD_SWEEP_ANY == RL_SK_ANY && RAYLIB_AMD_SWEEP_CLOSEST == RL_SK_CLOSEST, "sweep kinds");
+static_assert(sizeof(RaylibAMDSweepQuery) == 32 && sizeof(RaylibAMDSweepHit) == 32 && sizeof(RaylibAMDSweepHit) == sizeof(DSweepHit), "sweep records");
 
 typedef void (*OverlapKernel)(const DSceneView, const float4*, uint32_t, uint32_t, uint32_t, void*, uint32_t*, const int32_t*, unsigned int*, unsigned long long*);
 template <int KIND>
@@ -532,6 +542,21 @@ bool DeviceNearestPoints(Scene& sc, int32_t kind, const void* points, int32_t n,
 	const NearestKernel kernel = closest ? NearestKernelOfKind<RL_NK_CLOSEST>(D.plan) : NearestKernelOfKind<RL_NK_WITHIN>(D.plan);
 	D.kernel = (const void*)kernel;
 	D.out[0] = { out, (size_t)n * (closest ? sizeof(DNearestHit) : sizeof(uint32_t)), closest ? 15u : 3u, &RankCtx::qOut };
+	D.slotIndex = closest;
+	return RunQuery(sc, D, stats, [&](const QueryLaunch& L) {
+		hipLaunchKernelGGL(kernel, L.grid, dim3(RL_BLOCK), 0, L.st, L.view, L.in, (uint32_t)n, L.out[0], L.slotIndex, L.counter, L.stats);
+	});
+}
+
+// A swept-sphere call: 32-byte records in, a word (ANY) or a 32-byte record (CLOSEST, two 16-byte stores) per query out.
+bool DeviceSweepSpheres(Scene& sc, int32_t kind, const void* queries, int32_t n, void* out, bool hostMem, void* stream, RaylibAMDStats& stats)
+{
+	QueryDesc D("RaylibAMD_SweepSpheres", "RaylibAMD_SweepSpheresDevice", "queries", queries, sizeof(RaylibAMDSweepQuery), n, hostMem, stream);
+	D.plan = PlanSweep(sc, kind, ReadRenderKnobs());
+	const bool closest = kind == RAYLIB_AMD_SWEEP_CLOSEST;
+	const SweepKernel kernel = closest ? SweepKernelOfKind<RL_SK_CLOSEST>(D.plan) : SweepKernelOfKind<RL_SK_ANY>(D.plan);
+	D.kernel = (const void*)kernel;
+	D.out[0] = { out, (size_t)n * (closest ? sizeof(DSweepHit) : sizeof(uint32_t)), closest ? 15u : 3u, &RankCtx::qOut };
 	D.slotIndex = closest;
 	return RunQuery(sc, D, stats, [&](const QueryLaunch& L) {
 		hipLaunchKernelGGL(kernel, L.grid, dim3(RL_BLOCK), 0, L.st, L.view, L.in, (uint32_t)n, L.out[0], L.slotIndex, L.counter, L.stats);

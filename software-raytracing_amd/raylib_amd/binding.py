@@ -451,6 +451,31 @@ def nearest_points_all(lib, scene, points, max_hits, count=False, host=False):
     return (rows, counts) if count else rows
 
 
+SWEEP_ANY, SWEEP_CLOSEST = 0, 1                     # RAYLIB_AMD_SWEEP_*
+SWEEP_QUERY_DTYPE = np.dtype([("origin", "f4", 3), ("radius", "f4"), ("delta", "f4", 3), ("reserved", "u4")])                                           # RaylibAMDSweepQuery
+SWEEP_HIT_DTYPE = np.dtype([("t", "f4"), ("prim", "i4"), ("feature", "i4"), ("reserved0", "u4"), ("point", "f4", 3), ("reserved1", "u4")])   # RaylibAMDSweepHit
+
+
+def plan_sweep(lib, scene, kind):
+    """RaylibAMD_PlanSweep: (return code, plan dict)."""
+    return _plan(lib, "RaylibAMD_PlanSweep", scene, int(kind))
+
+
+def sweep_spheres(lib, scene, queries, kind, host=False):
+    """Batched swept-sphere queries (RaylibAMD_SweepSpheres / RaylibAMD_SweepSpheresDevice / RaylibAMD_SweepSpheresHost, statements W1 to W7).
+
+    queries: an (n, 8) float32 array -- origin xyz, radius, delta xyz and a word that is not read per row -- or a NumPy array of SWEEP_QUERY_DTYPE.  A NumPy
+    array goes through the host entry (host=True: through the oracle, which needs no device) and returns a NumPy array: uint32 for SWEEP_ANY, SWEEP_HIT_DTYPE
+    for SWEEP_CLOSEST.  A float32 torch tensor on the device goes through the device entry on torch.cuda.current_stream(), as nearest_points: enqueued on a
+    stream of the caller's, synchronous on torch's default stream (synchronised first).  It returns a tensor: (n,) int32 for ANY (0 / 1), (n, 8) int32 words
+    for CLOSEST.  Raises RuntimeError when the library refuses the call."""
+    kind = int(kind)
+    if kind not in (SWEEP_ANY, SWEEP_CLOSEST):
+        raise ValueError("unknown sweep kind %r" % kind)
+    dtype = SWEEP_HIT_DTYPE if kind == SWEEP_CLOSEST else np.dtype("u4")
+    return _query(lib, scene, queries, 8, "RaylibAMD_SweepSpheres", lambda n: [(n, dtype)], pre=(kind,), host=host, records=SWEEP_QUERY_DTYPE, type_error=_QUERIES_TYPE_ERROR)[0]
+
+
 SDF_UNSIGNED, SDF_SIGN_X, SDF_SIGN_Y, SDF_SIGN_Z, SDF_SIGN_MAJORITY = 0, 1, 2, 3, 4   # RAYLIB_AMD_SDF_*
 
 
@@ -1103,6 +1128,10 @@ _EXPORTS = {
     "RaylibAMD_NearestPointsDevice": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "RaylibAMD_NearestPointsHost": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "RaylibAMD_PlanNearest": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(QueryPlan)]),
+    "RaylibAMD_SweepSpheres": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "RaylibAMD_SweepSpheresDevice": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_SweepSpheresHost": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "RaylibAMD_PlanSweep": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(QueryPlan)]),
     "RaylibAMD_NearestPointsAll": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "RaylibAMD_NearestPointsAllDevice": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "RaylibAMD_NearestPointsAllHost": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -13,6 +13,7 @@ bool DeviceRenderMotion(Scene&, const RendererSettings&, const DCamera&, const D
 bool DeviceTemporalAccumulate(uint32_t, uint32_t, const RaylibAMDTemporalParams&, const float*, const RaylibAMDHitT*, const RaylibAMDMotion*, const RaylibAMDTemporalFrame*, float*, float*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceTraceRaysAll(Scene&, const void*, int32_t, int32_t, void*, uint32_t*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceNearestPoints(Scene&, int32_t, const void*, int32_t, void*, bool, void*, RaylibAMDStats&) { return false; }
+bool DeviceSweepSpheres(Scene&, int32_t, const void*, int32_t, void*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceNearestPointsAll(Scene&, const void*, int32_t, int32_t, void*, uint32_t*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceBakeDistanceField(Scene&, const RaylibAMDDistanceFieldParams&, float*, int32_t*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceOverlapTriangles(Scene&, int32_t, uint32_t, const void*, int32_t, int32_t, void*, uint32_t*, bool, void*, RaylibAMDStats&, void*, bool) { return false; }
