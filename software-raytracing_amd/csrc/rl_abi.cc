@@ -5,19 +5,13 @@
 #include "raylib.h"
 #include "raylib_amd.h"
 #include "rl_host.h"
+#include "rl_oracle.h"
 #include "rl_plan.h"
-#include "rl_progressive.h"
+#include "rl_progressive.h"   // RaylibAMD_ProgressiveDecideHost's rule
 #include "rl_lightmap.h"
-#include "rl_nearest.h"
-#include "rl_sweep.h"
-#include "rl_sdf.h"
-#include "rl_overlap.h"
-#include "rl_contact.h"
-#include "rl_motion.h"
-#include "rl_temporal.h"
-#include "raylib_amd_rng.h"
+#include "rl_sdf.h"           // SdfCentre: a refusal of the distance field's grid
+#include "rl_contact.h"       // ContactRecord and the contact kinds: the static_asserts on the ABI's record
 
-#include <float.h>
 #include <math.h>
 #include <stddef.h>
 #include <stdio.h>
@@ -150,6 +144,16 @@ int32_t RunOnDevice(void* stream, Call call)
 	RaylibAMDStats stats; memset(&stats, 0, sizeof(stats));
 	if (!call(stats)) return 0;
 	if (!stream) ReportOwnStats(stats);
+	return 1;
+}
+// An accepted call's way to its host oracle (rl_oracle.h): the host's copies made current -- the triangles and trees a move left stale, a texture's pixels that
+// live on the device -- then `call`, which runs the oracle on the scene
+template <typename Call>
+int32_t RunOnHost(Scene* s, Call call)
+{
+	if (!DeviceSyncMovedScene(*s)) return 0;
+	for (const std::shared_ptr<Image>& t : s->textures) t->SyncHost();
+	call();
 	return 1;
 }
 // The refusals of the queries on triangles (`family`: what the log calls them), for device entries and oracles alike: the arguments, a finalized scene of
@@ -987,23 +991,7 @@ int32_t RaylibAMD_MotionHost(uint32_t width, uint32_t height, SceneHandle sh, Ca
 	if (pixels == 0 || pixels > 0x7fffffffull) { Log("%s: a frame of %u x %u pixels (1 .. 2^31 - 1)", who, width, height); return 0; }
 	if (!s->finalized) { Log("%s: scene was not finalized (Raylib_FinalizeScene)", who); return 0; }
 	if (!MotionParamsValid(who, s, params, true)) return 0;
-	const DCamera pc = (params->prevCamera ? (const Camera*)params->prevCamera : c)->ToDevice();
-	for (size_t p = 0; p < (size_t)pixels; ++p) {
-		const float* r = rays + 7 * p;
-		RaylibAMDHitT h; memcpy(&h, hit + p, sizeof(h));
-		const bool isHit = h.prim >= 0;
-		float P[3] = { r[3], r[4], r[5] };
-		if (isHit) {
-			const int64_t k = (int64_t)h.prim - params->first;
-			if (h.prim < RAYLIB_AMD_PRIM_SPHERE && k >= 0 && k < params->count) MotionTrianglePoint(params->prevPositions + 9 * (size_t)k, h.b1, h.b2, P);
-			else MotionRayPoint(r, r + 3, h.t, P);
-		}
-		float o[3];
-		RaylibAMDMotion m;
-		m.status = MotionProject(pc.origin, pc.top_left, pc.horizontal, pc.vertical, (float)width, (float)height, isHit, P, o);
-		m.prevX = o[0]; m.prevY = o[1]; m.prevT = o[2];
-		memcpy(outMotion + p, &m, sizeof(m));
-	}
+	MotionHost(width, height, (params->prevCamera ? (const Camera*)params->prevCamera : c)->ToDevice(), params->first, params->count, params->prevPositions, rays, hit, outMotion);
 	return 1;
 }
 int32_t RaylibAMD_PlanMotion(SceneHandle scene, RaylibAMDQueryPlan* out) { return RaylibAMD_PlanGBuffer(scene, out); }
@@ -1042,33 +1030,11 @@ int32_t RaylibAMD_TemporalAccumulateDevice(uint32_t width, uint32_t height, cons
 {
 	return TemporalInternal("RaylibAMD_TemporalAccumulateDevice", width, height, params, colour, hit, motion, history, outColour, outLength, false, stream);
 }
-namespace {
-// the oracle's reads: arrays of any alignment
-struct HostTaps {
-	const float* colour; const RaylibAMDHitT* hit; const float* length;
-	bool Has() const { return colour != nullptr; }
-	TemporalTap Read(size_t q) const
-	{
-		TemporalTap t; RaylibAMDHitT h;
-		memcpy(&h, hit + q, sizeof(h));
-		memcpy(&t.r, colour + 4 * q, 3 * sizeof(float));
-		t.t = h.t; t.prim = h.prim; memcpy(&t.length, length + q, sizeof(float));
-		return t;
-	}
-};
-}
 int32_t RaylibAMD_TemporalAccumulateHost(uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
                                          const RaylibAMDMotion* motion, const RaylibAMDTemporalFrame* history, float* outColour, float* outLength)
 {
 	if (!TemporalArgsValid("RaylibAMD_TemporalAccumulateHost", width, height, params, colour, hit, motion, history, outColour, outLength)) return 0;
-	const HostTaps taps = { history ? history->colour : nullptr, history ? history->hit : nullptr, history ? history->length : nullptr };
-	for (size_t p = 0; p < (size_t)width * height; ++p) {
-		RaylibAMDHitT h; RaylibAMDMotion m; float c[3], o[4], len;
-		memcpy(&h, hit + p, sizeof(h)); memcpy(&m, motion + p, sizeof(m)); memcpy(c, colour + 4 * p, sizeof(c));
-		TemporalPixel(width, height, c, h.prim, m.prevX, m.prevY, m.prevT, m.status, params->depthTolerance, params->maxLength, taps, o, len);
-		o[3] = 1.0f;
-		memcpy(outColour + 4 * p, o, sizeof(o)); memcpy(outLength + p, &len, sizeof(len));
-	}
+	TemporalAccumulateHost(width, height, *params, colour, hit, motion, history, outColour, outLength);
 	return 1;
 }
 
@@ -1095,80 +1061,11 @@ int32_t RaylibAMD_TraceRaysAllDevice(SceneHandle sh, const RaylibAMDRay* rays, i
 {
 	return TraceRaysAllInternal("RaylibAMD_TraceRaysAllDevice", sh, rays, n, rayTime, maxHits, outHits, outCount, false, stream);
 }
-// Statement M1 on one ray and one triangle, for the oracles below: the statements of WalkStackHost's `triangle` (rl_bvh.cc: the plane t, the barycentrics, the own
-// box with the widened tMin clause, the slack) and the cut-out test (rl_dev_scene.h AlphaTestCandidateNI / TexFetch on the material's albedo map, whose converted
-// copy on the device is this powf of each texel), on [tMin, tMax] with tMin already raised to 0.  True: accepted, with its t and barycentrics.
-static bool HostRayAccepts(const Scene* s, const HostTriangle& T, const f3& o, const f3& d, float tMin, float tMax, float& tOut, float& paOut, float& pbOut)
-{
-	const float widen = 1.00001f, slack = 1.000009f;   // RL_BOX_WIDEN, RL_CANDIDATE_SLACK
-	const float oa[3] = { o.x, o.y, o.z }, inv[3] = { 1.0f / d.x, 1.0f / d.y, 1.0f / d.z };
-	const f3 nrm = normalize(cross(T.v1 - T.v0, T.v2 - T.v0));
-	const float t = dot((T.v0 - o), nrm) / dot(d, nrm);
-	if (!(t >= tMin && t <= FLT_MAX && t <= tMax)) return false;
-	const f3 p = o + t * d;
-	const f3 u = T.v1 - T.v0, v = T.v2 - T.v0, w = p - T.v0;
-	const float uv = dot(u, v), wv = dot(w, v), uu = dot(u, u), vv = dot(v, v), wu = dot(w, u);
-	const float denom = uv * uv - uu * vv;
-	const float pa = (uv * wv - vv * wu) / denom, pb = (uv * wu - uu * wv) / denom;
-	if (!(0.0f <= pa && 0.0f <= pb && pa + pb <= 1.0f)) return false;
-	const f3 mn = fmin3(fmin3(T.v0, T.v1), T.v2), mx = fmax3(fmax3(T.v0, T.v1), T.v2);
-	const float mna[3] = { mn.x, mn.y, mn.z }, mxa[3] = { mx.x, mx.y, mx.z };
-	float lo = -INFINITY, hi = FLT_MAX; bool ok = true;
-	for (int a = 0; a < 3; ++a) {
-		float t0 = (mna[a] - oa[a]) * inv[a], t1 = (mxa[a] - oa[a]) * inv[a];
-		if (inv[a] < 0.0f) std::swap(t0, t1);
-		lo = fmaxf(lo, t0); hi = fminf(hi, t1);
-		if (hi < lo) ok = false;
-	}
-	if (!(ok && !(hi * widen < tMin) && t * slack >= fmaxf(lo, tMin))) return false;
-	// the cut-out test: a triangle whose material is a microfacet one with an albedo map
-	if (T.material >= 0 && (size_t)T.material < s->materials.size()) {
-		const HostMaterial& M = s->materials[(size_t)T.material];
-		if (M.type == MAT_MICROFACET && M.tex[0] >= 0 && (size_t)M.tex[0] < s->textures.size()) {
-			const Image& im = *s->textures[(size_t)M.tex[0]];
-			im.SyncHost();
-			float U = (1 - pa - pb) * T.s0 + pa * T.s1 + pb * T.s2;
-			float V = (1 - pa - pb) * T.t0 + pa * T.t1 + pb * T.t2;
-			U = fmodf(U, 1.0f); if (U < 0.0f) U += 1.0f;
-			V = fmodf(V, 1.0f); if (V < 0.0f) V += 1.0f; V = 1.0f - V;
-			if (std::isnan(U) || std::isinf(U)) U = 0.0f;
-			if (std::isnan(V) || std::isinf(V)) V = 0.0f;
-			const int x = (int)((float)(uint32_t)(im.width - 1) * U), y = (int)((float)(uint32_t)(im.height - 1) * V);
-			const float alpha = powf(im.rgba[4 * ((size_t)y * im.width + (size_t)x) + 3], 2.2f);
-			if (!(alpha >= 0.5f)) return false;
-		}
-	}
-	tOut = t; paOut = pa; pbOut = pb;
-	return true;
-}
-// The oracle: every triangle slot in turn with statement M1 (HostRayAccepts) on the ray's own [QueryTMin(tMin), tMax]; the accepted ones sorted by (t, slot).
 int32_t RaylibAMD_TraceRaysAllHost(SceneHandle sh, const RaylibAMDRay* rays, int32_t n, float rayTime, int32_t maxHits, RaylibAMDHitT* outHits, uint32_t* outCount)
 {
 	Scene* s = (Scene*)sh;
 	if (!TraceRaysAllArgsValid("RaylibAMD_TraceRaysAllHost", s, rays, n, rayTime, maxHits, outHits)) return 0;
-	if (!DeviceSyncMovedScene(*s)) return 0;
-	const std::vector<uint32_t>& order = s->bvh.triOrder;
-	struct Key { float t; uint32_t slot; float b1, b2; };
-	std::vector<Key> keys;
-	for (int32_t i = 0; i < n; ++i) {
-		const RaylibAMDRay& Q = rays[i];
-		const f3 o = F3(Q.org[0], Q.org[1], Q.org[2]), d = F3(Q.dir[0], Q.dir[1], Q.dir[2]);
-		const float tMin = Q.tMin < 0.0f ? 0.0f : Q.tMin, tMax = Q.tMax;   // (a NaN bound fails every comparison below)
-		keys.clear();
-		for (uint32_t slot = 0; slot < (uint32_t)order.size(); ++slot) {
-			if (order[slot] >= s->triangles.size()) continue;
-			float t, pa, pb;
-			if (HostRayAccepts(s, s->triangles[order[slot]], o, d, tMin, tMax, t, pa, pb)) keys.push_back({ t, slot, pa, pb });
-		}
-		std::sort(keys.begin(), keys.end(), [](const Key& a, const Key& b) { return a.t < b.t || (a.t == b.t && a.slot < b.slot); });
-		RaylibAMDHitT* row = outHits + (size_t)i * (size_t)maxHits;
-		for (int32_t k = 0; k < maxHits; ++k) {
-			if ((size_t)k < keys.size()) { row[k].t = keys[(size_t)k].t; row[k].prim = (int32_t)order[keys[(size_t)k].slot]; row[k].b1 = keys[(size_t)k].b1; row[k].b2 = keys[(size_t)k].b2; }
-			else { row[k].t = 0.0f; row[k].prim = -1; row[k].b1 = 0.0f; row[k].b2 = 0.0f; }
-		}
-		if (outCount) outCount[i] = (uint32_t)keys.size();
-	}
-	return 1;
+	return RunOnHost(s, [&] { TraceRaysAllHost(*s, rays, n, maxHits, outHits, outCount); });
 }
 int32_t RaylibAMD_PlanRayQueryAll(SceneHandle sh, int32_t maxHits, int32_t wantCount, RaylibAMDQueryPlan* out)
 {
@@ -1198,32 +1095,11 @@ int32_t RaylibAMD_NearestPointsDevice(SceneHandle sh, int32_t kind, const Raylib
 {
 	return NearestPointsInternal("RaylibAMD_NearestPointsDevice", sh, kind, points, n, out, false, stream);
 }
-// the oracle: statements N1 to N4 (rl_nearest.h, the kernel's own source) over every triangle in export order
 int32_t RaylibAMD_NearestPointsHost(SceneHandle sh, int32_t kind, const RaylibAMDNearestQuery* points, int32_t n, void* out)
 {
 	Scene* s = (Scene*)sh;
 	if (!NearestArgsValid("RaylibAMD_NearestPointsHost", s, kind, points, n, out)) return 0;
-	if (!DeviceSyncMovedScene(*s)) return 0;
-	const size_t numTris = s->triangles.size();
-	for (int32_t i = 0; i < n; ++i) {
-		const RaylibAMDNearestQuery& Q = points[i];
-		RaylibAMDNearestHit best = { 0.0f, -1, 0.0f, 0.0f };
-		if (NearestTakesPart(Q.pos[0], Q.pos[1], Q.pos[2], Q.maxDist)) {
-			const float R2 = Q.maxDist * Q.maxDist;
-			for (size_t k = 0; k < numTris; ++k) {
-				const HostTriangle& t = s->triangles[k];
-				float b1, b2;
-				const float E = NearestTriangleE(Q.pos, &t.v0.x, &t.v1.x, &t.v2.x, b1, b2);
-				const float D = NearestTriangleD(E, NearestOwnBoxDist2(Q.pos, &t.v0.x, &t.v1.x, &t.v2.x));
-				if (!(D <= R2) || (best.prim >= 0 && !(D < best.dist2))) continue;   // (ascending k: an equal D keeps the lower index)
-				best.dist2 = D; best.prim = (int32_t)k; best.b1 = b1; best.b2 = b2;
-				if (kind == RAYLIB_AMD_NEAREST_WITHIN) break;
-			}
-		}
-		if (kind == RAYLIB_AMD_NEAREST_WITHIN) ((uint32_t*)out)[i] = best.prim >= 0 ? 1u : 0u;
-		else ((RaylibAMDNearestHit*)out)[i] = best.prim >= 0 ? best : RaylibAMDNearestHit{ 0.0f, -1, 0.0f, 0.0f };
-	}
-	return 1;
+	return RunOnHost(s, [&] { NearestPointsHost(*s, kind, points, n, out); });
 }
 int32_t RaylibAMD_PlanNearest(SceneHandle sh, int32_t kind, RaylibAMDQueryPlan* out)
 {
@@ -1253,32 +1129,11 @@ int32_t RaylibAMD_SweepSpheresDevice(SceneHandle sh, int32_t kind, const RaylibA
 {
 	return SweepSpheresInternal("RaylibAMD_SweepSpheresDevice", sh, kind, q, n, out, false, stream);
 }
-// the oracle: statements W1 to W6 (rl_sweep.h, the kernel's own source) over every triangle in export order
 int32_t RaylibAMD_SweepSpheresHost(SceneHandle sh, int32_t kind, const RaylibAMDSweepQuery* q, int32_t n, void* out)
 {
 	Scene* s = (Scene*)sh;
 	if (!SweepArgsValid("RaylibAMD_SweepSpheresHost", s, kind, q, n, out)) return 0;
-	if (!DeviceSyncMovedScene(*s)) return 0;
-	const size_t numTris = s->triangles.size();
-	for (int32_t i = 0; i < n; ++i) {
-		const RaylibAMDSweepQuery& Q = q[i];
-		RaylibAMDSweepHit best; memset(&best, 0, sizeof(best)); best.prim = -1;
-		SweepMove M;
-		if (SweepTakesPart(Q.origin, Q.delta, Q.radius, M)) {
-			for (size_t k = 0; k < numTris; ++k) {
-				const HostTriangle& tr = s->triangles[k];
-				float t, p[3]; int feature;
-				if (!SweepTriangle(M, &tr.v0.x, &tr.v1.x, &tr.v2.x, t, feature, p)) continue;
-				const float T = SweepTriangleT(t, SweepOwnBoxTime(M, &tr.v0.x, &tr.v1.x, &tr.v2.x));
-				if (!(T <= 1.0f) || (best.prim >= 0 && !(T < best.t))) continue;   // (ascending k: an equal T keeps the lower index)
-				best.t = T; best.prim = (int32_t)k; best.feature = feature; best.point[0] = p[0]; best.point[1] = p[1]; best.point[2] = p[2];
-				if (kind == RAYLIB_AMD_SWEEP_ANY) break;
-			}
-		}
-		if (kind == RAYLIB_AMD_SWEEP_ANY) ((uint32_t*)out)[i] = best.prim >= 0 ? 1u : 0u;
-		else ((RaylibAMDSweepHit*)out)[i] = best;
-	}
-	return 1;
+	return RunOnHost(s, [&] { SweepSpheresHost(*s, kind, q, n, out); });
 }
 int32_t RaylibAMD_PlanSweep(SceneHandle sh, int32_t kind, RaylibAMDQueryPlan* out)
 {
@@ -1309,35 +1164,11 @@ int32_t RaylibAMD_NearestPointsAllDevice(SceneHandle sh, const RaylibAMDNearestQ
 {
 	return NearestPointsAllInternal("RaylibAMD_NearestPointsAllDevice", sh, points, n, maxHits, outHits, outCount, false, stream);
 }
-// the oracle: statements K1 to K3 on N1 to N4 (rl_nearest.h, the kernel's own source) over every triangle in export order; the set sorted by (D, k)
 int32_t RaylibAMD_NearestPointsAllHost(SceneHandle sh, const RaylibAMDNearestQuery* points, int32_t n, int32_t maxHits, RaylibAMDNearestHit* outHits, uint32_t* outCount)
 {
 	Scene* s = (Scene*)sh;
 	if (!NearestAllArgsValid("RaylibAMD_NearestPointsAllHost", s, points, n, maxHits, outHits)) return 0;
-	if (!DeviceSyncMovedScene(*s)) return 0;
-	const size_t numTris = s->triangles.size();
-	std::vector<RaylibAMDNearestHit> set;
-	for (int32_t i = 0; i < n; ++i) {
-		const RaylibAMDNearestQuery& Q = points[i];
-		set.clear();
-		if (NearestTakesPart(Q.pos[0], Q.pos[1], Q.pos[2], Q.maxDist)) {
-			const float R2 = Q.maxDist * Q.maxDist;
-			for (size_t k = 0; k < numTris; ++k) {
-				const HostTriangle& t = s->triangles[k];
-				float b1, b2;
-				const float E = NearestTriangleE(Q.pos, &t.v0.x, &t.v1.x, &t.v2.x, b1, b2);
-				const float D = NearestTriangleD(E, NearestOwnBoxDist2(Q.pos, &t.v0.x, &t.v1.x, &t.v2.x));
-				if (D <= R2) set.push_back({ D, (int32_t)k, b1, b2 });
-			}
-		}
-		const size_t listed = std::min(set.size(), (size_t)maxHits);
-		std::partial_sort(set.begin(), set.begin() + (ptrdiff_t)listed, set.end(),
-		                  [](const RaylibAMDNearestHit& a, const RaylibAMDNearestHit& b) { return a.dist2 < b.dist2 || (a.dist2 == b.dist2 && a.prim < b.prim); });
-		RaylibAMDNearestHit* row = outHits + (size_t)i * (size_t)maxHits;
-		for (size_t k = 0; k < (size_t)maxHits; ++k) row[k] = k < listed ? set[k] : RaylibAMDNearestHit{ 0.0f, -1, 0.0f, 0.0f };
-		if (outCount) outCount[i] = (uint32_t)set.size();
-	}
-	return 1;
+	return RunOnHost(s, [&] { NearestPointsAllHost(*s, points, n, maxHits, outHits, outCount); });
 }
 int32_t RaylibAMD_PlanNearestAll(SceneHandle sh, int32_t maxHits, int32_t wantCount, RaylibAMDQueryPlan* out)
 {
@@ -1372,36 +1203,11 @@ int32_t RaylibAMD_OverlapTrianglesDevice(SceneHandle sh, int32_t kind, uint32_t 
 {
 	return OverlapTrianglesInternal("RaylibAMD_OverlapTrianglesDevice", sh, kind, flags, q, n, maxHits, out, outCount, false, stream);
 }
-// the oracle: statements O1 to O5 (rl_overlap.h, the kernel's own source) over every triangle in export order
 int32_t RaylibAMD_OverlapTrianglesHost(SceneHandle sh, int32_t kind, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, void* out, uint32_t* outCount)
 {
 	Scene* s = (Scene*)sh;
 	if (!OverlapArgsValid("RaylibAMD_OverlapTrianglesHost", s, kind, flags, q, n, maxHits, out, outCount)) return 0;
-	if (!DeviceSyncMovedScene(*s)) return 0;
-	const size_t numTris = s->triangles.size();
-	const bool list = kind == RAYLIB_AMD_OVERLAP_LIST, skipShared = (flags & RAYLIB_AMD_OVERLAP_SKIP_SHARED) != 0u;
-	for (int32_t i = 0; i < n; ++i) {
-		const RaylibAMDOverlapQuery& Q = q[i];
-		int32_t* row = list ? (int32_t*)out + (size_t)i * (size_t)maxHits : nullptr;
-		uint32_t count = 0;
-		if (OverlapTakesPart(Q.v0, Q.v1, Q.v2)) {
-			float lo[3], hi[3];
-			OverlapOwnBox(Q.v0, Q.v1, Q.v2, lo, hi);
-			for (size_t k = 0; k < numTris; ++k) {
-				const HostTriangle& t = s->triangles[k];
-				if (!OverlapAccepts(Q.v0, Q.v1, Q.v2, lo, hi, &t.v0.x, &t.v1.x, &t.v2.x, skipShared)) continue;
-				if (list && count < (uint32_t)maxHits) row[count] = (int32_t)k;   // (ascending k)
-				++count;
-				if (!list) break;
-			}
-		}
-		if (!list) ((uint32_t*)out)[i] = count ? 1u : 0u;
-		else {
-			for (uint32_t e = count; e < (uint32_t)maxHits; ++e) row[e] = -1;
-			if (outCount) outCount[i] = count;
-		}
-	}
-	return 1;
+	return RunOnHost(s, [&] { OverlapTrianglesHost(*s, kind, flags, q, n, maxHits, out, outCount); });
 }
 int32_t RaylibAMD_PlanOverlap(SceneHandle sh, int32_t kind, RaylibAMDQueryPlan* out)
 {
@@ -1439,38 +1245,12 @@ int32_t RaylibAMD_OverlapContactsDevice(SceneHandle sh, uint32_t flags, const Ra
 {
 	return OverlapContactsInternal("RaylibAMD_OverlapContactsDevice", sh, flags, q, n, maxHits, outIndex, outContact, outCount, false, stream);
 }
-// the oracle: O1 to O5 as RaylibAMD_OverlapTrianglesHost, then C1 to C6 (rl_contact.h, the kernel's own source) for every listed pair
 int32_t RaylibAMD_OverlapContactsHost(SceneHandle sh, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, int32_t* outIndex, RaylibAMDContact* outContact,
                                       uint32_t* outCount)
 {
 	Scene* s = (Scene*)sh;
 	if (!ContactArgsValid("RaylibAMD_OverlapContactsHost", s, flags, q, n, maxHits, outIndex, outContact, outCount)) return 0;
-	if (!DeviceSyncMovedScene(*s)) return 0;
-	const size_t numTris = s->triangles.size();
-	const bool skipShared = (flags & RAYLIB_AMD_OVERLAP_SKIP_SHARED) != 0u;
-	for (int32_t i = 0; i < n; ++i) {
-		const RaylibAMDOverlapQuery& Q = q[i];
-		int32_t* row = outIndex + (size_t)i * (size_t)maxHits;
-		RaylibAMDContact* rec = outContact + (size_t)i * (size_t)maxHits;
-		uint32_t count = 0;
-		if (OverlapTakesPart(Q.v0, Q.v1, Q.v2)) {
-			float lo[3], hi[3];
-			OverlapOwnBox(Q.v0, Q.v1, Q.v2, lo, hi);
-			for (size_t k = 0; k < numTris; ++k) {
-				const HostTriangle& t = s->triangles[k];
-				if (!OverlapAccepts(Q.v0, Q.v1, Q.v2, lo, hi, &t.v0.x, &t.v1.x, &t.v2.x, skipShared)) continue;
-				if (count < (uint32_t)maxHits) {   // (ascending k)
-					row[count] = (int32_t)k;
-					const ContactRecord R = ContactOfPair(Q.v0, Q.v1, Q.v2, &t.v0.x, &t.v1.x, &t.v2.x);
-					memcpy(&rec[count], &R, sizeof(R));
-				}
-				++count;
-			}
-		}
-		for (uint32_t e = count; e < (uint32_t)maxHits; ++e) { row[e] = -1; memset(&rec[e], 0, sizeof(rec[e])); }
-		if (outCount) outCount[i] = count;
-	}
-	return 1;
+	return RunOnHost(s, [&] { OverlapContactsHost(*s, flags, q, n, maxHits, outIndex, outContact, outCount); });
 }
 int32_t RaylibAMD_PlanOverlapContacts(SceneHandle sh, RaylibAMDQueryPlan* out) { return RaylibAMD_PlanOverlap(sh, RAYLIB_AMD_OVERLAP_LIST, out); }
 
@@ -1512,66 +1292,12 @@ int32_t RaylibAMD_BakeDistanceFieldDevice(SceneHandle sh, const RaylibAMDDistanc
 {
 	return BakeDistanceFieldInternal("RaylibAMD_BakeDistanceFieldDevice", sh, params, outDist, outPrim, false, stream);
 }
-// The oracle.  V3 and V4 per sign axis and row: statement M1 (HostRayAccepts) on every triangle, then for every voxel of the row the crossings ahead of its centre
-// counted one by one (no prefix trick: that is the device's).  V2 per voxel: statements N1 to N4 (rl_nearest.h) over every triangle in export order -- a triangle
-// whose own-box distance B already exceeds the bound is skipped, which changes nothing: D >= B (N3).  V5 at the store.
 int32_t RaylibAMD_BakeDistanceFieldHost(SceneHandle sh, const RaylibAMDDistanceFieldParams* params, float* outDist, int32_t* outPrim)
 {
 	Scene* s = (Scene*)sh;
 	RaylibAMDDistanceFieldParams G;
 	if (!DistanceFieldArgsValid("RaylibAMD_BakeDistanceFieldHost", s, params, outDist, true, G)) return 0;
-	if (!DeviceSyncMovedScene(*s)) return 0;
-	const uint32_t n[3] = { (uint32_t)G.dims[0], (uint32_t)G.dims[1], (uint32_t)G.dims[2] };
-	const size_t voxels = (size_t)n[0] * n[1] * n[2];
-	const size_t numTris = s->triangles.size();
-	// how many of the asked axes call a voxel inside
-	std::vector<uint8_t> votes(G.sign == RAYLIB_AMD_SDF_UNSIGNED ? 0 : voxels, 0);
-	const int asked = G.sign == RAYLIB_AMD_SDF_UNSIGNED ? 0 : G.sign == RAYLIB_AMD_SDF_SIGN_MAJORITY ? 3 : 1;
-	std::vector<float> ts;
-	for (int a = 0; a < 3 && asked; ++a) {
-		if (asked == 1 && a != G.sign - RAYLIB_AMD_SDF_SIGN_X) continue;
-		const int b = a == 0 ? 1 : 0, c = a == 2 ? 1 : 2;   // the other two axes, the lower one first
-		for (uint32_t ic = 0; ic < n[c]; ++ic) for (uint32_t ib = 0; ib < n[b]; ++ib) {
-			float org[3]; org[a] = G.origin[a]; org[b] = SdfCentre(G.origin[b], G.spacing[b], ib); org[c] = SdfCentre(G.origin[c], G.spacing[c], ic);
-			const f3 o = F3(org[0], org[1], org[2]), d = F3(a == 0 ? 1.0f : 0.0f, a == 1 ? 1.0f : 0.0f, a == 2 ? 1.0f : 0.0f);
-			ts.clear();
-			for (size_t k = 0; k < numTris; ++k) {
-				float t, pa, pb;
-				if (HostRayAccepts(s, s->triangles[k], o, d, 0.0f, FLT_MAX, t, pa, pb)) ts.push_back(t);
-			}
-			if (ts.empty()) continue;
-			for (uint32_t i = 0; i < n[a]; ++i) {
-				const float ti = SdfT(G.spacing[a], i);
-				size_t ahead = 0;
-				for (float t : ts) if (t > ti) ++ahead;
-				if (!(ahead & 1u)) continue;
-				uint32_t v[3]; v[a] = i; v[b] = ib; v[c] = ic;
-				++votes[((size_t)v[2] * n[1] + v[1]) * n[0] + v[0]];
-			}
-		}
-	}
-	const float R2 = G.maxDist * G.maxDist;
-	for (uint32_t k = 0; k < n[2]; ++k) for (uint32_t j = 0; j < n[1]; ++j) for (uint32_t i = 0; i < n[0]; ++i) {
-		const float pos[3] = { SdfCentre(G.origin[0], G.spacing[0], i), SdfCentre(G.origin[1], G.spacing[1], j), SdfCentre(G.origin[2], G.spacing[2], k) };
-		float bestD = 0.0f; int32_t prim = -1;
-		if (NearestTakesPart(pos[0], pos[1], pos[2], G.maxDist)) {
-			for (size_t q = 0; q < numTris; ++q) {
-				const HostTriangle& t = s->triangles[q];
-				const float B = NearestOwnBoxDist2(pos, &t.v0.x, &t.v1.x, &t.v2.x);
-				if (B > (prim >= 0 ? bestD : R2)) continue;
-				float b1, b2;
-				const float D = NearestTriangleD(NearestTriangleE(pos, &t.v0.x, &t.v1.x, &t.v2.x, b1, b2), B);
-				if (!(D <= R2) || (prim >= 0 && !(D < bestD))) continue;   // (ascending q: an equal D keeps the lower index)
-				bestD = D; prim = (int32_t)q;
-			}
-		}
-		const size_t at = ((size_t)k * n[1] + j) * n[0] + i;
-		float m = prim >= 0 ? __builtin_sqrtf(bestD) : G.maxDist;
-		if (asked && 2 * (int)votes[at] > asked) m = -m;
-		outDist[at] = m;
-		if (outPrim) outPrim[at] = prim;
-	}
-	return 1;
+	return RunOnHost(s, [&] { BakeDistanceFieldHost(*s, G, outDist, outPrim); });
 }
 int32_t RaylibAMD_PlanDistanceField(SceneHandle sh, const RaylibAMDDistanceFieldParams* params, RaylibAMDQueryPlan* outNearest, RaylibAMDQueryPlan* outRows)
 {
@@ -1731,28 +1457,14 @@ int32_t RaylibAMD_GatherAdaptiveDevice(SceneHandle sh, const RaylibAMDGatherPara
 	const GatherAdaptiveArgs a = { adaptive, outSamples };
 	return GatherInternal("RaylibAMD_GatherAdaptiveDevice", sh, params, points, n, out, false, stream, &a);
 }
-// statements A1 to A3 on the caller's keys: the oracle of k_gather_adaptive_resolve's moments and decision (csrc/rl_progressive.h, built without FMA)
+// statements A1 to A3 on the caller's keys (rl_oracle.cc): the oracle of k_gather_adaptive_resolve's moments and decision
 int32_t RaylibAMD_GatherAdaptiveDecideHost(const RaylibAMDGatherAdaptiveParams* adaptive, uint32_t cap, const float* keys, int64_t count, uint32_t* outSamples)
 {
 	const char* who = "RaylibAMD_GatherAdaptiveDecideHost";
 	if (count < 0 || (count > 0 && (!keys || !outSamples))) { Log("%s: null argument, or a negative count", who); return 0; }
 	if (cap == 0) { Log("%s: the cap is 0", who); return 0; }
 	if (!GatherAdaptiveValid(who, adaptive, cap)) return 0;
-	for (int64_t i = 0; i < count; ++i) {
-		const float* key = keys + (size_t)i * cap * 3;
-		float s1 = 0.0f, s2 = 0.0f;
-		uint32_t n = 0;
-		for (;;) {
-			const uint32_t now = (uint32_t)std::min<uint64_t>(cap, (uint64_t)n + adaptive->passSamples);
-			for (; n < now; ++n) {
-				const float lum = key[3 * (size_t)n] * 0.2126f + key[3 * (size_t)n + 1] * 0.7152f + key[3 * (size_t)n + 2] * 0.0722f;
-				const float y = lum / (1.0f + lum);
-				s1 += y; s2 += y * y;
-			}
-			if (n == cap || ProgressiveCellStops(ProgressivePixelError(s1, s2, n), n, adaptive->threshold, adaptive->minSamples)) break;
-		}
-		outSamples[i] = n;
-	}
+	GatherAdaptiveDecideHost(*adaptive, cap, keys, count, outSamples);
 	return 1;
 }
 int32_t RaylibAMD_GatherCompactTest(const uint32_t* live, uint32_t numLive, const uint8_t* stopped, const RaylibAMDGatherPoint* points, uint32_t numPoints,
@@ -1775,26 +1487,13 @@ int32_t RaylibAMD_PlanGatherCut(const RaylibAMDGatherParams* params, int32_t n, 
 	out->pointFirst = L.pointFirst; out->numPoints = L.numPoints; out->sampleBase = L.sampleBase; out->numSamples = L.numSamples; out->first = L.first; out->last = L.last;
 	return 1;
 }
-// statement 1 of the header's contract with the host's libm: csrc/rl_dev_core.h RandomInUnitSphere and normalize, csrc/rl_dev_shade.h's Lambertian flip
+// statement 1 of the header's contract with the host's libm (rl_oracle.cc)
 int32_t RaylibAMD_GatherDirectionsHost(const RaylibAMDGatherParams* params, const RaylibAMDGatherPoint* points, int32_t n, uint64_t seed, uint32_t sample, float* outDirs)
 {
 	const char* who = "RaylibAMD_GatherDirectionsHost";
 	if (!params || n < 0 || (n > 0 && (!points || !outDirs))) { Log("%s: null argument", who); return 0; }
 	if (!GatherKindValid(who, params)) return 0;
-	for (int32_t i = 0; i < n; ++i) {
-		RaylibRngStream g = raylib_rng_begin(seed, points[i].stream, params->sampleFirst + sample);
-		for (uint32_t k = 0; k < params->skipDraws; ++k) (void)raylib_rng_next_u32(&g);
-		const float u1 = raylib_rng_next_float(&g);
-		const float u2 = raylib_rng_next_float(&g);
-		const float z = 1.0f - 2.0f * u1;
-		const float r = sqrtf(fmaxf(0.0f, 1.0f - z * z));
-		const float phi = 2.0f * 3.141592f * u2;
-		float w[3] = { r * cosf(phi), r * sinf(phi), z };
-		const float* N = points[i].normal;
-		if (params->kind == RAYLIB_AMD_GATHER_IRRADIANCE && (double)(w[0] * N[0] + w[1] * N[1] + w[2] * N[2]) < 0.0) { w[0] = -w[0]; w[1] = -w[1]; w[2] = -w[2]; }
-		const float k = 1.0f / sqrtf(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-		outDirs[3 * (size_t)i + 0] = w[0] * k; outDirs[3 * (size_t)i + 1] = w[1] * k; outDirs[3 * (size_t)i + 2] = w[2] * k;
-	}
+	GatherDirectionsHost(*params, points, n, seed, sample, outDirs);
 	return 1;
 }
 

@@ -10,6 +10,7 @@
 // ray), <= 4 triangles per leaf stored contiguously, both child boxes in the
 // parent so a lane decides two children per 64-byte fetch.
 #include "rl_host.h"
+#include "rl_oracle.h"   // TriangleM1Host, and rl_slack.h's RL_BOX_WIDEN
 #include "rl_grid.h"
 
 #include <algorithm>
@@ -841,7 +842,6 @@ inline GridFactors MakeGridFactors(const float step[3], const float origin[3], c
 	return F;
 }
 inline float clampInv(float x) { return std::isinf(x) ? copysignf(1e30f, x) : x; }   // the grid walks' reciprocal of a direction component that is zero
-constexpr float kBoxWiden = 1.00001f;   // RL_BOX_WIDEN
 
 // One 8-wide node against one ray (NodeStep8): the steps are the powers of two whose exponents the node holds, one fma per 8-bit plane, the negated entry
 // distance (least of ntMin and the planes'), the exit distance (least of tmx and the planes'), and a child is hit where fma(exit, widen, -entry) is not
@@ -859,7 +859,7 @@ uint32_t Step8Host(const DNode8& nd, const float o[3], const float inv[3], const
 			const float qn = plane(neg[a] ? nd.qhi[a] : nd.qlo[a], ch), qf = plane(neg[a] ? nd.qlo[a] : nd.qhi[a], ch);
 			ntn = std::min(ntn, fmaf(qn, -F.A[a], F.nB[a])); tf = std::min(tf, fmaf(qf, F.A[a], F.Bf[a]));
 		}
-		if (!std::signbit(fmaf(tf, kBoxWiden, ntn))) hit |= 1u << ch;
+		if (!std::signbit(fmaf(tf, RL_BOX_WIDEN, ntn))) hit |= 1u << ch;
 	}
 	return hit;
 }
@@ -1100,7 +1100,7 @@ bool Walk8Host(const BVH& bvh, const std::vector<HostTriangle>& tris, const floa
 // same step), Traverse4 on the float boxes (tree 3: RL_WIDE_STEP_F) and on the grid nodes (tree 4: RL_WIDE_STEP_Q; NodeStep4 is the same step) with the 5-comparator sort and far-to-near pushes, and the walk of groups on
 // the 8-wide tree (tree 8: NodeStep8 / Push8; capacity in groups) -- the box arithmetic in float, operation by operation, the exit distance shrinking with the
 // best hit as on the device, and the device's guard: a push at sp == capacity is DROPPED, silently.  The triangle test is the reference's (geom/triangle.cc:18-58,
-// the host's f3 arithmetic is the device record's) with the ray queries' candidate rule (OwnBoxPassBox under RL_OWN_BOX_WIDEN_TMIN); spheres and cubes (tree 2) as
+// the host's f3 arithmetic is the device record's) with the ray queries' candidate rule (OwnBoxPassBox under RL_OWN_BOX_WIDEN_TMIN): TriangleM1Host, rl_oracle.h; spheres and cubes (tree 2) as
 // SphereHit / CubeHit at ray time 0; no cut-out test.  outT[i]: the closest accepted hit over [tMin, FLT_MAX] (INFINITY: none); outHighWater[i]: the largest sp
 // the ray reached, counting only pushes that were stored.  What a test proves with it: at the instance's capacity every ray gets the brute-force answer and some
 // ray fills the stack to the builder's reported need; at one entry less some ray loses its hit (tests/test_stack_edges_host.py).
@@ -1109,7 +1109,7 @@ bool WalkStackHost(const BVH& bvh, const std::vector<HostTriangle>& tris, const 
 {
 	if (capacity < 0 || (tree != 2 && tree != 3 && tree != 4 && tree != 8)) return false;
 	if (tree == 2 ? bvh.nodes.empty() : tree == 3 ? bvh.nodes4.empty() : tree == 4 ? bvh.nodes4q.empty() : bvh.nodes8.empty()) return false;
-	const float widen = kBoxWiden, slack = 1.000009f;   // RL_BOX_WIDEN, RL_CANDIDATE_SLACK
+	const float widen = RL_BOX_WIDEN;
 	for (int r = 0; r < n; ++r) {
 		const float* ray = rays + 6 * (size_t)r;
 		const f3 o = F3(ray[0], ray[1], ray[2]), d = F3(ray[3], ray[4], ray[5]);
@@ -1120,26 +1120,8 @@ bool WalkStackHost(const BVH& bvh, const std::vector<HostTriangle>& tris, const 
 		// one triangle slot, as the leaf code of every walk tests it
 		auto triangle = [&](uint32_t slot) -> bool {
 			if (slot >= bvh.triOrder.size() || bvh.triOrder[slot] >= tris.size()) return false;
-			const HostTriangle& T = tris[bvh.triOrder[slot]];
-			const f3 nrm = normalize(cross(T.v1 - T.v0, T.v2 - T.v0));
-			const float t = dot((T.v0 - o), nrm) / dot(d, nrm);
-			if (!(t >= tMin && t <= FLT_MAX && t < best)) return true;
-			const f3 p = o + t * d;
-			const f3 u = T.v1 - T.v0, v = T.v2 - T.v0, w = p - T.v0;
-			const float uv = dot(u, v), wv = dot(w, v), uu = dot(u, u), vv = dot(v, v), wu = dot(w, u);
-			const float denom = uv * uv - uu * vv;
-			const float pa = (uv * wv - vv * wu) / denom, pb = (uv * wu - uu * wv) / denom;
-			if (!(0.0f <= pa && 0.0f <= pb && pa + pb <= 1.0f)) return true;
-			const f3 mn = fmin3(fmin3(T.v0, T.v1), T.v2), mx = fmax3(fmax3(T.v0, T.v1), T.v2);
-			const float mna[3] = { mn.x, mn.y, mn.z }, mxa[3] = { mx.x, mx.y, mx.z };
-			float lo = -INFINITY, hi = FLT_MAX; bool ok = true;
-			for (int a = 0; a < 3; ++a) {
-				float t0 = (mna[a] - oa[a]) * inv[a], t1 = (mxa[a] - oa[a]) * inv[a];
-				if (inv[a] < 0.0f) std::swap(t0, t1);
-				lo = fmaxf(lo, t0); hi = fminf(hi, t1);
-				if (hi < lo) ok = false;
-			}
-			if (ok && !(hi * widen < tMin) && t * slack >= fmaxf(lo, tMin)) best = t;
+			float t, pa, pb;
+			if (TriangleM1Host(tris[bvh.triOrder[slot]], o, d, tMin, t, pa, pb) && t < best) best = t;
 			return true;
 		};
 		uint32_t high = 0;

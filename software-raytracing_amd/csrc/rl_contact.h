@@ -1,5 +1,5 @@
 // The contact segment of an accepted triangle pair (include/raylib_amd.h statements C1 to C6), one statement for the host and the device: k_overlap's contacts
-// instances (rl_k_overlap.inl) and the host oracle RaylibAMD_OverlapContactsHost (rl_abi.cc) compile this file.  Everything is float, single IEEE operations
+// instances (rl_k_overlap.inl) and the host oracle RaylibAMD_OverlapContactsHost (rl_oracle.cc) compile this file.  Everything is float, single IEEE operations
 // without FMA (the Makefile's -ffp-contract=off on either side); dot and cross are rl_overlap.h's, a / b is the IEEE quotient.
 // The shape of the arithmetic: each triangle's two crossing edges are cut by the other triangle's plane, once, and the segment's ends are
 // chosen among those four points by comparing one coordinate -- no endpoint is interpolated twice, so every endpoint lies on the edge its feature names, with a

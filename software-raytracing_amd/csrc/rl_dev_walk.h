@@ -3,13 +3,9 @@
 #pragma once
 
 #include "rl_dev_scene.h"
+#include "rl_slack.h"   // RL_BOX_WIDEN and RL_CANDIDATE_SLACK: the box tests' relative slack and the candidate rule's, shared with the host's restatements
 
 namespace rl {
-
-// Relative slack of every box test of a traversal (and of the candidate rule below): far above float rounding of the slab
-// arithmetic (a few ulp), far below anything visible.
-#define RL_BOX_WIDEN 1.00001f
-#define RL_CANDIDATE_SLACK 1.000009f   /* a little less than the boxes' slack: the pool schedule's v_rcp_f32 reciprocals may move a box entry by an ulp */
 
 // A candidate that passed the triangle test counts only if the ray also passes the reference's own box test
 // (geom/aabb.h:39-54, unwidened, t_max = FLT_MAX) on the triangle's exact AABB.  Why: the barycentric test accepts points a few

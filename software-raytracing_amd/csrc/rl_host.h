@@ -221,7 +221,7 @@ bool LoadOBJ(const char* path, OBJModel& out);
 void TransformOBJ(OBJModel& m, float tx, float ty, float tz, float yaw, float pitch, float roll, float sx, float sy, float sz);
 Image* LoadImageFile(const char* path);
 bool WriteImageFile(const Image& img, const char* path, uint32_t fileType);
-void PostProcessHost(Image& img);   // see rl_abi.cc: used only when the image never lived on a device
+void PostProcessHost(Image& img);   // rl_scene.cc; Raylib_PostProcess (rl_abi.cc) uses it only when the image never lived on a device
 
 // logging (rl_log.cc)
 void Log(const char* fmt, ...);
@@ -389,7 +389,7 @@ void DeviceProgressiveEnd(ProgressiveSession* S);
 bool DeviceProgressiveCompactTest(const uint32_t* live, uint32_t numLive, const uint8_t* stopped, const uint8_t* emptyOrNull, uint32_t numCells,
                                   uint32_t width, uint32_t height, uint32_t* outLive, uint32_t* outTrace, uint32_t outCounts[4]);
 
-// denoiser (rl_denoise.hip): the a-trous filter on the device and its host restatement; params checked by the caller (rl_abi.cc)
+// denoiser (rl_denoise.hip): the a-trous filter on the device and its host restatement; params checked by the caller (rl_abi.cc RaylibAMD_Denoise / RaylibAMD_DenoiseHost)
 void DenoiseHost(uint32_t width, uint32_t height, const float* color, bool hdr, const float* albedo, const float* normal,
                  const RaylibAMDDenoiseParams& params, float* out);
 // main, albedo and normal are uploaded first when their pixels live only on the host; out (which may be any of them) is reallocated

@@ -1,5 +1,5 @@
 // The motion plane's arithmetic (include/raylib_amd.h statements T2 to T4), one statement for the host and the device: k_motion (rl_k_motion.inl) and the
-// host oracle RaylibAMD_MotionHost (rl_abi.cc) compile this file.  Everything is float, single IEEE operations without FMA (the Makefile's
+// host oracle RaylibAMD_MotionHost (rl_oracle.cc) compile this file.  Everything is float, single IEEE operations without FMA (the Makefile's
 // -ffp-contract=off on either side); a / b and __builtin_sqrtf are the compiler's correctly rounded division and square root;
 // dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z.
 #pragma once

@@ -1,5 +1,5 @@
 // The nearest-point query's arithmetic (include/raylib_amd.h statements N1 to N3), one statement for the host and the device: k_nearest (rl_k_nearest.inl)
-// and the host oracle RaylibAMD_NearestPointsHost (rl_abi.cc) compile this file.  Everything is float, single IEEE operations without FMA (the Makefile's
+// and the host oracle RaylibAMD_NearestPointsHost (rl_oracle.cc) compile this file.  Everything is float, single IEEE operations without FMA (the Makefile's
 // -ffp-contract=off on either side); a / b and 1.0f / x are the compiler's correctly rounded divisions; dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z.
 // Why the result cannot depend on the tree walked: NearestBoxDist2 rounds monotonically at every operation, so a box that contains another is never farther
 // than it; a triangle's distance is at least its own box's (N3), the own box lies in its leaf's box, a binary node's boxes are the min / max of its children's,

@@ -1,5 +1,5 @@
 // The triangle-overlap query's arithmetic (include/raylib_amd.h statements O1 to O4), one statement for the host and the device: k_overlap (rl_k_overlap.inl)
-// and the host oracle RaylibAMD_OverlapTrianglesHost (rl_abi.cc) compile this file.  Everything is float, single IEEE operations without FMA (the Makefile's
+// and the host oracle RaylibAMD_OverlapTrianglesHost (rl_oracle.cc) compile this file.  Everything is float, single IEEE operations without FMA (the Makefile's
 // -ffp-contract=off on either side); dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z; least and greatest are found by comparisons, in the order written here.
 // Why a tree walk can equal the loop over every triangle with no slack anywhere: O2, the test of the query's own box against a triangle's own box, is pure
 // comparisons -- nothing rounds.  A triangle's own box lies in its leaf's box, a binary node's boxes are the min / max of its children's, and a grid box,

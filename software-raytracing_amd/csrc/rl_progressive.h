@@ -1,6 +1,7 @@
 // The stopping rule of progressive rendering (include/raylib_amd.h RaylibAMD_BeginProgressive), one statement for the device and the host:
-// k_progressive_resolve (rl_render.hip) decides with it, RaylibAMD_ProgressiveDecideHost (rl_abi.cc) is its oracle.  Both are built with
-// -ffp-contract=off, and every operation below is one IEEE operation (+ - * / sqrt, correctly rounded on gfx950 and x86-64), so the two agree bit for bit.
+// k_progressive_resolve (rl_render.hip) decides with it, RaylibAMD_ProgressiveDecideHost (rl_abi.cc) is its oracle, as
+// RaylibAMD_GatherAdaptiveDecideHost (rl_oracle.cc) is the adaptive gather's.  Both sides are built with -ffp-contract=off, and every operation below is one IEEE operation
+// (+ - * / sqrt, correctly rounded on gfx950 and x86-64), so the two agree bit for bit.
 #pragma once
 
 #include <stdint.h>

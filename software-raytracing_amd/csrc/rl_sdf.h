@@ -1,5 +1,5 @@
 // The distance-field bake's grid arithmetic (include/raylib_amd.h statement V1), one statement for the host and the device: the kernels of rl_k_sdf.inl and the
-// host oracle RaylibAMD_BakeDistanceFieldHost (rl_abi.cc) compile this file.  Single float operations without FMA (the Makefile's -ffp-contract=off on either
+// host oracle RaylibAMD_BakeDistanceFieldHost (rl_oracle.cc) compile this file.  Single float operations without FMA (the Makefile's -ffp-contract=off on either
 // side); (float)i rounds to nearest.  Every operation rounds monotonically, so neither value decreases in i.
 #pragma once
 

@@ -1,5 +1,5 @@
 // The swept-sphere query's arithmetic (include/raylib_amd.h RaylibAMD_SweepSpheres, statements W1 to W7), one statement for the host and the device: k_sweep
-// (rl_k_sweep.inl) and the host oracle RaylibAMD_SweepSpheresHost (rl_abi.cc) compile this file.  Everything is float, single IEEE operations without FMA (the
+// (rl_k_sweep.inl) and the host oracle RaylibAMD_SweepSpheresHost (rl_oracle.cc) compile this file.  Everything is float, single IEEE operations without FMA (the
 // Makefile's -ffp-contract=off on either side); a / b and 1.0f / x are the compiler's correctly rounded divisions, __builtin_sqrtf the correctly rounded root;
 // dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z, cross(a, b).x = a.y b.z - a.z b.y (and cyclic).
 //

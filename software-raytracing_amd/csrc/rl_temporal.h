@@ -1,5 +1,5 @@
 // The temporal accumulation's arithmetic (include/raylib_amd.h statement T7), one statement for the host and the device: k_temporal (rl_temporal.hip) and
-// the host oracle RaylibAMD_TemporalAccumulateHost (rl_abi.cc) compile this file.  Everything is float, single IEEE operations without FMA (the Makefile's
+// the host oracle RaylibAMD_TemporalAccumulateHost (rl_oracle.cc) compile this file.  Everything is float, single IEEE operations without FMA (the Makefile's
 // -ffp-contract=off on either side); a / b is the compiler's correctly rounded division.  The two sides differ in how they read a record -- 16-byte loads on
 // the device, memcpy from arrays of any alignment on the host -- which is the `Taps` argument.
 #pragma once

@@ -1,4 +1,4 @@
-// Sanitizer harness only (tools/bvh_host_check.sh): a stand-alone program over the BVH builder, its validators and the host walks (csrc/rl_bvh.cc) on a scene large
+// Sanitizer harness only (tools/host_check.sh bvh): a stand-alone program over the BVH builder, its validators and the host walks (csrc/rl_bvh.cc) on a scene large
 // enough that every threaded stage of the build engages -- the all-thread scans of the top levels and the task workers (from 2^17 primitives), the grid copy of
 // the 4-wide tree (from 2^16 nodes) and the emission of the 8-wide tree (from 2^15 nodes) --, built through the ABI and linked with tools/nodevice_stub.cc in
 // place of the device units.  Never part of libraylib.so.

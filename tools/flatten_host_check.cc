@@ -1,4 +1,4 @@
-// Sanitizer harness only (tools/flatten_host_check.sh): a stand-alone program over FlattenScene (csrc/rl_scene.cc) -- the step that turns a finalized scene into
+// Sanitizer harness only (tools/host_check.sh flatten): a stand-alone program over FlattenScene (csrc/rl_scene.cc) -- the step that turns a finalized scene into
 // the records the devices hold -- on the smallest scenes that reach each of its branches, built through the ABI and linked with tools/nodevice_stub.cc in place
 // of the device units.  Never part of libraylib.so.
 #include "raylib.h"

@@ -1,4 +1,4 @@
-// Sanitizer harness only (tools/gather_host_check.sh): a stand-alone program over the host side of RaylibAMD_Gather / RaylibAMD_GatherDevice -- the argument
+// Sanitizer harness only (tools/host_check.sh gather): a stand-alone program over the host side of RaylibAMD_Gather / RaylibAMD_GatherDevice -- the argument
 // checks and the scan of the points' times -- and over RaylibAMD_GatherDirectionsHost, linked with tools/nodevice_stub.cc in place of the device units, so every
 // accepted call with points ends at "no device" (0) after the host code under test has run.  Never part of libraylib.so.
 #include "raylib.h"

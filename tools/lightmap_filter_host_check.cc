@@ -1,4 +1,4 @@
-// Stand-alone sanitizer run over the host oracle of the lightmap atlas filter (rl::FilterLightmapHost, csrc/rl_lightmap_filter.hip; tools/lightmap_filter_host_check.sh):
+// Stand-alone sanitizer run over the host oracle of the lightmap atlas filter (rl::FilterLightmapHost, csrc/rl_lightmap_filter.hip; tools/host_check.sh lightmap_filter):
 // atlases from 1 x 1 to 67 x 41 with gutters, covered borders and corners, both kinds, K = 1 .. 8 (taps up to 256 texels outside the atlas), exact-size
 // arrays so that a read or write one element out of bounds is seen; in place; values that are not finite; the texel array's refusals.  No GPU, no Python.
 #include "rl_host.h"

@@ -1,4 +1,4 @@
-// Sanitizer harness only (tools/lightmap_host_check.sh): a stand-alone program over the host side of the lightmap calls -- the argument checks of all four and
+// Sanitizer harness only (tools/host_check.sh lightmap): a stand-alone program over the host side of the lightmap calls -- the argument checks of all four and
 // the oracle RaylibAMD_LightmapPointsHost --, linked with tools/nodevice_stub.cc in place of the device units, so every accepted device call ends at "no
 // device".  The outputs are heap arrays of exactly the size the contract names: the oracle may not write past min(count, capacity) records, and it must keep
 // inside its owner map for charts that lie on, across and far outside the atlas' edges.  Never part of libraylib.so.

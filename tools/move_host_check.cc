@@ -1,4 +1,4 @@
-// Stand-alone check of the host side of RaylibAMD_SceneMoveTriangles (tools/move_host_check.sh runs it under ASan + UBSan; tests/test_move_host.py runs it plain):
+// Stand-alone check of the host side of RaylibAMD_SceneMoveTriangles (tools/host_check.sh move runs it under ASan + UBSan; tests/test_move_host.py runs it plain):
 // the box ids the builder records per child of every wide record (csrc/rl_host.h BVH::boxOf4 / boxOf8 / boxOfLeafList), the grid rule shared with the device
 // (csrc/rl_grid.h) against the builder's former quantiser restated here, the leaf order as a permutation, and the host half of a moved scene's refresh (csrc/rl_bvh.cc
 // RefitWideFromBinary) behind a refit of the binary tree's boxes restated here.  Linked with rl_bvh.cc and rl_log.cc only; never part of libraylib.so.

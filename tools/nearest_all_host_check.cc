@@ -1,4 +1,4 @@
-// Sanitizer harness only (tools/nearest_all_host_check.sh): a stand-alone program over the host side of RaylibAMD_NearestPointsAll -- the host oracle
+// Sanitizer harness only (tools/host_check.sh nearest_all): a stand-alone program over the host side of RaylibAMD_NearestPointsAll -- the host oracle
 // RaylibAMD_NearestPointsAllHost on heap arrays of exactly the sizes the contract names, every refusal, and the planner -- linked with tools/nodevice_stub.cc in
 // place of the device units, so every accepted call of the plain and the device entry ends at "no device" (0).  Never part of libraylib.so.
 #include "raylib.h"

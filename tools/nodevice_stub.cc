@@ -1,4 +1,4 @@
-// Sanitizer harness only (tools/asan_host_check.sh and the stand-alone *_host_check programs): stands in for the HIP units -- the kernels and the host runtime
+// Sanitizer harness only (tools/asan_host_check.sh and the stand-alone *_host_check programs of tools/host_check.sh): stands in for the HIP units -- the kernels and the host runtime
 // that launches them (csrc/rl_rt_*.hip), every Device* entry of csrc/rl_host.h -- so that the HOST side of the library (ABI, OBJ/MTL loader, BVH builder,
 // scene flattening, planner, codecs, registries) can be built with g++ -fsanitize=address,undefined.  Never part of libraylib.so.
 #include "rl_host.h"

@@ -1,4 +1,4 @@
-// Sanitizer harness only (tools/overlap_host_check.sh): a stand-alone program over the host side of RaylibAMD_OverlapTriangles -- the host oracle
+// Sanitizer harness only (tools/host_check.sh overlap): a stand-alone program over the host side of RaylibAMD_OverlapTriangles -- the host oracle
 // RaylibAMD_OverlapTrianglesHost on heap arrays of exactly the sizes the contract names, every refusal, and the planner -- linked with tools/nodevice_stub.cc in
 // place of the device units, so every accepted call of the plain and the device entry ends at "no device" (0).  Never part of libraylib.so.
 #include "raylib.h"

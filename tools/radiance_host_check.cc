@@ -1,4 +1,4 @@
-// Sanitizer harness only (tools/radiance_host_check.sh): a stand-alone program over the host side of RaylibAMD_TraceRadiance / RaylibAMD_PlanRadiance -- the
+// Sanitizer harness only (tools/host_check.sh radiance): a stand-alone program over the host side of RaylibAMD_TraceRadiance / RaylibAMD_PlanRadiance -- the
 // argument checks, the scan of the rays' times and the planner -- linked with tools/nodevice_stub.cc in place of the device units, so every accepted call ends at
 // "no device" (0) after the host code under test has run.  Never part of libraylib.so.
 #include "raylib.h"

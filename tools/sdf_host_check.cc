@@ -1,4 +1,4 @@
-// Sanitizer harness only (tools/sdf_host_check.sh): a stand-alone program over the host side of RaylibAMD_BakeDistanceField -- the host oracle
+// Sanitizer harness only (tools/host_check.sh sdf): a stand-alone program over the host side of RaylibAMD_BakeDistanceField -- the host oracle
 // RaylibAMD_BakeDistanceFieldHost on heap arrays of exactly nx * ny * nz words, every refusal of statement V7 that needs no device, and the planner -- linked
 // with tools/nodevice_stub.cc in place of the device units, so every accepted call of the plain and the device entry ends at "no device" (0).  Never part of
 // libraylib.so.
