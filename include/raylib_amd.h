@@ -999,6 +999,16 @@ RAYLIB_API int32_t RaylibAMD_VerifyLazyPdf(uint32_t n, uint64_t seed, uint64_t* 
  * built with, which must lie inside; and outOutside: the differing inputs outside [C_MIN, .9999], which the sampler sends through the general prologue.  Any output
  * may be NULL.  Returns 1 when the sweep ran. */
 RAYLIB_API int32_t RaylibAMD_VerifySamplerRanged(int32_t mode, uint64_t* outMismatches, uint64_t* outFirstBits, uint32_t* outInterval, uint64_t* outOutside);
+/* The same instance normalises its vectors and takes its single square roots without sqrtf's and 1 / x's range guards, each behind one wave vote on the length or a
+ * written bound (csrc/rl_dev_core.h "normalize without the two range guards").  The claims, compared on the device (csrc/rl_render_lazy.hip k_verify_normalize_ranged).
+ * mode 0: all 2^32 bit patterns x of a squared length, the guard-free chain 1 / sqrt(x) against the general one; outMismatches counts those inside the vote's domain
+ * 2^-101 <= x <= FLT_MAX, outFirstOutside is the smallest pattern outside it at which the chains differ (~0: none) and outCount how many do.  mode 1: acosf without
+ * its guards (csrc/rl_glibc_math.h acosf_in_range_) against acosf on every float of the ranged sampler's interval of cosThetaI.  mode 2: the voted normalisation
+ * against the general one, component bits compared, on 64 + 2^24 vectors: an edge list (zero vectors, components +-0, subnormal lengths, squared lengths either
+ * side of 2^-101, infinities, NaN, overflowing lengths) and generated waves of every binary scale; outCount is the number of vectors whose wave took the guard-free
+ * side.  outMismatches: inputs whose results differ (a NaN may differ in payload) -- must be 0; outFirst: the smallest such bit pattern (mode 2: vector index).  Any
+ * output may be NULL.  Modes outside 0 .. 2 are refused (0).  Returns 1 when the sweep ran. */
+RAYLIB_API int32_t RaylibAMD_VerifyNormalizeRanged(int32_t mode, uint64_t* outMismatches, uint64_t* outFirst, uint64_t* outFirstOutside, uint64_t* outCount);
 
 /* ---- a finalized scene's triangles moved; its trees refitted on the device ---------------------------
  * Triangles [first, first + count) in RaylibAMD_SceneExportTriangles order take new vertices -- positions: count x 9 floats (v0 v1 v2) -- and, when normals is

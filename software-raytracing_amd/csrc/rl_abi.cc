@@ -814,6 +814,18 @@ int32_t RaylibAMD_VerifySamplerRanged(int32_t mode, uint64_t* outMismatches, uin
 	return 1;
 }
 
+int32_t RaylibAMD_VerifyNormalizeRanged(int32_t mode, uint64_t* outMismatches, uint64_t* outFirst, uint64_t* outFirstOutside, uint64_t* outCount)
+{
+	if (mode < 0 || mode > 2) return 0;
+	uint64_t out[4] = { 0, 0, 0, 0 };
+	if (!DeviceVerifyNormalizeRanged(mode, out)) return 0;
+	if (outMismatches) *outMismatches = out[0];
+	if (outFirst) *outFirst = out[1];
+	if (outFirstOutside) *outFirstOutside = out[2];
+	if (outCount) *outCount = out[3];
+	return 1;
+}
+
 int32_t RaylibAMD_VerifyLazyRefl(uint32_t n, uint64_t seed, uint64_t* outEvents, uint64_t* outUnsafe, uint64_t* outGuardFailed)
 {
 	uint64_t out[3] = { 0, 0, 0 };

@@ -71,6 +71,38 @@ __device__ __forceinline__ V3 cross(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.
 // (rtm::sqrt_ and rtm::rcp1_ are sqrtf and 1.0f / x bit for bit: rl_math.h)
 __device__ __forceinline__ float length(V3 a) { return rtm::sqrt_(a.x * a.x + a.y * a.y + a.z * a.z); }
 __device__ __forceinline__ V3 normalize(V3 a) { float k = rtm::rcp1_(length(a)); return v3(a.x * k, a.y * k, a.z * k); }
+// ---- normalize without the two range guards (RL_NORMALIZE_RANGED) ----
+// A translation unit's setting, made before its includes as RL_SAMPLER_RANGED is; off by default, and only the lazy instance's unit turns it on
+// (rl_render_lazy.hip).  normalize pays sqrt_'s guard and rcp1_'s for one fact about one float, len2.  Bits, so that the groups can be built apart:
+//   1: the surface frame (BuildSurface), 2: the sampler's two normalisations (BeckmannSample), 4: the recomputed half vector (ScatterLazy),
+//   8: the single-float sites -- SinThetaL's root and the root inside the ranged prologue's acos_ (rl_dev_shade.h).
+// (A definition on the compiler's command line reaches every unit: that is for `make variant` experiments, whose other kernels are then not the product's.)
+#ifndef RL_NORMALIZE_RANGED
+#define RL_NORMALIZE_RANGED 0
+#endif
+// 2^-101 <= len2 <= FLT_MAX: sqrt_in_range_'s domain.  The root then lies in [2^-50.5, 2^64], inside rcp1_in_range_'s [2^-126, 2^126): one condition for both.
+// False on a zero, a subnormal, a negative number, an infinity and NaN.
+__device__ __forceinline__ bool NormalizeInRange(float len2) { return (__float_as_uint(len2) - 0x0d000000u) < (0x7f800000u - 0x0d000000u); }
+// normalize's statements with neither guard: the same bits for NormalizeInRange(dot(a, a)), the caller's to guarantee
+__device__ __forceinline__ V3 normalize_ranged_(V3 a)
+{
+	float k = rlm::rcp1_in_range_(rtm::sqrt_in_range_(a.x * a.x + a.y * a.y + a.z * a.z));
+	return v3(a.x * k, a.y * k, a.z * k);
+}
+// normalize for a length of unknown range: if any lane's len2 is out of range the whole wave runs normalize, otherwise the ranged form (DivSpecular's pattern: one
+// scalar branch, no exec-mask region).  Nothing to prove about the bits: both short sequences equal sqrtf and 1.0f / x on their domains for every bit pattern
+// (RaylibAMD_VerifyExactMath, RaylibAMD_VerifyNormalizeRanged mode 0), so an in-range lane gets the same value from either side.
+__device__ __forceinline__ V3 normalize_voted_(V3 a)
+{
+	if (rtm::wave_any_(!NormalizeInRange(a.x * a.x + a.y * a.y + a.z * a.z))) return normalize(a);
+	return normalize_ranged_(a);
+}
+// sqrt_ of one float, voted the same way
+__device__ __forceinline__ float sqrt_voted_(float x)
+{
+	if (rtm::wave_any_(!NormalizeInRange(x))) return rtm::sqrt_(x);
+	return rtm::sqrt_in_range_(x);
+}
 __device__ __forceinline__ V3 reflect(V3 v, V3 n) { return v - 2.0f * dot(v, n) * n; }
 __device__ __forceinline__ V3 mix(V3 a, V3 b, float t) { return (1.0f - t) * a + t * b; }
 __device__ __forceinline__ V3 ld3(const float* p) { return v3(p[0], p[1], p[2]); }

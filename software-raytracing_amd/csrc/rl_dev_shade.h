@@ -10,6 +10,17 @@ namespace rl {
 // Surface interaction (reference geom/hit.h:16-36)
 struct Surf { float t; V3 p, n; float U, V; V3 tangent, bitangent; };
 
+// the tangent frame of s.n (geom/hit.cc:6-18), for BuildSurface under RL_NORMALIZE_RANGED bit 1 (rl_dev_core.h).  RANGED: s.n is a unit vector to a few ulps (the caller's to guarantee), and neither normalisation needs a test:
+// T is the axis with |s.n.axis| <= 0.9, so |cross(T, n)|^2 = 1 - n.axis^2 lies in [0.18, 1.01], and B is then a unit vector orthogonal to s.n to a few ulps:
+// |cross(n, B)|^2 lies in [0.98, 1.02].  Both far inside NormalizeInRange's [2^-101, FLT_MAX].
+template <bool RANGED>
+__device__ __forceinline__ void BuildFrame(Surf& s)
+{
+	V3 T = (fabsf(s.n.x) > 0.9f) ? v3(0.0f, 1.0f, 0.0f) : v3(1.0f, 0.0f, 0.0f);
+	V3 B = RANGED ? normalize_ranged_(cross(T, s.n)) : normalize(cross(T, s.n));
+	T = RANGED ? normalize_ranged_(cross(s.n, B)) : normalize(cross(s.n, B));
+	s.tangent = T; s.bitangent = B;
+}
 // HitResult for the winning primitive (reference geom/triangle.cc:43-47, geom/sphere.cc:19-41, geom/cube.cc:24-38)
 // + the tangent frame (geom/hit.cc:6-18).  Returns the material index.
 template <bool PRIMS, int LDS = 0>
@@ -23,7 +34,20 @@ __device__ __forceinline__ int BuildSurface(const DSceneView& S, V3 o, V3 d, con
 		const Shade sh = LDS ? ShadeFrom(sm + LdsAt<LDS>::SHADE + h.tri * RL_LDS_TSTRIDE) : LoadShade(S, h.tri);
 		c.shaded++;
 		const float a = h.a, b = h.b;
+#if RL_NORMALIZE_RANGED & 1
+		// The interpolated normal is the scene's: a zero or NaN one must still give the reference's NaN, so its length is voted on.  Where the vote passes every
+		// lane's s.n is a unit vector and the frame takes the ranged forms untested (BuildFrame); where it fails all three run the general form.
+		const V3 nv = (1 - a - b) * sh.n0 + a * sh.n1 + b * sh.n2;
+		if (rtm::wave_any_(!NormalizeInRange(nv.x * nv.x + nv.y * nv.y + nv.z * nv.z))) {
+			s.n = normalize(nv);
+			if (basis) BuildFrame<false>(s);
+		} else {
+			s.n = normalize_ranged_(nv);
+			if (basis) BuildFrame<true>(s);
+		}
+#else
 		s.n = normalize((1 - a - b) * sh.n0 + a * sh.n1 + b * sh.n2);
+#endif
 		s.U = (1 - a - b) * sh.s0 + a * sh.s1 + b * sh.s2;
 		s.V = (1 - a - b) * sh.t0 + a * sh.t1 + b * sh.t2;
 		material = sh.material;
@@ -46,12 +70,16 @@ __device__ __forceinline__ int BuildSurface(const DSceneView& S, V3 o, V3 d, con
 		    : (face == 3) ? v3(0.0f, 1.0f, 0.0f) : (face == 4) ? v3(0.0f, 0.0f, -1.0f) : (face == 5) ? v3(0.0f, 0.0f, 1.0f) : v3s(0.0f);
 		s.U = 0.0f; s.V = 0.0f;   // the reference leaves paramU / paramV unset for cubes
 	}
+#if RL_NORMALIZE_RANGED & 1
+	if (basis && kind != 0u) BuildFrame<false>(s);   // (a triangle's frame was made beside its normal, above)
+#else
 	if (basis) {
 		V3 T = (fabsf(s.n.x) > 0.9f) ? v3(0.0f, 1.0f, 0.0f) : v3(1.0f, 0.0f, 0.0f);
 		V3 B = normalize(cross(T, s.n));
 		T = normalize(cross(s.n, B));
 		s.tangent = T; s.bitangent = B;
 	}
+#endif
 	return material;
 }
 __device__ __forceinline__ V3 LocalToWorld(const Surf& s, V3 v)
@@ -116,7 +144,12 @@ __device__ RL_ERF_ATTR float Erf(float x)
 	float y = 1 - (((((a5 * t + a4) * t) + a3) * t + a2) * t + a1) * t * rtm::exp_(-x * x);
 	return sign * y;
 }
+#if RL_NORMALIZE_RANGED & 8
+// (voted: 1 - z z is an exact 0 for a direction along the normal, and NaN for a NaN one)
+__device__ __forceinline__ float SinThetaL(V3 w) { return sqrt_voted_(fmaxf(0.0f, 1.0f - w.z * w.z)); }
+#else
 __device__ __forceinline__ float SinThetaL(V3 w) { return rtm::sqrt_(fmaxf(0.0f, 1.0f - w.z * w.z)); }
+#endif
 
 // ---- the scattering event's divisions in the short form (RL_EXACT_DIV bits 1 and 2, rl_glibc_math.h) ----
 // (RL_EXACT_DIV is a translation unit's setting, made before its includes: the pool schedule's unit sets it to 0 and keeps every IEEE division, rl_render_pool.hip)
@@ -277,7 +310,11 @@ __device__ __forceinline__ void SamplerPrologueRanged(float cosThetaI, float& ta
 		float t = rlm::rcp1_in_range_(1 + p * cotThetaI);
 		c = 1 - (((((a5 * t + a4) * t) + a3) * t + a2) * t + a1) * t * expCot;
 	}
+#if RL_NORMALIZE_RANGED & 8
+	float thetaI = rtm::acos_in_range_(cosThetaI);   // (RaylibAMD_VerifyNormalizeRanged mode 1: every float of the interval)
+#else
 	float thetaI = rtm::acos_(cosThetaI);
+#endif
 	fit = 1 + thetaI * (-0.876f + thetaI * (0.4265f - 0.0594f * thetaI));
 	normalization = rlm::rcp1_in_range_(1 + c + SQRT_PI_INV * tanThetaI * expCot);
 }
@@ -371,7 +408,11 @@ __device__ __forceinline__ void BeckmannSample11(float cosThetaI, float U1, floa
 // reference render/material.cc:166-190
 __device__ __forceinline__ V3 BeckmannSample(V3 wi, float alpha_x, float alpha_y, float U1, float U2, Counters& cn)
 {
+#if RL_NORMALIZE_RANGED & 2
+	V3 wiStretched = normalize_voted_(v3(alpha_x * wi.x, alpha_y * wi.y, wi.z));   // (a grazing wi under a small alpha is arbitrarily short)
+#else
 	V3 wiStretched = normalize(v3(alpha_x * wi.x, alpha_y * wi.y, wi.z));
+#endif
 	float slope_x, slope_y;
 	BeckmannSample11(wiStretched.z, U1, U2, &slope_x, &slope_y, cn);
 #if RL_EXACT_DIV & 1
@@ -385,7 +426,13 @@ __device__ __forceinline__ V3 BeckmannSample(V3 wi, float alpha_x, float alpha_y
 	slope_x = tmp;
 	slope_x = alpha_x * slope_x;
 	slope_y = alpha_y * slope_y;
+#if RL_NORMALIZE_RANGED & 2
+	// len2 = (sx sx + sy sy) + 1 is at least 1 and finite when the slopes are.  Voted all the same, and not proved from ErfInvRanged's clamp: the .9999 branch's
+	// slopes are r cos, r sin with r = sqrt_(-log_(1 - U1)), infinite at U1 = 1, and the alphas are the caller's; the vote is one compare and a scalar branch.
+	return normalize_voted_(v3(-slope_x, -slope_y, 1.f));
+#else
 	return normalize(v3(-slope_x, -slope_y, 1.f));
+#endif
 }
 // reference render/brdf.h:39-58
 __device__ __forceinline__ float DistributionBeckmann(V3 N, V3 H, float roughness)
@@ -691,7 +738,11 @@ __device__ __forceinline__ void ScatterLazy(const DSceneView& S, const Mat& m, V
 	// ScatteringPdf(hit, -inD, WiW), material.cc:352-376
 	V3 wo = WorldToLocal(s, -inD);
 	V3 wi = WorldToLocal(s, WiW);
+#if RL_NORMALIZE_RANGED & 4
+	V3 wh = normalize_voted_(wo + wi);   // (arbitrarily short when Wo.Wh is small)
+#else
 	V3 wh = normalize(wo + wi);
+#endif
 	if (wh.z < 0.0f) wh.z = -wh.z;
 	exactSp = LazyScatterPdf(N, Wo, Wh, wh, roughness, sp, pdf);
 }

@@ -550,6 +550,34 @@ template <bool FD> RLM_FN float acosf_t(float x)
 	return small ? rSmall : (neg ? rNeg : rPos);
 }
 RLM_FN float acosf_(float x) { return acosf_t<(RL_EXACT_DIV & 4) != 0>(x); }
+// acosf_ for 2^-126 <= x < 1 (the ranged sampler's cosThetaI: rl_dev_shade.h SamplerPrologueRanged), the caller's to guarantee: its main path statement for
+// statement, without the |x| >= 1 block, without the x < -0.5 tail (x is positive) and with the guard-free square root -- s is read for x >= 0.5 only, where
+// z = (1 - x) / 2 lies in (0, 0.25]; for a smaller x it is computed from z = x x, which may be tiny or zero, and discarded.
+// (RaylibAMD_VerifyNormalizeRanged mode 1 compares the two on every float of the sampler's interval)
+RLM_FN float acosf_in_range_(float x)
+{
+	const bool FD = (RL_EXACT_DIV & 4) != 0;
+	const float one = 1.0000000000e+00f, pio2_hi = 1.5707962513e+00f, pio2_lo = 7.5497894159e-08f,
+		pS0 = 1.6666667163e-01f, pS1 = -3.2556581497e-01f, pS2 = 2.0121252537e-01f, pS3 = -4.0055535734e-02f,
+		pS4 = 7.9153501429e-04f, pS5 = 3.4793309169e-05f,
+		qS1 = -2.4033949375e+00f, qS2 = 2.0209457874e+00f, qS3 = -6.8828397989e-01f, qS4 = 7.7038154006e-02f;
+	const int32_t ix = (int32_t)asuint(x);
+	const bool small = ix < 0x3f000000;
+	if (small && ix <= 0x23000000) return pio2_hi + pio2_lo;
+	const float z = small ? x * x : (one - x) * 0.5f;
+	const float p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
+	const float q = one + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
+	const float r = qdiv_<FD>(p, q);   // q in [0.22, 1]
+	const float s = sqrtf_in_range_(z);
+	// x < 0.5
+	const float rSmall = pio2_hi - (x - (pio2_lo - r * x));
+	// x >= 0.5
+	const float df = asfloat(asuint(s) & 0xfffff000u);
+	const float c = qdiv_<FD>(z - df * df, s + df);
+	const float wPos = r * s + c;
+	const float rPos = 2.0f * (df + wPos);
+	return small ? rSmall : rPos;
+}
 
 // asinf (glibc e_asinf.c: glibc's own minimax p0..p4, not fdlibm's rational)
 RLM_FN float asinf_(float x)

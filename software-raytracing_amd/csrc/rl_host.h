@@ -364,6 +364,7 @@ bool DeviceEvalMath(int fn, const float* x, const float* y, int n, float* out);
 bool DeviceVerifyLazyRefl(uint32_t n, uint64_t seed, uint64_t out[3]);   // k_verify_lazy_refl: events, guard passed with a non-finite refl or sp, guard failed
 bool DeviceVerifyLazyPdf(uint32_t n, uint64_t seed, uint64_t out[3]);    // k_verify_lazy_pdf: events, quick with a pdf that is not positive and finite or a record that folds to other bits, not quick
 bool DeviceVerifySamplerRanged(int mode, uint64_t out[6]);   // k_verify_sampler_ranged: mismatches, the smallest mismatching bit pattern, mode 1's largest differing positive pattern below the branch and its mismatches outside the interval, the bits of C_MIN and of the branch's threshold
+bool DeviceVerifyNormalizeRanged(int mode, uint64_t out[4]);   // k_verify_normalize_ranged: mismatches, the smallest mismatching input, mode 0's smallest differing pattern outside the domain, mode 0's count of those or mode 2's vectors on the guard-free side
 bool DeviceVerifyExactMath(int which, uint64_t* outMismatches, uint64_t* outFirst);   // 0: rtm::rcp1_ vs 1.0f / x, 1: rtm::sqrt_ vs sqrtf, 2: rtm::div_by_ vs a / b, 3: Barycentric short vs divisions, 4: acosf_t / tanf_t short vs IEEE divisions; all 2^32 inputs
 bool DeviceEvalHook(int kind, Scene* sc, const DCamera* cam, int a, int b, const float* in, int n, uint64_t seed, float* out);
 void DeviceReleaseScene(DeviceScene* dev);

@@ -5,7 +5,7 @@
 //                        the multi-rank scatter, the test hooks)
 //   rl_render_views.hip  k_trace_views, k_resolve_views, k_aov_views: the views twins (RaylibAMD_RenderViews).  Instantiated beside the one-view kernels they
 //                        change how the helpers both call are inlined into those (tools/isa_equivalence.py)
-//   rl_render_lazy.hip   k_trace_lazy, k_trace_lazy_hitq, k_fold_lit, k_verify_lazy_refl, k_verify_lazy_pdf, k_verify_sampler_ranged: the leaf-list kernel's lazy-reflectance instance.  Beside the other k_trace instances it
+//   rl_render_lazy.hip   k_trace_lazy, k_trace_lazy_hitq, k_fold_lit, k_verify_lazy_refl, k_verify_lazy_pdf, k_verify_sampler_ranged, k_verify_normalize_ranged: the leaf-list kernel's lazy-reflectance instance.  Beside the other k_trace instances it
 //                        changes how two loops of the eager PLAIN instance are scheduled
 //   rl_render_pool.hip   k_trace_pool and its twin: a scheduler strategy of its own (Makefile POOLFLAGS)
 //   rl_query.hip         k_query (RaylibAMD_TraceRays): beside the render kernels it would change how the walks they share are inlined into those
@@ -500,5 +500,6 @@ __global__ void __launch_bounds__(RL_BLOCK) k_verify_exact_math(int which, unsig
 __global__ void __launch_bounds__(RL_BLOCK) k_verify_lazy_refl(uint32_t n, unsigned long long seed, unsigned long long* __restrict__ out);
 __global__ void __launch_bounds__(RL_BLOCK) k_verify_lazy_pdf(uint32_t n, unsigned long long seed, unsigned long long* __restrict__ out);
 __global__ void __launch_bounds__(RL_BLOCK) k_verify_sampler_ranged(int mode, unsigned long long* __restrict__ out);
+__global__ void __launch_bounds__(RL_BLOCK) k_verify_normalize_ranged(int mode, unsigned long long* __restrict__ out);
 
 } // namespace rl

@@ -92,6 +92,12 @@ __device__ __forceinline__ float log_in_range_(float x) { return logf(x); }
 __device__ __forceinline__ float exp_in_range_(float x) { return rlm::expf_in_range_(x); }
 __device__ __forceinline__ float log_in_range_(float x) { return rlm::logf_in_range_(x); }
 #endif
+// acos_ on the ranged sampler's interval of cosThetaI (rl_glibc_math.h acosf_in_range_)
+#if defined(RAYLIB_OCML_MATH)
+__device__ __forceinline__ float acos_in_range_(float x) { return acosf(x); }
+#else
+__device__ __forceinline__ float acos_in_range_(float x) { return rlm::acosf_in_range_(x); }
+#endif
 __device__ __forceinline__ float fmod1_(float x) { return fmodf(x, 1.0f); }
 // tanf and powf always inline, for the one kernel instance that may take them so (rl_dev_shade.h RL_PLAIN_INLINE_TAN / _POW)
 __device__ __forceinline__ float tan_inline_(float x)  { return rlm::tanf_(x); }

@@ -6,6 +6,12 @@
 // The Beckmann sampler with the guard-free forms of logf, expf, sqrtf and 1 / x where its arguments cannot reach the guards (rl_dev_shade.h "the ranged sampler";
 // swept by k_verify_sampler_ranged below).  Measured on this unit's kernel only: every other unit keeps the general sampler.
 #define RL_SAMPLER_RANGED 1
+// The normalisations and single square roots of a scattering event without sqrt_'s and rcp1_'s range guards, each behind one wave vote or a written bound
+// (rl_dev_core.h "normalize without the two range guards"; swept by k_verify_normalize_ranged below).  Bits 1 | 2 | 4 | 8: the surface frame, the sampler's two
+// normalisations, the recomputed half vector, the single-float sites.  As above, this unit's kernels only.
+#ifndef RL_NORMALIZE_RANGED
+#define RL_NORMALIZE_RANGED 15
+#endif
 
 // ---- the device library ----
 #include "rl_kernels.h"
@@ -253,6 +259,66 @@ k_verify_sampler_ranged(int mode, unsigned long long* __restrict__ out)
 	if (top) atomicMax(&out[2], top);
 	if (outside) atomicAdd(&out[3], outside);
 	if (tid == 0) { out[4] = __float_as_uint(RL_SAMPLER_C_MIN); out[5] = __float_as_uint(RL_SAMPLER_COS_NEAR_ONE); }   // the constants this build was compiled with
+}
+
+// Test hook: the ranged normalisations' claims (rl_dev_core.h "normalize without the two range guards"), whatever bits of the setting this build has on.
+//   mode 0: all 2^32 bit patterns x of len2 -- rcp1_in_range_(sqrtf_in_range_(x)) against rcp1_(sqrtf_(x)), normalize's scalar chain.  Counted: the mismatches inside
+//           NormalizeInRange's domain (must be 0); out[2] keeps the smallest pattern outside it at which the chains differ and out[3] counts those;
+//   mode 1: acosf_in_range_ against acos_ on every float of the ranged prologue's interval [RL_SAMPLER_C_MIN, RL_SAMPLER_COS_NEAR_ONE);
+//   mode 2: normalize_voted_ against normalize, component bits compared, on one wave of edge vectors (below) and 2^24 generated ones: waves whose lanes share a
+//           binary scale (2^0 down to 2^-51, where len2 crosses 2^-101, and up to 2^64, where it overflows), waves of mixed scales, waves with a component +-0.
+//           out[1] is the first differing vector's index, out[3] the vectors whose wave took the ranged side.
+// out[0]: mismatches (a NaN may meet a NaN of another payload); out[1]: the smallest mismatching input.
+#define RL_NORMALIZE_SWEEP_VECTORS (64u + (1u << 24))
+__global__ void __launch_bounds__(RL_BLOCK)
+k_verify_normalize_ranged(int mode, unsigned long long* __restrict__ out)
+{
+	RL_MATH_PROLOGUE();
+	const unsigned long long tid = (unsigned long long)blockIdx.x * RL_BLOCK + threadIdx.x, n = (unsigned long long)gridDim.x * RL_BLOCK;
+	unsigned long long bad = 0, first = ~0ull, firstOutside = ~0ull, count = 0;
+	if (mode == 2) {
+		// (whole waves walk the loop together -- RL_NORMALIZE_SWEEP_VECTORS is a multiple of 64 -- for the vote's sake)
+		const float inf = INFINITY, qnan = __uint_as_float(0x7fc00000u), sub = __uint_as_float(1u), lo = 0x1.6a09e6p-51f, hi = 0x1.6a09e8p-51f;   // lo lo < 2^-101 <= hi hi
+		const V3 edge[32] = {
+			v3(0.0f, 0.0f, 0.0f), v3(-0.0f, -0.0f, -0.0f), v3(0.0f, -0.0f, 0.0f), v3(0.0f, 1.0f, 1.0f), v3(1.0f, -0.0f, 1.0f), v3(-1.0f, 1.0f, 0.0f), v3(0.0f, 0.0f, -1.0f), v3(-0.0f, 2.0f, -0.0f),
+			v3(sub, 0.0f, 0.0f), v3(sub, sub, sub), v3(0x1p-70f, 0x1p-70f, 0.0f), v3(0x1p-127f, -0x1p-130f, 0x1p-149f), v3(0x1p-63f, 0.0f, 0x1p-64f), v3(0.0f, -0x1p-74f, 0.0f), v3(0x1p-126f, 0x1p-126f, 0x1p-126f), v3(-0x1p-60f, 0x1p-61f, 0x1p-62f),
+			v3(lo, 0.0f, 0.0f), v3(hi, 0.0f, 0.0f), v3(0.0f, -lo, 0.0f), v3(0.0f, 0.0f, -hi), v3(0x1p-51f, 0x1p-51f, 0.0f), v3(0x1p-51f, 0x1p-52f, 0x1p-52f), v3(0x1p-51f, 0x1p-51f, sub), v3(0x1p-50f, 0.0f, -0.0f),
+			v3(inf, 0.0f, 0.0f), v3(-inf, 1.0f, 1.0f), v3(inf, inf, -inf), v3(qnan, 1.0f, 1.0f), v3(1.0f, qnan, 0.0f), v3(0x1p64f, 0x1p64f, 0.0f), v3(FLT_MAX, -FLT_MAX, FLT_MAX), v3(0x1p63f, -0x1p63f, 0x1p63f) };
+		const int scale[8] = { 0, -20, -45, -50, -51, 40, 63, 64 };
+		for (unsigned long long i = tid; i < RL_NORMALIZE_SWEEP_VECTORS; i += n) {
+			const uint32_t w = (uint32_t)(i >> 6), lane = (uint32_t)i & 63u;
+			V3 v = edge[lane & 31u];
+			if (w > 0u) {
+				Rng g; g.s = raylib_rng_begin(0x6e6f726d616c697aull, (uint32_t)i, 0);
+				const uint32_t cls = w % 10u;
+				int e = scale[cls & 7u];
+				v = v3(2.0f * Next(g) - 1.0f, 2.0f * Next(g) - 1.0f, 2.0f * Next(g) - 1.0f);
+				if (cls == 8u) e = -80 + (int)(Next(g) * 146.0f);
+				if (cls == 9u) { const float z = (lane & 4u) ? -0.0f : 0.0f; const uint32_t k = lane % 3u; if (k == 0u) v.x = z; else if (k == 1u) v.y = z; else v.z = z; }
+				const float s = __uint_as_float((uint32_t)(127 + e) << 23);
+				v = v3(v.x * s, v.y * s, v.z * s);
+			}
+			const bool ranged = !rtm::wave_any_(!NormalizeInRange(v.x * v.x + v.y * v.y + v.z * v.z));
+			const V3 a = normalize_voted_(v), b = normalize(v);
+			if (!SameBitsOrNaN(a.x, b.x) || !SameBitsOrNaN(a.y, b.y) || !SameBitsOrNaN(a.z, b.z)) { ++bad; first = min(first, i); }
+			if (ranged) ++count;
+		}
+	} else {
+		for (unsigned long long b = tid; b < (1ull << 32); b += n) {
+			const uint32_t bits = (uint32_t)b;
+			const float x = __uint_as_float(bits);
+			if (mode == 0) {
+				const bool d = !SameBitsOrNaN(rlm::rcp1_in_range_(rlm::sqrtf_in_range_(x)), rlm::rcp1_(rlm::sqrtf_(x)));
+				if (NormalizeInRange(x)) { if (d) { ++bad; first = min(first, b); } }
+				else if (d) { ++count; firstOutside = min(firstOutside, b); }
+			} else if (x >= RL_SAMPLER_C_MIN && !(x >= RL_SAMPLER_COS_NEAR_ONE)) {
+				if (!SameBitsOrNaN(rtm::acos_in_range_(x), rtm::acos_(x))) { ++bad; first = min(first, b); }
+			}
+		}
+	}
+	if (bad) { atomicAdd(&out[0], bad); atomicMin(&out[1], first); }
+	if (firstOutside != ~0ull) atomicMin(&out[2], firstOutside);
+	if (count) atomicAdd(&out[3], count);
 }
 
 // ---- instances ----

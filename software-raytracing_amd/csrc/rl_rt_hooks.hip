@@ -91,6 +91,20 @@ bool DeviceVerifySamplerRanged(int mode, uint64_t out[6])
 	return ok;
 }
 
+// the ranged normalisations' sweeps (rl_render_lazy.hip), launched the same way
+bool DeviceVerifyNormalizeRanged(int mode, uint64_t out[4])
+{
+	std::lock_guard<std::mutex> lk(Rt().lock);
+	if (!EnsureRuntime()) return false;
+	HIP_OK(hipSetDevice(Rank0().device));
+	unsigned long long h[4] = { 0ull, ~0ull, ~0ull, 0ull };
+	DevBuf<unsigned long long> d;
+	if (!d.Upload(h, 4)) return false;
+	const bool ok = RunOnRank0(k_verify_normalize_ranged, 4096, RL_BLOCK, mode, d.ptr) && Download(h, d.ptr, 4);
+	for (int k = 0; k < 4; ++k) out[k] = h[k];
+	return ok;
+}
+
 // the two sweeps of the lazy instance's guards: three counts each
 static bool VerifyLazySweep(void (*kernel)(uint32_t, unsigned long long, unsigned long long*), uint32_t n, uint64_t seed, uint64_t out[3])
 {

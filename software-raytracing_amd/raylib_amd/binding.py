@@ -1202,6 +1202,7 @@ _EXPORTS = {
     "RaylibAMD_VerifyLazyRefl": (C.c_int32, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "RaylibAMD_VerifyLazyPdf": (C.c_int32, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "RaylibAMD_VerifySamplerRanged": (C.c_int32, [C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "RaylibAMD_VerifyNormalizeRanged": (C.c_int32, [C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "RaylibAMD_PlanRender": (C.c_int32, [C.c_void_p, C.POINTER(RendererSettings), C.c_int32, C.c_int32, C.c_int32, C.POINTER(RenderPlan)]),
     "RaylibAMD_SceneWalk8Host": (C.c_int32, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "RaylibAMD_SceneWalkStackHost": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),

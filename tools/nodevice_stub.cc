@@ -49,6 +49,7 @@ bool DeviceVerifyLazyRefl(uint32_t, uint64_t, uint64_t*) { return false; }
 bool DeviceVerifyLazyPdf(uint32_t, uint64_t, uint64_t*) { return false; }
 bool DeviceVerifyExactMath(int, uint64_t*, uint64_t*) { return false; }
 bool DeviceVerifySamplerRanged(int, uint64_t*) { return false; }
+bool DeviceVerifyNormalizeRanged(int, uint64_t*) { return false; }
 // rl_denoise.hip is a HIP unit too: the device filter fails, and its host restatement (RaylibAMD_DenoiseHost) is not part of this build
 bool DeviceDenoise(Image&, bool, Image*, Image*, Image&, const RaylibAMDDenoiseParams&) { return false; }
 void DenoiseHost(uint32_t, uint32_t, const float*, bool, const float*, const float*, const RaylibAMDDenoiseParams&, float*) {}
