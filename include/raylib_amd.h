@@ -195,7 +195,8 @@ RAYLIB_API int32_t RaylibAMD_PlanRayQuery(SceneHandle scene, int32_t kind, Rayli
  *     that is not finite; a scene that is not finalized; a BVH deeper than 64 levels; no device; on the device entry a plane pointer off rank 0's device, a
  *     16-byte plane that is not 16-byte aligned or `surface` not 4-byte aligned; on the images entry a handle that is unknown, or the same image twice.
  * Still out: the Reflectance mode (it draws random numbers behind the camera's, and the reference reads an uninitialised frame there); jittered samples
- * s >= 1; a views-batch twin; splitting the frame over ranks; a depth or position guide for RaylibAMD_Denoise (it would change the filter's statement). */
+ * s >= 1; a views-batch twin; splitting the frame over ranks.  (RaylibAMD_Denoise has no depth or position guide -- it would change that filter's statement;
+ * RaylibAMD_FilterVariance, statements S3 to S7, is the filter guided by this G-buffer's `hit` and `surface` planes.) */
 typedef struct RaylibAMDGBufferPlanes {
 	RaylibAMDHitT* hit; void* surface;
 	float *albedo, *surfaceNormal, *microNormal, *texcoord, *emission;   /* 4 floats per pixel each */
@@ -250,8 +251,8 @@ RAYLIB_API int32_t RaylibAMD_PlanGBuffer(SceneHandle scene, RaylibAMDQueryPlan* 
  *     W * H above 2^31 - 1; depthTolerance not finite or < 0; maxLength not finite or < 1; an output plane that is one of the history's planes (the taps read
  *     neighbours, so in place is a race); no device; on the device entry a pointer off rank 0's device, a colour, hit or motion plane not 16-byte aligned or
  *     a length plane not 4-byte aligned.
- * Still out: variance / moment planes and neighbourhood colour clamping; an ImageHandle entry; a views-batch twin; motion for spheres and moving cubes;
- * splitting over ranks. */
+ * Still out: neighbourhood colour clamping; an ImageHandle entry; a views-batch twin; motion for spheres and moving cubes; splitting over ranks.  (Moment
+ * planes and the variance-guided filter: statements S1 to S7 below.) */
 typedef struct RaylibAMDMotion { float prevX, prevY, prevT; uint32_t status; } RaylibAMDMotion;   /* 16 bytes */
 #define RAYLIB_AMD_MOTION_NONE    0   /* no previous position: zeros */
 #define RAYLIB_AMD_MOTION_SURFACE 1
@@ -291,6 +292,79 @@ RAYLIB_API int32_t RaylibAMD_TemporalAccumulateDevice(uint32_t width, uint32_t h
 /* The host oracle: the same arrays, no device. */
 RAYLIB_API int32_t RaylibAMD_TemporalAccumulateHost(uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
         const RaylibAMDMotion* motion, const RaylibAMDTemporalFrame* history, float* outColour, float* outLength);
+
+/* ---- variance-guided filter: temporal moments and an a-trous pass on planes ----------------------------
+ * The stage behind the accumulation: the luminance moments carried through the same reprojection, a per-pixel variance derived from them, and an edge-avoiding
+ * a-trous filter whose colour tolerance is that variance and whose guides are the G-buffer's own `hit` and `surface` planes (SVGF's core: Schied et al. 2017).
+ * Albedo is the caller's: divide by the G-buffer's albedo plane before the accumulation and multiply behind the filter.  Arithmetic: float, single IEEE
+ * operations without FMA, a / b and sqrt correctly rounded, expf the library's exact one (csrc/rl_glibc_math.h expf_); a + b + c is (a + b) + c; sums run in
+ * the stated tap order from +0; one source for the device and the host (csrc/rl_temporal.h, csrc/rl_variance.h).
+ * S1  Moments.  For this frame's pixel Y = (0.2126f * r + 0.7152f * g) + 0.0722f * b and m = (Y, Y * Y).  Wherever T7 resets, outMoments = m.  Wherever T7
+ *     blends, on the very taps and weights T7 counted and in T7's tap order from 0: Mk += w * history.moments[k], k = 0, 1; then M = Mk / Wsum and
+ *     outMoments = M + (m - M) / n'.
+ * S2  outColour and outLength of RaylibAMD_TemporalAccumulateMoments are RaylibAMD_TemporalAccumulate's bytes for the same inputs.  Refused: T8's list, a null
+ *     outMoments, a history with a null member (moments included), an output that is one of the history's planes, and on the device entry a moments plane that
+ *     is off rank 0's device or not 8-byte aligned.
+ * S3  Participants.  A pixel whose hit.prim is -1 passes through -- outColour = (colour.rgb, 1), outVariance = +0 -- and is never a tap.  Every other pixel
+ *     takes part, with P and n its surface record's p and n.  A colour channel that is not finite is read as 0, everywhere.
+ * S4  Guide distance between a centre p and a tap q: g = dn + dp.  dn = ((e.x e.x + e.y e.y) + e.z e.z) * invN with e = n(q) - n(p).  With d = P(q) - P(p),
+ *     dd = (d.x d.x + d.y d.y) + d.z d.z and nd = (n(p).x d.x + n(p).y d.y) + n(p).z d.z: dp = (nd * nd) / dd * invPl, and 0 where dd == 0.
+ *     invN = 1 / (sigmaNormal * sigmaNormal), invPl = 1 / (sigmaPlane * sigmaPlane), computed once on the host for both paths.  dp is a ratio -- the squared
+ *     sine of the angle between d and p's tangent plane -- and so has no scene scale.
+ * S5  Initial variance of a participant.  Where length >= historyLength: v0 = max(0, m2 - m1 * m1) with the pixel's own moments.  Elsewhere, over the 7 x 7
+ *     window q = p + (dx, dy), dy outer and dx inner, both -3 .. 3, the participants inside the frame: w = expf(-g), sums of w, w * m1(q), w * m2(q);
+ *     M1 = S1 / Sw, M2 = S2 / Sw and v0 = max(0, M2 - M1 * M1) * (historyLength / max(length, 1)).  max(0, v) is v where v > 0, else +0 (a NaN is 0).
+ * S6  Iteration i = 0 .. K - 1, step s = 2^i, on I_0 = colour and var_0 = v0.  gv(p): var_i under the 3 x 3 kernel at step 1 (dy outer, dx inner; weights
+ *     1/4 at the centre, 1/8 on the edges, 1/16 at the corners) over the participants inside the frame, divided by the sum of the weights used.
+ *     lambda = 1 / (sigmaLuminance * sqrt(gv(p)) + 1e-6f).  Taps q = p + s * (dx, dy), dy outer and dx inner, both -2 .. 2, k = {1/16, 1/4, 3/8, 1/4, 1/16};
+ *     taps outside the frame or not participating are skipped.  dl = |Y(I_i(q)) - Y(I_i(p))| * lambda, w = (k[dx+2] * k[dy+2]) * expf(-(dl + g)).
+ *     I_{i+1}(p) = sum(w * I_i(q)) / sum(w) per channel, var_{i+1}(p) = sum((w * w) * var_i(q)) / (sum(w) * sum(w)).  The centre tap always counts
+ *     (w = 9/64), so the divisor is >= 9/64.  outColour = (I_K, 1), outVariance = var_K.
+ * S7  No output bit depends on how pixels are dealt to lanes, tiles or launches, nor on whether outVariance was asked for.
+ * Filter refused (0, nothing written): a null planes struct, a null colour, moments, length, hit, surface or outColour; W or H equal to 0, or W * H above
+ *     2^31 - 1; iterations outside 1 .. 6; sigmaLuminance, sigmaNormal or sigmaPlane not finite or outside [1e-3, 1e3]; historyLength not finite or < 1;
+ *     outColour equal to colour; no device; on the device entry a pointer off rank 0's device, colour, hit or outColour not 16-byte aligned, moments not 8-byte
+ *     aligned, surface, length or outVariance not 4-byte aligned.
+ * Still out: albedo demodulation inside the call, neighbourhood colour clamping, an ImageHandle entry, a motion launch that emits `surface`, splitting over
+ * ranks. */
+typedef struct RaylibAMDTemporalMomentsFrame {      /* RaylibAMDTemporalFrame and the previous call's outMoments: W * H * 2 floats */
+	const float* colour; const RaylibAMDHitT* hit; const float* length; const float* moments;
+} RaylibAMDTemporalMomentsFrame;
+/* T7 with S1 on arrays in host memory; synchronous, with RaylibAMD_TemporalAccumulate's stats.  outMoments: W * H * 2 floats. */
+RAYLIB_API int32_t RaylibAMD_TemporalAccumulateMoments(uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
+        const RaylibAMDMotion* motion, const RaylibAMDTemporalMomentsFrame* history, float* outColour, float* outLength, float* outMoments);
+/* The same on pointers of rank 0's device, under RaylibAMD_TemporalAccumulateDevice's rules for the stream, the stats and the ranks. */
+RAYLIB_API int32_t RaylibAMD_TemporalAccumulateMomentsDevice(uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
+        const RaylibAMDMotion* motion, const RaylibAMDTemporalMomentsFrame* history, float* outColour, float* outLength, float* outMoments, void* stream);
+/* The host oracle: the same arrays, no device. */
+RAYLIB_API int32_t RaylibAMD_TemporalAccumulateMomentsHost(uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
+        const RaylibAMDMotion* motion, const RaylibAMDTemporalMomentsFrame* history, float* outColour, float* outLength, float* outMoments);
+
+typedef struct RaylibAMDVarianceFilterParams {      /* NULL: 5, 4, 0.35, 0.1, 4 */
+	int32_t iterations;                             /* K, 1 .. 6 */
+	float sigmaLuminance, sigmaNormal, sigmaPlane;  /* each finite, in [1e-3, 1e3] */
+	float historyLength;                            /* finite, >= 1: the length from which the temporal variance is trusted (S5) */
+} RaylibAMDVarianceFilterParams;
+typedef struct RaylibAMDVarianceFilterPlanes {      /* W * H records each, row-major; all required */
+	const float* colour;                            /* 4 floats per pixel: the accumulation's outColour */
+	const float* moments;                           /* 2 floats per pixel: its outMoments */
+	const float* length;                            /* 1 float per pixel: its outLength */
+	const RaylibAMDHitT* hit;                       /* the frame's hit plane, as RaylibAMD_RenderGBuffer or RaylibAMD_RenderMotion writes it */
+	const void* surface;                            /* the G-buffer's 44-byte surface records */
+} RaylibAMDVarianceFilterPlanes;
+/* S3 to S7 on arrays in host memory; synchronous, with stats (pixels = W * H, kernelMs over all 2 + K launches, traceLaunches = 2 + K, wallMs, ranks = 1).
+ * outColour: W * H * 4 floats; outVariance: W * H floats, or NULL.  The library keeps its scratch (48 bytes per pixel on the device, and a host call's
+ * staging) and grows it; a warm call allocates nothing. */
+RAYLIB_API int32_t RaylibAMD_FilterVariance(uint32_t width, uint32_t height, const RaylibAMDVarianceFilterParams* params, const RaylibAMDVarianceFilterPlanes* planes,
+        float* outColour, float* outVariance);
+/* The same on pointers of rank 0's device, under RaylibAMD_TemporalAccumulateDevice's rules for the stream, the stats and the ranks: on a hipStream_t the
+ * launches are enqueued there, behind a RaylibAMD_TemporalAccumulateMomentsDevice enqueued there, with no host synchronisation between them.  Calls on
+ * different streams share the scratch and are ordered one behind the other by an event of the library's. */
+RAYLIB_API int32_t RaylibAMD_FilterVarianceDevice(uint32_t width, uint32_t height, const RaylibAMDVarianceFilterParams* params, const RaylibAMDVarianceFilterPlanes* planes,
+        float* outColour, float* outVariance, void* stream);
+/* The host oracle: the same arrays, no device. */
+RAYLIB_API int32_t RaylibAMD_FilterVarianceHost(uint32_t width, uint32_t height, const RaylibAMDVarianceFilterParams* params, const RaylibAMDVarianceFilterPlanes* planes,
+        float* outColour, float* outVariance);
 
 /* ---- ordered multi-hit ray queries -------------------------------------------------------------
  * The first maxHits surfaces a ray crosses, in order, and how many it crosses in all: ordered transparency and depth peeling, thickness and x-ray views,

@@ -1050,6 +1050,90 @@ int32_t RaylibAMD_TemporalAccumulateHost(uint32_t width, uint32_t height, const 
 	return 1;
 }
 
+// RaylibAMD_TemporalAccumulateMoments / ...Device / ...Host (statements S1 and S2): T8's refusals on the frame's first three planes, then the moments' own
+static bool TemporalMomentsArgsValid(const char* who, uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
+                                     const RaylibAMDMotion* motion, const RaylibAMDTemporalMomentsFrame* history, const float* outColour, const float* outLength, const float* outMoments)
+{
+	const RaylibAMDTemporalFrame three = { history ? history->colour : nullptr, history ? history->hit : nullptr, history ? history->length : nullptr };
+	if (!outMoments || (history && !history->moments)) { Log("%s: null argument", who); return false; }
+	if (!TemporalArgsValid(who, width, height, params, colour, hit, motion, history ? &three : nullptr, outColour, outLength)) return false;
+	if (history)
+		for (const void* o : { (const void*)outColour, (const void*)outLength, (const void*)outMoments })
+			for (const void* h : { (const void*)history->colour, (const void*)history->hit, (const void*)history->length, (const void*)history->moments })
+				if (o == h) { Log("%s: an output plane is one of the history's: the taps read neighbours, in place is a race", who); return false; }
+	return true;
+}
+static int32_t TemporalMomentsInternal(const char* who, uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
+                                       const RaylibAMDMotion* motion, const RaylibAMDTemporalMomentsFrame* history, float* outColour, float* outLength, float* outMoments, bool hostMem,
+                                       void* stream)
+{
+	if (!TemporalMomentsArgsValid(who, width, height, params, colour, hit, motion, history, outColour, outLength, outMoments)) return 0;
+	const RaylibAMDTemporalFrame three = { history ? history->colour : nullptr, history ? history->hit : nullptr, history ? history->length : nullptr };
+	return RunOnDevice(stream, [&](RaylibAMDStats& stats) {
+		return DeviceTemporalAccumulate(width, height, *params, colour, hit, motion, history ? &three : nullptr, outColour, outLength, hostMem, stream, stats,
+		                                history ? history->moments : nullptr, outMoments);
+	});
+}
+int32_t RaylibAMD_TemporalAccumulateMoments(uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
+                                            const RaylibAMDMotion* motion, const RaylibAMDTemporalMomentsFrame* history, float* outColour, float* outLength, float* outMoments)
+{
+	return TemporalMomentsInternal("RaylibAMD_TemporalAccumulateMoments", width, height, params, colour, hit, motion, history, outColour, outLength, outMoments, true, nullptr);
+}
+int32_t RaylibAMD_TemporalAccumulateMomentsDevice(uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
+                                                  const RaylibAMDMotion* motion, const RaylibAMDTemporalMomentsFrame* history, float* outColour, float* outLength, float* outMoments,
+                                                  void* stream)
+{
+	return TemporalMomentsInternal("RaylibAMD_TemporalAccumulateMomentsDevice", width, height, params, colour, hit, motion, history, outColour, outLength, outMoments, false, stream);
+}
+int32_t RaylibAMD_TemporalAccumulateMomentsHost(uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
+                                                const RaylibAMDMotion* motion, const RaylibAMDTemporalMomentsFrame* history, float* outColour, float* outLength, float* outMoments)
+{
+	if (!TemporalMomentsArgsValid("RaylibAMD_TemporalAccumulateMomentsHost", width, height, params, colour, hit, motion, history, outColour, outLength, outMoments)) return 0;
+	TemporalAccumulateMomentsHost(width, height, *params, colour, hit, motion, history, outColour, outLength, outMoments);
+	return 1;
+}
+
+// RaylibAMD_FilterVariance / ...Device / ...Host (statements S3 to S7): the refusals every entry shares; `use` receives the caller's parameters or the defaults
+static bool FilterVarianceArgsValid(const char* who, uint32_t width, uint32_t height, const RaylibAMDVarianceFilterParams* params, const RaylibAMDVarianceFilterPlanes* planes,
+                                    const float* outColour, RaylibAMDVarianceFilterParams& use)
+{
+	if (!planes || !planes->colour || !planes->moments || !planes->length || !planes->hit || !planes->surface || !outColour) { Log("%s: null argument", who); return false; }
+	const uint64_t pixels = (uint64_t)width * height;
+	if (pixels == 0 || pixels > 0x7fffffffull) { Log("%s: a frame of %u x %u pixels (1 .. 2^31 - 1)", who, width, height); return false; }
+	use = params ? *params : RaylibAMDVarianceFilterParams{ 5, 4.0f, 0.35f, 0.1f, 4.0f };
+	if (use.iterations < 1 || use.iterations > 6) { Log("%s: %d iterations (1 .. 6)", who, use.iterations); return false; }
+	const float sigma[3] = { use.sigmaLuminance, use.sigmaNormal, use.sigmaPlane };
+	for (float v : sigma) if (!std::isfinite(v) || v < 1e-3f || v > 1e3f) { Log("%s: a sigma of %g is not in [1e-3, 1e3]", who, v); return false; }
+	if (!std::isfinite(use.historyLength) || use.historyLength < 1.0f) { Log("%s: historyLength %g is not a finite number >= 1", who, use.historyLength); return false; }
+	if (outColour == planes->colour) { Log("%s: outColour is the colour plane: the taps read neighbours", who); return false; }
+	return true;
+}
+static int32_t FilterVarianceInternal(const char* who, uint32_t width, uint32_t height, const RaylibAMDVarianceFilterParams* params, const RaylibAMDVarianceFilterPlanes* planes,
+                                      float* outColour, float* outVariance, bool hostMem, void* stream)
+{
+	RaylibAMDVarianceFilterParams use;
+	if (!FilterVarianceArgsValid(who, width, height, params, planes, outColour, use)) return 0;
+	return RunOnDevice(stream, [&](RaylibAMDStats& stats) { return DeviceFilterVariance(width, height, use, *planes, outColour, outVariance, hostMem, stream, stats); });
+}
+int32_t RaylibAMD_FilterVariance(uint32_t width, uint32_t height, const RaylibAMDVarianceFilterParams* params, const RaylibAMDVarianceFilterPlanes* planes, float* outColour,
+                                 float* outVariance)
+{
+	return FilterVarianceInternal("RaylibAMD_FilterVariance", width, height, params, planes, outColour, outVariance, true, nullptr);
+}
+int32_t RaylibAMD_FilterVarianceDevice(uint32_t width, uint32_t height, const RaylibAMDVarianceFilterParams* params, const RaylibAMDVarianceFilterPlanes* planes, float* outColour,
+                                       float* outVariance, void* stream)
+{
+	return FilterVarianceInternal("RaylibAMD_FilterVarianceDevice", width, height, params, planes, outColour, outVariance, false, stream);
+}
+int32_t RaylibAMD_FilterVarianceHost(uint32_t width, uint32_t height, const RaylibAMDVarianceFilterParams* params, const RaylibAMDVarianceFilterPlanes* planes, float* outColour,
+                                     float* outVariance)
+{
+	RaylibAMDVarianceFilterParams use;
+	if (!FilterVarianceArgsValid("RaylibAMD_FilterVarianceHost", width, height, params, planes, outColour, use)) return 0;
+	if (!FilterVarianceHost(width, height, use, *planes, outColour, outVariance)) { Log("RaylibAMD_FilterVarianceHost: no memory for a frame of %u x %u pixels", width, height); return 0; }
+	return 1;
+}
+
 // RaylibAMD_TraceRaysAll / RaylibAMD_TraceRaysAllDevice / RaylibAMD_TraceRaysAllHost / RaylibAMD_PlanRayQueryAll (statements M1 to M5): the refusals every entry shares
 static bool TraceRaysAllArgsValid(const char* who, const Scene* s, const void* rays, int32_t n, float rayTime, int32_t maxHits, const void* outHits)
 {

@@ -283,7 +283,11 @@ bool DeviceRenderMotion(Scene& scene, const RendererSettings& settings, const DC
 // RaylibAMD_TemporalAccumulate (hostMem) and RaylibAMD_TemporalAccumulateDevice on rank 0's device, behind frames in flight (stream: as DeviceTraceRays).  history
 // is null or has three planes; the frame has 1 .. 2^31 - 1 pixels, the parameters are in range, no output is a history plane: the ABI checked.
 bool DeviceTemporalAccumulate(uint32_t width, uint32_t height, const RaylibAMDTemporalParams& params, const float* colour, const RaylibAMDHitT* hit, const RaylibAMDMotion* motion,
-                              const RaylibAMDTemporalFrame* history, float* outColour, float* outLength, bool hostMem, void* stream, RaylibAMDStats& stats);
+                              const RaylibAMDTemporalFrame* history, float* outColour, float* outLength, bool hostMem, void* stream, RaylibAMDStats& stats,
+                              const float* histMoments = nullptr, float* outMoments = nullptr);
+// RaylibAMD_FilterVariance (hostMem) and RaylibAMD_FilterVarianceDevice, under the same rules.  params: the caller's or the defaults, checked.
+bool DeviceFilterVariance(uint32_t width, uint32_t height, const RaylibAMDVarianceFilterParams& params, const RaylibAMDVarianceFilterPlanes& planes, float* outColour,
+                          float* outVariance, bool hostMem, void* stream, RaylibAMDStats& stats);
 // RaylibAMD_TraceRaysAll (hostMem) and RaylibAMD_TraceRaysAllDevice, as DeviceTraceRays: outHits holds n rows of maxHits records, outCount (may be null) n words.
 // The scene holds triangles only, 1 <= maxHits <= RAYLIB_AMD_MAX_HITS and n * maxHits fits an int32_t: the ABI checked.
 bool DeviceTraceRaysAll(Scene& scene, const void* rays, int32_t n, int32_t maxHits, void* outHits, uint32_t* outCount, bool hostMem, void* stream, RaylibAMDStats& stats);

@@ -13,7 +13,9 @@
 //                        query unit widens the candidate rule, so this one is apart from it, and from the render kernels for k_query's reason
 //   rl_motion.hip        k_motion (RaylibAMD_RenderMotion): k_gbuffer's pixels, rays and walks with another finish -- the hit plane and the motion plane
 //                        (rl_motion.h); apart so that k_gbuffer and every other unit stay the code they are
-//   rl_temporal.hip      k_temporal (RaylibAMD_TemporalAccumulate): a streaming kernel on planes (rl_temporal.h); no scene, no walk
+//   rl_temporal.hip      k_temporal (RaylibAMD_TemporalAccumulate): a streaming kernel on planes (rl_temporal.h); no scene, no walk.  k_temporal_moments
+//                        (RaylibAMD_TemporalAccumulateMoments): the same walk with the moments' planes beside it
+//   rl_variance.hip      k_vf_pack, k_vf_variance, k_vf_iter (RaylibAMD_FilterVariance): the variance-guided a-trous filter on planes (rl_variance.h); no scene
 //   rl_multihit.hip      k_query_all (RaylibAMD_TraceRaysAll): the binary and the 8-wide walk again with a sorted list behind the triangle test, written on the
 //                        shared steps; apart so that k_query and every other unit stay the code they are
 //   rl_nearest.hip       k_nearest (RaylibAMD_NearestPoints): a walk of its own (point-to-box distances, no ray), which shares with the others the records and the
@@ -39,6 +41,7 @@
 
 #include "rl_dev_jobs.h"
 #include "rl_dev_pool.h"
+#include "rl_variance.h"
 
 namespace rl {
 
@@ -235,6 +238,23 @@ struct DTemporal {
 	float4* outColour; float* outLength;
 };
 __global__ void __launch_bounds__(RL_BLOCK) k_temporal(const DTemporal);
+// ... with the luminance moments beside it (RaylibAMD_TemporalAccumulateMoments, statements S1 and S2): the history's moments (null with the other three) and
+// the output's, two floats per pixel, 8-byte aligned
+__global__ void __launch_bounds__(RL_BLOCK) k_temporal_moments(const DTemporal, const float2* __restrict__, float2* __restrict__);
+
+// ---------------------------------------------------------------------------
+// The variance-guided filter (RaylibAMD_FilterVariance, statements S3 to S7; rl_variance.hip, arithmetic of rl_variance.h).  pack: colour, hit (float4 each) and
+// surface (11 words per pixel) of `pixels` pixels -> guides, values.  variance: guides, moments (2 floats per pixel), length, W, H, the constants; writes
+// values[].var.  iter: values in, guides, W, H, the step, the constants, values out (LAST: not written), the caller's colour and variance planes (LAST only;
+// the variance plane may be null).  pack takes ceil(pixels / RL_BLOCK) workgroups, the other two one per 16 x 16 tile, row-major.
+__global__ void __launch_bounds__(RL_BLOCK) k_vf_pack(const float4* __restrict__, const float4* __restrict__, const float* __restrict__, uint32_t, VfGuide* __restrict__,
+                                                      VfValue* __restrict__);
+__global__ void __launch_bounds__(RL_BLOCK) k_vf_variance(const VfGuide* __restrict__, const float* __restrict__, const float* __restrict__, uint32_t, uint32_t, const VfConst,
+                                                          VfValue*);
+#define RL_VF_ITER_ARGS const VfValue* __restrict__, const VfGuide* __restrict__, uint32_t, uint32_t, int32_t, const VfConst, VfValue* __restrict__, float4* __restrict__, float* __restrict__
+template <bool LAST> __global__ void __launch_bounds__(RL_BLOCK) k_vf_iter(RL_VF_ITER_ARGS);
+extern template __global__ void k_vf_iter<false>(RL_VF_ITER_ARGS);
+extern template __global__ void k_vf_iter<true>(RL_VF_ITER_ARGS);
 
 // ---------------------------------------------------------------------------
 // The ordered multi-hit ray queries (RaylibAMD_TraceRaysAll; rl_k_multihit.inl)

@@ -8,11 +8,13 @@
 #include "rl_contact.h"
 #include "rl_motion.h"
 #include "rl_temporal.h"
+#include "rl_variance.h"
 #include "raylib_amd_rng.h"
 
 #include <string.h>
 #include <algorithm>
 #include <cmath>
+#include <new>
 
 namespace rl {
 
@@ -83,8 +85,9 @@ void ForEachOverlap(const Scene& s, const RaylibAMDOverlapQuery& Q, bool skipSha
 
 // the temporal oracle's reads: arrays of any alignment
 struct HostTaps {
-	const float* colour; const RaylibAMDHitT* hit; const float* length;
+	const float* colour; const RaylibAMDHitT* hit; const float* length; const float* moments;
 	bool Has() const { return colour != nullptr; }
+	void Moments(size_t q, float m[2]) const { memcpy(m, moments + 2 * q, 2 * sizeof(float)); }
 	TemporalTap Read(size_t q) const
 	{
 		TemporalTap t; RaylibAMDHitT h;
@@ -279,18 +282,71 @@ void MotionHost(uint32_t width, uint32_t height, const DCamera& pc, int32_t firs
 	}
 }
 
-// Statement T7 (rl_temporal.h, the kernel's own source) per pixel
+// Statement T7 (rl_temporal.h, the kernel's own source) per pixel; MOMENTS: with statement S1 beside it
+template <bool MOMENTS>
+static void TemporalPixelsHost(uint32_t width, uint32_t height, const RaylibAMDTemporalParams& params, const float* colour, const RaylibAMDHitT* hit, const RaylibAMDMotion* motion,
+                               const HostTaps& taps, float* outColour, float* outLength, float* outMoments)
+{
+	for (size_t p = 0; p < (size_t)width * height; ++p) {
+		RaylibAMDHitT h; RaylibAMDMotion m; float c[3], o[4], len, mom[2];
+		memcpy(&h, hit + p, sizeof(h)); memcpy(&m, motion + p, sizeof(m)); memcpy(c, colour + 4 * p, sizeof(c));
+		TemporalPixelM<MOMENTS>(width, height, c, h.prim, m.prevX, m.prevY, m.prevT, m.status, params.depthTolerance, params.maxLength, taps, o, len, mom);
+		o[3] = 1.0f;
+		memcpy(outColour + 4 * p, o, sizeof(o)); memcpy(outLength + p, &len, sizeof(len));
+		if (MOMENTS) memcpy(outMoments + 2 * p, mom, sizeof(mom));
+	}
+}
 void TemporalAccumulateHost(uint32_t width, uint32_t height, const RaylibAMDTemporalParams& params, const float* colour, const RaylibAMDHitT* hit, const RaylibAMDMotion* motion,
                             const RaylibAMDTemporalFrame* history, float* outColour, float* outLength)
 {
-	const HostTaps taps = { history ? history->colour : nullptr, history ? history->hit : nullptr, history ? history->length : nullptr };
-	for (size_t p = 0; p < (size_t)width * height; ++p) {
-		RaylibAMDHitT h; RaylibAMDMotion m; float c[3], o[4], len;
-		memcpy(&h, hit + p, sizeof(h)); memcpy(&m, motion + p, sizeof(m)); memcpy(c, colour + 4 * p, sizeof(c));
-		TemporalPixel(width, height, c, h.prim, m.prevX, m.prevY, m.prevT, m.status, params.depthTolerance, params.maxLength, taps, o, len);
-		o[3] = 1.0f;
-		memcpy(outColour + 4 * p, o, sizeof(o)); memcpy(outLength + p, &len, sizeof(len));
+	const HostTaps taps = { history ? history->colour : nullptr, history ? history->hit : nullptr, history ? history->length : nullptr, nullptr };
+	TemporalPixelsHost<false>(width, height, params, colour, hit, motion, taps, outColour, outLength, nullptr);
+}
+void TemporalAccumulateMomentsHost(uint32_t width, uint32_t height, const RaylibAMDTemporalParams& params, const float* colour, const RaylibAMDHitT* hit, const RaylibAMDMotion* motion,
+                                   const RaylibAMDTemporalMomentsFrame* history, float* outColour, float* outLength, float* outMoments)
+{
+	const HostTaps taps = { history ? history->colour : nullptr, history ? history->hit : nullptr, history ? history->length : nullptr, history ? history->moments : nullptr };
+	TemporalPixelsHost<true>(width, height, params, colour, hit, motion, taps, outColour, outLength, outMoments);
+}
+
+// Statements S3 to S6 (rl_variance.h, the kernels' own source): the packed records the device makes, then the same per-pixel functions in the same order of
+// launches.  The caller's arrays may have any alignment and outColour may be any of them but `colour`: everything is read before anything is written.
+bool FilterVarianceHost(uint32_t width, uint32_t height, const RaylibAMDVarianceFilterParams& P, const RaylibAMDVarianceFilterPlanes& planes, float* outColour, float* outVariance)
+{
+	const int W = (int)width, H = (int)height;
+	const size_t n = (size_t)width * height;
+	const VfConst c = MakeVfConst(P.sigmaLuminance, P.sigmaNormal, P.sigmaPlane, P.historyLength);
+	std::vector<VfGuide> guides;
+	std::vector<VfValue> a, b;
+	std::vector<float> moments, length;
+	try { guides.resize(n); a.resize(n); b.resize(n); moments.resize(2 * n); length.resize(n); }
+	catch (const std::bad_alloc&) { return false; }   // (the ABI logs it)
+	memcpy(moments.data(), planes.moments, 2 * n * sizeof(float)); memcpy(length.data(), planes.length, n * sizeof(float));
+	for (size_t p = 0; p < n; ++p) {
+		RaylibAMDHitT h; float s[11], col[3];
+		memcpy(&h, planes.hit + p, sizeof(h)); memcpy(s, (const char*)planes.surface + 44 * p, sizeof(s)); memcpy(col, planes.colour + 4 * p, sizeof(col));
+		guides[p] = VfPackGuide(h.prim, s + 2, s + 5);
+		a[p].r = VfFin(col[0]); a[p].g = VfFin(col[1]); a[p].b = VfFin(col[2]); a[p].var = 0.0f;
 	}
+	for (int y = 0; y < H; ++y)
+		for (int x = 0; x < W; ++x) {
+			const size_t p = (size_t)y * width + (size_t)x;
+			if (guides[p].prim != -1) a[p].var = VfInitialVariance(guides.data(), moments.data(), length.data(), W, H, x, y, c);
+		}
+	for (int i = 0; i < P.iterations; ++i) {
+		for (int y = 0; y < H; ++y)
+			for (int x = 0; x < W; ++x) {
+				const size_t p = (size_t)y * width + (size_t)x;
+				b[p] = guides[p].prim == -1 ? a[p] : VfFilterPixel(a.data(), guides.data(), W, H, x, y, 1 << i, c);
+			}
+		a.swap(b);
+	}
+	for (size_t p = 0; p < n; ++p) {
+		const float o[4] = { a[p].r, a[p].g, a[p].b, 1.0f };
+		memcpy(outColour + 4 * p, o, sizeof(o));
+		if (outVariance) memcpy(outVariance + p, &a[p].var, sizeof(float));
+	}
+	return true;
 }
 
 // statements A1 to A3 on the caller's keys: the oracle of k_gather_adaptive_resolve's moments and decision (rl_progressive.h, built without FMA)

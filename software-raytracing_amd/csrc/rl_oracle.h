@@ -1,5 +1,5 @@
 // The host oracles (rl_oracle.cc): every query family's brute-force loop over the scene's triangles, in the arithmetic the kernels compile from the same
-// headers (rl_nearest.h, rl_sweep.h, rl_overlap.h, rl_contact.h, rl_sdf.h, rl_motion.h, rl_temporal.h, rl_progressive.h).  They are test instruments: the
+// headers (rl_nearest.h, rl_sweep.h, rl_overlap.h, rl_contact.h, rl_sdf.h, rl_motion.h, rl_temporal.h, rl_variance.h, rl_progressive.h).  They are test instruments: the
 // tests hold the kernels to them byte for byte.  Plain C++ on a scene whose host copies are current: no handle, no log, no refusal and no device -- the ABI
 // (rl_abi.cc: the family's ...ArgsValid, then RunOnHost) has checked the arguments and read back what a move left stale before it calls one of these.
 #pragma once
@@ -56,6 +56,10 @@ void MotionHost(uint32_t width, uint32_t height, const DCamera& prevCamera, int3
                 RaylibAMDMotion* outMotion);
 void TemporalAccumulateHost(uint32_t width, uint32_t height, const RaylibAMDTemporalParams& params, const float* colour, const RaylibAMDHitT* hit, const RaylibAMDMotion* motion,
                             const RaylibAMDTemporalFrame* history, float* outColour, float* outLength);
+void TemporalAccumulateMomentsHost(uint32_t width, uint32_t height, const RaylibAMDTemporalParams& params, const float* colour, const RaylibAMDHitT* hit, const RaylibAMDMotion* motion,
+                                   const RaylibAMDTemporalMomentsFrame* history, float* outColour, float* outLength, float* outMoments);
+// P: the caller's parameters or the defaults; planes: all five given.  False: no memory for the packed planes (nothing written)
+bool FilterVarianceHost(uint32_t width, uint32_t height, const RaylibAMDVarianceFilterParams& P, const RaylibAMDVarianceFilterPlanes& planes, float* outColour, float* outVariance);
 void GatherAdaptiveDecideHost(const RaylibAMDGatherAdaptiveParams& adaptive, uint32_t cap, const float* keys, int64_t count, uint32_t* outSamples);
 void GatherDirectionsHost(const RaylibAMDGatherParams& params, const RaylibAMDGatherPoint* points, int32_t n, uint64_t seed, uint32_t sample, float* outDirs);
 

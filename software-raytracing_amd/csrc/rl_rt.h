@@ -200,6 +200,10 @@ struct RankCtx {
 	DevBuf<void> qOut, qPrim;  // a host call's first output; its second (primitives, counts)
 	DevBuf<void> qContact;     // a host contacts call's records (RaylibAMD_OverlapContacts), staged as qPrim is
 	DevBuf<void> qPlane3, qPlane4, qPlane5, qPlane6;   // a host G-buffer call's fourth to seventh plane (RaylibAMD_RenderGBuffer), staged as qPrim is
+	// a variance filter call's scratch (DeviceFilterVariance), kept and grown: the packed guides, the two value planes of the iterations' ping-pong, and the
+	// event behind the last call's last launch -- every call waits for it on its own stream
+	DevBuf<VfGuide> vfGuides; DevBuf<VfValue> vfValues[2];
+	hipEvent_t vfEv = nullptr; bool vfEvUsed = false;
 	// a distance-field bake's bit volumes (DeviceBakeDistanceField), kept and grown, and the event behind the last bake's last kernel -- every bake waits for it
 	// on its own stream, so that two bakes on two streams never share the volumes at the same time
 	DevBuf<uint32_t> sdfBits;

@@ -451,29 +451,103 @@ bool DeviceRenderMotion(Scene& sc, const RendererSettings& settings, const DCame
 }
 
 // A temporal accumulation (RaylibAMD_TemporalAccumulate, statements T7 and T8): no scene, no plan, no work counter -- planes in, planes out, on rank 0's
-// device.  A host call stages its inputs back to back in qRays (every plane's size is a multiple of 16 bytes but the length plane's, which comes last) and
-// its outputs through qOut and qPrim.  A synchronous call brackets the kernel with the queries' event pair.
+// device.  A host call stages its inputs back to back in qRays (every plane's size is a multiple of 16 bytes but the moments', a multiple of 8, and the length
+// plane's, which come last in that order) and its outputs through qOut, qPrim and qContact.  A synchronous call brackets the kernel with the queries' event
+// pair.  outMoments (RaylibAMD_TemporalAccumulateMoments, statements S1 and S2): k_temporal_moments with the history's moments and that output beside the rest.
 static_assert(sizeof(RaylibAMDHitT) == sizeof(float4), "hit records");
 bool DeviceTemporalAccumulate(uint32_t W, uint32_t H, const RaylibAMDTemporalParams& params, const float* colour, const RaylibAMDHitT* hit, const RaylibAMDMotion* motion,
-                              const RaylibAMDTemporalFrame* history, float* outColour, float* outLength, bool hostMem, void* stream, RaylibAMDStats& stats)
+                              const RaylibAMDTemporalFrame* history, float* outColour, float* outLength, bool hostMem, void* stream, RaylibAMDStats& stats,
+                              const float* histMoments, float* outMoments)
 {
-	static const char* api = "RaylibAMD_TemporalAccumulate";
+	const char* api = outMoments ? "RaylibAMD_TemporalAccumulateMoments" : "RaylibAMD_TemporalAccumulate";
 	const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
 	const std::lock_guard<std::mutex> lock{ Rt().lock };
 	if (!EnsureRuntime()) return false;
 	RankCtx& R = Rank0();
 	HIP_OK(hipSetDevice(R.device));
-	const size_t pixels = (size_t)W * H, plane = pixels * sizeof(float4), lengths = pixels * sizeof(float);
-	const void* in[6] = { colour, hit, motion, history ? history->colour : nullptr, history ? (const void*)history->hit : nullptr, history ? history->length : nullptr };
-	const size_t inBytes[6] = { plane, plane, plane, history ? plane : 0, history ? plane : 0, history ? lengths : 0 };
-	QueryOut out[2] = { { outColour, plane, 15u, &RankCtx::qOut }, { outLength, lengths, 3u, &RankCtx::qPrim } };
+	const size_t pixels = (size_t)W * H, plane = pixels * sizeof(float4), lengths = pixels * sizeof(float), pairs = pixels * sizeof(float2);
+	const void* in[7] = { colour, hit, motion, history ? history->colour : nullptr, history ? (const void*)history->hit : nullptr, history ? histMoments : nullptr,
+	                      history ? history->length : nullptr };
+	const size_t inBytes[7] = { plane, plane, plane, history ? plane : 0, history ? plane : 0, history && outMoments ? pairs : 0, history ? lengths : 0 };
+	const uintptr_t inAlign[7] = { 15u, 15u, 15u, 15u, 15u, 7u, 3u };
+	QueryOut out[3] = { { outColour, plane, 15u, &RankCtx::qOut }, { outLength, lengths, 3u, &RankCtx::qPrim }, { outMoments, outMoments ? pairs : 0, 7u, &RankCtx::qContact } };
 	if (!hostMem) {
 		bool onDevice = true;
-		for (int k = 0; k < 6; ++k) if (inBytes[k] && !OnDevice(in[k], R.device)) onDevice = false;
+		for (int k = 0; k < 7; ++k) if (inBytes[k] && !OnDevice(in[k], R.device)) onDevice = false;
 		if (!onDevice) { Log("%sDevice: a pointer is not device memory of device %d", api, R.device); return false; }
-		for (int k = 0; k < 6; ++k)
-			if (inBytes[k] && ((uintptr_t)in[k] & (k == 5 ? 3u : 15u)) != 0) { Log("%sDevice: an input plane is not %u-byte aligned", api, k == 5 ? 4u : 16u); return false; }
-		if (!DevicePointersOk("RaylibAMD_TemporalAccumulateDevice", nullptr, R.device, nullptr, out, 2)) return false;
+		for (int k = 0; k < 7; ++k)
+			if (inBytes[k] && ((uintptr_t)in[k] & inAlign[k]) != 0) { Log("%sDevice: an input plane is not %u-byte aligned", api, (unsigned)inAlign[k] + 1u); return false; }
+		if (!DevicePointersOk(outMoments ? "RaylibAMD_TemporalAccumulateMomentsDevice" : "RaylibAMD_TemporalAccumulateDevice", nullptr, R.device, nullptr, out, 3)) return false;
+	}
+	const hipStream_t st = stream ? (hipStream_t)stream : R.stream;
+	const bool sync = !stream;
+	if (sync && !EnsureSyncStats(R)) return false;
+	memset(&stats, 0, sizeof(stats));
+	stats.ranks = 1; stats.devices = 1;
+	if (!StageOutputs(R, out, 3, hostMem)) return false;
+	const void* dev[7];
+	if (hostMem) {
+		size_t total = 0;
+		for (int k = 0; k < 7; ++k) total += inBytes[k];
+		if (!R.qRays.Grow(total)) return false;
+		size_t at = 0;
+		for (int k = 0; k < 7; ++k) {
+			dev[k] = inBytes[k] ? (const char*)R.qRays.ptr + at : nullptr;
+			if (inBytes[k]) HIP_OK(hipMemcpyAsync((void*)dev[k], in[k], inBytes[k], hipMemcpyHostToDevice, st));
+			at += inBytes[k];
+		}
+	} else {
+		for (int k = 0; k < 7; ++k) dev[k] = inBytes[k] ? in[k] : nullptr;
+	}
+	DTemporal T; memset(&T, 0, sizeof(T));
+	T.width = W; T.height = H; T.cellsX = (W + 7u) / 8u; T.numCells = T.cellsX * ((H + 7u) / 8u);
+	T.depthTolerance = params.depthTolerance; T.maxLength = params.maxLength;
+	T.colour = (const float4*)dev[0]; T.hit = (const float4*)dev[1]; T.motion = (const float4*)dev[2];
+	T.histColour = (const float4*)dev[3]; T.histHit = (const float4*)dev[4]; T.histLength = (const float*)dev[6];
+	T.outColour = (float4*)out[0].dev; T.outLength = (float*)out[1].dev;
+	// a wave per cell at a time: workgroups enough for the cells, at most the device filled once at the kernel's occupancy
+	const void* kernel = outMoments ? (const void*)k_temporal_moments : (const void*)k_temporal;
+	const int perCU = OccupancyOf(R, kernel);
+	if (perCU < 0) return false;
+	const uint64_t cellBlocks = ((uint64_t)T.numCells + RL_BLOCK / 64u - 1u) / (RL_BLOCK / 64u);
+	const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)R.numCUs * (uint64_t)std::max(1, perCU), cellBlocks));
+	if (sync && !BeginSync(R, st)) return false;
+	if (outMoments) hipLaunchKernelGGL(k_temporal_moments, dim3(blocks), dim3(RL_BLOCK), 0, st, T, (const float2*)dev[5], (float2*)out[2].dev);
+	else hipLaunchKernelGGL(k_temporal, dim3(blocks), dim3(RL_BLOCK), 0, st, T);
+	HIP_OK(hipGetLastError());
+	if (!sync) return true;
+	const bool ok = FinishSync(R, st, { CopyBack(out[0], hostMem), CopyBack(out[1], hostMem), CopyBack(out[2], hostMem) }, t0, stats);
+	if (ok) stats.pixels = pixels;
+	return ok;
+}
+
+// A variance-guided filter call (RaylibAMD_FilterVariance, statements S3 to S7): planes in, planes out, as the accumulation; 2 + K launches on the call's
+// stream with the library's scratch between them -- the guides (32 bytes per pixel) and the two value planes of the iterations' ping-pong (16 each), kept and
+// grown.  Calls on different streams share that scratch: every call waits on its own stream for the event behind the last call's last launch (vfEv), as the
+// path calls do with radEv.  A host call stages its inputs in qRays -- colour, hit (multiples of 16 bytes), moments (of 8), surface, length (of 4) -- and its
+// outputs through qOut and qPrim.
+static_assert(sizeof(DHitOut) == 11 * sizeof(float), "surface records are 11 words");
+bool DeviceFilterVariance(uint32_t W, uint32_t H, const RaylibAMDVarianceFilterParams& params, const RaylibAMDVarianceFilterPlanes& planes, float* outColour, float* outVariance,
+                          bool hostMem, void* stream, RaylibAMDStats& stats)
+{
+	static const char* api = "RaylibAMD_FilterVariance";
+	const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+	const std::lock_guard<std::mutex> lock{ Rt().lock };
+	if (!EnsureRuntime()) return false;
+	RankCtx& R = Rank0();
+	HIP_OK(hipSetDevice(R.device));
+	const size_t pixels = (size_t)W * H;
+	const void* in[5] = { planes.colour, planes.hit, planes.moments, planes.surface, planes.length };
+	const size_t inBytes[5] = { pixels * sizeof(float4), pixels * sizeof(float4), pixels * sizeof(float2), pixels * sizeof(DHitOut), pixels * sizeof(float) };
+	const uintptr_t inAlign[5] = { 15u, 15u, 7u, 3u, 3u };
+	QueryOut out[2] = { { outColour, pixels * sizeof(float4), 15u, &RankCtx::qOut }, { outVariance, outVariance ? pixels * sizeof(float) : 0, 3u, &RankCtx::qPrim } };
+	if (!hostMem) {
+		bool onDevice = true;
+		for (int k = 0; k < 5; ++k) if (!OnDevice(in[k], R.device)) onDevice = false;
+		if (!onDevice) { Log("%sDevice: a pointer is not device memory of device %d", api, R.device); return false; }
+		for (int k = 0; k < 5; ++k)
+			if (((uintptr_t)in[k] & inAlign[k]) != 0) { Log("%sDevice: an input plane is not %u-byte aligned", api, (unsigned)inAlign[k] + 1u); return false; }
+		if (!DevicePointersOk("RaylibAMD_FilterVarianceDevice", nullptr, R.device, nullptr, out, 2)) return false;
 	}
 	const hipStream_t st = stream ? (hipStream_t)stream : R.stream;
 	const bool sync = !stream;
@@ -481,37 +555,46 @@ bool DeviceTemporalAccumulate(uint32_t W, uint32_t H, const RaylibAMDTemporalPar
 	memset(&stats, 0, sizeof(stats));
 	stats.ranks = 1; stats.devices = 1;
 	if (!StageOutputs(R, out, 2, hostMem)) return false;
-	const void* dev[6];
+	if (!R.vfGuides.Grow(pixels * sizeof(VfGuide)) || !R.vfValues[0].Grow(pixels * sizeof(VfValue)) || !R.vfValues[1].Grow(pixels * sizeof(VfValue))) return false;
+	if (!R.vfEv) HIP_OK(hipEventCreateWithFlags(&R.vfEv, hipEventDisableTiming));
+	const void* dev[5];
 	if (hostMem) {
 		size_t total = 0;
-		for (int k = 0; k < 6; ++k) total += inBytes[k];
+		for (int k = 0; k < 5; ++k) total += inBytes[k];
 		if (!R.qRays.Grow(total)) return false;
 		size_t at = 0;
-		for (int k = 0; k < 6; ++k) {
-			dev[k] = inBytes[k] ? (const char*)R.qRays.ptr + at : nullptr;
-			if (inBytes[k]) HIP_OK(hipMemcpyAsync((void*)dev[k], in[k], inBytes[k], hipMemcpyHostToDevice, st));
+		for (int k = 0; k < 5; ++k) {
+			dev[k] = (const char*)R.qRays.ptr + at;
+			HIP_OK(hipMemcpyAsync((void*)dev[k], in[k], inBytes[k], hipMemcpyHostToDevice, st));
 			at += inBytes[k];
 		}
 	} else {
-		for (int k = 0; k < 6; ++k) dev[k] = in[k];
+		for (int k = 0; k < 5; ++k) dev[k] = in[k];
 	}
-	DTemporal T; memset(&T, 0, sizeof(T));
-	T.width = W; T.height = H; T.cellsX = (W + 7u) / 8u; T.numCells = T.cellsX * ((H + 7u) / 8u);
-	T.depthTolerance = params.depthTolerance; T.maxLength = params.maxLength;
-	T.colour = (const float4*)dev[0]; T.hit = (const float4*)dev[1]; T.motion = (const float4*)dev[2];
-	T.histColour = (const float4*)dev[3]; T.histHit = (const float4*)dev[4]; T.histLength = (const float*)dev[5];
-	T.outColour = (float4*)out[0].dev; T.outLength = (float*)out[1].dev;
-	// a wave per cell at a time: workgroups enough for the cells, at most the device filled once at the kernel's occupancy
-	const int perCU = OccupancyOf(R, (const void*)k_temporal);
-	if (perCU < 0) return false;
-	const uint64_t cellBlocks = ((uint64_t)T.numCells + RL_BLOCK / 64u - 1u) / (RL_BLOCK / 64u);
-	const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)R.numCUs * (uint64_t)std::max(1, perCU), cellBlocks));
+	if (R.vfEvUsed) HIP_OK(hipStreamWaitEvent(st, R.vfEv, 0));
+	const VfConst c = MakeVfConst(params.sigmaLuminance, params.sigmaNormal, params.sigmaPlane, params.historyLength);
+	const uint32_t n = (uint32_t)pixels;   // (1 .. 2^31 - 1: the ABI checked)
+	const dim3 linear((n + RL_BLOCK - 1u) / RL_BLOCK), tiles(((W + 15u) / 16u) * ((H + 15u) / 16u));   // (at most 2^23 + 1 and 2^27 workgroups)
 	if (sync && !BeginSync(R, st)) return false;
-	hipLaunchKernelGGL(k_temporal, dim3(blocks), dim3(RL_BLOCK), 0, st, T);
+	hipLaunchKernelGGL(k_vf_pack, linear, dim3(RL_BLOCK), 0, st, (const float4*)dev[0], (const float4*)dev[1], (const float*)dev[3], n, R.vfGuides.ptr, R.vfValues[0].ptr);
 	HIP_OK(hipGetLastError());
+	hipLaunchKernelGGL(k_vf_variance, tiles, dim3(RL_BLOCK), 0, st, (const VfGuide*)R.vfGuides.ptr, (const float*)dev[2], (const float*)dev[4], W, H, c, R.vfValues[0].ptr);
+	HIP_OK(hipGetLastError());
+	int cur = 0;
+	for (int i = 0; i < params.iterations; ++i, cur ^= 1) {
+		if (i + 1 < params.iterations)
+			hipLaunchKernelGGL(k_vf_iter<false>, tiles, dim3(RL_BLOCK), 0, st, (const VfValue*)R.vfValues[cur].ptr, (const VfGuide*)R.vfGuides.ptr, W, H, (int32_t)(1 << i), c,
+			                   R.vfValues[cur ^ 1].ptr, (float4*)nullptr, (float*)nullptr);
+		else
+			hipLaunchKernelGGL(k_vf_iter<true>, tiles, dim3(RL_BLOCK), 0, st, (const VfValue*)R.vfValues[cur].ptr, (const VfGuide*)R.vfGuides.ptr, W, H, (int32_t)(1 << i), c,
+			                   (VfValue*)nullptr, (float4*)out[0].dev, (float*)out[1].dev);
+		HIP_OK(hipGetLastError());
+	}
+	HIP_OK(hipEventRecord(R.vfEv, st));
+	R.vfEvUsed = true;
 	if (!sync) return true;
 	const bool ok = FinishSync(R, st, { CopyBack(out[0], hostMem), CopyBack(out[1], hostMem) }, t0, stats);
-	if (ok) stats.pixels = pixels;
+	if (ok) { stats.pixels = pixels; stats.traceLaunches = 2u + (uint32_t)params.iterations; }
 	return ok;
 }
 

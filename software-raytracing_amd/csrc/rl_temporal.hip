@@ -5,6 +5,9 @@
 // bytes stored.  The lanes are the G-buffer's: lane p of a wave is pixel (p & 7, p >> 3) of an 8 x 8 cell, so every plane is read and written as rows of
 // eight 16-byte records, and a wave's taps fall into the 9 x 9 neighbourhood of where its cell was -- the history is read from memory about once.  One
 // cell per wave, a grid-stride loop over the cells; no LDS, no atomics.
+//
+// k_temporal_moments (RaylibAMD_TemporalAccumulateMoments, statements S1 and S2) is the same walk with the moments' planes beside it: a tap reads 8 bytes
+// more, a pixel stores 8 bytes more.  It is a kernel of its own, so k_temporal's code is what it was (profiles/variance_filter_isa_equivalence.log).
 #include "rl_kernels.h"
 #include "rl_temporal.h"
 
@@ -21,6 +24,11 @@ struct DeviceTaps {
 		t.r = c.x; t.g = c.y; t.b = c.z; t.t = h.x; t.prim = __float_as_int(h.y); t.length = length[q];
 		return t;
 	}
+};
+// ... with the moments' plane beside the other three
+struct DeviceTapsMoments : DeviceTaps {
+	const float2* __restrict__ moments;
+	__device__ __forceinline__ void Moments(size_t q, float m[2]) const { const float2 v = moments[q]; m[0] = v.x; m[1] = v.y; }
 };
 } // namespace
 
@@ -40,6 +48,26 @@ k_temporal(const DTemporal T)
 		TemporalPixel(T.width, T.height, rgb, __float_as_int(h.y), m.x, m.y, m.z, __float_as_uint(m.w), T.depthTolerance, T.maxLength, taps, out, len);
 		T.outColour[p] = make_float4(out[0], out[1], out[2], 1.0f);
 		T.outLength[p] = len;
+	}
+}
+
+__global__ void __launch_bounds__(RL_BLOCK)
+k_temporal_moments(const DTemporal T, const float2* __restrict__ histMoments, float2* __restrict__ outMoments)
+{
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t wavesPerBlock = RL_BLOCK / 64u;
+	const DeviceTapsMoments taps = { { T.histColour, T.histHit, T.histLength }, histMoments };
+	for (uint32_t cell = blockIdx.x * wavesPerBlock + (threadIdx.x >> 6); cell < T.numCells; cell += gridDim.x * wavesPerBlock) {
+		const uint32_t x = (cell % T.cellsX) * 8u + (lane & 7u), y = (cell / T.cellsX) * 8u + (lane >> 3);
+		if (x >= T.width || y >= T.height) continue;
+		const size_t p = (size_t)y * T.width + x;
+		const float4 c = T.colour[p], h = T.hit[p], m = T.motion[p];
+		const float rgb[3] = { c.x, c.y, c.z };
+		float out[3], len, mom[2];
+		TemporalPixelM<true>(T.width, T.height, rgb, __float_as_int(h.y), m.x, m.y, m.z, __float_as_uint(m.w), T.depthTolerance, T.maxLength, taps, out, len, mom);
+		T.outColour[p] = make_float4(out[0], out[1], out[2], 1.0f);
+		T.outLength[p] = len;
+		outMoments[p] = make_float2(mom[0], mom[1]);
 	}
 }
 

@@ -367,6 +367,112 @@ def temporal_accumulate_device(lib, colour, hit, motion, history=None, depth_tol
     return out_c, out_l
 
 
+class TemporalMomentsFrame(C.Structure):
+    """include/raylib_amd.h RaylibAMDTemporalMomentsFrame: a TemporalFrame and the previous call's moments plane."""
+    _fields_ = [("colour", C.c_void_p), ("hit", C.c_void_p), ("length", C.c_void_p), ("moments", C.c_void_p)]
+
+
+class VarianceFilterParams(C.Structure):
+    """include/raylib_amd.h RaylibAMDVarianceFilterParams (a null pointer: 5, 4, 0.35, 0.1, 4)."""
+    _fields_ = [("iterations", C.c_int32), ("sigmaLuminance", C.c_float), ("sigmaNormal", C.c_float), ("sigmaPlane", C.c_float), ("historyLength", C.c_float)]
+
+
+class VarianceFilterPlanes(C.Structure):
+    """include/raylib_amd.h RaylibAMDVarianceFilterPlanes: all five are required."""
+    _fields_ = [("colour", C.c_void_p), ("moments", C.c_void_p), ("length", C.c_void_p), ("hit", C.c_void_p), ("surface", C.c_void_p)]
+
+
+VARIANCE_DEFAULTS = dict(iterations=5, sigma_luminance=4.0, sigma_normal=0.35, sigma_plane=0.1, history_length=4.0)
+
+
+def temporal_accumulate_moments(lib, colour, hit, motion, history=None, depth_tolerance=0.02, max_length=32.0, host=False):
+    """RaylibAMD_TemporalAccumulateMoments on NumPy arrays (host=True: RaylibAMD_TemporalAccumulateMomentsHost, the oracle, no device): temporal_accumulate's
+    arguments with a history of (colour, hit, length, moments), moments (h, w, 2) float32.  Returns (outColour (h, w, 4), outLength (h, w), outMoments (h, w, 2)).
+    Raises RuntimeError when the library refuses the call."""
+    colour = np.ascontiguousarray(colour, np.float32)
+    h, w = colour.shape[:2]
+    hit = np.ascontiguousarray(hit, HITT_DTYPE)
+    motion = np.ascontiguousarray(motion, MOTION_DTYPE)
+    assert colour.shape == (h, w, 4) and hit.size == w * h and motion.size == w * h
+    keep = None
+    hist = None
+    if history is not None:
+        keep = (np.ascontiguousarray(history[0], np.float32), np.ascontiguousarray(history[1], HITT_DTYPE), np.ascontiguousarray(history[2], np.float32),
+                np.ascontiguousarray(history[3], np.float32))
+        assert keep[0].size == w * h * 4 and keep[1].size == w * h and keep[2].size == w * h and keep[3].size == w * h * 2
+        hist = C.byref(TemporalMomentsFrame(*[a.ctypes.data for a in keep]))
+    out_c, out_l, out_m = np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.float32), np.zeros((h, w, 2), np.float32)
+    entry = "RaylibAMD_TemporalAccumulateMomentsHost" if host else "RaylibAMD_TemporalAccumulateMoments"
+    prm = TemporalParams(float(depth_tolerance), float(max_length))
+    if getattr(lib, entry)(int(w), int(h), C.byref(prm), colour.ctypes.data, hit.ctypes.data, motion.ctypes.data, hist, out_c.ctypes.data, out_l.ctypes.data,
+                           out_m.ctypes.data) != 1:
+        raise RuntimeError(entry + " refused the call")
+    return out_c, out_l, out_m
+
+
+def temporal_accumulate_moments_device(lib, colour, hit, motion, history=None, depth_tolerance=0.02, max_length=32.0, out=None):
+    """RaylibAMD_TemporalAccumulateMomentsDevice on torch.cuda.current_stream(), as temporal_accumulate_device: history None or (colour, hit, length, moments)
+    tensors of the previous frame; out: (outColour, outLength, outMoments) tensors to write into.  Returns (outColour (h, w, 4), outLength (h, w),
+    outMoments (h, w, 2)), float32 on the device.  Raises RuntimeError when the library refuses the call."""
+    import torch
+    h, w = colour.shape[:2]
+    out_c, out_l, out_m = out if out is not None else (torch.empty((h, w, 4), dtype=torch.float32, device="cuda"), torch.empty((h, w), dtype=torch.float32, device="cuda"),
+                                                       torch.empty((h, w, 2), dtype=torch.float32, device="cuda"))
+    hist = None if history is None else C.byref(TemporalMomentsFrame(*[t.data_ptr() for t in history]))
+    prm = TemporalParams(float(depth_tolerance), float(max_length))
+    if lib.RaylibAMD_TemporalAccumulateMomentsDevice(int(w), int(h), C.byref(prm), colour.data_ptr(), hit.data_ptr(), motion.data_ptr(), hist, out_c.data_ptr(), out_l.data_ptr(),
+                                                     out_m.data_ptr(), _ordered(torch.cuda.current_stream())) != 1:
+        raise RuntimeError("RaylibAMD_TemporalAccumulateMomentsDevice refused the call")
+    return out_c, out_l, out_m
+
+
+def _variance_params(params):
+    """None (the library's defaults: a null pointer) or a dict / VarianceFilterParams -> what the call is handed."""
+    if params is None:
+        return None
+    if isinstance(params, VarianceFilterParams):
+        return C.byref(params)
+    p = dict(VARIANCE_DEFAULTS, **params)
+    return C.byref(VarianceFilterParams(int(p["iterations"]), float(p["sigma_luminance"]), float(p["sigma_normal"]), float(p["sigma_plane"]), float(p["history_length"])))
+
+
+def filter_variance(lib, colour, moments, length, hit, surface, params=None, variance=True, host=False):
+    """RaylibAMD_FilterVariance on NumPy arrays (host=True: RaylibAMD_FilterVarianceHost, the oracle, no device): colour (h, w, 4), moments (h, w, 2) and length
+    (h, w) float32 as the accumulation leaves them, hit (h, w) HITT_DTYPE and surface (h, w) SURFACE_DTYPE as the G-buffer does.  params: None for the library's
+    defaults, or a dict with any of VARIANCE_DEFAULTS' keys.  Returns (outColour (h, w, 4), outVariance (h, w) or None when variance is False).  Raises
+    RuntimeError when the library refuses the call."""
+    colour = np.ascontiguousarray(colour, np.float32)
+    h, w = colour.shape[:2]
+    keep = (colour, np.ascontiguousarray(moments, np.float32), np.ascontiguousarray(length, np.float32), np.ascontiguousarray(hit, HITT_DTYPE),
+            np.ascontiguousarray(surface, SURFACE_DTYPE))
+    assert colour.shape == (h, w, 4) and keep[1].size == w * h * 2 and keep[2].size == w * h and keep[3].size == w * h and keep[4].size == w * h
+    planes = VarianceFilterPlanes(*[a.ctypes.data for a in keep])
+    out_c = np.zeros((h, w, 4), np.float32)
+    out_v = np.zeros((h, w), np.float32) if variance else None
+    entry = "RaylibAMD_FilterVarianceHost" if host else "RaylibAMD_FilterVariance"
+    if getattr(lib, entry)(int(w), int(h), _variance_params(params), C.byref(planes), out_c.ctypes.data, None if out_v is None else out_v.ctypes.data) != 1:
+        raise RuntimeError(entry + " refused the call")
+    return out_c, out_v
+
+
+def filter_variance_device(lib, colour, moments, length, hit, surface, params=None, variance=True, out=None):
+    """RaylibAMD_FilterVarianceDevice on torch.cuda.current_stream(), as temporal_accumulate_device: float32 tensors colour (h, w, 4), moments (h, w, 2), length
+    (h, w), and hit (h, w, 4), surface (h, w, 11) int32 words as gbuffer_device returns them; all contiguous, on the device.  out: (outColour, outVariance or
+    None) tensors to write into.  Returns (outColour, outVariance or None)."""
+    import torch
+    h, w = colour.shape[:2]
+    if out is not None:
+        out_c, out_v = out
+    else:
+        out_c = torch.empty((h, w, 4), dtype=torch.float32, device="cuda")
+        out_v = torch.empty((h, w), dtype=torch.float32, device="cuda") if variance else None
+    planes = VarianceFilterPlanes(colour.data_ptr(), moments.data_ptr(), length.data_ptr(), hit.data_ptr(), surface.data_ptr())
+    if lib.RaylibAMD_FilterVarianceDevice(int(w), int(h), _variance_params(params), C.byref(planes), out_c.data_ptr(), None if out_v is None else out_v.data_ptr(),
+                                          _ordered(torch.cuda.current_stream())) != 1:
+        raise RuntimeError("RaylibAMD_FilterVarianceDevice refused the call")
+    return out_c, out_v
+
+
 MAX_HITS = 16                                       # RAYLIB_AMD_MAX_HITS
 
 
@@ -1117,6 +1223,12 @@ _EXPORTS = {
     "RaylibAMD_TemporalAccumulate": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(TemporalParams)] + [C.c_void_p] * 3 + [C.POINTER(TemporalFrame)] + [C.c_void_p] * 2),
     "RaylibAMD_TemporalAccumulateDevice": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(TemporalParams)] + [C.c_void_p] * 3 + [C.POINTER(TemporalFrame)] + [C.c_void_p] * 3),
     "RaylibAMD_TemporalAccumulateHost": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(TemporalParams)] + [C.c_void_p] * 3 + [C.POINTER(TemporalFrame)] + [C.c_void_p] * 2),
+    "RaylibAMD_TemporalAccumulateMoments": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(TemporalParams)] + [C.c_void_p] * 3 + [C.POINTER(TemporalMomentsFrame)] + [C.c_void_p] * 3),
+    "RaylibAMD_TemporalAccumulateMomentsDevice": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(TemporalParams)] + [C.c_void_p] * 3 + [C.POINTER(TemporalMomentsFrame)] + [C.c_void_p] * 4),
+    "RaylibAMD_TemporalAccumulateMomentsHost": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(TemporalParams)] + [C.c_void_p] * 3 + [C.POINTER(TemporalMomentsFrame)] + [C.c_void_p] * 3),
+    "RaylibAMD_FilterVariance": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(VarianceFilterParams), C.POINTER(VarianceFilterPlanes)] + [C.c_void_p] * 2),
+    "RaylibAMD_FilterVarianceDevice": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(VarianceFilterParams), C.POINTER(VarianceFilterPlanes)] + [C.c_void_p] * 3),
+    "RaylibAMD_FilterVarianceHost": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(VarianceFilterParams), C.POINTER(VarianceFilterPlanes)] + [C.c_void_p] * 2),
     "RaylibAMD_TraceRadiance": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(PathRay), C.c_int32, C.POINTER(C.c_float)]),
     "RaylibAMD_TraceRadianceDevice": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(PathRay), C.c_int32, C.POINTER(C.c_float), C.c_void_p]),
     "RaylibAMD_PlanRadiance": (C.c_int32, [C.c_void_p, C.POINTER(RadianceParams), C.POINTER(QueryPlan)]),
@@ -1493,6 +1605,22 @@ class SceneSession:
     def temporal_accumulate_device(self, colour, hit, motion, history=None, depth_tolerance=0.02, max_length=32.0, out=None):
         """RaylibAMD_TemporalAccumulateDevice on torch's current stream (temporal_accumulate_device above)."""
         return temporal_accumulate_device(self.lib, colour, hit, motion, history, depth_tolerance, max_length, out)
+
+    def temporal_accumulate_moments(self, colour, hit, motion, history=None, depth_tolerance=0.02, max_length=32.0, host=False):
+        """RaylibAMD_TemporalAccumulateMoments / ...Host on NumPy arrays (temporal_accumulate_moments above; the call needs no scene)."""
+        return temporal_accumulate_moments(self.lib, colour, hit, motion, history, depth_tolerance, max_length, host)
+
+    def temporal_accumulate_moments_device(self, colour, hit, motion, history=None, depth_tolerance=0.02, max_length=32.0, out=None):
+        """RaylibAMD_TemporalAccumulateMomentsDevice on torch's current stream (temporal_accumulate_moments_device above)."""
+        return temporal_accumulate_moments_device(self.lib, colour, hit, motion, history, depth_tolerance, max_length, out)
+
+    def filter_variance(self, colour, moments, length, hit, surface, params=None, variance=True, host=False):
+        """RaylibAMD_FilterVariance / ...Host on NumPy arrays (filter_variance above; the call needs no scene)."""
+        return filter_variance(self.lib, colour, moments, length, hit, surface, params, variance, host)
+
+    def filter_variance_device(self, colour, moments, length, hit, surface, params=None, variance=True, out=None):
+        """RaylibAMD_FilterVarianceDevice on torch's current stream (filter_variance_device above)."""
+        return filter_variance_device(self.lib, colour, moments, length, hit, surface, params, variance, out)
 
     def render_cells(self, w, h, spp, rank, world, max_path=5, tmin=1e-4, mode=RENDERMODE_DEFAULT):
         """What rank `rank` of `world` renders: its cells back to back, (n_cells*64, 4) float32."""
