@@ -589,7 +589,7 @@ RAYLIB_API int32_t RaylibAMD_PlanDistanceField(SceneHandle scene, const RaylibAM
  * holds spheres or cubes; a BVH deeper than 64 levels; no device (the plain and the device entry; the host entry needs none); on the device entry a pointer
  * off rank 0's device, q not 16-byte aligned, out or outCount not 4-byte aligned.  n == 0 returns 1.
  * Still out: spheres and cubes; more than RAYLIB_AMD_MAX_OVERLAPS indices per query (the count is complete all the same); an 8-wide walk; query primitives
- * other than triangles.  The contact geometry of the listed pairs (the intersection segment) is the next section's, RaylibAMD_OverlapContacts; penetration depth
+ * other than triangles and oriented boxes (RaylibAMD_OverlapBoxes, below).  The contact geometry of the listed pairs (the intersection segment) is the next section's, RaylibAMD_OverlapContacts; penetration depth
  * is not a property of a triangle pair in a soup and stays out.
  * Checked against a loop over every triangle and an edge-piercing reference in double precision: tests/test_overlap_host.py, tests/test_gpu_overlap.py. */
 typedef struct RaylibAMDOverlapQuery {      /* 48 bytes, three 16-byte loads; 16-byte aligned on the device entry */
@@ -672,6 +672,62 @@ RAYLIB_API int32_t RaylibAMD_OverlapContactsHost(SceneHandle scene, uint32_t fla
         RaylibAMDContact* outContact, uint32_t* outCount);
 /* RaylibAMD_PlanOverlap's answer for RAYLIB_AMD_OVERLAP_LIST: the same tree and stack; the instance walked is the contacts one (k_overlap_contacts). */
 RAYLIB_API int32_t RaylibAMD_PlanOverlapContacts(SceneHandle scene, RaylibAMDQueryPlan* out);
+
+/* ---- oriented-box range queries: any, list and mark -----------------------------------------------
+ * Which triangles of the scene lie in this box -- region selection and streaming, conservative surface voxelisation (one box per voxel, ANY), trigger
+ * volumes, culling against a portal or a cell, and the broad phase in front of anything that is not a triangle, a point or a sphere.  The first of the query
+ * primitives other than triangles that the overlap section left out.  The result equals a loop over every triangle bit for bit, with no slack anywhere, on
+ * every tree, fresh or refitted (csrc/rl_box.h holds the statements for the host oracle and the kernel alike; csrc/rl_k_overlap_box.inl is the walk).
+ * Everything is float, single IEEE operations without FMA.  dot, cross, and the least and greatest of three values are the overlap section's (O).
+ * For query box Q and scene triangle T = (v0, v1, v2), in RaylibAMD_SceneExportTriangles order:
+ *   B1. Taking part.  A query takes part when all 15 of its floats are finite and every half >= 0 (-0.0 is 0).  The axes are used as given, neither normalised
+ *        nor checked for orthogonality; identity axes make the box axis-aligned, and then every frame coordinate of B3 is exactly v - center.  A query that
+ *        does not take part gets 0 (ANY), a row of -1 with count 0 (LIST), and sets no bit (MARK), without a walk.
+ *   B2. Enclosing box.  e.x = (|axis0.dir.x| * half0 + |axis1.dir.x| * half1) + |axis2.dir.x| * half2, and e.y, e.z likewise.  loQ = center - e,
+ *        hiQ = center + e.  Infinite values are fine; no NaN can arise.  T's own box is O2's.  T is not accepted unless the two boxes meet under O2's closed
+ *        comparison.  In exact arithmetic, with orthonormal axes, this removes nothing the next statements accept; at rounding level it may.  This is W5's
+ *        trade: the verdict is defined so that the tree cull is exact without a slack factor.
+ *   B3. Box frame.  d_k = v_k - center; p_k = (dot(axis0.dir, d_k), dot(axis1.dir, d_k), dot(axis2.dir, d_k)); h = (half0, half1, half2).
+ *   B4. Thirteen axes, in this order.
+ *        The three faces.  For i = 0..2, with the least and greatest of (p0[i], p1[i], p2[i]): the face separates when least > h[i] || greatest < -h[i].
+ *        The triangle's plane.  e0 = p1 - p0, e1 = p2 - p1, e2 = p0 - p2.  n = cross(e0, e1).  r = (h[0]*|n.x| + h[1]*|n.y|) + h[2]*|n.z| and
+ *        s = dot(n, p0).  The plane separates when s > r || s < -r.
+ *        The nine edge axes, i outer (box axis) and j inner (edge).  (u, w) is (1, 2), (2, 0), (0, 1) for i = 0, 1, 2.
+ *        proj(p) = p[w]*e_j[u] - p[u]*e_j[w], taken for p0, p1, p2.  r = h[u]*|e_j[w]| + h[w]*|e_j[u]|.  The axis separates when
+ *        least > r || greatest < -r.
+ *        T is accepted when no axis separates.  Touching counts as meeting.  A NaN (overflow) compares false and separates nothing, as in O4.  A zero half
+ *        extent is a rectangle, a segment or a point, and needs no special case.
+ *   B5. Result.  ANY: 1 exactly when some T is accepted.  LIST: RAYLIB_AMD_OVERLAP_LIST's contract -- the accepted triangles' export indices ascending, the
+ *        first min(maxHits, count) of them, with -1 behind them; outCount[i] is complete however small maxHits is.  MARK: one mask for the whole call,
+ *        (numTriangles + 31) / 32 words; bit k % 32 of word k / 32 is set exactly when some query accepts triangle k.  The call writes the whole mask: it
+ *        clears it first, on the call's stream, then ORs into it; bits at and above numTriangles are 0; n == 0 leaves it all zero.  An OR has no order, so the
+ *        mask is the same however the call is cut.
+ *   B6. Independence.  O6's paragraph, with loQ / hiQ of B2 as the box that drives the walk: a node whose box does not meet B2's box holds no triangle whose
+ *        own box does.  The result is the same on the binary and the grid-4 tree, fresh or refitted, for every cut into waves.
+ * Refusals (0, nothing written -- for MARK that includes the clear): q or out null with n > 0; n < 0; an unknown kind; LIST with maxHits outside
+ * 1 .. RAYLIB_AMD_MAX_OVERLAPS or n * maxHits above 2^31 - 1; ANY or MARK with a non-null outCount (maxHits is not read); a scene that is not finalized; a
+ * scene that holds spheres or cubes; a BVH deeper than 64 levels; no device (the plain and the device entry; the host entry needs none); on the device entry a
+ * pointer off rank 0's device, q not 16-byte aligned, out or outCount not 4-byte aligned.  n == 0 returns 1.
+ * Still out: spheres and cubes as targets; more than RAYLIB_AMD_MAX_OVERLAPS indices per query (MARK is the uncapped form); the 8-wide tree; capsules and
+ * frusta as query volumes; per-query masks; clipping the accepted triangles to the box.
+ * Checked against a NumPy restatement byte for byte and a 13-axis test in double precision: tests/test_box_host.py, tests/test_gpu_boxes.py. */
+typedef struct RaylibAMDBoxQuery {                   /* 64 bytes, four 16-byte loads; 16-byte aligned on the device entry */
+	float center[3]; uint32_t reserved;              /* reserved is not read */
+	struct { float dir[3]; float half; } axis[3];    /* the box's three axes, each with its half extent */
+} RaylibAMDBoxQuery;
+#define RAYLIB_AMD_BOX_ANY  0   /* out: uint32_t per query, 1 when some scene triangle is accepted (may stop at the first) */
+#define RAYLIB_AMD_BOX_LIST 1   /* out: maxHits int32_t per query (1 .. RAYLIB_AMD_MAX_OVERLAPS), outCount (may be NULL): uint32_t per query */
+#define RAYLIB_AMD_BOX_MARK 2   /* out: (numTriangles + 31) / 32 uint32_t for the whole call: bit k % 32 of word k / 32 is set when some query accepts triangle k */
+/* n queries from host memory, results to host memory; synchronous, on the device; stats as RaylibAMD_OverlapTriangles. */
+RAYLIB_API int32_t RaylibAMD_OverlapBoxes(SceneHandle scene, int32_t kind, const RaylibAMDBoxQuery* q, int32_t n, int32_t maxHits, void* out, uint32_t* outCount);
+/* The same on device pointers, with the stream, stats, move-ordering and multi-rank rules of RaylibAMD_OverlapTrianglesDevice. */
+RAYLIB_API int32_t RaylibAMD_OverlapBoxesDevice(SceneHandle scene, int32_t kind, const RaylibAMDBoxQuery* q, int32_t n, int32_t maxHits, void* out, uint32_t* outCount,
+        void* stream);
+/* The oracle: statements B1 to B5 over every triangle, no tree, no device.  After a move it refreshes the host's stale triangles first. */
+RAYLIB_API int32_t RaylibAMD_OverlapBoxesHost(SceneHandle scene, int32_t kind, const RaylibAMDBoxQuery* q, int32_t n, int32_t maxHits, void* out, uint32_t* outCount);
+/* RaylibAMD_PlanOverlap's answer (csrc/rl_plan.cc PlanOverlapBoxes): the same trees, the same stacks, the same RAYLIB_QUERY_TREE knob.  `early` is 1 for ANY
+ * only.  Returns as RaylibAMD_PlanOverlap; an unknown kind is 0. */
+RAYLIB_API int32_t RaylibAMD_PlanOverlapBoxes(SceneHandle scene, int32_t kind, RaylibAMDQueryPlan* out);
 
 /* ---- swept-sphere queries: the first time of impact ------------------------------------------------
  * The continuous member of the collision family: a sphere of radius r moves from origin to origin + delta, and the call says when, where and on which

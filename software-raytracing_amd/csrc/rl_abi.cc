@@ -1350,6 +1350,46 @@ int32_t RaylibAMD_OverlapContactsHost(SceneHandle sh, uint32_t flags, const Rayl
 }
 int32_t RaylibAMD_PlanOverlapContacts(SceneHandle sh, RaylibAMDQueryPlan* out) { return RaylibAMD_PlanOverlap(sh, RAYLIB_AMD_OVERLAP_LIST, out); }
 
+// RaylibAMD_OverlapBoxes / RaylibAMD_OverlapBoxesDevice / RaylibAMD_OverlapBoxesHost / RaylibAMD_PlanOverlapBoxes (statements B1 to B6): the refusals every entry shares
+static_assert(sizeof(RaylibAMDBoxQuery) == 64, "box records");
+static bool BoxKindValid(int32_t kind) { return kind == RAYLIB_AMD_BOX_ANY || kind == RAYLIB_AMD_BOX_LIST || kind == RAYLIB_AMD_BOX_MARK; }
+static bool OverlapBoxesArgsValid(const char* who, const Scene* s, int32_t kind, const void* q, int32_t n, int32_t maxHits, const void* out, const uint32_t* outCount)
+{
+	if (!BoxKindValid(kind)) { Log("%s: unknown box kind %d", who, kind); return false; }
+	const bool list = kind == RAYLIB_AMD_BOX_LIST;
+	if (!list && outCount) { Log("%s: outCount belongs to RAYLIB_AMD_BOX_LIST", who); return false; }
+	const QueryRows rows = { maxHits, RAYLIB_AMD_MAX_OVERLAPS, "queries", "indices", "words" };
+	return TriangleQueryArgsValid(who, "box queries", s, q, n, out, list ? &rows : nullptr);
+}
+static int32_t OverlapBoxesInternal(const char* who, SceneHandle sh, int32_t kind, const RaylibAMDBoxQuery* q, int32_t n, int32_t maxHits, void* out, uint32_t* outCount, bool hostMem,
+                                    void* stream)
+{
+	Scene* s = (Scene*)sh;
+	if (!OverlapBoxesArgsValid(who, s, kind, q, n, maxHits, out, outCount)) return 0;
+	return RunOnDevice(stream, [&](RaylibAMDStats& stats) { return DeviceOverlapBoxes(*s, kind, q, n, maxHits, out, outCount, hostMem, stream, stats); });
+}
+int32_t RaylibAMD_OverlapBoxes(SceneHandle sh, int32_t kind, const RaylibAMDBoxQuery* q, int32_t n, int32_t maxHits, void* out, uint32_t* outCount)
+{
+	return OverlapBoxesInternal("RaylibAMD_OverlapBoxes", sh, kind, q, n, maxHits, out, outCount, true, nullptr);
+}
+int32_t RaylibAMD_OverlapBoxesDevice(SceneHandle sh, int32_t kind, const RaylibAMDBoxQuery* q, int32_t n, int32_t maxHits, void* out, uint32_t* outCount, void* stream)
+{
+	return OverlapBoxesInternal("RaylibAMD_OverlapBoxesDevice", sh, kind, q, n, maxHits, out, outCount, false, stream);
+}
+int32_t RaylibAMD_OverlapBoxesHost(SceneHandle sh, int32_t kind, const RaylibAMDBoxQuery* q, int32_t n, int32_t maxHits, void* out, uint32_t* outCount)
+{
+	Scene* s = (Scene*)sh;
+	if (!OverlapBoxesArgsValid("RaylibAMD_OverlapBoxesHost", s, kind, q, n, maxHits, out, outCount)) return 0;
+	return RunOnHost(s, [&] { OverlapBoxesHost(*s, kind, q, n, maxHits, out, outCount); });
+}
+int32_t RaylibAMD_PlanOverlapBoxes(SceneHandle sh, int32_t kind, RaylibAMDQueryPlan* out)
+{
+	Scene* s = (Scene*)sh;
+	if (!s || !s->finalized || !out || !BoxKindValid(kind) || !s->spheres.empty() || !s->cubes.empty()) return 0;
+	const QueryPlan p = PlanOverlapBoxes(*s, kind, ReadRenderKnobs());
+	return ExportPlan(p, 0, p.early, out);
+}
+
 // RaylibAMD_BakeDistanceField / RaylibAMD_BakeDistanceFieldDevice / RaylibAMD_BakeDistanceFieldHost / RaylibAMD_PlanDistanceField (statements V1 to V7): the
 // refusals every entry shares; `grid` is the caller's parameters with maxDist's -0.0 read as +0.0
 static bool DistanceFieldArgsValid(const char* who, const Scene* s, const RaylibAMDDistanceFieldParams* p, const void* outDist, bool needOut, RaylibAMDDistanceFieldParams& grid)

@@ -1,9 +1,10 @@
 // The point walk of k_nearest, k_nearest_all and k_sdf_dist -- a walk that the distance from a point to a box drives, not a ray -- written once, with the pieces
 // that the box-driven kernels share: the isect record's vertices, the grid node's decode, the packed distance of the point walk's stack, the chunk claim and
-// the counter fold.  rl_nearest.hip, rl_overlap.hip, rl_sdf.hip and rl_sweep.hip include this file; no other unit does (the ray kernels keep their own claim and fold).
+// the counter fold.  rl_nearest.hip, rl_overlap.hip, rl_overlap_box.hip, rl_sdf.hip and rl_sweep.hip include this file; no other unit does (the ray kernels keep their own claim and fold).
 // k_sweep takes the pieces from here and keeps its walk -- the point walk's shape with a time bound in the distance's place -- in rl_k_sweep.inl.
 // k_overlap and k_overlap_contacts take the vertices and the claim from here and keep their box walk, its grid decode and their fold in rl_k_overlap.inl:
 // on the shared walk the 4-wide ANY instance ran 1 % longer than the parent's in every job (profiles/box_walk_ab.log).
+// k_overlap_box keeps that walk's text a second time (rl_k_overlap_box.inl) and takes the vertices, the claim, the grid node's decode and the fold from here.
 //
 // The walk: one point per lane, the stack is this lane's column of an LDS array (entry k at stk[k * RL_BLOCK]), the root is an inner node, a leaf holds <= 4
 // triangles stored back to back.  It pushes at most (children - 1) references per level, as the ray walks do, so the planner's bounds hold: the binary

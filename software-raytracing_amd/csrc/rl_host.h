@@ -306,6 +306,9 @@ bool DeviceBakeDistanceField(Scene& scene, const RaylibAMDDistanceFieldParams& g
 // contacts: RaylibAMD_OverlapContacts (Device) -- kind is LIST and outContact takes n * maxHits 32-byte records (non-null when n > 0).
 bool DeviceOverlapTriangles(Scene& scene, int32_t kind, uint32_t flags, const void* queries, int32_t n, int32_t maxHits, void* out, uint32_t* outCount, bool hostMem, void* stream,
                             RaylibAMDStats& stats, void* outContact = nullptr, bool contacts = false);
+// RaylibAMD_OverlapBoxes (hostMem) and RaylibAMD_OverlapBoxesDevice, as DeviceOverlapTriangles; kind and (for LIST) maxHits are valid, outCount is null for ANY
+// and MARK, n * maxHits fits 2^31 - 1: the ABI checked.  MARK: out is the call's mask, (triangles + 31) / 32 words, written whole even when n is 0.
+bool DeviceOverlapBoxes(Scene& scene, int32_t kind, const void* queries, int32_t n, int32_t maxHits, void* out, uint32_t* outCount, bool hostMem, void* stream, RaylibAMDStats& stats);
 // RaylibAMD_TraceRadiance (hostMem) and RaylibAMD_TraceRadianceDevice, as DeviceTraceRays; prm is valid (timeMin <= timeMax cover every ray's time and the
 // scene's boxes), seed is the library's: the ABI checked.
 // The path stack's budget: the grid is cut until its stack (32 bytes per bounce and resident lane) fits, and a maxPathLength at which one workgroup of 256

@@ -25,7 +25,9 @@
 //                        path into a box grown by the radius) and the largest narrow phase of the family; its walk is its own text, so every other unit stays the code it is
 //   rl_overlap.hip       k_overlap (RaylibAMD_OverlapTriangles): a walk of its own again (box against box, no ray, no distance) with a per-lane index list; apart for
 //                        the same reason
-//   rl_sdf.hip           k_sdf_rows, k_sdf_parity, k_sdf_dist (RaylibAMD_BakeDistanceField): k_query_all's counting walks written again and k_nearest's closest walk (PointWalk) on
+//   rl_overlap_box.hip   k_overlap_box (RaylibAMD_OverlapBoxes): k_overlap's walk written again, driven by the box that encloses an oriented query box, with a
+//                        box-against-triangle leaf test and a bit mask as a third output kind; apart so that rl_overlap.hip stays the code it is
+//   rl_sdf.hip          k_sdf_rows, k_sdf_parity, k_sdf_dist (RaylibAMD_BakeDistanceField): k_query_all's counting walks written again and k_nearest's closest walk (PointWalk) on
 //                        generated rays and points, with a bit volume between them; apart for the same reason
 //   rl_radiance.hip      k_radiance (RaylibAMD_TraceRadiance): the same reason, towards the render and the query kernels alike
 //   rl_gather.hip        k_gather (RaylibAMD_Gather: rl_k_radiance.inl's twin, the generator instances of its loop) and k_gather_resolve: beside k_radiance they would be
@@ -334,6 +336,20 @@ template <int TREE, int STACK> __global__ void __launch_bounds__(RL_BLOCK) k_ove
 #define RL_OVERLAP_CONTACTS_INSTANCES(X) X(2, 32) X(2, 64) X(4, 32) X(4, 64)
 #define RL_K_OVERLAP_CONTACTS(a, b) template __global__ void k_overlap_contacts<a, b>(RL_OVERLAP_CONTACTS_ARGS);
 RL_OVERLAP_CONTACTS_INSTANCES(extern RL_K_OVERLAP_CONTACTS)
+
+// ---------------------------------------------------------------------------
+// The oriented-box range queries (RaylibAMD_OverlapBoxes; rl_k_overlap_box.inl, arithmetic of rl_box.h)
+enum { RL_BK_ANY = 0, RL_BK_LIST = 1, RL_BK_MARK = 2 };   // RAYLIB_AMD_BOX_*
+// TREE, STACK: as k_overlap's.  queries: n records of four float4 (the centre and a word that is not read; each axis with its half extent).  maxHits:
+// 1 .. RL_MAX_OVERLAPS for LIST, and the launch then carries maxHits * RL_BLOCK words of dynamic LDS (the lanes' lists); not read for ANY and MARK.  out: uint32_t
+// per query (ANY), a row of maxHits int32_t (LIST), or the call's mask of (numTriangles + 31) / 32 words, cleared before the launch (MARK).  outCount: n words or
+// null (LIST).  slotIndex: triangle slot -> export index (null: the identity); LIST and MARK read it.  counters: CNT_RAYS (queries), CNT_NODES, CNT_TRIS sums, or null.
+#define RL_OVERLAP_BOX_ARGS const DSceneView, const float4* __restrict__, uint32_t, uint32_t, void* __restrict__, uint32_t* __restrict__, const int32_t* __restrict__, unsigned int* __restrict__, unsigned long long* __restrict__
+template <int TREE, int KIND, int STACK> __global__ void __launch_bounds__(RL_BLOCK) k_overlap_box(RL_OVERLAP_BOX_ARGS);
+// The instances rl_rt_rays.hip OverlapBoxKernelOfKind selects from: (TREE, KIND, STACK)
+#define RL_OVERLAP_BOX_INSTANCES(X) RL_OVERLAP_INSTANCES_K(X, 0) RL_OVERLAP_INSTANCES_K(X, 1) RL_OVERLAP_INSTANCES_K(X, 2)
+#define RL_K_OVERLAP_BOX(a, b, c) template __global__ void k_overlap_box<a, b, c>(RL_OVERLAP_BOX_ARGS);
+RL_OVERLAP_BOX_INSTANCES(extern RL_K_OVERLAP_BOX)
 
 // ---------------------------------------------------------------------------
 // Distance-field bakes (RaylibAMD_BakeDistanceField; rl_k_sdf.inl, statements V1 to V7 of include/raylib_amd.h)

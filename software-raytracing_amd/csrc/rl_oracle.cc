@@ -6,6 +6,7 @@
 #include "rl_sdf.h"
 #include "rl_overlap.h"
 #include "rl_contact.h"
+#include "rl_box.h"
 #include "rl_motion.h"
 #include "rl_temporal.h"
 #include "rl_variance.h"
@@ -214,6 +215,37 @@ void OverlapContactsHost(const Scene& s, uint32_t flags, const RaylibAMDOverlapQ
 		});
 		for (uint32_t e = count; e < (uint32_t)maxHits; ++e) { row[e] = -1; memset(&rec[e], 0, sizeof(rec[e])); }
 		if (outCount) outCount[i] = count;
+	}
+}
+
+// Statements B1 to B5 (rl_box.h, the kernel's own source) for every query box over every triangle in export order
+void OverlapBoxesHost(const Scene& s, int32_t kind, const RaylibAMDBoxQuery* q, int32_t n, int32_t maxHits, void* out, uint32_t* outCount)
+{
+	const bool list = kind == RAYLIB_AMD_BOX_LIST, mark = kind == RAYLIB_AMD_BOX_MARK;
+	if (mark && out) memset(out, 0, (s.triangles.size() + 31u) / 32u * sizeof(uint32_t));
+	for (int32_t i = 0; i < n; ++i) {
+		BoxQ Q;
+		for (int a = 0; a < 3; ++a) {
+			Q.c[a] = q[i].center[a]; Q.h[a] = q[i].axis[a].half;
+			for (int k = 0; k < 3; ++k) Q.a[a][k] = q[i].axis[a].dir[k];
+		}
+		int32_t* row = list ? (int32_t*)out + (size_t)i * (size_t)maxHits : nullptr;
+		uint32_t count = 0;
+		if (BoxTakesPart(Q)) {
+			BoxEnclosing(Q);
+			for (size_t k = 0; k < s.triangles.size(); ++k) {
+				const HostTriangle& t = s.triangles[k];
+				if (!BoxAccepts(Q, &t.v0.x, &t.v1.x, &t.v2.x)) continue;
+				if (list && count < (uint32_t)maxHits) row[count] = (int32_t)k;
+				if (mark) ((uint32_t*)out)[k >> 5] |= 1u << (k & 31u);
+				++count;
+				if (!list && !mark) break;   // (ANY stops at the first)
+			}
+		}
+		if (list) {
+			for (uint32_t e = count; e < (uint32_t)maxHits; ++e) row[e] = -1;
+			if (outCount) outCount[i] = count;
+		} else if (!mark) ((uint32_t*)out)[i] = count ? 1u : 0u;
 	}
 }
 

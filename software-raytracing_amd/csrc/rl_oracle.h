@@ -1,5 +1,5 @@
 // The host oracles (rl_oracle.cc): every query family's brute-force loop over the scene's triangles, in the arithmetic the kernels compile from the same
-// headers (rl_nearest.h, rl_sweep.h, rl_overlap.h, rl_contact.h, rl_sdf.h, rl_motion.h, rl_temporal.h, rl_variance.h, rl_progressive.h).  They are test instruments: the
+// headers (rl_nearest.h, rl_sweep.h, rl_overlap.h, rl_contact.h, rl_box.h, rl_sdf.h, rl_motion.h, rl_temporal.h, rl_variance.h, rl_progressive.h).  They are test instruments: the
 // tests hold the kernels to them byte for byte.  Plain C++ on a scene whose host copies are current: no handle, no log, no refusal and no device -- the ABI
 // (rl_abi.cc: the family's ...ArgsValid, then RunOnHost) has checked the arguments and read back what a move left stale before it calls one of these.
 #pragma once
@@ -49,6 +49,8 @@ void NearestPointsAllHost(const Scene& s, const RaylibAMDNearestQuery* points, i
 void SweepSpheresHost(const Scene& s, int32_t kind, const RaylibAMDSweepQuery* q, int32_t n, void* out);
 void OverlapTrianglesHost(const Scene& s, int32_t kind, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, void* out, uint32_t* outCount);
 void OverlapContactsHost(const Scene& s, uint32_t flags, const RaylibAMDOverlapQuery* q, int32_t n, int32_t maxHits, int32_t* outIndex, RaylibAMDContact* outContact, uint32_t* outCount);
+// MARK: out is the call's mask of (triangles + 31) / 32 words, written whole
+void OverlapBoxesHost(const Scene& s, int32_t kind, const RaylibAMDBoxQuery* q, int32_t n, int32_t maxHits, void* out, uint32_t* outCount);
 // G: the caller's grid with maxDist's -0.0 read as +0.0
 void BakeDistanceFieldHost(const Scene& s, const RaylibAMDDistanceFieldParams& G, float* outDist, int32_t* outPrim);
 // prevCamera: the previous frame's camera (the current one when the caller names none); first, count, prevPositions: the parameters'

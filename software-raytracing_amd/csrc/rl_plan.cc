@@ -238,6 +238,12 @@ QueryPlan PlanOverlap(const Scene& sc, int32_t kind, const RenderKnobs& k)
 	return p;
 }
 
+QueryPlan PlanOverlapBoxes(const Scene& sc, int32_t kind, const RenderKnobs& k)
+{
+	// PlanOverlap's rule: k_overlap_box is that walk with another leaf test (the rule's default was measured on triangles; for boxes: profiles/box_query_time.log)
+	return PlanOverlap(sc, kind == RAYLIB_AMD_BOX_ANY ? RAYLIB_AMD_OVERLAP_ANY : RAYLIB_AMD_OVERLAP_LIST, k);
+}
+
 GatherCut PlanGatherCut(uint32_t n, uint32_t sampleCount, bool sphere, const RenderKnobs& k)
 {
 	GatherCut c;

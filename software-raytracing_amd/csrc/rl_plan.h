@@ -113,6 +113,9 @@ DistanceFieldPlan PlanDistanceField(const Scene& sc, const RenderKnobs& knobs);
 // (children - 1) pushes per level, so the ray walks' stack bounds hold.  `early`: the kind is ANY.  The scene holds triangles
 // only (the entries refuse spheres and cubes before they plan).
 QueryPlan PlanOverlap(const Scene& sc, int32_t kind, const RenderKnobs& knobs);
+// Which tree and k_overlap_box instance a batch of oriented-box queries walks (RaylibAMD_OverlapBoxes, rl_k_overlap_box.inl): PlanOverlap's answer -- the same
+// walk, the same pushes, the same switch.  `early`: the kind is ANY (LIST and MARK walk to the end).
+QueryPlan PlanOverlapBoxes(const Scene& sc, int32_t kind, const RenderKnobs& knobs);
 
 // How RaylibAMD_Gather cuts n points x sampleCount samples into launches (rl_rt_rays.hip DeviceGather; RaylibAMD_PlanGatherCut): a launch holds at most `slots`
 // (point, sample) pairs -- RL_GATHER_SAMPLE_BUDGET over the slot's bytes (16 for IRRADIANCE, 32 for SH9), or RAYLIB_GATHER_BATCH, at most RL_GATHER_MAX_SLOTS.

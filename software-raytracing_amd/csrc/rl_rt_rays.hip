@@ -62,6 +62,16 @@ static OverlapContactsKernel OverlapContactsKernelOf(const QueryPlan& p)
 }
 static_assert(sizeof(RaylibAMDContact) == 2 * sizeof(float4), "contact records");
 
+typedef void (*OverlapBoxKernel)(const DSceneView, const float4*, uint32_t, uint32_t, void*, uint32_t*, const int32_t*, unsigned int*, unsigned long long*);
+template <int KIND>
+static OverlapBoxKernel OverlapBoxKernelOfKind(const QueryPlan& p)
+{
+	if (p.tree == TREE_GRID4) return p.stack <= 32 ? (OverlapBoxKernel)k_overlap_box<4, KIND, 32> : (OverlapBoxKernel)k_overlap_box<4, KIND, 64>;
+	return p.stack <= 32 ? (OverlapBoxKernel)k_overlap_box<2, KIND, 32> : (OverlapBoxKernel)k_overlap_box<2, KIND, 64>;
+}
+static_assert(RAYLIB_AMD_BOX_ANY == RL_BK_ANY && RAYLIB_AMD_BOX_LIST == RL_BK_LIST && RAYLIB_AMD_BOX_MARK == RL_BK_MARK, "box kinds");
+static_assert(sizeof(RaylibAMDBoxQuery) == 64, "box records");
+
 typedef void (*RadianceKernel)(const DSceneView, const SkyRot, const DRadianceParams, const float4*, uint32_t, float4*, float*, unsigned int*, unsigned long long*);
 static RadianceKernel RadianceKernelFor(const QueryPlan& p)
 {
@@ -691,6 +701,44 @@ bool DeviceOverlapTriangles(Scene& sc, int32_t kind, uint32_t flags, const void*
 			hipLaunchKernelGGL(kernel, L.grid, dim3(RL_BLOCK), (uint32_t)D.ldsBytes, L.st, L.view, L.in, (uint32_t)n, flags, (uint32_t)(list ? maxHits : 0), L.out[0], (uint32_t*)L.out[1], L.slotIndex,
 			                   L.counter, L.stats);
 	});
+}
+
+// An oriented-box call: 64-byte records in; a word per query (ANY), rows of maxHits indices and, when asked for, a count per query (LIST, with the lanes' lists
+// as dynamic LDS), or one mask of (triangles + 31) / 32 words for the whole call (MARK), which is cleared on the call's stream in front of the kernel that ORs
+// into it.  An empty MARK call still writes the mask -- all zero -- after the refusals of its pointers.
+bool DeviceOverlapBoxes(Scene& sc, int32_t kind, const void* queries, int32_t n, int32_t maxHits, void* out, uint32_t* outCount, bool hostMem, void* stream, RaylibAMDStats& stats)
+{
+	QueryDesc D("RaylibAMD_OverlapBoxes", "RaylibAMD_OverlapBoxesDevice", "queries", queries, sizeof(RaylibAMDBoxQuery), n, hostMem, stream);
+	D.plan = PlanOverlapBoxes(sc, kind, ReadRenderKnobs());
+	const bool list = kind == RAYLIB_AMD_BOX_LIST, mark = kind == RAYLIB_AMD_BOX_MARK;
+	const OverlapBoxKernel kernel = mark ? OverlapBoxKernelOfKind<RL_BK_MARK>(D.plan) : list ? OverlapBoxKernelOfKind<RL_BK_LIST>(D.plan) : OverlapBoxKernelOfKind<RL_BK_ANY>(D.plan);
+	D.kernel = (const void*)kernel;
+	D.ldsBytes = list ? (size_t)maxHits * RL_BLOCK * sizeof(uint32_t) : 0;
+	const size_t maskBytes = (sc.triangles.size() + 31u) / 32u * sizeof(uint32_t);
+	D.out[0] = { out, mark ? maskBytes : list ? (size_t)n * (size_t)maxHits * sizeof(int32_t) : (size_t)n * sizeof(uint32_t), 3u, &RankCtx::qOut };
+	D.out[1] = { outCount, outCount ? (size_t)n * sizeof(uint32_t) : 0, 3u, &RankCtx::qPrim };
+	D.slotIndex = list || mark;
+	if (mark && n == 0 && out && maskBytes) {
+		// (RunQuery asks an empty call's pointers nothing: this one writes)
+		if (!EnsureRuntime()) return false;
+		RankCtx& R = Rank0();
+		HIP_OK(hipSetDevice(R.device));
+		if (!hostMem && !DevicePointersOk(D.apiDevice, nullptr, R.device, nullptr, D.out, 1)) return false;
+	}
+	if (!RunQuery(sc, D, stats, [&](const QueryLaunch& L) {
+		if (mark) (void)hipMemsetAsync(L.out[0], 0, maskBytes, L.st);   // (a failure is the launch's error: LaunchOnRing asks hipGetLastError behind it)
+		hipLaunchKernelGGL(kernel, L.grid, dim3(RL_BLOCK), (uint32_t)D.ldsBytes, L.st, L.view, L.in, (uint32_t)n, (uint32_t)(list ? maxHits : 0), L.out[0], (uint32_t*)L.out[1], L.slotIndex,
+		                   L.counter, L.stats);
+	})) return false;
+	if (mark && n == 0 && out && maskBytes) {
+		if (hostMem) memset(out, 0, maskBytes);
+		else {
+			const hipStream_t st = stream ? (hipStream_t)stream : Rank0().stream;
+			HIP_OK(hipMemsetAsync(out, 0, maskBytes, st));
+			if (!stream) HIP_OK(hipStreamSynchronize(st));
+		}
+	}
+	return true;
 }
 
 // A distance-field bake (RaylibAMD_BakeDistanceField) is a nearest-point call without points and a multi-hit call without rays: up to three launches on one

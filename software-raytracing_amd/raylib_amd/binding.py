@@ -696,6 +696,47 @@ def overlap_contacts(lib, scene, queries, flags=0, max_hits=MAX_OVERLAPS, host=F
                         host=host, records=OVERLAP_QUERY_DTYPE, type_error=_QUERIES_TYPE_ERROR))
 
 
+BOX_ANY, BOX_LIST, BOX_MARK = 0, 1, 2               # RAYLIB_AMD_BOX_*
+BOX_QUERY_DTYPE = np.dtype([("center", "f4", 3), ("reserved", "u4"), ("axis", [("dir", "f4", 3), ("half", "f4")], 3)])   # RaylibAMDBoxQuery
+
+
+def box_queries(center, half, axes=None):
+    """BOX_QUERY_DTYPE records from (n, 3) centres, (n, 3) half extents and (n, 3, 3) axes (row k: axis k's direction; None: the identity, axis-aligned boxes)."""
+    q = np.zeros(len(center), BOX_QUERY_DTYPE)
+    q["center"] = center
+    q["axis"]["dir"] = np.eye(3, dtype=np.float32) if axes is None else axes
+    q["axis"]["half"] = half
+    return q
+
+
+def plan_overlap_boxes(lib, scene, kind):
+    """RaylibAMD_PlanOverlapBoxes: (return code, plan dict)."""
+    return _plan(lib, "RaylibAMD_PlanOverlapBoxes", scene, int(kind))
+
+
+def overlap_boxes(lib, scene, q, kind, k=MAX_OVERLAPS, count=True, host=False):
+    """Oriented-box range queries (RaylibAMD_OverlapBoxes / RaylibAMD_OverlapBoxesDevice / RaylibAMD_OverlapBoxesHost, statements B1 to B6).
+
+    q: BOX_QUERY_DTYPE records (or an (n, 16) float32 array of the same 64 bytes).  A NumPy array goes through the host entry (host=True: through the oracle,
+    which needs no device) and returns NumPy arrays: uint32 words for BOX_ANY; for BOX_LIST the (n, k) int32 rows, and with count=True the pair (rows, uint32
+    counts); for BOX_MARK the call's mask, (numTriangles + 31) // 32 uint32 words.  An (n, 16) float32 torch tensor on the device goes through the device entry
+    on torch.cuda.current_stream(), as overlap_triangles: enqueued on a stream of the caller's, synchronous on torch's default stream (synchronised first); it
+    returns int32 tensors of the same shapes.  Raises RuntimeError when the library refuses the call."""
+    kind, k = int(kind), int(k)
+    if kind not in (BOX_ANY, BOX_LIST, BOX_MARK):
+        raise ValueError("unknown box kind %r" % kind)
+    want_count = kind == BOX_LIST and count
+    if kind == BOX_LIST:
+        specs = _rows(k, np.int32, want_count)
+    elif kind == BOX_MARK:
+        words = (lib.RaylibAMD_SceneNumTriangles(scene) + 31) // 32
+        specs = lambda n: [(words, np.uint32), None]
+    else:
+        specs = lambda n: [(n, np.uint32), None]
+    out, counts = _query(lib, scene, q, 16, "RaylibAMD_OverlapBoxes", specs, pre=(kind,), mid=(k,), host=host, records=BOX_QUERY_DTYPE, type_error=_QUERIES_TYPE_ERROR)
+    return (out, counts) if want_count else out
+
+
 def move_triangles(lib, scene, first, positions, normals=None):
     """Move triangles [first, first + n) of a finalized scene (RaylibAMD_SceneMoveTriangles / RaylibAMD_SceneMoveTrianglesDevice).
 
@@ -1260,6 +1301,10 @@ _EXPORTS = {
     "RaylibAMD_OverlapContactsDevice": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "RaylibAMD_OverlapContactsHost": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "RaylibAMD_PlanOverlapContacts": (C.c_int32, [C.c_void_p, C.POINTER(QueryPlan)]),
+    "RaylibAMD_OverlapBoxes": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_OverlapBoxesDevice": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_OverlapBoxesHost": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "RaylibAMD_PlanOverlapBoxes": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(QueryPlan)]),
     "RaylibAMD_Gather": (C.c_int32, [C.c_void_p, C.POINTER(GatherParams), C.POINTER(GatherPoint), C.c_int32, C.POINTER(C.c_float)]),
     "RaylibAMD_GatherDevice": (C.c_int32, [C.c_void_p, C.POINTER(GatherParams), C.POINTER(GatherPoint), C.c_int32, C.POINTER(C.c_float), C.c_void_p]),
     "RaylibAMD_GatherDirectionsHost": (C.c_int32, [C.POINTER(GatherParams), C.POINTER(GatherPoint), C.c_int32, C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]),

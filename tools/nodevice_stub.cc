@@ -18,6 +18,7 @@ bool DeviceSweepSpheres(Scene&, int32_t, const void*, int32_t, void*, bool, void
 bool DeviceNearestPointsAll(Scene&, const void*, int32_t, int32_t, void*, uint32_t*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceBakeDistanceField(Scene&, const RaylibAMDDistanceFieldParams&, float*, int32_t*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceOverlapTriangles(Scene&, int32_t, uint32_t, const void*, int32_t, int32_t, void*, uint32_t*, bool, void*, RaylibAMDStats&, void*, bool) { return false; }
+bool DeviceOverlapBoxes(Scene&, int32_t, const void*, int32_t, int32_t, void*, uint32_t*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceTraceRadiance(Scene&, const RaylibAMDRadianceParams&, uint64_t, const void*, int32_t, float*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceGather(Scene&, int32_t, const RaylibAMDRadianceParams&, uint64_t, const void*, int32_t, float*, bool, void*, RaylibAMDStats&, const RaylibAMDGatherAdaptiveParams*,
                   uint32_t*) { return false; }
