@@ -75,7 +75,7 @@ typedef struct RaylibAMDStats {
 	uint32_t nodeBytes;       /* bytes of one record counted in nodesVisited: 64, or 80 for the 8-wide tree */
 	/* ---- the leaf-list kernel's lazy-reflectance instance (RaylibAMD_LastTraceLazy): 0 for every other kernel ---- */
 	uint64_t litPaths;        /* traced paths that ended with light in them (or met a vertex whose reflectance may not be skipped): the ones whose reflectances were evaluated */
-	uint64_t litFoldedInPlace;/* ... of them, those folded inside the megakernel instead of by k_fold_lit (the lit list was full, or the path had more vertices than an entry holds) */
+	uint64_t litFoldedInPlace;/* ... of them, those folded in place by their own lane instead of from an entry of the lit list by a whole wave (the lit list was full, or the path had more vertices than an entry holds) */
 } RaylibAMDStats;
 
 /* Seed of the per-(pixel, sample) streams of include/raylib_amd_rng.h. */
@@ -1267,7 +1267,7 @@ typedef struct RaylibAMDRenderPlan {
 	int32_t eagerTree;        /* the wide tree the scene's upload puts on the device (tree code, 0: none) */
 	uint32_t batch, sampleCount, blocks, stackStride, jobChunk, heads, jobsPerHead, guideShift;
 	uint64_t jobs;
-	int32_t lazy;             /* the plain instance's lazy-reflectance form (k_trace_lazy + k_fold_lit); 0 for a batch of views, whose twin stays eager */
+	int32_t lazy;             /* the plain instance's lazy-reflectance form (k_trace_lazy or its hit-queue form); 0 for a batch of views, whose twin stays eager */
 	int32_t hitQueue;         /* ... and of that, its hit-queue form (k_trace_lazy_hitq); the field was `reserved`, always 0 */
 } RaylibAMDRenderPlan;
 RAYLIB_API int32_t RaylibAMD_PlanRender(SceneHandle scene, const RendererSettings* settings, int32_t hasSky, int32_t numCUs, int32_t workgroupsPerCU, RaylibAMDRenderPlan* out);

@@ -273,12 +273,12 @@ struct DViews {
 };
 
 // k_trace's lazy-reflectance instance (rl_k_trace.inl RL_LAZY_REFL; the planner's conditions: rl_plan.cc, rl_scene.cc SceneLazyRefl) skips a vertex's reflectance
-// and hands the paths that end with light in them to k_fold_lit through this list: entries of RL_LIT_STRIDE float4 (terminal L | outIndex; record count; then up
-// to RL_FOLD_PREFETCH vertex records of two float4, camera first), reserved by the waves in chunks of RL_LIT_CHUNK entries.
-//   ctl[0] chunks handed out so far (may pass numChunks: a wave that draws one beyond folds in place); ctl[RL_LIT_CTL + c] entries filled in chunk c
+// and collects the paths that end with light in them in this list: entries of RL_LIT_STRIDE float4 (terminal L | outIndex; record count; then up
+// to RL_FOLD_PREFETCH vertex records of two float4, camera first), reserved by the waves in chunks of RL_LIT_CHUNK entries.  The wave that filled a chunk folds
+// it, entry `lane` in lane `lane`, and its last, partly filled one before it leaves (rl_dev_litfold.h): the list is scratch of the launch, nothing reads it afterwards.
+//   ctl[0] chunks handed out so far (may pass numChunks: a wave that draws one beyond folds in place), zeroed per launch
 // The interval of the materials the instance takes (closed; every scene of the repository lies inside): the bound argument is rl_dev_shade.h LazyVertexSafe's.
 #define RL_LIT_CHUNK 64u
-#define RL_LIT_CTL 16u
 #define RL_LAZY_ROUGHNESS_MIN 0x1p-10f
 #define RL_LAZY_ROUGHNESS_MAX 1.0f          /* what the loader and RaylibAMD_CreateMaterial saturate a microfacet roughness to */
 #define RL_LAZY_COLOR_MAX 16.0f      /* |albedo|, |metallic|, either sign (a mirror's albedo is not saturated) */
@@ -293,7 +293,7 @@ struct DViews {
 #define RL_LIT_MASK_MAX_WORDS 8u     /* a launch of more than 256 samples per slot keeps the unmasked path */
 struct DLitList {
 	float* entries;              // float4 units
-	uint32_t* ctl;
+	uint32_t* ctl;               // one word: the chunk counter
 	uint32_t numChunks;          // 0: no list, every lit path folds in place
 	uint32_t maskWords;          // words per slot of the mask: ceil(sampleCount / 32)
 	uint32_t* mask;              // null: no mask

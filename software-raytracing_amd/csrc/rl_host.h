@@ -259,7 +259,7 @@ bool DeviceRender(Scene& scene, const RenderRequest& req, RaylibAMDStats& stats)
 // RaylibAMD_RenderViews: `count` views (cameras[v]) of req.settings / req.seed into outDevice (view-major, count * W * H float4; nullptr: the library's
 // own buffer) and, when imagePixels is given, each view's frame copied into imagePixels[v] (W * H float4 on rank 0's device).  Synchronous.
 bool DeviceRenderViews(Scene& scene, const RenderRequest& req, const DCamera* cameras, uint32_t count, void* outDevice, void* const* imagePixels, RaylibAMDStats& stats);
-int32_t DeviceLastTraceLazy();    // 1: ... and of that, the lazy-reflectance instance (k_trace_lazy + k_fold_lit)
+int32_t DeviceLastTraceLazy();    // 1: ... and of that, the lazy-reflectance instance (k_trace_lazy or its hit-queue form)
 int32_t DeviceLastHitQueue();     // 1: ... and of that, its hit-queue form (k_trace_lazy_hitq)
 int32_t DeviceLastLitMask();      // 1: ... and that launch kept a lit-sample mask (rl_lit_mask.h: k_resolve_lit behind it)
 int32_t DeviceLastTracePlain();   // 1: the last path-traced render's megakernel was the leaf-list kernel's plain instance (rl_plan.cc)

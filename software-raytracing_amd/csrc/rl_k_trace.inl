@@ -454,32 +454,14 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 			}
 		}
 		if (Ballot(finLit) != 0ull) {
-			// ---- the lit paths that ended in this trip, wave-wide: an entry of the lit list each (k_fold_lit folds them, in full waves), reserved in the wave's chunk
-			// and, when that is full, in one more (one global atomic per RL_LIT_CHUNK entries; a returning atomic per trip on one address would be the rate at
-			// which the job counter once bound this kernel).  A path with more records than an entry holds, or without an entry because the list is used up, folds
-			// in place: slow, rare, the same statements on the same values.
+			// ---- the lit paths that ended in this trip, wave-wide (rl_dev_litfold.h): an entry of the lit list each, reserved in the wave's chunk and, when that
+			// is full, in one more; the chunk these entries complete is folded here by the whole wave, 64 entries in 64 lanes.  A path with more records than an
+			// entry holds, or without an entry because the list is used up, folds in place: slow, rare, the same statements on the same values.
 			RL_ARGS();
 			RL_LIT_ARGS();
 			const int nrec = depth + (finTop ? 1 : 0);
-			const bool wantEntry = finLit && nrec <= RL_FOLD_PREFETCH;
-			const unsigned long long em = Ballot(wantEntry);
-			const uint32_t n = (uint32_t)__popcll(em), rank = (uint32_t)__popcll(em & ((1ull << lane) - 1ull)), room = RL_LIT_CHUNK - litFill;
-			uint32_t fresh = ~0u;
-			if (n > room && !litFull) {
-				if (lane == 0 && LL.numChunks != 0u) fresh = atomicAdd(&LL.ctl[0], 1u);
-				fresh = __shfl(fresh, 0);
-				if (fresh >= LL.numChunks) { fresh = ~0u; litFull = true; }
-			}
-			uint32_t entry = ~0u;
-			if (wantEntry) {
-				if (rank < room) entry = litChunk * RL_LIT_CHUNK + litFill + rank;
-				else if (fresh != ~0u) entry = fresh * RL_LIT_CHUNK + (rank - room);
-			}
-			if (n > room) {   // the wave's chunk is full now, and the fresh one (if any) is the wave's
-				if (lane == 0 && litChunk != ~0u) LL.ctl[RL_LIT_CTL + litChunk] = RL_LIT_CHUNK;
-				litChunk = fresh; litFill = fresh != ~0u ? n - room : RL_LIT_CHUNK;
-			} else litFill += n;
-			if (lane == 0 && litChunk != ~0u && n != 0u) LL.ctl[RL_LIT_CTL + litChunk] = litFill;
+			uint32_t full;
+			const uint32_t entry = LitReserve(LL, lane, finLit && nrec <= RL_FOLD_PREFETCH, litChunk, litFill, litFull, full);
 			if (finLit) {
 				nLit++;
 				if (entry != ~0u) {
@@ -495,25 +477,10 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 					}
 				} else {
 					nInPlace++;
-					V3 L = finL;
-					#pragma nounroll
-					for (int k = nrec - 1; k >= 0; --k) {
-						float4 r0 = finRec0, r1 = finRec1;
-						if (k < depth) {
-							const float4* st = (const float4*)pathStack + ((size_t)k * P.stackStride + gtid) * 2u;
-							r0 = st[0]; r1 = st[1];
-						}
-						const Mat m = MatFrom<PLAIN>(sm + LdsAt<LDS>::MATS + RL_LAZY_REC_MAT(r1.w) * RL_LDS_MSTRIDE(PLAIN));
-						L = FoldLazyVertex(m, r0, r1, L);
-					}
-					if (!LL.mask) samples[outIndex] = make_sample(L.x, L.y, L.z);
-					else if (AnyBitSet(L)) {
-						const uint32_t s = outIndex / numSlots;
-						samples[outIndex] = make_sample(L.x, L.y, L.z);
-						atomicOr(&LL.mask[LitMaskWord(s, numSlots, outIndex - s * numSlots)], LitMaskBit(s));
-					}
+					LitFoldInPlace(LL, sm, samples, numSlots, outIndex, finL, nrec, depth, (const float4*)pathStack + (size_t)gtid * 2u, (size_t)P.stackStride * 2u, finRec0, finRec1);
 				}
 			}
+			if (full != ~0u) LitFoldChunk(LL, sm, samples, numSlots, full, RL_LIT_CHUNK, lane);
 		}
 		{   // (a bare block: the eager branch below is still inside `if (active)`, and the brace behind #endif closes either)
 #else
@@ -573,6 +540,12 @@ k_trace(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, SampleRGB*
 	}
 
 	RL_ARGS();
+#if RL_LAZY_REFL
+	{   // the chunk the wave still holds: its first litFill entries (litChunk is ~0u when the wave had no lit path, or the list ran out at its last reservation)
+		RL_LIT_ARGS();
+		if (litChunk != ~0u) LitFoldChunk(LL, sm, samples, numSlots, litChunk, litFill, lane);
+	}
+#endif
 #ifdef RL_DIAG_STAMPS
 	if (lane == 0) for (int k = 0; k < 4; ++k) { atomicAdd(&counters[CNT_COUNT + k], stampAcc[k]); atomicAdd(&counters[CNT_COUNT + 8 + k], subAcc[k]); atomicAdd(&counters[CNT_COUNT + 12 + k], c.tAcc[k]); atomicAdd(&counters[CNT_COUNT + 20 + k], laneAcc[k]); if (RL_DIAG_STAMPS < 2) atomicAdd(&counters[CNT_COUNT + 4 + k], laneT[k]); }
 #endif

@@ -9,34 +9,14 @@
 //   2. walk    the lanes that hold a bounce ray trace it; a miss runs the miss shader and ends the path;
 //   3. pop     every free lane takes a queued hit;
 //   4. shade   all active lanes: every one of them holds a hit;
-//   5. the wave-level part that finishes the lit paths, as in k_trace_lazy.
+//   5. the wave-level part that finishes the lit paths that ended in this trip, as in k_trace_lazy (rl_dev_litfold.h has the statements of both): a path of at
+//              most RL_FOLD_PREFETCH records becomes an entry of the wave's chunk of the lit list, and the wave that writes a chunk's 64th entry folds the chunk
+//              there, entry `lane` in lane `lane`; a path with more records, or without an entry because the list is used up, folds in place, in its lane alone.
+//              This instance ends lit paths at two places -- a camera ray that misses into light in a batch (part 1), and the trip's paths -- and reserves, writes
+//              and folds the same way at both;
+//   6. exit    behind the loop the wave folds the chunk it still holds, up to the entries it filled.  No kernel follows to finish the list.
 // No path changes its lane once it has one, the queue is the wave's own 1024 dwords of s_stack, and nothing here waits for another wave but the draw of a chunk.
 // maxPathLength >= 1 (the planner keeps k_trace_lazy otherwise: a camera ray is traced before its path has a depth to test).
-
-// A lit path's entry in the wave's chunk of the lit list, or ~0u when it folds in place: k_trace_lazy's reservation (one global atomic per RL_LIT_CHUNK entries), as a
-// function because this instance ends lit paths at two places -- a camera ray that misses into light in a batch, and the trip's paths.  Whole waves call it.
-__device__ __forceinline__ uint32_t LitReserve(const DLitList& LL, uint32_t lane, bool wantEntry, uint32_t& litChunk, uint32_t& litFill, bool& litFull)
-{
-	const unsigned long long em = Ballot(wantEntry);
-	const uint32_t n = (uint32_t)__popcll(em), rank = (uint32_t)__popcll(em & ((1ull << lane) - 1ull)), room = RL_LIT_CHUNK - litFill;
-	uint32_t fresh = ~0u;
-	if (n > room && !litFull) {
-		if (lane == 0 && LL.numChunks != 0u) fresh = atomicAdd(&LL.ctl[0], 1u);
-		fresh = __shfl(fresh, 0);
-		if (fresh >= LL.numChunks) { fresh = ~0u; litFull = true; }
-	}
-	uint32_t entry = ~0u;
-	if (wantEntry) {
-		if (rank < room) entry = litChunk * RL_LIT_CHUNK + litFill + rank;
-		else if (fresh != ~0u) entry = fresh * RL_LIT_CHUNK + (rank - room);
-	}
-	if (n > room) {   // the wave's chunk is full now, and the fresh one (if any) is the wave's
-		if (lane == 0 && litChunk != ~0u) LL.ctl[RL_LIT_CTL + litChunk] = RL_LIT_CHUNK;
-		litChunk = fresh; litFill = fresh != ~0u ? n - room : RL_LIT_CHUNK;
-	} else litFill += n;
-	if (lane == 0 && litChunk != ~0u && n != 0u) LL.ctl[RL_LIT_CTL + litChunk] = litFill;
-	return entry;
-}
 
 template <int STACK, bool PRIMS, bool FULL, int LDS, bool PLAIN>
 __global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 2))
@@ -196,7 +176,8 @@ k_trace_lazy_hitq(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, 
 			if (Ballot(qLit) != 0ull) {
 				// A camera ray that missed into light (a sun): k_trace_lazy ends it in the wave-level part of its trip as a lit path of zero records -- an entry of the
 				// lit list, whose fold is the identity, or, the list used up, in place -- and counts it in litPaths (and litFoldedInPlace).  The same here.
-				const uint32_t entry = LitReserve(LL, lane, qLit, litChunk, litFill, litFull);
+				uint32_t full;
+				const uint32_t entry = LitReserve(LL, lane, qLit, litChunk, litFill, litFull, full);
 				if (qLit) {
 					nLit++;
 					if (entry != ~0u) {
@@ -205,14 +186,10 @@ k_trace_lazy_hitq(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, 
 						e[1] = make_float4(__int_as_float(0), 0.0f, 0.0f, 0.0f);
 					} else {
 						nInPlace++;
-						if (!LL.mask) samples[qOut] = make_sample(qL.x, qL.y, qL.z);
-						else {   // (any bit of qL is set)
-							const uint32_t s = qOut / numSlots;
-							samples[qOut] = make_sample(qL.x, qL.y, qL.z);
-							atomicOr(&LL.mask[LitMaskWord(s, numSlots, qOut - s * numSlots)], LitMaskBit(s));
-						}
+						LitStoreSample(LL, samples, numSlots, qOut, qL);   // (any bit of qL is set)
 					}
 				}
+				if (full != ~0u) LitFoldChunk(LL, sm, samples, numSlots, full, RL_LIT_CHUNK, lane);
 			}
 			const unsigned long long hv = Ballot(qHit);
 			if (qHit) {
@@ -328,13 +305,15 @@ k_trace_lazy_hitq(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, 
 			}
 		}
 
-		// ---- 5. the lit paths that ended in this trip, wave-wide (k_trace_lazy's part): an entry of the lit list each, reserved in the wave's chunk; a path with
-		// more records than an entry holds, or without an entry because the list is used up, folds in place ----
+		// ---- 5. the lit paths that ended in this trip, wave-wide (k_trace_lazy's part): an entry of the lit list each, reserved in the wave's chunk, and the chunk
+		// these entries complete folded here by the whole wave; a path with more records than an entry holds, or without an entry because the list is used up,
+		// folds in place ----
 		if (Ballot(finLit) != 0ull) {
 			RL_ARGS();
 			RL_LIT_ARGS();
 			const int nrec = depth + (finTop ? 1 : 0);
-			const uint32_t entry = LitReserve(LL, lane, finLit && nrec <= RL_FOLD_PREFETCH, litChunk, litFill, litFull);
+			uint32_t full;
+			const uint32_t entry = LitReserve(LL, lane, finLit && nrec <= RL_FOLD_PREFETCH, litChunk, litFill, litFull, full);
 			if (finLit) {
 				nLit++;
 				if (entry != ~0u) {
@@ -350,29 +329,18 @@ k_trace_lazy_hitq(const DRenderParams Pk, const DSceneView Sk, const SkyRot Rk, 
 					}
 				} else {
 					nInPlace++;
-					V3 L = finL;
-					#pragma nounroll
-					for (int k = nrec - 1; k >= 0; --k) {
-						float4 r0 = finRec0, r1 = finRec1;
-						if (k < depth) {
-							const float4* st = (const float4*)pathStack + ((size_t)k * P.stackStride + gtid) * 2u;
-							r0 = st[0]; r1 = st[1];
-						}
-						const Mat m = MatFrom<PLAIN>(sm + LdsAt<LDS>::MATS + RL_LAZY_REC_MAT(r1.w) * RL_LDS_MSTRIDE(PLAIN));
-						L = FoldLazyVertex(m, r0, r1, L);
-					}
-					if (!LL.mask) samples[outIndex] = make_sample(L.x, L.y, L.z);
-					else if (AnyBitSet(L)) {
-						const uint32_t s = outIndex / numSlots;
-						samples[outIndex] = make_sample(L.x, L.y, L.z);
-						atomicOr(&LL.mask[LitMaskWord(s, numSlots, outIndex - s * numSlots)], LitMaskBit(s));
-					}
+					LitFoldInPlace(LL, sm, samples, numSlots, outIndex, finL, nrec, depth, (const float4*)pathStack + (size_t)gtid * 2u, (size_t)P.stackStride * 2u, finRec0, finRec1);
 				}
 			}
+			if (full != ~0u) LitFoldChunk(LL, sm, samples, numSlots, full, RL_LIT_CHUNK, lane);
 		}
 	}
 
 	RL_ARGS();
+	{   // the chunk the wave still holds: its first litFill entries (litChunk is ~0u when the wave had no lit path, or the list ran out at its last reservation)
+		RL_LIT_ARGS();
+		if (litChunk != ~0u) LitFoldChunk(LL, sm, samples, numSlots, litChunk, litFill, lane);
+	}
 	RL_TIMELINE(2);
 	// ---- counters: wave reduction, one atomic per wave and counter ----
 	uint32_t vals[CNT_COUNT] = { c.rays, c.nodes, c.tris, c.shaded, c.texels, c.samples, c.trips };

@@ -5,7 +5,7 @@
 //                        the multi-rank scatter, the test hooks)
 //   rl_render_views.hip  k_trace_views, k_resolve_views, k_aov_views: the views twins (RaylibAMD_RenderViews).  Instantiated beside the one-view kernels they
 //                        change how the helpers both call are inlined into those (tools/isa_equivalence.py)
-//   rl_render_lazy.hip   k_trace_lazy, k_trace_lazy_hitq, k_fold_lit, k_verify_lazy_refl, k_verify_lazy_pdf, k_verify_sampler_ranged, k_verify_normalize_ranged: the leaf-list kernel's lazy-reflectance instance.  Beside the other k_trace instances it
+//   rl_render_lazy.hip   k_trace_lazy, k_trace_lazy_hitq, k_resolve_lit, k_verify_lazy_refl, k_verify_lazy_pdf, k_verify_sampler_ranged, k_verify_normalize_ranged: the leaf-list kernel's lazy-reflectance instance.  Beside the other k_trace instances it
 //                        changes how two loops of the eager PLAIN instance are scheduled
 //   rl_render_pool.hip   k_trace_pool and its twin: a scheduler strategy of its own (Makefile POOLFLAGS)
 //   rl_query.hip         k_query (RaylibAMD_TraceRays): beside the render kernels it would change how the walks they share are inlined into those
@@ -78,20 +78,19 @@ __global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 
 RL_TRACE_INSTANCES(extern RL_K_TRACE)
 RL_TRACE_INSTANCES(extern RL_K_TRACE_VIEWS)
 // The lazy-reflectance instance of the leaf-list kernel's PLAIN instance (rl_k_trace.inl RL_LAZY_REFL, rl_dev_shade.h): a kernel name of its own with the lit list as
-// one more trailing argument, so that every other instance keeps its name and its code; and the kernel that folds the list's entries, one thread each, grid-stride over
-// the chunk counts on the device (the host never reads them).
+// one more trailing argument, so that every other instance keeps its name and its code.  Its waves fold the list's entries themselves, a chunk of 64 in 64 lanes
+// (rl_dev_litfold.h): no kernel follows it but the resolve.
 template <int STACK, bool PRIMS, bool FULL, int LDS, bool PLAIN>
 __global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 2)) k_trace_lazy(RL_TRACE_ARGS, const DLitList);
 #define RL_TRACE_LAZY_INSTANCES(X) X(16, false, true, 2, true)
 #define RL_K_TRACE_LAZY(a, b, c, d, e) template __global__ void k_trace_lazy<a, b, c, d, e>(RL_TRACE_ARGS, const DLitList);
 RL_TRACE_LAZY_INSTANCES(extern RL_K_TRACE_LAZY)
-// The lazy instance's hit-queue form (rl_k_trace_hitq.inl): the same arguments, the same paths and the same k_fold_lit behind it; its idle lanes take camera rays
+// The lazy instance's hit-queue form (rl_k_trace_hitq.inl): the same arguments, the same paths and the same fold of the lit list; its idle lanes take camera rays
 // that have been traced already, so that every lane enters the shading part with a hit.
 template <int STACK, bool PRIMS, bool FULL, int LDS, bool PLAIN>
 __global__ void __launch_bounds__(RL_BLOCK, (STACK <= 32 ? RL_TRACE_MIN_WAVES : 2)) k_trace_lazy_hitq(RL_TRACE_ARGS, const DLitList);
 #define RL_K_TRACE_LAZY_HITQ(a, b, c, d, e) template __global__ void k_trace_lazy_hitq<a, b, c, d, e>(RL_TRACE_ARGS, const DLitList);
 RL_TRACE_LAZY_INSTANCES(extern RL_K_TRACE_LAZY_HITQ)
-__global__ void __launch_bounds__(RL_BLOCK) k_fold_lit(const DSceneView S, const DLitList LL, SampleRGB* __restrict__ samples, uint32_t numSlots);
 // k_resolve for a batch of the lazy instance with a lit-sample mask (rl_lit_mask.h): the slot's flagged samples alone
 __global__ void __launch_bounds__(RL_BLOCK)
 k_resolve_lit(const DRenderParams P, const DSceneView S, const SkyRot R, const SampleRGB* __restrict__ samples, float4* __restrict__ accum, float4* __restrict__ out,

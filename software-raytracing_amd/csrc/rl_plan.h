@@ -45,7 +45,7 @@ struct TracePlan {
 	int lstack = 0;             // pool: entries of the traversal stack in LDS
 	int lds = 0;                // k_trace: 0, 1 = the scene in LDS, 2 = the leaf list
 	bool plain = false;         // the leaf-list kernel's instance without texture, cut-out and sky code
-	bool lazy = false;          // ... and of that, the lazy-reflectance instance (k_trace_lazy + k_fold_lit); the views twin of a lazy plan is the plain instance's
+	bool lazy = false;          // ... and of that, the lazy-reflectance instance (k_trace_lazy or its hit-queue form); the views twin of a lazy plan is the plain instance's
 	bool hitQueue = false;      // ... and of that, its hit-queue form (k_trace_lazy_hitq): idle lanes take camera rays that have been traced already
 	uint32_t pathsPerWave = 64, treeWidth = 2, nodeBytes = 64;   // RaylibAMDStats
 	bool keepNodes4 = true, keepNodes4f = true;   // the launch's view keeps the grid / float-box wide nodes (k_trace tells the tree by which is set)

@@ -1,4 +1,4 @@
-// The leaf-list kernel's lazy-reflectance instance (k_trace_lazy), its hit-queue form (k_trace_lazy_hitq), the kernel that finishes their lit paths (k_fold_lit) and the sweeps of its guards, as a translation
+// The leaf-list kernel's lazy-reflectance instance (k_trace_lazy), its hit-queue form (k_trace_lazy_hitq), the resolve that reads their lit-sample mask (k_resolve_lit) and the sweeps of its guards, as a translation
 // unit of their own: instantiated beside the other k_trace instances, the lazy one changes how the compiler schedules two loops of the eager PLAIN instance, and
 // the eager kernels must stay what they are (tools/isa_equivalence.py) -- the reason the views twins have their unit.
 
@@ -16,10 +16,11 @@
 // ---- the device library ----
 #include "rl_kernels.h"
 #include "rl_lit_mask.h"
+#include "rl_dev_litfold.h"
 
 namespace rl {
 
-// ---- the leaf-list kernel's lazy-reflectance instance and the kernel that finishes its lit paths (rl_dev_shade.h "lazy-reflectance instance") ----
+// ---- the leaf-list kernel's lazy-reflectance instance (rl_dev_shade.h "lazy-reflectance instance"); its lit paths are finished by its own waves (rl_dev_litfold.h) ----
 #define RL_VIEWS_TWIN 0
 #define RL_LAZY_REFL 1
 #include "rl_k_trace.inl"
@@ -28,37 +29,6 @@ namespace rl {
 
 // ---- its hit-queue form (k_trace_lazy_hitq): the idle lanes take camera rays that have been traced already.  In this unit, whose settings it shares ----
 #include "rl_k_trace_hitq.inl"
-
-// One thread per entry of the lit list (rl_device.h DLitList): the path's vertex records, camera first, folded from the last back to the camera exactly as k_trace
-// folds -- each vertex's reflectance evaluated here, in full waves, instead of at its scattering event -- and the sample stored; with a lit-sample mask
-// (rl_lit_mask.h) by its rule: all zero bits, neither stored nor flagged.  numSlots splits the entry's outIndex into sample and slot.
-__global__ void __launch_bounds__(RL_BLOCK)
-k_fold_lit(const DSceneView S, const DLitList LL, SampleRGB* __restrict__ samples, uint32_t numSlots)
-{
-	RL_MATH_PROLOGUE();
-	const uint32_t lane = threadIdx.x & 63u;
-	const uint32_t waves = gridDim.x * (RL_BLOCK / 64u);
-	const uint32_t used = min(LL.ctl[0], LL.numChunks);
-	for (uint32_t chunk = (blockIdx.x * RL_BLOCK + threadIdx.x) >> 6; chunk < used; chunk += waves) {
-		if (lane >= min(LL.ctl[RL_LIT_CTL + chunk], RL_LIT_CHUNK)) continue;
-		const float4* e = (const float4*)LL.entries + ((size_t)chunk * RL_LIT_CHUNK + lane) * RL_LIT_STRIDE;
-		const float4 h0 = e[0];
-		const int nrec = __float_as_int(e[1].x);   // (<= RL_FOLD_PREFETCH: k_trace_lazy folds longer paths in place)
-		V3 L = v3(h0.x, h0.y, h0.z);
-		#pragma nounroll
-		for (int k = nrec - 1; k >= 0; --k) {
-			const float4 r0 = e[2 + 2 * k], r1 = e[3 + 2 * k];
-			L = FoldLazyVertex(LoadMat(S, RL_LAZY_REC_MAT(r1.w)), r0, r1, L);
-		}
-		const uint32_t outIndex = __float_as_uint(h0.w);
-		if (!LL.mask) samples[outIndex] = make_sample(L.x, L.y, L.z);
-		else if (AnyBitSet(L)) {
-			const uint32_t s = outIndex / numSlots;
-			samples[outIndex] = make_sample(L.x, L.y, L.z);
-			atomicOr(&LL.mask[LitMaskWord(s, numSlots, outIndex - s * numSlots)], LitMaskBit(s));
-		}
-	}
-}
 
 // k_resolve (rl_k_resolve.inl) for a batch with a lit-sample mask: the same contract, one thread per slot.  A culled cell takes SumSlotBatch's branch as it is;
 // every other slot adds its flagged samples, in sample order (LitMaskSum) -- the samples the mask leaves out are +0 and were never stored.

@@ -185,7 +185,7 @@ struct RankCtx {
 	DevBuf<float4> cells;   // N > 1: this rank's cells back to back, when they are not rendered into the gather buffer
 	DevBuf<unsigned long long> counters;
 	DevBuf<unsigned int> jobCounter;
-	DevBuf<float4> litList; DevBuf<uint32_t> litCtl;   // the lazy-reflectance instance's lit list and its chunk counts (rl_device.h DLitList), reset per sample batch
+	DevBuf<float4> litList; DevBuf<uint32_t> litCtl;   // the lazy-reflectance instance's lit list and its chunk counter (rl_device.h DLitList), reset per sample batch
 	DevBuf<uint32_t> litMask;   // ... and its lit-sample mask (rl_lit_mask.h), zeroed per sample batch
 	// cells outside the scene's silhouette (CullCells), per frame slot: the list of the others and a flag per cell, pinned on the host and on the device;
 	// cullKey = what they were computed from (camera, frame, cells, bounds): an unchanged view re-uses them without a copy

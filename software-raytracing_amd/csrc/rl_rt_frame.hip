@@ -157,7 +157,7 @@ static bool EnqueueFrame(RankCtx& R, int q, const DeviceScene& DS, Frame& F, Pen
 		const int blocksPerCU = OccupancyOf(R, traceKernel, &plan);
 		if (blocksPerCU < 0) return false;
 		g_lastTracePlain.store(plan.plain ? 1 : 0, std::memory_order_relaxed);
-		const bool lazy = plan.lazy && !F.views;   // k_trace_lazy: the lit list is its trailing argument, and k_fold_lit follows it
+		const bool lazy = plan.lazy && !F.views;   // k_trace_lazy: the lit list is its trailing argument; its waves fold the list themselves, only the resolve follows
 		g_lastTraceLazy.store(lazy ? 1 : 0, std::memory_order_relaxed);
 		g_lastHitQueue.store(lazy && plan.hitQueue ? 1 : 0, std::memory_order_relaxed);
 		pend.lazy = lazy;
@@ -175,7 +175,6 @@ static bool EnqueueFrame(RankCtx& R, int q, const DeviceScene& DS, Frame& F, Pen
 		const void* resolveKernel = masked ? (const void*)k_resolve_lit : F.resolve;
 		const int depthSlots = P.maxPathLength > 1 ? P.maxPathLength : 1;
 		void* traceArgs[] = { &P, &F.view, &skyRot, &R.samples.ptr, &R.pathStack.ptr, &R.counters.ptr, &R.jobCounter.ptr, lazy ? (void*)&LL : (void*)F.views };
-		void* foldArgs[] = { &F.view, &LL, &R.samples.ptr, (void*)&numSlots };
 		void* resolveArgs[] = { &P, &F.view, &skyRot, &R.samples.ptr, F.resolveArgs[0], F.resolveArgs[1], F.resolveArgs[2], F.resolveArgs[3], masked ? (void*)&LL : F.resolveArgs[4] };
 		for (uint32_t s0 = F.sBegin; s0 < F.sEnd; s0 += batch) {
 			const LaunchPlan L = PlanLaunch(numCells, F.numActive, F.sEnd, s0, R.numCUs, blocksPerCU, plan, F.knobs);
@@ -190,14 +189,14 @@ static bool EnqueueFrame(RankCtx& R, int q, const DeviceScene& DS, Frame& F, Pen
 			if (lazy) {
 				// the lit list: an entry per 32 jobs of the launch (the Cornell frame lights 2 % of its traced paths, 0.7 % of its jobs; a scene that lights more folds the rest in
 				// place) and a chunk per wave on top, because every wave with a lit path holds a chunk of its own, unless RAYLIB_LIT_LIST says otherwise; in whole
-				// chunks; its head and chunk counts are reset behind the job counter
+				// chunks; its chunk counter is reset per launch
 				const uint64_t want = F.knobs.litList >= 0 ? (uint64_t)F.knobs.litList
 				                                           : std::max<uint64_t>(4096, L.jobs / 32) + (uint64_t)L.blocks * (RL_BLOCK / 64) * RL_LIT_CHUNK;
 				const uint32_t chunks = (uint32_t)std::min<uint64_t>(want / RL_LIT_CHUNK, 0x7FFFFFFFu / RL_LIT_CHUNK);
 				if (!R.litList.Grow(std::max<size_t>(1, chunks) * RL_LIT_CHUNK * RL_LIT_STRIDE * sizeof(float4))) return false;
-				if (!R.litCtl.Grow((RL_LIT_CTL + (size_t)chunks) * sizeof(uint32_t))) return false;
+				if (!R.litCtl.Grow(sizeof(uint32_t))) return false;
 				LL.entries = (float*)R.litList.ptr; LL.ctl = R.litCtl.ptr; LL.numChunks = chunks;
-				HIP_OK(hipMemsetAsync(R.litCtl.ptr, 0, (RL_LIT_CTL + (size_t)chunks) * sizeof(uint32_t), R.stream));
+				HIP_OK(hipMemsetAsync(R.litCtl.ptr, 0, sizeof(uint32_t), R.stream));
 				if (masked) {   // a bit per sample of this batch, zeroed behind the resolve that read the last batch's
 					const uint32_t words = (cnt + 31u) / 32u;
 					const size_t bytes = (size_t)words * numSlots * sizeof(uint32_t);
@@ -212,8 +211,6 @@ static bool EnqueueFrame(RankCtx& R, int q, const DeviceScene& DS, Frame& F, Pen
 			HIP_OK(hipEventRecord(R.ev[q][2], R.stream));
 			if (L.jobs > 0)   // (else no cell of this frame sees the scene: the resolve has all it needs)
 				HIP_OK(hipLaunchKernel(traceKernel, dim3(L.blocks), dim3(RL_BLOCK), traceArgs, 0, R.stream));
-			if (L.jobs > 0 && lazy && LL.numChunks > 0)   // the lit paths' samples, before anything reads the sample buffer (traceKernelMs covers both kernels)
-				HIP_OK(hipLaunchKernel((const void*)k_fold_lit, dim3(std::min<uint32_t>((LL.numChunks + 3u) / 4u, (uint32_t)R.numCUs * 8u)), dim3(RL_BLOCK), foldArgs, 0, R.stream));
 			HIP_OK(hipEventRecord(R.ev[q][3], R.stream));
 			HIP_OK(hipLaunchKernel(resolveKernel, dim3(rblocks), dim3(RL_BLOCK), resolveArgs, 0, R.stream));
 			++pend.launches;
