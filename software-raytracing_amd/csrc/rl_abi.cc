@@ -1008,89 +1008,80 @@ int32_t RaylibAMD_MotionHost(uint32_t width, uint32_t height, SceneHandle sh, Ca
 }
 int32_t RaylibAMD_PlanMotion(SceneHandle scene, RaylibAMDQueryPlan* out) { return RaylibAMD_PlanGBuffer(scene, out); }
 
-// RaylibAMD_TemporalAccumulate / ...Device / ...Host (statements T7 and T8): the refusals every entry shares
-static bool TemporalArgsValid(const char* who, uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
-                              const RaylibAMDMotion* motion, const RaylibAMDTemporalFrame* history, const float* outColour, const float* outLength)
+// RaylibAMD_TemporalAccumulate / ...Device / ...Host (statements T7 and T8) and RaylibAMD_TemporalAccumulateMoments / ...Device / ...Host (statements S1 and
+// S2): one description of the call (rl_host.h TemporalCall), which every entry fills from its arguments, and the refusals all six share -- the moments' own
+// null pointers first, then T8's list; an output that is one of the history's planes: outColour or outLength in place in the plain call, any of the three
+// outputs and any of the four planes in the moments call
+static RaylibAMDTemporalMomentsFrame History3(const RaylibAMDTemporalFrame* h)
 {
-	if (!params || !colour || !hit || !motion || !outColour || !outLength || (history && (!history->colour || !history->hit || !history->length))) {
+	return h ? RaylibAMDTemporalMomentsFrame{ h->colour, h->hit, h->length, nullptr } : RaylibAMDTemporalMomentsFrame{};
+}
+static RaylibAMDTemporalMomentsFrame History4(const RaylibAMDTemporalMomentsFrame* h) { return h ? *h : RaylibAMDTemporalMomentsFrame{}; }
+static bool TemporalArgsValid(const char* who, const TemporalCall& C)
+{
+	const RaylibAMDTemporalMomentsFrame& h = C.history;
+	if (C.moments && (!C.outMoments || (C.hasHistory && !h.moments))) { Log("%s: null argument", who); return false; }
+	if (!C.params || !C.colour || !C.hit || !C.motion || !C.outColour || !C.outLength || (C.hasHistory && (!h.colour || !h.hit || !h.length))) {
 		Log("%s: null argument", who); return false;
 	}
-	const uint64_t pixels = (uint64_t)width * height;
-	if (pixels == 0 || pixels > 0x7fffffffull) { Log("%s: a frame of %u x %u pixels (1 .. 2^31 - 1)", who, width, height); return false; }
-	if (!std::isfinite(params->depthTolerance) || params->depthTolerance < 0.0f) { Log("%s: depthTolerance %g is not a finite number >= 0", who, params->depthTolerance); return false; }
-	if (!std::isfinite(params->maxLength) || params->maxLength < 1.0f) { Log("%s: maxLength %g is not a finite number >= 1", who, params->maxLength); return false; }
-	if (history && (outColour == history->colour || outLength == history->length)) {
-		Log("%s: an output plane is one of the history's: the taps read neighbours, in place is a race", who); return false;
-	}
+	const uint64_t pixels = (uint64_t)C.width * C.height;
+	if (pixels == 0 || pixels > 0x7fffffffull) { Log("%s: a frame of %u x %u pixels (1 .. 2^31 - 1)", who, C.width, C.height); return false; }
+	if (!std::isfinite(C.params->depthTolerance) || C.params->depthTolerance < 0.0f) { Log("%s: depthTolerance %g is not a finite number >= 0", who, C.params->depthTolerance); return false; }
+	if (!std::isfinite(C.params->maxLength) || C.params->maxLength < 1.0f) { Log("%s: maxLength %g is not a finite number >= 1", who, C.params->maxLength); return false; }
+	bool inPlace = C.hasHistory && (C.outColour == h.colour || C.outLength == h.length);
+	if (C.hasHistory && C.moments)
+		for (const void* o : { (const void*)C.outColour, (const void*)C.outLength, (const void*)C.outMoments })
+			for (const void* p : { (const void*)h.colour, (const void*)h.hit, (const void*)h.length, (const void*)h.moments }) inPlace |= o == p;
+	if (inPlace) { Log("%s: an output plane is one of the history's: the taps read neighbours, in place is a race", who); return false; }
 	return true;
 }
-static int32_t TemporalInternal(const char* who, uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
-                                const RaylibAMDMotion* motion, const RaylibAMDTemporalFrame* history, float* outColour, float* outLength, bool hostMem, void* stream)
+static int32_t TemporalInternal(const char* who, const TemporalCall& C, bool hostMem, void* stream)
 {
-	if (!TemporalArgsValid(who, width, height, params, colour, hit, motion, history, outColour, outLength)) return 0;
-	return RunOnDevice(stream, [&](RaylibAMDStats& stats) {
-		return DeviceTemporalAccumulate(width, height, *params, colour, hit, motion, history, outColour, outLength, hostMem, stream, stats);
-	});
+	if (!TemporalArgsValid(who, C)) return 0;
+	return RunOnDevice(stream, [&](RaylibAMDStats& stats) { return DeviceTemporalAccumulate(C, hostMem, stream, stats); });
+}
+static int32_t TemporalHostInternal(const char* who, const TemporalCall& C)
+{
+	if (!TemporalArgsValid(who, C)) return 0;
+	TemporalAccumulateHost(C);
+	return 1;
 }
 int32_t RaylibAMD_TemporalAccumulate(uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
                                      const RaylibAMDMotion* motion, const RaylibAMDTemporalFrame* history, float* outColour, float* outLength)
 {
-	return TemporalInternal("RaylibAMD_TemporalAccumulate", width, height, params, colour, hit, motion, history, outColour, outLength, true, nullptr);
+	return TemporalInternal("RaylibAMD_TemporalAccumulate",
+	                        { width, height, params, colour, hit, motion, history != nullptr, History3(history), outColour, outLength, nullptr, false }, true, nullptr);
 }
 int32_t RaylibAMD_TemporalAccumulateDevice(uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
                                            const RaylibAMDMotion* motion, const RaylibAMDTemporalFrame* history, float* outColour, float* outLength, void* stream)
 {
-	return TemporalInternal("RaylibAMD_TemporalAccumulateDevice", width, height, params, colour, hit, motion, history, outColour, outLength, false, stream);
+	return TemporalInternal("RaylibAMD_TemporalAccumulateDevice",
+	                        { width, height, params, colour, hit, motion, history != nullptr, History3(history), outColour, outLength, nullptr, false }, false, stream);
 }
 int32_t RaylibAMD_TemporalAccumulateHost(uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
                                          const RaylibAMDMotion* motion, const RaylibAMDTemporalFrame* history, float* outColour, float* outLength)
 {
-	if (!TemporalArgsValid("RaylibAMD_TemporalAccumulateHost", width, height, params, colour, hit, motion, history, outColour, outLength)) return 0;
-	TemporalAccumulateHost(width, height, *params, colour, hit, motion, history, outColour, outLength);
-	return 1;
-}
-
-// RaylibAMD_TemporalAccumulateMoments / ...Device / ...Host (statements S1 and S2): T8's refusals on the frame's first three planes, then the moments' own
-static bool TemporalMomentsArgsValid(const char* who, uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
-                                     const RaylibAMDMotion* motion, const RaylibAMDTemporalMomentsFrame* history, const float* outColour, const float* outLength, const float* outMoments)
-{
-	const RaylibAMDTemporalFrame three = { history ? history->colour : nullptr, history ? history->hit : nullptr, history ? history->length : nullptr };
-	if (!outMoments || (history && !history->moments)) { Log("%s: null argument", who); return false; }
-	if (!TemporalArgsValid(who, width, height, params, colour, hit, motion, history ? &three : nullptr, outColour, outLength)) return false;
-	if (history)
-		for (const void* o : { (const void*)outColour, (const void*)outLength, (const void*)outMoments })
-			for (const void* h : { (const void*)history->colour, (const void*)history->hit, (const void*)history->length, (const void*)history->moments })
-				if (o == h) { Log("%s: an output plane is one of the history's: the taps read neighbours, in place is a race", who); return false; }
-	return true;
-}
-static int32_t TemporalMomentsInternal(const char* who, uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
-                                       const RaylibAMDMotion* motion, const RaylibAMDTemporalMomentsFrame* history, float* outColour, float* outLength, float* outMoments, bool hostMem,
-                                       void* stream)
-{
-	if (!TemporalMomentsArgsValid(who, width, height, params, colour, hit, motion, history, outColour, outLength, outMoments)) return 0;
-	const RaylibAMDTemporalFrame three = { history ? history->colour : nullptr, history ? history->hit : nullptr, history ? history->length : nullptr };
-	return RunOnDevice(stream, [&](RaylibAMDStats& stats) {
-		return DeviceTemporalAccumulate(width, height, *params, colour, hit, motion, history ? &three : nullptr, outColour, outLength, hostMem, stream, stats,
-		                                history ? history->moments : nullptr, outMoments);
-	});
+	return TemporalHostInternal("RaylibAMD_TemporalAccumulateHost",
+	                        { width, height, params, colour, hit, motion, history != nullptr, History3(history), outColour, outLength, nullptr, false });
 }
 int32_t RaylibAMD_TemporalAccumulateMoments(uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
                                             const RaylibAMDMotion* motion, const RaylibAMDTemporalMomentsFrame* history, float* outColour, float* outLength, float* outMoments)
 {
-	return TemporalMomentsInternal("RaylibAMD_TemporalAccumulateMoments", width, height, params, colour, hit, motion, history, outColour, outLength, outMoments, true, nullptr);
+	return TemporalInternal("RaylibAMD_TemporalAccumulateMoments",
+	                        { width, height, params, colour, hit, motion, history != nullptr, History4(history), outColour, outLength, outMoments, true }, true, nullptr);
 }
 int32_t RaylibAMD_TemporalAccumulateMomentsDevice(uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
                                                   const RaylibAMDMotion* motion, const RaylibAMDTemporalMomentsFrame* history, float* outColour, float* outLength, float* outMoments,
                                                   void* stream)
 {
-	return TemporalMomentsInternal("RaylibAMD_TemporalAccumulateMomentsDevice", width, height, params, colour, hit, motion, history, outColour, outLength, outMoments, false, stream);
+	return TemporalInternal("RaylibAMD_TemporalAccumulateMomentsDevice",
+	                        { width, height, params, colour, hit, motion, history != nullptr, History4(history), outColour, outLength, outMoments, true }, false, stream);
 }
 int32_t RaylibAMD_TemporalAccumulateMomentsHost(uint32_t width, uint32_t height, const RaylibAMDTemporalParams* params, const float* colour, const RaylibAMDHitT* hit,
                                                 const RaylibAMDMotion* motion, const RaylibAMDTemporalMomentsFrame* history, float* outColour, float* outLength, float* outMoments)
 {
-	if (!TemporalMomentsArgsValid("RaylibAMD_TemporalAccumulateMomentsHost", width, height, params, colour, hit, motion, history, outColour, outLength, outMoments)) return 0;
-	TemporalAccumulateMomentsHost(width, height, *params, colour, hit, motion, history, outColour, outLength, outMoments);
-	return 1;
+	return TemporalHostInternal("RaylibAMD_TemporalAccumulateMomentsHost",
+	                        { width, height, params, colour, hit, motion, history != nullptr, History4(history), outColour, outLength, outMoments, true });
 }
 
 // RaylibAMD_FilterVariance / ...Device / ...Host (statements S3 to S7): the refusals every entry shares; `use` receives the caller's parameters or the defaults

@@ -280,11 +280,18 @@ bool DeviceRenderGBuffer(Scene& scene, const RendererSettings& settings, const D
 // DeviceRenderGBuffer expects of the ABI, and: a plane is asked for, the range lies in the scene's triangles, positions are given when count > 0.
 bool DeviceRenderMotion(Scene& scene, const RendererSettings& settings, const DCamera& camera, const DCamera& prevCamera, uint64_t seed, int32_t first, int32_t count,
                         const float* prevPositions, const RaylibAMDMotionPlanes& planes, bool hostMem, void* stream, RaylibAMDStats& stats);
-// RaylibAMD_TemporalAccumulate (hostMem) and RaylibAMD_TemporalAccumulateDevice on rank 0's device, behind frames in flight (stream: as DeviceTraceRays).  history
-// is null or has three planes; the frame has 1 .. 2^31 - 1 pixels, the parameters are in range, no output is a history plane: the ABI checked.
-bool DeviceTemporalAccumulate(uint32_t width, uint32_t height, const RaylibAMDTemporalParams& params, const float* colour, const RaylibAMDHitT* hit, const RaylibAMDMotion* motion,
-                              const RaylibAMDTemporalFrame* history, float* outColour, float* outLength, bool hostMem, void* stream, RaylibAMDStats& stats,
-                              const float* histMoments = nullptr, float* outMoments = nullptr);
+// An accumulation call as its entry got it, RaylibAMD_TemporalAccumulate's (moments false: history.moments and outMoments are null and not looked at) or
+// RaylibAMD_TemporalAccumulateMoments's.  hasHistory false: the first frame, `history` is all null.
+struct TemporalCall {
+	uint32_t width, height; const RaylibAMDTemporalParams* params;
+	const float* colour; const RaylibAMDHitT* hit; const RaylibAMDMotion* motion;
+	bool hasHistory; RaylibAMDTemporalMomentsFrame history;
+	float *outColour, *outLength, *outMoments;
+	bool moments;
+};
+// RaylibAMD_TemporalAccumulate[Moments] (hostMem) and ...Device on rank 0's device, behind frames in flight (stream: as DeviceTraceRays).  The history's planes
+// are all given, the frame has 1 .. 2^31 - 1 pixels, the parameters are in range, no output is a history plane: the ABI checked.
+bool DeviceTemporalAccumulate(const TemporalCall& call, bool hostMem, void* stream, RaylibAMDStats& stats);
 // RaylibAMD_FilterVariance (hostMem) and RaylibAMD_FilterVarianceDevice, under the same rules.  params: the caller's or the defaults, checked.
 bool DeviceFilterVariance(uint32_t width, uint32_t height, const RaylibAMDVarianceFilterParams& params, const RaylibAMDVarianceFilterPlanes& planes, float* outColour,
                           float* outVariance, bool hostMem, void* stream, RaylibAMDStats& stats);

@@ -316,29 +316,22 @@ void MotionHost(uint32_t width, uint32_t height, const DCamera& pc, int32_t firs
 
 // Statement T7 (rl_temporal.h, the kernel's own source) per pixel; MOMENTS: with statement S1 beside it
 template <bool MOMENTS>
-static void TemporalPixelsHost(uint32_t width, uint32_t height, const RaylibAMDTemporalParams& params, const float* colour, const RaylibAMDHitT* hit, const RaylibAMDMotion* motion,
-                               const HostTaps& taps, float* outColour, float* outLength, float* outMoments)
+static void TemporalPixelsHost(const TemporalCall& C)
 {
-	for (size_t p = 0; p < (size_t)width * height; ++p) {
+	const HostTaps taps = { C.history.colour, C.history.hit, C.history.length, C.history.moments };
+	for (size_t p = 0; p < (size_t)C.width * C.height; ++p) {
 		RaylibAMDHitT h; RaylibAMDMotion m; float c[3], o[4], len, mom[2];
-		memcpy(&h, hit + p, sizeof(h)); memcpy(&m, motion + p, sizeof(m)); memcpy(c, colour + 4 * p, sizeof(c));
-		TemporalPixelM<MOMENTS>(width, height, c, h.prim, m.prevX, m.prevY, m.prevT, m.status, params.depthTolerance, params.maxLength, taps, o, len, mom);
+		memcpy(&h, C.hit + p, sizeof(h)); memcpy(&m, C.motion + p, sizeof(m)); memcpy(c, C.colour + 4 * p, sizeof(c));
+		TemporalPixelM<MOMENTS>(C.width, C.height, c, h.prim, m.prevX, m.prevY, m.prevT, m.status, C.params->depthTolerance, C.params->maxLength, taps, o, len, mom);
 		o[3] = 1.0f;
-		memcpy(outColour + 4 * p, o, sizeof(o)); memcpy(outLength + p, &len, sizeof(len));
-		if (MOMENTS) memcpy(outMoments + 2 * p, mom, sizeof(mom));
+		memcpy(C.outColour + 4 * p, o, sizeof(o)); memcpy(C.outLength + p, &len, sizeof(len));
+		if (MOMENTS) memcpy(C.outMoments + 2 * p, mom, sizeof(mom));
 	}
 }
-void TemporalAccumulateHost(uint32_t width, uint32_t height, const RaylibAMDTemporalParams& params, const float* colour, const RaylibAMDHitT* hit, const RaylibAMDMotion* motion,
-                            const RaylibAMDTemporalFrame* history, float* outColour, float* outLength)
+void TemporalAccumulateHost(const TemporalCall& C)
 {
-	const HostTaps taps = { history ? history->colour : nullptr, history ? history->hit : nullptr, history ? history->length : nullptr, nullptr };
-	TemporalPixelsHost<false>(width, height, params, colour, hit, motion, taps, outColour, outLength, nullptr);
-}
-void TemporalAccumulateMomentsHost(uint32_t width, uint32_t height, const RaylibAMDTemporalParams& params, const float* colour, const RaylibAMDHitT* hit, const RaylibAMDMotion* motion,
-                                   const RaylibAMDTemporalMomentsFrame* history, float* outColour, float* outLength, float* outMoments)
-{
-	const HostTaps taps = { history ? history->colour : nullptr, history ? history->hit : nullptr, history ? history->length : nullptr, history ? history->moments : nullptr };
-	TemporalPixelsHost<true>(width, height, params, colour, hit, motion, taps, outColour, outLength, outMoments);
+	if (C.moments) TemporalPixelsHost<true>(C);
+	else TemporalPixelsHost<false>(C);
 }
 
 // Statements S3 to S6 (rl_variance.h, the kernels' own source): the packed records the device makes, then the same per-pixel functions in the same order of

@@ -56,10 +56,8 @@ void BakeDistanceFieldHost(const Scene& s, const RaylibAMDDistanceFieldParams& G
 // prevCamera: the previous frame's camera (the current one when the caller names none); first, count, prevPositions: the parameters'
 void MotionHost(uint32_t width, uint32_t height, const DCamera& prevCamera, int32_t first, int32_t count, const float* prevPositions, const float* rays, const RaylibAMDHitT* hit,
                 RaylibAMDMotion* outMotion);
-void TemporalAccumulateHost(uint32_t width, uint32_t height, const RaylibAMDTemporalParams& params, const float* colour, const RaylibAMDHitT* hit, const RaylibAMDMotion* motion,
-                            const RaylibAMDTemporalFrame* history, float* outColour, float* outLength);
-void TemporalAccumulateMomentsHost(uint32_t width, uint32_t height, const RaylibAMDTemporalParams& params, const float* colour, const RaylibAMDHitT* hit, const RaylibAMDMotion* motion,
-                                   const RaylibAMDTemporalMomentsFrame* history, float* outColour, float* outLength, float* outMoments);
+// both accumulations' entries: call.moments says which
+void TemporalAccumulateHost(const TemporalCall& call);
 // P: the caller's parameters or the defaults; planes: all five given.  False: no memory for the packed planes (nothing written)
 bool FilterVarianceHost(uint32_t width, uint32_t height, const RaylibAMDVarianceFilterParams& P, const RaylibAMDVarianceFilterPlanes& planes, float* outColour, float* outVariance);
 void GatherAdaptiveDecideHost(const RaylibAMDGatherAdaptiveParams& adaptive, uint32_t cap, const float* keys, int64_t count, uint32_t* outSamples);

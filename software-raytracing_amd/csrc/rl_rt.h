@@ -6,7 +6,7 @@
 //   rl_rt_render.hip  whole frames over N ranks (gather, scatter, two frames in flight), DeviceRender, progressive sessions
 //   rl_rt_rays.hip    caller rays, points and triangles, and the camera's pixels: the queries (DeviceRenderGBuffer, DeviceRenderMotion, DeviceTraceRays, DeviceTraceRaysAll, DeviceNearestPoints, DeviceNearestPointsAll, DeviceSweepSpheres, DeviceOverlapTriangles
 //                     and its contacts, DeviceOverlapBoxes: one driver, RunQuery), DeviceBakeDistanceField on the same pieces, DeviceTraceRadiance, DeviceGather (plain and adaptive: one driver, GatherLocked),
-//                     DeviceTemporalAccumulate (planes in, planes out: no scene)
+//                     the plane calls (DeviceTemporalAccumulate, DeviceFilterVariance: planes in, planes out, no scene; one driver, RunPlanes)
 //   rl_rt_lightmap.hip  lightmaps: DeviceLightmapPoints, DeviceBakeLightmap (the raster stages, then DeviceGather's body or the caller's atlas, the filter, the atlas stages)
 //   rl_rt_move.hip    RaylibAMD_SceneMoveTriangles: the moved records and the refit of every tree on the device, the host copies' read-back, RaylibAMD_SceneCheckTrees
 //   rl_rt_hooks.hip   test hooks

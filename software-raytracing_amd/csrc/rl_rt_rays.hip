@@ -1,13 +1,15 @@
 // Host runtime: calls on rays, points and triangles of the caller's, on rank 0's device -- from host memory or from device pointers, on the library's stream
-// (synchronous, with stats) or enqueued on a stream of the caller's (rl_host.h).  Two families and what they share:
+// (synchronous, with stats) or enqueued on a stream of the caller's (rl_host.h).  Three families and what they share:
 //   The queries -- the camera's G-buffer, ray, ordered multi-hit, nearest-point, K-nearest, swept-sphere and triangle-overlap queries with their contacts -- are one call (RunQuery) that each entry
 //   describes by data (QueryDesc: plan, kernel, input records, outputs, dynamic LDS) and gives its launch; a distance-field bake is several launches on the
 //   same pieces.  Their scratch is a ring of work counters with an event per slot (LaunchOnRing).
 //   The path calls -- radiance along caller rays, and the gathers, which are that call with another generator -- share BeginPathCall and PathGrid, one counter
 //   and one path stack ordered by radEv.  A plain and an adaptive gather are one driver (GatherLocked): one prologue, one launch -- counter, event pair,
 //   k_gather, the launch's resolve --, one tail; a plain call loops over its cut's launches, an adaptive call over its passes of a shrinking, compacted set.
-//   Both share the refusals of a device call's pointers (DevicePointersOk), the staging of a host call through qRays / qOut, the grid that fills the device
-//   once (FillingGrid), the stats' header, and a synchronous call's counter block, event pair and tail (BeginSync, FinishSync).
+//   The plane calls -- the temporal accumulations and the variance-guided filter: planes in, planes out, no scene, no plan, no work counter -- are one call
+//   (RunPlanes) that each entry describes by data (PlaneCall: the planes read and written) and gives what it prepares and what it launches.
+//   All share the refusals of a device call's pointers (DevicePointersOk), the staging of a host call through qRays / qOut (StageOutputs), and a synchronous
+//   call's counter block, event pair and tail (BeginSync, FinishSync); the first two also the grid that fills the device once (FillingGrid) and the stats' header.
 #include "rl_rt.h"
 
 namespace rl {
@@ -135,15 +137,23 @@ bool OnDevice(const void* p, int device)
 // the device pointer the kernel gets (null for an output that is not written).
 #define RL_QUERY_OUTS 7   /* the outputs a call may have: a G-buffer's planes (most calls have one to three) */
 struct QueryOut { void* user = nullptr; size_t bytes = 0; uintptr_t align = 3u; DevBuf<void> RankCtx::* stage = nullptr; void* dev = nullptr; };
-// The refusals of a device call (`api`): the input (`what` names its records; null: the call has none) and every output the call writes are memory of the
-// device; the kernels read an input record as 16-byte loads (inAlign 15; 3: as 4-byte words); every output pointer given, written or not, is aligned as its
-// records are stored.
-static bool DevicePointersOk(const char* api, const char* what, int device, const void* in, const QueryOut* outs, size_t numOuts, uintptr_t inAlign = 15u)
+// An input of a call: the caller's pointer; the bytes the call reads there (0: none -- such an input is not checked, not staged, and null on the device); the
+// mask of its alignment (15: the kernels read it as 16-byte loads, 7: as 8-byte pairs, 3: as 4-byte words).
+struct CallIn { const void* user = nullptr; size_t bytes = 0; uintptr_t align = 15u; };
+// The refusals of a device call (`api`): every input the call reads (`what` names a query's records; null: planes) and every output it writes are memory of
+// the device; every input read is aligned as the kernels load it; every output pointer given, written or not, is aligned as its records are stored.
+static bool DevicePointersOk(const char* api, const char* what, int device, const CallIn* ins, size_t numIns, const QueryOut* outs, size_t numOuts)
 {
-	bool onDevice = !what || OnDevice(in, device);
+	bool onDevice = true;
+	for (size_t k = 0; k < numIns; ++k) if (ins[k].bytes && !OnDevice(ins[k].user, device)) onDevice = false;
 	for (size_t k = 0; k < numOuts; ++k) if (outs[k].bytes && !OnDevice(outs[k].user, device)) onDevice = false;
 	if (!onDevice) { Log("%s: a pointer is not device memory of device %d", api, device); return false; }
-	if (what && ((uintptr_t)in & inAlign) != 0) { Log("%s: the %s are not %u-byte aligned", api, what, (unsigned)inAlign + 1u); return false; }
+	for (size_t k = 0; k < numIns; ++k) {
+		if (!ins[k].bytes || ((uintptr_t)ins[k].user & ins[k].align) == 0) continue;
+		if (what) Log("%s: the %s are not %u-byte aligned", api, what, (unsigned)ins[k].align + 1u);
+		else Log("%s: an input plane is not %u-byte aligned", api, (unsigned)ins[k].align + 1u);
+		return false;
+	}
 	for (size_t k = 0; k < numOuts; ++k)
 		if (((uintptr_t)outs[k].user & outs[k].align) != 0) { Log("%s: the output is not %u-byte aligned", api, (unsigned)outs[k].align + 1u); return false; }
 	return true;
@@ -331,7 +341,8 @@ static bool RunQuery(Scene& sc, QueryDesc& D, RaylibAMDStats& stats, Launch laun
 	RankCtx& R = Rank0();
 	HIP_OK(hipSetDevice(R.device));
 	if (!D.plan.ok) { Log("%s: BVH depth %u exceeds the traversal stack (64)", D.api, sc.bvh.depth); return false; }
-	if (!D.hostMem && D.n > 0 && !DevicePointersOk(D.apiDevice, D.what, R.device, D.in, D.out, RL_QUERY_OUTS, D.inAlign)) return false;
+	const CallIn in = { D.in, D.inBytes, D.inAlign };
+	if (!D.hostMem && D.n > 0 && !DevicePointersOk(D.apiDevice, D.what, R.device, &in, 1, D.out, RL_QUERY_OUTS)) return false;
 	QueryCall U;
 	if (!BeginQueryCall(sc, R, D.plan, D.slotIndex, D.stream, U, stats)) return false;
 	if (D.exportSlot && !EnsureExportSlot(U.Cp, sc)) return false;
@@ -386,27 +397,37 @@ static GBufferKernel GBufferKernelOf(const QueryPlan& p)
 	return p.prims ? (GBufferKernel)k_gbuffer<2, 64, true> : (GBufferKernel)k_gbuffer<2, 64, false>;
 }
 static_assert(sizeof(RaylibAMDGBufferPlanes) == 7 * sizeof(void*) && RL_QUERY_OUTS >= 7, "a G-buffer's planes are the call's outputs");
+// a frame of W x H pixels in 8 x 8 cells, a wave's worth each: the shape members of DGBuffer and DTemporal
+template <typename Frame>
+static void SetFrameShape(Frame& F, uint32_t W, uint32_t H)
+{
+	F.width = W; F.height = H; F.cellsX = (W + 7u) / 8u; F.numCells = F.cellsX * ((H + 7u) / 8u);
+}
+// a G-buffer or motion call's record without its planes and their mask
+static DGBuffer MakeGBuffer(const RendererSettings& settings, const DCamera& camera, uint64_t seed)
+{
+	DGBuffer G; memset(&G, 0, sizeof(G));
+	G.camera = camera; G.seed = seed; G.rayTMin = settings.rayTMin;
+	SetFrameShape(G, settings.viewportWidth, settings.viewportHeight);
+	return G;
+}
 bool DeviceRenderGBuffer(Scene& sc, const RendererSettings& settings, const DCamera& camera, uint64_t seed, const RaylibAMDGBufferPlanes& planes, bool hostMem, void* stream,
                          RaylibAMDStats& stats)
 {
-	const uint32_t W = settings.viewportWidth, H = settings.viewportHeight;
-	const size_t pixels = (size_t)W * H;   // (1 .. 2^31 - 1: the ABI checked)
+	const size_t pixels = (size_t)settings.viewportWidth * settings.viewportHeight;   // (1 .. 2^31 - 1: the ABI checked)
 	QueryDesc D("RaylibAMD_RenderGBuffer", "RaylibAMD_RenderGBufferDevice", nullptr, nullptr, 0, (int32_t)pixels, hostMem, stream);
 	D.plan = PlanGBuffer(sc, ReadRenderKnobs());
 	const GBufferKernel kernel = GBufferKernelOf(D.plan);
 	D.kernel = (const void*)kernel;
 	void* const user[7] = { planes.hit, planes.surface, planes.albedo, planes.surfaceNormal, planes.microNormal, planes.texcoord, planes.emission };
 	DevBuf<void> RankCtx::* const stage[7] = { &RankCtx::qOut, &RankCtx::qPrim, &RankCtx::qContact, &RankCtx::qPlane3, &RankCtx::qPlane4, &RankCtx::qPlane5, &RankCtx::qPlane6 };
-	DGBuffer G; memset(&G, 0, sizeof(G));
+	DGBuffer G = MakeGBuffer(settings, camera, seed);
 	for (int k = 0; k < 7; ++k) {
 		const bool surface = k == 1;
 		D.out[k] = { user[k], user[k] ? pixels * (surface ? sizeof(DHitOut) : sizeof(float4)) : 0, surface ? 3u : 15u, stage[k] };
 		if (user[k]) G.mask |= 1u << k;
 	}
 	D.slotIndex = planes.hit != nullptr;
-	G.camera = camera; G.seed = seed;
-	G.width = W; G.height = H; G.cellsX = (W + 7u) / 8u; G.numCells = G.cellsX * ((H + 7u) / 8u);
-	G.rayTMin = settings.rayTMin;
 	const bool ok = RunQuery(sc, D, stats, [&](const QueryLaunch& L) {
 		G.hit = (float4*)L.out[0]; G.surface = (DHitOut*)L.out[1];
 		G.albedo = (float4*)L.out[2]; G.surfaceNormal = (float4*)L.out[3]; G.microNormal = (float4*)L.out[4]; G.texcoord = (float4*)L.out[5]; G.emission = (float4*)L.out[6];
@@ -433,8 +454,7 @@ static_assert(sizeof(RaylibAMDMotion) == sizeof(float4), "motion records");
 bool DeviceRenderMotion(Scene& sc, const RendererSettings& settings, const DCamera& camera, const DCamera& prevCamera, uint64_t seed, int32_t first, int32_t count,
                         const float* prevPositions, const RaylibAMDMotionPlanes& planes, bool hostMem, void* stream, RaylibAMDStats& stats)
 {
-	const uint32_t W = settings.viewportWidth, H = settings.viewportHeight;
-	const size_t pixels = (size_t)W * H;   // (1 .. 2^31 - 1: the ABI checked)
+	const size_t pixels = (size_t)settings.viewportWidth * settings.viewportHeight;   // (1 .. 2^31 - 1: the ABI checked)
 	QueryDesc D("RaylibAMD_RenderMotion", "RaylibAMD_RenderMotionDevice", count > 0 ? "previous positions" : nullptr, count > 0 ? prevPositions : nullptr, 0, (int32_t)pixels,
 	            hostMem, stream);
 	D.inBytes = (size_t)count * 9u * sizeof(float); D.inAlign = 3u;
@@ -444,11 +464,8 @@ bool DeviceRenderMotion(Scene& sc, const RendererSettings& settings, const DCame
 	D.out[0] = { planes.hit, planes.hit ? pixels * sizeof(float4) : 0, 15u, &RankCtx::qOut };
 	D.out[1] = { planes.motion, planes.motion ? pixels * sizeof(float4) : 0, 15u, &RankCtx::qPrim };
 	D.slotIndex = true;
-	DGBuffer G; memset(&G, 0, sizeof(G));
+	DGBuffer G = MakeGBuffer(settings, camera, seed);
 	G.mask = planes.hit ? RL_GB_HIT : 0u;
-	G.camera = camera; G.seed = seed;
-	G.width = W; G.height = H; G.cellsX = (W + 7u) / 8u; G.numCells = G.cellsX * ((H + 7u) / 8u);
-	G.rayTMin = settings.rayTMin;
 	DMotion M; memset(&M, 0, sizeof(M));
 	M.prevCamera = prevCamera; M.first = first; M.count = count;
 	const bool ok = RunQuery(sc, D, stats, [&](const QueryLaunch& L) {
@@ -460,152 +477,155 @@ bool DeviceRenderMotion(Scene& sc, const RendererSettings& settings, const DCame
 	return ok;
 }
 
-// A temporal accumulation (RaylibAMD_TemporalAccumulate, statements T7 and T8): no scene, no plan, no work counter -- planes in, planes out, on rank 0's
-// device.  A host call stages its inputs back to back in qRays (every plane's size is a multiple of 16 bytes but the moments', a multiple of 8, and the length
-// plane's, which come last in that order) and its outputs through qOut, qPrim and qContact.  A synchronous call brackets the kernel with the queries' event
-// pair.  outMoments (RaylibAMD_TemporalAccumulateMoments, statements S1 and S2): k_temporal_moments with the history's moments and that output beside the rest.
-static_assert(sizeof(RaylibAMDHitT) == sizeof(float4), "hit records");
-bool DeviceTemporalAccumulate(uint32_t W, uint32_t H, const RaylibAMDTemporalParams& params, const float* colour, const RaylibAMDHitT* hit, const RaylibAMDMotion* motion,
-                              const RaylibAMDTemporalFrame* history, float* outColour, float* outLength, bool hostMem, void* stream, RaylibAMDStats& stats,
-                              const float* histMoments, float* outMoments)
-{
-	const char* api = outMoments ? "RaylibAMD_TemporalAccumulateMoments" : "RaylibAMD_TemporalAccumulate";
+// ---- the plane calls: one call, described by data ----
+// What an entry says of its call: planes in, planes out, on rank 0's device -- no scene, no plan, no work counter.  Made first in the entry, as a QueryDesc:
+// the clock starts and the runtime lock is taken there.  api / apiDevice: the entry's names in the log; in: the planes read, in the order the launch gets
+// them and a host call stages them; out: the planes written; launches: what a synchronous call reports when it is more than one.
+#define RL_PLANE_INS 7
+#define RL_PLANE_OUTS 3
+struct PlaneCall {
 	const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
 	const std::lock_guard<std::mutex> lock{ Rt().lock };
+	const char *api, *apiDevice;
+	uint32_t W, H; bool hostMem; void* stream;
+	CallIn in[RL_PLANE_INS];
+	QueryOut out[RL_PLANE_OUTS];
+	uint32_t launches = 1;
+	PlaneCall(const char* api_, const char* apiDevice_, uint32_t W_, uint32_t H_, bool hostMem_, void* stream_)
+		: api(api_), apiDevice(apiDevice_), W(W_), H(H_), hostMem(hostMem_), stream(stream_) {}
+	size_t Pixels() const { return (size_t)W * H; }   // (1 .. 2^31 - 1: the ABI checked)
+};
+// what the entry's launch gets: the rank, the planes on the device (null: not read, not written) and the stream
+struct PlaneLaunch { RankCtx& R; const void* in[RL_PLANE_INS]; void* out[RL_PLANE_OUTS]; hipStream_t st; };
+// The call.  A device call's refusals come first; then `prepare(R, behind)` grows the entry's scratch, asks what its grid needs and may name in `behind` an
+// event the stream has to wait for -- all of it before anything is enqueued.  A host call's inputs are copied back to back into qRays in the entry's order,
+// which therefore lists them by descending alignment (16-byte planes, 8-byte pairs, 4-byte words: every plane's size is a multiple of its own alignment); an
+// entry that does not is refused here, on the host.  A synchronous call's event pair brackets the launches alone; `launch(L)` enqueues them and asks
+// hipGetLastError behind each (false: it failed, and said so); the outputs of a host call are copied back where the caller gave them.
+template <typename Prepare, typename Launch>
+static bool RunPlanes(PlaneCall& P, RaylibAMDStats& stats, Prepare prepare, Launch launch)
+{
 	if (!EnsureRuntime()) return false;
 	RankCtx& R = Rank0();
 	HIP_OK(hipSetDevice(R.device));
-	const size_t pixels = (size_t)W * H, plane = pixels * sizeof(float4), lengths = pixels * sizeof(float), pairs = pixels * sizeof(float2);
-	const void* in[7] = { colour, hit, motion, history ? history->colour : nullptr, history ? (const void*)history->hit : nullptr, history ? histMoments : nullptr,
-	                      history ? history->length : nullptr };
-	const size_t inBytes[7] = { plane, plane, plane, history ? plane : 0, history ? plane : 0, history && outMoments ? pairs : 0, history ? lengths : 0 };
-	const uintptr_t inAlign[7] = { 15u, 15u, 15u, 15u, 15u, 7u, 3u };
-	QueryOut out[3] = { { outColour, plane, 15u, &RankCtx::qOut }, { outLength, lengths, 3u, &RankCtx::qPrim }, { outMoments, outMoments ? pairs : 0, 7u, &RankCtx::qContact } };
-	if (!hostMem) {
-		bool onDevice = true;
-		for (int k = 0; k < 7; ++k) if (inBytes[k] && !OnDevice(in[k], R.device)) onDevice = false;
-		if (!onDevice) { Log("%sDevice: a pointer is not device memory of device %d", api, R.device); return false; }
-		for (int k = 0; k < 7; ++k)
-			if (inBytes[k] && ((uintptr_t)in[k] & inAlign[k]) != 0) { Log("%sDevice: an input plane is not %u-byte aligned", api, (unsigned)inAlign[k] + 1u); return false; }
-		if (!DevicePointersOk(outMoments ? "RaylibAMD_TemporalAccumulateMomentsDevice" : "RaylibAMD_TemporalAccumulateDevice", nullptr, R.device, nullptr, out, 3)) return false;
-	}
-	const hipStream_t st = stream ? (hipStream_t)stream : R.stream;
-	const bool sync = !stream;
+	if (!P.hostMem && !DevicePointersOk(P.apiDevice, nullptr, R.device, P.in, RL_PLANE_INS, P.out, RL_PLANE_OUTS)) return false;
+	const hipStream_t st = P.stream ? (hipStream_t)P.stream : R.stream;
+	const bool sync = !P.stream;
 	if (sync && !EnsureSyncStats(R)) return false;
 	memset(&stats, 0, sizeof(stats));
 	stats.ranks = 1; stats.devices = 1;
-	if (!StageOutputs(R, out, 3, hostMem)) return false;
-	const void* dev[7];
-	if (hostMem) {
+	if (!StageOutputs(R, P.out, RL_PLANE_OUTS, P.hostMem)) return false;
+	hipEvent_t behind = nullptr;
+	if (!prepare(R, behind)) return false;
+	PlaneLaunch L{ R, {}, {}, st };
+	for (int k = 0; k < RL_PLANE_OUTS; ++k) L.out[k] = P.out[k].dev;
+	for (int k = 0; k < RL_PLANE_INS; ++k) L.in[k] = P.in[k].bytes ? P.in[k].user : nullptr;
+	if (P.hostMem) {
 		size_t total = 0;
-		for (int k = 0; k < 7; ++k) total += inBytes[k];
+		for (const CallIn& i : P.in) {
+			if (i.bytes && (total & i.align) != 0) { Log("%s: an input plane would be staged at offset %zu, not %u-byte aligned", P.api, total, (unsigned)i.align + 1u); return false; }
+			total += i.bytes;
+		}
 		if (!R.qRays.Grow(total)) return false;
 		size_t at = 0;
-		for (int k = 0; k < 7; ++k) {
-			dev[k] = inBytes[k] ? (const char*)R.qRays.ptr + at : nullptr;
-			if (inBytes[k]) HIP_OK(hipMemcpyAsync((void*)dev[k], in[k], inBytes[k], hipMemcpyHostToDevice, st));
-			at += inBytes[k];
+		for (int k = 0; k < RL_PLANE_INS; ++k) {
+			if (!P.in[k].bytes) continue;
+			L.in[k] = (const char*)R.qRays.ptr + at;
+			HIP_OK(hipMemcpyAsync((void*)L.in[k], P.in[k].user, P.in[k].bytes, hipMemcpyHostToDevice, st));
+			at += P.in[k].bytes;
 		}
-	} else {
-		for (int k = 0; k < 7; ++k) dev[k] = inBytes[k] ? in[k] : nullptr;
 	}
-	DTemporal T; memset(&T, 0, sizeof(T));
-	T.width = W; T.height = H; T.cellsX = (W + 7u) / 8u; T.numCells = T.cellsX * ((H + 7u) / 8u);
-	T.depthTolerance = params.depthTolerance; T.maxLength = params.maxLength;
-	T.colour = (const float4*)dev[0]; T.hit = (const float4*)dev[1]; T.motion = (const float4*)dev[2];
-	T.histColour = (const float4*)dev[3]; T.histHit = (const float4*)dev[4]; T.histLength = (const float*)dev[6];
-	T.outColour = (float4*)out[0].dev; T.outLength = (float*)out[1].dev;
-	// a wave per cell at a time: workgroups enough for the cells, at most the device filled once at the kernel's occupancy
-	const void* kernel = outMoments ? (const void*)k_temporal_moments : (const void*)k_temporal;
-	const int perCU = OccupancyOf(R, kernel);
-	if (perCU < 0) return false;
-	const uint64_t cellBlocks = ((uint64_t)T.numCells + RL_BLOCK / 64u - 1u) / (RL_BLOCK / 64u);
-	const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)R.numCUs * (uint64_t)std::max(1, perCU), cellBlocks));
+	if (behind) HIP_OK(hipStreamWaitEvent(st, behind, 0));
 	if (sync && !BeginSync(R, st)) return false;
-	if (outMoments) hipLaunchKernelGGL(k_temporal_moments, dim3(blocks), dim3(RL_BLOCK), 0, st, T, (const float2*)dev[5], (float2*)out[2].dev);
-	else hipLaunchKernelGGL(k_temporal, dim3(blocks), dim3(RL_BLOCK), 0, st, T);
-	HIP_OK(hipGetLastError());
+	if (!launch(L)) return false;
 	if (!sync) return true;
-	const bool ok = FinishSync(R, st, { CopyBack(out[0], hostMem), CopyBack(out[1], hostMem), CopyBack(out[2], hostMem) }, t0, stats);
-	if (ok) stats.pixels = pixels;
-	return ok;
+	std::vector<CopyBack> back;
+	for (const QueryOut& o : P.out) back.emplace_back(o, P.hostMem);
+	if (!FinishSync(R, st, back, P.t0, stats)) return false;
+	stats.pixels = P.Pixels();
+	if (P.launches > 1) stats.traceLaunches = P.launches;
+	return true;
 }
 
-// A variance-guided filter call (RaylibAMD_FilterVariance, statements S3 to S7): planes in, planes out, as the accumulation; 2 + K launches on the call's
-// stream with the library's scratch between them -- the guides (32 bytes per pixel) and the two value planes of the iterations' ping-pong (16 each), kept and
-// grown.  Calls on different streams share that scratch: every call waits on its own stream for the event behind the last call's last launch (vfEv), as the
-// path calls do with radEv.  A host call stages its inputs in qRays -- colour, hit (multiples of 16 bytes), moments (of 8), surface, length (of 4) -- and its
-// outputs through qOut and qPrim.
+// A temporal accumulation (RaylibAMD_TemporalAccumulate, statements T7 and T8; with C.moments RaylibAMD_TemporalAccumulateMoments, statements S1 and S2:
+// k_temporal_moments with the history's moments and outMoments beside the rest).  A host call's outputs go through qOut, qPrim and qContact.
+static_assert(sizeof(RaylibAMDHitT) == sizeof(float4), "hit records");
+bool DeviceTemporalAccumulate(const TemporalCall& C, bool hostMem, void* stream, RaylibAMDStats& stats)
+{
+	PlaneCall P(C.moments ? "RaylibAMD_TemporalAccumulateMoments" : "RaylibAMD_TemporalAccumulate",
+	            C.moments ? "RaylibAMD_TemporalAccumulateMomentsDevice" : "RaylibAMD_TemporalAccumulateDevice", C.width, C.height, hostMem, stream);
+	const size_t plane = P.Pixels() * sizeof(float4), lengths = P.Pixels() * sizeof(float), pairs = P.Pixels() * sizeof(float2);
+	const size_t hist = C.hasHistory ? 1 : 0;   // (without a history none of its planes is read)
+	P.in[0] = { C.colour, plane }; P.in[1] = { C.hit, plane }; P.in[2] = { C.motion, plane };
+	P.in[3] = { C.history.colour, hist * plane }; P.in[4] = { C.history.hit, hist * plane };
+	P.in[5] = { C.history.moments, C.moments ? hist * pairs : 0, 7u }; P.in[6] = { C.history.length, hist * lengths, 3u };
+	P.out[0] = { C.outColour, plane, 15u, &RankCtx::qOut }; P.out[1] = { C.outLength, lengths, 3u, &RankCtx::qPrim };
+	P.out[2] = { C.outMoments, C.moments ? pairs : 0, 7u, &RankCtx::qContact };
+	DTemporal T; memset(&T, 0, sizeof(T));
+	SetFrameShape(T, C.width, C.height);
+	T.depthTolerance = C.params->depthTolerance; T.maxLength = C.params->maxLength;
+	uint32_t blocks = 0;
+	return RunPlanes(P, stats, [&](RankCtx& R, hipEvent_t&) -> bool {
+		// a wave per cell at a time: workgroups enough for the cells, at most the device filled once at the kernel's occupancy
+		const int perCU = OccupancyOf(R, C.moments ? (const void*)k_temporal_moments : (const void*)k_temporal);
+		if (perCU < 0) return false;
+		const uint64_t cellBlocks = ((uint64_t)T.numCells + RL_BLOCK / 64u - 1u) / (RL_BLOCK / 64u);
+		blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)R.numCUs * (uint64_t)std::max(1, perCU), cellBlocks));
+		return true;
+	}, [&](const PlaneLaunch& L) -> bool {
+		T.colour = (const float4*)L.in[0]; T.hit = (const float4*)L.in[1]; T.motion = (const float4*)L.in[2];
+		T.histColour = (const float4*)L.in[3]; T.histHit = (const float4*)L.in[4]; T.histLength = (const float*)L.in[6];
+		T.outColour = (float4*)L.out[0]; T.outLength = (float*)L.out[1];
+		if (C.moments) hipLaunchKernelGGL(k_temporal_moments, dim3(blocks), dim3(RL_BLOCK), 0, L.st, T, (const float2*)L.in[5], (float2*)L.out[2]);
+		else hipLaunchKernelGGL(k_temporal, dim3(blocks), dim3(RL_BLOCK), 0, L.st, T);
+		HIP_OK(hipGetLastError());
+		return true;
+	});
+}
+
+// A variance-guided filter call (RaylibAMD_FilterVariance, statements S3 to S7): 2 + K launches on the call's stream with the library's scratch between them
+// -- the guides (32 bytes per pixel) and the two value planes of the iterations' ping-pong (16 each), kept and grown.  Calls on different streams share that
+// scratch: every call waits on its own stream for the event behind the last call's last launch (vfEv), as the path calls do with radEv.  A host call's
+// outputs go through qOut and qPrim.
 static_assert(sizeof(DHitOut) == 11 * sizeof(float), "surface records are 11 words");
 bool DeviceFilterVariance(uint32_t W, uint32_t H, const RaylibAMDVarianceFilterParams& params, const RaylibAMDVarianceFilterPlanes& planes, float* outColour, float* outVariance,
                           bool hostMem, void* stream, RaylibAMDStats& stats)
 {
-	static const char* api = "RaylibAMD_FilterVariance";
-	const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-	const std::lock_guard<std::mutex> lock{ Rt().lock };
-	if (!EnsureRuntime()) return false;
-	RankCtx& R = Rank0();
-	HIP_OK(hipSetDevice(R.device));
-	const size_t pixels = (size_t)W * H;
-	const void* in[5] = { planes.colour, planes.hit, planes.moments, planes.surface, planes.length };
-	const size_t inBytes[5] = { pixels * sizeof(float4), pixels * sizeof(float4), pixels * sizeof(float2), pixels * sizeof(DHitOut), pixels * sizeof(float) };
-	const uintptr_t inAlign[5] = { 15u, 15u, 7u, 3u, 3u };
-	QueryOut out[2] = { { outColour, pixels * sizeof(float4), 15u, &RankCtx::qOut }, { outVariance, outVariance ? pixels * sizeof(float) : 0, 3u, &RankCtx::qPrim } };
-	if (!hostMem) {
-		bool onDevice = true;
-		for (int k = 0; k < 5; ++k) if (!OnDevice(in[k], R.device)) onDevice = false;
-		if (!onDevice) { Log("%sDevice: a pointer is not device memory of device %d", api, R.device); return false; }
-		for (int k = 0; k < 5; ++k)
-			if (((uintptr_t)in[k] & inAlign[k]) != 0) { Log("%sDevice: an input plane is not %u-byte aligned", api, (unsigned)inAlign[k] + 1u); return false; }
-		if (!DevicePointersOk("RaylibAMD_FilterVarianceDevice", nullptr, R.device, nullptr, out, 2)) return false;
-	}
-	const hipStream_t st = stream ? (hipStream_t)stream : R.stream;
-	const bool sync = !stream;
-	if (sync && !EnsureSyncStats(R)) return false;
-	memset(&stats, 0, sizeof(stats));
-	stats.ranks = 1; stats.devices = 1;
-	if (!StageOutputs(R, out, 2, hostMem)) return false;
-	if (!R.vfGuides.Grow(pixels * sizeof(VfGuide)) || !R.vfValues[0].Grow(pixels * sizeof(VfValue)) || !R.vfValues[1].Grow(pixels * sizeof(VfValue))) return false;
-	if (!R.vfEv) HIP_OK(hipEventCreateWithFlags(&R.vfEv, hipEventDisableTiming));
-	const void* dev[5];
-	if (hostMem) {
-		size_t total = 0;
-		for (int k = 0; k < 5; ++k) total += inBytes[k];
-		if (!R.qRays.Grow(total)) return false;
-		size_t at = 0;
-		for (int k = 0; k < 5; ++k) {
-			dev[k] = (const char*)R.qRays.ptr + at;
-			HIP_OK(hipMemcpyAsync((void*)dev[k], in[k], inBytes[k], hipMemcpyHostToDevice, st));
-			at += inBytes[k];
-		}
-	} else {
-		for (int k = 0; k < 5; ++k) dev[k] = in[k];
-	}
-	if (R.vfEvUsed) HIP_OK(hipStreamWaitEvent(st, R.vfEv, 0));
-	const VfConst c = MakeVfConst(params.sigmaLuminance, params.sigmaNormal, params.sigmaPlane, params.historyLength);
-	const uint32_t n = (uint32_t)pixels;   // (1 .. 2^31 - 1: the ABI checked)
-	const dim3 linear((n + RL_BLOCK - 1u) / RL_BLOCK), tiles(((W + 15u) / 16u) * ((H + 15u) / 16u));   // (at most 2^23 + 1 and 2^27 workgroups)
-	if (sync && !BeginSync(R, st)) return false;
-	hipLaunchKernelGGL(k_vf_pack, linear, dim3(RL_BLOCK), 0, st, (const float4*)dev[0], (const float4*)dev[1], (const float*)dev[3], n, R.vfGuides.ptr, R.vfValues[0].ptr);
-	HIP_OK(hipGetLastError());
-	hipLaunchKernelGGL(k_vf_variance, tiles, dim3(RL_BLOCK), 0, st, (const VfGuide*)R.vfGuides.ptr, (const float*)dev[2], (const float*)dev[4], W, H, c, R.vfValues[0].ptr);
-	HIP_OK(hipGetLastError());
-	int cur = 0;
-	for (int i = 0; i < params.iterations; ++i, cur ^= 1) {
-		if (i + 1 < params.iterations)
-			hipLaunchKernelGGL(k_vf_iter<false>, tiles, dim3(RL_BLOCK), 0, st, (const VfValue*)R.vfValues[cur].ptr, (const VfGuide*)R.vfGuides.ptr, W, H, (int32_t)(1 << i), c,
-			                   R.vfValues[cur ^ 1].ptr, (float4*)nullptr, (float*)nullptr);
-		else
-			hipLaunchKernelGGL(k_vf_iter<true>, tiles, dim3(RL_BLOCK), 0, st, (const VfValue*)R.vfValues[cur].ptr, (const VfGuide*)R.vfGuides.ptr, W, H, (int32_t)(1 << i), c,
-			                   (VfValue*)nullptr, (float4*)out[0].dev, (float*)out[1].dev);
+	PlaneCall P("RaylibAMD_FilterVariance", "RaylibAMD_FilterVarianceDevice", W, H, hostMem, stream);
+	const size_t pixels = P.Pixels();
+	P.in[0] = { planes.colour, pixels * sizeof(float4) }; P.in[1] = { planes.hit, pixels * sizeof(float4) };
+	P.in[2] = { planes.moments, pixels * sizeof(float2), 7u }; P.in[3] = { planes.surface, pixels * sizeof(DHitOut), 3u }; P.in[4] = { planes.length, pixels * sizeof(float), 3u };
+	P.out[0] = { outColour, pixels * sizeof(float4), 15u, &RankCtx::qOut }; P.out[1] = { outVariance, outVariance ? pixels * sizeof(float) : 0, 3u, &RankCtx::qPrim };
+	P.launches = 2u + (uint32_t)params.iterations;
+	return RunPlanes(P, stats, [&](RankCtx& R, hipEvent_t& behind) -> bool {
+		if (!R.vfGuides.Grow(pixels * sizeof(VfGuide)) || !R.vfValues[0].Grow(pixels * sizeof(VfValue)) || !R.vfValues[1].Grow(pixels * sizeof(VfValue))) return false;
+		if (!R.vfEv) HIP_OK(hipEventCreateWithFlags(&R.vfEv, hipEventDisableTiming));
+		if (R.vfEvUsed) behind = R.vfEv;
+		return true;
+	}, [&](const PlaneLaunch& L) -> bool {
+		RankCtx& R = L.R;
+		const hipStream_t st = L.st;
+		const VfConst c = MakeVfConst(params.sigmaLuminance, params.sigmaNormal, params.sigmaPlane, params.historyLength);
+		const uint32_t n = (uint32_t)pixels;
+		const dim3 linear((n + RL_BLOCK - 1u) / RL_BLOCK), tiles(((W + 15u) / 16u) * ((H + 15u) / 16u));   // (at most 2^23 + 1 and 2^27 workgroups)
+		hipLaunchKernelGGL(k_vf_pack, linear, dim3(RL_BLOCK), 0, st, (const float4*)L.in[0], (const float4*)L.in[1], (const float*)L.in[3], n, R.vfGuides.ptr, R.vfValues[0].ptr);
 		HIP_OK(hipGetLastError());
-	}
-	HIP_OK(hipEventRecord(R.vfEv, st));
-	R.vfEvUsed = true;
-	if (!sync) return true;
-	const bool ok = FinishSync(R, st, { CopyBack(out[0], hostMem), CopyBack(out[1], hostMem) }, t0, stats);
-	if (ok) { stats.pixels = pixels; stats.traceLaunches = 2u + (uint32_t)params.iterations; }
-	return ok;
+		hipLaunchKernelGGL(k_vf_variance, tiles, dim3(RL_BLOCK), 0, st, (const VfGuide*)R.vfGuides.ptr, (const float*)L.in[2], (const float*)L.in[4], W, H, c, R.vfValues[0].ptr);
+		HIP_OK(hipGetLastError());
+		int cur = 0;
+		for (int i = 0; i < params.iterations; ++i, cur ^= 1) {
+			if (i + 1 < params.iterations)
+				hipLaunchKernelGGL(k_vf_iter<false>, tiles, dim3(RL_BLOCK), 0, st, (const VfValue*)R.vfValues[cur].ptr, (const VfGuide*)R.vfGuides.ptr, W, H, (int32_t)(1 << i), c,
+				                   R.vfValues[cur ^ 1].ptr, (float4*)nullptr, (float*)nullptr);
+			else
+				hipLaunchKernelGGL(k_vf_iter<true>, tiles, dim3(RL_BLOCK), 0, st, (const VfValue*)R.vfValues[cur].ptr, (const VfGuide*)R.vfGuides.ptr, W, H, (int32_t)(1 << i), c,
+				                   (VfValue*)nullptr, (float4*)L.out[0], (float*)L.out[1]);
+			HIP_OK(hipGetLastError());
+		}
+		HIP_OK(hipEventRecord(R.vfEv, st));
+		R.vfEvUsed = true;
+		return true;
+	});
 }
 
 // An ordered multi-hit call: rows of maxHits records and, when asked for, a count per ray (staged through qPrim); the launch carries the lanes' lists as
@@ -723,7 +743,7 @@ bool DeviceOverlapBoxes(Scene& sc, int32_t kind, const void* queries, int32_t n,
 		if (!EnsureRuntime()) return false;
 		RankCtx& R = Rank0();
 		HIP_OK(hipSetDevice(R.device));
-		if (!hostMem && !DevicePointersOk(D.apiDevice, nullptr, R.device, nullptr, D.out, 1)) return false;
+		if (!hostMem && !DevicePointersOk(D.apiDevice, nullptr, R.device, nullptr, 0, D.out, 1)) return false;
 	}
 	if (!RunQuery(sc, D, stats, [&](const QueryLaunch& L) {
 		if (mark) (void)hipMemsetAsync(L.out[0], 0, maskBytes, L.st);   // (a failure is the launch's error: LaunchOnRing asks hipGetLastError behind it)
@@ -769,7 +789,7 @@ bool DeviceBakeDistanceField(Scene& sc, const RaylibAMDDistanceFieldParams& prm,
 		G.rowEnd[a] = (uint32_t)rows;   // (three axes of at most 2^31 - 1 voxels: at most 2^32 - 1 rows; the launches below are cut at 2^31 - 1)
 	}
 	QueryOut outs[2] = { { outDist, (size_t)voxels * sizeof(float), 3u, &RankCtx::qOut }, { outPrim, outPrim ? (size_t)voxels * sizeof(int32_t) : 0, 3u, &RankCtx::qPrim } };
-	if (!hostMem && !DevicePointersOk("RaylibAMD_BakeDistanceFieldDevice", nullptr, R.device, nullptr, outs, 2)) return false;
+	if (!hostMem && !DevicePointersOk("RaylibAMD_BakeDistanceFieldDevice", nullptr, R.device, nullptr, 0, outs, 2)) return false;
 	QueryCall U;
 	if (!BeginQueryCall(sc, R, plan.nearest, true, stream, U, stats)) return false;
 	if (G.axes && !EnsureWideTree(U.Cp, sc, plan.rows.tree)) return false;
@@ -832,7 +852,8 @@ static bool BeginPathCall(const char* api, const char* apiDevice, const char* wh
 	U.plan = PlanRadiance(sc, knobs);
 	if (!U.plan.ok) { Log("%s: BVH depth %u exceeds the traversal stack (64)", api, sc.bvh.depth); return false; }
 	const QueryOut result = { const_cast<void*>(out), (size_t)(n > 0), outAlign };   // (written whenever the call has input)
-	if (!hostMem && n > 0 && !DevicePointersOk(apiDevice, what, R.device, in, &result, 1)) return false;
+	const CallIn records = { in, (size_t)n * sizeof(RaylibAMDRay) };
+	if (!hostMem && n > 0 && !DevicePointersOk(apiDevice, what, R.device, &records, 1, &result, 1)) return false;
 	if (!UploadScene(sc) || !SyncSky(sc)) return false;
 	U.Cp = sc.device->copy[(size_t)R.devSlot];
 	if (!EnsureWideTree(U.Cp, sc, U.plan.tree)) return false;

@@ -329,44 +329,6 @@ def motion_host(lib, scene, camera, w, h, rays, hit, prev_camera=None, first=0, 
     return out
 
 
-def temporal_accumulate(lib, colour, hit, motion, history=None, depth_tolerance=0.02, max_length=32.0, host=False):
-    """RaylibAMD_TemporalAccumulate on NumPy arrays (host=True: RaylibAMD_TemporalAccumulateHost, the oracle, no device): colour (h, w, 4) float32, hit (h, w)
-    HITT_DTYPE, motion (h, w) MOTION_DTYPE, history None or the (colour, hit, length) of the previous frame.  Returns (outColour (h, w, 4), outLength (h, w)).
-    Raises RuntimeError when the library refuses the call."""
-    colour = np.ascontiguousarray(colour, np.float32)
-    h, w = colour.shape[:2]
-    hit = np.ascontiguousarray(hit, HITT_DTYPE)
-    motion = np.ascontiguousarray(motion, MOTION_DTYPE)
-    assert colour.shape == (h, w, 4) and hit.size == w * h and motion.size == w * h
-    keep = None
-    hist = None
-    if history is not None:
-        keep = (np.ascontiguousarray(history[0], np.float32), np.ascontiguousarray(history[1], HITT_DTYPE), np.ascontiguousarray(history[2], np.float32))
-        assert keep[0].size == w * h * 4 and keep[1].size == w * h and keep[2].size == w * h
-        hist = C.byref(TemporalFrame(*[a.ctypes.data for a in keep]))
-    out_c, out_l = np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.float32)
-    entry = "RaylibAMD_TemporalAccumulateHost" if host else "RaylibAMD_TemporalAccumulate"
-    prm = TemporalParams(float(depth_tolerance), float(max_length))
-    if getattr(lib, entry)(int(w), int(h), C.byref(prm), colour.ctypes.data, hit.ctypes.data, motion.ctypes.data, hist, out_c.ctypes.data, out_l.ctypes.data) != 1:
-        raise RuntimeError(entry + " refused the call")
-    return out_c, out_l
-
-
-def temporal_accumulate_device(lib, colour, hit, motion, history=None, depth_tolerance=0.02, max_length=32.0, out=None):
-    """RaylibAMD_TemporalAccumulateDevice on torch.cuda.current_stream(), as gbuffer_device: colour (h, w, 4) float32, hit and motion (h, w, 4) int32 as
-    motion_device returns them, history None or (colour, hit, length) tensors of the previous frame; all contiguous, on the device.  out: (outColour, outLength)
-    tensors to write into.  Returns (outColour (h, w, 4) float32, outLength (h, w) float32).  Raises RuntimeError when the library refuses the call."""
-    import torch
-    h, w = colour.shape[:2]
-    out_c, out_l = out if out is not None else (torch.empty((h, w, 4), dtype=torch.float32, device="cuda"), torch.empty((h, w), dtype=torch.float32, device="cuda"))
-    hist = None if history is None else C.byref(TemporalFrame(*[t.data_ptr() for t in history]))
-    prm = TemporalParams(float(depth_tolerance), float(max_length))
-    if lib.RaylibAMD_TemporalAccumulateDevice(int(w), int(h), C.byref(prm), colour.data_ptr(), hit.data_ptr(), motion.data_ptr(), hist, out_c.data_ptr(), out_l.data_ptr(),
-                                              _ordered(torch.cuda.current_stream())) != 1:
-        raise RuntimeError("RaylibAMD_TemporalAccumulateDevice refused the call")
-    return out_c, out_l
-
-
 class TemporalMomentsFrame(C.Structure):
     """include/raylib_amd.h RaylibAMDTemporalMomentsFrame: a TemporalFrame and the previous call's moments plane."""
     _fields_ = [("colour", C.c_void_p), ("hit", C.c_void_p), ("length", C.c_void_p), ("moments", C.c_void_p)]
@@ -383,47 +345,83 @@ class VarianceFilterPlanes(C.Structure):
 
 
 VARIANCE_DEFAULTS = dict(iterations=5, sigma_luminance=4.0, sigma_normal=0.35, sigma_plane=0.1, history_length=4.0)
+_TEMPORAL_PLANES = ((np.float32, 4), (HITT_DTYPE, 1), (MOTION_DTYPE, 1))            # colour, hit, motion
+_HISTORY_PLANES = ((np.float32, 4), (HITT_DTYPE, 1), (np.float32, 1), (np.float32, 2))   # colour, hit, length, moments
+
+
+def _planes(lib, entry, host, planes, kinds, outs, args):
+    """One plane call on NumPy arrays, behind the public wrappers.  planes: the input arrays, kinds: each one's (dtype, elements per pixel); the first is the
+    frame's colour, (h, w, 4).  entry: the host-memory entry's name, entry + "Host" its oracle; both take (w, h, *args(addresses of the planes), *outputs).
+    outs: the outputs' shapes behind (h, w), None for one not asked for.  Returns the tuple of float32 outputs; raises RuntimeError on a refusal."""
+    keep = [np.ascontiguousarray(a, d) for a, (d, _) in zip(planes, kinds)]
+    h, w = keep[0].shape[:2]
+    assert keep[0].shape == (h, w, 4) and all(a.size == w * h * k for a, (_, k) in zip(keep, kinds))
+    res = tuple(None if s is None else np.zeros((h, w) + s, np.float32) for s in outs)
+    name = entry + "Host" if host else entry
+    if getattr(lib, name)(int(w), int(h), *args([a.ctypes.data for a in keep]), *[None if o is None else o.ctypes.data for o in res]) != 1:
+        raise RuntimeError(name + " refused the call")
+    return res
+
+
+def _planes_device(lib, entry, colour, args, outs, out):
+    """The same through the device entry (`entry`) on tensors, on torch.cuda.current_stream(): args are the entry's arguments between (w, h) and the outputs;
+    out: the caller's output tensors, or None for fresh ones of the shapes `outs`."""
+    import torch
+    h, w = colour.shape[:2]
+    res = tuple(out) if out is not None else tuple(None if s is None else torch.empty((h, w) + s, dtype=torch.float32, device="cuda") for s in outs)
+    if getattr(lib, entry)(int(w), int(h), *args, *[None if o is None else o.data_ptr() for o in res], _ordered(torch.cuda.current_stream())) != 1:
+        raise RuntimeError(entry + " refused the call")
+    return res
+
+
+def _accumulation(moments):
+    """Entry, history structure (its fields are the planes a history has) and output shapes of the accumulation with or without the moments."""
+    if moments:
+        return "RaylibAMD_TemporalAccumulateMoments", TemporalMomentsFrame, ((4,), (), (2,))
+    return "RaylibAMD_TemporalAccumulate", TemporalFrame, ((4,), ())
+
+
+def _accumulate(lib, moments, host, colour, hit, motion, history, depth_tolerance, max_length):
+    entry, frame, outs = _accumulation(moments)
+    n = 0 if history is None else len(frame._fields_)
+    prm = TemporalParams(float(depth_tolerance), float(max_length))
+    return _planes(lib, entry, host, (colour, hit, motion) + (() if history is None else tuple(history)[:n]), _TEMPORAL_PLANES + _HISTORY_PLANES[:n], outs,
+                   lambda p: (C.byref(prm), p[0], p[1], p[2], C.byref(frame(*p[3:])) if n else None))
+
+
+def _accumulate_device(lib, moments, colour, hit, motion, history, depth_tolerance, max_length, out):
+    entry, frame, outs = _accumulation(moments)
+    hist = None if history is None else C.byref(frame(*[t.data_ptr() for t in history]))
+    args = (C.byref(TemporalParams(float(depth_tolerance), float(max_length))), colour.data_ptr(), hit.data_ptr(), motion.data_ptr(), hist)
+    return _planes_device(lib, entry + "Device", colour, args, outs, out)
+
+
+def temporal_accumulate(lib, colour, hit, motion, history=None, depth_tolerance=0.02, max_length=32.0, host=False):
+    """RaylibAMD_TemporalAccumulate on NumPy arrays (host=True: RaylibAMD_TemporalAccumulateHost, the oracle, no device): colour (h, w, 4) float32, hit (h, w)
+    HITT_DTYPE, motion (h, w) MOTION_DTYPE, history None or the (colour, hit, length) of the previous frame.  Returns (outColour (h, w, 4), outLength (h, w)).
+    Raises RuntimeError when the library refuses the call."""
+    return _accumulate(lib, False, host, colour, hit, motion, history, depth_tolerance, max_length)
+
+
+def temporal_accumulate_device(lib, colour, hit, motion, history=None, depth_tolerance=0.02, max_length=32.0, out=None):
+    """RaylibAMD_TemporalAccumulateDevice on torch.cuda.current_stream(), as gbuffer_device: colour (h, w, 4) float32, hit and motion (h, w, 4) int32 as
+    motion_device returns them, history None or (colour, hit, length) tensors of the previous frame; all contiguous, on the device.  out: (outColour, outLength)
+    tensors to write into.  Returns (outColour (h, w, 4) float32, outLength (h, w) float32).  Raises RuntimeError when the library refuses the call."""
+    return _accumulate_device(lib, False, colour, hit, motion, history, depth_tolerance, max_length, out)
 
 
 def temporal_accumulate_moments(lib, colour, hit, motion, history=None, depth_tolerance=0.02, max_length=32.0, host=False):
     """RaylibAMD_TemporalAccumulateMoments on NumPy arrays (host=True: RaylibAMD_TemporalAccumulateMomentsHost, the oracle, no device): temporal_accumulate's
     arguments with a history of (colour, hit, length, moments), moments (h, w, 2) float32.  Returns (outColour (h, w, 4), outLength (h, w), outMoments (h, w, 2)).
     Raises RuntimeError when the library refuses the call."""
-    colour = np.ascontiguousarray(colour, np.float32)
-    h, w = colour.shape[:2]
-    hit = np.ascontiguousarray(hit, HITT_DTYPE)
-    motion = np.ascontiguousarray(motion, MOTION_DTYPE)
-    assert colour.shape == (h, w, 4) and hit.size == w * h and motion.size == w * h
-    keep = None
-    hist = None
-    if history is not None:
-        keep = (np.ascontiguousarray(history[0], np.float32), np.ascontiguousarray(history[1], HITT_DTYPE), np.ascontiguousarray(history[2], np.float32),
-                np.ascontiguousarray(history[3], np.float32))
-        assert keep[0].size == w * h * 4 and keep[1].size == w * h and keep[2].size == w * h and keep[3].size == w * h * 2
-        hist = C.byref(TemporalMomentsFrame(*[a.ctypes.data for a in keep]))
-    out_c, out_l, out_m = np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.float32), np.zeros((h, w, 2), np.float32)
-    entry = "RaylibAMD_TemporalAccumulateMomentsHost" if host else "RaylibAMD_TemporalAccumulateMoments"
-    prm = TemporalParams(float(depth_tolerance), float(max_length))
-    if getattr(lib, entry)(int(w), int(h), C.byref(prm), colour.ctypes.data, hit.ctypes.data, motion.ctypes.data, hist, out_c.ctypes.data, out_l.ctypes.data,
-                           out_m.ctypes.data) != 1:
-        raise RuntimeError(entry + " refused the call")
-    return out_c, out_l, out_m
+    return _accumulate(lib, True, host, colour, hit, motion, history, depth_tolerance, max_length)
 
 
 def temporal_accumulate_moments_device(lib, colour, hit, motion, history=None, depth_tolerance=0.02, max_length=32.0, out=None):
     """RaylibAMD_TemporalAccumulateMomentsDevice on torch.cuda.current_stream(), as temporal_accumulate_device: history None or (colour, hit, length, moments)
     tensors of the previous frame; out: (outColour, outLength, outMoments) tensors to write into.  Returns (outColour (h, w, 4), outLength (h, w),
     outMoments (h, w, 2)), float32 on the device.  Raises RuntimeError when the library refuses the call."""
-    import torch
-    h, w = colour.shape[:2]
-    out_c, out_l, out_m = out if out is not None else (torch.empty((h, w, 4), dtype=torch.float32, device="cuda"), torch.empty((h, w), dtype=torch.float32, device="cuda"),
-                                                       torch.empty((h, w, 2), dtype=torch.float32, device="cuda"))
-    hist = None if history is None else C.byref(TemporalMomentsFrame(*[t.data_ptr() for t in history]))
-    prm = TemporalParams(float(depth_tolerance), float(max_length))
-    if lib.RaylibAMD_TemporalAccumulateMomentsDevice(int(w), int(h), C.byref(prm), colour.data_ptr(), hit.data_ptr(), motion.data_ptr(), hist, out_c.data_ptr(), out_l.data_ptr(),
-                                                     out_m.data_ptr(), _ordered(torch.cuda.current_stream())) != 1:
-        raise RuntimeError("RaylibAMD_TemporalAccumulateMomentsDevice refused the call")
-    return out_c, out_l, out_m
+    return _accumulate_device(lib, True, colour, hit, motion, history, depth_tolerance, max_length, out)
 
 
 def _variance_params(params):
@@ -441,36 +439,17 @@ def filter_variance(lib, colour, moments, length, hit, surface, params=None, var
     (h, w) float32 as the accumulation leaves them, hit (h, w) HITT_DTYPE and surface (h, w) SURFACE_DTYPE as the G-buffer does.  params: None for the library's
     defaults, or a dict with any of VARIANCE_DEFAULTS' keys.  Returns (outColour (h, w, 4), outVariance (h, w) or None when variance is False).  Raises
     RuntimeError when the library refuses the call."""
-    colour = np.ascontiguousarray(colour, np.float32)
-    h, w = colour.shape[:2]
-    keep = (colour, np.ascontiguousarray(moments, np.float32), np.ascontiguousarray(length, np.float32), np.ascontiguousarray(hit, HITT_DTYPE),
-            np.ascontiguousarray(surface, SURFACE_DTYPE))
-    assert colour.shape == (h, w, 4) and keep[1].size == w * h * 2 and keep[2].size == w * h and keep[3].size == w * h and keep[4].size == w * h
-    planes = VarianceFilterPlanes(*[a.ctypes.data for a in keep])
-    out_c = np.zeros((h, w, 4), np.float32)
-    out_v = np.zeros((h, w), np.float32) if variance else None
-    entry = "RaylibAMD_FilterVarianceHost" if host else "RaylibAMD_FilterVariance"
-    if getattr(lib, entry)(int(w), int(h), _variance_params(params), C.byref(planes), out_c.ctypes.data, None if out_v is None else out_v.ctypes.data) != 1:
-        raise RuntimeError(entry + " refused the call")
-    return out_c, out_v
+    kinds = ((np.float32, 4), (np.float32, 2), (np.float32, 1), (HITT_DTYPE, 1), (SURFACE_DTYPE, 1))
+    return _planes(lib, "RaylibAMD_FilterVariance", host, (colour, moments, length, hit, surface), kinds, ((4,), () if variance else None),
+                   lambda p: (_variance_params(params), C.byref(VarianceFilterPlanes(*p))))
 
 
 def filter_variance_device(lib, colour, moments, length, hit, surface, params=None, variance=True, out=None):
     """RaylibAMD_FilterVarianceDevice on torch.cuda.current_stream(), as temporal_accumulate_device: float32 tensors colour (h, w, 4), moments (h, w, 2), length
     (h, w), and hit (h, w, 4), surface (h, w, 11) int32 words as gbuffer_device returns them; all contiguous, on the device.  out: (outColour, outVariance or
-    None) tensors to write into.  Returns (outColour, outVariance or None)."""
-    import torch
-    h, w = colour.shape[:2]
-    if out is not None:
-        out_c, out_v = out
-    else:
-        out_c = torch.empty((h, w, 4), dtype=torch.float32, device="cuda")
-        out_v = torch.empty((h, w), dtype=torch.float32, device="cuda") if variance else None
+    None) tensors to write into.  Returns (outColour, outVariance or None).  Raises RuntimeError when the library refuses the call."""
     planes = VarianceFilterPlanes(colour.data_ptr(), moments.data_ptr(), length.data_ptr(), hit.data_ptr(), surface.data_ptr())
-    if lib.RaylibAMD_FilterVarianceDevice(int(w), int(h), _variance_params(params), C.byref(planes), out_c.data_ptr(), None if out_v is None else out_v.data_ptr(),
-                                          _ordered(torch.cuda.current_stream())) != 1:
-        raise RuntimeError("RaylibAMD_FilterVarianceDevice refused the call")
-    return out_c, out_v
+    return _planes_device(lib, "RaylibAMD_FilterVarianceDevice", colour, (_variance_params(params), C.byref(planes)), ((4,), () if variance else None), out)
 
 
 MAX_HITS = 16                                       # RAYLIB_AMD_MAX_HITS

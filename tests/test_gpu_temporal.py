@@ -71,9 +71,10 @@ def test_crafted_planes(gpu_lib):
     assert now.pixels == W * H and now.kernelMs > 0
 
 
-@pytest.mark.parametrize("size", [(1, 1), (8, 8), (64, 40)])
+@pytest.mark.parametrize("size", [(1, 1), (8, 8), (37, 21), (64, 40)])
 def test_sizes(gpu_lib, size):
-    """One pixel, one whole cell, several blocks' worth of cells: random planes with fractional motion everywhere."""
+    """One pixel, one whole cell, a frame that is no multiple of the cell with an odd pixel count, several blocks' worth of cells: random planes with fractional
+    motion everywhere."""
     w, h = size
     rng = np.random.RandomState(w)
     ys, xs = np.mgrid[0:h, 0:w]

@@ -3,6 +3,7 @@
 RaylibAMD_Denoise on the same frame; and what the filter does to a Cornell frame's error.
 
 usage: python tools/gpu_variance_filter.py [--width 1920] [--height 1080] [--runs 11] [--tess 91] [--lib PATH] [--log PATH]
+       python tools/gpu_variance_filter.py --overhead --lib PATH [--runs 11] [--log PATH]
 The scene is the bench's 298 116-triangle room (raylib_amd/scenes.py cornell, tess 91, a fifth of the triangles displaced) from the bench's interior camera.  Its
 planes: the G-buffer's hit and surface, two 1-spp frames accumulated with moments under identity motion (so every length is 2, below the default historyLength:
 every pixel takes the 7 x 7 spatial variance, the dearer branch of S5), and the denoiser's albedo and micro-normal images.
@@ -16,6 +17,7 @@ After a warm-up, --runs rounds in which these alternate:
 The filter's outputs are checked against RaylibAMD_FilterVarianceHost bit for bit on a 256 x 144 frame of the same scene before anything is timed (the host oracle
 at 1920 x 1080 takes minutes).  Then the quality figures of tests/test_gpu_variance.py (tests/variance_cases.quality) on the Cornell box.
 --log: everything printed, and the raw runs as JSON lines, with the library's build id.
+--overhead: the host path of a synchronous plane call, the tree's library against --lib's in one process (overhead()).
 """
 import argparse
 import ctypes as C
@@ -31,6 +33,45 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 os.environ.setdefault("RAYLIB_QUIET", "1")
 
 
+def overhead(args):
+    """--overhead: what a synchronous plane call costs beside its kernels -- wallMs - kernelMs of its stats, in microseconds: the staging of the input planes,
+    the copies back, the host's own work -- for the host entries of the accumulation with moments (with a history) and of the filter at K = 5, on frames of
+    1 x 1 and of width x height pixels (tests/variance_cases.no_bleed_planes: no scene is needed).  The tree's library and --lib's (another build, e.g. the parent
+    commit's) take turns call by call in this one process, --runs calls each after 3 warm-up calls.  Per build the median, the least and the greatest; the
+    tree's median is then placed against the other build's spread."""
+    import numpy as np
+    from raylib_amd import binding
+    import variance_cases as vc
+    builds = {"tree": binding.load(), "other": binding.load(args.lib)}
+    for lib in builds.values():
+        assert lib.Raylib_Initialize() == 1, "no HIP device"
+    lines = []
+
+    def say(s):
+        print(s); lines.append(s)
+    say("%-10s %-6s %11s %-17s %10s %10s %10s" % ("call", "build", "frame", "id", "median us", "least", "greatest"))
+    for w, h in ((1, 1), (args.width, args.height)):
+        colour, moments, length, hit, surface, _ = vc.no_bleed_planes(w, h)
+        motion = vc.identity_motion(hit)
+        calls = {"moments": lambda lib: binding.temporal_accumulate_moments(lib, colour, hit, motion, (colour, hit, length, moments)),
+                 "filter K=5": lambda lib: binding.filter_variance(lib, colour, moments, length, hit, surface, params=dict(iterations=5))}
+        for what, call in calls.items():
+            us = {name: [] for name in builds}
+            for k in range(args.runs + 3):
+                for name, lib in builds.items():
+                    call(lib)
+                    st = binding.Stats(); lib.RaylibAMD_GetLastStats(C.byref(st))
+                    if k >= 3:
+                        us[name].append((st.wallMs - st.kernelMs) * 1e3)
+            for name, lib in builds.items():
+                say("%-10s %-6s %11s %-17s %10.1f %10.1f %10.1f" % (what, name, "%d x %d" % (w, h), lib.RaylibAMD_BuildId().decode(), np.median(us[name]), min(us[name]), max(us[name])))
+            mid = np.median(us["tree"])
+            say("%-10s %d x %d: the tree's median is %s the other build's spread" % (what, w, h, "within" if min(us["other"]) <= mid <= max(us["other"]) else "below" if mid < min(us["other"]) else "ABOVE"))
+    if args.log:
+        with open(args.log, "w") as fh_:
+            fh_.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=1920)
@@ -39,7 +80,12 @@ def main():
     ap.add_argument("--tess", type=int, default=91)
     ap.add_argument("--lib")
     ap.add_argument("--log")
+    ap.add_argument("--overhead", action="store_true")
     args = ap.parse_args()
+    if args.overhead:
+        if not args.lib:
+            ap.error("--overhead compares the tree's library with --lib's")
+        return overhead(args)
     import numpy as np
     import torch
     from raylib_amd import binding, scenes

@@ -10,7 +10,7 @@ bool DeviceClosestHit(Scene&, const float*, int32_t, float, void*) { return fals
 bool DeviceTraceRays(Scene&, int32_t, const void*, int32_t, float, void*, int32_t*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceRenderGBuffer(Scene&, const RendererSettings&, const DCamera&, uint64_t, const RaylibAMDGBufferPlanes&, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceRenderMotion(Scene&, const RendererSettings&, const DCamera&, const DCamera&, uint64_t, int32_t, int32_t, const float*, const RaylibAMDMotionPlanes&, bool, void*, RaylibAMDStats&) { return false; }
-bool DeviceTemporalAccumulate(uint32_t, uint32_t, const RaylibAMDTemporalParams&, const float*, const RaylibAMDHitT*, const RaylibAMDMotion*, const RaylibAMDTemporalFrame*, float*, float*, bool, void*, RaylibAMDStats&, const float*, float*) { return false; }
+bool DeviceTemporalAccumulate(const TemporalCall&, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceFilterVariance(uint32_t, uint32_t, const RaylibAMDVarianceFilterParams&, const RaylibAMDVarianceFilterPlanes&, float*, float*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceTraceRaysAll(Scene&, const void*, int32_t, int32_t, void*, uint32_t*, bool, void*, RaylibAMDStats&) { return false; }
 bool DeviceNearestPoints(Scene&, int32_t, const void*, int32_t, void*, bool, void*, RaylibAMDStats&) { return false; }
